@@ -9,6 +9,7 @@ markers (125 GB of packed .bed resident in HBM); at --gpus G the individuals
 are sharded G ways ("strong" scaling: total work fixed).
 
     python bench.py --gpus 1 --steps 10 --warmup 2
+    python bench.py --gpus 1 --steps 10 --warmup 2 --dump-outputs DIR   (+ the last timed step's state as DIR/*.npy)
     python -m torch.distributed.run --nproc-per-node 8 ... bench.py --gpus 8 ...
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline`
@@ -144,6 +145,33 @@ def make_phenotype_on_device(dev, n_global, M, rank_rows, seed, h2=0.5, causal_f
     for j, b in zip(causal, beta):
         dev.update_marker(int(j), -float(b))  # eps += b * x_j
     return dev.get_residual()
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+DUMP_AXIS_CAP = 1 << 20  # longest marker / individual axis written whole once the outputs exceed DUMP_LIMIT_BYTES
+
+
+def dump_outputs(out_dir, scalars, per_marker, per_individual):
+    """--dump-outputs: write what the timed path computed in its last step as <out_dir>/<name>.npy (float64; integer
+    arrays become float64 too, exact).  Beyond DUMP_LIMIT_BYTES the marker and individual axes are each cut to a fixed,
+    seeded sample of DUMP_AXIS_CAP positions, written beside them as marker_index.npy / individual_index.npy."""
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in scalars.items()}
+    axes = (("marker", per_marker, 7), ("individual", per_individual, 11))
+    total = sum(a.nbytes for a in arrays.values()) + sum(np.asarray(v).size * 8 for _, group, _ in axes for v in group.values())
+    for axis, group, seed in axes:
+        n = len(next(iter(group.values()))) if group else 0
+        idx = None
+        if total > DUMP_LIMIT_BYTES and n > DUMP_AXIS_CAP:
+            idx = np.sort(np.random.default_rng(seed).choice(n, size=DUMP_AXIS_CAP, replace=False))
+            arrays[axis + "_index"] = idx.astype(np.float64)
+        for k, v in group.items():
+            v = np.asarray(v)
+            arrays[k] = (v if idx is None else v[idx]).astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(v))
+    print("outputs of the last timed step: %d arrays, %.1f MB in %s" % (len(arrays), sum(v.nbytes for v in arrays.values()) / 1e6, out_dir),
+          file=sys.stderr)
 
 
 BULK = None  # transport of the bulk reductions, agreed on by all ranks at the first handle: "rccl" or "gloo"
@@ -380,6 +408,11 @@ def main_bayesw(args):
         chain.iterate()
         stats.append(chain.sweep_stats())
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        st = chain.state()
+        beta, comp = chain.beta()
+        dump_outputs(args.dump_outputs, {"mu": st["mu"], "alpha": st["alpha"], "sigmaG": st["sigmaG"], "pi": st["pi"]},
+                     {"beta": beta, "components": comp, "order": chain.order()}, {"residual": dev.get_residual()})
     K = args.steps
     launches = sum(s["launches"] for s in stats)
     nnz = sum(s["nnz_updates"] for s in stats)
@@ -429,7 +462,11 @@ def main():
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE", help="library option (hgibbs_set_option), repeatable: option scans")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample", type=int, default=0, help="markers in the CPU baseline sample (0 = auto)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the chain state the last timed step left (beta, components, residual, ...) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.config in BW_CONFIGS:
         return main_bayesw(args)
 
@@ -561,6 +598,18 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t[0])
+
+    if args.dump_outputs:  # before the anatomy iteration below moves the chain on
+        st = chain.state()
+        beta, comp, acum = dev.get_beta()
+        eps = dev.get_residual()
+        if dist is not None:  # every rank holds its own rows of the residual
+            parts = [None] * world
+            dist.all_gather_object(parts, eps)
+            eps = np.concatenate(parts)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"sigmaE": st["sigmaE"], "mu": st["mu"], "sigmaG": st["sigmaG"], "estPi": st["estPi"]},
+                         {"beta": beta, "components": comp, "acum": acum, "order": chain.order()}, {"residual": eps})
 
     # one more (untimed) iteration on the build with stage timestamps: every rank runs it (the chain is collective)
     anatomy_all = None

@@ -9,6 +9,14 @@ Sources, in order of authority:
         SURVEY.md 8c lists; never executed)
       - dotp_lut.npz              : stdout of oracle/_ref/mk_lut (built from
         src/mk_lut.cpp), i.e. the content of src/dotp_lut.h
+      - reference_lut.npz         : the same tables as src/dotp_lut.h compiles
+        (oracle/_ref/libdotp_lut.so)
+      - reference_elf.npz         : what the structural pins read from src/hydra
+        with binutils: the .rodata span of the Ziggurat tables, the .comment
+        strings, call targets / mnemonics / scalar constants of three functions
+      - reference_arms.npz        : answers of the reference's arms()
+        (oracle/_ref/libarms.so) on tests/test_bayesw_oracle.py's cases
+      - reference_gh.npz          : the Gauss-Hermite literals of src/BayesW.cpp
   * the CPU oracle itself (regression pins; "parity unpinned" w.r.t. the
     reference for the Boost-dependent arithmetic):
       - rng_kat.npz     : first draws of every distribution wrapper, seed 1222
@@ -54,6 +62,94 @@ def from_reference():
         assert a.size == 1024 and b.size == 1024
         np.savez(os.path.join(GOLD, "dotp_lut.npz"), lut_a=a, lut_b=b)
         print("dotp_lut.npz from", mk)
+
+
+def reference_elf():
+    """The facts the structural pins of tests/test_oracle_rng.py need from the prebuilt ELF (read as data)."""
+    import shutil
+    elf = os.path.join(REF, "src", "hydra")
+    if not os.path.exists(elf) or not all(shutil.which(t) for t in ("nm", "objdump", "readelf")):
+        return
+    blob = open(elf, "rb").read()
+    lo, hi = 0xD6F80, 0xD83E0 + 8 * 129  # exp_x .. normal_y (SURVEY.md 8c)
+    out = {"zig_region": np.frombuffer(blob[lo:hi], dtype=np.uint8), "zig_region_offset": np.array([lo])}
+    out["comment"] = np.array(subprocess.check_output(["readelf", "-p", ".comment", elf]).decode())
+    syms = subprocess.check_output(["nm", "-n", elf]).decode().splitlines()
+
+    def dis(start, stop):
+        return subprocess.check_output(["objdump", "-d", "--no-show-raw-insn", "--start-address=0x%x" % start,
+                                        "--stop-address=0x%x" % stop, elf]).decode()
+    call = re.compile(r"call\s+[0-9a-f]+ <([^>]+)>")
+    # gamma_distribution<double>::operator()(mt19937&): up to the next symbol
+    for i, l in enumerate(syms):
+        if "gamma_distributionIdEclINS0_23mersenne_twister_engine" in l:
+            addr = int(l.split()[0], 16)
+            nxt = next(int(m.split()[0], 16) for m in syms[i + 1:] if m.split()[0] != l.split()[0] and len(m.split()) == 3)
+            break
+    d = dis(addr, nxt)
+    out["gamma_calls"] = np.array(call.findall(d))
+    out["gamma_consts"] = np.array(sorted({struct.unpack("<d", blob[int(a, 16) - 0x400000:int(a, 16) - 0x400000 + 8])[0]
+                                           for a in re.findall(r"sd\s+0x[0-9a-f]+\(%rip\),%xmm\d+\s+# ([0-9a-f]+)", d)}))
+    # std::shuffle<vector<int>::iterator, mt19937&>
+    addr = next(int(l.split()[0], 16) for l in syms if "_ZSt7shuffleIN9__gnu_cxx17__normal_iteratorIPiSt6vectorIiSaIiEEEE" in l)
+    lines = dis(addr, addr + 0x5a0).splitlines()
+    out["shuffle_mnemonics"] = np.array([l.split("\t")[-1].split()[0] for l in lines if "\t" in l])
+    first_call = next(i for i, l in enumerate(lines) if "uniform_int_distribution" in l)
+    head = [l.split("\t")[-1] for l in lines[:first_call] if "\t" in l]
+    out["shuffle_head"] = np.array([h for h in head if h.startswith(("div", "imul"))])
+    # Distributions_boost::beta_rng(double, double), up to its return
+    addr = next(int(l.split()[0], 16) for l in syms if l.endswith("_ZN19Distributions_boost8beta_rngEdd"))
+    body = [l for l in dis(addr, addr + 0xe0).splitlines() if "\t" in l]
+    body = body[:next(i for i, l in enumerate(body) if l.split("\t")[-1].split()[0].startswith("ret"))]
+    out["beta_calls"] = np.array(call.findall("\n".join(body)))
+    out["beta_mnemonics"] = np.array([l.split("\t")[-1].split()[0] for l in body])
+    np.savez(os.path.join(GOLD, "reference_elf.npz"), **out)
+    print("reference_elf.npz from", elf)
+
+
+def reference_build():
+    """Answers of the reference pieces oracle/Makefile compiles into oracle/_ref."""
+    import ctypes as C
+    import orc
+    lut = os.path.join(ROOT, "oracle", "_ref", "libdotp_lut.so")
+    if os.path.exists(lut):
+        R = C.CDLL(lut)
+        R.ref_dotp_lut_a.restype = C.POINTER(C.c_double)
+        R.ref_dotp_lut_b.restype = C.POINTER(C.c_double)
+        np.savez(os.path.join(GOLD, "reference_lut.npz"), lut_a=np.ctypeslib.as_array(R.ref_dotp_lut_a(), shape=(1024,)).copy(),
+                 lut_b=np.ctypeslib.as_array(R.ref_dotp_lut_b(), shape=(1024,)).copy())
+        print("reference_lut.npz from", lut)
+    lib = orc.ref_arms_lib()
+    if lib is None:
+        return
+    import test_bayesw_oracle as T
+    fn = getattr(lib, orc.REF_ARMS_SYMBOL)
+    fn.argtypes, fn.restype = T.ARMS_SIG, C.c_int
+    out = {}
+    for case, (dens, xinit, xl, xr) in T.CASES.items():
+        out["case_" + case] = np.array(T.run_arms(fn, dens, xinit, xl, xr, 250, 7), dtype=np.float64).reshape(-1, 3)
+    rows = [T.run_arms(fn, *t) for t in T.random_densities()]
+    out["random"] = np.full((len(rows), max(len(r) for r in rows), 3), np.nan)
+    for i, r in enumerate(rows):
+        out["random"][i, :len(r)] = r
+    out["random_len"] = np.array([len(r) for r in rows])
+    bed, y, fail, kw = T.chain_case()
+    chain = T._run(orc.load(), bed, 900, y, fail, 6, ref_lib=lib, **kw)
+    out.update(chain_mu=np.array([x[0] for x in chain]), chain_alpha=np.array([x[1] for x in chain]),
+               chain_beta=np.array([x[3] for x in chain]), chain_comp=np.array([x[4] for x in chain]),
+               chain_csv=np.array([x[5] for x in chain]))
+    np.savez(os.path.join(GOLD, "reference_arms.npz"), **out)
+    print("reference_arms.npz from", orc.REF_ARMS_SYMBOL)
+
+
+def reference_gh():
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import gen_gh_tables
+    if not os.path.exists(gen_gh_tables.REF):
+        return
+    lits = gen_gh_tables.reference_literals()
+    np.savez(os.path.join(GOLD, "reference_gh.npz"), **{k + str(n): np.array(v) for n, (x, w) in lits.items() for k, v in (("x", x), ("w", w))})
+    print("reference_gh.npz from", gen_gh_tables.REF)
 
 
 EXAMPLE_FILES = ["t_M10K_N_5K.fam", "t_M10K_N_5K.bim", "t_M10K_N_5K.dim", "normal.phen", "normal.group", "normal.mS", "normal.h2",
@@ -215,5 +311,8 @@ def from_oracle():
 if __name__ == "__main__":
     os.makedirs(GOLD, exist_ok=True)
     from_reference()
+    reference_elf()
+    reference_build()
+    reference_gh()
     example_inputs()
     from_oracle()

@@ -2,8 +2,9 @@
 host-only pieces of the product (hg_ars.h, the glibc rand() restatement).
 
 Pins available here: the reference's own ARS sampler compiled from src/BayesW_arms.cpp
-(oracle/_ref/libarms.so), libc's rand(), and the quadrature literals (checked against the
-reference's text by tools/gen_gh_tables.py when /root/reference is present).  The rest of
+(oracle/_ref/libarms.so; its answers recorded in tests/golden/reference_arms.npz), libc's rand(),
+and the quadrature literals (the reference's values recorded in tests/golden/reference_gh.npz,
+checked against tools/gen_gh_tables.py's output).  The rest of
 the BayesW chain is an unpinned restatement (the reference needs Eigen + Boost + MPI)."""
 import ctypes as C
 import math
@@ -72,18 +73,19 @@ def orc_arms(oracle):
 
 @pytest.fixture(scope="module")
 def ref_arms():
-    lib = orc.ref_arms_lib()
-    if lib is None:
-        pytest.skip("oracle/_ref/libarms.so not built (no /root/reference at build time)")
-    fn = getattr(lib, orc.REF_ARMS_SYMBOL)
-    fn.argtypes, fn.restype = ARMS_SIG, C.c_int
-    return fn
+    """What the reference's own arms() (src/BayesW_arms.cpp, built into oracle/_ref/libarms.so) returned on the cases
+    of this module, recorded by tests/golden/make_golden.py: (err, x, neval) rows."""
+    return np.load(os.path.join(ROOT, "tests", "golden", "reference_arms.npz"))
+
+
+def _rows(rows):
+    return [(int(e), float(x), int(n)) for e, x, n in rows]
 
 
 @pytest.mark.parametrize("case", sorted(CASES))
 def test_oracle_ars_is_the_reference_ars(orc_arms, ref_arms, case):
     dens, xinit, xl, xr = CASES[case]
-    a = run_arms(ref_arms, dens, xinit, xl, xr, 250, 7)
+    a = _rows(ref_arms["case_" + case])
     b = run_arms(orc_arms, dens, xinit, xl, xr, 250, 7)
     assert a == b  # samples, evaluation counts and error codes, bit for bit
     if case == "not_concave":
@@ -121,10 +123,12 @@ def test_gh_tables_product_and_oracle_copies_agree_and_generator_checks_the_refe
     b = open(os.path.join(ROOT, "hydra_amd", "csrc", "hg_gh_tables.h")).read().replace("HG_GH", "X").replace("hg_gh", "x")
     strip = lambda t: [l for l in t.splitlines() if "copy" not in l]
     assert strip(a) == strip(b)
-    if os.path.exists("/root/reference/src/BayesW.cpp"):
-        sys.path.insert(0, os.path.join(ROOT, "tools"))
-        import gen_gh_tables
-        assert gen_gh_tables.check_against_reference(gen_gh_tables.tables()) == 201
+    # the generator against the reference's literals (src/BayesW.cpp, recorded by tests/golden/make_golden.py)
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import gen_gh_tables
+    gold = np.load(os.path.join(ROOT, "tests", "golden", "reference_gh.npz"))
+    literals = {n: (list(gold["x%d" % n]), list(gold["w%d" % n])) for n in gen_gh_tables.ORDERS}
+    assert gen_gh_tables.check_against_reference(gen_gh_tables.tables(), literals) == 201
 
 
 def _case(M=260, N=900, seed=3, missing_rate=0.01):
@@ -144,17 +148,21 @@ def _run(oracle, bed, N, y, fail, iters, ref_lib=None, **kw):
     return out
 
 
-def test_oracle_chain_runs_the_same_on_the_reference_arms(oracle):
-    lib = orc.ref_arms_lib()
-    if lib is None:
-        pytest.skip("oracle/_ref/libarms.so not built")
+def chain_case():
+    """The BayesW chain run once on the reference's arms() (recorded) and once on the oracle's restatement."""
     _, bed, y, fail, _ = _case()
     groups = (np.arange(bed.shape[0]) % 2).astype(np.int32)
     mS = np.array([[0.0, 0.001, 0.01], [0.0, 0.0001, 0.1]])
-    a = _run(oracle, bed, 900, y, fail, 6, seed=5, quad=11, groups=groups, mS=mS)
-    b = _run(oracle, bed, 900, y, fail, 6, ref_lib=lib, seed=5, quad=11, groups=groups, mS=mS)
-    for x, z in zip(a, b):
-        assert x[0] == z[0] and x[1] == z[1] and np.array_equal(x[3], z[3]) and np.array_equal(x[4], z[4]) and x[5] == z[5]
+    return bed, y, fail, dict(seed=5, quad=11, groups=groups, mS=mS)
+
+
+def test_oracle_chain_runs_the_same_on_the_reference_arms(oracle, ref_arms):
+    bed, y, fail, kw = chain_case()
+    a = _run(oracle, bed, 900, y, fail, 6, **kw)
+    for it, x in enumerate(a):
+        assert x[0] == ref_arms["chain_mu"][it] and x[1] == ref_arms["chain_alpha"][it]
+        assert np.array_equal(x[3], ref_arms["chain_beta"][it]) and np.array_equal(x[4], ref_arms["chain_comp"][it])
+        assert x[5] == str(ref_arms["chain_csv"][it])
     assert sum(int((x[4] > 0).sum()) for x in a) > 20  # slabs were actually entered
 
 
@@ -247,7 +255,7 @@ GOLD = os.path.join(ROOT, "tests", "golden")
 
 def test_ars_known_answers(orc_arms):
     """tests/golden/bayesw_small.npz holds 100 draws per density made on rand() after srand(7): the numbers the
-    reference's arms() gives (test_oracle_ars_is_the_reference_ars proves that whenever oracle/_ref is built)."""
+    reference's arms() gives (test_oracle_ars_is_the_reference_ars checks that on its recorded answers)."""
     gold = np.load(os.path.join(GOLD, "bayesw_small.npz"))
     for case in ("normal", "gamma"):
         dens, xinit, xl, xr = CASES[case]
@@ -266,9 +274,9 @@ def test_bayesw_chain_regression(oracle):
     assert np.array_equal(ch.arr("eps"), gold["bw_eps"])
 
 
-def test_ars_matches_reference_on_random_densities(orc_arms, ref_arms):
-    """Property: over random parameters of the four densities BayesW samples (shapes of mu_dens, alpha_dens,
-    beta_dens, gamma_dens) the restated sampler and the reference's arms() agree bit for bit."""
+def random_densities():
+    """120 random parameter sets of the four densities BayesW samples (shapes of mu_dens, alpha_dens, beta_dens,
+    gamma_dens): (dens, xinit, xl, xr, n, seed) for run_arms."""
     rng = np.random.default_rng(2024)
     for trial in range(120):
         kind = trial % 3
@@ -289,5 +297,12 @@ def test_ars_matches_reference_on_random_densities(orc_arms, ref_arms):
             dens = lambda x: -a * x * 30.0 - float(np.exp((eps - x) * a - 0.577215664901532).sum()) - x * x / 200.0
             mu = 3.0 + rng.normal(0, 0.05)
             xinit, xl, xr = [0.95 * mu, mu, 1.005 * mu, 1.01 * mu], 0.8 * mu, 1.1 * mu
-        seed = int(rng.integers(1, 2 ** 31))
-        assert run_arms(ref_arms, dens, xinit, xl, xr, 5, seed) == run_arms(orc_arms, dens, xinit, xl, xr, 5, seed), (trial, kind)
+        yield dens, xinit, xl, xr, 5, int(rng.integers(1, 2 ** 31))
+
+
+def test_ars_matches_reference_on_random_densities(orc_arms, ref_arms):
+    """Property: over random parameters of the four densities BayesW samples the restated sampler and the
+    reference's arms() agree bit for bit."""
+    for trial, (dens, xinit, xl, xr, n, seed) in enumerate(random_densities()):
+        want = _rows(ref_arms["random"][trial][:ref_arms["random_len"][trial]])
+        assert run_arms(orc_arms, dens, xinit, xl, xr, n, seed) == want, (trial, trial % 3)

@@ -1,5 +1,5 @@
 """Oracle decode / statistics / dot / update / chain against the reference's own
-tables (dotp_lut.h via oracle/_ref and the committed fixture), the BED writer
+tables (dotp_lut.h as compiled via oracle/_ref and as mk_lut prints it, both recorded), the BED writer
 of the reference (get_bed_marker_from_sparse, src/data.cpp:838-864), and
 regression fixtures; plus the size-independent properties used at full size."""
 import ctypes as C
@@ -26,13 +26,11 @@ def test_decode_equals_reference_lut_fixture(oracle):
         assert np.array_equal(v, gold["lut_a"][4 * byte:4 * byte + 4])
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "libdotp_lut.so")), reason="oracle/_ref not built")
 def test_decode_equals_compiled_reference_lut(oracle):
-    R = C.CDLL(os.path.join(ROOT, "oracle", "_ref", "libdotp_lut.so"))
-    R.ref_dotp_lut_a.restype = C.POINTER(C.c_double)
-    R.ref_dotp_lut_b.restype = C.POINTER(C.c_double)
-    a = np.ctypeslib.as_array(R.ref_dotp_lut_a(), shape=(1024,))
-    b = np.ctypeslib.as_array(R.ref_dotp_lut_b(), shape=(1024,))
+    """The tables as the reference's header compiles (src/dotp_lut.h through oracle/_ref/libdotp_lut.so, recorded
+    in tests/golden/reference_lut.npz) equal mk_lut's printed ones and the oracle's decode."""
+    ref = np.load(os.path.join(GOLD, "reference_lut.npz"))
+    a, b = ref["lut_a"], ref["lut_b"]
     gold = np.load(os.path.join(GOLD, "dotp_lut.npz"))
     assert np.array_equal(a, gold["lut_a"]) and np.array_equal(b, gold["lut_b"])
     v, m = np.zeros(4), np.zeros(4)

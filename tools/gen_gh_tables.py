@@ -86,11 +86,12 @@ def tables():
     return out
 
 
-def check_against_reference(tabs):
-    src = open(REF).read()
+def reference_literals(path=REF):
+    """{n: (x_1..x_{n-1}, w_1..w_n)}: the doubles the reference's literals denote, in its own numbering."""
+    src = open(path).read()
     body = src[src.index("double BayesW::gauss_hermite_adaptive_integral"):src.index("void BayesW::marginal_likelihood_vec_calc")]
     blocks = re.split(r'if\s*\(\s*n\s*==\s*"(\d+)"\s*\)', body)
-    checked = 0
+    out = {}
     for i in range(1, len(blocks), 2):
         n = int(blocks[i])
         blk = re.sub(r"//.*", "", blocks[i + 1])
@@ -100,12 +101,22 @@ def check_against_reference(tabs):
         w = {int(a): float(b) for a, b in re.findall(r"\bw(\d+)\s*=\s*([0-9.]+)\s*;", blk)}
         for a, b in re.findall(r"\bw(\d+)\s*=\s*w(\d+)\s*;", blk):
             w[int(a)] = w[int(b)]
+        assert len(x) == n - 1 and len(w) == n, (n, len(x), len(w))
+        out[n] = ([x[k] for k in range(1, n)], [w[k] for k in range(1, n + 1)])
+    return out
+
+
+def check_against_reference(tabs, literals=None):
+    """Literal-by-literal comparison with the reference (its text, or reference_literals() recorded earlier)."""
+    literals = literals if literals is not None else reference_literals()
+    checked = 0
+    for n, (x, w) in literals.items():
         xs, ws = tabs[n]
         assert len(x) == n - 1 and len(w) == n, (n, len(x), len(w))
         for k in range(1, n):
-            assert float(xs[k - 1]) == x[k], (n, "x", k, xs[k - 1], x[k])
+            assert float(xs[k - 1]) == x[k - 1], (n, "x", k, xs[k - 1], x[k - 1])
         for k in range(1, n + 1):
-            assert float(ws[k - 1]) == w[k], (n, "w", k, ws[k - 1], w[k])
+            assert float(ws[k - 1]) == w[k - 1], (n, "w", k, ws[k - 1], w[k - 1])
         checked += 2 * n - 1
     return checked
 
