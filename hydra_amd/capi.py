@@ -21,7 +21,7 @@ ABI_SYMBOLS = [
     "hydra_rng_to_boost_words", "hydra_rng_from_boost_words", "hgibbs_set_model", "hgibbs_set_beta", "hgibbs_get_beta",
     "hgibbs_beta_sqnorm", "hgibbs_sweep", "hgibbs_set_option", "hgibbs_last_sweep_stats", "hgibbs_stream_ceiling", "hgibbs_debug_times", "hgibbs_resident_trace", "hydra_chain_create",
     "hydra_chain_destroy", "hydra_chain_iterate", "hydra_chain_state", "hydra_chain_csv_line", "hydra_chain_order",
-    "hydra_chain_last_nnz",
+    "hydra_chain_last_nnz", "hgibbs_score", "hgibbs_last_score_ms",
     # BayesW
     "hgibbs_grand_seed", "hgibbs_grand_next", "hgibbs_ars_sample", "hgibbs_w_init", "hgibbs_w_marker_stats", "hgibbs_w_set_model",
     "hgibbs_w_reduce", "hgibbs_w_refresh_vi", "hgibbs_w_get_vi", "hgibbs_w_marker_sums", "hgibbs_w_sweep", "hgibbs_w_last_sweep_stats", "hgibbs_w_ars_device_probe",
@@ -179,6 +179,8 @@ def lib():
     L.hydraw_chain_csv_line.argtypes = [vp, C.c_uint32, C.c_char_p, C.c_size_t]
     L.hydraw_chain_restore.argtypes = [vp, C.POINTER(WRestartState)]
     L.hydra_chain_last_nnz.restype = C.c_uint64
+    L.hgibbs_score.argtypes = [vp, C.c_int, dp, dp, dp]
+    L.hgibbs_last_score_ms.argtypes = [vp, dp]
     _lib = L
     return L
 
@@ -359,6 +361,21 @@ class Device:
 
     def set_option(self, name, value):
         check(self.L.hgibbs_set_option(self.h, name.encode(), int(value)))
+
+    def score(self, a, o):
+        """(S, M) weights a, o -> (n_local, S): sum_j [g_ij not missing] (a_sj g_ij + o_sj) (hgibbs_score)."""
+        a = np.ascontiguousarray(np.atleast_2d(a), dtype=np.float64)
+        o = np.ascontiguousarray(np.atleast_2d(o), dtype=np.float64)
+        if a.shape != o.shape or a.shape[1] != self.M:
+            raise ValueError("a and o must both be (S, %d)" % self.M)
+        out = np.zeros((self.n_local, a.shape[0]))
+        check(self.L.hgibbs_score(self.h, a.shape[0], _dp(a), _dp(o), _dp(out)))
+        return out
+
+    def last_score_ms(self):
+        v = C.c_double()
+        check(self.L.hgibbs_last_score_ms(self.h, C.byref(v)))
+        return v.value
 
     def debug_times(self):
         """The 48 stage-timestamp words of the sweep kernel's debug build (option debug_timing; 100 MHz ticks, accumulated

@@ -181,6 +181,9 @@ struct hgibbs_ctx {
     double res_deadline_s = 0.0; // option res_deadline_ms: the host's deadline for a resident sweep (0 = derived)
 
     hgibbs_sweep_stats stats{};
+    int score_sp = 0;     // option score_sp: samples per pass of hgibbs_score, 2, 4, 8 or 16 (0 = automatic, hg_score.hip.h)
+    int score_ranges = 0; // option score_ranges: at most this many ranges of markers per column of workgroups (0 = automatic)
+    double score_ms = 0.0; // device time of the last hgibbs_score (weights to digits, products, rounding)
 };
 
 static int ensure_scratch(hgibbs_ctx* h, size_t n)
@@ -1208,7 +1211,13 @@ int hgibbs_set_option(hgibbs_t h, const char* name, int64_t value)
     for (const char* o : {"cols_per_group", "slices", "gram_missing", "graph", "max_seg", "ext_limit", "gram", "carry", "ahead", "force_split", "chunk"})
         if (!std::strcmp(name, o) && h->engine == 0) h->engine_pinned = true;
     if (!std::strcmp(name, "batch") && value != 0 && h->engine == 0) h->engine_pinned = true; // a batch width (0 = auto names none)
-    if (!std::strcmp(name, "batch")) {
+    if (!std::strcmp(name, "score_sp")) {
+        if (value != 0 && value != 2 && value != 4 && value != 8 && value != 16) return fail("score_sp must be 0 (automatic), 2, 4, 8 or 16");
+        h->score_sp = (int)value;
+    } else if (!std::strcmp(name, "score_ranges")) {
+        if (value < 0 || value > 65535) return fail("score_ranges must be in [0,65535] (0 = automatic)");
+        h->score_ranges = (int)value;
+    } else if (!std::strcmp(name, "batch")) {
         if (value < 0 || value > MAX_BATCH) return fail("batch must be in [0,%d] (0 = auto)", MAX_BATCH);
         h->batch = (uint32_t)value;
     } else if (!std::strcmp(name, "cols_per_group")) {
@@ -2020,3 +2029,4 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
 } // extern "C"
 
 #include "hg_bayesw.hip.h"
+#include "hg_score.hip.h"

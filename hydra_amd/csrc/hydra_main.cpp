@@ -12,6 +12,10 @@
 //
 // `--mpibayes bayesWMPI --failure F --quad_points Q` runs BayesW (src/BayesW.cpp:905), sharded the same way.
 //
+// `--predict-bfile T [--predict-out F] [--predict-dry-run]` appended to a bayesMPI command line samples nothing: it scores the target
+// cohort T with the chain's .bet records at or after --burn-in (run_predict); the dry run stops after every
+// check and the marker-match report, before the device.
+//
 // Not reproduced (out of scope for the hot path): sparse
 // file formats, bayesFH, marker-sharded MPI, the .lst/tarball.
 // Multi-GPU: one process per GPU (RANK/WORLD_SIZE/LOCAL_RANK in the
@@ -51,6 +55,8 @@ struct Options { // src/options.hpp:20-138 (subset that reaches bayesMPI)
     bool readFromBedFile = false;
     bool restart = false, useXfilesInRestart = true; // options.hpp:33-34
     std::string failureFile, quad_points;            // options.hpp:56-58 (bayesWMPI)
+    std::string predictBfile, predictOut;            // --predict-bfile / --predict-out: score a target cohort (this build's, not hydra's)
+    bool predictDryRun = false;                      // --predict-dry-run: every check and the match report, then stop before the device
     int batch = 0, cpg = 0; // tuning knobs of this build (not hydra's)
 };
 
@@ -166,6 +172,9 @@ Options parse(int argc, const char* argv[])
         else if (a == "--quad_points") o.quad_points = need(i); // options.cpp:188-191
         else if (a == "--restart") o.restart = true;          // options.cpp:63-65
         else if (a == "--ignore-xfiles") o.useXfilesInRestart = false; // options.cpp:67-69
+        else if (a == "--predict-bfile") o.predictBfile = need(i);
+        else if (a == "--predict-out") o.predictOut = need(i);
+        else if (a == "--predict-dry-run") o.predictDryRun = true;
         else if (a == "--sparse-dir" || a == "--sparse-basename" ||
                  a == "--bed-to-sparse" || a == "--sparse-sync" || a == "--bed-sync")
             fatal("FATAL  : option " + a + " belongs to a part of hydra this build does not reproduce (SURVEY.md section 2)");
@@ -831,6 +840,198 @@ int run_bayesw(const Options& opt_in, int rank, int nranks, int local_rank)
     return 0;
 }
 
+// ---- --predict-bfile: score a target cohort with the chain's effects ----
+struct BimRows {
+    std::vector<std::string> id, a1, a2;
+};
+
+BimRows read_bim(const std::string& path, size_t limit)
+{
+    std::ifstream in(path);
+    if (!in) fatal("Error: can not open the file [" + path + "] to read.");
+    BimRows b;
+    std::string chr, id, gpos, pos, a1, a2;
+    while (b.id.size() < limit && in >> chr >> id >> gpos >> pos >> a1 >> a2) {
+        b.id.push_back(id);
+        b.a1.push_back(a1);
+        b.a2.push_back(a2);
+    }
+    return b;
+}
+
+// <dir>/<name>.bet: u32 Mtot, then (u32 iteration, Mtot f64) per thinned iteration (postproc/beta_converter.cpp); the records whose
+// iteration is at least `burnin`
+void read_bet_records(const std::string& path, unsigned Mtot, unsigned burnin, std::vector<unsigned>& its, std::vector<double>& beta)
+{
+    FILE* f = std::fopen(path.c_str(), "rb");
+    if (!f) fatal("FATAL  : can not open " + path + " (--predict-bfile scores with the chain's effects: run the chain first)");
+    unsigned m = 0;
+    if (std::fread(&m, sizeof m, 1, f) != 1 || m != Mtot) {
+        std::fclose(f);
+        fatal("FATAL  : " + path + " holds " + std::to_string(m) + " markers, --number-markers says " + std::to_string(Mtot));
+    }
+    std::vector<double> row(Mtot);
+    unsigned it = 0, total = 0;
+    while (std::fread(&it, sizeof it, 1, f) == 1) {
+        if (std::fread(row.data(), sizeof(double), Mtot, f) != Mtot) break; // (a record cut short: the chain was stopped while writing)
+        ++total;
+        if (it < burnin) continue;
+        its.push_back(it);
+        beta.insert(beta.end(), row.begin(), row.end());
+    }
+    std::fclose(f);
+    if (its.empty())
+        fatal("FATAL  : " + path + ": no record at or after --burn-in " + std::to_string(burnin) + " (" + std::to_string(total) + " records)");
+}
+
+int run_predict(const Options& opt, const std::vector<uint8_t>& keep, unsigned numInds, unsigned numNAs, unsigned Mtot, int local_rank)
+{
+    const std::string base = opt.mcmcOutDir + "/" + opt.mcmcOutNam;
+    const std::string out = opt.predictOut.empty() ? base + ".prs" : opt.predictOut;
+    const BimRows tr = read_bim(opt.bedFile + ".bim", Mtot);
+    std::vector<unsigned> its;
+    std::vector<double> betas;
+    read_bet_records(base + ".bet", Mtot, opt.burnin, its, betas);
+    const size_t S = its.size();
+
+    // target cohort: .fam (every row: the target needs no phenotype), .bim matched to the training markers by id
+    const std::string tp = opt.predictBfile;
+    std::vector<std::string> fid, iid;
+    {
+        std::ifstream in(tp + ".fam");
+        if (!in) fatal("Error: can not open the file [" + tp + ".fam] to read.");
+        std::string f, i, dad, mom, sex, phen;
+        while (in >> f >> i >> dad >> mom >> sex >> phen) {
+            fid.push_back(f);
+            iid.push_back(i);
+        }
+    }
+    const size_t nT = fid.size();
+    if (nT == 0) fatal("FATAL  : " + tp + ".fam lists no individual");
+    const BimRows tg = read_bim(tp + ".bim", (size_t)-1);
+    const size_t Mt = tg.id.size();
+    std::map<std::string, unsigned> train_idx;
+    for (unsigned j = 0; j < Mtot; ++j)
+        if (!train_idx.emplace(tr.id[j], j).second) fatal("FATAL  : the training .bim lists SNP id " + tr.id[j] + " twice: markers are matched by id");
+    std::map<std::string, int> seen;
+    std::vector<int> match(Mt, -1); // training marker of each target column, -1 = contributes nothing
+    std::vector<uint8_t> flip(Mt, 0);
+    size_t same = 0, swapped = 0, allele = 0, absent = 0;
+    for (size_t t = 0; t < Mt; ++t) {
+        if (!seen.emplace(tg.id[t], 1).second) fatal("FATAL  : " + tp + ".bim lists SNP id " + tg.id[t] + " twice: markers are matched by id");
+        const auto it = train_idx.find(tg.id[t]);
+        if (it == train_idx.end()) {
+            ++absent;
+            continue;
+        }
+        const unsigned j = it->second;
+        if (tg.a1[t] == tr.a1[j] && tg.a2[t] == tr.a2[j]) {
+            match[t] = (int)j;
+            ++same;
+        } else if (tg.a1[t] == tr.a2[j] && tg.a2[t] == tr.a1[j]) {
+            match[t] = (int)j;
+            flip[t] = 1;
+            ++swapped;
+        } else
+            ++allele;
+    }
+    std::printf("PREDICT: %zu target markers: %zu matched (%zu same alleles, %zu swapped), %zu allele mismatch, %zu not in training; "
+                "%zu of %u training markers unused\n",
+                Mt, same + swapped, same, swapped, allele, absent, (size_t)Mtot - same - swapped, Mtot);
+    std::printf("PREDICT: %zu records of %s (iterations %u .. %u), %zu target individuals -> %s\n", S, (base + ".bet").c_str(), its.front(),
+                its.back(), nT, out.c_str());
+    std::fflush(stdout);
+    if (same + swapped == 0) fatal("FATAL  : no marker of " + tp + ".bim matches a training marker (by SNP id and alleles)");
+
+    // target genotypes, read before the device opens
+    const size_t lenT = (nT + 3) / 4;
+    std::vector<uint8_t> bedT((size_t)Mt * lenT);
+    {
+        std::ifstream in(tp + ".bed", std::ios::binary);
+        if (!in) fatal("Error: can not open the file [" + tp + ".bed] to read.");
+        unsigned char magic[3];
+        in.read((char*)magic, 3);
+        if (!in || magic[0] != 0x6c || magic[1] != 0x1b || magic[2] != 0x01) fatal("FATAL  : " + tp + ".bed is not a SNP-major PLINK bed");
+        in.read((char*)bedT.data(), (std::streamsize)bedT.size());
+        if ((size_t)in.gcount() != bedT.size()) fatal("FATAL  : " + tp + ".bed is shorter than M x ceil(N/4)");
+    }
+    if (opt.predictDryRun) {
+        std::printf("PREDICT: dry run: inputs checked, nothing scored\n");
+        return 0;
+    }
+
+    // the chain's standardisation: mave, mstd of the training markers over the rows that kept their phenotype
+    std::vector<double> mave(Mtot), mstd(Mtot);
+    {
+        const size_t len = (numInds + 3) / 4;
+        std::vector<uint8_t> bed((size_t)Mtot * len);
+        std::ifstream in(opt.bedFile + ".bed", std::ios::binary);
+        if (!in) fatal("Error: can not open the file [" + opt.bedFile + ".bed] to read.");
+        unsigned char magic[3];
+        in.read((char*)magic, 3);
+        if (!in || magic[0] != 0x6c || magic[1] != 0x1b || magic[2] != 0x01) fatal("FATAL  : " + opt.bedFile + ".bed is not a SNP-major PLINK bed");
+        in.read((char*)bed.data(), (std::streamsize)bed.size());
+        if ((size_t)in.gcount() != bed.size()) fatal("FATAL  : " + opt.bedFile + ".bed is shorter than M x ceil(N/4)");
+        const unsigned Ntot = numInds - numNAs;
+        hgibbs_t dev = nullptr;
+        hg_check(hgibbs_create(local_rank, &dev), "hgibbs_create");
+        hg_check(hgibbs_load_bed(dev, bed.data(), len, numInds, Mtot, numNAs ? keep.data() : nullptr, 0, Ntot, Ntot), "hgibbs_load_bed");
+        hg_check(hgibbs_marker_stats(dev, mave.data(), mstd.data(), nullptr, nullptr, nullptr), "hgibbs_marker_stats");
+        hgibbs_destroy(dev);
+    }
+
+    hgibbs_t dev = nullptr;
+    hg_check(hgibbs_create(local_rank, &dev), "hgibbs_create");
+    hg_check(hgibbs_load_bed(dev, bedT.data(), lenT, (uint32_t)nT, (uint32_t)Mt, nullptr, 0, (uint32_t)nT, (uint32_t)std::max<size_t>(nT, 2)),
+             "hgibbs_load_bed (target)");
+    std::vector<uint8_t>().swap(bedT);
+    // x = (g - mave) mstd on the chain's scale; a swapped target column counts the other allele: g -> 2 - g
+    const size_t chunk = 32;
+    std::vector<double> score(nT * S), a, o, part;
+    for (size_t s0 = 0; s0 < S; s0 += chunk) {
+        const size_t sc = std::min(chunk, S - s0);
+        a.assign(sc * Mt, 0.0);
+        o.assign(sc * Mt, 0.0);
+        for (size_t s = 0; s < sc; ++s) {
+            const double* b = betas.data() + (s0 + s) * Mtot;
+            for (size_t t = 0; t < Mt; ++t) {
+                if (match[t] < 0) continue;
+                const unsigned j = (unsigned)match[t];
+                const double w = b[j] * mstd[j];
+                a[s * Mt + t] = flip[t] ? -w : w;
+                o[s * Mt + t] = flip[t] ? w * (2.0 - mave[j]) : -w * mave[j];
+            }
+        }
+        part.resize(nT * sc);
+        hg_check(hgibbs_score(dev, (int)sc, a.data(), o.data(), part.data()), "hgibbs_score");
+        for (size_t i = 0; i < nT; ++i)
+            for (size_t s = 0; s < sc; ++s) score[i * S + s0 + s] = part[i * sc + s];
+    }
+    hgibbs_destroy(dev);
+
+    FILE* f = std::fopen(out.c_str(), "w");
+    if (!f) fatal("FATAL  : can not create " + out);
+    std::fprintf(f, "FID IID mean sd\n");
+    for (size_t i = 0; i < nT; ++i) {
+        double m = 0.0;
+        for (size_t s = 0; s < S; ++s) m += score[i * S + s];
+        m /= (double)S;
+        double v = 0.0;
+        for (size_t s = 0; s < S; ++s) v += (score[i * S + s] - m) * (score[i * S + s] - m);
+        const double sd = S > 1 ? std::sqrt(v / (double)(S - 1)) : 0.0;
+        std::fprintf(f, "%s %s %.17g %.17g\n", fid[i].c_str(), iid[i].c_str(), m, sd);
+    }
+    if (std::fclose(f) != 0) fatal("FATAL  : short write on " + out);
+    f = std::fopen((out + ".bin").c_str(), "wb");
+    if (!f) fatal("FATAL  : can not create " + out + ".bin");
+    const uint32_t hdr[2] = {(uint32_t)nT, (uint32_t)S};
+    pwrite_at(f, 0, hdr, sizeof hdr);
+    pwrite_at(f, sizeof hdr, score.data(), score.size() * sizeof(double));
+    if (std::fclose(f) != 0) fatal("FATAL  : short write on " + out + ".bin");
+    std::printf("PREDICT: wrote %s and %s.bin\n", out.c_str(), out.c_str());
+    return 0;
+}
+
 } // namespace
 
 int main(int argc, const char* argv[])
@@ -855,6 +1056,12 @@ int main(int argc, const char* argv[])
     const int rank = (e = std::getenv("RANK")) ? std::atoi(e) : 0;
     const int nranks = (e = std::getenv("WORLD_SIZE")) ? std::atoi(e) : 1;
     const int local_rank = (e = std::getenv("LOCAL_RANK")) ? std::atoi(e) : rank;
+    if (!opt.predictBfile.empty()) {
+        if (opt.bayesType == "bayesWMPI") fatal("FATAL  : --predict-bfile scores with bayesMPI effects only, not with --mpibayes bayesWMPI");
+        if (opt.restart) fatal("FATAL  : --predict-bfile does not sample: it cannot be combined with --restart");
+        if (nranks > 1) fatal("FATAL  : --predict-bfile runs on one process (WORLD_SIZE = " + std::to_string(nranks) + ")");
+    } else if (!opt.predictOut.empty() || opt.predictDryRun)
+        fatal(std::string("FATAL  : ") + (opt.predictDryRun ? "--predict-dry-run" : "--predict-out") + " needs --predict-bfile");
     if (opt.bayesType == "bayesWMPI") return run_bayesw(opt, rank, nranks, local_rank); // main.cpp:164-167
 
     // ---- inputs (main.cpp:69-70,88; BayesRRm.cpp:969-997) -------------------
@@ -882,6 +1089,7 @@ int main(int argc, const char* argv[])
                         numInds, numInds, numNAs, Ntot);
         std::printf("INFO   : Full dataset includes Mtot=%d markers and Ntot=%d individuals.\n", Mtot, (int)numInds);
     }
+    if (!opt.predictBfile.empty()) return run_predict(opt, keep, (unsigned)numInds, numNAs, Mtot, local_rank);
 
     std::vector<int32_t> groups;
     std::vector<std::vector<double>> mS;

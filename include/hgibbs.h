@@ -227,6 +227,22 @@ int hgibbs_debug_times(hgibbs_t h, uint64_t* out48);
  * reserved for experiments (tools/res_anatomy.py reads the first eight) */
 int hgibbs_resident_trace(hgibbs_t h, uint64_t* out, uint64_t words);
 
+/* ---- scoring a cohort with posterior effects ------ */
+/* For the BED loaded on the handle (this rank's n_local rows, M columns; no collective) and S weight vectors:
+ *     out[i*S + s] = sum_j [g_ij not missing] (a[s*M + j] * g_ij + o[s*M + j])
+ * with g_ij in {0, 1, 2} the genotype as hgibbs_load_bed reads it; a missing call contributes nothing (mean imputation on the
+ * standardised scale when a = beta * mstd, o = -beta * mstd * mave; an allele flip is a = -beta * mstd, o = beta * mstd * (2 - mave)).
+ * a, o: S x M row-major host arrays; out: n_local x S row-major.  The sums are exact integer sums of the weights rounded to
+ * fixed point, one scale per sample from max_j max(|a_sj|, |o_sj|), so |out - exact| <= 3 M max|weight| 2^-52 and the result
+ * does not depend on how the work is split (bit-identical for any S chunking).  Refused: S <= 0, a handle without genotypes,
+ * a weight that is not finite.  Options (hgibbs_set_option): score_sp, samples per pass, 2, 4, 8 or 16 (0 = automatic);
+ * score_ranges, at most this many ranges of markers split over workgroups (0 = automatic; 1 = every workgroup takes all markers
+ * up to 2^21).  The marker-stats counts say which columns have missing calls: when hgibbs_marker_stats has not run, this rank's
+ * own counts are taken (no collective). */
+int hgibbs_score(hgibbs_t h, int S, const double* a, const double* o, double* out);
+/* device time of the last hgibbs_score in ms: every kernel of the call (scales, digits, products, rounding), not the host copies */
+int hgibbs_last_score_ms(hgibbs_t h, double* ms);
+
 /* ======================================================================== */
 /* Host driver: the body of BayesRRm::runMpiGibbs (src/BayesRRm.cpp:933-2939)
  * for --mpibayes bayesMPI, restated on top of hgibbs_*.                     */
