@@ -144,7 +144,8 @@ struct ResParams {
     unsigned long long* trace;   // debug_timing: [8][RS_TRACE] wall-clock stamps of the last RS_TRACE messages (tools/res_anatomy.py)
     int dbg;
     int pivots; // 1: Gram terms with predicted pivots are taken when a column is streamed (messages RS_PIVOT need no round trip)
-    int tune;   // experiments (option res_tune): bits 0-1: priority of the younger wave of each SIMD (waves 4 .. 7) in the refill
+    int unused_; // (free: keeps the offsets of the fields below.  Without it pivots and early_advance share one 8-byte word, which the second
+                 // walker's chain (w2_chain) then loads as one, and the compiler allocates that loop's registers differently)
     int early_advance; // second walker: a walk that has run out of dots moves the window on at once (a message that only advances) when at least this many positions have passed (0: it waits)
     uint32_t wend_mask; // 15 (second walker, B >= 32): the window ends at a multiple of sixteen positions -- min((C + B) & ~15, M) -- so that the
                         // streaming workgroups' second form admits every group of sixteen columns in ONE round (else 0: the window is C + B)
@@ -625,7 +626,7 @@ __device__ __forceinline__ void res_streamer(const ResParams& p, unsigned char* 
         constexpr int r = decltype(rtag)::value;
         const uint32_t pn = __builtin_amdgcn_readfirstlane(pos_of(k));
         const int32_t mk = __builtin_amdgcn_readlane(ids, r);
-        // (the stride is a multiple of 1 KiB and a shard's BED below 4 TiB -- resident_plan -- : one 32-bit multiply and a shift instead of a
+        // (the stride is a multiple of 1 KiB and a shard's BED below 4 TiB -- plan_sweep -- : one 32-bit multiply and a shift instead of a
         // 64-bit multiply's four; scalar instructions cost the wave its issue slot like any other)
         rs_set_load<T, r>(voff, p.bed + ((size_t)((uint32_t)(pn < M ? mk : 0) * (uint32_t)(p.stride >> 10)) << 10));
     };
@@ -728,11 +729,6 @@ __device__ __forceinline__ void res_streamer(const ResParams& p, unsigned char* 
         if constexpr (MISS) {
             if (upd) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); // every wave's share of the updated LDS copy is in place
         }
-        if ((p.tune & 3) && wave >= 4) { // (wave-uniform; the priority is an immediate)
-            if ((p.tune & 3) == 1) __builtin_amdgcn_s_setprio(1);
-            else if ((p.tune & 3) == 2) __builtin_amdgcn_s_setprio(2);
-            else __builtin_amdgcn_s_setprio(3);
-        }
         const uint32_t round_k0 = nk; // this wave's columns of the round: k in [round_k0, nk) behind the passes
         uint32_t done_k0 = nk, done_m = 0; // the sets the last pass consumed: reloaded behind the raw dots
         while (count_w) {
@@ -833,7 +829,6 @@ __device__ __forceinline__ void res_streamer(const ResParams& p, unsigned char* 
             count_w -= m;
         }
         lap(3);
-        if (p.tune & 3) __builtin_amdgcn_s_setprio(0);
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); // the window's new columns and this round's group sums are in LDS for every wave
         lap(4);
         if (DBG && wg == 0 && tid == 0) p.progress[1] = ((unsigned long long)seq << 8) | 2u;
@@ -2017,7 +2012,7 @@ __device__ __attribute__((noinline)) void res_walker(const ResParams& p, unsigne
 // has component 0 and counts for cass[group][0] (the walker counted the events); one outside the adaptive set gets effect 0, Acum 1.
 __global__ __launch_bounds__(256) void k_res_finish(ResParams p)
 {
-    __shared__ int lc[256]; // GK <= 256 (resident_plan)
+    __shared__ int lc[256]; // GK <= 256 (plan_sweep)
     if (p.state->error != 0u) return; // the sweep was given up: the slots hold no numerators
     for (int i = threadIdx.x; i < 256; i += blockDim.x) lc[i] = 0;
     __syncthreads();

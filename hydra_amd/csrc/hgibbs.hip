@@ -86,7 +86,6 @@ struct hgibbs_ctx {
     unsigned long long* counts = nullptr; // 3*M: n1, n2, nmiss (global after all-reduce)
     bool have_stats = false;
     bool any_missing = false; // some column has missing calls
-    double missing_col_frac = 0.0; // fraction of columns with missing calls (decides which build of the sweep kernel runs)
     int gram_missing = -1; // carry columns with missing calls through the extension: -1 auto, 0 never, 1 whenever possible
 
     // covariates: C columns of n_pad doubles in the permuted eps layout
@@ -154,7 +153,7 @@ struct hgibbs_ctx {
     uint32_t window = 0;      // option window: columns kept in LDS per streaming workgroup (0 auto; power of two <= 256)
     uint32_t res_cus = 0;     // option res_cus: compute units the resident engine may use (0 = all)
     int res_walker = 0;       // option walker: 0 auto (the second where it applies), 1 the first walker, 2 the second (hg_walker2.hip.h; refused where it does not apply)
-    bool res_attr_set[20] = {}; // the resident kernels whose LDS opt-in has been made on THIS handle's device
+    bool res_attr_set[20] = {}; // the resident builds (RES_BUILDS, by SweepPlan::slot) whose LDS opt-in has been made on THIS handle's device
     bool res_dead = false;     // a resident kernel did not come back even after the abort word: the stream (and the handle) cannot be used any more
     uint32_t res_probed_w = 0;     // several ranks: the grid size the probe launch has found resident together with the peers' (0: not yet)
     unsigned long long res_probe_id = 0;
@@ -165,7 +164,6 @@ struct hgibbs_ctx {
     int res_walker2_ranks = 1; // option walker2_ranks: several ranks run the second walker too (0: the first, as in round 3)
     double eps_abs_bound = 0.0; // (sum of eps^8)^(1/8) >= max |eps| as of the last reduce_eps_all
     int res_refill = 0;       // option refill: the streaming workgroups' form -- 1 first (hg_resident.hip.h: fused multiply-adds), 2 second (hg_streamer2.hip.h: integer matrix products), 0 auto
-    int res_tune = 0;         // option res_tune: experiments of the resident kernel (ResParams::tune)
     int res_pivots = 0;       // option pivots: Gram terms with predicted pivots at streaming time (no round trip for those events)
     unsigned char* res_acc = nullptr; // Gram + raw-dot accumulators, batch counters
     ResMsg* res_msg = nullptr;
@@ -957,7 +955,6 @@ static int compute_stats(hgibbs_ctx* h)
         uint64_t nmc = 0;
         for (uint32_t i = 0; i < h->M; ++i) nmc += c[3ull * i + 2] != 0 ? 1u : 0u;
         h->any_missing = nmc != 0;
-        h->missing_col_frac = (double)nmc / (double)h->M;
     }
     h->have_stats = true;
     return 0;
@@ -1264,8 +1261,6 @@ int hgibbs_set_option(hgibbs_t h, const char* name, int64_t value)
         h->res_wend = value != 0;
     } else if (!std::strcmp(name, "announce")) {
         h->res_announce = value != 0;
-    } else if (!std::strcmp(name, "res_tune")) {
-        h->res_tune = (int)value;
     } else if (!std::strcmp(name, "walker")) {
         if (value < 0 || value > 2) return fail("walker must be 0 (auto), 1 (first) or 2 (second)");
         h->res_walker = (int)value;
@@ -1344,89 +1339,126 @@ int hgibbs_last_sweep_stats(hgibbs_t h, hgibbs_sweep_stats* out)
 
 } // extern "C"
 
-// ---- the resident engine (hg_resident.hip.h) -------------------------------------------------------------------
-struct ResPlan {
-    bool ok = false;
-    int T = 1;        // wave tiles per streaming workgroup
-    uint32_t W = 0;   // streaming workgroups (+ 1 walker)
-    uint32_t B = 0;   // window
+// ---- the sweep plan: which engine runs a sweep, and how the resident engine (hg_resident.hip.h) runs it -----------------------------
+using ResKernel = void (*)(ResParams, const ResParams*);
+
+// the resident builds, by slot = 4 form + 2 stage clocks + missing-call build; form 0, 1: the first form of the streaming workgroups at
+// T = 1, 2; 2, 3: the second form at T = 1, 2; 4: the second form at T = 4
+static const ResKernel RES_BUILDS[] = {
+    k_sweep_resident<1, 0, 0>, k_sweep_resident<1, 0, 1>, k_sweep_resident<1, 1, 0>, k_sweep_resident<1, 1, 1>,
+    k_sweep_resident<2, 0, 0>, k_sweep_resident<2, 0, 1>, k_sweep_resident<2, 1, 0>, k_sweep_resident<2, 1, 1>,
+    k_sweep_limb<1, 0, 0>,     k_sweep_limb<1, 0, 1>,     k_sweep_limb<1, 1, 0>,     k_sweep_limb<1, 1, 1>,
+    k_sweep_limb<2, 0, 0>,     k_sweep_limb<2, 0, 1>,     k_sweep_limb<2, 1, 0>,     k_sweep_limb<2, 1, 1>,
+    k_sweep_limb4<0, 0>,       k_sweep_limb4<0, 1>,       k_sweep_limb4<1, 0>,       k_sweep_limb4<1, 1>,
+};
+static_assert(sizeof(RES_BUILDS) / sizeof(RES_BUILDS[0]) == sizeof(hgibbs_ctx::res_attr_set), "one LDS opt-in flag per resident build");
+
+// What one sweep runs, decided once from the handle's options and state and this sweep's adaV and opening reduction (DESIGN.md §4,
+// "the sweep plan").  The engine options, the ranks' vote and the probe act on `resident` in hgibbs_sweep.
+struct SweepPlan {
+    bool resident = false;      // the resident engine applies
+    const char* why = nullptr;  // else why not
+    int T = 1;                  // wave tiles per streaming workgroup
+    uint32_t W = 0;             // streaming workgroups (+ 1 walker)
+    uint32_t B = 0;             // window
+    int refill = 1;             // the streaming workgroups' form: 1 fused multiply-adds (hg_resident.hip.h), 2 integer matrix products (hg_streamer2.hip.h)
+    int walker = 1;             // 1 the first walker, 2 the second (hg_walker2.hip.h); 0: the second was asked for and does not apply
+    int pivots = 0;             // ResParams::pivots
+    uint32_t wend_mask = 0;     // ResParams::wend_mask
+    size_t streamer_lds = 0;    // the streaming workgroups' LDS
+    size_t lds = 0;             // the launch's: the larger of the streaming workgroups' and this walker's
+    int slot = 0;               // the build: RES_BUILDS[slot], its LDS opt-in h->res_attr_set[slot]
+    ResKernel kern = nullptr;
 };
 
-static int resident_refill(const hgibbs_ctx* h);
-// nullptr when the resident engine can run this handle's sweeps, else the reason why not
-static const char* resident_plan(hgibbs_ctx* h, ResPlan* pl)
+static SweepPlan plan_sweep(const hgibbs_ctx* h)
 {
-    pl->ok = false;
-    if (h->nranks > 1 && !(h->p2p_ready && h->p2p_enabled)) return "several ranks without peer mailboxes (hgibbs_p2p_import): the RCCL / host exchange lives in the batch engine";
-    if (h->nranks > RX_MAXR) return "more than eight ranks";
-    if (h->force_split) return "force_split";
-    if (h->G * h->K > 256 || h->K > MAX_K || h->K < 2) return "mixture size";
+    SweepPlan pl;
+    auto refuse = [&](const char* why) {
+        pl.why = why;
+        return pl;
+    };
+    if (h->nranks > 1 && !(h->p2p_ready && h->p2p_enabled)) return refuse("several ranks without peer mailboxes (hgibbs_p2p_import): the RCCL / host exchange lives in the batch engine");
+    if (h->nranks > RX_MAXR) return refuse("more than eight ranks");
+    if (h->force_split) return refuse("force_split");
+    if (h->G * h->K > 256 || h->K > MAX_K || h->K < 2) return refuse("mixture size");
     const uint32_t cus = h->res_cus ? std::min<uint32_t>(h->res_cus, (uint32_t)h->num_cu) : (uint32_t)h->num_cu;
-    if (cus < 2) return "fewer than two compute units";
+    if (cus < 2) return refuse("fewer than two compute units");
+    // the form: option refill; auto takes the second, but the first where predicted pivots are asked for (their Gram terms are taken in
+    // the first form's refill only) or where the residual may lie beyond 32: the second form holds eps as round(eps 2^44) in seven signed
+    // digits, |eps| < 64 (RL_EX, hg_streamer2.hip.h).  Asked for by option, the kernel's own check refuses such a sweep (error 5)
+    pl.refill = h->res_refill ? h->res_refill : (h->res_pivots || !(h->eps_abs_bound < 32.0)) ? 1 : 2;
     const uint32_t ntile = h->n_pad / TILE;
     uint32_t T = (ntile + (cus - 1) - 1) / (cus - 1);
     if (T > (uint32_t)RS_TMAX) {
         // four tiles per workgroup: the second form of the streaming workgroups only (eps is 2 T doubles per lane there; the window
         // shrinks to 128 columns to make room for their codes), one rank, no predicted pivots, a residual inside the digits' range
-        const bool four = T <= (uint32_t)RL_TMAX && h->nranks <= 1 && resident_refill(h) == 2 && (h->res_refill == 2 || h->eps_abs_bound < 16.0); // (half the range of T <= 2)
-        if (!four) return T <= (uint32_t)RL_TMAX ? "more than 2048 individuals per compute unit need the second form of the streaming workgroups on one rank (option refill, |eps| < 32)"
-                                                  : "more individuals than the compute units hold (4096 each)";
+        const bool four = T <= (uint32_t)RL_TMAX && h->nranks <= 1 && pl.refill == 2 && (h->res_refill == 2 || h->eps_abs_bound < 16.0); // (half the range of T <= 2)
+        if (!four) return refuse(T <= (uint32_t)RL_TMAX ? "more than 2048 individuals per compute unit need the second form of the streaming workgroups on one rank (option refill, |eps| < 32)"
+                                                       : "more individuals than the compute units hold (4096 each)");
         T = (uint32_t)RL_TMAX;
     }
-    if ((h->stride & 1023u) || (uint64_t)h->M * (h->stride >> 10) >= (1ull << 32)) return "a shard's BED columns are addressed in 32 bits of KiB";
-    pl->T = (int)T;
-    pl->W = (ntile + T - 1) / T;
-    uint32_t B = h->window ? h->window : (uint32_t)RS_BMAX;
-    while (B * T > 512u) B >>= 1;
-    pl->B = B;
-    pl->ok = true;
-    return nullptr;
+    if ((h->stride & 1023u) || (uint64_t)h->M * (h->stride >> 10) >= (1ull << 32)) return refuse("a shard's BED columns are addressed in 32 bits of KiB");
+    pl.T = (int)T;
+    pl.W = (ntile + T - 1) / T;
+    pl.B = h->window ? h->window : (uint32_t)RS_BMAX;
+    while (pl.B * T > 512u) pl.B >>= 1;
+    // the walker: option walker; auto takes the second where it applies -- every marker takes a uniform, the mixture tables and the
+    // tabulated bound fit its LDS, one rank or option walker2_ranks
+    const bool w2_ok = h->res_all_ada && h->G * h->K <= HT_LDS && h->G <= RS_FG && (h->nranks <= 1 || h->res_walker2_ranks);
+    pl.walker = w2_ok ? (h->res_walker == 1 ? 1 : 2) : (h->res_walker == 2 ? 0 : 1);
+    pl.pivots = (h->nranks > 1 || h->any_missing || pl.refill == 2) ? 0 : h->res_pivots; // (the pivot terms have no cross-rank exchange and no four-term form)
+    pl.wend_mask = (pl.walker == 2 && pl.B >= 32u && h->res_wend) ? 15u : 0u;
+    pl.streamer_lds = pl.refill == 2 ? rl_streamer_lds(pl.B, pl.T) : h->any_missing ? rs_streamer_lds_miss(pl.B, pl.T) : rs_streamer_lds(pl.B, pl.T);
+    pl.lds = std::max(pl.streamer_lds, pl.walker == 2 ? rs_walker2_lds(pl.B) : rs_walker_lds(pl.B));
+    const int form = pl.refill == 2 ? (pl.T == RL_TMAX ? 4 : 1 + pl.T) : pl.T - 1;
+    pl.slot = 4 * form + (h->debug_timing ? 2 : 0) + (h->any_missing ? 1 : 0); // (missing calls: the build that keeps s2 per column and the four-term Gram sums)
+    pl.kern = RES_BUILDS[pl.slot];
+    pl.resident = true;
+    return pl;
 }
 
-// the streaming workgroups' form of this handle's resident sweeps (option refill; env HGIBBS_REFILL for handles that do not set it)
-static int resident_refill(const hgibbs_ctx* h)
+// the plan's kernel with its LDS opt-in made on this handle's device (per handle: the attribute belongs to the function ON A DEVICE)
+static int res_opt_in(hgibbs_ctx* h, const SweepPlan& pl)
 {
-    static const int env_refill = std::getenv("HGIBBS_REFILL") ? std::atoi(std::getenv("HGIBBS_REFILL")) : 0;
-    const int want = h->res_refill ? h->res_refill : env_refill;
-    if (want == 0 && h->res_pivots) return 1; // (predicted pivots -- off by default -- take their Gram terms in the first form's refill only)
-    // the second form holds eps as round(eps 2^44) in seven signed digits: |eps| < 64 (RL_EX, hg_streamer2.hip.h).  Left to itself the
-    // library takes the first form for a sweep that starts with a residual beyond 32 (or with no bound at all); asked for by option, the
-    // kernel's own check refuses such a sweep (error 5)
-    if (want == 0 && !(h->eps_abs_bound < 32.0)) return 1;
-    return want == 1 ? 1 : 2;
-}
-static size_t resident_streamer_lds(const hgibbs_ctx* h, const ResPlan& pl)
-{
-    if (resident_refill(h) == 2 || pl.T == RL_TMAX) return rl_streamer_lds(pl.B, pl.T);
-    return h->any_missing ? rs_streamer_lds_miss(pl.B, pl.T) : rs_streamer_lds(pl.B, pl.T);
-}
-
-// the resident kernel of a plan (T tiles per workgroup, stage clocks, missing-call build), with its LDS opt-in made on this handle's device
-static int resident_kernel(hgibbs_ctx* h, const ResPlan& pl, void (**out)(ResParams, const ResParams*))
-{
-    void (*kern)(ResParams, const ResParams*) = nullptr;
-    const bool dbg = h->debug_timing;
-    const bool miss = h->any_missing; // the build that keeps s2 per column and the four-term Gram sums
-    const bool limb = resident_refill(h) == 2 || pl.T == RL_TMAX;
-    if (limb) {
-        switch (pl.T) {
-        case 4: kern = miss ? (dbg ? k_sweep_limb4<1, 1> : k_sweep_limb4<0, 1>) : (dbg ? k_sweep_limb4<1, 0> : k_sweep_limb4<0, 0>); break;
-        case 1: kern = miss ? (dbg ? k_sweep_limb<1, 1, 1> : k_sweep_limb<1, 0, 1>) : (dbg ? k_sweep_limb<1, 1, 0> : k_sweep_limb<1, 0, 0>); break;
-        default: kern = miss ? (dbg ? k_sweep_limb<2, 1, 1> : k_sweep_limb<2, 0, 1>) : (dbg ? k_sweep_limb<2, 1, 0> : k_sweep_limb<2, 0, 0>); break;
-        }
-    } else {
-        switch (pl.T) {
-        case 1: kern = miss ? (dbg ? k_sweep_resident<1, 1, 1> : k_sweep_resident<1, 0, 1>) : (dbg ? k_sweep_resident<1, 1, 0> : k_sweep_resident<1, 0, 0>); break;
-        default: kern = miss ? (dbg ? k_sweep_resident<2, 1, 1> : k_sweep_resident<2, 0, 1>) : (dbg ? k_sweep_resident<2, 1, 0> : k_sweep_resident<2, 0, 0>); break;
-        }
+    if (!h->res_attr_set[pl.slot]) {
+        HIP_TRY(hipFuncSetAttribute((const void*)pl.kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        h->res_attr_set[pl.slot] = true;
     }
-    const int ai = (pl.T == RL_TMAX ? 16 : (limb ? 8 : 0) + (pl.T == 1 ? 0 : 1) * 4) + (dbg ? 2 : 0) + (miss ? 1 : 0);
-    if (!h->res_attr_set[ai]) { // (per handle: the attribute belongs to the function ON A DEVICE)
-        HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        h->res_attr_set[ai] = true;
-    }
-    *out = kern;
     return 0;
+}
+
+// the fields both engines' parameters share: BED, sweep order and metadata, effects, hyper tables, generator, Ziggurat tables
+template <class P>
+static void fill_sweep_common(const hgibbs_ctx* h, P& p, double sigmaE, double eps_sum)
+{
+    const int GK = h->G * h->K;
+    p.bed = h->bed;
+    p.stride = h->stride;
+    p.n_pad = h->n_pad;
+    p.n_local = h->n_local;
+    p.M = h->M;
+    p.n_minus_1 = (double)(h->n_global - 1);
+    p.n_total = (double)h->n_global;
+    p.eps_sum = eps_sum;
+    p.order = h->order;
+    p.s_mave = h->s_mave;
+    p.s_mstd = h->s_mstd;
+    p.s_bold = h->s_bold;
+    p.s_ga = h->s_ga;
+    p.beta = h->beta;
+    p.comp = h->comp;
+    p.acum = h->acum;
+    p.cass = h->cass;
+    p.K = h->K;
+    p.GK = GK;
+    p.denom = h->tables;
+    p.logpi = h->tables + (size_t)GK;
+    p.hlog = h->tables + (size_t)2 * GK;
+    p.sdk = h->tables + (size_t)3 * GK;
+    p.i_2sigE = 1.0 / (2.0 * sigmaE);
+    p.mt = h->mt;
+    p.zig = ZigTables{h->zig, h->zig + 129, h->zig + 258, h->zig + 515};
 }
 
 // Several ranks: is this rank's resident grid resident at once, and at the same time as every peer's?  A launch of the sweep kernel that
@@ -1434,10 +1466,9 @@ static int resident_kernel(hgibbs_ctx* h, const ResPlan& pl, void (**out)(ResPar
 // else runs), then one scalar all-reduce: the ranks run the resident engine only if every rank says yes.  Asked once per grid size.  (One
 // rank finds out by itself, inside the sweep's own launch: hgibbs_sweep falls back then.)  Returns non-zero when some rank's grid is not
 // resident -- e.g. ranks that share one device and whose kernels the device runs one after the other.
-static int resident_probe(hgibbs_ctx* h, const ResPlan& pl)
+static int resident_probe(hgibbs_ctx* h, const SweepPlan& pl)
 {
-    void (*kern)(ResParams, const ResParams*) = nullptr;
-    if (resident_kernel(h, pl, &kern)) return 1;
+    if (res_opt_in(h, pl)) return 1;
     ResParams p{};
     p.W = pl.W;
     p.B = pl.B;
@@ -1451,9 +1482,10 @@ static int resident_probe(hgibbs_ctx* h, const ResPlan& pl)
     p.rank = h->nranks > 1 ? h->rank : 0;
     for (int r = 0; r < RX_MAXR; ++r) p.mbox[r] = (h->nranks > 1 && r < h->nranks) ? (unsigned char*)h->peer_base[r] + MBOX_RES_OFF : nullptr;
     p.sweep_id = ++h->res_probe_id; // (the ranks probe alike: the handshake's words of an earlier probe never match)
-    const size_t lds = std::max(resident_streamer_lds(h, pl), std::max(rs_walker_lds(pl.B), rs_walker2_lds(pl.B)));
+    // (the probe is asked once per grid size, and the walker may change from one sweep to the next: room for either walker)
+    const size_t lds = std::max(pl.streamer_lds, std::max(rs_walker_lds(pl.B), rs_walker2_lds(pl.B)));
     if (hipMemsetAsync(h->res_progress, 0, 16 * sizeof(unsigned long long), h->stream) != hipSuccess || hipMemsetAsync(h->res_state, 0, sizeof(ResState), h->stream) != hipSuccess) return 1;
-    kern<<<dim3(pl.W + 1), RS_BLOCK, lds, h->stream>>>(p, h->res_params);
+    pl.kern<<<dim3(pl.W + 1), RS_BLOCK, lds, h->stream>>>(p, h->res_params);
     if (hipGetLastError() != hipSuccess) return 1;
     if (hipMemcpyAsync(h->res_state_host, h->res_state, sizeof(ResState), hipMemcpyDeviceToHost, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) return 1;
     h->scratch_host[0] = h->res_state_host->error ? 1.0 : 0.0;
@@ -1468,41 +1500,15 @@ static int resident_probe(hgibbs_ctx* h, const ResPlan& pl)
     return 0;
 }
 
-static int sweep_resident(hgibbs_ctx* h, const ResPlan& pl, double sigmaE, hgibbs_rng_state* rng, int32_t* cass_host, uint64_t* nnz_updates)
+// r0: (sum, sum of squares) of eps over all individuals at sweep start (hgibbs_sweep's opening reduction)
+static int sweep_resident(hgibbs_ctx* h, const SweepPlan& pl, const double r0[2], double sigmaE, hgibbs_rng_state* rng, int32_t* cass_host, uint64_t* nnz_updates)
 {
-    const int G = h->G, K = h->K;
+    if (!pl.walker) return fail("hgibbs_sweep: the second walker does not apply (frozen markers, more than %d groups or %d table entries, or several ranks with walker2_ranks = 0)", RS_FG, HT_LDS);
     static const bool timing = std::getenv("HGIBBS_TIMING") != nullptr;
     const auto t_0 = std::chrono::steady_clock::now();
-    double r0[2];
-    if (reduce_eps_all(h, r0)) return 1; // (sum, sum of squares) over all individuals
     ResParams p{};
-    p.bed = h->bed;
-    p.stride = h->stride;
+    fill_sweep_common(h, p, sigmaE, r0[0]); // eps_sum: s2 of every column without missing calls, see sweep_batch
     p.eps = h->eps[h->eps_cur];
-    p.n_pad = h->n_pad;
-    p.n_local = h->n_local;
-    p.M = h->M;
-    p.n_minus_1 = (double)(h->n_global - 1);
-    p.n_total = (double)h->n_global;
-    p.eps_sum = r0[0]; // s2 of every column (none has missing calls here), see hgibbs_sweep
-    p.order = h->order;
-    p.s_mave = h->s_mave;
-    p.s_mstd = h->s_mstd;
-    p.s_bold = h->s_bold;
-    p.s_ga = h->s_ga;
-    p.beta = h->beta;
-    p.comp = h->comp;
-    p.acum = h->acum;
-    p.cass = h->cass;
-    p.K = K;
-    p.GK = G * K;
-    p.denom = h->tables;
-    p.logpi = h->tables + (size_t)G * K;
-    p.hlog = h->tables + (size_t)2 * G * K;
-    p.sdk = h->tables + (size_t)3 * G * K;
-    p.i_2sigE = 1.0 / (2.0 * sigmaE);
-    p.mt = h->mt;
-    p.zig = ZigTables{h->zig, h->zig + 129, h->zig + 258, h->zig + 515};
     p.rng_idx = rng->idx;
     p.W = pl.W;
     p.B = pl.B;
@@ -1533,24 +1539,16 @@ static int sweep_resident(hgibbs_ctx* h, const ResPlan& pl, double sigmaE, hgibb
     p.timeout = (unsigned long long)(h->res_timeout_s * 1e8);
     p.rdv_timeout = (unsigned long long)(std::min(h->res_timeout_s, 0.1) * 1e8); // the grid's workgroups start within microseconds of each other -- or not at all
     p.dbg = h->debug_timing ? 1 : 0;
-    p.pivots = (h->nranks > 1 || h->any_missing || resident_refill(h) == 2 || pl.T == RL_TMAX) ? 0 : h->res_pivots; // (the pivot terms have no cross-rank exchange and no four-term form)
+    p.pivots = pl.pivots;
     p.nranks = h->nranks > 1 ? h->nranks : 1;
     p.rank = h->nranks > 1 ? h->rank : 0;
     for (int r = 0; r < RX_MAXR; ++r) p.mbox[r] = (h->nranks > 1 && r < h->nranks) ? (unsigned char*)h->peer_base[r] + MBOX_RES_OFF : nullptr;
     p.all_ada = h->res_all_ada ? 1 : 0;
-    {
-        // the second walker: every marker takes a uniform, the mixture tables and the tabulated bound fit its LDS, one rank
-        const bool w2_ok = h->res_all_ada && p.GK <= HT_LDS && G <= RS_FG && (p.nranks == 1 || h->res_walker2_ranks);
-        if (h->res_walker == 2 && !w2_ok) return fail("hgibbs_sweep: the second walker does not apply (frozen markers, more than %d groups or %d table entries, or several ranks with walker2_ranks = 0)", RS_FG, HT_LDS);
-        static const int env_walker = std::getenv("HGIBBS_WALKER") ? std::atoi(std::getenv("HGIBBS_WALKER")) : 0; // (test runs: the default walker of handles that do not set the option)
-        const int want = h->res_walker ? h->res_walker : env_walker;
-        p.walker = (want != 1 && w2_ok) ? 2 : 1; // (auto: the second walker where it applies)
-    }
+    p.walker = pl.walker;
     p.pred = h->pred;
-    p.tune = h->res_tune;
     p.early_advance = p.nranks > 1 ? 0 : h->res_early; // (several ranks: the replicas must send the same messages -- an advance that depends on when the dots arrive would not be)
     p.announce = h->res_announce;
-    p.wend_mask = (p.walker == 2 && pl.B >= 32u && h->res_wend) ? 15u : 0u;
+    p.wend_mask = pl.wend_mask;
     {
         // the predicted events of this sweep, in sweep order (read by the streaming workgroups and by the walker)
         const uint32_t nchunk = (h->M + PRED_CHUNK - 1) / PRED_CHUNK;
@@ -1567,22 +1565,20 @@ static int sweep_resident(hgibbs_ctx* h, const ResPlan& pl, double sigmaE, hgibb
     HIP_TRY(hipMemsetAsync(h->res_acc, 0, RES_ACC_BYTES, h->stream));
     HIP_TRY(hipMemsetAsync(h->res_msg, 0, RS_MSG * sizeof(ResMsg), h->stream));
     HIP_TRY(hipMemsetAsync(h->res_state, 0, sizeof(ResState), h->stream));
-    const size_t lds = std::max(resident_streamer_lds(h, pl), p.walker == 2 ? rs_walker2_lds(pl.B) : rs_walker_lds(pl.B));
-    void (*kern)(ResParams, const ResParams*) = nullptr;
-    if (resident_kernel(h, pl, &kern)) return 1;
+    if (res_opt_in(h, pl)) return 1;
     {
         // every workgroup of the grid waits for the others: all of them must be resident at once
         int per_cu = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, RS_BLOCK, lds));
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pl.kern, RS_BLOCK, pl.lds));
         if (per_cu < 1 || (uint64_t)per_cu * (uint64_t)h->num_cu < (uint64_t)pl.W + 1)
             return fail("hgibbs_sweep: the resident grid of %u workgroups does not fit the device (%d per compute unit, %d units)", pl.W + 1, per_cu, h->num_cu);
     }
     if (std::getenv("HGIBBS_DEBUG"))
-        std::fprintf(stderr, "[hgibbs] resident sweep: T %d, %u streaming workgroups, window %u, LDS %zu B, fixed-point scale 2^%d\n", pl.T, pl.W, pl.B, lds, (int)std::log2(p.fx_scale));
+        std::fprintf(stderr, "[hgibbs] resident sweep: T %d, %u streaming workgroups, window %u, LDS %zu B, fixed-point scale 2^%d\n", pl.T, pl.W, pl.B, pl.lds, (int)std::log2(p.fx_scale));
     HIP_TRY(hipEventRecord(h->ev0, h->stream));
     *h->res_params_host = p;
     HIP_TRY(hipMemcpyAsync(h->res_params, h->res_params_host, sizeof(ResParams), hipMemcpyHostToDevice, h->stream));
-    kern<<<dim3(pl.W + 1), RS_BLOCK, lds, h->stream>>>(p, h->res_params);
+    pl.kern<<<dim3(pl.W + 1), RS_BLOCK, pl.lds, h->stream>>>(p, h->res_params);
     HIP_TRY(hipGetLastError());
     k_res_finish<<<dim3((h->M + 255u) / 256u), 256, 0, h->stream>>>(p); // numerators -> Acum, components and cass of the markers that were no event
     HIP_TRY(hipGetLastError());
@@ -1651,7 +1647,7 @@ static int sweep_resident(hgibbs_ctx* h, const ResPlan& pl, double sigmaE, hgibb
     HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
     rng->idx = st.rng_idx;
     HIP_TRY(hipMemcpy(rng->x, h->mt, MT_N * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (cass_host) HIP_TRY(hipMemcpy(cass_host, h->cass, (size_t)G * K * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (cass_host) HIP_TRY(hipMemcpy(cass_host, h->cass, (size_t)h->G * h->K * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (nnz_updates) *nnz_updates = st.nnz;
     hgibbs_sweep_stats& s = h->stats;
     s = hgibbs_sweep_stats{};
@@ -1664,8 +1660,8 @@ static int sweep_resident(hgibbs_ctx* h, const ResPlan& pl, double sigmaE, hgibb
     s.streamed_columns = h->M;
     s.tiles_per_workgroup_min = s.tiles_per_workgroup_max = (uint32_t)pl.T;
     s.engine = 2;
-    s.walker = (uint32_t)p.walker;
-    s.refill = (uint32_t)(pl.T == RL_TMAX ? 2 : resident_refill(h));
+    s.walker = (uint32_t)pl.walker;
+    s.refill = (uint32_t)pl.refill;
     s.rounds = st.rounds;
     s.events = st.events;
     s.advances = st.advances;
@@ -1688,54 +1684,38 @@ static int sweep_resident(hgibbs_ctx* h, const ResPlan& pl, double sigmaE, hgibb
     return 0;
 }
 
-extern "C" {
+// the batch builds k_sweep_batch<CPG, SEG, MG, NOMISS, DBG> by their parameters (columns per group, tier, missing-call Gram build, no
+// missing call in the data, stage clocks), with the draw launch k_sweep_draw<SEG, MG> of the split path.  NOMISS and the stage clocks
+// exist at four columns per group only.
+struct BatchBuild {
+    uint32_t cpg;
+    int tier, mg, nomiss, dbg;
+    void (*kern)(SweepParams);
+    void (*draw)(SweepParams);
+};
+static const BatchBuild BATCH_BUILDS[] = {
+    {2, 2, 0, 0, 0, k_sweep_batch<2, 2, 0>, k_sweep_draw<2, 0>},
+    {4, 2, 0, 0, 0, k_sweep_batch<4, 2, 0>, k_sweep_draw<2, 0>},
+    {4, 2, 0, 1, 0, k_sweep_batch<4, 2, 0, 1>, k_sweep_draw<2, 0>},
+    {4, 2, 0, 0, 1, k_sweep_batch<4, 2, 0, 0, 1>, k_sweep_draw<2, 0>},
+    {4, 2, 0, 1, 1, k_sweep_batch<4, 2, 0, 1, 1>, k_sweep_draw<2, 0>},
+    {8, 2, 0, 0, 0, k_sweep_batch<8, 2, 0>, k_sweep_draw<2, 0>},
+    {16, 2, 0, 0, 0, k_sweep_batch<16, 2, 0>, k_sweep_draw<2, 0>},
+    {4, 4, 0, 0, 0, k_sweep_batch<4, 4, 0>, k_sweep_draw<4, 0>},
+    {4, 4, 0, 1, 0, k_sweep_batch<4, 4, 0, 1>, k_sweep_draw<4, 0>},
+    {4, 4, 0, 0, 1, k_sweep_batch<4, 4, 0, 0, 1>, k_sweep_draw<4, 0>},
+    {4, 4, 0, 1, 1, k_sweep_batch<4, 4, 0, 1, 1>, k_sweep_draw<4, 0>},
+    {8, 4, 0, 0, 0, k_sweep_batch<8, 4, 0>, k_sweep_draw<4, 0>},
+    {4, 2, 1, 0, 0, k_sweep_batch<4, 2, 1>, k_sweep_draw<2, 1>},
+    {4, 2, 1, 0, 1, k_sweep_batch<4, 2, 1, 0, 1>, k_sweep_draw<2, 1>},
+    {8, 2, 1, 0, 0, k_sweep_batch<8, 2, 1>, k_sweep_draw<2, 1>},
+};
 
-int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const double* sigmaG_host, const double* estPi_host,
-                 const uint8_t* adaV_host, hgibbs_rng_state* rng, int32_t* cass_host, uint64_t* nnz_updates)
+// the batch engine (hg_sweep.hip.h): chunks of launches, each accepting a batch of markers; r0 as for sweep_resident
+static int sweep_batch(hgibbs_ctx* h, const double r0[2], double sigmaE, hgibbs_rng_state* rng, int32_t* cass_host, uint64_t* nnz_updates)
 {
-    if (!h || !h->bed) return fail("hgibbs_sweep: no data loaded");
-    if (h->res_dead) return fail("hgibbs_sweep: a resident kernel of this handle never came back: the handle cannot be used any more");
-    if (h->G < 1) return fail("hgibbs_sweep: model not set");
-    if (!order_host || !sigmaG_host || !estPi_host || !adaV_host || !rng) return fail("hgibbs_sweep: null argument");
-    const auto t_prep0 = std::chrono::steady_clock::now();
-    HIP_TRY(hipSetDevice(h->device));
-    if (compute_stats(h)) return 1;
     const int G = h->G, K = h->K;
     const uint32_t M = h->M;
-    for (uint32_t i = 0; i < M; ++i)
-        if (order_host[i] < 0 || (uint32_t)order_host[i] >= M) return fail("hgibbs_sweep: order[%u]=%d outside [0,%u)", i, order_host[i], M);
-    if (rng->idx > (uint32_t)MT_N) return fail("hgibbs_sweep: rng idx %u > 624", rng->idx);
-
-    // per-sweep hyper tables (the marker-independent factors of src/BayesRRm.cpp:1721-1723,1750,1875,1901)
-    const double dNm1 = (double)(h->n_global - 1);
-    std::vector<double> tab((size_t)4 * G * K, 0.0);
-    double* denom = tab.data();
-    double* logpi = denom + (size_t)G * K;
-    double* hlog = logpi + (size_t)G * K;
-    double* sdk = hlog + (size_t)G * K;
-    for (int g = 0; g < G; ++g) {
-        const double sigE_G = sigmaE / sigmaG_host[g];
-        const double sigG_E = sigmaG_host[g] / sigmaE;
-        for (int k = 0; k < K; ++k) {
-            logpi[g * K + k] = log(estPi_host[g * K + k]);
-            if (k >= 1) {
-                denom[g * K + k] = dNm1 + sigE_G * h->cVaI[g * K + k];
-                hlog[g * K + k] = 0.5 * log(sigG_E * dNm1 * h->cVa[g * K + k] + 1.0);
-                sdk[g * K + k] = sqrt(sigmaE / denom[g * K + k]);
-            }
-        }
-    }
-    HIP_TRY(hipMemcpyAsync(h->tables, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->order, order_host, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->adaV, adaV_host, (size_t)M, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->mt, rng->x, MT_N * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemsetAsync(h->cass, 0, (size_t)G * K * sizeof(int32_t), h->stream));
-    HIP_TRY(hipMemsetAsync(h->ticket, 0, (16 + MAX_GROUPS + 256) * sizeof(uint32_t), h->stream));
-    HIP_TRY(hipMemsetAsync(h->aticket, 0, (AHEAD_MAX / 2 + 4) * sizeof(uint32_t), h->stream));
-    k_gather_meta<<<(M + 255) / 256, 256, 0, h->stream>>>(h->order, h->mave, h->mstd, h->beta, h->groups, h->adaV, h->counts, h->s_mave, h->s_mstd,
-                                                       h->s_bold, h->s_ga, M);
-    HIP_TRY(hipGetLastError());
-
     const uint32_t cpg = h->cols_per_group;
     const uint32_t batch = h->batch ? h->batch : ((h->n_local >= 20000u || h->nranks > 1) ? 256u : 128u);
     const uint32_t ngroups = (batch + cpg - 1) / cpg;
@@ -1753,94 +1733,19 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
     *cnt_host = SweepCounters{};
     cnt_host->tiles_min = 0xffffffffu;
     HIP_TRY(hipMemcpyAsync(h->desc, h->desc_host, sizeof(SweepDesc) + sizeof(SweepCounters), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream)); // staging buffers are on the host stack / pageable
-
-    // which engine runs this sweep
-    ResPlan plan{};
-    {
-        const char* why = resident_plan(h, &plan);
-        if (h->engine == 1 || (h->engine == 0 && h->engine_pinned)) plan.ok = false;
-        if (h->engine == 0 && h->res_not_resident && plan.ok) {
-            plan.ok = false;
-            why = "an earlier resident grid was not resident at once (the device is shared)";
-        }
-        if (h->nranks > 1) {
-            // the ranks run ONE engine: the resident one only if every rank can (a rank with a larger shard, another option or no
-            // mailbox would otherwise wait for peers that are in the other engine's exchange)
-            h->scratch_host[0] = plan.ok ? 0.0 : 1.0;
-            HIP_TRY(hipMemcpyAsync(h->sums, h->scratch_host, sizeof(double), hipMemcpyHostToDevice, h->stream));
-            if (bulk_allreduce(h, h->sums, 1, 0)) return 1;
-            HIP_TRY(hipMemcpyAsync(h->scratch_host, h->sums, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(hipStreamSynchronize(h->stream));
-            if (h->scratch_host[0] != 0.0) {
-                if (plan.ok) why = "another rank cannot run it";
-                plan.ok = false;
-            }
-            // (every rank has the same answer now) a rank whose grid is not resident at once must be known BEFORE its peers wait for it
-            if (plan.ok && h->res_probed_w != plan.W + 1 && resident_probe(h, plan)) {
-                plan.ok = false;
-                why = "some rank's resident grid is not resident at once (a shared device)";
-            }
-        }
-        if (h->engine == 2 && !plan.ok) return fail("hgibbs_sweep: the resident engine does not apply: %s", why ? why : "the batch engine was asked for by an option");
-        if (std::getenv("HGIBBS_DEBUG"))
-            std::fprintf(stderr, "[hgibbs] engine: %s%s%s\n", plan.ok ? "resident" : "batch", why ? " -- resident refused: " : "", why ? why : "");
-    }
-    if (std::getenv("HGIBBS_TIMING"))
-        std::fprintf(stderr, "[hgibbs] sweep preparation (checks, tables, order / adaV upload, metadata gather) %.3f ms\n",
-                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_prep0).count());
-    h->res_all_ada = std::memchr(adaV_host, 0, (size_t)M) == nullptr;
-    if (plan.ok) {
-        const int rc = sweep_resident(h, plan, sigmaE, rng, cass_host, nnz_updates);
-        // 2: the grid was found partly resident at the kernel's start (a shared device) and NOTHING was touched: with engine = 0 this sweep and
-        // the following ones run on the batch engine (several ranks have agreed on that before the launch: resident_probe)
-        if (rc != 2 || h->engine == 2 || h->nranks > 1) return rc ? 1 : 0;
-        if (std::getenv("HGIBBS_DEBUG")) std::fprintf(stderr, "[hgibbs] engine: the resident grid was not resident at once -- this sweep and the following ones run on the batch engine\n");
-    }
 
     SweepParams p{};
-    p.bed = h->bed;
-    p.stride = h->stride;
+    // s2 = sum_i nm_i eps_i of a column WITHOUT missing calls is the plain sum of eps (src/BayesRRm.cpp:1788 with
+    // every nm_i = 1).  A marker update adds mstd (g_i - mave) nm_i dbeta to eps_i, and mave is the mean of g over the
+    // marker's non-missing calls, so the update's sum over i is zero: the sum of eps is the same before and after
+    // every update of the sweep up to the rounding of the adds (~1e-16 of |eps|, random sign; far below the 1e-9
+    // the dots are held to).  It is therefore reduced once per sweep, in fixed order and over all ranks, instead of
+    // once per launch by the streaming loop.  Columns with missing calls keep their own masked sum per marker.
+    fill_sweep_common(h, p, sigmaE, r0[0]);
     p.eps0 = h->eps[0];
     p.eps1 = h->eps[1];
-    p.n_pad = h->n_pad;
-    p.n_local = h->n_local;
-    p.M = M;
-    p.n_minus_1 = dNm1;
-    p.n_total = (double)h->n_global;
-    double eps_sum_start = 0.0;
-    {
-        // s2 = sum_i nm_i eps_i of a column WITHOUT missing calls is the plain sum of eps (src/BayesRRm.cpp:1788 with
-        // every nm_i = 1).  A marker update adds mstd (g_i - mave) nm_i dbeta to eps_i, and mave is the mean of g over the
-        // marker's non-missing calls, so the update's sum over i is zero: the sum of eps is the same before and after
-        // every update of the sweep up to the rounding of the adds (~1e-16 of |eps|, random sign; far below the 1e-9
-        // the dots are held to).  It is therefore reduced once per sweep, in fixed order and over all ranks, instead of
-        // once per launch by the streaming loop.  Columns with missing calls keep their own masked sum per marker.
-        double r[2];
-        if (reduce_eps_all(h, r)) return 1;
-        p.eps_sum = r[0];
-        eps_sum_start = r[0];
-    }
     p.gram = h->gram ? 1 : 0;
-    p.order = h->order;
-    p.beta = h->beta;
-    p.comp = h->comp;
-    p.acum = h->acum;
-    p.cass = h->cass;
-    p.K = K;
-    p.GK = G * K;
-    p.s_mave = h->s_mave;
-    p.s_mstd = h->s_mstd;
-    p.s_bold = h->s_bold;
-    p.s_ga = h->s_ga;
     p.dbg = (h->debug_timing && h->cols_per_group == 4) ? h->dbg : nullptr;
-    p.denom = h->tables;
-    p.logpi = h->tables + (size_t)G * K;
-    p.hlog = h->tables + (size_t)2 * G * K;
-    p.sdk = h->tables + (size_t)3 * G * K;
-    p.i_2sigE = 1.0 / (2.0 * sigmaE);
-    p.mt = h->mt;
-    p.zig = ZigTables{h->zig, h->zig + 129, h->zig + 258, h->zig + 515};
     p.desc = h->desc;
     p.counters = reinterpret_cast<SweepCounters*>(h->desc + 1);
     p.partials = h->partials;
@@ -1903,22 +1808,13 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
         return fail("hgibbs_sweep: %u groups of %d partial rows exceed the partial buffer", groups_max, group_rows((int)cpg, tier, mg ? 1 : 0));
     uint64_t total_launches = 0;
     // the build of the kernel this sweep runs
-    void (*kern)(SweepParams) = nullptr;
-    const bool nomiss = !h->any_missing;
+    const bool nomiss = !h->any_missing && cpg == 4;
     const bool dbg = h->debug_timing && cpg == 4; // stage timestamps exist in the builds of the default column count only
-    if (mg) {
-        kern = (cpg == 4) ? (dbg ? k_sweep_batch<4, 2, 1, 0, 1> : k_sweep_batch<4, 2, 1>) : k_sweep_batch<8, 2, 1>;
-    } else if (tier == 4) {
-        if (cpg == 4) kern = nomiss ? (dbg ? k_sweep_batch<4, 4, 0, 1, 1> : k_sweep_batch<4, 4, 0, 1>) : (dbg ? k_sweep_batch<4, 4, 0, 0, 1> : k_sweep_batch<4, 4, 0>);
-        else kern = k_sweep_batch<8, 4, 0>;
-    } else {
-        switch (cpg) {
-        case 2: kern = k_sweep_batch<2, 2, 0>; break;
-        case 4: kern = nomiss ? (dbg ? k_sweep_batch<4, 2, 0, 1, 1> : k_sweep_batch<4, 2, 0, 1>) : (dbg ? k_sweep_batch<4, 2, 0, 0, 1> : k_sweep_batch<4, 2, 0>); break;
-        case 8: kern = k_sweep_batch<8, 2, 0>; break;
-        default: kern = k_sweep_batch<16, 2, 0>; break;
-        }
-    }
+    const BatchBuild* build = nullptr;
+    for (const BatchBuild& b : BATCH_BUILDS)
+        if (b.cpg == cpg && b.tier == tier && b.mg == (mg ? 1 : 0) && b.nomiss == (nomiss ? 1 : 0) && b.dbg == (dbg ? 1 : 0)) build = &b;
+    if (!build) return fail("hgibbs_sweep: no build of the sweep kernel for %u columns per group, tier %d, missing-call Gram %d", cpg, tier, (int)mg);
+    void (*const kern)(SweepParams) = build->kern;
     // the active workgroups of a launch must be co-resident (a second round of workgroups would double the streaming
     // phase): how many fit depends on the build's registers and on this launch's LDS size (K, batch capacity, rows)
     {
@@ -1969,9 +1865,7 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
                 // (hydra's own MPI_Allreduce, say) on a host copy -- a stream round trip per batch, the parity baseline
                 if (h->comm) NCCL_TRY(ncclAllReduce(h->sums, h->sums, nr * MAX_BATCH, ncclDouble, ncclSum, h->comm, h->stream));
                 else if (h->nranks > 1 && bulk_allreduce(h, h->sums, (size_t)nr * MAX_BATCH, 0)) return 1;
-                if (mg) k_sweep_draw<2, 1><<<1, BLOCK, lds, h->stream>>>(p);
-                else if (tier == 4) k_sweep_draw<4, 0><<<1, BLOCK, lds, h->stream>>>(p);
-                else k_sweep_draw<2, 0><<<1, BLOCK, lds, h->stream>>>(p);
+                build->draw<<<1, BLOCK, lds, h->stream>>>(p);
             }
         }
         total_launches += (uint64_t)n;
@@ -2021,9 +1915,108 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
         // how far the updates' roundings have moved it (src/BayesRRm.cpp:331 re-sums eps per marker)
         double r[2];
         if (reduce_eps_all(h, r)) return 1;
-        h->stats.eps_sum_drift = std::fabs(r[0] - eps_sum_start);
+        h->stats.eps_sum_drift = std::fabs(r[0] - r0[0]);
     }
     return 0;
+}
+
+extern "C" {
+
+int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const double* sigmaG_host, const double* estPi_host,
+                 const uint8_t* adaV_host, hgibbs_rng_state* rng, int32_t* cass_host, uint64_t* nnz_updates)
+{
+    if (!h || !h->bed) return fail("hgibbs_sweep: no data loaded");
+    if (h->res_dead) return fail("hgibbs_sweep: a resident kernel of this handle never came back: the handle cannot be used any more");
+    if (h->G < 1) return fail("hgibbs_sweep: model not set");
+    if (!order_host || !sigmaG_host || !estPi_host || !adaV_host || !rng) return fail("hgibbs_sweep: null argument");
+    const auto t_prep0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipSetDevice(h->device));
+    if (compute_stats(h)) return 1;
+    const int G = h->G, K = h->K;
+    const uint32_t M = h->M;
+    for (uint32_t i = 0; i < M; ++i)
+        if (order_host[i] < 0 || (uint32_t)order_host[i] >= M) return fail("hgibbs_sweep: order[%u]=%d outside [0,%u)", i, order_host[i], M);
+    if (rng->idx > (uint32_t)MT_N) return fail("hgibbs_sweep: rng idx %u > 624", rng->idx);
+
+    // per-sweep hyper tables (the marker-independent factors of src/BayesRRm.cpp:1721-1723,1750,1875,1901)
+    const double dNm1 = (double)(h->n_global - 1);
+    std::vector<double> tab((size_t)4 * G * K, 0.0);
+    double* denom = tab.data();
+    double* logpi = denom + (size_t)G * K;
+    double* hlog = logpi + (size_t)G * K;
+    double* sdk = hlog + (size_t)G * K;
+    for (int g = 0; g < G; ++g) {
+        const double sigE_G = sigmaE / sigmaG_host[g];
+        const double sigG_E = sigmaG_host[g] / sigmaE;
+        for (int k = 0; k < K; ++k) {
+            logpi[g * K + k] = log(estPi_host[g * K + k]);
+            if (k >= 1) {
+                denom[g * K + k] = dNm1 + sigE_G * h->cVaI[g * K + k];
+                hlog[g * K + k] = 0.5 * log(sigG_E * dNm1 * h->cVa[g * K + k] + 1.0);
+                sdk[g * K + k] = sqrt(sigmaE / denom[g * K + k]);
+            }
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(h->tables, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->order, order_host, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->adaV, adaV_host, (size_t)M, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->mt, rng->x, MT_N * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemsetAsync(h->cass, 0, (size_t)G * K * sizeof(int32_t), h->stream));
+    HIP_TRY(hipMemsetAsync(h->ticket, 0, (16 + MAX_GROUPS + 256) * sizeof(uint32_t), h->stream));
+    HIP_TRY(hipMemsetAsync(h->aticket, 0, (AHEAD_MAX / 2 + 4) * sizeof(uint32_t), h->stream));
+    k_gather_meta<<<(M + 255) / 256, 256, 0, h->stream>>>(h->order, h->mave, h->mstd, h->beta, h->groups, h->adaV, h->counts, h->s_mave, h->s_mstd,
+                                                       h->s_bold, h->s_ga, M);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(h->stream)); // staging buffers are on the host stack / pageable
+    h->res_all_ada = std::memchr(adaV_host, 0, (size_t)M) == nullptr;
+    if (std::getenv("HGIBBS_TIMING"))
+        std::fprintf(stderr, "[hgibbs] sweep preparation (checks, tables, order / adaV upload, metadata gather) %.3f ms\n",
+                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_prep0).count());
+
+    // (sum, sum of squares) of eps over all individuals at sweep start, for whichever engine runs; it also refreshes the bound on
+    // max |eps| the plan's form of the streaming workgroups depends on
+    double r0[2];
+    if (reduce_eps_all(h, r0)) return 1;
+
+    // which engine runs this sweep
+    SweepPlan plan = plan_sweep(h);
+    {
+        if (h->engine == 1 || (h->engine == 0 && h->engine_pinned)) plan.resident = false;
+        if (h->engine == 0 && h->res_not_resident && plan.resident) {
+            plan.resident = false;
+            plan.why = "an earlier resident grid was not resident at once (the device is shared)";
+        }
+        if (h->nranks > 1) {
+            // the ranks run ONE engine: the resident one only if every rank can (a rank with a larger shard, another option or no
+            // mailbox would otherwise wait for peers that are in the other engine's exchange)
+            h->scratch_host[0] = plan.resident ? 0.0 : 1.0;
+            HIP_TRY(hipMemcpyAsync(h->sums, h->scratch_host, sizeof(double), hipMemcpyHostToDevice, h->stream));
+            if (bulk_allreduce(h, h->sums, 1, 0)) return 1;
+            HIP_TRY(hipMemcpyAsync(h->scratch_host, h->sums, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(hipStreamSynchronize(h->stream));
+            if (h->scratch_host[0] != 0.0) {
+                if (plan.resident) plan.why = "another rank cannot run it";
+                plan.resident = false;
+            }
+            // (every rank has the same answer now) a rank whose grid is not resident at once must be known BEFORE its peers wait for it
+            if (plan.resident && h->res_probed_w != plan.W + 1 && resident_probe(h, plan)) {
+                plan.resident = false;
+                plan.why = "some rank's resident grid is not resident at once (a shared device)";
+            }
+        }
+        if (h->engine == 2 && !plan.resident) return fail("hgibbs_sweep: the resident engine does not apply: %s", plan.why ? plan.why : "the batch engine was asked for by an option");
+        if (std::getenv("HGIBBS_DEBUG"))
+            std::fprintf(stderr, "[hgibbs] engine: %s%s%s\n", plan.resident ? "resident" : "batch", plan.why ? " -- resident refused: " : "", plan.why ? plan.why : "");
+    }
+    if (plan.resident) {
+        const int rc = sweep_resident(h, plan, r0, sigmaE, rng, cass_host, nnz_updates);
+        // 2: the grid was found partly resident at the kernel's start (a shared device) and NOTHING was touched: with engine = 0 this sweep and
+        // the following ones run on the batch engine (several ranks have agreed on that before the launch: resident_probe)
+        if (rc != 2 || h->engine == 2 || h->nranks > 1) return rc ? 1 : 0;
+        if (std::getenv("HGIBBS_DEBUG")) std::fprintf(stderr, "[hgibbs] engine: the resident grid was not resident at once -- this sweep and the following ones run on the batch engine\n");
+        if (reduce_eps_all(h, r0)) return 1;
+    }
+    return sweep_batch(h, r0, sigmaE, rng, cass_host, nnz_updates);
 }
 
 } // extern "C"

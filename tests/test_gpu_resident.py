@@ -280,6 +280,122 @@ def test_random_configurations_match_the_oracle(oracle, case):
                   missing_rate=0.03 if missing_cols > 0.0 else 0.0, missing_cols=missing_cols)
 
 
+def _direct_sweep(bed, N, y, opts, adaV=None, eps=None, seed=3):
+    """One sweep through hgibbs_sweep on a fresh handle, without a chain around it: Chain's default mixture, the standardised phenotype
+    (or eps) as the residual, every marker adaptive unless adaV says otherwise.  Returns the handle and the generator."""
+    dev = capi.Device(0)
+    dev.load_bed(bed, N)
+    for k, v in opts.items():
+        dev.set_option(k, v)
+    M = dev.M
+    mS = np.array([[0.0, 1e-4, 1e-3, 1e-2]])
+    dev.set_model(None, mS, np.where(mS > 0.0, 1.0 / np.maximum(mS, 1e-300), 0.0))
+    if eps is None:
+        eps = (y - y.mean()) * np.sqrt((N - 1) / np.sum((y - y.mean()) ** 2))
+    dev.set_residual(eps)
+    rng = capi.RngState()
+    for i, w in enumerate(np.random.default_rng(seed).integers(0, 1 << 32, size=624, dtype=np.uint64)):
+        rng.x[i] = int(w)
+    rng.idx = 624
+    dev.sweep(np.random.default_rng(seed + 1).permutation(M).astype(np.int32), 0.5, np.array([0.1]), np.array([[0.5, 0.3, 0.15, 0.05]]),
+              np.ones(M, dtype=np.uint8) if adaV is None else adaV, rng)
+    return dev, rng
+
+
+# What the sweep plan decides for a configuration (hgibbs.hip: plan_sweep), as sweep_stats() reports it: engine (1 batch, 2 resident),
+# walker, refill form, tiles per streaming workgroup, whether predicted pivots were taken.  Resident rows run against the oracle
+# (run_vs_oracle, the engine option as given); T None: the batch engine's own tile count, not the plan's; walker and refill stay 0 on a
+# fresh handle whose sweeps run on the batch engine.  The second walker's pivots counter also counts announced events, so the rows
+# that check the pivots rule turn announcements off (option announce; they are off anyway while predicted pivots are taken).
+PLAN_TABLE = [
+    # id, M, N, options, case, expected (engine, walker, refill, T, pivots > 0) or "refused"
+    ("default", 300, 9001, {"engine": 0}, {}, (2, 2, 2, 1, True)),
+    ("two_tiles", 400, 8000, {"res_cus": 5}, {}, (2, 2, 2, 2, True)),
+    ("four_tiles", 400, 8000, {"res_cus": 3}, {}, (2, 2, 2, 4, True)),
+    ("four_tiles_first_form_auto", 400, 8000, {"engine": 0, "res_cus": 3, "refill": 1}, {}, (1, 0, 0, None, False)),
+    ("four_tiles_first_form_resident", 400, 8000, {"engine": 2, "res_cus": 3, "refill": 1}, {}, "refused"),
+    ("frozen_marker", 300, 9001, {"engine": 0}, {"frozen": True}, (2, 1, 2, 1, False)),
+    ("five_groups", 400, 3000, {}, {"G": 5}, (2, 1, 2, 1, False)),
+    ("mixture_beyond_256", 400, 3000, {"engine": 0}, {"G": 65}, (1, 0, 0, None, False)),
+    ("pivots", 500, 5000, {"pivots": 1, "announce": 0}, {"causal_frac": 0.2}, (2, 2, 1, 1, True)),
+    ("pivots_missing_calls", 500, 5000, {"pivots": 1, "announce": 0}, {"causal_frac": 0.2, "missing_rate": 0.02}, (2, 2, 1, 1, False)),
+    ("batch_option", 300, 9001, {"engine": 0, "cols_per_group": 4}, {}, (1, 0, 0, None, False)),
+    ("outlier_residual", 200, 9001, {}, {"outlier": True}, (2, 2, 1, 1, True)),
+]
+
+
+def _device_chain(bed, N, y, opts, groups=None, mS=None):
+    dev = capi.Device(0)
+    dev.load_bed(bed, N)
+    for k, v in opts.items():
+        dev.set_option(k, v)
+    return dev, capi.Chain(dev, y, mS=mS, groups=groups, seed=1222, shuffle=1)
+
+
+def _chain_vs_oracle(oracle, bed, N, y, opts, groups=None, mS=None, iters=2):
+    """A chain on whichever engine the options give, against the oracle (components exact, beta within tolerance)."""
+    ref = orc.Chain(oracle, bed, N, y, groups=groups, mS=mS, seed=1222, shuffle=1)
+    dev, ch = _device_chain(bed, N, y, opts, groups, mS)
+    for _ in range(iters):
+        ref.iterate()
+        ch.iterate()
+    beta, comp, _ = dev.get_beta()
+    assert np.array_equal(comp, ref.arr("components")) and close(beta, ref.arr("beta"))
+    return dev
+
+
+@pytest.mark.parametrize("M,N,opts,case,expect", [r[1:] for r in PLAN_TABLE], ids=[r[0] for r in PLAN_TABLE])
+def test_the_plan_of_a_sweep(oracle, M, N, opts, case, expect):
+    kw = {k: case[k] for k in ("causal_frac", "missing_rate") if k in case}
+    groups = mS = None
+    if "G" in case:
+        G = case["G"]
+        groups = (np.arange(M) % G).astype(np.int32)
+        mS = np.tile(np.array([[0.0, 1e-4, 1e-3, 1e-2]]), (G, 1))
+    bed, y = make_case(M, N, seed=5 if case.get("outlier") else M + N, **kw)
+    if case.get("frozen"):  # a zero in adaV: that marker takes no draw (a chain gets there when a group's variance falls to 0)
+        adaV = np.ones(M, dtype=np.uint8)
+        adaV[5] = 0
+        dev, _ = _direct_sweep(bed, N, y, opts, adaV=adaV)
+    elif case.get("outlier"):  # test_a_residual_beyond_the_digits_range's residual
+        y = y.copy()
+        y[7] += 1e6 * np.std(y)
+        dev = _chain_vs_oracle(oracle, bed, N, y, opts)
+    elif expect == "refused":
+        _, ch = _device_chain(bed, N, y, opts)
+        with pytest.raises(capi.HgError, match="resident engine does not apply"):
+            ch.iterate()
+        return
+    elif expect[0] == 2:
+        iters = 3 if opts.get("pivots") else 2  # (the first sweep starts from beta = 0: no predicted events)
+        _, _, dev = run_vs_oracle(oracle, M, N, iters=iters, groups=groups, mS=mS, opts=opts, **kw)
+    else:
+        dev = _chain_vs_oracle(oracle, bed, N, y, opts, groups, mS)
+    ss = dev.sweep_stats()
+    engine, walker, refill, T, pivots = expect
+    assert (ss["engine"], ss["walker"], ss["refill"], ss["pivots"] > 0) == (engine, walker, refill, pivots)
+    if T is not None:
+        assert ss["tiles_per_workgroup_max"] == T
+
+
+def test_a_large_residual_on_a_fresh_handle_takes_the_batch_engine(oracle):
+    """The four-tile geometry needs the second form and |eps| < 16.  A handle whose first call is a sweep (no reduction before it) with
+    one |eps| > 64 is planned from that sweep's own opening reduction: engine 0 runs it on the batch engine, with the chain a handle
+    forced to the batch engine runs."""
+    M, N = 400, 8000
+    bed, y = make_case(M, N, seed=M + N)
+    eps = (y - y.mean()) * np.sqrt((N - 1) / np.sum((y - y.mean()) ** 2))
+    eps[7] = 80.0
+    out = []
+    for engine in (0, 1):
+        dev, rng = _direct_sweep(bed, N, y, {"engine": engine, "res_cus": 3}, eps=eps)
+        assert dev.sweep_stats()["engine"] == 1
+        beta, comp, _ = dev.get_beta()
+        out.append((beta, comp, dev.get_residual(), np.array(rng.x, dtype=np.uint32), rng.idx))
+    assert np.array_equal(out[0][0], out[1][0]) and np.array_equal(out[0][1], out[1][1]) and np.array_equal(out[0][2], out[1][2])
+    assert np.array_equal(out[0][3], out[1][3]) and out[0][4] == out[1][4]
+
+
 def test_auto_engine_falls_back_to_the_batch_engine(oracle):
     """engine = 0 (the default): where the resident engine does not apply -- here one streaming workgroup for six wave tiles --
     the sweep runs on the batch engine, silently and with the same chain."""
