@@ -79,6 +79,8 @@ enum {
     R_WORDS = 32
 };
 enum { RT_EXTEND = 0, RT_ADVANCE = 1, RT_PIVOT = 2, RT_EVENT = 3, RT_END = 4 };
+// the decider's statistics of the sweep, by lane
+enum { W2_ST_ROUNDS = 0, W2_ST_EVENTS, W2_ST_ADV, W2_ST_NNZ, W2_ST_CHUNKS, W2_ST_REFOLD, W2_ST_PIVOTS, W2_ST_PRED, W2_ST_ANN };
 
 // LDS of the walker workgroup.  The carve-up is a list of byte offsets (host and device agree on its end); the device takes its
 // pointers from it with the LDS address space in their TYPE: res_walker2 is a function of its own (not inlined into the kernel), and
@@ -218,6 +220,7 @@ __device__ __forceinline__ Walk2Lds walk2_lds(uint32_t B)
 // The roles are functions of their own so that each gets a register allocation of its own (the chain's four slots per lane want most
 // of the register file).
 #define W2_BEXPR pr.B
+#define W2_PIVEXPR (pr.pivots != 0)
 #define W2_PROLOGUE \
     const int tid = threadIdx.x, lane = tid & 63; \
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6); \
@@ -227,9 +230,9 @@ __device__ __forceinline__ Walk2Lds walk2_lds(uint32_t B)
     const uint32_t W = pr.W, nsh = pr.nsh, rsh = pr.rsh; \
     const double n_total = pr.n_total, n_minus_1 = pr.n_minus_1, i_2sigE = pr.i_2sigE, eps_sum = pr.eps_sum, fx_unscale = pr.fx_unscale; \
     const unsigned long long timeout = pr.timeout; \
-    const bool pivots = pr.pivots != 0; \
+    const bool pivots = W2_PIVEXPR; \
     const uint32_t early_advance = (uint32_t)pr.early_advance; \
-    const bool announce = pr.announce != 0 && pr.pivots == 0; \
+    const bool announce = pr.announce != 0 && !pivots; \
     const uint32_t rng_idx0 = pr.rng_idx; \
     ResMsg* const msg = pr.msg; \
     ResState* const state = pr.state; \
@@ -271,19 +274,34 @@ __device__ __forceinline__ Walk2Lds walk2_lds(uint32_t B)
 // (BC: the window as a compile-time constant -- 256, the size that is used where speed matters -- or 0: whatever the sweep's parameters say.
 // With the constant the LDS arrays are at constant addresses and the slot arithmetic is immediate: the wave's few scalar registers are not
 // spent on three dozen array bases, and a wave issues one instruction every four to five clocks whatever it is.)
-template <int DBG, int MISS, int BC, int RANKS> // (RANKS: several ranks -- the exchange through the mailboxes is compiled in)
-__device__ __attribute__((noinline)) void w2_chain(const ResParams& pr)
+// (DECIDE: the instance wave 0 runs -- it decides; waves 1-3 run the instance without the decider's code and state.  PIV: the predicted-pivot
+// path is compiled in; res_walker2 picks it where the sweep takes pivots, which the plan allows with one rank and no missing calls only.)
+template <int DBG, int MISS, int BC, int RANKS, int DECIDE, int PIV>
+__device__ __attribute__((noinline)) void w2_chain(const ResParams& prg)
 {
+    // The parameters through a pointer the compiler knows to be the same in every lane and constant for the launch.  A called function
+    // receives its pointer argument in vector registers: read through that, every parameter -- M, K, the timeout, the options -- and all
+    // that depends on one is a per-lane value to the compiler, the decider's loop-carried state with it, and its uniform control flow
+    // compiles to exec-mask branches.  (The kernel's copy in device memory is written before the launch only.)
+    typedef const __attribute__((address_space(4))) ResParams w2_cparams;
+    const unsigned long long pga = (unsigned long long)(uintptr_t)&prg;
+    const unsigned long long pgu = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(pga >> 32)) << 32) |
+                                   (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)pga);
+    w2_cparams& pr = *(w2_cparams*)(uintptr_t)pgu;
 #undef W2_BEXPR
 #define W2_BEXPR (BC ? (uint32_t)BC : pr.B)
+#undef W2_PIVEXPR
+#define W2_PIVEXPR (PIV != 0)
     W2_PROLOGUE
 #undef W2_BEXPR
 #define W2_BEXPR pr.B
+#undef W2_PIVEXPR
+#define W2_PIVEXPR (pr.pivots != 0)
     // =====================================================================================================================
     // the chain: wave w holds the window slots 64 w + lane, one position per lane; wave 0 also decides
     // =====================================================================================================================
     __builtin_amdgcn_s_setprio(3);
-    const bool decider = wave == 0;
+    constexpr bool decider = DECIDE != 0;
     const uint32_t nch = B >= 64u ? B / 64u : 1u; // chain waves in use
     const uint32_t slot = (uint32_t)wave * 64u + (uint32_t)lane;
     const bool son = slot < B;
@@ -315,7 +333,10 @@ __device__ __attribute__((noinline)) void w2_chain(const ResParams& pr)
     uint32_t seq = 0, nev = 0, pi = 0, evn = 0, pf_n = 0, gpos = rng_idx0, blk = 1u;
     uint32_t rdone_seen = 0, wpub_seen = 0, evw_seen = 0, pld_seen = W2_PRED, fpub_seen = 0, mpub_seen = m0;
     unsigned long long cm[W2_NCH] = {0ull, 0ull, 0ull, 0ull}; // candidates among the tested positions [C, Fs), by chain wave
-    uint32_t n_rounds = 0, n_events = 0, n_adv = 0, n_nnz = 0, n_chunks = 0, n_refold = 0, n_pivots = 0, n_pred = 0, n_ann = 0;
+    // the sweep's statistics, one per lane of a vector register (W2_ST_*): they are not the loop's scalar state, and a round adds its
+    // increments in one instruction from a mask of the counters that move
+    uint32_t stat = 0;
+    auto count = [&](uint32_t bits) { stat += (bits >> (uint32_t)lane) & 1u; };
     uint32_t err = 0;
     bool failed = false;
     unsigned long long tacc[8] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
@@ -332,7 +353,9 @@ __device__ __attribute__((noinline)) void w2_chain(const ResParams& pr)
     uint32_t nspin = 0;
     auto spin_fail = [&](unsigned long long t0) {
         if (aborted()) return true;
-        if (wall_clock64() - t0 > timeout || ((++nspin & 1023u) == 0u && __hip_atomic_load(progress + 2, HG_RLX_AGENT) != 0ull)) { // (or the host gave the sweep up)
+        // (or the host gave the sweep up; the host's word read as the scalar it is: a load through a generic pointer is a per-lane value to the
+        // compiler, and a wait that may end by it would make every exit of the loop around it -- and the decider's state -- per lane)
+        if (wall_clock64() - t0 > timeout || ((++nspin & 1023u) == 0u && w2_uni((uint32_t)(__hip_atomic_load(progress + 2, HG_RLX_AGENT) != 0ull)) != 0u)) {
             if (lane == 0) w2_st(sh.sw + S_ABORT, 1u);
             return true;
         }
@@ -362,16 +385,20 @@ __device__ __attribute__((noinline)) void w2_chain(const ResParams& pr)
             r[R_SXN] = Sxn;
             r[R_FD] = Fd;
             r[R_SEQ] = seq;
-            r[R_PIN] = pi;
-            r[R_PIQ] = piq;
             r[R_NEV] = nev;
             r[R_GPOSR] = gpos % W2_RING;
-            r[R_PFN] = pf_n;
             *(W2_LDS double*)(r + R_DB) = db;
             *(W2_LDS double*)(r + R_MQ) = mq;
             *(W2_LDS double*)(r + R_SQ) = sq;
-            *(W2_LDS double*)(r + R_GSQ) = gsq;
-            *(W2_LDS double*)(r + R_NMQ) = nmq;
+            if (PIV) { // (the fields only the predicted-pivot path reads)
+                r[R_PIN] = pi;
+                r[R_PIQ] = piq;
+                r[R_PFN] = pf_n;
+            }
+            if (MISS) {
+                *(W2_LDS double*)(r + R_GSQ) = gsq;
+                *(W2_LDS double*)(r + R_NMQ) = nmq;
+            }
             w2_lds_done();
             w2_st(sh.sw + S_RECSEQ, rno + 1u);
         }
@@ -391,8 +418,8 @@ __device__ __attribute__((noinline)) void w2_chain(const ResParams& pr)
         const uint32_t r_type = w2_uni(rc[R_TYPE]);
         if (r_type == (uint32_t)RT_END) break;
         const uint32_t r_q = w2_uni(rc[R_Q]), r_cn = w2_uni(rc[R_CN]), r_sxo = w2_uni(rc[R_SXO]), r_sxn = w2_uni(rc[R_SXN]), r_fd = w2_uni(rc[R_FD]);
-        const uint32_t r_pfn = w2_uni(rc[R_PFN]);
-        if (r_type == (uint32_t)RT_PIVOT) {
+        const uint32_t r_pfn = PIV ? w2_uni(rc[R_PFN]) : 0u;
+        if (PIV && r_type == (uint32_t)RT_PIVOT) {
             // a predicted pivot: its Gram term with this column came with the column's dot.  Columns whose dot was here before this record
             // take the correction now; the others find the pivot on the list of fired ones when their dot is absorbed (below, or later)
             const uint32_t jo = pos_of_slot(sl, C);
@@ -410,7 +437,7 @@ __device__ __attribute__((noinline)) void w2_chain(const ResParams& pr)
             const bool arr = son && j >= Fs && j < r_fd;
             const double dnew = sh.dpr[sl];
             dpr = arr ? dnew : dpr;
-            for (uint32_t f = 0; f < r_pfn; ++f) { // (uniform, rarely any)
+            for (uint32_t f = 0; PIV && f < r_pfn; ++f) { // (uniform, rarely any)
                 const uint32_t fmsg = sh.pf_msg[f], fpos = sh.pf_pos[f], fpi = sh.pf_pi[f];
                 const double fdb = sh.pf_val[3 * f], fmv = sh.pf_val[3 * f + 1], fsd = sh.pf_val[3 * f + 2];
                 const bool hit = arr && fmsg > sbt && fpos < j;
@@ -573,7 +600,7 @@ __device__ __attribute__((noinline)) void w2_chain(const ResParams& pr)
                 const double a = sh.mave[ms], d = sh.mstd[ms], b = sh.bold[ms];
                 const int g = sh.ga[ms] & 0x0fffffff;
                 const double sc = sh.fscale[g];
-                const uint32_t bno = rc[R_SEQ], bpi = rc[R_PIN];
+                const uint32_t bno = rc[R_SEQ], bpi = PIV ? rc[R_PIN] : 0u;
                 mave = take ? a : mave;
                 mstd = take ? d : mstd;
                 boldn = take ? b * n_minus_1 : boldn;
@@ -652,10 +679,10 @@ __device__ __attribute__((noinline)) void w2_chain(const ResParams& pr)
         const uint32_t fc_rdone = __hip_atomic_load(sh.sw + S_RDONE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP),
                        fc_wpub = __hip_atomic_load(sh.sw + S_WPUB, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP),
                        fc_evw = __hip_atomic_load(sh.sw + S_EVW, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (lane == 0 && (DBG || (n_chunks & 255u) == 0u)) w2_gst(progress, ((unsigned long long)n_rounds << 8) | 1u);
+        if (lane == W2_ST_CHUNKS && (DBG || (stat & 255u) == 0u)) w2_gst(progress, ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)stat, W2_ST_ROUNDS) << 8) | 1u);
         // fired pivots stay on record only while a column streamed before their update is without its dot (entries are in message order).
         // (The chain waves read the list while they take a record; it changes only here, behind their answers.)
-        if (pf_n) {
+        if (PIV && pf_n) {
             if (Fs >= Sx) pf_n = 0;
             else {
                 const uint32_t bF = w2_uni(sh.batch[Fs & bmask]);
@@ -678,7 +705,7 @@ __device__ __attribute__((noinline)) void w2_chain(const ResParams& pr)
         }
         // the generator: the words a decision can reach exist
         if (gpos + B + 96u > blk * (uint32_t)MT_N && !wait_seen(blk, S_BLK, (gpos + B + 96u + (uint32_t)MT_N - 1u) / (uint32_t)MT_N)) break;
-        ++n_chunks;
+        count(1u << W2_ST_CHUNKS);
         bool found = false, announced = false;
         uint32_t qpos = 0, q_consumed = 0;
         int q_k = 0;
@@ -711,6 +738,9 @@ __device__ __attribute__((noinline)) void w2_chain(const ResParams& pr)
                 const double cmq_v = sh.mave[ms], csq_v = sh.mstd[ms], cgsq_v = MISS ? sh.gsum[ms] : 0.0, cnmq_v = MISS ? sh.nmis[ms] : 0.0; // (for the record, if this one is the event)
                 const int ga_v = sh.ga[ms];
                 const uint32_t word_v = sh.mt[upos];
+                // (and the two words behind it: the normal draw's Ziggurat fast path, should the marker take a component k > 0)
+                const uint32_t zp1 = upos + 1u == W2_RING ? 0u : upos + 1u, zp2 = zp1 + 1u == W2_RING ? 0u : zp1 + 1u;
+                const uint32_t zw1 = sh.mt[zp1], zw2 = sh.mt[zp2];
                 const double bold = w2_uni(bold_v);
                 // a marker whose effect is non-zero WILL be an event (whatever is drawn changes the effect, and nothing in front of it is one):
                 // the streaming workgroups are asked for its Gram terms now -- they travel while the draw is made (RS_ANNOUNCE; the slot
@@ -718,6 +748,24 @@ __device__ __attribute__((noinline)) void w2_chain(const ResParams& pr)
                 if (announce && !announced && bold != 0.0 && qc + 1u < Sx && (seq + 6u <= (uint32_t)RS_MSG || rdone_seen >= seq + 6u - (uint32_t)RS_MSG)) {
                     if (lane == 0) rs_store16(msg + ((seq + 1u) % RS_MSG), rs_u4(rs_msg_word0((uint32_t)RS_ANNOUNCE, qc - C + 1u, seq + 1u, 0u, 0u), seq + 1u, 0u, 0u));
                     announced = true;
+                }
+                // The unit normal of a7 depends on the ring position only, not on the component: its first Ziggurat step (unit_normal,
+                // hg_rng.h: two words, one layer test -- the usual way out) is a chain of its own beside the exponentials and the walk.  Taken
+                // where that step returns and both words exist; else the draw below runs the whole of norm_rng_sd on lane 0 as before.
+                const uint32_t zleft = blk * (uint32_t)MT_N - (gpos + (qc - C) + 1u);
+                double z;
+                bool zfast;
+                {
+                    const uint32_t u1 = mt_temper(w2_uni(zw1)), u2 = mt_temper(w2_uni(zw2));
+                    int zi = (int)(u1 & 0xffu);
+                    double r = (double)(u1 >> 8) * (1.0 / 16777216.0);
+                    r += (double)(u2 & 0x1fffffffu);
+                    r *= (1.0 / 536870912.0);
+                    const int sign = (zi & 1) * 2 - 1;
+                    zi >>= 1;
+                    const double x = r * sh.zig_nx[zi];
+                    zfast = zleft >= 2u && x < sh.zig_nx[zi + 1];
+                    z = x * sign;
                 }
                 const int g0 = w2_uni(ga_v & 0x0fffffff) * K;
                 const double prob = (double)mt_temper(word_v) * (1.0 / 4294967296.0);
@@ -766,16 +814,21 @@ __device__ __attribute__((noinline)) void w2_chain(const ResParams& pr)
                 uint32_t consumed = 0u, gerr = 0u;
                 if (k > 0) { // (uniform) a7: the new effect, on one lane
                     const double mean_k = rs_readlane(mk, k), sd_k = rs_readlane(sdl, k);
-                    if (lane == 0) {
-                        RingGen g{sh.mt, upos + 1u == W2_RING ? 0u : upos + 1u, blk * (uint32_t)MT_N - (gpos + (qc - C) + 1u), 0u, 0u};
-                        const ZigLds zt{sh.zig_nx, sh.zig_ny, zig_ex, zig_ey};
-                        bnew = norm_rng_sd(g, zt, mean_k, sd_k);
-                        consumed = g.n;
-                        gerr = g.err;
+                    if (zfast) { // (uniform) norm_rng_sd's own arithmetic on the drawn unit normal
+                        bnew = z * sd_k + mean_k;
+                        consumed = 2u;
+                    } else {
+                        if (lane == 0) {
+                            RingGen g{sh.mt, zp1, zleft, 0u, 0u};
+                            const ZigLds zt{sh.zig_nx, sh.zig_ny, zig_ex, zig_ey};
+                            bnew = norm_rng_sd(g, zt, mean_k, sd_k);
+                            consumed = g.n;
+                            gerr = g.err;
+                        }
+                        bnew = w2_uni(bnew);
+                        consumed = (uint32_t)__builtin_amdgcn_readlane((int)consumed, 0);
+                        gerr = (uint32_t)__builtin_amdgcn_readlane((int)gerr, 0);
                     }
-                    bnew = w2_uni(bnew);
-                    consumed = (uint32_t)__builtin_amdgcn_readlane((int)consumed, 0);
-                    gerr = (uint32_t)__builtin_amdgcn_readlane((int)gerr, 0);
                 }
                 if (gerr) {
                     err = gerr;
@@ -811,7 +864,7 @@ __device__ __attribute__((noinline)) void w2_chain(const ResParams& pr)
         const bool early = !found && Fs < Sx && early_thr != 0u && Fs - C >= early_thr;
         if (!found && Fs < Sx && !early) {
             // every position with a dot has passed: the walk needs dots that are still on their way
-            ++n_refold;
+            count(1u << W2_ST_REFOLD);
             if (!wait_seen(fpub_seen, S_FPUB, Fs + 1u)) break;
             lap(0);
             publish(RT_EXTEND, 0u, C, Sx, Sx, fpub_seen < Sx ? fpub_seen : Sx, 0u, 0.0, 0.0, 0.0, 0.0, 0.0);
@@ -827,7 +880,7 @@ __device__ __attribute__((noinline)) void w2_chain(const ResParams& pr)
         const bool predicted = found && q_bold != 0.0;
         // a predicted pivot whose Gram terms came with the columns: the oldest batch with columns behind it lists it
         bool pivot = false;
-        if (pivots && is_event && predicted && pf_n < (uint32_t)RS_PFIRE)
+        if (PIV && is_event && predicted && pf_n < (uint32_t)RS_PFIRE)
             pivot = qpos + 1u >= Sx || pi - w2_uni(sh.bl_pi[w2_uni(sh.batch[(qpos + 1u) & bmask]) % W2_NB]) < (uint32_t)RS_PMAX;
         // flow control: never more than RS_MSG - 3 messages ahead of the slowest streaming workgroup (batches completed = messages
         // taken + 1); room in the results ring and on the event record
@@ -843,7 +896,6 @@ __device__ __attribute__((noinline)) void w2_chain(const ResParams& pr)
         if (evn + 2u > W2_EV && !wait_seen(evw_seen, S_EVW, evn + 2u - W2_EV)) break;
         lap(2);
         ++seq;
-        ++n_rounds;
         if (lane == 0) {
             const uint32_t kf = (pivot ? (uint32_t)RS_PIVOT : (announced ? (uint32_t)RS_ANNOUNCED : (is_event ? (uint32_t)RS_EVENT : (uint32_t)RS_ADVANCE))) | (Cn >= M ? (uint32_t)RS_LAST : 0u);
             const unsigned long long db = (unsigned long long)__double_as_longlong(dbeta);
@@ -855,77 +907,65 @@ __device__ __attribute__((noinline)) void w2_chain(const ResParams& pr)
             }
             rs_store16(msg + (seq % RS_MSG), rs_u4(rs_msg_word0(kf, ncons, seq, (uint32_t)db, (uint32_t)(db >> 32)), seq, (uint32_t)db, (uint32_t)(db >> 32)));
         }
+        // ---- behind the message: the statistics, the event on record, the batch, the hand-over words and the next record ----
+        count((1u << W2_ST_ROUNDS) | (is_event ? (1u << W2_ST_EVENTS) | (changed ? 1u << W2_ST_NNZ : 0u) | (predicted ? 1u << W2_ST_PRED : 0u) |
+                                                      (announced ? 1u << W2_ST_ANN : 0u)
+                                                : 1u << W2_ST_ADV) |
+              (pivot ? 1u << W2_ST_PIVOTS : 0u));
         const bool round_trip = is_event && !pivot;
         if (round_trip) ++nev;
-        // (behind the message: what only the record needs)
         const double mq = q_mq, sq = q_sq, gsq = q_gsq, nmq = q_nmq; // (came with the candidate's other values; a round without an event records zeros: nobody reads them)
-        // the event on record (the consumed positions' numerators are in the results ring: the bound test left them there)
-        if (found) {
-            if (lane == 0) {
-                sh.ev_pos[evn % W2_EV] = qpos;
-                sh.ev_k[evn % W2_EV] = (uint32_t)q_k;
-                sh.ev_bnew[evn % W2_EV] = q_bnew;
-            }
-            ++evn;
-        }
-        if (is_event) {
-            ++n_events;
-            if (changed) ++n_nnz;
-            if (predicted) ++n_pred;
-            if (announced) ++n_ann;
-        } else
-            ++n_adv;
+        const uint32_t evr = evn; // the event's entry on record (the consumed positions' numerators are in the results ring: the bound test left them there)
+        if (found) ++evn;
         const uint32_t piq = pi;
         // dots that are here by now may be absorbed with this record
         fpub_seen = w2_ld(sh.sw + S_FPUB);
         const uint32_t Fd = fpub_seen < Sx ? fpub_seen : Sx;
-        if (pivot) {
-            ++n_pivots;
-            if (Fs < Sx) { // columns behind the event whose dot (streamed before this update) has not been absorbed: the correction waits for it
-                if (lane == 0) {
-                    sh.pf_pos[pf_n] = qpos;
-                    sh.pf_msg[pf_n] = seq;
-                    sh.pf_pi[pf_n] = pi;
-                    sh.pf_val[3 * pf_n] = dbeta;
-                    sh.pf_val[3 * pf_n + 1] = mq;
-                    sh.pf_val[3 * pf_n + 2] = sq;
-                }
-                ++pf_n;
+        if (PIV && pivot && Fs < Sx) { // columns behind the event whose dot (streamed before this update) has not been absorbed: the correction waits for it
+            if (lane == 0) {
+                sh.pf_pos[pf_n] = qpos;
+                sh.pf_msg[pf_n] = seq;
+                sh.pf_pi[pf_n] = pi;
+                sh.pf_val[3 * pf_n] = dbeta;
+                sh.pf_val[3 * pf_n + 1] = mq;
+                sh.pf_val[3 * pf_n + 2] = sq;
             }
+            ++pf_n;
         }
-        if (predicted) ++pi;
-        if (lane == 0) { // this batch's pivots: the first predicted positions of the window [Cn, Sn)
-            uint32_t np = 0, p0 = 0xffffffffu;
-            if (pivots) {
-                const uint32_t e0 = sh.pred[pi % W2_PRED], e1 = sh.pred[(pi + 1u) % W2_PRED], e2 = sh.pred[(pi + 2u) % W2_PRED], e3 = sh.pred[(pi + 3u) % W2_PRED];
-                np = (e0 < Sn ? 1u : 0u) + (e1 < Sn ? 1u : 0u) + (e2 < Sn ? 1u : 0u) + (e3 < Sn ? 1u : 0u);
-                if (np) p0 = e0;
-            }
-            sh.bl_pi[seq % W2_NB] = pi;
-            sh.bl_np[seq % W2_NB] = np;
-            sh.bl_p0[seq % W2_NB] = p0;
-            sh.bl_sn[seq % W2_NB] = Sn;
-        }
+        if (PIV && predicted) ++pi;
         // the generator moves past the consumed positions' uniforms and the draw
         gpos += ncons + q_consumed;
-        w2_lds_done();
-        if (lane == 0) {
+        const uint32_t rtype = found ? (pivot ? (uint32_t)RT_PIVOT : (is_event ? (uint32_t)RT_EVENT : (uint32_t)RT_ADVANCE)) : (uint32_t)RT_ADVANCE;
+        if (lane == 0) { // (one block of lane 0's writes)
+            if (found) {
+                sh.ev_pos[evr % W2_EV] = qpos;
+                sh.ev_k[evr % W2_EV] = (uint32_t)q_k;
+                sh.ev_bnew[evr % W2_EV] = q_bnew;
+            }
+            if (PIV) { // this batch's pivots: the first predicted positions of the window [Cn, Sn)
+                const uint32_t e0 = sh.pred[pi % W2_PRED], e1 = sh.pred[(pi + 1u) % W2_PRED], e2 = sh.pred[(pi + 2u) % W2_PRED], e3 = sh.pred[(pi + 3u) % W2_PRED];
+                const uint32_t np = (e0 < Sn ? 1u : 0u) + (e1 < Sn ? 1u : 0u) + (e2 < Sn ? 1u : 0u) + (e3 < Sn ? 1u : 0u);
+                sh.bl_pi[seq % W2_NB] = pi;
+                sh.bl_np[seq % W2_NB] = np;
+                sh.bl_p0[seq % W2_NB] = np ? e0 : 0xffffffffu;
+            }
+            sh.bl_sn[seq % W2_NB] = Sn;
+            w2_lds_done();
             w2_st(sh.sw + S_SEQPUB, seq);
             w2_st(sh.sw + S_EVN, evn); // (before the cursor: the housekeeper reads the cursor first)
             w2_st(sh.sw + S_CPUB, Cn);
             w2_st(sh.sw + S_GPOS, gpos);
-            w2_st(sh.sw + S_PCUR, pi);
+            if (PIV) w2_st(sh.sw + S_PCUR, pi);
         }
         if (Cn >= M) { // the sweep is over
             C = Cn;
             break;
         }
         // the record: what happened, for every chain wave (this one included)
-        publish(found ? (pivot ? (uint32_t)RT_PIVOT : (is_event ? (uint32_t)RT_EVENT : (uint32_t)RT_ADVANCE)) : (uint32_t)RT_ADVANCE, found ? qpos : Cn - 1u, Cn, Sx, Sn, Fd, piq, dbeta,
-                mq, sq, gsq, nmq);
+        publish(rtype, found ? qpos : Cn - 1u, Cn, Sx, Sn, Fd, piq, dbeta, mq, sq, gsq, nmq);
         lap(4);
         // the staged list of predicted positions reaches far enough (the housekeeper refills behind S_PCUR)
-        if (pivots && !wait_seen(pld_seen, S_PLD, pi + 8u)) break;
+        if (PIV && !wait_seen(pld_seen, S_PLD, pi + 8u)) break;
     }
     if (decider) {
         if (C < M) { // the sweep was given up
@@ -942,14 +982,15 @@ __device__ __attribute__((noinline)) void w2_chain(const ResParams& pr)
             w2_lds_done();
             w2_st(sh.sw + S_END, 1u);
             state->cursor = C;
-            state->rounds = n_rounds;
-            state->events = n_events;
-            state->advances = n_adv;
-            state->nnz = n_nnz;
-            state->chunks = n_chunks;
-            state->refolds = n_refold;
-            state->pivots = n_pivots + n_ann; // (events whose Gram terms the walker did not have to wait a whole round trip for: predicted pivots, or announced)
-            state->predicted = n_pred;
+            auto st = [&](int i) { return (uint32_t)__builtin_amdgcn_readlane((int)stat, i); };
+            state->rounds = st(W2_ST_ROUNDS);
+            state->events = st(W2_ST_EVENTS);
+            state->advances = st(W2_ST_ADV);
+            state->nnz = st(W2_ST_NNZ);
+            state->chunks = st(W2_ST_CHUNKS);
+            state->refolds = st(W2_ST_REFOLD);
+            state->pivots = st(W2_ST_PIVOTS) + st(W2_ST_ANN); // (events whose Gram terms the walker did not have to wait a whole round trip for: predicted pivots, or announced)
+            state->predicted = st(W2_ST_PRED);
             if (DBG)
                 for (int i = 0; i < 8; ++i) state->t[i] = tacc[i];
         }
@@ -1295,6 +1336,7 @@ __device__ __attribute__((noinline)) void res_walker2(const ResParams& pr)
     for (uint32_t j = (uint32_t)tid; j < m0; j += RS_BLOCK) stage_meta(j);
     for (uint32_t i = (uint32_t)tid; i < W2_PRED; i += RS_BLOCK) sh.pred[i] = i < M + 16u ? gpred[i] : 0xffffffffu;
     for (uint32_t j = (uint32_t)tid; j < Sx0; j += RS_BLOCK) sh.batch[j & bmask] = 0u;
+    for (uint32_t i = (uint32_t)tid; i < W2_NB; i += RS_BLOCK) sh.bl_np[i] = 0u; // (the decider writes a batch's pivots only where the sweep takes them)
     __syncthreads();
     // thresholds of the first block; the tabulated bound (see res_walker: f(n2) = log sum_l>0 exp(c_l + n2 r_l) is convex in n2 = num^2,
     // so the chord between two grid points is an upper bound)
@@ -1336,9 +1378,22 @@ __device__ __attribute__((noinline)) void res_walker2(const ResParams& pr)
 
     if (wave < W2_NCH) {
         if ((uint32_t)wave < (B >= 64u ? B / 64u : 1u)) {
-            if (pr.nranks > 1) w2_chain<DBG, MISS, 0, 1>(pr);
-            else if (B == 256u) w2_chain<DBG, MISS, 256, 0>(pr);
-            else w2_chain<DBG, MISS, 0, 0>(pr);
+            // (by role: wave 0 decides; by feature: predicted pivots -- never with several ranks or missing calls, plan_sweep)
+            if (wave == 0) {
+                if (pr.nranks > 1) w2_chain<DBG, MISS, 0, 1, 1, 0>(pr);
+                else if (!MISS && pr.pivots) {
+                    if (B == 256u) w2_chain<DBG, MISS, 256, 0, 1, 1>(pr);
+                    else w2_chain<DBG, MISS, 0, 0, 1, 1>(pr);
+                } else if (B == 256u) w2_chain<DBG, MISS, 256, 0, 1, 0>(pr);
+                else w2_chain<DBG, MISS, 0, 0, 1, 0>(pr);
+            } else {
+                if (pr.nranks > 1) w2_chain<DBG, MISS, 0, 1, 0, 0>(pr);
+                else if (!MISS && pr.pivots) {
+                    if (B == 256u) w2_chain<DBG, MISS, 256, 0, 0, 1>(pr);
+                    else w2_chain<DBG, MISS, 0, 0, 0, 1>(pr);
+                } else if (B == 256u) w2_chain<DBG, MISS, 256, 0, 0, 0>(pr);
+                else w2_chain<DBG, MISS, 0, 0, 0, 0>(pr);
+            }
         }
     } else if (wave == 4) {
         if (pr.nranks > 1) w2_folder<MISS, 1>(pr);
