@@ -21,7 +21,7 @@ ABI_SYMBOLS = [
     "hydra_rng_to_boost_words", "hydra_rng_from_boost_words", "hgibbs_set_model", "hgibbs_set_beta", "hgibbs_get_beta",
     "hgibbs_beta_sqnorm", "hgibbs_sweep", "hgibbs_set_option", "hgibbs_last_sweep_stats", "hgibbs_stream_ceiling", "hgibbs_debug_times", "hgibbs_resident_trace", "hydra_chain_create",
     "hydra_chain_destroy", "hydra_chain_iterate", "hydra_chain_state", "hydra_chain_csv_line", "hydra_chain_order",
-    "hydra_chain_last_nnz", "hgibbs_score", "hgibbs_last_score_ms",
+    "hydra_chain_last_nnz", "hgibbs_score", "hgibbs_last_score_ms", "hgibbs_ld", "hgibbs_last_ld_ms",
     # BayesW
     "hgibbs_grand_seed", "hgibbs_grand_next", "hgibbs_ars_sample", "hgibbs_w_init", "hgibbs_w_marker_stats", "hgibbs_w_set_model",
     "hgibbs_w_reduce", "hgibbs_w_refresh_vi", "hgibbs_w_get_vi", "hgibbs_w_marker_sums", "hgibbs_w_sweep", "hgibbs_w_last_sweep_stats", "hgibbs_w_ars_device_probe",
@@ -181,6 +181,8 @@ def lib():
     L.hydra_chain_last_nnz.restype = C.c_uint64
     L.hgibbs_score.argtypes = [vp, C.c_int, dp, dp, dp]
     L.hgibbs_last_score_ms.argtypes = [vp, dp]
+    L.hgibbs_ld.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, dp, C.POINTER(C.c_int64)]
+    L.hgibbs_last_ld_ms.argtypes = [vp, dp]
     _lib = L
     return L
 
@@ -375,6 +377,22 @@ class Device:
     def last_score_ms(self):
         v = C.c_double()
         check(self.L.hgibbs_last_score_ms(self.h, C.byref(v)))
+        return v.value
+
+    def ld(self, W, m0=0, count=None, r=True, sums=True):
+        """Windowed LD (hgibbs_ld): r (count, W) with r[j - m0, d - 1] = x_j'x_{j+d} / (N - 1), and sums (count, W, 4) int64
+        G, Bjq, Bqj, D; either may be turned off (None returned)."""
+        if count is None:
+            count = self.M - m0
+        rr = np.zeros((count, W)) if r else None
+        ss = np.zeros((count, W, 4), dtype=np.int64) if sums else None
+        check(self.L.hgibbs_ld(self.h, m0, count, W, _dp(rr) if r else None,
+                               ss.ctypes.data_as(C.POINTER(C.c_int64)) if sums else None))
+        return rr, ss
+
+    def last_ld_ms(self):
+        v = C.c_double()
+        check(self.L.hgibbs_last_ld_ms(self.h, C.byref(v)))
         return v.value
 
     def debug_times(self):

@@ -182,6 +182,8 @@ struct hgibbs_ctx {
     int score_sp = 0;     // option score_sp: samples per pass of hgibbs_score, 2, 4, 8 or 16 (0 = automatic, hg_score.hip.h)
     int score_ranges = 0; // option score_ranges: at most this many ranges of markers per column of workgroups (0 = automatic)
     double score_ms = 0.0; // device time of the last hgibbs_score (weights to digits, products, rounding)
+    int ld_split = 0;      // option ld_split: ranges of individuals the workgroups of hgibbs_ld split the columns into (0 = automatic)
+    double ld_ms = 0.0;    // device time of the last hgibbs_ld (every piece: zeroing, products, final formula)
 };
 
 static int ensure_scratch(hgibbs_ctx* h, size_t n)
@@ -1211,6 +1213,9 @@ int hgibbs_set_option(hgibbs_t h, const char* name, int64_t value)
     if (!std::strcmp(name, "score_sp")) {
         if (value != 0 && value != 2 && value != 4 && value != 8 && value != 16) return fail("score_sp must be 0 (automatic), 2, 4, 8 or 16");
         h->score_sp = (int)value;
+    } else if (!std::strcmp(name, "ld_split")) {
+        if (value < 0 || value > 65535) return fail("ld_split must be in [0,65535] (0 = automatic)");
+        h->ld_split = (int)value;
     } else if (!std::strcmp(name, "score_ranges")) {
         if (value < 0 || value > 65535) return fail("score_ranges must be in [0,65535] (0 = automatic)");
         h->score_ranges = (int)value;
@@ -2023,3 +2028,4 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
 
 #include "hg_bayesw.hip.h"
 #include "hg_score.hip.h"
+#include "hg_ld.hip.h"

@@ -16,6 +16,11 @@
 // cohort T with the chain's .bet records at or after --burn-in (run_predict); the dry run stops after every
 // check and the marker-match report, before the device.
 //
+// `--ld-window W [--ld-window-kb KB] [--ld-window-r2 T] [--ld-out F] [--ld-bin]` appended to a bayesMPI command line samples nothing
+// either: it computes r between every marker and the next W markers of its chromosome (within KB kilobases when given) on the chain's
+// own rows and standardisation, with hgibbs_ld (run_ld), and writes the pairs with r^2 >= T as PLINK's --r
+// table to <dir>/<name>.ld (or F), and with --ld-bin the whole band as f32 to <out>.bin.
+//
 // Not reproduced (out of scope for the hot path): sparse
 // file formats, bayesFH, marker-sharded MPI, the .lst/tarball.
 // Multi-GPU: one process per GPU (RANK/WORLD_SIZE/LOCAL_RANK in the
@@ -32,6 +37,7 @@
 #include <cstring>
 #include <fstream>
 #include <iostream>
+#include <limits>
 #include <map>
 #include <sstream>
 #include <string>
@@ -57,6 +63,10 @@ struct Options { // src/options.hpp:20-138 (subset that reaches bayesMPI)
     std::string failureFile, quad_points;            // options.hpp:56-58 (bayesWMPI)
     std::string predictBfile, predictOut;            // --predict-bfile / --predict-out: score a target cohort (this build's, not hydra's)
     bool predictDryRun = false;                      // --predict-dry-run: every check and the match report, then stop before the device
+    long long ldWindow = 0;                          // --ld-window W: windowed LD of the training markers
+    double ldWindowKb = -1.0, ldWindowR2 = 0.2;      // --ld-window-kb (-1: no bp limit), --ld-window-r2
+    bool ldGiven = false, ldKbGiven = false, ldR2Given = false, ldBin = false;
+    std::string ldOut;                               // --ld-out
     int batch = 0, cpg = 0; // tuning knobs of this build (not hydra's)
 };
 
@@ -175,6 +185,18 @@ Options parse(int argc, const char* argv[])
         else if (a == "--predict-bfile") o.predictBfile = need(i);
         else if (a == "--predict-out") o.predictOut = need(i);
         else if (a == "--predict-dry-run") o.predictDryRun = true;
+        else if (a == "--ld-window") {
+            o.ldWindow = std::atoll(need(i));
+            o.ldGiven = true;
+        }
+        else if (a == "--ld-window-kb") {
+            o.ldWindowKb = std::atof(need(i));
+            o.ldKbGiven = true;
+        } else if (a == "--ld-window-r2") {
+            o.ldWindowR2 = std::atof(need(i));
+            o.ldR2Given = true;
+        } else if (a == "--ld-out") o.ldOut = need(i);
+        else if (a == "--ld-bin") o.ldBin = true;
         else if (a == "--sparse-dir" || a == "--sparse-basename" ||
                  a == "--bed-to-sparse" || a == "--sparse-sync" || a == "--bed-sync")
             fatal("FATAL  : option " + a + " belongs to a part of hydra this build does not reproduce (SURVEY.md section 2)");
@@ -843,6 +865,8 @@ int run_bayesw(const Options& opt_in, int rank, int nranks, int local_rank)
 // ---- --predict-bfile: score a target cohort with the chain's effects ----
 struct BimRows {
     std::vector<std::string> id, a1, a2;
+    std::vector<std::string> chr; // (--ld-window)
+    std::vector<long long> bp;
 };
 
 BimRows read_bim(const std::string& path, size_t limit)
@@ -855,6 +879,8 @@ BimRows read_bim(const std::string& path, size_t limit)
         b.id.push_back(id);
         b.a1.push_back(a1);
         b.a2.push_back(a2);
+        b.chr.push_back(chr);
+        b.bp.push_back(std::atoll(pos.c_str()));
     }
     return b;
 }
@@ -1032,6 +1058,97 @@ int run_predict(const Options& opt, const std::vector<uint8_t>& keep, unsigned n
     return 0;
 }
 
+// ---- --ld-window: windowed LD of the training markers on the chain's rows ----
+int run_ld(const Options& opt, const std::vector<uint8_t>& keep, unsigned numInds, unsigned numNAs, unsigned Mtot, int local_rank)
+{
+    const std::string out = opt.ldOut.empty() ? opt.mcmcOutDir + "/" + opt.mcmcOutNam + ".ld" : opt.ldOut;
+    const BimRows bim = read_bim(opt.bedFile + ".bim", Mtot);
+    const uint32_t W = (uint32_t)opt.ldWindow;
+    const long long maxbp = opt.ldKbGiven ? (long long)std::llround(1000.0 * opt.ldWindowKb) : -1;
+    // a pair (j, q) is kept when 0 < q - j <= W in .bim order, on one chromosome and, with --ld-window-kb, within 1000 KB bp
+    auto kept = [&](unsigned j, unsigned q) {
+        return bim.chr[q] == bim.chr[j] && (maxbp < 0 || std::llabs(bim.bp[q] - bim.bp[j]) <= maxbp);
+    };
+    std::map<std::string, int> chroms;
+    unsigned long long npairs = 0;
+    for (unsigned j = 0; j < Mtot; ++j) {
+        chroms.emplace(bim.chr[j], 1);
+        for (unsigned q = j + 1; q < Mtot && q - j <= W; ++q) npairs += kept(j, q) ? 1u : 0u;
+    }
+    std::printf("LD     : %u markers, window %u markers%s, %zu chromosomes, %llu pairs in the window; r^2 >= %g -> %s%s\n", Mtot, W,
+                maxbp >= 0 ? (" and " + std::to_string(maxbp) + " bp").c_str() : "", chroms.size(), npairs, opt.ldWindowR2, out.c_str(),
+                opt.ldBin ? (" and " + out + ".bin").c_str() : "");
+    std::fflush(stdout);
+
+    const size_t len = (numInds + 3) / 4;
+    std::vector<uint8_t> bed((size_t)Mtot * len);
+    {
+        std::ifstream in(opt.bedFile + ".bed", std::ios::binary);
+        if (!in) fatal("Error: can not open the file [" + opt.bedFile + ".bed] to read.");
+        unsigned char magic[3];
+        in.read((char*)magic, 3);
+        if (!in || magic[0] != 0x6c || magic[1] != 0x1b || magic[2] != 0x01) fatal("FATAL  : " + opt.bedFile + ".bed is not a SNP-major PLINK bed");
+        in.read((char*)bed.data(), (std::streamsize)bed.size());
+        if ((size_t)in.gcount() != bed.size()) fatal("FATAL  : " + opt.bedFile + ".bed is shorter than M x ceil(N/4)");
+    }
+    struct stat sb;
+    if (opt.ldOut.empty() && stat(opt.mcmcOutDir.c_str(), &sb) != 0)
+        if (std::system(("mkdir -p " + opt.mcmcOutDir).c_str()) != 0) fatal("FATAL  : can not create --mcmc-out-dir");
+    FILE* f = std::fopen(out.c_str(), "w");
+    if (!f) fatal("FATAL  : can not create " + out);
+    FILE* fb = nullptr;
+    if (opt.ldBin) {
+        fb = std::fopen((out + ".bin").c_str(), "wb");
+        if (!fb) fatal("FATAL  : can not create " + out + ".bin");
+        const uint32_t hdr[2] = {Mtot, W};
+        if (std::fwrite(hdr, sizeof hdr, 1, fb) != 1) fatal("FATAL  : short write on " + out + ".bin");
+    }
+    std::fprintf(f, "CHR_A BP_A SNP_A CHR_B BP_B SNP_B R\n");
+
+    // the chain's rows (NA phenotype, and NA covariate rows with --covariates, dropped) and its standardisation
+    const unsigned Ntot = numInds - numNAs;
+    hgibbs_t dev = nullptr;
+    hg_check(hgibbs_create(local_rank, &dev), "hgibbs_create");
+    hg_check(hgibbs_load_bed(dev, bed.data(), len, numInds, Mtot, numNAs ? keep.data() : nullptr, 0, Ntot, Ntot), "hgibbs_load_bed");
+    std::vector<uint8_t>().swap(bed);
+    hg_check(hgibbs_marker_stats(dev, nullptr, nullptr, nullptr, nullptr, nullptr), "hgibbs_marker_stats");
+
+    // chunks of markers: host memory stays at about 2^22 pairs
+    const unsigned chunk = std::max(1u, (unsigned)((1u << 22) / W));
+    std::vector<double> r;
+    std::vector<float> rf;
+    unsigned long long written = 0;
+    double ms = 0.0;
+    for (unsigned m0 = 0; m0 < Mtot; m0 += chunk) {
+        const unsigned cnt = std::min(chunk, Mtot - m0);
+        r.resize((size_t)cnt * W);
+        hg_check(hgibbs_ld(dev, m0, cnt, W, r.data(), nullptr), "hgibbs_ld");
+        double t = 0.0;
+        hg_check(hgibbs_last_ld_ms(dev, &t), "hgibbs_last_ld_ms");
+        ms += t;
+        if (fb) rf.assign((size_t)cnt * W, std::numeric_limits<float>::quiet_NaN());
+        for (unsigned jj = 0; jj < cnt; ++jj) {
+            const unsigned j = m0 + jj;
+            for (unsigned d = 1; d <= W && j + d < Mtot; ++d) {
+                const unsigned q = j + d;
+                const double v = r[(size_t)jj * W + d - 1];
+                if (std::isnan(v) || !kept(j, q)) continue;
+                if (fb) rf[(size_t)jj * W + d - 1] = (float)v;
+                if (v * v < opt.ldWindowR2) continue;
+                std::fprintf(f, "%s %lld %s %s %lld %s %.12g\n", bim.chr[j].c_str(), bim.bp[j], bim.id[j].c_str(), bim.chr[q].c_str(), bim.bp[q],
+                             bim.id[q].c_str(), v);
+                ++written;
+            }
+        }
+        if (fb && std::fwrite(rf.data(), sizeof(float), rf.size(), fb) != rf.size()) fatal("FATAL  : short write on " + out + ".bin");
+    }
+    hgibbs_destroy(dev);
+    if (std::fclose(f) != 0) fatal("FATAL  : short write on " + out);
+    if (fb && std::fclose(fb) != 0) fatal("FATAL  : short write on " + out + ".bin");
+    std::printf("LD     : wrote %llu pairs with r^2 >= %g to %s (%.3f ms on the device)\n", written, opt.ldWindowR2, out.c_str(), ms);
+    return 0;
+}
+
 } // namespace
 
 int main(int argc, const char* argv[])
@@ -1056,6 +1173,18 @@ int main(int argc, const char* argv[])
     const int rank = (e = std::getenv("RANK")) ? std::atoi(e) : 0;
     const int nranks = (e = std::getenv("WORLD_SIZE")) ? std::atoi(e) : 1;
     const int local_rank = (e = std::getenv("LOCAL_RANK")) ? std::atoi(e) : rank;
+    if (opt.ldGiven) {
+        if (opt.bayesType == "bayesWMPI") fatal("FATAL  : --ld-window takes a bayesMPI command line, not --mpibayes bayesWMPI");
+        if (!opt.predictBfile.empty()) fatal("FATAL  : --ld-window cannot be combined with --predict-bfile");
+        if (opt.restart) fatal("FATAL  : --ld-window does not sample: it cannot be combined with --restart");
+        if (nranks > 1) fatal("FATAL  : --ld-window runs on one process (WORLD_SIZE = " + std::to_string(nranks) + ")");
+        if (opt.ldWindow < 1 || opt.ldWindow > 4096)
+            fatal("FATAL  : --ld-window " + std::to_string(opt.ldWindow) + ": the window must be 1 to 4096 markers (the widest hgibbs_ld takes)");
+        if (!(opt.ldWindowR2 >= 0.0 && opt.ldWindowR2 <= 1.0)) fatal("FATAL  : --ld-window-r2 must be in [0, 1]");
+        if (opt.ldKbGiven && !(opt.ldWindowKb >= 0.0)) fatal("FATAL  : --ld-window-kb must not be negative");
+    } else if (!opt.ldOut.empty() || opt.ldKbGiven || opt.ldR2Given || opt.ldBin)
+        fatal(std::string("FATAL  : ") + (!opt.ldOut.empty() ? "--ld-out" : opt.ldKbGiven ? "--ld-window-kb" : opt.ldR2Given ? "--ld-window-r2" : "--ld-bin") +
+              " needs --ld-window");
     if (!opt.predictBfile.empty()) {
         if (opt.bayesType == "bayesWMPI") fatal("FATAL  : --predict-bfile scores with bayesMPI effects only, not with --mpibayes bayesWMPI");
         if (opt.restart) fatal("FATAL  : --predict-bfile does not sample: it cannot be combined with --restart");
@@ -1090,6 +1219,7 @@ int main(int argc, const char* argv[])
         std::printf("INFO   : Full dataset includes Mtot=%d markers and Ntot=%d individuals.\n", Mtot, (int)numInds);
     }
     if (!opt.predictBfile.empty()) return run_predict(opt, keep, (unsigned)numInds, numNAs, Mtot, local_rank);
+    if (opt.ldGiven) return run_ld(opt, keep, (unsigned)numInds, numNAs, Mtot, local_rank);
 
     std::vector<int32_t> groups;
     std::vector<std::vector<double>> mS;

@@ -243,6 +243,21 @@ int hgibbs_score(hgibbs_t h, int S, const double* a, const double* o, double* ou
 /* device time of the last hgibbs_score in ms: every kernel of the call (scales, digits, products, rounding), not the host copies */
 int hgibbs_last_score_ms(hgibbs_t h, double* ms);
 
+/* ---- windowed LD of the loaded markers ------------ */
+/* For markers j in [m0, m0 + count) and d = 1..W (pairs j, j + d with j + d < M, by index):
+ *   r_host[(j - m0) * W + d - 1]        = x_j'x_{j+d} / (N - 1)            (NaN where j + d >= M or either mstd is not finite)
+ *   sums_host[((j - m0) * W + d - 1)*4 + t], t = 0..3: the exact integers
+ *       G = sum g_j g_q, Bjq = sum g_j [q called], Bqj = sum g_q [j called], D = sum [j called][q called]   (g = 0 at a missing call)
+ * with x the chain's standardised genotypes (x = 0 at a missing call), so r is Pearson's r of the allele counts without missing
+ * calls and r after mean imputation with them; sums are 0 where j + d >= M.  Either output pointer may be NULL.  Needs the
+ * marker stats (hgibbs_marker_stats; computed here when they are not); one rank only (several: error, message); 1 <= W <= 4096;
+ * n_local < 2^29.  Every sum is an exact integer, so the results are bit-identical for any m0 / count chunking and any value of the
+ * option ld_split (ranges of individuals split over workgroups, 0 = automatic).  Host memory: count * W doubles and 4 count * W
+ * int64 at most; the device works in pieces of at most 2^24 pairs. */
+int hgibbs_ld(hgibbs_t h, uint32_t m0, uint32_t count, uint32_t W, double* r_host, int64_t* sums_host);
+/* device time of the last hgibbs_ld in ms: every kernel of the call (zeroing, products, final formula), not the host copies */
+int hgibbs_last_ld_ms(hgibbs_t h, double* ms);
+
 /* ======================================================================== */
 /* Host driver: the body of BayesRRm::runMpiGibbs (src/BayesRRm.cpp:933-2939)
  * for --mpibayes bayesMPI, restated on top of hgibbs_*.                     */
