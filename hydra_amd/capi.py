@@ -22,6 +22,7 @@ ABI_SYMBOLS = [
     "hgibbs_beta_sqnorm", "hgibbs_sweep", "hgibbs_set_option", "hgibbs_last_sweep_stats", "hgibbs_stream_ceiling", "hgibbs_debug_times", "hgibbs_resident_trace", "hydra_chain_create",
     "hydra_chain_destroy", "hydra_chain_iterate", "hydra_chain_state", "hydra_chain_csv_line", "hydra_chain_order",
     "hydra_chain_last_nnz", "hgibbs_score", "hgibbs_last_score_ms", "hgibbs_ld", "hgibbs_last_ld_ms",
+    "hgibbs_marker_dots", "hgibbs_last_marker_dots_ms",
     # BayesW
     "hgibbs_grand_seed", "hgibbs_grand_next", "hgibbs_ars_sample", "hgibbs_w_init", "hgibbs_w_marker_stats", "hgibbs_w_set_model",
     "hgibbs_w_reduce", "hgibbs_w_refresh_vi", "hgibbs_w_get_vi", "hgibbs_w_marker_sums", "hgibbs_w_sweep", "hgibbs_w_last_sweep_stats", "hgibbs_w_ars_device_probe",
@@ -183,6 +184,8 @@ def lib():
     L.hgibbs_last_score_ms.argtypes = [vp, dp]
     L.hgibbs_ld.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, dp, C.POINTER(C.c_int64)]
     L.hgibbs_last_ld_ms.argtypes = [vp, dp]
+    L.hgibbs_marker_dots.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_int, dp, dp, dp]
+    L.hgibbs_last_marker_dots_ms.argtypes = [vp, dp]
     _lib = L
     return L
 
@@ -393,6 +396,25 @@ class Device:
     def last_ld_ms(self):
         v = C.c_double()
         check(self.L.hgibbs_last_ld_ms(self.h, C.byref(v)))
+        return v.value
+
+    def marker_dots(self, U, m0=0, count=None, raw=False):
+        """x_j'u_k for markers j in [m0, m0 + count) against the rows u_k of U (K, n_local) (hgibbs_marker_dots): out (count, K),
+        and with raw=True also (count, K, 2) the sums P = sum_called g u, Q = sum_called u, each rounded once."""
+        U = np.ascontiguousarray(np.atleast_2d(U), dtype=np.float64)
+        if U.shape[1] != self.n_local:
+            raise ValueError("U must be (K, %d)" % self.n_local)
+        if count is None:
+            count = self.M - m0
+        K = U.shape[0]
+        out = np.zeros((count, K))
+        rr = np.zeros((count, K, 2)) if raw else None
+        check(self.L.hgibbs_marker_dots(self.h, m0, count, K, _dp(U), _dp(out), _dp(rr) if raw else None))
+        return (out, rr) if raw else out
+
+    def last_marker_dots_ms(self):
+        v = C.c_double()
+        check(self.L.hgibbs_last_marker_dots_ms(self.h, C.byref(v)))
         return v.value
 
     def debug_times(self):

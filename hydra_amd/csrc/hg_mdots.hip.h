@@ -1,0 +1,371 @@
+// Dots of the loaded markers against dense vectors over the individuals: for markers j in [m0, m0 + count)
+// and K vectors u_k over the handle's n_local individuals, the exact integer sums
+//
+//     P_jk = sum_{i called} g_ij q_ik,   Q_jk = sum_{i called} q_ik,      q_ik = round(u_ik 2^E_k)
+//
+// and from them, each rounded to f64 ONCE, x_j'u_k = mstd_j (P_jk - mave_j Q_jk) with the chain's own standardisation.  This is the
+// refill's product x_j'eps (hg_streamer2.hip.h) as a standalone operator for K vectors: the digits of u against the BED codes on
+// v_mfma_i32_16x16x64_i8.
+//
+//   scale    one per vector, as hgibbs_score takes it (k_score_max, k_score_ksum): E_k = 52 - e_k with max_i |u_ik| < 2^e_k (0 for an
+//            all-zero vector), q = llrint(u 2^E_k), |q| <= 2^52, in seven signed base-256 digits (sc_quant, sc_digit).  The only error
+//            is that rounding: |P 2^-E_k - sum g u| <= n 2^-E_k <= 2 n max|u_k| 2^-52 and |Q 2^-E_k - sum u| <= n max|u_k| 2^-52,
+//            each before its one rounding to f64.  k_score_ksum also gives sum_{i < n_local} q_ik exactly (two 64-bit halves).
+//   A        (16 rows x 64 individuals, bytes): the digits of two vectors.  Rows 0..6 hold vector 2 t, rows 8..14 vector 2 t + 1, rows
+//            7 and 15 are zero; byte order of rl_expand16 (dword q, byte i = individual 4 i + q of the sixteen of a dword).  k_mdots_digits
+//            writes this image once per call in HBM: [slice of 512 individuals][tile t][k-step s][lane] 16 bytes, zero past n_local.
+//   B        (64 individuals x 16 markers): lane (c, g) of k-step s expands ONE stored BED dword of marker c, dword 8 g + s of the slice
+//            (the lane loads its eight dwords of the slice as two 16-byte loads).  No transpose: this is hg_ld.hip.h's operand.
+//   D        (i32): lane (c, g), register r = digit (4 g + r) mod 8 of vector 2 t + (g >> 1) against marker c.  The lane puts its four
+//            digits together (d0 + 2^8 d1 + 2^16 d2 + 2^24 d3, |.| < 2^56) and adds them to the pair's low (g even) or high (g odd: units
+//            of 2^32) 64-bit sum by an atomic add, as k_score does: |P| 2^E can exceed 2^64, the two halves do not.
+//   missing  the first product counts a missing call (code 3) as 3; in 16-marker tiles that hold a column with missing calls (the
+//            marker-stats nmiss) a second product of the same digits against the indicator bytes [code == 3] gives R = sum_missing q.
+//            Then P = D - 3 R and Q = sum_all q - R (k_mdots_final).  The second product is compiled only into k_mdots<.., true>,
+//            launched only when some column of the handle has missing calls.
+//   padding  BED slots past n_local are code 3, but they meet zero digits: they add nothing to D or R.
+//   exact    every i32 partial is a sum of |digit| x code <= 128 x 3 over the individuals of the workgroup's range; the host caps a
+//            range at MD_SUB_MAX slices (2^22 individuals: 384 x 2^22 < 2^31), so no partial overflows before it leaves for the
+//            64-bit sums.  n_local < 2^29 keeps the final halves (|lo| < 2 n 2^31.01) inside an int64; the adds themselves wrap
+//            harmlessly (modular).  Integer sums do not depend on tiling, workgroups, the individual split (option mdots_split),
+//            m0 / count chunking or launch order: the results are bit-identical across all of them.
+//   reuse    workgroup = MD_WAVES waves x MT marker tiles (MT = 4 at TP <= 2: 256 markers), TP vector tiles a pass.  Per slice of 512
+//            individuals the workgroup stages TP x 8 KB of digits in LDS (double-buffered, one barrier a slice) for all its markers:
+//            32 bytes of digits per marker and tile against 128 bytes of codes, 1/4 at K <= 2.  K > 8 takes ceil(K / 8) passes.
+#pragma once
+
+namespace {
+
+constexpr int MD_WAVES = 4;                  // waves per workgroup
+constexpr int MD_SUBD = 32;                  // dwords of a column per slice: 512 individuals, 128 bytes, eight k-steps
+constexpr int MD_SUBI = MD_SUBD * 16;        // individuals per slice
+constexpr int MD_TPMAX = 4;                  // vector tiles per pass (the LDS staging: 2 x 4 x 8 KB = 64 KB)
+constexpr int MD_KMAX = 32;                  // vectors per call at most (16 tiles: four passes)
+constexpr uint32_t MD_SUB_MAX = 8192;        // slices per workgroup at most (i32 headroom, above)
+constexpr uint32_t MD_NMAX = 1u << 29;       // n_local below this keeps the final 64-bit halves exact
+constexpr int MD_TPB = 256;                  // threads of the helper kernels
+
+constexpr int md_mt(int TP) { return TP <= 2 ? 4 : 2; } // marker tiles per wave
+
+// The digit image: block (s8, t) = (k-step of the whole column, tile), lane (r, g): digit r & 7 of vector 2 t + (r >> 3) over the
+// sixteen individuals of dword 8 g + (s8 % 8) of slice s8 / 8
+__global__ __launch_bounds__(64) void k_mdots_digits(const double* __restrict__ U, uint32_t n_local, int K, int tiles,
+                                                     const int* __restrict__ scale, rl_v4i* __restrict__ img)
+{
+    const uint32_t s8 = blockIdx.x, t = blockIdx.y, lane = threadIdx.x;
+    const uint32_t r = lane & 15u, g = lane >> 4, d = r & 7u;
+    const uint32_t k = 2u * t + (r >> 3);
+    const uint32_t sub = s8 / 8u, s = s8 % 8u;
+    rl_v4i w = {0, 0, 0, 0};
+    if (k < (uint32_t)K && d < 7u) {
+        const int E = scale[k];
+        const uint64_t i0 = ((uint64_t)sub * MD_SUBD + 8u * g + s) * 16u; // first individual of the dword
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            uint32_t wq = 0;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const uint64_t ind = i0 + 4u * (uint32_t)i + (uint32_t)q;
+                if (ind >= n_local) continue;
+                wq |= (uint32_t)(uint8_t)sc_digit(sc_quant(U[(size_t)k * n_local + ind], E), (int)d) << (8 * i);
+            }
+            w[q] = (int)wq;
+        }
+    }
+    img[(((size_t)sub * tiles + t) * 8u + s) * 64u + lane] = w;
+}
+
+// The product.  Workgroup (x, y): marker tiles tw0 + MT w + 0 .. MT - 1 for wave w, tw0 = t0 + MD_WAVES MT x; slices
+// [y sub_per, (y + 1) sub_per) of the n_sub; vector tiles tv0 .. tv0 + ntp - 1 (ntp <= TP) of the image's `tiles`.
+template <int TP, bool MISS>
+__global__ __launch_bounds__(MD_WAVES * 64) void k_mdots(const uint8_t* __restrict__ bed, uint64_t stride, uint32_t M, uint32_t t0,
+                                                         uint32_t t1, uint32_t sub_per, uint32_t n_sub, const rl_v4i* __restrict__ img,
+                                                         int tiles, int tv0, int ntp, int K, const uint8_t* __restrict__ tmiss,
+                                                         uint32_t m0, uint32_t count, unsigned long long* __restrict__ acc)
+{
+    constexpr int MT = md_mt(TP);
+    constexpr int NU = TP * 8 * 64;                   // 16-byte units of digits per slice
+    constexpr int UPT = NU / (MD_WAVES * 64);         // of them per thread when staging
+    __shared__ rl_v4i stage[2][NU];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t s0 = blockIdx.y * sub_per, s1 = min(n_sub, s0 + sub_per);
+    if (s0 >= s1) return; // (uniform)
+    const uint32_t tw = t0 + (uint32_t)MT * (MD_WAVES * blockIdx.x + wave); // this wave's first marker tile
+    const bool wave_on = tw < t1;                                            // (wave-uniform)
+    const uint32_t c = lane & 15u, g = lane >> 4;
+    const uint32_t nu = (uint32_t)ntp * 8u * 64u;     // units staged
+
+    rl_v4i pre[UPT];
+    auto load_digits = [&](uint32_t sub) {
+        const rl_v4i* src = img + ((size_t)sub * tiles + (uint32_t)tv0) * 8u * 64u;
+#pragma unroll
+        for (int k = 0; k < UPT; ++k) {
+            const uint32_t u = tid + (uint32_t)k * (MD_WAVES * 64);
+            pre[k] = u < nu ? src[u] : rl_v4i{0, 0, 0, 0};
+        }
+    };
+    auto store_digits = [&](int buf) {
+#pragma unroll
+        for (int k = 0; k < UPT; ++k) stage[buf][tid + (uint32_t)k * (MD_WAVES * 64)] = pre[k];
+    };
+    uint4 cw[MT][2];
+    auto load_codes = [&](uint32_t sub, uint4 (&dst)[MT][2]) {
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            const uint32_t j = 16u * (tw + (uint32_t)m) + c;
+            uint4 a = make_uint4(0u, 0u, 0u, 0u), b = a; // (markers past M: code 0, never written out)
+            if (wave_on && j < M) {
+                const uint4* p = reinterpret_cast<const uint4*>(bed + (uint64_t)j * stride + (uint64_t)sub * (MD_SUBD * 4) + g * 32u);
+                a = p[0];
+                b = p[1];
+            }
+            dst[m][0] = a;
+            dst[m][1] = b;
+        }
+    };
+
+    rl_v4i D[MT][TP], R[MT][MISS ? TP : 1];
+    bool tm[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+        tm[m] = MISS && wave_on && tw + (uint32_t)m < t1 && tmiss[tw + (uint32_t)m];
+#pragma unroll
+        for (int t = 0; t < TP; ++t) {
+            D[m][t] = rl_v4i{0, 0, 0, 0};
+            if constexpr (MISS) R[m][t] = rl_v4i{0, 0, 0, 0};
+        }
+    }
+
+    load_digits(s0);
+    store_digits(0);
+    load_codes(s0, cw);
+    __syncthreads();
+    for (uint32_t sub = s0; sub < s1; ++sub) {
+        const int buf = (int)((sub - s0) & 1u);
+        const bool more = sub + 1u < s1;
+        uint4 nw[MT][2];
+        if (more) {
+            load_digits(sub + 1u);
+            load_codes(sub + 1u, nw);
+        }
+        if (wave_on) {
+#pragma unroll
+            for (int s = 0; s < 8; ++s) {
+                rl_v4i z[MT];
+#pragma unroll
+                for (int m = 0; m < MT; ++m) {
+                    const uint4 v = cw[m][s >> 2];
+                    const uint32_t x = (s & 3) == 0 ? v.x : (s & 3) == 1 ? v.y : (s & 3) == 2 ? v.z : v.w;
+                    z[m] = rl_expand16(x);
+                }
+#pragma unroll
+                for (int t = 0; t < TP; ++t) {
+                    if (t < ntp) { // (uniform)
+                        const rl_v4i A = stage[buf][(t * 8 + s) * 64 + (int)lane];
+#pragma unroll
+                        for (int m = 0; m < MT; ++m) {
+                            D[m][t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A, z[m], D[m][t], 0, 0, 0);
+                            if constexpr (MISS) {
+                                if (tm[m]) { // (wave-uniform) the tile holds a column with missing calls
+                                    rl_v4i zm;
+                                    zm.x = z[m].x & (z[m].x >> 1);
+                                    zm.y = z[m].y & (z[m].y >> 1);
+                                    zm.z = z[m].z & (z[m].z >> 1);
+                                    zm.w = z[m].w & (z[m].w >> 1);
+                                    R[m][t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A, zm, R[m][t], 0, 0, 0);
+                                }
+                            }
+                        }
+                    }
+                }
+            }
+        }
+        if (more) {
+            store_digits(buf ^ 1);
+#pragma unroll
+            for (int m = 0; m < MT; ++m) {
+                cw[m][0] = nw[m][0];
+                cw[m][1] = nw[m][1];
+            }
+        }
+        __syncthreads();
+    }
+    if (!wave_on) return;
+
+    // lane (c, g), tile t, register r: digit (4 g + r) mod 8 of vector 2 (tv0 + t) + (g >> 1) against marker 16 (tw + m) + c
+    auto put = [&](const rl_v4i& a) {
+        return (long long)a[0] + ((long long)a[1] << 8) + ((long long)a[2] << 16) + ((long long)a[3] << 24);
+    };
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+        const uint32_t j = 16u * (tw + (uint32_t)m) + c;
+        if (j < m0 || j - m0 >= count || j >= M) continue;
+#pragma unroll
+        for (int t = 0; t < TP; ++t) {
+            const uint32_t k = 2u * (uint32_t)(tv0 + t) + (g >> 1);
+            if (t >= ntp || k >= (uint32_t)K) continue;
+            unsigned long long* p = acc + ((uint64_t)(j - m0) * (uint32_t)K + k) * 4u + (g & 1u);
+            const long long v = put(D[m][t]);
+            if (v) __hip_atomic_fetch_add(p, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if constexpr (MISS) {
+                if (tm[m]) {
+                    const long long w = put(R[m][t]);
+                    if (w) __hip_atomic_fetch_add(p + 2, (unsigned long long)w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            }
+        }
+    }
+}
+
+// (hi 2^32 + lo) 2^-E as ONE rounding: carry the low word's high bits into hi (exact), then hi 2^32 is exact in f64
+__device__ __forceinline__ double md_round(long long hi, long long lo, int E)
+{
+    hi += lo >> 32;
+    lo &= 0xFFFFFFFFll;
+    return ldexp(ldexp((double)hi, 32) + (double)lo, -E);
+}
+
+// One thread per (marker, vector): P = D - 3 R, Q = sum_all q - R, each rounded once; x_j'u_k = mstd (P - mave Q)
+__global__ __launch_bounds__(MD_TPB) void k_mdots_final(const unsigned long long* __restrict__ acc, const unsigned long long* __restrict__ ksum,
+                                                        const int* __restrict__ scale, const double* __restrict__ mave,
+                                                        const double* __restrict__ mstd, uint32_t m0, uint32_t count, int K,
+                                                        double* __restrict__ out, double* __restrict__ raw)
+{
+    const uint64_t e = (uint64_t)blockIdx.x * MD_TPB + threadIdx.x;
+    if (e >= (uint64_t)count * (uint32_t)K) return;
+    const uint32_t j = m0 + (uint32_t)(e / (uint32_t)K), k = (uint32_t)(e % (uint32_t)K);
+    const unsigned long long* a = acc + 4u * e;
+    const unsigned long long Rlo = a[2], Rhi = a[3];
+    const long long Plo = (long long)(a[0] - 3ull * Rlo), Phi = (long long)(a[1] - 3ull * Rhi);
+    const long long Qlo = (long long)(ksum[2u * k + 1u] - Rlo), Qhi = (long long)(ksum[2u * k] - Rhi);
+    const int E = scale[k];
+    const double P = md_round(Phi, Plo, E), Q = md_round(Qhi, Qlo, E);
+    const double sd = mstd[j];
+    out[e] = isfinite(sd) ? sd * (P - mave[j] * Q) : __builtin_nan("");
+    if (raw) {
+        raw[2u * e] = P;
+        raw[2u * e + 1u] = Q;
+    }
+}
+
+} // namespace
+
+template <int TP>
+static void mdots_launch(hgibbs_ctx* h, dim3 grid, uint32_t t0, uint32_t t1, uint32_t sub_per, uint32_t n_sub, const rl_v4i* img, int tiles,
+                         int tv0, int ntp, int K, const uint8_t* tmiss, uint32_t m0, uint32_t count, unsigned long long* acc)
+{
+    if (h->any_missing)
+        k_mdots<TP, true><<<grid, MD_WAVES * 64, 0, h->stream>>>(h->bed, h->stride, h->M, t0, t1, sub_per, n_sub, img, tiles, tv0, ntp, K, tmiss, m0, count, acc);
+    else
+        k_mdots<TP, false><<<grid, MD_WAVES * 64, 0, h->stream>>>(h->bed, h->stride, h->M, t0, t1, sub_per, n_sub, img, tiles, tv0, ntp, K, tmiss, m0, count, acc);
+}
+
+extern "C" int hgibbs_marker_dots(hgibbs_t h, uint32_t m0, uint32_t count, int K, const double* U, double* out, double* raw)
+{
+    if (!h) return fail("hgibbs_marker_dots: null handle");
+    if (!h->bed) return fail("hgibbs_marker_dots: no genotypes loaded on this handle");
+    if (h->nranks > 1 || h->comm) return fail("hgibbs_marker_dots: one rank only (this handle has %d): the dots are not summed over ranks", h->nranks);
+    if (K <= 0 || K > MD_KMAX) return fail("hgibbs_marker_dots: K = %d, must be in [1, %d]", K, MD_KMAX);
+    if (!U || !out) return fail("hgibbs_marker_dots: null argument");
+    if ((uint64_t)m0 + count > h->M) return fail("hgibbs_marker_dots: markers [%u, %llu) out of range (M = %u)", m0, (unsigned long long)m0 + count, h->M);
+    if (h->n_local >= MD_NMAX) return fail("hgibbs_marker_dots: %u individuals, at most %u (64-bit sums)", h->n_local, MD_NMAX - 1u);
+    const uint32_t n = h->n_local;
+    for (size_t i = 0; i < (size_t)K * n; ++i)
+        if (!std::isfinite(U[i])) return fail("hgibbs_marker_dots: U[%d][%zu] = %g is not finite", (int)(i / n), i % n, U[i]);
+    if (count == 0) return 0;
+    HIP_TRY(hipSetDevice(h->device));
+    if (compute_stats(h)) return 1;
+    const uint32_t M = h->M, ntile = (M + 15u) / 16u;
+
+    // tiles of sixteen markers with a missing call in a column (the counts of hgibbs_marker_stats)
+    std::vector<uint8_t> tmiss(ntile, 0);
+    {
+        std::vector<unsigned long long> cts((size_t)M * 3);
+        HIP_TRY(hipMemcpy(cts.data(), h->counts, cts.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        for (uint32_t j = 0; j < M; ++j)
+            if (cts[3ull * j + 2]) tmiss[j / 16u] = 1;
+    }
+
+    const int tiles = (K + 1) / 2;
+    const uint32_t n_sub = (n + MD_SUBI - 1) / MD_SUBI; // slices that hold individuals (all inside n_pad, a multiple of 4096)
+    struct Bufs {
+        double *U = nullptr, *out = nullptr, *raw = nullptr;
+        unsigned long long *maxbits = nullptr, *acc = nullptr;
+        uint32_t* bad = nullptr;
+        int* scale = nullptr;
+        rl_v4i* img = nullptr;
+        uint8_t* tmiss = nullptr;
+        ~Bufs()
+        {
+            void* p[] = {U, out, raw, maxbits, acc, bad, scale, img, tmiss}; // (ksum lies inside maxbits)
+            for (void* x : p)
+                if (x) (void)hipFree(x);
+        }
+    } b;
+    const size_t nk = (size_t)count * K;
+    HIP_TRY(hipMalloc(&b.U, (size_t)K * n * sizeof(double)));
+    HIP_TRY(hipMalloc(&b.maxbits, (size_t)K * 3 * sizeof(unsigned long long))); // max, then the two halves of sum_i q
+    unsigned long long* ksum = b.maxbits + K;
+    HIP_TRY(hipMalloc(&b.bad, sizeof(uint32_t)));
+    HIP_TRY(hipMalloc(&b.scale, (size_t)K * sizeof(int)));
+    HIP_TRY(hipMalloc(&b.img, (size_t)n_sub * tiles * 8 * 64 * sizeof(rl_v4i)));
+    HIP_TRY(hipMalloc(&b.tmiss, tmiss.size()));
+    HIP_TRY(hipMalloc(&b.acc, nk * 4 * sizeof(unsigned long long)));
+    HIP_TRY(hipMalloc(&b.out, nk * sizeof(double)));
+    if (raw) HIP_TRY(hipMalloc(&b.raw, nk * 2 * sizeof(double)));
+    HIP_TRY(hipMemcpyAsync(b.U, U, (size_t)K * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(b.tmiss, tmiss.data(), tmiss.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemsetAsync(b.bad, 0, sizeof(uint32_t), h->stream));
+    HIP_TRY(hipMemsetAsync(b.maxbits, 0, (size_t)K * 3 * sizeof(unsigned long long), h->stream));
+    HIP_TRY(hipMemsetAsync(b.acc, 0, nk * 4 * sizeof(unsigned long long), h->stream));
+
+    // device time from here to the rounded result: every kernel of the call, not the host copies around it
+    HIP_TRY(hipEventRecord(h->ev0, h->stream));
+    {
+        // the scales and sum_i q of hgibbs_score, with a = o = u_k (vectors of n_local entries)
+        const uint32_t per = std::max<uint32_t>(1u, std::min<uint32_t>((n + 2047u) / 2048u, (2048u + (uint32_t)K - 1u) / (uint32_t)K));
+        k_score_max<<<dim3(K, per), SC_TPB, 0, h->stream>>>(b.U, b.U, n, b.maxbits, b.bad);
+        HIP_TRY(hipGetLastError());
+        k_score_ksum<<<dim3(K, per), SC_TPB, 0, h->stream>>>(b.U, n, b.maxbits, b.scale, ksum);
+        HIP_TRY(hipGetLastError());
+        k_mdots_digits<<<dim3(n_sub * 8u, tiles), 64, 0, h->stream>>>(b.U, n, K, tiles, b.scale, b.img);
+        HIP_TRY(hipGetLastError());
+    }
+    const uint32_t t0 = m0 / 16u, t1 = (m0 + count - 1u) / 16u + 1u;
+    for (int tv0 = 0; tv0 < tiles; tv0 += MD_TPMAX) {
+        const int ntp = std::min(MD_TPMAX, tiles - tv0);
+        const int tp = ntp <= 1 ? 1 : ntp <= 2 ? 2 : 4;
+        const uint32_t per_wg = (uint32_t)(MD_WAVES * md_mt(tp)); // marker tiles per workgroup
+        const uint32_t gx = (t1 - t0 + per_wg - 1u) / per_wg;
+        // individual ranges: enough workgroups for eight per compute unit (option mdots_split fixes the number), no range above MD_SUB_MAX slices
+        uint32_t gy = h->mdots_split ? (uint32_t)h->mdots_split : (8u * (uint32_t)h->num_cu + gx - 1u) / gx;
+        gy = std::max(gy, (n_sub + MD_SUB_MAX - 1u) / MD_SUB_MAX);
+        gy = std::max(1u, std::min(gy, n_sub));
+        const uint32_t sub_per = (n_sub + gy - 1u) / gy;
+        gy = (n_sub + sub_per - 1u) / sub_per;
+        const dim3 grid(gx, gy);
+        switch (tp) {
+        case 1: mdots_launch<1>(h, grid, t0, t1, sub_per, n_sub, b.img, tiles, tv0, ntp, K, b.tmiss, m0, count, b.acc); break;
+        case 2: mdots_launch<2>(h, grid, t0, t1, sub_per, n_sub, b.img, tiles, tv0, ntp, K, b.tmiss, m0, count, b.acc); break;
+        default: mdots_launch<4>(h, grid, t0, t1, sub_per, n_sub, b.img, tiles, tv0, ntp, K, b.tmiss, m0, count, b.acc); break;
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    k_mdots_final<<<(uint32_t)((nk + MD_TPB - 1) / MD_TPB), MD_TPB, 0, h->stream>>>(b.acc, ksum, b.scale, h->mave, h->mstd, m0, count, K, b.out, b.raw);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev1, h->stream));
+    HIP_TRY(hipEventSynchronize(h->ev1));
+    HIP_TRY(hipMemcpy(out, b.out, nk * sizeof(double), hipMemcpyDeviceToHost));
+    if (raw) HIP_TRY(hipMemcpy(raw, b.raw, nk * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    h->mdots_ms = ms;
+    return 0;
+}
+
+extern "C" int hgibbs_last_marker_dots_ms(hgibbs_t h, double* ms)
+{
+    if (!h || !ms) return fail("hgibbs_last_marker_dots_ms: null argument");
+    *ms = h->mdots_ms;
+    return 0;
+}

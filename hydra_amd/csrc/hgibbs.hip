@@ -184,6 +184,8 @@ struct hgibbs_ctx {
     double score_ms = 0.0; // device time of the last hgibbs_score (weights to digits, products, rounding)
     int ld_split = 0;      // option ld_split: ranges of individuals the workgroups of hgibbs_ld split the columns into (0 = automatic)
     double ld_ms = 0.0;    // device time of the last hgibbs_ld (every piece: zeroing, products, final formula)
+    int mdots_split = 0;   // option mdots_split: ranges of individuals the workgroups of hgibbs_marker_dots split the columns into (0 = automatic)
+    double mdots_ms = 0.0; // device time of the last hgibbs_marker_dots (scales, digits, products, rounding)
 };
 
 static int ensure_scratch(hgibbs_ctx* h, size_t n)
@@ -1216,6 +1218,9 @@ int hgibbs_set_option(hgibbs_t h, const char* name, int64_t value)
     } else if (!std::strcmp(name, "ld_split")) {
         if (value < 0 || value > 65535) return fail("ld_split must be in [0,65535] (0 = automatic)");
         h->ld_split = (int)value;
+    } else if (!std::strcmp(name, "mdots_split")) {
+        if (value < 0 || value > 65535) return fail("mdots_split must be in [0,65535] (0 = automatic)");
+        h->mdots_split = (int)value;
     } else if (!std::strcmp(name, "score_ranges")) {
         if (value < 0 || value > 65535) return fail("score_ranges must be in [0,65535] (0 = automatic)");
         h->score_ranges = (int)value;
@@ -2029,3 +2034,4 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
 #include "hg_bayesw.hip.h"
 #include "hg_score.hip.h"
 #include "hg_ld.hip.h"
+#include "hg_mdots.hip.h"

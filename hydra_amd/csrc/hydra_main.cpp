@@ -21,6 +21,11 @@
 // own rows and standardisation, with hgibbs_ld (run_ld), and writes the pairs with r^2 >= T as PLINK's --r
 // table to <dir>/<name>.ld (or F), and with --ld-bin the whole band as f32 to <out>.bin.
 //
+// `--assoc [--assoc-no-loco] [--assoc-out F]` appended to a bayesMPI command line samples nothing either: it tests every marker for
+// association on the chain's rows, against the scaled phenotype minus the chain's genetic value from the other chromosomes (LOCO
+// offsets from the .bet records at or after --burn-in; none with --assoc-no-loco), with the covariates projected out, through
+// hgibbs_score and hgibbs_marker_dots (run_assoc), and writes <dir>/<name>.assoc (or F).
+//
 // Not reproduced (out of scope for the hot path): sparse
 // file formats, bayesFH, marker-sharded MPI, the .lst/tarball.
 // Multi-GPU: one process per GPU (RANK/WORLD_SIZE/LOCAL_RANK in the
@@ -67,6 +72,8 @@ struct Options { // src/options.hpp:20-138 (subset that reaches bayesMPI)
     double ldWindowKb = -1.0, ldWindowR2 = 0.2;      // --ld-window-kb (-1: no bp limit), --ld-window-r2
     bool ldGiven = false, ldKbGiven = false, ldR2Given = false, ldBin = false;
     std::string ldOut;                               // --ld-out
+    bool assoc = false, assocNoLoco = false;         // --assoc: per-marker association tests; --assoc-no-loco: without LOCO offsets
+    std::string assocOut;                            // --assoc-out
     int batch = 0, cpg = 0; // tuning knobs of this build (not hydra's)
 };
 
@@ -197,6 +204,9 @@ Options parse(int argc, const char* argv[])
             o.ldR2Given = true;
         } else if (a == "--ld-out") o.ldOut = need(i);
         else if (a == "--ld-bin") o.ldBin = true;
+        else if (a == "--assoc") o.assoc = true;
+        else if (a == "--assoc-no-loco") o.assocNoLoco = true;
+        else if (a == "--assoc-out") o.assocOut = need(i);
         else if (a == "--sparse-dir" || a == "--sparse-basename" ||
                  a == "--bed-to-sparse" || a == "--sparse-sync" || a == "--bed-sync")
             fatal("FATAL  : option " + a + " belongs to a part of hydra this build does not reproduce (SURVEY.md section 2)");
@@ -887,10 +897,11 @@ BimRows read_bim(const std::string& path, size_t limit)
 
 // <dir>/<name>.bet: u32 Mtot, then (u32 iteration, Mtot f64) per thinned iteration (postproc/beta_converter.cpp); the records whose
 // iteration is at least `burnin`
-void read_bet_records(const std::string& path, unsigned Mtot, unsigned burnin, std::vector<unsigned>& its, std::vector<double>& beta)
+void read_bet_records(const std::string& path, unsigned Mtot, unsigned burnin, std::vector<unsigned>& its, std::vector<double>& beta,
+                      const char* why = "--predict-bfile scores with the chain's effects")
 {
     FILE* f = std::fopen(path.c_str(), "rb");
-    if (!f) fatal("FATAL  : can not open " + path + " (--predict-bfile scores with the chain's effects: run the chain first)");
+    if (!f) fatal("FATAL  : can not open " + path + " (" + why + ": run the chain first)");
     unsigned m = 0;
     if (std::fread(&m, sizeof m, 1, f) != 1 || m != Mtot) {
         std::fclose(f);
@@ -908,6 +919,21 @@ void read_bet_records(const std::string& path, unsigned Mtot, unsigned burnin, s
     std::fclose(f);
     if (its.empty())
         fatal("FATAL  : " + path + ": no record at or after --burn-in " + std::to_string(burnin) + " (" + std::to_string(total) + " records)");
+}
+
+// the training genotypes: M x ceil(numInds / 4) bytes of <bfile>.bed after its magic
+std::vector<uint8_t> read_training_bed(const Options& opt, unsigned numInds, unsigned Mtot)
+{
+    const size_t len = (numInds + 3) / 4;
+    std::vector<uint8_t> bed((size_t)Mtot * len);
+    std::ifstream in(opt.bedFile + ".bed", std::ios::binary);
+    if (!in) fatal("Error: can not open the file [" + opt.bedFile + ".bed] to read.");
+    unsigned char magic[3];
+    in.read((char*)magic, 3);
+    if (!in || magic[0] != 0x6c || magic[1] != 0x1b || magic[2] != 0x01) fatal("FATAL  : " + opt.bedFile + ".bed is not a SNP-major PLINK bed");
+    in.read((char*)bed.data(), (std::streamsize)bed.size());
+    if ((size_t)in.gcount() != bed.size()) fatal("FATAL  : " + opt.bedFile + ".bed is shorter than M x ceil(N/4)");
+    return bed;
 }
 
 int run_predict(const Options& opt, const std::vector<uint8_t>& keep, unsigned numInds, unsigned numNAs, unsigned Mtot, int local_rank)
@@ -990,14 +1016,7 @@ int run_predict(const Options& opt, const std::vector<uint8_t>& keep, unsigned n
     std::vector<double> mave(Mtot), mstd(Mtot);
     {
         const size_t len = (numInds + 3) / 4;
-        std::vector<uint8_t> bed((size_t)Mtot * len);
-        std::ifstream in(opt.bedFile + ".bed", std::ios::binary);
-        if (!in) fatal("Error: can not open the file [" + opt.bedFile + ".bed] to read.");
-        unsigned char magic[3];
-        in.read((char*)magic, 3);
-        if (!in || magic[0] != 0x6c || magic[1] != 0x1b || magic[2] != 0x01) fatal("FATAL  : " + opt.bedFile + ".bed is not a SNP-major PLINK bed");
-        in.read((char*)bed.data(), (std::streamsize)bed.size());
-        if ((size_t)in.gcount() != bed.size()) fatal("FATAL  : " + opt.bedFile + ".bed is shorter than M x ceil(N/4)");
+        std::vector<uint8_t> bed = read_training_bed(opt, numInds, Mtot);
         const unsigned Ntot = numInds - numNAs;
         hgibbs_t dev = nullptr;
         hg_check(hgibbs_create(local_rank, &dev), "hgibbs_create");
@@ -1081,16 +1100,7 @@ int run_ld(const Options& opt, const std::vector<uint8_t>& keep, unsigned numInd
     std::fflush(stdout);
 
     const size_t len = (numInds + 3) / 4;
-    std::vector<uint8_t> bed((size_t)Mtot * len);
-    {
-        std::ifstream in(opt.bedFile + ".bed", std::ios::binary);
-        if (!in) fatal("Error: can not open the file [" + opt.bedFile + ".bed] to read.");
-        unsigned char magic[3];
-        in.read((char*)magic, 3);
-        if (!in || magic[0] != 0x6c || magic[1] != 0x1b || magic[2] != 0x01) fatal("FATAL  : " + opt.bedFile + ".bed is not a SNP-major PLINK bed");
-        in.read((char*)bed.data(), (std::streamsize)bed.size());
-        if ((size_t)in.gcount() != bed.size()) fatal("FATAL  : " + opt.bedFile + ".bed is shorter than M x ceil(N/4)");
-    }
+    std::vector<uint8_t> bed = read_training_bed(opt, numInds, Mtot);
     struct stat sb;
     if (opt.ldOut.empty() && stat(opt.mcmcOutDir.c_str(), &sb) != 0)
         if (std::system(("mkdir -p " + opt.mcmcOutDir).c_str()) != 0) fatal("FATAL  : can not create --mcmc-out-dir");
@@ -1149,6 +1159,200 @@ int run_ld(const Options& opt, const std::vector<uint8_t>& keep, unsigned numInd
     return 0;
 }
 
+// ---- --assoc: per-marker association tests with LOCO offsets ----
+// Z'Z = L L' (Cholesky, in place, lower triangle); false when Z is rank-deficient
+bool cholesky(std::vector<double>& A, int q)
+{
+    for (int k = 0; k < q; ++k) {
+        const double d0 = A[(size_t)k * q + k];
+        double d = d0;
+        for (int p = 0; p < k; ++p) d -= A[(size_t)k * q + p] * A[(size_t)k * q + p];
+        if (!(d > 1e-12 * d0)) return false;
+        d = std::sqrt(d);
+        A[(size_t)k * q + k] = d;
+        for (int i = k + 1; i < q; ++i) {
+            double v = A[(size_t)i * q + k];
+            for (int p = 0; p < k; ++p) v -= A[(size_t)i * q + p] * A[(size_t)k * q + p];
+            A[(size_t)i * q + k] = v / d;
+        }
+    }
+    return true;
+}
+
+// x = (L L')^-1 b
+std::vector<double> chol_solve(const std::vector<double>& L, int q, std::vector<double> b)
+{
+    for (int i = 0; i < q; ++i) {
+        for (int p = 0; p < i; ++p) b[i] -= L[(size_t)i * q + p] * b[p];
+        b[i] /= L[(size_t)i * q + i];
+    }
+    for (int i = q - 1; i >= 0; --i) {
+        for (int p = i + 1; p < q; ++p) b[i] -= L[(size_t)p * q + i] * b[p];
+        b[i] /= L[(size_t)i * q + i];
+    }
+    return b;
+}
+
+int run_assoc(const Options& opt, const std::vector<uint8_t>& keep, const std::vector<double>& y_raw, const std::vector<double>& covX, int C,
+              unsigned numInds, unsigned numNAs, unsigned Mtot, int local_rank)
+{
+    const std::string base = opt.mcmcOutDir + "/" + opt.mcmcOutNam;
+    const std::string out = opt.assocOut.empty() ? base + ".assoc" : opt.assocOut;
+    const bool loco = !opt.assocNoLoco;
+    const BimRows bim = read_bim(opt.bedFile + ".bim", Mtot);
+    const unsigned N = numInds - numNAs;
+    const int q = 1 + C;
+
+    // maximal runs of equal chromosome in .bim order (an unsorted .bim works); chromosome c(j) as an index
+    std::map<std::string, int> chrom_idx;
+    std::vector<int> cj(Mtot);
+    std::vector<unsigned> runs; // first marker of each run, then Mtot
+    for (unsigned j = 0; j < Mtot; ++j) {
+        cj[j] = chrom_idx.emplace(bim.chr[j], (int)chrom_idx.size()).first->second;
+        if (j == 0 || bim.chr[j] != bim.chr[j - 1]) runs.push_back(j);
+    }
+    const size_t nruns = runs.size(), nchrom = chrom_idx.size();
+    runs.push_back(Mtot);
+    std::vector<unsigned> its;
+    std::vector<double> betas;
+    if (loco) read_bet_records(base + ".bet", Mtot, opt.burnin, its, betas, "--assoc takes its LOCO offsets from the chain's effects");
+    std::printf("ASSOC  : %u markers, %zu chromosomes in %zu runs, %d covariates, %u individuals -> %s\n", Mtot, nchrom, nruns, C, N, out.c_str());
+    if (loco)
+        std::printf("ASSOC  : LOCO offsets from %zu records of %s (iterations %u .. %u)\n", its.size(), (base + ".bet").c_str(), its.front(), its.back());
+    else
+        std::printf("ASSOC  : no LOCO offsets (--assoc-no-loco): every chromosome is tested against the scaled phenotype\n");
+    if (loco && nchrom == 1) std::printf("WARNING: --assoc with one chromosome: G - G_c is 0, no offset is taken out\n");
+    std::fflush(stdout);
+    if ((long long)N <= (long long)q + 1) fatal("FATAL  : --assoc needs more individuals (" + std::to_string(N) + ") than covariates + 2");
+
+    // the chain's scaled phenotype (hydra_chain.cpp: centre, then y'y = N - 1) and Z = [1 | covariates]
+    std::vector<double> y(y_raw);
+    {
+        double mean = 0.0;
+        for (unsigned i = 0; i < N; ++i) mean += y[i];
+        mean /= N;
+        for (unsigned i = 0; i < N; ++i) y[i] -= mean;
+        double sqn = 0.0;
+        for (unsigned i = 0; i < N; ++i) sqn += y[i] * y[i];
+        sqn = std::sqrt((double)(N - 1) / sqn);
+        for (unsigned i = 0; i < N; ++i) y[i] *= sqn;
+    }
+    std::vector<double> Z((size_t)q * N); // column-major: Z[c * N + i]
+    for (unsigned i = 0; i < N; ++i) {
+        Z[i] = 1.0;
+        for (int c = 0; c < C; ++c) Z[(size_t)(1 + c) * N + i] = covX[(size_t)i * C + c];
+    }
+    std::vector<double> L((size_t)q * q);
+    for (int a = 0; a < q; ++a)
+        for (int b = 0; b < q; ++b) {
+            double v = 0.0;
+            for (unsigned i = 0; i < N; ++i) v += Z[(size_t)a * N + i] * Z[(size_t)b * N + i];
+            L[(size_t)a * q + b] = v;
+        }
+    if (!cholesky(L, q)) fatal("FATAL  : --assoc: the covariates are rank-deficient (Z = [1 | covariates] has dependent columns)");
+    auto project = [&](std::vector<double>& v) { // v <- v - Z (Z'Z)^-1 Z'v
+        std::vector<double> w(q, 0.0);
+        for (int a = 0; a < q; ++a)
+            for (unsigned i = 0; i < N; ++i) w[a] += Z[(size_t)a * N + i] * v[i];
+        w = chol_solve(L, q, w);
+        for (int a = 0; a < q; ++a)
+            for (unsigned i = 0; i < N; ++i) v[i] -= Z[(size_t)a * N + i] * w[a];
+    };
+
+    const size_t len = (numInds + 3) / 4;
+    std::vector<uint8_t> bed = read_training_bed(opt, numInds, Mtot);
+    struct stat sb;
+    if (opt.assocOut.empty() && stat(opt.mcmcOutDir.c_str(), &sb) != 0)
+        if (std::system(("mkdir -p " + opt.mcmcOutDir).c_str()) != 0) fatal("FATAL  : can not create --mcmc-out-dir");
+    FILE* f = std::fopen(out.c_str(), "w");
+    if (!f) fatal("FATAL  : can not create " + out);
+    std::fprintf(f, "CHR SNP BP A1 A2 FREQ N BETA SE CHISQ P\n");
+
+    // the chain's rows and standardisation
+    hgibbs_t dev = nullptr;
+    hg_check(hgibbs_create(local_rank, &dev), "hgibbs_create");
+    hg_check(hgibbs_load_bed(dev, bed.data(), len, numInds, Mtot, numNAs ? keep.data() : nullptr, 0, N, N), "hgibbs_load_bed");
+    std::vector<uint8_t>().swap(bed);
+    std::vector<double> mave(Mtot), mstd(Mtot);
+    std::vector<uint64_t> n1(Mtot), n2(Mtot), nmiss(Mtot);
+    hg_check(hgibbs_marker_stats(dev, mave.data(), mstd.data(), n1.data(), n2.data(), nmiss.data()), "hgibbs_marker_stats");
+    double ms = 0.0;
+
+    // r_c = y - (G - G_c), projected off Z: G_c from hgibbs_score with one "sample" per chromosome
+    std::vector<std::vector<double>> r(loco ? nchrom : 1, y);
+    if (loco) {
+        const size_t S = its.size();
+        std::vector<double> bbar(Mtot, 0.0);
+        for (size_t s = 0; s < S; ++s)
+            for (unsigned j = 0; j < Mtot; ++j) bbar[j] += betas[s * Mtot + j];
+        for (unsigned j = 0; j < Mtot; ++j) bbar[j] /= (double)S;
+        std::vector<double> a(nchrom * Mtot, 0.0), o(nchrom * Mtot, 0.0), Gc((size_t)N * nchrom);
+        for (unsigned j = 0; j < Mtot; ++j) {
+            if (!std::isfinite(mstd[j])) continue; // (score refuses non-finite weights; x = 0 there anyway)
+            a[(size_t)cj[j] * Mtot + j] = bbar[j] * mstd[j];
+            o[(size_t)cj[j] * Mtot + j] = -bbar[j] * mstd[j] * mave[j];
+        }
+        hg_check(hgibbs_score(dev, (int)nchrom, a.data(), o.data(), Gc.data()), "hgibbs_score");
+        double t = 0.0;
+        hg_check(hgibbs_last_score_ms(dev, &t), "hgibbs_last_score_ms");
+        ms += t;
+        for (unsigned i = 0; i < N; ++i) {
+            double G = 0.0;
+            for (size_t c = 0; c < nchrom; ++c) G += Gc[(size_t)i * nchrom + c];
+            for (size_t c = 0; c < nchrom; ++c) r[c][i] = y[i] - (G - Gc[(size_t)i * nchrom + c]);
+        }
+    }
+    std::vector<double> rr(r.size(), 0.0);
+    for (size_t c = 0; c < r.size(); ++c) {
+        project(r[c]);
+        for (unsigned i = 0; i < N; ++i) rr[c] += r[c][i] * r[c][i];
+    }
+
+    // one hgibbs_marker_dots per run: U = [r_c, columns of Z] gives s = x_j'r_c and t = Z'x_j
+    const int K = 1 + q;
+    std::vector<double> U((size_t)K * N), dots;
+    std::copy(Z.begin(), Z.end(), U.begin() + N);
+    const double dof = (double)N - (double)q - 1.0;
+    unsigned long long written = 0;
+    for (size_t ru = 0; ru < nruns; ++ru) {
+        const unsigned m0 = runs[ru], cnt = runs[ru + 1] - runs[ru];
+        const size_t c = loco ? (size_t)cj[m0] : 0;
+        std::copy(r[c].begin(), r[c].end(), U.begin());
+        dots.resize((size_t)cnt * K);
+        hg_check(hgibbs_marker_dots(dev, m0, cnt, K, U.data(), dots.data(), nullptr), "hgibbs_marker_dots");
+        double t = 0.0;
+        hg_check(hgibbs_last_marker_dots_ms(dev, &t), "hgibbs_last_marker_dots_ms");
+        ms += t;
+        for (unsigned jj = 0; jj < cnt; ++jj) {
+            const unsigned j = m0 + jj;
+            const double m = mave[j], sd = mstd[j];
+            const unsigned long long called = (unsigned long long)N - nmiss[j];
+            const double n0 = (double)(called - n1[j] - n2[j]);
+            const double xx = sd * sd * ((double)n1[j] * (1.0 - m) * (1.0 - m) + (double)n2[j] * (2.0 - m) * (2.0 - m) + n0 * m * m);
+            const double s = dots[(size_t)jj * K];
+            std::vector<double> tz(dots.begin() + (size_t)jj * K + 1, dots.begin() + (size_t)(jj + 1) * K);
+            const std::vector<double> w = chol_solve(L, q, tz);
+            double v = xx;
+            for (int a = 0; a < q; ++a) v -= tz[a] * w[a];
+            std::fprintf(f, "%s %s %lld %s %s %.12g %llu ", bim.chr[j].c_str(), bim.id[j].c_str(), bim.bp[j], bim.a1[j].c_str(), bim.a2[j].c_str(),
+                         m / 2.0, called);
+            if (!std::isfinite(sd) || !(v > 1e-9 * xx)) std::fprintf(f, "NA NA NA NA\n");
+            else {
+                const double b = s / v;
+                const double s2 = (rr[c] - s * s / v) / dof;
+                const double se = std::sqrt(s2 / v);
+                const double chisq = b * b / (se * se);
+                std::fprintf(f, "%.12g %.12g %.12g %.12g\n", b * sd, se * sd, chisq, std::erfc(std::sqrt(chisq / 2.0)));
+            }
+            ++written;
+        }
+    }
+    hgibbs_destroy(dev);
+    if (std::fclose(f) != 0) fatal("FATAL  : short write on " + out);
+    std::printf("ASSOC  : wrote %llu rows to %s (%.3f ms on the device)\n", written, out.c_str(), ms);
+    return 0;
+}
+
 } // namespace
 
 int main(int argc, const char* argv[])
@@ -1191,6 +1395,14 @@ int main(int argc, const char* argv[])
         if (nranks > 1) fatal("FATAL  : --predict-bfile runs on one process (WORLD_SIZE = " + std::to_string(nranks) + ")");
     } else if (!opt.predictOut.empty() || opt.predictDryRun)
         fatal(std::string("FATAL  : ") + (opt.predictDryRun ? "--predict-dry-run" : "--predict-out") + " needs --predict-bfile");
+    if (opt.assoc) {
+        if (opt.bayesType == "bayesWMPI") fatal("FATAL  : --assoc takes a bayesMPI command line, not --mpibayes bayesWMPI");
+        if (!opt.predictBfile.empty()) fatal("FATAL  : --assoc cannot be combined with --predict-bfile");
+        if (opt.ldGiven) fatal("FATAL  : --assoc cannot be combined with --ld-window");
+        if (opt.restart) fatal("FATAL  : --assoc does not sample: it cannot be combined with --restart");
+        if (nranks > 1) fatal("FATAL  : --assoc runs on one process (WORLD_SIZE = " + std::to_string(nranks) + ")");
+    } else if (!opt.assocOut.empty() || opt.assocNoLoco)
+        fatal(std::string("FATAL  : ") + (!opt.assocOut.empty() ? "--assoc-out" : "--assoc-no-loco") + " needs --assoc");
     if (opt.bayesType == "bayesWMPI") return run_bayesw(opt, rank, nranks, local_rank); // main.cpp:164-167
 
     // ---- inputs (main.cpp:69-70,88; BayesRRm.cpp:969-997) -------------------
@@ -1220,6 +1432,7 @@ int main(int argc, const char* argv[])
     }
     if (!opt.predictBfile.empty()) return run_predict(opt, keep, (unsigned)numInds, numNAs, Mtot, local_rank);
     if (opt.ldGiven) return run_ld(opt, keep, (unsigned)numInds, numNAs, Mtot, local_rank);
+    if (opt.assoc) return run_assoc(opt, keep, y, covX, C, (unsigned)numInds, numNAs, Mtot, local_rank);
 
     std::vector<int32_t> groups;
     std::vector<std::vector<double>> mS;

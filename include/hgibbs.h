@@ -258,6 +258,22 @@ int hgibbs_ld(hgibbs_t h, uint32_t m0, uint32_t count, uint32_t W, double* r_hos
 /* device time of the last hgibbs_ld in ms: every kernel of the call (zeroing, products, final formula), not the host copies */
 int hgibbs_last_ld_ms(hgibbs_t h, double* ms);
 
+/* ---- dots of the loaded markers against dense vectors */
+/* For markers j in [m0, m0 + count) of the loaded BED and K vectors u_k over this rank's n_local individuals:
+ *   out[(j - m0)*K + k]           = x_j'u_k = mstd_j (P_jk - mave_j Q_jk)      (NaN where mstd_j is not finite)
+ *   raw[((j - m0)*K + k)*2 + 0/1] = P_jk = sum_{i called} g_ij u_ik,  Q_jk = sum_{i called} u_ik
+ * U: K x n_local row-major (U[k*n_local + i]).  raw may be NULL.
+ * x is the chain's standardised genotype (x = 0 at a missing call), g in {0, 1, 2} the genotype as hgibbs_load_bed reads it.  Each
+ * vector gets one scale, E_k = 52 - e_k with max_i |u_ik| < 2^e_k (E_k = 0 for an all-zero vector), and q = llrint(u 2^E_k); P and Q
+ * are the exact integer sums of the q's, each rounded to f64 once (times 2^-E_k).  The only error is the rounding of u:
+ * |P - sum g u| <= n 2^-E_k <= 2 n max|u_k| 2^-52 and |Q - sum u| <= n max|u_k| 2^-52 before that one rounding, so the results are
+ * bit-identical for any m0 / count chunking, any value of the option mdots_split (ranges of individuals split over workgroups,
+ * 0 = automatic) and any repeat.  Needs the marker stats (computed here when they are not).  Refused: K <= 0 or K > 32 (the LDS
+ * staging takes four tiles of two vectors a pass, at most four passes), a non-finite entry of U, m0 + count > M, a handle without
+ * genotypes, several ranks, n_local >= 2^29. */
+int hgibbs_marker_dots(hgibbs_t h, uint32_t m0, uint32_t count, int K, const double* U, double* out, double* raw);
+int hgibbs_last_marker_dots_ms(hgibbs_t h, double* ms);   /* every kernel of the last call, not the host copies */
+
 /* ======================================================================== */
 /* Host driver: the body of BayesRRm::runMpiGibbs (src/BayesRRm.cpp:933-2939)
  * for --mpibayes bayesMPI, restated on top of hgibbs_*.                     */
