@@ -22,7 +22,7 @@ ABI_SYMBOLS = [
     "hgibbs_beta_sqnorm", "hgibbs_sweep", "hgibbs_set_option", "hgibbs_last_sweep_stats", "hgibbs_stream_ceiling", "hgibbs_debug_times", "hgibbs_resident_trace", "hydra_chain_create",
     "hydra_chain_destroy", "hydra_chain_iterate", "hydra_chain_state", "hydra_chain_csv_line", "hydra_chain_order",
     "hydra_chain_last_nnz", "hgibbs_score", "hgibbs_last_score_ms", "hgibbs_ld", "hgibbs_last_ld_ms",
-    "hgibbs_marker_dots", "hgibbs_last_marker_dots_ms",
+    "hgibbs_marker_dots", "hgibbs_last_marker_dots_ms", "hgibbs_king", "hgibbs_king_pairs", "hgibbs_king_pairs_get", "hgibbs_last_king_ms",
     # BayesW
     "hgibbs_grand_seed", "hgibbs_grand_next", "hgibbs_ars_sample", "hgibbs_w_init", "hgibbs_w_marker_stats", "hgibbs_w_set_model",
     "hgibbs_w_reduce", "hgibbs_w_refresh_vi", "hgibbs_w_get_vi", "hgibbs_w_marker_sums", "hgibbs_w_sweep", "hgibbs_w_last_sweep_stats", "hgibbs_w_ars_device_probe",
@@ -186,6 +186,10 @@ def lib():
     L.hgibbs_last_ld_ms.argtypes = [vp, dp]
     L.hgibbs_marker_dots.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_int, dp, dp, dp]
     L.hgibbs_last_marker_dots_ms.argtypes = [vp, dp]
+    L.hgibbs_king.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32)]
+    L.hgibbs_king_pairs.argtypes = [vp, C.c_double, C.POINTER(C.c_uint64)]
+    L.hgibbs_king_pairs_get.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), dp]
+    L.hgibbs_last_king_ms.argtypes = [vp, dp]
     _lib = L
     return L
 
@@ -415,6 +419,34 @@ class Device:
     def last_marker_dots_ms(self):
         v = C.c_double()
         check(self.L.hgibbs_last_marker_dots_ms(self.h, C.byref(v)))
+        return v.value
+
+    def king(self, a0=0, acount=None, b0=0, bcount=None):
+        """KING counts of rows [a0, a0 + acount) x [b0, b0 + bcount) (hgibbs_king): int32 (acount, bcount, 5) with NSNP, HET_a,
+        HET_b, HETHET, IBS0."""
+        if acount is None:
+            acount = self.n_local - a0
+        if bcount is None:
+            bcount = self.n_local - b0
+        out = np.zeros((acount, bcount, 5), dtype=np.int32)
+        check(self.L.hgibbs_king(self.h, a0, acount, b0, bcount, out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out
+
+    def king_pairs(self, cutoff):
+        """Every pair a < b with KINSHIP >= cutoff (hgibbs_king_pairs, then hgibbs_king_pairs_get), sorted by (a, b): ab uint32 (P, 2),
+        counts int32 (P, 5), kin float64 (P,)."""
+        n = C.c_uint64()
+        check(self.L.hgibbs_king_pairs(self.h, float(cutoff), C.byref(n)))
+        P = n.value
+        ab = np.zeros((P, 2), dtype=np.uint32)
+        cnt = np.zeros((P, 5), dtype=np.int32)
+        kin = np.zeros(P)
+        check(self.L.hgibbs_king_pairs_get(self.h, ab.ctypes.data_as(C.POINTER(C.c_uint32)), cnt.ctypes.data_as(C.POINTER(C.c_int32)), _dp(kin)))
+        return ab, cnt, kin
+
+    def last_king_ms(self):
+        v = C.c_double()
+        check(self.L.hgibbs_last_king_ms(self.h, C.byref(v)))
         return v.value
 
     def debug_times(self):

@@ -186,6 +186,11 @@ struct hgibbs_ctx {
     double ld_ms = 0.0;    // device time of the last hgibbs_ld (every piece: zeroing, products, final formula)
     int mdots_split = 0;   // option mdots_split: ranges of individuals the workgroups of hgibbs_marker_dots split the columns into (0 = automatic)
     double mdots_ms = 0.0; // device time of the last hgibbs_marker_dots (scales, digits, products, rounding)
+    int king_split = 0;    // option king_split: ranges of markers the workgroups of hgibbs_king split the k dimension into (0 = automatic)
+    double king_ms = 0.0;  // device time of the last hgibbs_king / hgibbs_king_pairs (image, zeroing, products, every run of the list)
+    std::vector<uint32_t> king_ab;    // the last hgibbs_king_pairs list, sorted by (a, b): a, b per pair
+    std::vector<int32_t> king_counts; // NSNP, HET_a, HET_b, HETHET, IBS0 per pair
+    std::vector<double> king_kin;     // KINSHIP per pair
 };
 
 static int ensure_scratch(hgibbs_ctx* h, size_t n)
@@ -1218,6 +1223,9 @@ int hgibbs_set_option(hgibbs_t h, const char* name, int64_t value)
     } else if (!std::strcmp(name, "ld_split")) {
         if (value < 0 || value > 65535) return fail("ld_split must be in [0,65535] (0 = automatic)");
         h->ld_split = (int)value;
+    } else if (!std::strcmp(name, "king_split")) {
+        if (value < 0 || value > 65535) return fail("king_split must be in [0,65535] (0 = automatic)");
+        h->king_split = (int)value;
     } else if (!std::strcmp(name, "mdots_split")) {
         if (value < 0 || value > 65535) return fail("mdots_split must be in [0,65535] (0 = automatic)");
         h->mdots_split = (int)value;
@@ -2035,3 +2043,4 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
 #include "hg_score.hip.h"
 #include "hg_ld.hip.h"
 #include "hg_mdots.hip.h"
+#include "hg_king.hip.h"

@@ -26,6 +26,10 @@
 // offsets from the .bet records at or after --burn-in; none with --assoc-no-loco), with the covariates projected out, through
 // hgibbs_score and hgibbs_marker_dots (run_assoc), and writes <dir>/<name>.assoc (or F).
 //
+// `--king [--king-cutoff T] [--king-out F]` appended to a bayesMPI command line samples nothing either: it computes the KING-robust
+// kinship of every pair of the chain's rows with hgibbs_king_pairs (run_king) and writes the pairs with
+// KINSHIP >= T (default 0.0442) to <dir>/<name>.kin0 (or F).
+//
 // Not reproduced (out of scope for the hot path): sparse
 // file formats, bayesFH, marker-sharded MPI, the .lst/tarball.
 // Multi-GPU: one process per GPU (RANK/WORLD_SIZE/LOCAL_RANK in the
@@ -74,6 +78,8 @@ struct Options { // src/options.hpp:20-138 (subset that reaches bayesMPI)
     std::string ldOut;                               // --ld-out
     bool assoc = false, assocNoLoco = false;         // --assoc: per-marker association tests; --assoc-no-loco: without LOCO offsets
     std::string assocOut;                            // --assoc-out
+    bool king = false, kingCutoffGiven = false;      // --king: KING-robust kinship of the chain's rows; --king-cutoff given
+    std::string kingCutoff = "0.0442", kingOut;      // --king-cutoff T (checked before the device), --king-out
     int batch = 0, cpg = 0; // tuning knobs of this build (not hydra's)
 };
 
@@ -207,6 +213,11 @@ Options parse(int argc, const char* argv[])
         else if (a == "--assoc") o.assoc = true;
         else if (a == "--assoc-no-loco") o.assocNoLoco = true;
         else if (a == "--assoc-out") o.assocOut = need(i);
+        else if (a == "--king") o.king = true;
+        else if (a == "--king-cutoff") {
+            o.kingCutoff = need(i);
+            o.kingCutoffGiven = true;
+        } else if (a == "--king-out") o.kingOut = need(i);
         else if (a == "--sparse-dir" || a == "--sparse-basename" ||
                  a == "--bed-to-sparse" || a == "--sparse-sync" || a == "--bed-sync")
             fatal("FATAL  : option " + a + " belongs to a part of hydra this build does not reproduce (SURVEY.md section 2)");
@@ -1353,6 +1364,69 @@ int run_assoc(const Options& opt, const std::vector<uint8_t>& keep, const std::v
     return 0;
 }
 
+// ---- --king: KING-robust kinship of the chain's rows ----
+// --king-cutoff as a number: NaN unless the whole argument is one
+double king_cutoff(const Options& opt)
+{
+    const char* s = opt.kingCutoff.c_str();
+    char* end = nullptr;
+    const double v = std::strtod(s, &end);
+    return (end != s && *end == 0) ? v : std::numeric_limits<double>::quiet_NaN();
+}
+
+int run_king(const Options& opt, const std::vector<uint8_t>& keep, unsigned numInds, unsigned numNAs, unsigned Mtot, int local_rank)
+{
+    const std::string out = opt.kingOut.empty() ? opt.mcmcOutDir + "/" + opt.mcmcOutNam + ".kin0" : opt.kingOut;
+    const double cutoff = king_cutoff(opt);
+    // FID and IID of the chain's rows (NA phenotype, and NA covariate rows with --covariates, dropped), in .fam order
+    std::vector<std::string> fid, iid;
+    {
+        std::ifstream in(opt.bedFile + ".fam");
+        if (!in) fatal("Error: can not open the file [" + opt.bedFile + ".fam] to read.");
+        std::string f, i, dad, mom, sex, phen;
+        for (unsigned r = 0; r < numInds && (in >> f >> i >> dad >> mom >> sex >> phen); ++r)
+            if (!numNAs || keep[r]) {
+                fid.push_back(f);
+                iid.push_back(i);
+            }
+    }
+    const unsigned Ntot = numInds - numNAs;
+    if (fid.size() != Ntot) fatal("FATAL  : " + opt.bedFile + ".fam: " + std::to_string(fid.size()) + " kept rows, expected " + std::to_string(Ntot));
+    const size_t len = (numInds + 3) / 4;
+    std::vector<uint8_t> bed = read_training_bed(opt, numInds, Mtot);
+    struct stat sb;
+    if (opt.kingOut.empty() && stat(opt.mcmcOutDir.c_str(), &sb) != 0)
+        if (std::system(("mkdir -p " + opt.mcmcOutDir).c_str()) != 0) fatal("FATAL  : can not create --mcmc-out-dir");
+    FILE* f = std::fopen(out.c_str(), "w");
+    if (!f) fatal("FATAL  : can not create " + out);
+    std::fprintf(f, "#FID1\tIID1\tFID2\tIID2\tNSNP\tHETHET\tIBS0\tKINSHIP\n");
+
+    hgibbs_t dev = nullptr;
+    hg_check(hgibbs_create(local_rank, &dev), "hgibbs_create");
+    hg_check(hgibbs_load_bed(dev, bed.data(), len, numInds, Mtot, numNAs ? keep.data() : nullptr, 0, Ntot, Ntot), "hgibbs_load_bed");
+    std::vector<uint8_t>().swap(bed);
+    uint64_t np = 0;
+    hg_check(hgibbs_king_pairs(dev, cutoff, &np), "hgibbs_king_pairs");
+    std::vector<uint32_t> ab(2 * np);
+    std::vector<int32_t> cnt(5 * np);
+    std::vector<double> kin(np);
+    hg_check(hgibbs_king_pairs_get(dev, ab.data(), cnt.data(), kin.data()), "hgibbs_king_pairs_get");
+    double ms = 0.0;
+    hg_check(hgibbs_last_king_ms(dev, &ms), "hgibbs_last_king_ms");
+    hgibbs_destroy(dev);
+    // HETHET and IBS0 as proportions of NSNP, as KING's .kin0 writes them; the list comes sorted by (a, b): .fam order
+    for (uint64_t p = 0; p < np; ++p) {
+        const uint32_t a = ab[2 * p], b = ab[2 * p + 1];
+        const int32_t* k = &cnt[5 * p];
+        std::fprintf(f, "%s\t%s\t%s\t%s\t%d\t%.12g\t%.12g\t%.12g\n", fid[a].c_str(), iid[a].c_str(), fid[b].c_str(), iid[b].c_str(), k[0],
+                     (double)k[3] / (double)k[0], (double)k[4] / (double)k[0], kin[p]);
+    }
+    if (std::fclose(f) != 0) fatal("FATAL  : short write on " + out);
+    std::printf("KING   : %llu pairs tested, %llu with KINSHIP >= %g written to %s (%.3f ms on the device)\n",
+                (unsigned long long)Ntot * (Ntot - 1ull) / 2ull, (unsigned long long)np, cutoff, out.c_str(), ms);
+    return 0;
+}
+
 } // namespace
 
 int main(int argc, const char* argv[])
@@ -1403,6 +1477,16 @@ int main(int argc, const char* argv[])
         if (nranks > 1) fatal("FATAL  : --assoc runs on one process (WORLD_SIZE = " + std::to_string(nranks) + ")");
     } else if (!opt.assocOut.empty() || opt.assocNoLoco)
         fatal(std::string("FATAL  : ") + (!opt.assocOut.empty() ? "--assoc-out" : "--assoc-no-loco") + " needs --assoc");
+    if (opt.king) {
+        if (opt.bayesType == "bayesWMPI") fatal("FATAL  : --king takes a bayesMPI command line, not --mpibayes bayesWMPI");
+        if (!opt.predictBfile.empty()) fatal("FATAL  : --king cannot be combined with --predict-bfile");
+        if (opt.ldGiven) fatal("FATAL  : --king cannot be combined with --ld-window");
+        if (opt.assoc) fatal("FATAL  : --king cannot be combined with --assoc");
+        if (opt.restart) fatal("FATAL  : --king does not sample: it cannot be combined with --restart");
+        if (nranks > 1) fatal("FATAL  : --king runs on one process (WORLD_SIZE = " + std::to_string(nranks) + ")");
+        if (!std::isfinite(king_cutoff(opt))) fatal("FATAL  : --king-cutoff " + opt.kingCutoff + ": the cutoff must be a finite number");
+    } else if (!opt.kingOut.empty() || opt.kingCutoffGiven)
+        fatal(std::string("FATAL  : ") + (!opt.kingOut.empty() ? "--king-out" : "--king-cutoff") + " needs --king");
     if (opt.bayesType == "bayesWMPI") return run_bayesw(opt, rank, nranks, local_rank); // main.cpp:164-167
 
     // ---- inputs (main.cpp:69-70,88; BayesRRm.cpp:969-997) -------------------
@@ -1433,6 +1517,7 @@ int main(int argc, const char* argv[])
     if (!opt.predictBfile.empty()) return run_predict(opt, keep, (unsigned)numInds, numNAs, Mtot, local_rank);
     if (opt.ldGiven) return run_ld(opt, keep, (unsigned)numInds, numNAs, Mtot, local_rank);
     if (opt.assoc) return run_assoc(opt, keep, y, covX, C, (unsigned)numInds, numNAs, Mtot, local_rank);
+    if (opt.king) return run_king(opt, keep, (unsigned)numInds, numNAs, Mtot, local_rank);
 
     std::vector<int32_t> groups;
     std::vector<std::vector<double>> mS;

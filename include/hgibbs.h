@@ -274,6 +274,26 @@ int hgibbs_last_ld_ms(hgibbs_t h, double* ms);
 int hgibbs_marker_dots(hgibbs_t h, uint32_t m0, uint32_t count, int K, const double* U, double* out, double* raw);
 int hgibbs_last_marker_dots_ms(hgibbs_t h, double* ms);   /* every kernel of the last call, not the host copies */
 
+/* ---- KING-robust kinship of the loaded rows -------- */
+/* For rows a, b of the handle (the n_local rows kept at hgibbs_load_bed), over the markers where both calls are present, five exact
+ * counts in this order: NSNP (called in both), HET_a, HET_b (a, resp. b, heterozygous among those), HETHET (both heterozygous), IBS0
+ * (one homozygous 0, the other homozygous 2); KINSHIP = 1/2 - (4 IBS0 + (HET_a - HETHET) + (HET_b - HETHET)) / (4 min(HET_a, HET_b)),
+ * NaN when min(HET_a, HET_b) = 0.  One rank only; M < 2^31.  The counts are exact integers: bit-identical for any blocking and any
+ * value of the option king_split (ranges of markers split over workgroups, 0 = automatic).  The call builds an individual-major copy
+ * of the codes on the device (the size of the loaded BED) and refuses, with a message, when it does not fit in free memory.
+ *
+ * hgibbs_king: counts[((a - a0) * bcount + (b - b0)) * 5 + t] for a in [a0, a0 + acount), b in [b0, b0 + bcount); any offsets, a == b
+ *   allowed (HET_a = HET_b = HETHET there). */
+int hgibbs_king(hgibbs_t h, uint32_t a0, uint32_t acount, uint32_t b0, uint32_t bcount, int32_t* counts);
+/* hgibbs_king_pairs: every pair a < b with KINSHIP >= cutoff (finite; NaN pairs never pass); *npairs = their number.  The list is
+ *   grown inside the call when it overflows (no pair is dropped) and kept in the handle, sorted by (a, b), until the next call. */
+int hgibbs_king_pairs(hgibbs_t h, double cutoff, uint64_t* npairs);
+/* copies the list out: ab[2 p], ab[2 p + 1] = a, b; counts[5 p + t]; kin[p].  Any pointer may be NULL. */
+int hgibbs_king_pairs_get(hgibbs_t h, uint32_t* ab, int32_t* counts, double* kin);
+/* device time of the last hgibbs_king / hgibbs_king_pairs in ms: every kernel of the call (image, zeroing, products, every run of the
+ * list), not the host copies or the allocations */
+int hgibbs_last_king_ms(hgibbs_t h, double* ms);
+
 /* ======================================================================== */
 /* Host driver: the body of BayesRRm::runMpiGibbs (src/BayesRRm.cpp:933-2939)
  * for --mpibayes bayesMPI, restated on top of hgibbs_*.                     */
