@@ -23,6 +23,7 @@ ABI_SYMBOLS = [
     "hydra_chain_destroy", "hydra_chain_iterate", "hydra_chain_state", "hydra_chain_csv_line", "hydra_chain_order",
     "hydra_chain_last_nnz", "hgibbs_score", "hgibbs_last_score_ms", "hgibbs_ld", "hgibbs_last_ld_ms",
     "hgibbs_marker_dots", "hgibbs_last_marker_dots_ms", "hgibbs_king", "hgibbs_king_pairs", "hgibbs_king_pairs_get", "hgibbs_last_king_ms",
+    "hgibbs_pca", "hgibbs_last_pca_ms",
     # BayesW
     "hgibbs_grand_seed", "hgibbs_grand_next", "hgibbs_ars_sample", "hgibbs_w_init", "hgibbs_w_marker_stats", "hgibbs_w_set_model",
     "hgibbs_w_reduce", "hgibbs_w_refresh_vi", "hgibbs_w_get_vi", "hgibbs_w_marker_sums", "hgibbs_w_sweep", "hgibbs_w_last_sweep_stats", "hgibbs_w_ars_device_probe",
@@ -43,6 +44,10 @@ class SweepStats(C.Structure):
                 ("tiles_per_workgroup_max", C.c_uint32), ("engine", C.c_uint32), ("walker", C.c_uint32), ("eps_sum_drift", C.c_double),
                 ("rounds", C.c_uint64), ("events", C.c_uint64), ("advances", C.c_uint64), ("chunks", C.c_uint64), ("refolds", C.c_uint64), ("pivots", C.c_uint64), ("predicted", C.c_uint64), ("shader_mhz", C.c_double),
                 ("ticks", C.c_uint64 * 16), ("refill", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
+class PcaReport(C.Structure):
+    _fields_ = [("iters_run", C.c_int32), ("m_used", C.c_uint32), ("ritz_change", C.c_double), ("resid", C.c_double * 32)]
 
 
 class RestartState(C.Structure):
@@ -190,6 +195,8 @@ def lib():
     L.hgibbs_king_pairs.argtypes = [vp, C.c_double, C.POINTER(C.c_uint64)]
     L.hgibbs_king_pairs_get.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), dp]
     L.hgibbs_last_king_ms.argtypes = [vp, dp]
+    L.hgibbs_pca.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double, dp, C.c_uint64, dp, dp, dp, C.POINTER(PcaReport)]
+    L.hgibbs_last_pca_ms.argtypes = [vp, dp]
     _lib = L
     return L
 
@@ -448,6 +455,33 @@ class Device:
         v = C.c_double()
         check(self.L.hgibbs_last_king_ms(self.h, C.byref(v)))
         return v.value
+
+    def pca(self, K, L=None, iters=20, tol=1e-10, Q0=None, seed=1, loadings=False):
+        """The top K principal components of the loaded rows (hgibbs_pca): eigenvalues (K,), PCs (K, n_local), loadings (K, M) or None,
+        and the report as a dict (iters_run, m_used, ritz_change, resid (K,)).  L is the panel width (default: the smallest multiple
+        of 8 that is >= K + 8, at most 32); Q0 (L, n_local) replaces the seeded start panel."""
+        if L is None:
+            L = min(32, (K + 8 + 7) // 8 * 8)
+        q = None
+        if Q0 is not None:
+            q = np.ascontiguousarray(Q0, dtype=np.float64)
+            if q.shape != (L, self.n_local):
+                raise ValueError("Q0 must be (%d, %d)" % (L, self.n_local))
+        kk = max(int(K), 0)
+        val = np.zeros(kk)
+        pcs = np.zeros((kk, self.n_local))
+        ld = np.zeros((kk, self.M)) if loadings else None
+        rep = PcaReport()
+        check(self.L.hgibbs_pca(self.h, int(K), int(L), int(iters), float(tol), _dp(q) if q is not None else None, int(seed) & (2 ** 64 - 1),
+                                _dp(val), _dp(pcs), _dp(ld) if loadings else None, C.byref(rep)))
+        return val, pcs, ld, {"iters_run": rep.iters_run, "m_used": rep.m_used, "ritz_change": rep.ritz_change,
+                              "resid": np.array(rep.resid[:kk], dtype=np.float64)}
+
+    def last_pca_ms(self):
+        """Device ms of the last pca(): whole call, X'Q products, X T products, panel algebra of the iterations."""
+        v = (C.c_double * 4)()
+        check(self.L.hgibbs_last_pca_ms(self.h, v))
+        return [v[i] for i in range(4)]
 
     def debug_times(self):
         """The 48 stage-timestamp words of the sweep kernel's debug build (option debug_timing; 100 MHz ticks, accumulated

@@ -260,24 +260,34 @@ static void mdots_launch(hgibbs_ctx* h, dim3 grid, uint32_t t0, uint32_t t1, uin
         k_mdots<TP, false><<<grid, MD_WAVES * 64, 0, h->stream>>>(h->bed, h->stride, h->M, t0, t1, sub_per, n_sub, img, tiles, tv0, ntp, K, tmiss, m0, count, acc);
 }
 
-extern "C" int hgibbs_marker_dots(hgibbs_t h, uint32_t m0, uint32_t count, int K, const double* U, double* out, double* raw)
-{
-    if (!h) return fail("hgibbs_marker_dots: null handle");
-    if (!h->bed) return fail("hgibbs_marker_dots: no genotypes loaded on this handle");
-    if (h->nranks > 1 || h->comm) return fail("hgibbs_marker_dots: one rank only (this handle has %d): the dots are not summed over ranks", h->nranks);
-    if (K <= 0 || K > MD_KMAX) return fail("hgibbs_marker_dots: K = %d, must be in [1, %d]", K, MD_KMAX);
-    if (!U || !out) return fail("hgibbs_marker_dots: null argument");
-    if ((uint64_t)m0 + count > h->M) return fail("hgibbs_marker_dots: markers [%u, %llu) out of range (M = %u)", m0, (unsigned long long)m0 + count, h->M);
-    if (h->n_local >= MD_NMAX) return fail("hgibbs_marker_dots: %u individuals, at most %u (64-bit sums)", h->n_local, MD_NMAX - 1u);
-    const uint32_t n = h->n_local;
-    for (size_t i = 0; i < (size_t)K * n; ++i)
-        if (!std::isfinite(U[i])) return fail("hgibbs_marker_dots: U[%d][%zu] = %g is not finite", (int)(i / n), i % n, U[i]);
-    if (count == 0) return 0;
-    HIP_TRY(hipSetDevice(h->device));
-    if (compute_stats(h)) return 1;
-    const uint32_t M = h->M, ntile = (M + 15u) / 16u;
+// The work buffers of the pipeline for up to `kmax` vectors against up to `cmax` markers of a chunk, allocated once by the caller
+// (hgibbs_marker_dots per call, hgibbs_pca per call for all its iterations): everything but the vectors and the results.
+struct MdotsWs {
+    unsigned long long *maxbits = nullptr, *acc = nullptr; // (ksum lies inside maxbits)
+    uint32_t* bad = nullptr;
+    int* scale = nullptr;
+    rl_v4i* img = nullptr;
+    uint8_t* tmiss = nullptr;
+    int kmax = 0;
+    uint32_t cmax = 0;
+    ~MdotsWs()
+    {
+        void* p[] = {maxbits, acc, bad, scale, img, tmiss};
+        for (void* x : p)
+            if (x) (void)hipFree(x);
+    }
+};
 
-    // tiles of sixteen markers with a missing call in a column (the counts of hgibbs_marker_stats)
+static size_t mdots_ws_bytes(const hgibbs_ctx* h, int kmax, uint32_t cmax)
+{
+    const uint32_t n_sub = (h->n_local + MD_SUBI - 1) / MD_SUBI;
+    return (size_t)n_sub * ((kmax + 1) / 2) * 8 * 64 * sizeof(rl_v4i) + (size_t)cmax * kmax * 4 * sizeof(unsigned long long) + (h->M + 15u) / 16u + 4096;
+}
+
+// Allocates the buffers and reads the marker-stats counts once (tiles of sixteen markers with a missing call in a column); synchronises
+static int mdots_ws_create(hgibbs_ctx* h, MdotsWs& b, int kmax, uint32_t cmax)
+{
+    const uint32_t M = h->M, ntile = (M + 15u) / 16u, n = h->n_local;
     std::vector<uint8_t> tmiss(ntile, 0);
     {
         std::vector<unsigned long long> cts((size_t)M * 3);
@@ -285,50 +295,46 @@ extern "C" int hgibbs_marker_dots(hgibbs_t h, uint32_t m0, uint32_t count, int K
         for (uint32_t j = 0; j < M; ++j)
             if (cts[3ull * j + 2]) tmiss[j / 16u] = 1;
     }
-
-    const int tiles = (K + 1) / 2;
+    const int tiles = (kmax + 1) / 2;
     const uint32_t n_sub = (n + MD_SUBI - 1) / MD_SUBI; // slices that hold individuals (all inside n_pad, a multiple of 4096)
-    struct Bufs {
-        double *U = nullptr, *out = nullptr, *raw = nullptr;
-        unsigned long long *maxbits = nullptr, *acc = nullptr;
-        uint32_t* bad = nullptr;
-        int* scale = nullptr;
-        rl_v4i* img = nullptr;
-        uint8_t* tmiss = nullptr;
-        ~Bufs()
-        {
-            void* p[] = {U, out, raw, maxbits, acc, bad, scale, img, tmiss}; // (ksum lies inside maxbits)
-            for (void* x : p)
-                if (x) (void)hipFree(x);
-        }
-    } b;
-    const size_t nk = (size_t)count * K;
-    HIP_TRY(hipMalloc(&b.U, (size_t)K * n * sizeof(double)));
-    HIP_TRY(hipMalloc(&b.maxbits, (size_t)K * 3 * sizeof(unsigned long long))); // max, then the two halves of sum_i q
-    unsigned long long* ksum = b.maxbits + K;
+    b.kmax = kmax;
+    b.cmax = cmax;
+    HIP_TRY(hipMalloc(&b.maxbits, (size_t)kmax * 3 * sizeof(unsigned long long))); // max, then the two halves of sum_i q
     HIP_TRY(hipMalloc(&b.bad, sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&b.scale, (size_t)K * sizeof(int)));
+    HIP_TRY(hipMalloc(&b.scale, (size_t)kmax * sizeof(int)));
     HIP_TRY(hipMalloc(&b.img, (size_t)n_sub * tiles * 8 * 64 * sizeof(rl_v4i)));
     HIP_TRY(hipMalloc(&b.tmiss, tmiss.size()));
-    HIP_TRY(hipMalloc(&b.acc, nk * 4 * sizeof(unsigned long long)));
-    HIP_TRY(hipMalloc(&b.out, nk * sizeof(double)));
-    if (raw) HIP_TRY(hipMalloc(&b.raw, nk * 2 * sizeof(double)));
-    HIP_TRY(hipMemcpyAsync(b.U, U, (size_t)K * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(b.tmiss, tmiss.data(), tmiss.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMalloc(&b.acc, (size_t)cmax * kmax * 4 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemcpy(b.tmiss, tmiss.data(), tmiss.size(), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// Zeroes the sums of one product (stream-ordered, no synchronisation)
+static int mdots_dev_clear(hgibbs_ctx* h, MdotsWs& b, uint32_t count, int K)
+{
     HIP_TRY(hipMemsetAsync(b.bad, 0, sizeof(uint32_t), h->stream));
     HIP_TRY(hipMemsetAsync(b.maxbits, 0, (size_t)K * 3 * sizeof(unsigned long long), h->stream));
-    HIP_TRY(hipMemsetAsync(b.acc, 0, nk * 4 * sizeof(unsigned long long), h->stream));
+    HIP_TRY(hipMemsetAsync(b.acc, 0, (size_t)count * K * 4 * sizeof(unsigned long long), h->stream));
+    return 0;
+}
 
-    // device time from here to the rounded result: every kernel of the call, not the host copies around it
-    HIP_TRY(hipEventRecord(h->ev0, h->stream));
+// The kernels of one product on device pointers: dU (K x n_local, vector-major) -> dout (count x K), draw (count x K x 2) or null.
+// Stream-ordered: no allocation, no synchronisation.  mdots_dev_clear comes first.
+static int mdots_dev_run(hgibbs_ctx* h, MdotsWs& b, uint32_t m0, uint32_t count, int K, const double* dU, double* dout, double* draw)
+{
+    const uint32_t n = h->n_local;
+    const int tiles = (K + 1) / 2;
+    const uint32_t n_sub = (n + MD_SUBI - 1) / MD_SUBI;
+    const size_t nk = (size_t)count * K;
+    unsigned long long* ksum = b.maxbits + K;
     {
         // the scales and sum_i q of hgibbs_score, with a = o = u_k (vectors of n_local entries)
         const uint32_t per = std::max<uint32_t>(1u, std::min<uint32_t>((n + 2047u) / 2048u, (2048u + (uint32_t)K - 1u) / (uint32_t)K));
-        k_score_max<<<dim3(K, per), SC_TPB, 0, h->stream>>>(b.U, b.U, n, b.maxbits, b.bad);
+        k_score_max<<<dim3(K, per), SC_TPB, 0, h->stream>>>(dU, dU, n, b.maxbits, b.bad);
         HIP_TRY(hipGetLastError());
-        k_score_ksum<<<dim3(K, per), SC_TPB, 0, h->stream>>>(b.U, n, b.maxbits, b.scale, ksum);
+        k_score_ksum<<<dim3(K, per), SC_TPB, 0, h->stream>>>(dU, n, b.maxbits, b.scale, ksum);
         HIP_TRY(hipGetLastError());
-        k_mdots_digits<<<dim3(n_sub * 8u, tiles), 64, 0, h->stream>>>(b.U, n, K, tiles, b.scale, b.img);
+        k_mdots_digits<<<dim3(n_sub * 8u, tiles), 64, 0, h->stream>>>(dU, n, K, tiles, b.scale, b.img);
         HIP_TRY(hipGetLastError());
     }
     const uint32_t t0 = m0 / 16u, t1 = (m0 + count - 1u) / 16u + 1u;
@@ -351,8 +357,49 @@ extern "C" int hgibbs_marker_dots(hgibbs_t h, uint32_t m0, uint32_t count, int K
         }
         HIP_TRY(hipGetLastError());
     }
-    k_mdots_final<<<(uint32_t)((nk + MD_TPB - 1) / MD_TPB), MD_TPB, 0, h->stream>>>(b.acc, ksum, b.scale, h->mave, h->mstd, m0, count, K, b.out, b.raw);
+    k_mdots_final<<<(uint32_t)((nk + MD_TPB - 1) / MD_TPB), MD_TPB, 0, h->stream>>>(b.acc, ksum, b.scale, h->mave, h->mstd, m0, count, K, dout, draw);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int hgibbs_marker_dots(hgibbs_t h, uint32_t m0, uint32_t count, int K, const double* U, double* out, double* raw)
+{
+    if (!h) return fail("hgibbs_marker_dots: null handle");
+    if (!h->bed) return fail("hgibbs_marker_dots: no genotypes loaded on this handle");
+    if (h->nranks > 1 || h->comm) return fail("hgibbs_marker_dots: one rank only (this handle has %d): the dots are not summed over ranks", h->nranks);
+    if (K <= 0 || K > MD_KMAX) return fail("hgibbs_marker_dots: K = %d, must be in [1, %d]", K, MD_KMAX);
+    if (!U || !out) return fail("hgibbs_marker_dots: null argument");
+    if ((uint64_t)m0 + count > h->M) return fail("hgibbs_marker_dots: markers [%u, %llu) out of range (M = %u)", m0, (unsigned long long)m0 + count, h->M);
+    if (h->n_local >= MD_NMAX) return fail("hgibbs_marker_dots: %u individuals, at most %u (64-bit sums)", h->n_local, MD_NMAX - 1u);
+    const uint32_t n = h->n_local;
+    for (size_t i = 0; i < (size_t)K * n; ++i)
+        if (!std::isfinite(U[i])) return fail("hgibbs_marker_dots: U[%d][%zu] = %g is not finite", (int)(i / n), i % n, U[i]);
+    if (count == 0) return 0;
+    HIP_TRY(hipSetDevice(h->device));
+    if (compute_stats(h)) return 1;
+
+    // a thin wrapper around the device-pointer pipeline: its own workspace, the vectors in, the results out
+    MdotsWs ws;
+    struct Bufs {
+        double *U = nullptr, *out = nullptr, *raw = nullptr;
+        ~Bufs()
+        {
+            void* p[] = {U, out, raw};
+            for (void* x : p)
+                if (x) (void)hipFree(x);
+        }
+    } b;
+    const size_t nk = (size_t)count * K;
+    HIP_TRY(hipMalloc(&b.U, (size_t)K * n * sizeof(double)));
+    if (mdots_ws_create(h, ws, K, count)) return 1;
+    HIP_TRY(hipMalloc(&b.out, nk * sizeof(double)));
+    if (raw) HIP_TRY(hipMalloc(&b.raw, nk * 2 * sizeof(double)));
+    HIP_TRY(hipMemcpyAsync(b.U, U, (size_t)K * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (mdots_dev_clear(h, ws, count, K)) return 1;
+
+    // device time from here to the rounded result: every kernel of the call, not the host copies around it
+    HIP_TRY(hipEventRecord(h->ev0, h->stream));
+    if (mdots_dev_run(h, ws, m0, count, K, b.U, b.out, b.raw)) return 1;
     HIP_TRY(hipEventRecord(h->ev1, h->stream));
     HIP_TRY(hipEventSynchronize(h->ev1));
     HIP_TRY(hipMemcpy(out, b.out, nk * sizeof(double), hipMemcpyDeviceToHost));

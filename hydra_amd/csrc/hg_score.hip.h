@@ -318,16 +318,35 @@ static void score_launch(hgibbs_ctx* h, dim3 grid, uint32_t kb_per, const rl_v4i
     k_score<SP><<<grid, SC_IND, 0, h->stream>>>(h->bed, h->stride, h->M, h->n_local, kb_per, wdig, mdig, mslot, S, s0, acc);
 }
 
-extern "C" int hgibbs_score(hgibbs_t h, int S, const double* a, const double* o, double* out)
-{
-    if (!h) return fail("hgibbs_score: null handle");
-    if (!h->bed) return fail("hgibbs_score: no genotypes loaded on this handle");
-    if (S <= 0) return fail("hgibbs_score: S = %d, needs at least one weight vector", S);
-    if (!a || !o || !out) return fail("hgibbs_score: null argument");
-    HIP_TRY(hipSetDevice(h->device));
-    const uint32_t M = h->M, n = h->n_local, nkb = (M + 63u) / 64u;
-    const int sp = score_sp_for(h, S), tiles = sp / 2;
+// The work buffers of the pipeline for up to `smax` weight vectors, allocated once by the caller (hgibbs_score per call, hgibbs_pca
+// per call for all its iterations): everything but the weights and the results.
+struct ScoreWs {
+    int* scale = nullptr;
+    unsigned long long *maxbits = nullptr, *ksum = nullptr, *acc = nullptr; // (ksum lies inside maxbits)
+    uint32_t* bad = nullptr;
+    int32_t* mslot = nullptr;
+    rl_v4i *wdig = nullptr, *mdig = nullptr;
+    int smax = 0, sp = 0;
+    ~ScoreWs()
+    {
+        void* p[] = {scale, maxbits, bad, mslot, wdig, mdig, acc};
+        for (void* x : p)
+            if (x) (void)hipFree(x);
+    }
+};
 
+static size_t score_ws_bytes(const hgibbs_ctx* h, int smax)
+{
+    const uint32_t nkb = (h->M + 63u) / 64u;
+    const int tiles = score_sp_for(h, smax) / 2;
+    return 2 * (size_t)nkb * tiles * 64 * sizeof(rl_v4i) + (size_t)h->n_local * smax * 2 * sizeof(unsigned long long) + (size_t)nkb * 4 + 4096;
+}
+
+// Allocates the buffers and reads the marker counts once (blocks of 64 markers with a column that has missing calls); synchronises
+static int score_ws_create(hgibbs_ctx* h, ScoreWs& b, int smax)
+{
+    const uint32_t M = h->M, n = h->n_local, nkb = (M + 63u) / 64u;
+    const int sp = score_sp_for(h, smax), tiles = sp / 2;
     // blocks of 64 markers with a column that has missing calls: from the counts of hgibbs_marker_stats when they exist (summed
     // over ranks: a superset of this shard's, which costs only a product over zeros), else from this shard's own counts (no collective)
     std::vector<int32_t> mslot(nkb, -1);
@@ -344,49 +363,45 @@ extern "C" int hgibbs_score(hgibbs_t h, int S, const double* a, const double* o,
         for (uint32_t j = 0; j < M; ++j)
             if (c[3ull * j + 2] && mslot[j / 64u] < 0) mslot[j / 64u] = (int32_t)nm++;
     }
-
-    struct Bufs {
-        double *a = nullptr, *o = nullptr, *out = nullptr;
-        int* scale = nullptr;
-        unsigned long long *maxbits = nullptr, *ksum = nullptr;
-        uint32_t* bad = nullptr;
-        int32_t* mslot = nullptr;
-        rl_v4i *wdig = nullptr, *mdig = nullptr;
-        unsigned long long* acc = nullptr;
-        ~Bufs()
-        {
-            void* p[] = {a, o, out, scale, maxbits, bad, mslot, wdig, mdig, acc}; // (ksum lies inside maxbits)
-            for (void* x : p)
-                if (x) (void)hipFree(x);
-        }
-    } b;
-    const size_t SM = (size_t)S * M, NS = (size_t)n * S;
-    HIP_TRY(hipMalloc(&b.a, SM * sizeof(double)));
-    HIP_TRY(hipMalloc(&b.o, SM * sizeof(double)));
-    HIP_TRY(hipMalloc(&b.scale, (size_t)S * sizeof(int)));
-    HIP_TRY(hipMalloc(&b.maxbits, (size_t)S * 3 * sizeof(unsigned long long))); // max, then the two halves of sum_j q_o
-    b.ksum = b.maxbits + S;
+    b.smax = smax;
+    b.sp = sp;
+    HIP_TRY(hipMalloc(&b.scale, (size_t)smax * sizeof(int)));
+    HIP_TRY(hipMalloc(&b.maxbits, (size_t)smax * 3 * sizeof(unsigned long long))); // max, then the two halves of sum_j q_o
     HIP_TRY(hipMalloc(&b.bad, sizeof(uint32_t)));
     HIP_TRY(hipMalloc(&b.mslot, (size_t)nkb * sizeof(int32_t)));
     HIP_TRY(hipMalloc(&b.wdig, (size_t)nkb * tiles * 64 * sizeof(rl_v4i)));
     if (nm) HIP_TRY(hipMalloc(&b.mdig, (size_t)nm * tiles * 64 * sizeof(rl_v4i)));
-    HIP_TRY(hipMalloc(&b.acc, NS * 2 * sizeof(unsigned long long)));
-    HIP_TRY(hipMalloc(&b.out, NS * sizeof(double)));
-    HIP_TRY(hipMemcpyAsync(b.a, a, SM * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(b.o, o, SM * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(b.mslot, mslot.data(), (size_t)nkb * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMalloc(&b.acc, (size_t)n * smax * 2 * sizeof(unsigned long long)));
     HIP_TRY(hipMemsetAsync(b.bad, 0, sizeof(uint32_t), h->stream));
-    HIP_TRY(hipMemsetAsync(b.maxbits, 0, (size_t)S * 3 * sizeof(unsigned long long), h->stream));
-    HIP_TRY(hipMemsetAsync(b.acc, 0, NS * 2 * sizeof(unsigned long long), h->stream));
+    HIP_TRY(hipMemcpyAsync(b.mslot, mslot.data(), (size_t)nkb * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream)); // (mslot is a local)
+    return 0;
+}
 
-    // device time from here to the rounded result: every kernel of the call, not the host copies around it
-    HIP_TRY(hipEventRecord(h->ev0, h->stream));
+// Zeroes the sums of one product (stream-ordered, no synchronisation); with clear_bad = false the flag of non-finite weights, zero
+// from score_ws_create, is left to gather over several products
+static int score_dev_clear(hgibbs_ctx* h, ScoreWs& b, int S, bool clear_bad = true)
+{
+    b.ksum = b.maxbits + S;
+    if (clear_bad) HIP_TRY(hipMemsetAsync(b.bad, 0, sizeof(uint32_t), h->stream));
+    HIP_TRY(hipMemsetAsync(b.maxbits, 0, (size_t)S * 3 * sizeof(unsigned long long), h->stream));
+    HIP_TRY(hipMemsetAsync(b.acc, 0, (size_t)h->n_local * S * 2 * sizeof(unsigned long long), h->stream));
+    return 0;
+}
+
+// The kernels of one product on device pointers: da, dov (S x M, vector-major) -> dout (n_local x S).  Stream-ordered: no allocation,
+// no synchronisation; b.bad is left for the caller to read.  score_dev_clear comes first.  S <= smax, with the pass size of smax.
+static int score_dev_run(hgibbs_ctx* h, ScoreWs& b, int S, const double* da, const double* dov, double* dout)
+{
+    const uint32_t M = h->M, n = h->n_local, nkb = (M + 63u) / 64u;
+    const int sp = b.sp, tiles = sp / 2;
+    const size_t NS = (size_t)n * S;
     {
         // workgroups per sample for the scale: about 2048 in all, at least 2048 markers each (grid y: at most 65535)
         const uint32_t per = std::max<uint32_t>(1u, std::min<uint32_t>((M + 2047u) / 2048u, (2048u + (uint32_t)S - 1u) / (uint32_t)S));
-        k_score_max<<<dim3(S, per), SC_TPB, 0, h->stream>>>(b.a, b.o, M, b.maxbits, b.bad);
+        k_score_max<<<dim3(S, per), SC_TPB, 0, h->stream>>>(da, dov, M, b.maxbits, b.bad);
         HIP_TRY(hipGetLastError());
-        k_score_ksum<<<dim3(S, per), SC_TPB, 0, h->stream>>>(b.o, M, b.maxbits, b.scale, b.ksum);
+        k_score_ksum<<<dim3(S, per), SC_TPB, 0, h->stream>>>(dov, M, b.maxbits, b.scale, b.ksum);
         HIP_TRY(hipGetLastError());
     }
 
@@ -399,7 +414,7 @@ extern "C" int hgibbs_score(hgibbs_t h, int S, const double* a, const double* o,
     const uint32_t kb_per = (nkb + gy - 1u) / gy;
     gy = (nkb + kb_per - 1u) / kb_per;
     for (uint32_t s0 = 0; s0 < (uint32_t)S; s0 += (uint32_t)sp) {
-        k_score_digits<<<dim3(nkb, tiles), 64, 0, h->stream>>>(b.a, b.o, M, (uint32_t)S, s0, tiles, b.scale, b.mslot, b.wdig, b.mdig);
+        k_score_digits<<<dim3(nkb, tiles), 64, 0, h->stream>>>(da, dov, M, (uint32_t)S, s0, tiles, b.scale, b.mslot, b.wdig, b.mdig);
         HIP_TRY(hipGetLastError());
         const dim3 grid(gx, gy);
         switch (sp) {
@@ -410,11 +425,46 @@ extern "C" int hgibbs_score(hgibbs_t h, int S, const double* a, const double* o,
         }
         HIP_TRY(hipGetLastError());
     }
-    k_score_final<<<(uint32_t)((NS + SC_TPB - 1) / SC_TPB), SC_TPB, 0, h->stream>>>(b.acc, b.ksum, b.scale, n, (uint32_t)S, b.out);
+    k_score_final<<<(uint32_t)((NS + SC_TPB - 1) / SC_TPB), SC_TPB, 0, h->stream>>>(b.acc, b.ksum, b.scale, n, (uint32_t)S, dout);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int hgibbs_score(hgibbs_t h, int S, const double* a, const double* o, double* out)
+{
+    if (!h) return fail("hgibbs_score: null handle");
+    if (!h->bed) return fail("hgibbs_score: no genotypes loaded on this handle");
+    if (S <= 0) return fail("hgibbs_score: S = %d, needs at least one weight vector", S);
+    if (!a || !o || !out) return fail("hgibbs_score: null argument");
+    HIP_TRY(hipSetDevice(h->device));
+    const uint32_t M = h->M, n = h->n_local;
+
+    // a thin wrapper around the device-pointer pipeline: its own workspace, the weights in, the results out
+    ScoreWs ws;
+    struct Bufs {
+        double *a = nullptr, *o = nullptr, *out = nullptr;
+        ~Bufs()
+        {
+            void* p[] = {a, o, out};
+            for (void* x : p)
+                if (x) (void)hipFree(x);
+        }
+    } b;
+    const size_t SM = (size_t)S * M, NS = (size_t)n * S;
+    if (score_ws_create(h, ws, S)) return 1;
+    HIP_TRY(hipMalloc(&b.a, SM * sizeof(double)));
+    HIP_TRY(hipMalloc(&b.o, SM * sizeof(double)));
+    HIP_TRY(hipMalloc(&b.out, NS * sizeof(double)));
+    HIP_TRY(hipMemcpyAsync(b.a, a, SM * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(b.o, o, SM * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (score_dev_clear(h, ws, S)) return 1;
+
+    // device time from here to the rounded result: every kernel of the call, not the host copies around it
+    HIP_TRY(hipEventRecord(h->ev0, h->stream));
+    if (score_dev_run(h, ws, S, b.a, b.o, b.out)) return 1;
     HIP_TRY(hipEventRecord(h->ev1, h->stream));
     uint32_t bad = 0;
-    HIP_TRY(hipMemcpyAsync(&bad, b.bad, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(&bad, ws.bad, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (bad) return fail("hgibbs_score: a weight (a or o) is not finite"); // (out untouched; what the kernels made of it is dropped)
     HIP_TRY(hipMemcpy(out, b.out, NS * sizeof(double), hipMemcpyDeviceToHost));

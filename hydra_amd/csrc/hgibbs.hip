@@ -188,6 +188,7 @@ struct hgibbs_ctx {
     double mdots_ms = 0.0; // device time of the last hgibbs_marker_dots (scales, digits, products, rounding)
     int king_split = 0;    // option king_split: ranges of markers the workgroups of hgibbs_king split the k dimension into (0 = automatic)
     double king_ms = 0.0;  // device time of the last hgibbs_king / hgibbs_king_pairs (image, zeroing, products, every run of the list)
+    double pca_ms[5] = {0, 0, 0, 0, 0}; // device time of the last hgibbs_pca: whole call, X'Q products, X T products, panel algebra of the iterations, the rest
     std::vector<uint32_t> king_ab;    // the last hgibbs_king_pairs list, sorted by (a, b): a, b per pair
     std::vector<int32_t> king_counts; // NSNP, HET_a, HET_b, HETHET, IBS0 per pair
     std::vector<double> king_kin;     // KINSHIP per pair
@@ -2044,3 +2045,4 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
 #include "hg_ld.hip.h"
 #include "hg_mdots.hip.h"
 #include "hg_king.hip.h"
+#include "hg_pca.hip.h"

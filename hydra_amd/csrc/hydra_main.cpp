@@ -30,6 +30,10 @@
 // kinship of every pair of the chain's rows with hgibbs_king_pairs (run_king) and writes the pairs with
 // KINSHIP >= T (default 0.0442) to <dir>/<name>.kin0 (or F).
 //
+// `--pca K [--pca-iters P] [--pca-tol T] [--pca-out F] [--pca-loadings]` appended to a bayesMPI command line samples nothing either: it
+// computes the K leading principal components of the chain's rows with hgibbs_pca (run_pca), seeded by --seed,
+// and writes <dir>/<name>.eigenvec (or F), .eigenval, a .cov file that --covariates reads as it stands and, with --pca-loadings, .var.
+//
 // Not reproduced (out of scope for the hot path): sparse
 // file formats, bayesFH, marker-sharded MPI, the .lst/tarball.
 // Multi-GPU: one process per GPU (RANK/WORLD_SIZE/LOCAL_RANK in the
@@ -80,6 +84,8 @@ struct Options { // src/options.hpp:20-138 (subset that reaches bayesMPI)
     std::string assocOut;                            // --assoc-out
     bool king = false, kingCutoffGiven = false;      // --king: KING-robust kinship of the chain's rows; --king-cutoff given
     std::string kingCutoff = "0.0442", kingOut;      // --king-cutoff T (checked before the device), --king-out
+    bool pca = false, pcaLoadings = false, pcaItersGiven = false, pcaTolGiven = false, pcaOutGiven = false; // --pca K; which --pca-* were given
+    std::string pcaK, pcaIters, pcaTol, pcaOut;      // --pca K, --pca-iters P, --pca-tol T as given (checked before the device), --pca-out
     int batch = 0, cpg = 0; // tuning knobs of this build (not hydra's)
 };
 
@@ -218,6 +224,19 @@ Options parse(int argc, const char* argv[])
             o.kingCutoff = need(i);
             o.kingCutoffGiven = true;
         } else if (a == "--king-out") o.kingOut = need(i);
+        else if (a == "--pca") {
+            o.pcaK = need(i);
+            o.pca = true;
+        } else if (a == "--pca-iters") {
+            o.pcaIters = need(i);
+            o.pcaItersGiven = true;
+        } else if (a == "--pca-tol") {
+            o.pcaTol = need(i);
+            o.pcaTolGiven = true;
+        } else if (a == "--pca-out") {
+            o.pcaOut = need(i);
+            o.pcaOutGiven = true;
+        } else if (a == "--pca-loadings") o.pcaLoadings = true;
         else if (a == "--sparse-dir" || a == "--sparse-basename" ||
                  a == "--bed-to-sparse" || a == "--sparse-sync" || a == "--bed-sync")
             fatal("FATAL  : option " + a + " belongs to a part of hydra this build does not reproduce (SURVEY.md section 2)");
@@ -1427,6 +1446,126 @@ int run_king(const Options& opt, const std::vector<uint8_t>& keep, unsigned numI
     return 0;
 }
 
+// ---- --pca: principal components of the chain's rows ----
+// an option's argument as an integer, resp. a number: false unless the whole argument is one
+bool whole_int(const std::string& t, long& v)
+{
+    const char* s = t.c_str();
+    char* end = nullptr;
+    v = std::strtol(s, &end, 10);
+    return end != s && *end == 0;
+}
+
+bool whole_num(const std::string& t, double& v)
+{
+    const char* s = t.c_str();
+    char* end = nullptr;
+    v = std::strtod(s, &end);
+    return end != s && *end == 0;
+}
+
+constexpr int PCA_KMAX = 24; // the panel is the smallest multiple of 8 that is >= K + 8, at most 32 vectors
+
+int run_pca(const Options& opt, const std::vector<uint8_t>& keep, unsigned numInds, unsigned numNAs, unsigned Mtot, int local_rank)
+{
+    long K = 0, iters = 20;
+    double tol = 1e-10;
+    whole_int(opt.pcaK, K);
+    if (opt.pcaItersGiven) whole_int(opt.pcaIters, iters);
+    if (opt.pcaTolGiven) whole_num(opt.pcaTol, tol);
+    const int L = std::min(32, (int)((K + 8 + 7) / 8) * 8);
+    // <out>: --pca-out without its .eigenvec, else <dir>/<name>
+    std::string vec = opt.pcaOut.empty() ? opt.mcmcOutDir + "/" + opt.mcmcOutNam + ".eigenvec" : opt.pcaOut, pre = vec;
+    if (pre.size() > 9 && pre.compare(pre.size() - 9, 9, ".eigenvec") == 0) pre.resize(pre.size() - 9);
+    // FID and IID of every .fam row; the chain's rows (NA phenotype, and NA covariate rows with --covariates, dropped) are the kept ones
+    std::vector<std::string> fid, iid;
+    {
+        std::ifstream in(opt.bedFile + ".fam");
+        if (!in) fatal("Error: can not open the file [" + opt.bedFile + ".fam] to read.");
+        std::string f, i, dad, mom, sex, phen;
+        for (unsigned r = 0; r < numInds && (in >> f >> i >> dad >> mom >> sex >> phen); ++r) {
+            fid.push_back(f);
+            iid.push_back(i);
+        }
+    }
+    if (fid.size() != numInds) fatal("FATAL  : " + opt.bedFile + ".fam: " + std::to_string(fid.size()) + " rows, expected " + std::to_string(numInds));
+    const unsigned Ntot = numInds - numNAs;
+    const size_t len = (numInds + 3) / 4;
+    std::vector<uint8_t> bed = read_training_bed(opt, numInds, Mtot);
+    struct stat sb;
+    if (opt.pcaOut.empty() && stat(opt.mcmcOutDir.c_str(), &sb) != 0)
+        if (std::system(("mkdir -p " + opt.mcmcOutDir).c_str()) != 0) fatal("FATAL  : can not create --mcmc-out-dir");
+    FILE* f = std::fopen(vec.c_str(), "w");
+    if (!f) fatal("FATAL  : can not create " + vec);
+    std::fprintf(f, "#FID\tIID");
+    for (long k = 0; k < K; ++k) std::fprintf(f, "\tPC%ld", k + 1);
+    std::fprintf(f, "\n");
+    std::fflush(f);
+    std::printf("PCA    : %ld components, panel of %d vectors, at most %ld iterations, tolerance %g, seed %u\n", K, L, iters, tol, opt.seed);
+
+    hgibbs_t dev = nullptr;
+    hg_check(hgibbs_create(local_rank, &dev), "hgibbs_create");
+    hg_check(hgibbs_load_bed(dev, bed.data(), len, numInds, Mtot, numNAs ? keep.data() : nullptr, 0, Ntot, Ntot), "hgibbs_load_bed");
+    std::vector<uint8_t>().swap(bed);
+    std::vector<double> eigval(K), pcs((size_t)K * Ntot), load(opt.pcaLoadings ? (size_t)K * Mtot : 0);
+    hgibbs_pca_report rep;
+    hg_check(hgibbs_pca(dev, (int)K, L, (int)iters, tol, nullptr, (uint64_t)opt.seed, eigval.data(), pcs.data(), opt.pcaLoadings ? load.data() : nullptr, &rep),
+             "hgibbs_pca");
+    double ms[4] = {0, 0, 0, 0};
+    hg_check(hgibbs_last_pca_ms(dev, ms), "hgibbs_last_pca_ms");
+    hgibbs_destroy(dev);
+
+    FILE* c = std::fopen((pre + ".cov").c_str(), "w");
+    if (!c) fatal("FATAL  : can not create " + pre + ".cov");
+    unsigned at = 0;
+    for (unsigned r = 0; r < numInds; ++r) {
+        const bool kept = !numNAs || keep[r];
+        std::fprintf(c, "%s %s", fid[r].c_str(), iid[r].c_str());
+        if (kept) std::fprintf(f, "%s\t%s", fid[r].c_str(), iid[r].c_str());
+        for (long k = 0; k < K; ++k) {
+            if (kept) {
+                std::fprintf(f, "\t%.12g", pcs[(size_t)k * Ntot + at]);
+                std::fprintf(c, " %.12g", pcs[(size_t)k * Ntot + at]);
+            } else
+                std::fprintf(c, " NA");
+        }
+        std::fprintf(c, "\n");
+        if (kept) {
+            std::fprintf(f, "\n");
+            ++at;
+        }
+    }
+    if (std::fclose(f) != 0) fatal("FATAL  : short write on " + vec);
+    if (std::fclose(c) != 0) fatal("FATAL  : short write on " + pre + ".cov");
+    FILE* v = std::fopen((pre + ".eigenval").c_str(), "w");
+    if (!v) fatal("FATAL  : can not create " + pre + ".eigenval");
+    for (long k = 0; k < K; ++k) std::fprintf(v, "%.12g\n", eigval[k]);
+    if (std::fclose(v) != 0) fatal("FATAL  : short write on " + pre + ".eigenval");
+    if (opt.pcaLoadings) {
+        const BimRows bim = read_bim(opt.bedFile + ".bim", Mtot);
+        FILE* w = std::fopen((pre + ".var").c_str(), "w");
+        if (!w) fatal("FATAL  : can not create " + pre + ".var");
+        std::fprintf(w, "#CHR\tSNP\tA1\tA2");
+        for (long k = 0; k < K; ++k) std::fprintf(w, "\tPC%ld", k + 1);
+        std::fprintf(w, "\n");
+        for (unsigned j = 0; j < Mtot; ++j) {
+            std::fprintf(w, "%s\t%s\t%s\t%s", bim.chr[j].c_str(), bim.id[j].c_str(), bim.a1[j].c_str(), bim.a2[j].c_str());
+            for (long k = 0; k < K; ++k) {
+                const double x = load[(size_t)k * Mtot + j];
+                if (std::isfinite(x)) std::fprintf(w, "\t%.12g", x);
+                else std::fprintf(w, "\tNA");
+            }
+            std::fprintf(w, "\n");
+        }
+        if (std::fclose(w) != 0) fatal("FATAL  : short write on " + pre + ".var");
+    }
+    double worst = 0.0;
+    for (long k = 0; k < K; ++k) worst = std::max(worst, rep.resid[k]);
+    std::printf("PCA    : %u rows, %u markers used, panel of %d, %d iterations run, last Ritz change %g, largest residual %g, written to %s (%.3f ms on the device)\n",
+                Ntot, rep.m_used, L, rep.iters_run, rep.ritz_change, worst, vec.c_str(), ms[0]);
+    return 0;
+}
+
 } // namespace
 
 int main(int argc, const char* argv[])
@@ -1487,6 +1626,27 @@ int main(int argc, const char* argv[])
         if (!std::isfinite(king_cutoff(opt))) fatal("FATAL  : --king-cutoff " + opt.kingCutoff + ": the cutoff must be a finite number");
     } else if (!opt.kingOut.empty() || opt.kingCutoffGiven)
         fatal(std::string("FATAL  : ") + (!opt.kingOut.empty() ? "--king-out" : "--king-cutoff") + " needs --king");
+    if (opt.pca) {
+        if (opt.bayesType == "bayesWMPI") fatal("FATAL  : --pca takes a bayesMPI command line, not --mpibayes bayesWMPI");
+        if (!opt.predictBfile.empty()) fatal("FATAL  : --pca cannot be combined with --predict-bfile");
+        if (opt.ldGiven) fatal("FATAL  : --pca cannot be combined with --ld-window");
+        if (opt.assoc) fatal("FATAL  : --pca cannot be combined with --assoc");
+        if (opt.king) fatal("FATAL  : --pca cannot be combined with --king");
+        if (opt.restart) fatal("FATAL  : --pca does not sample: it cannot be combined with --restart");
+        if (nranks > 1) fatal("FATAL  : --pca runs on one process (WORLD_SIZE = " + std::to_string(nranks) + ")");
+        long v = 0;
+        double t = 0.0;
+        if (!whole_int(opt.pcaK, v) || v < 1 || v > PCA_KMAX)
+            fatal("FATAL  : --pca " + opt.pcaK + ": the number of components must be an integer from 1 to " + std::to_string(PCA_KMAX));
+        if (opt.pcaItersGiven && (!whole_int(opt.pcaIters, v) || v < 1))
+            fatal("FATAL  : --pca-iters " + opt.pcaIters + ": needs at least one iteration");
+        if (opt.pcaItersGiven && v > std::numeric_limits<int>::max())
+            fatal("FATAL  : --pca-iters " + opt.pcaIters + ": at most " + std::to_string(std::numeric_limits<int>::max()) + " iterations");
+        if (opt.pcaTolGiven && (!whole_num(opt.pcaTol, t) || !std::isfinite(t) || t < 0.0))
+            fatal("FATAL  : --pca-tol " + opt.pcaTol + ": the tolerance must be a finite number >= 0");
+    } else if (opt.pcaItersGiven || opt.pcaTolGiven || opt.pcaOutGiven || opt.pcaLoadings)
+        fatal(std::string("FATAL  : ") + (opt.pcaItersGiven ? "--pca-iters" : opt.pcaTolGiven ? "--pca-tol" : opt.pcaOutGiven ? "--pca-out" : "--pca-loadings") +
+              " needs --pca");
     if (opt.bayesType == "bayesWMPI") return run_bayesw(opt, rank, nranks, local_rank); // main.cpp:164-167
 
     // ---- inputs (main.cpp:69-70,88; BayesRRm.cpp:969-997) -------------------
@@ -1518,6 +1678,7 @@ int main(int argc, const char* argv[])
     if (opt.ldGiven) return run_ld(opt, keep, (unsigned)numInds, numNAs, Mtot, local_rank);
     if (opt.assoc) return run_assoc(opt, keep, y, covX, C, (unsigned)numInds, numNAs, Mtot, local_rank);
     if (opt.king) return run_king(opt, keep, (unsigned)numInds, numNAs, Mtot, local_rank);
+    if (opt.pca) return run_pca(opt, keep, (unsigned)numInds, numNAs, Mtot, local_rank);
 
     std::vector<int32_t> groups;
     std::vector<std::vector<double>> mS;

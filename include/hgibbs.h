@@ -294,6 +294,35 @@ int hgibbs_king_pairs_get(hgibbs_t h, uint32_t* ab, int32_t* counts, double* kin
  * list), not the host copies or the allocations */
 int hgibbs_last_king_ms(hgibbs_t h, double* ms);
 
+/* ---- principal components of the loaded rows ------- */
+/* The top K eigenpairs of A = X X' / M_used over the handle's n_local rows, X the chain's standardised genotypes (hgibbs_marker_stats;
+ * x = 0 at a missing call; a marker without a finite mstd contributes nothing and is not counted in M_used), by block subspace
+ * iteration on a panel of L vectors (K <= L <= 32) with a final Rayleigh-Ritz step.  A is never formed: an iteration is T = X'Q through
+ * the kernels of hgibbs_marker_dots and Y = X T through those of hgibbs_score, on panels that stay in device memory; Y is made
+ * orthonormal by CholeskyQR done twice.  The call stops after `iters` iterations or, for tol > 0, when the largest relative change of
+ * the first K Ritz values between two iterations is <= tol.
+ *   Q0        L x n_local start vectors (vector-major), or NULL: then entry (k, i) comes from a counter hash of (seed, k, i)
+ *   eigval    K eigenvalues of A, descending
+ *   pcs       K x n_local, unit length, orthonormal; the entry of largest magnitude of each is positive (lowest index on a tie)
+ *   loadings  K x M unit-length right singular vectors X'v_k / sqrt(M_used lambda_k), NaN outside M_used; or NULL
+ *   rep       iterations run, M_used, the last relative change of the Ritz values (HUGE_VAL after one iteration) and
+ *             resid[k] = |A v_k - lambda_k v_k| / lambda_k from one more pair of products; or NULL (no residuals, no products)
+ * The products are exact integer operators and every floating-point sum of the panel algebra runs in a fixed order: for given
+ * arguments the results are bit-identical whatever the options mdots_split, score_sp and score_ranges say.  Refused with a message:
+ * several ranks, no genotypes, K < 1, K > L, L > 32, L >= n_local, L > M_used, iters < 1, tol negative or not finite, a non-finite
+ * Q0, n_local >= 2^29, panels that do not fit in free device memory, a panel that loses rank. */
+typedef struct {
+    int32_t iters_run;
+    uint32_t m_used;
+    double ritz_change;
+    double resid[32];
+} hgibbs_pca_report;
+int hgibbs_pca(hgibbs_t h, int K, int L, int iters, double tol, const double* Q0, uint64_t seed, double* eigval, double* pcs,
+               double* loadings, hgibbs_pca_report* rep);
+/* device time of the last hgibbs_pca in ms, kernels only: ms4[0] the whole call, [1] the X'Q products, [2] the X T products, [3] the
+ * panel algebra of the iterations (fold, Gram matrices, CholeskyQR); the start panel, the final step and the residuals are in [0] only */
+int hgibbs_last_pca_ms(hgibbs_t h, double* ms4);
+
 /* ======================================================================== */
 /* Host driver: the body of BayesRRm::runMpiGibbs (src/BayesRRm.cpp:933-2939)
  * for --mpibayes bayesMPI, restated on top of hgibbs_*.                     */
