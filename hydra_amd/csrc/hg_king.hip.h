@@ -243,30 +243,25 @@ __global__ __launch_bounds__(256) void k_king_image(const uint8_t* __restrict__ 
 // the checks every entry point makes
 int king_check(hgibbs_ctx* h, const char* who)
 {
-    if (!h) return fail("%s: null handle", who);
-    if (!h->bed) return fail("%s: no genotypes loaded on this handle", who);
-    if (h->nranks > 1 || h->comm) return fail("%s: one rank only (this handle has %d): pairs across shards are not formed", who, h->nranks);
+    if (op_guard(h, who, "pairs across shards are not formed")) return 1;
     if (h->M >= (1u << 31)) return fail("%s: %u markers, at most 2^31 - 1 (i32 counts)", who, h->M);
     if (h->n_local > 65535u * 16u * KG_BT) return fail("%s: %u rows, at most %u (blocks of %d rows)", who, h->n_local, 65535u * 16u * KG_BT, 16 * KG_BT);
     return 0;
 }
 
-// the individual-major image of the whole BED (freed by the caller): allocated here, refused when it does not fit beside `extra`
-// bytes; king_image_build writes it
-int king_image(hgibbs_ctx* h, size_t extra, uint32_t*& img, uint32_t& npi, uint32_t& ntile, uint32_t& nks, const char* who)
+// the individual-major image of the whole BED: allocated here, refused when it does not fit beside `extra` bytes; king_image_build
+// writes it
+int king_image(hgibbs_ctx* h, size_t extra, DevBuf<uint32_t>& img, uint32_t& npi, uint32_t& ntile, uint32_t& nks, const char* who)
 {
     ntile = (h->n_local + 15u) / 16u;
     npi = 16u * ntile;
     nks = (h->M + 63u) / 64u;
     const uint32_t ngrp = 4u * nks;
-    const size_t bytes = (size_t)ngrp * npi * 4u;
-    size_t fre = 0, tot = 0;
-    HIP_TRY(hipMemGetInfo(&fre, &tot));
-    if (bytes + extra + (64ull << 20) > fre)
-        return fail("%s: the individual-major image needs %.1f MiB and the call %.1f MiB more, %.1f MiB of device memory are free", who,
-                    bytes / 1048576.0, extra / 1048576.0, fre / 1048576.0);
-    HIP_TRY(hipMalloc(&img, bytes));
-    return 0;
+    const size_t words = (size_t)ngrp * npi;
+    if (need_device_memory(words * 4u + extra, "%s: the individual-major image needs %.1f MiB and the call %.1f MiB more", who, words * 4u / 1048576.0,
+                           extra / 1048576.0))
+        return 1;
+    return img.alloc(words);
 }
 
 int king_image_build(hgibbs_ctx* h, uint32_t* img, uint32_t npi, uint32_t ntile, uint32_t nks)
@@ -285,32 +280,6 @@ dim3 king_grid(size_t nbp, uint32_t split)
     return dim3(gx, (uint32_t)((nbp + gx - 1) / gx), split);
 }
 
-struct KingBufs {
-    uint32_t* img = nullptr;
-    uint32_t* bpairs = nullptr;
-    int32_t* counts = nullptr;
-    unsigned long long* nlist = nullptr;
-    uint32_t* ab = nullptr;
-    int32_t* lcounts = nullptr;
-    double* lkin = nullptr;
-    void free_list()
-    {
-        void* q[] = {ab, lcounts, lkin};
-        for (void* x : q)
-            if (x) (void)hipFree(x);
-        ab = nullptr;
-        lcounts = nullptr;
-        lkin = nullptr;
-    }
-    ~KingBufs()
-    {
-        free_list();
-        void* q[] = {img, bpairs, counts, nlist};
-        for (void* x : q)
-            if (x) (void)hipFree(x);
-    }
-};
-
 } // namespace
 
 extern "C" int hgibbs_king(hgibbs_t h, uint32_t a0, uint32_t acount, uint32_t b0, uint32_t bcount, int32_t* counts)
@@ -327,22 +296,15 @@ extern "C" int hgibbs_king(hgibbs_t h, uint32_t a0, uint32_t acount, uint32_t b0
     // pieces of A rows: at most 2^25 pairs (640 MiB of counts) on the device at a time
     const uint32_t piece = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(acount, (1ull << 25) / bcount));
     const size_t pbytes = (size_t)piece * bcount * 5u * sizeof(int32_t);
-    KingBufs b;
+    DevBuf<uint32_t> img, bpairs;
+    DevBuf<int32_t> dcounts;
     uint32_t npi = 0, ntile = 0, nks = 0;
     double total_ms = 0.0;
-    auto lap = [&]() -> int { // device time since ev0
-        HIP_TRY(hipEventRecord(h->ev1, h->stream));
-        HIP_TRY(hipEventSynchronize(h->ev1));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-        total_ms += ms;
-        return 0;
-    };
-    if (king_image(h, pbytes, b.img, npi, ntile, nks, "hgibbs_king")) return 1;
-    HIP_TRY(hipMalloc(&b.counts, pbytes));
-    HIP_TRY(hipEventRecord(h->ev0, h->stream)); // (after the allocations: the device time is the kernels')
-    if (king_image_build(h, b.img, npi, ntile, nks)) return 1;
-    if (lap()) return 1;
+    if (king_image(h, pbytes, img, npi, ntile, nks, "hgibbs_king")) return 1;
+    if (dcounts.alloc((size_t)piece * bcount * 5u)) return 1;
+    if (lap_begin(h)) return 1; // (after the allocations: the device time is the kernels')
+    if (king_image_build(h, img, npi, ntile, nks)) return 1;
+    if (lap_end(h, total_ms)) return 1;
     const uint32_t tb0 = b0 / 16u, nbb = ((b0 + bcount - 1u) / 16u - tb0) / KG_BT + 1u;
     for (uint32_t p0 = a0; p0 < a0 + acount; p0 += piece) {
         const uint32_t pc = std::min(piece, a0 + acount - p0);
@@ -351,18 +313,15 @@ extern "C" int hgibbs_king(hgibbs_t h, uint32_t a0, uint32_t acount, uint32_t b0
         bp.reserve((size_t)nba * nbb);
         for (uint32_t i = 0; i < nba; ++i)
             for (uint32_t j = 0; j < nbb; ++j) bp.push_back((i << 16) | j);
-        if (b.bpairs) HIP_TRY(hipFree(b.bpairs));
-        b.bpairs = nullptr;
-        HIP_TRY(hipMalloc(&b.bpairs, bp.size() * sizeof(uint32_t)));
-        HIP_TRY(hipMemcpy(b.bpairs, bp.data(), bp.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        if (bpairs.alloc(bp.size())) return 1;
+        HIP_TRY(hipMemcpy(bpairs, bp.data(), bp.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         // marker ranges: enough workgroups for two per compute unit (option king_split fixes the number)
-        uint32_t split = h->king_split ? (uint32_t)h->king_split : (uint32_t)((2ull * h->num_cu + bp.size() - 1) / bp.size());
-        split = std::max(1u, std::min(split, nks));
-        const uint32_t ks_per = (nks + split - 1u) / split;
-        split = (nks + ks_per - 1u) / ks_per;
+        uint32_t ks_per = 0;
+        const uint32_t split =
+            split_ranges(nks, h->king_split ? (uint32_t)h->king_split : (uint32_t)((2ull * h->num_cu + bp.size() - 1) / bp.size()), NO_CAP, ks_per);
         KingArgs a{};
-        a.img = b.img;
-        a.bpairs = b.bpairs;
+        a.img = img;
+        a.bpairs = bpairs;
         a.nbp = (uint32_t)bp.size();
         a.npi = npi;
         a.ntile = ntile;
@@ -370,17 +329,17 @@ extern "C" int hgibbs_king(hgibbs_t h, uint32_t a0, uint32_t acount, uint32_t b0
         a.ks_per = ks_per;
         a.ta0 = ta0;
         a.tb0 = tb0;
-        a.counts = b.counts;
+        a.counts = dcounts;
         a.ra0 = p0;
         a.racount = pc;
         a.rb0 = b0;
         a.rbcount = bcount;
-        HIP_TRY(hipEventRecord(h->ev0, h->stream));
-        HIP_TRY(hipMemsetAsync(b.counts, 0, (size_t)pc * bcount * 5u * sizeof(int32_t), h->stream));
+        if (lap_begin(h)) return 1;
+        HIP_TRY(hipMemsetAsync(dcounts, 0, (size_t)pc * bcount * 5u * sizeof(int32_t), h->stream));
         k_king<false><<<king_grid(bp.size(), split), KG_WAVES * 64, 0, h->stream>>>(a);
         HIP_TRY(hipGetLastError());
-        if (lap()) return 1;
-        HIP_TRY(hipMemcpy(counts + (size_t)(p0 - a0) * bcount * 5u, b.counts, (size_t)pc * bcount * 5u * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (lap_end(h, total_ms)) return 1;
+        HIP_TRY(hipMemcpy(counts + (size_t)(p0 - a0) * bcount * 5u, dcounts, (size_t)pc * bcount * 5u * sizeof(int32_t), hipMemcpyDeviceToHost));
     }
     h->king_ms = total_ms;
     return 0;
@@ -398,7 +357,10 @@ extern "C" int hgibbs_king_pairs(hgibbs_t h, double cutoff, uint64_t* npairs)
     *npairs = 0;
     h->king_ms = 0.0;
 
-    KingBufs b;
+    DevBuf<uint32_t> img, bpairs, dab;
+    DevBuf<unsigned long long> nlist;
+    DevBuf<int32_t> lcounts;
+    DevBuf<double> lkin;
     uint32_t npi = 0, ntile = 0, nks = 0;
     const uint64_t all = (uint64_t)h->n_local * (h->n_local - 1u) / 2u;
     unsigned long long cap = std::max<uint64_t>(1, std::min<uint64_t>(all, KG_LIST0));
@@ -409,21 +371,19 @@ extern "C" int hgibbs_king_pairs(hgibbs_t h, double cutoff, uint64_t* npairs)
     bp.reserve((size_t)nb * (nb + 1u) / 2u);
     for (uint32_t i = 0; i < nb; ++i)
         for (uint32_t j = i; j < nb; ++j) bp.push_back((i << 16) | j);
-    if (king_image(h, cap * per + bp.size() * sizeof(uint32_t), b.img, npi, ntile, nks, "hgibbs_king_pairs")) return 1;
-    HIP_TRY(hipMalloc(&b.bpairs, bp.size() * sizeof(uint32_t)));
-    HIP_TRY(hipMemcpy(b.bpairs, bp.data(), bp.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc(&b.nlist, sizeof(unsigned long long)));
+    if (king_image(h, cap * per + bp.size() * sizeof(uint32_t), img, npi, ntile, nks, "hgibbs_king_pairs")) return 1;
+    if (bpairs.alloc(bp.size())) return 1;
+    HIP_TRY(hipMemcpy(bpairs, bp.data(), bp.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (nlist.alloc(1)) return 1;
     unsigned long long found = 0;
     for (bool first = true;; first = false) {
-        HIP_TRY(hipMalloc(&b.ab, cap * 2 * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc(&b.lcounts, cap * 5 * sizeof(int32_t)));
-        HIP_TRY(hipMalloc(&b.lkin, cap * sizeof(double)));
-        HIP_TRY(hipEventRecord(h->ev0, h->stream)); // (after the allocations: the device time is the kernels')
-        if (first && king_image_build(h, b.img, npi, ntile, nks)) return 1;
-        HIP_TRY(hipMemsetAsync(b.nlist, 0, sizeof(unsigned long long), h->stream));
+        if (dab.alloc(cap * 2) || lcounts.alloc(cap * 5) || lkin.alloc(cap)) return 1;
+        if (lap_begin(h)) return 1; // (after the allocations: the device time is the kernels')
+        if (first && king_image_build(h, img, npi, ntile, nks)) return 1;
+        HIP_TRY(hipMemsetAsync(nlist, 0, sizeof(unsigned long long), h->stream));
         KingArgs a{};
-        a.img = b.img;
-        a.bpairs = b.bpairs;
+        a.img = img;
+        a.bpairs = bpairs;
         a.nbp = (uint32_t)bp.size();
         a.npi = npi;
         a.ntile = ntile;
@@ -431,28 +391,23 @@ extern "C" int hgibbs_king_pairs(hgibbs_t h, double cutoff, uint64_t* npairs)
         a.ks_per = nks; // every marker in one workgroup: the formula needs the whole counts
         a.n_local = h->n_local;
         a.cutoff = cutoff;
-        a.nlist = b.nlist;
+        a.nlist = nlist;
         a.cap = cap;
-        a.ab = b.ab;
-        a.lcounts = b.lcounts;
-        a.lkin = b.lkin;
+        a.ab = dab;
+        a.lcounts = lcounts;
+        a.lkin = lkin;
         k_king<true><<<king_grid(bp.size(), 1), KG_WAVES * 64, 0, h->stream>>>(a);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(h->ev1, h->stream));
-        HIP_TRY(hipEventSynchronize(h->ev1));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-        total_ms += ms;
-        HIP_TRY(hipMemcpy(&found, b.nlist, sizeof found, hipMemcpyDeviceToHost));
+        if (lap_end(h, total_ms)) return 1;
+        HIP_TRY(hipMemcpy(&found, nlist, sizeof found, hipMemcpyDeviceToHost));
         if (found <= cap) break;
-        // the list overflowed: every pair was counted, so the second run fits exactly
-        b.free_list();
+        // the list overflowed: every pair was counted, so the second run fits exactly (the first list goes before the check)
+        dab.release();
+        lcounts.release();
+        lkin.release();
         cap = found;
-        size_t fre = 0, tot = 0;
-        HIP_TRY(hipMemGetInfo(&fre, &tot));
-        if (cap * per + (64ull << 20) > fre)
-            return fail("hgibbs_king_pairs: %llu pairs pass the cutoff %g: the list needs %.1f MiB, %.1f MiB of device memory are free", found,
-                        cutoff, cap * per / 1048576.0, fre / 1048576.0);
+        if (need_device_memory(cap * per, "hgibbs_king_pairs: %llu pairs pass the cutoff %g: the list needs %.1f MiB", found, cutoff, cap * per / 1048576.0))
+            return 1;
     }
 
     // the list, sorted by (a, b): the order of the atomics never shows
@@ -460,9 +415,9 @@ extern "C" int hgibbs_king_pairs(hgibbs_t h, double cutoff, uint64_t* npairs)
     std::vector<int32_t> cnt(found * 5);
     std::vector<double> kin(found);
     if (found) {
-        HIP_TRY(hipMemcpy(ab.data(), b.ab, ab.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(cnt.data(), b.lcounts, cnt.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(kin.data(), b.lkin, kin.size() * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(ab.data(), dab, ab.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(cnt.data(), lcounts, cnt.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(kin.data(), lkin, kin.size() * sizeof(double), hipMemcpyDeviceToHost));
     }
     std::vector<uint64_t> key(found);
     for (size_t i = 0; i < found; ++i) key[i] = ((uint64_t)ab[2 * i] << 32) | ab[2 * i + 1];

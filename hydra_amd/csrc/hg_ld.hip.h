@@ -225,9 +225,7 @@ __global__ __launch_bounds__(LD_TPB) void k_ld_final(const unsigned long long* _
 
 extern "C" int hgibbs_ld(hgibbs_t h, uint32_t m0, uint32_t count, uint32_t W, double* r_host, int64_t* sums_host)
 {
-    if (!h) return fail("hgibbs_ld: null handle");
-    if (!h->bed) return fail("hgibbs_ld: no genotypes loaded on this handle");
-    if (h->nranks > 1 || h->comm) return fail("hgibbs_ld: one rank only (this handle has %d): the band is not exchanged between ranks", h->nranks);
+    if (op_guard(h, "hgibbs_ld", "the band is not exchanged between ranks")) return 1;
     if (W == 0 || W > LD_WMAX) return fail("hgibbs_ld: W = %u, must be in [1, %u]", W, LD_WMAX);
     if ((uint64_t)m0 + count > h->M) return fail("hgibbs_ld: markers [%u, %llu) out of range (M = %u)", m0, (unsigned long long)m0 + count, h->M);
     if (h->n_local >= LD_NMAX) return fail("hgibbs_ld: %u individuals, at most %u (i32 partial sums)", h->n_local, LD_NMAX - 1u);
@@ -237,35 +235,22 @@ extern "C" int hgibbs_ld(hgibbs_t h, uint32_t m0, uint32_t count, uint32_t W, do
     const uint32_t M = h->M, ntile = (M + 15u) / 16u;
 
     // tiles of sixteen markers with a missing call in a column (the counts of hgibbs_marker_stats)
-    std::vector<uint8_t> tmiss(ntile, 0);
-    {
-        std::vector<unsigned long long> c((size_t)M * 3);
-        HIP_TRY(hipMemcpy(c.data(), h->counts, c.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        for (uint32_t j = 0; j < M; ++j)
-            if (c[3ull * j + 2]) tmiss[j / 16u] = 1;
-    }
+    std::vector<uint8_t> tmiss;
+    if (missing_tiles(h, 16u, tmiss)) return 1;
 
     // pieces of at most 2^24 pairs (the device's sums: 512 MiB) and 2^20 markers (grid y)
     const uint32_t piece = std::max<uint32_t>(16u, (uint32_t)std::min<uint64_t>({(uint64_t)count, 1ull << 20, ((1ull << 24) / W + 15u) / 16u * 16u}));
-    struct Bufs {
-        uint8_t* tmiss = nullptr;
-        unsigned long long* acc = nullptr;
-        double* r = nullptr;
-        long long* sums = nullptr;
-        ~Bufs()
-        {
-            void* p[] = {tmiss, acc, r, sums};
-            for (void* x : p)
-                if (x) (void)hipFree(x);
-        }
-    } b;
+    DevBuf<uint8_t> dmiss;
+    DevBuf<unsigned long long> acc;
+    DevBuf<double> r;
+    DevBuf<long long> sums;
     const size_t np = (size_t)piece * W;
     tmiss.resize((size_t)ntile + LD_WMAX / 16 + LD_QP + LD_WAVES, 0); // (the window's tiles past M read as clean)
-    HIP_TRY(hipMalloc(&b.tmiss, tmiss.size()));
-    HIP_TRY(hipMemcpy(b.tmiss, tmiss.data(), tmiss.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc(&b.acc, np * 4 * sizeof(unsigned long long)));
-    if (r_host) HIP_TRY(hipMalloc(&b.r, np * sizeof(double)));
-    if (sums_host) HIP_TRY(hipMalloc(&b.sums, np * 4 * sizeof(long long)));
+    if (dmiss.alloc(tmiss.size())) return 1;
+    HIP_TRY(hipMemcpy(dmiss, tmiss.data(), tmiss.size(), hipMemcpyHostToDevice));
+    if (acc.alloc(np * 4)) return 1;
+    if (r_host && r.alloc(np)) return 1;
+    if (sums_host && sums.alloc(np * 4)) return 1;
 
     const uint32_t n_sub = (h->n_local + LD_SUBD * 16 - 1) / (LD_SUBD * 16);
     const uint32_t nq = (W + 15u) / 16u + 1u; // B tiles per A tile: A tile t pairs with tiles t .. t + floor((W + 15) / 16)
@@ -275,30 +260,24 @@ extern "C" int hgibbs_ld(hgibbs_t h, uint32_t m0, uint32_t count, uint32_t W, do
         const uint32_t t0 = p0 / 16u, t1 = (p0 + pc - 1u) / 16u + 1u;
         const uint32_t gy = (t1 - t0 + LD_WAVES - 1u) / LD_WAVES, gz = (nq + LD_QP - 1u) / LD_QP;
         // individual ranges: enough workgroups for eight per compute unit (option ld_split fixes the number)
-        uint32_t gx = h->ld_split ? (uint32_t)h->ld_split : (8u * (uint32_t)h->num_cu + gy * gz - 1u) / (gy * gz);
-        gx = std::max(1u, std::min(gx, n_sub));
-        const uint32_t sub_per = (n_sub + gx - 1u) / gx;
-        gx = (n_sub + sub_per - 1u) / sub_per;
-        HIP_TRY(hipEventRecord(h->ev0, h->stream));
-        HIP_TRY(hipMemsetAsync(b.acc, 0, (size_t)pc * W * 4 * sizeof(unsigned long long), h->stream));
+        uint32_t sub_per = 0;
+        const uint32_t gx = split_ranges(n_sub, h->ld_split ? (uint32_t)h->ld_split : (8u * (uint32_t)h->num_cu + gy * gz - 1u) / (gy * gz), NO_CAP, sub_per);
+        if (lap_begin(h)) return 1;
+        HIP_TRY(hipMemsetAsync(acc, 0, (size_t)pc * W * 4 * sizeof(unsigned long long), h->stream));
         const dim3 grid(gx, gy, gz);
         if (h->any_missing)
-            k_ld<true><<<grid, LD_WAVES * 64, 0, h->stream>>>(h->bed, h->stride, M, h->n_local, t0, t1, nq, sub_per, n_sub, b.tmiss, W, p0, pc, b.acc);
+            k_ld<true><<<grid, LD_WAVES * 64, 0, h->stream>>>(h->bed, h->stride, M, h->n_local, t0, t1, nq, sub_per, n_sub, dmiss, W, p0, pc, acc);
         else
-            k_ld<false><<<grid, LD_WAVES * 64, 0, h->stream>>>(h->bed, h->stride, M, h->n_local, t0, t1, nq, sub_per, n_sub, b.tmiss, W, p0, pc, b.acc);
+            k_ld<false><<<grid, LD_WAVES * 64, 0, h->stream>>>(h->bed, h->stride, M, h->n_local, t0, t1, nq, sub_per, n_sub, dmiss, W, p0, pc, acc);
         HIP_TRY(hipGetLastError());
         const uint64_t npc = (uint64_t)pc * W;
-        k_ld_final<<<(uint32_t)((npc + LD_TPB - 1) / LD_TPB), LD_TPB, 0, h->stream>>>(b.acc, h->counts, h->mave, h->mstd, M, h->n_local, h->n_global,
-                                                                                       W, p0, pc, b.r, b.sums);
+        k_ld_final<<<(uint32_t)((npc + LD_TPB - 1) / LD_TPB), LD_TPB, 0, h->stream>>>(acc, h->counts, h->mave, h->mstd, M, h->n_local, h->n_global,
+                                                                                       W, p0, pc, r, sums);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(h->ev1, h->stream));
-        HIP_TRY(hipEventSynchronize(h->ev1));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-        total_ms += ms;
+        if (lap_end(h, total_ms)) return 1;
         const size_t off = (size_t)(p0 - m0) * W;
-        if (r_host) HIP_TRY(hipMemcpy(r_host + off, b.r, npc * sizeof(double), hipMemcpyDeviceToHost));
-        if (sums_host) HIP_TRY(hipMemcpy(sums_host + off * 4, b.sums, npc * 4 * sizeof(long long), hipMemcpyDeviceToHost));
+        if (r_host) HIP_TRY(hipMemcpy(r_host + off, r, npc * sizeof(double), hipMemcpyDeviceToHost));
+        if (sums_host) HIP_TRY(hipMemcpy(sums_host + off * 4, sums, npc * 4 * sizeof(long long), hipMemcpyDeviceToHost));
     }
     h->ld_ms = total_ms;
     return 0;

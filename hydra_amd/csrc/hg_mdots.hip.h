@@ -217,14 +217,6 @@ __global__ __launch_bounds__(MD_WAVES * 64) void k_mdots(const uint8_t* __restri
     }
 }
 
-// (hi 2^32 + lo) 2^-E as ONE rounding: carry the low word's high bits into hi (exact), then hi 2^32 is exact in f64
-__device__ __forceinline__ double md_round(long long hi, long long lo, int E)
-{
-    hi += lo >> 32;
-    lo &= 0xFFFFFFFFll;
-    return ldexp(ldexp((double)hi, 32) + (double)lo, -E);
-}
-
 // One thread per (marker, vector): P = D - 3 R, Q = sum_all q - R, each rounded once; x_j'u_k = mstd (P - mave Q)
 __global__ __launch_bounds__(MD_TPB) void k_mdots_final(const unsigned long long* __restrict__ acc, const unsigned long long* __restrict__ ksum,
                                                         const int* __restrict__ scale, const double* __restrict__ mave,
@@ -239,7 +231,7 @@ __global__ __launch_bounds__(MD_TPB) void k_mdots_final(const unsigned long long
     const long long Plo = (long long)(a[0] - 3ull * Rlo), Phi = (long long)(a[1] - 3ull * Rhi);
     const long long Qlo = (long long)(ksum[2u * k + 1u] - Rlo), Qhi = (long long)(ksum[2u * k] - Rhi);
     const int E = scale[k];
-    const double P = md_round(Phi, Plo, E), Q = md_round(Qhi, Qlo, E);
+    const double P = round_halves(Phi, Plo, E), Q = round_halves(Qhi, Qlo, E);
     const double sd = mstd[j];
     out[e] = isfinite(sd) ? sd * (P - mave[j] * Q) : __builtin_nan("");
     if (raw) {
@@ -263,19 +255,13 @@ static void mdots_launch(hgibbs_ctx* h, dim3 grid, uint32_t t0, uint32_t t1, uin
 // The work buffers of the pipeline for up to `kmax` vectors against up to `cmax` markers of a chunk, allocated once by the caller
 // (hgibbs_marker_dots per call, hgibbs_pca per call for all its iterations): everything but the vectors and the results.
 struct MdotsWs {
-    unsigned long long *maxbits = nullptr, *acc = nullptr; // (ksum lies inside maxbits)
-    uint32_t* bad = nullptr;
-    int* scale = nullptr;
-    rl_v4i* img = nullptr;
-    uint8_t* tmiss = nullptr;
+    DevBuf<unsigned long long> maxbits, acc; // (ksum lies inside maxbits)
+    DevBuf<uint32_t> bad;
+    DevBuf<int> scale;
+    DevBuf<rl_v4i> img;
+    DevBuf<uint8_t> tmiss;
     int kmax = 0;
     uint32_t cmax = 0;
-    ~MdotsWs()
-    {
-        void* p[] = {maxbits, acc, bad, scale, img, tmiss};
-        for (void* x : p)
-            if (x) (void)hipFree(x);
-    }
 };
 
 static size_t mdots_ws_bytes(const hgibbs_ctx* h, int kmax, uint32_t cmax)
@@ -287,24 +273,19 @@ static size_t mdots_ws_bytes(const hgibbs_ctx* h, int kmax, uint32_t cmax)
 // Allocates the buffers and reads the marker-stats counts once (tiles of sixteen markers with a missing call in a column); synchronises
 static int mdots_ws_create(hgibbs_ctx* h, MdotsWs& b, int kmax, uint32_t cmax)
 {
-    const uint32_t M = h->M, ntile = (M + 15u) / 16u, n = h->n_local;
-    std::vector<uint8_t> tmiss(ntile, 0);
-    {
-        std::vector<unsigned long long> cts((size_t)M * 3);
-        HIP_TRY(hipMemcpy(cts.data(), h->counts, cts.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        for (uint32_t j = 0; j < M; ++j)
-            if (cts[3ull * j + 2]) tmiss[j / 16u] = 1;
-    }
+    const uint32_t n = h->n_local;
+    std::vector<uint8_t> tmiss;
+    if (missing_tiles(h, 16u, tmiss)) return 1;
     const int tiles = (kmax + 1) / 2;
     const uint32_t n_sub = (n + MD_SUBI - 1) / MD_SUBI; // slices that hold individuals (all inside n_pad, a multiple of 4096)
     b.kmax = kmax;
     b.cmax = cmax;
-    HIP_TRY(hipMalloc(&b.maxbits, (size_t)kmax * 3 * sizeof(unsigned long long))); // max, then the two halves of sum_i q
-    HIP_TRY(hipMalloc(&b.bad, sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&b.scale, (size_t)kmax * sizeof(int)));
-    HIP_TRY(hipMalloc(&b.img, (size_t)n_sub * tiles * 8 * 64 * sizeof(rl_v4i)));
-    HIP_TRY(hipMalloc(&b.tmiss, tmiss.size()));
-    HIP_TRY(hipMalloc(&b.acc, (size_t)cmax * kmax * 4 * sizeof(unsigned long long)));
+    if (b.maxbits.alloc((size_t)kmax * 3)) return 1; // max, then the two halves of sum_i q
+    if (b.bad.alloc(1)) return 1;
+    if (b.scale.alloc((size_t)kmax)) return 1;
+    if (b.img.alloc((size_t)n_sub * tiles * 8 * 64)) return 1;
+    if (b.tmiss.alloc(tmiss.size())) return 1;
+    if (b.acc.alloc((size_t)cmax * kmax * 4)) return 1;
     HIP_TRY(hipMemcpy(b.tmiss, tmiss.data(), tmiss.size(), hipMemcpyHostToDevice));
     return 0;
 }
@@ -344,11 +325,8 @@ static int mdots_dev_run(hgibbs_ctx* h, MdotsWs& b, uint32_t m0, uint32_t count,
         const uint32_t per_wg = (uint32_t)(MD_WAVES * md_mt(tp)); // marker tiles per workgroup
         const uint32_t gx = (t1 - t0 + per_wg - 1u) / per_wg;
         // individual ranges: enough workgroups for eight per compute unit (option mdots_split fixes the number), no range above MD_SUB_MAX slices
-        uint32_t gy = h->mdots_split ? (uint32_t)h->mdots_split : (8u * (uint32_t)h->num_cu + gx - 1u) / gx;
-        gy = std::max(gy, (n_sub + MD_SUB_MAX - 1u) / MD_SUB_MAX);
-        gy = std::max(1u, std::min(gy, n_sub));
-        const uint32_t sub_per = (n_sub + gy - 1u) / gy;
-        gy = (n_sub + sub_per - 1u) / sub_per;
+        uint32_t sub_per = 0;
+        const uint32_t gy = split_ranges(n_sub, h->mdots_split ? (uint32_t)h->mdots_split : (8u * (uint32_t)h->num_cu + gx - 1u) / gx, MD_SUB_MAX, sub_per);
         const dim3 grid(gx, gy);
         switch (tp) {
         case 1: mdots_launch<1>(h, grid, t0, t1, sub_per, n_sub, b.img, tiles, tv0, ntp, K, b.tmiss, m0, count, b.acc); break;
@@ -364,9 +342,7 @@ static int mdots_dev_run(hgibbs_ctx* h, MdotsWs& b, uint32_t m0, uint32_t count,
 
 extern "C" int hgibbs_marker_dots(hgibbs_t h, uint32_t m0, uint32_t count, int K, const double* U, double* out, double* raw)
 {
-    if (!h) return fail("hgibbs_marker_dots: null handle");
-    if (!h->bed) return fail("hgibbs_marker_dots: no genotypes loaded on this handle");
-    if (h->nranks > 1 || h->comm) return fail("hgibbs_marker_dots: one rank only (this handle has %d): the dots are not summed over ranks", h->nranks);
+    if (op_guard(h, "hgibbs_marker_dots", "the dots are not summed over ranks")) return 1;
     if (K <= 0 || K > MD_KMAX) return fail("hgibbs_marker_dots: K = %d, must be in [1, %d]", K, MD_KMAX);
     if (!U || !out) return fail("hgibbs_marker_dots: null argument");
     if ((uint64_t)m0 + count > h->M) return fail("hgibbs_marker_dots: markers [%u, %llu) out of range (M = %u)", m0, (unsigned long long)m0 + count, h->M);
@@ -380,32 +356,22 @@ extern "C" int hgibbs_marker_dots(hgibbs_t h, uint32_t m0, uint32_t count, int K
 
     // a thin wrapper around the device-pointer pipeline: its own workspace, the vectors in, the results out
     MdotsWs ws;
-    struct Bufs {
-        double *U = nullptr, *out = nullptr, *raw = nullptr;
-        ~Bufs()
-        {
-            void* p[] = {U, out, raw};
-            for (void* x : p)
-                if (x) (void)hipFree(x);
-        }
-    } b;
+    DevBuf<double> dU, dout, draw;
     const size_t nk = (size_t)count * K;
-    HIP_TRY(hipMalloc(&b.U, (size_t)K * n * sizeof(double)));
+    if (dU.alloc((size_t)K * n)) return 1;
     if (mdots_ws_create(h, ws, K, count)) return 1;
-    HIP_TRY(hipMalloc(&b.out, nk * sizeof(double)));
-    if (raw) HIP_TRY(hipMalloc(&b.raw, nk * 2 * sizeof(double)));
-    HIP_TRY(hipMemcpyAsync(b.U, U, (size_t)K * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (dout.alloc(nk)) return 1;
+    if (raw && draw.alloc(nk * 2)) return 1;
+    HIP_TRY(hipMemcpyAsync(dU, U, (size_t)K * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
     if (mdots_dev_clear(h, ws, count, K)) return 1;
 
     // device time from here to the rounded result: every kernel of the call, not the host copies around it
-    HIP_TRY(hipEventRecord(h->ev0, h->stream));
-    if (mdots_dev_run(h, ws, m0, count, K, b.U, b.out, b.raw)) return 1;
-    HIP_TRY(hipEventRecord(h->ev1, h->stream));
-    HIP_TRY(hipEventSynchronize(h->ev1));
-    HIP_TRY(hipMemcpy(out, b.out, nk * sizeof(double), hipMemcpyDeviceToHost));
-    if (raw) HIP_TRY(hipMemcpy(raw, b.raw, nk * 2 * sizeof(double), hipMemcpyDeviceToHost));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    double ms = 0.0;
+    if (lap_begin(h)) return 1;
+    if (mdots_dev_run(h, ws, m0, count, K, dU, dout, draw)) return 1;
+    if (lap_end(h, ms)) return 1;
+    HIP_TRY(hipMemcpy(out, dout, nk * sizeof(double), hipMemcpyDeviceToHost));
+    if (raw) HIP_TRY(hipMemcpy(raw, draw, nk * 2 * sizeof(double), hipMemcpyDeviceToHost));
     h->mdots_ms = ms;
     return 0;
 }

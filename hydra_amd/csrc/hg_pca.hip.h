@@ -300,13 +300,7 @@ struct PcaClock {
 };
 
 struct PcaBufs {
-    double *Q = nullptr, *Q1 = nullptr, *Y = nullptr, *T = nullptr, *a = nullptr, *o = nullptr, *partial = nullptr, *small = nullptr, *out = nullptr;
-    ~PcaBufs()
-    {
-        void* p[] = {Q, Q1, Y, T, a, o, partial, small, out};
-        for (void* x : p)
-            if (x) (void)hipFree(x);
-    }
+    DevBuf<double> Q, Q1, Y, T, a, o, partial, small, out;
 };
 
 // P'P (n x L panel) into dG (device, L x L): the partials, then their sum
@@ -325,9 +319,7 @@ int pca_gram(hgibbs_ctx* h, PcaBufs& b, const double* P, uint32_t n, int L, int 
 extern "C" int hgibbs_pca(hgibbs_t h, int K, int L, int iters, double tol, const double* Q0, uint64_t seed, double* eigval, double* pcs,
                           double* loadings, hgibbs_pca_report* rep)
 {
-    if (!h) return fail("hgibbs_pca: null handle");
-    if (!h->bed) return fail("hgibbs_pca: no genotypes loaded on this handle");
-    if (h->nranks > 1 || h->comm) return fail("hgibbs_pca: one rank only (this handle has %d): the panel products are not summed over ranks", h->nranks);
+    if (op_guard(h, "hgibbs_pca", "the panel products are not summed over ranks")) return 1;
     if (K < 1) return fail("hgibbs_pca: K = %d, needs at least one component", K);
     if (K > L) return fail("hgibbs_pca: K = %d above the panel width L = %d", K, L);
     if (L > PG_LMAX) return fail("hgibbs_pca: L = %d, at most %d vectors in the panel", L, PG_LMAX);
@@ -357,26 +349,15 @@ extern "C" int hgibbs_pca(hgibbs_t h, int K, int L, int iters, double tol, const
     const size_t nbmax = (big + PG_ROWS - 1) / PG_ROWS;
     const size_t outn = loadings ? (size_t)K * M : 0;
     const size_t bytes = (3 * nL + 3 * ML + nbmax * L * L + outn + 8 * PG_LMAX * PG_LMAX) * sizeof(double) + mdots_ws_bytes(h, L, M) + score_ws_bytes(h, L);
-    {
-        size_t fre = 0, tot = 0;
-        HIP_TRY(hipMemGetInfo(&fre, &tot));
-        if (bytes + (64ull << 20) > fre)
-            return fail("hgibbs_pca: the panels and work buffers need %.1f MiB, %.1f MiB of device memory are free", bytes / 1048576.0, fre / 1048576.0);
-    }
+    if (need_device_memory(bytes, "hgibbs_pca: the panels and work buffers need %.1f MiB", bytes / 1048576.0)) return 1;
     PcaBufs b;
     MdotsWs mw;
     ScoreWs sw;
     PcaClock clk;
     clk.stream = h->stream;
-    HIP_TRY(hipMalloc(&b.Q, nL * sizeof(double)));
-    HIP_TRY(hipMalloc(&b.Q1, nL * sizeof(double)));
-    HIP_TRY(hipMalloc(&b.Y, nL * sizeof(double)));
-    HIP_TRY(hipMalloc(&b.T, ML * sizeof(double)));
-    HIP_TRY(hipMalloc(&b.a, ML * sizeof(double)));
-    HIP_TRY(hipMalloc(&b.o, ML * sizeof(double)));
-    HIP_TRY(hipMalloc(&b.partial, nbmax * L * L * sizeof(double)));
-    HIP_TRY(hipMalloc(&b.small, 8 * PG_LMAX * PG_LMAX * sizeof(double)));
-    if (loadings) HIP_TRY(hipMalloc(&b.out, outn * sizeof(double)));
+    if (b.Q.alloc(nL) || b.Q1.alloc(nL) || b.Y.alloc(nL) || b.T.alloc(ML) || b.a.alloc(ML) || b.o.alloc(ML)) return 1;
+    if (b.partial.alloc(nbmax * L * L) || b.small.alloc(8 * PG_LMAX * PG_LMAX)) return 1;
+    if (loadings && b.out.alloc(outn)) return 1;
     if (mdots_ws_create(h, mw, L, M)) return 1;
     if (score_ws_create(h, sw, L)) return 1;
     if (clk.create()) return 1;

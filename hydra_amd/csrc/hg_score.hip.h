@@ -285,18 +285,16 @@ __global__ __launch_bounds__(SC_IND) void k_score(const uint8_t* __restrict__ be
     }
 }
 
-// out[i][s] = (hi 2^32 + lo) 2^-E_s, hi and lo with the constant sum_j q_o added: carry the low word's high bits into hi (exact),
-// then hi 2^32 is exact in f64 and the sum rounds once
+// out[i][s] = (hi 2^32 + lo) 2^-E_s, hi and lo with the constant sum_j q_o added, rounded once (round_halves)
 __global__ __launch_bounds__(SC_TPB) void k_score_final(const unsigned long long* __restrict__ acc, const unsigned long long* __restrict__ ksum,
                                                         const int* __restrict__ scale, uint32_t n_local, uint32_t S, double* __restrict__ out)
 {
     const uint64_t k = (uint64_t)blockIdx.x * SC_TPB + threadIdx.x;
     if (k >= (uint64_t)n_local * S) return;
     const uint32_t s = (uint32_t)(k % S);
-    long long lo = (long long)(acc[2 * k] + ksum[2 * s + 1]);
-    long long hi = (long long)(acc[2 * k + 1] + ksum[2 * s]) + (lo >> 32);
-    lo &= 0xFFFFFFFFll;
-    out[k] = ldexp(ldexp((double)hi, 32) + (double)lo, -scale[s]);
+    const long long lo = (long long)(acc[2 * k] + ksum[2 * s + 1]);
+    const long long hi = (long long)(acc[2 * k + 1] + ksum[2 * s]);
+    out[k] = round_halves(hi, lo, scale[s]);
 }
 
 } // namespace
@@ -321,18 +319,13 @@ static void score_launch(hgibbs_ctx* h, dim3 grid, uint32_t kb_per, const rl_v4i
 // The work buffers of the pipeline for up to `smax` weight vectors, allocated once by the caller (hgibbs_score per call, hgibbs_pca
 // per call for all its iterations): everything but the weights and the results.
 struct ScoreWs {
-    int* scale = nullptr;
-    unsigned long long *maxbits = nullptr, *ksum = nullptr, *acc = nullptr; // (ksum lies inside maxbits)
-    uint32_t* bad = nullptr;
-    int32_t* mslot = nullptr;
-    rl_v4i *wdig = nullptr, *mdig = nullptr;
+    DevBuf<int> scale;
+    DevBuf<unsigned long long> maxbits, acc;
+    unsigned long long* ksum = nullptr; // (lies inside maxbits)
+    DevBuf<uint32_t> bad;
+    DevBuf<int32_t> mslot;
+    DevBuf<rl_v4i> wdig, mdig;
     int smax = 0, sp = 0;
-    ~ScoreWs()
-    {
-        void* p[] = {scale, maxbits, bad, mslot, wdig, mdig, acc};
-        for (void* x : p)
-            if (x) (void)hipFree(x);
-    }
 };
 
 static size_t score_ws_bytes(const hgibbs_ctx* h, int smax)
@@ -349,29 +342,26 @@ static int score_ws_create(hgibbs_ctx* h, ScoreWs& b, int smax)
     const int sp = score_sp_for(h, smax), tiles = sp / 2;
     // blocks of 64 markers with a column that has missing calls: from the counts of hgibbs_marker_stats when they exist (summed
     // over ranks: a superset of this shard's, which costs only a product over zeros), else from this shard's own counts (no collective)
-    std::vector<int32_t> mslot(nkb, -1);
-    uint32_t nm = 0;
-    {
-        if (!h->have_stats && h->nranks <= 1 && !h->comm && compute_stats(h)) return 1;
-        if (!h->have_stats) {
-            k_counts<<<h->M, BLOCK, 0, h->stream>>>(h->bed, h->stride, h->n_pad, h->n_local, h->counts, h->M); // (local; compute_stats redoes them)
-            HIP_TRY(hipGetLastError());
-        }
-        std::vector<unsigned long long> c((size_t)M * 3);
-        HIP_TRY(hipMemcpyAsync(c.data(), h->counts, c.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        for (uint32_t j = 0; j < M; ++j)
-            if (c[3ull * j + 2] && mslot[j / 64u] < 0) mslot[j / 64u] = (int32_t)nm++;
+    if (!h->have_stats && h->nranks <= 1 && !h->comm && compute_stats(h)) return 1;
+    if (!h->have_stats) {
+        k_counts<<<h->M, BLOCK, 0, h->stream>>>(h->bed, h->stride, h->n_pad, h->n_local, h->counts, h->M); // (local; compute_stats redoes them)
+        HIP_TRY(hipGetLastError());
     }
+    std::vector<uint8_t> miss;
+    if (missing_tiles(h, 64u, miss)) return 1;
+    std::vector<int32_t> mslot(nkb, -1); // the slots of the blocks with missing calls, in marker order
+    uint32_t nm = 0;
+    for (uint32_t kb = 0; kb < nkb; ++kb)
+        if (miss[kb]) mslot[kb] = (int32_t)nm++;
     b.smax = smax;
     b.sp = sp;
-    HIP_TRY(hipMalloc(&b.scale, (size_t)smax * sizeof(int)));
-    HIP_TRY(hipMalloc(&b.maxbits, (size_t)smax * 3 * sizeof(unsigned long long))); // max, then the two halves of sum_j q_o
-    HIP_TRY(hipMalloc(&b.bad, sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&b.mslot, (size_t)nkb * sizeof(int32_t)));
-    HIP_TRY(hipMalloc(&b.wdig, (size_t)nkb * tiles * 64 * sizeof(rl_v4i)));
-    if (nm) HIP_TRY(hipMalloc(&b.mdig, (size_t)nm * tiles * 64 * sizeof(rl_v4i)));
-    HIP_TRY(hipMalloc(&b.acc, (size_t)n * smax * 2 * sizeof(unsigned long long)));
+    if (b.scale.alloc((size_t)smax)) return 1;
+    if (b.maxbits.alloc((size_t)smax * 3)) return 1; // max, then the two halves of sum_j q_o
+    if (b.bad.alloc(1)) return 1;
+    if (b.mslot.alloc(nkb)) return 1;
+    if (b.wdig.alloc((size_t)nkb * tiles * 64)) return 1;
+    if (nm && b.mdig.alloc((size_t)nm * tiles * 64)) return 1;
+    if (b.acc.alloc((size_t)n * smax * 2)) return 1;
     HIP_TRY(hipMemsetAsync(b.bad, 0, sizeof(uint32_t), h->stream));
     HIP_TRY(hipMemcpyAsync(b.mslot, mslot.data(), (size_t)nkb * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream)); // (mslot is a local)
@@ -408,11 +398,9 @@ static int score_dev_run(hgibbs_ctx* h, ScoreWs& b, int S, const double* da, con
     // grid: workgroups of 256 individuals x ranges of marker blocks, enough of them to fill the device (8 per compute unit); the
     // ranges never exceed SC_KB_MAX blocks (i32 headroom of the digit sums)
     const uint32_t gx = h->n_pad / SC_IND;
-    uint32_t gy = std::max<uint32_t>(1u, std::min<uint32_t>(nkb, (8u * (uint32_t)h->num_cu + gx - 1u) / gx));
-    if (h->score_ranges) gy = std::min<uint32_t>(gy, (uint32_t)h->score_ranges);
-    gy = std::max(gy, (nkb + SC_KB_MAX - 1u) / SC_KB_MAX);
-    const uint32_t kb_per = (nkb + gy - 1u) / gy;
-    gy = (nkb + kb_per - 1u) / kb_per;
+    uint32_t want = (8u * (uint32_t)h->num_cu + gx - 1u) / gx, kb_per = 0;
+    if (h->score_ranges) want = std::min(want, (uint32_t)h->score_ranges);
+    const uint32_t gy = split_ranges(nkb, want, SC_KB_MAX, kb_per);
     for (uint32_t s0 = 0; s0 < (uint32_t)S; s0 += (uint32_t)sp) {
         k_score_digits<<<dim3(nkb, tiles), 64, 0, h->stream>>>(da, dov, M, (uint32_t)S, s0, tiles, b.scale, b.mslot, b.wdig, b.mdig);
         HIP_TRY(hipGetLastError());
@@ -432,8 +420,7 @@ static int score_dev_run(hgibbs_ctx* h, ScoreWs& b, int S, const double* da, con
 
 extern "C" int hgibbs_score(hgibbs_t h, int S, const double* a, const double* o, double* out)
 {
-    if (!h) return fail("hgibbs_score: null handle");
-    if (!h->bed) return fail("hgibbs_score: no genotypes loaded on this handle");
+    if (op_guard(h, "hgibbs_score", nullptr)) return 1;
     if (S <= 0) return fail("hgibbs_score: S = %d, needs at least one weight vector", S);
     if (!a || !o || !out) return fail("hgibbs_score: null argument");
     HIP_TRY(hipSetDevice(h->device));
@@ -441,35 +428,25 @@ extern "C" int hgibbs_score(hgibbs_t h, int S, const double* a, const double* o,
 
     // a thin wrapper around the device-pointer pipeline: its own workspace, the weights in, the results out
     ScoreWs ws;
-    struct Bufs {
-        double *a = nullptr, *o = nullptr, *out = nullptr;
-        ~Bufs()
-        {
-            void* p[] = {a, o, out};
-            for (void* x : p)
-                if (x) (void)hipFree(x);
-        }
-    } b;
+    DevBuf<double> da, dov, dout;
     const size_t SM = (size_t)S * M, NS = (size_t)n * S;
     if (score_ws_create(h, ws, S)) return 1;
-    HIP_TRY(hipMalloc(&b.a, SM * sizeof(double)));
-    HIP_TRY(hipMalloc(&b.o, SM * sizeof(double)));
-    HIP_TRY(hipMalloc(&b.out, NS * sizeof(double)));
-    HIP_TRY(hipMemcpyAsync(b.a, a, SM * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(b.o, o, SM * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (da.alloc(SM) || dov.alloc(SM) || dout.alloc(NS)) return 1;
+    HIP_TRY(hipMemcpyAsync(da, a, SM * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(dov, o, SM * sizeof(double), hipMemcpyHostToDevice, h->stream));
     if (score_dev_clear(h, ws, S)) return 1;
 
     // device time from here to the rounded result: every kernel of the call, not the host copies around it
-    HIP_TRY(hipEventRecord(h->ev0, h->stream));
-    if (score_dev_run(h, ws, S, b.a, b.o, b.out)) return 1;
-    HIP_TRY(hipEventRecord(h->ev1, h->stream));
+    if (lap_begin(h)) return 1;
+    if (score_dev_run(h, ws, S, da, dov, dout)) return 1;
+    if (lap_mark(h)) return 1;
     uint32_t bad = 0;
     HIP_TRY(hipMemcpyAsync(&bad, ws.bad, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (bad) return fail("hgibbs_score: a weight (a or o) is not finite"); // (out untouched; what the kernels made of it is dropped)
-    HIP_TRY(hipMemcpy(out, b.out, NS * sizeof(double), hipMemcpyDeviceToHost));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    HIP_TRY(hipMemcpy(out, dout, NS * sizeof(double), hipMemcpyDeviceToHost));
+    double ms = 0.0;
+    if (lap_read(h, ms)) return 1;
     h->score_ms = ms;
     return 0;
 }

@@ -2041,6 +2041,7 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
 } // extern "C"
 
 #include "hg_bayesw.hip.h"
+#include "hg_ops.hip.h"
 #include "hg_score.hip.h"
 #include "hg_ld.hip.h"
 #include "hg_mdots.hip.h"

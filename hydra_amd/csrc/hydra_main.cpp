@@ -49,12 +49,14 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <initializer_list>
 #include <iostream>
 #include <limits>
 #include <map>
 #include <sstream>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/hgibbs.h"
@@ -251,20 +253,86 @@ Options parse(int argc, const char* argv[])
     return o;
 }
 
-size_t count_fam(const std::string& path, std::vector<std::string>* ids)
+// ---- what every path of the CLI does with its files, once -------------------
+// an option's argument as an integer, resp. a number: false unless the whole argument is one
+bool whole_int(const std::string& t, long& v)
+{
+    const char* s = t.c_str();
+    char* end = nullptr;
+    v = std::strtol(s, &end, 10);
+    return end != s && *end == 0;
+}
+
+bool whole_num(const std::string& t, double& v)
+{
+    const char* s = t.c_str();
+    char* end = nullptr;
+    v = std::strtod(s, &end);
+    return end != s && *end == 0;
+}
+
+// FID and IID of the rows of a .fam, at most `limit` of them; with `keep`, only of the rows it marks
+struct FamIds {
+    std::vector<std::string> fid, iid;
+};
+
+FamIds read_fam_ids(const std::string& path, size_t limit, const std::vector<uint8_t>* keep)
 {
     std::ifstream in(path);
     if (!in) fatal("Error: can not open the file [" + path + "] to read.");
-    std::string fid, pid, dad, mom, sex, phen;
-    size_t n = 0;
+    FamIds ids;
+    std::string f, i, dad, mom, sex, phen;
+    for (size_t r = 0; r < limit && (in >> f >> i >> dad >> mom >> sex >> phen); ++r) // data.cpp:1454
+        if (!keep || (*keep)[r]) {
+            ids.fid.push_back(f);
+            ids.iid.push_back(i);
+        }
+    return ids;
+}
+
+// the genotypes of <prefix>.bed after its magic: M x ceil(numInds / 4) bytes
+std::vector<uint8_t> read_bed(const std::string& prefix, size_t numInds, size_t M)
+{
+    std::ifstream in(prefix + ".bed", std::ios::binary);
+    if (!in) fatal("Error: can not open the file [" + prefix + ".bed] to read.");
+    unsigned char magic[3];
+    in.read((char*)magic, 3);
+    if (!in || magic[0] != 0x6c || magic[1] != 0x1b || magic[2] != 0x01) fatal("FATAL  : " + prefix + ".bed is not a SNP-major PLINK bed");
+    std::vector<uint8_t> bed(M * ((numInds + 3) / 4));
+    in.read((char*)bed.data(), (std::streamsize)bed.size());
+    if ((size_t)in.gcount() != bed.size()) fatal("FATAL  : " + prefix + ".bed is shorter than M x ceil(N/4)");
+    return bed;
+}
+
+// --mcmc-out-dir, made when it is not there (the caller asks when an output goes to its default path)
+void make_out_dir(const Options& o)
+{
+    struct stat sb;
+    if (stat(o.mcmcOutDir.c_str(), &sb) != 0 && std::system(("mkdir -p " + o.mcmcOutDir).c_str()) != 0) fatal("FATAL  : can not create --mcmc-out-dir");
+}
+
+FILE* open_out(const std::string& p, const char* mode)
+{
+    FILE* f = std::fopen(p.c_str(), mode);
+    if (!f) fatal("FATAL  : can not create " + p);
+    return f;
+}
+
+void close_out(FILE* f, const std::string& p)
+{
+    if (std::fclose(f) != 0) fatal("FATAL  : short write on " + p);
+}
+
+size_t count_fam(const std::string& path, std::vector<std::string>* ids)
+{
+    const FamIds fam = read_fam_ids(path, (size_t)-1, nullptr);
     std::map<std::string, int> seen;
-    while (in >> fid >> pid >> dad >> mom >> sex >> phen) { // data.cpp:1454
-        const std::string id = fid + ":" + pid;
-        if (!seen.emplace(id, 1).second) fatal("Error: Duplicate individual ID found: \"" + fid + "\t" + pid + "\".");
+    for (size_t r = 0; r < fam.fid.size(); ++r) {
+        const std::string id = fam.fid[r] + ":" + fam.iid[r];
+        if (!seen.emplace(id, 1).second) fatal("Error: Duplicate individual ID found: \"" + fam.fid[r] + "\t" + fam.iid[r] + "\".");
         if (ids) ids->push_back(id);
-        ++n;
     }
-    return n;
+    return fam.fid.size();
 }
 
 size_t count_bim(const std::string& path)
@@ -677,9 +745,7 @@ int run_bayesw(const Options& opt_in, int rank, int nranks, int local_rank)
         opt.save = (opt.save / opt.thin) * opt.thin;
         std::printf("         opt.save reset to %d, the closest multiple of opt.thin (%d)\n", opt.save, opt.thin);
     }
-    struct stat sb;
-    if (stat(opt.mcmcOutDir.c_str(), &sb) != 0)
-        if (std::system(("mkdir -p " + opt.mcmcOutDir).c_str()) != 0) fatal("FATAL  : can not create --mcmc-out-dir");
+    make_out_dir(opt);
     const std::string base_in = opt.mcmcOutDir + "/" + opt.mcmcOutNam; // a restart reads <name>.*, writes <name>_rs.* (:994-1008)
     const std::string base = opt.restart ? base_in + "_rs" : base_in;
 
@@ -693,15 +759,7 @@ int run_bayesw(const Options& opt_in, int rank, int nranks, int local_rank)
     const unsigned per = ((Ntot + nranks - 1) / nranks + 3) / 4 * 4;
     const unsigned lo = std::min(Ntot, rank * per), hi = std::min(Ntot, (rank + 1) * per);
     {
-        std::vector<uint8_t> bed;
-        std::ifstream in(opt.bedFile + ".bed", std::ios::binary);
-        if (!in) fatal("Error: can not open the file [" + opt.bedFile + ".bed] to read.");
-        unsigned char magic[3];
-        in.read((char*)magic, 3);
-        if (!in || magic[0] != 0x6c || magic[1] != 0x1b || magic[2] != 0x01) fatal("FATAL  : " + opt.bedFile + ".bed is not a SNP-major PLINK bed");
-        bed.resize((size_t)Mtot * snpLenByt);
-        in.read((char*)bed.data(), (std::streamsize)bed.size());
-        if ((size_t)in.gcount() != bed.size()) fatal("FATAL  : " + opt.bedFile + ".bed is shorter than M x ceil(N/4)");
+        const std::vector<uint8_t> bed = read_bed(opt.bedFile, numInds, Mtot);
         hg_check(hgibbs_load_bed(dev, bed.data(), snpLenByt, (uint32_t)numInds, Mtot, numNAs ? keep.data() : nullptr, lo, hi, Ntot), "hgibbs_load_bed");
         std::printf("INFO   : rank %3d took %.3f seconds to load  %lu bytes  =>  BW = %7.3f GB/s\n", rank, now_s() - tl0, (unsigned long)bed.size(),
                     (double)bed.size() * 1e-9 / (now_s() - tl0));
@@ -807,11 +865,7 @@ int run_bayesw(const Options& opt_in, int rank, int nranks, int local_rank)
                     std::string(100, '*').c_str());
     }
 
-    auto open_trunc = [&](const std::string& p) {
-        FILE* f = std::fopen(p.c_str(), "wb+");
-        if (!f) fatal("FATAL  : can not create " + p);
-        return f;
-    };
+    auto open_trunc = [&](const std::string& p) { return open_out(p, "wb+"); };
     // the shared files are rank 0's (every rank holds the same chain); the others write theirs into the void
     auto open_shared = [&](const std::string& p) { return open_trunc(rank == 0 ? p : std::string("/dev/null")); };
     FILE* outf = open_shared(base + ".csv");
@@ -951,49 +1005,45 @@ void read_bet_records(const std::string& path, unsigned Mtot, unsigned burnin, s
         fatal("FATAL  : " + path + ": no record at or after --burn-in " + std::to_string(burnin) + " (" + std::to_string(total) + " records)");
 }
 
-// the training genotypes: M x ceil(numInds / 4) bytes of <bfile>.bed after its magic
-std::vector<uint8_t> read_training_bed(const Options& opt, unsigned numInds, unsigned Mtot)
+// The chain's cohort as every analysis mode takes it: the rows that kept their phenotype (and, with --covariates, every covariate)
+// of the first Mtot markers of --bfile
+struct Cohort {
+    const std::vector<uint8_t>& keep; // per .fam row
+    unsigned numInds, numNAs, Ntot;   // .fam rows, dropped rows, the chain's rows
+    unsigned Mtot;
+    int local_rank;
+};
+
+// A handle on the chain's rows, as one shard, from the training genotypes (read_bed of --bfile); the host copy is released
+hgibbs_t open_training(const Cohort& co, std::vector<uint8_t>& bed)
 {
-    const size_t len = (numInds + 3) / 4;
-    std::vector<uint8_t> bed((size_t)Mtot * len);
-    std::ifstream in(opt.bedFile + ".bed", std::ios::binary);
-    if (!in) fatal("Error: can not open the file [" + opt.bedFile + ".bed] to read.");
-    unsigned char magic[3];
-    in.read((char*)magic, 3);
-    if (!in || magic[0] != 0x6c || magic[1] != 0x1b || magic[2] != 0x01) fatal("FATAL  : " + opt.bedFile + ".bed is not a SNP-major PLINK bed");
-    in.read((char*)bed.data(), (std::streamsize)bed.size());
-    if ((size_t)in.gcount() != bed.size()) fatal("FATAL  : " + opt.bedFile + ".bed is shorter than M x ceil(N/4)");
-    return bed;
+    hgibbs_t dev = nullptr;
+    hg_check(hgibbs_create(co.local_rank, &dev), "hgibbs_create");
+    hg_check(hgibbs_load_bed(dev, bed.data(), (co.numInds + 3) / 4, co.numInds, co.Mtot, co.numNAs ? co.keep.data() : nullptr, 0, co.Ntot, co.Ntot),
+             "hgibbs_load_bed");
+    std::vector<uint8_t>().swap(bed);
+    return dev;
 }
 
-int run_predict(const Options& opt, const std::vector<uint8_t>& keep, unsigned numInds, unsigned numNAs, unsigned Mtot, int local_rank)
+int run_predict(const Options& opt, const Cohort& co)
 {
     const std::string base = opt.mcmcOutDir + "/" + opt.mcmcOutNam;
     const std::string out = opt.predictOut.empty() ? base + ".prs" : opt.predictOut;
-    const BimRows tr = read_bim(opt.bedFile + ".bim", Mtot);
+    const BimRows tr = read_bim(opt.bedFile + ".bim", co.Mtot);
     std::vector<unsigned> its;
     std::vector<double> betas;
-    read_bet_records(base + ".bet", Mtot, opt.burnin, its, betas);
+    read_bet_records(base + ".bet", co.Mtot, opt.burnin, its, betas);
     const size_t S = its.size();
 
     // target cohort: .fam (every row: the target needs no phenotype), .bim matched to the training markers by id
     const std::string tp = opt.predictBfile;
-    std::vector<std::string> fid, iid;
-    {
-        std::ifstream in(tp + ".fam");
-        if (!in) fatal("Error: can not open the file [" + tp + ".fam] to read.");
-        std::string f, i, dad, mom, sex, phen;
-        while (in >> f >> i >> dad >> mom >> sex >> phen) {
-            fid.push_back(f);
-            iid.push_back(i);
-        }
-    }
-    const size_t nT = fid.size();
+    const FamIds tfam = read_fam_ids(tp + ".fam", (size_t)-1, nullptr);
+    const size_t nT = tfam.fid.size();
     if (nT == 0) fatal("FATAL  : " + tp + ".fam lists no individual");
     const BimRows tg = read_bim(tp + ".bim", (size_t)-1);
     const size_t Mt = tg.id.size();
     std::map<std::string, unsigned> train_idx;
-    for (unsigned j = 0; j < Mtot; ++j)
+    for (unsigned j = 0; j < co.Mtot; ++j)
         if (!train_idx.emplace(tr.id[j], j).second) fatal("FATAL  : the training .bim lists SNP id " + tr.id[j] + " twice: markers are matched by id");
     std::map<std::string, int> seen;
     std::vector<int> match(Mt, -1); // training marker of each target column, -1 = contributes nothing
@@ -1019,7 +1069,7 @@ int run_predict(const Options& opt, const std::vector<uint8_t>& keep, unsigned n
     }
     std::printf("PREDICT: %zu target markers: %zu matched (%zu same alleles, %zu swapped), %zu allele mismatch, %zu not in training; "
                 "%zu of %u training markers unused\n",
-                Mt, same + swapped, same, swapped, allele, absent, (size_t)Mtot - same - swapped, Mtot);
+                Mt, same + swapped, same, swapped, allele, absent, (size_t)co.Mtot - same - swapped, co.Mtot);
     std::printf("PREDICT: %zu records of %s (iterations %u .. %u), %zu target individuals -> %s\n", S, (base + ".bet").c_str(), its.front(),
                 its.back(), nT, out.c_str());
     std::fflush(stdout);
@@ -1027,36 +1077,23 @@ int run_predict(const Options& opt, const std::vector<uint8_t>& keep, unsigned n
 
     // target genotypes, read before the device opens
     const size_t lenT = (nT + 3) / 4;
-    std::vector<uint8_t> bedT((size_t)Mt * lenT);
-    {
-        std::ifstream in(tp + ".bed", std::ios::binary);
-        if (!in) fatal("Error: can not open the file [" + tp + ".bed] to read.");
-        unsigned char magic[3];
-        in.read((char*)magic, 3);
-        if (!in || magic[0] != 0x6c || magic[1] != 0x1b || magic[2] != 0x01) fatal("FATAL  : " + tp + ".bed is not a SNP-major PLINK bed");
-        in.read((char*)bedT.data(), (std::streamsize)bedT.size());
-        if ((size_t)in.gcount() != bedT.size()) fatal("FATAL  : " + tp + ".bed is shorter than M x ceil(N/4)");
-    }
+    std::vector<uint8_t> bedT = read_bed(tp, nT, Mt);
     if (opt.predictDryRun) {
         std::printf("PREDICT: dry run: inputs checked, nothing scored\n");
         return 0;
     }
 
     // the chain's standardisation: mave, mstd of the training markers over the rows that kept their phenotype
-    std::vector<double> mave(Mtot), mstd(Mtot);
+    std::vector<double> mave(co.Mtot), mstd(co.Mtot);
     {
-        const size_t len = (numInds + 3) / 4;
-        std::vector<uint8_t> bed = read_training_bed(opt, numInds, Mtot);
-        const unsigned Ntot = numInds - numNAs;
-        hgibbs_t dev = nullptr;
-        hg_check(hgibbs_create(local_rank, &dev), "hgibbs_create");
-        hg_check(hgibbs_load_bed(dev, bed.data(), len, numInds, Mtot, numNAs ? keep.data() : nullptr, 0, Ntot, Ntot), "hgibbs_load_bed");
+        std::vector<uint8_t> bed = read_bed(opt.bedFile, co.numInds, co.Mtot);
+        hgibbs_t dev = open_training(co, bed);
         hg_check(hgibbs_marker_stats(dev, mave.data(), mstd.data(), nullptr, nullptr, nullptr), "hgibbs_marker_stats");
         hgibbs_destroy(dev);
     }
 
     hgibbs_t dev = nullptr;
-    hg_check(hgibbs_create(local_rank, &dev), "hgibbs_create");
+    hg_check(hgibbs_create(co.local_rank, &dev), "hgibbs_create");
     hg_check(hgibbs_load_bed(dev, bedT.data(), lenT, (uint32_t)nT, (uint32_t)Mt, nullptr, 0, (uint32_t)nT, (uint32_t)std::max<size_t>(nT, 2)),
              "hgibbs_load_bed (target)");
     std::vector<uint8_t>().swap(bedT);
@@ -1068,7 +1105,7 @@ int run_predict(const Options& opt, const std::vector<uint8_t>& keep, unsigned n
         a.assign(sc * Mt, 0.0);
         o.assign(sc * Mt, 0.0);
         for (size_t s = 0; s < sc; ++s) {
-            const double* b = betas.data() + (s0 + s) * Mtot;
+            const double* b = betas.data() + (s0 + s) * co.Mtot;
             for (size_t t = 0; t < Mt; ++t) {
                 if (match[t] < 0) continue;
                 const unsigned j = (unsigned)match[t];
@@ -1084,8 +1121,7 @@ int run_predict(const Options& opt, const std::vector<uint8_t>& keep, unsigned n
     }
     hgibbs_destroy(dev);
 
-    FILE* f = std::fopen(out.c_str(), "w");
-    if (!f) fatal("FATAL  : can not create " + out);
+    FILE* f = open_out(out, "w");
     std::fprintf(f, "FID IID mean sd\n");
     for (size_t i = 0; i < nT; ++i) {
         double m = 0.0;
@@ -1094,24 +1130,23 @@ int run_predict(const Options& opt, const std::vector<uint8_t>& keep, unsigned n
         double v = 0.0;
         for (size_t s = 0; s < S; ++s) v += (score[i * S + s] - m) * (score[i * S + s] - m);
         const double sd = S > 1 ? std::sqrt(v / (double)(S - 1)) : 0.0;
-        std::fprintf(f, "%s %s %.17g %.17g\n", fid[i].c_str(), iid[i].c_str(), m, sd);
+        std::fprintf(f, "%s %s %.17g %.17g\n", tfam.fid[i].c_str(), tfam.iid[i].c_str(), m, sd);
     }
-    if (std::fclose(f) != 0) fatal("FATAL  : short write on " + out);
-    f = std::fopen((out + ".bin").c_str(), "wb");
-    if (!f) fatal("FATAL  : can not create " + out + ".bin");
+    close_out(f, out);
+    f = open_out(out + ".bin", "wb");
     const uint32_t hdr[2] = {(uint32_t)nT, (uint32_t)S};
     pwrite_at(f, 0, hdr, sizeof hdr);
     pwrite_at(f, sizeof hdr, score.data(), score.size() * sizeof(double));
-    if (std::fclose(f) != 0) fatal("FATAL  : short write on " + out + ".bin");
+    close_out(f, out + ".bin");
     std::printf("PREDICT: wrote %s and %s.bin\n", out.c_str(), out.c_str());
     return 0;
 }
 
 // ---- --ld-window: windowed LD of the training markers on the chain's rows ----
-int run_ld(const Options& opt, const std::vector<uint8_t>& keep, unsigned numInds, unsigned numNAs, unsigned Mtot, int local_rank)
+int run_ld(const Options& opt, const Cohort& co)
 {
     const std::string out = opt.ldOut.empty() ? opt.mcmcOutDir + "/" + opt.mcmcOutNam + ".ld" : opt.ldOut;
-    const BimRows bim = read_bim(opt.bedFile + ".bim", Mtot);
+    const BimRows bim = read_bim(opt.bedFile + ".bim", co.Mtot);
     const uint32_t W = (uint32_t)opt.ldWindow;
     const long long maxbp = opt.ldKbGiven ? (long long)std::llround(1000.0 * opt.ldWindowKb) : -1;
     // a pair (j, q) is kept when 0 < q - j <= W in .bim order, on one chromosome and, with --ld-window-kb, within 1000 KB bp
@@ -1120,37 +1155,28 @@ int run_ld(const Options& opt, const std::vector<uint8_t>& keep, unsigned numInd
     };
     std::map<std::string, int> chroms;
     unsigned long long npairs = 0;
-    for (unsigned j = 0; j < Mtot; ++j) {
+    for (unsigned j = 0; j < co.Mtot; ++j) {
         chroms.emplace(bim.chr[j], 1);
-        for (unsigned q = j + 1; q < Mtot && q - j <= W; ++q) npairs += kept(j, q) ? 1u : 0u;
+        for (unsigned q = j + 1; q < co.Mtot && q - j <= W; ++q) npairs += kept(j, q) ? 1u : 0u;
     }
-    std::printf("LD     : %u markers, window %u markers%s, %zu chromosomes, %llu pairs in the window; r^2 >= %g -> %s%s\n", Mtot, W,
+    std::printf("LD     : %u markers, window %u markers%s, %zu chromosomes, %llu pairs in the window; r^2 >= %g -> %s%s\n", co.Mtot, W,
                 maxbp >= 0 ? (" and " + std::to_string(maxbp) + " bp").c_str() : "", chroms.size(), npairs, opt.ldWindowR2, out.c_str(),
                 opt.ldBin ? (" and " + out + ".bin").c_str() : "");
     std::fflush(stdout);
 
-    const size_t len = (numInds + 3) / 4;
-    std::vector<uint8_t> bed = read_training_bed(opt, numInds, Mtot);
-    struct stat sb;
-    if (opt.ldOut.empty() && stat(opt.mcmcOutDir.c_str(), &sb) != 0)
-        if (std::system(("mkdir -p " + opt.mcmcOutDir).c_str()) != 0) fatal("FATAL  : can not create --mcmc-out-dir");
-    FILE* f = std::fopen(out.c_str(), "w");
-    if (!f) fatal("FATAL  : can not create " + out);
+    std::vector<uint8_t> bed = read_bed(opt.bedFile, co.numInds, co.Mtot);
+    if (opt.ldOut.empty()) make_out_dir(opt);
+    FILE* f = open_out(out, "w");
     FILE* fb = nullptr;
     if (opt.ldBin) {
-        fb = std::fopen((out + ".bin").c_str(), "wb");
-        if (!fb) fatal("FATAL  : can not create " + out + ".bin");
-        const uint32_t hdr[2] = {Mtot, W};
+        fb = open_out(out + ".bin", "wb");
+        const uint32_t hdr[2] = {co.Mtot, W};
         if (std::fwrite(hdr, sizeof hdr, 1, fb) != 1) fatal("FATAL  : short write on " + out + ".bin");
     }
     std::fprintf(f, "CHR_A BP_A SNP_A CHR_B BP_B SNP_B R\n");
 
-    // the chain's rows (NA phenotype, and NA covariate rows with --covariates, dropped) and its standardisation
-    const unsigned Ntot = numInds - numNAs;
-    hgibbs_t dev = nullptr;
-    hg_check(hgibbs_create(local_rank, &dev), "hgibbs_create");
-    hg_check(hgibbs_load_bed(dev, bed.data(), len, numInds, Mtot, numNAs ? keep.data() : nullptr, 0, Ntot, Ntot), "hgibbs_load_bed");
-    std::vector<uint8_t>().swap(bed);
+    // the chain's rows and its standardisation
+    hgibbs_t dev = open_training(co, bed);
     hg_check(hgibbs_marker_stats(dev, nullptr, nullptr, nullptr, nullptr, nullptr), "hgibbs_marker_stats");
 
     // chunks of markers: host memory stays at about 2^22 pairs
@@ -1159,8 +1185,8 @@ int run_ld(const Options& opt, const std::vector<uint8_t>& keep, unsigned numInd
     std::vector<float> rf;
     unsigned long long written = 0;
     double ms = 0.0;
-    for (unsigned m0 = 0; m0 < Mtot; m0 += chunk) {
-        const unsigned cnt = std::min(chunk, Mtot - m0);
+    for (unsigned m0 = 0; m0 < co.Mtot; m0 += chunk) {
+        const unsigned cnt = std::min(chunk, co.Mtot - m0);
         r.resize((size_t)cnt * W);
         hg_check(hgibbs_ld(dev, m0, cnt, W, r.data(), nullptr), "hgibbs_ld");
         double t = 0.0;
@@ -1169,7 +1195,7 @@ int run_ld(const Options& opt, const std::vector<uint8_t>& keep, unsigned numInd
         if (fb) rf.assign((size_t)cnt * W, std::numeric_limits<float>::quiet_NaN());
         for (unsigned jj = 0; jj < cnt; ++jj) {
             const unsigned j = m0 + jj;
-            for (unsigned d = 1; d <= W && j + d < Mtot; ++d) {
+            for (unsigned d = 1; d <= W && j + d < co.Mtot; ++d) {
                 const unsigned q = j + d;
                 const double v = r[(size_t)jj * W + d - 1];
                 if (std::isnan(v) || !kept(j, q)) continue;
@@ -1183,8 +1209,8 @@ int run_ld(const Options& opt, const std::vector<uint8_t>& keep, unsigned numInd
         if (fb && std::fwrite(rf.data(), sizeof(float), rf.size(), fb) != rf.size()) fatal("FATAL  : short write on " + out + ".bin");
     }
     hgibbs_destroy(dev);
-    if (std::fclose(f) != 0) fatal("FATAL  : short write on " + out);
-    if (fb && std::fclose(fb) != 0) fatal("FATAL  : short write on " + out + ".bin");
+    close_out(f, out);
+    if (fb) close_out(fb, out + ".bin");
     std::printf("LD     : wrote %llu pairs with r^2 >= %g to %s (%.3f ms on the device)\n", written, opt.ldWindowR2, out.c_str(), ms);
     return 0;
 }
@@ -1223,30 +1249,29 @@ std::vector<double> chol_solve(const std::vector<double>& L, int q, std::vector<
     return b;
 }
 
-int run_assoc(const Options& opt, const std::vector<uint8_t>& keep, const std::vector<double>& y_raw, const std::vector<double>& covX, int C,
-              unsigned numInds, unsigned numNAs, unsigned Mtot, int local_rank)
+int run_assoc(const Options& opt, const Cohort& co, const std::vector<double>& y_raw, const std::vector<double>& covX, int C)
 {
     const std::string base = opt.mcmcOutDir + "/" + opt.mcmcOutNam;
     const std::string out = opt.assocOut.empty() ? base + ".assoc" : opt.assocOut;
     const bool loco = !opt.assocNoLoco;
-    const BimRows bim = read_bim(opt.bedFile + ".bim", Mtot);
-    const unsigned N = numInds - numNAs;
+    const BimRows bim = read_bim(opt.bedFile + ".bim", co.Mtot);
+    const unsigned N = co.Ntot;
     const int q = 1 + C;
 
     // maximal runs of equal chromosome in .bim order (an unsorted .bim works); chromosome c(j) as an index
     std::map<std::string, int> chrom_idx;
-    std::vector<int> cj(Mtot);
+    std::vector<int> cj(co.Mtot);
     std::vector<unsigned> runs; // first marker of each run, then Mtot
-    for (unsigned j = 0; j < Mtot; ++j) {
+    for (unsigned j = 0; j < co.Mtot; ++j) {
         cj[j] = chrom_idx.emplace(bim.chr[j], (int)chrom_idx.size()).first->second;
         if (j == 0 || bim.chr[j] != bim.chr[j - 1]) runs.push_back(j);
     }
     const size_t nruns = runs.size(), nchrom = chrom_idx.size();
-    runs.push_back(Mtot);
+    runs.push_back(co.Mtot);
     std::vector<unsigned> its;
     std::vector<double> betas;
-    if (loco) read_bet_records(base + ".bet", Mtot, opt.burnin, its, betas, "--assoc takes its LOCO offsets from the chain's effects");
-    std::printf("ASSOC  : %u markers, %zu chromosomes in %zu runs, %d covariates, %u individuals -> %s\n", Mtot, nchrom, nruns, C, N, out.c_str());
+    if (loco) read_bet_records(base + ".bet", co.Mtot, opt.burnin, its, betas, "--assoc takes its LOCO offsets from the chain's effects");
+    std::printf("ASSOC  : %u markers, %zu chromosomes in %zu runs, %d covariates, %u individuals -> %s\n", co.Mtot, nchrom, nruns, C, N, out.c_str());
     if (loco)
         std::printf("ASSOC  : LOCO offsets from %zu records of %s (iterations %u .. %u)\n", its.size(), (base + ".bet").c_str(), its.front(), its.back());
     else
@@ -1289,22 +1314,15 @@ int run_assoc(const Options& opt, const std::vector<uint8_t>& keep, const std::v
             for (unsigned i = 0; i < N; ++i) v[i] -= Z[(size_t)a * N + i] * w[a];
     };
 
-    const size_t len = (numInds + 3) / 4;
-    std::vector<uint8_t> bed = read_training_bed(opt, numInds, Mtot);
-    struct stat sb;
-    if (opt.assocOut.empty() && stat(opt.mcmcOutDir.c_str(), &sb) != 0)
-        if (std::system(("mkdir -p " + opt.mcmcOutDir).c_str()) != 0) fatal("FATAL  : can not create --mcmc-out-dir");
-    FILE* f = std::fopen(out.c_str(), "w");
-    if (!f) fatal("FATAL  : can not create " + out);
+    std::vector<uint8_t> bed = read_bed(opt.bedFile, co.numInds, co.Mtot);
+    if (opt.assocOut.empty()) make_out_dir(opt);
+    FILE* f = open_out(out, "w");
     std::fprintf(f, "CHR SNP BP A1 A2 FREQ N BETA SE CHISQ P\n");
 
     // the chain's rows and standardisation
-    hgibbs_t dev = nullptr;
-    hg_check(hgibbs_create(local_rank, &dev), "hgibbs_create");
-    hg_check(hgibbs_load_bed(dev, bed.data(), len, numInds, Mtot, numNAs ? keep.data() : nullptr, 0, N, N), "hgibbs_load_bed");
-    std::vector<uint8_t>().swap(bed);
-    std::vector<double> mave(Mtot), mstd(Mtot);
-    std::vector<uint64_t> n1(Mtot), n2(Mtot), nmiss(Mtot);
+    hgibbs_t dev = open_training(co, bed);
+    std::vector<double> mave(co.Mtot), mstd(co.Mtot);
+    std::vector<uint64_t> n1(co.Mtot), n2(co.Mtot), nmiss(co.Mtot);
     hg_check(hgibbs_marker_stats(dev, mave.data(), mstd.data(), n1.data(), n2.data(), nmiss.data()), "hgibbs_marker_stats");
     double ms = 0.0;
 
@@ -1312,15 +1330,15 @@ int run_assoc(const Options& opt, const std::vector<uint8_t>& keep, const std::v
     std::vector<std::vector<double>> r(loco ? nchrom : 1, y);
     if (loco) {
         const size_t S = its.size();
-        std::vector<double> bbar(Mtot, 0.0);
+        std::vector<double> bbar(co.Mtot, 0.0);
         for (size_t s = 0; s < S; ++s)
-            for (unsigned j = 0; j < Mtot; ++j) bbar[j] += betas[s * Mtot + j];
-        for (unsigned j = 0; j < Mtot; ++j) bbar[j] /= (double)S;
-        std::vector<double> a(nchrom * Mtot, 0.0), o(nchrom * Mtot, 0.0), Gc((size_t)N * nchrom);
-        for (unsigned j = 0; j < Mtot; ++j) {
+            for (unsigned j = 0; j < co.Mtot; ++j) bbar[j] += betas[s * co.Mtot + j];
+        for (unsigned j = 0; j < co.Mtot; ++j) bbar[j] /= (double)S;
+        std::vector<double> a(nchrom * co.Mtot, 0.0), o(nchrom * co.Mtot, 0.0), Gc((size_t)N * nchrom);
+        for (unsigned j = 0; j < co.Mtot; ++j) {
             if (!std::isfinite(mstd[j])) continue; // (score refuses non-finite weights; x = 0 there anyway)
-            a[(size_t)cj[j] * Mtot + j] = bbar[j] * mstd[j];
-            o[(size_t)cj[j] * Mtot + j] = -bbar[j] * mstd[j] * mave[j];
+            a[(size_t)cj[j] * co.Mtot + j] = bbar[j] * mstd[j];
+            o[(size_t)cj[j] * co.Mtot + j] = -bbar[j] * mstd[j] * mave[j];
         }
         hg_check(hgibbs_score(dev, (int)nchrom, a.data(), o.data(), Gc.data()), "hgibbs_score");
         double t = 0.0;
@@ -1378,52 +1396,27 @@ int run_assoc(const Options& opt, const std::vector<uint8_t>& keep, const std::v
         }
     }
     hgibbs_destroy(dev);
-    if (std::fclose(f) != 0) fatal("FATAL  : short write on " + out);
+    close_out(f, out);
     std::printf("ASSOC  : wrote %llu rows to %s (%.3f ms on the device)\n", written, out.c_str(), ms);
     return 0;
 }
 
 // ---- --king: KING-robust kinship of the chain's rows ----
-// --king-cutoff as a number: NaN unless the whole argument is one
-double king_cutoff(const Options& opt)
-{
-    const char* s = opt.kingCutoff.c_str();
-    char* end = nullptr;
-    const double v = std::strtod(s, &end);
-    return (end != s && *end == 0) ? v : std::numeric_limits<double>::quiet_NaN();
-}
-
-int run_king(const Options& opt, const std::vector<uint8_t>& keep, unsigned numInds, unsigned numNAs, unsigned Mtot, int local_rank)
+int run_king(const Options& opt, const Cohort& co)
 {
     const std::string out = opt.kingOut.empty() ? opt.mcmcOutDir + "/" + opt.mcmcOutNam + ".kin0" : opt.kingOut;
-    const double cutoff = king_cutoff(opt);
-    // FID and IID of the chain's rows (NA phenotype, and NA covariate rows with --covariates, dropped), in .fam order
-    std::vector<std::string> fid, iid;
-    {
-        std::ifstream in(opt.bedFile + ".fam");
-        if (!in) fatal("Error: can not open the file [" + opt.bedFile + ".fam] to read.");
-        std::string f, i, dad, mom, sex, phen;
-        for (unsigned r = 0; r < numInds && (in >> f >> i >> dad >> mom >> sex >> phen); ++r)
-            if (!numNAs || keep[r]) {
-                fid.push_back(f);
-                iid.push_back(i);
-            }
-    }
-    const unsigned Ntot = numInds - numNAs;
-    if (fid.size() != Ntot) fatal("FATAL  : " + opt.bedFile + ".fam: " + std::to_string(fid.size()) + " kept rows, expected " + std::to_string(Ntot));
-    const size_t len = (numInds + 3) / 4;
-    std::vector<uint8_t> bed = read_training_bed(opt, numInds, Mtot);
-    struct stat sb;
-    if (opt.kingOut.empty() && stat(opt.mcmcOutDir.c_str(), &sb) != 0)
-        if (std::system(("mkdir -p " + opt.mcmcOutDir).c_str()) != 0) fatal("FATAL  : can not create --mcmc-out-dir");
-    FILE* f = std::fopen(out.c_str(), "w");
-    if (!f) fatal("FATAL  : can not create " + out);
+    double cutoff = 0.0;
+    whole_num(opt.kingCutoff, cutoff);
+    // FID and IID of the chain's rows, in .fam order
+    const FamIds fam = read_fam_ids(opt.bedFile + ".fam", co.numInds, co.numNAs ? &co.keep : nullptr);
+    const unsigned Ntot = co.Ntot;
+    if (fam.fid.size() != Ntot) fatal("FATAL  : " + opt.bedFile + ".fam: " + std::to_string(fam.fid.size()) + " kept rows, expected " + std::to_string(Ntot));
+    std::vector<uint8_t> bed = read_bed(opt.bedFile, co.numInds, co.Mtot);
+    if (opt.kingOut.empty()) make_out_dir(opt);
+    FILE* f = open_out(out, "w");
     std::fprintf(f, "#FID1\tIID1\tFID2\tIID2\tNSNP\tHETHET\tIBS0\tKINSHIP\n");
 
-    hgibbs_t dev = nullptr;
-    hg_check(hgibbs_create(local_rank, &dev), "hgibbs_create");
-    hg_check(hgibbs_load_bed(dev, bed.data(), len, numInds, Mtot, numNAs ? keep.data() : nullptr, 0, Ntot, Ntot), "hgibbs_load_bed");
-    std::vector<uint8_t>().swap(bed);
+    hgibbs_t dev = open_training(co, bed);
     uint64_t np = 0;
     hg_check(hgibbs_king_pairs(dev, cutoff, &np), "hgibbs_king_pairs");
     std::vector<uint32_t> ab(2 * np);
@@ -1437,36 +1430,19 @@ int run_king(const Options& opt, const std::vector<uint8_t>& keep, unsigned numI
     for (uint64_t p = 0; p < np; ++p) {
         const uint32_t a = ab[2 * p], b = ab[2 * p + 1];
         const int32_t* k = &cnt[5 * p];
-        std::fprintf(f, "%s\t%s\t%s\t%s\t%d\t%.12g\t%.12g\t%.12g\n", fid[a].c_str(), iid[a].c_str(), fid[b].c_str(), iid[b].c_str(), k[0],
+        std::fprintf(f, "%s\t%s\t%s\t%s\t%d\t%.12g\t%.12g\t%.12g\n", fam.fid[a].c_str(), fam.iid[a].c_str(), fam.fid[b].c_str(), fam.iid[b].c_str(), k[0],
                      (double)k[3] / (double)k[0], (double)k[4] / (double)k[0], kin[p]);
     }
-    if (std::fclose(f) != 0) fatal("FATAL  : short write on " + out);
+    close_out(f, out);
     std::printf("KING   : %llu pairs tested, %llu with KINSHIP >= %g written to %s (%.3f ms on the device)\n",
                 (unsigned long long)Ntot * (Ntot - 1ull) / 2ull, (unsigned long long)np, cutoff, out.c_str(), ms);
     return 0;
 }
 
 // ---- --pca: principal components of the chain's rows ----
-// an option's argument as an integer, resp. a number: false unless the whole argument is one
-bool whole_int(const std::string& t, long& v)
-{
-    const char* s = t.c_str();
-    char* end = nullptr;
-    v = std::strtol(s, &end, 10);
-    return end != s && *end == 0;
-}
-
-bool whole_num(const std::string& t, double& v)
-{
-    const char* s = t.c_str();
-    char* end = nullptr;
-    v = std::strtod(s, &end);
-    return end != s && *end == 0;
-}
-
 constexpr int PCA_KMAX = 24; // the panel is the smallest multiple of 8 that is >= K + 8, at most 32 vectors
 
-int run_pca(const Options& opt, const std::vector<uint8_t>& keep, unsigned numInds, unsigned numNAs, unsigned Mtot, int local_rank)
+int run_pca(const Options& opt, const Cohort& co)
 {
     long K = 0, iters = 20;
     double tol = 1e-10;
@@ -1477,37 +1453,21 @@ int run_pca(const Options& opt, const std::vector<uint8_t>& keep, unsigned numIn
     // <out>: --pca-out without its .eigenvec, else <dir>/<name>
     std::string vec = opt.pcaOut.empty() ? opt.mcmcOutDir + "/" + opt.mcmcOutNam + ".eigenvec" : opt.pcaOut, pre = vec;
     if (pre.size() > 9 && pre.compare(pre.size() - 9, 9, ".eigenvec") == 0) pre.resize(pre.size() - 9);
-    // FID and IID of every .fam row; the chain's rows (NA phenotype, and NA covariate rows with --covariates, dropped) are the kept ones
-    std::vector<std::string> fid, iid;
-    {
-        std::ifstream in(opt.bedFile + ".fam");
-        if (!in) fatal("Error: can not open the file [" + opt.bedFile + ".fam] to read.");
-        std::string f, i, dad, mom, sex, phen;
-        for (unsigned r = 0; r < numInds && (in >> f >> i >> dad >> mom >> sex >> phen); ++r) {
-            fid.push_back(f);
-            iid.push_back(i);
-        }
-    }
-    if (fid.size() != numInds) fatal("FATAL  : " + opt.bedFile + ".fam: " + std::to_string(fid.size()) + " rows, expected " + std::to_string(numInds));
-    const unsigned Ntot = numInds - numNAs;
-    const size_t len = (numInds + 3) / 4;
-    std::vector<uint8_t> bed = read_training_bed(opt, numInds, Mtot);
-    struct stat sb;
-    if (opt.pcaOut.empty() && stat(opt.mcmcOutDir.c_str(), &sb) != 0)
-        if (std::system(("mkdir -p " + opt.mcmcOutDir).c_str()) != 0) fatal("FATAL  : can not create --mcmc-out-dir");
-    FILE* f = std::fopen(vec.c_str(), "w");
-    if (!f) fatal("FATAL  : can not create " + vec);
+    // FID and IID of every .fam row; the chain's rows are the kept ones
+    const FamIds fam = read_fam_ids(opt.bedFile + ".fam", co.numInds, nullptr);
+    if (fam.fid.size() != co.numInds) fatal("FATAL  : " + opt.bedFile + ".fam: " + std::to_string(fam.fid.size()) + " rows, expected " + std::to_string(co.numInds));
+    const unsigned Ntot = co.Ntot;
+    std::vector<uint8_t> bed = read_bed(opt.bedFile, co.numInds, co.Mtot);
+    if (opt.pcaOut.empty()) make_out_dir(opt);
+    FILE* f = open_out(vec, "w");
     std::fprintf(f, "#FID\tIID");
     for (long k = 0; k < K; ++k) std::fprintf(f, "\tPC%ld", k + 1);
     std::fprintf(f, "\n");
     std::fflush(f);
     std::printf("PCA    : %ld components, panel of %d vectors, at most %ld iterations, tolerance %g, seed %u\n", K, L, iters, tol, opt.seed);
 
-    hgibbs_t dev = nullptr;
-    hg_check(hgibbs_create(local_rank, &dev), "hgibbs_create");
-    hg_check(hgibbs_load_bed(dev, bed.data(), len, numInds, Mtot, numNAs ? keep.data() : nullptr, 0, Ntot, Ntot), "hgibbs_load_bed");
-    std::vector<uint8_t>().swap(bed);
-    std::vector<double> eigval(K), pcs((size_t)K * Ntot), load(opt.pcaLoadings ? (size_t)K * Mtot : 0);
+    hgibbs_t dev = open_training(co, bed);
+    std::vector<double> eigval(K), pcs((size_t)K * Ntot), load(opt.pcaLoadings ? (size_t)K * co.Mtot : 0);
     hgibbs_pca_report rep;
     hg_check(hgibbs_pca(dev, (int)K, L, (int)iters, tol, nullptr, (uint64_t)opt.seed, eigval.data(), pcs.data(), opt.pcaLoadings ? load.data() : nullptr, &rep),
              "hgibbs_pca");
@@ -1515,13 +1475,12 @@ int run_pca(const Options& opt, const std::vector<uint8_t>& keep, unsigned numIn
     hg_check(hgibbs_last_pca_ms(dev, ms), "hgibbs_last_pca_ms");
     hgibbs_destroy(dev);
 
-    FILE* c = std::fopen((pre + ".cov").c_str(), "w");
-    if (!c) fatal("FATAL  : can not create " + pre + ".cov");
+    FILE* c = open_out(pre + ".cov", "w");
     unsigned at = 0;
-    for (unsigned r = 0; r < numInds; ++r) {
-        const bool kept = !numNAs || keep[r];
-        std::fprintf(c, "%s %s", fid[r].c_str(), iid[r].c_str());
-        if (kept) std::fprintf(f, "%s\t%s", fid[r].c_str(), iid[r].c_str());
+    for (unsigned r = 0; r < co.numInds; ++r) {
+        const bool kept = !co.numNAs || co.keep[r];
+        std::fprintf(c, "%s %s", fam.fid[r].c_str(), fam.iid[r].c_str());
+        if (kept) std::fprintf(f, "%s\t%s", fam.fid[r].c_str(), fam.iid[r].c_str());
         for (long k = 0; k < K; ++k) {
             if (kept) {
                 std::fprintf(f, "\t%.12g", pcs[(size_t)k * Ntot + at]);
@@ -1535,35 +1494,112 @@ int run_pca(const Options& opt, const std::vector<uint8_t>& keep, unsigned numIn
             ++at;
         }
     }
-    if (std::fclose(f) != 0) fatal("FATAL  : short write on " + vec);
-    if (std::fclose(c) != 0) fatal("FATAL  : short write on " + pre + ".cov");
-    FILE* v = std::fopen((pre + ".eigenval").c_str(), "w");
-    if (!v) fatal("FATAL  : can not create " + pre + ".eigenval");
+    close_out(f, vec);
+    close_out(c, pre + ".cov");
+    FILE* v = open_out(pre + ".eigenval", "w");
     for (long k = 0; k < K; ++k) std::fprintf(v, "%.12g\n", eigval[k]);
-    if (std::fclose(v) != 0) fatal("FATAL  : short write on " + pre + ".eigenval");
+    close_out(v, pre + ".eigenval");
     if (opt.pcaLoadings) {
-        const BimRows bim = read_bim(opt.bedFile + ".bim", Mtot);
-        FILE* w = std::fopen((pre + ".var").c_str(), "w");
-        if (!w) fatal("FATAL  : can not create " + pre + ".var");
+        const BimRows bim = read_bim(opt.bedFile + ".bim", co.Mtot);
+        FILE* w = open_out(pre + ".var", "w");
         std::fprintf(w, "#CHR\tSNP\tA1\tA2");
         for (long k = 0; k < K; ++k) std::fprintf(w, "\tPC%ld", k + 1);
         std::fprintf(w, "\n");
-        for (unsigned j = 0; j < Mtot; ++j) {
+        for (unsigned j = 0; j < co.Mtot; ++j) {
             std::fprintf(w, "%s\t%s\t%s\t%s", bim.chr[j].c_str(), bim.id[j].c_str(), bim.a1[j].c_str(), bim.a2[j].c_str());
             for (long k = 0; k < K; ++k) {
-                const double x = load[(size_t)k * Mtot + j];
+                const double x = load[(size_t)k * co.Mtot + j];
                 if (std::isfinite(x)) std::fprintf(w, "\t%.12g", x);
                 else std::fprintf(w, "\tNA");
             }
             std::fprintf(w, "\n");
         }
-        if (std::fclose(w) != 0) fatal("FATAL  : short write on " + pre + ".var");
+        close_out(w, pre + ".var");
     }
     double worst = 0.0;
     for (long k = 0; k < K; ++k) worst = std::max(worst, rep.resid[k]);
     std::printf("PCA    : %u rows, %u markers used, panel of %d, %d iterations run, last Ritz change %g, largest residual %g, written to %s (%.3f ms on the device)\n",
                 Ntot, rep.m_used, L, rep.iters_run, rep.ritz_change, worst, vec.c_str(), ms[0]);
     return 0;
+}
+
+// ---- the analysis modes -------------------------------------------------------
+// An analysis mode is an option that, appended to a bayesMPI command line, samples nothing and runs one analysis on the chain's rows
+// (run_predict .. run_pca above).  What the modes share is refused in one place, from one row per mode.
+struct Mode {
+    const char* flag;   // the option that asks for the mode
+    bool given;
+    const char* wmpi;   // how it refuses --mpibayes bayesWMPI, after its flag
+    const char* orphan; // the first of its dependent options that was given: they need the mode (null: none was)
+};
+enum { PREDICT, LD, ASSOC, KING, PCA, NMODES }; // the order in which a mode names the earlier ones it cannot be combined with
+
+const char* first_given(std::initializer_list<std::pair<const char*, bool>> deps)
+{
+    for (const auto& d : deps)
+        if (d.second) return d.first;
+    return nullptr;
+}
+
+// the modes' own arguments
+void check_ld_args(const Options& opt)
+{
+    if (opt.ldWindow < 1 || opt.ldWindow > 4096)
+        fatal("FATAL  : --ld-window " + std::to_string(opt.ldWindow) + ": the window must be 1 to 4096 markers (the widest hgibbs_ld takes)");
+    if (!(opt.ldWindowR2 >= 0.0 && opt.ldWindowR2 <= 1.0)) fatal("FATAL  : --ld-window-r2 must be in [0, 1]");
+    if (opt.ldKbGiven && !(opt.ldWindowKb >= 0.0)) fatal("FATAL  : --ld-window-kb must not be negative");
+}
+
+void check_king_args(const Options& opt)
+{
+    double t = 0.0;
+    if (!whole_num(opt.kingCutoff, t) || !std::isfinite(t)) fatal("FATAL  : --king-cutoff " + opt.kingCutoff + ": the cutoff must be a finite number");
+}
+
+void check_pca_args(const Options& opt)
+{
+    long v = 0;
+    double t = 0.0;
+    if (!whole_int(opt.pcaK, v) || v < 1 || v > PCA_KMAX)
+        fatal("FATAL  : --pca " + opt.pcaK + ": the number of components must be an integer from 1 to " + std::to_string(PCA_KMAX));
+    if (opt.pcaItersGiven && (!whole_int(opt.pcaIters, v) || v < 1)) fatal("FATAL  : --pca-iters " + opt.pcaIters + ": needs at least one iteration");
+    if (opt.pcaItersGiven && v > std::numeric_limits<int>::max())
+        fatal("FATAL  : --pca-iters " + opt.pcaIters + ": at most " + std::to_string(std::numeric_limits<int>::max()) + " iterations");
+    if (opt.pcaTolGiven && (!whole_num(opt.pcaTol, t) || !std::isfinite(t) || t < 0.0))
+        fatal("FATAL  : --pca-tol " + opt.pcaTol + ": the tolerance must be a finite number >= 0");
+}
+
+// Every refusal of the modes, before anything is read: mode by mode (--ld-window first, then in the table's order), what all share,
+// then the mode's own arguments
+void check_modes(const Options& opt, int nranks)
+{
+    const char* const takes = "takes a bayesMPI command line, not --mpibayes bayesWMPI";
+    const Mode modes[NMODES] = {
+        {"--predict-bfile", !opt.predictBfile.empty(), "scores with bayesMPI effects only, not with --mpibayes bayesWMPI",
+         first_given({{"--predict-dry-run", opt.predictDryRun}, {"--predict-out", !opt.predictOut.empty()}})},
+        {"--ld-window", opt.ldGiven, takes,
+         first_given({{"--ld-out", !opt.ldOut.empty()}, {"--ld-window-kb", opt.ldKbGiven}, {"--ld-window-r2", opt.ldR2Given}, {"--ld-bin", opt.ldBin}})},
+        {"--assoc", opt.assoc, takes, first_given({{"--assoc-out", !opt.assocOut.empty()}, {"--assoc-no-loco", opt.assocNoLoco}})},
+        {"--king", opt.king, takes, first_given({{"--king-out", !opt.kingOut.empty()}, {"--king-cutoff", opt.kingCutoffGiven}})},
+        {"--pca", opt.pca, takes,
+         first_given({{"--pca-iters", opt.pcaItersGiven}, {"--pca-tol", opt.pcaTolGiven}, {"--pca-out", opt.pcaOutGiven}, {"--pca-loadings", opt.pcaLoadings}})},
+    };
+    for (const int i : {LD, PREDICT, ASSOC, KING, PCA}) {
+        const Mode& m = modes[i];
+        const std::string flag = m.flag;
+        if (!m.given) {
+            if (m.orphan) fatal(std::string("FATAL  : ") + m.orphan + " needs " + flag);
+            continue;
+        }
+        if (opt.bayesType == "bayesWMPI") fatal("FATAL  : " + flag + " " + m.wmpi);
+        for (int j = 0; j < i; ++j)
+            if (modes[j].given) fatal("FATAL  : " + flag + " cannot be combined with " + modes[j].flag);
+        if (opt.restart) fatal("FATAL  : " + flag + " does not sample: it cannot be combined with --restart");
+        if (nranks > 1) fatal("FATAL  : " + flag + " runs on one process (WORLD_SIZE = " + std::to_string(nranks) + ")");
+        if (i == LD) check_ld_args(opt);
+        if (i == KING) check_king_args(opt);
+        if (i == PCA) check_pca_args(opt);
+    }
 }
 
 } // namespace
@@ -1590,63 +1626,7 @@ int main(int argc, const char* argv[])
     const int rank = (e = std::getenv("RANK")) ? std::atoi(e) : 0;
     const int nranks = (e = std::getenv("WORLD_SIZE")) ? std::atoi(e) : 1;
     const int local_rank = (e = std::getenv("LOCAL_RANK")) ? std::atoi(e) : rank;
-    if (opt.ldGiven) {
-        if (opt.bayesType == "bayesWMPI") fatal("FATAL  : --ld-window takes a bayesMPI command line, not --mpibayes bayesWMPI");
-        if (!opt.predictBfile.empty()) fatal("FATAL  : --ld-window cannot be combined with --predict-bfile");
-        if (opt.restart) fatal("FATAL  : --ld-window does not sample: it cannot be combined with --restart");
-        if (nranks > 1) fatal("FATAL  : --ld-window runs on one process (WORLD_SIZE = " + std::to_string(nranks) + ")");
-        if (opt.ldWindow < 1 || opt.ldWindow > 4096)
-            fatal("FATAL  : --ld-window " + std::to_string(opt.ldWindow) + ": the window must be 1 to 4096 markers (the widest hgibbs_ld takes)");
-        if (!(opt.ldWindowR2 >= 0.0 && opt.ldWindowR2 <= 1.0)) fatal("FATAL  : --ld-window-r2 must be in [0, 1]");
-        if (opt.ldKbGiven && !(opt.ldWindowKb >= 0.0)) fatal("FATAL  : --ld-window-kb must not be negative");
-    } else if (!opt.ldOut.empty() || opt.ldKbGiven || opt.ldR2Given || opt.ldBin)
-        fatal(std::string("FATAL  : ") + (!opt.ldOut.empty() ? "--ld-out" : opt.ldKbGiven ? "--ld-window-kb" : opt.ldR2Given ? "--ld-window-r2" : "--ld-bin") +
-              " needs --ld-window");
-    if (!opt.predictBfile.empty()) {
-        if (opt.bayesType == "bayesWMPI") fatal("FATAL  : --predict-bfile scores with bayesMPI effects only, not with --mpibayes bayesWMPI");
-        if (opt.restart) fatal("FATAL  : --predict-bfile does not sample: it cannot be combined with --restart");
-        if (nranks > 1) fatal("FATAL  : --predict-bfile runs on one process (WORLD_SIZE = " + std::to_string(nranks) + ")");
-    } else if (!opt.predictOut.empty() || opt.predictDryRun)
-        fatal(std::string("FATAL  : ") + (opt.predictDryRun ? "--predict-dry-run" : "--predict-out") + " needs --predict-bfile");
-    if (opt.assoc) {
-        if (opt.bayesType == "bayesWMPI") fatal("FATAL  : --assoc takes a bayesMPI command line, not --mpibayes bayesWMPI");
-        if (!opt.predictBfile.empty()) fatal("FATAL  : --assoc cannot be combined with --predict-bfile");
-        if (opt.ldGiven) fatal("FATAL  : --assoc cannot be combined with --ld-window");
-        if (opt.restart) fatal("FATAL  : --assoc does not sample: it cannot be combined with --restart");
-        if (nranks > 1) fatal("FATAL  : --assoc runs on one process (WORLD_SIZE = " + std::to_string(nranks) + ")");
-    } else if (!opt.assocOut.empty() || opt.assocNoLoco)
-        fatal(std::string("FATAL  : ") + (!opt.assocOut.empty() ? "--assoc-out" : "--assoc-no-loco") + " needs --assoc");
-    if (opt.king) {
-        if (opt.bayesType == "bayesWMPI") fatal("FATAL  : --king takes a bayesMPI command line, not --mpibayes bayesWMPI");
-        if (!opt.predictBfile.empty()) fatal("FATAL  : --king cannot be combined with --predict-bfile");
-        if (opt.ldGiven) fatal("FATAL  : --king cannot be combined with --ld-window");
-        if (opt.assoc) fatal("FATAL  : --king cannot be combined with --assoc");
-        if (opt.restart) fatal("FATAL  : --king does not sample: it cannot be combined with --restart");
-        if (nranks > 1) fatal("FATAL  : --king runs on one process (WORLD_SIZE = " + std::to_string(nranks) + ")");
-        if (!std::isfinite(king_cutoff(opt))) fatal("FATAL  : --king-cutoff " + opt.kingCutoff + ": the cutoff must be a finite number");
-    } else if (!opt.kingOut.empty() || opt.kingCutoffGiven)
-        fatal(std::string("FATAL  : ") + (!opt.kingOut.empty() ? "--king-out" : "--king-cutoff") + " needs --king");
-    if (opt.pca) {
-        if (opt.bayesType == "bayesWMPI") fatal("FATAL  : --pca takes a bayesMPI command line, not --mpibayes bayesWMPI");
-        if (!opt.predictBfile.empty()) fatal("FATAL  : --pca cannot be combined with --predict-bfile");
-        if (opt.ldGiven) fatal("FATAL  : --pca cannot be combined with --ld-window");
-        if (opt.assoc) fatal("FATAL  : --pca cannot be combined with --assoc");
-        if (opt.king) fatal("FATAL  : --pca cannot be combined with --king");
-        if (opt.restart) fatal("FATAL  : --pca does not sample: it cannot be combined with --restart");
-        if (nranks > 1) fatal("FATAL  : --pca runs on one process (WORLD_SIZE = " + std::to_string(nranks) + ")");
-        long v = 0;
-        double t = 0.0;
-        if (!whole_int(opt.pcaK, v) || v < 1 || v > PCA_KMAX)
-            fatal("FATAL  : --pca " + opt.pcaK + ": the number of components must be an integer from 1 to " + std::to_string(PCA_KMAX));
-        if (opt.pcaItersGiven && (!whole_int(opt.pcaIters, v) || v < 1))
-            fatal("FATAL  : --pca-iters " + opt.pcaIters + ": needs at least one iteration");
-        if (opt.pcaItersGiven && v > std::numeric_limits<int>::max())
-            fatal("FATAL  : --pca-iters " + opt.pcaIters + ": at most " + std::to_string(std::numeric_limits<int>::max()) + " iterations");
-        if (opt.pcaTolGiven && (!whole_num(opt.pcaTol, t) || !std::isfinite(t) || t < 0.0))
-            fatal("FATAL  : --pca-tol " + opt.pcaTol + ": the tolerance must be a finite number >= 0");
-    } else if (opt.pcaItersGiven || opt.pcaTolGiven || opt.pcaOutGiven || opt.pcaLoadings)
-        fatal(std::string("FATAL  : ") + (opt.pcaItersGiven ? "--pca-iters" : opt.pcaTolGiven ? "--pca-tol" : opt.pcaOutGiven ? "--pca-out" : "--pca-loadings") +
-              " needs --pca");
+    check_modes(opt, nranks);
     if (opt.bayesType == "bayesWMPI") return run_bayesw(opt, rank, nranks, local_rank); // main.cpp:164-167
 
     // ---- inputs (main.cpp:69-70,88; BayesRRm.cpp:969-997) -------------------
@@ -1674,11 +1654,12 @@ int main(int argc, const char* argv[])
                         numInds, numInds, numNAs, Ntot);
         std::printf("INFO   : Full dataset includes Mtot=%d markers and Ntot=%d individuals.\n", Mtot, (int)numInds);
     }
-    if (!opt.predictBfile.empty()) return run_predict(opt, keep, (unsigned)numInds, numNAs, Mtot, local_rank);
-    if (opt.ldGiven) return run_ld(opt, keep, (unsigned)numInds, numNAs, Mtot, local_rank);
-    if (opt.assoc) return run_assoc(opt, keep, y, covX, C, (unsigned)numInds, numNAs, Mtot, local_rank);
-    if (opt.king) return run_king(opt, keep, (unsigned)numInds, numNAs, Mtot, local_rank);
-    if (opt.pca) return run_pca(opt, keep, (unsigned)numInds, numNAs, Mtot, local_rank);
+    const Cohort co{keep, (unsigned)numInds, numNAs, Ntot, Mtot, local_rank};
+    if (!opt.predictBfile.empty()) return run_predict(opt, co);
+    if (opt.ldGiven) return run_ld(opt, co);
+    if (opt.assoc) return run_assoc(opt, co, y, covX, C);
+    if (opt.king) return run_king(opt, co);
+    if (opt.pca) return run_pca(opt, co);
 
     std::vector<int32_t> groups;
     std::vector<std::vector<double>> mS;
@@ -1709,9 +1690,7 @@ int main(int argc, const char* argv[])
         if (rank == 0) std::printf("         opt.save reset to %d, the closest multiple of opt.thin (%d)\n", opt.save, opt.thin);
     }
 
-    struct stat sb;
-    if (stat(opt.mcmcOutDir.c_str(), &sb) != 0 && rank == 0)
-        if (std::system(("mkdir -p " + opt.mcmcOutDir).c_str()) != 0) fatal("FATAL  : can not create --mcmc-out-dir");
+    if (rank == 0) make_out_dir(opt);
     // a restart reads <name>.* and writes <name>_rs.* so the failed job's files stay untouched (:1206-1220)
     const std::string base_in = opt.mcmcOutDir + "/" + opt.mcmcOutNam;
     const std::string base = opt.restart ? base_in + "_rs" : base_in;
@@ -1726,17 +1705,7 @@ int main(int argc, const char* argv[])
     // ---- genotypes: Data::load_data_from_bed_file, data.cpp:671-739 -----------
     const double tl0 = now_s();
     const size_t snpLenByt = (numInds + 3) / 4;
-    std::vector<uint8_t> bed;
-    {
-        std::ifstream in(opt.bedFile + ".bed", std::ios::binary);
-        if (!in) fatal("Error: can not open the file [" + opt.bedFile + ".bed] to read.");
-        unsigned char magic[3];
-        in.read((char*)magic, 3);
-        if (!in || magic[0] != 0x6c || magic[1] != 0x1b || magic[2] != 0x01) fatal("FATAL  : " + opt.bedFile + ".bed is not a SNP-major PLINK bed");
-        bed.resize((size_t)Mtot * snpLenByt);
-        in.read((char*)bed.data(), (std::streamsize)bed.size());
-        if ((size_t)in.gcount() != bed.size()) fatal("FATAL  : " + opt.bedFile + ".bed is shorter than M x ceil(N/4)");
-    }
+    std::vector<uint8_t> bed = read_bed(opt.bedFile, numInds, Mtot);
     // individuals sharded in multiples of 4 of the KEPT rows
     const unsigned per = ((Ntot + nranks - 1) / nranks + 3) / 4 * 4;
     const unsigned lo = std::min(Ntot, rank * per), hi = std::min(Ntot, (rank + 1) * per);
@@ -1833,11 +1802,7 @@ int main(int argc, const char* argv[])
 
     // ---- outputs (rank 0 writes the shared files) ----------------------------
     FILE *outf = nullptr, *betf = nullptr, *cpnf = nullptr, *acuf = nullptr, *xbetf = nullptr, *xcpnf = nullptr;
-    auto open_trunc = [&](const std::string& p) {
-        FILE* f = std::fopen(p.c_str(), "wb+");
-        if (!f) fatal("FATAL  : can not create " + p);
-        return f;
-    };
+    auto open_trunc = [&](const std::string& p) { return open_out(p, "wb+"); };
     if (rank == 0) {
         outf = open_trunc(base + ".csv");
         betf = open_trunc(base + ".bet");
