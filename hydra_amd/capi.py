@@ -18,7 +18,7 @@ ABI_SYMBOLS = [
     "hgibbs_marker_stats", "hgibbs_set_residual", "hgibbs_get_residual", "hgibbs_reduce_eps", "hgibbs_add_scalar",
     "hgibbs_update_marker", "hgibbs_dot_marker", "hgibbs_set_covariates", "hgibbs_cov_dot", "hgibbs_cov_update",
     "hydra_chain_set_covariates", "hydra_chain_gamma", "hgibbs_set_components", "hydra_chain_restore",
-    "hydra_rng_to_boost_words", "hydra_rng_from_boost_words", "hgibbs_set_model", "hgibbs_set_beta", "hgibbs_get_beta",
+    "hydra_rng_to_boost_words", "hydra_rng_from_boost_words", "hydra_rng_shuffle", "hgibbs_set_model", "hgibbs_set_beta", "hgibbs_get_beta",
     "hgibbs_beta_sqnorm", "hgibbs_sweep", "hgibbs_set_option", "hgibbs_last_sweep_stats", "hgibbs_stream_ceiling", "hgibbs_debug_times", "hgibbs_resident_trace", "hydra_chain_create",
     "hydra_chain_destroy", "hydra_chain_iterate", "hydra_chain_state", "hydra_chain_csv_line", "hydra_chain_order",
     "hydra_chain_last_nnz", "hgibbs_score", "hgibbs_last_score_ms", "hgibbs_ld", "hgibbs_last_ld_ms",
@@ -135,6 +135,7 @@ def lib():
     L.hydra_chain_restore.argtypes = [vp, C.POINTER(RestartState)]
     L.hydra_rng_to_boost_words.argtypes = [C.POINTER(RngState), u32p]
     L.hydra_rng_from_boost_words.argtypes = [u32p, C.POINTER(RngState)]
+    L.hydra_rng_shuffle.argtypes = [C.POINTER(RngState), ip, C.c_uint32]
     L.hgibbs_set_model.argtypes = [vp, C.c_int, C.c_int, ip, dp, dp]
     L.hgibbs_set_beta.argtypes = [vp, dp]
     L.hgibbs_get_beta.argtypes = [vp, dp, ip, dp]
@@ -220,6 +221,13 @@ def _u8(a):
 
 def _u64(a):
     return a.ctypes.data_as(C.POINTER(C.c_uint64))
+
+
+def rng_shuffle(rng, v):
+    """hydra_rng_shuffle: the chain's marker shuffle on a caller's RngState and contiguous int32 array, both in place."""
+    if v.dtype != np.int32 or not v.flags.c_contiguous:
+        raise ValueError("rng_shuffle: a contiguous int32 array is required")
+    check(lib().hydra_rng_shuffle(C.byref(rng), _ip(v), v.size))
 
 
 class Device:

@@ -271,4 +271,92 @@ inline void shuffle_libstdcxx6(T* first, size_t n, Mt& g)
     }
 }
 
+// ---- the same shuffle, fast (host only): identical permutation, identical generator state afterwards ----
+// Mt::twist() without the modulo: three segments whose loads run ahead of (or 227 words behind) the stores, so the
+// compiler vectorises the first two.  Same words as Mt::twist() (which stays as it is: the device compiles it too).
+inline void mt_twist_bulk(uint32_t* x)
+{
+    for (int i = 0; i < MT_N - MT_M; ++i) x[i] = mt_mix(x[i], x[i + 1], x[i + MT_M]);
+    for (int i = MT_N - MT_M; i < MT_N - 1; ++i) x[i] = mt_mix(x[i], x[i + 1], x[i + MT_M - MT_N]);
+    x[MT_N - 1] = mt_mix(x[MT_N - 1], x[0], x[MT_M - 1]);
+}
+
+// Swap indices of the positions i0 .. i0 + len - 1 from len raw words, assuming none of them is rejected; returns whether
+// one was (then q is valid only before the first rejected word).  All operands fit 32 bits: (i + 1) * scaling <= 2^32 - 1.
+// Both quotients come from one correctly rounded double division and truncation (the compiler vectorises that; there is
+// no vector integer division).  That is exact: for integers a, b < 2^32 with a = q b + r, 0 <= r < b, the true quotient
+// lies at least 1/b below q + 1, while the rounding error of the division is at most half an ulp of a number below q + 1,
+// i.e. at most (q + 1) 2^-53 <= q 2^-52 < 2^-20 / b (as q b < 2^32; for q = 0 the quotient is at most 1 - 2^-32 and
+// rounds to a number below 1): the rounded quotient stays below q + 1, and it is never below q because q itself is a
+// double.  Conversions of 32-bit integers to double are exact, and IEEE division gives the same bits at every vector width.
+#define HG_SHUFFLE_INDICES_BODY                                          \
+    uint32_t bad = 0;                                                    \
+    for (uint32_t k = 0; k < len; ++k) {                                 \
+        const uint32_t ue = i0 + k + 1u;                                 \
+        const uint32_t sc = (uint32_t)(4294967295.0 / (double)ue);       \
+        q[k] = (uint32_t)((double)w[k] / (double)sc);                    \
+        bad |= (uint32_t)(w[k] >= ue * sc);                              \
+    }                                                                    \
+    return bad != 0;
+inline bool shuffle_indices_base(const uint32_t* w, uint32_t i0, uint32_t len, uint32_t* q) { HG_SHUFFLE_INDICES_BODY }
+#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
+// the same loop compiled for four divisions at a time, taken where the CPU has them (the build itself assumes no more than x86-64)
+__attribute__((target("avx2"))) inline bool shuffle_indices_avx2(const uint32_t* w, uint32_t i0, uint32_t len, uint32_t* q) { HG_SHUFFLE_INDICES_BODY }
+inline bool shuffle_indices(const uint32_t* w, uint32_t i0, uint32_t len, uint32_t* q)
+{
+    static const bool avx2 = __builtin_cpu_supports("avx2");
+    return avx2 ? shuffle_indices_avx2(w, i0, len, q) : shuffle_indices_base(w, i0, len, q);
+}
+#else
+inline bool shuffle_indices(const uint32_t* w, uint32_t i0, uint32_t len, uint32_t* q) { return shuffle_indices_base(w, i0, len, q); }
+#endif
+#undef HG_SHUFFLE_INDICES_BODY
+
+// shuffle_libstdcxx6 (the definition, above) with the generator's words made a block at a time and the indices computed in
+// runs that the compiler can vectorise; the swaps then run over ready indices.  Words are taken from the generator only
+// as far as positions are left (each needs at least one), and a 624-word block is twisted only when a word of it is
+// needed: g.x and g.idx end where the sequential form leaves them.  A rejected word (about 60 per million positions) ends
+// a run: the positions before it stand, the word is dropped, and the next run starts behind it.
+template <class T>
+inline void shuffle_libstdcxx6_fast(T* first, size_t n, Mt& g)
+{
+    constexpr uint32_t BLK = 4096;
+    uint32_t w[BLK], q[BLK];
+    size_t i = 1;
+    while (i < n) {
+        const uint32_t want = (uint32_t)((n - i < (size_t)BLK) ? n - i : (size_t)BLK);
+        uint32_t have = 0;
+        while (have < want) {
+            if (g.idx >= (uint32_t)MT_N) {
+                mt_twist_bulk(g.x);
+                g.idx = 0;
+            }
+            const uint32_t take = ((uint32_t)MT_N - g.idx < want - have) ? (uint32_t)MT_N - g.idx : want - have;
+            const uint32_t* src = g.x + g.idx;
+            for (uint32_t k = 0; k < take; ++k) w[have + k] = mt_temper(src[k]);
+            g.idx += take;
+            have += take;
+        }
+        uint32_t done = 0, used = 0; // positions that have their index, words consumed
+        while (used < have) {
+            const uint32_t len = have - used, i0 = (uint32_t)i + done;
+            uint32_t ok = len;
+            if (shuffle_indices(w + used, i0, len, q + done)) {
+                for (ok = 0; ok < len; ++ok) {
+                    const uint32_t ue = i0 + ok + 1u;
+                    if (w[used + ok] >= ue * (0xffffffffu / ue)) break;
+                }
+            }
+            done += ok;
+            used += ok + (ok < len ? 1u : 0u);
+        }
+        for (uint32_t k = 0; k < done; ++k) {
+            const T t = first[i + k];
+            first[i + k] = first[q[k]];
+            first[q[k]] = t;
+        }
+        i += done;
+    }
+}
+
 } // namespace hg

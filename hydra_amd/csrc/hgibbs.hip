@@ -131,6 +131,18 @@ struct hgibbs_ctx {
     size_t scratch_n = 0;
     double* scratch_host = nullptr; // pinned, 4096 doubles
     double* beta_host = nullptr;    // pinned, M doubles (lazy)
+    uint32_t* bsq_idx_host = nullptr; // pinned, M + 1 words (lazy): hgibbs_beta_sqnorm's list of markers, its length in the last word
+    uint32_t bsq_guess = 1024;        // entries of the list fetched with its length (the last call's length and a margin)
+    // pinned staging of a sweep's inputs and small results (lazy): what the host writes or reads travels without a bounce buffer
+    int32_t* order_host = nullptr;    // M
+    uint8_t* adaV_host = nullptr;     // M: the caller's adaV as the device holds it
+    bool adaV_on_device = false;
+    uint32_t* sweep_io_host = nullptr; // MT_N generator words, G*K cass, then the order check's word
+    size_t sweep_io_words = 0;
+    uint32_t* order_bad = nullptr;     // device: the first sweep position whose order entry is outside [0, M) (k_gather_meta), else 0xffffffff
+    const void* occ_kern = nullptr;    // the last occupancy query (resident kernel, LDS bytes) and its answer
+    size_t occ_lds = 0;
+    int occ_per_cu = 0;
 
     // options
     uint32_t batch = 0; // 0 = auto: 256 for shards of >= 20k individuals or several ranks, else 128
@@ -375,14 +387,19 @@ __global__ void k_stats(const unsigned long long* __restrict__ counts, uint32_t 
 }
 
 // per-marker metadata in sweep order (one pass per sweep): the draw phase then
-// reads contiguous, order-independent rows
+// reads contiguous, order-independent rows.  An order entry outside [0, M) is not followed: the smallest such position goes to *bad
+// (0xffffffff before the launch), which the host reads before any sweep kernel runs.
 __global__ void k_gather_meta(const int32_t* __restrict__ order, const double* __restrict__ mave, const double* __restrict__ mstd,
                               const double* __restrict__ beta, const int32_t* __restrict__ groups, const uint8_t* __restrict__ adaV,
-                              const unsigned long long* __restrict__ counts, double* s_mave, double* s_mstd, double* s_bold, int32_t* s_ga, uint32_t M)
+                              const unsigned long long* __restrict__ counts, double* s_mave, double* s_mstd, double* s_bold, int32_t* s_ga, uint32_t M, uint32_t* bad)
 {
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= M) return;
     const int m = order[j];
+    if ((uint32_t)m >= M) {
+        atomicMin(bad, j);
+        return;
+    }
     s_mave[j] = mave[m];
     s_mstd[j] = mstd[m];
     s_bold[j] = beta[m];
@@ -392,15 +409,17 @@ __global__ void k_gather_meta(const int32_t* __restrict__ order, const double* _
 // The sweep positions whose marker's effect is non-zero at sweep start (it WILL change: a predicted event), ascending, followed by 16
 // sentinels 0xffffffff: the resident engine's streaming workgroups and its walker both read the window's pivots off this list.
 // Three small launches: per chunk of 4096 positions a count, one workgroup's exclusive scan of the counts, an order-preserving scatter.
+// They compact the non-zero entries of any array of M doubles: hgibbs_beta_sqnorm runs them over beta in marker order and takes the
+// values along (payload), the sweep runs them over s_bold without (payload = nullptr).
 constexpr uint32_t PRED_CHUNK = 4096;
-__global__ __launch_bounds__(256) void k_pred_count(const double* __restrict__ s_bold, uint32_t M, uint32_t* cnt)
+__global__ __launch_bounds__(256) void k_pred_count(const double* __restrict__ src, uint32_t M, uint32_t* cnt)
 {
     __shared__ uint32_t wsum[4];
     const uint32_t base = blockIdx.x * PRED_CHUNK;
     uint32_t n = 0;
     for (uint32_t i = 0; i < PRED_CHUNK / 256; ++i) {
         const uint32_t j = base + i * 256 + threadIdx.x;
-        n += (uint32_t)__popcll(__ballot(j < M && s_bold[j] != 0.0));
+        n += (uint32_t)__popcll(__ballot(j < M && src[j] != 0.0));
     }
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = n; // (every lane of a wave holds the wave's count)
     __syncthreads();
@@ -431,7 +450,7 @@ __global__ __launch_bounds__(1024) void k_pred_scan(uint32_t* cnt, uint32_t nchu
         run += v;
     }
 }
-__global__ __launch_bounds__(256) void k_pred_scatter(const double* __restrict__ s_bold, uint32_t M, const uint32_t* __restrict__ cnt, uint32_t nchunk, uint32_t* pred)
+__global__ __launch_bounds__(256) void k_pred_scatter(const double* __restrict__ src, uint32_t M, const uint32_t* __restrict__ cnt, uint32_t nchunk, uint32_t* pred, double* payload)
 {
     __shared__ uint32_t wsum[4];
     const uint32_t base = blockIdx.x * PRED_CHUNK;
@@ -439,14 +458,19 @@ __global__ __launch_bounds__(256) void k_pred_scatter(const double* __restrict__
     uint32_t run = cnt[blockIdx.x];
     for (uint32_t i = 0; i < PRED_CHUNK / 256; ++i) {
         const uint32_t j = base + i * 256 + threadIdx.x;
-        const bool f = j < M && s_bold[j] != 0.0;
+        const double v = j < M ? src[j] : 0.0;
+        const bool f = v != 0.0;
         const unsigned long long m = __ballot(f);
         __syncthreads(); // (the previous pass's wsum has been read)
         if (lane == 0) wsum[wave] = (uint32_t)__popcll(m);
         __syncthreads();
         uint32_t before = 0;
         for (int w = 0; w < wave; ++w) before += wsum[w];
-        if (f) pred[run + before + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = j;
+        if (f) {
+            const uint32_t at = run + before + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+            pred[at] = j;
+            if (payload) payload[at] = v;
+        }
         run += wsum[0] + wsum[1] + wsum[2] + wsum[3];
     }
     if (blockIdx.x == 0 && threadIdx.x < 16) pred[cnt[nchunk] + threadIdx.x] = 0xffffffffu;
@@ -702,7 +726,7 @@ int hgibbs_destroy(hgibbs_t h)
         if (h->peer_base[r] && h->peer_base[r] != h->mbox) (void)hipIpcCloseMemHandle(h->peer_base[r]);
     if (h->mbox) (void)hipFree(h->mbox);
     void* ptrs[] = {h->bed, h->eps[0], h->eps[1], h->mave, h->mstd, h->counts, h->groups, h->beta, h->comp, h->acum, h->order,
-                    h->adaV, h->covX, h->s_mave, h->s_mstd, h->s_bold, h->s_ga, h->pred, h->pred_cnt, h->dbg, h->cass, h->tables, h->mt, h->zig, h->desc, h->partials, h->totals, h->ticket, h->sums, h->scratch, h->carry, h->ahead_raw, h->apartials, h->aticket, h->res_acc, h->res_msg, h->res_state, h->res_trace};
+                    h->adaV, h->covX, h->s_mave, h->s_mstd, h->s_bold, h->s_ga, h->pred, h->pred_cnt, h->dbg, h->cass, h->tables, h->mt, h->zig, h->desc, h->partials, h->totals, h->ticket, h->sums, h->scratch, h->carry, h->ahead_raw, h->apartials, h->aticket, h->res_acc, h->res_msg, h->res_state, h->res_trace, h->order_bad};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (h->desc_host) (void)hipHostFree(h->desc_host);
@@ -714,6 +738,10 @@ int hgibbs_destroy(hgibbs_t h)
     if (h->res_progress_host) (void)hipHostFree(h->res_progress_host);
     if (h->aux_stream) (void)hipStreamDestroy(h->aux_stream);
     if (h->beta_host) (void)hipHostFree(h->beta_host);
+    if (h->bsq_idx_host) (void)hipHostFree(h->bsq_idx_host);
+    if (h->order_host) (void)hipHostFree(h->order_host);
+    if (h->adaV_host) (void)hipHostFree(h->adaV_host);
+    if (h->sweep_io_host) (void)hipHostFree(h->sweep_io_host);
     (void)hipEventDestroy(h->ev0);
     (void)hipEventDestroy(h->ev1);
     (void)hipStreamDestroy(h->stream);
@@ -825,6 +853,7 @@ static int alloc_problem(hgibbs_ctx* h, uint32_t n_global, uint32_t n_local, uin
     HIP_TRY(hipMalloc(&h->acum, (size_t)M * sizeof(double)));
     HIP_TRY(hipMalloc(&h->order, (size_t)M * sizeof(int32_t)));
     HIP_TRY(hipMalloc(&h->adaV, (size_t)M));
+    HIP_TRY(hipMalloc(&h->order_bad, sizeof(uint32_t)));
     HIP_TRY(hipMalloc(&h->s_mave, (size_t)M * sizeof(double)));
     HIP_TRY(hipMalloc(&h->s_mstd, (size_t)M * sizeof(double)));
     HIP_TRY(hipMalloc(&h->s_bold, (size_t)M * sizeof(double)));
@@ -1200,14 +1229,42 @@ int hgibbs_beta_sqnorm(hgibbs_t h, double* bsq_host)
 {
     if (!h || !h->bed || h->G < 1) return fail("hgibbs_beta_sqnorm: model not set");
     HIP_TRY(hipSetDevice(h->device));
-    // M doubles cross PCIe once per iteration (they are needed on the host for
-    // the .bet output anyway); the sum then runs sequentially in marker order,
-    // exactly as src/BayesRRm.cpp:2496-2499.
-    if (!h->beta_host) HIP_TRY(hipHostMalloc(&h->beta_host, (size_t)h->M * sizeof(double)));
-    HIP_TRY(hipMemcpyAsync(h->beta_host, h->beta, (size_t)h->M * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    // The sum runs sequentially in marker order on the host, exactly as src/BayesRRm.cpp:2496-2499 -- over the non-zero effects
+    // only: a zero effect adds +0.0 (the square of -0.0 too), and a sum that starts at +0.0 and only ever receives squares is
+    // never -0.0, so that add leaves its bits alone.  The device compacts (marker, effect) in marker order (k_pred_*, with the
+    // sweep's list and its s_bold as the buffers: both are rebuilt at the next sweep's start); the list's length travels with a
+    // guessed number of entries, so a sparse model needs one synchronise and about 12 bytes per non-zero effect instead of 8 M.
+    const uint32_t M = h->M, nchunk = (M + PRED_CHUNK - 1) / PRED_CHUNK;
+    if (!h->beta_host) HIP_TRY(hipHostMalloc(&h->beta_host, (size_t)M * sizeof(double)));
+    if (!h->bsq_idx_host) HIP_TRY(hipHostMalloc(&h->bsq_idx_host, ((size_t)M + 1) * sizeof(uint32_t)));
+    k_pred_count<<<nchunk, 256, 0, h->stream>>>(h->beta, M, h->pred_cnt);
+    k_pred_scan<<<1, 1024, 0, h->stream>>>(h->pred_cnt, nchunk);
+    k_pred_scatter<<<nchunk, 256, 0, h->stream>>>(h->beta, M, h->pred_cnt, nchunk, h->pred, h->s_bold);
+    HIP_TRY(hipGetLastError());
+    const uint32_t got = std::min(M, h->bsq_guess);
+    HIP_TRY(hipMemcpyAsync(h->bsq_idx_host + M, h->pred_cnt + nchunk, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->bsq_idx_host, h->pred, (size_t)got * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->beta_host, h->s_bold, (size_t)got * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
+    const uint32_t n = h->bsq_idx_host[M];
+    if (n > M) return fail("hgibbs_beta_sqnorm: list of %u non-zero effects among %u markers", n, M);
+    h->bsq_guess = n + n / 8 + 1024;
     for (int g = 0; g < h->G; ++g) bsq_host[g] = 0.0;
-    for (uint32_t i = 0; i < h->M; ++i) bsq_host[h->groups_host[i]] += h->beta_host[i] * h->beta_host[i];
+    // Dense models: the list moves 12 bytes per entry where the whole vector moves 8 per marker, and both sums do one add per
+    // element they hold, so the list stops paying at two thirds of M; the whole vector is taken from half of M on (the two
+    // paths cost about the same between the two, and this path has already paid for the compaction).
+    if (n > M / 2) {
+        HIP_TRY(hipMemcpyAsync(h->beta_host, h->beta, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        for (uint32_t i = 0; i < M; ++i) bsq_host[h->groups_host[i]] += h->beta_host[i] * h->beta_host[i];
+        return 0;
+    }
+    if (n > got) {
+        HIP_TRY(hipMemcpyAsync(h->bsq_idx_host + got, h->pred + got, (size_t)(n - got) * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(h->beta_host + got, h->s_bold + got, (size_t)(n - got) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    for (uint32_t i = 0; i < n; ++i) bsq_host[h->groups_host[h->bsq_idx_host[i]]] += h->beta_host[i] * h->beta_host[i];
     return 0;
 }
 
@@ -1573,7 +1630,7 @@ static int sweep_resident(hgibbs_ctx* h, const SweepPlan& pl, const double r0[2]
         const uint32_t nchunk = (h->M + PRED_CHUNK - 1) / PRED_CHUNK;
         k_pred_count<<<nchunk, 256, 0, h->stream>>>(h->s_bold, h->M, h->pred_cnt);
         k_pred_scan<<<1, 1024, 0, h->stream>>>(h->pred_cnt, nchunk);
-        k_pred_scatter<<<nchunk, 256, 0, h->stream>>>(h->s_bold, h->M, h->pred_cnt, nchunk, h->pred);
+        k_pred_scatter<<<nchunk, 256, 0, h->stream>>>(h->s_bold, h->M, h->pred_cnt, nchunk, h->pred, nullptr);
         HIP_TRY(hipGetLastError());
     }
     p.sweep_id = ++h->res_sweep_id; // every rank runs the same sweeps on the resident engine (agreed in hgibbs_sweep): the counters stay equal
@@ -1587,8 +1644,12 @@ static int sweep_resident(hgibbs_ctx* h, const SweepPlan& pl, const double r0[2]
     if (res_opt_in(h, pl)) return 1;
     {
         // every workgroup of the grid waits for the others: all of them must be resident at once
-        int per_cu = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pl.kern, RS_BLOCK, pl.lds));
+        if (h->occ_kern != (const void*)pl.kern || h->occ_lds != pl.lds) {
+            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&h->occ_per_cu, pl.kern, RS_BLOCK, pl.lds));
+            h->occ_kern = (const void*)pl.kern;
+            h->occ_lds = pl.lds;
+        }
+        const int per_cu = h->occ_per_cu;
         if (per_cu < 1 || (uint64_t)per_cu * (uint64_t)h->num_cu < (uint64_t)pl.W + 1)
             return fail("hgibbs_sweep: the resident grid of %u workgroups does not fit the device (%d per compute unit, %d units)", pl.W + 1, per_cu, h->num_cu);
     }
@@ -1603,6 +1664,10 @@ static int sweep_resident(hgibbs_ctx* h, const SweepPlan& pl, const double r0[2]
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(h->ev1, h->stream));
     HIP_TRY(hipMemcpyAsync(h->res_state_host, h->res_state, sizeof(ResState), hipMemcpyDeviceToHost, h->stream));
+    // the generator's words and cass come back behind it, into the handle's pinned staging: one wait for all three
+    HIP_TRY(hipMemcpyAsync(h->sweep_io_host, h->mt, MT_N * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->sweep_io_host + MT_N, h->cass, (size_t)h->G * h->K * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    const auto t_launch = std::chrono::steady_clock::now();
     {
         // the kernel bounds every wait of its own; the host's deadline is the last line of defence (a kernel that does not come
         // back is reported with where its walker and its first streaming workgroup stand, not waited for)
@@ -1665,8 +1730,8 @@ static int sweep_resident(hgibbs_ctx* h, const SweepPlan& pl, const double r0[2]
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
     rng->idx = st.rng_idx;
-    HIP_TRY(hipMemcpy(rng->x, h->mt, MT_N * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (cass_host) HIP_TRY(hipMemcpy(cass_host, h->cass, (size_t)h->G * h->K * sizeof(int32_t), hipMemcpyDeviceToHost));
+    std::memcpy(rng->x, h->sweep_io_host, MT_N * sizeof(uint32_t));
+    if (cass_host) std::memcpy(cass_host, h->sweep_io_host + MT_N, (size_t)h->G * h->K * sizeof(int32_t));
     if (nnz_updates) *nnz_updates = st.nnz;
     hgibbs_sweep_stats& s = h->stats;
     s = hgibbs_sweep_stats{};
@@ -1697,8 +1762,8 @@ static int sweep_resident(hgibbs_ctx* h, const SweepPlan& pl, const double r0[2]
     }
     if (timing) {
         auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-        std::fprintf(stderr, "[hgibbs] resident sweep: host until the kernel is back %.3f ms (device %.3f), results + drift %.3f\n", ms(t_0, t_kernel), (double)s.device_ms,
-                     ms(t_kernel, std::chrono::steady_clock::now()));
+        std::fprintf(stderr, "[hgibbs] resident sweep: launch preparation %.3f ms, kernel wait %.3f ms (device %.3f), results + drift %.3f\n", ms(t_0, t_launch), ms(t_launch, t_kernel),
+                     (double)s.device_ms, ms(t_kernel, std::chrono::steady_clock::now()));
     }
     return 0;
 }
@@ -1953,8 +2018,6 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
     if (compute_stats(h)) return 1;
     const int G = h->G, K = h->K;
     const uint32_t M = h->M;
-    for (uint32_t i = 0; i < M; ++i)
-        if (order_host[i] < 0 || (uint32_t)order_host[i] >= M) return fail("hgibbs_sweep: order[%u]=%d outside [0,%u)", i, order_host[i], M);
     if (rng->idx > (uint32_t)MT_N) return fail("hgibbs_sweep: rng idx %u > 624", rng->idx);
 
     // per-sweep hyper tables (the marker-independent factors of src/BayesRRm.cpp:1721-1723,1750,1875,1901)
@@ -1976,26 +2039,51 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
             }
         }
     }
+    // order and adaV travel through pinned staging in the handle; adaV only when it differs from what the device holds (it changes
+    // when a group is switched off, and the caller owns the pointer: compared, not assumed)
+    const size_t io_words = (size_t)MT_N + (size_t)G * K + 1;
+    if (h->sweep_io_words != io_words) {
+        if (h->sweep_io_host) HIP_TRY(hipHostFree(h->sweep_io_host));
+        h->sweep_io_host = nullptr;
+        HIP_TRY(hipHostMalloc(&h->sweep_io_host, io_words * sizeof(uint32_t)));
+        h->sweep_io_words = io_words;
+    }
+    if (!h->order_host) HIP_TRY(hipHostMalloc(&h->order_host, (size_t)M * sizeof(int32_t)));
+    if (!h->adaV_host) HIP_TRY(hipHostMalloc(&h->adaV_host, (size_t)M));
+    uint32_t* const order_bad_host = h->sweep_io_host + MT_N + (size_t)G * K;
     HIP_TRY(hipMemcpyAsync(h->tables, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->order, order_host, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->adaV, adaV_host, (size_t)M, hipMemcpyHostToDevice, h->stream));
+    std::memcpy(h->order_host, order_host, (size_t)M * sizeof(int32_t));
+    HIP_TRY(hipMemcpyAsync(h->order, h->order_host, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    if (!h->adaV_on_device || std::memcmp(h->adaV_host, adaV_host, (size_t)M) != 0) {
+        std::memcpy(h->adaV_host, adaV_host, (size_t)M);
+        HIP_TRY(hipMemcpyAsync(h->adaV, h->adaV_host, (size_t)M, hipMemcpyHostToDevice, h->stream));
+        h->res_all_ada = std::memchr(adaV_host, 0, (size_t)M) == nullptr;
+        h->adaV_on_device = true;
+    }
     HIP_TRY(hipMemcpyAsync(h->mt, rng->x, MT_N * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemsetAsync(h->cass, 0, (size_t)G * K * sizeof(int32_t), h->stream));
     HIP_TRY(hipMemsetAsync(h->ticket, 0, (16 + MAX_GROUPS + 256) * sizeof(uint32_t), h->stream));
     HIP_TRY(hipMemsetAsync(h->aticket, 0, (AHEAD_MAX / 2 + 4) * sizeof(uint32_t), h->stream));
+    HIP_TRY(hipMemsetAsync(h->order_bad, 0xff, sizeof(uint32_t), h->stream));
     k_gather_meta<<<(M + 255) / 256, 256, 0, h->stream>>>(h->order, h->mave, h->mstd, h->beta, h->groups, h->adaV, h->counts, h->s_mave, h->s_mstd,
-                                                       h->s_bold, h->s_ga, M);
+                                                       h->s_bold, h->s_ga, M, h->order_bad);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(h->stream)); // staging buffers are on the host stack / pageable
-    h->res_all_ada = std::memchr(adaV_host, 0, (size_t)M) == nullptr;
-    if (std::getenv("HGIBBS_TIMING"))
-        std::fprintf(stderr, "[hgibbs] sweep preparation (checks, tables, order / adaV upload, metadata gather) %.3f ms\n",
-                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_prep0).count());
+    HIP_TRY(hipMemcpyAsync(order_bad_host, h->order_bad, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    const auto t_prep1 = std::chrono::steady_clock::now();
 
     // (sum, sum of squares) of eps over all individuals at sweep start, for whichever engine runs; it also refreshes the bound on
-    // max |eps| the plan's form of the streaming workgroups depends on
+    // max |eps| the plan's form of the streaming workgroups depends on.  Enqueued behind the uploads and the gather: its
+    // synchronise is the preparation's only one (the tables and the generator words are on the host stack / pageable until then)
     double r0[2];
     if (reduce_eps_all(h, r0)) return 1;
+    if (*order_bad_host != 0xffffffffu) {
+        // nothing but the sweep's scratch has been written so far
+        const uint32_t i = *order_bad_host;
+        return fail("hgibbs_sweep: order[%u]=%d outside [0,%u)", i, order_host[i], M);
+    }
+    if (std::getenv("HGIBBS_TIMING"))
+        std::fprintf(stderr, "[hgibbs] sweep preparation: host work and enqueue (tables, order / adaV staging) %.3f ms, wait for uploads, metadata gather and opening reduction %.3f ms\n",
+                     std::chrono::duration<double, std::milli>(t_prep1 - t_prep0).count(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_prep1).count());
 
     // which engine runs this sweep
     SweepPlan plan = plan_sweep(h);

@@ -199,7 +199,7 @@ int hydra_chain_iterate(hydra_chain_t c)
     const auto t_mu = tnow();
     // :1691-1694
     if (c->shuffle) {
-        hg::shuffle_libstdcxx6(c->order.data(), c->order.size(), gen);
+        hg::shuffle_libstdcxx6_fast(c->order.data(), c->order.size(), gen);
     }
     std::fill(c->m0.begin(), c->m0.end(), 0);
     const auto t_shuffle = tnow();
@@ -237,7 +237,7 @@ int hydra_chain_iterate(hydra_chain_t c)
 
     // :2646-2681 fixed effects: one conditional normal per covariate, shuffled order
     if (c->C > 0) {
-        hg::shuffle_libstdcxx6(c->xI.data(), c->xI.size(), gen);
+        hg::shuffle_libstdcxx6_fast(c->xI.data(), c->xI.size(), gen);
         const double sigmaF = 1.0; // s02F, src/BayesRRm.h:34 (sigmaF = s02F, :2680)
         const double sigE_sigF = c->sigmaE / sigmaF;
         const double dNm1 = (double)(c->N - 1);
@@ -330,6 +330,16 @@ int hydra_rng_from_boost_words(const uint32_t* words624, hgibbs_rng_state* st)
     if (!st || !words624) return cfail("hydra_rng_from_boost_words: null argument");
     std::memcpy(st->x, words624, 624 * sizeof(uint32_t));
     st->idx = 624; // mt.i = mt.state_size
+    return 0;
+}
+
+int hydra_rng_shuffle(hgibbs_rng_state* st, int32_t* v, uint32_t n)
+{
+    if (!st || (n && !v)) return cfail("hydra_rng_shuffle: null argument");
+    if (st->idx > (uint32_t)hg::MT_N) return cfail("hydra_rng_shuffle: rng idx > 624");
+    hg::Mt gen{st->x, st->idx};
+    hg::shuffle_libstdcxx6_fast(v, (size_t)n, gen);
+    st->idx = gen.idx;
     return 0;
 }
 

@@ -243,7 +243,7 @@ int hydraw_chain_iterate(hydraw_chain_t c)
     }
     // 1a. fixed effects, :1365-1415
     if (c->C > 0) {
-        hg::shuffle_libstdcxx6(c->xI.data(), c->xI.size(), gen);
+        hg::shuffle_libstdcxx6_fast(c->xI.data(), c->xI.size(), gen);
         for (int i = 0; i < c->C; ++i) {
             const int col = (int)c->xI[i];
             const double gamma_old = c->gamma[col];
@@ -270,7 +270,7 @@ int hydraw_chain_iterate(hydraw_chain_t c)
     if (hgibbs_w_refresh_vi(c->dev, c->alpha)) return 1; // :1457-1459
 
     if (c->shuffle) { // :1461-1463
-        hg::shuffle_libstdcxx6(c->order.data(), c->order.size(), gen);
+        hg::shuffle_libstdcxx6_fast(c->order.data(), c->order.size(), gen);
     }
     std::fill(c->m0.begin(), c->m0.end(), 0);
     c->rng.idx = gen.idx;

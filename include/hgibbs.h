@@ -475,6 +475,9 @@ int hydra_chain_restore(hydra_chain_t c, const hydra_restart_state* st);
  * src/distributions_boost.cpp:38-44) and back (`file >> rng`, :46-55) */
 int hydra_rng_to_boost_words(const hgibbs_rng_state* st, uint32_t* words624);
 int hydra_rng_from_boost_words(const uint32_t* words624, hgibbs_rng_state* st);
+/* the chain's shuffle of the marker order (std::shuffle as the reference binary runs it, src/BayesRRm.cpp:1692) on a
+ * caller's generator state and array: v[0..n) permuted, st advanced by the words the shuffle consumed */
+int hydra_rng_shuffle(hgibbs_rng_state* st, int32_t* v, uint32_t n);
 /* markers with deltaBeta != 0 in the last sweep */
 uint64_t hydra_chain_last_nnz(hydra_chain_t c);
 
