@@ -23,7 +23,7 @@ ABI_SYMBOLS = [
     "hydra_chain_destroy", "hydra_chain_iterate", "hydra_chain_state", "hydra_chain_csv_line", "hydra_chain_order",
     "hydra_chain_last_nnz", "hgibbs_score", "hgibbs_last_score_ms", "hgibbs_ld", "hgibbs_last_ld_ms",
     "hgibbs_marker_dots", "hgibbs_last_marker_dots_ms", "hgibbs_king", "hgibbs_king_pairs", "hgibbs_king_pairs_get", "hgibbs_last_king_ms",
-    "hgibbs_pca", "hgibbs_last_pca_ms",
+    "hgibbs_pca", "hgibbs_last_pca_ms", "hgibbs_region_var", "hgibbs_last_region_var_ms",
     # BayesW
     "hgibbs_grand_seed", "hgibbs_grand_next", "hgibbs_ars_sample", "hgibbs_w_init", "hgibbs_w_marker_stats", "hgibbs_w_set_model",
     "hgibbs_w_reduce", "hgibbs_w_refresh_vi", "hgibbs_w_get_vi", "hgibbs_w_marker_sums", "hgibbs_w_sweep", "hgibbs_w_last_sweep_stats", "hgibbs_w_ars_device_probe",
@@ -198,6 +198,8 @@ def lib():
     L.hgibbs_last_king_ms.argtypes = [vp, dp]
     L.hgibbs_pca.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double, dp, C.c_uint64, dp, dp, dp, C.POINTER(PcaReport)]
     L.hgibbs_last_pca_ms.argtypes = [vp, dp]
+    L.hgibbs_region_var.argtypes = [vp, C.c_int, dp, dp, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), dp, dp]
+    L.hgibbs_last_region_var_ms.argtypes = [vp, dp]
     _lib = L
     return L
 
@@ -399,6 +401,33 @@ class Device:
     def last_score_ms(self):
         v = C.c_double()
         check(self.L.hgibbs_last_score_ms(self.h, C.byref(v)))
+        return v.value
+
+    def region_var(self, a, o, sets):
+        """(S, M) weights a, o and a list of marker index arrays (each strictly increasing) -> (mean, var), both (nsets, S): mean and
+        ddof = 1 variance over the rows of sum_{j in set} [g_ij not missing] (a_sj g_ij + o_sj) (hgibbs_region_var)."""
+        a = np.ascontiguousarray(np.atleast_2d(a), dtype=np.float64)
+        o = np.ascontiguousarray(np.atleast_2d(o), dtype=np.float64)
+        if a.shape != o.shape or a.shape[1] != self.M:
+            raise ValueError("a and o must both be (S, %d)" % self.M)
+        sets = [np.asarray(r, dtype=np.int64).ravel() for r in sets]
+        for r in sets:
+            if r.size and (r.min() < 0 or r.max() > 0xFFFFFFFF):
+                raise ValueError("a marker index does not fit in 32 bits")
+        off = np.zeros(len(sets) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([r.size for r in sets], dtype=np.uint64)
+        idx = np.ascontiguousarray(np.concatenate(sets) if sets else np.zeros(0), dtype=np.uint32)
+        if idx.size == 0:
+            idx = np.zeros(1, dtype=np.uint32)  # (a pointer to pass; off says that nothing is read)
+        mean = np.zeros((len(sets), a.shape[0]))
+        var = np.zeros((len(sets), a.shape[0]))
+        check(self.L.hgibbs_region_var(self.h, a.shape[0], _dp(a), _dp(o), len(sets), off.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                       idx.ctypes.data_as(C.POINTER(C.c_uint32)), _dp(mean), _dp(var)))
+        return mean, var
+
+    def last_region_var_ms(self):
+        v = C.c_double()
+        check(self.L.hgibbs_last_region_var_ms(self.h, C.byref(v)))
         return v.value
 
     def ld(self, W, m0=0, count=None, r=True, sums=True):

@@ -200,6 +200,8 @@ struct hgibbs_ctx {
     double mdots_ms = 0.0; // device time of the last hgibbs_marker_dots (scales, digits, products, rounding)
     int king_split = 0;    // option king_split: ranges of markers the workgroups of hgibbs_king split the k dimension into (0 = automatic)
     double king_ms = 0.0;  // device time of the last hgibbs_king / hgibbs_king_pairs (image, zeroing, products, every run of the list)
+    int rvar_kb_max = 0;   // option rvar_kb_max: a marker set of more blocks of 64 than this takes hgibbs_region_var's large-set path (0 = SC_KB_MAX)
+    double rvar_ms = 0.0;  // device time of the last hgibbs_region_var (scales, digits, products and epilogue, the large sets' scores, mean and var)
     double pca_ms[5] = {0, 0, 0, 0, 0}; // device time of the last hgibbs_pca: whole call, X'Q products, X T products, panel algebra of the iterations, the rest
     std::vector<uint32_t> king_ab;    // the last hgibbs_king_pairs list, sorted by (a, b): a, b per pair
     std::vector<int32_t> king_counts; // NSNP, HET_a, HET_b, HETHET, IBS0 per pair
@@ -1287,6 +1289,9 @@ int hgibbs_set_option(hgibbs_t h, const char* name, int64_t value)
     } else if (!std::strcmp(name, "mdots_split")) {
         if (value < 0 || value > 65535) return fail("mdots_split must be in [0,65535] (0 = automatic)");
         h->mdots_split = (int)value;
+    } else if (!std::strcmp(name, "rvar_kb_max")) {
+        if (value < 0 || value > 32768) return fail("rvar_kb_max must be in [0,32768] (0 = the i32 headroom, 32768 blocks of 64 markers)");
+        h->rvar_kb_max = (int)value;
     } else if (!std::strcmp(name, "score_ranges")) {
         if (value < 0 || value > 65535) return fail("score_ranges must be in [0,65535] (0 = automatic)");
         h->score_ranges = (int)value;
@@ -2131,6 +2136,7 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
 #include "hg_bayesw.hip.h"
 #include "hg_ops.hip.h"
 #include "hg_score.hip.h"
+#include "hg_rvar.hip.h"
 #include "hg_ld.hip.h"
 #include "hg_mdots.hip.h"
 #include "hg_king.hip.h"

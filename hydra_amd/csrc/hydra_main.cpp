@@ -34,6 +34,12 @@
 // computes the K leading principal components of the chain's rows with hgibbs_pca (run_pca), seeded by --seed,
 // and writes <dir>/<name>.eigenvec (or F), .eigenval, a .cov file that --covariates reads as it stands and, with --pca-loadings, .var.
 //
+// `--pve [--pve-window-kb KB | --pve-window-snps W | --pve-sets F | --pve-groups] [--pve-threshold T] [--pve-out F] [--pve-bin]` appended
+// to a bayesMPI command line samples nothing either: for every marker set (one per chromosome when none is defined) and every .bet record
+// at or after --burn-in it takes the variance over the chain's rows of the set's genetic value with hgibbs_region_var (run_pve,
+// DESIGN.md section 18) and writes posterior mean and sd of the variance explained, its share of the genetic variance and the window
+// posterior probability of association to <dir>/<name>.pve (or F), and with --pve-bin the variances themselves to <out>.bin.
+//
 // Not reproduced (out of scope for the hot path): sparse
 // file formats, bayesFH, marker-sharded MPI, the .lst/tarball.
 // Multi-GPU: one process per GPU (RANK/WORLD_SIZE/LOCAL_RANK in the
@@ -42,6 +48,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdint>
@@ -88,6 +95,8 @@ struct Options { // src/options.hpp:20-138 (subset that reaches bayesMPI)
     std::string kingCutoff = "0.0442", kingOut;      // --king-cutoff T (checked before the device), --king-out
     bool pca = false, pcaLoadings = false, pcaItersGiven = false, pcaTolGiven = false, pcaOutGiven = false; // --pca K; which --pca-* were given
     std::string pcaK, pcaIters, pcaTol, pcaOut;      // --pca K, --pca-iters P, --pca-tol T as given (checked before the device), --pca-out
+    bool pve = false, pveKbGiven = false, pveSnpsGiven = false, pveGroups = false, pveThresholdGiven = false, pveBin = false; // --pve; which --pve-* were given
+    std::string pveKb, pveSnps, pveSets, pveThreshold, pveOut; // --pve-window-kb KB, --pve-window-snps W, --pve-threshold T as given, --pve-sets, --pve-out
     int batch = 0, cpg = 0; // tuning knobs of this build (not hydra's)
 };
 
@@ -239,6 +248,20 @@ Options parse(int argc, const char* argv[])
             o.pcaOut = need(i);
             o.pcaOutGiven = true;
         } else if (a == "--pca-loadings") o.pcaLoadings = true;
+        else if (a == "--pve") o.pve = true;
+        else if (a == "--pve-window-kb") {
+            o.pveKb = need(i);
+            o.pveKbGiven = true;
+        } else if (a == "--pve-window-snps") {
+            o.pveSnps = need(i);
+            o.pveSnpsGiven = true;
+        } else if (a == "--pve-sets") o.pveSets = need(i);
+        else if (a == "--pve-groups") o.pveGroups = true;
+        else if (a == "--pve-threshold") {
+            o.pveThreshold = need(i);
+            o.pveThresholdGiven = true;
+        } else if (a == "--pve-out") o.pveOut = need(i);
+        else if (a == "--pve-bin") o.pveBin = true;
         else if (a == "--sparse-dir" || a == "--sparse-basename" ||
                  a == "--bed-to-sparse" || a == "--sparse-sync" || a == "--bed-sync")
             fatal("FATAL  : option " + a + " belongs to a part of hydra this build does not reproduce (SURVEY.md section 2)");
@@ -1523,16 +1546,226 @@ int run_pca(const Options& opt, const Cohort& co)
     return 0;
 }
 
+// ---- --pve: posterior variance explained by marker sets ----
+struct PveSets {
+    std::vector<std::string> name;
+    std::vector<std::vector<uint32_t>> idx; // markers of each set, increasing
+    std::string how;                        // how the sets were defined, for the report
+};
+
+PveSets pve_sets(const Options& opt, const BimRows& bim, unsigned Mtot)
+{
+    PveSets ps;
+    auto add = [&](const std::string& name) {
+        ps.name.push_back(name);
+        ps.idx.emplace_back();
+        return ps.idx.size() - 1;
+    };
+    if (opt.pveKbGiven) {
+        double kb = 0.0;
+        whole_num(opt.pveKb, kb);
+        ps.how = "windows of " + opt.pveKb + " kb";
+        std::map<std::pair<std::string, long long>, size_t> at;
+        for (unsigned j = 0; j < Mtot; ++j) {
+            const long long w = (long long)std::floor((double)bim.bp[j] / (1000.0 * kb));
+            auto it = at.find({bim.chr[j], w});
+            if (it == at.end()) it = at.emplace(std::make_pair(bim.chr[j], w), add(bim.chr[j] + ":" + std::to_string(w))).first;
+            ps.idx[it->second].push_back(j);
+        }
+    } else if (opt.pveSnpsGiven) {
+        long W = 0;
+        whole_int(opt.pveSnps, W);
+        ps.how = "windows of " + opt.pveSnps + " markers";
+        unsigned run0 = 0;
+        for (unsigned j = 0; j < Mtot; ++j) {
+            if (j && bim.chr[j] != bim.chr[j - 1]) run0 = j;
+            if ((j - run0) % (unsigned long)W == 0) {
+                unsigned last = j; // the window ends with its run or after W markers
+                while (last + 1 < Mtot && last + 1 - j < (unsigned long)W && bim.chr[last + 1] == bim.chr[j]) ++last;
+                add(bim.chr[j] + ":" + std::to_string(j + 1) + "-" + std::to_string(last + 1));
+            }
+            ps.idx.back().push_back(j);
+        }
+    } else if (!opt.pveSets.empty()) {
+        ps.how = "from " + opt.pveSets;
+        std::ifstream in(opt.pveSets);
+        if (!in) fatal("Error: can not open the file [" + opt.pveSets + "] to read.");
+        std::map<std::string, uint32_t> snp;
+        for (unsigned j = 0; j < Mtot; ++j) snp.emplace(bim.id[j], j);
+        std::map<std::string, size_t> at;
+        std::map<std::pair<size_t, uint32_t>, int> seen;
+        std::string line;
+        size_t lineno = 0;
+        while (std::getline(in, line)) {
+            ++lineno;
+            const std::vector<std::string> col = tokens(line, " \t\r");
+            if (col.empty()) continue;
+            const std::string where = "FATAL  : " + opt.pveSets + " line " + std::to_string(lineno) + ": ";
+            if (col.size() != 2) fatal(where + "expected SETNAME SNPID");
+            const auto j = snp.find(col[1]);
+            if (j == snp.end()) fatal(where + "SNP " + col[1] + " is not among the first " + std::to_string(Mtot) + " markers of " + opt.bedFile + ".bim");
+            auto it = at.find(col[0]);
+            if (it == at.end()) it = at.emplace(col[0], add(col[0])).first;
+            if (!seen.emplace(std::make_pair(it->second, j->second), 1).second) fatal(where + "SNP " + col[1] + " is given twice for set " + col[0]);
+            ps.idx[it->second].push_back(j->second);
+        }
+        if (ps.idx.empty()) fatal("FATAL  : " + opt.pveSets + " names no set");
+        for (auto& r : ps.idx) std::sort(r.begin(), r.end());
+    } else if (opt.pveGroups) {
+        ps.how = "the groups of " + opt.groupIndexFile;
+        const std::vector<int32_t> groups = read_groups(opt.groupIndexFile);
+        if (groups.size() < Mtot) fatal("FATAL  : group file covers fewer markers than --number-markers");
+        std::map<int32_t, size_t> at; // in ascending order of the group's number
+        for (unsigned j = 0; j < Mtot; ++j) at.emplace(groups[j], 0);
+        for (auto& g : at) g.second = add("group" + std::to_string(g.first));
+        for (unsigned j = 0; j < Mtot; ++j) ps.idx[at[groups[j]]].push_back(j);
+    } else {
+        ps.how = "one per chromosome";
+        std::map<std::string, size_t> at;
+        for (unsigned j = 0; j < Mtot; ++j) {
+            auto it = at.find(bim.chr[j]);
+            if (it == at.end()) it = at.emplace(bim.chr[j], add("chr" + bim.chr[j])).first;
+            ps.idx[it->second].push_back(j);
+        }
+    }
+    return ps;
+}
+
+int run_pve(const Options& opt, const Cohort& co)
+{
+    const std::string base = opt.mcmcOutDir + "/" + opt.mcmcOutNam;
+    const std::string out = opt.pveOut.empty() ? base + ".pve" : opt.pveOut;
+    const unsigned M = co.Mtot, N = co.Ntot;
+    const BimRows bim = read_bim(opt.bedFile + ".bim", M);
+    PveSets ps = pve_sets(opt, bim, M);
+    const size_t nsets = ps.idx.size();
+    std::vector<unsigned> its;
+    std::vector<double> betas;
+    read_bet_records(base + ".bet", M, opt.burnin, its, betas, "--pve takes the variance explained from the chain's effects");
+    const size_t S = its.size();
+    double T = 1.0 / (double)nsets;
+    if (opt.pveThresholdGiven) whole_num(opt.pveThreshold, T);
+    std::printf("PVE    : %zu sets (%s), %u markers, %u individuals, %zu records of %s (iterations %u .. %u), threshold %g -> %s\n", nsets, ps.how.c_str(), M,
+                N, S, (base + ".bet").c_str(), its.front(), its.back(), T, out.c_str());
+    std::fflush(stdout);
+    if (N < 2) fatal("FATAL  : --pve needs at least two individuals");
+
+    // the last set: every marker
+    ps.name.push_back("ALL");
+    ps.idx.emplace_back(M);
+    for (unsigned j = 0; j < M; ++j) ps.idx.back()[j] = j;
+    const size_t R = nsets + 1;
+    std::vector<uint64_t> off(R + 1, 0);
+    for (size_t r = 0; r < R; ++r) off[r + 1] = off[r] + ps.idx[r].size();
+    std::vector<uint32_t> idx;
+    idx.reserve(off[R]);
+    for (const auto& r : ps.idx) idx.insert(idx.end(), r.begin(), r.end());
+
+    std::vector<uint8_t> bed = read_bed(opt.bedFile, co.numInds, M);
+    if (opt.pveOut.empty()) make_out_dir(opt);
+    FILE* f = open_out(out, "w");
+    std::fprintf(f, "SET CHR BP_FIRST BP_LAST NSNP PIP PVE_MEAN PVE_SD SHARE_MEAN SHARE_SD WPPA\n");
+    FILE* fb = opt.pveBin ? open_out(out + ".bin", "wb") : nullptr;
+
+    // the chain's rows and standardisation; the records in chunks of at most 32
+    hgibbs_t dev = open_training(co, bed);
+    std::vector<double> mave(M), mstd(M);
+    hg_check(hgibbs_marker_stats(dev, mave.data(), mstd.data(), nullptr, nullptr, nullptr), "hgibbs_marker_stats");
+    std::vector<double> var(R * S); // set-major
+    double ms = 0.0;
+    const size_t CH = 32;
+    std::vector<double> a(CH * M), o(CH * M), mean(R * CH), v(R * CH);
+    for (size_t s0 = 0; s0 < S; s0 += CH) {
+        const size_t ns = std::min(CH, S - s0);
+        for (size_t s = 0; s < ns; ++s)
+            for (unsigned j = 0; j < M; ++j) {
+                const double b = betas[(s0 + s) * M + j];
+                const bool live = b != 0.0 && std::isfinite(mstd[j]);
+                a[s * M + j] = live ? b * mstd[j] : 0.0;
+                o[s * M + j] = live ? -b * mstd[j] * mave[j] : 0.0;
+            }
+        hg_check(hgibbs_region_var(dev, (int)ns, a.data(), o.data(), (uint32_t)R, off.data(), idx.data(), mean.data(), v.data()), "hgibbs_region_var");
+        double t = 0.0;
+        hg_check(hgibbs_last_region_var_ms(dev, &t), "hgibbs_last_region_var_ms");
+        ms += t;
+        for (size_t r = 0; r < R; ++r)
+            for (size_t s = 0; s < ns; ++s) var[r * S + s0 + s] = v[r * ns + s];
+    }
+    hgibbs_destroy(dev);
+
+    if (fb) {
+        const uint32_t hd[2] = {(uint32_t)R, (uint32_t)S};
+        if (std::fwrite(hd, sizeof(uint32_t), 2, fb) != 2 || std::fwrite(var.data(), sizeof(double), var.size(), fb) != var.size())
+            fatal("FATAL  : short write on " + out + ".bin");
+        close_out(fb, out + ".bin");
+    }
+    auto num = [&](double x, bool na) {
+        if (na) std::fprintf(f, " NA");
+        else std::fprintf(f, " %.12g", x);
+    };
+    auto mean_sd = [&](const std::vector<double>& x, double& m, double& sd) {
+        m = 0.0;
+        for (double y : x) m += y;
+        m /= (double)x.size();
+        sd = 0.0;
+        for (double y : x) sd += (y - m) * (y - m);
+        sd = x.size() > 1 ? std::sqrt(sd / (double)(x.size() - 1)) : 0.0;
+    };
+    std::vector<double> pve(S), share(S);
+    for (size_t r = 0; r < R; ++r) {
+        const std::vector<uint32_t>& set = ps.idx[r];
+        bool one_chr = !set.empty();
+        long long bp0 = 0, bp1 = 0;
+        for (size_t k = 0; k < set.size(); ++k) {
+            const uint32_t j = set[k];
+            if (bim.chr[j] != bim.chr[set[0]]) one_chr = false;
+            bp0 = k ? std::min(bp0, bim.bp[j]) : bim.bp[j];
+            bp1 = k ? std::max(bp1, bim.bp[j]) : bim.bp[j];
+        }
+        size_t nin = 0, nabove = 0;
+        for (size_t s = 0; s < S; ++s) {
+            bool in = false;
+            for (const uint32_t j : set)
+                if (betas[s * M + j] != 0.0) {
+                    in = true;
+                    break;
+                }
+            nin += in;
+            const double all = var[nsets * S + s];
+            pve[s] = var[r * S + s];
+            share[s] = all != 0.0 ? pve[s] / all : 0.0;
+            nabove += share[s] > T;
+        }
+        double pm, psd, sm, ssd;
+        mean_sd(pve, pm, psd);
+        mean_sd(share, sm, ssd);
+        std::fprintf(f, "%s", ps.name[r].c_str());
+        if (one_chr) std::fprintf(f, " %s %lld %lld", bim.chr[set[0]].c_str(), bp0, bp1);
+        else std::fprintf(f, " NA NA NA");
+        std::fprintf(f, " %zu", set.size());
+        num((double)nin / (double)S, false);
+        num(pm, false);
+        num(psd, S < 2);
+        num(sm, false);
+        num(ssd, S < 2);
+        num((double)nabove / (double)S, false);
+        std::fprintf(f, "\n");
+    }
+    close_out(f, out);
+    std::printf("PVE    : wrote %zu rows to %s (%.3f ms on the device)\n", R, out.c_str(), ms);
+    return 0;
+}
+
 // ---- the analysis modes -------------------------------------------------------
 // An analysis mode is an option that, appended to a bayesMPI command line, samples nothing and runs one analysis on the chain's rows
-// (run_predict .. run_pca above).  What the modes share is refused in one place, from one row per mode.
+// (run_predict .. run_pve above).  What the modes share is refused in one place, from one row per mode.
 struct Mode {
     const char* flag;   // the option that asks for the mode
     bool given;
     const char* wmpi;   // how it refuses --mpibayes bayesWMPI, after its flag
     const char* orphan; // the first of its dependent options that was given: they need the mode (null: none was)
 };
-enum { PREDICT, LD, ASSOC, KING, PCA, NMODES }; // the order in which a mode names the earlier ones it cannot be combined with
+enum { PREDICT, LD, ASSOC, KING, PCA, PVE, NMODES }; // the order in which a mode names the earlier ones it cannot be combined with
 
 const char* first_given(std::initializer_list<std::pair<const char*, bool>> deps)
 {
@@ -1569,6 +1802,23 @@ void check_pca_args(const Options& opt)
         fatal("FATAL  : --pca-tol " + opt.pcaTol + ": the tolerance must be a finite number >= 0");
 }
 
+void check_pve_args(const Options& opt)
+{
+    const char* const definer[4] = {"--pve-window-kb", "--pve-window-snps", "--pve-sets", "--pve-groups"};
+    const bool given[4] = {opt.pveKbGiven, opt.pveSnpsGiven, !opt.pveSets.empty(), opt.pveGroups};
+    for (int x = 0; x < 4; ++x)
+        for (int y = x + 1; y < 4; ++y)
+            if (given[x] && given[y]) fatal(std::string("FATAL  : ") + definer[x] + " cannot be combined with " + definer[y] + ": one way to define the sets");
+    long w = 0;
+    double t = 0.0;
+    if (opt.pveKbGiven && (!whole_num(opt.pveKb, t) || !std::isfinite(t) || !(t > 0.0)))
+        fatal("FATAL  : --pve-window-kb " + opt.pveKb + ": the window must be a finite number of kilobases > 0");
+    if (opt.pveSnpsGiven && (!whole_int(opt.pveSnps, w) || w < 1)) fatal("FATAL  : --pve-window-snps " + opt.pveSnps + ": the window must be an integer >= 1");
+    if (opt.pveThresholdGiven && (!whole_num(opt.pveThreshold, t) || !std::isfinite(t) || t < 0.0 || t >= 1.0))
+        fatal("FATAL  : --pve-threshold " + opt.pveThreshold + ": the threshold must be a finite number in [0, 1)");
+    if (opt.pveGroups && opt.groupIndexFile.empty()) fatal("FATAL  : --pve-groups needs --groupIndexFile");
+}
+
 // Every refusal of the modes, before anything is read: mode by mode (--ld-window first, then in the table's order), what all share,
 // then the mode's own arguments
 void check_modes(const Options& opt, int nranks)
@@ -1583,8 +1833,11 @@ void check_modes(const Options& opt, int nranks)
         {"--king", opt.king, takes, first_given({{"--king-out", !opt.kingOut.empty()}, {"--king-cutoff", opt.kingCutoffGiven}})},
         {"--pca", opt.pca, takes,
          first_given({{"--pca-iters", opt.pcaItersGiven}, {"--pca-tol", opt.pcaTolGiven}, {"--pca-out", opt.pcaOutGiven}, {"--pca-loadings", opt.pcaLoadings}})},
+        {"--pve", opt.pve, takes,
+         first_given({{"--pve-window-kb", opt.pveKbGiven}, {"--pve-window-snps", opt.pveSnpsGiven}, {"--pve-sets", !opt.pveSets.empty()}, {"--pve-groups", opt.pveGroups},
+                      {"--pve-threshold", opt.pveThresholdGiven}, {"--pve-out", !opt.pveOut.empty()}, {"--pve-bin", opt.pveBin}})},
     };
-    for (const int i : {LD, PREDICT, ASSOC, KING, PCA}) {
+    for (const int i : {LD, PREDICT, ASSOC, KING, PCA, PVE}) {
         const Mode& m = modes[i];
         const std::string flag = m.flag;
         if (!m.given) {
@@ -1599,6 +1852,7 @@ void check_modes(const Options& opt, int nranks)
         if (i == LD) check_ld_args(opt);
         if (i == KING) check_king_args(opt);
         if (i == PCA) check_pca_args(opt);
+        if (i == PVE) check_pve_args(opt);
     }
 }
 
@@ -1660,6 +1914,7 @@ int main(int argc, const char* argv[])
     if (opt.assoc) return run_assoc(opt, co, y, covX, C);
     if (opt.king) return run_king(opt, co);
     if (opt.pca) return run_pca(opt, co);
+    if (opt.pve) return run_pve(opt, co);
 
     std::vector<int32_t> groups;
     std::vector<std::vector<double>> mS;

@@ -243,6 +243,32 @@ int hgibbs_score(hgibbs_t h, int S, const double* a, const double* o, double* ou
 /* device time of the last hgibbs_score in ms: every kernel of the call (scales, digits, products, rounding), not the host copies */
 int hgibbs_last_score_ms(hgibbs_t h, double* ms);
 
+/* ---- mean and variance of the scores of marker sets */
+/* For the BED on the handle, S weight vectors (a, o: S x M as in hgibbs_score) and nsets marker sets
+ * (set r = markers idx[off[r] .. off[r+1]), off[0] = 0, strictly increasing inside a set; sets may overlap, be empty, be scattered):
+ *   v_irs       = sum_{j in set r} [g_ij not missing] (a_sj g_ij + o_sj)          (never stored)
+ *   mean[r*S+s] = (1/n) sum_i v_irs,   var[r*S+s] = sum_i (v_irs - mean)^2 / (n - 1),   n = n_local
+ * Every v_irs is, bit for bit, the value hgibbs_score returns for the same weights with everything outside the set zeroed: the
+ * exact integer digit sums of the weights in fixed point and one rounding.  The scale 2^E is therefore one per (set, sample), from
+ * max_{j in set} max(|a_sj|, |o_sj|), and |v - exact| <= 3 |set| max_{j in set}|w_sj| 2^-52 per entry -- never more than
+ * 3 |set| max|w_s| 2^-52 with the maximum over all of the sample's weights, and as sharp for a set of small effects beside large
+ * ones elsewhere.  With d that bound and B the largest |v| of the pair: |mean - exact| <= d + n eps B, and var, computed as
+ * (sum v^2 - (sum v)^2 / n) / (n - 1) without centring, is off by at most about 2 n / (n - 1) (2 B d + n eps B^2), eps = 2^-53; with the
+ * chain's standardised weights (a = beta mstd, o = -beta mstd mave) the mean is 0 up to rounding and nothing cancels.
+ * The sums over i run in one fixed order (a fixed tree inside a block of 256 rows, then the row blocks in ascending order, no
+ * floating-point atomics): mean and var are bit-identical across repeats, any chunking of S, any order or chunking of the sets, and
+ * every value of the options score_sp and rvar_kb_max.  An empty set gives 0, 0.  var may be NULL.
+ * A set of more than rvar_kb_max blocks of 64 markers (option; 0 = default = 32768 blocks, 2^21 markers, the i32 headroom of the
+ * digit sums) is scored through hgibbs_score's kernels into an n x samples-per-pass buffer and reduced in the same order.
+ * Needs the marker stats (computed here when they are not).  One rank only.  Refused with a message: S <= 0, nsets = 0, n_local < 2,
+ * an index >= M, indices not strictly increasing within a set, a weight that is not finite (in a set or not), buffers that do not
+ * fit in free device memory, and what one call does not take: 2^24 or more blocks of 64 list entries in all (every set rounded up),
+ * more than 65535 x 2^20 pairs of a non-empty set and a block of 256 rows -- pass the sets in several calls. */
+int hgibbs_region_var(hgibbs_t h, int S, const double* a, const double* o, uint32_t nsets, const uint64_t* off, const uint32_t* idx,
+                      double* mean, double* var);
+/* device time of the last hgibbs_region_var in ms: every kernel of the call, not the host copies */
+int hgibbs_last_region_var_ms(hgibbs_t h, double* ms);
+
 /* ---- windowed LD of the loaded markers ------------ */
 /* For markers j in [m0, m0 + count) and d = 1..W (pairs j, j + d with j + d < M, by index):
  *   r_host[(j - m0) * W + d - 1]        = x_j'x_{j+d} / (N - 1)            (NaN where j + d >= M or either mstd is not finite)
