@@ -24,6 +24,7 @@ ABI_SYMBOLS = [
     "hydra_chain_last_nnz", "hgibbs_score", "hgibbs_last_score_ms", "hgibbs_ld", "hgibbs_last_ld_ms",
     "hgibbs_marker_dots", "hgibbs_last_marker_dots_ms", "hgibbs_king", "hgibbs_king_pairs", "hgibbs_king_pairs_get", "hgibbs_last_king_ms",
     "hgibbs_pca", "hgibbs_last_pca_ms", "hgibbs_region_var", "hgibbs_last_region_var_ms",
+    "hgibbs_grm", "hgibbs_grm_info", "hgibbs_last_grm_ms",
     # BayesW
     "hgibbs_grand_seed", "hgibbs_grand_next", "hgibbs_ars_sample", "hgibbs_w_init", "hgibbs_w_marker_stats", "hgibbs_w_set_model",
     "hgibbs_w_reduce", "hgibbs_w_refresh_vi", "hgibbs_w_get_vi", "hgibbs_w_marker_sums", "hgibbs_w_sweep", "hgibbs_w_last_sweep_stats", "hgibbs_w_ars_device_probe",
@@ -200,6 +201,9 @@ def lib():
     L.hgibbs_last_pca_ms.argtypes = [vp, dp]
     L.hgibbs_region_var.argtypes = [vp, C.c_int, dp, dp, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), dp, dp]
     L.hgibbs_last_region_var_ms.argtypes = [vp, dp]
+    L.hgibbs_grm.argtypes = [vp, C.c_uint32, C.c_uint32, dp, C.POINTER(C.c_int32)]
+    L.hgibbs_grm_info.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
+    L.hgibbs_last_grm_ms.argtypes = [vp, dp]
     _lib = L
     return L
 
@@ -491,6 +495,28 @@ class Device:
     def last_king_ms(self):
         v = C.c_double()
         check(self.L.hgibbs_last_king_ms(self.h, C.byref(v)))
+        return v.value
+
+    def grm(self, a0=0, acount=None):
+        """S = X X' and NSNP of rows [a0, a0 + acount), each with its columns 0 .. a (hgibbs_grm): packed 1-D arrays in GCTA's order,
+        float64 S and int32 nsnp; the GCTA entry is S / nsnp."""
+        if acount is None:
+            acount = self.n_local - a0
+        n = sum(a + 1 for a in range(a0, a0 + acount))
+        S = np.zeros(n)
+        nsnp = np.zeros(n, dtype=np.int32)
+        check(self.L.hgibbs_grm(self.h, a0, acount, _dp(S), nsnp.ctypes.data_as(C.POINTER(C.c_int32))))
+        return S, nsnp
+
+    def grm_info(self):
+        """(M_used, E) of the last grm()"""
+        m, e = C.c_uint32(), C.c_int32()
+        check(self.L.hgibbs_grm_info(self.h, C.byref(m), C.byref(e)))
+        return m.value, e.value
+
+    def last_grm_ms(self):
+        v = C.c_double()
+        check(self.L.hgibbs_last_grm_ms(self.h, C.byref(v)))
         return v.value
 
     def pca(self, K, L=None, iters=20, tol=1e-10, Q0=None, seed=1, loadings=False):

@@ -206,6 +206,10 @@ struct hgibbs_ctx {
     std::vector<uint32_t> king_ab;    // the last hgibbs_king_pairs list, sorted by (a, b): a, b per pair
     std::vector<int32_t> king_counts; // NSNP, HET_a, HET_b, HETHET, IBS0 per pair
     std::vector<double> king_kin;     // KINSHIP per pair
+    int grm_split = 0;     // option grm_split: ranges of markers the workgroups of hgibbs_grm split the k dimension into (0 = automatic)
+    double grm_ms = 0.0;   // device time of the last hgibbs_grm (scale, table, image, zeroing, products, rounding)
+    uint32_t grm_used = 0; // M_used and E of the last hgibbs_grm (hgibbs_grm_info)
+    int grm_E = 0;
 };
 
 static int ensure_scratch(hgibbs_ctx* h, size_t n)
@@ -1286,6 +1290,9 @@ int hgibbs_set_option(hgibbs_t h, const char* name, int64_t value)
     } else if (!std::strcmp(name, "king_split")) {
         if (value < 0 || value > 65535) return fail("king_split must be in [0,65535] (0 = automatic)");
         h->king_split = (int)value;
+    } else if (!std::strcmp(name, "grm_split")) {
+        if (value < 0 || value > 65535) return fail("grm_split must be in [0,65535] (0 = automatic)");
+        h->grm_split = (int)value;
     } else if (!std::strcmp(name, "mdots_split")) {
         if (value < 0 || value > 65535) return fail("mdots_split must be in [0,65535] (0 = automatic)");
         h->mdots_split = (int)value;
@@ -2141,3 +2148,4 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
 #include "hg_mdots.hip.h"
 #include "hg_king.hip.h"
 #include "hg_pca.hip.h"
+#include "hg_grm.hip.h"

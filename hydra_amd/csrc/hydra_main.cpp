@@ -40,6 +40,11 @@
 // DESIGN.md section 18) and writes posterior mean and sd of the variance explained, its share of the genetic variance and the window
 // posterior probability of association to <dir>/<name>.pve (or F), and with --pve-bin the variances themselves to <out>.bin.
 //
+// `--grm [--grm-out PREFIX] [--grm-sparse T]` appended to a bayesMPI command line samples nothing either: it computes the genomic
+// relationship matrix of the chain's rows, A = X X' / NSNP on the chain's own standardisation, with hgibbs_grm (run_grm, DESIGN.md
+// section 19) and writes GCTA's PREFIX.grm.id, .grm.bin and .grm.N.bin (PREFIX defaults to <dir>/<name>), and with --grm-sparse the
+// diagonal and the pairs with A >= T to PREFIX.grm.sp.
+//
 // Not reproduced (out of scope for the hot path): sparse
 // file formats, bayesFH, marker-sharded MPI, the .lst/tarball.
 // Multi-GPU: one process per GPU (RANK/WORLD_SIZE/LOCAL_RANK in the
@@ -97,6 +102,8 @@ struct Options { // src/options.hpp:20-138 (subset that reaches bayesMPI)
     std::string pcaK, pcaIters, pcaTol, pcaOut;      // --pca K, --pca-iters P, --pca-tol T as given (checked before the device), --pca-out
     bool pve = false, pveKbGiven = false, pveSnpsGiven = false, pveGroups = false, pveThresholdGiven = false, pveBin = false; // --pve; which --pve-* were given
     std::string pveKb, pveSnps, pveSets, pveThreshold, pveOut; // --pve-window-kb KB, --pve-window-snps W, --pve-threshold T as given, --pve-sets, --pve-out
+    bool grm = false, grmSparseGiven = false;        // --grm: genomic relationship matrix of the chain's rows; --grm-sparse given
+    std::string grmOut, grmSparse;                   // --grm-out PREFIX, --grm-sparse T as given (checked before the device)
     int batch = 0, cpg = 0; // tuning knobs of this build (not hydra's)
 };
 
@@ -262,7 +269,12 @@ Options parse(int argc, const char* argv[])
             o.pveThresholdGiven = true;
         } else if (a == "--pve-out") o.pveOut = need(i);
         else if (a == "--pve-bin") o.pveBin = true;
-        else if (a == "--sparse-dir" || a == "--sparse-basename" ||
+        else if (a == "--grm") o.grm = true;
+        else if (a == "--grm-out") o.grmOut = need(i);
+        else if (a == "--grm-sparse") {
+            o.grmSparse = need(i);
+            o.grmSparseGiven = true;
+        } else if (a == "--sparse-dir" || a == "--sparse-basename" ||
                  a == "--bed-to-sparse" || a == "--sparse-sync" || a == "--bed-sync")
             fatal("FATAL  : option " + a + " belongs to a part of hydra this build does not reproduce (SURVEY.md section 2)");
         else
@@ -1756,16 +1768,85 @@ int run_pve(const Options& opt, const Cohort& co)
     return 0;
 }
 
+// ---- --grm: genomic relationship matrix of the chain's rows ----
+int run_grm(const Options& opt, const Cohort& co)
+{
+    const std::string prefix = opt.grmOut.empty() ? opt.mcmcOutDir + "/" + opt.mcmcOutNam : opt.grmOut;
+    double T = 0.0;
+    if (opt.grmSparseGiven) whole_num(opt.grmSparse, T);
+    const FamIds fam = read_fam_ids(opt.bedFile + ".fam", co.numInds, co.numNAs ? &co.keep : nullptr);
+    const unsigned N = co.Ntot;
+    if (fam.fid.size() != N) fatal("FATAL  : " + opt.bedFile + ".fam: " + std::to_string(fam.fid.size()) + " kept rows, expected " + std::to_string(N));
+    std::vector<uint8_t> bed = read_bed(opt.bedFile, co.numInds, co.Mtot);
+    if (opt.grmOut.empty()) make_out_dir(opt);
+    const std::string idp = prefix + ".grm.id", binp = prefix + ".grm.bin", nbinp = prefix + ".grm.N.bin", spp = prefix + ".grm.sp";
+    FILE* fid = open_out(idp, "w");
+    for (unsigned i = 0; i < N; ++i) std::fprintf(fid, "%s\t%s\n", fam.fid[i].c_str(), fam.iid[i].c_str());
+    close_out(fid, idp);
+    FILE* fb = open_out(binp, "wb");
+    FILE* fn = open_out(nbinp, "wb");
+    FILE* fs = opt.grmSparseGiven ? open_out(spp, "w") : nullptr;
+
+    hgibbs_t dev = open_training(co, bed);
+    // rows in chunks: at most 2^25 pairs (what the device holds at a time) and, with the f32 copies, a quarter of the free host memory
+    const long pages = sysconf(_SC_AVPHYS_PAGES), psz = sysconf(_SC_PAGESIZE);
+    const unsigned long long avail = pages > 0 && psz > 0 ? (unsigned long long)pages * (unsigned long long)psz : (1ull << 30);
+    const unsigned long long cap = std::max<unsigned long long>(1, std::min<unsigned long long>(1ull << 25, avail / 4 / 20));
+    std::vector<double> S;
+    std::vector<int32_t> ns;
+    std::vector<float> fa, fc;
+    double ms = 0.0;
+    unsigned long long pairs = 0, above = 0;
+    uint32_t used = 0;
+    for (unsigned a0 = 0; a0 < N;) {
+        unsigned a1 = a0;
+        unsigned long long n = 0;
+        while (a1 < N && (a1 == a0 || n + a1 + 1ull <= cap)) n += a1++ + 1ull;
+        S.resize(n);
+        ns.resize(n);
+        fa.resize(n);
+        fc.resize(n);
+        hg_check(hgibbs_grm(dev, a0, a1 - a0, S.data(), ns.data()), "hgibbs_grm");
+        double t = 0.0;
+        hg_check(hgibbs_last_grm_ms(dev, &t), "hgibbs_last_grm_ms");
+        ms += t;
+        hg_check(hgibbs_grm_info(dev, &used, nullptr), "hgibbs_grm_info");
+        size_t k = 0;
+        for (unsigned a = a0; a < a1; ++a)
+            for (unsigned b = 0; b <= a; ++b, ++k) {
+                const double A = ns[k] ? S[k] / (double)ns[k] : std::numeric_limits<double>::quiet_NaN(); // the division in f64, one cast
+                fa[k] = (float)A;
+                fc[k] = (float)ns[k];
+                if (fs && (a == b || A >= T)) {
+                    std::fprintf(fs, "%u\t%u\t%.9g\n", a, b, A);
+                    above += a != b;
+                }
+            }
+        if (std::fwrite(fa.data(), sizeof(float), n, fb) != n) fatal("FATAL  : short write on " + binp);
+        if (std::fwrite(fc.data(), sizeof(float), n, fn) != n) fatal("FATAL  : short write on " + nbinp);
+        pairs += n;
+        a0 = a1;
+    }
+    hgibbs_destroy(dev);
+    close_out(fb, binp);
+    close_out(fn, nbinp);
+    if (fs) close_out(fs, spp);
+    std::printf("GRM    : %u rows, %u of %u markers used, %llu entries written to %s (%.3f ms on the device)", N, used, co.Mtot, pairs, binp.c_str(), ms);
+    if (fs) std::printf(", %llu off-diagonal pairs with A >= %g in %s", above, T, spp.c_str());
+    std::printf("\n");
+    return 0;
+}
+
 // ---- the analysis modes -------------------------------------------------------
 // An analysis mode is an option that, appended to a bayesMPI command line, samples nothing and runs one analysis on the chain's rows
-// (run_predict .. run_pve above).  What the modes share is refused in one place, from one row per mode.
+// (run_predict .. run_grm above).  What the modes share is refused in one place, from one row per mode.
 struct Mode {
     const char* flag;   // the option that asks for the mode
     bool given;
     const char* wmpi;   // how it refuses --mpibayes bayesWMPI, after its flag
     const char* orphan; // the first of its dependent options that was given: they need the mode (null: none was)
 };
-enum { PREDICT, LD, ASSOC, KING, PCA, PVE, NMODES }; // the order in which a mode names the earlier ones it cannot be combined with
+enum { PREDICT, LD, ASSOC, KING, PCA, PVE, GRM, NMODES }; // the order in which a mode names the earlier ones it cannot be combined with
 
 const char* first_given(std::initializer_list<std::pair<const char*, bool>> deps)
 {
@@ -1802,6 +1883,13 @@ void check_pca_args(const Options& opt)
         fatal("FATAL  : --pca-tol " + opt.pcaTol + ": the tolerance must be a finite number >= 0");
 }
 
+void check_grm_args(const Options& opt)
+{
+    double t = 0.0;
+    if (opt.grmSparseGiven && (!whole_num(opt.grmSparse, t) || !std::isfinite(t)))
+        fatal("FATAL  : --grm-sparse " + opt.grmSparse + ": the cutoff must be a finite number");
+}
+
 void check_pve_args(const Options& opt)
 {
     const char* const definer[4] = {"--pve-window-kb", "--pve-window-snps", "--pve-sets", "--pve-groups"};
@@ -1836,8 +1924,9 @@ void check_modes(const Options& opt, int nranks)
         {"--pve", opt.pve, takes,
          first_given({{"--pve-window-kb", opt.pveKbGiven}, {"--pve-window-snps", opt.pveSnpsGiven}, {"--pve-sets", !opt.pveSets.empty()}, {"--pve-groups", opt.pveGroups},
                       {"--pve-threshold", opt.pveThresholdGiven}, {"--pve-out", !opt.pveOut.empty()}, {"--pve-bin", opt.pveBin}})},
+        {"--grm", opt.grm, takes, first_given({{"--grm-out", !opt.grmOut.empty()}, {"--grm-sparse", opt.grmSparseGiven}})},
     };
-    for (const int i : {LD, PREDICT, ASSOC, KING, PCA, PVE}) {
+    for (const int i : {LD, PREDICT, ASSOC, KING, PCA, PVE, GRM}) {
         const Mode& m = modes[i];
         const std::string flag = m.flag;
         if (!m.given) {
@@ -1853,6 +1942,7 @@ void check_modes(const Options& opt, int nranks)
         if (i == KING) check_king_args(opt);
         if (i == PCA) check_pca_args(opt);
         if (i == PVE) check_pve_args(opt);
+        if (i == GRM) check_grm_args(opt);
     }
 }
 
@@ -1915,6 +2005,7 @@ int main(int argc, const char* argv[])
     if (opt.king) return run_king(opt, co);
     if (opt.pca) return run_pca(opt, co);
     if (opt.pve) return run_pve(opt, co);
+    if (opt.grm) return run_grm(opt, co);
 
     std::vector<int32_t> groups;
     std::vector<std::vector<double>> mS;

@@ -349,6 +349,32 @@ int hgibbs_pca(hgibbs_t h, int K, int L, int iters, double tol, const double* Q0
  * panel algebra of the iterations (fold, Gram matrices, CholeskyQR); the start panel, the final step and the residuals are in [0] only */
 int hgibbs_last_pca_ms(hgibbs_t h, double* ms4);
 
+/* ---- genomic relationship matrix of the loaded rows -- */
+/* S = X X' over the handle's n_local rows, X the chain's standardised genotypes (x = 0 at a missing call), and the number of markers
+ * both rows are called at: the GCTA entry is A_ab = S_ab / NSNP_ab (NaN when NSNP_ab = 0).  mave_j and mstd_j are those of
+ * hgibbs_marker_stats (computed here when they are not), g in {0, 1, 2} the genotype as hgibbs_load_bed reads it.
+ *   A marker is USED when mstd_j is finite; M_used is their number.  Per used marker and genotype g, two f64 values, every operation
+ *   rounded to f64 on its own (no fused multiply-add):   y_jg = (mstd_j * mstd_j) * (g - mave_j),   z_jg = mave_j * y_jg.
+ *   W = the largest |y| or |z| of that table, e the smallest integer with W < 2^e, E = 52 - e (0 for an all-zero table);
+ *   qy = llrint(y 2^E), qz = llrint(z 2^E).  For a >= b (row a is the weight side, b the code side):
+ *     T_ab    = sum over used j with a and b called of ( g_bj qy[j][g_aj] - qz[j][g_aj] )      an exact integer
+ *     S_ab    = T_ab 2^-E, rounded to f64 once
+ *     NSNP_ab = the number of used j with a and b called
+ *   |S_ab - exact| <= 1.5 M_used 2^-E <= 3 M_used W 2^-52.
+ * hgibbs_grm covers rows a in [a0, a0 + acount), each with its columns b = 0 .. a, packed in GCTA's order: row a0 first, then row
+ * a0 + 1, ...: sum of (a + 1) entries.  Either output pointer may be NULL.  Every sum is an integer: the results are bit-identical for
+ * any chunking of the rows, any value of the option grm_split (ranges of markers split over workgroups, 0 = automatic; the parts meet
+ * in i32 atomic adds of the per-digit accumulators) and any repeat.  A call of more than 2^25 pairs works in pieces of rows.  The
+ * call builds an individual-major copy of the codes on the device (the size of the loaded BED).  Refused with a message: several
+ * ranks, no genotypes, acount = 0, a0 + acount > n_local, M_used = 0, M > 5 592 405 (a per-digit sum is at most 384 M and stays
+ * inside an i32), more rows than hgibbs_king takes, buffers that do not fit in free device memory. */
+int hgibbs_grm(hgibbs_t h, uint32_t a0, uint32_t acount, double* S, int32_t* nsnp);
+/* M_used and E of the last hgibbs_grm (0, 0 after a refused one); either pointer may be NULL */
+int hgibbs_grm_info(hgibbs_t h, uint32_t* m_used, int32_t* E);
+/* device time of the last hgibbs_grm in ms: every kernel of the call (scale, table, image, zeroing, products, rounding), not the host
+ * copies or the allocations */
+int hgibbs_last_grm_ms(hgibbs_t h, double* ms);
+
 /* ======================================================================== */
 /* Host driver: the body of BayesRRm::runMpiGibbs (src/BayesRRm.cpp:933-2939)
  * for --mpibayes bayesMPI, restated on top of hgibbs_*.                     */
