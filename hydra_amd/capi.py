@@ -22,6 +22,7 @@ ABI_SYMBOLS = [
     "hgibbs_beta_sqnorm", "hgibbs_sweep", "hgibbs_set_option", "hgibbs_last_sweep_stats", "hgibbs_stream_ceiling", "hgibbs_debug_times", "hgibbs_resident_trace", "hydra_chain_create",
     "hydra_chain_destroy", "hydra_chain_iterate", "hydra_chain_state", "hydra_chain_csv_line", "hydra_chain_order",
     "hydra_chain_last_nnz", "hgibbs_score", "hgibbs_last_score_ms", "hgibbs_ld", "hgibbs_last_ld_ms",
+    "hgibbs_ld_scores", "hgibbs_last_ld_scores_ms",
     "hgibbs_marker_dots", "hgibbs_last_marker_dots_ms", "hgibbs_king", "hgibbs_king_pairs", "hgibbs_king_pairs_get", "hgibbs_last_king_ms",
     "hgibbs_pca", "hgibbs_last_pca_ms", "hgibbs_region_var", "hgibbs_last_region_var_ms",
     "hgibbs_grm", "hgibbs_grm_info", "hgibbs_last_grm_ms",
@@ -88,6 +89,10 @@ class ModelDesc(C.Structure):
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int)
+
+
+C_U32P = C.POINTER(C.c_uint32)
+C_U64P = C.POINTER(C.c_uint64)
 
 
 class HgError(RuntimeError):
@@ -191,6 +196,8 @@ def lib():
     L.hgibbs_last_score_ms.argtypes = [vp, dp]
     L.hgibbs_ld.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, dp, C.POINTER(C.c_int64)]
     L.hgibbs_last_ld_ms.argtypes = [vp, dp]
+    L.hgibbs_ld_scores.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint64), C.c_int, dp]
+    L.hgibbs_last_ld_scores_ms.argtypes = [vp, dp, dp]
     L.hgibbs_marker_dots.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_int, dp, dp, dp]
     L.hgibbs_last_marker_dots_ms.argtypes = [vp, dp]
     L.hgibbs_king.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32)]
@@ -449,6 +456,33 @@ class Device:
         v = C.c_double()
         check(self.L.hgibbs_last_ld_ms(self.h, C.byref(v)))
         return v.value
+
+    def ld_scores(self, W, ahead=None, annot=None, C=None, adjust=True):
+        """LD scores (hgibbs_ld_scores): (M, C) float64 with l2[j, c] = a_jc + sum over the pairs of j's window of a_qc t_jq.  ahead (M,)
+        uint32: pair (j, q), j < q, is in the window iff q - j <= ahead[j] (None: min(W, M - 1 - j)); annot (M,) uint64: bit c says the
+        marker is in annotation c (None: one column with every marker); C defaults to 1 without annot and to the highest bit used + 1
+        with it; adjust: t = r^2 - (1 - r^2) / (N - 2), else r^2."""
+        ah = an = None
+        if ahead is not None:
+            ah = np.ascontiguousarray(ahead, dtype=np.uint32)
+            if ah.shape != (self.M,):
+                raise ValueError("ahead must be (%d,)" % self.M)
+        if annot is not None:
+            an = np.ascontiguousarray(annot, dtype=np.uint64)
+            if an.shape != (self.M,):
+                raise ValueError("annot must be (%d,)" % self.M)
+        if C is None:
+            C = 1 if an is None else max(1, int(np.bitwise_or.reduce(an)).bit_length())
+        out = np.zeros((self.M, max(int(C), 0)))
+        check(self.L.hgibbs_ld_scores(self.h, W, ah.ctypes.data_as(C_U32P) if ah is not None else None, C,
+                                      an.ctypes.data_as(C_U64P) if an is not None else None, 1 if adjust else 0, _dp(out)))
+        return out
+
+    def last_ld_scores_ms(self):
+        """(products ms, reduce ms) of the last ld_scores()"""
+        a, b = C.c_double(), C.c_double()
+        check(self.L.hgibbs_last_ld_scores_ms(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def marker_dots(self, U, m0=0, count=None, raw=False):
         """x_j'u_k for markers j in [m0, m0 + count) against the rows u_k of U (K, n_local) (hgibbs_marker_dots): out (count, K),

@@ -184,7 +184,31 @@ __global__ __launch_bounds__(LD_WAVES * 64) void k_ld(const uint8_t* __restrict_
     }
 }
 
-// One thread per pair: the clean pairs' Bjq, Bqj, D from the counts, then r in one f64 formula (NaN past M or where an mstd is not finite)
+// The four sums of pair (j, q), q < M, from its accumulators a4 (the clean pairs' Bjq, Bqj, D from the counts), and r in ONE f64 formula
+// (NaN where an mstd is not finite).  hgibbs_ld and hgibbs_ld_scores (hg_ldscore.hip.h) both take r from here.
+__device__ __forceinline__ double ld_pair_r(const unsigned long long* __restrict__ a4, const unsigned long long* __restrict__ counts,
+                                            const double* __restrict__ mave, const double* __restrict__ mstd, uint32_t j, uint32_t q,
+                                            uint32_t n_local, uint32_t N, long long& G, long long& Bjq, long long& Bqj, long long& Dc)
+{
+    const unsigned long long* cj = counts + 3ull * j;
+    const unsigned long long* cq = counts + 3ull * q;
+    G = (long long)a4[0];
+    if (cj[2] == 0 && cq[2] == 0) {
+        Bjq = (long long)(cj[0] + 2 * cj[1]);
+        Bqj = (long long)(cq[0] + 2 * cq[1]);
+        Dc = (long long)n_local;
+    } else {
+        Bjq = (long long)a4[1];
+        Bqj = (long long)a4[2];
+        Dc = (long long)a4[3];
+    }
+    const double sj = mstd[j], sq = mstd[q], mj = mave[j], mq = mave[q];
+    if (isfinite(sj) && isfinite(sq))
+        return sj * sq * ((double)G - mq * (double)Bjq - mj * (double)Bqj + mj * mq * (double)Dc) / (double)(N - 1u);
+    return __builtin_nan("");
+}
+
+// One thread per pair: the sums and r of ld_pair_r (r NaN past M)
 __global__ __launch_bounds__(LD_TPB) void k_ld_final(const unsigned long long* __restrict__ acc, const unsigned long long* __restrict__ counts,
                                                      const double* __restrict__ mave, const double* __restrict__ mstd, uint32_t M, uint32_t n_local,
                                                      uint32_t N, uint32_t W, uint32_t m0, uint32_t count, double* __restrict__ r,
@@ -195,23 +219,7 @@ __global__ __launch_bounds__(LD_TPB) void k_ld_final(const unsigned long long* _
     const uint32_t j = m0 + (uint32_t)(k / W), q = j + 1u + (uint32_t)(k % W);
     long long G = 0, Bjq = 0, Bqj = 0, Dc = 0;
     double v = __builtin_nan("");
-    if (q < M) {
-        const unsigned long long* cj = counts + 3ull * j;
-        const unsigned long long* cq = counts + 3ull * q;
-        G = (long long)acc[4 * k];
-        if (cj[2] == 0 && cq[2] == 0) {
-            Bjq = (long long)(cj[0] + 2 * cj[1]);
-            Bqj = (long long)(cq[0] + 2 * cq[1]);
-            Dc = (long long)n_local;
-        } else {
-            Bjq = (long long)acc[4 * k + 1];
-            Bqj = (long long)acc[4 * k + 2];
-            Dc = (long long)acc[4 * k + 3];
-        }
-        const double sj = mstd[j], sq = mstd[q], mj = mave[j], mq = mave[q];
-        if (isfinite(sj) && isfinite(sq))
-            v = sj * sq * ((double)G - mq * (double)Bjq - mj * (double)Bqj + mj * mq * (double)Dc) / (double)(N - 1u);
-    }
+    if (q < M) v = ld_pair_r(acc + 4 * k, counts, mave, mstd, j, q, n_local, N, G, Bjq, Bqj, Dc);
     if (r) r[k] = v;
     if (sums) {
         sums[4 * k] = G;

@@ -45,6 +45,13 @@
 // section 19) and writes GCTA's PREFIX.grm.id, .grm.bin and .grm.N.bin (PREFIX defaults to <dir>/<name>), and with --grm-sparse the
 // diagonal and the pairs with A >= T to PREFIX.grm.sp.
 //
+// `--ld-score [--ld-score-kb KB | --ld-score-snps W] [--ld-score-sets F | --ld-score-groups] [--ld-score-raw] [--ld-score-out PREFIX]`
+// appended to a bayesMPI command line samples nothing either: it computes the LD score of every marker, the sum of the adjusted r^2 (raw
+// with --ld-score-raw) over the markers of its chromosome within KB kilobases (default 1000) or W markers on either side, on the chain's
+// own rows and standardisation, with hgibbs_ld_scores (run_ldscore), partitioned by the sets of F or the groups of
+// --groupIndexFile behind a `base` column, and writes LDSC's PREFIX.l2.ldscore, .l2.M and .l2.M_5_50 as plain text (PREFIX defaults to
+// <dir>/<name>).  Not covered: cM windows, gzip, the regression itself (ldsc reads these files).
+//
 // Not reproduced (out of scope for the hot path): sparse
 // file formats, bayesFH, marker-sharded MPI, the .lst/tarball.
 // Multi-GPU: one process per GPU (RANK/WORLD_SIZE/LOCAL_RANK in the
@@ -104,6 +111,8 @@ struct Options { // src/options.hpp:20-138 (subset that reaches bayesMPI)
     std::string pveKb, pveSnps, pveSets, pveThreshold, pveOut; // --pve-window-kb KB, --pve-window-snps W, --pve-threshold T as given, --pve-sets, --pve-out
     bool grm = false, grmSparseGiven = false;        // --grm: genomic relationship matrix of the chain's rows; --grm-sparse given
     std::string grmOut, grmSparse;                   // --grm-out PREFIX, --grm-sparse T as given (checked before the device)
+    bool ldScore = false, ldScoreKbGiven = false, ldScoreSnpsGiven = false, ldScoreGroups = false, ldScoreRaw = false; // --ld-score; which --ld-score-* were given
+    std::string ldScoreKb, ldScoreSnps, ldScoreSets, ldScoreOut; // --ld-score-kb KB, --ld-score-snps W as given (checked before the device), --ld-score-sets, --ld-score-out PREFIX
     int batch = 0, cpg = 0; // tuning knobs of this build (not hydra's)
 };
 
@@ -274,7 +283,18 @@ Options parse(int argc, const char* argv[])
         else if (a == "--grm-sparse") {
             o.grmSparse = need(i);
             o.grmSparseGiven = true;
-        } else if (a == "--sparse-dir" || a == "--sparse-basename" ||
+        } else if (a == "--ld-score") o.ldScore = true;
+        else if (a == "--ld-score-kb") {
+            o.ldScoreKb = need(i);
+            o.ldScoreKbGiven = true;
+        } else if (a == "--ld-score-snps") {
+            o.ldScoreSnps = need(i);
+            o.ldScoreSnpsGiven = true;
+        } else if (a == "--ld-score-sets") o.ldScoreSets = need(i);
+        else if (a == "--ld-score-groups") o.ldScoreGroups = true;
+        else if (a == "--ld-score-raw") o.ldScoreRaw = true;
+        else if (a == "--ld-score-out") o.ldScoreOut = need(i);
+        else if (a == "--sparse-dir" || a == "--sparse-basename" ||
                  a == "--bed-to-sparse" || a == "--sparse-sync" || a == "--bed-sync")
             fatal("FATAL  : option " + a + " belongs to a part of hydra this build does not reproduce (SURVEY.md section 2)");
         else
@@ -1559,10 +1579,47 @@ int run_pca(const Options& opt, const Cohort& co)
 }
 
 // ---- --pve: posterior variance explained by marker sets ----
-struct PveSets {
+struct MarkerSets {
     std::vector<std::string> name;
     std::vector<std::vector<uint32_t>> idx; // markers of each set, increasing
-    std::string how;                        // how the sets were defined, for the report
+};
+
+// The SETNAME SNPID file of --pve-sets and --ld-score-sets: the sets in the order in which the file first names them
+MarkerSets read_sets_file(const std::string& path, const std::string& bedFile, const BimRows& bim, unsigned Mtot)
+{
+    MarkerSets ms;
+    std::ifstream in(path);
+    if (!in) fatal("Error: can not open the file [" + path + "] to read.");
+    std::map<std::string, uint32_t> snp;
+    for (unsigned j = 0; j < Mtot; ++j) snp.emplace(bim.id[j], j);
+    std::map<std::string, size_t> at;
+    std::map<std::pair<size_t, uint32_t>, int> seen;
+    std::string line;
+    size_t lineno = 0;
+    while (std::getline(in, line)) {
+        ++lineno;
+        const std::vector<std::string> col = tokens(line, " \t\r");
+        if (col.empty()) continue;
+        const std::string where = "FATAL  : " + path + " line " + std::to_string(lineno) + ": ";
+        if (col.size() != 2) fatal(where + "expected SETNAME SNPID");
+        const auto j = snp.find(col[1]);
+        if (j == snp.end()) fatal(where + "SNP " + col[1] + " is not among the first " + std::to_string(Mtot) + " markers of " + bedFile + ".bim");
+        auto it = at.find(col[0]);
+        if (it == at.end()) {
+            ms.name.push_back(col[0]);
+            ms.idx.emplace_back();
+            it = at.emplace(col[0], ms.idx.size() - 1).first;
+        }
+        if (!seen.emplace(std::make_pair(it->second, j->second), 1).second) fatal(where + "SNP " + col[1] + " is given twice for set " + col[0]);
+        ms.idx[it->second].push_back(j->second);
+    }
+    if (ms.idx.empty()) fatal("FATAL  : " + path + " names no set");
+    for (auto& r : ms.idx) std::sort(r.begin(), r.end());
+    return ms;
+}
+
+struct PveSets : MarkerSets {
+    std::string how; // how the sets were defined, for the report
 };
 
 PveSets pve_sets(const Options& opt, const BimRows& bim, unsigned Mtot)
@@ -1600,29 +1657,7 @@ PveSets pve_sets(const Options& opt, const BimRows& bim, unsigned Mtot)
         }
     } else if (!opt.pveSets.empty()) {
         ps.how = "from " + opt.pveSets;
-        std::ifstream in(opt.pveSets);
-        if (!in) fatal("Error: can not open the file [" + opt.pveSets + "] to read.");
-        std::map<std::string, uint32_t> snp;
-        for (unsigned j = 0; j < Mtot; ++j) snp.emplace(bim.id[j], j);
-        std::map<std::string, size_t> at;
-        std::map<std::pair<size_t, uint32_t>, int> seen;
-        std::string line;
-        size_t lineno = 0;
-        while (std::getline(in, line)) {
-            ++lineno;
-            const std::vector<std::string> col = tokens(line, " \t\r");
-            if (col.empty()) continue;
-            const std::string where = "FATAL  : " + opt.pveSets + " line " + std::to_string(lineno) + ": ";
-            if (col.size() != 2) fatal(where + "expected SETNAME SNPID");
-            const auto j = snp.find(col[1]);
-            if (j == snp.end()) fatal(where + "SNP " + col[1] + " is not among the first " + std::to_string(Mtot) + " markers of " + opt.bedFile + ".bim");
-            auto it = at.find(col[0]);
-            if (it == at.end()) it = at.emplace(col[0], add(col[0])).first;
-            if (!seen.emplace(std::make_pair(it->second, j->second), 1).second) fatal(where + "SNP " + col[1] + " is given twice for set " + col[0]);
-            ps.idx[it->second].push_back(j->second);
-        }
-        if (ps.idx.empty()) fatal("FATAL  : " + opt.pveSets + " names no set");
-        for (auto& r : ps.idx) std::sort(r.begin(), r.end());
+        static_cast<MarkerSets&>(ps) = read_sets_file(opt.pveSets, opt.bedFile, bim, Mtot);
     } else if (opt.pveGroups) {
         ps.how = "the groups of " + opt.groupIndexFile;
         const std::vector<int32_t> groups = read_groups(opt.groupIndexFile);
@@ -1837,16 +1872,146 @@ int run_grm(const Options& opt, const Cohort& co)
     return 0;
 }
 
+// ---- --ld-score: LD scores of the training markers on the chain's rows ----
+int run_ldscore(const Options& opt, const Cohort& co)
+{
+    const std::string prefix = opt.ldScoreOut.empty() ? opt.mcmcOutDir + "/" + opt.mcmcOutNam : opt.ldScoreOut;
+    const std::string bimp = opt.bedFile + ".bim";
+    const unsigned M = co.Mtot;
+    const BimRows bim = read_bim(bimp, M);
+    auto marker = [&](unsigned j) { return bim.id[j] + " (row " + std::to_string(j + 1) + ")"; };
+
+    // the window is an index interval: every chromosome one run and, with a kb window, bp not decreasing inside it
+    const bool bySnps = opt.ldScoreSnpsGiven;
+    double kb = 1000.0;
+    long wsnps = 0;
+    if (opt.ldScoreKbGiven) whole_num(opt.ldScoreKb, kb);
+    if (bySnps) whole_int(opt.ldScoreSnps, wsnps);
+    const long long maxbp = (long long)std::llround(1000.0 * kb);
+    std::map<std::string, int> chroms;
+    for (unsigned j = 0; j < M; ++j) {
+        if (j == 0 || bim.chr[j] != bim.chr[j - 1]) {
+            if (!chroms.emplace(bim.chr[j], 1).second)
+                fatal("FATAL  : " + bimp + ": chromosome " + bim.chr[j] + " comes back at marker " + marker(j) +
+                      " after another chromosome: --ld-score needs every chromosome as one contiguous run");
+        } else if (!bySnps && bim.bp[j] < bim.bp[j - 1])
+            fatal("FATAL  : " + bimp + ": bp decreases at marker " + marker(j) + " inside chromosome " + bim.chr[j] +
+                  ": with a kb window the markers of a chromosome must be in bp order (the window must be an index interval; --ld-score-snps takes any order)");
+    }
+    std::vector<uint32_t> ahead(M, 0);
+    unsigned long long npairs = 0;
+    uint32_t widest = 0;
+    for (unsigned j = 0, e = 0; j < M; ++j) { // e: one past the last marker of j's window
+        e = std::max(e, j + 1);
+        while (e < M && bim.chr[e] == bim.chr[j] && (bySnps ? (long)(e - j) <= wsnps : bim.bp[e] - bim.bp[j] <= maxbp)) ++e;
+        const unsigned n = e - 1 - j;
+        if (n > 4096)
+            fatal("FATAL  : marker " + marker(j) + " has " + std::to_string(n) + " markers ahead of it in its window, at most 4096 (the widest hgibbs_ld_scores takes): narrow the window");
+        ahead[j] = n;
+        npairs += n;
+        widest = std::max(widest, n);
+    }
+    const uint32_t W = std::max(1u, widest);
+
+    // annotations: none (one column), or `base` and the sets or groups in definition order
+    std::vector<std::string> colname;
+    std::vector<uint64_t> annot;
+    if (!opt.ldScoreSets.empty() || opt.ldScoreGroups) {
+        MarkerSets ms;
+        if (!opt.ldScoreSets.empty()) ms = read_sets_file(opt.ldScoreSets, opt.bedFile, bim, M);
+        else {
+            const std::vector<int32_t> groups = read_groups(opt.groupIndexFile);
+            if (groups.size() < M) fatal("FATAL  : group file covers fewer markers than --number-markers");
+            std::map<int32_t, size_t> at; // in ascending order of the group's number
+            for (unsigned j = 0; j < M; ++j) at.emplace(groups[j], 0);
+            for (auto& g : at) {
+                g.second = ms.idx.size();
+                ms.name.push_back("group" + std::to_string(g.first));
+                ms.idx.emplace_back();
+            }
+            for (unsigned j = 0; j < M; ++j) ms.idx[at[groups[j]]].push_back(j);
+        }
+        if (ms.idx.size() > 63)
+            fatal("FATAL  : --ld-score: " + std::to_string(ms.idx.size()) + " annotations, at most 63 beside the base column (hgibbs_ld_scores takes 64 columns)");
+        colname.push_back("base");
+        annot.assign(M, 1ull);
+        for (size_t c = 0; c < ms.idx.size(); ++c) {
+            colname.push_back(ms.name[c]);
+            for (const uint32_t j : ms.idx[c]) annot[j] |= 1ull << (c + 1);
+        }
+    }
+    const uint32_t C = colname.empty() ? 1u : (uint32_t)colname.size();
+    const std::string l2p = prefix + ".l2.ldscore", mp = prefix + ".l2.M", m5p = prefix + ".l2.M_5_50";
+    std::printf("LDSCORE: %u markers, %zu chromosomes, window %s, %llu pairs in the window, widest window %u markers ahead, %u columns (%s r^2) -> %s\n", M,
+                chroms.size(), bySnps ? (std::to_string(wsnps) + " markers").c_str() : (std::to_string(maxbp) + " bp").c_str(), npairs, widest, C,
+                opt.ldScoreRaw ? "raw" : "adjusted", l2p.c_str());
+    std::fflush(stdout);
+    if (!opt.ldScoreRaw && co.Ntot < 3) fatal("FATAL  : --ld-score: the adjusted r^2 - (1 - r^2) / (N - 2) needs at least three individuals (--ld-score-raw takes fewer)");
+
+    std::vector<uint8_t> bed = read_bed(opt.bedFile, co.numInds, M);
+    if (opt.ldScoreOut.empty()) make_out_dir(opt);
+    FILE* f = open_out(l2p, "w");
+    FILE* fm = open_out(mp, "w");
+    FILE* fm5 = open_out(m5p, "w");
+
+    // the chain's rows and its standardisation; the counts give the allele frequencies
+    hgibbs_t dev = open_training(co, bed);
+    std::vector<double> mstd(M), l2((size_t)M * C);
+    std::vector<uint64_t> n1(M), n2(M), nmiss(M);
+    hg_check(hgibbs_marker_stats(dev, nullptr, mstd.data(), n1.data(), n2.data(), nmiss.data()), "hgibbs_marker_stats");
+    hg_check(hgibbs_ld_scores(dev, W, ahead.data(), C, annot.empty() ? nullptr : annot.data(), opt.ldScoreRaw ? 0 : 1, l2.data()), "hgibbs_ld_scores");
+    double products_ms = 0.0, reduce_ms = 0.0;
+    hg_check(hgibbs_last_ld_scores_ms(dev, &products_ms, &reduce_ms), "hgibbs_last_ld_scores_ms");
+    hgibbs_destroy(dev);
+
+    std::fprintf(f, "CHR\tSNP\tBP");
+    if (colname.empty()) std::fprintf(f, "\tL2");
+    for (const std::string& n : colname) std::fprintf(f, "\t%sL2", n.c_str());
+    std::fprintf(f, "\n");
+    std::vector<unsigned long long> cnt(C, 0), cnt5(C, 0);
+    unsigned written = 0;
+    double sum0 = 0.0;
+    for (unsigned j = 0; j < M; ++j) {
+        if (!std::isfinite(mstd[j])) continue;
+        const double called = (double)co.Ntot - (double)nmiss[j];
+        const double p = called > 0.0 ? ((double)n1[j] + 2.0 * (double)n2[j]) / (2.0 * called) : 0.0;
+        const bool common = std::min(p, 1.0 - p) > 0.05;
+        std::fprintf(f, "%s\t%s\t%lld", bim.chr[j].c_str(), bim.id[j].c_str(), bim.bp[j]);
+        for (uint32_t c = 0; c < C; ++c) {
+            std::fprintf(f, "\t%.12g", l2[(size_t)j * C + c]);
+            if (annot.empty() || ((annot[j] >> c) & 1ull)) {
+                ++cnt[c];
+                cnt5[c] += common ? 1u : 0u;
+            }
+        }
+        std::fprintf(f, "\n");
+        sum0 += l2[(size_t)j * C];
+        ++written;
+    }
+    for (uint32_t c = 0; c < C; ++c) {
+        std::fprintf(fm, "%s%llu", c ? "\t" : "", cnt[c]);
+        std::fprintf(fm5, "%s%llu", c ? "\t" : "", cnt5[c]);
+    }
+    std::fprintf(fm, "\n");
+    std::fprintf(fm5, "\n");
+    close_out(f, l2p);
+    close_out(fm, mp);
+    close_out(fm5, m5p);
+    std::printf("LDSCORE: wrote %u of %u markers to %s (%u without a finite sd left out), mean L2 of column 0 %.6g (products %.3f ms, reduce %.3f ms on the device)\n",
+                written, M, l2p.c_str(), M - written, written ? sum0 / written : 0.0, products_ms, reduce_ms);
+    return 0;
+}
+
 // ---- the analysis modes -------------------------------------------------------
 // An analysis mode is an option that, appended to a bayesMPI command line, samples nothing and runs one analysis on the chain's rows
-// (run_predict .. run_grm above).  What the modes share is refused in one place, from one row per mode.
+// (run_predict .. run_ldscore above).  What the modes share is refused in one place, from one row per mode.
 struct Mode {
     const char* flag;   // the option that asks for the mode
     bool given;
     const char* wmpi;   // how it refuses --mpibayes bayesWMPI, after its flag
     const char* orphan; // the first of its dependent options that was given: they need the mode (null: none was)
 };
-enum { PREDICT, LD, ASSOC, KING, PCA, PVE, GRM, NMODES }; // the order in which a mode names the earlier ones it cannot be combined with
+enum { PREDICT, LD, ASSOC, KING, PCA, PVE, GRM, LDSCORE, NMODES }; // the order in which a mode names the earlier ones it cannot be combined with
 
 const char* first_given(std::initializer_list<std::pair<const char*, bool>> deps)
 {
@@ -1890,6 +2055,20 @@ void check_grm_args(const Options& opt)
         fatal("FATAL  : --grm-sparse " + opt.grmSparse + ": the cutoff must be a finite number");
 }
 
+void check_ldscore_args(const Options& opt)
+{
+    if (opt.ldScoreKbGiven && opt.ldScoreSnpsGiven) fatal("FATAL  : --ld-score-kb cannot be combined with --ld-score-snps: one way to define the window");
+    if (!opt.ldScoreSets.empty() && opt.ldScoreGroups)
+        fatal("FATAL  : --ld-score-sets cannot be combined with --ld-score-groups: one way to define the annotations");
+    long w = 0;
+    double t = 0.0;
+    if (opt.ldScoreKbGiven && (!whole_num(opt.ldScoreKb, t) || !std::isfinite(t) || t < 0.0))
+        fatal("FATAL  : --ld-score-kb " + opt.ldScoreKb + ": the window must be a finite number of kilobases >= 0");
+    if (opt.ldScoreSnpsGiven && (!whole_int(opt.ldScoreSnps, w) || w < 1 || w > 4096))
+        fatal("FATAL  : --ld-score-snps " + opt.ldScoreSnps + ": the window must be an integer from 1 to 4096 markers (the widest hgibbs_ld_scores takes)");
+    if (opt.ldScoreGroups && opt.groupIndexFile.empty()) fatal("FATAL  : --ld-score-groups needs --groupIndexFile");
+}
+
 void check_pve_args(const Options& opt)
 {
     const char* const definer[4] = {"--pve-window-kb", "--pve-window-snps", "--pve-sets", "--pve-groups"};
@@ -1925,8 +2104,11 @@ void check_modes(const Options& opt, int nranks)
          first_given({{"--pve-window-kb", opt.pveKbGiven}, {"--pve-window-snps", opt.pveSnpsGiven}, {"--pve-sets", !opt.pveSets.empty()}, {"--pve-groups", opt.pveGroups},
                       {"--pve-threshold", opt.pveThresholdGiven}, {"--pve-out", !opt.pveOut.empty()}, {"--pve-bin", opt.pveBin}})},
         {"--grm", opt.grm, takes, first_given({{"--grm-out", !opt.grmOut.empty()}, {"--grm-sparse", opt.grmSparseGiven}})},
+        {"--ld-score", opt.ldScore, takes,
+         first_given({{"--ld-score-kb", opt.ldScoreKbGiven}, {"--ld-score-snps", opt.ldScoreSnpsGiven}, {"--ld-score-sets", !opt.ldScoreSets.empty()},
+                      {"--ld-score-groups", opt.ldScoreGroups}, {"--ld-score-raw", opt.ldScoreRaw}, {"--ld-score-out", !opt.ldScoreOut.empty()}})},
     };
-    for (const int i : {LD, PREDICT, ASSOC, KING, PCA, PVE, GRM}) {
+    for (const int i : {LD, PREDICT, ASSOC, KING, PCA, PVE, GRM, LDSCORE}) {
         const Mode& m = modes[i];
         const std::string flag = m.flag;
         if (!m.given) {
@@ -1943,6 +2125,7 @@ void check_modes(const Options& opt, int nranks)
         if (i == PCA) check_pca_args(opt);
         if (i == PVE) check_pve_args(opt);
         if (i == GRM) check_grm_args(opt);
+        if (i == LDSCORE) check_ldscore_args(opt);
     }
 }
 
@@ -2006,6 +2189,7 @@ int main(int argc, const char* argv[])
     if (opt.pca) return run_pca(opt, co);
     if (opt.pve) return run_pve(opt, co);
     if (opt.grm) return run_grm(opt, co);
+    if (opt.ldScore) return run_ldscore(opt, co);
 
     std::vector<int32_t> groups;
     std::vector<std::vector<double>> mS;

@@ -181,6 +181,7 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
  *   ahead           columns a launch streams ahead of its batch while its last workgroup draws, 0..256 (default 0: measured
  *                   slower on MI355X; needs carry)
  *   graph           1: replay the launches from a captured HIP graph
+ *   ldscore_piece   hgibbs_ld_scores: band rows per piece, 0..2^20 (0 = automatic)
  *   p2p, force_split, chunk, debug_timing, w_kernel_timing   transport selection and diagnostics */
 int hgibbs_set_option(hgibbs_t h, const char* name, int64_t value);
 /* Statistics of the last sweep: launches, markers per launch, device time of
@@ -283,6 +284,24 @@ int hgibbs_last_region_var_ms(hgibbs_t h, double* ms);
 int hgibbs_ld(hgibbs_t h, uint32_t m0, uint32_t count, uint32_t W, double* r_host, int64_t* sums_host);
 /* device time of the last hgibbs_ld in ms: every kernel of the call (zeroing, products, final formula), not the host copies */
 int hgibbs_last_ld_ms(hgibbs_t h, double* ms);
+
+/* ---- LD scores of the loaded markers -------------- */
+/* l2[j*C + c] = a_jc + sum_{q != j in j's window} a_qc t_jq over the M loaded markers (marker-major), where
+ *   window   a pair (j, q), j < q, is in the window iff q - j <= ahead[j]; it counts for both of its markers.  ahead: M entries with
+ *            ahead[j] <= W and j + ahead[j] < M, or NULL for min(W, M - 1 - j)
+ *   a_qc     bit c of annot[q] (binary annotations), 1 <= C <= 64 and no bit at or above C; annot = NULL means C = 1 with every marker
+ *   t_jq     r^2, or with adjust != 0 the estimator r^2 - (1 - r^2) / (N - 2), N = n_global (N >= 3); r is exactly hgibbs_ld's r
+ * A marker whose mstd is not finite contributes to nobody and its own row is NaN in every column.  The band never leaves the device:
+ * the four integer sums of a piece of band rows (hgibbs_ld's products, at most 2^24 pairs) are reduced there, forwards and backwards,
+ * into an M x C accumulator of signed 64-bit fixed point, llrint(t 2^44) per pair with integer adds, converted once at the end.  So
+ * the result is bit-identical for any value of the options ldscore_piece (band rows per piece, 0 = automatic, rounded up to a multiple
+ * of 16, at most 2^20) and ld_split and for any repeat, and column c of a call with C columns equals the call with C = 1 and annot
+ * reduced to bit c.  |l2 - exact| <= (terms of the marker's window) x 2^-45 beyond the rounding of r.  One rank only; 1 <= W <= 4096;
+ * n_local < 2^29; refused when the accumulator and a piece's sums do not fit in free device memory. */
+int hgibbs_ld_scores(hgibbs_t h, uint32_t W, const uint32_t* ahead, uint32_t C, const uint64_t* annot, int adjust, double* l2);
+/* device time of the last hgibbs_ld_scores in ms: the products (zeroing and hgibbs_ld's product kernel, every piece) and the reduce
+ * (the reduction kernel of every piece, zeroing the accumulator and the final conversion); not the host copies */
+int hgibbs_last_ld_scores_ms(hgibbs_t h, double* products_ms, double* reduce_ms);
 
 /* ---- dots of the loaded markers against dense vectors */
 /* For markers j in [m0, m0 + count) of the loaded BED and K vectors u_k over this rank's n_local individuals:
