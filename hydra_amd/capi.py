@@ -23,6 +23,7 @@ ABI_SYMBOLS = [
     "hydra_chain_destroy", "hydra_chain_iterate", "hydra_chain_state", "hydra_chain_csv_line", "hydra_chain_order",
     "hydra_chain_last_nnz", "hgibbs_score", "hgibbs_last_score_ms", "hgibbs_ld", "hgibbs_last_ld_ms",
     "hgibbs_ld_scores", "hgibbs_last_ld_scores_ms",
+    "hgibbs_ld_mask", "hgibbs_last_ld_mask_ms", "hgibbs_ld_greedy", "hgibbs_ld_clump",
     "hgibbs_marker_dots", "hgibbs_last_marker_dots_ms", "hgibbs_king", "hgibbs_king_pairs", "hgibbs_king_pairs_get", "hgibbs_last_king_ms",
     "hgibbs_pca", "hgibbs_last_pca_ms", "hgibbs_region_var", "hgibbs_last_region_var_ms",
     "hgibbs_grm", "hgibbs_grm_info", "hgibbs_last_grm_ms",
@@ -198,6 +199,10 @@ def lib():
     L.hgibbs_last_ld_ms.argtypes = [vp, dp]
     L.hgibbs_ld_scores.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint64), C.c_int, dp]
     L.hgibbs_last_ld_scores_ms.argtypes = [vp, dp, dp]
+    L.hgibbs_ld_mask.argtypes = [vp, C.c_uint32, u32p, C.c_double, u64p, u64p, u64p]
+    L.hgibbs_last_ld_mask_ms.argtypes = [vp, dp, dp]
+    L.hgibbs_ld_greedy.argtypes = [C.c_uint32, C.c_uint32, u64p, u64p, u32p, C.c_uint32, u8p, ip]
+    L.hgibbs_ld_clump.argtypes = [vp, C.c_uint32, u32p, C.c_double, u32p, C.c_uint32, u8p, ip, u64p]
     L.hgibbs_marker_dots.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_int, dp, dp, dp]
     L.hgibbs_last_marker_dots_ms.argtypes = [vp, dp]
     L.hgibbs_king.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32)]
@@ -241,6 +246,31 @@ def rng_shuffle(rng, v):
     if v.dtype != np.int32 or not v.flags.c_contiguous:
         raise ValueError("rng_shuffle: a contiguous int32 array is required")
     check(lib().hydra_rng_shuffle(C.byref(rng), _ip(v), v.size))
+
+
+def _order_and_leaders(M, order, may_lead):
+    od = np.ascontiguousarray(order, dtype=np.uint32).reshape(-1)
+    ml = None
+    if may_lead is not None:
+        ml = np.ascontiguousarray(may_lead, dtype=np.uint8)
+        if ml.shape != (M,):
+            raise ValueError("may_lead must be (%d,)" % M)
+    return od, ml
+
+
+def ld_greedy(M, W, fwd, bwd, order, may_lead=None):
+    """hgibbs_ld_greedy (host only): the greedy selection on two masks in Device.ld_mask's layout, (M, wpr) uint64 each.  order: the
+    participating markers in descending priority; may_lead (M,) bytes or None for "all may".  Returns owner (M,) int32: the leader
+    that claimed the marker (itself for a leader), -1 for a marker nobody claimed or that does not participate."""
+    wpr = (int(W) + 63) // 64
+    fwd = np.ascontiguousarray(fwd, dtype=np.uint64)
+    bwd = np.ascontiguousarray(bwd, dtype=np.uint64)
+    if 1 <= W <= 4096 and (fwd.shape != (M, wpr) or bwd.shape != (M, wpr)):
+        raise ValueError("fwd and bwd must be (%d, %d)" % (M, wpr))
+    od, ml = _order_and_leaders(M, order, may_lead)
+    owner = np.full(max(int(M), 1), -1, dtype=np.int32)
+    check(lib().hgibbs_ld_greedy(M, W, _u64(fwd), _u64(bwd), od.ctypes.data_as(C_U32P), od.size, _u8(ml) if ml is not None else None, _ip(owner)))
+    return owner[:M]
 
 
 class Device:
@@ -482,6 +512,43 @@ class Device:
         """(products ms, reduce ms) of the last ld_scores()"""
         a, b = C.c_double(), C.c_double()
         check(self.L.hgibbs_last_ld_scores_ms(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def _ahead(self, ahead):
+        if ahead is None:
+            return None
+        ah = np.ascontiguousarray(ahead, dtype=np.uint32)
+        if ah.shape != (self.M,):
+            raise ValueError("ahead must be (%d,)" % self.M)
+        return ah
+
+    def ld_mask(self, W, t, ahead=None, backward=True):
+        """LD masks (hgibbs_ld_mask): fwd, bwd (M, wpr) uint64, wpr = (W + 63) // 64, and the number of passing pairs.  Bit (d - 1) % 64 of
+        fwd[j, (d - 1) // 64] says that pair (j, j + d) is in the window (d <= ahead[j]; None: min(W, M - 1 - j)) and has r * r >= t with
+        hgibbs_ld's r; bwd[q] holds the same bit for pair (q - d, q).  backward=False: bwd is not computed (None returned)."""
+        ah = self._ahead(ahead)
+        wpr = (max(int(W), 1) + 63) // 64
+        fwd = np.zeros((self.M, wpr), dtype=np.uint64)
+        bwd = np.zeros((self.M, wpr), dtype=np.uint64) if backward else None
+        n = C.c_uint64(0)
+        check(self.L.hgibbs_ld_mask(self.h, W, ah.ctypes.data_as(C_U32P) if ah is not None else None, t, _u64(fwd),
+                                    _u64(bwd) if backward else None, C.byref(n)))
+        return fwd, bwd, n.value
+
+    def ld_clump(self, W, t, order, may_lead=None, ahead=None):
+        """hgibbs_ld_clump: ld_mask, then ld_greedy on its masks.  Returns owner (M,) int32 and the number of passing pairs."""
+        ah = self._ahead(ahead)
+        od, ml = _order_and_leaders(self.M, order, may_lead)
+        owner = np.full(self.M, -1, dtype=np.int32)
+        n = C.c_uint64(0)
+        check(self.L.hgibbs_ld_clump(self.h, W, ah.ctypes.data_as(C_U32P) if ah is not None else None, t, od.ctypes.data_as(C_U32P), od.size,
+                                     _u8(ml) if ml is not None else None, _ip(owner), C.byref(n)))
+        return owner, n.value
+
+    def last_ld_mask_ms(self):
+        """(products ms, reduce ms) of the last ld_mask() or ld_clump()"""
+        a, b = C.c_double(), C.c_double()
+        check(self.L.hgibbs_last_ld_mask_ms(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
     def marker_dots(self, U, m0=0, count=None, raw=False):

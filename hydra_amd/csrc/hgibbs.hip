@@ -211,6 +211,8 @@ struct hgibbs_ctx {
     uint32_t grm_used = 0; // M_used and E of the last hgibbs_grm (hgibbs_grm_info)
     int grm_E = 0;
     int ldscore_piece = 0; // option ldscore_piece: band rows per piece of hgibbs_ld_scores (0 = automatic: the 2^24-pair bound)
+    int ldmask_piece = 0;  // option ldmask_piece: band rows per piece of hgibbs_ld_mask (0 = automatic: the 2^24-pair bound)
+    double ldm_ms[2] = {0, 0}; // device time of the last hgibbs_ld_mask: the products (zeroing, k_ld) and the reduce (zeroing the masks, k_ldm_reduce)
     double lds_ms[2] = {0, 0}; // device time of the last hgibbs_ld_scores: the products (zeroing, k_ld) and the reduce (k_lds_reduce, k_lds_final)
 };
 
@@ -1292,6 +1294,9 @@ int hgibbs_set_option(hgibbs_t h, const char* name, int64_t value)
     } else if (!std::strcmp(name, "ldscore_piece")) {
         if (value < 0 || value > (1 << 20)) return fail("ldscore_piece must be in [0,1048576] (0 = automatic)");
         h->ldscore_piece = (int)value;
+    } else if (!std::strcmp(name, "ldmask_piece")) {
+        if (value < 0 || value > (1 << 20)) return fail("ldmask_piece must be in [0,1048576] (0 = automatic)");
+        h->ldmask_piece = (int)value;
     } else if (!std::strcmp(name, "king_split")) {
         if (value < 0 || value > 65535) return fail("king_split must be in [0,65535] (0 = automatic)");
         h->king_split = (int)value;
@@ -2151,6 +2156,7 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
 #include "hg_rvar.hip.h"
 #include "hg_ld.hip.h"
 #include "hg_ldscore.hip.h"
+#include "hg_ldmask.hip.h"
 #include "hg_mdots.hip.h"
 #include "hg_king.hip.h"
 #include "hg_pca.hip.h"

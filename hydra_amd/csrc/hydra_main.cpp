@@ -52,6 +52,16 @@
 // --groupIndexFile behind a `base` column, and writes LDSC's PREFIX.l2.ldscore, .l2.M and .l2.M_5_50 as plain text (PREFIX defaults to
 // <dir>/<name>).  Not covered: cM windows, gzip, the regression itself (ldsc reads these files).
 //
+// `--clump FILE [--clump-p1 P1] [--clump-p2 P2] [--clump-r2 R2] [--clump-kb KB | --clump-snps W] [--clump-snp-field NAME] [--clump-field NAME]
+// [--clump-out F]` appended to a bayesMPI command line samples nothing either: it turns the table FILE of per-marker P values (the .assoc
+// of --assoc as it stands) into independent signals, PLINK's clump walk on the chain's own rows and standardisation: hgibbs_ld_mask reduces
+// the band to one bit per pair (r^2 >= R2 within KB kilobases, default 250, or W markers), hgibbs_ld_greedy walks the markers with P <= P2
+// by ascending P, those with P <= P1 lead (run_ldselect); <dir>/<name>.clumped (or F) has PLINK's columns.
+//
+// `--ld-prune T [--ld-prune-kb KB | --ld-prune-snps W] [--ld-prune-out PREFIX]` appended to a bayesMPI command line samples nothing either:
+// the same walk over every marker with a finite sd by descending minor allele frequency keeps a maximal set without a pair of r^2 > T
+// inside the window (default 50 markers) and writes PREFIX.prune.in and PREFIX.prune.out (PREFIX defaults to <dir>/<name>).
+//
 // Not reproduced (out of scope for the hot path): sparse
 // file formats, bayesFH, marker-sharded MPI, the .lst/tarball.
 // Multi-GPU: one process per GPU (RANK/WORLD_SIZE/LOCAL_RANK in the
@@ -113,6 +123,10 @@ struct Options { // src/options.hpp:20-138 (subset that reaches bayesMPI)
     std::string grmOut, grmSparse;                   // --grm-out PREFIX, --grm-sparse T as given (checked before the device)
     bool ldScore = false, ldScoreKbGiven = false, ldScoreSnpsGiven = false, ldScoreGroups = false, ldScoreRaw = false; // --ld-score; which --ld-score-* were given
     std::string ldScoreKb, ldScoreSnps, ldScoreSets, ldScoreOut; // --ld-score-kb KB, --ld-score-snps W as given (checked before the device), --ld-score-sets, --ld-score-out PREFIX
+    bool clump = false, clumpKbGiven = false, clumpSnpsGiven = false; // --clump FILE; which window option was given
+    std::string clumpFile, clumpP1, clumpP2, clumpR2, clumpKb, clumpSnps, clumpSnpField, clumpField, clumpOut; // --clump-* as given (checked before the device; empty: not given)
+    bool ldPrune = false, ldPruneKbGiven = false, ldPruneSnpsGiven = false; // --ld-prune T; which window option was given
+    std::string ldPruneT, ldPruneKb, ldPruneSnps, ldPruneOut; // --ld-prune T, --ld-prune-kb KB, --ld-prune-snps W as given, --ld-prune-out PREFIX
     int batch = 0, cpg = 0; // tuning knobs of this build (not hydra's)
 };
 
@@ -294,6 +308,31 @@ Options parse(int argc, const char* argv[])
         else if (a == "--ld-score-groups") o.ldScoreGroups = true;
         else if (a == "--ld-score-raw") o.ldScoreRaw = true;
         else if (a == "--ld-score-out") o.ldScoreOut = need(i);
+        else if (a == "--clump") {
+            o.clumpFile = need(i);
+            o.clump = true;
+        } else if (a == "--clump-p1") o.clumpP1 = need(i);
+        else if (a == "--clump-p2") o.clumpP2 = need(i);
+        else if (a == "--clump-r2") o.clumpR2 = need(i);
+        else if (a == "--clump-kb") {
+            o.clumpKb = need(i);
+            o.clumpKbGiven = true;
+        } else if (a == "--clump-snps") {
+            o.clumpSnps = need(i);
+            o.clumpSnpsGiven = true;
+        } else if (a == "--clump-snp-field") o.clumpSnpField = need(i);
+        else if (a == "--clump-field") o.clumpField = need(i);
+        else if (a == "--clump-out") o.clumpOut = need(i);
+        else if (a == "--ld-prune") {
+            o.ldPruneT = need(i);
+            o.ldPrune = true;
+        } else if (a == "--ld-prune-kb") {
+            o.ldPruneKb = need(i);
+            o.ldPruneKbGiven = true;
+        } else if (a == "--ld-prune-snps") {
+            o.ldPruneSnps = need(i);
+            o.ldPruneSnpsGiven = true;
+        } else if (a == "--ld-prune-out") o.ldPruneOut = need(i);
         else if (a == "--sparse-dir" || a == "--sparse-basename" ||
                  a == "--bed-to-sparse" || a == "--sparse-sync" || a == "--bed-sync")
             fatal("FATAL  : option " + a + " belongs to a part of hydra this build does not reproduce (SURVEY.md section 2)");
@@ -1872,6 +1911,46 @@ int run_grm(const Options& opt, const Cohort& co)
     return 0;
 }
 
+// The window of --ld-score, --clump and --ld-prune (`flag`) as an index interval per chromosome: every chromosome must be one run and,
+// with a kb window, bp must not decrease inside it; ahead[j] = the markers of j's chromosome behind it within wsnps markers, resp.
+// maxbp base pairs (two pointers), at most 4096 (the widest `op` takes)
+struct LdWindow {
+    std::vector<uint32_t> ahead;
+    unsigned long long npairs = 0;
+    uint32_t widest = 0;
+    size_t nchroms = 0;
+};
+
+LdWindow ld_window(const std::string& flag, const char* op, const BimRows& bim, const std::string& bimp, unsigned M, bool bySnps, long wsnps,
+                   long long maxbp)
+{
+    auto marker = [&](unsigned j) { return bim.id[j] + " (row " + std::to_string(j + 1) + ")"; };
+    std::map<std::string, int> chroms;
+    for (unsigned j = 0; j < M; ++j) {
+        if (j == 0 || bim.chr[j] != bim.chr[j - 1]) {
+            if (!chroms.emplace(bim.chr[j], 1).second)
+                fatal("FATAL  : " + bimp + ": chromosome " + bim.chr[j] + " comes back at marker " + marker(j) +
+                      " after another chromosome: " + flag + " needs every chromosome as one contiguous run");
+        } else if (!bySnps && bim.bp[j] < bim.bp[j - 1])
+            fatal("FATAL  : " + bimp + ": bp decreases at marker " + marker(j) + " inside chromosome " + bim.chr[j] +
+                  ": with a kb window the markers of a chromosome must be in bp order (the window must be an index interval; " + flag + "-snps takes any order)");
+    }
+    LdWindow w;
+    w.ahead.assign(M, 0);
+    w.nchroms = chroms.size();
+    for (unsigned j = 0, e = 0; j < M; ++j) { // e: one past the last marker of j's window
+        e = std::max(e, j + 1);
+        while (e < M && bim.chr[e] == bim.chr[j] && (bySnps ? (long)(e - j) <= wsnps : bim.bp[e] - bim.bp[j] <= maxbp)) ++e;
+        const unsigned n = e - 1 - j;
+        if (n > 4096)
+            fatal("FATAL  : marker " + marker(j) + " has " + std::to_string(n) + " markers ahead of it in its window, at most 4096 (the widest " + op + " takes): narrow the window");
+        w.ahead[j] = n;
+        w.npairs += n;
+        w.widest = std::max(w.widest, n);
+    }
+    return w;
+}
+
 // ---- --ld-score: LD scores of the training markers on the chain's rows ----
 int run_ldscore(const Options& opt, const Cohort& co)
 {
@@ -1879,38 +1958,19 @@ int run_ldscore(const Options& opt, const Cohort& co)
     const std::string bimp = opt.bedFile + ".bim";
     const unsigned M = co.Mtot;
     const BimRows bim = read_bim(bimp, M);
-    auto marker = [&](unsigned j) { return bim.id[j] + " (row " + std::to_string(j + 1) + ")"; };
 
-    // the window is an index interval: every chromosome one run and, with a kb window, bp not decreasing inside it
+    // the window is an index interval per chromosome
     const bool bySnps = opt.ldScoreSnpsGiven;
     double kb = 1000.0;
     long wsnps = 0;
     if (opt.ldScoreKbGiven) whole_num(opt.ldScoreKb, kb);
     if (bySnps) whole_int(opt.ldScoreSnps, wsnps);
     const long long maxbp = (long long)std::llround(1000.0 * kb);
-    std::map<std::string, int> chroms;
-    for (unsigned j = 0; j < M; ++j) {
-        if (j == 0 || bim.chr[j] != bim.chr[j - 1]) {
-            if (!chroms.emplace(bim.chr[j], 1).second)
-                fatal("FATAL  : " + bimp + ": chromosome " + bim.chr[j] + " comes back at marker " + marker(j) +
-                      " after another chromosome: --ld-score needs every chromosome as one contiguous run");
-        } else if (!bySnps && bim.bp[j] < bim.bp[j - 1])
-            fatal("FATAL  : " + bimp + ": bp decreases at marker " + marker(j) + " inside chromosome " + bim.chr[j] +
-                  ": with a kb window the markers of a chromosome must be in bp order (the window must be an index interval; --ld-score-snps takes any order)");
-    }
-    std::vector<uint32_t> ahead(M, 0);
-    unsigned long long npairs = 0;
-    uint32_t widest = 0;
-    for (unsigned j = 0, e = 0; j < M; ++j) { // e: one past the last marker of j's window
-        e = std::max(e, j + 1);
-        while (e < M && bim.chr[e] == bim.chr[j] && (bySnps ? (long)(e - j) <= wsnps : bim.bp[e] - bim.bp[j] <= maxbp)) ++e;
-        const unsigned n = e - 1 - j;
-        if (n > 4096)
-            fatal("FATAL  : marker " + marker(j) + " has " + std::to_string(n) + " markers ahead of it in its window, at most 4096 (the widest hgibbs_ld_scores takes): narrow the window");
-        ahead[j] = n;
-        npairs += n;
-        widest = std::max(widest, n);
-    }
+    const LdWindow win = ld_window("--ld-score", "hgibbs_ld_scores", bim, bimp, M, bySnps, wsnps, maxbp);
+    const std::vector<uint32_t>& ahead = win.ahead;
+    const unsigned long long npairs = win.npairs;
+    const uint32_t widest = win.widest;
+    const size_t nchroms = win.nchroms;
     const uint32_t W = std::max(1u, widest);
 
     // annotations: none (one column), or `base` and the sets or groups in definition order
@@ -1943,7 +2003,7 @@ int run_ldscore(const Options& opt, const Cohort& co)
     const uint32_t C = colname.empty() ? 1u : (uint32_t)colname.size();
     const std::string l2p = prefix + ".l2.ldscore", mp = prefix + ".l2.M", m5p = prefix + ".l2.M_5_50";
     std::printf("LDSCORE: %u markers, %zu chromosomes, window %s, %llu pairs in the window, widest window %u markers ahead, %u columns (%s r^2) -> %s\n", M,
-                chroms.size(), bySnps ? (std::to_string(wsnps) + " markers").c_str() : (std::to_string(maxbp) + " bp").c_str(), npairs, widest, C,
+                nchroms, bySnps ? (std::to_string(wsnps) + " markers").c_str() : (std::to_string(maxbp) + " bp").c_str(), npairs, widest, C,
                 opt.ldScoreRaw ? "raw" : "adjusted", l2p.c_str());
     std::fflush(stdout);
     if (!opt.ldScoreRaw && co.Ntot < 3) fatal("FATAL  : --ld-score: the adjusted r^2 - (1 - r^2) / (N - 2) needs at least three individuals (--ld-score-raw takes fewer)");
@@ -2002,16 +2062,213 @@ int run_ldscore(const Options& opt, const Cohort& co)
     return 0;
 }
 
+// ---- --clump, --ld-prune: LD clumping and pruning of the training markers ----
+// the arguments of the two modes with their defaults (check_clump_args and check_ldprune_args have refused what does not parse)
+double num_or(const std::string& t, double dflt)
+{
+    double v = dflt;
+    if (!t.empty()) whole_num(t, v);
+    return v;
+}
+
+// The table of --clump: the P of every row matched to the .bim by id (NaN: no usable row), and what was counted on the way
+struct ClumpTable {
+    std::vector<double> p; // per .bim marker
+    unsigned rows = 0, matched = 0, unknown = 0, badp = 0;
+};
+
+ClumpTable read_clump_table(const std::string& path, const std::string& snpField, const std::string& pField, const BimRows& bim, unsigned M,
+                            const std::string& bimp)
+{
+    std::ifstream in(path);
+    if (!in) fatal("FATAL  : --clump: can not open the file [" + path + "] to read.");
+    std::string line;
+    if (!std::getline(in, line)) fatal("FATAL  : --clump: " + path + " has no header line");
+    const std::vector<std::string> head = tokens(line, " \t\r");
+    size_t cs = head.size(), cp = head.size();
+    for (size_t c = 0; c < head.size(); ++c) {
+        if (head[c] == snpField && cs == head.size()) cs = c;
+        if (head[c] == pField && cp == head.size()) cp = c;
+    }
+    if (cs == head.size()) fatal("FATAL  : --clump: " + path + " has no column " + snpField + " in its header line (--clump-snp-field names the column of the marker ids)");
+    if (cp == head.size()) fatal("FATAL  : --clump: " + path + " has no column " + pField + " in its header line (--clump-field names the column of the P values)");
+    std::map<std::string, unsigned> at;
+    for (unsigned j = 0; j < M; ++j)
+        if (!at.emplace(bim.id[j], j).second) fatal("FATAL  : " + bimp + " lists SNP id " + bim.id[j] + " twice: --clump matches markers by id");
+    ClumpTable t;
+    t.p.assign(M, std::numeric_limits<double>::quiet_NaN());
+    std::map<std::string, unsigned> seen; // id -> line
+    for (unsigned ln = 2; std::getline(in, line); ++ln) {
+        const std::vector<std::string> tok = tokens(line, " \t\r");
+        if (tok.empty()) continue;
+        if (tok.size() <= std::max(cs, cp))
+            fatal("FATAL  : --clump: " + path + " line " + std::to_string(ln) + " has " + std::to_string(tok.size()) + " columns, the header names " + std::to_string(head.size()));
+        ++t.rows;
+        const auto first = seen.emplace(tok[cs], ln);
+        if (!first.second)
+            fatal("FATAL  : --clump: " + path + " line " + std::to_string(ln) + ": SNP id " + tok[cs] + " was already on line " + std::to_string(first.first->second) + ": one row per marker");
+        const auto hit = at.find(tok[cs]);
+        if (hit == at.end()) {
+            ++t.unknown;
+            continue;
+        }
+        ++t.matched;
+        double v = 0.0;
+        if (!whole_num(tok[cp], v) || !(v >= 0.0 && v <= 1.0)) { // NA, nan, anything that is no number in [0, 1]
+            ++t.badp;
+            continue;
+        }
+        t.p[hit->second] = v;
+    }
+    return t;
+}
+
+int run_ldselect(const Options& opt, const Cohort& co, bool clump)
+{
+    const std::string flag = clump ? "--clump" : "--ld-prune";
+    const char* tag = clump ? "CLUMP  " : "PRUNE  ";
+    const std::string base = opt.mcmcOutDir + "/" + opt.mcmcOutNam;
+    const std::string bimp = opt.bedFile + ".bim";
+    const unsigned M = co.Mtot;
+    const BimRows bim = read_bim(bimp, M);
+
+    // the window: kilobases (--clump: 250 unless markers are asked for) or markers (--ld-prune: 50 unless kilobases are asked for)
+    const bool kbGiven = clump ? opt.clumpKbGiven : opt.ldPruneKbGiven, snpsGiven = clump ? opt.clumpSnpsGiven : opt.ldPruneSnpsGiven;
+    const bool bySnps = clump ? snpsGiven : !kbGiven;
+    const double kb = num_or(clump ? opt.clumpKb : opt.ldPruneKb, 250.0);
+    long wsnps = 50;
+    if (snpsGiven) whole_int(clump ? opt.clumpSnps : opt.ldPruneSnps, wsnps);
+    const long long maxbp = (long long)std::llround(1000.0 * kb);
+    const LdWindow win = ld_window(flag, "hgibbs_ld_mask", bim, bimp, M, bySnps, wsnps, maxbp);
+    const uint32_t W = std::max(1u, win.widest);
+    const std::string window = bySnps ? std::to_string(wsnps) + " markers" : std::to_string(maxbp) + " bp";
+
+    // who takes part, before the device knows which markers have a finite sd
+    const double P1 = num_or(opt.clumpP1, 1e-4), P2 = num_or(opt.clumpP2, 1e-2), R2 = num_or(opt.clumpR2, 0.5), T = num_or(opt.ldPruneT, 0.0);
+    ClumpTable tab;
+    std::string out, outOut;
+    if (clump) {
+        tab = read_clump_table(opt.clumpFile, opt.clumpSnpField.empty() ? "SNP" : opt.clumpSnpField, opt.clumpField.empty() ? "P" : opt.clumpField, bim, M, bimp);
+        out = opt.clumpOut.empty() ? base + ".clumped" : opt.clumpOut;
+        unsigned part = 0, lead = 0;
+        for (unsigned j = 0; j < M; ++j) {
+            part += tab.p[j] <= P2 ? 1u : 0u;
+            lead += tab.p[j] <= P1 ? 1u : 0u;
+        }
+        std::printf("%s: %u rows read from %s, %u matched to the .bim (%u ids not in it, %u without a P in [0, 1]), %u participating (P <= %g), %u able to lead (P <= %g), "
+                    "window %s, %llu pairs in the window, widest window %u markers ahead, r^2 >= %g -> %s\n",
+                    tag, tab.rows, opt.clumpFile.c_str(), tab.matched, tab.unknown, tab.badp, part, P2, lead, P1, window.c_str(), win.npairs, win.widest, R2, out.c_str());
+    } else {
+        const std::string prefix = opt.ldPruneOut.empty() ? base : opt.ldPruneOut;
+        out = prefix + ".prune.in";
+        outOut = prefix + ".prune.out";
+        std::printf("%s: %u markers, %zu chromosomes, window %s, %llu pairs in the window, widest window %u markers ahead, r^2 > %g -> %s\n", tag, M, win.nchroms,
+                    window.c_str(), win.npairs, win.widest, T, out.c_str());
+    }
+    std::fflush(stdout);
+
+    std::vector<uint8_t> bed = read_bed(opt.bedFile, co.numInds, M);
+    if (clump ? opt.clumpOut.empty() : opt.ldPruneOut.empty()) make_out_dir(opt);
+    FILE* f = open_out(out, "w");
+    FILE* fo = clump ? nullptr : open_out(outOut, "w");
+
+    // the chain's rows and its standardisation; the counts give the allele frequencies
+    hgibbs_t dev = open_training(co, bed);
+    std::vector<double> mstd(M);
+    std::vector<uint64_t> n1(M), n2(M), nmiss(M);
+    hg_check(hgibbs_marker_stats(dev, nullptr, mstd.data(), n1.data(), n2.data(), nmiss.data()), "hgibbs_marker_stats");
+
+    // the order of priority: P ascending, resp. minor allele frequency descending; ties in .bim order
+    std::vector<double> key(M, 0.0);
+    std::vector<uint32_t> order;
+    std::vector<uint8_t> mayLead;
+    unsigned nosd = 0;
+    if (clump) mayLead.assign(M, 0);
+    for (unsigned j = 0; j < M; ++j) {
+        if (clump) {
+            if (!(tab.p[j] <= P2)) continue;
+            if (!std::isfinite(mstd[j])) {
+                ++nosd;
+                continue;
+            }
+            key[j] = tab.p[j];
+            mayLead[j] = tab.p[j] <= P1 ? 1 : 0;
+        } else {
+            if (!std::isfinite(mstd[j])) {
+                ++nosd;
+                continue;
+            }
+            const double called = (double)co.Ntot - (double)nmiss[j];
+            const double p = called > 0.0 ? ((double)n1[j] + 2.0 * (double)n2[j]) / (2.0 * called) : 0.0;
+            key[j] = -std::min(p, 1.0 - p);
+        }
+        order.push_back(j);
+    }
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
+
+    // one bit per pair from the device, then the walk on the host
+    const double t = clump ? R2 : std::nextafter(T, std::numeric_limits<double>::infinity());
+    const size_t nm = (size_t)M * ((W + 63u) / 64u);
+    std::vector<uint64_t> fwd(nm), bwd(nm);
+    uint64_t npass = 0;
+    hg_check(hgibbs_ld_mask(dev, W, win.ahead.data(), t, fwd.data(), bwd.data(), &npass), "hgibbs_ld_mask");
+    double products_ms = 0.0, reduce_ms = 0.0;
+    hg_check(hgibbs_last_ld_mask_ms(dev, &products_ms, &reduce_ms), "hgibbs_last_ld_mask_ms");
+    hgibbs_destroy(dev);
+    std::vector<int32_t> owner(M, -1);
+    const double t0 = now_s();
+    hg_check(hgibbs_ld_greedy(M, W, fwd.data(), bwd.data(), order.data(), (uint32_t)order.size(), clump ? mayLead.data() : nullptr, owner.data()), "hgibbs_ld_greedy");
+    const double walk_ms = 1000.0 * (now_s() - t0);
+
+    unsigned leaders = 0, claimed = 0;
+    if (clump) {
+        std::vector<std::vector<uint32_t>> members(M);
+        for (unsigned j = 0; j < M; ++j)
+            if (owner[j] >= 0 && (unsigned)owner[j] != j) members[owner[j]].push_back(j); // (.bim order)
+        std::fprintf(f, "CHR F SNP BP P TOTAL NSIG S05 S01 S001 S0001 SP2\n");
+        for (const uint32_t v : order) { // the leaders in the order they were taken
+            if ((uint32_t)owner[v] != v) continue;
+            unsigned bin[5] = {0, 0, 0, 0, 0};
+            std::string sp2;
+            for (const uint32_t q : members[v]) {
+                const double pq = tab.p[q];
+                ++bin[pq > 0.05 ? 0 : pq > 0.01 ? 1 : pq > 0.001 ? 2 : pq > 0.0001 ? 3 : 4];
+                sp2 += (sp2.empty() ? "" : ",") + bim.id[q] + "(1)";
+            }
+            std::fprintf(f, "%s 1 %s %lld %.12g %zu %u %u %u %u %u %s\n", bim.chr[v].c_str(), bim.id[v].c_str(), bim.bp[v], tab.p[v], members[v].size(), bin[0],
+                         bin[1], bin[2], bin[3], bin[4], sp2.empty() ? "NONE" : sp2.c_str());
+            ++leaders;
+            claimed += (unsigned)members[v].size();
+        }
+        close_out(f, out);
+        std::printf("%s: %u clumps with %u markers claimed among %zu participating (%u without a finite sd left out), %llu passing pairs, wrote %s "
+                    "(products %.3f ms, reduce %.3f ms on the device, the walk %.3f ms on the host)\n",
+                    tag, leaders, claimed, order.size(), nosd, (unsigned long long)npass, out.c_str(), products_ms, reduce_ms, walk_ms);
+    } else {
+        for (unsigned j = 0; j < M; ++j) {
+            const bool in = owner[j] >= 0 && (unsigned)owner[j] == j;
+            std::fprintf(in ? f : fo, "%s\n", bim.id[j].c_str());
+            leaders += in ? 1u : 0u;
+        }
+        close_out(f, out);
+        close_out(fo, outOut);
+        std::printf("%s: kept %u of %u markers in %s, %u in %s (%u without a finite sd among them), %llu passing pairs "
+                    "(products %.3f ms, reduce %.3f ms on the device, the walk %.3f ms on the host)\n",
+                    tag, leaders, M, out.c_str(), M - leaders, outOut.c_str(), nosd, (unsigned long long)npass, products_ms, reduce_ms, walk_ms);
+    }
+    return 0;
+}
+
 // ---- the analysis modes -------------------------------------------------------
 // An analysis mode is an option that, appended to a bayesMPI command line, samples nothing and runs one analysis on the chain's rows
-// (run_predict .. run_ldscore above).  What the modes share is refused in one place, from one row per mode.
+// (run_predict .. run_ldselect above).  What the modes share is refused in one place, from one row per mode.
 struct Mode {
     const char* flag;   // the option that asks for the mode
     bool given;
     const char* wmpi;   // how it refuses --mpibayes bayesWMPI, after its flag
     const char* orphan; // the first of its dependent options that was given: they need the mode (null: none was)
 };
-enum { PREDICT, LD, ASSOC, KING, PCA, PVE, GRM, LDSCORE, NMODES }; // the order in which a mode names the earlier ones it cannot be combined with
+enum { PREDICT, LD, ASSOC, KING, PCA, PVE, GRM, LDSCORE, CLUMP, LDPRUNE, NMODES }; // the order in which a mode names the earlier ones it cannot be combined with
 
 const char* first_given(std::initializer_list<std::pair<const char*, bool>> deps)
 {
@@ -2069,6 +2326,45 @@ void check_ldscore_args(const Options& opt)
     if (opt.ldScoreGroups && opt.groupIndexFile.empty()) fatal("FATAL  : --ld-score-groups needs --groupIndexFile");
 }
 
+// a threshold of --clump or --ld-prune: a number as a whole, in [0, 1]
+void check_unit(const char* flag, const std::string& t, const char* what)
+{
+    double v = 0.0;
+    if (!t.empty() && (!whole_num(t, v) || !(v >= 0.0 && v <= 1.0))) fatal(std::string("FATAL  : ") + flag + " " + t + ": " + what + " must be a number in [0, 1]");
+}
+
+// the window options of --clump and --ld-prune
+void check_ldselect_window(const std::string& flag, bool kbGiven, const std::string& kb, bool snpsGiven, const std::string& snps)
+{
+    if (kbGiven && snpsGiven) fatal("FATAL  : " + flag + "-kb cannot be combined with " + flag + "-snps: one way to define the window");
+    long w = 0;
+    double t = 0.0;
+    if (kbGiven && (!whole_num(kb, t) || !std::isfinite(t) || t < 0.0)) fatal("FATAL  : " + flag + "-kb " + kb + ": the window must be a finite number of kilobases >= 0");
+    if (snpsGiven && (!whole_int(snps, w) || w < 1 || w > 4096))
+        fatal("FATAL  : " + flag + "-snps " + snps + ": the window must be an integer from 1 to 4096 markers (the widest hgibbs_ld_mask takes)");
+}
+
+void check_clump_args(const Options& opt)
+{
+    check_unit("--clump-p1", opt.clumpP1, "the P a marker needs to lead a clump");
+    check_unit("--clump-p2", opt.clumpP2, "the P a marker needs to take part");
+    check_unit("--clump-r2", opt.clumpR2, "the threshold on r^2");
+    double p1 = 1e-4, p2 = 1e-2;
+    if (!opt.clumpP1.empty()) whole_num(opt.clumpP1, p1);
+    if (!opt.clumpP2.empty()) whole_num(opt.clumpP2, p2);
+    if (p2 < p1)
+        fatal("FATAL  : --clump-p2 " + (opt.clumpP2.empty() ? std::string("0.01") : opt.clumpP2) + " is below --clump-p1 " +
+              (opt.clumpP1.empty() ? std::string("0.0001") : opt.clumpP1) + ": a marker that may lead a clump must take part");
+    check_ldselect_window("--clump", opt.clumpKbGiven, opt.clumpKb, opt.clumpSnpsGiven, opt.clumpSnps);
+}
+
+void check_ldprune_args(const Options& opt)
+{
+    if (opt.ldPruneT.empty()) fatal("FATAL  : --ld-prune : the threshold on r^2 must be a number in [0, 1]");
+    check_unit("--ld-prune", opt.ldPruneT, "the threshold on r^2");
+    check_ldselect_window("--ld-prune", opt.ldPruneKbGiven, opt.ldPruneKb, opt.ldPruneSnpsGiven, opt.ldPruneSnps);
+}
+
 void check_pve_args(const Options& opt)
 {
     const char* const definer[4] = {"--pve-window-kb", "--pve-window-snps", "--pve-sets", "--pve-groups"};
@@ -2107,8 +2403,14 @@ void check_modes(const Options& opt, int nranks)
         {"--ld-score", opt.ldScore, takes,
          first_given({{"--ld-score-kb", opt.ldScoreKbGiven}, {"--ld-score-snps", opt.ldScoreSnpsGiven}, {"--ld-score-sets", !opt.ldScoreSets.empty()},
                       {"--ld-score-groups", opt.ldScoreGroups}, {"--ld-score-raw", opt.ldScoreRaw}, {"--ld-score-out", !opt.ldScoreOut.empty()}})},
+        {"--clump", opt.clump, takes,
+         first_given({{"--clump-p1", !opt.clumpP1.empty()}, {"--clump-p2", !opt.clumpP2.empty()}, {"--clump-r2", !opt.clumpR2.empty()}, {"--clump-kb", opt.clumpKbGiven},
+                      {"--clump-snps", opt.clumpSnpsGiven}, {"--clump-snp-field", !opt.clumpSnpField.empty()}, {"--clump-field", !opt.clumpField.empty()},
+                      {"--clump-out", !opt.clumpOut.empty()}})},
+        {"--ld-prune", opt.ldPrune, takes,
+         first_given({{"--ld-prune-kb", opt.ldPruneKbGiven}, {"--ld-prune-snps", opt.ldPruneSnpsGiven}, {"--ld-prune-out", !opt.ldPruneOut.empty()}})},
     };
-    for (const int i : {LD, PREDICT, ASSOC, KING, PCA, PVE, GRM, LDSCORE}) {
+    for (const int i : {LD, PREDICT, ASSOC, KING, PCA, PVE, GRM, LDSCORE, CLUMP, LDPRUNE}) {
         const Mode& m = modes[i];
         const std::string flag = m.flag;
         if (!m.given) {
@@ -2126,6 +2428,8 @@ void check_modes(const Options& opt, int nranks)
         if (i == PVE) check_pve_args(opt);
         if (i == GRM) check_grm_args(opt);
         if (i == LDSCORE) check_ldscore_args(opt);
+        if (i == CLUMP) check_clump_args(opt);
+        if (i == LDPRUNE) check_ldprune_args(opt);
     }
 }
 
@@ -2190,6 +2494,8 @@ int main(int argc, const char* argv[])
     if (opt.pve) return run_pve(opt, co);
     if (opt.grm) return run_grm(opt, co);
     if (opt.ldScore) return run_ldscore(opt, co);
+    if (opt.clump) return run_ldselect(opt, co, true);
+    if (opt.ldPrune) return run_ldselect(opt, co, false);
 
     std::vector<int32_t> groups;
     std::vector<std::vector<double>> mS;

@@ -182,6 +182,7 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
  *                   slower on MI355X; needs carry)
  *   graph           1: replay the launches from a captured HIP graph
  *   ldscore_piece   hgibbs_ld_scores: band rows per piece, 0..2^20 (0 = automatic)
+ *   ldmask_piece    hgibbs_ld_mask: band rows per piece, 0..2^20 (0 = automatic; rounded up to a multiple of 16)
  *   p2p, force_split, chunk, debug_timing, w_kernel_timing   transport selection and diagnostics */
 int hgibbs_set_option(hgibbs_t h, const char* name, int64_t value);
 /* Statistics of the last sweep: launches, markers per launch, device time of
@@ -302,6 +303,42 @@ int hgibbs_ld_scores(hgibbs_t h, uint32_t W, const uint32_t* ahead, uint32_t C, 
 /* device time of the last hgibbs_ld_scores in ms: the products (zeroing and hgibbs_ld's product kernel, every piece) and the reduce
  * (the reduction kernel of every piece, zeroing the accumulator and the final conversion); not the host copies */
 int hgibbs_last_ld_scores_ms(hgibbs_t h, double* products_ms, double* reduce_ms);
+
+/* ---- LD masks and the greedy selection on them ----- */
+/* One bit per pair of the band of the M loaded markers, forwards and backwards:
+ *   window   exactly that of hgibbs_ld_scores: a pair (j, q), j < q, is in the window iff q - j <= ahead[j].  ahead: M entries with
+ *            ahead[j] <= W and j + ahead[j] < M (refused otherwise), or NULL for min(W, M - 1 - j)
+ *   passes   a pair passes iff it is in the window, r is not NaN, and r * r >= t.  r is exactly hgibbs_ld's r, so both markers have a
+ *            finite mstd; the comparison is done on the f64 product
+ *   masks    wpr = (W + 63) / 64 words per marker.
+ *            fwd[j*wpr + (d-1)/64] bit (d-1)%64 is set iff pair (j, j + d) passes;
+ *            bwd[q*wpr + (d-1)/64] bit (d-1)%64 is set iff q >= d and pair (q - d, q) passes.
+ *            Every other bit is 0, including the bits of offsets above W in a row's last word.  bwd may be NULL.
+ *   npass    may be NULL: the number of passing pairs
+ * t must be finite and >= 0 (refused otherwise, with a message); t = 0 gives every in-window pair with a finite r.  The band never
+ * leaves the device: the four integer sums of a piece of band rows (hgibbs_ld's products, at most 2^24 pairs) are reduced there to the
+ * two masks, with plain stores forwards and 64-bit atomic ORs backwards.  So the result is bit-identical for any value of the options
+ * ldmask_piece (band rows per piece, 0 = automatic, rounded up to a multiple of 16, at most 2^20) and ld_split and for any repeat.
+ * One rank only; 1 <= W <= 4096; n_local < 2^29; a handle without genotypes and a null fwd are refused, and so is a call whose two
+ * M x wpr x 8-byte masks and a piece's sums do not fit in free device memory. */
+int hgibbs_ld_mask(hgibbs_t h, uint32_t W, const uint32_t* ahead, double t, uint64_t* fwd, uint64_t* bwd, uint64_t* npass);
+/* device time of the last hgibbs_ld_mask (or hgibbs_ld_clump) in ms: the products (zeroing the sums and hgibbs_ld's product kernel, every
+ * piece) and the reduce (zeroing the masks and the reduction kernel of every piece); not the host copies */
+int hgibbs_last_ld_mask_ms(hgibbs_t h, double* products_ms, double* reduce_ms);
+/* The greedy selection on two masks in hgibbs_ld_mask's layout (host only: no handle, no device).  order holds norder distinct marker
+ * indices below M, the participating markers in descending priority (a duplicate or an index >= M is refused by name); may_lead has M
+ * bytes, or is NULL for "all may".  owner[M] starts at -1 everywhere; then for k = 0 .. norder - 1, with v = order[k]:
+ *   if owner[v] != -1, continue; if v may not lead, continue;
+ *   otherwise owner[v] = v, and every participating q whose pair with v passes and whose owner is -1 gets owner[q] = v.  A pair with v
+ *   passes when its bit is set in v's forward or backward row.
+ * This is PLINK's clump walk: a participating marker that may not lead and is never claimed stays -1, and so does every marker that
+ * does not participate.  Refused: W outside 1..4096, M = 0 or M >= 2^31, a null fwd, bwd or owner, a null order with norder > 0. */
+int hgibbs_ld_greedy(uint32_t M, uint32_t W, const uint64_t* fwd, const uint64_t* bwd, const uint32_t* order, uint32_t norder,
+                     const uint8_t* may_lead, int32_t* owner);
+/* hgibbs_ld_mask into internal host buffers, then hgibbs_ld_greedy on them: owner is by definition what the two calls give, it refuses
+ * what either refuses, and hgibbs_last_ld_mask_ms stays valid after it.  npass may be NULL. */
+int hgibbs_ld_clump(hgibbs_t h, uint32_t W, const uint32_t* ahead, double t, const uint32_t* order, uint32_t norder,
+                    const uint8_t* may_lead, int32_t* owner, uint64_t* npass);
 
 /* ---- dots of the loaded markers against dense vectors */
 /* For markers j in [m0, m0 + count) of the loaded BED and K vectors u_k over this rank's n_local individuals:
