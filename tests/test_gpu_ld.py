@@ -32,13 +32,15 @@ def oracle_stats(geno):
 
 
 def reference(geno, W, block=64):
-    """sums (M, W, 4) int64: G, Bjq, Bqj, D of (j, j + d + 1), 0 past M; r (M, W) f64 = x_j'x_q / (N - 1), NaN past M"""
+    """sums (M, W, 4) int64: G, Bjq, Bqj, D of (j, j + d + 1), 0 past M; r (M, W) f64 = x_j'x_q / (N - 1), NaN past M and where an mstd
+    is not finite"""
     M, N = geno.shape
     g = np.where(geno == 3, 0, geno).astype(np.float64)
     c = (geno != 3).astype(np.float64)
     mave, mstd = oracle_stats(geno)
     with np.errstate(invalid="ignore"):
         x = np.where(geno == 3, 0.0, (g - mave[:, None]) * mstd[:, None])
+    fin = np.isfinite(mstd)
     sums = np.zeros((M, W, 4), dtype=np.int64)
     r = np.full((M, W), np.nan)
     for j0 in range(0, M, block):
@@ -48,6 +50,10 @@ def reference(geno, W, block=64):
         P = [g[j0:j1] @ g[j0:q1].T, g[j0:j1] @ c[j0:q1].T, c[j0:j1] @ g[j0:q1].T, c[j0:j1] @ c[j0:q1].T]
         with np.errstate(invalid="ignore"):
             X = x[j0:j1] @ x[j0:q1].T / (N - 1)
+        # r is NaN where an mstd is not finite.  A monomorphic column brings that about by itself (x = 0 x inf), a column with no call
+        # at all does not (mave and mstd are NaN, but x is 0 at every missing call), so the rule is applied
+        X[~fin[j0:j1], :] = np.nan
+        X[:, ~fin[j0:q1]] = np.nan
         for jj in range(j1 - j0):
             nd = min(W, M - 1 - (j0 + jj))  # pairs (j, j + d), d = 1 .. nd: columns jj + 1 .. jj + nd of the block's products
             for t in range(4):
@@ -108,6 +114,77 @@ def test_clean_data_and_padding():
         assert np.array_equal(s, ref_s)
         ok = ~np.isnan(ref_r)
         assert np.array_equal(np.isnan(r), ~ok) and np.max(np.abs(r[ok] - ref_r[ok])) <= 1e-12
+
+
+GRID_N = [2, 15, 16, 17, 63, 65, 511, 512, 513, 1025]
+GRID_M = [1, 2, 15, 16, 17, 63, 64, 65, 145]
+GRID_W = [1, 16, 129, 4096]  # 129: the first window with a second pass of LD_QP tiles; 4096 = LD_WMAX: 29 passes, 256 tiles past M
+
+
+def make_grid(N, M, seed, missing_cols=True):
+    """make() where it can plant its columns (M >= 4); below that by hand: polymorphic columns, one missing call in the last"""
+    if M >= 4:
+        return make(N, M, seed, missing_cols)
+    geno = synth.make_genotypes(M, N, seed=seed)
+    if missing_cols:
+        geno[M - 1, 0] = 3
+    return geno
+
+
+def check_band(dev, ref_s, ref_r, W, what):
+    """hgibbs_ld at window W against the leading W columns of a reference taken at a window at least as wide"""
+    r, s = dev.ld(W)
+    rs, rr = ref_s[:, :W], ref_r[:, :W]
+    assert np.array_equal(s, rs), "%s: integer sums differ" % (what,)
+    ok = ~np.isnan(rr)
+    assert np.array_equal(np.isnan(r), ~ok), "%s: NaN pattern differs" % (what,)
+    if ok.any():
+        assert np.max(np.abs(r[ok] - rr[ok])) <= 1e-12, "%s: r beyond 1e-12" % (what,)
+    return r, s
+
+
+def run_grid(N, missing_cols):
+    for M in GRID_M:
+        geno = make_grid(N, M, seed=N + M, missing_cols=missing_cols)
+        assert bool((geno == 3).any()) == missing_cols
+        dev = device(geno)
+        ref_s, ref_r = reference(geno, max(GRID_W))
+        for W in GRID_W:
+            r, s = check_band(dev, ref_s, ref_r, W, "N=%d M=%d W=%d" % (N, M, W))
+            if M == 1:  # a band without a pair
+                assert np.all(np.isnan(r)) and not s.any()
+        dev.close()
+
+
+@pytest.mark.parametrize("N", GRID_N)
+def test_edge_grid(N):
+    """individuals below one slice of 512 and next to 16, 64, 512 and 1024; markers of one tile of sixteen or less and next to 16, 64
+    and 144 (nine tiles: one pass); every window of GRID_W.  Data with missing calls: k_ld<true>"""
+    run_grid(N, True)
+
+
+@pytest.mark.parametrize("N", [16, 513])
+def test_edge_grid_clean(N):
+    """no missing call anywhere: k_ld<false>"""
+    run_grid(N, False)
+
+
+def test_the_piece_loop():
+    """hgibbs_ld's own pieces: 4 200 band rows x 4 096 offsets are 17.2 M pairs, two pieces of at most 2^24.  r against NumPy, bit for bit
+    against the same band fetched in chunks of 1 000 markers (one piece each), and those chunks' sums against NumPy exactly."""
+    N, M, W = 130, 4200, 4096
+    geno = make(N, M, seed=N + M)
+    dev = device(geno)
+    ref_s, ref_r = reference(geno, W, block=256)
+    r, none = dev.ld(W, sums=False)
+    assert none is None
+    ok = ~np.isnan(ref_r)
+    assert np.array_equal(np.isnan(r), ~ok) and np.max(np.abs(r[ok] - ref_r[ok])) <= 1e-12
+    for a in range(0, M, 1000):
+        n = min(1000, M - a)
+        rc, sc = dev.ld(W, m0=a, count=n)
+        assert same_bits(rc, r[a:a + n]), a
+        assert np.array_equal(sc, ref_s[a:a + n]), a
 
 
 def test_the_chains_own_dot():

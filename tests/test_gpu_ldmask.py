@@ -12,6 +12,7 @@ from hydra_amd import capi, synth
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ldwalk  # noqa: E402
 import orc  # noqa: E402
+from test_gpu_ld import GRID_M, GRID_W, make_grid  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -43,12 +44,15 @@ def reference_r(geno, W, block=64):
     mave, mstd = oracle_stats(geno)
     with np.errstate(invalid="ignore"):
         x = np.where(geno == 3, 0.0, (g - mave[:, None]) * mstd[:, None])
+    fin = np.isfinite(mstd)
     r = np.full((M, W), np.nan)
     for j0 in range(0, M, block):
         j1 = min(M, j0 + block)
         q1 = min(M, j1 + W)
         with np.errstate(invalid="ignore"):
             X = x[j0:j1] @ x[j0:q1].T / (N - 1)
+        X[~fin[j0:j1], :] = np.nan  # (a column with no call at all: x = 0 everywhere, tests/test_gpu_ld.py's reference)
+        X[:, ~fin[j0:q1]] = np.nan
         for jj in range(j1 - j0):
             nd = min(W, M - 1 - (j0 + jj))
             r[j0 + jj, :nd] = X[jj, jj + 1:jj + 1 + nd]
@@ -271,6 +275,23 @@ def test_ld_clump_equals_the_mask_and_the_python_walk(cohorts):
         dev.ld_clump(W, t, np.array([1, 1], dtype=np.uint32))
     with pytest.raises(capi.HgError, match="hgibbs_ld_mask: t = -1"):
         dev.ld_clump(W, -1.0, order)
+
+
+@pytest.mark.parametrize("N", [2, 16, 17, 513])
+def test_edge_grid_against_the_devices_own_band(N):
+    """tests/test_gpu_ld.py's grid of markers and windows (W = 4096: 64 words a marker), exactly, against the device's own band, which
+    that file holds to NumPy's at the same shapes"""
+    for M in GRID_M:
+        geno = make_grid(N, M, seed=N + M)
+        dev = device(geno)
+        band, _ = dev.ld(max(GRID_W), sums=False)
+        for W in GRID_W:
+            ahead = default_ahead(M, W)
+            for t in (0.0, 0.2):
+                fwd, bwd, npass = dev.ld_mask(W, t)
+                assert fwd.shape == (M, (W + 63) // 64)
+                check_masks(fwd, bwd, npass, band_from_r(band[:, :W], ahead, t), W, "N=%d M=%d W=%d t=%g" % (N, M, W, t))
+        dev.close()
 
 
 def test_refusals():

@@ -16,6 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXE = os.path.join(ROOT, "hydra_amd", "bin", "hydra_mi355x")
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import orc  # noqa: E402
+from test_gpu_ld import GRID_M, GRID_W, make_grid  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -41,12 +42,15 @@ def reference_r(geno, W, block=64):
     mave, mstd = oracle_stats(geno)
     with np.errstate(invalid="ignore"):
         x = np.where(geno == 3, 0.0, (g - mave[:, None]) * mstd[:, None])
+    fin = np.isfinite(mstd)
     r = np.full((M, W), np.nan)
     for j0 in range(0, M, block):
         j1 = min(M, j0 + block)
         q1 = min(M, j1 + W)
         with np.errstate(invalid="ignore"):
             X = x[j0:j1] @ x[j0:q1].T / (N - 1)
+        X[~fin[j0:j1], :] = np.nan  # (a column with no call at all: x = 0 everywhere, tests/test_gpu_ld.py's reference)
+        X[:, ~fin[j0:q1]] = np.nan
         for jj in range(j1 - j0):
             nd = min(W, M - 1 - (j0 + jj))
             r[j0 + jj, :nd] = X[jj, jj + 1:jj + 1 + nd]
@@ -259,6 +263,28 @@ def test_against_the_devices_own_band():
     ok = ~np.isnan(ref)
     # (the host's own f64 summation of up to 67 terms below 1 each rounds too: at most terms x 2^-53 x l, far below 2^-44 a term)
     assert np.all(np.abs(got - ref)[ok] <= (terms[:, None] * 2.0 ** -44)[ok])
+
+
+@pytest.mark.parametrize("N", [2, 16, 17, 513])
+def test_edge_grid_against_the_devices_own_band(N):
+    """tests/test_gpu_ld.py's grid of markers and windows (W = 4096: 64 reduce tiles a row): the scores of the device's own band, which
+    that file holds to NumPy's at the same shapes.  The terms are the band's own, so only the fixed point (2^-45 a term) and the
+    summation here differ: far inside close()'s 3e-12 x terms.  N = 2 without the adjustment, which needs N >= 3."""
+    for M in GRID_M:
+        geno = make_grid(N, M, seed=N + M)
+        dev = device(geno)
+        band, _ = dev.ld(max(GRID_W), sums=False)
+        _, finite = reference_r(geno, 1)
+        one = np.ones(M, dtype=np.uint64)
+        three = np.random.default_rng(N + M).integers(0, 8, size=M).astype(np.uint64)
+        for W in GRID_W:
+            ahead = default_ahead(M, W)
+            for adjust in ((True, False) if N >= 3 else (False,)):
+                for annot, C in ((one, 1), (three, 3)):
+                    ref, terms = scores_from_r(band[:, :W], finite, N, ahead, annot, C, adjust)
+                    got = dev.ld_scores(W, annot=annot if C > 1 else None, C=C, adjust=adjust)
+                    close(got, ref, terms, "N=%d M=%d W=%d C=%d adjust=%s" % (N, M, W, C, adjust))
+        dev.close()
 
 
 def test_refusals():

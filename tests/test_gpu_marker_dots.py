@@ -146,6 +146,63 @@ def test_bit_identical_across_chunkings_splits_and_repeats():
     assert dev.marker_dots(U, m0=M, count=0).shape == (0, K)
 
 
+@pytest.fixture(scope="module")
+def sweep_cohort():
+    """N = 513: two slices of 512 individuals, the second with one; M = 257: one marker past a workgroup of 256.  make()'s mixed clean
+    and missing tiles"""
+    N, M = 513, 257
+    geno = make(N, M, seed=N + M)
+    dev, mave, mstd = device(geno)
+    yield geno, dev, mave, mstd
+    dev.close()
+
+
+@pytest.mark.parametrize("K", range(1, 33))
+def test_every_vector_count(sweep_cohort, K):
+    """every K a call takes: passes of one, two, three (K = 5, 6) and four vector tiles, an odd last tile, and the second, third and
+    fourth pass of K > 8, 16, 24"""
+    geno, dev, mave, mstd = sweep_cohort
+    check(dev, geno, vectors(K, geno.shape[1], seed=K), mave, mstd)
+
+
+def test_chunks_at_the_largest_vector_count(sweep_cohort):
+    geno, dev, mave, mstd = sweep_cohort
+    M, K = geno.shape[0], 32
+    U = vectors(K, geno.shape[1], seed=40)
+    out0, raw0 = dev.marker_dots(U, raw=True)
+    for step in (1, 17, 128):
+        parts = [dev.marker_dots(U, m0=a, count=min(step, M - a), raw=True) for a in range(0, M, step)]
+        assert same_bits(np.concatenate([p[0] for p in parts]), out0), step
+        assert same_bits(np.concatenate([p[1] for p in parts]), raw0), step
+
+
+def make_edge(N, M, seed, missing):
+    """missing: make()'s data with one more missing call in every fourth column, so that small cohorts have some too; else data with no
+    missing call anywhere, which takes the build without the second product"""
+    if not missing:
+        return synth.make_genotypes(M, N, seed=seed)
+    geno = make(N, M, seed)
+    for j in range(1, M, 4):
+        geno[j, (3 * j) % N] = 3
+    if M == 1:
+        geno[0, N - 1] = 3
+    return geno
+
+
+@pytest.mark.parametrize("N", [2, 15, 16, 17, 63, 65, 511, 512, 513])
+@pytest.mark.parametrize("missing", [True, False])
+def test_edge_grid(N, missing):
+    """individuals below one slice of 512 and next to 16, 64 and 512; markers of one tile of sixteen or less and next to 16, 128 and 256;
+    K = 1, 5 (a pass with three of its four tiles used) and 9 (a second pass)"""
+    for M in (1, 15, 16, 17, 127, 128, 129, 255, 257):
+        geno = make_edge(N, M, seed=N + M, missing=missing)
+        assert bool((geno == 3).any()) == missing
+        dev, mave, mstd = device(geno)
+        for K in (1, 5, 9):
+            check(dev, geno, vectors(K, N, seed=K + M), mave, mstd)
+        dev.close()
+
+
 def test_refusals():
     N, M = 300, 40
     geno = make(N, M, seed=2)

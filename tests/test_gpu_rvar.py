@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from hydra_amd import capi, synth
-from test_gpu_score import EXE, _bet, load, weights
+from test_gpu_score import EXE, _bet, digit_samples, load, weights
 
 pytestmark = pytest.mark.gpu
 
@@ -126,6 +126,69 @@ def test_region_var_is_bit_identical_however_the_work_is_cut(missing):
         dev.set_option("score_sp", 0)
     dev.set_option("rvar_kb_max", 0)
     assert dev.last_region_var_ms() > 0.0
+
+
+DIGIT_ANCHOR = 100
+# 1, 2, 63 and 64 markers with the anchor among them, first, last and inside; and one of 65 (the anchor and 64 others), more than one
+# block of 64, which rvar_kb_max = 1 sends through score_dev_run and k_rvar_dense
+DIGIT_SETS = [np.array([DIGIT_ANCHOR]), np.array([DIGIT_ANCHOR, 150]), np.arange(38, 101), np.arange(100, 164), np.arange(64, 129)]
+
+
+def digit_reference(geno, kappa, lam, sets):
+    """mean and var of digit_samples' scores from exact integers.  v_i = K_i 256^d 2^-40 with K_i = sum_{j in set} [g != 3] (kappa g +
+    lambda), |K_i| <= 64 (2 x 127 + 127) = 24 384 < 2^15 for the anchor and at most 64 other markers: every sum of v (< 2^15 x 4097) and
+    of v^2 (< 2^30 x 4097 units) over at most 4 097 rows is exact in f64 in ANY order, so s1 and s2 are the exact ones, and k_rvar_final's
+    formula m = s1 / n, var = max(0, (s2 - s1 m) / (n - 1)) in f64 (no fused multiply-add: the build has -ffp-contract=off) is all
+    that rounds."""
+    n = geno.shape[1]
+    g = np.where(geno == 3, 0, geno).astype(np.int64)
+    called = (geno != 3).astype(np.int64)
+    mean, var = np.zeros((len(sets), 7)), np.zeros((len(sets), 7))
+    for r, idx in enumerate(sets):
+        K = kappa[:, idx] @ g[idx] + lam[:, idx] @ called[idx]  # (7, n) int64
+        assert np.abs(K).max() < 1 << 15
+        for d in range(7):
+            unit = np.ldexp(1.0, 8 * d - 40)
+            s1 = np.float64(int(K[d].sum())) * unit
+            s2 = np.float64(int((K[d] * K[d]).sum())) * unit * unit
+            m = s1 / np.float64(n)
+            mean[r, d] = m
+            var[r, d] = max(0.0, (s2 - s1 * m) / (np.float64(n) - 1.0))
+    return mean, var
+
+
+@pytest.mark.parametrize("N", [2, 63, 257, 4097])
+@pytest.mark.parametrize("missing", [0.0, 0.02])
+def test_region_var_bits_of_every_digit_on_its_own(N, missing):
+    """Weights for which every order of the sums over the rows gives the same bits (digit_samples, digit_reference), so mean and var are
+    compared bit for bit without restating rv_tree: the weights of sample d live in base-256 digit d alone (E = 40,
+    tests/test_score_restatement_cpu.py), and on clean data a kernel that drops that digit returns var = 0 there.  With missing calls
+    the second product's operand -(3 q_a + q_o) carries into digit d + 1 for d < 6."""
+    M = 200
+    geno = synth.make_genotypes(M, N, seed=N + 11, missing_rate=missing)
+    geno[DIGIT_ANCHOR] = 0
+    dev = capi.Device(0)
+    dev.load_bed(synth.pack_bed_columns(geno), N)
+    a, o, kappa, lam = digit_samples(M, DIGIT_ANCHOR, seed=N)
+    rmean, rvar = digit_reference(geno, kappa, lam, DIGIT_SETS)
+    assert np.all(rvar[0] == 0.0) and np.all(rmean[0] == 0.0)  # the anchor alone
+    assert np.all(np.any(rvar > 0.0, axis=0))  # every digit's sample varies in some set
+
+    def same(what):
+        mean, var = dev.region_var(a, o, DIGIT_SETS)
+        dm, dv = float(np.max(np.abs(mean - rmean))), float(np.max(np.abs(var - rvar)))
+        print(N, missing, what, "largest |device - restatement|: mean", dm, "var", dv)
+        assert np.array_equal(mean.view(np.int64), rmean.view(np.int64)), (what, dm)
+        assert np.array_equal(var.view(np.int64), rvar.view(np.int64)), (what, dv)
+        assert np.all(np.any(var > 0.0, axis=0)), what
+
+    for kb in (0, 1):  # 1: the set of 65 markers takes the dense path
+        dev.set_option("rvar_kb_max", kb)
+        for sp in (0, 2, 4, 8, 16):
+            dev.set_option("score_sp", sp)
+            same(("rvar_kb_max", kb, "score_sp", sp))
+    dev.set_option("score_sp", 0)
+    dev.set_option("rvar_kb_max", 0)
 
 
 @pytest.mark.parametrize("N,M", [(63, 20000), (130001, 3000)])
