@@ -16,120 +16,14 @@ import pytest
 
 from hydra_amd import capi, synth
 
+from pca_restate import VAL_BOUND, VEC_BOUND, dense, device, numpy_pca, same_bits, start_panel, structured, val_err, vec_err, zmat
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXE = os.path.join(ROOT, "hydra_amd", "bin", "hydra_mi355x")
 
-VEC_BOUND = 8.8e-14
-VAL_BOUND = 2.2e-14
-assert VEC_BOUND <= 1e-9 and VAL_BOUND <= 1e-12  # a result that needs more has lost half its digits
-
-
-# ---- data: P populations, Balding-Nichols allele frequencies, binomial genotypes, missing calls ----
-def structured(N, M, P=4, F=0.02, miss=0.02, seed=1, sizes=None):
-    rng = np.random.default_rng(seed)
-    p = rng.uniform(0.05, 0.5, size=M)
-    freq = rng.beta((p * (1 - F) / F)[:, None], ((1 - p) * (1 - F) / F)[:, None], size=(M, P))
-    if sizes is None:
-        pop = np.arange(N) % P
-    else:  # unequal populations: their eigenvalues spread
-        w = np.asarray(sizes, dtype=np.float64)
-        pop = np.searchsorted(np.cumsum(w / w.sum()), (np.arange(N) + 0.5) / N)
-    geno = rng.binomial(2, freq[:, pop]).astype(np.int8)
-    if miss > 0:
-        geno[rng.random((M, N)) < miss] = 3
-    return geno, pop
-
-
-def zmat(geno):
-    """Z (N x M) from synth.standardize with the markers outside M_used (no finite mstd) as zero columns, and M_used"""
-    with np.errstate(all="ignore"):
-        Z = synth.standardize(geno)
-    good = np.isfinite(Z).all(axis=0) & (geno != 3).any(axis=1)  # (a marker missing everywhere is a zero column there already)
-    Z[:, ~good] = 0.0
-    return Z, good
-
-
-def fix_sign(V, *others):
-    for k in range(V.shape[0]):
-        at = int(np.argmax(np.abs(V[k])))  # (the lowest index on a tie)
-        if V[k, at] < 0:
-            V[k] = -V[k]
-            for o in others:
-                o[k] = -o[k]
-
-
-def numpy_pca(Z, m_used, K, L, iters, tol, Q0):
-    """The algorithm of hgibbs_pca restated: same start panel, Householder QR, numpy.linalg.eigh for the Ritz step"""
-    Q = np.linalg.qr(Q0.T)[0]
-    prev, it = None, 0
-    while True:
-        it += 1
-        T = Z.T @ Q
-        th, W = np.linalg.eigh(T.T @ T)
-        th, W = th[::-1], W[:, ::-1]
-        change = np.inf if prev is None else np.max(np.abs(th[:K] - prev[:K]) / th[:K])
-        prev = th
-        if it >= iters or (tol > 0 and it > 1 and change <= tol):
-            break
-        Q = np.linalg.qr(Z @ T)[0]
-    val = th[:K] / m_used
-    V = (Q @ W[:, :K]).T.copy()
-    ld = (T @ W[:, :K] / np.sqrt(th[:K])).T.copy()
-    fix_sign(V, ld)
-    return val, V, ld, it
-
-
-def dense(Z, m_used, K):
-    lam, U = np.linalg.eigh(Z @ Z.T / m_used)
-    return lam[::-1], U[:, ::-1][:, :K].T
-
-
-def vec_err(V, R):
-    """max_k |v_k - s_k r_k|_2, s_k the sign that aligns them"""
-    return max(float(np.linalg.norm(V[k] - np.sign(V[k] @ R[k]) * R[k])) for k in range(V.shape[0]))
-
-
-def val_err(a, b):
-    return float(np.max(np.abs(a - b) / np.abs(b)))
-
-
-_M64 = (1 << 64) - 1
-
-
-def mix64(z):
-    """synth._mix64 on uint64 arrays"""
-    with np.errstate(over="ignore"):
-        z = z + np.uint64(0x9E3779B97F4A7C15)
-        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-        return z ^ (z >> np.uint64(31))
-
-
-def start_panel(seed, L, n):
-    """The NumPy twin of k_pca_init: entry (k, i) = (2 x + 1 - 2^52) 2^-52, x the top 52 bits of mix64((seed ^ mix64(k)) + i c)"""
-    Q0 = np.zeros((L, n))
-    i = np.arange(n, dtype=np.uint64)
-    for k in range(L):
-        assert int(mix64(np.array([k], dtype=np.uint64))[0]) == synth._mix64(k)
-        base = np.uint64((seed & _M64) ^ synth._mix64(k))
-        with np.errstate(over="ignore"):
-            h = mix64(base + i * np.uint64(0xD1B54A32D192ED03))
-        x = (h >> np.uint64(12)).astype(np.int64)
-        Q0[k] = np.ldexp((2 * x + 1 - (1 << 52)).astype(np.float64), -52)
-    return Q0
-
-
-def device(geno, keep=None):
-    M, N = geno.shape
-    dev = capi.Device(0)
-    dev.load_bed(synth.pack_bed_columns(geno), N, keep=keep)
-    return dev
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint64), np.ascontiguousarray(b).view(np.uint64))
+assert VEC_BOUND == 8.8e-14 and VAL_BOUND == 2.2e-14  # (the bounds of the docstring above; they live beside the shared helpers)
 
 
 def between_share(v, pop):
