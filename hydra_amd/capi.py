@@ -27,6 +27,7 @@ ABI_SYMBOLS = [
     "hgibbs_marker_dots", "hgibbs_last_marker_dots_ms", "hgibbs_king", "hgibbs_king_pairs", "hgibbs_king_pairs_get", "hgibbs_last_king_ms",
     "hgibbs_pca", "hgibbs_last_pca_ms", "hgibbs_region_var", "hgibbs_last_region_var_ms",
     "hgibbs_grm", "hgibbs_grm_info", "hgibbs_last_grm_ms",
+    "hgibbs_grm_rowsums", "hgibbs_last_grm_rowsums_ms", "hgibbs_he_fit",
     # BayesW
     "hgibbs_grand_seed", "hgibbs_grand_next", "hgibbs_ars_sample", "hgibbs_w_init", "hgibbs_w_marker_stats", "hgibbs_w_set_model",
     "hgibbs_w_reduce", "hgibbs_w_refresh_vi", "hgibbs_w_get_vi", "hgibbs_w_marker_sums", "hgibbs_w_sweep", "hgibbs_w_last_sweep_stats", "hgibbs_w_ars_device_probe",
@@ -51,6 +52,15 @@ class SweepStats(C.Structure):
 
 class PcaReport(C.Structure):
     _fields_ = [("iters_run", C.c_int32), ("m_used", C.c_uint32), ("ritz_change", C.c_double), ("resid", C.c_double * 32)]
+
+
+class HeForm(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("intercept", "slope", "h2", "intercept_se", "slope_se", "h2_se", "intercept_se_jk", "slope_se_jk",
+                                         "h2_se_jk", "intercept_p", "slope_p", "intercept_p_jk", "slope_p_jk")]
+
+
+class HeResult(C.Structure):
+    _fields_ = [("n_used", C.c_uint32), ("n_left_out", C.c_uint32), ("pairs", C.c_uint64), ("vp", C.c_double), ("cp", HeForm), ("sd", HeForm)]
 
 
 class RestartState(C.Structure):
@@ -216,6 +226,9 @@ def lib():
     L.hgibbs_grm.argtypes = [vp, C.c_uint32, C.c_uint32, dp, C.POINTER(C.c_int32)]
     L.hgibbs_grm_info.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
     L.hgibbs_last_grm_ms.argtypes = [vp, dp]
+    L.hgibbs_grm_rowsums.argtypes = [vp, C.c_int, dp, dp, dp, dp, dp, u32p]
+    L.hgibbs_last_grm_rowsums_ms.argtypes = [vp, dp, dp]
+    L.hgibbs_he_fit.argtypes = [C.c_uint32, dp, dp, dp, dp, dp, u32p, C.POINTER(HeResult)]
     _lib = L
     return L
 
@@ -271,6 +284,23 @@ def ld_greedy(M, W, fwd, bwd, order, may_lead=None):
     owner = np.full(max(int(M), 1), -1, dtype=np.int32)
     check(lib().hgibbs_ld_greedy(M, W, _u64(fwd), _u64(bwd), od.ctypes.data_as(C_U32P), od.size, _u8(ml) if ml is not None else None, _ip(owner)))
     return owner[:M]
+
+
+def he_fit(y, ay, ayy, a1, a2, partners):
+    """hgibbs_he_fit (host only): Haseman-Elston regression from the row sums of Device.grm_rowsums for Y = [y, y * y] (ay = A y,
+    ayy = A (y o y)).  Returns a dict: n_used, n_left_out, pairs, vp, and under "cp" and "sd" a dict of intercept, slope, h2, their OLS
+    and jackknife SEs (…_se, …_se_jk) and the P values of intercept and slope (…_p, …_p_jk)."""
+    v = [np.ascontiguousarray(x, dtype=np.float64).reshape(-1) for x in (y, ay, ayy, a1, a2)]
+    pt = np.ascontiguousarray(partners, dtype=np.uint32).reshape(-1)
+    n = v[0].size
+    if any(x.size != n for x in v) or pt.size != n:
+        raise ValueError("he_fit: y, ay, ayy, a1, a2 and partners must have one length")
+    res = HeResult()
+    check(lib().hgibbs_he_fit(n, *[_dp(x) for x in v], pt.ctypes.data_as(C_U32P), C.byref(res)))
+    out = {k: getattr(res, k) for k in ("n_used", "n_left_out", "pairs", "vp")}
+    for form in ("cp", "sd"):
+        out[form] = {k: getattr(getattr(res, form), k) for k, _ in HeForm._fields_}
+    return out
 
 
 class Device:
@@ -619,6 +649,25 @@ class Device:
         v = C.c_double()
         check(self.L.hgibbs_last_grm_ms(self.h, C.byref(v)))
         return v.value
+
+    def grm_rowsums(self, Y):
+        """Row sums of the relationship matrix over each row's partners (hgibbs_grm_rowsums): Y (P, n_local) or (n_local,).  Returns
+        ay (n_local, P) = A Y', a1 and a2 (n_local,) = the sums of A and of A^2, diag (n_local,) and partners (n_local,) uint32."""
+        Y = np.ascontiguousarray(np.atleast_2d(np.asarray(Y, dtype=np.float64)))
+        P, n = Y.shape[0], self.n_local
+        if Y.ndim != 2 or (P and n and Y.shape[1] != n):
+            raise ValueError("Y must be (P, %d)" % n)
+        ay = np.zeros((n, P))
+        a1, a2, diag = np.zeros(n), np.zeros(n), np.zeros(n)
+        partners = np.zeros(n, dtype=np.uint32)
+        check(self.L.hgibbs_grm_rowsums(self.h, P, _dp(Y), _dp(ay), _dp(a1), _dp(a2), _dp(diag), partners.ctypes.data_as(C_U32P)))
+        return ay, a1, a2, diag, partners
+
+    def last_grm_rowsums_ms(self):
+        """(products ms, reduce ms) of the last grm_rowsums()"""
+        a, b = C.c_double(), C.c_double()
+        check(self.L.hgibbs_last_grm_rowsums_ms(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def pca(self, K, L=None, iters=20, tol=1e-10, Q0=None, seed=1, loadings=False):
         """The top K principal components of the loaded rows (hgibbs_pca): eigenvalues (K,), PCs (K, n_local), loadings (K, M) or None,

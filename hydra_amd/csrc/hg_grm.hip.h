@@ -306,22 +306,22 @@ struct GrmPiece {
     std::vector<uint32_t> bp;
 };
 
-} // namespace
-
-extern "C" int hgibbs_grm(hgibbs_t h, uint32_t a0, uint32_t acount, double* S, int32_t* nsnp)
+int grm_mmax_check(const hgibbs_ctx* h, const char* who)
 {
-    if (king_check(h, "hgibbs_grm")) return 1;
-    h->grm_ms = 0.0;
-    h->grm_used = 0;
-    h->grm_E = 0;
-    if (h->M > GR_MMAX) return fail("hgibbs_grm: %u markers, at most %u (a digit's sum, at most 384 a marker, stays inside an i32)", h->M, GR_MMAX);
-    if (acount == 0) return fail("hgibbs_grm: no rows asked for (acount = 0)");
-    if ((uint64_t)a0 + acount > h->n_local)
-        return fail("hgibbs_grm: rows [%u, %llu) out of range (n_local = %u)", a0, (unsigned long long)a0 + acount, h->n_local);
-    HIP_TRY(hipSetDevice(h->device));
-    if (compute_stats(h)) return 1;
+    if (h->M > GR_MMAX) return fail("%s: %u markers, at most %u (a digit's sum, at most 384 a marker, stays inside an i32)", who, h->M, GR_MMAX);
+    return 0;
+}
 
+// The frame of hgibbs_grm and hgibbs_grm_rowsums (`who`): rows [a0, a0 + acount) in pieces of at most grm_piece (GR_PIECE) pairs, the
+// table and the image, then per piece the products, which leave the piece's S and NSNP on the device, and step(piece, pairs done
+// before it, dS, dn), which does with them what the caller is there for.  The caller has set the device and run compute_stats (the
+// marker stats are a precondition, not computed here); the device time of the kernels launched here goes to total_ms, M_used and E to
+// used and E.
+template <class Step>
+int grm_pieces(hgibbs_ctx* h, const char* who, uint32_t a0, uint32_t acount, double& total_ms, uint32_t& used, int& E, Step&& step)
+{
     // pieces of rows, at most GR_PIECE pairs each (a row alone has fewer), and their block pairs
+    const uint64_t piece = h->grm_piece ? (uint64_t)h->grm_piece : GR_PIECE;
     const uint32_t nks = (h->M + 63u) / 64u, aend = a0 + acount;
     std::vector<GrmPiece> pieces;
     uint64_t maxpairs = 0, maxbp = 0;
@@ -330,7 +330,7 @@ extern "C" int hgibbs_grm(hgibbs_t h, uint32_t a0, uint32_t acount, double* S, i
         GrmPiece pc{};
         pc.p0 = p0;
         uint32_t a = p0;
-        while (a < aend && (a == p0 || pc.pairs + a + 1ull <= GR_PIECE)) pc.pairs += a++ + 1ull;
+        while (a < aend && (a == p0 || pc.pairs + a + 1ull <= piece)) pc.pairs += a++ + 1ull;
         pc.pc = a - p0;
         pc.ta0 = p0 / 16u;
         const uint32_t tlast = (a - 1u) / 16u, nba = (tlast - pc.ta0) / KG_BT + 1u;
@@ -356,12 +356,11 @@ extern "C" int hgibbs_grm(hgibbs_t h, uint32_t a0, uint32_t acount, double* S, i
     const size_t tabw = (size_t)4u * nks * GR_TW;
     const size_t extra = tabw * sizeof(rl_v4i) + maxbp * sizeof(uint32_t) +
                          maxpairs * (sizeof(double) + sizeof(int32_t) + (parts ? GR_NA * sizeof(int32_t) : 0));
-    if (king_image(h, extra, img, npi, ntile, nks2, "hgibbs_grm")) return 1;
+    if (king_image(h, extra, img, npi, ntile, nks2, who)) return 1;
     if (tab.alloc(tabw) || meta.alloc(2) || bpairs.alloc(maxbp) || dS.alloc(maxpairs) || dn.alloc(maxpairs)) return 1;
     if (parts && dacc.alloc(maxpairs * GR_NA)) return 1;
 
     // W and M_used, then the table and the image
-    double total_ms = 0.0;
     const uint32_t mblocks = (h->M + 255u) / 256u;
     if (lap_begin(h)) return 1;
     HIP_TRY(hipMemsetAsync(meta, 0, 2 * sizeof(unsigned long long), h->stream));
@@ -371,8 +370,8 @@ extern "C" int hgibbs_grm(hgibbs_t h, uint32_t a0, uint32_t acount, double* S, i
     if (lap_end(h, total_ms)) return 1;
     unsigned long long mh[2] = {0, 0};
     HIP_TRY(hipMemcpy(mh, meta, sizeof mh, hipMemcpyDeviceToHost));
-    if (mh[1] == 0) return fail("hgibbs_grm: no marker of the %u loaded has a finite mstd (M_used = 0): the matrix is not defined", h->M);
-    int E = 0;
+    if (mh[1] == 0) return fail("%s: no marker of the %u loaded has a finite mstd (M_used = 0): the matrix is not defined", who, h->M);
+    E = 0;
     {
         double W;
         std::memcpy(&W, &mh[0], sizeof W);
@@ -382,6 +381,7 @@ extern "C" int hgibbs_grm(hgibbs_t h, uint32_t a0, uint32_t acount, double* S, i
             E = 52 - e;
         }
     }
+    used = (uint32_t)mh[1];
     if (lap_begin(h)) return 1;
     k_grm_table<<<mblocks, 256, 0, h->stream>>>(h->mave, h->mstd, h->M, E, reinterpret_cast<uint8_t*>(tab.p));
     HIP_TRY(hipGetLastError());
@@ -419,12 +419,39 @@ extern "C" int hgibbs_grm(hgibbs_t h, uint32_t a0, uint32_t acount, double* S, i
         }
         HIP_TRY(hipGetLastError());
         if (lap_end(h, total_ms)) return 1;
-        if (S) HIP_TRY(hipMemcpy(S + done, dS, pc.pairs * sizeof(double), hipMemcpyDeviceToHost));
-        if (nsnp) HIP_TRY(hipMemcpy(nsnp + done, dn, pc.pairs * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (step(pc, done, (const double*)dS, (const int32_t*)dn)) return 1;
         done += pc.pairs;
     }
+    return 0;
+}
+
+} // namespace
+
+extern "C" int hgibbs_grm(hgibbs_t h, uint32_t a0, uint32_t acount, double* S, int32_t* nsnp)
+{
+    if (king_check(h, "hgibbs_grm")) return 1;
+    h->grm_ms = 0.0;
+    h->grm_used = 0;
+    h->grm_E = 0;
+    if (grm_mmax_check(h, "hgibbs_grm")) return 1;
+    if (acount == 0) return fail("hgibbs_grm: no rows asked for (acount = 0)");
+    if ((uint64_t)a0 + acount > h->n_local)
+        return fail("hgibbs_grm: rows [%u, %llu) out of range (n_local = %u)", a0, (unsigned long long)a0 + acount, h->n_local);
+    HIP_TRY(hipSetDevice(h->device));
+    if (compute_stats(h)) return 1;
+
+    double total_ms = 0.0;
+    uint32_t used = 0;
+    int E = 0;
+    // the step of a piece: the copy out
+    auto copy_out = [&](const GrmPiece& pc, size_t done, const double* dS, const int32_t* dn) -> int {
+        if (S) HIP_TRY(hipMemcpy(S + done, dS, pc.pairs * sizeof(double), hipMemcpyDeviceToHost));
+        if (nsnp) HIP_TRY(hipMemcpy(nsnp + done, dn, pc.pairs * sizeof(int32_t), hipMemcpyDeviceToHost));
+        return 0;
+    };
+    if (grm_pieces(h, "hgibbs_grm", a0, acount, total_ms, used, E, copy_out)) return 1;
     h->grm_ms = total_ms;
-    h->grm_used = (uint32_t)mh[1];
+    h->grm_used = used;
     h->grm_E = E;
     return 0;
 }

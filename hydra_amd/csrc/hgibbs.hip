@@ -210,6 +210,8 @@ struct hgibbs_ctx {
     double grm_ms = 0.0;   // device time of the last hgibbs_grm (scale, table, image, zeroing, products, rounding)
     uint32_t grm_used = 0; // M_used and E of the last hgibbs_grm (hgibbs_grm_info)
     int grm_E = 0;
+    long long grm_piece = 0; // option grm_piece: pairs per piece of rows of hgibbs_grm and hgibbs_grm_rowsums (0 = GR_PIECE); a row alone may exceed it
+    double grs_ms[2] = {0, 0}; // device time of the last hgibbs_grm_rowsums: the products (hgibbs_grm's kernels) and the reduce (zeroing, k_grs_reduce, k_grs_final)
     int ldscore_piece = 0; // option ldscore_piece: band rows per piece of hgibbs_ld_scores (0 = automatic: the 2^24-pair bound)
     int ldmask_piece = 0;  // option ldmask_piece: band rows per piece of hgibbs_ld_mask (0 = automatic: the 2^24-pair bound)
     double ldm_ms[2] = {0, 0}; // device time of the last hgibbs_ld_mask: the products (zeroing, k_ld) and the reduce (zeroing the masks, k_ldm_reduce)
@@ -1303,6 +1305,9 @@ int hgibbs_set_option(hgibbs_t h, const char* name, int64_t value)
     } else if (!std::strcmp(name, "grm_split")) {
         if (value < 0 || value > 65535) return fail("grm_split must be in [0,65535] (0 = automatic)");
         h->grm_split = (int)value;
+    } else if (!std::strcmp(name, "grm_piece")) {
+        if (value < 0 || value > (1ll << 25)) return fail("grm_piece must be in [0,33554432] (0 = automatic: 2^25 pairs)");
+        h->grm_piece = (long long)value;
     } else if (!std::strcmp(name, "mdots_split")) {
         if (value < 0 || value > 65535) return fail("mdots_split must be in [0,65535] (0 = automatic)");
         h->mdots_split = (int)value;
@@ -2161,3 +2166,4 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
 #include "hg_king.hip.h"
 #include "hg_pca.hip.h"
 #include "hg_grm.hip.h"
+#include "hg_grmsums.hip.h"

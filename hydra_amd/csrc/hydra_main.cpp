@@ -62,6 +62,13 @@
 // the same walk over every marker with a finite sd by descending minor allele frequency keeps a maximal set without a pair of r^2 > T
 // inside the window (default 50 markers) and writes PREFIX.prune.in and PREFIX.prune.out (PREFIX defaults to <dir>/<name>).
 //
+// `--he [--he-out F] [--he-rows]` appended to a bayesMPI command line samples nothing either: it estimates the SNP heritability of the
+// chain's scaled phenotype (with --covariates, [1 | covariates] projected out as --assoc does and scaled again) by Haseman-Elston
+// regression on the off-diagonal entries of the relationship matrix of --grm, which never leaves the device: hgibbs_grm_rowsums reduces it
+// to a few sums per row, hgibbs_he_fit fits HE-CP and HE-SD with OLS and delete-one-individual jackknife standard errors (run_he,
+// DESIGN.md section 22).  <dir>/<name>.HEreg (or F) has the layout of GCTA's --HEreg; with --he-rows <out>.rows has the per-row sums.
+// Not covered: bivariate HE, several matrices, REML.
+//
 // Not reproduced (out of scope for the hot path): sparse
 // file formats, bayesFH, marker-sharded MPI, the .lst/tarball.
 // Multi-GPU: one process per GPU (RANK/WORLD_SIZE/LOCAL_RANK in the
@@ -121,6 +128,8 @@ struct Options { // src/options.hpp:20-138 (subset that reaches bayesMPI)
     std::string pveKb, pveSnps, pveSets, pveThreshold, pveOut; // --pve-window-kb KB, --pve-window-snps W, --pve-threshold T as given, --pve-sets, --pve-out
     bool grm = false, grmSparseGiven = false;        // --grm: genomic relationship matrix of the chain's rows; --grm-sparse given
     std::string grmOut, grmSparse;                   // --grm-out PREFIX, --grm-sparse T as given (checked before the device)
+    bool he = false, heRows = false;                 // --he: Haseman-Elston regression on the chain's rows; --he-rows: the per-row sums too
+    std::string heOut;                               // --he-out F
     bool ldScore = false, ldScoreKbGiven = false, ldScoreSnpsGiven = false, ldScoreGroups = false, ldScoreRaw = false; // --ld-score; which --ld-score-* were given
     std::string ldScoreKb, ldScoreSnps, ldScoreSets, ldScoreOut; // --ld-score-kb KB, --ld-score-snps W as given (checked before the device), --ld-score-sets, --ld-score-out PREFIX
     bool clump = false, clumpKbGiven = false, clumpSnpsGiven = false; // --clump FILE; which window option was given
@@ -294,6 +303,9 @@ Options parse(int argc, const char* argv[])
         else if (a == "--pve-bin") o.pveBin = true;
         else if (a == "--grm") o.grm = true;
         else if (a == "--grm-out") o.grmOut = need(i);
+        else if (a == "--he") o.he = true;
+        else if (a == "--he-out") o.heOut = need(i);
+        else if (a == "--he-rows") o.heRows = true;
         else if (a == "--grm-sparse") {
             o.grmSparse = need(i);
             o.grmSparseGiven = true;
@@ -1343,6 +1355,50 @@ std::vector<double> chol_solve(const std::vector<double>& L, int q, std::vector<
     return b;
 }
 
+// the chain's scaling of a phenotype (hydra_chain.cpp): centre, then y'y = N - 1
+void scale_phenotype(std::vector<double>& y, unsigned N)
+{
+    double mean = 0.0;
+    for (unsigned i = 0; i < N; ++i) mean += y[i];
+    mean /= N;
+    for (unsigned i = 0; i < N; ++i) y[i] -= mean;
+    double sqn = 0.0;
+    for (unsigned i = 0; i < N; ++i) sqn += y[i] * y[i];
+    sqn = std::sqrt((double)(N - 1) / sqn);
+    for (unsigned i = 0; i < N; ++i) y[i] *= sqn;
+}
+
+// Z = [1 | covariates] over N rows and the projection off its columns, for --assoc and --he (`flag`: who refuses dependent columns)
+struct CovProjector {
+    unsigned N;
+    int q;
+    std::vector<double> Z; // column-major: Z[c * N + i]
+    std::vector<double> L; // the Cholesky factor of Z'Z
+    CovProjector(const char* flag, const std::vector<double>& covX, int C, unsigned N_) : N(N_), q(1 + C), Z((size_t)(1 + C) * N_), L((size_t)(1 + C) * (1 + C))
+    {
+        for (unsigned i = 0; i < N; ++i) {
+            Z[i] = 1.0;
+            for (int c = 0; c < C; ++c) Z[(size_t)(1 + c) * N + i] = covX[(size_t)i * C + c];
+        }
+        for (int a = 0; a < q; ++a)
+            for (int b = 0; b < q; ++b) {
+                double v = 0.0;
+                for (unsigned i = 0; i < N; ++i) v += Z[(size_t)a * N + i] * Z[(size_t)b * N + i];
+                L[(size_t)a * q + b] = v;
+            }
+        if (!cholesky(L, q)) fatal(std::string("FATAL  : ") + flag + ": the covariates are rank-deficient (Z = [1 | covariates] has dependent columns)");
+    }
+    void project(std::vector<double>& v) const // v <- v - Z (Z'Z)^-1 Z'v
+    {
+        std::vector<double> w(q, 0.0);
+        for (int a = 0; a < q; ++a)
+            for (unsigned i = 0; i < N; ++i) w[a] += Z[(size_t)a * N + i] * v[i];
+        w = chol_solve(L, q, w);
+        for (int a = 0; a < q; ++a)
+            for (unsigned i = 0; i < N; ++i) v[i] -= Z[(size_t)a * N + i] * w[a];
+    }
+};
+
 int run_assoc(const Options& opt, const Cohort& co, const std::vector<double>& y_raw, const std::vector<double>& covX, int C)
 {
     const std::string base = opt.mcmcOutDir + "/" + opt.mcmcOutNam;
@@ -1374,39 +1430,12 @@ int run_assoc(const Options& opt, const Cohort& co, const std::vector<double>& y
     std::fflush(stdout);
     if ((long long)N <= (long long)q + 1) fatal("FATAL  : --assoc needs more individuals (" + std::to_string(N) + ") than covariates + 2");
 
-    // the chain's scaled phenotype (hydra_chain.cpp: centre, then y'y = N - 1) and Z = [1 | covariates]
+    // the chain's scaled phenotype and Z = [1 | covariates]
     std::vector<double> y(y_raw);
-    {
-        double mean = 0.0;
-        for (unsigned i = 0; i < N; ++i) mean += y[i];
-        mean /= N;
-        for (unsigned i = 0; i < N; ++i) y[i] -= mean;
-        double sqn = 0.0;
-        for (unsigned i = 0; i < N; ++i) sqn += y[i] * y[i];
-        sqn = std::sqrt((double)(N - 1) / sqn);
-        for (unsigned i = 0; i < N; ++i) y[i] *= sqn;
-    }
-    std::vector<double> Z((size_t)q * N); // column-major: Z[c * N + i]
-    for (unsigned i = 0; i < N; ++i) {
-        Z[i] = 1.0;
-        for (int c = 0; c < C; ++c) Z[(size_t)(1 + c) * N + i] = covX[(size_t)i * C + c];
-    }
-    std::vector<double> L((size_t)q * q);
-    for (int a = 0; a < q; ++a)
-        for (int b = 0; b < q; ++b) {
-            double v = 0.0;
-            for (unsigned i = 0; i < N; ++i) v += Z[(size_t)a * N + i] * Z[(size_t)b * N + i];
-            L[(size_t)a * q + b] = v;
-        }
-    if (!cholesky(L, q)) fatal("FATAL  : --assoc: the covariates are rank-deficient (Z = [1 | covariates] has dependent columns)");
-    auto project = [&](std::vector<double>& v) { // v <- v - Z (Z'Z)^-1 Z'v
-        std::vector<double> w(q, 0.0);
-        for (int a = 0; a < q; ++a)
-            for (unsigned i = 0; i < N; ++i) w[a] += Z[(size_t)a * N + i] * v[i];
-        w = chol_solve(L, q, w);
-        for (int a = 0; a < q; ++a)
-            for (unsigned i = 0; i < N; ++i) v[i] -= Z[(size_t)a * N + i] * w[a];
-    };
+    scale_phenotype(y, N);
+    const CovProjector proj("--assoc", covX, C, N);
+    const std::vector<double>&Z = proj.Z, &L = proj.L;
+    auto project = [&](std::vector<double>& v) { proj.project(v); };
 
     std::vector<uint8_t> bed = read_bed(opt.bedFile, co.numInds, co.Mtot);
     if (opt.assocOut.empty()) make_out_dir(opt);
@@ -2259,16 +2288,88 @@ int run_ldselect(const Options& opt, const Cohort& co, bool clump)
     return 0;
 }
 
+// ---- --he: Haseman-Elston regression on the chain's rows ----
+int run_he(const Options& opt, const Cohort& co, const std::vector<double>& y_raw, const std::vector<double>& covX, int C)
+{
+    const std::string out = opt.heOut.empty() ? opt.mcmcOutDir + "/" + opt.mcmcOutNam + ".HEreg" : opt.heOut;
+    const std::string rowsp = out + ".rows";
+    const FamIds fam = read_fam_ids(opt.bedFile + ".fam", co.numInds, co.numNAs ? &co.keep : nullptr);
+    const unsigned N = co.Ntot;
+    if (fam.fid.size() != N) fatal("FATAL  : " + opt.bedFile + ".fam: " + std::to_string(fam.fid.size()) + " kept rows, expected " + std::to_string(N));
+    if ((long long)N <= (long long)C + 2) fatal("FATAL  : --he needs more individuals (" + std::to_string(N) + ") than covariates + 2");
+
+    // the chain's scaled phenotype; with covariates [1 | covariates] projected out as --assoc does, then scaled again
+    std::vector<double> y(y_raw);
+    scale_phenotype(y, N);
+    if (C > 0) {
+        CovProjector("--he", covX, C, N).project(y);
+        scale_phenotype(y, N);
+    }
+    std::vector<uint8_t> bed = read_bed(opt.bedFile, co.numInds, co.Mtot);
+    if (opt.heOut.empty()) make_out_dir(opt);
+    FILE* f = open_out(out, "w");
+    FILE* fr = opt.heRows ? open_out(rowsp, "w") : nullptr;
+
+    hgibbs_t dev = open_training(co, bed);
+    std::vector<double> Y((size_t)2 * N), ay((size_t)2 * N), a1(N), a2(N), diag(N);
+    std::vector<uint32_t> partners(N);
+    for (unsigned i = 0; i < N; ++i) {
+        Y[i] = y[i];
+        Y[(size_t)N + i] = y[i] * y[i];
+    }
+    hg_check(hgibbs_grm_rowsums(dev, 2, Y.data(), ay.data(), a1.data(), a2.data(), diag.data(), partners.data()), "hgibbs_grm_rowsums");
+    double products_ms = 0.0, reduce_ms = 0.0;
+    hg_check(hgibbs_last_grm_rowsums_ms(dev, &products_ms, &reduce_ms), "hgibbs_last_grm_rowsums_ms");
+    uint32_t used = 0;
+    hg_check(hgibbs_grm_info(dev, &used, nullptr), "hgibbs_grm_info");
+    hgibbs_destroy(dev);
+
+    std::vector<double> ayv(N), ayy(N);
+    for (unsigned i = 0; i < N; ++i) {
+        ayv[i] = ay[(size_t)2 * i];
+        ayy[i] = ay[(size_t)2 * i + 1];
+    }
+    for (unsigned i = 0; i < N; ++i)
+        if (!partners[i])
+            std::printf("WARNING: --he leaves out %s %s: it shares no called marker with anyone\n", fam.fid[i].c_str(), fam.iid[i].c_str());
+    hgibbs_he_result res{};
+    hg_check(hgibbs_he_fit(N, y.data(), ayv.data(), ayy.data(), a1.data(), a2.data(), partners.data(), &res), "hgibbs_he_fit");
+
+    const hgibbs_he_form* forms[2] = {&res.cp, &res.sd};
+    const char* names[2] = {"HE-CP", "HE-SD"};
+    for (int k = 0; k < 2; ++k) {
+        const hgibbs_he_form& r = *forms[k];
+        std::fprintf(f, "%s%s\nCoefficient\tEstimate\tSE_OLS\tSE_Jackknife\tP_OLS\tP_Jackknife\n", k ? "\n" : "", names[k]);
+        std::fprintf(f, "Intercept\t%.9g\t%.9g\t%.9g\t%.9g\t%.9g\n", r.intercept, r.intercept_se, r.intercept_se_jk, r.intercept_p, r.intercept_p_jk);
+        std::fprintf(f, "V(G)/Vp\t%.9g\t%.9g\t%.9g\t%.9g\t%.9g\n", r.h2, r.h2_se, r.h2_se_jk, r.slope_p, r.slope_p_jk);
+    }
+    close_out(f, out);
+    if (fr) {
+        std::fprintf(fr, "FID\tIID\tNPARTNERS\tA_DIAG\tA_SUM\tA_SQSUM\tAY\n");
+        for (unsigned i = 0; i < N; ++i)
+            std::fprintf(fr, "%s\t%s\t%u\t%.12g\t%.12g\t%.12g\t%.12g\n", fam.fid[i].c_str(), fam.iid[i].c_str(), partners[i], diag[i], a1[i], a2[i], ayv[i]);
+        close_out(fr, rowsp);
+    }
+    std::printf("HE     : %u rows, %u of %u markers used, %llu pairs, %u rows left out, %d covariates -> %s\n", N, used, co.Mtot,
+                (unsigned long long)res.pairs, res.n_left_out, C, out.c_str());
+    std::printf("HE     : HE-CP V(G)/Vp %.6g (SE %.3g OLS, %.3g jackknife), HE-SD V(G)/Vp %.6g (SE %.3g OLS, %.3g jackknife), Vp %.6g taken as fixed\n",
+                res.cp.h2, res.cp.h2_se, res.cp.h2_se_jk, res.sd.h2, res.sd.h2_se, res.sd.h2_se_jk, res.vp);
+    std::printf("HE     : products %.3f ms, reduce %.3f ms on the device", products_ms, reduce_ms);
+    if (fr) std::printf(", the per-row sums in %s", rowsp.c_str());
+    std::printf("\n");
+    return 0;
+}
+
 // ---- the analysis modes -------------------------------------------------------
 // An analysis mode is an option that, appended to a bayesMPI command line, samples nothing and runs one analysis on the chain's rows
-// (run_predict .. run_ldselect above).  What the modes share is refused in one place, from one row per mode.
+// (run_predict .. run_he above).  What the modes share is refused in one place, from one row per mode.
 struct Mode {
     const char* flag;   // the option that asks for the mode
     bool given;
     const char* wmpi;   // how it refuses --mpibayes bayesWMPI, after its flag
     const char* orphan; // the first of its dependent options that was given: they need the mode (null: none was)
 };
-enum { PREDICT, LD, ASSOC, KING, PCA, PVE, GRM, LDSCORE, CLUMP, LDPRUNE, NMODES }; // the order in which a mode names the earlier ones it cannot be combined with
+enum { PREDICT, LD, ASSOC, KING, PCA, PVE, GRM, LDSCORE, CLUMP, LDPRUNE, HE, NMODES }; // the order in which a mode names the earlier ones it cannot be combined with
 
 const char* first_given(std::initializer_list<std::pair<const char*, bool>> deps)
 {
@@ -2409,8 +2510,9 @@ void check_modes(const Options& opt, int nranks)
                       {"--clump-out", !opt.clumpOut.empty()}})},
         {"--ld-prune", opt.ldPrune, takes,
          first_given({{"--ld-prune-kb", opt.ldPruneKbGiven}, {"--ld-prune-snps", opt.ldPruneSnpsGiven}, {"--ld-prune-out", !opt.ldPruneOut.empty()}})},
+        {"--he", opt.he, takes, first_given({{"--he-out", !opt.heOut.empty()}, {"--he-rows", opt.heRows}})},
     };
-    for (const int i : {LD, PREDICT, ASSOC, KING, PCA, PVE, GRM, LDSCORE, CLUMP, LDPRUNE}) {
+    for (const int i : {LD, PREDICT, ASSOC, KING, PCA, PVE, GRM, LDSCORE, CLUMP, LDPRUNE, HE}) {
         const Mode& m = modes[i];
         const std::string flag = m.flag;
         if (!m.given) {
@@ -2496,6 +2598,7 @@ int main(int argc, const char* argv[])
     if (opt.ldScore) return run_ldscore(opt, co);
     if (opt.clump) return run_ldselect(opt, co, true);
     if (opt.ldPrune) return run_ldselect(opt, co, false);
+    if (opt.he) return run_he(opt, co, y, covX, C);
 
     std::vector<int32_t> groups;
     std::vector<std::vector<double>> mS;

@@ -183,6 +183,7 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
  *   graph           1: replay the launches from a captured HIP graph
  *   ldscore_piece   hgibbs_ld_scores: band rows per piece, 0..2^20 (0 = automatic)
  *   ldmask_piece    hgibbs_ld_mask: band rows per piece, 0..2^20 (0 = automatic; rounded up to a multiple of 16)
+ *   grm_piece       hgibbs_grm, hgibbs_grm_rowsums: pairs per piece of rows, 0..2^25 (0 = automatic: 2^25; a row alone may exceed it)
  *   p2p, force_split, chunk, debug_timing, w_kernel_timing   transport selection and diagnostics */
 int hgibbs_set_option(hgibbs_t h, const char* name, int64_t value);
 /* Statistics of the last sweep: launches, markers per launch, device time of
@@ -420,16 +421,73 @@ int hgibbs_last_pca_ms(hgibbs_t h, double* ms4);
  * hgibbs_grm covers rows a in [a0, a0 + acount), each with its columns b = 0 .. a, packed in GCTA's order: row a0 first, then row
  * a0 + 1, ...: sum of (a + 1) entries.  Either output pointer may be NULL.  Every sum is an integer: the results are bit-identical for
  * any chunking of the rows, any value of the option grm_split (ranges of markers split over workgroups, 0 = automatic; the parts meet
- * in i32 atomic adds of the per-digit accumulators) and any repeat.  A call of more than 2^25 pairs works in pieces of rows.  The
+ * in i32 atomic adds of the per-digit accumulators) and any repeat.  A call of more than 2^25 pairs works in pieces of rows (option
+ * grm_piece: another number of pairs per piece, 0 = 2^25; a row alone may exceed it; the results do not depend on it).  The
  * call builds an individual-major copy of the codes on the device (the size of the loaded BED).  Refused with a message: several
  * ranks, no genotypes, acount = 0, a0 + acount > n_local, M_used = 0, M > 5 592 405 (a per-digit sum is at most 384 M and stays
  * inside an i32), more rows than hgibbs_king takes, buffers that do not fit in free device memory. */
 int hgibbs_grm(hgibbs_t h, uint32_t a0, uint32_t acount, double* S, int32_t* nsnp);
-/* M_used and E of the last hgibbs_grm (0, 0 after a refused one); either pointer may be NULL */
+/* M_used and E of the last hgibbs_grm or hgibbs_grm_rowsums (0, 0 after a refused call of either); either pointer may be NULL */
 int hgibbs_grm_info(hgibbs_t h, uint32_t* m_used, int32_t* E);
 /* device time of the last hgibbs_grm in ms: every kernel of the call (scale, table, image, zeroing, products, rounding), not the host
  * copies or the allocations */
 int hgibbs_last_grm_ms(hgibbs_t h, double* ms);
+
+/* ---- row sums of the relationship matrix and Haseman-Elston regression -- */
+/* What a regression on the off-diagonal entries needs of the matrix, reduced on the device: the triangle never reaches the host.
+ * S_ab and NSNP_ab are exactly hgibbs_grm's over all n_local rows.  For a != b with NSNP_ab > 0, A_ab = S_ab / (double)NSNP_ab (one IEEE
+ * division); such b are the PARTNERS of a.  k is the smallest integer with n_local <= 2^k, F = 58 - k, fx(t) = llrint(t 2^F).  Per row a,
+ * the sums running over its partners b:
+ *     AY[a][p]    = sum fx(A_ab * Y[p][b])      (one f64 product, then the exact scaling)
+ *     A1[a]       = sum fx(A_ab)
+ *     A2[a]       = sum fx(A_ab * A_ab)
+ *     partners[a] = their number
+ *     diag[a]     = S_aa / NSNP_aa, NaN when NSNP_aa = 0
+ * Y: P vectors over the rows, vector-major (Y[p*n_local + b]), 1 <= P <= 8, every entry finite.  ay[a*P + p], a1[a], a2[a] are
+ * (double)sum 2^-F, converted once; any output pointer may be NULL.  |ay - sum A_ab Y_pb| <= partners 2^-(F+1) beyond the rounding of each
+ * product and the one conversion.
+ *   Range: every term t (A_ab Y[p][b], A_ab, A_ab^2) must satisfy |t| < 16; then |fx(t)| <= 2^(62 - k) and a row's sum of fewer than 2^k
+ *   terms stays below 2^62.  The device keeps the largest |t| it met; when that is >= 16 the call is refused after the run, the message
+ *   names the magnitude, and no output is touched.  Nothing wraps silently.
+ * Every sum is an integer sum of per-pair integers: the results are bit-identical for any value of the options grm_split and grm_piece,
+ * any tile shape, any launch order and any repeat, and column p of a call with P vectors equals the call with P = 1 and that vector.
+ * The products are hgibbs_grm's kernels on pieces of rows of at most grm_piece pairs; a reducer sums each piece where it lies, into an
+ * n_local x (P + 3) accumulator of signed 64-bit integers.  Refused with a message: several ranks, no genotypes, n_local < 2, P outside
+ * 1..8, a null or non-finite Y, M > 5 592 405, M_used = 0, more rows than hgibbs_king takes, buffers that do not fit in free device
+ * memory, the range rule.  The handle serves every other operator after any refusal. */
+int hgibbs_grm_rowsums(hgibbs_t h, int P, const double* Y, double* ay, double* a1, double* a2, double* diag, uint32_t* partners);
+/* device time of the last hgibbs_grm_rowsums in ms: the products (every kernel hgibbs_grm would run: scale, table, image, zeroing,
+ * products, rounding) and the reduce (zeroing the accumulator, the reduction kernel of every piece, the final conversion); not the
+ * host copies.  0, 0 after a refused call, whether it was refused before the device work or after it (the range rule) */
+int hgibbs_last_grm_rowsums_ms(hgibbs_t h, double* products_ms, double* reduce_ms);
+
+/* Haseman-Elston regression from those row sums (host only: no handle, no device).  Inputs over n rows: y, ay = A y, ayy = A (y o y),
+ * a1, a2, partners, as hgibbs_grm_rowsums gives them for Y = [y, y o y].  Rows with partners = 0 are left out and counted; n' rows
+ * remain and each must have partners = n' - 1 (refused otherwise, naming the first row that has not), so that the pairs are all
+ * m = n'(n' - 1)/2 pairs of the used rows.  Over those pairs z is regressed on A by OLS with an intercept, for z = y_a y_b (HE-CP) and
+ * z = (y_a - y_b)^2 (HE-SD), from closed forms of sum A, sum A^2, sum z, sum A z, sum z^2 in the row sums and the power sums of y:
+ *   slope = (m sum Az - sum A sum z) / D, D = m sum A^2 - (sum A)^2;  intercept = (sum z - slope sum A) / m;
+ *   s^2 = (sum z^2 - intercept sum z - slope sum Az) / (m - 2);  SE^2(slope) = s^2 m / D;  SE^2(intercept) = s^2 sum A^2 / D.
+ * The jackknife deletes one individual at a time (its n' - 1 pairs leave every sum, in closed form): SE_jk^2 = (n' - 1)/n' sum (theta_(-a)
+ * - mean)^2.  Vp = sum (y - ybar)^2 / (n' - 1) over the used rows; h2 = slope / Vp for CP and -slope / (2 Vp) for SD, and the SEs of h2
+ * are the slope's scaled the same way: Vp IS TAKEN AS FIXED.  The P values are two-sided normal (erfc) of estimate / SE; h2's are the
+ * slope's.  Refused with a message: a null argument, n' < 4, a non-finite input in a used row, a constant y, D <= 0. */
+typedef struct {
+    double intercept, slope, h2;
+    double intercept_se, slope_se, h2_se;          /* OLS */
+    double intercept_se_jk, slope_se_jk, h2_se_jk; /* delete-one-individual jackknife */
+    double intercept_p, slope_p;                   /* from the OLS SEs */
+    double intercept_p_jk, slope_p_jk;             /* from the jackknife SEs */
+} hgibbs_he_form;
+typedef struct {
+    uint32_t n_used;     /* n' */
+    uint32_t n_left_out; /* rows with partners = 0 */
+    uint64_t pairs;      /* m */
+    double vp;
+    hgibbs_he_form cp, sd;
+} hgibbs_he_result;
+int hgibbs_he_fit(uint32_t n, const double* y, const double* ay, const double* ayy, const double* a1, const double* a2,
+                  const uint32_t* partners, hgibbs_he_result* out);
 
 /* ======================================================================== */
 /* Host driver: the body of BayesRRm::runMpiGibbs (src/BayesRRm.cpp:933-2939)
