@@ -229,40 +229,80 @@ __global__ __launch_bounds__(LD_TPB) void k_ld_final(const unsigned long long* _
     }
 }
 
-} // namespace
+// ---- the band frame: the host code that hgibbs_ld, hgibbs_ld_scores (hg_ldscore.hip.h) and hgibbs_ld_mask
+// (hg_ldmask.hip.h) share.  They run k_ld<MISS> on pieces of the same band and differ in what they do with a piece's sums.
 
-extern "C" int hgibbs_ld(hgibbs_t h, uint32_t m0, uint32_t count, uint32_t W, double* r_host, int64_t* sums_host)
+// The checks every entry point makes first.  ms: the caller's two timers in the handle, zeroed once the handle is known to be usable, so
+// that a call refused after that reads as 0 ms (null: hgibbs_ld, whose ld_ms keeps the last finished call's time)
+int ld_band_check(hgibbs_ctx* h, const char* who, uint32_t W, double (hgibbs_ctx::*ms)[2])
 {
-    if (op_guard(h, "hgibbs_ld", "the band is not exchanged between ranks")) return 1;
-    if (W == 0 || W > LD_WMAX) return fail("hgibbs_ld: W = %u, must be in [1, %u]", W, LD_WMAX);
-    if ((uint64_t)m0 + count > h->M) return fail("hgibbs_ld: markers [%u, %llu) out of range (M = %u)", m0, (unsigned long long)m0 + count, h->M);
-    if (h->n_local >= LD_NMAX) return fail("hgibbs_ld: %u individuals, at most %u (i32 partial sums)", h->n_local, LD_NMAX - 1u);
-    if (count == 0) return 0;
-    HIP_TRY(hipSetDevice(h->device));
-    if (compute_stats(h)) return 1;
-    const uint32_t M = h->M, ntile = (M + 15u) / 16u;
+    if (op_guard(h, who, "the band is not exchanged between ranks")) return 1;
+    if (ms) (h->*ms)[0] = (h->*ms)[1] = 0.0;
+    if (W == 0 || W > LD_WMAX) return fail("%s: W = %u, must be in [1, %u]", who, W, LD_WMAX);
+    if (h->n_local >= LD_NMAX) return fail("%s: %u individuals, at most %u (i32 partial sums)", who, h->n_local, LD_NMAX - 1u);
+    return 0;
+}
 
+// ah[j] = the pairs ahead of marker j: ahead[j], refused where it leaves the window or the markers (ahead = NULL: min(W, M - 1 - j))
+int ld_ahead(const char* who, uint32_t M, uint32_t W, const uint32_t* ahead, std::vector<uint32_t>& ah)
+{
+    ah.resize(M);
+    for (uint32_t j = 0; j < M; ++j) {
+        if (!ahead) {
+            ah[j] = std::min(W, M - 1u - j);
+            continue;
+        }
+        if (ahead[j] > W) return fail("%s: ahead[%u] = %u is above W = %u", who, j, ahead[j], W);
+        if ((uint64_t)j + ahead[j] >= M) return fail("%s: marker %u + ahead[%u] = %u is past the last marker (M = %u)", who, j, j, ahead[j], M);
+        ah[j] = ahead[j];
+    }
+    return 0;
+}
+
+// Band rows of a piece: at most 2^24 pairs (the device's sums: 512 MiB; that bound on rows rounded up to 16) and 2^20 rows (grid y);
+// rows_opt (options ldscore_piece, ldmask_piece; 0: none) fixes the rows, rounded up to 16; at most `count` rounded up to 16, at least 16.
+// hgibbs_ld (rows_opt = 0) cut max(16, min(count, 2^20, cap)) before the frame: the same pieces for every input, since the two bounds are
+// multiples of 16 (where one of them is at most count, both formulas give it; where count is below both, both give one piece of count rows).
+uint32_t ld_piece_rows(uint32_t W, int rows_opt, uint32_t count)
+{
+    uint64_t piece = std::min<uint64_t>(((1ull << 24) / W + 15u) / 16u * 16u, 1ull << 20);
+    if (rows_opt) piece = std::min<uint64_t>(piece, ((uint64_t)rows_opt + 15u) / 16u * 16u);
+    return (uint32_t)std::max<uint64_t>(16u, std::min<uint64_t>(piece, ((uint64_t)count + 15u) / 16u * 16u));
+}
+
+// Flags of tiles of sixteen markers that k_ld may read: the markers' and the widest window's past them
+size_t ld_flag_count(uint32_t M) { return (size_t)((M + 15u) / 16u) + LD_WMAX / 16 + LD_QP + LD_WAVES; }
+
+// What the pieces of a call share on the device: the missing-tile flags (ld_flag_count(M) bytes) and the sums of one piece of `piece`
+// rows (ld_piece_rows), 32 bytes a pair.  The caller has set the device and run compute_stats; its own buffers come after these.
+struct LdBand {
+    DevBuf<uint8_t> dmiss;
+    DevBuf<unsigned long long> acc;
+    uint32_t W = 0, piece = 0;
+};
+
+int ld_band_open(hgibbs_ctx* h, uint32_t W, uint32_t piece, LdBand& b)
+{
     // tiles of sixteen markers with a missing call in a column (the counts of hgibbs_marker_stats)
     std::vector<uint8_t> tmiss;
     if (missing_tiles(h, 16u, tmiss)) return 1;
+    tmiss.resize(ld_flag_count(h->M), 0); // (the window's tiles past M read as clean)
+    b.W = W;
+    b.piece = piece;
+    if (b.dmiss.alloc(tmiss.size()) || b.acc.alloc((size_t)piece * W * 4)) return 1;
+    HIP_TRY(hipMemcpy(b.dmiss, tmiss.data(), tmiss.size(), hipMemcpyHostToDevice));
+    return 0;
+}
 
-    // pieces of at most 2^24 pairs (the device's sums: 512 MiB) and 2^20 markers (grid y)
-    const uint32_t piece = std::max<uint32_t>(16u, (uint32_t)std::min<uint64_t>({(uint64_t)count, 1ull << 20, ((1ull << 24) / W + 15u) / 16u * 16u}));
-    DevBuf<uint8_t> dmiss;
-    DevBuf<unsigned long long> acc;
-    DevBuf<double> r;
-    DevBuf<long long> sums;
-    const size_t np = (size_t)piece * W;
-    tmiss.resize((size_t)ntile + LD_WMAX / 16 + LD_QP + LD_WAVES, 0); // (the window's tiles past M read as clean)
-    if (dmiss.alloc(tmiss.size())) return 1;
-    HIP_TRY(hipMemcpy(dmiss, tmiss.data(), tmiss.size(), hipMemcpyHostToDevice));
-    if (acc.alloc(np * 4)) return 1;
-    if (r_host && r.alloc(np)) return 1;
-    if (sums_host && sums.alloc(np * 4)) return 1;
-
+// The band rows [m0, m0 + count) in pieces: per piece [p0, p0 + pc) the zeroing and the products, then step(p0, pc, acc), which does with
+// the piece's sums what the caller is there for.  The step is entered with the products' lap open (lap_begin, the zeroing, k_ld) and
+// closes it itself: after its own kernel into one timer (hgibbs_ld), or at once into the products' timer, then a second lap for its reduce.
+template <class Step>
+int ld_band_pieces(hgibbs_ctx* h, const LdBand& b, uint32_t m0, uint32_t count, Step&& step)
+{
+    const uint32_t M = h->M, W = b.W, piece = b.piece;
     const uint32_t n_sub = (h->n_local + LD_SUBD * 16 - 1) / (LD_SUBD * 16);
     const uint32_t nq = (W + 15u) / 16u + 1u; // B tiles per A tile: A tile t pairs with tiles t .. t + floor((W + 15) / 16)
-    double total_ms = 0.0;
     for (uint32_t p0 = m0; p0 < m0 + count; p0 += piece) {
         const uint32_t pc = std::min(piece, m0 + count - p0);
         const uint32_t t0 = p0 / 16u, t1 = (p0 + pc - 1u) / 16u + 1u;
@@ -271,22 +311,49 @@ extern "C" int hgibbs_ld(hgibbs_t h, uint32_t m0, uint32_t count, uint32_t W, do
         uint32_t sub_per = 0;
         const uint32_t gx = split_ranges(n_sub, h->ld_split ? (uint32_t)h->ld_split : (8u * (uint32_t)h->num_cu + gy * gz - 1u) / (gy * gz), NO_CAP, sub_per);
         if (lap_begin(h)) return 1;
-        HIP_TRY(hipMemsetAsync(acc, 0, (size_t)pc * W * 4 * sizeof(unsigned long long), h->stream));
+        HIP_TRY(hipMemsetAsync(b.acc, 0, (size_t)pc * W * 4 * sizeof(unsigned long long), h->stream));
         const dim3 grid(gx, gy, gz);
         if (h->any_missing)
-            k_ld<true><<<grid, LD_WAVES * 64, 0, h->stream>>>(h->bed, h->stride, M, h->n_local, t0, t1, nq, sub_per, n_sub, dmiss, W, p0, pc, acc);
+            k_ld<true><<<grid, LD_WAVES * 64, 0, h->stream>>>(h->bed, h->stride, M, h->n_local, t0, t1, nq, sub_per, n_sub, b.dmiss, W, p0, pc, b.acc);
         else
-            k_ld<false><<<grid, LD_WAVES * 64, 0, h->stream>>>(h->bed, h->stride, M, h->n_local, t0, t1, nq, sub_per, n_sub, dmiss, W, p0, pc, acc);
+            k_ld<false><<<grid, LD_WAVES * 64, 0, h->stream>>>(h->bed, h->stride, M, h->n_local, t0, t1, nq, sub_per, n_sub, b.dmiss, W, p0, pc, b.acc);
         HIP_TRY(hipGetLastError());
+        if (step(p0, pc, (unsigned long long*)b.acc)) return 1;
+    }
+    return 0;
+}
+
+} // namespace
+
+extern "C" int hgibbs_ld(hgibbs_t h, uint32_t m0, uint32_t count, uint32_t W, double* r_host, int64_t* sums_host)
+{
+    if (ld_band_check(h, "hgibbs_ld", W, nullptr)) return 1;
+    if ((uint64_t)m0 + count > h->M) return fail("hgibbs_ld: markers [%u, %llu) out of range (M = %u)", m0, (unsigned long long)m0 + count, h->M);
+    if (count == 0) return 0;
+    HIP_TRY(hipSetDevice(h->device));
+    if (compute_stats(h)) return 1;
+    LdBand band;
+    if (ld_band_open(h, W, ld_piece_rows(W, 0, count), band)) return 1;
+    DevBuf<double> r;
+    DevBuf<long long> sums;
+    const size_t np = (size_t)band.piece * W;
+    if (r_host && r.alloc(np)) return 1;
+    if (sums_host && sums.alloc(np * 4)) return 1;
+
+    double total_ms = 0.0;
+    // the step of a piece: r and the sums of its pairs inside the products' lap, and the copies out
+    auto finish = [&](uint32_t p0, uint32_t pc, const unsigned long long* acc) -> int {
         const uint64_t npc = (uint64_t)pc * W;
-        k_ld_final<<<(uint32_t)((npc + LD_TPB - 1) / LD_TPB), LD_TPB, 0, h->stream>>>(acc, h->counts, h->mave, h->mstd, M, h->n_local, h->n_global,
+        k_ld_final<<<(uint32_t)((npc + LD_TPB - 1) / LD_TPB), LD_TPB, 0, h->stream>>>(acc, h->counts, h->mave, h->mstd, h->M, h->n_local, h->n_global,
                                                                                        W, p0, pc, r, sums);
         HIP_TRY(hipGetLastError());
         if (lap_end(h, total_ms)) return 1;
         const size_t off = (size_t)(p0 - m0) * W;
         if (r_host) HIP_TRY(hipMemcpy(r_host + off, r, npc * sizeof(double), hipMemcpyDeviceToHost));
         if (sums_host) HIP_TRY(hipMemcpy(sums_host + off * 4, sums, npc * 4 * sizeof(long long), hipMemcpyDeviceToHost));
-    }
+        return 0;
+    };
+    if (ld_band_pieces(h, band, m0, count, finish)) return 1;
     h->ld_ms = total_ms;
     return 0;
 }

@@ -7,7 +7,7 @@
 //   masks     wpr = (W + 63) / 64 words per marker.  fwd[j wpr + (d - 1) / 64] bit (d - 1) % 64 is set iff pair (j, j + d) passes;
 //             bwd[q wpr + (d - 1) / 64] bit (d - 1) % 64 is set iff q >= d and pair (q - d, q) passes.  Every other bit is 0, the bits of
 //             offsets above W in a row's last word included.
-//   products  k_ld<MISS>, unchanged, fills the 64-bit sums of a piece of band rows (at most 2^24 pairs), as in hgibbs_ld_scores.
+//   products  the band frame of hg_ld.hip.h (ld_band_pieces), as in hgibbs_ld_scores: k_ld<MISS>, unchanged, fills a piece's 64-bit sums.
 //   reduce    k_ldm_reduce replaces k_ld_final: a workgroup takes LM_ROWS band rows x LM_OFFS offsets of the piece.  A wave takes one row
 //             at a time, lane = offset: 64 lanes read 2 KiB of sums in a row and decide `pass`.
 //             forward   __ballot(pass) IS word blockIdx.x of row j: one lane stores it (plain store; each (row, word) belongs to exactly one
@@ -80,80 +80,46 @@ __global__ __launch_bounds__(LM_WAVES * 64) void k_ldm_reduce(const unsigned lon
 
 extern "C" int hgibbs_ld_mask(hgibbs_t h, uint32_t W, const uint32_t* ahead, double t, uint64_t* fwd, uint64_t* bwd, uint64_t* npass)
 {
-    if (op_guard(h, "hgibbs_ld_mask", "the band is not exchanged between ranks")) return 1;
-    h->ldm_ms[0] = h->ldm_ms[1] = 0.0;
-    if (W == 0 || W > LD_WMAX) return fail("hgibbs_ld_mask: W = %u, must be in [1, %u]", W, LD_WMAX);
-    if (h->n_local >= LD_NMAX) return fail("hgibbs_ld_mask: %u individuals, at most %u (i32 partial sums)", h->n_local, LD_NMAX - 1u);
+    if (ld_band_check(h, "hgibbs_ld_mask", W, &hgibbs_ctx::ldm_ms)) return 1;
     if (!(std::isfinite(t) && t >= 0.0)) return fail("hgibbs_ld_mask: t = %g, the threshold on r^2 must be finite and >= 0", t);
     if (!fwd) return fail("hgibbs_ld_mask: null output (fwd)");
     const uint32_t M = h->M;
-    std::vector<uint32_t> ah(M);
-    for (uint32_t j = 0; j < M; ++j) {
-        if (!ahead) {
-            ah[j] = std::min(W, M - 1u - j);
-            continue;
-        }
-        if (ahead[j] > W) return fail("hgibbs_ld_mask: ahead[%u] = %u is above W = %u", j, ahead[j], W);
-        if ((uint64_t)j + ahead[j] >= M) return fail("hgibbs_ld_mask: marker %u + ahead[%u] = %u is past the last marker (M = %u)", j, j, ahead[j], M);
-        ah[j] = ahead[j];
-    }
+    std::vector<uint32_t> ah;
+    if (ld_ahead("hgibbs_ld_mask", M, W, ahead, ah)) return 1;
     HIP_TRY(hipSetDevice(h->device));
     if (compute_stats(h)) return 1;
-    const uint32_t ntile = (M + 15u) / 16u;
 
-    std::vector<uint8_t> tmiss;
-    if (missing_tiles(h, 16u, tmiss)) return 1;
-
-    // pieces of band rows: at most 2^24 pairs (the device's sums: 512 MiB) and 2^20 rows (grid y); option ldmask_piece fixes the rows
-    const uint32_t cap = (uint32_t)(((1ull << 24) / W + 15u) / 16u * 16u);
-    uint32_t piece = std::min<uint32_t>(cap, 1u << 20);
-    if (h->ldmask_piece) piece = std::min(piece, ((uint32_t)h->ldmask_piece + 15u) / 16u * 16u);
-    piece = std::max(16u, std::min(piece, (M + 15u) / 16u * 16u));
+    const uint32_t piece = ld_piece_rows(W, h->ldmask_piece, M);
     const uint32_t wpr = (W + 63u) / 64u;
     const size_t np = (size_t)piece * W, nm = (size_t)M * wpr;
-    tmiss.resize((size_t)ntile + LD_WMAX / 16 + LD_QP + LD_WAVES, 0); // (the window's tiles past M read as clean)
-    if (need_device_memory(2 * nm * 8 + np * 32 + (size_t)M * 4 + 8 + tmiss.size(),
+    if (need_device_memory(2 * nm * 8 + np * 32 + (size_t)M * 4 + 8 + ld_flag_count(M),
                            "hgibbs_ld_mask: the two %u x %u-word masks (%.1f MiB) and the sums of a piece of %u band rows (%.1f MiB)", M, wpr,
                            2 * nm * 8 / 1048576.0, piece, np * 32 / 1048576.0))
         return 1;
-    DevBuf<uint8_t> dmiss;
-    DevBuf<unsigned long long> acc, dfwd, dbwd, dn;
+    LdBand band;
+    if (ld_band_open(h, W, piece, band)) return 1;
+    DevBuf<unsigned long long> dfwd, dbwd, dn;
     DevBuf<uint32_t> dah;
-    if (dmiss.alloc(tmiss.size()) || acc.alloc(np * 4) || dfwd.alloc(nm) || (bwd && dbwd.alloc(nm)) || dn.alloc(1) || dah.alloc(M)) return 1;
-    HIP_TRY(hipMemcpy(dmiss, tmiss.data(), tmiss.size(), hipMemcpyHostToDevice));
+    if (dfwd.alloc(nm) || (bwd && dbwd.alloc(nm)) || dn.alloc(1) || dah.alloc(M)) return 1;
     HIP_TRY(hipMemcpy(dah, ah.data(), (size_t)M * sizeof(uint32_t), hipMemcpyHostToDevice));
 
-    const uint32_t n_sub = (h->n_local + LD_SUBD * 16 - 1) / (LD_SUBD * 16);
-    const uint32_t nq = (W + 15u) / 16u + 1u;
     double products_ms = 0.0, reduce_ms = 0.0;
     if (lap_begin(h)) return 1;
     HIP_TRY(hipMemsetAsync(dfwd, 0, nm * sizeof(unsigned long long), h->stream));
     if (bwd) HIP_TRY(hipMemsetAsync(dbwd, 0, nm * sizeof(unsigned long long), h->stream));
     HIP_TRY(hipMemsetAsync(dn, 0, sizeof(unsigned long long), h->stream));
     if (lap_end(h, reduce_ms)) return 1;
-    for (uint32_t p0 = 0; p0 < M; p0 += piece) {
-        const uint32_t pc = std::min(piece, M - p0);
-        const uint32_t t0 = p0 / 16u, t1 = (p0 + pc - 1u) / 16u + 1u;
-        const uint32_t gy = (t1 - t0 + LD_WAVES - 1u) / LD_WAVES, gz = (nq + LD_QP - 1u) / LD_QP;
-        uint32_t sub_per = 0;
-        const uint32_t gx = split_ranges(n_sub, h->ld_split ? (uint32_t)h->ld_split : (8u * (uint32_t)h->num_cu + gy * gz - 1u) / (gy * gz), NO_CAP, sub_per);
-        if (lap_begin(h)) return 1;
-        HIP_TRY(hipMemsetAsync(acc, 0, (size_t)pc * W * 4 * sizeof(unsigned long long), h->stream));
-        const dim3 grid(gx, gy, gz);
-        if (h->any_missing)
-            k_ld<true><<<grid, LD_WAVES * 64, 0, h->stream>>>(h->bed, h->stride, M, h->n_local, t0, t1, nq, sub_per, n_sub, dmiss, W, p0, pc, acc);
-        else
-            k_ld<false><<<grid, LD_WAVES * 64, 0, h->stream>>>(h->bed, h->stride, M, h->n_local, t0, t1, nq, sub_per, n_sub, dmiss, W, p0, pc, acc);
-        HIP_TRY(hipGetLastError());
+    // the step of a piece: the products' lap ends, the reduce has its own
+    auto reduce = [&](uint32_t p0, uint32_t pc, const unsigned long long* acc) -> int {
         if (lap_end(h, products_ms)) return 1;
-
         if (lap_begin(h)) return 1;
         const dim3 rgrid(wpr, (pc + LM_ROWS - 1u) / LM_ROWS);
         k_ldm_reduce<<<rgrid, LM_WAVES * 64, 0, h->stream>>>(acc, h->counts, h->mave, h->mstd, dah, M, h->n_local, h->n_global, W, wpr, p0, pc, t, dfwd,
                                                              bwd ? (unsigned long long*)dbwd : nullptr, dn);
         HIP_TRY(hipGetLastError());
-        if (lap_end(h, reduce_ms)) return 1;
-    }
+        return lap_end(h, reduce_ms);
+    };
+    if (ld_band_pieces(h, band, 0, M, reduce)) return 1;
     HIP_TRY(hipMemcpy(fwd, dfwd, nm * sizeof(uint64_t), hipMemcpyDeviceToHost));
     if (bwd) HIP_TRY(hipMemcpy(bwd, dbwd, nm * sizeof(uint64_t), hipMemcpyDeviceToHost));
     if (npass) HIP_TRY(hipMemcpy(npass, dn, sizeof(uint64_t), hipMemcpyDeviceToHost));

@@ -3,7 +3,7 @@
 //
 //   pairs     (j, q), j < q, is in the window iff q - j <= ahead[j]; it counts for both of its markers.  A pair with a marker whose mstd
 //             is not finite counts for neither.
-//   products  k_ld<MISS>, unchanged, fills the 64-bit sums of a piece of band rows (at most 2^24 pairs), as in hgibbs_ld.
+//   products  the band frame of hg_ld.hip.h (ld_band_pieces): k_ld<MISS>, unchanged, fills the 64-bit sums of a piece of band rows.
 //   reduce    k_lds_reduce replaces k_ld_final: a workgroup takes LS_ROWS band rows x LS_OFFS offsets of the piece.  A wave takes one row
 //             at a time, lane = offset: 64 lanes read 2 KiB of sums in a row, form t and fx = llrint(t 2^44).
 //             forward   L[j][c] += sum_q a_qc fx: C = 1 is one sum across the wave; otherwise lane c sums the 64 pairs, the pair's fx and
@@ -129,25 +129,14 @@ __global__ __launch_bounds__(256) void k_lds_final(unsigned long long* __restric
 
 extern "C" int hgibbs_ld_scores(hgibbs_t h, uint32_t W, const uint32_t* ahead, uint32_t C, const uint64_t* annot, int adjust, double* l2)
 {
-    if (op_guard(h, "hgibbs_ld_scores", "the band is not exchanged between ranks")) return 1;
-    h->lds_ms[0] = h->lds_ms[1] = 0.0;
-    if (W == 0 || W > LD_WMAX) return fail("hgibbs_ld_scores: W = %u, must be in [1, %u]", W, LD_WMAX);
-    if (h->n_local >= LD_NMAX) return fail("hgibbs_ld_scores: %u individuals, at most %u (i32 partial sums)", h->n_local, LD_NMAX - 1u);
+    if (ld_band_check(h, "hgibbs_ld_scores", W, &hgibbs_ctx::lds_ms)) return 1;
     if (C == 0 || C > LS_CMAX) return fail("hgibbs_ld_scores: C = %u, must be in [1, %u]", C, LS_CMAX);
     if (!annot && C != 1u) return fail("hgibbs_ld_scores: C = %u without annotations (annot = NULL means one column with every marker)", C);
     if (adjust && h->n_global < 3u) return fail("hgibbs_ld_scores: N = %u, the adjusted term r^2 - (1 - r^2) / (N - 2) needs N >= 3", h->n_global);
     if (!l2) return fail("hgibbs_ld_scores: null output");
     const uint32_t M = h->M;
-    std::vector<uint32_t> ah(M);
-    for (uint32_t j = 0; j < M; ++j) {
-        if (!ahead) {
-            ah[j] = std::min(W, M - 1u - j);
-            continue;
-        }
-        if (ahead[j] > W) return fail("hgibbs_ld_scores: ahead[%u] = %u is above W = %u", j, ahead[j], W);
-        if ((uint64_t)j + ahead[j] >= M) return fail("hgibbs_ld_scores: marker %u + ahead[%u] = %u is past the last marker (M = %u)", j, j, ahead[j], M);
-        ah[j] = ahead[j];
-    }
+    std::vector<uint32_t> ah;
+    if (ld_ahead("hgibbs_ld_scores", M, W, ahead, ah)) return 1;
     std::vector<unsigned long long> an(M, 1ull);
     if (annot)
         for (uint32_t j = 0; j < M; ++j) {
@@ -156,53 +145,29 @@ extern "C" int hgibbs_ld_scores(hgibbs_t h, uint32_t W, const uint32_t* ahead, u
         }
     HIP_TRY(hipSetDevice(h->device));
     if (compute_stats(h)) return 1;
-    const uint32_t ntile = (M + 15u) / 16u;
 
-    std::vector<uint8_t> tmiss;
-    if (missing_tiles(h, 16u, tmiss)) return 1;
-
-    // pieces of band rows: at most 2^24 pairs (the device's sums: 512 MiB) and 2^20 rows (grid y); option ldscore_piece fixes the rows
-    const uint32_t cap = (uint32_t)(((1ull << 24) / W + 15u) / 16u * 16u);
-    uint32_t piece = std::min<uint32_t>(cap, 1u << 20);
-    if (h->ldscore_piece) piece = std::min(piece, ((uint32_t)h->ldscore_piece + 15u) / 16u * 16u);
-    piece = std::max(16u, std::min(piece, (M + 15u) / 16u * 16u));
+    const uint32_t piece = ld_piece_rows(W, h->ldscore_piece, M);
     const size_t np = (size_t)piece * W, nl = (size_t)M * C;
-    tmiss.resize((size_t)ntile + LD_WMAX / 16 + LD_QP + LD_WAVES, 0); // (the window's tiles past M read as clean)
-    if (need_device_memory(nl * 8 + np * 32 + (size_t)M * 12 + tmiss.size(),
+    if (need_device_memory(nl * 8 + np * 32 + (size_t)M * 12 + ld_flag_count(M),
                            "hgibbs_ld_scores: the %u x %u accumulator (%.1f MiB) and the sums of a piece of %u band rows (%.1f MiB)", M, C,
                            nl * 8 / 1048576.0, piece, np * 32 / 1048576.0))
         return 1;
-    DevBuf<uint8_t> dmiss;
-    DevBuf<unsigned long long> acc, L, dan;
+    LdBand band;
+    if (ld_band_open(h, W, piece, band)) return 1;
+    DevBuf<unsigned long long> L, dan;
     DevBuf<uint32_t> dah;
-    if (dmiss.alloc(tmiss.size()) || acc.alloc(np * 4) || L.alloc(nl) || dan.alloc(M) || dah.alloc(M)) return 1;
-    HIP_TRY(hipMemcpy(dmiss, tmiss.data(), tmiss.size(), hipMemcpyHostToDevice));
+    if (L.alloc(nl) || dan.alloc(M) || dah.alloc(M)) return 1;
     HIP_TRY(hipMemcpy(dan, an.data(), (size_t)M * sizeof(unsigned long long), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dah, ah.data(), (size_t)M * sizeof(uint32_t), hipMemcpyHostToDevice));
 
-    const uint32_t n_sub = (h->n_local + LD_SUBD * 16 - 1) / (LD_SUBD * 16);
-    const uint32_t nq = (W + 15u) / 16u + 1u;
     const size_t lds = (size_t)C * LS_SPAN * sizeof(unsigned long long);
     double products_ms = 0.0, reduce_ms = 0.0;
     if (lap_begin(h)) return 1;
     HIP_TRY(hipMemsetAsync(L, 0, nl * sizeof(unsigned long long), h->stream));
     if (lap_end(h, reduce_ms)) return 1;
-    for (uint32_t p0 = 0; p0 < M; p0 += piece) {
-        const uint32_t pc = std::min(piece, M - p0);
-        const uint32_t t0 = p0 / 16u, t1 = (p0 + pc - 1u) / 16u + 1u;
-        const uint32_t gy = (t1 - t0 + LD_WAVES - 1u) / LD_WAVES, gz = (nq + LD_QP - 1u) / LD_QP;
-        uint32_t sub_per = 0;
-        const uint32_t gx = split_ranges(n_sub, h->ld_split ? (uint32_t)h->ld_split : (8u * (uint32_t)h->num_cu + gy * gz - 1u) / (gy * gz), NO_CAP, sub_per);
-        if (lap_begin(h)) return 1;
-        HIP_TRY(hipMemsetAsync(acc, 0, (size_t)pc * W * 4 * sizeof(unsigned long long), h->stream));
-        const dim3 grid(gx, gy, gz);
-        if (h->any_missing)
-            k_ld<true><<<grid, LD_WAVES * 64, 0, h->stream>>>(h->bed, h->stride, M, h->n_local, t0, t1, nq, sub_per, n_sub, dmiss, W, p0, pc, acc);
-        else
-            k_ld<false><<<grid, LD_WAVES * 64, 0, h->stream>>>(h->bed, h->stride, M, h->n_local, t0, t1, nq, sub_per, n_sub, dmiss, W, p0, pc, acc);
-        HIP_TRY(hipGetLastError());
+    // the step of a piece: the products' lap ends, the reduce has its own
+    auto reduce = [&](uint32_t p0, uint32_t pc, const unsigned long long* acc) -> int {
         if (lap_end(h, products_ms)) return 1;
-
         if (lap_begin(h)) return 1;
         const dim3 rgrid((W + LS_OFFS - 1u) / LS_OFFS, (pc + LS_ROWS - 1u) / LS_ROWS);
         if (C == 1u)
@@ -212,8 +177,9 @@ extern "C" int hgibbs_ld_scores(hgibbs_t h, uint32_t W, const uint32_t* ahead, u
             k_lds_reduce<false><<<rgrid, LS_WAVES * 64, lds, h->stream>>>(acc, h->counts, h->mave, h->mstd, dah, dan, M, h->n_local, h->n_global, W, p0, pc,
                                                                            C, adjust, L);
         HIP_TRY(hipGetLastError());
-        if (lap_end(h, reduce_ms)) return 1;
-    }
+        return lap_end(h, reduce_ms);
+    };
+    if (ld_band_pieces(h, band, 0, M, reduce)) return 1;
     if (lap_begin(h)) return 1;
     k_lds_final<<<(uint32_t)((nl + 255u) / 256u), 256, 0, h->stream>>>(L, dan, h->mstd, M, C);
     HIP_TRY(hipGetLastError());

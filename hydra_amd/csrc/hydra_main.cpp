@@ -1686,6 +1686,23 @@ MarkerSets read_sets_file(const std::string& path, const std::string& bedFile, c
     return ms;
 }
 
+// The groups of --pve-groups and --ld-score-groups: one set per group number of the group index file, in ascending order of the number
+MarkerSets sets_from_groups(const Options& opt, unsigned Mtot)
+{
+    MarkerSets ms;
+    const std::vector<int32_t> groups = read_groups(opt.groupIndexFile);
+    if (groups.size() < Mtot) fatal("FATAL  : group file covers fewer markers than --number-markers");
+    std::map<int32_t, size_t> at;
+    for (unsigned j = 0; j < Mtot; ++j) at.emplace(groups[j], 0);
+    for (auto& g : at) {
+        g.second = ms.idx.size();
+        ms.name.push_back("group" + std::to_string(g.first));
+        ms.idx.emplace_back();
+    }
+    for (unsigned j = 0; j < Mtot; ++j) ms.idx[at[groups[j]]].push_back(j);
+    return ms;
+}
+
 struct PveSets : MarkerSets {
     std::string how; // how the sets were defined, for the report
 };
@@ -1728,12 +1745,7 @@ PveSets pve_sets(const Options& opt, const BimRows& bim, unsigned Mtot)
         static_cast<MarkerSets&>(ps) = read_sets_file(opt.pveSets, opt.bedFile, bim, Mtot);
     } else if (opt.pveGroups) {
         ps.how = "the groups of " + opt.groupIndexFile;
-        const std::vector<int32_t> groups = read_groups(opt.groupIndexFile);
-        if (groups.size() < Mtot) fatal("FATAL  : group file covers fewer markers than --number-markers");
-        std::map<int32_t, size_t> at; // in ascending order of the group's number
-        for (unsigned j = 0; j < Mtot; ++j) at.emplace(groups[j], 0);
-        for (auto& g : at) g.second = add("group" + std::to_string(g.first));
-        for (unsigned j = 0; j < Mtot; ++j) ps.idx[at[groups[j]]].push_back(j);
+        static_cast<MarkerSets&>(ps) = sets_from_groups(opt, Mtot);
     } else {
         ps.how = "one per chromosome";
         std::map<std::string, size_t> at;
@@ -1948,6 +1960,7 @@ struct LdWindow {
     unsigned long long npairs = 0;
     uint32_t widest = 0;
     size_t nchroms = 0;
+    std::string what; // the window in words, for the report: "<n> markers" or "<bp> bp"
 };
 
 LdWindow ld_window(const std::string& flag, const char* op, const BimRows& bim, const std::string& bimp, unsigned M, bool bySnps, long wsnps,
@@ -1967,6 +1980,7 @@ LdWindow ld_window(const std::string& flag, const char* op, const BimRows& bim, 
     LdWindow w;
     w.ahead.assign(M, 0);
     w.nchroms = chroms.size();
+    w.what = bySnps ? std::to_string(wsnps) + " markers" : std::to_string(maxbp) + " bp";
     for (unsigned j = 0, e = 0; j < M; ++j) { // e: one past the last marker of j's window
         e = std::max(e, j + 1);
         while (e < M && bim.chr[e] == bim.chr[j] && (bySnps ? (long)(e - j) <= wsnps : bim.bp[e] - bim.bp[j] <= maxbp)) ++e;
@@ -2006,20 +2020,7 @@ int run_ldscore(const Options& opt, const Cohort& co)
     std::vector<std::string> colname;
     std::vector<uint64_t> annot;
     if (!opt.ldScoreSets.empty() || opt.ldScoreGroups) {
-        MarkerSets ms;
-        if (!opt.ldScoreSets.empty()) ms = read_sets_file(opt.ldScoreSets, opt.bedFile, bim, M);
-        else {
-            const std::vector<int32_t> groups = read_groups(opt.groupIndexFile);
-            if (groups.size() < M) fatal("FATAL  : group file covers fewer markers than --number-markers");
-            std::map<int32_t, size_t> at; // in ascending order of the group's number
-            for (unsigned j = 0; j < M; ++j) at.emplace(groups[j], 0);
-            for (auto& g : at) {
-                g.second = ms.idx.size();
-                ms.name.push_back("group" + std::to_string(g.first));
-                ms.idx.emplace_back();
-            }
-            for (unsigned j = 0; j < M; ++j) ms.idx[at[groups[j]]].push_back(j);
-        }
+        const MarkerSets ms = opt.ldScoreSets.empty() ? sets_from_groups(opt, M) : read_sets_file(opt.ldScoreSets, opt.bedFile, bim, M);
         if (ms.idx.size() > 63)
             fatal("FATAL  : --ld-score: " + std::to_string(ms.idx.size()) + " annotations, at most 63 beside the base column (hgibbs_ld_scores takes 64 columns)");
         colname.push_back("base");
@@ -2032,7 +2033,7 @@ int run_ldscore(const Options& opt, const Cohort& co)
     const uint32_t C = colname.empty() ? 1u : (uint32_t)colname.size();
     const std::string l2p = prefix + ".l2.ldscore", mp = prefix + ".l2.M", m5p = prefix + ".l2.M_5_50";
     std::printf("LDSCORE: %u markers, %zu chromosomes, window %s, %llu pairs in the window, widest window %u markers ahead, %u columns (%s r^2) -> %s\n", M,
-                nchroms, bySnps ? (std::to_string(wsnps) + " markers").c_str() : (std::to_string(maxbp) + " bp").c_str(), npairs, widest, C,
+                nchroms, win.what.c_str(), npairs, widest, C,
                 opt.ldScoreRaw ? "raw" : "adjusted", l2p.c_str());
     std::fflush(stdout);
     if (!opt.ldScoreRaw && co.Ntot < 3) fatal("FATAL  : --ld-score: the adjusted r^2 - (1 - r^2) / (N - 2) needs at least three individuals (--ld-score-raw takes fewer)");
@@ -2170,7 +2171,6 @@ int run_ldselect(const Options& opt, const Cohort& co, bool clump)
     const long long maxbp = (long long)std::llround(1000.0 * kb);
     const LdWindow win = ld_window(flag, "hgibbs_ld_mask", bim, bimp, M, bySnps, wsnps, maxbp);
     const uint32_t W = std::max(1u, win.widest);
-    const std::string window = bySnps ? std::to_string(wsnps) + " markers" : std::to_string(maxbp) + " bp";
 
     // who takes part, before the device knows which markers have a finite sd
     const double P1 = num_or(opt.clumpP1, 1e-4), P2 = num_or(opt.clumpP2, 1e-2), R2 = num_or(opt.clumpR2, 0.5), T = num_or(opt.ldPruneT, 0.0);
@@ -2186,13 +2186,13 @@ int run_ldselect(const Options& opt, const Cohort& co, bool clump)
         }
         std::printf("%s: %u rows read from %s, %u matched to the .bim (%u ids not in it, %u without a P in [0, 1]), %u participating (P <= %g), %u able to lead (P <= %g), "
                     "window %s, %llu pairs in the window, widest window %u markers ahead, r^2 >= %g -> %s\n",
-                    tag, tab.rows, opt.clumpFile.c_str(), tab.matched, tab.unknown, tab.badp, part, P2, lead, P1, window.c_str(), win.npairs, win.widest, R2, out.c_str());
+                    tag, tab.rows, opt.clumpFile.c_str(), tab.matched, tab.unknown, tab.badp, part, P2, lead, P1, win.what.c_str(), win.npairs, win.widest, R2, out.c_str());
     } else {
         const std::string prefix = opt.ldPruneOut.empty() ? base : opt.ldPruneOut;
         out = prefix + ".prune.in";
         outOut = prefix + ".prune.out";
         std::printf("%s: %u markers, %zu chromosomes, window %s, %llu pairs in the window, widest window %u markers ahead, r^2 > %g -> %s\n", tag, M, win.nchroms,
-                    window.c_str(), win.npairs, win.widest, T, out.c_str());
+                    win.what.c_str(), win.npairs, win.widest, T, out.c_str());
     }
     std::fflush(stdout);
 

@@ -171,7 +171,8 @@ def test_edge_grid_clean(N):
 
 def test_the_piece_loop():
     """hgibbs_ld's own pieces: 4 200 band rows x 4 096 offsets are 17.2 M pairs, two pieces of at most 2^24.  r against NumPy, bit for bit
-    against the same band fetched in chunks of 1 000 markers (one piece each), and those chunks' sums against NumPy exactly."""
+    against the same band fetched in chunks of 1 000 markers (one piece each), and those chunks' sums against NumPy exactly.  Then one
+    call of two pieces whose first marker is no multiple of 16: rows [7, 4197) are 17.16 M pairs, cut into [7, 4103) and [4103, 4197)."""
     N, M, W = 130, 4200, 4096
     geno = make(N, M, seed=N + M)
     dev = device(geno)
@@ -185,6 +186,9 @@ def test_the_piece_loop():
         rc, sc = dev.ld(W, m0=a, count=n)
         assert same_bits(rc, r[a:a + n]), a
         assert np.array_equal(sc, ref_s[a:a + n]), a
+    rc, sc = dev.ld(W, m0=7, count=4190)
+    assert same_bits(rc, r[7:4197])
+    assert np.array_equal(sc, ref_s[7:4197])
 
 
 def test_the_chains_own_dot():
