@@ -28,6 +28,7 @@ ABI_SYMBOLS = [
     "hgibbs_pca", "hgibbs_last_pca_ms", "hgibbs_region_var", "hgibbs_last_region_var_ms",
     "hgibbs_grm", "hgibbs_grm_info", "hgibbs_last_grm_ms",
     "hgibbs_grm_rowsums", "hgibbs_last_grm_rowsums_ms", "hgibbs_he_fit",
+    "hgibbs_row_sums", "hgibbs_last_row_sums_ms", "hgibbs_hwe_exact",
     # BayesW
     "hgibbs_grand_seed", "hgibbs_grand_next", "hgibbs_ars_sample", "hgibbs_w_init", "hgibbs_w_marker_stats", "hgibbs_w_set_model",
     "hgibbs_w_reduce", "hgibbs_w_refresh_vi", "hgibbs_w_get_vi", "hgibbs_w_marker_sums", "hgibbs_w_sweep", "hgibbs_w_last_sweep_stats", "hgibbs_w_ars_device_probe",
@@ -229,6 +230,9 @@ def lib():
     L.hgibbs_grm_rowsums.argtypes = [vp, C.c_int, dp, dp, dp, dp, dp, u32p]
     L.hgibbs_last_grm_rowsums_ms.argtypes = [vp, dp, dp]
     L.hgibbs_he_fit.argtypes = [C.c_uint32, dp, dp, dp, dp, dp, u32p, C.POINTER(HeResult)]
+    L.hgibbs_row_sums.argtypes = [vp, C.c_int, dp, dp]
+    L.hgibbs_last_row_sums_ms.argtypes = [vp, dp]
+    L.hgibbs_hwe_exact.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, dp]
     _lib = L
     return L
 
@@ -301,6 +305,14 @@ def he_fit(y, ay, ayy, a1, a2, partners):
     for form in ("cp", "sd"):
         out[form] = {k: getattr(getattr(res, form), k) for k, _ in HeForm._fields_}
     return out
+
+
+def hwe_exact(n_het, n_hom_a, n_hom_b):
+    """hgibbs_hwe_exact (host only): the P value of the exact test of Hardy-Weinberg proportions (Wigginton, Cutler & Abecasis 2005)
+    for the genotype counts; NaN without genotypes."""
+    p = C.c_double()
+    check(lib().hgibbs_hwe_exact(int(n_het), int(n_hom_a), int(n_hom_b), C.byref(p)))
+    return p.value
 
 
 class Device:
@@ -472,6 +484,20 @@ class Device:
     def last_score_ms(self):
         v = C.c_double()
         check(self.L.hgibbs_last_score_ms(self.h, C.byref(v)))
+        return v.value
+
+    def row_sums(self, tab):
+        """(T, M, 4) tables -> (n_local, T): sum_j tab[t, j, code_ij], code 3 = missing call (hgibbs_row_sums)."""
+        tab = np.ascontiguousarray(tab, dtype=np.float64)
+        if tab.ndim != 3 or tab.shape[1:] != (self.M, 4):
+            raise ValueError("tab must be (T, %d, 4)" % self.M)
+        out = np.zeros((self.n_local, tab.shape[0]))
+        check(self.L.hgibbs_row_sums(self.h, tab.shape[0], _dp(tab), _dp(out)))
+        return out
+
+    def last_row_sums_ms(self):
+        v = C.c_double()
+        check(self.L.hgibbs_last_row_sums_ms(self.h, C.byref(v)))
         return v.value
 
     def region_var(self, a, o, sets):

@@ -194,6 +194,8 @@ struct hgibbs_ctx {
     int score_sp = 0;     // option score_sp: samples per pass of hgibbs_score, 2, 4, 8 or 16 (0 = automatic, hg_score.hip.h)
     int score_ranges = 0; // option score_ranges: at most this many ranges of markers per column of workgroups (0 = automatic)
     double score_ms = 0.0; // device time of the last hgibbs_score (weights to digits, products, rounding)
+    int rowsums_ranges = 0;    // option rowsums_ranges: at most this many ranges of markers per column of workgroups of hgibbs_row_sums (0 = automatic)
+    double row_sums_ms = 0.0;  // device time of the last hgibbs_row_sums (scales, digits, products, rounding); 0 after a refused call
     int ld_split = 0;      // option ld_split: ranges of individuals the workgroups of hgibbs_ld split the columns into (0 = automatic)
     double ld_ms = 0.0;    // device time of the last hgibbs_ld (every piece: zeroing, products, final formula)
     int mdots_split = 0;   // option mdots_split: ranges of individuals the workgroups of hgibbs_marker_dots split the columns into (0 = automatic)
@@ -1317,6 +1319,9 @@ int hgibbs_set_option(hgibbs_t h, const char* name, int64_t value)
     } else if (!std::strcmp(name, "score_ranges")) {
         if (value < 0 || value > 65535) return fail("score_ranges must be in [0,65535] (0 = automatic)");
         h->score_ranges = (int)value;
+    } else if (!std::strcmp(name, "rowsums_ranges")) {
+        if (value < 0 || value > 65535) return fail("rowsums_ranges must be in [0,65535] (0 = automatic)");
+        h->rowsums_ranges = (int)value;
     } else if (!std::strcmp(name, "batch")) {
         if (value < 0 || value > MAX_BATCH) return fail("batch must be in [0,%d] (0 = auto)", MAX_BATCH);
         h->batch = (uint32_t)value;
@@ -2158,6 +2163,7 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
 #include "hg_bayesw.hip.h"
 #include "hg_ops.hip.h"
 #include "hg_score.hip.h"
+#include "hg_rowsums.hip.h"
 #include "hg_rvar.hip.h"
 #include "hg_ld.hip.h"
 #include "hg_ldscore.hip.h"

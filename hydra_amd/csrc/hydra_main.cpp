@@ -69,6 +69,13 @@
 // DESIGN.md section 22).  <dir>/<name>.HEreg (or F) has the layout of GCTA's --HEreg; with --he-rows <out>.rows has the per-row sums.
 // Not covered: bivariate HE, several matrices, REML.
 //
+// `--qc [--qc-out PREFIX] [--qc-maf X] [--qc-geno X] [--qc-mind X] [--qc-hwe P] [--qc-het-sd K]` appended to a bayesMPI command line samples
+// nothing either: the quality control that comes before everything else, on the chain's rows.  Per marker, from the counts of
+// hgibbs_marker_stats: allele frequency (.frq), call rate (.lmiss) and the exact Hardy-Weinberg test of hgibbs_hwe_exact (.hwe); per
+// row, from ONE call of hgibbs_row_sums with seven tables: call rate (.imiss), homozygosity and F (.het) and GCTA's three inbreeding
+// estimates (.ibc) over the autosomal markers with a finite sd (run_qc).  With thresholds, PREFIX.qc.exclude and
+// PREFIX.qc.remove list what fails them; PREFIX defaults to <dir>/<name>.  Tab-separated; not byte parity with PLINK or GCTA.
+//
 // Not reproduced (out of scope for the hot path): sparse
 // file formats, bayesFH, marker-sharded MPI, the .lst/tarball.
 // Multi-GPU: one process per GPU (RANK/WORLD_SIZE/LOCAL_RANK in the
@@ -130,6 +137,8 @@ struct Options { // src/options.hpp:20-138 (subset that reaches bayesMPI)
     std::string grmOut, grmSparse;                   // --grm-out PREFIX, --grm-sparse T as given (checked before the device)
     bool he = false, heRows = false;                 // --he: Haseman-Elston regression on the chain's rows; --he-rows: the per-row sums too
     std::string heOut;                               // --he-out F
+    bool qc = false, qcMafGiven = false, qcGenoGiven = false, qcMindGiven = false, qcHweGiven = false, qcHetSdGiven = false; // --qc; which thresholds were given
+    std::string qcOut, qcMaf, qcGeno, qcMind, qcHwe, qcHetSd; // --qc-out PREFIX; --qc-maf X, --qc-geno X, --qc-mind X, --qc-hwe P, --qc-het-sd K as given (checked before the device)
     bool ldScore = false, ldScoreKbGiven = false, ldScoreSnpsGiven = false, ldScoreGroups = false, ldScoreRaw = false; // --ld-score; which --ld-score-* were given
     std::string ldScoreKb, ldScoreSnps, ldScoreSets, ldScoreOut; // --ld-score-kb KB, --ld-score-snps W as given (checked before the device), --ld-score-sets, --ld-score-out PREFIX
     bool clump = false, clumpKbGiven = false, clumpSnpsGiven = false; // --clump FILE; which window option was given
@@ -306,6 +315,24 @@ Options parse(int argc, const char* argv[])
         else if (a == "--he") o.he = true;
         else if (a == "--he-out") o.heOut = need(i);
         else if (a == "--he-rows") o.heRows = true;
+        else if (a == "--qc") o.qc = true;
+        else if (a == "--qc-out") o.qcOut = need(i);
+        else if (a == "--qc-maf") {
+            o.qcMaf = need(i);
+            o.qcMafGiven = true;
+        } else if (a == "--qc-geno") {
+            o.qcGeno = need(i);
+            o.qcGenoGiven = true;
+        } else if (a == "--qc-mind") {
+            o.qcMind = need(i);
+            o.qcMindGiven = true;
+        } else if (a == "--qc-hwe") {
+            o.qcHwe = need(i);
+            o.qcHweGiven = true;
+        } else if (a == "--qc-het-sd") {
+            o.qcHetSd = need(i);
+            o.qcHetSdGiven = true;
+        }
         else if (a == "--grm-sparse") {
             o.grmSparse = need(i);
             o.grmSparseGiven = true;
@@ -2360,16 +2387,171 @@ int run_he(const Options& opt, const Cohort& co, const std::vector<double>& y_ra
     return 0;
 }
 
+// ---- --qc: quality control of the chain's rows and the training markers ----
+// a number as the tables print it: nine digits, NA when it is not defined
+std::string qc_num(double v)
+{
+    if (!std::isfinite(v)) return "NA";
+    char b[32];
+    std::snprintf(b, sizeof b, "%.9g", v);
+    return b;
+}
+
+int run_qc(const Options& opt, const Cohort& co)
+{
+    const std::string prefix = opt.qcOut.empty() ? opt.mcmcOutDir + "/" + opt.mcmcOutNam : opt.qcOut;
+    const bool markerT = opt.qcMafGiven || opt.qcGenoGiven || opt.qcHweGiven, rowT = opt.qcMindGiven || opt.qcHetSdGiven;
+    double tMaf = 0.0, tGeno = 0.0, tMind = 0.0, tHwe = 0.0, tHet = 0.0;
+    whole_num(opt.qcMaf, tMaf);
+    whole_num(opt.qcGeno, tGeno);
+    whole_num(opt.qcMind, tMind);
+    whole_num(opt.qcHwe, tHwe);
+    whole_num(opt.qcHetSd, tHet);
+    const FamIds fam = read_fam_ids(opt.bedFile + ".fam", co.numInds, co.numNAs ? &co.keep : nullptr);
+    const unsigned N = co.Ntot, M = co.Mtot;
+    if (fam.fid.size() != N) fatal("FATAL  : " + opt.bedFile + ".fam: " + std::to_string(fam.fid.size()) + " kept rows, expected " + std::to_string(N));
+    const BimRows bim = read_bim(opt.bedFile + ".bim", M);
+    if (bim.id.size() != M) fatal("FATAL  : " + opt.bedFile + ".bim: " + std::to_string(bim.id.size()) + " rows, expected " + std::to_string(M));
+    std::vector<uint8_t> bed = read_bed(opt.bedFile, co.numInds, M);
+    if (opt.qcOut.empty()) make_out_dir(opt);
+    const char* const ext[6] = {".frq", ".lmiss", ".hwe", ".imiss", ".het", ".ibc"};
+    const char* const head[6] = {"CHR\tSNP\tA1\tA2\tMAF\tNCHROBS\n",        "CHR\tSNP\tN_MISS\tN_GENO\tF_MISS\n", "CHR\tSNP\tTEST\tA1\tA2\tGENO\tO(HET)\tE(HET)\tP\n",
+                                 "FID\tIID\tN_MISS\tN_GENO\tF_MISS\n",      "FID\tIID\tO(HOM)\tE(HOM)\tN(NM)\tF\n", "FID\tIID\tNOMISS\tFhat1\tFhat2\tFhat3\n"};
+    FILE* f[6];
+    for (int k = 0; k < 6; ++k) {
+        f[k] = open_out(prefix + ext[k], "w");
+        std::fputs(head[k], f[k]);
+    }
+    FILE* fx = markerT ? open_out(prefix + ".qc.exclude", "w") : nullptr;
+    FILE* fr = rowT ? open_out(prefix + ".qc.remove", "w") : nullptr;
+    if (fx) std::fputs("SNP\tREASON\n", fx);
+    if (fr) std::fputs("FID\tIID\tREASON\n", fr);
+
+    hgibbs_t dev = open_training(co, bed);
+    std::vector<double> mave(M), mstd(M);
+    std::vector<uint64_t> n1(M), n2(M), nm(M);
+    hg_check(hgibbs_marker_stats(dev, mave.data(), mstd.data(), n1.data(), n2.data(), nm.data()), "hgibbs_marker_stats");
+
+    // the seven tables: t0 missing calls over every marker; over the QC markers (a finite sd, chromosome 1 .. 22)
+    // t1 called, t2 homozygous, t3 expected homozygosity, t4 .. t6 the terms of GCTA's Fhat1 .. Fhat3
+    const int T = 7;
+    std::vector<double> tab((size_t)T * M * 4, 0.0);
+    std::vector<uint8_t> qcm(M, 0);
+    unsigned nqc = 0;
+    for (unsigned j = 0; j < M; ++j) {
+        auto at = [&](int t) { return &tab[((size_t)t * M + j) * 4]; };
+        at(0)[3] = 1.0;
+        long chr = 0;
+        if (!std::isfinite(mstd[j]) || !whole_int(bim.chr[j], chr) || chr < 1 || chr > 22) continue;
+        qcm[j] = 1;
+        ++nqc;
+        const double nc = (double)(N - nm[j]), p = ((double)n1[j] + 2.0 * (double)n2[j]) / (2.0 * nc), h = 2.0 * p * (1.0 - p);
+        const double e = 1.0 - h * (2.0 * nc) / (2.0 * nc - 1.0);
+        for (int g = 0; g < 3; ++g) {
+            const double x = (double)g;
+            at(1)[g] = 1.0;
+            at(2)[g] = g == 1 ? 0.0 : 1.0;
+            at(3)[g] = e;
+            at(4)[g] = (x - 2.0 * p) * (x - 2.0 * p) / h - 1.0;
+            at(5)[g] = 1.0 - x * (2.0 - x) / h;
+            at(6)[g] = (x * x - (1.0 + 2.0 * p) * x + 2.0 * p * p) / h;
+        }
+    }
+    std::vector<double> sums((size_t)N * T);
+    hg_check(hgibbs_row_sums(dev, T, tab.data(), sums.data()), "hgibbs_row_sums");
+    double ms = 0.0;
+    hg_check(hgibbs_last_row_sums_ms(dev, &ms), "hgibbs_last_row_sums_ms");
+    hgibbs_destroy(dev);
+
+    // per marker, in .bim order
+    const double NaN = std::numeric_limits<double>::quiet_NaN();
+    unsigned xMono = 0, xMaf = 0, xGeno = 0, xHwe = 0, xAny = 0;
+    for (unsigned j = 0; j < M; ++j) {
+        const uint64_t ncl = (uint64_t)N - nm[j], n0 = ncl - n1[j] - n2[j];
+        const double p = ncl ? ((double)n1[j] + 2.0 * (double)n2[j]) / (2.0 * (double)ncl) : NaN;
+        const double fmiss = (double)nm[j] / (double)N;
+        double P = NaN;
+        hg_check(hgibbs_hwe_exact((uint32_t)n1[j], (uint32_t)n2[j], (uint32_t)n0, &P), "hgibbs_hwe_exact");
+        const char *chr = bim.chr[j].c_str(), *id = bim.id[j].c_str(), *a1 = bim.a1[j].c_str(), *a2 = bim.a2[j].c_str();
+        std::fprintf(f[0], "%s\t%s\t%s\t%s\t%s\t%llu\n", chr, id, a1, a2, qc_num(p).c_str(), 2ull * ncl);
+        std::fprintf(f[1], "%s\t%s\t%llu\t%u\t%s\n", chr, id, (unsigned long long)nm[j], N, qc_num(fmiss).c_str());
+        std::fprintf(f[2], "%s\t%s\tALL\t%s\t%s\t%llu/%llu/%llu\t%s\t%s\t%s\n", chr, id, a1, a2, (unsigned long long)n2[j], (unsigned long long)n1[j],
+                     (unsigned long long)n0, qc_num(ncl ? (double)n1[j] / (double)ncl : NaN).c_str(), qc_num(2.0 * p * (1.0 - p)).c_str(), qc_num(P).c_str());
+        if (!fx) continue;
+        std::string why;
+        auto add = [&](const char* r) { why += (why.empty() ? "" : ","); why += r; };
+        if (!std::isfinite(mstd[j])) {
+            add("MONO");
+            ++xMono;
+        } else {
+            if (opt.qcMafGiven && std::min(p, 1.0 - p) < tMaf) add("MAF"), ++xMaf;
+            if (opt.qcGenoGiven && fmiss > tGeno) add("GENO"), ++xGeno;
+            if (opt.qcHweGiven && P < tHwe) add("HWE"), ++xHwe;
+        }
+        if (!why.empty()) {
+            std::fprintf(fx, "%s\t%s\n", id, why.c_str());
+            ++xAny;
+        }
+    }
+
+    // per kept row, in .fam order
+    std::vector<double> F(N, NaN);
+    for (unsigned i = 0; i < N; ++i) {
+        const double* s = &sums[(size_t)i * T];
+        if (s[1] > 0.0 && s[1] - s[3] != 0.0) F[i] = (s[2] - s[3]) / (s[1] - s[3]);
+    }
+    double fmean = NaN, fsd = NaN;
+    {
+        long double a = 0.0L, q = 0.0L;
+        unsigned k = 0;
+        for (unsigned i = 0; i < N; ++i)
+            if (std::isfinite(F[i])) a += F[i], ++k;
+        if (k >= 2) {
+            a /= k;
+            for (unsigned i = 0; i < N; ++i)
+                if (std::isfinite(F[i])) q += ((long double)F[i] - a) * ((long double)F[i] - a);
+            fmean = (double)a;
+            fsd = (double)std::sqrt(q / (k - 1));
+        }
+    }
+    unsigned rMind = 0, rHet = 0, rAny = 0;
+    for (unsigned i = 0; i < N; ++i) {
+        const double* s = &sums[(size_t)i * T];
+        const char *fid = fam.fid[i].c_str(), *iid = fam.iid[i].c_str();
+        const double fmiss = s[0] / (double)M, nn = s[1];
+        std::fprintf(f[3], "%s\t%s\t%.0f\t%u\t%s\n", fid, iid, s[0], M, qc_num(fmiss).c_str());
+        std::fprintf(f[4], "%s\t%s\t%.0f\t%s\t%.0f\t%s\n", fid, iid, s[2], qc_num(s[3]).c_str(), nn, qc_num(F[i]).c_str());
+        std::fprintf(f[5], "%s\t%s\t%.0f\t%s\t%s\t%s\n", fid, iid, nn, qc_num(nn > 0.0 ? s[4] / nn : NaN).c_str(), qc_num(nn > 0.0 ? s[5] / nn : NaN).c_str(),
+                     qc_num(nn > 0.0 ? s[6] / nn : NaN).c_str());
+        if (!fr) continue;
+        std::string why;
+        if (opt.qcMindGiven && fmiss > tMind) why = "MIND", ++rMind;
+        if (opt.qcHetSdGiven && std::isfinite(F[i]) && std::isfinite(fsd) && std::fabs(F[i] - fmean) > tHet * fsd) why += (why.empty() ? "HET" : ",HET"), ++rHet;
+        if (!why.empty()) {
+            std::fprintf(fr, "%s\t%s\t%s\n", fid, iid, why.c_str());
+            ++rAny;
+        }
+    }
+    for (int k = 0; k < 6; ++k) close_out(f[k], prefix + ext[k]);
+    if (fx) close_out(fx, prefix + ".qc.exclude");
+    if (fr) close_out(fr, prefix + ".qc.remove");
+    std::printf("QC     : %u rows, %u markers (%u enter the per-row statistics) -> %s.{frq,lmiss,hwe,imiss,het,ibc} (row sums %.3f ms on the device)\n", N, M, nqc,
+                prefix.c_str(), ms);
+    std::printf("QC     : markers listed %u (MONO %u, MAF %u, GENO %u, HWE %u)%s; rows listed %u (MIND %u, HET %u)%s\n", xAny, xMono, xMaf, xGeno, xHwe,
+                fx ? "" : " [no marker threshold]", rAny, rMind, rHet, fr ? "" : " [no row threshold]");
+    return 0;
+}
+
 // ---- the analysis modes -------------------------------------------------------
 // An analysis mode is an option that, appended to a bayesMPI command line, samples nothing and runs one analysis on the chain's rows
-// (run_predict .. run_he above).  What the modes share is refused in one place, from one row per mode.
+// (run_predict .. run_qc above).  What the modes share is refused in one place, from one row per mode.
 struct Mode {
     const char* flag;   // the option that asks for the mode
     bool given;
     const char* wmpi;   // how it refuses --mpibayes bayesWMPI, after its flag
     const char* orphan; // the first of its dependent options that was given: they need the mode (null: none was)
 };
-enum { PREDICT, LD, ASSOC, KING, PCA, PVE, GRM, LDSCORE, CLUMP, LDPRUNE, HE, NMODES }; // the order in which a mode names the earlier ones it cannot be combined with
+enum { PREDICT, LD, ASSOC, KING, PCA, PVE, GRM, LDSCORE, CLUMP, LDPRUNE, HE, QC, NMODES }; // the order in which a mode names the earlier ones it cannot be combined with
 
 const char* first_given(std::initializer_list<std::pair<const char*, bool>> deps)
 {
@@ -2483,6 +2665,21 @@ void check_pve_args(const Options& opt)
     if (opt.pveGroups && opt.groupIndexFile.empty()) fatal("FATAL  : --pve-groups needs --groupIndexFile");
 }
 
+void check_qc_args(const Options& opt)
+{
+    struct { const char* flag; bool given; const std::string& t; double lo, hi; const char* what; } const unit[4] = {
+        {"--qc-maf", opt.qcMafGiven, opt.qcMaf, 0.0, 0.5, "the minor allele frequency must be a number in [0, 0.5]"},
+        {"--qc-geno", opt.qcGenoGiven, opt.qcGeno, 0.0, 1.0, "the missing rate of a marker must be a number in [0, 1]"},
+        {"--qc-mind", opt.qcMindGiven, opt.qcMind, 0.0, 1.0, "the missing rate of an individual must be a number in [0, 1]"},
+        {"--qc-hwe", opt.qcHweGiven, opt.qcHwe, 0.0, 1.0, "the P value must be a number in [0, 1]"},
+    };
+    double v = 0.0;
+    for (const auto& u : unit)
+        if (u.given && (!whole_num(u.t, v) || !(v >= u.lo && v <= u.hi))) fatal(std::string("FATAL  : ") + u.flag + " " + u.t + ": " + u.what);
+    if (opt.qcHetSdGiven && (!whole_num(opt.qcHetSd, v) || !std::isfinite(v) || !(v > 0.0)))
+        fatal("FATAL  : --qc-het-sd " + opt.qcHetSd + ": the number of standard deviations must be a finite number > 0");
+}
+
 // Every refusal of the modes, before anything is read: mode by mode (--ld-window first, then in the table's order), what all share,
 // then the mode's own arguments
 void check_modes(const Options& opt, int nranks)
@@ -2511,8 +2708,11 @@ void check_modes(const Options& opt, int nranks)
         {"--ld-prune", opt.ldPrune, takes,
          first_given({{"--ld-prune-kb", opt.ldPruneKbGiven}, {"--ld-prune-snps", opt.ldPruneSnpsGiven}, {"--ld-prune-out", !opt.ldPruneOut.empty()}})},
         {"--he", opt.he, takes, first_given({{"--he-out", !opt.heOut.empty()}, {"--he-rows", opt.heRows}})},
+        {"--qc", opt.qc, takes,
+         first_given({{"--qc-out", !opt.qcOut.empty()}, {"--qc-maf", opt.qcMafGiven}, {"--qc-geno", opt.qcGenoGiven}, {"--qc-mind", opt.qcMindGiven},
+                      {"--qc-hwe", opt.qcHweGiven}, {"--qc-het-sd", opt.qcHetSdGiven}})},
     };
-    for (const int i : {LD, PREDICT, ASSOC, KING, PCA, PVE, GRM, LDSCORE, CLUMP, LDPRUNE, HE}) {
+    for (const int i : {LD, PREDICT, ASSOC, KING, PCA, PVE, GRM, LDSCORE, CLUMP, LDPRUNE, HE, QC}) {
         const Mode& m = modes[i];
         const std::string flag = m.flag;
         if (!m.given) {
@@ -2532,6 +2732,7 @@ void check_modes(const Options& opt, int nranks)
         if (i == LDSCORE) check_ldscore_args(opt);
         if (i == CLUMP) check_clump_args(opt);
         if (i == LDPRUNE) check_ldprune_args(opt);
+        if (i == QC) check_qc_args(opt);
     }
 }
 
@@ -2599,6 +2800,7 @@ int main(int argc, const char* argv[])
     if (opt.clump) return run_ldselect(opt, co, true);
     if (opt.ldPrune) return run_ldselect(opt, co, false);
     if (opt.he) return run_he(opt, co, y, covX, C);
+    if (opt.qc) return run_qc(opt, co);
 
     std::vector<int32_t> groups;
     std::vector<std::vector<double>> mS;

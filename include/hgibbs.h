@@ -184,6 +184,7 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
  *   ldscore_piece   hgibbs_ld_scores: band rows per piece, 0..2^20 (0 = automatic)
  *   ldmask_piece    hgibbs_ld_mask: band rows per piece, 0..2^20 (0 = automatic; rounded up to a multiple of 16)
  *   grm_piece       hgibbs_grm, hgibbs_grm_rowsums: pairs per piece of rows, 0..2^25 (0 = automatic: 2^25; a row alone may exceed it)
+ *   rowsums_ranges  hgibbs_row_sums: at most this many ranges of markers split over workgroups, 0..65535 (0 = automatic)
  *   p2p, force_split, chunk, debug_timing, w_kernel_timing   transport selection and diagnostics */
 int hgibbs_set_option(hgibbs_t h, const char* name, int64_t value);
 /* Statistics of the last sweep: launches, markers per launch, device time of
@@ -245,6 +246,37 @@ int hgibbs_resident_trace(hgibbs_t h, uint64_t* out, uint64_t words);
 int hgibbs_score(hgibbs_t h, int S, const double* a, const double* o, double* out);
 /* device time of the last hgibbs_score in ms: every kernel of the call (scales, digits, products, rounding), not the host copies */
 int hgibbs_last_score_ms(hgibbs_t h, double* ms);
+
+/* ---- row sums of a function of the genotype */
+/* For the BED loaded on the handle and T tables of M x 4 doubles on the host (tab[(t*M + j)*4 + c], table-major),
+ *   out[i*T + t] = sum_j tab[(t*M + j)*4 + code_ij]      over the M loaded markers, for this handle's n_local rows
+ * where code_ij in {0, 1, 2, 3} is the genotype as the handle stores it: the count of A1 alleles, 3 = missing call.  Padding slots
+ * beyond n_local produce no output row.  One pass over the codes on the device.  The contract, which a restatement in integers
+ * matches bit for bit:
+ *   scale     each table t has one: e_t the smallest integer with max_{j,c} |tab_t[j][c]| < 2^e_t (frexp), E_t = 52 - e_t, and
+ *             E_t = 0 for an all-zero table
+ *   quantise  q = llrint(ldexp(v, E_t)) (round to nearest, ties to even), written in seven signed base-256 digits
+ *   sum       the row's sum is the exact integer sum_j q[t][j][code_ij], turned to f64 ONCE (round to nearest even), times 2^-E_t;
+ *             the workgroups' parts meet in 64-bit integer atomic adds, never floating-point ones
+ * so |out - exact| <= M max|tab_t| 2^-52 before that one rounding (0.5 2^-E_t per term, 2^-E_t <= 2 max 2^-52); a table whose
+ * entries are all 0 or 1 returns the exact count; column t of a call with T tables equals the call with T = 1 and that table; and
+ * the result does not depend on any tiling, on the option rowsums_ranges or on repeats.  Refused with a message: a null argument,
+ * T outside 1..16, a table entry that is not finite, a handle of several ranks, a handle without genotypes, buffers that do not
+ * fit in free device memory (the tables, 16 T bytes per marker of digits for up to 8 tables a pass, 24 T bytes per row), M >= 2^31
+ * (the 64-bit sums).  The i32 sums of a digit allow 2^17 blocks of 64 markers per workgroup: longer marker lists are always split
+ * into ranges, so that bound refuses nothing.  Option (hgibbs_set_option): rowsums_ranges, at most this many ranges of markers split
+ * over workgroups (0 = automatic). */
+int hgibbs_row_sums(hgibbs_t h, int T, const double* tab, double* out);
+/* device time of the last hgibbs_row_sums in ms: every kernel of the call (scales, digits, products, rounding), not the host
+ * copies; 0 after a refused call */
+int hgibbs_last_row_sums_ms(hgibbs_t h, double* ms);
+
+/* The exact test of Hardy-Weinberg proportions of Wigginton, Cutler & Abecasis (2005) (host only: no handle, no device).  Given the
+ * allele counts of n_het + n_hom_a + n_hom_b genotypes, P(het = k) is proportional to the number of arrangements; the weights are
+ * computed by the two-sided recursion outward from the mode and normalised by their sum.  *p = the sum of the probabilities of every
+ * feasible k whose probability is <= P(n_het) (1 + 1e-9): the factor is the tie rule, which keeps mirror-image counts from being
+ * dropped by a rounding error.  No genotypes: *p = NaN, returns 0.  Refused: a null pointer. */
+int hgibbs_hwe_exact(uint32_t n_het, uint32_t n_hom_a, uint32_t n_hom_b, double* p);
 
 /* ---- mean and variance of the scores of marker sets */
 /* For the BED on the handle, S weight vectors (a, o: S x M as in hgibbs_score) and nsets marker sets
