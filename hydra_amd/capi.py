@@ -29,6 +29,7 @@ ABI_SYMBOLS = [
     "hgibbs_grm", "hgibbs_grm_info", "hgibbs_last_grm_ms",
     "hgibbs_grm_rowsums", "hgibbs_last_grm_rowsums_ms", "hgibbs_he_fit",
     "hgibbs_row_sums", "hgibbs_last_row_sums_ms", "hgibbs_hwe_exact",
+    "hgibbs_sparse_begin", "hgibbs_sparse_put", "hgibbs_sparse_end", "hgibbs_sparse_counts", "hgibbs_sparse_get", "hgibbs_last_sparse_ms",
     # BayesW
     "hgibbs_grand_seed", "hgibbs_grand_next", "hgibbs_ars_sample", "hgibbs_w_init", "hgibbs_w_marker_stats", "hgibbs_w_set_model",
     "hgibbs_w_reduce", "hgibbs_w_refresh_vi", "hgibbs_w_get_vi", "hgibbs_w_marker_sums", "hgibbs_w_sweep", "hgibbs_w_last_sweep_stats", "hgibbs_w_ars_device_probe",
@@ -62,6 +63,11 @@ class HeForm(C.Structure):
 
 class HeResult(C.Structure):
     _fields_ = [("n_used", C.c_uint32), ("n_left_out", C.c_uint32), ("pairs", C.c_uint64), ("vp", C.c_double), ("cp", HeForm), ("sd", HeForm)]
+
+
+class SparseList(C.Structure):
+    _fields_ = [("start", C.POINTER(C.c_uint64)), ("len", C.POINTER(C.c_uint64)), ("idx", C.POINTER(C.c_uint32)),
+                ("idx_base", C.c_uint64), ("idx_count", C.c_uint64)]
 
 
 class RestartState(C.Structure):
@@ -232,6 +238,13 @@ def lib():
     L.hgibbs_he_fit.argtypes = [C.c_uint32, dp, dp, dp, dp, dp, u32p, C.POINTER(HeResult)]
     L.hgibbs_row_sums.argtypes = [vp, C.c_int, dp, dp]
     L.hgibbs_last_row_sums_ms.argtypes = [vp, dp]
+    sl = C.POINTER(SparseList)
+    L.hgibbs_sparse_begin.argtypes = [vp, C.c_uint32, C.c_uint32, u8p, C.c_uint32, C.c_uint32, C.c_uint32]
+    L.hgibbs_sparse_put.argtypes = [vp, C.c_uint32, C.c_uint32, sl, sl, sl]
+    L.hgibbs_sparse_end.argtypes = [vp]
+    L.hgibbs_sparse_counts.argtypes = [vp, C.c_uint32, C.c_uint32, u64p, u64p, u64p]
+    L.hgibbs_sparse_get.argtypes = [vp, C.c_uint32, C.c_uint32, u32p, u32p, u32p]
+    L.hgibbs_last_sparse_ms.argtypes = [vp, dp, dp]
     L.hgibbs_hwe_exact.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, dp]
     _lib = L
     return L
@@ -402,6 +415,57 @@ class Device:
         out = np.zeros((mcount, (self.n_local + 3) // 4), dtype=np.uint8)
         check(self.L.hgibbs_get_bed(self.h, m0, mcount, _u8(out), out.shape[1]))
         return out
+
+    # -- hydra's sparse representation: three index lists per marker (genotype 1, genotype 2, missing call) --
+    def sparse_begin(self, n_total, M, keep=None, row_begin=0, row_end=None, n_global=None):
+        kept = int(np.count_nonzero(keep)) if keep is not None else n_total
+        if row_end is None:
+            row_end = kept
+        if n_global is None:
+            n_global = kept
+        kp = _u8(np.ascontiguousarray(keep, dtype=np.uint8)) if keep is not None else None
+        check(self.L.hgibbs_sparse_begin(self.h, n_total, M, kp, row_begin, row_end, n_global))
+
+    def sparse_put(self, m0, lists):
+        """lists: three (start, len, idx, idx_base) for genotype 1, genotype 2 and missing calls; start and len hold one entry per
+        marker of the slab, start as absolute positions, idx the piece of the index list that starts at idx_base."""
+        hold, args, count = [], [], None
+        for start, ln, idx, base in lists:
+            start = np.ascontiguousarray(start, dtype=np.uint64)
+            ln = np.ascontiguousarray(ln, dtype=np.uint64)
+            idx = np.ascontiguousarray(idx, dtype=np.uint32)
+            if count is None:
+                count = start.shape[0]
+            if start.shape[0] != count or ln.shape[0] != count:
+                raise ValueError("start and len must hold one entry per marker of the slab")
+            hold.append((start, ln, idx))
+            args.append(SparseList(_u64(start), _u64(ln), idx.ctypes.data_as(C_U32P), int(base), idx.shape[0]))
+        check(self.L.hgibbs_sparse_put(self.h, m0, count, C.byref(args[0]), C.byref(args[1]), C.byref(args[2])))
+
+    def sparse_end(self):
+        check(self.L.hgibbs_sparse_end(self.h))
+        self._dims()
+
+    def sparse_counts(self, m0=0, count=None):
+        if count is None:
+            count = self.M - m0
+        n1, n2, nm = (np.zeros(count, dtype=np.uint64) for _ in range(3))
+        check(self.L.hgibbs_sparse_counts(self.h, m0, count, _u64(n1), _u64(n2), _u64(nm)))
+        return n1, n2, nm
+
+    def sparse_get(self, m0=0, count=None, want=(True, True, True)):
+        """The three concatenated index lists of markers [m0, m0 + count); a list not wanted comes back as None."""
+        if count is None:
+            count = self.M - m0
+        cnt = self.sparse_counts(m0, count)
+        out = [np.zeros(int(c.sum()), dtype=np.uint32) if w else None for c, w in zip(cnt, want)]
+        check(self.L.hgibbs_sparse_get(self.h, m0, count, *[o.ctypes.data_as(C_U32P) if o is not None else None for o in out]))
+        return out
+
+    def last_sparse_ms(self):
+        a, b = C.c_double(), C.c_double()
+        check(self.L.hgibbs_last_sparse_ms(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def marker_stats(self):
         M = self.M

@@ -57,6 +57,8 @@ extern "C" void hgibbs_set_error_(const char* msg) { g_err = msg; }
 // ---------------------------------------------------------------------------
 struct BwState; // BayesW side of the handle (hg_bayesw.hip.h)
 static void bw_free(BwState* b);
+struct SparseLoad; // a load from index lists between hgibbs_sparse_begin and hgibbs_sparse_end (hg_sparse.hip.h)
+static void sp_free(SparseLoad* s);
 
 struct hgibbs_ctx {
     int device = 0;
@@ -218,6 +220,9 @@ struct hgibbs_ctx {
     int ldmask_piece = 0;  // option ldmask_piece: band rows per piece of hgibbs_ld_mask (0 = automatic: the 2^24-pair bound)
     double ldm_ms[2] = {0, 0}; // device time of the last hgibbs_ld_mask: the products (zeroing, k_ld) and the reduce (zeroing the masks, k_ldm_reduce)
     double lds_ms[2] = {0, 0}; // device time of the last hgibbs_ld_scores: the products (zeroing, k_ld) and the reduce (k_lds_reduce, k_lds_final)
+    SparseLoad* sp = nullptr;      // hgibbs_sparse_begin .. hgibbs_sparse_end: the image in the making (bed stays null until it is published)
+    long long sparse_piece = 0;    // option sparse_piece: bytes of index buffers per piece of markers of hgibbs_sparse_get (0 = automatic)
+    double sparse_ms[2] = {0, 0};  // device time of the last sparse load (begin .. end, every kernel) and of the last hgibbs_sparse_get
 };
 
 static int ensure_scratch(hgibbs_ctx* h, size_t n)
@@ -736,6 +741,7 @@ int hgibbs_destroy(hgibbs_t h)
     (void)hipStreamSynchronize(h->stream);
     if (h->comm) ncclCommDestroy(h->comm);
     bw_free(h->bw);
+    sp_free(h->sp);
     for (int r = 0; r < MAX_RANKS; ++r)
         if (h->peer_base[r] && h->peer_base[r] != h->mbox) (void)hipIpcCloseMemHandle(h->peer_base[r]);
     if (h->mbox) (void)hipFree(h->mbox);
@@ -848,6 +854,7 @@ static int alloc_problem(hgibbs_ctx* h, uint32_t n_global, uint32_t n_local, uin
 {
     if (n_local == 0 || M == 0) return fail("empty problem: n_local=%u M=%u", n_local, M);
     if (h->bed) return fail("data already loaded on this handle");
+    if (h->sp) return fail("a sparse load is in progress on this handle (hgibbs_sparse_end)");
     h->n_global = n_global;
     h->n_local = n_local;
     h->M = M;
@@ -1388,6 +1395,9 @@ int hgibbs_set_option(hgibbs_t h, const char* name, int64_t value)
         h->w_kernel_timing = value != 0;
     } else if (!std::strcmp(name, "debug_timing")) {
         h->debug_timing = value != 0;
+    } else if (!std::strcmp(name, "sparse_piece")) {
+        if (value < 0) return fail("sparse_piece must be >= 0 bytes (0 = automatic)");
+        h->sparse_piece = (long long)value;
     } else if (!std::strcmp(name, "chunk")) {
         h->chunk = (int)value;
     } else {
@@ -2173,3 +2183,4 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
 #include "hg_pca.hip.h"
 #include "hg_grm.hip.h"
 #include "hg_grmsums.hip.h"
+#include "hg_sparse.hip.h"

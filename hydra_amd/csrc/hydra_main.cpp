@@ -76,8 +76,14 @@
 // estimates (.ibc) over the autosomal markers with a finite sd (run_qc).  With thresholds, PREFIX.qc.exclude and
 // PREFIX.qc.remove list what fails them; PREFIX defaults to <dir>/<name>.  Tab-separated; not byte parity with PLINK or GCTA.
 //
-// Not reproduced (out of scope for the hot path): sparse
-// file formats, bayesFH, marker-sharded MPI, the .lst/tarball.
+// `--sparse-dir D --sparse-basename B` reads the genotypes from hydra's ten sparse files D/B.{dim,sl?,ss?,si?} (? = 1, 2, m) instead of
+// --bfile's .bed, for the chains and every mode above; --bfile is then optional for the chains (N = --number-individuals, the
+// phenotype file is read line by line), and with it only .fam/.bim are taken from it.  `--bed-to-sparse --bfile X [--sparse-dir D
+// --sparse-basename B]` writes those files from the whole X.bed and samples nothing.
+//
+// Not reproduced (out of scope for the hot path): the mixed
+// in-memory representation (--threshold-fnz), --sparse-sync/--bed-sync, --check-RAM,
+// marker-block files, bayesFH, marker-sharded MPI, the .lst/tarball.
 // Multi-GPU: one process per GPU (RANK/WORLD_SIZE/LOCAL_RANK in the
 // environment, as torchrun/mpirun export them); individuals are sharded and the
 // ncclUniqueId travels through a file in --mcmc-out-dir.
@@ -145,6 +151,9 @@ struct Options { // src/options.hpp:20-138 (subset that reaches bayesMPI)
     std::string clumpFile, clumpP1, clumpP2, clumpR2, clumpKb, clumpSnps, clumpSnpField, clumpField, clumpOut; // --clump-* as given (checked before the device; empty: not given)
     bool ldPrune = false, ldPruneKbGiven = false, ldPruneSnpsGiven = false; // --ld-prune T; which window option was given
     std::string ldPruneT, ldPruneKb, ldPruneSnps, ldPruneOut; // --ld-prune T, --ld-prune-kb KB, --ld-prune-snps W as given, --ld-prune-out PREFIX
+    std::string sparseDir, sparseBsn;                // --sparse-dir D --sparse-basename B: hydra's sparse genotype files D/B.*
+    bool bedToSparse = false, preferBed = false;     // --bed-to-sparse: write them from --bfile; --read-from-bed-file: read the BED though the pair is given
+    bool blocksPerRankGiven = false;                 // --blocks-per-rank n: hydra's marker-sharded layout, no meaning here
     int batch = 0, cpg = 0; // tuning knobs of this build (not hydra's)
 };
 
@@ -372,14 +381,22 @@ Options parse(int argc, const char* argv[])
             o.ldPruneSnps = need(i);
             o.ldPruneSnpsGiven = true;
         } else if (a == "--ld-prune-out") o.ldPruneOut = need(i);
-        else if (a == "--sparse-dir" || a == "--sparse-basename" ||
-                 a == "--bed-to-sparse" || a == "--sparse-sync" || a == "--bed-sync")
+        else if (a == "--sparse-dir") o.sparseDir = need(i);
+        else if (a == "--sparse-basename") o.sparseBsn = need(i);
+        else if (a == "--bed-to-sparse") o.bedToSparse = true;
+        else if (a == "--read-from-bed-file") o.preferBed = true;
+        else if (a == "--blocks-per-rank") {
+            (void)need(i);
+            o.blocksPerRankGiven = true;
+        } else if (a == "--sparse-sync" || a == "--bed-sync")
             fatal("FATAL  : option " + a + " belongs to a part of hydra this build does not reproduce (SURVEY.md section 2)");
         else
             fatal("\nError: invalid option \"" + a + "\".\n"); // options.cpp:292-295
     }
     if (!o.seedGiven) o.seed = (unsigned)std::time(nullptr); // options.hpp:105
-    if (o.analysisType == "RAM") {                           // options.cpp:303-326
+    if (o.sparseDir.empty() != o.sparseBsn.empty())          // options.cpp:328-331
+        fatal("FATAL  : --sparse-dir and --sparse-basename must either be both set or unset (this build does not reproduce a default for one of them)");
+    if (o.analysisType == "RAM" && !o.bedToSparse) {         // options.cpp:303-326
         if (o.mcmcOutDir.empty()) fatal("FATAL  : --mcmc-out-dir is mandatory with --mpibayes");
         if (o.mcmcOutNam.empty()) fatal("FATAL  : --mcmc-out-name is mandatory with --mpibayes");
     }
@@ -590,6 +607,260 @@ void pwrite_at(FILE* f, long off, const void* p, size_t n)
 double now_s()
 {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// ---- hydra's sparse genotype files --------------------------------------------------------------------------
+// <dir>/<basename>.dim, the text "N M", and per class c in {1, 2, m} (genotype 1, genotype 2, missing call): .sl<c> and .ss<c>, M uint64
+// each (a marker's entries, the absolute position of its first entry), and .si<c>, the uint32 row indices (layout restated from
+// src/BayesRRm.cpp:437-770 and src/data.cpp:1072-1106, 1224-1290)
+const char* const SP_CLASS[3] = {"1", "2", "m"};
+
+struct SparseSource {
+    bool on = false;                    // the genotypes come from the sparse files, not from --bfile's .bed
+    std::string prefix;                 // <dir>/<basename>
+    std::vector<uint64_t> ss[3], sl[3]; // the first --number-markers entries of the six files
+};
+SparseSource g_sparse;
+
+bool use_sparse(const Options& o)
+{
+    return !o.sparseDir.empty() && !o.preferBed;
+}
+
+uint64_t readable_size(const std::string& p)
+{
+    struct stat sb;
+    FILE* f = std::fopen(p.c_str(), "rb");
+    if (!f || stat(p.c_str(), &sb) != 0 || !S_ISREG(sb.st_mode)) fatal("Error: can not open the file [" + p + "] to read.");
+    std::fclose(f);
+    return (uint64_t)sb.st_size;
+}
+
+// Every check of the sparse files, before any device is created; each refusal names the file and the fact.
+void open_sparse(const Options& opt, size_t numInds, unsigned M)
+{
+    SparseSource& s = g_sparse;
+    s.prefix = opt.sparseDir + "/" + opt.sparseBsn;
+    const std::string dim = s.prefix + ".dim";
+    (void)readable_size(dim);
+    std::ifstream in(dim);
+    long long n = -1, m = -1;
+    if (!(in >> n >> m) || n <= 0 || m <= 0) fatal("FATAL  : " + dim + " does not parse as \"N M\"");
+    if ((unsigned long long)n != numInds)
+        fatal("FATAL  : " + dim + " says N = " + std::to_string(n) + ", --number-individuals says " + std::to_string(numInds));
+    if ((unsigned long long)m < M) fatal("FATAL  : " + dim + " says M = " + std::to_string(m) + ": --number-markers " + std::to_string(M) + " exceeds it");
+    for (int c = 0; c < 3; ++c)
+        for (int k = 0; k < 2; ++k) {
+            const std::string path = s.prefix + (k ? ".sl" : ".ss") + SP_CLASS[c];
+            const uint64_t size = readable_size(path);
+            if (size < 8ull * M)
+                fatal("FATAL  : " + path + " holds " + std::to_string(size) + " bytes, fewer than 8 x --number-markers = " + std::to_string(8ull * M));
+            std::vector<uint64_t>& v = k ? s.sl[c] : s.ss[c];
+            v.resize(M);
+            FILE* f = std::fopen(path.c_str(), "rb");
+            if (!f || std::fread(v.data(), 8, M, f) != M) fatal("FATAL  : " + path + ": short read");
+            std::fclose(f);
+        }
+    for (int c = 0; c < 3; ++c) {
+        const std::string cl = SP_CLASS[c];
+        for (unsigned j = 0; j < M; ++j) {
+            if (s.sl[c][j] > numInds)
+                fatal("FATAL  : " + s.prefix + ".sl" + cl + ": marker " + std::to_string(j) + " lists " + std::to_string(s.sl[c][j]) + " rows, more than N = " +
+                      std::to_string(numInds));
+            if (s.ss[c][j] > (1ull << 60)) fatal("FATAL  : " + s.prefix + ".ss" + cl + ": marker " + std::to_string(j) + " starts at " + std::to_string(s.ss[c][j]));
+            if (j + 1 < M && s.ss[c][j + 1] < s.ss[c][j] + s.sl[c][j])
+                fatal("FATAL  : " + s.prefix + ".ss" + cl + ": marker " + std::to_string(j + 1) + " starts at " + std::to_string(s.ss[c][j + 1]) + ", before marker " +
+                      std::to_string(j) + " ends (" + std::to_string(s.ss[c][j]) + " + " + std::to_string(s.sl[c][j]) + ")");
+        }
+        const std::string path = s.prefix + ".si" + cl;
+        const uint64_t size = readable_size(path), need = 4 * (s.ss[c][M - 1] + s.sl[c][M - 1]);
+        if (size < need)
+            fatal("FATAL  : " + path + " holds " + std::to_string(size) + " bytes, fewer than 4 x (ss[last] + sl[last]) = " + std::to_string(need));
+    }
+    s.on = true;
+}
+
+// The sparse files onto the handle (hgibbs_sparse_begin / _put / _end), streamed in slabs of markers of at most 64 MiB a list (a marker
+// alone may exceed it): the host never holds more than a slab.  Rows that keep drops or that lie outside [lo, hi) are skipped by the
+// library.  Returns the bytes of index lists read.
+size_t load_sparse(hgibbs_t dev, size_t numInds, unsigned M, const uint8_t* keep, unsigned lo, unsigned hi, unsigned Ntot)
+{
+    const SparseSource& s = g_sparse;
+    FILE* f[3];
+    for (int c = 0; c < 3; ++c)
+        if (!(f[c] = std::fopen((s.prefix + ".si" + SP_CLASS[c]).c_str(), "rb"))) fatal("Error: can not open the file [" + s.prefix + ".si" + SP_CLASS[c] + "] to read.");
+    hg_check(hgibbs_sparse_begin(dev, (uint32_t)numInds, M, keep, lo, hi, Ntot), "hgibbs_sparse_begin");
+    const uint64_t cap = (64ull << 20) / 4;
+    std::vector<uint32_t> buf[3];
+    size_t bytes = 0;
+    for (unsigned j0 = 0; j0 < M;) {
+        unsigned j1 = j0 + 1;
+        auto fits = [&](unsigned j) {
+            for (int c = 0; c < 3; ++c)
+                if (s.ss[c][j] + s.sl[c][j] - s.ss[c][j0] > cap) return false;
+            return true;
+        };
+        while (j1 < M && fits(j1)) ++j1;
+        hgibbs_sparse_list li[3];
+        for (int c = 0; c < 3; ++c) {
+            const uint64_t base = s.ss[c][j0], n = s.ss[c][j1 - 1] + s.sl[c][j1 - 1] - base;
+            buf[c].resize(n);
+            if (fseeko(f[c], (off_t)(4 * base), SEEK_SET) != 0 || std::fread(buf[c].data(), 4, n, f[c]) != n)
+                fatal("FATAL  : " + s.prefix + ".si" + SP_CLASS[c] + ": short read");
+            li[c] = hgibbs_sparse_list{s.ss[c].data() + j0, s.sl[c].data() + j0, buf[c].data(), base, n};
+            bytes += 4 * n;
+        }
+        hg_check(hgibbs_sparse_put(dev, j0, j1 - j0, &li[0], &li[1], &li[2]), "hgibbs_sparse_put");
+        j0 = j1;
+    }
+    hg_check(hgibbs_sparse_end(dev), "hgibbs_sparse_end");
+    for (int c = 0; c < 3; ++c) std::fclose(f[c]);
+    return bytes;
+}
+
+// The training genotypes as the host holds them before the device takes them: --bfile's .bed, or nothing when they come from the
+// sparse files (those are streamed by put_genotypes)
+std::vector<uint8_t> read_training(const std::string& prefix, size_t numInds, size_t M)
+{
+    return g_sparse.on ? std::vector<uint8_t>() : read_bed(prefix, numInds, M);
+}
+
+// The genotypes of the kept rows [lo, hi) onto the handle, from either representation (Data::load_data_from_bed_file, data.cpp:671-739,
+// resp. load_data_from_sparse_files, :1224-1290): the device image is the same bytes either way.  Returns the bytes read; the host
+// copy is released.
+size_t put_genotypes(hgibbs_t dev, std::vector<uint8_t>& bed, size_t numInds, unsigned M, const uint8_t* keep, unsigned lo, unsigned hi, unsigned Ntot)
+{
+    if (g_sparse.on) return load_sparse(dev, numInds, M, keep, lo, hi, Ntot);
+    hg_check(hgibbs_load_bed(dev, bed.data(), (numInds + 3) / 4, (uint32_t)numInds, M, keep, lo, hi, Ntot), "hgibbs_load_bed");
+    const size_t bytes = bed.size();
+    std::vector<uint8_t>().swap(bed);
+    return bytes;
+}
+
+// Data::readPhenotypeFile(path, numberIndividuals, y), the reader of the route without a .fam (src/main.cpp:96-118): one line per
+// individual in file order, numInds lines required; "NA" marks a dropped individual
+void read_phen_lines(const std::string& path, size_t numInds, std::vector<double>& y, std::vector<uint8_t>& keep)
+{
+    std::ifstream in(path);
+    if (!in) fatal("Error: can not open the phenotype file [" + path + "] to read.");
+    keep.assign(numInds, 1);
+    y.clear();
+    std::string line;
+    size_t lineno = 0;
+    while (lineno < numInds && std::getline(in, line)) {
+        std::vector<std::string> col = tokens(line, " \t");
+        if (col.size() < 3) continue;
+        if (col[2] != "NA") y.push_back(std::atof(col[2].c_str()));
+        else keep[lineno] = 0;
+        ++lineno;
+    }
+    if (lineno != numInds) fatal("FATAL  : phenotype file covers " + std::to_string(lineno) + " of " + std::to_string(numInds) + " individuals");
+}
+
+// the INFO lines of the sparse route
+void sparse_info(const Options& opt, int rank, int nranks)
+{
+    if (rank != 0) return;
+    std::printf("INFO   : genotypes are read from the sparse files %s.*\n", g_sparse.prefix.c_str());
+    if (!opt.bedFile.empty())
+        std::printf("INFO   : --bfile with --sparse-dir/--sparse-basename is hydra's mixed representation, the same numbers twice: this build reads the sparse files and "
+                    "takes only .fam/.bim from --bfile\n");
+    if (nranks > 1) std::printf("INFO   : each of the %d ranks reads every slab of the sparse files; the library skips the rows outside a rank's shard\n", nranks);
+}
+
+// --bed-to-sparse: BayesRRm::write_sparse_data_files, src/BayesRRm.cpp:437-770 -- the whole .bed (every .fam row, NA phenotypes
+// included, every .bim marker) as the ten sparse files, compacted on the device (hgibbs_sparse_counts / hgibbs_sparse_get)
+int run_bed_to_sparse(const Options& opt, int nranks, int local_rank)
+{
+    if (nranks > 1) fatal("FATAL  : --bed-to-sparse runs on one process (WORLD_SIZE = " + std::to_string(nranks) + "): one process converts the whole file");
+    if (opt.bedFile.empty()) fatal("FATAL  : --bed-to-sparse needs --bfile");
+    // directory and name: the pair, else those of --bfile (BayesRRm.cpp:3093-3114)
+    const std::string::size_type cut = opt.bedFile.find_last_of('/');
+    std::string dir = cut == std::string::npos ? std::string(".") : (cut == 0 ? std::string("/") : opt.bedFile.substr(0, cut));
+    std::string bsn = cut == std::string::npos ? opt.bedFile : opt.bedFile.substr(cut + 1);
+    if (!opt.sparseDir.empty()) {
+        struct stat sb;
+        if (stat(opt.sparseDir.c_str(), &sb) != 0 || !S_ISDIR(sb.st_mode))
+            fatal("Fatal: requested directory for sparse output (" + opt.sparseDir + ") not found. Must be an existing directory.");
+        dir = opt.sparseDir;
+        bsn = opt.sparseBsn;
+    }
+    const std::string prefix = dir + "/" + bsn;
+    const size_t N = count_fam(opt.bedFile + ".fam", nullptr), Msz = count_bim(opt.bedFile + ".bim");
+    if (N == 0 || Msz == 0 || Msz >= 0x80000000ull) fatal("FATAL  : " + opt.bedFile + ": " + std::to_string(N) + " individuals, " + std::to_string(Msz) + " markers");
+    const unsigned M = (unsigned)Msz;
+    if (opt.blocksPerRankGiven) std::printf("INFO   : --blocks-per-rank ignored: one process writes the files in slabs of markers\n");
+    std::printf("INFO   : will always convert the whole file: N = %zu individuals (NA phenotypes included), M = %u markers\n", N, M);
+    std::vector<uint8_t> bed = read_bed(opt.bedFile, N, M);
+    const double t0 = now_s();
+    hgibbs_t dev = nullptr;
+    hg_check(hgibbs_create(local_rank, &dev), "hgibbs_create");
+    hg_check(hgibbs_load_bed(dev, bed.data(), (N + 3) / 4, (uint32_t)N, M, nullptr, 0, (uint32_t)N, (uint32_t)std::max<size_t>(N, 2)), "hgibbs_load_bed");
+    std::vector<uint8_t>().swap(bed);
+
+    FILE *fl[3], *fs[3], *fi[3];
+    for (int c = 0; c < 3; ++c) {
+        fl[c] = open_out(prefix + ".sl" + SP_CLASS[c], "wb");
+        fs[c] = open_out(prefix + ".ss" + SP_CLASS[c], "wb");
+        fi[c] = open_out(prefix + ".si" + SP_CLASS[c], "wb");
+    }
+    uint64_t at[3] = {0, 0, 0}; // entries written so far: the next marker's absolute start
+    const unsigned CH = 65536;  // markers whose counts are fetched together
+    const uint64_t cap = (256ull << 20) / 4; // entries of the three lists of a slab together (a marker alone may exceed it)
+    std::vector<uint64_t> cnt[3], ss;
+    std::vector<uint32_t> idx[3];
+    double dev_ms = 0.0;
+    for (unsigned m0 = 0; m0 < M; m0 += CH) {
+        const unsigned mc = std::min(CH, M - m0);
+        for (int c = 0; c < 3; ++c) cnt[c].resize(mc);
+        hg_check(hgibbs_sparse_counts(dev, m0, mc, cnt[0].data(), cnt[1].data(), cnt[2].data()), "hgibbs_sparse_counts");
+        for (unsigned k0 = 0; k0 < mc;) {
+            uint64_t tot[3] = {0, 0, 0};
+            unsigned k1 = k0;
+            for (; k1 < mc; ++k1) {
+                if (k1 > k0 && tot[0] + tot[1] + tot[2] + cnt[0][k1] + cnt[1][k1] + cnt[2][k1] > cap) break;
+                for (int c = 0; c < 3; ++c) tot[c] += cnt[c][k1];
+            }
+            for (int c = 0; c < 3; ++c) idx[c].resize(tot[c]);
+            hg_check(hgibbs_sparse_get(dev, m0 + k0, k1 - k0, idx[0].data(), idx[1].data(), idx[2].data()), "hgibbs_sparse_get");
+            double ms = 0.0;
+            hg_check(hgibbs_last_sparse_ms(dev, nullptr, &ms), "hgibbs_last_sparse_ms");
+            dev_ms += ms;
+            for (int c = 0; c < 3; ++c) {
+                ss.resize(k1 - k0);
+                for (unsigned k = k0; k < k1; ++k) {
+                    ss[k - k0] = at[c];
+                    at[c] += cnt[c][k];
+                }
+                if (std::fwrite(cnt[c].data() + k0, 8, k1 - k0, fl[c]) != k1 - k0 || std::fwrite(ss.data(), 8, k1 - k0, fs[c]) != k1 - k0 ||
+                    std::fwrite(idx[c].data(), 4, tot[c], fi[c]) != tot[c])
+                    fatal("FATAL  : short write on " + prefix + ".s??" );
+            }
+            k0 = k1;
+        }
+    }
+    for (int c = 0; c < 3; ++c) {
+        close_out(fl[c], prefix + ".sl" + SP_CLASS[c]);
+        close_out(fs[c], prefix + ".ss" + SP_CLASS[c]);
+        close_out(fi[c], prefix + ".si" + SP_CLASS[c]);
+    }
+    FILE* fd = open_out(prefix + ".dim", "w");
+    std::fprintf(fd, "%d %d\n", (int)N, (int)M);
+    close_out(fd, prefix + ".dim");
+    hg_check(hgibbs_destroy(dev), "hgibbs_destroy");
+    // the sizes on disk against what was written (check_file_size, BayesRRm.cpp:740-748)
+    for (int c = 0; c < 3; ++c) {
+        const std::pair<std::string, uint64_t> want[3] = {{".sl", 8ull * M}, {".ss", 8ull * M}, {".si", 4 * at[c]}};
+        for (const auto& w : want) {
+            const std::string path = prefix + w.first + SP_CLASS[c];
+            const uint64_t size = readable_size(path);
+            if (size != w.second) fatal("FATAL  : " + path + " holds " + std::to_string(size) + " bytes, " + std::to_string(w.second) + " were written");
+        }
+    }
+    std::printf("INFO   : wrote %s.{dim,sl?,ss?,si?}: %llu + %llu + %llu entries (genotype 1, genotype 2, missing call) in %.3f seconds, %.3f ms of them in the "
+                "device's compaction\n",
+                prefix.c_str(), (unsigned long long)at[0], (unsigned long long)at[1], (unsigned long long)at[2], now_s() - t0, dev_ms);
+    return 0;
 }
 
 // ---- restart readers: Data::read_mcmc_output_*_file, src/data.cpp:33-519 ----
@@ -836,9 +1107,12 @@ int run_bayesw(const Options& opt_in, int rank, int nranks, int local_rank)
     if (opt.failureFile.empty()) fatal("FATAL  : --failure is mandatory with --mpibayes bayesWMPI");
     if (opt.quad_points.empty()) fatal("Possible number of quad_points = 3,5,7,9,11,13,15,17,25"); // src/BayesW.cpp:706-708
     const int quad = std::atoi(opt.quad_points.c_str());
-    std::vector<std::string> fam_ids;
-    const size_t numInds = count_fam(opt.bedFile + ".fam", &fam_ids);
-    const size_t numSnps = count_bim(opt.bedFile + ".bim");
+    // without --bfile (the sparse route, src/main.cpp:96-118) N and M are the options' and the files are read line by line
+    const bool haveBed = !opt.bedFile.empty();
+    if (!haveBed && opt.numberIndividuals == 0) fatal("FATAL  : opt.numberIndividuals is zero! Set it via --number-individuals in call.");
+    if (!haveBed && opt.numberMarkers == 0) fatal("FATAL  : opt.numberMarkers is zero! Set it via --number-markers in call.");
+    const size_t numInds = haveBed ? count_fam(opt.bedFile + ".fam", nullptr) : opt.numberIndividuals;
+    const size_t numSnps = haveBed ? count_bim(opt.bedFile + ".bim") : opt.numberMarkers;
     std::vector<double> y, covX;
     std::vector<int32_t> fail;
     std::vector<uint8_t> keep;
@@ -852,6 +1126,10 @@ int run_bayesw(const Options& opt_in, int rank, int nranks, int local_rank)
     if (Mtot > numSnps) fatal("FATAL  : --number-markers exceeds the .bim file");
     const unsigned Ntot = (unsigned)numInds - numNAs;
     std::printf("INFO   : Full dataset includes Mtot=%d markers and Ntot=%d individuals.\n", Mtot, (int)numInds);
+    if (use_sparse(opt)) {
+        open_sparse(opt, numInds, Mtot);
+        sparse_info(opt, rank, nranks);
+    }
 
     std::vector<int32_t> groups;
     std::vector<std::vector<double>> mS;
@@ -887,15 +1165,14 @@ int run_bayesw(const Options& opt_in, int rank, int nranks, int local_rank)
     if (nranks > 1) setup_ranks(dev, base, rank, nranks);
     if (opt.batch) hg_check(hgibbs_set_option(dev, "batch", opt.batch), "batch");
     const double tl0 = now_s();
-    const size_t snpLenByt = (numInds + 3) / 4;
     // individuals sharded in multiples of 4 of the KEPT rows
     const unsigned per = ((Ntot + nranks - 1) / nranks + 3) / 4 * 4;
     const unsigned lo = std::min(Ntot, rank * per), hi = std::min(Ntot, (rank + 1) * per);
     {
-        const std::vector<uint8_t> bed = read_bed(opt.bedFile, numInds, Mtot);
-        hg_check(hgibbs_load_bed(dev, bed.data(), snpLenByt, (uint32_t)numInds, Mtot, numNAs ? keep.data() : nullptr, lo, hi, Ntot), "hgibbs_load_bed");
-        std::printf("INFO   : rank %3d took %.3f seconds to load  %lu bytes  =>  BW = %7.3f GB/s\n", rank, now_s() - tl0, (unsigned long)bed.size(),
-                    (double)bed.size() * 1e-9 / (now_s() - tl0));
+        std::vector<uint8_t> bed = read_training(opt.bedFile, numInds, Mtot);
+        const size_t bytes = put_genotypes(dev, bed, numInds, Mtot, numNAs ? keep.data() : nullptr, lo, hi, Ntot);
+        std::printf("INFO   : rank %3d took %.3f seconds to load  %lu bytes  =>  BW = %7.3f GB/s\n", rank, now_s() - tl0, (unsigned long)bytes,
+                    (double)bytes * 1e-9 / (now_s() - tl0));
     }
     if (numNAs) std::printf("INFO   : Ntot adjusted by -%d to account for NAs in phenotype file. Now Ntot=%d\n", numNAs, Ntot);
 
@@ -1147,14 +1424,13 @@ struct Cohort {
     int local_rank;
 };
 
-// A handle on the chain's rows, as one shard, from the training genotypes (read_bed of --bfile); the host copy is released
+// A handle on the chain's rows, as one shard, from the training genotypes (read_training: --bfile's .bed, or the sparse files); the
+// host copy is released
 hgibbs_t open_training(const Cohort& co, std::vector<uint8_t>& bed)
 {
     hgibbs_t dev = nullptr;
     hg_check(hgibbs_create(co.local_rank, &dev), "hgibbs_create");
-    hg_check(hgibbs_load_bed(dev, bed.data(), (co.numInds + 3) / 4, co.numInds, co.Mtot, co.numNAs ? co.keep.data() : nullptr, 0, co.Ntot, co.Ntot),
-             "hgibbs_load_bed");
-    std::vector<uint8_t>().swap(bed);
+    (void)put_genotypes(dev, bed, co.numInds, co.Mtot, co.numNAs ? co.keep.data() : nullptr, 0, co.Ntot, co.Ntot);
     return dev;
 }
 
@@ -1219,7 +1495,7 @@ int run_predict(const Options& opt, const Cohort& co)
     // the chain's standardisation: mave, mstd of the training markers over the rows that kept their phenotype
     std::vector<double> mave(co.Mtot), mstd(co.Mtot);
     {
-        std::vector<uint8_t> bed = read_bed(opt.bedFile, co.numInds, co.Mtot);
+        std::vector<uint8_t> bed = read_training(opt.bedFile, co.numInds, co.Mtot);
         hgibbs_t dev = open_training(co, bed);
         hg_check(hgibbs_marker_stats(dev, mave.data(), mstd.data(), nullptr, nullptr, nullptr), "hgibbs_marker_stats");
         hgibbs_destroy(dev);
@@ -1297,7 +1573,7 @@ int run_ld(const Options& opt, const Cohort& co)
                 opt.ldBin ? (" and " + out + ".bin").c_str() : "");
     std::fflush(stdout);
 
-    std::vector<uint8_t> bed = read_bed(opt.bedFile, co.numInds, co.Mtot);
+    std::vector<uint8_t> bed = read_training(opt.bedFile, co.numInds, co.Mtot);
     if (opt.ldOut.empty()) make_out_dir(opt);
     FILE* f = open_out(out, "w");
     FILE* fb = nullptr;
@@ -1464,7 +1740,7 @@ int run_assoc(const Options& opt, const Cohort& co, const std::vector<double>& y
     const std::vector<double>&Z = proj.Z, &L = proj.L;
     auto project = [&](std::vector<double>& v) { proj.project(v); };
 
-    std::vector<uint8_t> bed = read_bed(opt.bedFile, co.numInds, co.Mtot);
+    std::vector<uint8_t> bed = read_training(opt.bedFile, co.numInds, co.Mtot);
     if (opt.assocOut.empty()) make_out_dir(opt);
     FILE* f = open_out(out, "w");
     std::fprintf(f, "CHR SNP BP A1 A2 FREQ N BETA SE CHISQ P\n");
@@ -1561,7 +1837,7 @@ int run_king(const Options& opt, const Cohort& co)
     const FamIds fam = read_fam_ids(opt.bedFile + ".fam", co.numInds, co.numNAs ? &co.keep : nullptr);
     const unsigned Ntot = co.Ntot;
     if (fam.fid.size() != Ntot) fatal("FATAL  : " + opt.bedFile + ".fam: " + std::to_string(fam.fid.size()) + " kept rows, expected " + std::to_string(Ntot));
-    std::vector<uint8_t> bed = read_bed(opt.bedFile, co.numInds, co.Mtot);
+    std::vector<uint8_t> bed = read_training(opt.bedFile, co.numInds, co.Mtot);
     if (opt.kingOut.empty()) make_out_dir(opt);
     FILE* f = open_out(out, "w");
     std::fprintf(f, "#FID1\tIID1\tFID2\tIID2\tNSNP\tHETHET\tIBS0\tKINSHIP\n");
@@ -1607,7 +1883,7 @@ int run_pca(const Options& opt, const Cohort& co)
     const FamIds fam = read_fam_ids(opt.bedFile + ".fam", co.numInds, nullptr);
     if (fam.fid.size() != co.numInds) fatal("FATAL  : " + opt.bedFile + ".fam: " + std::to_string(fam.fid.size()) + " rows, expected " + std::to_string(co.numInds));
     const unsigned Ntot = co.Ntot;
-    std::vector<uint8_t> bed = read_bed(opt.bedFile, co.numInds, co.Mtot);
+    std::vector<uint8_t> bed = read_training(opt.bedFile, co.numInds, co.Mtot);
     if (opt.pcaOut.empty()) make_out_dir(opt);
     FILE* f = open_out(vec, "w");
     std::fprintf(f, "#FID\tIID");
@@ -1815,7 +2091,7 @@ int run_pve(const Options& opt, const Cohort& co)
     idx.reserve(off[R]);
     for (const auto& r : ps.idx) idx.insert(idx.end(), r.begin(), r.end());
 
-    std::vector<uint8_t> bed = read_bed(opt.bedFile, co.numInds, M);
+    std::vector<uint8_t> bed = read_training(opt.bedFile, co.numInds, M);
     if (opt.pveOut.empty()) make_out_dir(opt);
     FILE* f = open_out(out, "w");
     std::fprintf(f, "SET CHR BP_FIRST BP_LAST NSNP PIP PVE_MEAN PVE_SD SHARE_MEAN SHARE_SD WPPA\n");
@@ -1919,7 +2195,7 @@ int run_grm(const Options& opt, const Cohort& co)
     const FamIds fam = read_fam_ids(opt.bedFile + ".fam", co.numInds, co.numNAs ? &co.keep : nullptr);
     const unsigned N = co.Ntot;
     if (fam.fid.size() != N) fatal("FATAL  : " + opt.bedFile + ".fam: " + std::to_string(fam.fid.size()) + " kept rows, expected " + std::to_string(N));
-    std::vector<uint8_t> bed = read_bed(opt.bedFile, co.numInds, co.Mtot);
+    std::vector<uint8_t> bed = read_training(opt.bedFile, co.numInds, co.Mtot);
     if (opt.grmOut.empty()) make_out_dir(opt);
     const std::string idp = prefix + ".grm.id", binp = prefix + ".grm.bin", nbinp = prefix + ".grm.N.bin", spp = prefix + ".grm.sp";
     FILE* fid = open_out(idp, "w");
@@ -2065,7 +2341,7 @@ int run_ldscore(const Options& opt, const Cohort& co)
     std::fflush(stdout);
     if (!opt.ldScoreRaw && co.Ntot < 3) fatal("FATAL  : --ld-score: the adjusted r^2 - (1 - r^2) / (N - 2) needs at least three individuals (--ld-score-raw takes fewer)");
 
-    std::vector<uint8_t> bed = read_bed(opt.bedFile, co.numInds, M);
+    std::vector<uint8_t> bed = read_training(opt.bedFile, co.numInds, M);
     if (opt.ldScoreOut.empty()) make_out_dir(opt);
     FILE* f = open_out(l2p, "w");
     FILE* fm = open_out(mp, "w");
@@ -2223,7 +2499,7 @@ int run_ldselect(const Options& opt, const Cohort& co, bool clump)
     }
     std::fflush(stdout);
 
-    std::vector<uint8_t> bed = read_bed(opt.bedFile, co.numInds, M);
+    std::vector<uint8_t> bed = read_training(opt.bedFile, co.numInds, M);
     if (clump ? opt.clumpOut.empty() : opt.ldPruneOut.empty()) make_out_dir(opt);
     FILE* f = open_out(out, "w");
     FILE* fo = clump ? nullptr : open_out(outOut, "w");
@@ -2332,7 +2608,7 @@ int run_he(const Options& opt, const Cohort& co, const std::vector<double>& y_ra
         CovProjector("--he", covX, C, N).project(y);
         scale_phenotype(y, N);
     }
-    std::vector<uint8_t> bed = read_bed(opt.bedFile, co.numInds, co.Mtot);
+    std::vector<uint8_t> bed = read_training(opt.bedFile, co.numInds, co.Mtot);
     if (opt.heOut.empty()) make_out_dir(opt);
     FILE* f = open_out(out, "w");
     FILE* fr = opt.heRows ? open_out(rowsp, "w") : nullptr;
@@ -2412,7 +2688,7 @@ int run_qc(const Options& opt, const Cohort& co)
     if (fam.fid.size() != N) fatal("FATAL  : " + opt.bedFile + ".fam: " + std::to_string(fam.fid.size()) + " kept rows, expected " + std::to_string(N));
     const BimRows bim = read_bim(opt.bedFile + ".bim", M);
     if (bim.id.size() != M) fatal("FATAL  : " + opt.bedFile + ".bim: " + std::to_string(bim.id.size()) + " rows, expected " + std::to_string(M));
-    std::vector<uint8_t> bed = read_bed(opt.bedFile, co.numInds, M);
+    std::vector<uint8_t> bed = read_training(opt.bedFile, co.numInds, M);
     if (opt.qcOut.empty()) make_out_dir(opt);
     const char* const ext[6] = {".frq", ".lmiss", ".hwe", ".imiss", ".het", ".ibc"};
     const char* const head[6] = {"CHR\tSNP\tA1\tA2\tMAF\tNCHROBS\n",        "CHR\tSNP\tN_MISS\tN_GENO\tF_MISS\n", "CHR\tSNP\tTEST\tA1\tA2\tGENO\tO(HET)\tE(HET)\tP\n",
@@ -2720,6 +2996,8 @@ void check_modes(const Options& opt, int nranks)
             continue;
         }
         if (opt.bayesType == "bayesWMPI") fatal("FATAL  : " + flag + " " + m.wmpi);
+        if (opt.bedFile.empty())
+            fatal("FATAL  : " + flag + " needs --bfile: its .fam and .bim name the rows and the markers (the genotypes may still come from --sparse-dir/--sparse-basename)");
         for (int j = 0; j < i; ++j)
             if (modes[j].given) fatal("FATAL  : " + flag + " cannot be combined with " + modes[j].flag);
         if (opt.restart) fatal("FATAL  : " + flag + " does not sample: it cannot be combined with --restart");
@@ -2745,34 +3023,40 @@ int main(int argc, const char* argv[])
         return 1;
     }
     Options opt = parse(argc, argv);
+    const char* e;
+    const int rank = (e = std::getenv("RANK")) ? std::atoi(e) : 0;
+    const int nranks = (e = std::getenv("WORLD_SIZE")) ? std::atoi(e) : 1;
+    const int local_rank = (e = std::getenv("LOCAL_RANK")) ? std::atoi(e) : rank;
+    if (opt.bedToSparse) return run_bed_to_sparse(opt, nranks, local_rank); // main.cpp:47-55: samples nothing, needs no --mpibayes
     if (!((opt.bayesType == "bayesMPI" || opt.bayesType == "bayesWMPI") && opt.analysisType == "RAM")) {
         std::cerr << "\n Error: Wrong analysis requested: " << opt.analysisType << " + " << opt.bayesType
                   << " (this build reproduces --mpibayes bayesMPI and bayesWMPI)" << std::endl;
         return 0; // the reference catches the throw and still returns 0 (main.cpp:179-189)
     }
-    if (!opt.readFromBedFile) fatal("FATAL: either go for BED, SPARSE or BOTH (this build reads --bfile)");
+    const bool haveBed = !opt.bedFile.empty();
+    if (!haveBed && !use_sparse(opt)) fatal("FATAL: either go for BED, SPARSE or BOTH (give --bfile, or --sparse-dir with --sparse-basename)");
     if ((opt.groupIndexFile.empty()) != (opt.groupMixtureFile.empty()))
         fatal("FATAL   : you need to activate both --groupIndexFile and --groupMixtureFile");
     if (opt.syncRate > 1)
         std::printf("WARNING: --sync-rate %d ignored: individuals are sharded, every marker sees the current residual\n", opt.syncRate);
 
-    const char* e;
-    const int rank = (e = std::getenv("RANK")) ? std::atoi(e) : 0;
-    const int nranks = (e = std::getenv("WORLD_SIZE")) ? std::atoi(e) : 1;
-    const int local_rank = (e = std::getenv("LOCAL_RANK")) ? std::atoi(e) : rank;
     check_modes(opt, nranks);
     if (opt.bayesType == "bayesWMPI") return run_bayesw(opt, rank, nranks, local_rank); // main.cpp:164-167
 
     // ---- inputs (main.cpp:69-70,88; BayesRRm.cpp:969-997) -------------------
+    // without --bfile (the sparse route, main.cpp:96-118) N and M are the options' and the phenotype file is read line by line
+    if (!haveBed && opt.numberIndividuals == 0) fatal("FATAL  : opt.numberIndividuals is zero! Set it via --number-individuals in call.");
+    if (!haveBed && opt.numberMarkers == 0) fatal("FATAL  : opt.numberMarkers is zero! Set it via --number-markers in call.");
     std::vector<std::string> fam_ids;
-    const size_t numInds = count_fam(opt.bedFile + ".fam", &fam_ids);
-    const size_t numSnps = count_bim(opt.bedFile + ".bim");
+    const size_t numInds = haveBed ? count_fam(opt.bedFile + ".fam", &fam_ids) : opt.numberIndividuals;
+    const size_t numSnps = haveBed ? count_bim(opt.bedFile + ".bim") : opt.numberMarkers;
     std::vector<double> y;
     std::vector<uint8_t> keep;
     std::vector<double> covX;
     int C = 0;
     if (opt.covariates) read_phen_cov(opt.phenotypeFile, opt.covariatesFile, numInds, y, keep, covX, C); // main.cpp:80-83
-    else read_phen(opt.phenotypeFile, fam_ids, y, keep);
+    else if (haveBed) read_phen(opt.phenotypeFile, fam_ids, y, keep);
+    else read_phen_lines(opt.phenotypeFile, numInds, y, keep);
     const unsigned numNAs = (unsigned)(numInds - y.size());
 
     if (opt.numberIndividuals == 0) fatal("FATAL  : opt.numberIndividuals is zero! Set it via --number-individuals in call.");
@@ -2787,6 +3071,10 @@ int main(int argc, const char* argv[])
             std::printf("WARNING: opt.numberIndividuals set to %zu but will be adjusted to %zu - %u = %u due to NAs in phenotype file.\n",
                         numInds, numInds, numNAs, Ntot);
         std::printf("INFO   : Full dataset includes Mtot=%d markers and Ntot=%d individuals.\n", Mtot, (int)numInds);
+    }
+    if (use_sparse(opt)) {
+        open_sparse(opt, numInds, Mtot);
+        sparse_info(opt, rank, nranks);
     }
     const Cohort co{keep, (unsigned)numInds, numNAs, Ntot, Mtot, local_rank};
     if (!opt.predictBfile.empty()) return run_predict(opt, co);
@@ -2845,16 +3133,13 @@ int main(int argc, const char* argv[])
 
     // ---- genotypes: Data::load_data_from_bed_file, data.cpp:671-739 -----------
     const double tl0 = now_s();
-    const size_t snpLenByt = (numInds + 3) / 4;
-    std::vector<uint8_t> bed = read_bed(opt.bedFile, numInds, Mtot);
+    std::vector<uint8_t> bed = read_training(opt.bedFile, numInds, Mtot);
     // individuals sharded in multiples of 4 of the KEPT rows
     const unsigned per = ((Ntot + nranks - 1) / nranks + 3) / 4 * 4;
     const unsigned lo = std::min(Ntot, rank * per), hi = std::min(Ntot, (rank + 1) * per);
-    hg_check(hgibbs_load_bed(dev, bed.data(), snpLenByt, (uint32_t)numInds, Mtot, numNAs ? keep.data() : nullptr, lo, hi, Ntot),
-             "hgibbs_load_bed");
+    const size_t loaded = put_genotypes(dev, bed, numInds, Mtot, numNAs ? keep.data() : nullptr, lo, hi, Ntot);
     std::printf("INFO   : rank %3d took %.3f seconds to load  %lu bytes  =>  BW = %7.3f GB/s\n", rank, now_s() - tl0,
-                (unsigned long)bed.size(), (double)bed.size() * 1e-9 / (now_s() - tl0));
-    std::vector<uint8_t>().swap(bed);
+                (unsigned long)loaded, (double)loaded * 1e-9 / (now_s() - tl0));
 
     hydra_model_desc md{};
     md.seed = opt.seed + (unsigned)0 * 1000; // every rank replicates rank 0's stream (BayesRRm.cpp:1228 with rank = 0)

@@ -91,6 +91,45 @@ int hgibbs_dims(hgibbs_t h, uint32_t* n_global, uint32_t* n_local, uint32_t* M, 
 /* Copy packed columns [m0, m0+mcount) of this rank's shard back (tests). */
 int hgibbs_get_bed(hgibbs_t h, uint32_t m0, uint32_t mcount, uint8_t* out_host, uint64_t out_stride);
 
+/* ---- hydra's sparse representation: replaces Data::load_data_from_sparse_files and the writers behind --bed-to-sparse
+ * (layout: src/BayesRRm.cpp:437-770, src/data.cpp:1072-1106, 1224-1290) --------------------------------------------
+ * Per marker three lists of 0-based row indices of the file: the rows with genotype 1, with genotype 2, with a missing call
+ * (genotype 0 is stored nowhere).  A list of `count` markers is given as the files hold it: start[k] is the ABSOLUTE position of
+ * marker k's first entry in the index file (.ss?), len[k] its entries (.sl?), and idx the piece of the index file (.si?) that starts
+ * at absolute position idx_base and holds idx_count entries. */
+typedef struct {
+    const uint64_t* start;
+    const uint64_t* len;
+    const uint32_t* idx;
+    uint64_t idx_base, idx_count;
+} hgibbs_sparse_list;
+/* Loading: begin, then put in slabs of markers (any cut, any order, each marker once), then end.
+ * begin takes hgibbs_load_bed's arguments after the BED pointer, with their meaning and refusals, allocates as it does and fills the
+ * image with genotype 0 (padding slots: missing).  Until end succeeds the image is not on the handle: every other call sees a handle
+ * without genotypes.
+ * put scatters the slab's entries on the device: an entry whose row keep_host drops or that lies outside [row_begin, row_end) is
+ * skipped; the order of entries within a list is free.  Refused with a message that names the marker, the row and the fact: a row
+ * listed twice for a marker (in one list or in two), an index >= n_total (the smallest such marker and row of the call); and before
+ * any device work: a null list, m0 + count > M, a marker put already, start[k] < idx_base, start[k] + len[k] > idx_base + idx_count,
+ * len[k] > n_total.  A refused put abandons the load: the handle is as it was before begin.
+ * end refuses unless every marker was put; it then publishes the image.  hgibbs_get_bed then returns byte for byte what it returns
+ * after hgibbs_load_bed of the equivalent BED with the same keep_host, rows and n_global. */
+int hgibbs_sparse_begin(hgibbs_t h, uint32_t n_total, uint32_t M, const uint8_t* keep_host, uint32_t row_begin, uint32_t row_end,
+                        uint32_t n_global);
+int hgibbs_sparse_put(hgibbs_t h, uint32_t m0, uint32_t count, const hgibbs_sparse_list* ones, const hgibbs_sparse_list* twos,
+                      const hgibbs_sparse_list* miss);
+int hgibbs_sparse_end(hgibbs_t h);
+/* Writing, on one rank (several are refused): counts gives, for markers [m0, m0 + count), the lengths of the three lists over the
+ * handle's rows; get writes for each marker in turn the ascending local row indices of genotype 1 into idx1, of genotype 2 into idx2,
+ * of missing calls into idxm, each concatenated over the markers and sized by the caller from counts.  Any pointer may be NULL (that
+ * output is skipped).  Padding slots are never listed.  The lists are bit-identical for any cut of the markers, any value of the
+ * option sparse_piece and any repeat; put back through begin / put / end with keep_host = NULL they reproduce the image. */
+int hgibbs_sparse_counts(hgibbs_t h, uint32_t m0, uint32_t count, uint64_t* n1, uint64_t* n2, uint64_t* nm);
+int hgibbs_sparse_get(hgibbs_t h, uint32_t m0, uint32_t count, uint32_t* idx1, uint32_t* idx2, uint32_t* idxm);
+/* device time in ms of every kernel of the last load (begin .. end, summed; 0 after a refused call) and of the compaction kernels of
+ * the last hgibbs_sparse_get (0 after a refused call); host copies are not included.  Either pointer may be NULL. */
+int hgibbs_last_sparse_ms(hgibbs_t h, double* put_ms, double* get_ms);
+
 /* a2: per-marker counts and mave/mstd (src/BayesRRm.cpp:1502-1508), counts
  * summed over ranks.  Any output pointer may be NULL. */
 int hgibbs_marker_stats(hgibbs_t h, double* mave_host, double* mstd_host, uint64_t* n1_host, uint64_t* n2_host,
@@ -185,6 +224,8 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
  *   ldmask_piece    hgibbs_ld_mask: band rows per piece, 0..2^20 (0 = automatic; rounded up to a multiple of 16)
  *   grm_piece       hgibbs_grm, hgibbs_grm_rowsums: pairs per piece of rows, 0..2^25 (0 = automatic: 2^25; a row alone may exceed it)
  *   rowsums_ranges  hgibbs_row_sums: at most this many ranges of markers split over workgroups, 0..65535 (0 = automatic)
+ *   sparse_piece    hgibbs_sparse_get: bytes of index buffers per piece of markers (0 = automatic: a quarter of the free device memory,
+ *                   at most 1 GiB; a marker alone may exceed it)
  *   p2p, force_split, chunk, debug_timing, w_kernel_timing   transport selection and diagnostics */
 int hgibbs_set_option(hgibbs_t h, const char* name, int64_t value);
 /* Statistics of the last sweep: launches, markers per launch, device time of
