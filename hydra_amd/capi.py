@@ -24,7 +24,8 @@ ABI_SYMBOLS = [
     "hydra_chain_last_nnz", "hgibbs_score", "hgibbs_last_score_ms", "hgibbs_ld", "hgibbs_last_ld_ms",
     "hgibbs_ld_scores", "hgibbs_last_ld_scores_ms",
     "hgibbs_ld_mask", "hgibbs_last_ld_mask_ms", "hgibbs_ld_greedy", "hgibbs_ld_clump",
-    "hgibbs_marker_dots", "hgibbs_last_marker_dots_ms", "hgibbs_king", "hgibbs_king_pairs", "hgibbs_king_pairs_get", "hgibbs_last_king_ms",
+    "hgibbs_marker_dots", "hgibbs_last_marker_dots_ms", "hgibbs_marker_class_sums", "hgibbs_last_marker_class_sums_ms", "hgibbs_logit_null",
+    "hgibbs_king", "hgibbs_king_pairs", "hgibbs_king_pairs_get", "hgibbs_last_king_ms",
     "hgibbs_pca", "hgibbs_last_pca_ms", "hgibbs_region_var", "hgibbs_last_region_var_ms",
     "hgibbs_grm", "hgibbs_grm_info", "hgibbs_last_grm_ms",
     "hgibbs_grm_rowsums", "hgibbs_last_grm_rowsums_ms", "hgibbs_he_fit",
@@ -222,6 +223,9 @@ def lib():
     L.hgibbs_ld_clump.argtypes = [vp, C.c_uint32, u32p, C.c_double, u32p, C.c_uint32, u8p, ip, u64p]
     L.hgibbs_marker_dots.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_int, dp, dp, dp]
     L.hgibbs_last_marker_dots_ms.argtypes = [vp, dp]
+    L.hgibbs_marker_class_sums.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_int, dp, dp]
+    L.hgibbs_last_marker_class_sums_ms.argtypes = [vp, dp]
+    L.hgibbs_logit_null.argtypes = [C.c_uint32, C.c_int, dp, dp, dp, dp, dp, dp, C.POINTER(C.c_int)]
     L.hgibbs_king.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32)]
     L.hgibbs_king_pairs.argtypes = [vp, C.c_double, C.POINTER(C.c_uint64)]
     L.hgibbs_king_pairs_get.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), dp]
@@ -326,6 +330,23 @@ def hwe_exact(n_het, n_hom_a, n_hom_b):
     p = C.c_double()
     check(lib().hgibbs_hwe_exact(int(n_het), int(n_hom_a), int(n_hom_b), C.byref(p)))
     return p.value
+
+
+def logit_null(Z, y):
+    """hgibbs_logit_null (host only): the maximum-likelihood logistic fit of y in {0, 1} on the columns of Z (n, q), first column ones.
+    Returns a dict: coef (q,), mu (n,), w = mu (1 - mu) (n,), chol (q, q) the lower Cholesky factor of Z'WZ, iters."""
+    Z = np.asarray(Z, dtype=np.float64)
+    if Z.ndim != 2:
+        raise ValueError("logit_null: Z must be (n, q)")
+    n, q = Z.shape
+    y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+    if y.size != n:
+        raise ValueError("logit_null: y must have Z's %d rows" % n)
+    Zc = np.ascontiguousarray(Z.T)  # column-major
+    coef, mu, w, chol = np.zeros(max(q, 1)), np.zeros(max(n, 1)), np.zeros(max(n, 1)), np.zeros((max(q, 1), max(q, 1)))
+    it = C.c_int(0)
+    check(lib().hgibbs_logit_null(n, q, _dp(Zc), _dp(y), _dp(coef), _dp(mu), _dp(w), _dp(chol), C.byref(it)))
+    return {"coef": coef[:q], "mu": mu[:n], "w": w[:n], "chol": np.ascontiguousarray(chol[:q, :q].T), "iters": it.value}
 
 
 class Device:
@@ -688,6 +709,24 @@ class Device:
     def last_marker_dots_ms(self):
         v = C.c_double()
         check(self.L.hgibbs_last_marker_dots_ms(self.h, C.byref(v)))
+        return v.value
+
+    def marker_class_sums(self, U, m0=0, count=None):
+        """Sums of the rows u_k of U (K, n_local) over the individuals of each genotype code, for markers j in [m0, m0 + count)
+        (hgibbs_marker_class_sums): out (count, K, 4), codes 0, 1, 2 copies of A1 and 3 a missing call, each rounded once."""
+        U = np.ascontiguousarray(np.atleast_2d(U), dtype=np.float64)
+        if U.shape[1] != self.n_local:
+            raise ValueError("U must be (K, %d)" % self.n_local)
+        if count is None:
+            count = self.M - m0
+        K = U.shape[0]
+        out = np.zeros((count, K, 4))
+        check(self.L.hgibbs_marker_class_sums(self.h, m0, count, K, _dp(U), _dp(out)))
+        return out
+
+    def last_marker_class_sums_ms(self):
+        v = C.c_double()
+        check(self.L.hgibbs_last_marker_class_sums_ms(self.h, C.byref(v)))
         return v.value
 
     def king(self, a0=0, acount=None, b0=0, bcount=None):

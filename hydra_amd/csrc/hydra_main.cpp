@@ -24,7 +24,10 @@
 // `--assoc [--assoc-no-loco] [--assoc-out F]` appended to a bayesMPI command line samples nothing either: it tests every marker for
 // association on the chain's rows, against the scaled phenotype minus the chain's genetic value from the other chromosomes (LOCO
 // offsets from the .bet records at or after --burn-in; none with --assoc-no-loco), with the covariates projected out, through
-// hgibbs_score and hgibbs_marker_dots (run_assoc), and writes <dir>/<name>.assoc (or F).
+// hgibbs_score and hgibbs_marker_dots (run_assoc), and writes <dir>/<name>.assoc (or F).  With --assoc-logistic
+// the phenotype is case/control and the table is the logistic score test: a null model per chromosome on [1 | covariates | G - G_c]
+// (hgibbs_logit_null) and the sums of its vectors over the rows of each genotype through hgibbs_marker_class_sums
+// (run_assoc_logistic), written to <dir>/<name>.assoc.logistic (or F).
 //
 // `--king [--king-cutoff T] [--king-out F]` appended to a bayesMPI command line samples nothing either: it computes the KING-robust
 // kinship of every pair of the chain's rows with hgibbs_king_pairs (run_king) and writes the pairs with
@@ -133,6 +136,7 @@ struct Options { // src/options.hpp:20-138 (subset that reaches bayesMPI)
     std::string ldOut;                               // --ld-out
     bool assoc = false, assocNoLoco = false;         // --assoc: per-marker association tests; --assoc-no-loco: without LOCO offsets
     std::string assocOut;                            // --assoc-out
+    bool assocLogistic = false;                      // --assoc-logistic: the logistic score test of a case/control phenotype
     bool king = false, kingCutoffGiven = false;      // --king: KING-robust kinship of the chain's rows; --king-cutoff given
     std::string kingCutoff = "0.0442", kingOut;      // --king-cutoff T (checked before the device), --king-out
     bool pca = false, pcaLoadings = false, pcaItersGiven = false, pcaTolGiven = false, pcaOutGiven = false; // --pca K; which --pca-* were given
@@ -287,6 +291,7 @@ Options parse(int argc, const char* argv[])
         else if (a == "--assoc") o.assoc = true;
         else if (a == "--assoc-no-loco") o.assocNoLoco = true;
         else if (a == "--assoc-out") o.assocOut = need(i);
+        else if (a == "--assoc-logistic") o.assocLogistic = true;
         else if (a == "--king") o.king = true;
         else if (a == "--king-cutoff") {
             o.kingCutoff = need(i);
@@ -1702,6 +1707,46 @@ struct CovProjector {
     }
 };
 
+// maximal runs of equal chromosome in .bim order (an unsorted .bim works); chromosome c(j) as an index
+struct ChromRuns {
+    std::vector<int> cj;
+    std::vector<unsigned> runs; // first marker of each run, then Mtot
+    size_t nruns = 0, nchrom = 0;
+    ChromRuns(const BimRows& bim, unsigned Mtot) : cj(Mtot)
+    {
+        std::map<std::string, int> chrom_idx;
+        for (unsigned j = 0; j < Mtot; ++j) {
+            cj[j] = chrom_idx.emplace(bim.chr[j], (int)chrom_idx.size()).first->second;
+            if (j == 0 || bim.chr[j] != bim.chr[j - 1]) runs.push_back(j);
+        }
+        nruns = runs.size();
+        nchrom = chrom_idx.size();
+        runs.push_back(Mtot);
+    }
+};
+
+// Gc[i * nchrom + c]: the chain's genetic value of row i from chromosome c, the mean effects of the .bet records through hgibbs_score
+// with one "sample" per chromosome; the device time is added to ms
+std::vector<double> loco_genetic_values(hgibbs_t dev, const std::vector<double>& betas, size_t S, unsigned Mtot, unsigned N, const std::vector<int>& cj,
+                                        size_t nchrom, const std::vector<double>& mave, const std::vector<double>& mstd, double& ms)
+{
+    std::vector<double> bbar(Mtot, 0.0);
+    for (size_t s = 0; s < S; ++s)
+        for (unsigned j = 0; j < Mtot; ++j) bbar[j] += betas[s * Mtot + j];
+    for (unsigned j = 0; j < Mtot; ++j) bbar[j] /= (double)S;
+    std::vector<double> a(nchrom * Mtot, 0.0), o(nchrom * Mtot, 0.0), Gc((size_t)N * nchrom);
+    for (unsigned j = 0; j < Mtot; ++j) {
+        if (!std::isfinite(mstd[j])) continue; // (score refuses non-finite weights; x = 0 there anyway)
+        a[(size_t)cj[j] * Mtot + j] = bbar[j] * mstd[j];
+        o[(size_t)cj[j] * Mtot + j] = -bbar[j] * mstd[j] * mave[j];
+    }
+    hg_check(hgibbs_score(dev, (int)nchrom, a.data(), o.data(), Gc.data()), "hgibbs_score");
+    double t = 0.0;
+    hg_check(hgibbs_last_score_ms(dev, &t), "hgibbs_last_score_ms");
+    ms += t;
+    return Gc;
+}
+
 int run_assoc(const Options& opt, const Cohort& co, const std::vector<double>& y_raw, const std::vector<double>& covX, int C)
 {
     const std::string base = opt.mcmcOutDir + "/" + opt.mcmcOutNam;
@@ -1711,16 +1756,10 @@ int run_assoc(const Options& opt, const Cohort& co, const std::vector<double>& y
     const unsigned N = co.Ntot;
     const int q = 1 + C;
 
-    // maximal runs of equal chromosome in .bim order (an unsorted .bim works); chromosome c(j) as an index
-    std::map<std::string, int> chrom_idx;
-    std::vector<int> cj(co.Mtot);
-    std::vector<unsigned> runs; // first marker of each run, then Mtot
-    for (unsigned j = 0; j < co.Mtot; ++j) {
-        cj[j] = chrom_idx.emplace(bim.chr[j], (int)chrom_idx.size()).first->second;
-        if (j == 0 || bim.chr[j] != bim.chr[j - 1]) runs.push_back(j);
-    }
-    const size_t nruns = runs.size(), nchrom = chrom_idx.size();
-    runs.push_back(co.Mtot);
+    const ChromRuns cr(bim, co.Mtot);
+    const std::vector<int>& cj = cr.cj;
+    const std::vector<unsigned>& runs = cr.runs;
+    const size_t nruns = cr.nruns, nchrom = cr.nchrom;
     std::vector<unsigned> its;
     std::vector<double> betas;
     if (loco) read_bet_records(base + ".bet", co.Mtot, opt.burnin, its, betas, "--assoc takes its LOCO offsets from the chain's effects");
@@ -1755,21 +1794,7 @@ int run_assoc(const Options& opt, const Cohort& co, const std::vector<double>& y
     // r_c = y - (G - G_c), projected off Z: G_c from hgibbs_score with one "sample" per chromosome
     std::vector<std::vector<double>> r(loco ? nchrom : 1, y);
     if (loco) {
-        const size_t S = its.size();
-        std::vector<double> bbar(co.Mtot, 0.0);
-        for (size_t s = 0; s < S; ++s)
-            for (unsigned j = 0; j < co.Mtot; ++j) bbar[j] += betas[s * co.Mtot + j];
-        for (unsigned j = 0; j < co.Mtot; ++j) bbar[j] /= (double)S;
-        std::vector<double> a(nchrom * co.Mtot, 0.0), o(nchrom * co.Mtot, 0.0), Gc((size_t)N * nchrom);
-        for (unsigned j = 0; j < co.Mtot; ++j) {
-            if (!std::isfinite(mstd[j])) continue; // (score refuses non-finite weights; x = 0 there anyway)
-            a[(size_t)cj[j] * co.Mtot + j] = bbar[j] * mstd[j];
-            o[(size_t)cj[j] * co.Mtot + j] = -bbar[j] * mstd[j] * mave[j];
-        }
-        hg_check(hgibbs_score(dev, (int)nchrom, a.data(), o.data(), Gc.data()), "hgibbs_score");
-        double t = 0.0;
-        hg_check(hgibbs_last_score_ms(dev, &t), "hgibbs_last_score_ms");
-        ms += t;
+        const std::vector<double> Gc = loco_genetic_values(dev, betas, its.size(), co.Mtot, N, cj, nchrom, mave, mstd, ms);
         for (unsigned i = 0; i < N; ++i) {
             double G = 0.0;
             for (size_t c = 0; c < nchrom; ++c) G += Gc[(size_t)i * nchrom + c];
@@ -1824,6 +1849,153 @@ int run_assoc(const Options& opt, const Cohort& co, const std::vector<double>& y
     hgibbs_destroy(dev);
     close_out(f, out);
     std::printf("ASSOC  : wrote %llu rows to %s (%.3f ms on the device)\n", written, out.c_str(), ms);
+    return 0;
+}
+
+// ---- --assoc --assoc-logistic: the logistic score test of a case/control phenotype ----
+int run_assoc_logistic(const Options& opt, const Cohort& co, const std::vector<double>& y_raw, const std::vector<double>& covX, int C)
+{
+    const std::string base = opt.mcmcOutDir + "/" + opt.mcmcOutNam;
+    const std::string out = opt.assocOut.empty() ? base + ".assoc.logistic" : opt.assocOut;
+    const bool loco = !opt.assocNoLoco;
+    const BimRows bim = read_bim(opt.bedFile + ".bim", co.Mtot);
+    const unsigned N = co.Ntot;
+    const int q = 1 + C;
+
+    const ChromRuns cr(bim, co.Mtot);
+    const std::vector<int>& cj = cr.cj;
+    const std::vector<unsigned>& runs = cr.runs;
+    const size_t nruns = cr.nruns, nchrom = cr.nchrom;
+    std::vector<unsigned> its;
+    std::vector<double> betas;
+    if (loco) read_bet_records(base + ".bet", co.Mtot, opt.burnin, its, betas, "--assoc takes its LOCO offsets from the chain's effects");
+    std::printf("ASSOC  : %u markers, %zu chromosomes in %zu runs, %d covariates, %u individuals -> %s\n", co.Mtot, nchrom, nruns, C, N, out.c_str());
+    if (loco)
+        std::printf("ASSOC  : LOCO predictors from %zu records of %s (iterations %u .. %u)\n", its.size(), (base + ".bet").c_str(), its.front(), its.back());
+    else
+        std::printf("ASSOC  : no LOCO predictor (--assoc-no-loco): one null model of [1 | covariates] for every chromosome\n");
+    if (loco && nchrom == 1) std::printf("WARNING: --assoc with one chromosome: G - G_c is 0, no offset is taken out\n");
+    std::fflush(stdout);
+    if ((long long)N <= (long long)q + 1) fatal("FATAL  : --assoc needs more individuals (" + std::to_string(N) + ") than covariates + 2");
+    const CovProjector proj("--assoc", covX, C, N); // (Z = [1 | covariates], and the linear mode's refusal of dependent columns)
+
+    // the refusals of this mode, before any device call: the phenotype, the number of vectors, the null model of [1 | covariates]
+    std::vector<double> vals(y_raw.begin(), y_raw.begin() + N);
+    std::sort(vals.begin(), vals.end());
+    vals.erase(std::unique(vals.begin(), vals.end()), vals.end());
+    if (vals.size() != 2)
+        fatal("FATAL  : --assoc-logistic: the phenotype takes " + std::to_string(vals.size()) +
+              " distinct values on the kept rows, a case/control phenotype takes exactly two (the larger one is the case)");
+    const bool gcol = loco && nchrom > 1;  // the LOCO predictor G - G_c as a column of the null model
+    const int qn = q + (gcol ? 1 : 0);     // columns of the null model
+    const int K = 2 + qn;                  // y - mu, w z_1 .. w z_qn, the case indicator
+    if (K > 32)
+        fatal("FATAL  : --assoc-logistic: " + std::to_string(C) + " covariates make " + std::to_string(K) + " vectors (y - mu, one per column of the null model" +
+              (gcol ? " with the LOCO predictor" : "") + ", the case indicator), hgibbs_marker_class_sums takes at most 32");
+    std::vector<double> d(N);
+    unsigned ncase = 0;
+    for (unsigned i = 0; i < N; ++i) ncase += (d[i] = y_raw[i] == vals[1] ? 1.0 : 0.0) != 0.0;
+    struct Null {
+        std::vector<double> coef, mu, w, L;
+        int iters = 0;
+    };
+    std::vector<double> Zc((size_t)qn * N);
+    std::copy(proj.Z.begin(), proj.Z.end(), Zc.begin());
+    auto fit = [&](int cols, Null& f) {
+        f.coef.assign(cols, 0.0);
+        f.mu.assign(N, 0.0);
+        f.w.assign(N, 0.0);
+        f.L.assign((size_t)cols * cols, 0.0);
+        hg_check(hgibbs_logit_null(N, cols, Zc.data(), d.data(), f.coef.data(), f.mu.data(), f.w.data(), f.L.data(), &f.iters), "--assoc-logistic");
+    };
+    std::vector<Null> nulls(gcol ? nchrom : 1);
+    fit(q, nulls[0]); // (with a LOCO predictor this one only refuses early; the fits per chromosome follow)
+    int iters = gcol ? 0 : nulls[0].iters;
+
+    std::vector<uint8_t> bed = read_training(opt.bedFile, co.numInds, co.Mtot);
+    if (opt.assocOut.empty()) make_out_dir(opt);
+    FILE* f = open_out(out, "w");
+    std::fprintf(f, "CHR SNP BP A1 A2 FREQ N BETA SE CHISQ P N_CASE N_CTRL FREQ_CASE FREQ_CTRL\n");
+
+    // the chain's rows and standardisation
+    hgibbs_t dev = open_training(co, bed);
+    std::vector<double> mave(co.Mtot), mstd(co.Mtot);
+    std::vector<uint64_t> n1(co.Mtot), n2(co.Mtot), nmiss(co.Mtot);
+    hg_check(hgibbs_marker_stats(dev, mave.data(), mstd.data(), n1.data(), n2.data(), nmiss.data()), "hgibbs_marker_stats");
+    double ms = 0.0;
+
+    // one null model per chromosome on [1 | covariates | G - G_c]: the predictor is on the scaled phenotype's scale and gets a coefficient
+    std::vector<std::vector<double>> gc; // the last column per chromosome
+    if (gcol) {
+        const std::vector<double> Gc = loco_genetic_values(dev, betas, its.size(), co.Mtot, N, cj, nchrom, mave, mstd, ms);
+        gc.assign(nchrom, std::vector<double>(N));
+        for (unsigned i = 0; i < N; ++i) {
+            double G = 0.0;
+            for (size_t c = 0; c < nchrom; ++c) G += Gc[(size_t)i * nchrom + c];
+            for (size_t c = 0; c < nchrom; ++c) gc[c][i] = G - Gc[(size_t)i * nchrom + c];
+        }
+        for (size_t c = 0; c < nchrom; ++c) {
+            std::copy(gc[c].begin(), gc[c].end(), Zc.begin() + (size_t)q * N);
+            fit(qn, nulls[c]);
+            iters += nulls[c].iters;
+        }
+    }
+
+    // one hgibbs_marker_class_sums per run: U = [y - mu, w z_1 .. w z_qn, d]
+    std::vector<double> U((size_t)K * N), sums, t(qn), v(qn);
+    std::copy(d.begin(), d.end(), U.begin() + (size_t)(K - 1) * N);
+    unsigned long long written = 0;
+    for (size_t ru = 0; ru < nruns; ++ru) {
+        const unsigned m0 = runs[ru], cnt = runs[ru + 1] - runs[ru];
+        const Null& nm = nulls[gcol ? (size_t)cj[m0] : 0];
+        if (gcol) std::copy(gc[(size_t)cj[m0]].begin(), gc[(size_t)cj[m0]].end(), Zc.begin() + (size_t)q * N);
+        for (unsigned i = 0; i < N; ++i) {
+            U[i] = d[i] - nm.mu[i];
+            for (int a = 0; a < qn; ++a) U[(size_t)(1 + a) * N + i] = nm.w[i] * Zc[(size_t)a * N + i];
+        }
+        sums.resize((size_t)cnt * K * 4);
+        hg_check(hgibbs_marker_class_sums(dev, m0, cnt, K, U.data(), sums.data()), "hgibbs_marker_class_sums");
+        double tms = 0.0;
+        hg_check(hgibbs_last_marker_class_sums_ms(dev, &tms), "hgibbs_last_marker_class_sums_ms");
+        ms += tms;
+        for (unsigned jj = 0; jj < cnt; ++jj) {
+            const unsigned j = m0 + jj;
+            const double m = mave[j], sd = mstd[j];
+            const unsigned long long called = (unsigned long long)N - nmiss[j];
+            const double* S = &sums[(size_t)jj * K * 4];
+            auto xu = [&](int k) { return sd * (S[4 * k + 1] + 2.0 * S[4 * k + 2] - m * (S[4 * k] + S[4 * k + 1] + S[4 * k + 2])); }; // x_j'u_k
+            const double xwx = sd * sd * (m * m * S[4] + (1.0 - m) * (1.0 - m) * S[5] + (2.0 - m) * (2.0 - m) * S[6]);
+            double V = xwx;
+            for (int a = 0; a < qn; ++a) { // v = L^-1 t: t'(Z'WZ)^-1 t = v'v
+                double e = xu(1 + a);
+                for (int p = 0; p < a; ++p) e -= nm.L[(size_t)a + (size_t)qn * p] * v[p];
+                v[a] = e / nm.L[(size_t)a + (size_t)qn * a];
+                V -= v[a] * v[a];
+            }
+            std::fprintf(f, "%s %s %lld %s %s %.12g %llu ", bim.chr[j].c_str(), bim.id[j].c_str(), bim.bp[j], bim.a1[j].c_str(), bim.a2[j].c_str(),
+                         m / 2.0, called);
+            if (!std::isfinite(sd) || !(V > 1e-9 * xwx)) std::fprintf(f, "NA NA NA NA");
+            else {
+                const double Uj = xu(0), chisq = Uj * Uj / V;
+                std::fprintf(f, "%.12g %.12g %.12g %.12g", sd * Uj / V, sd / std::sqrt(V), chisq, std::erfc(std::sqrt(chisq / 2.0)));
+            }
+            // the sums of the case indicator are exact counts of the cases by genotype; the controls are the rest of the marker's stats
+            const double* Sd = S + 4 * (K - 1);
+            const double c1 = Sd[1], c2 = Sd[2], ca = Sd[0] + c1 + c2;
+            const double k1 = (double)n1[j] - c1, k2 = (double)n2[j] - c2, ka = (double)called - ca;
+            std::fprintf(f, " %.12g %.12g", ca, ka);
+            for (const double fr : {ca > 0.0 ? (c1 + 2.0 * c2) / (2.0 * ca) : -1.0, ka > 0.0 ? (k1 + 2.0 * k2) / (2.0 * ka) : -1.0}) {
+                if (fr < 0.0) std::fprintf(f, " NA");
+                else std::fprintf(f, " %.12g", fr);
+            }
+            std::fprintf(f, "\n");
+            ++written;
+        }
+    }
+    hgibbs_destroy(dev);
+    close_out(f, out);
+    std::printf("ASSOC  : wrote %llu rows to %s (%u cases, %u controls, %d iterations of %zu null models, %.3f ms on the device)\n", written, out.c_str(),
+                ncase, N - ncase, iters, nulls.size(), ms);
     return 0;
 }
 
@@ -2966,7 +3138,7 @@ void check_modes(const Options& opt, int nranks)
          first_given({{"--predict-dry-run", opt.predictDryRun}, {"--predict-out", !opt.predictOut.empty()}})},
         {"--ld-window", opt.ldGiven, takes,
          first_given({{"--ld-out", !opt.ldOut.empty()}, {"--ld-window-kb", opt.ldKbGiven}, {"--ld-window-r2", opt.ldR2Given}, {"--ld-bin", opt.ldBin}})},
-        {"--assoc", opt.assoc, takes, first_given({{"--assoc-out", !opt.assocOut.empty()}, {"--assoc-no-loco", opt.assocNoLoco}})},
+        {"--assoc", opt.assoc, takes, first_given({{"--assoc-out", !opt.assocOut.empty()}, {"--assoc-no-loco", opt.assocNoLoco}, {"--assoc-logistic", opt.assocLogistic}})},
         {"--king", opt.king, takes, first_given({{"--king-out", !opt.kingOut.empty()}, {"--king-cutoff", opt.kingCutoffGiven}})},
         {"--pca", opt.pca, takes,
          first_given({{"--pca-iters", opt.pcaItersGiven}, {"--pca-tol", opt.pcaTolGiven}, {"--pca-out", opt.pcaOutGiven}, {"--pca-loadings", opt.pcaLoadings}})},
@@ -3079,7 +3251,7 @@ int main(int argc, const char* argv[])
     const Cohort co{keep, (unsigned)numInds, numNAs, Ntot, Mtot, local_rank};
     if (!opt.predictBfile.empty()) return run_predict(opt, co);
     if (opt.ldGiven) return run_ld(opt, co);
-    if (opt.assoc) return run_assoc(opt, co, y, covX, C);
+    if (opt.assoc) return opt.assocLogistic ? run_assoc_logistic(opt, co, y, covX, C) : run_assoc(opt, co, y, covX, C);
     if (opt.king) return run_king(opt, co);
     if (opt.pca) return run_pca(opt, co);
     if (opt.pve) return run_pve(opt, co);

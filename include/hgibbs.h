@@ -430,6 +430,33 @@ int hgibbs_ld_clump(hgibbs_t h, uint32_t W, const uint32_t* ahead, double t, con
 int hgibbs_marker_dots(hgibbs_t h, uint32_t m0, uint32_t count, int K, const double* U, double* out, double* raw);
 int hgibbs_last_marker_dots_ms(hgibbs_t h, double* ms);   /* every kernel of the last call, not the host copies */
 
+/* ---- sums of dense vectors over the rows of each genotype code, per marker */
+/* For markers j in [m0, m0 + count) of the loaded BED and K vectors u_k over this rank's n_local individuals (U as
+ * hgibbs_marker_dots takes it: U[k*n_local + i]):
+ *   out[((j - m0)*K + k)*4 + c] = S_jkc = sum_{i : code_ij = c} u_ik,   c = 0, 1, 2 the copies of A1 as hgibbs_load_bed reads them,
+ *                                                                     c = 3 a missing call
+ * the per-marker counterpart of hgibbs_row_sums: any sum_i f(g_ij) u_ik is a combination of the four.  Scale and quantisation are
+ * those of hgibbs_marker_dots (E_k = 52 - e_k with max_i |u_ik| < 2^e_k, E_k = 0 for an all-zero vector, q = llrint(u 2^E_k)); each
+ * of the four is the exact integer sum of its q's, rounded to f64 once (times 2^-E_k), class 0 as sum_i q_ik - S1 - S2 - S3 in
+ * integers.  The only error is the rounding of u, |S_jkc - sum u| <= n_c max|u_k| 2^-52 over the n_c rows of the class before that
+ * one rounding, so a 0/1 vector returns exact counts, S1 + 2 S2 and S0 + S1 + S2 of an integer-valued vector are hgibbs_marker_dots'
+ * raw P and Q, and the results are bit-identical for any m0 / count chunking, any value of the option mdots_split and any repeat.
+ * The sums use neither mave nor mstd: a monomorphic marker has them like any other.  Needs the marker stats (computed here when
+ * they are not).  Refused: K <= 0 or K > 32, a non-finite entry of U, m0 + count > M, a handle without genotypes, several ranks,
+ * n_local >= 2^29, buffers that do not fit in free device memory. */
+int hgibbs_marker_class_sums(hgibbs_t h, uint32_t m0, uint32_t count, int K, const double* U, double* out /* count x K x 4 */);
+int hgibbs_last_marker_class_sums_ms(hgibbs_t h, double* ms);   /* every kernel of the last call, not the host copies */
+
+/* The null model of a logistic score test (host only: no handle, no device; hg_logit.cpp).  Z: n x q column-major, first column all
+ * ones; y: n entries in {0, 1}.  Newton / IRLS in f64 from coefficients 0, every sum in row order (bit-reproducible), the step halved
+ * while the deviance rises (by more than 1e-12 of itself: less is the rounding of its sum).  Stop rule: when max_a |score_a| / sqrt(info_aa) <= 1e-10 one more full step is taken and the fit ends;
+ * at most 50 steps.  coef: the q coefficients; mu: the n fitted probabilities; w = mu (1 - mu); chol: q x q column-major, the lower
+ * Cholesky factor of Z'WZ at coef (zero above the diagonal); iters: the steps taken (may be NULL).  Refused, each by name: a null
+ * argument, q outside 1..64, a non-finite Z, a first column that is not all ones, fewer rows than q + 2, a y outside {0, 1},
+ * "dependent columns" (Z'WZ without a Cholesky factor: a pivot at or below 1e-10 of its diagonal entry), "separation" (no
+ * convergence within 50 steps, or every row fitted to within 1e-6 of its y). */
+int hgibbs_logit_null(uint32_t n, int q, const double* Z, const double* y, double* coef, double* mu, double* w, double* chol, int* iters);
+
 /* ---- KING-robust kinship of the loaded rows -------- */
 /* For rows a, b of the handle (the n_local rows kept at hgibbs_load_bed), over the markers where both calls are present, five exact
  * counts in this order: NSNP (called in both), HET_a, HET_b (a, resp. b, heterozygous among those), HETHET (both heterozygous), IBS0
