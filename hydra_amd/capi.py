@@ -25,6 +25,7 @@ ABI_SYMBOLS = [
     "hgibbs_ld_scores", "hgibbs_last_ld_scores_ms",
     "hgibbs_ld_mask", "hgibbs_last_ld_mask_ms", "hgibbs_ld_greedy", "hgibbs_ld_clump",
     "hgibbs_marker_dots", "hgibbs_last_marker_dots_ms", "hgibbs_marker_class_sums", "hgibbs_last_marker_class_sums_ms", "hgibbs_logit_null",
+    "hgibbs_spa_roots", "hgibbs_last_spa_ms", "hgibbs_spa_pvalue",
     "hgibbs_king", "hgibbs_king_pairs", "hgibbs_king_pairs_get", "hgibbs_last_king_ms",
     "hgibbs_pca", "hgibbs_last_pca_ms", "hgibbs_region_var", "hgibbs_last_region_var_ms",
     "hgibbs_grm", "hgibbs_grm_info", "hgibbs_last_grm_ms",
@@ -55,6 +56,12 @@ class SweepStats(C.Structure):
 
 class PcaReport(C.Structure):
     _fields_ = [("iters_run", C.c_int32), ("m_used", C.c_uint32), ("ritz_change", C.c_double), ("resid", C.c_double * 32)]
+
+
+class SpaRoot(C.Structure):
+    """hgibbs_spa_root: index 0 is the tail at +|s|, index 1 the tail at -|s|"""
+    _fields_ = [("t", C.c_double * 2), ("K", C.c_double * 2), ("K2", C.c_double * 2), ("k2_0", C.c_double), ("s_lo", C.c_double),
+                ("s_hi", C.c_double), ("iters", C.c_int32 * 2), ("flags", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
 class HeForm(C.Structure):
@@ -226,6 +233,9 @@ def lib():
     L.hgibbs_marker_class_sums.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_int, dp, dp]
     L.hgibbs_last_marker_class_sums_ms.argtypes = [vp, dp]
     L.hgibbs_logit_null.argtypes = [C.c_uint32, C.c_int, dp, dp, dp, dp, dp, dp, C.POINTER(C.c_int)]
+    L.hgibbs_spa_roots.argtypes = [vp, C.c_uint32, C_U32P, C.c_int, dp, dp, dp, dp, dp, C.POINTER(SpaRoot)]
+    L.hgibbs_last_spa_ms.argtypes = [vp, dp]
+    L.hgibbs_spa_pvalue.argtypes = [C.c_double, C.POINTER(SpaRoot), dp, dp, dp, C.POINTER(C.c_int)]
     L.hgibbs_king.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32)]
     L.hgibbs_king_pairs.argtypes = [vp, C.c_double, C.POINTER(C.c_uint64)]
     L.hgibbs_king_pairs_get.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), dp]
@@ -347,6 +357,14 @@ def logit_null(Z, y):
     it = C.c_int(0)
     check(lib().hgibbs_logit_null(n, q, _dp(Zc), _dp(y), _dp(coef), _dp(mu), _dp(w), _dp(chol), C.byref(it)))
     return {"coef": coef[:q], "mu": mu[:n], "w": w[:n], "chol": np.ascontiguousarray(chol[:q, :q].T), "iters": it.value}
+
+
+def spa_pvalue(s, root):
+    """hgibbs_spa_pvalue (host only): the saddlepoint p-value of the score s from a SpaRoot of Device.spa_roots.  Returns
+    (p_upper, p_lower, p, valid); p is NaN and valid False unless both tails are valid."""
+    up, dn, p, ok = C.c_double(), C.c_double(), C.c_double(), C.c_int()
+    check(lib().hgibbs_spa_pvalue(float(s), C.byref(root), C.byref(up), C.byref(dn), C.byref(p), C.byref(ok)))
+    return up.value, dn.value, p.value, bool(ok.value)
 
 
 class Device:
@@ -727,6 +745,31 @@ class Device:
     def last_marker_class_sums_ms(self):
         v = C.c_double()
         check(self.L.hgibbs_last_marker_class_sums_ms(self.h, C.byref(v)))
+        return v.value
+
+    def spa_roots(self, markers, Z, mu, B, xv, s):
+        """The saddlepoints of the logistic score test for a list of markers (hgibbs_spa_roots): Z (n_local, q) and mu (n_local,) of
+        the null model, B (nm, q), xv (nm, 4) and s (nm,) per entry.  Returns a ctypes array of nm SpaRoot."""
+        markers = np.ascontiguousarray(markers, dtype=np.uint32).reshape(-1)
+        nm = markers.size
+        Z = np.asarray(Z, dtype=np.float64)
+        if Z.ndim != 2 or Z.shape[0] != self.n_local:
+            raise ValueError("Z must be (%d, q)" % self.n_local)
+        q = Z.shape[1]
+        Zc = np.ascontiguousarray(Z.T)  # column-major
+        mu = np.ascontiguousarray(mu, dtype=np.float64).reshape(-1)
+        B = np.ascontiguousarray(B, dtype=np.float64).reshape(-1)
+        xv = np.ascontiguousarray(xv, dtype=np.float64).reshape(-1)
+        s = np.ascontiguousarray(s, dtype=np.float64).reshape(-1)
+        if mu.size != self.n_local or B.size != nm * q or xv.size != nm * 4 or s.size != nm:
+            raise ValueError("mu must be (%d,), B (%d, %d), xv (%d, 4), s (%d,)" % (self.n_local, nm, q, nm, nm))
+        out = (SpaRoot * max(nm, 1))()
+        check(self.L.hgibbs_spa_roots(self.h, nm, markers.ctypes.data_as(C_U32P), q, _dp(Zc), _dp(mu), _dp(B), _dp(xv), _dp(s), out))
+        return out
+
+    def last_spa_ms(self):
+        v = C.c_double()
+        check(self.L.hgibbs_last_spa_ms(self.h, C.byref(v)))
         return v.value
 
     def king(self, a0=0, acount=None, b0=0, bcount=None):

@@ -203,6 +203,7 @@ struct hgibbs_ctx {
     int mdots_split = 0;   // option mdots_split: ranges of individuals the workgroups of hgibbs_marker_dots split the columns into (0 = automatic)
     double mdots_ms = 0.0; // device time of the last hgibbs_marker_dots (scales, digits, products, rounding)
     double mclass_ms = 0.0; // device time of the last hgibbs_marker_class_sums (scales, digits, products, rounding)
+    double spa_ms = 0.0;    // device time of the last hgibbs_spa_roots (the row-major copy of Z and the root kernel); 0 after a refused call
     int king_split = 0;    // option king_split: ranges of markers the workgroups of hgibbs_king split the k dimension into (0 = automatic)
     double king_ms = 0.0;  // device time of the last hgibbs_king / hgibbs_king_pairs (image, zeroing, products, every run of the list)
     int rvar_kb_max = 0;   // option rvar_kb_max: a marker set of more blocks of 64 than this takes hgibbs_region_var's large-set path (0 = SC_KB_MAX)
@@ -2181,6 +2182,7 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
 #include "hg_ldmask.hip.h"
 #include "hg_mdots.hip.h"
 #include "hg_mclass.hip.h"
+#include "hg_spa.hip.h"
 #include "hg_king.hip.h"
 #include "hg_pca.hip.h"
 #include "hg_grm.hip.h"

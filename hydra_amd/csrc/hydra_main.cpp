@@ -27,7 +27,9 @@
 // hgibbs_score and hgibbs_marker_dots (run_assoc), and writes <dir>/<name>.assoc (or F).  With --assoc-logistic
 // the phenotype is case/control and the table is the logistic score test: a null model per chromosome on [1 | covariates | G - G_c]
 // (hgibbs_logit_null) and the sums of its vectors over the rows of each genotype through hgibbs_marker_class_sums
-// (run_assoc_logistic), written to <dir>/<name>.assoc.logistic (or F).
+// (run_assoc_logistic), written to <dir>/<name>.assoc.logistic (or F).  `--assoc-spa [--assoc-spa-sd T]` with it replaces P by a
+// saddlepoint approximation for the markers whose score is more than T (default 2) SD from 0 and adds the columns P_NORM and SPA
+// (hgibbs_spa_roots, hgibbs_spa_pvalue).
 //
 // `--king [--king-cutoff T] [--king-out F]` appended to a bayesMPI command line samples nothing either: it computes the KING-robust
 // kinship of every pair of the chain's rows with hgibbs_king_pairs (run_king) and writes the pairs with
@@ -137,6 +139,8 @@ struct Options { // src/options.hpp:20-138 (subset that reaches bayesMPI)
     bool assoc = false, assocNoLoco = false;         // --assoc: per-marker association tests; --assoc-no-loco: without LOCO offsets
     std::string assocOut;                            // --assoc-out
     bool assocLogistic = false;                      // --assoc-logistic: the logistic score test of a case/control phenotype
+    bool assocSpa = false, assocSpaSdGiven = false;  // --assoc-spa: saddlepoint p-values for the markers whose score is beyond --assoc-spa-sd SD
+    std::string assocSpaSd = "2";                    // --assoc-spa-sd
     bool king = false, kingCutoffGiven = false;      // --king: KING-robust kinship of the chain's rows; --king-cutoff given
     std::string kingCutoff = "0.0442", kingOut;      // --king-cutoff T (checked before the device), --king-out
     bool pca = false, pcaLoadings = false, pcaItersGiven = false, pcaTolGiven = false, pcaOutGiven = false; // --pca K; which --pca-* were given
@@ -292,6 +296,8 @@ Options parse(int argc, const char* argv[])
         else if (a == "--assoc-no-loco") o.assocNoLoco = true;
         else if (a == "--assoc-out") o.assocOut = need(i);
         else if (a == "--assoc-logistic") o.assocLogistic = true;
+        else if (a == "--assoc-spa") o.assocSpa = true;
+        else if (a == "--assoc-spa-sd") { o.assocSpaSd = need(i); o.assocSpaSdGiven = true; }
         else if (a == "--king") o.king = true;
         else if (a == "--king-cutoff") {
             o.kingCutoff = need(i);
@@ -1915,7 +1921,10 @@ int run_assoc_logistic(const Options& opt, const Cohort& co, const std::vector<d
     std::vector<uint8_t> bed = read_training(opt.bedFile, co.numInds, co.Mtot);
     if (opt.assocOut.empty()) make_out_dir(opt);
     FILE* f = open_out(out, "w");
-    std::fprintf(f, "CHR SNP BP A1 A2 FREQ N BETA SE CHISQ P N_CASE N_CTRL FREQ_CASE FREQ_CTRL\n");
+    const bool spa = opt.assocSpa;
+    double spa_sd = 2.0;
+    whole_num(opt.assocSpaSd, spa_sd);
+    std::fprintf(f, "CHR SNP BP A1 A2 FREQ N BETA SE CHISQ P N_CASE N_CTRL FREQ_CASE FREQ_CTRL%s\n", spa ? " P_NORM SPA" : "");
 
     // the chain's rows and standardisation
     hgibbs_t dev = open_training(co, bed);
@@ -1944,7 +1953,13 @@ int run_assoc_logistic(const Options& opt, const Cohort& co, const std::vector<d
     // one hgibbs_marker_class_sums per run: U = [y - mu, w z_1 .. w z_qn, d]
     std::vector<double> U((size_t)K * N), sums, t(qn), v(qn);
     std::copy(d.begin(), d.end(), U.begin() + (size_t)(K - 1) * N);
-    unsigned long long written = 0;
+    unsigned long long written = 0, spa_n = 0, spa_valid = 0;
+    double spa_ms = 0.0;
+    std::vector<double> Uv, Vv, spa_B, spa_xv, spa_s;
+    std::vector<uint8_t> tested;
+    std::vector<long> spa_at; // the marker's entry in the run's list, or -1
+    std::vector<uint32_t> spa_mk;
+    std::vector<hgibbs_spa_root> spa_roots;
     for (size_t ru = 0; ru < nruns; ++ru) {
         const unsigned m0 = runs[ru], cnt = runs[ru + 1] - runs[ru];
         const Null& nm = nulls[gcol ? (size_t)cj[m0] : 0];
@@ -1958,10 +1973,18 @@ int run_assoc_logistic(const Options& opt, const Cohort& co, const std::vector<d
         double tms = 0.0;
         hg_check(hgibbs_last_marker_class_sums_ms(dev, &tms), "hgibbs_last_marker_class_sums_ms");
         ms += tms;
+        // the score test per marker; with --assoc-spa the markers beyond spa_sd standard deviations are listed for one hgibbs_spa_roots call
+        Uv.assign(cnt, 0.0);
+        Vv.assign(cnt, 0.0);
+        tested.assign(cnt, 0);
+        spa_at.assign(cnt, -1);
+        spa_mk.clear();
+        spa_B.clear();
+        spa_xv.clear();
+        spa_s.clear();
         for (unsigned jj = 0; jj < cnt; ++jj) {
             const unsigned j = m0 + jj;
             const double m = mave[j], sd = mstd[j];
-            const unsigned long long called = (unsigned long long)N - nmiss[j];
             const double* S = &sums[(size_t)jj * K * 4];
             auto xu = [&](int k) { return sd * (S[4 * k + 1] + 2.0 * S[4 * k + 2] - m * (S[4 * k] + S[4 * k + 1] + S[4 * k + 2])); }; // x_j'u_k
             const double xwx = sd * sd * (m * m * S[4] + (1.0 - m) * (1.0 - m) * S[5] + (2.0 - m) * (2.0 - m) * S[6]);
@@ -1972,12 +1995,53 @@ int run_assoc_logistic(const Options& opt, const Cohort& co, const std::vector<d
                 v[a] = e / nm.L[(size_t)a + (size_t)qn * a];
                 V -= v[a] * v[a];
             }
+            if (!std::isfinite(sd) || !(V > 1e-9 * xwx)) continue;
+            tested[jj] = 1;
+            Uv[jj] = xu(0);
+            Vv[jj] = V;
+            if (spa && std::isfinite(V) && std::fabs(Uv[jj]) / std::sqrt(V) > spa_sd) {
+                // b_j = (Z'WZ)^-1 Z'W x_j = L^-T v, the value of each genotype code, the score
+                for (int a = qn - 1; a >= 0; --a) {
+                    double e = v[a];
+                    for (int p = a + 1; p < qn; ++p) e -= nm.L[(size_t)p + (size_t)qn * a] * t[p];
+                    t[a] = e / nm.L[(size_t)a + (size_t)qn * a];
+                }
+                spa_at[jj] = (long)spa_mk.size();
+                spa_mk.push_back(j);
+                spa_B.insert(spa_B.end(), t.begin(), t.end());
+                for (const double x : {(0.0 - m) * sd, (1.0 - m) * sd, (2.0 - m) * sd, 0.0}) spa_xv.push_back(x);
+                spa_s.push_back(Uv[jj]);
+            }
+        }
+        spa_roots.resize(spa_mk.size());
+        if (!spa_mk.empty()) {
+            hg_check(hgibbs_spa_roots(dev, (uint32_t)spa_mk.size(), spa_mk.data(), qn, Zc.data(), nm.mu.data(), spa_B.data(), spa_xv.data(), spa_s.data(),
+                                      spa_roots.data()), "hgibbs_spa_roots");
+            double sms = 0.0;
+            hg_check(hgibbs_last_spa_ms(dev, &sms), "hgibbs_last_spa_ms");
+            spa_ms += sms;
+        }
+        for (unsigned jj = 0; jj < cnt; ++jj) {
+            const unsigned j = m0 + jj;
+            const double m = mave[j], sd = mstd[j];
+            const unsigned long long called = (unsigned long long)N - nmiss[j];
+            const double* S = &sums[(size_t)jj * K * 4];
             std::fprintf(f, "%s %s %lld %s %s %.12g %llu ", bim.chr[j].c_str(), bim.id[j].c_str(), bim.bp[j], bim.a1[j].c_str(), bim.a2[j].c_str(),
                          m / 2.0, called);
-            if (!std::isfinite(sd) || !(V > 1e-9 * xwx)) std::fprintf(f, "NA NA NA NA");
+            double p_norm = 0.0;
+            int spa_ok = -1; // -1 not applied, 0 applied and fell back to the normal P, 1 applied and valid
+            if (!tested[jj]) std::fprintf(f, "NA NA NA NA");
             else {
-                const double Uj = xu(0), chisq = Uj * Uj / V;
-                std::fprintf(f, "%.12g %.12g %.12g %.12g", sd * Uj / V, sd / std::sqrt(V), chisq, std::erfc(std::sqrt(chisq / 2.0)));
+                const double Uj = Uv[jj], V = Vv[jj], chisq = Uj * Uj / V;
+                double p = p_norm = std::erfc(std::sqrt(chisq / 2.0));
+                if (spa_at[jj] >= 0) {
+                    double ps = 0.0;
+                    hg_check(hgibbs_spa_pvalue(Uj, &spa_roots[(size_t)spa_at[jj]], nullptr, nullptr, &ps, &spa_ok), "hgibbs_spa_pvalue");
+                    if (spa_ok) p = ps;
+                    ++spa_n;
+                    spa_valid += spa_ok ? 1u : 0u;
+                }
+                std::fprintf(f, "%.12g %.12g %.12g %.12g", sd * Uj / V, sd / std::sqrt(V), chisq, p);
             }
             // the sums of the case indicator are exact counts of the cases by genotype; the controls are the rest of the marker's stats
             const double* Sd = S + 4 * (K - 1);
@@ -1988,6 +2052,11 @@ int run_assoc_logistic(const Options& opt, const Cohort& co, const std::vector<d
                 if (fr < 0.0) std::fprintf(f, " NA");
                 else std::fprintf(f, " %.12g", fr);
             }
+            if (spa) {
+                if (!tested[jj]) std::fprintf(f, " NA NA");
+                else if (spa_ok < 0) std::fprintf(f, " %.12g NA", p_norm);
+                else std::fprintf(f, " %.12g %d", p_norm, spa_ok);
+            }
             std::fprintf(f, "\n");
             ++written;
         }
@@ -1996,6 +2065,9 @@ int run_assoc_logistic(const Options& opt, const Cohort& co, const std::vector<d
     close_out(f, out);
     std::printf("ASSOC  : wrote %llu rows to %s (%u cases, %u controls, %d iterations of %zu null models, %.3f ms on the device)\n", written, out.c_str(),
                 ncase, N - ncase, iters, nulls.size(), ms);
+    if (spa)
+        std::printf("ASSOC  : SPA on %llu markers (|z| > %g): %llu valid, %llu fell back, %.3f ms on the device\n", spa_n, spa_sd, spa_valid, spa_n - spa_valid,
+                    spa_ms);
     return 0;
 }
 
@@ -3017,6 +3089,16 @@ void check_ld_args(const Options& opt)
     if (opt.ldKbGiven && !(opt.ldWindowKb >= 0.0)) fatal("FATAL  : --ld-window-kb must not be negative");
 }
 
+void check_assoc_args(const Options& opt)
+{
+    if (!opt.assocLogistic)
+        if (const char* o = first_given({{"--assoc-spa", opt.assocSpa}, {"--assoc-spa-sd", opt.assocSpaSdGiven}})) fatal(std::string("FATAL  : ") + o + " needs --assoc-logistic");
+    if (opt.assocSpaSdGiven && !opt.assocSpa) fatal("FATAL  : --assoc-spa-sd needs --assoc-spa");
+    double t = 0.0;
+    if (opt.assocSpaSdGiven && (!whole_num(opt.assocSpaSd, t) || !std::isfinite(t) || !(t >= 0.1)))
+        fatal("FATAL  : --assoc-spa-sd " + opt.assocSpaSd + ": the threshold must be a finite number of standard deviations >= 0.1 (the saddlepoint formula divides by a quantity that goes to 0 with the score)");
+}
+
 void check_king_args(const Options& opt)
 {
     double t = 0.0;
@@ -3138,7 +3220,8 @@ void check_modes(const Options& opt, int nranks)
          first_given({{"--predict-dry-run", opt.predictDryRun}, {"--predict-out", !opt.predictOut.empty()}})},
         {"--ld-window", opt.ldGiven, takes,
          first_given({{"--ld-out", !opt.ldOut.empty()}, {"--ld-window-kb", opt.ldKbGiven}, {"--ld-window-r2", opt.ldR2Given}, {"--ld-bin", opt.ldBin}})},
-        {"--assoc", opt.assoc, takes, first_given({{"--assoc-out", !opt.assocOut.empty()}, {"--assoc-no-loco", opt.assocNoLoco}, {"--assoc-logistic", opt.assocLogistic}})},
+        {"--assoc", opt.assoc, takes, first_given({{"--assoc-out", !opt.assocOut.empty()}, {"--assoc-no-loco", opt.assocNoLoco}, {"--assoc-logistic", opt.assocLogistic},
+                                                   {"--assoc-spa", opt.assocSpa}, {"--assoc-spa-sd", opt.assocSpaSdGiven}})},
         {"--king", opt.king, takes, first_given({{"--king-out", !opt.kingOut.empty()}, {"--king-cutoff", opt.kingCutoffGiven}})},
         {"--pca", opt.pca, takes,
          first_given({{"--pca-iters", opt.pcaItersGiven}, {"--pca-tol", opt.pcaTolGiven}, {"--pca-out", opt.pcaOutGiven}, {"--pca-loadings", opt.pcaLoadings}})},
@@ -3175,6 +3258,7 @@ void check_modes(const Options& opt, int nranks)
         if (opt.restart) fatal("FATAL  : " + flag + " does not sample: it cannot be combined with --restart");
         if (nranks > 1) fatal("FATAL  : " + flag + " runs on one process (WORLD_SIZE = " + std::to_string(nranks) + ")");
         if (i == LD) check_ld_args(opt);
+        if (i == ASSOC) check_assoc_args(opt);
         if (i == KING) check_king_args(opt);
         if (i == PCA) check_pca_args(opt);
         if (i == PVE) check_pve_args(opt);

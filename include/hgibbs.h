@@ -457,6 +457,46 @@ int hgibbs_last_marker_class_sums_ms(hgibbs_t h, double* ms);   /* every kernel 
  * convergence within 50 steps, or every row fitted to within 1e-6 of its y). */
 int hgibbs_logit_null(uint32_t n, int q, const double* Z, const double* y, double* coef, double* mu, double* w, double* chol, int* iters);
 
+/* ---- saddlepoints of the logistic score test, per listed marker */
+/* One record per entry of a marker list.  [0] is the tail at tau = +|s|, [1] the tail at tau = -|s|. */
+typedef struct {
+    double t[2], K[2], K2[2];   /* [0] the tail at +|s|, [1] at -|s|: saddlepoint, K and K'' there */
+    double k2_0, s_lo, s_hi;    /* K''(0) and the open range of K': a tau outside it has no saddlepoint */
+    int32_t iters[2];           /* passes after pass 0 */
+    uint32_t flags;             /* bit 0/1: tail converged; bit 2/3: tail unreachable */
+    uint32_t reserved_;
+} hgibbs_spa_root;
+
+/* For entry e of the list: marker j = markers[e] of the loaded BED (any index below M, in any order, duplicates allowed: the entries
+ * are independent), the null model's rows Z (n_local x q column-major, Z[k*n_local + i], as hgibbs_logit_null takes it) and mu (fitted
+ * probabilities strictly inside (0, 1)), and the entry's own B[e*q + k] = b_k, xv[e*4 + c] (the value of genotype code c; code 3 is a
+ * missing call) and score s[e].  With a_i = xv[code_ij] - sum_k Z_ik b_k and u = a_i t, under d_i ~ Bernoulli(mu_i),
+ *   K(t) = sum_i [log(1 - mu_i + mu_i e^u) - u mu_i],  K'(t) = sum_i a_i (p_i - mu_i),  K''(t) = sum_i a_i^2 p_i (1 - p_i),
+ *   p_i = mu_i e^u / (1 - mu_i + mu_i e^u),
+ * each term in the branch-free stable form on E = expm1(-|u|).  Pass 0 gives k2_0 = K''(0), c = sum a_i mu_i,
+ * s_hi = sum max(a_i, 0) - c and s_lo = sum min(a_i, 0) - c; a tail whose tau is not strictly inside (s_lo, s_hi) is flagged
+ * unreachable and not iterated.  Root rule per tail, both tails in the same passes over the rows: start at t = tau / k2_0 with the
+ * open bracket (0, inf) resp. (-inf, 0); the sign of K'(t) - tau tightens the bracket; the proposal is t' = t - (K' - tau) / K''; first
+ * the stop rule |t' - t| <= 1e-9 max(|t|, 1 / sqrt(k2_0)) (the tail takes t', one more pass gives K(t') and K''(t'), the converged flag
+ * is set), only then the safeguard (a t' not strictly inside the bracket becomes its midpoint when both ends are finite, else 2 t).
+ * At most 64 passes per entry after pass 0; a tail still open then has neither flag.  Every sum over the rows runs in one fixed
+ * order that depends on n_local only (a fixed stride per thread, a fixed tree in the workgroup, no atomics): the records are
+ * bit-identical for any chunking of the list, any position of an entry in it and any repeat.  Padding slots past n_local take no
+ * part.  nm = 0 returns 0 and touches nothing.  Refused: a null argument, q outside 1..64, a marker index >= M, a non-finite entry of
+ * Z, B, xv or s, a mu not strictly inside (0, 1), several ranks, a handle without genotypes, buffers that do not fit in free device
+ * memory. */
+int hgibbs_spa_roots(hgibbs_t h, uint32_t nm, const uint32_t* markers, int q, const double* Z /* n_local x q column-major, as hgibbs_logit_null */,
+                     const double* mu, const double* B /* nm x q */, const double* xv /* nm x 4 */, const double* s /* nm */, hgibbs_spa_root* out);
+int hgibbs_last_spa_ms(hgibbs_t h, double* ms);   /* every kernel of the last call, not the host copies; 0 after a refused call */
+
+/* The saddlepoint p-value from a record of hgibbs_spa_roots (host only: no handle, no device; hg_spa.cpp), Barndorff-Nielsen form.
+ * Per tail, with tau = +|s| resp. -|s|, t, K = K(t), K2 = K''(t):  w = sign(t) sqrt(2 (t tau - K)),  v = t sqrt(K2),
+ * z = w + log(v / w) / w,  tail = erfc(|z| / sqrt 2) / 2.  A tail is valid only if it converged, t tau - K > 0, K2 > 0, v / w > 0 and
+ * z is finite with tau's sign; a tail that underflows to 0 is valid.  p_upper, p_lower (either may be NULL): the tails, NaN where not
+ * valid; p = p_upper + p_lower and valid = 1 when both are valid, else p = NaN and valid = 0 (valid may be NULL): the caller keeps
+ * the normal approximation then.  Refused: a null r or p. */
+int hgibbs_spa_pvalue(double s, const hgibbs_spa_root* r, double* p_upper, double* p_lower, double* p, int* valid);
+
 /* ---- KING-robust kinship of the loaded rows -------- */
 /* For rows a, b of the handle (the n_local rows kept at hgibbs_load_bed), over the markers where both calls are present, five exact
  * counts in this order: NSNP (called in both), HET_a, HET_b (a, resp. b, heterozygous among those), HETHET (both heterozygous), IBS0

@@ -1,0 +1,160 @@
+"""hgibbs_spa_roots against the NumPy restatement of tests/spa_restate.py: flags, saddlepoints, K and K'' per tail and the numbers of
+pass 0 on a grid of cohort sizes and null-model widths; bit-identity across chunkings, orders, duplicates and repeats; every refusal,
+each followed by a call that works."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from hydra_amd import capi, synth
+
+import spa_restate as R
+
+pytestmark = pytest.mark.gpu
+
+# Ten times the largest relative difference between the float64 and the longdouble restatement over the markers of this grid, as
+# tests/test_spa_restatement_cpu.py prints it.  Measured on the CPU: t 2.65e-13, K 3.98e-12, K'' 2.42e-13, p 1.11e-11.  The margin of
+# ten covers the device's other summation order and the last places of its expm1, log1p and division.
+TOL_T = 2.7e-12
+TOL_K = 4.0e-11
+TOL_K2 = 2.5e-12
+TOL_P = 1.2e-10
+
+
+def device(geno):
+    dev = capi.Device(0)
+    dev.load_bed(synth.pack_bed_columns(geno), geno.shape[1])
+    return dev
+
+
+def call(dev, case, idx):
+    idx = np.asarray(idx)
+    return dev.spa_roots(idx, case["Z"], case["mu"], case["B"][idx], case["xv"][idx], case["s"][idx])
+
+
+def raw(recs, k=None):
+    b = bytes(recs)
+    size = C.sizeof(capi.SpaRoot)
+    return b if k is None else b[k * size:(k + 1) * size]
+
+
+def close(got, want, tol):
+    return abs(got - float(want)) <= tol * abs(float(want))
+
+
+@pytest.mark.parametrize("n", R.GRID_N)
+@pytest.mark.parametrize("q", R.GRID_Q)
+def test_grid_against_the_restatement(n, q):
+    case = R.roots_case(n, q)
+    ref = R.case_roots(case)
+    dev = device(case["geno"])
+    everything = np.arange(R.GRID_M)
+    recs = call(dev, case, everything)
+    assert dev.last_spa_ms() > 0.0
+    seen = set()
+    for j, want in enumerate(ref):
+        got = recs[j]
+        assert got.flags == want["flags"] and got.reserved_ == 0, (j, got.flags, want["flags"])
+        seen.add(got.flags)
+        for name in ("k2_0", "s_lo", "s_hi"):
+            assert close(getattr(got, name), want[name], 1e-12), (j, name)
+        for z in range(2):
+            assert 0 <= got.iters[z] <= R.PASSES
+            if got.flags >> z & 1:
+                assert close(got.t[z], want["t"][z], TOL_T), (j, z, got.t[z], want["t"][z])
+                assert close(got.K[z], want["K"][z], TOL_K), (j, z, got.K[z], want["K"][z])
+                assert close(got.K2[z], want["K2"][z], TOL_K2), (j, z)
+                assert got.iters[z] >= 2
+            elif got.flags >> (2 + z) & 1:  # unreachable: never iterated
+                assert (got.t[z], got.K[z], got.K2[z], got.iters[z]) == (0.0, 0.0, 0.0, 0)
+        gp, wp = capi.spa_pvalue(case["s"][j], got), R.pvalue(case["s"][j], want)
+        assert gp[3] == wp[3], j
+        if wp[3]:
+            assert close(gp[2], wp[2], TOL_P), (j, gp, wp)
+    assert 3 in seen and 12 in seen  # converged tails and the unreachable entry
+    # bit-identity: reversed, in calls of 1 and of 7, repeated, and a duplicate index
+    whole = raw(recs)
+    rev = call(dev, case, everything[::-1])
+    assert all(raw(rev, R.GRID_M - 1 - j) == raw(recs, j) for j in range(R.GRID_M))
+    assert b"".join(raw(call(dev, case, [j])) for j in range(0, R.GRID_M, 9)) == b"".join(raw(recs, j) for j in range(0, R.GRID_M, 9))
+    assert b"".join(raw(call(dev, case, everything[k:k + 7])) for k in range(0, R.GRID_M, 7)) == whole
+    assert raw(call(dev, case, everything)) == whole
+    dup = call(dev, case, [11, 40, 11])
+    assert raw(dup, 0) == raw(dup, 2) == raw(recs, 11) and raw(dup, 1) == raw(recs, 40)
+    dev.close()
+
+
+def test_refusals_leave_the_handle_usable():
+    case = R.roots_case(261, 5)
+    dev = device(case["geno"])
+    n, q = case["Z"].shape
+    idx = np.arange(8)
+    good = dict(markers=idx, Z=case["Z"], mu=case["mu"], B=case["B"][idx], xv=case["xv"][idx], s=case["s"][idx])
+    want = raw(dev.spa_roots(**good))
+
+    def spoiled(name, at, value):
+        a = np.array(good[name], dtype=np.float64 if name != "markers" else np.uint32)
+        a[at] = value
+        return dict(good, **{name: a})
+
+    def usable():
+        sums = dev.marker_class_sums(np.ones((1, n)))
+        assert sums.shape == (R.GRID_M, 1, 4) and np.all(sums.sum(axis=2) == n)
+        assert raw(dev.spa_roots(**good)) == want
+
+    bad = [
+        (spoiled("markers", 3, R.GRID_M), "markers[3] = 64 out of range (M = 64)"),
+        (spoiled("Z", (5, 2), np.nan), "Z[5][2] = nan is not finite"),
+        (spoiled("B", (1, 4), np.inf), "B[1][4] = inf is not finite"),
+        (spoiled("xv", (2, 3), np.nan), "xv[2][3] = nan is not finite"),
+        (spoiled("s", 7, -np.inf), "s[7] = -inf is not finite"),
+        (spoiled("mu", 9, 0.0), "mu[9] = 0 is not strictly inside (0, 1)"),
+        (spoiled("mu", 9, 1.0), "mu[9] = 1 is not strictly inside (0, 1)"),
+        (spoiled("mu", 9, np.nan), "mu[9] = nan is not strictly inside (0, 1)"),
+        (dict(good, Z=np.ones((n, 65)), B=np.zeros((8, 65))), "q = 65, must be in [1, 64]"),
+    ]
+    for args, msg in bad:
+        with pytest.raises(capi.HgError, match="hgibbs_spa_roots: "):
+            try:
+                dev.spa_roots(**args)
+            except capi.HgError as e:
+                assert msg in str(e), (msg, str(e))
+                raise
+        assert dev.last_spa_ms() == 0.0  # 0 after a refused call
+        usable()
+    # null arguments and q = 0 straight through the ABI
+    L, dp = capi.lib(), C.POINTER(C.c_double)
+    out = (capi.SpaRoot * 8)()
+    ptr = dict(markers=idx.astype(np.uint32).ctypes.data_as(capi.C_U32P))
+    keep = {k: np.ascontiguousarray(good[k].T if k == "Z" else good[k], dtype=np.float64) for k in ("Z", "mu", "B", "xv", "s")}
+    ptr.update({k: v.ctypes.data_as(dp) for k, v in keep.items()})
+    order = ("Z", "mu", "B", "xv", "s")
+    for missing in ("markers",) + order + ("out",):
+        a = dict(ptr, out=out)
+        a[missing] = None
+        assert L.hgibbs_spa_roots(dev.h, 8, a["markers"], q, *[a[k] for k in order], a["out"]) != 0
+        assert "hgibbs_spa_roots: null argument" in L.hgibbs_last_error().decode()
+        usable()
+    assert L.hgibbs_spa_roots(dev.h, 8, ptr["markers"], 0, *[ptr[k] for k in order], out) != 0
+    assert "hgibbs_spa_roots: q = 0, must be in [1, 64]" in L.hgibbs_last_error().decode()
+    assert L.hgibbs_spa_roots(None, 8, ptr["markers"], q, *[ptr[k] for k in order], out) != 0
+    assert "hgibbs_spa_roots: null handle" in L.hgibbs_last_error().decode()
+    # an empty list touches nothing
+    before = raw(out)
+    assert L.hgibbs_spa_roots(dev.h, 0, ptr["markers"], q, *[ptr[k] for k in order], out) == 0 and raw(out) == before
+    usable()
+    dev.close()
+    # a handle without genotypes
+    empty = capi.Device(0)
+    assert L.hgibbs_spa_roots(empty.h, 8, ptr["markers"], q, *[ptr[k] for k in order], out) != 0
+    assert "hgibbs_spa_roots: no genotypes loaded on this handle" in L.hgibbs_last_error().decode()
+    empty.close()
+
+
+def test_several_ranks_refused():
+    case = R.roots_case(261, 1)
+    dev = capi.Device(0)
+    dev.comm_init_external(2, 0, lambda arr: None)  # a stub world of two ranks
+    dev.load_bed(synth.pack_bed_columns(case["geno"]), 261, row_begin=0, row_end=130, n_global=261)
+    with pytest.raises(capi.HgError, match="hgibbs_spa_roots: one rank only"):
+        dev.spa_roots([0], case["Z"][:dev.n_local], case["mu"][:dev.n_local], case["B"][:1], case["xv"][:1], case["s"][:1])
