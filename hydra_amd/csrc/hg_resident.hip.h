@@ -339,6 +339,41 @@ __device__ __forceinline__ uint32_t wave_sum16_scatter(const uint32_t (&acc)[16]
     return (lane & 1) ? (w >> 16) : (w & 0xffffu);
 }
 
+// The same over NA = 4 or 8 accumulators (a wave with at most 2 NA columns): lane c < 2 NA gets the sum of column c.
+// A step with one value left per lane adds the partner's whole: NA = 8 costs ~half of the sixteen's instructions, NA = 4 a third.
+template <int NA>
+__device__ __forceinline__ uint32_t wave_sum_scatter(const uint32_t (&acc)[NA], int lane)
+{
+    static_assert(NA == 4 || NA == 8, "four or eight accumulators");
+    auto dpp = [](uint32_t v, auto ctrl) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, decltype(ctrl)::value, 0xF, 0xF, false); };
+    using QX1 = std::integral_constant<int, 0xB1>; // lane ^ 1
+    using QX2 = std::integral_constant<int, 0x4E>; // lane ^ 2
+    using QX3 = std::integral_constant<int, 0x1B>; // lane ^ 3
+    using HM = std::integral_constant<int, 0x141>; // lane ^ 7
+    using RM = std::integral_constant<int, 0x140>; // lane ^ 15
+    const bool b0 = lane & 1, b1 = lane & 2, b2 = lane & 4;
+    uint32_t b[NA / 2], c[NA / 4], v;
+#pragma unroll
+    for (int i = 0; i < NA / 2; ++i) b[i] = (b0 ? acc[2 * i + 1] : acc[2 * i]) + dpp(b0 ? acc[2 * i] : acc[2 * i + 1], QX1{});
+#pragma unroll
+    for (int i = 0; i < NA / 4; ++i) c[i] = (b1 ? b[2 * i + 1] : b[2 * i]) + dpp(b1 ? b[2 * i] : b[2 * i + 1], QX2{});
+    if constexpr (NA == 8) v = (b2 ? c[1] : c[0]) + dpp(dpp(b2 ? c[0] : c[1], QX3{}), HM{}); // ^ 3 then ^ 7 = ^ 4
+    else v = c[0] + dpp(dpp(c[0], QX3{}), HM{});
+    v += dpp(dpp(v, HM{}), RM{}); // ^ 7 then ^ 15 = ^ 8
+    v += (uint32_t)__shfl_xor((int)v, 16, 64);
+    v += (uint32_t)__shfl_xor((int)v, 32, 64);
+    // every lane: the wave's sum of accumulator lane & (NA - 1)
+    const uint32_t w = (uint32_t)__shfl((int)v, lane >> 1, 64);
+    return (lane & 1) ? (w >> 16) : (w & 0xffffu);
+}
+// popcount(x) + a as the ONE instruction it is (v_bcnt_u32_b32's add operand): a chain of these is a sum of popcounts without an add
+__device__ __forceinline__ uint32_t popc_add(uint32_t x, uint32_t a)
+{
+    uint32_t r;
+    asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(a));
+    return r;
+}
+
 // four 64-lane integer sums at once (hg_sweep.hip.h: wave_sum_u32), step by step over the four: totals returned wave-uniform
 __device__ __forceinline__ void wave_sum_u32x4(uint32_t (&v)[4])
 {
@@ -510,36 +545,84 @@ __device__ __forceinline__ void rs_gram_terms(const ResParams& p, const uint32_t
     }
     } else
     if (V && with_gram) {
+    // Every instruction costs the wave the same issue slot, so the loop is written by its instruction count: the
+    // wave's nw columns sit in consecutive ring slots from s0 on, so a group of eight that does not straddle the ring's wrap is read
+    // from ONE address with immediate offsets (no slot arithmetic per column; the group that does straddle takes a slot per column);
+    // a column's popcounts chain through v_bcnt_u32_b32's add operand (written by hand: the compiler chains one of the four and adds
+    // the rest); of the last group only the half that holds columns is computed; the reduce-scatter is as wide as the wave's columns.
+    const uint32_t nw = i0 < V ? (V - i0 < Vw ? V - i0 : Vw) : 0u; // columns of this wave (wave-uniform)
+    if (nw) {
     GramPivot gp[T];
 #pragma unroll
     for (int t = 0; t < T; ++t) gp[t] = gram_pivot_x(xq[t]);
-    uint32_t acc[16];
+    const uint32_t s0 = (q + 1u + i0) & bmask;
+    // the group of eight columns from the wave's CB-th on into four accumulators (a column pair each; FULL: all eight are the wave's,
+    // otherwise the first four and, where the wave has more, the rest); read together, past the wave's last: window slots all the same
+    auto group = [&](auto cbtag, auto fulltag, uint32_t* a) __attribute__((always_inline)) {
+        constexpr int CB = decltype(cbtag)::value;
+        constexpr bool FULL = decltype(fulltag)::value;
+        const uint32_t sc = (s0 + (uint32_t)CB) & bmask; // slot of the group's first column
+        uint32_t wv[8][T];
+        if (sc + 8u <= bmask + 1u) { // wave-uniform: no wrap inside the group
+            const uint32_t* rp = ring + sc * 64u * T + (uint32_t)lane * T;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0u;
+            for (int c = 0; c < 8; ++c)
 #pragma unroll
-    for (int cb = 0; cb < 32; cb += 8) {
-        if ((uint32_t)cb < Vw) { // wave-uniform; the eight columns of a group are read together (past the end: column V - 1 again, unused)
-            uint32_t wv[8][T];
+                for (int t = 0; t < T; ++t) wv[c][t] = rp[c * 64 * T + t];
+        } else {
 #pragma unroll
             for (int c = 0; c < 8; ++c) {
-                const uint32_t i = i0 + (uint32_t)(cb + c);
-                const uint32_t slot = (q + 1u + (i < V ? i : V - 1u)) & bmask;
-                const uint32_t* rp = ring + slot * 64u * T + (uint32_t)lane * T;
+                const uint32_t* rp = ring + ((sc + (uint32_t)c) & bmask) * 64u * T + (uint32_t)lane * T;
 #pragma unroll
                 for (int t = 0; t < T; ++t) wv[c][t] = rp[t];
             }
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                uint32_t g = 0u;
-#pragma unroll
-                for (int t = 0; t < T; ++t) g += gram16x(wv[c][t], gp[t]);
-                acc[(cb + c) >> 1] += g << (16 * (c & 1)); // a lane adds at most 64 T <= 256 per column: the 64-lane sum fits 16 bits
-            }
+            asm volatile("" ::: "memory"); // (keeps the two forms of the reads apart: merged, every column gets an address register again)
         }
+        auto half = [&](auto htag) __attribute__((always_inline)) {
+            constexpr int H = decltype(htag)::value;
+#pragma unroll
+            for (int c = H; c < H + 4; ++c) {
+                uint32_t g = (uint32_t)__popc(wv[c][0] & gp[0].uu);
+                g = popc_add(wv[c][0] & gp[0].vv, g);
+#pragma unroll
+                for (int t = 1; t < T; ++t) {
+                    g = popc_add(wv[c][t] & gp[t].uu, g);
+                    g = popc_add(wv[c][t] & gp[t].vv, g);
+                }
+                // a lane adds at most 64 T <= 256 per column: the 64-lane sum fits 16 bits
+                if (c & 1) a[c >> 1] |= g << 16;
+                else a[c >> 1] = g;
+            }
+        };
+        half(std::integral_constant<int, 0>{});
+        if (FULL || nw > (uint32_t)CB + 4u) half(std::integral_constant<int, 4>{});
+        else a[2] = a[3] = 0u; // (summed like the others, read by no lane that sends)
+    };
+    using std::integral_constant;
+    using std::true_type;
+    using std::false_type;
+    uint32_t mine; // lane c: the wave's Gram term of its column c
+    if (nw <= 8u) {
+        uint32_t acc[4];
+        group(integral_constant<int, 0>{}, false_type{}, acc);
+        mine = wave_sum_scatter<4>(acc, lane);
+    } else if (nw <= 16u) {
+        uint32_t acc[8];
+        group(integral_constant<int, 0>{}, true_type{}, acc);
+        group(integral_constant<int, 8>{}, false_type{}, acc + 4);
+        mine = wave_sum_scatter<8>(acc, lane);
+    } else {
+        uint32_t acc[16];
+        group(integral_constant<int, 0>{}, true_type{}, acc);
+        group(integral_constant<int, 8>{}, true_type{}, acc + 4);
+        group(integral_constant<int, 16>{}, false_type{}, acc + 8);
+        if (nw > 24u) group(integral_constant<int, 24>{}, false_type{}, acc + 12);
+        else acc[12] = acc[13] = acc[14] = acc[15] = 0u;
+        mine = wave_sum16_scatter(acc, lane);
     }
-    const uint32_t mine = wave_sum16_scatter(acc, lane); // lane c: the wave's Gram term of its column c
-    if ((uint32_t)lane < Vw && i0 + (uint32_t)lane < V) // one instruction per wave, contiguous words (by window slot of the column, up to the wrap): count in the top byte
+    if ((uint32_t)lane < nw) // one instruction per wave, contiguous words (by window slot of the column, up to the wrap): count in the top byte
         __hip_atomic_fetch_add(p.gacc + ((size_t)(nev & 1u) * RS_NSH + (wg % p.nsh)) * RS_GROW + ((q + 1u + i0 + (uint32_t)lane) & bmask), RS_ONE | mine, HG_RLX_AGENT);
+    }
     }
 }
 
