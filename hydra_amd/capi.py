@@ -19,7 +19,7 @@ ABI_SYMBOLS = [
     "hgibbs_update_marker", "hgibbs_dot_marker", "hgibbs_set_covariates", "hgibbs_cov_dot", "hgibbs_cov_update",
     "hydra_chain_set_covariates", "hydra_chain_gamma", "hgibbs_set_components", "hydra_chain_restore",
     "hydra_rng_to_boost_words", "hydra_rng_from_boost_words", "hydra_rng_shuffle", "hgibbs_set_model", "hgibbs_set_beta", "hgibbs_get_beta",
-    "hgibbs_beta_sqnorm", "hgibbs_sweep", "hgibbs_set_option", "hgibbs_last_sweep_stats", "hgibbs_stream_ceiling", "hgibbs_debug_times", "hgibbs_resident_trace", "hydra_chain_create",
+    "hgibbs_beta_sqnorm", "hgibbs_sweep", "hgibbs_set_option", "hgibbs_walker_search", "hgibbs_last_sweep_stats", "hgibbs_stream_ceiling", "hgibbs_debug_times", "hgibbs_resident_trace", "hydra_chain_create",
     "hydra_chain_destroy", "hydra_chain_iterate", "hydra_chain_state", "hydra_chain_csv_line", "hydra_chain_order",
     "hydra_chain_last_nnz", "hgibbs_score", "hgibbs_last_score_ms", "hgibbs_ld", "hgibbs_last_ld_ms",
     "hgibbs_ld_scores", "hgibbs_last_ld_scores_ms",
@@ -51,7 +51,7 @@ class SweepStats(C.Structure):
                 ("accepted_markers", C.c_uint64), ("streamed_columns", C.c_uint64), ("tiles_per_workgroup_min", C.c_uint32),
                 ("tiles_per_workgroup_max", C.c_uint32), ("engine", C.c_uint32), ("walker", C.c_uint32), ("eps_sum_drift", C.c_double),
                 ("rounds", C.c_uint64), ("events", C.c_uint64), ("advances", C.c_uint64), ("chunks", C.c_uint64), ("refolds", C.c_uint64), ("pivots", C.c_uint64), ("predicted", C.c_uint64), ("shader_mhz", C.c_double),
-                ("ticks", C.c_uint64 * 16), ("refill", C.c_uint32), ("reserved_", C.c_uint32)]
+                ("ticks", C.c_uint64 * 16), ("refill", C.c_uint32), ("turned_down", C.c_uint32)]
 
 
 class PcaReport(C.Structure):
@@ -174,6 +174,7 @@ def lib():
     L.hgibbs_beta_sqnorm.argtypes = [vp, dp]
     L.hgibbs_sweep.argtypes = [vp, ip, C.c_double, dp, dp, u8p, C.POINTER(RngState), ip, u64p]
     L.hgibbs_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
+    L.hgibbs_walker_search.argtypes = [u64p, C.c_uint32, C.c_uint32, u32p, C.c_uint32]
     L.hgibbs_last_sweep_stats.argtypes = [vp, C.POINTER(SweepStats)]
     L.hgibbs_stream_ceiling.argtypes = [vp, C.c_uint64, C.c_int, dp]
     L.hgibbs_debug_times.argtypes = [vp, C.POINTER(C.c_uint64)]
@@ -900,7 +901,7 @@ class Device:
                 "accepted_markers": s.accepted_markers, "streamed_columns": s.streamed_columns,
                 "tiles_per_workgroup_min": s.tiles_per_workgroup_min, "tiles_per_workgroup_max": s.tiles_per_workgroup_max,
                 "engine": s.engine, "walker": s.walker, "refill": s.refill, "eps_sum_drift": s.eps_sum_drift, "rounds": s.rounds, "events": s.events,
-                "advances": s.advances, "chunks": s.chunks, "refolds": s.refolds, "pivots": s.pivots, "predicted": s.predicted, "shader_mhz": s.shader_mhz, "ticks": list(s.ticks)}
+                "advances": s.advances, "chunks": s.chunks, "refolds": s.refolds, "pivots": s.pivots, "predicted": s.predicted, "turned_down": s.turned_down, "shader_mhz": s.shader_mhz, "ticks": list(s.ticks)}
 
 
 class Chain:

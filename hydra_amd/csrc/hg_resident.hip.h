@@ -90,7 +90,7 @@ __host__ __device__ inline uint32_t rs_window_end(uint32_t C, uint32_t B, uint32
 __host__ __device__ inline uint32_t rs_msg_word0(uint32_t kf, uint32_t ncons, uint32_t seq, uint32_t lo, uint32_t hi) { return (kf << 28) | (rs_msg_check(seq, lo, hi) << 12) | ncons; }
 
 struct ResState { // device -> host, written by the walker at the end of the sweep
-    uint32_t cursor, rng_idx, error, pad;
+    uint32_t cursor, rng_idx, error, turned_down; // (turned_down, second walker: candidates the exact decision found to be no event)
     unsigned long long rounds, events, advances, nnz, chunks, refolds, pivots, predicted;
     unsigned long long shader_ticks, wall_ticks; // s_memtime and 100 MHz wall clock over the walker's life: the clock the chip held
     unsigned long long t[16]; // 100 MHz ticks: walker [0] fold [1] collect [2] evaluate [3] scan + draw [4] announce + outputs + prefetch;
@@ -144,8 +144,10 @@ struct ResParams {
     unsigned long long* trace;   // debug_timing: [8][RS_TRACE] wall-clock stamps of the last RS_TRACE messages (tools/res_anatomy.py)
     int dbg;
     int pivots; // 1: Gram terms with predicted pivots are taken when a column is streamed (messages RS_PIVOT need no round trip)
-    int unused_; // (free: keeps the offsets of the fields below.  Without it pivots and early_advance share one 8-byte word, which the second
-                 // walker's chain (w2_chain) then loads as one, and the compiler allocates that loop's registers differently)
+    int bound_slack; // second walker, a test hook (option bound_slack, default 0): taken off every threshold of the tabulated bound where the thresholds
+                     // are made (tq_of), so that more positions -- with a large value all of them -- go through the exact decision.  The chain's code
+                     // does not read it.  (The field also keeps the offsets below: without a word here pivots and early_advance share one 8-byte
+                     // word, which the second walker's chain (w2_chain) then loads as one, and the compiler allocates that loop's registers differently.)
     int early_advance; // second walker: a walk that has run out of dots moves the window on at once (a message that only advances) when at least this many positions have passed (0: it waits)
     uint32_t wend_mask; // 15 (second walker, B >= 32): the window ends at a multiple of sixteen positions -- min((C + B) & ~15, M) -- so that the
                         // streaming workgroups' second form admits every group of sixteen columns in ONE round (else 0: the window is C + B)

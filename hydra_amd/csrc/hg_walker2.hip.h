@@ -80,7 +80,7 @@ enum {
 };
 enum { RT_EXTEND = 0, RT_ADVANCE = 1, RT_PIVOT = 2, RT_EVENT = 3, RT_END = 4 };
 // the decider's statistics of the sweep, by lane
-enum { W2_ST_ROUNDS = 0, W2_ST_EVENTS, W2_ST_ADV, W2_ST_NNZ, W2_ST_CHUNKS, W2_ST_REFOLD, W2_ST_PIVOTS, W2_ST_PRED, W2_ST_ANN };
+enum { W2_ST_ROUNDS = 0, W2_ST_EVENTS, W2_ST_ADV, W2_ST_NNZ, W2_ST_CHUNKS, W2_ST_REFOLD, W2_ST_PIVOTS, W2_ST_PRED, W2_ST_ANN, W2_ST_TURNED };
 
 // LDS of the walker workgroup.  The carve-up is a list of byte offsets (host and device agree on its end); the device takes its
 // pointers from it with the LDS address space in their TYPE: res_walker2 is a function of its own (not inlined into the kernel), and
@@ -221,12 +221,14 @@ __device__ __forceinline__ Walk2Lds walk2_lds(uint32_t B)
 // of the register file).
 #define W2_BEXPR pr.B
 #define W2_PIVEXPR (pr.pivots != 0)
+#define W2_KEXPR pr.K
 #define W2_PROLOGUE \
     const int tid = threadIdx.x, lane = tid & 63; \
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6); \
     const uint32_t B = W2_BEXPR, bmask = B - 1u, M = pr.M; \
     const uint32_t MR = 2u * B, mrmask = MR - 1u; \
-    const int K = pr.K, GK = pr.GK; \
+    const int K = W2_KEXPR, GK = pr.GK; \
+    const double bound_slack = (double)pr.bound_slack; \
     const uint32_t W = pr.W, nsh = pr.nsh, rsh = pr.rsh; \
     const double n_total = pr.n_total, n_minus_1 = pr.n_minus_1, i_2sigE = pr.i_2sigE, eps_sum = pr.eps_sum, fx_unscale = pr.fx_unscale; \
     const unsigned long long timeout = pr.timeout; \
@@ -266,18 +268,50 @@ __device__ __forceinline__ Walk2Lds walk2_lds(uint32_t B)
     }; \
     auto tq_of = [&](uint32_t word) { \
         const double prob = (double)mt_temper(word) * (1.0 / 4294967296.0); \
-        return log(1.0 / prob - 1.0) - 1e-9; \
+        return log(1.0 / prob - 1.0) - 1e-9 - bound_slack; /* (bound_slack: 0 but in tests -- a lower threshold only sends more positions to the exact decision) */ \
     }; \
     auto aborted = [&]() { return w2_ld(sh.sw + S_ABORT) != 0u; }; \
     auto ended = [&]() { return w2_ld(sh.sw + S_END) != 0u; };
+
+// The candidates of the window: chain wave i answers with the 64-bit mask of its slots 64 i .. 64 i + 63, `nch` waves are in use (one where
+// the window is at most 64 slots: then only the bits below the window's size are ever set).  WINDOW ORDER from the cursor's slot s0 is: wave
+// s0 / 64 from lane s0 % 64 up, the waves behind it (wrapping at nch), and last the lanes of wave s0 / 64 below the cursor's -- the wrap
+// inside a wave.  The index arithmetic of the decider's search is here, for the device and for the host (hgibbs_walker_search; the CPU suite
+// runs it against a naive loop): the slot of the first candidate in window order, or 0xffffffff.  get(i) is wave i's mask.
+// The common case -- the next event is near -- is the first probe.
+template <class Get>
+__host__ __device__ __forceinline__ uint32_t w2_first_candidate(uint32_t s0, uint32_t nch, Get&& get)
+{
+    const uint32_t i0 = s0 >> 6;
+    const unsigned long long lowm = (1ull << (s0 & 63u)) - 1ull;
+    const unsigned long long m0 = get(i0);
+    unsigned long long mm = m0 & ~lowm;
+    if (mm) return i0 * 64u + (uint32_t)__builtin_ctzll(mm);
+    uint32_t i = i0;
+    for (uint32_t t = 1; t < nch; ++t) {
+        i = i + 1u == nch ? 0u : i + 1u;
+        mm = get(i);
+        if (mm) return i * 64u + (uint32_t)__builtin_ctzll(mm);
+    }
+    mm = m0 & lowm;
+    return mm ? i0 * 64u + (uint32_t)__builtin_ctzll(mm) : 0xffffffffu;
+}
+// wave i's mask without the candidate at slot qs (the exact decision found no event there: the search goes on behind it)
+__host__ __device__ __forceinline__ unsigned long long w2_without_candidate(unsigned long long m, uint32_t i, uint32_t qs)
+{
+    return i == (qs >> 6) ? m & ~(1ull << (qs & 63u)) : m;
+}
 
 // (BC: the window as a compile-time constant -- 256, the size that is used where speed matters -- or 0: whatever the sweep's parameters say.
 // With the constant the LDS arrays are at constant addresses and the slot arithmetic is immediate: the wave's few scalar registers are not
 // spent on three dozen array bases, and a wave issues one instruction every four to five clocks whatever it is.)
 // (DECIDE: the instance wave 0 runs -- it decides; waves 1-3 run the instance without the decider's code and state.  PIV: the predicted-pivot
-// path is compiled in; res_walker2 picks it where the sweep takes pivots, which the plan allows with one rank and no missing calls only.)
-template <int DBG, int MISS, int BC, int RANKS, int DECIDE, int PIV>
-__device__ __attribute__((noinline)) void w2_chain(const ResParams& prg)
+// path is compiled in; res_walker2 picks it where the sweep takes pivots, which the plan allows with one rank and no missing calls only.
+// KC: the number of mixture components as a compile-time constant -- 4, what the decider of a single rank's 256-column window runs where the
+// model has four -- or 0: whatever the sweep's parameters say.  With the constant a5's sum over the components is K - 1 DPP steps and its
+// walk K - 1 compare-and-select steps with no test of K between them; the arithmetic is the same.)
+template <int DBG, int MISS, int BC, int RANKS, int DECIDE, int PIV, int KC>
+__device__ __forceinline__ void w2_chain_body(const ResParams& prg)
 {
     // The parameters through a pointer the compiler knows to be the same in every lane and constant for the launch.  A called function
     // receives its pointer argument in vector registers: read through that, every parameter -- M, K, the timeout, the options -- and all
@@ -292,11 +326,15 @@ __device__ __attribute__((noinline)) void w2_chain(const ResParams& prg)
 #define W2_BEXPR (BC ? (uint32_t)BC : pr.B)
 #undef W2_PIVEXPR
 #define W2_PIVEXPR (PIV != 0)
+#undef W2_KEXPR
+#define W2_KEXPR (KC ? KC : pr.K)
     W2_PROLOGUE
 #undef W2_BEXPR
 #define W2_BEXPR pr.B
 #undef W2_PIVEXPR
 #define W2_PIVEXPR (pr.pivots != 0)
+#undef W2_KEXPR
+#define W2_KEXPR pr.K
     // =====================================================================================================================
     // the chain: wave w holds the window slots 64 w + lane, one position per lane; wave 0 also decides
     // =====================================================================================================================
@@ -332,7 +370,15 @@ __device__ __attribute__((noinline)) void w2_chain(const ResParams& prg)
     // ---- the decider's own state (wave 0; uniform) ----
     uint32_t seq = 0, nev = 0, pi = 0, evn = 0, pf_n = 0, gpos = rng_idx0, blk = 1u;
     uint32_t rdone_seen = 0, wpub_seen = 0, evw_seen = 0, pld_seen = W2_PRED, fpub_seen = 0, mpub_seen = m0;
-    unsigned long long cm[W2_NCH] = {0ull, 0ull, 0ull, 0ull}; // candidates among the tested positions [C, Fs), by chain wave
+    // candidates among the tested positions [C, Fs): chain wave i's 64-bit mask in LANE i of a register pair.  The search reads a wave's mask
+    // with a scalar index (v_readlane), and the other waves' answers arrive in their lanes by one LDS read; as four scalar pairs every probe
+    // of the search chose among them by 64-bit selects (114 instructions).
+    uint32_t cml = 0, cmh = 0;
+    auto cm_of = [&](uint32_t i) {
+        return ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)cmh, (int)i) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)cml, (int)i);
+    };
+    // (lane i = 1 .. nch - 1 reads wave i's answer; every other lane entry 0, which nobody writes: zeros)
+    const uint32_t ans_i = (lane >= 1 && (uint32_t)lane < nch) ? (uint32_t)lane : 0u;
     // the sweep's statistics, one per lane of a vector register (W2_ST_*): they are not the loop's scalar state, and a round adds its
     // increments in one instruction from a mask of the counters that move
     uint32_t stat = 0;
@@ -651,28 +697,34 @@ __device__ __attribute__((noinline)) void w2_chain(const ResParams& prg)
         // =================================================================================================================
         // the decider: the other waves' answers, the first candidate in window order, the exact decision, the next record
         // =================================================================================================================
-        if (r_type != (uint32_t)RT_EXTEND) cm[0] = cm[1] = cm[2] = cm[3] = 0ull;
-        cm[0] |= mymask;
-        if (nch > 1u) { // the other waves' answers: all three entries in one round trip, again until each carries this record's number
-            const unsigned long long t0 = wall_clock64();
-            for (;;) {
-                const u4_t a1 = *(const volatile W2_LDS u4_t*)(sh.ans + 4), a2 = *(const volatile W2_LDS u4_t*)(sh.ans + 8), a3 = *(const volatile W2_LDS u4_t*)(sh.ans + 12);
-                const bool ok = w2_uni(a1.z) == rno && (nch < 3u || (w2_uni(a2.z) == rno && w2_uni(a3.z) == rno));
-                if (ok) {
-                    cm[1] |= ((unsigned long long)w2_uni(a1.y) << 32) | w2_uni(a1.x);
-                    if (nch >= 3u) {
-                        cm[2] |= ((unsigned long long)w2_uni(a2.y) << 32) | w2_uni(a2.x);
-                        cm[3] |= ((unsigned long long)w2_uni(a3.y) << 32) | w2_uni(a3.x);
+        {
+            // the other waves' answers, each in its own lane: one read of 16 bytes per lane, again until every entry carries this record's number
+            uint32_t al = 0u, ah = 0u;
+            if (nch > 1u) {
+                const uint32_t want = ans_i ? rno : 0u;
+                unsigned long long t0 = 0ull;
+                for (bool first = true;; first = false) {
+                    const u4_t a = *(const volatile W2_LDS u4_t*)(sh.ans + 4u * ans_i);
+                    if (__ballot(a.z != want) == 0ull) {
+                        al = a.x;
+                        ah = a.y;
+                        break;
                     }
-                    break;
-                }
-                if (spin_fail(t0)) {
-                    failed = true;
-                    break;
+                    if (first) t0 = wall_clock64(); // (the clock is read only where the answers were not there at once)
+                    else if (spin_fail(t0)) {
+                        failed = true;
+                        break;
+                    }
                 }
             }
+            if (failed) break;
+            // this wave's own mask into lane 0; a record that moved the window starts the masks afresh
+            al = lane == 0 ? (uint32_t)mymask : al;
+            ah = lane == 0 ? (uint32_t)(mymask >> 32) : ah;
+            const uint32_t keep = r_type != (uint32_t)RT_EXTEND ? 0u : 0xffffffffu;
+            cml = (cml & keep) | al;
+            cmh = (cmh & keep) | ah;
         }
-        if (failed) break;
         lap(1);
         // the counters the message's flow control will ask for leave LDS now, all at once, and are looked at behind the exact decision: read
         // one by one where they are needed they were three trips to LDS in front of every message (their cached values go stale every round)
@@ -711,25 +763,11 @@ __device__ __attribute__((noinline)) void w2_chain(const ResParams& prg)
         int q_k = 0;
         double q_bnew = 0.0, q_bold = 0.0, q_mq = 0.0, q_sq = 0.0, q_gsq = 0.0, q_nmq = 0.0;
         {
-            const uint32_t s0 = C & bmask, i0 = s0 >> 6, l0 = s0 & 63u;
-            const unsigned long long lowm = (1ull << l0) - 1ull;
+            const uint32_t s0 = C & bmask;
             for (;;) {
-                uint32_t qs = 0xffffffffu;
-#pragma unroll
-                for (int t = 0; t <= W2_NCH; ++t) {
-                    if ((uint32_t)t <= nch && qs == 0xffffffffu) {
-                        uint32_t i = i0 + (uint32_t)t;
-                        i = i >= nch ? i - nch : i;
-                        unsigned long long mm = i == 0u ? cm[0] : (i == 1u ? cm[1] : (i == 2u ? cm[2] : cm[3]));
-                        if (t == 0) mm &= ~lowm;
-                        if ((uint32_t)t == nch) mm &= lowm;
-                        if (mm) qs = i * 64u + (uint32_t)(__ffsll((long long)mm) - 1);
-                    }
-                }
-                qs = w2_uni(qs);
-                if (qs == 0xffffffffu) break; // uniform
+                const uint32_t qs = w2_first_candidate(s0, nch, cm_of); // (scalar: the masks are read with scalar indices)
+                if (qs == 0xffffffffu) break;
                 const uint32_t qc = pos_of_slot(qs, C);
-                const uint32_t qi = qs >> 6, ql = qs & 63u;
                 const uint32_t ms = qc & mrmask;
                 uint32_t upos = gposr + (qc - C);
                 upos = upos >= W2_RING ? upos - W2_RING : upos;
@@ -789,23 +827,36 @@ __device__ __attribute__((noinline)) void w2_chain(const ResParams& prg)
                 const unsigned long long bm = __ballot(bigp);
                 double sum = ex, cur = ex;
 #pragma unroll
-                for (int x = 1; x < 8; ++x) {
+                for (int x = 1; x < (KC ? KC : 8); ++x) {
                     cur = rs_dpp_f64<0x101>(cur); // row_shl:1 -- lane i takes lane i + 1's
-                    if (x < K) sum += cur;        // wave-uniform
+                    if (x < K) sum += cur;        // wave-uniform (KC: K - 1 steps, no test)
                 }
                 const bool anyb = ((bm >> (lane & ~7)) & 0xffull) != 0ull;
                 const double thr = anyb ? 0.0 : 1.0 / sum; // of walk step kk, valid in the first lane of its group
                 int k = K - 1;
-                double acum = 0.0;
-                bool fnd = false;
+                if constexpr (KC != 0) {
+                    // K is known: the thresholds' running sums in the walk's order, then the selects from the last step down -- the step that
+                    // assigns last is the first that passes walking up; no branch, no flag
+                    double ac[KC > 1 ? KC - 1 : 1];
 #pragma unroll
-                for (int sidx = 0; sidx < 7; ++sidx) {
-                    if (sidx + 1 < K) { // wave-uniform
+                    for (int sidx = 0; sidx + 1 < KC; ++sidx) {
                         const double t = rs_readlane(thr, 8 * sidx);
-                        acum = sidx ? acum + t : t;
-                        if (!fnd && prob <= acum) {
-                            k = sidx;
-                            fnd = true;
+                        ac[sidx] = sidx ? ac[sidx - 1] + t : t;
+                    }
+#pragma unroll
+                    for (int sidx = KC - 2; sidx >= 0; --sidx) k = prob <= ac[sidx] ? sidx : k;
+                } else {
+                    double acum = 0.0;
+                    bool fnd = false;
+#pragma unroll
+                    for (int sidx = 0; sidx < 7; ++sidx) {
+                        if (sidx + 1 < K) { // wave-uniform
+                            const double t = rs_readlane(thr, 8 * sidx);
+                            acum = sidx ? acum + t : t;
+                            if (!fnd && prob <= acum) {
+                                k = sidx;
+                                fnd = true;
+                            }
                         }
                     }
                 }
@@ -849,11 +900,10 @@ __device__ __attribute__((noinline)) void w2_chain(const ResParams& prg)
                     break;
                 }
                 // too close to call, and no event: on to the next candidate
-                const unsigned long long bit = 1ull << ql;
-                if (qi == 0u) cm[0] &= ~bit;
-                else if (qi == 1u) cm[1] &= ~bit;
-                else if (qi == 2u) cm[2] &= ~bit;
-                else cm[3] &= ~bit;
+                count(1u << W2_ST_TURNED);
+                const unsigned long long cmn = w2_without_candidate(((unsigned long long)cmh << 32) | cml, (uint32_t)lane, qs);
+                cml = (uint32_t)cmn;
+                cmh = (uint32_t)(cmn >> 32);
             }
         }
         lap(3);
@@ -991,10 +1041,24 @@ __device__ __attribute__((noinline)) void w2_chain(const ResParams& prg)
             state->refolds = st(W2_ST_REFOLD);
             state->pivots = st(W2_ST_PIVOTS) + st(W2_ST_ANN); // (events whose Gram terms the walker did not have to wait a whole round trip for: predicted pivots, or announced)
             state->predicted = st(W2_ST_PRED);
+            state->turned_down = st(W2_ST_TURNED);
             if (DBG)
                 for (int i = 0; i < 8; ++i) state->t[i] = tacc[i];
         }
     }
+}
+
+// the chain's instances as functions of their own: by role and feature with the run-time K, and the decider of a single rank's 256-column
+// window for four components
+template <int DBG, int MISS, int BC, int RANKS, int DECIDE, int PIV>
+__device__ __attribute__((noinline)) void w2_chain(const ResParams& prg)
+{
+    w2_chain_body<DBG, MISS, BC, RANKS, DECIDE, PIV, 0>(prg);
+}
+template <int DBG, int MISS>
+__device__ __attribute__((noinline)) void w2_chain_k4(const ResParams& prg)
+{
+    w2_chain_body<DBG, MISS, 256, 0, 1, 0, 4>(prg);
 }
 
 template <int MISS, int RANKS>
@@ -1384,8 +1448,11 @@ __device__ __attribute__((noinline)) void res_walker2(const ResParams& pr)
                 else if (!MISS && pr.pivots) {
                     if (B == 256u) w2_chain<DBG, MISS, 256, 0, 1, 1>(pr);
                     else w2_chain<DBG, MISS, 0, 0, 1, 1>(pr);
-                } else if (B == 256u) w2_chain<DBG, MISS, 256, 0, 1, 0>(pr);
-                else w2_chain<DBG, MISS, 0, 0, 1, 0>(pr);
+                } else if (B == 256u) {
+                    // (four components, as every benchmark configuration has them: a5 with K as a constant)
+                    if (K == 4) w2_chain_k4<DBG, MISS>(pr);
+                    else w2_chain<DBG, MISS, 256, 0, 1, 0>(pr);
+                } else w2_chain<DBG, MISS, 0, 0, 1, 0>(pr);
             } else {
                 if (pr.nranks > 1) w2_chain<DBG, MISS, 0, 1, 0, 0>(pr);
                 else if (!MISS && pr.pivots) {

@@ -174,6 +174,7 @@ struct hgibbs_ctx {
     bool res_not_resident = false; // a resident grid was found partly resident (another process on the device): engine 0 means the batch engine from then on
     int res_early = 24;       // option early_advance (ResParams::early_advance)
     int res_announce = 1;     // option announce (ResParams::announce)
+    int res_bound_slack = 0;  // option bound_slack (ResParams::bound_slack)
     int res_wend = 1;         // option window_end16 (ResParams::wend_mask)
     int res_walker2_ranks = 1; // option walker2_ranks: several ranks run the second walker too (0: the first, as in round 3)
     double eps_abs_bound = 0.0; // (sum of eps^8)^(1/8) >= max |eps| as of the last reduce_eps_all
@@ -1378,6 +1379,9 @@ int hgibbs_set_option(hgibbs_t h, const char* name, int64_t value)
         h->res_wend = value != 0;
     } else if (!std::strcmp(name, "announce")) {
         h->res_announce = value != 0;
+    } else if (!std::strcmp(name, "bound_slack")) {
+        if (value < 0 || value > 1000000) return fail("bound_slack must be in [0,1000000]");
+        h->res_bound_slack = (int)value;
     } else if (!std::strcmp(name, "walker")) {
         if (value < 0 || value > 2) return fail("walker must be 0 (auto), 1 (first) or 2 (second)");
         h->res_walker = (int)value;
@@ -1406,6 +1410,26 @@ int hgibbs_set_option(hgibbs_t h, const char* name, int64_t value)
         return fail("hgibbs_set_option: unknown option '%s'", name);
     }
     return 0;
+}
+
+/* The second walker's candidate search on the host (hg_walker2.hip.h: w2_first_candidate, w2_without_candidate -- the very
+ * functions the decider calls): the slots of all candidates in window order from the cursor's slot, found as the decider finds them:
+ * the first, that one cleared, the next, until the masks are empty. */
+int hgibbs_walker_search(const uint64_t* masks, uint32_t nch, uint32_t cursor_slot, uint32_t* slots, uint32_t cap)
+{
+    if (!masks || (!slots && cap)) return fail("hgibbs_walker_search: null argument"), -1; // (a count is returned: failure is -1)
+    if (nch < 1 || nch > (uint32_t)W2_NCH || cursor_slot >= nch * 64u) return fail("hgibbs_walker_search: 1 <= nch <= %d and cursor_slot < 64 nch", W2_NCH), -1;
+    unsigned long long cm[W2_NCH] = {0ull, 0ull, 0ull, 0ull};
+    for (uint32_t i = 0; i < nch; ++i) cm[i] = masks[i];
+    uint32_t n = 0;
+    for (;;) {
+        const uint32_t qs = w2_first_candidate(cursor_slot, nch, [&](uint32_t i) { return cm[i]; });
+        if (qs == 0xffffffffu) break;
+        if (n >= cap) return fail("hgibbs_walker_search: more than %u candidates", cap), -1;
+        slots[n++] = qs;
+        for (uint32_t i = 0; i < (uint32_t)W2_NCH; ++i) cm[i] = w2_without_candidate(cm[i], i, qs);
+    }
+    return (int)n;
 }
 
 /* stage timestamps (100 MHz ticks) of the LAST launch that did work: [0] first
@@ -1668,6 +1692,7 @@ static int sweep_resident(hgibbs_ctx* h, const SweepPlan& pl, const double r0[2]
     p.pred = h->pred;
     p.early_advance = p.nranks > 1 ? 0 : h->res_early; // (several ranks: the replicas must send the same messages -- an advance that depends on when the dots arrive would not be)
     p.announce = h->res_announce;
+    p.bound_slack = h->res_bound_slack;
     p.wend_mask = pl.wend_mask;
     {
         // the predicted events of this sweep, in sweep order (read by the streaming workgroups and by the walker)
@@ -1797,6 +1822,7 @@ static int sweep_resident(hgibbs_ctx* h, const SweepPlan& pl, const double r0[2]
     s.refolds = st.refolds;
     s.pivots = st.pivots;
     s.predicted = st.predicted;
+    s.turned_down = st.turned_down;
     for (int i = 0; i < 16; ++i) s.ticks[i] = st.t[i];
     s.shader_mhz = st.wall_ticks ? 100.0 * (double)st.shader_ticks / (double)st.wall_ticks : 0.0;
     {

@@ -205,6 +205,8 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
  *                   workgroups then takes every group of sixteen columns once); 0 = at exactly `window` columns behind the cursor
  *   early_advance   second walker: a walk that runs out of dots moves the window on at once when at least this many positions have
  *                   passed (default 24; 0 = it waits)
+ *   bound_slack     second walker, for tests: taken off every threshold of the tabulated bound (default 0).  The bound only ever skips
+ *                   exact evaluations, so the chain does not depend on it; from 1000 on every position goes through the exact decision
  *   res_timeout_ms  resident engine: longest wait of any workgroup for another before the sweep is abandoned with an error
  *                   (default 2000); res_deadline_ms: the host's own deadline for the kernel (0 = derived from M, extended while the
  *                   walker's round counter moves)
@@ -228,6 +230,11 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
  *                   at most 1 GiB; a marker alone may exceed it)
  *   p2p, force_split, chunk, debug_timing, w_kernel_timing   transport selection and diagnostics */
 int hgibbs_set_option(hgibbs_t h, const char* name, int64_t value);
+/* The candidate search of the resident engine's second walker, on the host (no device needed; the device code calls the same
+ * functions).  masks[i], i < nch <= 4: the candidates of window slots 64 i .. 64 i + 63.  Writes the slots of all candidates in
+ * window order from cursor_slot (< 64 nch) on -- upwards, wrapping at 64 nch -- found as the walker finds them: the first, that one
+ * cleared, the next.  Returns their number, or -1 (more than cap, bad arguments). */
+int hgibbs_walker_search(const uint64_t* masks, uint32_t nch, uint32_t cursor_slot, uint32_t* slots, uint32_t cap);
 /* Statistics of the last sweep: launches, markers per launch, device time of
  * the sweep in ms (HIP events on the sweep's stream). */
 typedef struct {
@@ -256,7 +263,9 @@ typedef struct {
                                * [3] scan + draw [4] message + results + prefetch; streaming workgroup 0: [8] wait [9] update [10] Gram [11] stream */
     uint32_t refill;          /* resident engine: the streaming workgroups' form -- 1 = fused multiply-adds per individual (hg_resident.hip.h),
                                * 2 = integer matrix products over signed base-256 digits of eps (hg_streamer2.hip.h; option refill) */
-    uint32_t reserved_;
+    uint32_t turned_down;     /* resident engine, second walker: candidates of the tabulated bound that the exact decision found to be no event
+                               * (the bound is within about 1e-3 of the function: a handful per sweep; every marker without an event with
+                               * option bound_slack >= 1000) */
 } hgibbs_sweep_stats;
 int hgibbs_last_sweep_stats(hgibbs_t h, hgibbs_sweep_stats* out);
 /* measured streaming ceiling of this GPU: device-to-device copy of `bytes` (choose well above the 256 MB
