@@ -26,6 +26,7 @@ ABI_SYMBOLS = [
     "hgibbs_ld_mask", "hgibbs_last_ld_mask_ms", "hgibbs_ld_greedy", "hgibbs_ld_clump",
     "hgibbs_marker_dots", "hgibbs_last_marker_dots_ms", "hgibbs_marker_class_sums", "hgibbs_last_marker_class_sums_ms", "hgibbs_logit_null",
     "hgibbs_spa_roots", "hgibbs_last_spa_ms", "hgibbs_spa_pvalue",
+    "hgibbs_firth_fit", "hgibbs_last_firth_ms", "hgibbs_firth_stats",
     "hgibbs_king", "hgibbs_king_pairs", "hgibbs_king_pairs_get", "hgibbs_last_king_ms",
     "hgibbs_pca", "hgibbs_last_pca_ms", "hgibbs_region_var", "hgibbs_last_region_var_ms",
     "hgibbs_grm", "hgibbs_grm_info", "hgibbs_last_grm_ms",
@@ -62,6 +63,12 @@ class SpaRoot(C.Structure):
     """hgibbs_spa_root: index 0 is the tail at +|s|, index 1 the tail at -|s|"""
     _fields_ = [("t", C.c_double * 2), ("K", C.c_double * 2), ("K2", C.c_double * 2), ("k2_0", C.c_double), ("s_lo", C.c_double),
                 ("s_hi", C.c_double), ("iters", C.c_int32 * 2), ("flags", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
+class FirthRec(C.Structure):
+    """hgibbs_firth_rec: flags bit 0 converged, bit 1 degenerate"""
+    _fields_ = [("beta", C.c_double), ("K", C.c_double), ("K2", C.c_double), ("g", C.c_double), ("k2_0", C.c_double),
+                ("iters", C.c_int32), ("flags", C.c_uint32)]
 
 
 class HeForm(C.Structure):
@@ -237,6 +244,9 @@ def lib():
     L.hgibbs_spa_roots.argtypes = [vp, C.c_uint32, C_U32P, C.c_int, dp, dp, dp, dp, dp, C.POINTER(SpaRoot)]
     L.hgibbs_last_spa_ms.argtypes = [vp, dp]
     L.hgibbs_spa_pvalue.argtypes = [C.c_double, C.POINTER(SpaRoot), dp, dp, dp, C.POINTER(C.c_int)]
+    L.hgibbs_firth_fit.argtypes = [vp, C.c_uint32, C_U32P, C.c_int, dp, dp, dp, dp, dp, C.POINTER(FirthRec)]
+    L.hgibbs_last_firth_ms.argtypes = [vp, dp]
+    L.hgibbs_firth_stats.argtypes = [C.c_double, C.POINTER(FirthRec), dp, dp, dp, C.POINTER(C.c_int)]
     L.hgibbs_king.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32)]
     L.hgibbs_king_pairs.argtypes = [vp, C.c_double, C.POINTER(C.c_uint64)]
     L.hgibbs_king_pairs_get.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), dp]
@@ -366,6 +376,14 @@ def spa_pvalue(s, root):
     up, dn, p, ok = C.c_double(), C.c_double(), C.c_double(), C.c_int()
     check(lib().hgibbs_spa_pvalue(float(s), C.byref(root), C.byref(up), C.byref(dn), C.byref(p), C.byref(ok)))
     return up.value, dn.value, p.value, bool(ok.value)
+
+
+def firth_stats(s, rec):
+    """hgibbs_firth_stats (host only): the statistics of the score s from a FirthRec of Device.firth_fit.  Returns (lrt, se, p, valid);
+    the three numbers are NaN and valid False where the fit does not stand (the caller keeps the score test)."""
+    lrt, se, p, ok = C.c_double(), C.c_double(), C.c_double(), C.c_int()
+    check(lib().hgibbs_firth_stats(float(s), C.byref(rec), C.byref(lrt), C.byref(se), C.byref(p), C.byref(ok)))
+    return lrt.value, se.value, p.value, bool(ok.value)
 
 
 class Device:
@@ -771,6 +789,31 @@ class Device:
     def last_spa_ms(self):
         v = C.c_double()
         check(self.L.hgibbs_last_spa_ms(self.h, C.byref(v)))
+        return v.value
+
+    def firth_fit(self, markers, Z, mu, B, xv, s):
+        """Firth's penalised fit of the score test's one-parameter model for a list of markers (hgibbs_firth_fit): the arguments of
+        spa_roots.  Returns a ctypes array of nm FirthRec.  Option firth_piece: entries per piece of the list (0 = automatic)."""
+        markers = np.ascontiguousarray(markers, dtype=np.uint32).reshape(-1)
+        nm = markers.size
+        Z = np.asarray(Z, dtype=np.float64)
+        if Z.ndim != 2 or Z.shape[0] != self.n_local:
+            raise ValueError("Z must be (%d, q)" % self.n_local)
+        q = Z.shape[1]
+        Zc = np.ascontiguousarray(Z.T)  # column-major
+        mu = np.ascontiguousarray(mu, dtype=np.float64).reshape(-1)
+        B = np.ascontiguousarray(B, dtype=np.float64).reshape(-1)
+        xv = np.ascontiguousarray(xv, dtype=np.float64).reshape(-1)
+        s = np.ascontiguousarray(s, dtype=np.float64).reshape(-1)
+        if mu.size != self.n_local or B.size != nm * q or xv.size != nm * 4 or s.size != nm:
+            raise ValueError("mu must be (%d,), B (%d, %d), xv (%d, 4), s (%d,)" % (self.n_local, nm, q, nm, nm))
+        out = (FirthRec * max(nm, 1))()
+        check(self.L.hgibbs_firth_fit(self.h, nm, markers.ctypes.data_as(C_U32P), q, _dp(Zc), _dp(mu), _dp(B), _dp(xv), _dp(s), out))
+        return out
+
+    def last_firth_ms(self):
+        v = C.c_double()
+        check(self.L.hgibbs_last_firth_ms(self.h, C.byref(v)))
         return v.value
 
     def king(self, a0=0, acount=None, b0=0, bcount=None):

@@ -205,6 +205,8 @@ struct hgibbs_ctx {
     double mdots_ms = 0.0; // device time of the last hgibbs_marker_dots (scales, digits, products, rounding)
     double mclass_ms = 0.0; // device time of the last hgibbs_marker_class_sums (scales, digits, products, rounding)
     double spa_ms = 0.0;    // device time of the last hgibbs_spa_roots (the row-major copy of Z and the root kernel); 0 after a refused call
+    double firth_ms = 0.0;  // device time of the last hgibbs_firth_fit (the row-major copy of Z and every piece's kernel); 0 after a refused call
+    long long firth_piece = 0; // option firth_piece: entries of the list per piece of hgibbs_firth_fit (0 = automatic)
     int king_split = 0;    // option king_split: ranges of markers the workgroups of hgibbs_king split the k dimension into (0 = automatic)
     double king_ms = 0.0;  // device time of the last hgibbs_king / hgibbs_king_pairs (image, zeroing, products, every run of the list)
     int rvar_kb_max = 0;   // option rvar_kb_max: a marker set of more blocks of 64 than this takes hgibbs_region_var's large-set path (0 = SC_KB_MAX)
@@ -1404,6 +1406,9 @@ int hgibbs_set_option(hgibbs_t h, const char* name, int64_t value)
     } else if (!std::strcmp(name, "sparse_piece")) {
         if (value < 0) return fail("sparse_piece must be >= 0 bytes (0 = automatic)");
         h->sparse_piece = (long long)value;
+    } else if (!std::strcmp(name, "firth_piece")) {
+        if (value < 0) return fail("firth_piece must be >= 0 entries (0 = automatic)");
+        h->firth_piece = (long long)value;
     } else if (!std::strcmp(name, "chunk")) {
         h->chunk = (int)value;
     } else {
@@ -2209,6 +2214,7 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
 #include "hg_mdots.hip.h"
 #include "hg_mclass.hip.h"
 #include "hg_spa.hip.h"
+#include "hg_firth.hip.h"
 #include "hg_king.hip.h"
 #include "hg_pca.hip.h"
 #include "hg_grm.hip.h"

@@ -29,7 +29,9 @@
 // (hgibbs_logit_null) and the sums of its vectors over the rows of each genotype through hgibbs_marker_class_sums
 // (run_assoc_logistic), written to <dir>/<name>.assoc.logistic (or F).  `--assoc-spa [--assoc-spa-sd T]` with it replaces P by a
 // saddlepoint approximation for the markers whose score is more than T (default 2) SD from 0 and adds the columns P_NORM and SPA
-// (hgibbs_spa_roots, hgibbs_spa_pvalue).
+// (hgibbs_spa_roots, hgibbs_spa_pvalue).  `--assoc-firth [--assoc-firth-p T]` with it (and without --assoc-spa) refits
+// the markers whose score-test P is at most T (default 0.05) with Firth's penalised likelihood, writes BETA, SE, CHISQ and P from that fit
+// and adds the columns P_NORM, BETA_SCORE, SE_SCORE and FIRTH (hgibbs_firth_fit, hgibbs_firth_stats).
 //
 // `--king [--king-cutoff T] [--king-out F]` appended to a bayesMPI command line samples nothing either: it computes the KING-robust
 // kinship of every pair of the chain's rows with hgibbs_king_pairs (run_king) and writes the pairs with
@@ -141,6 +143,8 @@ struct Options { // src/options.hpp:20-138 (subset that reaches bayesMPI)
     bool assocLogistic = false;                      // --assoc-logistic: the logistic score test of a case/control phenotype
     bool assocSpa = false, assocSpaSdGiven = false;  // --assoc-spa: saddlepoint p-values for the markers whose score is beyond --assoc-spa-sd SD
     std::string assocSpaSd = "2";                    // --assoc-spa-sd
+    bool assocFirth = false, assocFirthPGiven = false; // --assoc-firth: Firth's penalised fit for the markers whose score-test P is at most --assoc-firth-p
+    std::string assocFirthP = "0.05";                // --assoc-firth-p
     bool king = false, kingCutoffGiven = false;      // --king: KING-robust kinship of the chain's rows; --king-cutoff given
     std::string kingCutoff = "0.0442", kingOut;      // --king-cutoff T (checked before the device), --king-out
     bool pca = false, pcaLoadings = false, pcaItersGiven = false, pcaTolGiven = false, pcaOutGiven = false; // --pca K; which --pca-* were given
@@ -298,6 +302,8 @@ Options parse(int argc, const char* argv[])
         else if (a == "--assoc-logistic") o.assocLogistic = true;
         else if (a == "--assoc-spa") o.assocSpa = true;
         else if (a == "--assoc-spa-sd") { o.assocSpaSd = need(i); o.assocSpaSdGiven = true; }
+        else if (a == "--assoc-firth") o.assocFirth = true;
+        else if (a == "--assoc-firth-p") { o.assocFirthP = need(i); o.assocFirthPGiven = true; }
         else if (a == "--king") o.king = true;
         else if (a == "--king-cutoff") {
             o.kingCutoff = need(i);
@@ -1924,7 +1930,10 @@ int run_assoc_logistic(const Options& opt, const Cohort& co, const std::vector<d
     const bool spa = opt.assocSpa;
     double spa_sd = 2.0;
     whole_num(opt.assocSpaSd, spa_sd);
-    std::fprintf(f, "CHR SNP BP A1 A2 FREQ N BETA SE CHISQ P N_CASE N_CTRL FREQ_CASE FREQ_CTRL%s\n", spa ? " P_NORM SPA" : "");
+    const bool firth = opt.assocFirth; // (never with spa: check_assoc_args)
+    double firth_p = 0.05;
+    whole_num(opt.assocFirthP, firth_p);
+    std::fprintf(f, "CHR SNP BP A1 A2 FREQ N BETA SE CHISQ P N_CASE N_CTRL FREQ_CASE FREQ_CTRL%s\n", spa ? " P_NORM SPA" : firth ? " P_NORM BETA_SCORE SE_SCORE FIRTH" : "");
 
     // the chain's rows and standardisation
     hgibbs_t dev = open_training(co, bed);
@@ -1953,13 +1962,15 @@ int run_assoc_logistic(const Options& opt, const Cohort& co, const std::vector<d
     // one hgibbs_marker_class_sums per run: U = [y - mu, w z_1 .. w z_qn, d]
     std::vector<double> U((size_t)K * N), sums, t(qn), v(qn);
     std::copy(d.begin(), d.end(), U.begin() + (size_t)(K - 1) * N);
-    unsigned long long written = 0, spa_n = 0, spa_valid = 0;
-    double spa_ms = 0.0;
-    std::vector<double> Uv, Vv, spa_B, spa_xv, spa_s;
+    // corr_*: the run's list of markers that get a correction, --assoc-spa's or --assoc-firth's (never both), and its counters
+    unsigned long long written = 0, corr_n = 0, corr_valid = 0;
+    double corr_ms = 0.0;
+    std::vector<double> Uv, Vv, corr_B, corr_xv, corr_s;
     std::vector<uint8_t> tested;
-    std::vector<long> spa_at; // the marker's entry in the run's list, or -1
-    std::vector<uint32_t> spa_mk;
+    std::vector<long> corr_at; // the marker's entry in the run's list, or -1
+    std::vector<uint32_t> corr_mk;
     std::vector<hgibbs_spa_root> spa_roots;
+    std::vector<hgibbs_firth_rec> firth_recs;
     for (size_t ru = 0; ru < nruns; ++ru) {
         const unsigned m0 = runs[ru], cnt = runs[ru + 1] - runs[ru];
         const Null& nm = nulls[gcol ? (size_t)cj[m0] : 0];
@@ -1973,15 +1984,16 @@ int run_assoc_logistic(const Options& opt, const Cohort& co, const std::vector<d
         double tms = 0.0;
         hg_check(hgibbs_last_marker_class_sums_ms(dev, &tms), "hgibbs_last_marker_class_sums_ms");
         ms += tms;
-        // the score test per marker; with --assoc-spa the markers beyond spa_sd standard deviations are listed for one hgibbs_spa_roots call
+        // the score test per marker; with --assoc-spa the markers beyond spa_sd standard deviations are listed for one hgibbs_spa_roots call,
+        // with --assoc-firth the markers whose P is at most firth_p for one hgibbs_firth_fit call
         Uv.assign(cnt, 0.0);
         Vv.assign(cnt, 0.0);
         tested.assign(cnt, 0);
-        spa_at.assign(cnt, -1);
-        spa_mk.clear();
-        spa_B.clear();
-        spa_xv.clear();
-        spa_s.clear();
+        corr_at.assign(cnt, -1);
+        corr_mk.clear();
+        corr_B.clear();
+        corr_xv.clear();
+        corr_s.clear();
         for (unsigned jj = 0; jj < cnt; ++jj) {
             const unsigned j = m0 + jj;
             const double m = mave[j], sd = mstd[j];
@@ -1999,27 +2011,36 @@ int run_assoc_logistic(const Options& opt, const Cohort& co, const std::vector<d
             tested[jj] = 1;
             Uv[jj] = xu(0);
             Vv[jj] = V;
-            if (spa && std::isfinite(V) && std::fabs(Uv[jj]) / std::sqrt(V) > spa_sd) {
+            if ((spa && std::isfinite(V) && std::fabs(Uv[jj]) / std::sqrt(V) > spa_sd) ||
+                (firth && std::isfinite(V) && std::erfc(std::sqrt(Uv[jj] * Uv[jj] / V / 2.0)) <= firth_p)) {
                 // b_j = (Z'WZ)^-1 Z'W x_j = L^-T v, the value of each genotype code, the score
                 for (int a = qn - 1; a >= 0; --a) {
                     double e = v[a];
                     for (int p = a + 1; p < qn; ++p) e -= nm.L[(size_t)p + (size_t)qn * a] * t[p];
                     t[a] = e / nm.L[(size_t)a + (size_t)qn * a];
                 }
-                spa_at[jj] = (long)spa_mk.size();
-                spa_mk.push_back(j);
-                spa_B.insert(spa_B.end(), t.begin(), t.end());
-                for (const double x : {(0.0 - m) * sd, (1.0 - m) * sd, (2.0 - m) * sd, 0.0}) spa_xv.push_back(x);
-                spa_s.push_back(Uv[jj]);
+                corr_at[jj] = (long)corr_mk.size();
+                corr_mk.push_back(j);
+                corr_B.insert(corr_B.end(), t.begin(), t.end());
+                for (const double x : {(0.0 - m) * sd, (1.0 - m) * sd, (2.0 - m) * sd, 0.0}) corr_xv.push_back(x);
+                corr_s.push_back(Uv[jj]);
             }
         }
-        spa_roots.resize(spa_mk.size());
-        if (!spa_mk.empty()) {
-            hg_check(hgibbs_spa_roots(dev, (uint32_t)spa_mk.size(), spa_mk.data(), qn, Zc.data(), nm.mu.data(), spa_B.data(), spa_xv.data(), spa_s.data(),
+        spa_roots.resize(spa ? corr_mk.size() : 0);
+        firth_recs.resize(firth ? corr_mk.size() : 0);
+        if (firth && !corr_mk.empty()) {
+            hg_check(hgibbs_firth_fit(dev, (uint32_t)corr_mk.size(), corr_mk.data(), qn, Zc.data(), nm.mu.data(), corr_B.data(), corr_xv.data(), corr_s.data(),
+                                      firth_recs.data()), "hgibbs_firth_fit");
+            double sms = 0.0;
+            hg_check(hgibbs_last_firth_ms(dev, &sms), "hgibbs_last_firth_ms");
+            corr_ms += sms;
+        }
+        if (spa && !corr_mk.empty()) {
+            hg_check(hgibbs_spa_roots(dev, (uint32_t)corr_mk.size(), corr_mk.data(), qn, Zc.data(), nm.mu.data(), corr_B.data(), corr_xv.data(), corr_s.data(),
                                       spa_roots.data()), "hgibbs_spa_roots");
             double sms = 0.0;
             hg_check(hgibbs_last_spa_ms(dev, &sms), "hgibbs_last_spa_ms");
-            spa_ms += sms;
+            corr_ms += sms;
         }
         for (unsigned jj = 0; jj < cnt; ++jj) {
             const unsigned j = m0 + jj;
@@ -2028,20 +2049,32 @@ int run_assoc_logistic(const Options& opt, const Cohort& co, const std::vector<d
             const double* S = &sums[(size_t)jj * K * 4];
             std::fprintf(f, "%s %s %lld %s %s %.12g %llu ", bim.chr[j].c_str(), bim.id[j].c_str(), bim.bp[j], bim.a1[j].c_str(), bim.a2[j].c_str(),
                          m / 2.0, called);
-            double p_norm = 0.0;
-            int spa_ok = -1; // -1 not applied, 0 applied and fell back to the normal P, 1 applied and valid
+            double p_norm = 0.0, beta_score = 0.0, se_score = 0.0;
+            int corr_ok = -1; // -1 not applied, 0 applied and fell back to the normal P (the score test), 1 applied and valid
             if (!tested[jj]) std::fprintf(f, "NA NA NA NA");
             else {
                 const double Uj = Uv[jj], V = Vv[jj], chisq = Uj * Uj / V;
                 double p = p_norm = std::erfc(std::sqrt(chisq / 2.0));
-                if (spa_at[jj] >= 0) {
+                double beta = beta_score = sd * Uj / V, se = se_score = sd / std::sqrt(V), stat = chisq;
+                if (firth && corr_at[jj] >= 0) {
+                    double lrt = 0.0, fse = 0.0, fp = 0.0;
+                    hg_check(hgibbs_firth_stats(Uj, &firth_recs[(size_t)corr_at[jj]], &lrt, &fse, &fp, &corr_ok), "hgibbs_firth_stats");
+                    if (corr_ok) {
+                        beta = sd * firth_recs[(size_t)corr_at[jj]].beta;
+                        se = sd * fse;
+                        stat = lrt;
+                        p = fp;
+                    }
+                    ++corr_n;
+                    corr_valid += corr_ok ? 1u : 0u;
+                } else if (corr_at[jj] >= 0) {
                     double ps = 0.0;
-                    hg_check(hgibbs_spa_pvalue(Uj, &spa_roots[(size_t)spa_at[jj]], nullptr, nullptr, &ps, &spa_ok), "hgibbs_spa_pvalue");
-                    if (spa_ok) p = ps;
-                    ++spa_n;
-                    spa_valid += spa_ok ? 1u : 0u;
+                    hg_check(hgibbs_spa_pvalue(Uj, &spa_roots[(size_t)corr_at[jj]], nullptr, nullptr, &ps, &corr_ok), "hgibbs_spa_pvalue");
+                    if (corr_ok) p = ps;
+                    ++corr_n;
+                    corr_valid += corr_ok ? 1u : 0u;
                 }
-                std::fprintf(f, "%.12g %.12g %.12g %.12g", sd * Uj / V, sd / std::sqrt(V), chisq, p);
+                std::fprintf(f, "%.12g %.12g %.12g %.12g", beta, se, stat, p);
             }
             // the sums of the case indicator are exact counts of the cases by genotype; the controls are the rest of the marker's stats
             const double* Sd = S + 4 * (K - 1);
@@ -2054,8 +2087,12 @@ int run_assoc_logistic(const Options& opt, const Cohort& co, const std::vector<d
             }
             if (spa) {
                 if (!tested[jj]) std::fprintf(f, " NA NA");
-                else if (spa_ok < 0) std::fprintf(f, " %.12g NA", p_norm);
-                else std::fprintf(f, " %.12g %d", p_norm, spa_ok);
+                else if (corr_ok < 0) std::fprintf(f, " %.12g NA", p_norm);
+                else std::fprintf(f, " %.12g %d", p_norm, corr_ok);
+            } else if (firth) {
+                if (!tested[jj]) std::fprintf(f, " NA NA NA NA");
+                else if (corr_ok < 0) std::fprintf(f, " %.12g %.12g %.12g NA", p_norm, beta_score, se_score);
+                else std::fprintf(f, " %.12g %.12g %.12g %d", p_norm, beta_score, se_score, corr_ok);
             }
             std::fprintf(f, "\n");
             ++written;
@@ -2066,8 +2103,11 @@ int run_assoc_logistic(const Options& opt, const Cohort& co, const std::vector<d
     std::printf("ASSOC  : wrote %llu rows to %s (%u cases, %u controls, %d iterations of %zu null models, %.3f ms on the device)\n", written, out.c_str(),
                 ncase, N - ncase, iters, nulls.size(), ms);
     if (spa)
-        std::printf("ASSOC  : SPA on %llu markers (|z| > %g): %llu valid, %llu fell back, %.3f ms on the device\n", spa_n, spa_sd, spa_valid, spa_n - spa_valid,
-                    spa_ms);
+        std::printf("ASSOC  : SPA on %llu markers (|z| > %g): %llu valid, %llu fell back, %.3f ms on the device\n", corr_n, spa_sd, corr_valid, corr_n - corr_valid,
+                    corr_ms);
+    if (firth)
+        std::printf("ASSOC  : Firth on %llu markers (P <= %g): %llu valid, %llu fell back, %.3f ms on the device\n", corr_n, firth_p, corr_valid, corr_n - corr_valid,
+                    corr_ms);
     return 0;
 }
 
@@ -3092,11 +3132,17 @@ void check_ld_args(const Options& opt)
 void check_assoc_args(const Options& opt)
 {
     if (!opt.assocLogistic)
-        if (const char* o = first_given({{"--assoc-spa", opt.assocSpa}, {"--assoc-spa-sd", opt.assocSpaSdGiven}})) fatal(std::string("FATAL  : ") + o + " needs --assoc-logistic");
+        if (const char* o = first_given({{"--assoc-spa", opt.assocSpa}, {"--assoc-spa-sd", opt.assocSpaSdGiven}, {"--assoc-firth", opt.assocFirth},
+                                         {"--assoc-firth-p", opt.assocFirthPGiven}}))
+            fatal(std::string("FATAL  : ") + o + " needs --assoc-logistic");
     if (opt.assocSpaSdGiven && !opt.assocSpa) fatal("FATAL  : --assoc-spa-sd needs --assoc-spa");
     double t = 0.0;
     if (opt.assocSpaSdGiven && (!whole_num(opt.assocSpaSd, t) || !std::isfinite(t) || !(t >= 0.1)))
         fatal("FATAL  : --assoc-spa-sd " + opt.assocSpaSd + ": the threshold must be a finite number of standard deviations >= 0.1 (the saddlepoint formula divides by a quantity that goes to 0 with the score)");
+    if (opt.assocFirthPGiven && !opt.assocFirth) fatal("FATAL  : --assoc-firth-p needs --assoc-firth");
+    if (opt.assocFirth && opt.assocSpa) fatal("FATAL  : --assoc-firth with --assoc-spa: choose one correction (each writes its own P)");
+    if (opt.assocFirthPGiven && (!whole_num(opt.assocFirthP, t) || !std::isfinite(t) || !(t > 0.0 && t <= 1.0)))
+        fatal("FATAL  : --assoc-firth-p " + opt.assocFirthP + ": the threshold must be a finite number in (0, 1] (the score-test P at or below which a marker is refitted)");
 }
 
 void check_king_args(const Options& opt)
@@ -3221,7 +3267,8 @@ void check_modes(const Options& opt, int nranks)
         {"--ld-window", opt.ldGiven, takes,
          first_given({{"--ld-out", !opt.ldOut.empty()}, {"--ld-window-kb", opt.ldKbGiven}, {"--ld-window-r2", opt.ldR2Given}, {"--ld-bin", opt.ldBin}})},
         {"--assoc", opt.assoc, takes, first_given({{"--assoc-out", !opt.assocOut.empty()}, {"--assoc-no-loco", opt.assocNoLoco}, {"--assoc-logistic", opt.assocLogistic},
-                                                   {"--assoc-spa", opt.assocSpa}, {"--assoc-spa-sd", opt.assocSpaSdGiven}})},
+                                                   {"--assoc-spa", opt.assocSpa}, {"--assoc-spa-sd", opt.assocSpaSdGiven},
+                                                   {"--assoc-firth", opt.assocFirth}, {"--assoc-firth-p", opt.assocFirthPGiven}})},
         {"--king", opt.king, takes, first_given({{"--king-out", !opt.kingOut.empty()}, {"--king-cutoff", opt.kingCutoffGiven}})},
         {"--pca", opt.pca, takes,
          first_given({{"--pca-iters", opt.pcaItersGiven}, {"--pca-tol", opt.pcaTolGiven}, {"--pca-out", opt.pcaOutGiven}, {"--pca-loadings", opt.pcaLoadings}})},

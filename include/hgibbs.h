@@ -228,6 +228,8 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
  *   rowsums_ranges  hgibbs_row_sums: at most this many ranges of markers split over workgroups, 0..65535 (0 = automatic)
  *   sparse_piece    hgibbs_sparse_get: bytes of index buffers per piece of markers (0 = automatic: a quarter of the free device memory,
  *                   at most 1 GiB; a marker alone may exceed it)
+ *   firth_piece     hgibbs_firth_fit: entries of the list per piece (0 = automatic: as many as a quarter of the free device memory holds
+ *                   rows of n_local doubles for; a piece holds at least 1 entry and at most 2^24; a negative value is refused)
  *   p2p, force_split, chunk, debug_timing, w_kernel_timing   transport selection and diagnostics */
 int hgibbs_set_option(hgibbs_t h, const char* name, int64_t value);
 /* The candidate search of the resident engine's second walker, on the host (no device needed; the device code calls the same
@@ -505,6 +507,49 @@ int hgibbs_last_spa_ms(hgibbs_t h, double* ms);   /* every kernel of the last ca
  * valid; p = p_upper + p_lower and valid = 1 when both are valid, else p = NaN and valid = 0 (valid may be NULL): the caller keeps
  * the normal approximation then.  Refused: a null r or p. */
 int hgibbs_spa_pvalue(double s, const hgibbs_spa_root* r, double* p_upper, double* p_lower, double* p, int* valid);
+
+/* ---- Firth's penalised fit of the logistic score test's one-parameter model, per listed marker */
+/* One record per entry of a marker list. */
+typedef struct {
+    double beta;       /* the stationary point of l* the rule found, in units of a */
+    double K, K2;      /* K(beta), K''(beta) from the closing pass (0 unless converged) */
+    double g;          /* the modified score at the last iterated point */
+    double k2_0;       /* K''(0) = the score test's V */
+    int32_t iters;     /* passes after pass 0, the closing one included */
+    uint32_t flags;    /* bit 0 converged; bit 1 degenerate (k2_0 not finite or <= 0: not iterated, every other field 0) */
+} hgibbs_firth_rec;
+
+/* The inputs are those of hgibbs_spa_roots, entry by entry (markers, Z, mu, B, xv; a_i, u = a_i t, p_i and the stable form of the terms
+ * as there), and s[e] is the entry's score sum_i a_i (d_i - mu_i): the operator never sees d.  In the model
+ * logit P(d_i = 1) = logit(mu_i) + beta a_i the log-likelihood ratio is l(t) - l(0) = t s - K(t), and Firth's penalised one is
+ * l*(t) - l*(0) = t s - K(t) + log(K''(t) / K''(0)) / 2.  With v = p (1 - p),
+ *   K''' = sum_i a_i^3 v_i (1 - 2 p_i),  K'''' = sum_i a_i^4 v_i (1 - 6 v_i),
+ *   g(t) = s - K' + K''' / (2 K''),  g'(t) = -K'' + (K'''' / K'' - (K''' / K'')^2) / 2.
+ * Root rule, Newton on g with a bracket: pass 0 is at t = 0 and gives k2_0 and scale = 1 / sqrt(k2_0) (a k2_0 that is not finite or not
+ * positive sets the degenerate flag and ends the entry); lo = -inf, hi = +inf, tg = 0.  When g and g' are finite at t: tg = t, g > 0
+ * sets lo = t, g < 0 sets hi = t, the proposal is t' = t - g / g'; first the stop rule |t' - t| <= 1e-9 max(|t|, scale) (the entry takes
+ * t', one closing pass gives K(t') and K''(t'), the converged flag is set), only then the safeguard (a t' not strictly inside (lo, hi)
+ * becomes the midpoint when both ends are finite, else 2 t, or +-scale with g's sign when t = 0).  When g or g' is not finite at t (the
+ * probabilities have saturated): the bracket end on t's side of tg becomes t, the next point is (t + tg) / 2, no sign is taken.  At
+ * most 64 passes after pass 0, the closing one included; an entry still open then has no flag, and beta is the point the rule would
+ * have taken next.  l* can have more than one stationary point: the record is the one this rule reaches from 0.  Any finite s is
+ * taken; for an s outside the range of K' (section 26's [s_lo, s_hi]), which no phenotype gives, l* need not have a maximum and only
+ * the bound on the passes is promised.
+ * Every sum over the rows runs in hgibbs_spa_roots' order, which depends on n_local only.  Pass 0 writes a_i to a scratch row per
+ * entry (n_local doubles) that the later passes read; the list is processed in pieces of entries so that the scratch fits: option
+ * firth_piece.  The records are bit-identical for any firth_piece, any chunking of the list, any position of an entry in it, duplicates
+ * and repeats.  nm = 0 returns 0 and touches nothing.  Refused: a null argument, q outside 1..64, a marker index >= M, a non-finite
+ * entry of Z, B, xv or s, a mu not strictly inside (0, 1), several ranks, a handle without genotypes, buffers that do not fit in free
+ * device memory. */
+int hgibbs_firth_fit(hgibbs_t h, uint32_t nm, const uint32_t* markers, int q, const double* Z /* n_local x q column-major, as hgibbs_logit_null */,
+                     const double* mu, const double* B /* nm x q */, const double* xv /* nm x 4 */, const double* s /* nm */, hgibbs_firth_rec* out);
+int hgibbs_last_firth_ms(hgibbs_t h, double* ms);   /* every kernel of the last call, not the host copies; 0 after a refused call */
+
+/* The statistics of a record of hgibbs_firth_fit (host only: no handle, no device; hg_firth.cpp).
+ * lrt = 2 (beta s - K + log(K2 / k2_0) / 2), a value in [-1e-9, 0) becomes 0;  se = 1 / sqrt(K2);  p = erfc(sqrt(lrt / 2)).
+ * valid = 1 iff the record is converged and not degenerate, K2 > 0 and lrt is finite and >= 0 after the clamp; otherwise valid = 0 and
+ * lrt, se and p are NaN: the caller keeps the score test.  lrt, se and valid may be NULL.  Refused: a null r or p. */
+int hgibbs_firth_stats(double s, const hgibbs_firth_rec* r, double* lrt, double* se, double* p, int* valid);
 
 /* ---- KING-robust kinship of the loaded rows -------- */
 /* For rows a, b of the handle (the n_local rows kept at hgibbs_load_bed), over the markers where both calls are present, five exact

@@ -1,0 +1,200 @@
+"""hgibbs_firth_fit against the NumPy restatement of tests/firth_restate.py: flags, the fitted effect, K and K'' there, K''(0) and the
+p-value of hgibbs_firth_stats on a grid of cohort sizes and null-model widths; bit-identity across chunkings, orders, duplicates, repeats
+and the option firth_piece; every refusal, each followed by a call that works."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from hydra_amd import capi, synth
+
+import firth_restate as F
+
+pytestmark = pytest.mark.gpu
+
+# Ten times the largest relative difference between the float64 and the longdouble restatement over the entries of this grid, as
+# tests/test_firth_restatement_cpu.py prints it.  Measured on the CPU: beta 8.24e-13, K 9.86e-13, K'' 1.87e-12, p 8.58e-14.  The margin
+# of ten covers the device's other summation order and the last places of its expm1, log1p and division.
+TOL_BETA = 8.3e-12
+TOL_K = 9.9e-12
+TOL_K2 = 1.9e-11
+TOL_P = 8.6e-13
+NE = F.GRID_M + 1
+
+
+def device(geno):
+    dev = capi.Device(0)
+    dev.load_bed(synth.pack_bed_columns(geno), geno.shape[1])
+    return dev
+
+
+def call(dev, case, idx):
+    idx = np.asarray(idx)
+    return dev.firth_fit(case["markers"][idx], case["Z"], case["mu"], case["B"][idx], case["xv"][idx], case["s"][idx])
+
+
+def raw(recs, k=None):
+    b = bytes(recs)
+    size = C.sizeof(capi.FirthRec)
+    return b if k is None else b[k * size:(k + 1) * size]
+
+
+def close(got, want, tol):
+    return abs(got - float(want)) <= tol * abs(float(want))
+
+
+def test_the_record_is_48_bytes():
+    assert C.sizeof(capi.FirthRec) == 48
+
+
+@pytest.mark.parametrize("n", F.GRID_N)
+@pytest.mark.parametrize("q", F.GRID_Q)
+def test_grid_against_the_restatement(n, q):
+    case = F.fit_case(n, q)
+    ref = F.case_fits(case)
+    dev = device(case["geno"])
+    everything = np.arange(NE)
+    recs = call(dev, case, everything)
+    ms = dev.last_firth_ms()
+    print("n %d q %d: %d entries in %.3f ms on the device" % (n, q, NE, ms))
+    assert ms > 0.0
+    worst = dict(beta=0.0, K=0.0, K2=0.0, p=0.0)
+    for e, want in enumerate(ref):
+        got = recs[e]
+        assert got.flags == want["flags"], (e, got.flags, want["flags"])
+        if got.flags & F.DEGENERATE:
+            assert e == F.FLAT and raw(recs, e) == bytes(40) + (0).to_bytes(4, "little") + (2).to_bytes(4, "little")
+            assert capi.firth_stats(case["s"][e], got)[3] is False
+            continue
+        assert got.flags == F.CONVERGED and 1 <= got.iters <= F.PASSES, (e, got.iters)
+        assert close(got.k2_0, want["k2_0"], 1e-12), e
+        gp, wp = capi.firth_stats(case["s"][e], got), F.stats(case["s"][e], want)
+        for name, a, b in (("beta", got.beta, want["beta"]), ("K", got.K, want["K"]), ("K2", got.K2, want["K2"]), ("p", gp[2], wp[2])):
+            worst[name] = max(worst[name], F.rel(a, b))
+        assert close(got.beta, want["beta"], TOL_BETA), (e, got.beta, want["beta"])
+        assert close(got.K, want["K"], TOL_K), (e, got.K, want["K"])
+        assert close(got.K2, want["K2"], TOL_K2), (e, got.K2, want["K2"])
+        assert gp[3] and wp[3], e
+        assert close(gp[2], wp[2], TOL_P), (e, gp, wp)
+    print("largest relative difference device / restatement: beta %.3g, K %.3g, K2 %.3g, p %.3g" % (worst["beta"], worst["K"], worst["K2"], worst["p"]))
+    # bit-identity: reversed, in calls of 1 and of 7, repeated, a duplicate index, and pieces of 1, of 3 and automatic
+    whole = raw(recs)
+    rev = call(dev, case, everything[::-1])
+    assert all(raw(rev, NE - 1 - e) == raw(recs, e) for e in range(NE))
+    assert b"".join(raw(call(dev, case, [e])) for e in range(0, NE, 9)) == b"".join(raw(recs, e) for e in range(0, NE, 9))
+    assert b"".join(raw(call(dev, case, everything[k:k + 7])) for k in range(0, NE, 7)) == whole
+    assert raw(call(dev, case, everything)) == whole
+    dup = call(dev, case, [11, 40, 11])
+    assert raw(dup, 0) == raw(dup, 2) == raw(recs, 11) and raw(dup, 1) == raw(recs, 40)
+    for piece in (1, 3, 0):
+        dev.set_option("firth_piece", piece)
+        assert raw(call(dev, case, everything)) == whole, piece
+    dev.close()
+
+
+def test_refusals_leave_the_handle_usable():
+    case = F.fit_case(261, 5)
+    dev = device(case["geno"])
+    n, q = case["Z"].shape
+    idx = np.arange(8)
+    good = dict(markers=idx, Z=case["Z"], mu=case["mu"], B=case["B"][idx], xv=case["xv"][idx], s=case["s"][idx])
+    want = raw(dev.firth_fit(**good))
+
+    def spoiled(name, at, value):
+        a = np.array(good[name], dtype=np.float64 if name != "markers" else np.uint32)
+        a[at] = value
+        return dict(good, **{name: a})
+
+    def usable():
+        sums = dev.marker_class_sums(np.ones((1, n)))
+        assert sums.shape == (F.GRID_M, 1, 4) and np.all(sums.sum(axis=2) == n)
+        assert raw(dev.firth_fit(**good)) == want
+        assert dev.last_firth_ms() > 0.0
+
+    bad = [
+        (spoiled("markers", 3, F.GRID_M), "markers[3] = 64 out of range (M = 64)"),
+        (spoiled("Z", (5, 2), np.nan), "Z[5][2] = nan is not finite"),
+        (spoiled("B", (1, 4), np.inf), "B[1][4] = inf is not finite"),
+        (spoiled("xv", (2, 3), np.nan), "xv[2][3] = nan is not finite"),
+        (spoiled("s", 7, -np.inf), "s[7] = -inf is not finite"),
+        (spoiled("mu", 9, 0.0), "mu[9] = 0 is not strictly inside (0, 1)"),
+        (spoiled("mu", 9, 1.0), "mu[9] = 1 is not strictly inside (0, 1)"),
+        (spoiled("mu", 9, np.nan), "mu[9] = nan is not strictly inside (0, 1)"),
+        (dict(good, Z=np.ones((n, 65)), B=np.zeros((8, 65))), "q = 65, must be in [1, 64]"),
+    ]
+    for args, msg in bad:
+        with pytest.raises(capi.HgError, match="hgibbs_firth_fit: "):
+            try:
+                dev.firth_fit(**args)
+            except capi.HgError as e:
+                assert msg in str(e), (msg, str(e))
+                raise
+        assert dev.last_firth_ms() == 0.0  # 0 after a refused call
+        usable()
+    # the option takes a number of entries from 0
+    with pytest.raises(capi.HgError, match="firth_piece must be >= 0"):
+        dev.set_option("firth_piece", -1)
+    usable()
+    # null arguments and q = 0 straight through the ABI
+    L, dp = capi.lib(), C.POINTER(C.c_double)
+    out = (capi.FirthRec * 8)()
+    ptr = dict(markers=idx.astype(np.uint32).ctypes.data_as(capi.C_U32P))
+    keep = {k: np.ascontiguousarray(good[k].T if k == "Z" else good[k], dtype=np.float64) for k in ("Z", "mu", "B", "xv", "s")}
+    ptr.update({k: v.ctypes.data_as(dp) for k, v in keep.items()})
+    order = ("Z", "mu", "B", "xv", "s")
+    for missing in ("markers",) + order + ("out",):
+        a = dict(ptr, out=out)
+        a[missing] = None
+        assert L.hgibbs_firth_fit(dev.h, 8, a["markers"], q, *[a[k] for k in order], a["out"]) != 0
+        assert "hgibbs_firth_fit: null argument" in L.hgibbs_last_error().decode()
+        assert dev.last_firth_ms() == 0.0
+        usable()
+    assert L.hgibbs_firth_fit(dev.h, 8, ptr["markers"], 0, *[ptr[k] for k in order], out) != 0
+    assert "hgibbs_firth_fit: q = 0, must be in [1, 64]" in L.hgibbs_last_error().decode()
+    assert dev.last_firth_ms() == 0.0
+    usable()
+    assert L.hgibbs_firth_fit(None, 8, ptr["markers"], q, *[ptr[k] for k in order], out) != 0
+    assert "hgibbs_firth_fit: null handle" in L.hgibbs_last_error().decode()
+    assert L.hgibbs_last_firth_ms(dev.h, None) != 0 and L.hgibbs_last_firth_ms(None, C.byref(C.c_double())) != 0
+    # an empty list touches nothing
+    before = raw(out)
+    assert L.hgibbs_firth_fit(dev.h, 0, ptr["markers"], q, *[ptr[k] for k in order], out) == 0 and raw(out) == before
+    usable()
+    dev.close()
+    # a handle without genotypes
+    empty = capi.Device(0)
+    assert L.hgibbs_firth_fit(empty.h, 8, ptr["markers"], q, *[ptr[k] for k in order], out) != 0
+    assert "hgibbs_firth_fit: no genotypes loaded on this handle" in L.hgibbs_last_error().decode()
+    assert empty.last_firth_ms() == 0.0
+    empty.close()
+
+
+def test_refuses_what_does_not_fit_in_device_memory():
+    """The scratch is one row of n_local doubles per entry of a piece.  With automatic pieces it never outgrows the device; an explicit
+    firth_piece can: six million entries in one piece on 8197 rows need 393 GB of it, more than any device this library runs on holds
+    (an MI355X has 288 GB).  The host's share is 0.6 GB of list and records."""
+    case = F.fit_case(8197, 1)
+    dev = device(case["geno"])
+    good = dict(markers=np.arange(8), Z=case["Z"], mu=case["mu"], B=case["B"][:8], xv=case["xv"][:8], s=case["s"][:8])
+    want = raw(dev.firth_fit(**good))
+    assert dev.last_firth_ms() > 0.0
+    nm = 6_000_000
+    dev.set_option("firth_piece", nm)
+    with pytest.raises(capi.HgError, match=r"hgibbs_firth_fit: 6000000 markers against a null model of 1 columns and pieces of 6000000 entries need "
+                                           r"375801\.3 MiB, [0-9.]+ MiB of device memory are free"):
+        dev.firth_fit(np.zeros(nm, dtype=np.uint32), case["Z"], case["mu"], np.zeros((nm, 1)), np.ones((nm, 4)), np.zeros(nm))
+    assert dev.last_firth_ms() == 0.0
+    assert raw(dev.firth_fit(**good)) == want and dev.last_firth_ms() > 0.0  # (eight entries fit in a piece of six million)
+    dev.set_option("firth_piece", 0)
+    assert raw(dev.firth_fit(**good)) == want
+    dev.close()
+
+
+def test_several_ranks_refused():
+    case = F.fit_case(261, 1)
+    dev = capi.Device(0)
+    dev.comm_init_external(2, 0, lambda arr: None)  # a stub world of two ranks
+    dev.load_bed(synth.pack_bed_columns(case["geno"]), 261, row_begin=0, row_end=130, n_global=261)
+    with pytest.raises(capi.HgError, match="hgibbs_firth_fit: one rank only"):
+        dev.firth_fit([0], case["Z"][:dev.n_local], case["mu"][:dev.n_local], case["B"][:1], case["xv"][:1], case["s"][:1])
+    assert dev.last_firth_ms() == 0.0
