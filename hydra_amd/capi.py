@@ -25,6 +25,7 @@ ABI_SYMBOLS = [
     "hgibbs_ld_scores", "hgibbs_last_ld_scores_ms",
     "hgibbs_ld_mask", "hgibbs_last_ld_mask_ms", "hgibbs_ld_greedy", "hgibbs_ld_clump",
     "hgibbs_marker_dots", "hgibbs_last_marker_dots_ms", "hgibbs_marker_class_sums", "hgibbs_last_marker_class_sums_ms", "hgibbs_logit_null",
+    "hgibbs_set_gram", "hgibbs_last_set_gram_ms", "hgibbs_set_tests",
     "hgibbs_spa_roots", "hgibbs_last_spa_ms", "hgibbs_spa_pvalue",
     "hgibbs_firth_fit", "hgibbs_last_firth_ms", "hgibbs_firth_stats",
     "hgibbs_king", "hgibbs_king_pairs", "hgibbs_king_pairs_get", "hgibbs_last_king_ms",
@@ -63,6 +64,12 @@ class SpaRoot(C.Structure):
     """hgibbs_spa_root: index 0 is the tail at +|s|, index 1 the tail at -|s|"""
     _fields_ = [("t", C.c_double * 2), ("K", C.c_double * 2), ("K2", C.c_double * 2), ("k2_0", C.c_double), ("s_lo", C.c_double),
                 ("s_hi", C.c_double), ("iters", C.c_int32 * 2), ("flags", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
+class SetResult(C.Structure):
+    """hgibbs_set_result"""
+    _fields_ = [("q", C.c_double), ("p_skat", C.c_double), ("t_burden", C.c_double), ("p_burden", C.c_double), ("lam_sum", C.c_double),
+                ("lam_max", C.c_double), ("neig", C.c_int32), ("skat_ok", C.c_int32)]
 
 
 class FirthRec(C.Structure):
@@ -240,6 +247,9 @@ def lib():
     L.hgibbs_last_marker_dots_ms.argtypes = [vp, dp]
     L.hgibbs_marker_class_sums.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_int, dp, dp]
     L.hgibbs_last_marker_class_sums_ms.argtypes = [vp, dp]
+    L.hgibbs_set_gram.argtypes = [vp, C.c_uint32, C_U64P, C_U32P, dp, dp, dp]
+    L.hgibbs_last_set_gram_ms.argtypes = [vp, dp]
+    L.hgibbs_set_tests.argtypes = [C.c_uint32, dp, dp, dp, C.POINTER(SetResult)]
     L.hgibbs_logit_null.argtypes = [C.c_uint32, C.c_int, dp, dp, dp, dp, dp, dp, C.POINTER(C.c_int)]
     L.hgibbs_spa_roots.argtypes = [vp, C.c_uint32, C_U32P, C.c_int, dp, dp, dp, dp, dp, C.POINTER(SpaRoot)]
     L.hgibbs_last_spa_ms.argtypes = [vp, dp]
@@ -376,6 +386,20 @@ def spa_pvalue(s, root):
     up, dn, p, ok = C.c_double(), C.c_double(), C.c_double(), C.c_int()
     check(lib().hgibbs_spa_pvalue(float(s), C.byref(root), C.byref(up), C.byref(dn), C.byref(p), C.byref(ok)))
     return up.value, dn.value, p.value, bool(ok.value)
+
+
+def set_tests(U, Phi, a):
+    """hgibbs_set_tests (host only): burden and SKAT statistics of one marker set from its scores U (m,), their covariance Phi (m, m)
+    and the weights a (m,).  Returns a SetResult."""
+    U = np.ascontiguousarray(U, dtype=np.float64).reshape(-1)
+    m = U.size
+    Phi = np.ascontiguousarray(Phi, dtype=np.float64)
+    a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+    if Phi.shape != (m, m) or a.size != m:
+        raise ValueError("set_tests: Phi must be (%d, %d) and a (%d,)" % (m, m, m))
+    r = SetResult()
+    check(lib().hgibbs_set_tests(m, _dp(U), _dp(Phi), _dp(a), C.byref(r)))
+    return r
 
 
 def firth_stats(s, rec):
@@ -764,6 +788,38 @@ class Device:
     def last_marker_class_sums_ms(self):
         v = C.c_double()
         check(self.L.hgibbs_last_marker_class_sums_ms(self.h, C.byref(v)))
+        return v.value
+
+    def set_gram(self, sets, w, raw=False):
+        """Row-weighted Gram matrices of marker sets (hgibbs_set_gram): sets is a list of index lists, w (n_local,) the non-negative
+        row weights.  Returns a list of (m_s, m_s) arrays sum_i w_i x_ia x_ib, and with raw=True also a list of (m_s, m_s, 3) arrays
+        GG, GC, CC, each rounded once.  Option sgram_split: ranges of individuals split over workgroups (0 = automatic)."""
+        lists = [np.ascontiguousarray(x, dtype=np.uint32).reshape(-1) for x in sets]
+        off = np.zeros(len(lists) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([x.size for x in lists], dtype=np.uint64)
+        idx = np.ascontiguousarray(np.concatenate(lists) if lists else np.zeros(0), dtype=np.uint32)
+        if idx.size == 0:
+            idx = np.zeros(1, dtype=np.uint32)
+        w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+        if w.size != self.n_local:
+            raise ValueError("w must be (%d,)" % self.n_local)
+        E = int(sum(int(x.size) ** 2 for x in lists))
+        out = np.zeros(max(E, 1))
+        rr = np.zeros(max(E, 1) * 3) if raw else None
+        check(self.L.hgibbs_set_gram(self.h, len(lists), off.ctypes.data_as(C_U64P), idx.ctypes.data_as(C_U32P), _dp(w), _dp(out),
+                                     _dp(rr) if raw else None))
+        outs, raws, b = [], [], 0
+        for x in lists:
+            m = int(x.size)
+            outs.append(out[b:b + m * m].reshape(m, m).copy())
+            if raw:
+                raws.append(rr[3 * b:3 * (b + m * m)].reshape(m, m, 3).copy())
+            b += m * m
+        return (outs, raws) if raw else outs
+
+    def last_set_gram_ms(self):
+        v = C.c_double()
+        check(self.L.hgibbs_last_set_gram_ms(self.h, C.byref(v)))
         return v.value
 
     def spa_roots(self, markers, Z, mu, B, xv, s):

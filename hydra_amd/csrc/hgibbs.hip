@@ -204,6 +204,8 @@ struct hgibbs_ctx {
     int mdots_split = 0;   // option mdots_split: ranges of individuals the workgroups of hgibbs_marker_dots split the columns into (0 = automatic)
     double mdots_ms = 0.0; // device time of the last hgibbs_marker_dots (scales, digits, products, rounding)
     double mclass_ms = 0.0; // device time of the last hgibbs_marker_class_sums (scales, digits, products, rounding)
+    int sgram_split = 0;    // option sgram_split: ranges of individuals the workgroups of hgibbs_set_gram split the columns into (0 = automatic)
+    double sgram_ms = 0.0;  // device time of the last hgibbs_set_gram (scale, digits, products, rounding); 0 after a refused call
     double spa_ms = 0.0;    // device time of the last hgibbs_spa_roots (the row-major copy of Z and the root kernel); 0 after a refused call
     double firth_ms = 0.0;  // device time of the last hgibbs_firth_fit (the row-major copy of Z and every piece's kernel); 0 after a refused call
     long long firth_piece = 0; // option firth_piece: entries of the list per piece of hgibbs_firth_fit (0 = automatic)
@@ -1325,6 +1327,9 @@ int hgibbs_set_option(hgibbs_t h, const char* name, int64_t value)
     } else if (!std::strcmp(name, "mdots_split")) {
         if (value < 0 || value > 65535) return fail("mdots_split must be in [0,65535] (0 = automatic)");
         h->mdots_split = (int)value;
+    } else if (!std::strcmp(name, "sgram_split")) {
+        if (value < 0 || value > 65535) return fail("sgram_split must be in [0,65535] (0 = automatic)");
+        h->sgram_split = (int)value;
     } else if (!std::strcmp(name, "rvar_kb_max")) {
         if (value < 0 || value > 32768) return fail("rvar_kb_max must be in [0,32768] (0 = the i32 headroom, 32768 blocks of 64 markers)");
         h->rvar_kb_max = (int)value;
@@ -2213,6 +2218,7 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
 #include "hg_ldmask.hip.h"
 #include "hg_mdots.hip.h"
 #include "hg_mclass.hip.h"
+#include "hg_sgram.hip.h"
 #include "hg_spa.hip.h"
 #include "hg_firth.hip.h"
 #include "hg_king.hip.h"

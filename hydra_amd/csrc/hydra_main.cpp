@@ -32,6 +32,9 @@
 // (hgibbs_spa_roots, hgibbs_spa_pvalue).  `--assoc-firth [--assoc-firth-p T]` with it (and without --assoc-spa) refits
 // the markers whose score-test P is at most T (default 0.05) with Firth's penalised likelihood, writes BETA, SE, CHISQ and P from that fit
 // and adds the columns P_NORM, BETA_SCORE, SE_SCORE and FIRTH (hgibbs_firth_fit, hgibbs_firth_stats).
+// `--assoc-sets FILE [--assoc-set-beta A B] [--assoc-set-maf X] [--assoc-set-out F]` with --assoc-logistic also tests the marker sets of
+// FILE (SETNAME SNPID, --pve-sets' format): burden and SKAT from the plain scores and their joint covariance under the null model
+// (hgibbs_set_gram, hgibbs_set_tests), written to <dir>/<name>.assoc.sets (or F).
 //
 // `--king [--king-cutoff T] [--king-out F]` appended to a bayesMPI command line samples nothing either: it computes the KING-robust
 // kinship of every pair of the chain's rows with hgibbs_king_pairs (run_king) and writes the pairs with
@@ -145,6 +148,9 @@ struct Options { // src/options.hpp:20-138 (subset that reaches bayesMPI)
     std::string assocSpaSd = "2";                    // --assoc-spa-sd
     bool assocFirth = false, assocFirthPGiven = false; // --assoc-firth: Firth's penalised fit for the markers whose score-test P is at most --assoc-firth-p
     std::string assocFirthP = "0.05";                // --assoc-firth-p
+    std::string assocSets, assocSetOut;              // --assoc-sets FILE: burden and SKAT of the file's marker sets; --assoc-set-out
+    std::string assocSetA = "1", assocSetB = "25", assocSetMaf = "0.5"; // --assoc-set-beta A B, --assoc-set-maf X as given
+    bool assocSetBetaGiven = false, assocSetMafGiven = false;
     bool king = false, kingCutoffGiven = false;      // --king: KING-robust kinship of the chain's rows; --king-cutoff given
     std::string kingCutoff = "0.0442", kingOut;      // --king-cutoff T (checked before the device), --king-out
     bool pca = false, pcaLoadings = false, pcaItersGiven = false, pcaTolGiven = false, pcaOutGiven = false; // --pca K; which --pca-* were given
@@ -304,6 +310,10 @@ Options parse(int argc, const char* argv[])
         else if (a == "--assoc-spa-sd") { o.assocSpaSd = need(i); o.assocSpaSdGiven = true; }
         else if (a == "--assoc-firth") o.assocFirth = true;
         else if (a == "--assoc-firth-p") { o.assocFirthP = need(i); o.assocFirthPGiven = true; }
+        else if (a == "--assoc-sets") o.assocSets = need(i);
+        else if (a == "--assoc-set-beta") { o.assocSetA = need(i); o.assocSetB = need(i); o.assocSetBetaGiven = true; }
+        else if (a == "--assoc-set-maf") { o.assocSetMaf = need(i); o.assocSetMafGiven = true; }
+        else if (a == "--assoc-set-out") o.assocSetOut = need(i);
         else if (a == "--king") o.king = true;
         else if (a == "--king-cutoff") {
             o.kingCutoff = need(i);
@@ -1864,6 +1874,12 @@ int run_assoc(const Options& opt, const Cohort& co, const std::vector<double>& y
     return 0;
 }
 
+struct MarkerSets {
+    std::vector<std::string> name;
+    std::vector<std::vector<uint32_t>> idx; // markers of each set, increasing
+};
+MarkerSets read_sets_file(const std::string& path, const std::string& bedFile, const BimRows& bim, unsigned Mtot, size_t* unknown = nullptr);
+
 // ---- --assoc --assoc-logistic: the logistic score test of a case/control phenotype ----
 int run_assoc_logistic(const Options& opt, const Cohort& co, const std::vector<double>& y_raw, const std::vector<double>& covX, int C)
 {
@@ -1923,6 +1939,54 @@ int run_assoc_logistic(const Options& opt, const Cohort& co, const std::vector<d
     std::vector<Null> nulls(gcol ? nchrom : 1);
     fit(q, nulls[0]); // (with a LOCO predictor this one only refuses early; the fits per chromosome follow)
     int iters = gcol ? 0 : nulls[0].iters;
+
+    // --assoc-sets: the file, the weights' parameters and the sets' places, each refused before any device call
+    const bool sets_on = !opt.assocSets.empty();
+    const std::string sets_out = opt.assocSetOut.empty() ? base + ".assoc.sets" : opt.assocSetOut;
+    MarkerSets msets;
+    double setA = 1.0, setB = 25.0, setMaf = 0.5;
+    std::vector<long> mem_at;       // per marker: its slot among the sets' members, or -1
+    std::vector<size_t> set_run;    // per set: the run of its markers (nruns: none of its ids was found)
+    size_t nmem = 0;
+    if (sets_on) {
+        size_t unknown = 0, listed = 0;
+        msets = read_sets_file(opt.assocSets, opt.bedFile, bim, co.Mtot, &unknown);
+        if (!whole_num(opt.assocSetA, setA) || !whole_num(opt.assocSetB, setB) || !std::isfinite(setA) || !std::isfinite(setB) || !(setA > 0.0 && setB > 0.0))
+            fatal("FATAL  : --assoc-set-beta " + opt.assocSetA + " " + opt.assocSetB + ": both parameters of the weights' beta density must be finite numbers > 0");
+        if (!whole_num(opt.assocSetMaf, setMaf) || !std::isfinite(setMaf) || !(setMaf > 0.0 && setMaf <= 0.5))
+            fatal("FATAL  : --assoc-set-maf " + opt.assocSetMaf + ": the bound on the minor allele frequency must be a finite number in (0, 0.5]");
+        std::vector<size_t> runof(co.Mtot);
+        for (size_t ru = 0; ru < nruns; ++ru)
+            for (unsigned j = runs[ru]; j < runs[ru + 1]; ++j) runof[j] = ru;
+        mem_at.assign(co.Mtot, -1);
+        set_run.assign(msets.idx.size(), nruns);
+        for (size_t s = 0; s < msets.idx.size(); ++s) {
+            const std::vector<uint32_t>& ix = msets.idx[s];
+            listed += ix.size();
+            for (const uint32_t j : ix) {
+                if (runof[j] != runof[ix[0]])
+                    fatal("FATAL  : --assoc-sets: set " + msets.name[s] + " has markers on more than one chromosome run (" + bim.id[ix[0]] + " on " + bim.chr[ix[0]] + ", " +
+                          bim.id[j] + " on " + bim.chr[j] + "): a set is tested under one null model");
+                if (mem_at[j] < 0) mem_at[j] = (long)nmem++;
+            }
+            if (!ix.empty()) set_run[s] = runof[ix[0]];
+        }
+        // (the filters need the device's marker statistics, so the operator's limit is held against the ids found: no filter can add one)
+        for (size_t s = 0; s < msets.idx.size(); ++s)
+            if (msets.idx[s].size() > 1024)
+                fatal("FATAL  : --assoc-sets: set " + msets.name[s] + " has " + std::to_string(msets.idx[s].size()) + " markers, hgibbs_set_gram takes at most 1024 a set");
+        if (listed == 0)
+            fatal("FATAL  : --assoc-sets: none of the " + std::to_string(unknown) + " ids of " + opt.assocSets + " is among the first " + std::to_string(co.Mtot) +
+                  " markers of " + opt.bedFile + ".bim");
+        std::printf("ASSOC  : %zu sets of %zu markers from %s (%zu ids are not in the .bim), weights dbeta(MAF; %g, %g), MAF <= %g -> %s\n", msets.idx.size(), listed,
+                    opt.assocSets.c_str(), unknown, setA, setB, setMaf, sets_out.c_str());
+        std::fflush(stdout);
+    }
+    std::vector<double> mem_U(nmem, 0.0), mem_v(nmem * (size_t)qn, 0.0);
+    std::vector<uint8_t> mem_ok(nmem, 0);
+    std::vector<hgibbs_set_result> set_res(msets.idx.size());
+    std::vector<size_t> set_used(msets.idx.size(), 0);
+    double sets_ms = 0.0;
 
     std::vector<uint8_t> bed = read_training(opt.bedFile, co.numInds, co.Mtot);
     if (opt.assocOut.empty()) make_out_dir(opt);
@@ -2011,6 +2075,12 @@ int run_assoc_logistic(const Options& opt, const Cohort& co, const std::vector<d
             tested[jj] = 1;
             Uv[jj] = xu(0);
             Vv[jj] = V;
+            if (sets_on && mem_at[j] >= 0) { // a set member keeps its plain score and L^-1 t
+                const size_t e = (size_t)mem_at[j];
+                mem_ok[e] = 1;
+                mem_U[e] = Uv[jj];
+                std::copy(v.begin(), v.begin() + qn, mem_v.begin() + e * (size_t)qn);
+            }
             if ((spa && std::isfinite(V) && std::fabs(Uv[jj]) / std::sqrt(V) > spa_sd) ||
                 (firth && std::isfinite(V) && std::erfc(std::sqrt(Uv[jj] * Uv[jj] / V / 2.0)) <= firth_p)) {
                 // b_j = (Z'WZ)^-1 Z'W x_j = L^-T v, the value of each genotype code, the score
@@ -2097,11 +2167,109 @@ int run_assoc_logistic(const Options& opt, const Cohort& co, const std::vector<d
             std::fprintf(f, "\n");
             ++written;
         }
+        // the sets of this run: Phi = out - (L^-1 t_j).(L^-1 t_k) with hgibbs_set_gram's out under this run's w, then per copy of A1
+        if (sets_on) {
+            constexpr uint64_t SET_CHUNK = 1ull << 22; // entries of out per hgibbs_set_gram call (a set of 1024 has 2^20)
+            std::vector<size_t> todo;
+            for (size_t s = 0; s < msets.idx.size(); ++s)
+                if (set_run[s] == ru) todo.push_back(s);
+            std::vector<std::vector<uint32_t>> used(todo.size());
+            for (size_t k = 0; k < todo.size(); ++k) {
+                for (const uint32_t j : msets.idx[todo[k]]) {
+                    const double p = mave[j] / 2.0;
+                    if (mem_ok[(size_t)mem_at[j]] && std::min(p, 1.0 - p) <= setMaf) used[k].push_back(j);
+                }
+                set_used[todo[k]] = used[k].size();
+            }
+            for (size_t k0 = 0; k0 < todo.size();) {
+                std::vector<uint64_t> off{0};
+                std::vector<uint32_t> gidx;
+                std::vector<size_t> part;
+                uint64_t E = 0;
+                size_t k1 = k0;
+                for (; k1 < todo.size(); ++k1) {
+                    const uint64_t mm = (uint64_t)used[k1].size() * used[k1].size();
+                    if (!part.empty() && E + mm > SET_CHUNK) break;
+                    if (mm == 0) continue;
+                    part.push_back(k1);
+                    gidx.insert(gidx.end(), used[k1].begin(), used[k1].end());
+                    off.push_back(gidx.size());
+                    E += mm;
+                }
+                k0 = k1;
+                if (part.empty()) continue;
+                std::vector<double> G(E);
+                hg_check(hgibbs_set_gram(dev, (uint32_t)part.size(), off.data(), gidx.data(), nm.w.data(), G.data(), nullptr), "hgibbs_set_gram");
+                double gms = 0.0;
+                hg_check(hgibbs_last_set_gram_ms(dev, &gms), "hgibbs_last_set_gram_ms");
+                sets_ms += gms;
+                uint64_t b0 = 0;
+                for (const size_t k : part) {
+                    const std::vector<uint32_t>& ix = used[k];
+                    const size_t m = ix.size();
+                    std::vector<double> Ug(m), Ph(m * m), aw(m);
+                    const double lc = std::lgamma(setA + setB) - std::lgamma(setA) - std::lgamma(setB);
+                    for (size_t a = 0; a < m; ++a) {
+                        const size_t ea = (size_t)mem_at[ix[a]];
+                        const double p = mave[ix[a]] / 2.0, maf = std::min(p, 1.0 - p);
+                        Ug[a] = mem_U[ea] / mstd[ix[a]];
+                        aw[a] = std::exp(lc + (setA - 1.0) * std::log(maf) + (setB - 1.0) * std::log1p(-maf));
+                        for (size_t b = 0; b < m; ++b) {
+                            const size_t eb = (size_t)mem_at[ix[b]];
+                            double tt = 0.0;
+                            for (int c = 0; c < qn; ++c) tt += mem_v[ea * (size_t)qn + c] * mem_v[eb * (size_t)qn + c];
+                            Ph[a * m + b] = (G[b0 + a * m + b] - tt) / (mstd[ix[a]] * mstd[ix[b]]);
+                        }
+                    }
+                    hg_check(hgibbs_set_tests((uint32_t)m, Ug.data(), Ph.data(), aw.data(), &set_res[todo[k]]), "hgibbs_set_tests");
+                    b0 += (uint64_t)m * m;
+                }
+            }
+        }
     }
     hgibbs_destroy(dev);
     close_out(f, out);
-    std::printf("ASSOC  : wrote %llu rows to %s (%u cases, %u controls, %d iterations of %zu null models, %.3f ms on the device)\n", written, out.c_str(),
-                ncase, N - ncase, iters, nulls.size(), ms);
+    if (sets_on) {
+        FILE* fs = open_out(sets_out, "w");
+        std::fprintf(fs, "SET\tCHR\tBP_FIRST\tBP_LAST\tNSNP\tNUSED\tNEIG\tQ\tP_SKAT\tSKAT_OK\tT_BURDEN\tP_BURDEN\n");
+        auto num = [&](double x) {
+            if (std::isfinite(x)) std::fprintf(fs, "\t%.12g", x);
+            else std::fprintf(fs, "\tNA");
+        };
+        for (size_t s = 0; s < msets.idx.size(); ++s) {
+            const std::vector<uint32_t>& ix = msets.idx[s];
+            std::fprintf(fs, "%s", msets.name[s].c_str());
+            if (ix.empty()) std::fprintf(fs, "\tNA\tNA\tNA");
+            else {
+                long long lo = bim.bp[ix[0]], hi = lo;
+                for (const uint32_t j : ix) {
+                    lo = std::min(lo, bim.bp[j]);
+                    hi = std::max(hi, bim.bp[j]);
+                }
+                std::fprintf(fs, "\t%s\t%lld\t%lld", bim.chr[ix[0]].c_str(), lo, hi);
+            }
+            std::fprintf(fs, "\t%zu\t%zu", ix.size(), set_used[s]);
+            if (set_used[s] == 0) std::fprintf(fs, "\t0\tNA\tNA\tNA\tNA\tNA\n");
+            else {
+                const hgibbs_set_result& r = set_res[s];
+                std::fprintf(fs, "\t%d", r.neig);
+                num(r.q);
+                num(r.p_skat);
+                if (r.neig > 0) std::fprintf(fs, "\t%d", r.skat_ok);
+                else std::fprintf(fs, "\tNA");
+                num(r.t_burden);
+                num(r.p_burden);
+                std::fprintf(fs, "\n");
+            }
+        }
+        close_out(fs, sets_out);
+    }
+    if (sets_on)
+        std::printf("ASSOC  : wrote %llu rows to %s (%u cases, %u controls, %d iterations of %zu null models, %.3f ms on the device), %zu sets to %s (%.3f ms of hgibbs_set_gram on the device)\n",
+                    written, out.c_str(), ncase, N - ncase, iters, nulls.size(), ms, msets.idx.size(), sets_out.c_str(), sets_ms);
+    else
+        std::printf("ASSOC  : wrote %llu rows to %s (%u cases, %u controls, %d iterations of %zu null models, %.3f ms on the device)\n", written, out.c_str(),
+                    ncase, N - ncase, iters, nulls.size(), ms);
     if (spa)
         std::printf("ASSOC  : SPA on %llu markers (|z| > %g): %llu valid, %llu fell back, %.3f ms on the device\n", corr_n, spa_sd, corr_valid, corr_n - corr_valid,
                     corr_ms);
@@ -2234,13 +2402,9 @@ int run_pca(const Options& opt, const Cohort& co)
 }
 
 // ---- --pve: posterior variance explained by marker sets ----
-struct MarkerSets {
-    std::vector<std::string> name;
-    std::vector<std::vector<uint32_t>> idx; // markers of each set, increasing
-};
-
-// The SETNAME SNPID file of --pve-sets and --ld-score-sets: the sets in the order in which the file first names them
-MarkerSets read_sets_file(const std::string& path, const std::string& bedFile, const BimRows& bim, unsigned Mtot)
+// The SETNAME SNPID file of --pve-sets, --ld-score-sets and --assoc-sets: the sets in the order in which the file first names them.
+// unknown: null refuses an id the .bim lacks; otherwise such an id is counted there and left out (a set may end up empty).
+MarkerSets read_sets_file(const std::string& path, const std::string& bedFile, const BimRows& bim, unsigned Mtot, size_t* unknown)
 {
     MarkerSets ms;
     std::ifstream in(path);
@@ -2258,12 +2422,16 @@ MarkerSets read_sets_file(const std::string& path, const std::string& bedFile, c
         const std::string where = "FATAL  : " + path + " line " + std::to_string(lineno) + ": ";
         if (col.size() != 2) fatal(where + "expected SETNAME SNPID");
         const auto j = snp.find(col[1]);
-        if (j == snp.end()) fatal(where + "SNP " + col[1] + " is not among the first " + std::to_string(Mtot) + " markers of " + bedFile + ".bim");
+        if (j == snp.end() && !unknown) fatal(where + "SNP " + col[1] + " is not among the first " + std::to_string(Mtot) + " markers of " + bedFile + ".bim");
         auto it = at.find(col[0]);
         if (it == at.end()) {
             ms.name.push_back(col[0]);
             ms.idx.emplace_back();
             it = at.emplace(col[0], ms.idx.size() - 1).first;
+        }
+        if (j == snp.end()) {
+            ++*unknown;
+            continue;
         }
         if (!seen.emplace(std::make_pair(it->second, j->second), 1).second) fatal(where + "SNP " + col[1] + " is given twice for set " + col[0]);
         ms.idx[it->second].push_back(j->second);
@@ -3143,6 +3311,11 @@ void check_assoc_args(const Options& opt)
     if (opt.assocFirth && opt.assocSpa) fatal("FATAL  : --assoc-firth with --assoc-spa: choose one correction (each writes its own P)");
     if (opt.assocFirthPGiven && (!whole_num(opt.assocFirthP, t) || !std::isfinite(t) || !(t > 0.0 && t <= 1.0)))
         fatal("FATAL  : --assoc-firth-p " + opt.assocFirthP + ": the threshold must be a finite number in (0, 1] (the score-test P at or below which a marker is refitted)");
+    if (opt.assocSets.empty())
+        if (const char* o = first_given({{"--assoc-set-beta", opt.assocSetBetaGiven}, {"--assoc-set-maf", opt.assocSetMafGiven}, {"--assoc-set-out", !opt.assocSetOut.empty()}}))
+            fatal(std::string("FATAL  : ") + o + " needs --assoc-sets");
+    if (!opt.assocSets.empty() && !opt.assocLogistic)
+        fatal("FATAL  : --assoc-sets needs --assoc-logistic (the set tests of the linear model are not built)");
 }
 
 void check_king_args(const Options& opt)
@@ -3268,7 +3441,9 @@ void check_modes(const Options& opt, int nranks)
          first_given({{"--ld-out", !opt.ldOut.empty()}, {"--ld-window-kb", opt.ldKbGiven}, {"--ld-window-r2", opt.ldR2Given}, {"--ld-bin", opt.ldBin}})},
         {"--assoc", opt.assoc, takes, first_given({{"--assoc-out", !opt.assocOut.empty()}, {"--assoc-no-loco", opt.assocNoLoco}, {"--assoc-logistic", opt.assocLogistic},
                                                    {"--assoc-spa", opt.assocSpa}, {"--assoc-spa-sd", opt.assocSpaSdGiven},
-                                                   {"--assoc-firth", opt.assocFirth}, {"--assoc-firth-p", opt.assocFirthPGiven}})},
+                                                   {"--assoc-firth", opt.assocFirth}, {"--assoc-firth-p", opt.assocFirthPGiven},
+                                                   {"--assoc-sets", !opt.assocSets.empty()}, {"--assoc-set-beta", opt.assocSetBetaGiven},
+                                                   {"--assoc-set-maf", opt.assocSetMafGiven}, {"--assoc-set-out", !opt.assocSetOut.empty()}})},
         {"--king", opt.king, takes, first_given({{"--king-out", !opt.kingOut.empty()}, {"--king-cutoff", opt.kingCutoffGiven}})},
         {"--pca", opt.pca, takes,
          first_given({{"--pca-iters", opt.pcaItersGiven}, {"--pca-tol", opt.pcaTolGiven}, {"--pca-out", opt.pcaOutGiven}, {"--pca-loadings", opt.pcaLoadings}})},

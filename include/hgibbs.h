@@ -458,6 +458,48 @@ int hgibbs_last_marker_dots_ms(hgibbs_t h, double* ms);   /* every kernel of the
 int hgibbs_marker_class_sums(hgibbs_t h, uint32_t m0, uint32_t count, int K, const double* U, double* out /* count x K x 4 */);
 int hgibbs_last_marker_class_sums_ms(hgibbs_t h, double* ms);   /* every kernel of the last call, not the host copies */
 
+/* ---- row-weighted Gram matrices of marker sets */
+/* Sets in hgibbs_region_var's convention: set s lists the m_s = off[s + 1] - off[s] markers idx[off[s]] .. idx[off[s + 1] - 1] of the
+ * loaded BED, in any order, not necessarily contiguous; a marker may belong to several sets.  w: one non-negative weight per
+ * individual of this rank (n_local).  With base_s = sum_{s' < s} m_s'^2, q_i = llrint(w_i 2^E) (hgibbs_marker_dots' scale rule, one
+ * E for the vector: E = 52 - e with max_i w_i < 2^e, 0 for an all-zero w), g in {0, 1, 2} the stored genotype and c in {0, 1}
+ * "called", for positions a, b of set s:
+ *   raw[(base_s + a m_s + b)*3 + 0] = GG_ab = 2^-E sum_i q_i g_ia g_ib      (a missing call contributes 0)
+ *   raw[(base_s + a m_s + b)*3 + 1] = GC_ab = 2^-E sum_i q_i g_ia c_ib
+ *   raw[(base_s + a m_s + b)*3 + 2] = CC_ab = 2^-E sum_i q_i c_ia c_ib
+ *   out[base_s + a m_s + b] = (sd_a sd_b) (((GG_ab - m_b GC_ab) - m_a GC_ba) + (m_a m_b) CC_ab)
+ * with m = mave and sd = mstd of the markers, every operation in f64 in this order; out is NaN where either mstd is not finite.  It
+ * is sum_i w_i x_ia x_ib for the chain's standardised x (0 at a missing call).  raw may be NULL.  Every raw sum is an exact integer,
+ * rounded to f64 once; the only error before the combination is the rounding of w:
+ * |GG - sum w g_a g_b| <= 2 n 2^-E <= 4 n max(w) 2^-52, |GC - ..| <= n 2^-E, |CC - ..| <= n 2^-E / 2, each before its one rounding.
+ * So the results are bit-identical for any repeat, any batching of the sets over calls, any order of the sets and any value of the
+ * option sgram_split (ranges of individuals split over workgroups, 0 = automatic).  Needs the marker stats (computed here when they
+ * are not).  Refused, by name: nsets = 0, an empty set, a set of more than 1024 markers, an index >= M, an index listed twice within
+ * one set, a non-finite or negative entry of w, a handle without genotypes, several ranks, n_local >= 2^29, buffers that do not fit
+ * in free device memory. */
+int hgibbs_set_gram(hgibbs_t h, uint32_t nsets, const uint64_t* off /* nsets + 1 */, const uint32_t* idx /* off[nsets] marker indices */,
+                    const double* w /* n_local */, double* out, double* raw /* may be NULL */);
+int hgibbs_last_set_gram_ms(hgibbs_t h, double* ms);   /* every kernel of the last call, not the host copies; 0 after a refused call */
+
+/* Burden and SKAT statistics of one marker set (host only: no handle, no device; hg_settest.cpp).  U: the m scores; Phi: their
+ * m x m covariance under the null model (symmetric, the upper triangle is read); a: the m weights.
+ *   burden  t_burden = (sum a_j U_j)^2 / (a'Phi a), p_burden = erfc(sqrt(t_burden / 2)); both NaN when
+ *           a'Phi a <= 1e-9 sum a_j^2 Phi_jj.
+ *   SKAT    q = sum a_j^2 U_j^2; lam: the eigenvalues of diag(a) Phi diag(a) by cyclic Jacobi, those above 1e-10 lam_max kept, neig
+ *           their number, lam_sum and lam_max their sum and largest.  With neig = 0 these fields are NaN and skat_ok = 0.
+ *           p_skat = P(sum_k lam_k chi^2_1 >= q) by the saddlepoint approximation in hgibbs_spa_pvalue's Barndorff-Nielsen form:
+ *           K(z) = -1/2 sum log(1 - 2 z lam_k), the root of K'(z) = q on (-inf, 1 / (2 lam_max)) by hgibbs_spa_roots' bracketed
+ *           Newton rule and stop rule (every sum over the sorted eigenvalues in order: bit-reproducible),
+ *           w = sign(z) sqrt(2 (z q - K)), v = z sqrt(K''), p = erfc((w + log(v / w) / w) / sqrt 2) / 2; for
+ *           |q - lam_sum| < 1e-6 sqrt(2 sum lam^2) the form's limit erfc(rho / (6 sqrt 2)) / 2, rho = K'''(0) / K''(0)^(3/2) (to first
+ *           order 1/2 - rho / (6 sqrt(2 pi))).
+ *           skat_ok = 1 when the tail is valid by hgibbs_spa_pvalue's rules, the sign rule excepted: the argument keeps its sign here,
+ *           and between the median and the mean of the sum it is positive while z is negative (or the limit was taken); otherwise skat_ok = 0 and
+ *           p_skat is the normal tail of (q - lam_sum) / sqrt(2 sum lam^2).
+ * Refused: a null argument, m = 0, a non-finite entry of U, a or the upper triangle of Phi. */
+typedef struct { double q, p_skat, t_burden, p_burden, lam_sum, lam_max; int32_t neig, skat_ok; } hgibbs_set_result;
+int hgibbs_set_tests(uint32_t m, const double* U /* m */, const double* Phi /* m x m, symmetric */, const double* a /* m weights */, hgibbs_set_result* r);
+
 /* The null model of a logistic score test (host only: no handle, no device; hg_logit.cpp).  Z: n x q column-major, first column all
  * ones; y: n entries in {0, 1}.  Newton / IRLS in f64 from coefficients 0, every sum in row order (bit-reproducible), the step halved
  * while the deviance rises (by more than 1e-12 of itself: less is the rounding of its sum).  Stop rule: when max_a |score_a| / sqrt(info_aa) <= 1e-10 one more full step is taken and the fit ends;
