@@ -822,9 +822,8 @@ class Device:
         check(self.L.hgibbs_last_set_gram_ms(self.h, C.byref(v)))
         return v.value
 
-    def spa_roots(self, markers, Z, mu, B, xv, s):
-        """The saddlepoints of the logistic score test for a list of markers (hgibbs_spa_roots): Z (n_local, q) and mu (n_local,) of
-        the null model, B (nm, q), xv (nm, 4) and s (nm,) per entry.  Returns a ctypes array of nm SpaRoot."""
+    def _null_list(self, fn, rec, markers, Z, mu, B, xv, s):
+        """The arguments that spa_roots and firth_fit share, checked and marshalled for `fn`; returns its nm records of type `rec`."""
         markers = np.ascontiguousarray(markers, dtype=np.uint32).reshape(-1)
         nm = markers.size
         Z = np.asarray(Z, dtype=np.float64)
@@ -838,9 +837,14 @@ class Device:
         s = np.ascontiguousarray(s, dtype=np.float64).reshape(-1)
         if mu.size != self.n_local or B.size != nm * q or xv.size != nm * 4 or s.size != nm:
             raise ValueError("mu must be (%d,), B (%d, %d), xv (%d, 4), s (%d,)" % (self.n_local, nm, q, nm, nm))
-        out = (SpaRoot * max(nm, 1))()
-        check(self.L.hgibbs_spa_roots(self.h, nm, markers.ctypes.data_as(C_U32P), q, _dp(Zc), _dp(mu), _dp(B), _dp(xv), _dp(s), out))
+        out = (rec * max(nm, 1))()
+        check(fn(self.h, nm, markers.ctypes.data_as(C_U32P), q, _dp(Zc), _dp(mu), _dp(B), _dp(xv), _dp(s), out))
         return out
+
+    def spa_roots(self, markers, Z, mu, B, xv, s):
+        """The saddlepoints of the logistic score test for a list of markers (hgibbs_spa_roots): Z (n_local, q) and mu (n_local,) of
+        the null model, B (nm, q), xv (nm, 4) and s (nm,) per entry.  Returns a ctypes array of nm SpaRoot."""
+        return self._null_list(self.L.hgibbs_spa_roots, SpaRoot, markers, Z, mu, B, xv, s)
 
     def last_spa_ms(self):
         v = C.c_double()
@@ -850,22 +854,7 @@ class Device:
     def firth_fit(self, markers, Z, mu, B, xv, s):
         """Firth's penalised fit of the score test's one-parameter model for a list of markers (hgibbs_firth_fit): the arguments of
         spa_roots.  Returns a ctypes array of nm FirthRec.  Option firth_piece: entries per piece of the list (0 = automatic)."""
-        markers = np.ascontiguousarray(markers, dtype=np.uint32).reshape(-1)
-        nm = markers.size
-        Z = np.asarray(Z, dtype=np.float64)
-        if Z.ndim != 2 or Z.shape[0] != self.n_local:
-            raise ValueError("Z must be (%d, q)" % self.n_local)
-        q = Z.shape[1]
-        Zc = np.ascontiguousarray(Z.T)  # column-major
-        mu = np.ascontiguousarray(mu, dtype=np.float64).reshape(-1)
-        B = np.ascontiguousarray(B, dtype=np.float64).reshape(-1)
-        xv = np.ascontiguousarray(xv, dtype=np.float64).reshape(-1)
-        s = np.ascontiguousarray(s, dtype=np.float64).reshape(-1)
-        if mu.size != self.n_local or B.size != nm * q or xv.size != nm * 4 or s.size != nm:
-            raise ValueError("mu must be (%d,), B (%d, %d), xv (%d, 4), s (%d,)" % (self.n_local, nm, q, nm, nm))
-        out = (FirthRec * max(nm, 1))()
-        check(self.L.hgibbs_firth_fit(self.h, nm, markers.ctypes.data_as(C_U32P), q, _dp(Zc), _dp(mu), _dp(B), _dp(xv), _dp(s), out))
-        return out
+        return self._null_list(self.L.hgibbs_firth_fit, FirthRec, markers, Z, mu, B, xv, s)
 
     def last_firth_ms(self):
         v = C.c_double()

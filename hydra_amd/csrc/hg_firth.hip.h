@@ -11,8 +11,8 @@
 //
 //   shape    one workgroup of SPA_TPB threads per entry, the rows per thread and the tree of spa_reduce as in k_spa_roots: the order
 //            of every sum depends on n_local only.  No atomics.  The entries share nothing.
-//   a-cache  pass 0 forms a_i from the row-major Z (q reads per row) and writes it to the entry's row of `cache` (n doubles); the later
-//            passes read that one double per row.  Thread tid writes and reads the elements tid, tid + SPA_TPB, ...: no element is
+//   a-cache  pass 0 forms a_i (spa_adjusted: q reads of the row-major Z per row) and writes it to the entry's row of `cache` (n doubles);
+//            the later passes read that one double per row.  Thread tid writes and reads the elements tid, tid + SPA_TPB, ...: no element is
 //            touched by two threads, so nothing is synchronised.  The host cuts the list into pieces whose rows of the cache fit.
 //   pass 0   at t = 0: k2_0 = K''(0), scale = 1 / sqrt(k2_0); a k2_0 that is not finite or not positive ends the entry (flag bit 1, every
 //            other field 0).  lo = -inf, hi = +inf, tg = 0 (the last point with a finite g and g').
@@ -36,19 +36,15 @@ static_assert(sizeof(hgibbs_firth_rec) == 48, "hgibbs_firth_rec is part of the A
 // One row's terms at t, added to k1 .. k4 (K' .. K'''') and, in the closing pass, kk (K): spa_terms with two more sums
 __device__ __forceinline__ void firth_terms(double a, double m, double t, bool closing, double& k1, double& k2, double& k3, double& k4, double& kk)
 {
-    const double u = a * t;
-    const bool neg = u <= 0.0;
-    const double E = expm1(-fabs(u));
-    const double c = neg ? m : 1.0 - m;
-    const double cE = c * E;
-    const double p = (neg ? m * (1.0 + E) : m) / (1.0 + cE);
+    double u, cE;
+    const double p = logit_point(a, m, t, u, cE);
     const double v = p * (1.0 - p);
     const double a2 = a * a;
     k1 += a * (p - m);
     k2 += a2 * v;
     k3 += (a2 * a) * (v * (1.0 - 2.0 * p));
     k4 += (a2 * a2) * (v * (1.0 - 6.0 * v));
-    if (closing) kk += ((neg ? 0.0 : u) + log1p(cE)) - u * m;
+    if (closing) kk += logit_log_term(u, cE, m);
 }
 
 // the entries [e0, e0 + gridDim.x) of the list; cache: gridDim.x rows of n doubles
@@ -79,12 +75,7 @@ __global__ __launch_bounds__(SPA_TPB) void k_firth_fit(const uint8_t* __restrict
         for (int k = 0; k < 6; ++k) v[k] = 0.0;
         if (pass == 0) {
             for (uint32_t i = tid; i < n; i += SPA_TPB) {
-                const uint32_t code = (col[i >> 4] >> (2u * (i & 15u))) & 3u;
-                const double* z = Zr + (uint64_t)i * (uint32_t)q;
-                double zb = 0.0;
-#pragma unroll 4
-                for (int k = 0; k < q; ++k) zb += z[k] * sb[k]; // (the sum stays in column order)
-                const double a = (code == 0u ? x0 : code == 1u ? x1 : code == 2u ? x2 : x3) - zb;
+                const double a = spa_adjusted(col, Zr, q, sb, x0, x1, x2, x3, i);
                 ca[i] = a;
                 firth_terms(a, mu[i], 0.0, false, v[0], v[1], v[2], v[3], v[4]);
             }
@@ -141,27 +132,13 @@ extern "C" int hgibbs_firth_fit(hgibbs_t h, uint32_t nm, const uint32_t* markers
 {
     if (h) h->firth_ms = 0.0; // (before the guard: 0 after every refusal, those of the guard included)
     if (op_guard(h, "hgibbs_firth_fit", "the sums over the rows are not summed over ranks")) return 1;
-    if (!markers || !Z || !mu || !B || !xv || !s || !out) return fail("hgibbs_firth_fit: null argument");
-    if (q < 1 || q > SPA_QMAX) return fail("hgibbs_firth_fit: q = %d, must be in [1, %d]", q, SPA_QMAX);
-    if (nm == 0) return 0;
-    const uint32_t n = h->n_local;
-    for (uint32_t e = 0; e < nm; ++e)
-        if (markers[e] >= h->M) return fail("hgibbs_firth_fit: markers[%u] = %u out of range (M = %u)", e, markers[e], h->M);
-    for (size_t k = 0; k < (size_t)q * n; ++k)
-        if (!std::isfinite(Z[k])) return fail("hgibbs_firth_fit: Z[%zu][%d] = %g is not finite", k % n, (int)(k / n), Z[k]);
-    for (uint32_t i = 0; i < n; ++i)
-        if (!(mu[i] > 0.0 && mu[i] < 1.0)) return fail("hgibbs_firth_fit: mu[%u] = %g is not strictly inside (0, 1)", i, mu[i]);
-    for (size_t k = 0; k < (size_t)nm * q; ++k)
-        if (!std::isfinite(B[k])) return fail("hgibbs_firth_fit: B[%zu][%d] = %g is not finite", k / q, (int)(k % q), B[k]);
-    for (size_t k = 0; k < (size_t)nm * 4; ++k)
-        if (!std::isfinite(xv[k])) return fail("hgibbs_firth_fit: xv[%zu][%d] = %g is not finite", k / 4, (int)(k % 4), xv[k]);
-    for (uint32_t e = 0; e < nm; ++e)
-        if (!std::isfinite(s[e])) return fail("hgibbs_firth_fit: s[%u] = %g is not finite", e, s[e]);
+    if (const int c = null_list_check(h, "hgibbs_firth_fit", nm, markers, q, Z, mu, B, xv, s, out)) return c > 0;
     HIP_TRY(hipSetDevice(h->device));
 
     // the list's own buffers, then the a-cache of one piece: `piece` entries of n doubles each
-    const size_t nq = (size_t)n * q, row = (size_t)n * sizeof(double);
-    const size_t bytes = (2 * nq + n + (size_t)nm * (q + 5)) * sizeof(double) + (size_t)nm * (sizeof(uint32_t) + sizeof(hgibbs_firth_rec));
+    const uint32_t n = h->n_local;
+    const size_t row = (size_t)n * sizeof(double);
+    const size_t bytes = NullList::bytes(n, nm, q) + (size_t)nm * sizeof(hgibbs_firth_rec);
     uint32_t piece = (uint32_t)std::min<uint64_t>({(uint64_t)nm, (uint64_t)FIRTH_PIECE_MAX, h->firth_piece ? (uint64_t)h->firth_piece : ~0ull});
     if (!h->firth_piece) { // automatic: a quarter of the free memory, one entry at the least
         size_t fre = 0, tot = 0;
@@ -171,26 +148,14 @@ extern "C" int hgibbs_firth_fit(hgibbs_t h, uint32_t nm, const uint32_t* markers
     if (need_device_memory(bytes + (size_t)piece * row, "hgibbs_firth_fit: %u markers against a null model of %d columns and pieces of %u entries need %.1f MiB", nm,
                            q, piece, (bytes + (size_t)piece * row) / 1048576.0))
         return 1;
-    DevBuf<double> dZ, dZr, dmu, dB, dxv, ds, dcache;
-    DevBuf<uint32_t> dmk;
+    NullList l;
     DevBuf<hgibbs_firth_rec> dout;
-    if (dZ.alloc(nq) || dZr.alloc(nq) || dmu.alloc(n) || dB.alloc((size_t)nm * q) || dxv.alloc((size_t)nm * 4) || ds.alloc(nm) || dmk.alloc(nm) || dout.alloc(nm) ||
-        dcache.alloc((size_t)piece * n))
-        return 1;
-    HIP_TRY(hipMemcpyAsync(dZ, Z, nq * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(dmu, mu, (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(dB, B, (size_t)nm * q * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(dxv, xv, (size_t)nm * 4 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(ds, s, (size_t)nm * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(dmk, markers, (size_t)nm * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-
+    DevBuf<double> dcache;
     // device time of every kernel, not the host copies around them; the pieces follow each other on the stream and share the cache
     double ms = 0.0;
-    if (lap_begin(h)) return 1;
-    k_spa_rowmajor<<<(uint32_t)((nq + SPA_TPB - 1) / SPA_TPB), SPA_TPB, 0, h->stream>>>(dZ, n, q, dZr);
-    HIP_TRY(hipGetLastError());
+    if (dout.alloc(nm) || dcache.alloc((size_t)piece * n) || null_list_begin(h, l, nm, markers, q, Z, mu, B, xv, s)) return 1;
     for (uint32_t e0 = 0; e0 < nm; e0 += piece) {
-        k_firth_fit<<<std::min(piece, nm - e0), SPA_TPB, 0, h->stream>>>(h->bed, h->stride, n, dmk, q, dZr, dmu, dB, dxv, ds, e0, dcache, dout);
+        k_firth_fit<<<std::min(piece, nm - e0), SPA_TPB, 0, h->stream>>>(h->bed, h->stride, n, l.dmk, q, l.dZr, l.dmu, l.dB, l.dxv, l.ds, e0, dcache, dout);
         HIP_TRY(hipGetLastError());
     }
     if (lap_end(h, ms)) return 1;

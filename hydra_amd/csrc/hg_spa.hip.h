@@ -15,9 +15,9 @@
 //   sums     per thread in row order, then spa_reduce: a shuffle tree inside the wave, the waves' sums through LDS, added as
 //            (w0 + w1) + (w2 + w3).  No atomics.  The order depends on n_local only: bit-identical for any chunking of the list, any
 //            position in it and any repeat.
-//   terms    the branch-free stable form: E = expm1(-|u|); for u <= 0, D = 1 + mu E, p = mu (1 + E) / D, log term log1p(mu E); for
-//            u > 0, D = 1 + (1 - mu) E, p = mu / D, log term u + log1p((1 - mu) E).  The log term is evaluated only in a tail's
-//            closing pass (K is not needed before).  f64 expm1, log1p and division of the device library; no contraction.
+//   terms    the branch-free stable form (logit_point, also k_firth_fit's): E = expm1(-|u|); for u <= 0, D = 1 + mu E, p = mu (1 + E) / D,
+//            log term log1p(mu E); for u > 0, D = 1 + (1 - mu) E, p = mu / D, log term u + log1p((1 - mu) E).  The log term is evaluated only
+//            in a tail's closing pass (K is not needed before).  f64 expm1, log1p and division of the device library; no contraction.
 //   pass 0   k2_0 = K''(0), c = sum a_i mu_i, s_hi = sum max(a_i, 0) - c, s_lo = sum min(a_i, 0) - c.  A tail whose tau is not
 //            strictly inside (s_lo, s_hi) is unreachable (flag bit 2 + tail) and is not iterated.
 //   root     from t = tau / k2_0 with the open bracket (0, inf) resp. (-inf, 0): the sign of K'(t) - tau tightens the bracket, the
@@ -67,19 +67,40 @@ __device__ __forceinline__ void spa_reduce(double (&v)[6], double (*red)[6], uin
     __syncthreads();
 }
 
-// One row's terms of one tail at t, added to k1 (K'), k2 (K'') and, in the closing pass, kk (K)
-__device__ __forceinline__ void spa_terms(double a, double m, double t, bool closing, double& k1, double& k2, double& kk)
+// The stable logistic point of one row at u = a t, in the form of the header: p, with u and cE = c E for the log term
+__device__ __forceinline__ double logit_point(double a, double m, double t, double& u, double& cE)
 {
-    const double u = a * t;
+    u = a * t;
     const bool neg = u <= 0.0;
     const double E = expm1(-fabs(u));
     const double c = neg ? m : 1.0 - m;
-    const double cE = c * E;
+    cE = c * E;
     const double D = 1.0 + cE;
-    const double p = (neg ? m * (1.0 + E) : m) / D;
+    return (neg ? m * (1.0 + E) : m) / D;
+}
+__device__ __forceinline__ double logit_log_term(double u, double cE, double m) { return ((u <= 0.0 ? 0.0 : u) + log1p(cE)) - u * m; } // the row's term of K
+
+// One row's terms of one tail at t, added to k1 (K'), k2 (K'') and, in the closing pass, kk (K)
+__device__ __forceinline__ void spa_terms(double a, double m, double t, bool closing, double& k1, double& k2, double& kk)
+{
+    double u, cE;
+    const double p = logit_point(a, m, t, u, cE);
     k1 += a * (p - m);
     k2 += (a * a) * (p * (1.0 - p));
-    if (closing) kk += ((neg ? 0.0 : u) + log1p(cE)) - u * m;
+    if (closing) kk += logit_log_term(u, cE, m);
+}
+
+// The adjusted genotype a_i of row i: the value xv of the row's BED code in the marker's column `col`, less row i of the row-major Z
+// times the entry's b (in LDS)
+__device__ __forceinline__ double spa_adjusted(const uint32_t* col, const double* Zr, int q, const double* sb, double x0, double x1, double x2,
+                                               double x3, uint32_t i)
+{
+    const uint32_t code = (col[i >> 4] >> (2u * (i & 15u))) & 3u;
+    const double* z = Zr + (uint64_t)i * (uint32_t)q;
+    double zb = 0.0;
+#pragma unroll 4
+    for (int k = 0; k < q; ++k) zb += z[k] * sb[k]; // (the loads of four columns in flight; the sum stays in column order)
+    return (code == 0u ? x0 : code == 1u ? x1 : code == 2u ? x2 : x3) - zb;
 }
 
 __global__ __launch_bounds__(SPA_TPB) void k_spa_roots(const uint8_t* __restrict__ bed, uint64_t stride, uint32_t n, const uint32_t* __restrict__ markers,
@@ -96,20 +117,11 @@ __global__ __launch_bounds__(SPA_TPB) void k_spa_roots(const uint8_t* __restrict
     const double sabs = fabs(s[e]);
     __syncthreads();
 
-    auto adjusted = [&](uint32_t i) {
-        const uint32_t code = (col[i >> 4] >> (2u * (i & 15u))) & 3u;
-        const double* z = Zr + (uint64_t)i * (uint32_t)q;
-        double zb = 0.0;
-#pragma unroll 4
-        for (int k = 0; k < q; ++k) zb += z[k] * sb[k]; // (the loads of four columns in flight; the sum stays in column order)
-        return (code == 0u ? x0 : code == 1u ? x1 : code == 2u ? x2 : x3) - zb;
-    };
-
     double v[6];
 #pragma unroll
     for (int k = 0; k < 6; ++k) v[k] = 0.0;
     for (uint32_t i = tid; i < n; i += SPA_TPB) {
-        const double a = adjusted(i), m = mu[i];
+        const double a = spa_adjusted(col, Zr, q, sb, x0, x1, x2, x3, i), m = mu[i];
         v[0] += (a * a) * (m * (1.0 - m));
         v[1] += a * m;
         v[2] += fmax(a, 0.0);
@@ -141,7 +153,7 @@ __global__ __launch_bounds__(SPA_TPB) void k_spa_roots(const uint8_t* __restrict
 #pragma unroll
         for (int k = 0; k < 6; ++k) v[k] = 0.0;
         for (uint32_t i = tid; i < n; i += SPA_TPB) {
-            const double a = adjusted(i), m = mu[i];
+            const double a = spa_adjusted(col, Zr, q, sb, x0, x1, x2, x3, i), m = mu[i];
             if (st0) spa_terms(a, m, t[0], st0 == 2, v[0], v[1], v[2]);
             if (st1) spa_terms(a, m, t[1], st1 == 2, v[3], v[4], v[5]);
         }
@@ -186,52 +198,73 @@ __global__ __launch_bounds__(SPA_TPB) void k_spa_roots(const uint8_t* __restrict
     }
 }
 
+// ---- a list of markers against a null model: the host code that hgibbs_spa_roots and hgibbs_firth_fit share ----
+struct NullList {
+    DevBuf<double> dZ, dZr, dmu, dB, dxv, ds;
+    DevBuf<uint32_t> dmk;
+    // the bytes of the buffers above for nm entries, without the caller's records
+    static size_t bytes(uint32_t n, uint32_t nm, int q) { return (2 * ((size_t)n * q) + n + (size_t)nm * (q + 5)) * sizeof(double) + (size_t)nm * sizeof(uint32_t); }
+};
+
+// The arguments of `who`, after op_guard: null check, bound on q, every value.  0: go on; 1: refused; -1: an empty list, of which nothing is read
+int null_list_check(const hgibbs_ctx* h, const char* who, uint32_t nm, const uint32_t* markers, int q, const double* Z, const double* mu, const double* B,
+                    const double* xv, const double* s, const void* out)
+{
+    if (!markers || !Z || !mu || !B || !xv || !s || !out) return fail("%s: null argument", who);
+    if (q < 1 || q > SPA_QMAX) return fail("%s: q = %d, must be in [1, %d]", who, q, SPA_QMAX);
+    if (nm == 0) return -1;
+    const uint32_t n = h->n_local;
+    for (uint32_t e = 0; e < nm; ++e)
+        if (markers[e] >= h->M) return fail("%s: markers[%u] = %u out of range (M = %u)", who, e, markers[e], h->M);
+    for (size_t k = 0; k < (size_t)q * n; ++k)
+        if (!std::isfinite(Z[k])) return fail("%s: Z[%zu][%d] = %g is not finite", who, k % n, (int)(k / n), Z[k]);
+    for (uint32_t i = 0; i < n; ++i)
+        if (!(mu[i] > 0.0 && mu[i] < 1.0)) return fail("%s: mu[%u] = %g is not strictly inside (0, 1)", who, i, mu[i]);
+    for (size_t k = 0; k < (size_t)nm * q; ++k)
+        if (!std::isfinite(B[k])) return fail("%s: B[%zu][%d] = %g is not finite", who, k / q, (int)(k % q), B[k]);
+    for (size_t k = 0; k < (size_t)nm * 4; ++k)
+        if (!std::isfinite(xv[k])) return fail("%s: xv[%zu][%d] = %g is not finite", who, k / 4, (int)(k % 4), xv[k]);
+    for (uint32_t e = 0; e < nm; ++e)
+        if (!std::isfinite(s[e])) return fail("%s: s[%u] = %g is not finite", who, e, s[e]);
+    return 0;
+}
+
+// The list's buffers and their uploads on the handle's stream; then the caller's lap begins, with the row-major copy of Z as its first kernel
+int null_list_begin(hgibbs_ctx* h, NullList& l, uint32_t nm, const uint32_t* markers, int q, const double* Z, const double* mu, const double* B,
+                     const double* xv, const double* s)
+{
+    const uint32_t n = h->n_local;
+    const size_t nq = (size_t)n * q;
+    if (l.dZ.alloc(nq) || l.dZr.alloc(nq) || l.dmu.alloc(n) || l.dB.alloc((size_t)nm * q) || l.dxv.alloc((size_t)nm * 4) || l.ds.alloc(nm) || l.dmk.alloc(nm)) return 1;
+    HIP_TRY(hipMemcpyAsync(l.dZ, Z, nq * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(l.dmu, mu, (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(l.dB, B, (size_t)nm * q * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(l.dxv, xv, (size_t)nm * 4 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(l.ds, s, (size_t)nm * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(l.dmk, markers, (size_t)nm * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    if (lap_begin(h)) return 1;
+    k_spa_rowmajor<<<(uint32_t)((nq + SPA_TPB - 1) / SPA_TPB), SPA_TPB, 0, h->stream>>>(l.dZ, n, q, l.dZr);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 } // namespace
 
 extern "C" int hgibbs_spa_roots(hgibbs_t h, uint32_t nm, const uint32_t* markers, int q, const double* Z, const double* mu, const double* B,
                                 const double* xv, const double* s, hgibbs_spa_root* out)
 {
+    if (h) h->spa_ms = 0.0; // (before the guard: 0 after every refusal, those of the guard included)
     if (op_guard(h, "hgibbs_spa_roots", "the sums over the rows are not summed over ranks")) return 1;
-    h->spa_ms = 0.0;
-    if (!markers || !Z || !mu || !B || !xv || !s || !out) return fail("hgibbs_spa_roots: null argument");
-    if (q < 1 || q > SPA_QMAX) return fail("hgibbs_spa_roots: q = %d, must be in [1, %d]", q, SPA_QMAX);
-    if (nm == 0) return 0;
-    const uint32_t n = h->n_local;
-    for (uint32_t e = 0; e < nm; ++e)
-        if (markers[e] >= h->M) return fail("hgibbs_spa_roots: markers[%u] = %u out of range (M = %u)", e, markers[e], h->M);
-    for (size_t k = 0; k < (size_t)q * n; ++k)
-        if (!std::isfinite(Z[k])) return fail("hgibbs_spa_roots: Z[%zu][%d] = %g is not finite", k % n, (int)(k / n), Z[k]);
-    for (uint32_t i = 0; i < n; ++i)
-        if (!(mu[i] > 0.0 && mu[i] < 1.0)) return fail("hgibbs_spa_roots: mu[%u] = %g is not strictly inside (0, 1)", i, mu[i]);
-    for (size_t k = 0; k < (size_t)nm * q; ++k)
-        if (!std::isfinite(B[k])) return fail("hgibbs_spa_roots: B[%zu][%d] = %g is not finite", k / q, (int)(k % q), B[k]);
-    for (size_t k = 0; k < (size_t)nm * 4; ++k)
-        if (!std::isfinite(xv[k])) return fail("hgibbs_spa_roots: xv[%zu][%d] = %g is not finite", k / 4, (int)(k % 4), xv[k]);
-    for (uint32_t e = 0; e < nm; ++e)
-        if (!std::isfinite(s[e])) return fail("hgibbs_spa_roots: s[%u] = %g is not finite", e, s[e]);
+    if (const int c = null_list_check(h, "hgibbs_spa_roots", nm, markers, q, Z, mu, B, xv, s, out)) return c > 0;
     HIP_TRY(hipSetDevice(h->device));
 
-    const size_t nq = (size_t)n * q;
-    const size_t bytes = (2 * nq + n + (size_t)nm * (q + 5)) * sizeof(double) + (size_t)nm * (sizeof(uint32_t) + sizeof(hgibbs_spa_root));
+    const size_t bytes = NullList::bytes(h->n_local, nm, q) + (size_t)nm * sizeof(hgibbs_spa_root);
     if (need_device_memory(bytes, "hgibbs_spa_roots: %u markers against a null model of %d columns need %.1f MiB", nm, q, bytes / 1048576.0)) return 1;
-    DevBuf<double> dZ, dZr, dmu, dB, dxv, ds;
-    DevBuf<uint32_t> dmk;
+    NullList l;
     DevBuf<hgibbs_spa_root> dout;
-    if (dZ.alloc(nq) || dZr.alloc(nq) || dmu.alloc(n) || dB.alloc((size_t)nm * q) || dxv.alloc((size_t)nm * 4) || ds.alloc(nm) || dmk.alloc(nm) || dout.alloc(nm))
-        return 1;
-    HIP_TRY(hipMemcpyAsync(dZ, Z, nq * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(dmu, mu, (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(dB, B, (size_t)nm * q * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(dxv, xv, (size_t)nm * 4 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(ds, s, (size_t)nm * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(dmk, markers, (size_t)nm * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-
-    // device time of both kernels, not the host copies around them
-    double ms = 0.0;
-    if (lap_begin(h)) return 1;
-    k_spa_rowmajor<<<(uint32_t)((nq + SPA_TPB - 1) / SPA_TPB), SPA_TPB, 0, h->stream>>>(dZ, n, q, dZr);
-    HIP_TRY(hipGetLastError());
-    k_spa_roots<<<nm, SPA_TPB, 0, h->stream>>>(h->bed, h->stride, n, dmk, q, dZr, dmu, dB, dxv, ds, dout);
+    double ms = 0.0; // device time of both kernels, not the host copies around them
+    if (dout.alloc(nm) || null_list_begin(h, l, nm, markers, q, Z, mu, B, xv, s)) return 1;
+    k_spa_roots<<<nm, SPA_TPB, 0, h->stream>>>(h->bed, h->stride, h->n_local, l.dmk, q, l.dZr, l.dmu, l.dB, l.dxv, l.ds, dout);
     HIP_TRY(hipGetLastError());
     if (lap_end(h, ms)) return 1;
     HIP_TRY(hipMemcpy(out, dout, (size_t)nm * sizeof(hgibbs_spa_root), hipMemcpyDeviceToHost));

@@ -112,6 +112,7 @@
 #include <iostream>
 #include <limits>
 #include <map>
+#include <optional>
 #include <sstream>
 #include <string>
 #include <thread>
@@ -1442,6 +1443,68 @@ void read_bet_records(const std::string& path, unsigned Mtot, unsigned burnin, s
         fatal("FATAL  : " + path + ": no record at or after --burn-in " + std::to_string(burnin) + " (" + std::to_string(total) + " records)");
 }
 
+// Named sets of markers (--pve, --ld-score, --assoc-sets)
+struct MarkerSets {
+    std::vector<std::string> name;
+    std::vector<std::vector<uint32_t>> idx; // markers of each set, increasing
+};
+
+// The SETNAME SNPID file of --pve-sets, --ld-score-sets and --assoc-sets: the sets in the order in which the file first names them.
+// unknown: null refuses an id the .bim lacks; otherwise such an id is counted there and left out (a set may end up empty).
+MarkerSets read_sets_file(const std::string& path, const std::string& bedFile, const BimRows& bim, unsigned Mtot, size_t* unknown = nullptr)
+{
+    MarkerSets ms;
+    std::ifstream in(path);
+    if (!in) fatal("Error: can not open the file [" + path + "] to read.");
+    std::map<std::string, uint32_t> snp;
+    for (unsigned j = 0; j < Mtot; ++j) snp.emplace(bim.id[j], j);
+    std::map<std::string, size_t> at;
+    std::map<std::pair<size_t, uint32_t>, int> seen;
+    std::string line;
+    size_t lineno = 0;
+    while (std::getline(in, line)) {
+        ++lineno;
+        const std::vector<std::string> col = tokens(line, " \t\r");
+        if (col.empty()) continue;
+        const std::string where = "FATAL  : " + path + " line " + std::to_string(lineno) + ": ";
+        if (col.size() != 2) fatal(where + "expected SETNAME SNPID");
+        const auto j = snp.find(col[1]);
+        if (j == snp.end() && !unknown) fatal(where + "SNP " + col[1] + " is not among the first " + std::to_string(Mtot) + " markers of " + bedFile + ".bim");
+        auto it = at.find(col[0]);
+        if (it == at.end()) {
+            ms.name.push_back(col[0]);
+            ms.idx.emplace_back();
+            it = at.emplace(col[0], ms.idx.size() - 1).first;
+        }
+        if (j == snp.end()) {
+            ++*unknown;
+            continue;
+        }
+        if (!seen.emplace(std::make_pair(it->second, j->second), 1).second) fatal(where + "SNP " + col[1] + " is given twice for set " + col[0]);
+        ms.idx[it->second].push_back(j->second);
+    }
+    if (ms.idx.empty()) fatal("FATAL  : " + path + " names no set");
+    for (auto& r : ms.idx) std::sort(r.begin(), r.end());
+    return ms;
+}
+
+// The groups of --pve-groups and --ld-score-groups: one set per group number of the group index file, in ascending order of the number
+MarkerSets sets_from_groups(const Options& opt, unsigned Mtot)
+{
+    MarkerSets ms;
+    const std::vector<int32_t> groups = read_groups(opt.groupIndexFile);
+    if (groups.size() < Mtot) fatal("FATAL  : group file covers fewer markers than --number-markers");
+    std::map<int32_t, size_t> at;
+    for (unsigned j = 0; j < Mtot; ++j) at.emplace(groups[j], 0);
+    for (auto& g : at) {
+        g.second = ms.idx.size();
+        ms.name.push_back("group" + std::to_string(g.first));
+        ms.idx.emplace_back();
+    }
+    for (unsigned j = 0; j < Mtot; ++j) ms.idx[at[groups[j]]].push_back(j);
+    return ms;
+}
+
 // The chain's cohort as every analysis mode takes it: the rows that kept their phenotype (and, with --covariates, every covariate)
 // of the first Mtot markers of --bfile
 struct Cohort {
@@ -1747,226 +1810,264 @@ struct ChromRuns {
     }
 };
 
-// Gc[i * nchrom + c]: the chain's genetic value of row i from chromosome c, the mean effects of the .bet records through hgibbs_score
-// with one "sample" per chromosome; the device time is added to ms
-std::vector<double> loco_genetic_values(hgibbs_t dev, const std::vector<double>& betas, size_t S, unsigned Mtot, unsigned N, const std::vector<int>& cj,
-                                        size_t nchrom, const std::vector<double>& mave, const std::vector<double>& mstd, double& ms)
-{
-    std::vector<double> bbar(Mtot, 0.0);
-    for (size_t s = 0; s < S; ++s)
-        for (unsigned j = 0; j < Mtot; ++j) bbar[j] += betas[s * Mtot + j];
-    for (unsigned j = 0; j < Mtot; ++j) bbar[j] /= (double)S;
-    std::vector<double> a(nchrom * Mtot, 0.0), o(nchrom * Mtot, 0.0), Gc((size_t)N * nchrom);
-    for (unsigned j = 0; j < Mtot; ++j) {
-        if (!std::isfinite(mstd[j])) continue; // (score refuses non-finite weights; x = 0 there anyway)
-        a[(size_t)cj[j] * Mtot + j] = bbar[j] * mstd[j];
-        o[(size_t)cj[j] * Mtot + j] = -bbar[j] * mstd[j] * mave[j];
-    }
-    hg_check(hgibbs_score(dev, (int)nchrom, a.data(), o.data(), Gc.data()), "hgibbs_score");
-    double t = 0.0;
-    hg_check(hgibbs_last_score_ms(dev, &t), "hgibbs_last_score_ms");
-    ms += t;
-    return Gc;
-}
-
-int run_assoc(const Options& opt, const Cohort& co, const std::vector<double>& y_raw, const std::vector<double>& covX, int C)
-{
-    const std::string base = opt.mcmcOutDir + "/" + opt.mcmcOutNam;
-    const std::string out = opt.assocOut.empty() ? base + ".assoc" : opt.assocOut;
-    const bool loco = !opt.assocNoLoco;
-    const BimRows bim = read_bim(opt.bedFile + ".bim", co.Mtot);
-    const unsigned N = co.Ntot;
-    const int q = 1 + C;
-
-    const ChromRuns cr(bim, co.Mtot);
-    const std::vector<int>& cj = cr.cj;
-    const std::vector<unsigned>& runs = cr.runs;
-    const size_t nruns = cr.nruns, nchrom = cr.nchrom;
+// What both models of --assoc share.  The constructor: the names, the .bim and its runs, the chain's records for LOCO, the banner, the
+// refusals of too few rows and of dependent covariates.  open(), after the model's own refusals: the genotypes, the table, the device
+// with the chain's rows, the marker statistics.
+struct AssocFrame {
+    const Options& opt;
+    const Cohort& co;
+    const std::string base, out;
+    const bool loco;
+    const BimRows bim;
+    const unsigned N;
+    const int C, q;
+    const ChromRuns cr;
     std::vector<unsigned> its;
-    std::vector<double> betas;
-    if (loco) read_bet_records(base + ".bet", co.Mtot, opt.burnin, its, betas, "--assoc takes its LOCO offsets from the chain's effects");
-    std::printf("ASSOC  : %u markers, %zu chromosomes in %zu runs, %d covariates, %u individuals -> %s\n", co.Mtot, nchrom, nruns, C, N, out.c_str());
-    if (loco)
-        std::printf("ASSOC  : LOCO offsets from %zu records of %s (iterations %u .. %u)\n", its.size(), (base + ".bet").c_str(), its.front(), its.back());
-    else
-        std::printf("ASSOC  : no LOCO offsets (--assoc-no-loco): every chromosome is tested against the scaled phenotype\n");
-    if (loco && nchrom == 1) std::printf("WARNING: --assoc with one chromosome: G - G_c is 0, no offset is taken out\n");
-    std::fflush(stdout);
-    if ((long long)N <= (long long)q + 1) fatal("FATAL  : --assoc needs more individuals (" + std::to_string(N) + ") than covariates + 2");
+    std::vector<double> betas, mave, mstd;
+    std::vector<uint64_t> n1, n2, nmiss;
+    std::optional<CovProjector> proj; // Z = [1 | covariates]
+    FILE* f = nullptr;
+    hgibbs_t dev = nullptr;
+    double ms = 0.0; // device time of the tests
+    unsigned long long written = 0;
 
-    // the chain's scaled phenotype and Z = [1 | covariates]
-    std::vector<double> y(y_raw);
-    scale_phenotype(y, N);
-    const CovProjector proj("--assoc", covX, C, N);
-    const std::vector<double>&Z = proj.Z, &L = proj.L;
-    auto project = [&](std::vector<double>& v) { proj.project(v); };
+    AssocFrame(const Options& opt_, const Cohort& co_, const std::vector<double>& covX, int C_, bool logistic)
+        : opt(opt_), co(co_), base(opt_.mcmcOutDir + "/" + opt_.mcmcOutNam), out(opt_.assocOut.empty() ? base + (logistic ? ".assoc.logistic" : ".assoc") : opt_.assocOut), loco(!opt_.assocNoLoco),
+          bim(read_bim(opt_.bedFile + ".bim", co_.Mtot)), N(co_.Ntot), C(C_), q(1 + C_), cr(bim, co_.Mtot), mave(co_.Mtot), mstd(co_.Mtot), n1(co_.Mtot), n2(co_.Mtot),
+          nmiss(co_.Mtot)
+    {
+        if (loco) read_bet_records(base + ".bet", co.Mtot, opt.burnin, its, betas, "--assoc takes its LOCO offsets from the chain's effects");
+        std::printf("ASSOC  : %u markers, %zu chromosomes in %zu runs, %d covariates, %u individuals -> %s\n", co.Mtot, cr.nchrom, cr.nruns, C, N, out.c_str());
+        if (loco)
+            std::printf("ASSOC  : LOCO %s from %zu records of %s (iterations %u .. %u)\n", logistic ? "predictors" : "offsets", its.size(), (base + ".bet").c_str(), its.front(), its.back());
+        else
+            std::printf("ASSOC  : %s\n", logistic ? "no LOCO predictor (--assoc-no-loco): one null model of [1 | covariates] for every chromosome"
+                                              : "no LOCO offsets (--assoc-no-loco): every chromosome is tested against the scaled phenotype");
+        if (loco && cr.nchrom == 1) std::printf("WARNING: --assoc with one chromosome: G - G_c is 0, no offset is taken out\n");
+        std::fflush(stdout);
+        if ((long long)N <= (long long)q + 1) fatal("FATAL  : --assoc needs more individuals (" + std::to_string(N) + ") than covariates + 2");
+        proj.emplace("--assoc", covX, C, N);
+    }
 
-    std::vector<uint8_t> bed = read_training(opt.bedFile, co.numInds, co.Mtot);
-    if (opt.assocOut.empty()) make_out_dir(opt);
-    FILE* f = open_out(out, "w");
-    std::fprintf(f, "CHR SNP BP A1 A2 FREQ N BETA SE CHISQ P\n");
+    void open(const std::string& header)
+    {
+        std::vector<uint8_t> bed = read_training(opt.bedFile, co.numInds, co.Mtot);
+        if (opt.assocOut.empty()) make_out_dir(opt);
+        f = open_out(out, "w");
+        std::fprintf(f, "%s\n", header.c_str());
+        dev = open_training(co, bed); // the chain's rows and standardisation
+        hg_check(hgibbs_marker_stats(dev, mave.data(), mstd.data(), n1.data(), n2.data(), nmiss.data()), "hgibbs_marker_stats");
+    }
 
-    // the chain's rows and standardisation
-    hgibbs_t dev = open_training(co, bed);
-    std::vector<double> mave(co.Mtot), mstd(co.Mtot);
-    std::vector<uint64_t> n1(co.Mtot), n2(co.Mtot), nmiss(co.Mtot);
-    hg_check(hgibbs_marker_stats(dev, mave.data(), mstd.data(), n1.data(), n2.data(), nmiss.data()), "hgibbs_marker_stats");
-    double ms = 0.0;
-
-    // r_c = y - (G - G_c), projected off Z: G_c from hgibbs_score with one "sample" per chromosome
-    std::vector<std::vector<double>> r(loco ? nchrom : 1, y);
-    if (loco) {
-        const std::vector<double> Gc = loco_genetic_values(dev, betas, its.size(), co.Mtot, N, cj, nchrom, mave, mstd, ms);
+    // gc[c][i] = G - G_c, the chain's genetic value of row i without chromosome c.  G_c: the mean effects of the .bet records through
+    // hgibbs_score with one "sample" per chromosome; its device time is added to ms
+    std::vector<std::vector<double>> loco_predictors()
+    {
+        const unsigned Mtot = co.Mtot;
+        const size_t S = its.size(), nchrom = cr.nchrom;
+        std::vector<double> bbar(Mtot, 0.0);
+        for (size_t s = 0; s < S; ++s)
+            for (unsigned j = 0; j < Mtot; ++j) bbar[j] += betas[s * Mtot + j];
+        for (unsigned j = 0; j < Mtot; ++j) bbar[j] /= (double)S;
+        std::vector<double> a(nchrom * Mtot, 0.0), o(nchrom * Mtot, 0.0), Gc((size_t)N * nchrom);
+        for (unsigned j = 0; j < Mtot; ++j) {
+            if (!std::isfinite(mstd[j])) continue; // (score refuses non-finite weights; x = 0 there anyway)
+            a[(size_t)cr.cj[j] * Mtot + j] = bbar[j] * mstd[j];
+            o[(size_t)cr.cj[j] * Mtot + j] = -bbar[j] * mstd[j] * mave[j];
+        }
+        hg_check(hgibbs_score(dev, (int)nchrom, a.data(), o.data(), Gc.data()), "hgibbs_score");
+        add_ms(hgibbs_last_score_ms, "hgibbs_last_score_ms", ms);
+        std::vector<std::vector<double>> gc(nchrom, std::vector<double>(N));
         for (unsigned i = 0; i < N; ++i) {
             double G = 0.0;
             for (size_t c = 0; c < nchrom; ++c) G += Gc[(size_t)i * nchrom + c];
-            for (size_t c = 0; c < nchrom; ++c) r[c][i] = y[i] - (G - Gc[(size_t)i * nchrom + c]);
+            for (size_t c = 0; c < nchrom; ++c) gc[c][i] = G - Gc[(size_t)i * nchrom + c];
         }
+        return gc;
+    }
+
+    void add_ms(int (*last)(hgibbs_t, double*), const char* what, double& total) const // the device time of the last call of an operator
+    {
+        double t = 0.0;
+        hg_check(last(dev, &t), what);
+        total += t;
+    }
+    void close()
+    {
+        hgibbs_destroy(dev);
+        close_out(f, out);
+    }
+    unsigned long long called(unsigned j) const { return (unsigned long long)N - nmiss[j]; }
+    void row_prefix(unsigned j) const // CHR SNP BP A1 A2 FREQ N of marker j, and the blank before the model's columns
+    {
+        std::fprintf(f, "%s %s %lld %s %s %.12g %llu ", bim.chr[j].c_str(), bim.id[j].c_str(), bim.bp[j], bim.a1[j].c_str(), bim.a2[j].c_str(), mave[j] / 2.0, called(j));
+    }
+};
+
+int run_assoc(const Options& opt, const Cohort& co, const std::vector<double>& y_raw, const std::vector<double>& covX, int C)
+{
+    AssocFrame fr(opt, co, covX, C, false);
+    const unsigned N = fr.N;
+    const int q = fr.q, K = 1 + q;
+    std::vector<double> y(y_raw); // the chain's scaled phenotype
+    scale_phenotype(y, N);
+    fr.open("CHR SNP BP A1 A2 FREQ N BETA SE CHISQ P");
+
+    // r_c = y - (G - G_c), projected off Z
+    std::vector<std::vector<double>> r(fr.loco ? fr.cr.nchrom : 1, y);
+    if (fr.loco) {
+        const std::vector<std::vector<double>> gc = fr.loco_predictors();
+        for (size_t c = 0; c < r.size(); ++c)
+            for (unsigned i = 0; i < N; ++i) r[c][i] = y[i] - gc[c][i];
     }
     std::vector<double> rr(r.size(), 0.0);
     for (size_t c = 0; c < r.size(); ++c) {
-        project(r[c]);
+        fr.proj->project(r[c]);
         for (unsigned i = 0; i < N; ++i) rr[c] += r[c][i] * r[c][i];
     }
 
     // one hgibbs_marker_dots per run: U = [r_c, columns of Z] gives s = x_j'r_c and t = Z'x_j
-    const int K = 1 + q;
     std::vector<double> U((size_t)K * N), dots;
-    std::copy(Z.begin(), Z.end(), U.begin() + N);
+    std::copy(fr.proj->Z.begin(), fr.proj->Z.end(), U.begin() + N);
     const double dof = (double)N - (double)q - 1.0;
-    unsigned long long written = 0;
-    for (size_t ru = 0; ru < nruns; ++ru) {
-        const unsigned m0 = runs[ru], cnt = runs[ru + 1] - runs[ru];
-        const size_t c = loco ? (size_t)cj[m0] : 0;
+    for (size_t ru = 0; ru < fr.cr.nruns; ++ru) {
+        const unsigned m0 = fr.cr.runs[ru], cnt = fr.cr.runs[ru + 1] - fr.cr.runs[ru];
+        const size_t c = fr.loco ? (size_t)fr.cr.cj[m0] : 0;
         std::copy(r[c].begin(), r[c].end(), U.begin());
         dots.resize((size_t)cnt * K);
-        hg_check(hgibbs_marker_dots(dev, m0, cnt, K, U.data(), dots.data(), nullptr), "hgibbs_marker_dots");
-        double t = 0.0;
-        hg_check(hgibbs_last_marker_dots_ms(dev, &t), "hgibbs_last_marker_dots_ms");
-        ms += t;
+        hg_check(hgibbs_marker_dots(fr.dev, m0, cnt, K, U.data(), dots.data(), nullptr), "hgibbs_marker_dots");
+        fr.add_ms(hgibbs_last_marker_dots_ms, "hgibbs_last_marker_dots_ms", fr.ms);
         for (unsigned jj = 0; jj < cnt; ++jj) {
             const unsigned j = m0 + jj;
-            const double m = mave[j], sd = mstd[j];
-            const unsigned long long called = (unsigned long long)N - nmiss[j];
-            const double n0 = (double)(called - n1[j] - n2[j]);
-            const double xx = sd * sd * ((double)n1[j] * (1.0 - m) * (1.0 - m) + (double)n2[j] * (2.0 - m) * (2.0 - m) + n0 * m * m);
+            const double m = fr.mave[j], sd = fr.mstd[j];
+            const double n0 = (double)(fr.called(j) - fr.n1[j] - fr.n2[j]);
+            const double xx = sd * sd * ((double)fr.n1[j] * (1.0 - m) * (1.0 - m) + (double)fr.n2[j] * (2.0 - m) * (2.0 - m) + n0 * m * m);
             const double s = dots[(size_t)jj * K];
             std::vector<double> tz(dots.begin() + (size_t)jj * K + 1, dots.begin() + (size_t)(jj + 1) * K);
-            const std::vector<double> w = chol_solve(L, q, tz);
+            const std::vector<double> w = chol_solve(fr.proj->L, q, tz);
             double v = xx;
             for (int a = 0; a < q; ++a) v -= tz[a] * w[a];
-            std::fprintf(f, "%s %s %lld %s %s %.12g %llu ", bim.chr[j].c_str(), bim.id[j].c_str(), bim.bp[j], bim.a1[j].c_str(), bim.a2[j].c_str(),
-                         m / 2.0, called);
-            if (!std::isfinite(sd) || !(v > 1e-9 * xx)) std::fprintf(f, "NA NA NA NA\n");
+            fr.row_prefix(j);
+            if (!std::isfinite(sd) || !(v > 1e-9 * xx)) std::fprintf(fr.f, "NA NA NA NA\n");
             else {
                 const double b = s / v;
                 const double s2 = (rr[c] - s * s / v) / dof;
                 const double se = std::sqrt(s2 / v);
                 const double chisq = b * b / (se * se);
-                std::fprintf(f, "%.12g %.12g %.12g %.12g\n", b * sd, se * sd, chisq, std::erfc(std::sqrt(chisq / 2.0)));
+                std::fprintf(fr.f, "%.12g %.12g %.12g %.12g\n", b * sd, se * sd, chisq, std::erfc(std::sqrt(chisq / 2.0)));
             }
-            ++written;
+            ++fr.written;
         }
     }
-    hgibbs_destroy(dev);
-    close_out(f, out);
-    std::printf("ASSOC  : wrote %llu rows to %s (%.3f ms on the device)\n", written, out.c_str(), ms);
+    fr.close();
+    std::printf("ASSOC  : wrote %llu rows to %s (%.3f ms on the device)\n", fr.written, fr.out.c_str(), fr.ms);
     return 0;
 }
 
-struct MarkerSets {
-    std::vector<std::string> name;
-    std::vector<std::vector<uint32_t>> idx; // markers of each set, increasing
-};
-MarkerSets read_sets_file(const std::string& path, const std::string& bedFile, const BimRows& bim, unsigned Mtot, size_t* unknown = nullptr);
-
 // ---- --assoc --assoc-logistic: the logistic score test of a case/control phenotype ----
-int run_assoc_logistic(const Options& opt, const Cohort& co, const std::vector<double>& y_raw, const std::vector<double>& covX, int C)
-{
-    const std::string base = opt.mcmcOutDir + "/" + opt.mcmcOutNam;
-    const std::string out = opt.assocOut.empty() ? base + ".assoc.logistic" : opt.assocOut;
-    const bool loco = !opt.assocNoLoco;
-    const BimRows bim = read_bim(opt.bedFile + ".bim", co.Mtot);
-    const unsigned N = co.Ntot;
-    const int q = 1 + C;
+struct LogitNull {
+    std::vector<double> coef, mu, w, L;
+    int iters = 0;
+};
 
-    const ChromRuns cr(bim, co.Mtot);
-    const std::vector<int>& cj = cr.cj;
-    const std::vector<unsigned>& runs = cr.runs;
-    const size_t nruns = cr.nruns, nchrom = cr.nchrom;
-    std::vector<unsigned> its;
-    std::vector<double> betas;
-    if (loco) read_bet_records(base + ".bet", co.Mtot, opt.burnin, its, betas, "--assoc takes its LOCO offsets from the chain's effects");
-    std::printf("ASSOC  : %u markers, %zu chromosomes in %zu runs, %d covariates, %u individuals -> %s\n", co.Mtot, nchrom, nruns, C, N, out.c_str());
-    if (loco)
-        std::printf("ASSOC  : LOCO predictors from %zu records of %s (iterations %u .. %u)\n", its.size(), (base + ".bet").c_str(), its.front(), its.back());
-    else
-        std::printf("ASSOC  : no LOCO predictor (--assoc-no-loco): one null model of [1 | covariates] for every chromosome\n");
-    if (loco && nchrom == 1) std::printf("WARNING: --assoc with one chromosome: G - G_c is 0, no offset is taken out\n");
-    std::fflush(stdout);
-    if ((long long)N <= (long long)q + 1) fatal("FATAL  : --assoc needs more individuals (" + std::to_string(N) + ") than covariates + 2");
-    const CovProjector proj("--assoc", covX, C, N); // (Z = [1 | covariates], and the linear mode's refusal of dependent columns)
-
-    // the refusals of this mode, before any device call: the phenotype, the number of vectors, the null model of [1 | covariates]
-    std::vector<double> vals(y_raw.begin(), y_raw.begin() + N);
-    std::sort(vals.begin(), vals.end());
-    vals.erase(std::unique(vals.begin(), vals.end()), vals.end());
-    if (vals.size() != 2)
-        fatal("FATAL  : --assoc-logistic: the phenotype takes " + std::to_string(vals.size()) +
-              " distinct values on the kept rows, a case/control phenotype takes exactly two (the larger one is the case)");
-    const bool gcol = loco && nchrom > 1;  // the LOCO predictor G - G_c as a column of the null model
-    const int qn = q + (gcol ? 1 : 0);     // columns of the null model
-    const int K = 2 + qn;                  // y - mu, w z_1 .. w z_qn, the case indicator
-    if (K > 32)
-        fatal("FATAL  : --assoc-logistic: " + std::to_string(C) + " covariates make " + std::to_string(K) + " vectors (y - mu, one per column of the null model" +
-              (gcol ? " with the LOCO predictor" : "") + ", the case indicator), hgibbs_marker_class_sums takes at most 32");
-    std::vector<double> d(N);
+// The null models: the case indicator d, the columns Zc = [1 | covariates | the run's LOCO predictor] and one fit per chromosome (one in
+// all without a predictor column).  The constructor holds the mode's refusals, which come before any device call.
+struct LogitNulls {
+    const unsigned N;
+    const int q;
+    const bool gcol;   // the LOCO predictor G - G_c as a column of the null model
+    const int qn, K;   // columns of the null model; vectors of a run: y - mu, w z_1 .. w z_qn, the case indicator
+    std::vector<double> d, Zc, U;
     unsigned ncase = 0;
-    for (unsigned i = 0; i < N; ++i) ncase += (d[i] = y_raw[i] == vals[1] ? 1.0 : 0.0) != 0.0;
-    struct Null {
-        std::vector<double> coef, mu, w, L;
-        int iters = 0;
-    };
-    std::vector<double> Zc((size_t)qn * N);
-    std::copy(proj.Z.begin(), proj.Z.end(), Zc.begin());
-    auto fit = [&](int cols, Null& f) {
-        f.coef.assign(cols, 0.0);
-        f.mu.assign(N, 0.0);
-        f.w.assign(N, 0.0);
-        f.L.assign((size_t)cols * cols, 0.0);
-        hg_check(hgibbs_logit_null(N, cols, Zc.data(), d.data(), f.coef.data(), f.mu.data(), f.w.data(), f.L.data(), &f.iters), "--assoc-logistic");
-    };
-    std::vector<Null> nulls(gcol ? nchrom : 1);
-    fit(q, nulls[0]); // (with a LOCO predictor this one only refuses early; the fits per chromosome follow)
-    int iters = gcol ? 0 : nulls[0].iters;
+    std::vector<LogitNull> nulls;
+    std::vector<std::vector<double>> gc; // the last column per chromosome
+    int iters = 0;
 
-    // --assoc-sets: the file, the weights' parameters and the sets' places, each refused before any device call
-    const bool sets_on = !opt.assocSets.empty();
-    const std::string sets_out = opt.assocSetOut.empty() ? base + ".assoc.sets" : opt.assocSetOut;
+    LogitNulls(const AssocFrame& fr, const std::vector<double>& y_raw)
+        : N(fr.N), q(fr.q), gcol(fr.loco && fr.cr.nchrom > 1), qn(q + (gcol ? 1 : 0)), K(2 + qn), d(fr.N), Zc((size_t)qn * fr.N), U((size_t)K * fr.N)
+    {
+        std::vector<double> vals(y_raw.begin(), y_raw.begin() + N);
+        std::sort(vals.begin(), vals.end());
+        vals.erase(std::unique(vals.begin(), vals.end()), vals.end());
+        if (vals.size() != 2)
+            fatal("FATAL  : --assoc-logistic: the phenotype takes " + std::to_string(vals.size()) +
+                  " distinct values on the kept rows, a case/control phenotype takes exactly two (the larger one is the case)");
+        if (K > 32)
+            fatal("FATAL  : --assoc-logistic: " + std::to_string(fr.C) + " covariates make " + std::to_string(K) + " vectors (y - mu, one per column of the null model" +
+                  (gcol ? " with the LOCO predictor" : "") + ", the case indicator), hgibbs_marker_class_sums takes at most 32");
+        for (unsigned i = 0; i < N; ++i) ncase += (d[i] = y_raw[i] == vals[1] ? 1.0 : 0.0) != 0.0;
+        std::copy(fr.proj->Z.begin(), fr.proj->Z.end(), Zc.begin());
+        nulls.resize(gcol ? fr.cr.nchrom : 1);
+        fit(q, nulls[0]); // (with a LOCO predictor this one only refuses early; the fits per chromosome follow)
+        iters = gcol ? 0 : nulls[0].iters;
+        std::copy(d.begin(), d.end(), U.begin() + (size_t)(K - 1) * N);
+    }
+    void fit(int cols, LogitNull& f)
+    {
+        f = LogitNull{std::vector<double>(cols), std::vector<double>(N), std::vector<double>(N), std::vector<double>((size_t)cols * cols), 0};
+        hg_check(hgibbs_logit_null(N, cols, Zc.data(), d.data(), f.coef.data(), f.mu.data(), f.w.data(), f.L.data(), &f.iters), "--assoc-logistic");
+    }
+    // one null model per chromosome on [1 | covariates | G - G_c]: the predictor is on the scaled phenotype's scale and gets a coefficient
+    void fit_chromosomes(AssocFrame& fr)
+    {
+        if (gcol) gc = fr.loco_predictors();
+        for (size_t c = 0; c < gc.size(); ++c) {
+            std::copy(gc[c].begin(), gc[c].end(), Zc.begin() + (size_t)q * N);
+            fit(qn, nulls[c]);
+            iters += nulls[c].iters;
+        }
+    }
+    // The null model of the run that starts at marker m0; Zc and U = [y - mu, w z_1 .. w z_qn, d] become that run's
+    const LogitNull& begin_run(const AssocFrame& fr, unsigned m0)
+    {
+        const size_t c = gcol ? (size_t)fr.cr.cj[m0] : 0;
+        const LogitNull& nm = nulls[c];
+        if (gcol) std::copy(gc[c].begin(), gc[c].end(), Zc.begin() + (size_t)q * N);
+        for (unsigned i = 0; i < N; ++i) {
+            U[i] = d[i] - nm.mu[i];
+            for (int a = 0; a < qn; ++a) U[(size_t)(1 + a) * N + i] = nm.w[i] * Zc[(size_t)a * N + i];
+        }
+        return nm;
+    }
+};
+
+// --assoc-sets: the file, the weights' parameters and the sets' places, each refused before any device call; then what the runs keep per
+// member for the sets' tests, and the results
+struct SetPlan {
+    const bool on;
+    const std::string out;
     MarkerSets msets;
-    double setA = 1.0, setB = 25.0, setMaf = 0.5;
-    std::vector<long> mem_at;       // per marker: its slot among the sets' members, or -1
-    std::vector<size_t> set_run;    // per set: the run of its markers (nruns: none of its ids was found)
-    size_t nmem = 0;
-    if (sets_on) {
-        size_t unknown = 0, listed = 0;
-        msets = read_sets_file(opt.assocSets, opt.bedFile, bim, co.Mtot, &unknown);
-        if (!whole_num(opt.assocSetA, setA) || !whole_num(opt.assocSetB, setB) || !std::isfinite(setA) || !std::isfinite(setB) || !(setA > 0.0 && setB > 0.0))
+    double a = 1.0, b = 25.0, maf = 0.5;
+    std::vector<long> mem_at;         // per marker: its slot among the sets' members, or -1
+    std::vector<size_t> set_run;      // per set: the run of its markers (nruns: none of its ids was found)
+    std::vector<double> mem_U, mem_v; // per member: its plain score and L^-1 t (qn values)
+    std::vector<uint8_t> mem_ok;
+    std::vector<hgibbs_set_result> res;
+    std::vector<size_t> used; // per set: the members that were tested and pass the MAF bound
+    double ms = 0.0;          // device time of hgibbs_set_gram
+
+    SetPlan(const AssocFrame& fr, int qn) : on(!fr.opt.assocSets.empty()), out(fr.opt.assocSetOut.empty() ? fr.base + ".assoc.sets" : fr.opt.assocSetOut)
+    {
+        if (!on) return;
+        const Options& opt = fr.opt;
+        size_t unknown = 0, listed = 0, nmem = 0;
+        msets = read_sets_file(opt.assocSets, opt.bedFile, fr.bim, fr.co.Mtot, &unknown);
+        if (!whole_num(opt.assocSetA, a) || !whole_num(opt.assocSetB, b) || !std::isfinite(a) || !std::isfinite(b) || !(a > 0.0 && b > 0.0))
             fatal("FATAL  : --assoc-set-beta " + opt.assocSetA + " " + opt.assocSetB + ": both parameters of the weights' beta density must be finite numbers > 0");
-        if (!whole_num(opt.assocSetMaf, setMaf) || !std::isfinite(setMaf) || !(setMaf > 0.0 && setMaf <= 0.5))
+        if (!whole_num(opt.assocSetMaf, maf) || !std::isfinite(maf) || !(maf > 0.0 && maf <= 0.5))
             fatal("FATAL  : --assoc-set-maf " + opt.assocSetMaf + ": the bound on the minor allele frequency must be a finite number in (0, 0.5]");
-        std::vector<size_t> runof(co.Mtot);
-        for (size_t ru = 0; ru < nruns; ++ru)
-            for (unsigned j = runs[ru]; j < runs[ru + 1]; ++j) runof[j] = ru;
-        mem_at.assign(co.Mtot, -1);
-        set_run.assign(msets.idx.size(), nruns);
+        std::vector<size_t> runof(fr.co.Mtot);
+        for (size_t ru = 0; ru < fr.cr.nruns; ++ru)
+            for (unsigned j = fr.cr.runs[ru]; j < fr.cr.runs[ru + 1]; ++j) runof[j] = ru;
+        mem_at.assign(fr.co.Mtot, -1);
+        set_run.assign(msets.idx.size(), fr.cr.nruns);
         for (size_t s = 0; s < msets.idx.size(); ++s) {
             const std::vector<uint32_t>& ix = msets.idx[s];
             listed += ix.size();
             for (const uint32_t j : ix) {
                 if (runof[j] != runof[ix[0]])
-                    fatal("FATAL  : --assoc-sets: set " + msets.name[s] + " has markers on more than one chromosome run (" + bim.id[ix[0]] + " on " + bim.chr[ix[0]] + ", " +
-                          bim.id[j] + " on " + bim.chr[j] + "): a set is tested under one null model");
+                    fatal("FATAL  : --assoc-sets: set " + msets.name[s] + " has markers on more than one chromosome run (" + fr.bim.id[ix[0]] + " on " + fr.bim.chr[ix[0]] + ", " +
+                          fr.bim.id[j] + " on " + fr.bim.chr[j] + "): a set is tested under one null model");
                 if (mem_at[j] < 0) mem_at[j] = (long)nmem++;
             }
             if (!ix.empty()) set_run[s] = runof[ix[0]];
@@ -1976,306 +2077,271 @@ int run_assoc_logistic(const Options& opt, const Cohort& co, const std::vector<d
             if (msets.idx[s].size() > 1024)
                 fatal("FATAL  : --assoc-sets: set " + msets.name[s] + " has " + std::to_string(msets.idx[s].size()) + " markers, hgibbs_set_gram takes at most 1024 a set");
         if (listed == 0)
-            fatal("FATAL  : --assoc-sets: none of the " + std::to_string(unknown) + " ids of " + opt.assocSets + " is among the first " + std::to_string(co.Mtot) +
+            fatal("FATAL  : --assoc-sets: none of the " + std::to_string(unknown) + " ids of " + opt.assocSets + " is among the first " + std::to_string(fr.co.Mtot) +
                   " markers of " + opt.bedFile + ".bim");
         std::printf("ASSOC  : %zu sets of %zu markers from %s (%zu ids are not in the .bim), weights dbeta(MAF; %g, %g), MAF <= %g -> %s\n", msets.idx.size(), listed,
-                    opt.assocSets.c_str(), unknown, setA, setB, setMaf, sets_out.c_str());
+                    opt.assocSets.c_str(), unknown, a, b, maf, out.c_str());
         std::fflush(stdout);
+        mem_U.assign(nmem, 0.0);
+        mem_v.assign(nmem * (size_t)qn, 0.0);
+        mem_ok.assign(nmem, 0);
+        res.resize(msets.idx.size());
+        used.assign(msets.idx.size(), 0);
     }
-    std::vector<double> mem_U(nmem, 0.0), mem_v(nmem * (size_t)qn, 0.0);
-    std::vector<uint8_t> mem_ok(nmem, 0);
-    std::vector<hgibbs_set_result> set_res(msets.idx.size());
-    std::vector<size_t> set_used(msets.idx.size(), 0);
-    double sets_ms = 0.0;
+};
 
-    std::vector<uint8_t> bed = read_training(opt.bedFile, co.numInds, co.Mtot);
-    if (opt.assocOut.empty()) make_out_dir(opt);
-    FILE* f = open_out(out, "w");
-    const bool spa = opt.assocSpa;
-    double spa_sd = 2.0;
-    whole_num(opt.assocSpaSd, spa_sd);
-    const bool firth = opt.assocFirth; // (never with spa: check_assoc_args)
-    double firth_p = 0.05;
-    whole_num(opt.assocFirthP, firth_p);
-    std::fprintf(f, "CHR SNP BP A1 A2 FREQ N BETA SE CHISQ P N_CASE N_CTRL FREQ_CASE FREQ_CTRL%s\n", spa ? " P_NORM SPA" : firth ? " P_NORM BETA_SCORE SE_SCORE FIRTH" : "");
+// %.12g, or NA where the number is not defined
+std::string num_or_na(double x, bool defined)
+{
+    char t[32];
+    std::snprintf(t, sizeof t, "%.12g", x);
+    return defined ? t : "NA";
+}
 
-    // the chain's rows and standardisation
-    hgibbs_t dev = open_training(co, bed);
-    std::vector<double> mave(co.Mtot), mstd(co.Mtot);
-    std::vector<uint64_t> n1(co.Mtot), n2(co.Mtot), nmiss(co.Mtot);
-    hg_check(hgibbs_marker_stats(dev, mave.data(), mstd.data(), n1.data(), n2.data(), nmiss.data()), "hgibbs_marker_stats");
+struct AssocRow {
+    double beta, se, stat, p;
+    int ok; // -2 the marker is not tested (NA); the correction: -1 not applied, 0 applied and fell back to the normal P (the score test), 1 applied and valid
+};
+
+// The correction of the score test, --assoc-spa's or --assoc-firth's (never both: check_assoc_args): its threshold, the run's list of
+// markers that get it (one entry each, as hgibbs_spa_roots and hgibbs_firth_fit take them), and the counters
+struct Correction {
+    const bool spa, firth;
+    double thr; // --assoc-spa-sd, in standard deviations, or --assoc-firth-p
+    std::vector<uint32_t> mk;
+    std::vector<double> B, xv, s;
+    unsigned long long n = 0, valid = 0;
     double ms = 0.0;
+    explicit Correction(const Options& opt) : spa(opt.assocSpa), firth(opt.assocFirth), thr(opt.assocSpa ? 2.0 : 0.05) { whole_num(spa ? opt.assocSpaSd : opt.assocFirthP, thr); }
+    bool wants(double U, double V) const // the markers beyond thr standard deviations, resp. whose P is at most thr
+    {
+        return (spa && std::isfinite(V) && std::fabs(U) / std::sqrt(V) > thr) || (firth && std::isfinite(V) && std::erfc(std::sqrt(U * U / V / 2.0)) <= thr);
+    }
+};
 
-    // one null model per chromosome on [1 | covariates | G - G_c]: the predictor is on the scaled phenotype's scale and gets a coefficient
-    std::vector<std::vector<double>> gc; // the last column per chromosome
-    if (gcol) {
-        const std::vector<double> Gc = loco_genetic_values(dev, betas, its.size(), co.Mtot, N, cj, nchrom, mave, mstd, ms);
-        gc.assign(nchrom, std::vector<double>(N));
-        for (unsigned i = 0; i < N; ++i) {
-            double G = 0.0;
-            for (size_t c = 0; c < nchrom; ++c) G += Gc[(size_t)i * nchrom + c];
-            for (size_t c = 0; c < nchrom; ++c) gc[c][i] = G - Gc[(size_t)i * nchrom + c];
-        }
-        for (size_t c = 0; c < nchrom; ++c) {
-            std::copy(gc[c].begin(), gc[c].end(), Zc.begin() + (size_t)q * N);
-            fit(qn, nulls[c]);
-            iters += nulls[c].iters;
-        }
-    }
+// The score test of one run: hgibbs_marker_class_sums' sums, and per marker the plain test's row and the row that is written (the plain
+// one until correct_run puts a correction's numbers there)
+struct RunScores {
+    unsigned m0 = 0, cnt = 0;
+    std::vector<double> sums, t, v; // t, v: one marker's b_j and L^-1 t
+    std::vector<AssocRow> score, row;
+    explicit RunScores(int qn) : t(qn), v(qn) {}
+};
 
-    // one hgibbs_marker_class_sums per run: U = [y - mu, w z_1 .. w z_qn, d]
-    std::vector<double> U((size_t)K * N), sums, t(qn), v(qn);
-    std::copy(d.begin(), d.end(), U.begin() + (size_t)(K - 1) * N);
-    // corr_*: the run's list of markers that get a correction, --assoc-spa's or --assoc-firth's (never both), and its counters
-    unsigned long long written = 0, corr_n = 0, corr_valid = 0;
-    double corr_ms = 0.0;
-    std::vector<double> Uv, Vv, corr_B, corr_xv, corr_s;
-    std::vector<uint8_t> tested;
-    std::vector<long> corr_at; // the marker's entry in the run's list, or -1
-    std::vector<uint32_t> corr_mk;
-    std::vector<hgibbs_spa_root> spa_roots;
-    std::vector<hgibbs_firth_rec> firth_recs;
-    for (size_t ru = 0; ru < nruns; ++ru) {
-        const unsigned m0 = runs[ru], cnt = runs[ru + 1] - runs[ru];
-        const Null& nm = nulls[gcol ? (size_t)cj[m0] : 0];
-        if (gcol) std::copy(gc[(size_t)cj[m0]].begin(), gc[(size_t)cj[m0]].end(), Zc.begin() + (size_t)q * N);
-        for (unsigned i = 0; i < N; ++i) {
-            U[i] = d[i] - nm.mu[i];
-            for (int a = 0; a < qn; ++a) U[(size_t)(1 + a) * N + i] = nm.w[i] * Zc[(size_t)a * N + i];
+// One hgibbs_marker_class_sums for the run `ru`, then the score test per marker; a set member's plain score and L^-1 t go to sp, a
+// marker that gets a correction to cx's list with b_j = (Z'WZ)^-1 Z'W x_j, the value of each genotype code and the score
+void score_run(AssocFrame& fr, const LogitNulls& nl, const LogitNull& nm, size_t ru, RunScores& rs, Correction& cx, SetPlan& sp)
+{
+    const int qn = nl.qn, K = nl.K;
+    const unsigned m0 = rs.m0 = fr.cr.runs[ru], cnt = rs.cnt = fr.cr.runs[ru + 1] - fr.cr.runs[ru];
+    std::vector<double>&t = rs.t, &v = rs.v;
+    rs.sums.resize((size_t)cnt * K * 4);
+    hg_check(hgibbs_marker_class_sums(fr.dev, m0, cnt, K, nl.U.data(), rs.sums.data()), "hgibbs_marker_class_sums");
+    fr.add_ms(hgibbs_last_marker_class_sums_ms, "hgibbs_last_marker_class_sums_ms", fr.ms);
+    rs.score.assign(cnt, AssocRow{0.0, 0.0, 0.0, 0.0, -2});
+    rs.row = rs.score;
+    cx.mk.clear();
+    cx.B.clear();
+    cx.xv.clear();
+    cx.s.clear();
+    for (unsigned jj = 0; jj < cnt; ++jj) {
+        const unsigned j = m0 + jj;
+        const double m = fr.mave[j], sd = fr.mstd[j];
+        const double* S = &rs.sums[(size_t)jj * K * 4];
+        auto xu = [&](int k) { return sd * (S[4 * k + 1] + 2.0 * S[4 * k + 2] - m * (S[4 * k] + S[4 * k + 1] + S[4 * k + 2])); }; // x_j'u_k
+        const double xwx = sd * sd * (m * m * S[4] + (1.0 - m) * (1.0 - m) * S[5] + (2.0 - m) * (2.0 - m) * S[6]);
+        double V = xwx;
+        for (int a = 0; a < qn; ++a) { // v = L^-1 t: t'(Z'WZ)^-1 t = v'v
+            double e = xu(1 + a);
+            for (int p = 0; p < a; ++p) e -= nm.L[(size_t)a + (size_t)qn * p] * v[p];
+            v[a] = e / nm.L[(size_t)a + (size_t)qn * a];
+            V -= v[a] * v[a];
         }
-        sums.resize((size_t)cnt * K * 4);
-        hg_check(hgibbs_marker_class_sums(dev, m0, cnt, K, U.data(), sums.data()), "hgibbs_marker_class_sums");
-        double tms = 0.0;
-        hg_check(hgibbs_last_marker_class_sums_ms(dev, &tms), "hgibbs_last_marker_class_sums_ms");
-        ms += tms;
-        // the score test per marker; with --assoc-spa the markers beyond spa_sd standard deviations are listed for one hgibbs_spa_roots call,
-        // with --assoc-firth the markers whose P is at most firth_p for one hgibbs_firth_fit call
-        Uv.assign(cnt, 0.0);
-        Vv.assign(cnt, 0.0);
-        tested.assign(cnt, 0);
-        corr_at.assign(cnt, -1);
-        corr_mk.clear();
-        corr_B.clear();
-        corr_xv.clear();
-        corr_s.clear();
-        for (unsigned jj = 0; jj < cnt; ++jj) {
-            const unsigned j = m0 + jj;
-            const double m = mave[j], sd = mstd[j];
-            const double* S = &sums[(size_t)jj * K * 4];
-            auto xu = [&](int k) { return sd * (S[4 * k + 1] + 2.0 * S[4 * k + 2] - m * (S[4 * k] + S[4 * k + 1] + S[4 * k + 2])); }; // x_j'u_k
-            const double xwx = sd * sd * (m * m * S[4] + (1.0 - m) * (1.0 - m) * S[5] + (2.0 - m) * (2.0 - m) * S[6]);
-            double V = xwx;
-            for (int a = 0; a < qn; ++a) { // v = L^-1 t: t'(Z'WZ)^-1 t = v'v
-                double e = xu(1 + a);
-                for (int p = 0; p < a; ++p) e -= nm.L[(size_t)a + (size_t)qn * p] * v[p];
-                v[a] = e / nm.L[(size_t)a + (size_t)qn * a];
-                V -= v[a] * v[a];
-            }
-            if (!std::isfinite(sd) || !(V > 1e-9 * xwx)) continue;
-            tested[jj] = 1;
-            Uv[jj] = xu(0);
-            Vv[jj] = V;
-            if (sets_on && mem_at[j] >= 0) { // a set member keeps its plain score and L^-1 t
-                const size_t e = (size_t)mem_at[j];
-                mem_ok[e] = 1;
-                mem_U[e] = Uv[jj];
-                std::copy(v.begin(), v.begin() + qn, mem_v.begin() + e * (size_t)qn);
-            }
-            if ((spa && std::isfinite(V) && std::fabs(Uv[jj]) / std::sqrt(V) > spa_sd) ||
-                (firth && std::isfinite(V) && std::erfc(std::sqrt(Uv[jj] * Uv[jj] / V / 2.0)) <= firth_p)) {
-                // b_j = (Z'WZ)^-1 Z'W x_j = L^-T v, the value of each genotype code, the score
-                for (int a = qn - 1; a >= 0; --a) {
-                    double e = v[a];
-                    for (int p = a + 1; p < qn; ++p) e -= nm.L[(size_t)p + (size_t)qn * a] * t[p];
-                    t[a] = e / nm.L[(size_t)a + (size_t)qn * a];
-                }
-                corr_at[jj] = (long)corr_mk.size();
-                corr_mk.push_back(j);
-                corr_B.insert(corr_B.end(), t.begin(), t.end());
-                for (const double x : {(0.0 - m) * sd, (1.0 - m) * sd, (2.0 - m) * sd, 0.0}) corr_xv.push_back(x);
-                corr_s.push_back(Uv[jj]);
-            }
+        if (!std::isfinite(sd) || !(V > 1e-9 * xwx)) continue;
+        const double Uj = xu(0), chisq = Uj * Uj / V;
+        rs.row[jj] = rs.score[jj] = {sd * Uj / V, sd / std::sqrt(V), chisq, std::erfc(std::sqrt(chisq / 2.0)), -1};
+        if (sp.on && sp.mem_at[j] >= 0) { // a set member keeps its plain score and L^-1 t
+            const size_t e = (size_t)sp.mem_at[j];
+            sp.mem_ok[e] = 1;
+            sp.mem_U[e] = Uj;
+            std::copy(v.begin(), v.begin() + qn, sp.mem_v.begin() + e * (size_t)qn);
         }
-        spa_roots.resize(spa ? corr_mk.size() : 0);
-        firth_recs.resize(firth ? corr_mk.size() : 0);
-        if (firth && !corr_mk.empty()) {
-            hg_check(hgibbs_firth_fit(dev, (uint32_t)corr_mk.size(), corr_mk.data(), qn, Zc.data(), nm.mu.data(), corr_B.data(), corr_xv.data(), corr_s.data(),
-                                      firth_recs.data()), "hgibbs_firth_fit");
-            double sms = 0.0;
-            hg_check(hgibbs_last_firth_ms(dev, &sms), "hgibbs_last_firth_ms");
-            corr_ms += sms;
+        if (!cx.wants(Uj, V)) continue;
+        for (int a = qn - 1; a >= 0; --a) { // b_j = L^-T v
+            double e = v[a];
+            for (int p = a + 1; p < qn; ++p) e -= nm.L[(size_t)p + (size_t)qn * a] * t[p];
+            t[a] = e / nm.L[(size_t)a + (size_t)qn * a];
         }
-        if (spa && !corr_mk.empty()) {
-            hg_check(hgibbs_spa_roots(dev, (uint32_t)corr_mk.size(), corr_mk.data(), qn, Zc.data(), nm.mu.data(), corr_B.data(), corr_xv.data(), corr_s.data(),
-                                      spa_roots.data()), "hgibbs_spa_roots");
-            double sms = 0.0;
-            hg_check(hgibbs_last_spa_ms(dev, &sms), "hgibbs_last_spa_ms");
-            corr_ms += sms;
+        cx.mk.push_back(j);
+        cx.B.insert(cx.B.end(), t.begin(), t.end());
+        for (const double x : {(0.0 - m) * sd, (1.0 - m) * sd, (2.0 - m) * sd, 0.0}) cx.xv.push_back(x);
+        cx.s.push_back(Uj);
+    }
+}
+
+// The correction of one run: the one device call that applies to cx's list, then per entry the row's four numbers and whether the
+// correction holds; where it does not, the entry's row keeps the score test's numbers
+void correct_run(AssocFrame& fr, const LogitNulls& nl, const LogitNull& nm, RunScores& rs, Correction& cx)
+{
+    const uint32_t ne = (uint32_t)cx.mk.size();
+    if (ne == 0) return;
+    std::vector<hgibbs_spa_root> roots(cx.firth ? 0 : ne);
+    std::vector<hgibbs_firth_rec> recs(cx.firth ? ne : 0);
+    if (cx.firth) {
+        hg_check(hgibbs_firth_fit(fr.dev, ne, cx.mk.data(), nl.qn, nl.Zc.data(), nm.mu.data(), cx.B.data(), cx.xv.data(), cx.s.data(), recs.data()), "hgibbs_firth_fit");
+        fr.add_ms(hgibbs_last_firth_ms, "hgibbs_last_firth_ms", cx.ms);
+    } else {
+        hg_check(hgibbs_spa_roots(fr.dev, ne, cx.mk.data(), nl.qn, nl.Zc.data(), nm.mu.data(), cx.B.data(), cx.xv.data(), cx.s.data(), roots.data()), "hgibbs_spa_roots");
+        fr.add_ms(hgibbs_last_spa_ms, "hgibbs_last_spa_ms", cx.ms);
+    }
+    for (uint32_t e = 0; e < ne; ++e) {
+        const double sd = fr.mstd[cx.mk[e]];
+        AssocRow& r = rs.row[cx.mk[e] - rs.m0];
+        double stat = 0.0, se = 0.0, p = 0.0;
+        if (cx.firth) {
+            hg_check(hgibbs_firth_stats(cx.s[e], &recs[e], &stat, &se, &p, &r.ok), "hgibbs_firth_stats");
+            if (r.ok) r = {sd * recs[e].beta, sd * se, stat, p, r.ok};
+        } else {
+            hg_check(hgibbs_spa_pvalue(cx.s[e], &roots[e], nullptr, nullptr, &p, &r.ok), "hgibbs_spa_pvalue");
+            if (r.ok) r.p = p;
         }
-        for (unsigned jj = 0; jj < cnt; ++jj) {
-            const unsigned j = m0 + jj;
-            const double m = mave[j], sd = mstd[j];
-            const unsigned long long called = (unsigned long long)N - nmiss[j];
-            const double* S = &sums[(size_t)jj * K * 4];
-            std::fprintf(f, "%s %s %lld %s %s %.12g %llu ", bim.chr[j].c_str(), bim.id[j].c_str(), bim.bp[j], bim.a1[j].c_str(), bim.a2[j].c_str(),
-                         m / 2.0, called);
-            double p_norm = 0.0, beta_score = 0.0, se_score = 0.0;
-            int corr_ok = -1; // -1 not applied, 0 applied and fell back to the normal P (the score test), 1 applied and valid
-            if (!tested[jj]) std::fprintf(f, "NA NA NA NA");
-            else {
-                const double Uj = Uv[jj], V = Vv[jj], chisq = Uj * Uj / V;
-                double p = p_norm = std::erfc(std::sqrt(chisq / 2.0));
-                double beta = beta_score = sd * Uj / V, se = se_score = sd / std::sqrt(V), stat = chisq;
-                if (firth && corr_at[jj] >= 0) {
-                    double lrt = 0.0, fse = 0.0, fp = 0.0;
-                    hg_check(hgibbs_firth_stats(Uj, &firth_recs[(size_t)corr_at[jj]], &lrt, &fse, &fp, &corr_ok), "hgibbs_firth_stats");
-                    if (corr_ok) {
-                        beta = sd * firth_recs[(size_t)corr_at[jj]].beta;
-                        se = sd * fse;
-                        stat = lrt;
-                        p = fp;
-                    }
-                    ++corr_n;
-                    corr_valid += corr_ok ? 1u : 0u;
-                } else if (corr_at[jj] >= 0) {
-                    double ps = 0.0;
-                    hg_check(hgibbs_spa_pvalue(Uj, &spa_roots[(size_t)corr_at[jj]], nullptr, nullptr, &ps, &corr_ok), "hgibbs_spa_pvalue");
-                    if (corr_ok) p = ps;
-                    ++corr_n;
-                    corr_valid += corr_ok ? 1u : 0u;
-                }
-                std::fprintf(f, "%.12g %.12g %.12g %.12g", beta, se, stat, p);
-            }
-            // the sums of the case indicator are exact counts of the cases by genotype; the controls are the rest of the marker's stats
-            const double* Sd = S + 4 * (K - 1);
-            const double c1 = Sd[1], c2 = Sd[2], ca = Sd[0] + c1 + c2;
-            const double k1 = (double)n1[j] - c1, k2 = (double)n2[j] - c2, ka = (double)called - ca;
-            std::fprintf(f, " %.12g %.12g", ca, ka);
-            for (const double fr : {ca > 0.0 ? (c1 + 2.0 * c2) / (2.0 * ca) : -1.0, ka > 0.0 ? (k1 + 2.0 * k2) / (2.0 * ka) : -1.0}) {
-                if (fr < 0.0) std::fprintf(f, " NA");
-                else std::fprintf(f, " %.12g", fr);
-            }
-            if (spa) {
-                if (!tested[jj]) std::fprintf(f, " NA NA");
-                else if (corr_ok < 0) std::fprintf(f, " %.12g NA", p_norm);
-                else std::fprintf(f, " %.12g %d", p_norm, corr_ok);
-            } else if (firth) {
-                if (!tested[jj]) std::fprintf(f, " NA NA NA NA");
-                else if (corr_ok < 0) std::fprintf(f, " %.12g %.12g %.12g NA", p_norm, beta_score, se_score);
-                else std::fprintf(f, " %.12g %.12g %.12g %d", p_norm, beta_score, se_score, corr_ok);
-            }
-            std::fprintf(f, "\n");
-            ++written;
+        ++cx.n;
+        cx.valid += r.ok ? 1u : 0u;
+    }
+}
+
+// The rows of one run: the frame's prefix, BETA SE CHISQ P (the correction's where the marker has one), the case/control columns and
+// the correction's trailing columns
+void write_rows(AssocFrame& fr, int K, const RunScores& rs, const Correction& cx)
+{
+    for (unsigned jj = 0; jj < rs.cnt; ++jj) {
+        const unsigned j = rs.m0 + jj;
+        const AssocRow &sc = rs.score[jj], &r = rs.row[jj];
+        auto num = [&](double x) { return num_or_na(x, sc.ok > -2); };
+        // the sums of the case indicator are exact counts of the cases by genotype; the controls are the rest of the marker's stats
+        const double* Sd = &rs.sums[(size_t)jj * K * 4] + 4 * (K - 1);
+        const double c1 = Sd[1], c2 = Sd[2], ca = Sd[0] + c1 + c2;
+        const double k1 = (double)fr.n1[j] - c1, k2 = (double)fr.n2[j] - c2, ka = (double)fr.called(j) - ca;
+        fr.row_prefix(j);
+        std::fprintf(fr.f, "%s %s %s %s %.12g %.12g %s %s", num(r.beta).c_str(), num(r.se).c_str(), num(r.stat).c_str(), num(r.p).c_str(), ca, ka,
+                     num_or_na((c1 + 2.0 * c2) / (2.0 * ca), ca > 0.0).c_str(), num_or_na((k1 + 2.0 * k2) / (2.0 * ka), ka > 0.0).c_str());
+        if (cx.spa || cx.firth) std::fprintf(fr.f, " %s", num(sc.p).c_str()); // P_NORM
+        if (cx.firth) std::fprintf(fr.f, " %s %s", num(sc.beta).c_str(), num(sc.se).c_str()); // BETA_SCORE SE_SCORE
+        if (cx.spa || cx.firth) std::fprintf(fr.f, " %s", r.ok >= 0 ? std::to_string(r.ok).c_str() : "NA"); // SPA or FIRTH
+        std::fprintf(fr.f, "\n");
+        ++fr.written;
+    }
+}
+
+// The sets of the run `ru`: their tested members within the MAF bound, packed into hgibbs_set_gram calls of at most SET_CHUNK entries;
+// per set Phi = out - (L^-1 t_j).(L^-1 t_k) with hgibbs_set_gram's out under this run's w, then per copy of A1
+void sets_run(const AssocFrame& fr, const LogitNull& nm, int qn, size_t ru, SetPlan& sp)
+{
+    constexpr uint64_t SET_CHUNK = 1ull << 22; // entries of out per hgibbs_set_gram call (a set of 1024 has 2^20)
+    std::vector<size_t> todo;
+    for (size_t s = 0; s < sp.msets.idx.size(); ++s)
+        if (sp.set_run[s] == ru) todo.push_back(s);
+    std::vector<std::vector<uint32_t>> used(todo.size());
+    for (size_t k = 0; k < todo.size(); ++k) {
+        for (const uint32_t j : sp.msets.idx[todo[k]]) {
+            const double p = fr.mave[j] / 2.0;
+            if (sp.mem_ok[(size_t)sp.mem_at[j]] && std::min(p, 1.0 - p) <= sp.maf) used[k].push_back(j);
         }
-        // the sets of this run: Phi = out - (L^-1 t_j).(L^-1 t_k) with hgibbs_set_gram's out under this run's w, then per copy of A1
-        if (sets_on) {
-            constexpr uint64_t SET_CHUNK = 1ull << 22; // entries of out per hgibbs_set_gram call (a set of 1024 has 2^20)
-            std::vector<size_t> todo;
-            for (size_t s = 0; s < msets.idx.size(); ++s)
-                if (set_run[s] == ru) todo.push_back(s);
-            std::vector<std::vector<uint32_t>> used(todo.size());
-            for (size_t k = 0; k < todo.size(); ++k) {
-                for (const uint32_t j : msets.idx[todo[k]]) {
-                    const double p = mave[j] / 2.0;
-                    if (mem_ok[(size_t)mem_at[j]] && std::min(p, 1.0 - p) <= setMaf) used[k].push_back(j);
-                }
-                set_used[todo[k]] = used[k].size();
-            }
-            for (size_t k0 = 0; k0 < todo.size();) {
-                std::vector<uint64_t> off{0};
-                std::vector<uint32_t> gidx;
-                std::vector<size_t> part;
-                uint64_t E = 0;
-                size_t k1 = k0;
-                for (; k1 < todo.size(); ++k1) {
-                    const uint64_t mm = (uint64_t)used[k1].size() * used[k1].size();
-                    if (!part.empty() && E + mm > SET_CHUNK) break;
-                    if (mm == 0) continue;
-                    part.push_back(k1);
-                    gidx.insert(gidx.end(), used[k1].begin(), used[k1].end());
-                    off.push_back(gidx.size());
-                    E += mm;
-                }
-                k0 = k1;
-                if (part.empty()) continue;
-                std::vector<double> G(E);
-                hg_check(hgibbs_set_gram(dev, (uint32_t)part.size(), off.data(), gidx.data(), nm.w.data(), G.data(), nullptr), "hgibbs_set_gram");
-                double gms = 0.0;
-                hg_check(hgibbs_last_set_gram_ms(dev, &gms), "hgibbs_last_set_gram_ms");
-                sets_ms += gms;
-                uint64_t b0 = 0;
-                for (const size_t k : part) {
-                    const std::vector<uint32_t>& ix = used[k];
-                    const size_t m = ix.size();
-                    std::vector<double> Ug(m), Ph(m * m), aw(m);
-                    const double lc = std::lgamma(setA + setB) - std::lgamma(setA) - std::lgamma(setB);
-                    for (size_t a = 0; a < m; ++a) {
-                        const size_t ea = (size_t)mem_at[ix[a]];
-                        const double p = mave[ix[a]] / 2.0, maf = std::min(p, 1.0 - p);
-                        Ug[a] = mem_U[ea] / mstd[ix[a]];
-                        aw[a] = std::exp(lc + (setA - 1.0) * std::log(maf) + (setB - 1.0) * std::log1p(-maf));
-                        for (size_t b = 0; b < m; ++b) {
-                            const size_t eb = (size_t)mem_at[ix[b]];
-                            double tt = 0.0;
-                            for (int c = 0; c < qn; ++c) tt += mem_v[ea * (size_t)qn + c] * mem_v[eb * (size_t)qn + c];
-                            Ph[a * m + b] = (G[b0 + a * m + b] - tt) / (mstd[ix[a]] * mstd[ix[b]]);
-                        }
-                    }
-                    hg_check(hgibbs_set_tests((uint32_t)m, Ug.data(), Ph.data(), aw.data(), &set_res[todo[k]]), "hgibbs_set_tests");
-                    b0 += (uint64_t)m * m;
+        sp.used[todo[k]] = used[k].size();
+    }
+    for (size_t k0 = 0; k0 < todo.size();) {
+        std::vector<uint64_t> off{0};
+        std::vector<uint32_t> gidx;
+        std::vector<size_t> part;
+        uint64_t E = 0;
+        size_t k1 = k0;
+        for (; k1 < todo.size(); ++k1) {
+            const uint64_t mm = (uint64_t)used[k1].size() * used[k1].size();
+            if (!part.empty() && E + mm > SET_CHUNK) break;
+            if (mm == 0) continue;
+            part.push_back(k1);
+            gidx.insert(gidx.end(), used[k1].begin(), used[k1].end());
+            off.push_back(gidx.size());
+            E += mm;
+        }
+        k0 = k1;
+        if (part.empty()) continue;
+        std::vector<double> G(E);
+        hg_check(hgibbs_set_gram(fr.dev, (uint32_t)part.size(), off.data(), gidx.data(), nm.w.data(), G.data(), nullptr), "hgibbs_set_gram");
+        fr.add_ms(hgibbs_last_set_gram_ms, "hgibbs_last_set_gram_ms", sp.ms);
+        uint64_t b0 = 0;
+        for (const size_t k : part) {
+            const std::vector<uint32_t>& ix = used[k];
+            const size_t m = ix.size();
+            std::vector<double> Ug(m), Ph(m * m), aw(m);
+            const double lc = std::lgamma(sp.a + sp.b) - std::lgamma(sp.a) - std::lgamma(sp.b);
+            for (size_t a = 0; a < m; ++a) {
+                const size_t ea = (size_t)sp.mem_at[ix[a]];
+                const double p = fr.mave[ix[a]] / 2.0, maf = std::min(p, 1.0 - p);
+                Ug[a] = sp.mem_U[ea] / fr.mstd[ix[a]];
+                aw[a] = std::exp(lc + (sp.a - 1.0) * std::log(maf) + (sp.b - 1.0) * std::log1p(-maf));
+                for (size_t b = 0; b < m; ++b) {
+                    const size_t eb = (size_t)sp.mem_at[ix[b]];
+                    double tt = 0.0;
+                    for (int c = 0; c < qn; ++c) tt += sp.mem_v[ea * (size_t)qn + c] * sp.mem_v[eb * (size_t)qn + c];
+                    Ph[a * m + b] = (G[b0 + a * m + b] - tt) / (fr.mstd[ix[a]] * fr.mstd[ix[b]]);
                 }
             }
+            hg_check(hgibbs_set_tests((uint32_t)m, Ug.data(), Ph.data(), aw.data(), &sp.res[todo[k]]), "hgibbs_set_tests");
+            b0 += (uint64_t)m * m;
         }
     }
-    hgibbs_destroy(dev);
-    close_out(f, out);
-    if (sets_on) {
-        FILE* fs = open_out(sets_out, "w");
-        std::fprintf(fs, "SET\tCHR\tBP_FIRST\tBP_LAST\tNSNP\tNUSED\tNEIG\tQ\tP_SKAT\tSKAT_OK\tT_BURDEN\tP_BURDEN\n");
-        auto num = [&](double x) {
-            if (std::isfinite(x)) std::fprintf(fs, "\t%.12g", x);
-            else std::fprintf(fs, "\tNA");
-        };
-        for (size_t s = 0; s < msets.idx.size(); ++s) {
-            const std::vector<uint32_t>& ix = msets.idx[s];
-            std::fprintf(fs, "%s", msets.name[s].c_str());
-            if (ix.empty()) std::fprintf(fs, "\tNA\tNA\tNA");
-            else {
-                long long lo = bim.bp[ix[0]], hi = lo;
-                for (const uint32_t j : ix) {
-                    lo = std::min(lo, bim.bp[j]);
-                    hi = std::max(hi, bim.bp[j]);
-                }
-                std::fprintf(fs, "\t%s\t%lld\t%lld", bim.chr[ix[0]].c_str(), lo, hi);
-            }
-            std::fprintf(fs, "\t%zu\t%zu", ix.size(), set_used[s]);
-            if (set_used[s] == 0) std::fprintf(fs, "\t0\tNA\tNA\tNA\tNA\tNA\n");
-            else {
-                const hgibbs_set_result& r = set_res[s];
-                std::fprintf(fs, "\t%d", r.neig);
-                num(r.q);
-                num(r.p_skat);
-                if (r.neig > 0) std::fprintf(fs, "\t%d", r.skat_ok);
-                else std::fprintf(fs, "\tNA");
-                num(r.t_burden);
-                num(r.p_burden);
-                std::fprintf(fs, "\n");
-            }
+}
+
+void write_sets_table(const BimRows& bim, const SetPlan& sp)
+{
+    FILE* fs = open_out(sp.out, "w");
+    std::fprintf(fs, "SET\tCHR\tBP_FIRST\tBP_LAST\tNSNP\tNUSED\tNEIG\tQ\tP_SKAT\tSKAT_OK\tT_BURDEN\tP_BURDEN\n");
+    auto num = [](double x) { return num_or_na(x, std::isfinite(x)); };
+    for (size_t s = 0; s < sp.msets.idx.size(); ++s) {
+        const std::vector<uint32_t>& ix = sp.msets.idx[s];
+        std::fprintf(fs, "%s", sp.msets.name[s].c_str());
+        if (ix.empty()) std::fprintf(fs, "\tNA\tNA\tNA");
+        else {
+            const auto lh = std::minmax_element(ix.begin(), ix.end(), [&](uint32_t a, uint32_t b) { return bim.bp[a] < bim.bp[b]; });
+            std::fprintf(fs, "\t%s\t%lld\t%lld", bim.chr[ix[0]].c_str(), bim.bp[*lh.first], bim.bp[*lh.second]);
         }
-        close_out(fs, sets_out);
+        std::fprintf(fs, "\t%zu\t%zu", ix.size(), sp.used[s]);
+        const hgibbs_set_result& r = sp.res[s];
+        if (sp.used[s] == 0) std::fprintf(fs, "\t0\tNA\tNA\tNA\tNA\tNA\n");
+        else
+            std::fprintf(fs, "\t%d\t%s\t%s\t%s\t%s\t%s\n", r.neig, num(r.q).c_str(), num(r.p_skat).c_str(), r.neig > 0 ? std::to_string(r.skat_ok).c_str() : "NA",
+                         num(r.t_burden).c_str(), num(r.p_burden).c_str());
     }
-    if (sets_on)
-        std::printf("ASSOC  : wrote %llu rows to %s (%u cases, %u controls, %d iterations of %zu null models, %.3f ms on the device), %zu sets to %s (%.3f ms of hgibbs_set_gram on the device)\n",
-                    written, out.c_str(), ncase, N - ncase, iters, nulls.size(), ms, msets.idx.size(), sets_out.c_str(), sets_ms);
-    else
-        std::printf("ASSOC  : wrote %llu rows to %s (%u cases, %u controls, %d iterations of %zu null models, %.3f ms on the device)\n", written, out.c_str(),
-                    ncase, N - ncase, iters, nulls.size(), ms);
-    if (spa)
-        std::printf("ASSOC  : SPA on %llu markers (|z| > %g): %llu valid, %llu fell back, %.3f ms on the device\n", corr_n, spa_sd, corr_valid, corr_n - corr_valid,
-                    corr_ms);
-    if (firth)
-        std::printf("ASSOC  : Firth on %llu markers (P <= %g): %llu valid, %llu fell back, %.3f ms on the device\n", corr_n, firth_p, corr_valid, corr_n - corr_valid,
-                    corr_ms);
+    close_out(fs, sp.out);
+}
+
+int run_assoc_logistic(const Options& opt, const Cohort& co, const std::vector<double>& y_raw, const std::vector<double>& covX, int C)
+{
+    AssocFrame fr(opt, co, covX, C, true);
+    LogitNulls nl(fr, y_raw);
+    SetPlan sp(fr, nl.qn);
+    Correction cx(opt);
+    fr.open(std::string("CHR SNP BP A1 A2 FREQ N BETA SE CHISQ P N_CASE N_CTRL FREQ_CASE FREQ_CTRL") +
+            (cx.spa ? " P_NORM SPA" : cx.firth ? " P_NORM BETA_SCORE SE_SCORE FIRTH" : ""));
+    nl.fit_chromosomes(fr);
+    RunScores rs(nl.qn);
+    for (size_t ru = 0; ru < fr.cr.nruns; ++ru) {
+        const LogitNull& nm = nl.begin_run(fr, fr.cr.runs[ru]);
+        score_run(fr, nl, nm, ru, rs, cx, sp);
+        correct_run(fr, nl, nm, rs, cx);
+        write_rows(fr, nl.K, rs, cx);
+        if (sp.on) sets_run(fr, nm, nl.qn, ru, sp);
+    }
+    fr.close();
+    if (sp.on) write_sets_table(fr.bim, sp);
+    std::printf("ASSOC  : wrote %llu rows to %s (%u cases, %u controls, %d iterations of %zu null models, %.3f ms on the device)", fr.written, fr.out.c_str(), nl.ncase,
+                fr.N - nl.ncase, nl.iters, nl.nulls.size(), fr.ms);
+    if (sp.on) std::printf(", %zu sets to %s (%.3f ms of hgibbs_set_gram on the device)", sp.msets.idx.size(), sp.out.c_str(), sp.ms);
+    std::printf("\n");
+    if (cx.spa || cx.firth)
+        std::printf("ASSOC  : %s on %llu markers (%s %g): %llu valid, %llu fell back, %.3f ms on the device\n", cx.spa ? "SPA" : "Firth", cx.n, cx.spa ? "|z| >" : "P <=",
+                    cx.thr, cx.valid, cx.n - cx.valid, cx.ms);
     return 0;
 }
 
@@ -2402,62 +2468,6 @@ int run_pca(const Options& opt, const Cohort& co)
 }
 
 // ---- --pve: posterior variance explained by marker sets ----
-// The SETNAME SNPID file of --pve-sets, --ld-score-sets and --assoc-sets: the sets in the order in which the file first names them.
-// unknown: null refuses an id the .bim lacks; otherwise such an id is counted there and left out (a set may end up empty).
-MarkerSets read_sets_file(const std::string& path, const std::string& bedFile, const BimRows& bim, unsigned Mtot, size_t* unknown)
-{
-    MarkerSets ms;
-    std::ifstream in(path);
-    if (!in) fatal("Error: can not open the file [" + path + "] to read.");
-    std::map<std::string, uint32_t> snp;
-    for (unsigned j = 0; j < Mtot; ++j) snp.emplace(bim.id[j], j);
-    std::map<std::string, size_t> at;
-    std::map<std::pair<size_t, uint32_t>, int> seen;
-    std::string line;
-    size_t lineno = 0;
-    while (std::getline(in, line)) {
-        ++lineno;
-        const std::vector<std::string> col = tokens(line, " \t\r");
-        if (col.empty()) continue;
-        const std::string where = "FATAL  : " + path + " line " + std::to_string(lineno) + ": ";
-        if (col.size() != 2) fatal(where + "expected SETNAME SNPID");
-        const auto j = snp.find(col[1]);
-        if (j == snp.end() && !unknown) fatal(where + "SNP " + col[1] + " is not among the first " + std::to_string(Mtot) + " markers of " + bedFile + ".bim");
-        auto it = at.find(col[0]);
-        if (it == at.end()) {
-            ms.name.push_back(col[0]);
-            ms.idx.emplace_back();
-            it = at.emplace(col[0], ms.idx.size() - 1).first;
-        }
-        if (j == snp.end()) {
-            ++*unknown;
-            continue;
-        }
-        if (!seen.emplace(std::make_pair(it->second, j->second), 1).second) fatal(where + "SNP " + col[1] + " is given twice for set " + col[0]);
-        ms.idx[it->second].push_back(j->second);
-    }
-    if (ms.idx.empty()) fatal("FATAL  : " + path + " names no set");
-    for (auto& r : ms.idx) std::sort(r.begin(), r.end());
-    return ms;
-}
-
-// The groups of --pve-groups and --ld-score-groups: one set per group number of the group index file, in ascending order of the number
-MarkerSets sets_from_groups(const Options& opt, unsigned Mtot)
-{
-    MarkerSets ms;
-    const std::vector<int32_t> groups = read_groups(opt.groupIndexFile);
-    if (groups.size() < Mtot) fatal("FATAL  : group file covers fewer markers than --number-markers");
-    std::map<int32_t, size_t> at;
-    for (unsigned j = 0; j < Mtot; ++j) at.emplace(groups[j], 0);
-    for (auto& g : at) {
-        g.second = ms.idx.size();
-        ms.name.push_back("group" + std::to_string(g.first));
-        ms.idx.emplace_back();
-    }
-    for (unsigned j = 0; j < Mtot; ++j) ms.idx[at[groups[j]]].push_back(j);
-    return ms;
-}
-
 struct PveSets : MarkerSets {
     std::string how; // how the sets were defined, for the report
 };

@@ -92,6 +92,21 @@ def test_grid_against_the_restatement(n, q):
     dev.close()
 
 
+@pytest.mark.parametrize("q", (1, 5))
+def test_k2_0_is_that_of_spa_roots_bit_for_bit(q):
+    """Both kernels form a_i from one function (spa_adjusted, hg_spa.hip.h) and their terms from one logistic point: at t = 0 each sums
+    a^2 mu (1 - mu) over the same rows per thread and through the same tree, so K''(0) of the two records has the same bits.  261 rows
+    are one full stride of the 256 threads and a tail; the 64 markers of the grid, without the flat entry at the list's end."""
+    case = F.fit_case(261, q)
+    dev = device(case["geno"])
+    idx = np.arange(F.GRID_M)
+    args = (case["markers"][idx], case["Z"], case["mu"], case["B"][idx], case["xv"][idx], case["s"][idx])
+    firth, spa = dev.firth_fit(*args), dev.spa_roots(*args)
+    for e in idx:
+        assert firth[e].k2_0 > 0.0 and firth[e].k2_0.hex() == spa[e].k2_0.hex(), (e, firth[e].k2_0.hex(), spa[e].k2_0.hex())
+    dev.close()
+
+
 def test_refusals_leave_the_handle_usable():
     case = F.fit_case(261, 5)
     dev = device(case["geno"])

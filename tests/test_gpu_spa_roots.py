@@ -101,6 +101,7 @@ def test_refusals_leave_the_handle_usable():
         sums = dev.marker_class_sums(np.ones((1, n)))
         assert sums.shape == (R.GRID_M, 1, 4) and np.all(sums.sum(axis=2) == n)
         assert raw(dev.spa_roots(**good)) == want
+        assert dev.last_spa_ms() > 0.0
 
     bad = [
         (spoiled("markers", 3, R.GRID_M), "markers[3] = 64 out of range (M = 64)"),
@@ -134,11 +135,15 @@ def test_refusals_leave_the_handle_usable():
         a[missing] = None
         assert L.hgibbs_spa_roots(dev.h, 8, a["markers"], q, *[a[k] for k in order], a["out"]) != 0
         assert "hgibbs_spa_roots: null argument" in L.hgibbs_last_error().decode()
+        assert dev.last_spa_ms() == 0.0
         usable()
     assert L.hgibbs_spa_roots(dev.h, 8, ptr["markers"], 0, *[ptr[k] for k in order], out) != 0
     assert "hgibbs_spa_roots: q = 0, must be in [1, 64]" in L.hgibbs_last_error().decode()
+    assert dev.last_spa_ms() == 0.0
+    usable()
     assert L.hgibbs_spa_roots(None, 8, ptr["markers"], q, *[ptr[k] for k in order], out) != 0
     assert "hgibbs_spa_roots: null handle" in L.hgibbs_last_error().decode()
+    assert L.hgibbs_last_spa_ms(dev.h, None) != 0 and L.hgibbs_last_spa_ms(None, C.byref(C.c_double())) != 0
     # an empty list touches nothing
     before = raw(out)
     assert L.hgibbs_spa_roots(dev.h, 0, ptr["markers"], q, *[ptr[k] for k in order], out) == 0 and raw(out) == before
@@ -148,6 +153,7 @@ def test_refusals_leave_the_handle_usable():
     empty = capi.Device(0)
     assert L.hgibbs_spa_roots(empty.h, 8, ptr["markers"], q, *[ptr[k] for k in order], out) != 0
     assert "hgibbs_spa_roots: no genotypes loaded on this handle" in L.hgibbs_last_error().decode()
+    assert empty.last_spa_ms() == 0.0  # (as test_gpu_firth.py has it; the alternation with usable() above is what pins the zeroing)
     empty.close()
 
 
