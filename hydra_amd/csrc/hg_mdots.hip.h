@@ -32,6 +32,19 @@
 //   reuse    workgroup = MD_WAVES waves x MT marker tiles (MT = 4 at TP <= 2: 256 markers), TP vector tiles a pass.  Per slice of 512
 //            individuals the workgroup stages TP x 8 KB of digits in LDS (double-buffered, one barrier a slice) for all its markers:
 //            32 bytes of digits per marker and tile against 128 bytes of codes, 1/4 at K <= 2.  K > 8 takes ceil(K / 8) passes.
+//
+// The frame.  Everything above but the product itself is shared by the operators on the digit image (k_mdots here, k_mclass in
+// hg_mclass.hip.h), on either side of the launch:
+//
+//   md_frame      (device) the workgroup's range and tiles, the staging of the digits, the prefetch of the codes, the slice loop with
+//                 its barrier, and the walk over (marker, vector) at the end.  A kernel owns its accumulators and gives two
+//                 lambdas: the products of one slice, and what to add at one (marker tile m, vector tile t).
+//   md_dword, md_join, md_add   the dword of a k-step, four digit registers as one 64-bit value, the atomic add of a non-zero
+//                 value; k_sgram (hg_sgram.hip.h), which has no LDS stage and a loop of its own, takes only these.
+//   digit_image   (host) k_score_max, k_score_ksum, k_mdots_digits: the scales, sum_i q and the image of K vectors.
+//   md_passes     (host) the passes of at most MD_TPMAX vector tiles: per pass the build (from the operator's table, by tiles in
+//                 the pass and h->any_missing), the grid and the ranges of individuals (mdots_split, MD_SUB_MAX).
+//   kvec_guard    (host) the refusals of an entry point that takes K vectors against markers [m0, m0 + count).
 #pragma once
 
 namespace {
@@ -75,13 +88,39 @@ __global__ __launch_bounds__(64) void k_mdots_digits(const double* __restrict__ 
     img[(((size_t)sub * tiles + t) * 8u + s) * 64u + lane] = w;
 }
 
-// The product.  Workgroup (x, y): marker tiles tw0 + MT w + 0 .. MT - 1 for wave w, tw0 = t0 + MD_WAVES MT x; slices
-// [y sub_per, (y + 1) sub_per) of the n_sub; vector tiles tv0 .. tv0 + ntp - 1 (ntp <= TP) of the image's `tiles`.
-template <int TP, bool MISS>
-__global__ __launch_bounds__(MD_WAVES * 64) void k_mdots(const uint8_t* __restrict__ bed, uint64_t stride, uint32_t M, uint32_t t0,
-                                                         uint32_t t1, uint32_t sub_per, uint32_t n_sub, const rl_v4i* __restrict__ img,
-                                                         int tiles, int tv0, int ntp, int K, const uint8_t* __restrict__ tmiss,
-                                                         uint32_t m0, uint32_t count, unsigned long long* __restrict__ acc)
+// dword s of the eight a lane holds of a slice
+__device__ __forceinline__ uint32_t md_dword(const uint4 (&w)[2], int s)
+{
+    const uint4 v = w[s >> 2];
+    return (s & 3) == 0 ? v.x : (s & 3) == 1 ? v.y : (s & 3) == 2 ? v.z : v.w;
+}
+
+// four digit registers as one value: d0 + 2^8 d1 + 2^16 d2 + 2^24 d3
+__device__ __forceinline__ long long md_join(const rl_v4i& a)
+{
+    return (long long)a[0] + ((long long)a[1] << 8) + ((long long)a[2] << 16) + ((long long)a[3] << 24);
+}
+
+__device__ __forceinline__ void md_add(unsigned long long* p, long long v)
+{
+    if (v) __hip_atomic_fetch_add(p, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The frame of a product on the digit image, with the kernel's own arguments.  Workgroup (x, y): marker tiles tw + 0 .. MT - 1 for
+// wave w, tw = t0 + MT (MD_WAVES x + w); slices [y sub_per, (y + 1) sub_per) of the n_sub; vector tiles tv0 .. tv0 + ntp - 1
+// (ntp <= TP) of the image's `tiles`.  Per slice it calls
+//     slice(st, cw, tm)    st: the staged digits at this lane, tile t of k-step s at st[(t * 8 + s) * 64]; cw[m]: the lane's eight
+//                          dwords of marker 16 (tw + m) + c (zero past M); tm[m]: MISS and tile tw + m holds a column with missing
+//                          calls (wave-uniform).  Only waves with a tile below t1 get the call.
+// and at the end, for every (m, t) whose marker j lies in [m0, m0 + count) and whose vector k = 2 (tv0 + t) + (g >> 1) is below K,
+//     out(m, t, tm[m], p)  p = acc + ((j - m0) K + k) W + (g & 1): the lane's half (low at g even, high at g odd) of the first of
+//                          the entry's W 64-bit sums.  Lane (c, g), tile t, register r holds digit (4 g + r) mod 8 of that vector
+//                          against that marker.
+template <int TP, bool MISS, int W, class Slice, class Out>
+__device__ __forceinline__ void md_frame(const uint8_t* __restrict__ bed, uint64_t stride, uint32_t M, uint32_t t0, uint32_t t1,
+                                         uint32_t sub_per, uint32_t n_sub, const rl_v4i* __restrict__ img, int tiles, int tv0, int ntp,
+                                         int K, const uint8_t* __restrict__ tmiss, uint32_t m0, uint32_t count,
+                                         unsigned long long* __restrict__ acc, Slice&& slice, Out&& out)
 {
     constexpr int MT = md_mt(TP);
     constexpr int NU = TP * 8 * 64;                   // 16-byte units of digits per slice
@@ -123,18 +162,9 @@ __global__ __launch_bounds__(MD_WAVES * 64) void k_mdots(const uint8_t* __restri
             dst[m][1] = b;
         }
     };
-
-    rl_v4i D[MT][TP], R[MT][MISS ? TP : 1];
     bool tm[MT];
 #pragma unroll
-    for (int m = 0; m < MT; ++m) {
-        tm[m] = MISS && wave_on && tw + (uint32_t)m < t1 && tmiss[tw + (uint32_t)m];
-#pragma unroll
-        for (int t = 0; t < TP; ++t) {
-            D[m][t] = rl_v4i{0, 0, 0, 0};
-            if constexpr (MISS) R[m][t] = rl_v4i{0, 0, 0, 0};
-        }
-    }
+    for (int m = 0; m < MT; ++m) tm[m] = MISS && wave_on && tw + (uint32_t)m < t1 && tmiss[tw + (uint32_t)m];
 
     load_digits(s0);
     store_digits(0);
@@ -148,20 +178,54 @@ __global__ __launch_bounds__(MD_WAVES * 64) void k_mdots(const uint8_t* __restri
             load_digits(sub + 1u);
             load_codes(sub + 1u, nw);
         }
-        if (wave_on) {
+        if (wave_on) slice(stage[buf] + lane, cw, tm);
+        if (more) {
+            store_digits(buf ^ 1);
+#pragma unroll
+            for (int m = 0; m < MT; ++m) {
+                cw[m][0] = nw[m][0];
+                cw[m][1] = nw[m][1];
+            }
+        }
+        __syncthreads();
+    }
+    if (!wave_on) return;
+
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+        const uint32_t j = 16u * (tw + (uint32_t)m) + c;
+        if (j < m0 || j - m0 >= count || j >= M) continue;
+#pragma unroll
+        for (int t = 0; t < TP; ++t) {
+            const uint32_t k = 2u * (uint32_t)(tv0 + t) + (g >> 1);
+            if (t >= ntp || k >= (uint32_t)K) continue;
+            out(m, t, tm[m], acc + ((uint64_t)(j - m0) * (uint32_t)K + k) * (uint32_t)W + (g & 1u));
+        }
+    }
+}
+
+// The product: the codes of a k-step stay in registers (z) for all vector tiles; A is read from the stage per tile.
+// acc: [marker - m0][vector][D, R][half] 64-bit sums.
+template <int TP, bool MISS>
+__global__ __launch_bounds__(MD_WAVES * 64) void k_mdots(const uint8_t* __restrict__ bed, uint64_t stride, uint32_t M, uint32_t t0,
+                                                         uint32_t t1, uint32_t sub_per, uint32_t n_sub, const rl_v4i* __restrict__ img,
+                                                         int tiles, int tv0, int ntp, int K, const uint8_t* __restrict__ tmiss,
+                                                         uint32_t m0, uint32_t count, unsigned long long* __restrict__ acc)
+{
+    constexpr int MT = md_mt(TP);
+    rl_v4i D[MT][TP] = {}, R[MT][MISS ? TP : 1] = {};
+    md_frame<TP, MISS, 4>(
+        bed, stride, M, t0, t1, sub_per, n_sub, img, tiles, tv0, ntp, K, tmiss, m0, count, acc,
+        [&](const rl_v4i* st, const uint4 (&cw)[MT][2], const bool (&tm)[MT]) {
 #pragma unroll
             for (int s = 0; s < 8; ++s) {
                 rl_v4i z[MT];
 #pragma unroll
-                for (int m = 0; m < MT; ++m) {
-                    const uint4 v = cw[m][s >> 2];
-                    const uint32_t x = (s & 3) == 0 ? v.x : (s & 3) == 1 ? v.y : (s & 3) == 2 ? v.z : v.w;
-                    z[m] = rl_expand16(x);
-                }
+                for (int m = 0; m < MT; ++m) z[m] = rl_expand16(md_dword(cw[m], s));
 #pragma unroll
                 for (int t = 0; t < TP; ++t) {
                     if (t < ntp) { // (uniform)
-                        const rl_v4i A = stage[buf][(t * 8 + s) * 64 + (int)lane];
+                        const rl_v4i A = st[(t * 8 + s) * 64];
 #pragma unroll
                         for (int m = 0; m < MT; ++m) {
                             D[m][t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A, z[m], D[m][t], 0, 0, 0);
@@ -179,42 +243,13 @@ __global__ __launch_bounds__(MD_WAVES * 64) void k_mdots(const uint8_t* __restri
                     }
                 }
             }
-        }
-        if (more) {
-            store_digits(buf ^ 1);
-#pragma unroll
-            for (int m = 0; m < MT; ++m) {
-                cw[m][0] = nw[m][0];
-                cw[m][1] = nw[m][1];
-            }
-        }
-        __syncthreads();
-    }
-    if (!wave_on) return;
-
-    // lane (c, g), tile t, register r: digit (4 g + r) mod 8 of vector 2 (tv0 + t) + (g >> 1) against marker 16 (tw + m) + c
-    auto put = [&](const rl_v4i& a) {
-        return (long long)a[0] + ((long long)a[1] << 8) + ((long long)a[2] << 16) + ((long long)a[3] << 24);
-    };
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-        const uint32_t j = 16u * (tw + (uint32_t)m) + c;
-        if (j < m0 || j - m0 >= count || j >= M) continue;
-#pragma unroll
-        for (int t = 0; t < TP; ++t) {
-            const uint32_t k = 2u * (uint32_t)(tv0 + t) + (g >> 1);
-            if (t >= ntp || k >= (uint32_t)K) continue;
-            unsigned long long* p = acc + ((uint64_t)(j - m0) * (uint32_t)K + k) * 4u + (g & 1u);
-            const long long v = put(D[m][t]);
-            if (v) __hip_atomic_fetch_add(p, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        },
+        [&](int m, int t, bool missing, unsigned long long* p) {
+            md_add(p, md_join(D[m][t]));
             if constexpr (MISS) {
-                if (tm[m]) {
-                    const long long w = put(R[m][t]);
-                    if (w) __hip_atomic_fetch_add(p + 2, (unsigned long long)w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
+                if (missing) md_add(p + 2, md_join(R[m][t]));
             }
-        }
-    }
+        });
 }
 
 // One thread per (marker, vector): P = D - 3 R, Q = sum_all q - R, each rounded once; x_j'u_k = mstd (P - mave Q)
@@ -241,16 +276,6 @@ __global__ __launch_bounds__(MD_TPB) void k_mdots_final(const unsigned long long
 }
 
 } // namespace
-
-template <int TP>
-static void mdots_launch(hgibbs_ctx* h, dim3 grid, uint32_t t0, uint32_t t1, uint32_t sub_per, uint32_t n_sub, const rl_v4i* img, int tiles,
-                         int tv0, int ntp, int K, const uint8_t* tmiss, uint32_t m0, uint32_t count, unsigned long long* acc)
-{
-    if (h->any_missing)
-        k_mdots<TP, true><<<grid, MD_WAVES * 64, 0, h->stream>>>(h->bed, h->stride, h->M, t0, t1, sub_per, n_sub, img, tiles, tv0, ntp, K, tmiss, m0, count, acc);
-    else
-        k_mdots<TP, false><<<grid, MD_WAVES * 64, 0, h->stream>>>(h->bed, h->stride, h->M, t0, t1, sub_per, n_sub, img, tiles, tv0, ntp, K, tmiss, m0, count, acc);
-}
 
 // The work buffers of the pipeline for up to `kmax` vectors against up to `cmax` markers of a chunk, allocated once by the caller
 // (hgibbs_marker_dots per call, hgibbs_pca per call for all its iterations): everything but the vectors and the results.
@@ -299,58 +324,81 @@ static int mdots_dev_clear(hgibbs_ctx* h, MdotsWs& b, uint32_t count, int K)
     return 0;
 }
 
-// The kernels of one product on device pointers: dU (K x n_local, vector-major) -> dout (count x K), draw (count x K x 2) or null.
-// Stream-ordered: no allocation, no synchronisation.  mdots_dev_clear comes first.
-static int mdots_dev_run(hgibbs_ctx* h, MdotsWs& b, uint32_t m0, uint32_t count, int K, const double* dU, double* dout, double* draw)
+// The scales and sum_i q of hgibbs_score with a = o = u_k, then the digit image: dU (K x n_local, vector-major) -> scale[K],
+// maxbits[K] with ksum = maxbits + K (two halves a vector), img of (K + 1) / 2 tiles.  maxbits and bad were zeroed.  Stream-ordered.
+static int digit_image(hgibbs_ctx* h, const double* dU, int K, unsigned long long* maxbits, uint32_t* bad, int* scale, rl_v4i* img)
 {
-    const uint32_t n = h->n_local;
+    const uint32_t n = h->n_local, n_sub = (n + MD_SUBI - 1) / MD_SUBI;
     const int tiles = (K + 1) / 2;
-    const uint32_t n_sub = (n + MD_SUBI - 1) / MD_SUBI;
-    const size_t nk = (size_t)count * K;
-    unsigned long long* ksum = b.maxbits + K;
-    {
-        // the scales and sum_i q of hgibbs_score, with a = o = u_k (vectors of n_local entries)
-        const uint32_t per = std::max<uint32_t>(1u, std::min<uint32_t>((n + 2047u) / 2048u, (2048u + (uint32_t)K - 1u) / (uint32_t)K));
-        k_score_max<<<dim3(K, per), SC_TPB, 0, h->stream>>>(dU, dU, n, b.maxbits, b.bad);
-        HIP_TRY(hipGetLastError());
-        k_score_ksum<<<dim3(K, per), SC_TPB, 0, h->stream>>>(dU, n, b.maxbits, b.scale, ksum);
-        HIP_TRY(hipGetLastError());
-        k_mdots_digits<<<dim3(n_sub * 8u, tiles), 64, 0, h->stream>>>(dU, n, K, tiles, b.scale, b.img);
-        HIP_TRY(hipGetLastError());
-    }
+    const uint32_t per = std::max<uint32_t>(1u, std::min<uint32_t>((n + 2047u) / 2048u, (2048u + (uint32_t)K - 1u) / (uint32_t)K));
+    k_score_max<<<dim3(K, per), SC_TPB, 0, h->stream>>>(dU, dU, n, maxbits, bad);
+    HIP_TRY(hipGetLastError());
+    k_score_ksum<<<dim3(K, per), SC_TPB, 0, h->stream>>>(dU, n, maxbits, scale, maxbits + K);
+    HIP_TRY(hipGetLastError());
+    k_mdots_digits<<<dim3(n_sub * 8u, tiles), 64, 0, h->stream>>>(dU, n, K, tiles, scale, img);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// An operator's builds: [tiles in the pass: 1, 2, more][any_missing], each with the TP it was built for (md_mt gives the grid)
+using MdKernel = decltype(&k_mdots<1, false>);
+struct MdBuild {
+    int tp;
+    MdKernel clean, missing;
+};
+
+// The passes over the workspace's image of K vectors against markers [m0, m0 + count), into b.acc
+static int md_passes(hgibbs_ctx* h, MdotsWs& b, uint32_t m0, uint32_t count, int K, const MdBuild (&builds)[3])
+{
+    const int tiles = (K + 1) / 2;
+    const uint32_t n_sub = (h->n_local + MD_SUBI - 1) / MD_SUBI;
     const uint32_t t0 = m0 / 16u, t1 = (m0 + count - 1u) / 16u + 1u;
     for (int tv0 = 0; tv0 < tiles; tv0 += MD_TPMAX) {
         const int ntp = std::min(MD_TPMAX, tiles - tv0);
-        const int tp = ntp <= 1 ? 1 : ntp <= 2 ? 2 : 4;
-        const uint32_t per_wg = (uint32_t)(MD_WAVES * md_mt(tp)); // marker tiles per workgroup
+        const MdBuild& bd = builds[ntp <= 1 ? 0 : ntp <= 2 ? 1 : 2];
+        const uint32_t per_wg = (uint32_t)(MD_WAVES * md_mt(bd.tp)); // marker tiles per workgroup
         const uint32_t gx = (t1 - t0 + per_wg - 1u) / per_wg;
         // individual ranges: enough workgroups for eight per compute unit (option mdots_split fixes the number), no range above MD_SUB_MAX slices
         uint32_t sub_per = 0;
         const uint32_t gy = split_ranges(n_sub, h->mdots_split ? (uint32_t)h->mdots_split : (8u * (uint32_t)h->num_cu + gx - 1u) / gx, MD_SUB_MAX, sub_per);
-        const dim3 grid(gx, gy);
-        switch (tp) {
-        case 1: mdots_launch<1>(h, grid, t0, t1, sub_per, n_sub, b.img, tiles, tv0, ntp, K, b.tmiss, m0, count, b.acc); break;
-        case 2: mdots_launch<2>(h, grid, t0, t1, sub_per, n_sub, b.img, tiles, tv0, ntp, K, b.tmiss, m0, count, b.acc); break;
-        default: mdots_launch<4>(h, grid, t0, t1, sub_per, n_sub, b.img, tiles, tv0, ntp, K, b.tmiss, m0, count, b.acc); break;
-        }
+        (h->any_missing ? bd.missing : bd.clean)<<<dim3(gx, gy), MD_WAVES * 64, 0, h->stream>>>(h->bed, h->stride, h->M, t0, t1, sub_per, n_sub, b.img, tiles, tv0, ntp, K, b.tmiss, m0, count, b.acc);
         HIP_TRY(hipGetLastError());
     }
-    k_mdots_final<<<(uint32_t)((nk + MD_TPB - 1) / MD_TPB), MD_TPB, 0, h->stream>>>(b.acc, ksum, b.scale, h->mave, h->mstd, m0, count, K, dout, draw);
+    return 0;
+}
+
+// The kernels of one product on device pointers: dU (K x n_local, vector-major) -> dout (count x K), draw (count x K x 2) or null.
+// Stream-ordered: no allocation, no synchronisation.  mdots_dev_clear comes first.
+static int mdots_dev_run(hgibbs_ctx* h, MdotsWs& b, uint32_t m0, uint32_t count, int K, const double* dU, double* dout, double* draw)
+{
+    static const MdBuild builds[3] = {{1, k_mdots<1, false>, k_mdots<1, true>}, {2, k_mdots<2, false>, k_mdots<2, true>}, {4, k_mdots<4, false>, k_mdots<4, true>}};
+    const size_t nk = (size_t)count * K;
+    if (digit_image(h, dU, K, b.maxbits, b.bad, b.scale, b.img)) return 1;
+    if (md_passes(h, b, m0, count, K, builds)) return 1;
+    k_mdots_final<<<(uint32_t)((nk + MD_TPB - 1) / MD_TPB), MD_TPB, 0, h->stream>>>(b.acc, b.maxbits + K, b.scale, h->mave, h->mstd, m0, count, K, dout, draw);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// The refusals of an entry point that takes K vectors U against markers [m0, m0 + count), after op_guard, under the name `who`
+static int kvec_guard(hgibbs_ctx* h, const char* who, uint32_t m0, uint32_t count, int K, const double* U, const double* out)
+{
+    if (K <= 0 || K > MD_KMAX) return fail("%s: K = %d, must be in [1, %d]", who, K, MD_KMAX);
+    if (!U || !out) return fail("%s: null argument", who);
+    if ((uint64_t)m0 + count > h->M) return fail("%s: markers [%u, %llu) out of range (M = %u)", who, m0, (unsigned long long)m0 + count, h->M);
+    if (h->n_local >= MD_NMAX) return fail("%s: %u individuals, at most %u (64-bit sums)", who, h->n_local, MD_NMAX - 1u);
+    const uint32_t n = h->n_local;
+    for (size_t i = 0; i < (size_t)K * n; ++i)
+        if (!std::isfinite(U[i])) return fail("%s: U[%d][%zu] = %g is not finite", who, (int)(i / n), i % n, U[i]);
     return 0;
 }
 
 extern "C" int hgibbs_marker_dots(hgibbs_t h, uint32_t m0, uint32_t count, int K, const double* U, double* out, double* raw)
 {
     if (op_guard(h, "hgibbs_marker_dots", "the dots are not summed over ranks")) return 1;
-    if (K <= 0 || K > MD_KMAX) return fail("hgibbs_marker_dots: K = %d, must be in [1, %d]", K, MD_KMAX);
-    if (!U || !out) return fail("hgibbs_marker_dots: null argument");
-    if ((uint64_t)m0 + count > h->M) return fail("hgibbs_marker_dots: markers [%u, %llu) out of range (M = %u)", m0, (unsigned long long)m0 + count, h->M);
-    if (h->n_local >= MD_NMAX) return fail("hgibbs_marker_dots: %u individuals, at most %u (64-bit sums)", h->n_local, MD_NMAX - 1u);
-    const uint32_t n = h->n_local;
-    for (size_t i = 0; i < (size_t)K * n; ++i)
-        if (!std::isfinite(U[i])) return fail("hgibbs_marker_dots: U[%d][%zu] = %g is not finite", (int)(i / n), i % n, U[i]);
+    if (kvec_guard(h, "hgibbs_marker_dots", m0, count, K, U, out)) return 1;
     if (count == 0) return 0;
+    const uint32_t n = h->n_local;
     HIP_TRY(hipSetDevice(h->device));
     if (compute_stats(h)) return 1;
 

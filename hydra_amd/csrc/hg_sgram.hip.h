@@ -125,9 +125,7 @@ __global__ __launch_bounds__(SG_WAVES * 64) void k_sgram(const uint8_t* __restri
         const rl_v4i* dg = img + (size_t)sub * 8u * 64u; // (one tile: the image of one vector)
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
-            const uint4 va = wa[s >> 2], vb = wb[s >> 2];
-            const uint32_t xa = (s & 3) == 0 ? va.x : (s & 3) == 1 ? va.y : (s & 3) == 2 ? va.z : va.w;
-            const uint32_t xb = (s & 3) == 0 ? vb.x : (s & 3) == 1 ? vb.y : (s & 3) == 2 ? vb.z : vb.w;
+            const uint32_t xa = md_dword(wa, s), xb = md_dword(wb, s);
             // tile ta: the values.  Clean build: the code itself (a padding slot's 3 meets zero digits)
             rl_v4i ga = rl_expand16(xa), ga2, ca, ca2;
             if constexpr (MISS) {
@@ -175,12 +173,9 @@ __global__ __launch_bounds__(SG_WAVES * 64) void k_sgram(const uint8_t* __restri
         }
     }
 
-    auto add = [&](unsigned long long* p, long long v) {
-        if (v) __hip_atomic_fetch_add(p, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    };
     auto put = [&](const rl_v4i (&D)[7], int r, unsigned long long* p) {
-        add(p, (long long)D[0][r] + ((long long)D[1][r] << 8) + ((long long)D[2][r] << 16) + ((long long)D[3][r] << 24));
-        add(p + 1, (long long)D[4][r] + ((long long)D[5][r] << 8) + ((long long)D[6][r] << 16));
+        md_add(p, md_join(rl_v4i{D[0][r], D[1][r], D[2][r], D[3][r]}));
+        md_add(p + 1, md_join(rl_v4i{D[4][r], D[5][r], D[6][r], 0}));
     };
     if (pa < jb.m) {
 #pragma unroll
@@ -198,8 +193,7 @@ __global__ __launch_bounds__(SG_WAVES * 64) void k_sgram(const uint8_t* __restri
             }
         }
         // the tile's own sums: lane (c, 0) registers 0..3 = digits 0..3, lane (c, 1) registers 0..2 = digits 4..6 (row 7 is zero)
-        if (diag && g < 2u)
-            add(psum + 2u * (jb.ioff + pa) + g, (long long)PS[0] + ((long long)PS[1] << 8) + ((long long)PS[2] << 16) + ((long long)PS[3] << 24));
+        if (diag && g < 2u) md_add(psum + 2u * (jb.ioff + pa) + g, md_join(PS));
     }
 }
 
@@ -357,14 +351,8 @@ extern "C" int hgibbs_set_gram(hgibbs_t h, uint32_t nsets, const uint64_t* off, 
     // device time from here to the rounded result: every kernel of the call, not the host copies around it
     double ms = 0.0;
     if (lap_begin(h)) return 1;
+    if (digit_image(h, dw, 1, maxbits, bad, scale, img)) return 1; // (one vector, one tile)
     unsigned long long* ksum = maxbits + 1;
-    const uint32_t per = std::max<uint32_t>(1u, std::min<uint32_t>((n + 2047u) / 2048u, 2048u));
-    k_score_max<<<dim3(1, per), SC_TPB, 0, h->stream>>>(dw, dw, n, maxbits, bad);
-    HIP_TRY(hipGetLastError());
-    k_score_ksum<<<dim3(1, per), SC_TPB, 0, h->stream>>>(dw, n, maxbits, scale, ksum);
-    HIP_TRY(hipGetLastError());
-    k_mdots_digits<<<dim3(n_sub * 8u, 1), 64, 0, h->stream>>>(dw, n, 1, 1, scale, img);
-    HIP_TRY(hipGetLastError());
     // row ranges: enough workgroups for eight per compute unit (option sgram_split fixes the number), no range above SG_SUB_MAX slices
     const uint32_t nj = (uint32_t)jobs.size();
     uint32_t sub_per = 0;
