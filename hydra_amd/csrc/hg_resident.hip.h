@@ -778,13 +778,6 @@ __device__ __forceinline__ void res_streamer(const ResParams& p, unsigned char* 
 #pragma unroll
             for (int t = 0; t < T; ++t) xq[t] = ring[slotq * 64u * T + (uint32_t)lane * T + t];
             const double2 mq = meta[slotq];
-            if (upd && tid < 16) { // the update's pair table (read behind the Gram terms, below)
-                const double av = mq.x, sd = mq.y, db = dbeta;
-                const double v0 = -(av * sd * db), v1 = db * (1.0 - av) * sd, v2 = db * (2.0 - av) * sd;
-                // (window codes: the x form 00 / 01 / 11 = genotype 0 / 1 / 2; 10 = missing call, addend 0)
-                auto addend = [&](uint32_t c) { return 0.0 + ((c == 0u) ? v0 : ((c == 1u) ? v1 : ((c == 3u) ? v2 : 0.0))); };
-                tab[tid] = make_double2(addend((uint32_t)tid & 3u), addend(((uint32_t)tid >> 2) & 3u));
-            }
 
             // ---- FIRST what the walker waits for (they need the window's codes only, not eps): the integer Gram terms A_jq = sum_i g_ij g_iq of the window columns behind q (their dots were taken before this
             // update): the walker corrects them, x_j'eps_new = x_j'eps_old + dbeta mstd_j mstd_q (A_jq - N mave_j mave_q) ----
@@ -792,6 +785,13 @@ __device__ __forceinline__ void res_streamer(const ResParams& p, unsigned char* 
             if (with_gram) ++nev;
             lap(2);
             if (timing) p.trace[6 * RS_TRACE + seq % RS_TRACE] = wall_clock64();
+            if (upd && tid < 16) { // the update's pair table, behind the Gram terms the walker waits for: first read behind the barrier below
+                const double av = mq.x, sd = mq.y, db = dbeta;
+                const double v0 = -(av * sd * db), v1 = db * (1.0 - av) * sd, v2 = db * (2.0 - av) * sd;
+                // (window codes: the x form 00 / 01 / 11 = genotype 0 / 1 / 2; 10 = missing call, addend 0)
+                auto addend = [&](uint32_t c) { return 0.0 + ((c == 0u) ? v0 : ((c == 1u) ? v1 : ((c == 3u) ? v2 : 0.0))); };
+                tab[tid] = make_double2(addend((uint32_t)tid & 3u), addend(((uint32_t)tid >> 2) & 3u));
+            }
             // ---- a8 (src/BayesRRm.cpp:1976-2010,2022,2471): eps += {v0, v1, v2, 0}[code] on the registers of every wave, while the
             // Gram atomics are on their way (an LDS-only barrier: __syncthreads() would wait for them to be performed) ----
             rs_lds_barrier(); // (an announcement: everybody has read the message before the polling lane writes the next one)

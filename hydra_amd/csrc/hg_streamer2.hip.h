@@ -347,6 +347,25 @@ __device__ __forceinline__ void res_streamer_limb(const ResParams& p, unsigned c
         rl_id_load<T, r>(p.order + (pi < M ? pi : 0u));
         if (wave == 0 && gl < 2u) rl_meta_load<T, r>(mbase + (pn < M ? pn : 0u)); // what travels with the column: k-group 0 its mave, k-group 1 its mstd
     };
+    // the same where the group G and the group G + NG lie below M in full (wave-uniform, tested once per round): no lane needs a select
+    // (what travels with the column is asked for in wave 0's own block of the pass)
+    auto load_set_whole = [&](auto rtag, uint32_t G, int32_t id) __attribute__((always_inline)) {
+        constexpr int r = decltype(rtag)::value;
+        rl_set_load<T, r>(p.bed + ((size_t)((uint32_t)id * (uint32_t)(p.stride >> 10)) << 10) + coff);
+        rl_id_load<T, r>(p.order + (16u * (G + (uint32_t)NG) + cl));
+    };
+    // The group pass by what is wave-uniform ("The refill's group pass").  With the window's end on a multiple of
+    // sixteen (wend_mask = 15: Sx and Sn are multiples of sixteen or M) a group G of a round, Sx / 16 <= G <= G1 = (Sn - 1) / 16, that
+    // lies below M in full, G < M / 16, is the round's in full: 16 G >= Sx, and 16 G + 16 <= Sn (Sn a multiple of sixteen above 16 G, or
+    // Sn = M >= 16 (M / 16) >= 16 G + 16).  A round with G1 < gwhole2 = M / 16 - 2 NG that is not the last takes every group without a
+    // test per lane: no lane tests the window, every set's next group (G + NG) may leave at once, and neither its columns nor the ids
+    // behind them (G + 2 NG) need a select against M.  Every other round -- the sweep's last 32 NG positions, a window that ends
+    // anywhere (wend_mask = 0: gwhole2 = 0) -- takes the per-lane form.
+    const uint32_t gwhole = p.wend_mask == 15u ? M >> 4 : 0u;
+    const uint32_t gwhole2 = gwhole > 2u * (uint32_t)NG ? gwhole - 2u * (uint32_t)NG : 0u;
+    uint32_t* const ringl = ring + cl * 64u * T + Dc;                                   // the lane's dwords of window slot cl
+    double* const metal = reinterpret_cast<double*>(meta + cl) + (gl & 1u);              // (wave 0, k-groups 0 and 1) its half of the slot's (mave, mstd)
+    const uint32_t accl = lds_addr(acc1) - 512u + 8u * cl;                              // the lane's column of acc1, less the 512 of rl_acc_off: the constant rides in the add's offset field
     {
         int32_t id0[NG];
 #pragma unroll
@@ -413,17 +432,17 @@ __device__ __forceinline__ void res_streamer_limb(const ResParams& p, unsigned c
             for (int t = 0; t < T; ++t) xq[t] = ring[slotq * 64u * T + (uint32_t)lane * T + t];
             const uint32_t xqe = ring[slotq * 64u * T + (uint32_t)wave * 8u * T + bw]; // the codes of the block this lane owns individuals of
             const double2 mq = meta[slotq];
-            if (upd && tid < 4) { // the update's addends by window code (x form 00 / 01 / 11 = genotype 0 / 1 / 2; 10 = missing call, addend 0)
-                const double av = mq.x, sd = mq.y, db = dbeta;
-                const double v0 = -(av * sd * db), v1 = db * (1.0 - av) * sd, v2 = db * (2.0 - av) * sd;
-                tab1[tid] = 0.0 + (tid == 0 ? v0 : (tid == 1 ? v1 : (tid == 3 ? v2 : 0.0)));
-            }
             // ---- FIRST what the walker waits for: the integer Gram terms of the window columns behind q (hg_resident.hip.h: rs_gram_terms) ----
             if (with_gram) rs_gram_terms<T, MISS>(p, ring, meta, wg, wave, lane, q, Sx, bmask, nev, xq, mq);
 
             if (with_gram) ++nev;
             lap(2);
             if (timing) p.trace[6 * RS_TRACE + seq % RS_TRACE] = wall_clock64();
+            if (upd && tid < 4) { // the update's addends by window code (x form 00 / 01 / 11 = genotype 0 / 1 / 2; 10 = missing call, addend 0) -- behind the Gram terms: first read behind the barrier below
+                const double av = mq.x, sd = mq.y, db = dbeta;
+                const double v0 = -(av * sd * db), v1 = db * (1.0 - av) * sd, v2 = db * (2.0 - av) * sd;
+                tab1[tid] = 0.0 + (tid == 0 ? v0 : (tid == 1 ? v1 : (tid == 3 ? v2 : 0.0)));
+            }
             // ---- a8 (src/BayesRRm.cpp:1976-2010,2022,2471): eps += {v0, v1, 0, v2}[code] on the individuals this lane owns, then their digits ----
             rs_lds_barrier(); // (the table; an announcement: everybody has read the message before the polling lane writes the next one)
             if (upd) {
@@ -448,19 +467,23 @@ __device__ __forceinline__ void res_streamer_limb(const ResParams& p, unsigned c
         // G0 .. G1 of sixteen, every wave its slice of every column ----
         if (nnew) {
             const uint32_t G0 = Sx >> 4, G1 = (Sn - 1u) >> 4;
+            const uint32_t accr = accl - 8u * Sx; // the lane's accumulator of position p of this round: accr + 8 (p - cl)
+            const bool whole = G1 < gwhole2 && !last; // wave-uniform: the round's groups, their sets' next groups and the ids behind those lie below M in full
             for (uint32_t gb = G0; gb <= G1; gb += (uint32_t)NG) { // (more than NG groups: the first fill, a long advance)
                 if (gb != G0) cols_landed();
-                auto one = [&](auto rtag) __attribute__((always_inline)) {
+                uint32_t gbo = gb;
+                asm volatile("" : "+s"(gbo)); // (a value of this turn: the sets' groups, slots and addresses of both forms, hoisted in front of the loop, are ninety instructions a round)
+                auto one = [&](auto rtag, auto wtag) __attribute__((always_inline)) {
                     constexpr int r = decltype(rtag)::value;
-                    const uint32_t G = gb + (((uint32_t)r - gb) & (uint32_t)(NG - 1));
+                    constexpr bool WHOLE = decltype(wtag)::value;
+                    const uint32_t G = gbo + (((uint32_t)r - gbo) & (uint32_t)(NG - 1));
                     if (G <= G1) { // wave-uniform
                         uint32_t w[ND];
                         rl_set_read<T, r>(w, keep);
-                        const uint32_t pc = 16u * G + cl;
-                        const bool mine = pc >= Sx && pc < Sn;
                         bool anym = false;
                         int mlo = 0, mhi = 0;
-                        if (wave == 0) rl_meta_read<T, r>(mlo, mhi); // (wave 0 fills the slots' (mave, mstd))
+                        if constexpr (!WHOLE)
+                            if (wave == 0) rl_meta_read<T, r>(mlo, mhi); // (wave 0 fills the slots' (mave, mstd))
                         if constexpr (MISS) {
                             // a column with missing calls is known by its codes: 11 anywhere in the group's dwords of this wave (no flag needed)
                             uint32_t any3 = 0u;
@@ -489,15 +512,13 @@ __device__ __forceinline__ void res_streamer_limb(const ResParams& p, unsigned c
                                 xf[d] = gram_xform(w[d]);
                         }
                         // the window keeps the x form: what the update's table and the Gram terms of every later event need, made once
-                        if (mine) {
-                            uint32_t* rp = ring + (pc & bmask) * 64u * T + Dc;
+                        auto ring_write = [&](uint32_t* rp) {
                             if constexpr (T == 4) {
                                 *reinterpret_cast<u4_t*>(rp) = rs_u4(xf[0], xf[1], xf[ND - 6], xf[ND - 5]);
                                 *reinterpret_cast<u4_t*>(rp + 4) = rs_u4(xf[ND - 4], xf[ND - 3], xf[ND - 2], xf[ND - 1]);
                             } else if constexpr (T == 2) *reinterpret_cast<u4_t*>(rp) = rs_u4(xf[0], xf[1], xf[ND - 2], xf[ND - 1]);
                             else *reinterpret_cast<uint2*>(rp) = make_uint2(xf[0], xf[1]);
-                            if (wave == 0 && gl < 2u) reinterpret_cast<double*>(meta + (pc & bmask))[gl] = __hiloint2double(mhi, mlo);
-                        }
+                        };
                         // lane (c, g) register rr: digit 4 g + rr of column c over the wave's slice (the digits are the product's ROWS): the lane
                         // puts its four digits together -- d0 + 2^8 d1 + 2^16 d2 + 2^24 d3, times 2^32 in k-group 1 (digits 4 .. 6; groups 2 and 3
                         // hold zeros) -- and adds them to the position's accumulator: ONE instruction per group of sixteen columns, two lanes a column
@@ -506,7 +527,42 @@ __device__ __forceinline__ void res_streamer_limb(const ResParams& p, unsigned c
                             const int t01 = a[0] + (a[1] << 8), t23 = a[2] + (a[3] << 8); // (|digit sum| < 2^17: 25 bits each)
                             return ((long long)t01 + ((long long)t23 << 16)) << (32u * (gl & 1u));
                         };
-                        {
+                        if constexpr (WHOLE) {
+                            // ---- a round of whole groups (see gwhole2): every lane's position is the round's, every set's next group leaves ----
+                            const uint32_t s16 = (16u * G) & bmask; // the group's first window slot (B >= 32: the sixteen do not wrap)
+                            ring_write(ringl + s16 * 64u * T);
+                            // the set's next group leaves HBM now (waited for by hand, at the top of the next round) -- in front of the sums:
+                            // their instructions stand where the product's results are waited for
+                            load_set_whole(rtag, G + (uint32_t)NG, rl_id_read<T, r>());
+                            if (gl < 2u) {
+                                // (the same integer to the same word as in the other form: the position's accumulator is acc1[16 G + cl - Sx],
+                                // its address the round's accr, the group's 128 G and the 512 of the offset field)
+                                const long long v = digits_sum(a1);
+                                asm volatile("ds_add_u64 %0, %1 offset:512" ::"v"(accr + 128u * G), "v"(v) : "memory");
+                                if constexpr (MISS) {
+                                    if (anym) { // wave-uniform
+                                        const long long v2 = digits_sum(a2);
+                                        if (v2) asm volatile("ds_add_u64 %0, %1 offset:512" ::"v"(accr + 128u * G + 8u * B), "v"(v2) : "memory");
+                                    }
+                                }
+                            }
+                            // wave 0 alone, behind ONE scalar branch: the (mave, mstd) that came with the set go to the slots, and those of
+                            // the next group leave
+                            if (wave == 0) {
+                                rl_meta_read<T, r>(mlo, mhi);
+                                if (gl < 2u) {
+                                    metal[2u * s16] = __hiloint2double(mhi, mlo);
+                                    rl_meta_load<T, r>(mbase + (16u * (G + (uint32_t)NG) + cl));
+                                }
+                            }
+                        } else {
+                            // ---- the sweep's last groups, and every group of a window that ends anywhere: by lane ----
+                            const uint32_t pc = 16u * G + cl;
+                            const bool mine = pc >= Sx && pc < Sn;
+                            if (mine) {
+                                ring_write(ring + (pc & bmask) * 64u * T + Dc);
+                                if (wave == 0 && gl < 2u) reinterpret_cast<double*>(meta + (pc & bmask))[gl] = __hiloint2double(mhi, mlo);
+                            }
                             const bool on = mine && gl < 2u;
                             const long long v = digits_sum(a1);
                             if (on) asm volatile("ds_add_u64 %0, %1" ::"v"(lds_addr(acc1 + (pc - Sx))), "v"(v) : "memory");
@@ -516,12 +572,13 @@ __device__ __forceinline__ void res_streamer_limb(const ResParams& p, unsigned c
                                     if (on && v2) asm volatile("ds_add_u64 %0, %1" ::"v"(lds_addr(acc2 + (pc - Sx))), "v"(v2) : "memory");
                                 }
                             }
+                            // the set's group is admitted in full: its next group leaves HBM now (waited for by hand, at the top of the next round)
+                            if (16u * G + 16u <= Sn && !last) load_set(rtag, G + (uint32_t)NG, rl_id_read<T, r>());
                         }
-                        // the set's group is admitted in full: its next group leaves HBM now (waited for by hand, at the top of the next round)
-                        if (16u * G + 16u <= Sn && !last) load_set(rtag, G + (uint32_t)NG, rl_id_read<T, r>());
                     }
                 };
-                [&]<int... R>(std::integer_sequence<int, R...>) { (one(std::integral_constant<int, R>{}), ...); }(std::make_integer_sequence<int, NG>{});
+                if (whole) [&]<int... R>(std::integer_sequence<int, R...>) { (one(std::integral_constant<int, R>{}, std::true_type{}), ...); }(std::make_integer_sequence<int, NG>{});
+                else [&]<int... R>(std::integer_sequence<int, R...>) { (one(std::integral_constant<int, R>{}, std::false_type{}), ...); }(std::make_integer_sequence<int, NG>{});
             }
         }
         lap(3);
