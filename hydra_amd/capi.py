@@ -29,6 +29,7 @@ ABI_SYMBOLS = [
     "hgibbs_spa_roots", "hgibbs_last_spa_ms", "hgibbs_spa_pvalue",
     "hgibbs_firth_fit", "hgibbs_last_firth_ms", "hgibbs_firth_stats",
     "hgibbs_king", "hgibbs_king_pairs", "hgibbs_king_pairs_get", "hgibbs_last_king_ms",
+    "hgibbs_roh", "hgibbs_roh_get", "hgibbs_last_roh_ms",
     "hgibbs_pca", "hgibbs_last_pca_ms", "hgibbs_region_var", "hgibbs_last_region_var_ms",
     "hgibbs_grm", "hgibbs_grm_info", "hgibbs_last_grm_ms",
     "hgibbs_grm_rowsums", "hgibbs_last_grm_rowsums_ms", "hgibbs_he_fit",
@@ -76,6 +77,27 @@ class FirthRec(C.Structure):
     """hgibbs_firth_rec: flags bit 0 converged, bit 1 degenerate"""
     _fields_ = [("beta", C.c_double), ("K", C.c_double), ("K2", C.c_double), ("g", C.c_double), ("k2_0", C.c_double),
                 ("iters", C.c_int32), ("flags", C.c_uint32)]
+
+
+class RohParams(C.Structure):
+    """hgibbs_roh_params"""
+    _fields_ = [("window", C.c_uint32), ("window_het", C.c_uint32), ("window_missing", C.c_uint32), ("need", C.c_uint32 * 65),
+                ("min_snps", C.c_uint32), ("min_bp", C.c_int64), ("dens_bp", C.c_int64), ("gap_bp", C.c_int64), ("max_het", C.c_uint32)]
+
+
+# hgibbs_roh_seg as a numpy record
+ROH_SEG = np.dtype([(k, np.uint32) for k in ("row", "first", "last", "nsnp", "nhet", "nmiss")])
+
+
+def roh_need(threshold, window):
+    """need[0 .. 64] of hgibbs_roh_params: need[n] = the smallest integer c with float(c) / float(n) >= threshold, n = 1 .. window"""
+    need = [0] * 65
+    for n in range(1, int(window) + 1):
+        c = 1
+        while float(c) / float(n) < threshold:
+            c += 1
+        need[n] = c
+    return need
 
 
 class HeForm(C.Structure):
@@ -261,6 +283,9 @@ def lib():
     L.hgibbs_king_pairs.argtypes = [vp, C.c_double, C.POINTER(C.c_uint64)]
     L.hgibbs_king_pairs_get.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), dp]
     L.hgibbs_last_king_ms.argtypes = [vp, dp]
+    L.hgibbs_roh.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int64), C.POINTER(RohParams), C.POINTER(C.c_uint64)]
+    L.hgibbs_roh_get.argtypes = [vp, C.c_void_p]
+    L.hgibbs_last_roh_ms.argtypes = [vp, dp]
     L.hgibbs_pca.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double, dp, C.c_uint64, dp, dp, dp, C.POINTER(PcaReport)]
     L.hgibbs_last_pca_ms.argtypes = [vp, dp]
     L.hgibbs_region_var.argtypes = [vp, C.c_int, dp, dp, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), dp, dp]
@@ -887,6 +912,35 @@ class Device:
     def last_king_ms(self):
         v = C.c_double()
         check(self.L.hgibbs_last_king_ms(self.h, C.byref(v)))
+        return v.value
+
+    def roh(self, run_off, idx, bp, window=50, window_het=1, window_missing=5, threshold=0.05, min_snps=100, min_bp=1000000, dens_bp=50000,
+            gap_bp=1000000, max_het=None, need=None):
+        """Runs of homozygosity of every row (hgibbs_roh, then hgibbs_roh_get): run r is the entries run_off[r] .. run_off[r + 1] - 1 of
+        idx (markers) and bp.  Returns a record array (ROH_SEG: row, first, last, nsnp, nhet, nmiss) sorted by (row, first); first and
+        last are positions in idx.  need: the table itself (65 entries) in place of the one roh_need makes of threshold."""
+        run_off = np.ascontiguousarray(run_off, dtype=np.uint32)
+        idx = np.ascontiguousarray(idx, dtype=np.uint32)
+        bp = np.ascontiguousarray(bp, dtype=np.int64)
+        if run_off.ndim != 1 or run_off.size < 1 or idx.shape != bp.shape or idx.ndim != 1 or idx.size < int(run_off[-1]):
+            raise ValueError("run_off needs nruns + 1 entries, idx and bp run_off[-1] each")
+        p = RohParams()
+        p.window, p.window_het, p.window_missing, p.min_snps = int(window), int(window_het), int(window_missing), int(min_snps)
+        p.min_bp, p.dens_bp, p.gap_bp = int(min_bp), int(dens_bp), int(gap_bp)
+        p.max_het = 0xFFFFFFFF if max_het is None else int(max_het)
+        if need is None:
+            need = roh_need(threshold, window) if 1 <= int(window) <= 64 else [0] * 65
+        p.need[:] = [int(v) for v in need]
+        n = C.c_uint64()
+        check(self.L.hgibbs_roh(self.h, run_off.size - 1, run_off.ctypes.data_as(C.POINTER(C.c_uint32)), idx.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                bp.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(p), C.byref(n)))
+        segs = np.zeros(n.value, dtype=ROH_SEG)
+        check(self.L.hgibbs_roh_get(self.h, segs.ctypes.data_as(C.c_void_p)))
+        return segs
+
+    def last_roh_ms(self):
+        v = C.c_double()
+        check(self.L.hgibbs_last_roh_ms(self.h, C.byref(v)))
         return v.value
 
     def grm(self, a0=0, acount=None):

@@ -1,4 +1,4 @@
-// Host code shared by the operators that run on a handle's rows without sampling (hg_score, hg_ld, hg_mdots, hg_king, hg_pca, hg_grm.hip.h;
+// Host code shared by the operators that run on a handle's rows without sampling (hg_score, hg_ld, hg_mdots, hg_king, hg_roh, hg_pca, hg_grm.hip.h;
 // DESIGN.md section 17): what every one of them needs around its kernels, once.
 #pragma once
 

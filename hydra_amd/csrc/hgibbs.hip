@@ -217,6 +217,9 @@ struct hgibbs_ctx {
     std::vector<uint32_t> king_ab;    // the last hgibbs_king_pairs list, sorted by (a, b): a, b per pair
     std::vector<int32_t> king_counts; // NSNP, HET_a, HET_b, HETHET, IBS0 per pair
     std::vector<double> king_kin;     // KINSHIP per pair
+    long long roh_list0 = 0; // option roh_list0: first capacity of hgibbs_roh's segment list (0 = RH_LIST0); a second run follows when it overflows
+    double roh_ms = 0.0;     // device time of the last hgibbs_roh (every run of the kernel); 0 after a refused call
+    std::vector<hgibbs_roh_seg> roh_segs; // the last hgibbs_roh list, sorted by (row, first)
     int grm_split = 0;     // option grm_split: ranges of markers the workgroups of hgibbs_grm split the k dimension into (0 = automatic)
     double grm_ms = 0.0;   // device time of the last hgibbs_grm (scale, table, image, zeroing, products, rounding)
     uint32_t grm_used = 0; // M_used and E of the last hgibbs_grm (hgibbs_grm_info)
@@ -1318,6 +1321,9 @@ int hgibbs_set_option(hgibbs_t h, const char* name, int64_t value)
     } else if (!std::strcmp(name, "king_split")) {
         if (value < 0 || value > 65535) return fail("king_split must be in [0,65535] (0 = automatic)");
         h->king_split = (int)value;
+    } else if (!std::strcmp(name, "roh_list0")) {
+        if (value < 0 || value > (1ll << 31)) return fail("roh_list0 must be in [0,2147483648] (0 = automatic: 2^20 segments)");
+        h->roh_list0 = (long long)value;
     } else if (!std::strcmp(name, "grm_split")) {
         if (value < 0 || value > 65535) return fail("grm_split must be in [0,65535] (0 = automatic)");
         h->grm_split = (int)value;
@@ -2222,6 +2228,7 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
 #include "hg_spa.hip.h"
 #include "hg_firth.hip.h"
 #include "hg_king.hip.h"
+#include "hg_roh.hip.h"
 #include "hg_pca.hip.h"
 #include "hg_grm.hip.h"
 #include "hg_grmsums.hip.h"

@@ -86,6 +86,13 @@
 // estimates (.ibc) over the autosomal markers with a finite sd (run_qc).  With thresholds, PREFIX.qc.exclude and
 // PREFIX.qc.remove list what fails them; PREFIX defaults to <dir>/<name>.  Tab-separated; not byte parity with PLINK or GCTA.
 //
+// `--homozyg [--homozyg-window-snp W] [--homozyg-window-het H] [--homozyg-window-missing X] [--homozyg-window-threshold T] [--homozyg-snp S]
+// [--homozyg-kb L] [--homozyg-density D] [--homozyg-gap G] [--homozyg-het H2] [--homozyg-out PREFIX]` appended to a bayesMPI command line
+// samples nothing either: runs of homozygosity of the chain's rows over --qc's QC markers, PLINK 1.9's --homozyg scan restated in
+// integers, as ONE call of hgibbs_roh (run_homozyg).  PREFIX.hom has one row per segment, PREFIX.hom.indiv one per
+// row with F_ROH, PREFIX.hom.summary one per .bim marker; PREFIX defaults to <dir>/<name>.  Tab-separated; PLINK has not been run
+// against it.  Not covered: --homozyg-group, windows above 64 markers, cM.
+//
 // `--sparse-dir D --sparse-basename B` reads the genotypes from hydra's ten sparse files D/B.{dim,sl?,ss?,si?} (? = 1, 2, m) instead of
 // --bfile's .bed, for the chains and every mode above; --bfile is then optional for the chains (N = --number-individuals, the
 // phenotype file is read line by line), and with it only .fam/.bim are taken from it.  `--bed-to-sparse --bfile X [--sparse-dir D
@@ -163,6 +170,10 @@ struct Options { // src/options.hpp:20-138 (subset that reaches bayesMPI)
     bool he = false, heRows = false;                 // --he: Haseman-Elston regression on the chain's rows; --he-rows: the per-row sums too
     std::string heOut;                               // --he-out F
     bool qc = false, qcMafGiven = false, qcGenoGiven = false, qcMindGiven = false, qcHweGiven = false, qcHetSdGiven = false; // --qc; which thresholds were given
+    bool homozyg = false; // --homozyg: runs of homozygosity of the chain's rows (run_homozyg)
+    // --homozyg-window-snp W, -window-het H, -window-missing X, -window-threshold T, -snp S, -kb L, -density D, -gap G, -het H2 as given
+    // (empty: PLINK 1.9's default; checked before the device), --homozyg-out PREFIX
+    std::string hzWindow, hzWindowHet, hzWindowMissing, hzThreshold, hzSnp, hzKb, hzDensity, hzGap, hzHet, hzOut;
     std::string qcOut, qcMaf, qcGeno, qcMind, qcHwe, qcHetSd; // --qc-out PREFIX; --qc-maf X, --qc-geno X, --qc-mind X, --qc-hwe P, --qc-het-sd K as given (checked before the device)
     bool ldScore = false, ldScoreKbGiven = false, ldScoreSnpsGiven = false, ldScoreGroups = false, ldScoreRaw = false; // --ld-score; which --ld-score-* were given
     std::string ldScoreKb, ldScoreSnps, ldScoreSets, ldScoreOut; // --ld-score-kb KB, --ld-score-snps W as given (checked before the device), --ld-score-sets, --ld-score-out PREFIX
@@ -352,6 +363,17 @@ Options parse(int argc, const char* argv[])
         else if (a == "--he") o.he = true;
         else if (a == "--he-out") o.heOut = need(i);
         else if (a == "--he-rows") o.heRows = true;
+        else if (a == "--homozyg") o.homozyg = true;
+        else if (a == "--homozyg-window-snp") o.hzWindow = need(i);
+        else if (a == "--homozyg-window-het") o.hzWindowHet = need(i);
+        else if (a == "--homozyg-window-missing") o.hzWindowMissing = need(i);
+        else if (a == "--homozyg-window-threshold") o.hzThreshold = need(i);
+        else if (a == "--homozyg-snp") o.hzSnp = need(i);
+        else if (a == "--homozyg-kb") o.hzKb = need(i);
+        else if (a == "--homozyg-density") o.hzDensity = need(i);
+        else if (a == "--homozyg-gap") o.hzGap = need(i);
+        else if (a == "--homozyg-het") o.hzHet = need(i);
+        else if (a == "--homozyg-out") o.hzOut = need(i);
         else if (a == "--qc") o.qc = true;
         else if (a == "--qc-out") o.qcOut = need(i);
         else if (a == "--qc-maf") {
@@ -3280,6 +3302,170 @@ int run_qc(const Options& opt, const Cohort& co)
     return 0;
 }
 
+// ---- --homozyg: runs of homozygosity of the chain's rows ----
+// PLINK 1.9's defaults; an argument that was given is parsed as a whole and refused by name when it is out of range (check_homozyg_args
+// calls this before anything is read, run_homozyg again for the values)
+struct HomozygArgs {
+    long window = 50, windowHet = 1, windowMissing = 5, snp = 100, het = -1; // het: -1 = no limit
+    double threshold = 0.05, kb = 1000.0, density = 50.0, gap = 1000.0;
+};
+
+HomozygArgs homozyg_args(const Options& opt)
+{
+    HomozygArgs a;
+    auto count = [](const char* flag, const std::string& t, long lo, long hi, const char* what, long& v) {
+        long x = 0;
+        if (t.empty()) return;
+        if (!whole_int(t, x) || x < lo || x > hi) fatal(std::string("FATAL  : ") + flag + " " + t + ": " + what);
+        v = x;
+    };
+    auto kilobases = [](const char* flag, const std::string& t, const char* what, double& v) {
+        double x = 0.0;
+        if (t.empty()) return;
+        if (!whole_num(t, x) || !std::isfinite(x) || x < 0.0 || x > 1e12) fatal(std::string("FATAL  : ") + flag + " " + t + ": " + what);
+        v = x;
+    };
+    count("--homozyg-window-snp", opt.hzWindow, 1, 64, "the window must be an integer from 1 to 64 markers (the widest hgibbs_roh takes: a window is one 64-bit word)", a.window);
+    count("--homozyg-window-het", opt.hzWindowHet, 0, 64, "the hets a window may hold must be an integer from 0 to 64", a.windowHet);
+    count("--homozyg-window-missing", opt.hzWindowMissing, 0, 64, "the missing calls a window may hold must be an integer from 0 to 64", a.windowMissing);
+    count("--homozyg-snp", opt.hzSnp, 1, 2147483647, "the markers a segment needs must be an integer >= 1", a.snp);
+    count("--homozyg-het", opt.hzHet, 0, 2147483647, "the hets a segment may hold must be an integer >= 0", a.het);
+    if (!opt.hzThreshold.empty() && (!whole_num(opt.hzThreshold, a.threshold) || !(a.threshold > 0.0 && a.threshold <= 1.0)))
+        fatal("FATAL  : --homozyg-window-threshold " + opt.hzThreshold + ": the share of homozygous windows must be a number in (0, 1]");
+    kilobases("--homozyg-kb", opt.hzKb, "the length a segment needs must be a finite number of kilobases from 0 to 1e12", a.kb);
+    kilobases("--homozyg-density", opt.hzDensity, "the kilobases per marker a segment may have must be a finite number from 0 to 1e12", a.density);
+    kilobases("--homozyg-gap", opt.hzGap, "the gap that cuts a segment must be a finite number of kilobases from 0 to 1e12", a.gap);
+    return a;
+}
+
+int run_homozyg(const Options& opt, const Cohort& co)
+{
+    const std::string prefix = opt.hzOut.empty() ? opt.mcmcOutDir + "/" + opt.mcmcOutNam : opt.hzOut;
+    const std::string bimp = opt.bedFile + ".bim";
+    const HomozygArgs ha = homozyg_args(opt);
+    hgibbs_roh_params p{};
+    p.window = (uint32_t)ha.window;
+    p.window_het = (uint32_t)ha.windowHet;
+    p.window_missing = (uint32_t)ha.windowMissing;
+    for (uint32_t n = 1; n <= p.window; ++n) { // the smallest c with c / n >= threshold: the device compares integers only
+        uint32_t c = 1;
+        while ((double)c / (double)n < ha.threshold) ++c;
+        p.need[n] = c;
+    }
+    p.min_snps = (uint32_t)ha.snp;
+    p.min_bp = (int64_t)std::llround(ha.kb * 1000.0);
+    p.dens_bp = (int64_t)std::llround(ha.density * 1000.0);
+    p.gap_bp = (int64_t)std::llround(ha.gap * 1000.0);
+    p.max_het = ha.het < 0 ? UINT32_MAX : (uint32_t)ha.het;
+
+    const FamIds fam = read_fam_ids(opt.bedFile + ".fam", co.numInds, co.numNAs ? &co.keep : nullptr);
+    const unsigned N = co.Ntot, M = co.Mtot;
+    if (fam.fid.size() != N) fatal("FATAL  : " + opt.bedFile + ".fam: " + std::to_string(fam.fid.size()) + " kept rows, expected " + std::to_string(N));
+    const BimRows bim = read_bim(bimp, M);
+    if (bim.id.size() != M) fatal("FATAL  : " + bimp + ": " + std::to_string(bim.id.size()) + " rows, expected " + std::to_string(M));
+    // an autosome (chromosome 1 .. 22) must be one run of the .bim, in bp order: a segment is an index interval
+    const ChromRuns cr(bim, M);
+    std::vector<uint8_t> autosome(cr.nruns, 0);
+    {
+        auto marker = [&](unsigned j) { return bim.id[j] + " (row " + std::to_string(j + 1) + ")"; };
+        std::vector<uint8_t> seen(cr.nchrom, 0);
+        for (size_t r = 0; r < cr.nruns; ++r) {
+            const unsigned j0 = cr.runs[r], j1 = cr.runs[r + 1];
+            long chr = 0;
+            if (!whole_int(bim.chr[j0], chr) || chr < 1 || chr > 22) continue;
+            autosome[r] = 1;
+            if (seen[cr.cj[j0]])
+                fatal("FATAL  : " + bimp + ": chromosome " + bim.chr[j0] + " comes back at marker " + marker(j0) +
+                      " after another chromosome: --homozyg needs every chromosome as one contiguous run");
+            seen[cr.cj[j0]] = 1;
+            for (unsigned j = j0; j < j1; ++j) {
+                if (j > j0 && bim.bp[j] < bim.bp[j - 1])
+                    fatal("FATAL  : " + bimp + ": bp decreases at marker " + marker(j) + " inside chromosome " + bim.chr[j] +
+                          ": --homozyg needs the markers of a chromosome in bp order (a segment must be an index interval)");
+                if (bim.bp[j] < 0) fatal("FATAL  : " + bimp + ": marker " + marker(j) + " has a negative bp");
+            }
+        }
+    }
+    std::vector<uint8_t> bed = read_training(opt.bedFile, co.numInds, M);
+    if (opt.hzOut.empty()) make_out_dir(opt);
+    FILE* fh = open_out(prefix + ".hom", "w");
+    FILE* fi = open_out(prefix + ".hom.indiv", "w");
+    FILE* fs = open_out(prefix + ".hom.summary", "w");
+    std::fputs("FID\tIID\tCHR\tSNP1\tSNP2\tPOS1\tPOS2\tKB\tNSNP\tDENSITY\tPHOM\tPHET\n", fh);
+    std::fputs("FID\tIID\tNSEG\tKB\tKBAVG\tFROH\n", fi);
+    std::fputs("CHR\tSNP\tBP\tN_ROH\n", fs);
+
+    hgibbs_t dev = open_training(co, bed);
+    std::vector<double> mstd(M);
+    hg_check(hgibbs_marker_stats(dev, nullptr, mstd.data(), nullptr, nullptr, nullptr), "hgibbs_marker_stats");
+    // the selection: --qc's QC markers (a finite sd, chromosome 1 .. 22), one run per chromosome
+    std::vector<uint32_t> run_off{0}, idx;
+    std::vector<int64_t> bp;
+    long long span = 0; // sum over chromosomes of last selected bp - first selected bp
+    for (size_t r = 0; r < cr.nruns; ++r) {
+        if (!autosome[r]) continue;
+        for (unsigned j = cr.runs[r]; j < cr.runs[r + 1]; ++j)
+            if (std::isfinite(mstd[j])) idx.push_back(j), bp.push_back(bim.bp[j]);
+        if (idx.size() == run_off.back()) continue; // nothing selected on this chromosome
+        span += bp.back() - bp[run_off.back()];
+        run_off.push_back((uint32_t)idx.size());
+    }
+    const uint32_t nruns = (uint32_t)run_off.size() - 1u;
+    uint64_t nseg = 0;
+    hg_check(hgibbs_roh(dev, nruns, run_off.data(), idx.data(), bp.data(), &p, &nseg), "hgibbs_roh");
+    std::vector<hgibbs_roh_seg> segs(nseg);
+    hg_check(hgibbs_roh_get(dev, segs.data()), "hgibbs_roh_get");
+    double ms = 0.0;
+    hg_check(hgibbs_last_roh_ms(dev, &ms), "hgibbs_last_roh_ms");
+    hgibbs_destroy(dev);
+
+    // the list is sorted by (row, first): rows in .fam order, then by position
+    std::vector<long long> diff(idx.size() + 1, 0); // per position: rows whose segment starts here minus rows whose segment ended before
+    unsigned rowsWith = 0;
+    size_t s = 0;
+    for (unsigned i = 0; i < N; ++i) {
+        unsigned k = 0;
+        long long sum = 0;
+        for (; s < segs.size() && segs[s].row == i; ++s, ++k) {
+            const hgibbs_roh_seg& g = segs[s];
+            const unsigned j1 = idx[g.first], j2 = idx[g.last];
+            const long long len = bp[g.last] - bp[g.first];
+            const double kb = (double)len / 1000.0, n = (double)g.nsnp;
+            sum += len;
+            diff[g.first] += 1;
+            diff[g.last + 1] -= 1;
+            std::fprintf(fh, "%s\t%s\t%s\t%s\t%s\t%lld\t%lld\t%s\t%u\t%s\t%s\t%s\n", fam.fid[i].c_str(), fam.iid[i].c_str(), bim.chr[j1].c_str(), bim.id[j1].c_str(),
+                         bim.id[j2].c_str(), (long long)bp[g.first], (long long)bp[g.last], qc_num(kb).c_str(), g.nsnp, qc_num(kb / n).c_str(),
+                         qc_num((double)(g.nsnp - g.nhet - g.nmiss) / n).c_str(), qc_num((double)g.nhet / n).c_str());
+        }
+        if (k) ++rowsWith;
+        const double kb = (double)sum / 1000.0;
+        std::fprintf(fi, "%s\t%s\t%u\t%s\t%s\t%s\n", fam.fid[i].c_str(), fam.iid[i].c_str(), k, qc_num(kb).c_str(), k ? qc_num(kb / (double)k).c_str() : "NA",
+                     span > 0 ? qc_num((double)sum / (double)span).c_str() : "NA");
+    }
+    // per .bim marker: the rows with a segment over it (a segment lies inside one run, so one running sum serves every chromosome)
+    {
+        size_t k = 0;
+        long long over = 0;
+        for (unsigned j = 0; j < M; ++j) {
+            if (k < idx.size() && idx[k] == j) {
+                over += diff[k++];
+                std::fprintf(fs, "%s\t%s\t%lld\t%lld\n", bim.chr[j].c_str(), bim.id[j].c_str(), bim.bp[j], over);
+            } else
+                std::fprintf(fs, "%s\t%s\t%lld\tNA\n", bim.chr[j].c_str(), bim.id[j].c_str(), bim.bp[j]);
+        }
+    }
+    close_out(fh, prefix + ".hom");
+    close_out(fi, prefix + ".hom.indiv");
+    close_out(fs, prefix + ".hom.summary");
+    std::printf("HOMOZYG: %u rows, %zu of %u markers selected on %u chromosomes; window %ld markers (%ld het, %ld missing, threshold %g), segments of >= %ld markers, >= %g kb, "
+                "<= %g kb per marker, gap %g kb%s\n",
+                N, idx.size(), M, nruns, ha.window, ha.windowHet, ha.windowMissing, ha.threshold, ha.snp, ha.kb, ha.density, ha.gap,
+                ha.het < 0 ? "" : (", <= " + std::to_string(ha.het) + " hets").c_str());
+    std::printf("HOMOZYG: %llu segments in %u rows -> %s.{hom,hom.indiv,hom.summary} (%.3f ms on the device)\n", (unsigned long long)nseg, rowsWith, prefix.c_str(), ms);
+    return 0;
+}
+
 // ---- the analysis modes -------------------------------------------------------
 // An analysis mode is an option that, appended to a bayesMPI command line, samples nothing and runs one analysis on the chain's rows
 // (run_predict .. run_qc above).  What the modes share is refused in one place, from one row per mode.
@@ -3289,7 +3475,7 @@ struct Mode {
     const char* wmpi;   // how it refuses --mpibayes bayesWMPI, after its flag
     const char* orphan; // the first of its dependent options that was given: they need the mode (null: none was)
 };
-enum { PREDICT, LD, ASSOC, KING, PCA, PVE, GRM, LDSCORE, CLUMP, LDPRUNE, HE, QC, NMODES }; // the order in which a mode names the earlier ones it cannot be combined with
+enum { PREDICT, LD, ASSOC, KING, PCA, PVE, GRM, LDSCORE, CLUMP, LDPRUNE, HE, QC, HOMOZYG, NMODES }; // the order in which a mode names the earlier ones it cannot be combined with
 
 const char* first_given(std::initializer_list<std::pair<const char*, bool>> deps)
 {
@@ -3439,6 +3625,11 @@ void check_qc_args(const Options& opt)
         fatal("FATAL  : --qc-het-sd " + opt.qcHetSd + ": the number of standard deviations must be a finite number > 0");
 }
 
+void check_homozyg_args(const Options& opt)
+{
+    (void)homozyg_args(opt); // refuses by name what is out of range
+}
+
 // Every refusal of the modes, before anything is read: mode by mode (--ld-window first, then in the table's order), what all share,
 // then the mode's own arguments
 void check_modes(const Options& opt, int nranks)
@@ -3474,8 +3665,13 @@ void check_modes(const Options& opt, int nranks)
         {"--qc", opt.qc, takes,
          first_given({{"--qc-out", !opt.qcOut.empty()}, {"--qc-maf", opt.qcMafGiven}, {"--qc-geno", opt.qcGenoGiven}, {"--qc-mind", opt.qcMindGiven},
                       {"--qc-hwe", opt.qcHweGiven}, {"--qc-het-sd", opt.qcHetSdGiven}})},
+        {"--homozyg", opt.homozyg, takes,
+         first_given({{"--homozyg-window-snp", !opt.hzWindow.empty()}, {"--homozyg-window-het", !opt.hzWindowHet.empty()},
+                      {"--homozyg-window-missing", !opt.hzWindowMissing.empty()}, {"--homozyg-window-threshold", !opt.hzThreshold.empty()},
+                      {"--homozyg-snp", !opt.hzSnp.empty()}, {"--homozyg-kb", !opt.hzKb.empty()}, {"--homozyg-density", !opt.hzDensity.empty()},
+                      {"--homozyg-gap", !opt.hzGap.empty()}, {"--homozyg-het", !opt.hzHet.empty()}, {"--homozyg-out", !opt.hzOut.empty()}})},
     };
-    for (const int i : {LD, PREDICT, ASSOC, KING, PCA, PVE, GRM, LDSCORE, CLUMP, LDPRUNE, HE, QC}) {
+    for (const int i : {LD, PREDICT, ASSOC, KING, PCA, PVE, GRM, LDSCORE, CLUMP, LDPRUNE, HE, QC, HOMOZYG}) {
         const Mode& m = modes[i];
         const std::string flag = m.flag;
         if (!m.given) {
@@ -3499,6 +3695,7 @@ void check_modes(const Options& opt, int nranks)
         if (i == CLUMP) check_clump_args(opt);
         if (i == LDPRUNE) check_ldprune_args(opt);
         if (i == QC) check_qc_args(opt);
+        if (i == HOMOZYG) check_homozyg_args(opt);
     }
 }
 
@@ -3577,6 +3774,7 @@ int main(int argc, const char* argv[])
     if (opt.ldPrune) return run_ldselect(opt, co, false);
     if (opt.he) return run_he(opt, co, y, covX, C);
     if (opt.qc) return run_qc(opt, co);
+    if (opt.homozyg) return run_homozyg(opt, co);
 
     std::vector<int32_t> groups;
     std::vector<std::vector<double>> mS;

@@ -225,6 +225,7 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
  *   ldscore_piece   hgibbs_ld_scores: band rows per piece, 0..2^20 (0 = automatic)
  *   ldmask_piece    hgibbs_ld_mask: band rows per piece, 0..2^20 (0 = automatic; rounded up to a multiple of 16)
  *   grm_piece       hgibbs_grm, hgibbs_grm_rowsums: pairs per piece of rows, 0..2^25 (0 = automatic: 2^25; a row alone may exceed it)
+ *   roh_list0       hgibbs_roh: first capacity of the segment list, 0..2^31 (0 = automatic: 2^20; a second run follows an overflow)
  *   rowsums_ranges  hgibbs_row_sums: at most this many ranges of markers split over workgroups, 0..65535 (0 = automatic)
  *   sparse_piece    hgibbs_sparse_get: bytes of index buffers per piece of markers (0 = automatic: a quarter of the free device memory,
  *                   at most 1 GiB; a marker alone may exceed it)
@@ -612,6 +613,29 @@ int hgibbs_king_pairs_get(hgibbs_t h, uint32_t* ab, int32_t* counts, double* kin
 /* device time of the last hgibbs_king / hgibbs_king_pairs in ms: every kernel of the call (image, zeroing, products, every run of the
  * list), not the host copies or the allocations */
 int hgibbs_last_king_ms(hgibbs_t h, double* ms);
+
+/* ---- runs of homozygosity of the loaded rows ------- */
+/* PLINK 1.9's --homozyg scan restated in integers, for every row of the handle over a list of runs: run r is the entries
+ * [run_off[r], run_off[r + 1]) of idx (markers of the handle, ascending) and bp (not decreasing), run_off[0] = 0; a position is an entry.
+ * Codes: 1 = het, 3 = missing call.  Within a run of L entries window s covers the positions [s, s + window), 0 <= s <= L - window, and
+ * is homozygous when it holds at most window_het hets and at most window_missing missing calls.  A position that lies in n windows is
+ * covered when at least need[n] of them are homozygous (the caller's table: the smallest c with (double)c / (double)n >= threshold;
+ * need[0] is not read).  A segment is a maximal stretch of covered positions, also cut between neighbours whose bp differ by more than
+ * gap_bp.  Segment [first, last] with nsnp = last - first + 1 and len = bp[last] - bp[first] is kept iff nsnp >= min_snps, len >= min_bp,
+ * len <= dens_bp nsnp (in 64 bits) and, unless max_het is UINT32_MAX, nhet <= max_het.  A run shorter than the window has no segment.
+ * Integers only: the list is bit-identical for any capacity of the list and any repeat.  One rank only.  Refused: a handle without
+ * genotypes, several ranks, a null argument, window outside 1..64, need[n] outside 1..n for an n in 1..window, a marker index >= M, idx
+ * not ascending or bp decreasing within a run, bp outside 0..2^62, a negative limit, more than 65535 runs, 2^31 entries or more,
+ * buffers that do not fit in free device memory.  A refused call leaves the previous list alone. */
+typedef struct { uint32_t window, window_het, window_missing; uint32_t need[65]; uint32_t min_snps;
+                 int64_t min_bp, dens_bp, gap_bp; uint32_t max_het /* UINT32_MAX: none */; } hgibbs_roh_params;
+typedef struct { uint32_t row, first, last /* positions in idx, inclusive */, nsnp, nhet, nmiss; } hgibbs_roh_seg;
+/* *nseg = the number of kept segments.  The list is an atomic append, counted in full: when it overflows its first capacity (option
+ * roh_list0) the kernel runs once more with the exact one; it is kept in the handle, sorted by (row, first), until the next call. */
+int hgibbs_roh(hgibbs_t h, uint32_t nruns, const uint32_t* run_off /* nruns + 1 */, const uint32_t* idx /* run_off[nruns] markers, ascending within a run */,
+               const int64_t* bp /* per entry of idx */, const hgibbs_roh_params* p, uint64_t* nseg);
+int hgibbs_roh_get(hgibbs_t h, hgibbs_roh_seg* segs);   /* sorted by (row, first); kept on the handle until the next call */
+int hgibbs_last_roh_ms(hgibbs_t h, double* ms);         /* every kernel of the last call, not the host copies; 0 after a refused call */
 
 /* ---- principal components of the loaded rows ------- */
 /* The top K eigenpairs of A = X X' / M_used over the handle's n_local rows, X the chain's standardised genotypes (hgibbs_marker_stats;
