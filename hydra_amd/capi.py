@@ -30,6 +30,7 @@ ABI_SYMBOLS = [
     "hgibbs_firth_fit", "hgibbs_last_firth_ms", "hgibbs_firth_stats",
     "hgibbs_king", "hgibbs_king_pairs", "hgibbs_king_pairs_get", "hgibbs_last_king_ms",
     "hgibbs_roh", "hgibbs_roh_get", "hgibbs_last_roh_ms",
+    "hgibbs_pair_tables", "hgibbs_last_pair_tables_ms", "hgibbs_epi_scan", "hgibbs_epi_scan_get", "hgibbs_last_epi_ms", "hgibbs_epi_test",
     "hgibbs_pca", "hgibbs_last_pca_ms", "hgibbs_region_var", "hgibbs_last_region_var_ms",
     "hgibbs_grm", "hgibbs_grm_info", "hgibbs_last_grm_ms",
     "hgibbs_grm_rowsums", "hgibbs_last_grm_rowsums_ms", "hgibbs_he_fit",
@@ -77,6 +78,11 @@ class FirthRec(C.Structure):
     """hgibbs_firth_rec: flags bit 0 converged, bit 1 degenerate"""
     _fields_ = [("beta", C.c_double), ("K", C.c_double), ("K2", C.c_double), ("g", C.c_double), ("k2_0", C.c_double),
                 ("iters", C.c_int32), ("flags", C.c_uint32)]
+
+
+class EpiResult(C.Structure):
+    """hgibbs_epi_result"""
+    _fields_ = [("ksa", C.c_double), ("lr", C.c_double), ("df", C.c_int), ("iters", C.c_int), ("converged", C.c_int), ("p", C.c_double)]
 
 
 class RohParams(C.Structure):
@@ -286,6 +292,12 @@ def lib():
     L.hgibbs_roh.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int64), C.POINTER(RohParams), C.POINTER(C.c_uint64)]
     L.hgibbs_roh_get.argtypes = [vp, C.c_void_p]
     L.hgibbs_last_roh_ms.argtypes = [vp, dp]
+    L.hgibbs_pair_tables.argtypes = [vp, C.c_uint32, C_U32P, C.c_uint32, C_U32P, u8p, C.POINTER(C.c_int32)]
+    L.hgibbs_last_pair_tables_ms.argtypes = [vp, dp]
+    L.hgibbs_epi_scan.argtypes = [vp, C.c_uint32, C_U32P, C.c_uint32, C_U32P, u8p, C.c_double, C.POINTER(C.c_uint64)]
+    L.hgibbs_epi_scan_get.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), dp]
+    L.hgibbs_last_epi_ms.argtypes = [vp, dp, dp]
+    L.hgibbs_epi_test.argtypes = [C.POINTER(C.c_int32), C.POINTER(EpiResult)]
     L.hgibbs_pca.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double, dp, C.c_uint64, dp, dp, dp, C.POINTER(PcaReport)]
     L.hgibbs_last_pca_ms.argtypes = [vp, dp]
     L.hgibbs_region_var.argtypes = [vp, C.c_int, dp, dp, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), dp, dp]
@@ -424,6 +436,17 @@ def set_tests(U, Phi, a):
         raise ValueError("set_tests: Phi must be (%d, %d) and a (%d,)" % (m, m, m))
     r = SetResult()
     check(lib().hgibbs_set_tests(m, _dp(U), _dp(Phi), _dp(a), C.byref(r)))
+    return r
+
+
+def epi_test(table):
+    """hgibbs_epi_test (host only): BOOST's interaction test of one 2 x 3 x 3 table, table[k, i, j] (or its 18 counts in that order).
+    Returns an EpiResult: ksa, lr, df, iters, converged, p."""
+    t = np.ascontiguousarray(table, dtype=np.int32).reshape(-1)
+    if t.size != 18:
+        raise ValueError("epi_test: the table has 18 counts")
+    r = EpiResult()
+    check(lib().hgibbs_epi_test(_ip(t), C.byref(r)))
     return r
 
 
@@ -942,6 +965,57 @@ class Device:
         v = C.c_double()
         check(self.L.hgibbs_last_roh_ms(self.h, C.byref(v)))
         return v.value
+
+    def _cls(self, cls):
+        if cls is None:
+            return None
+        cls = np.ascontiguousarray(cls, dtype=np.uint8).reshape(-1)
+        if cls.size != self.n_local:
+            raise ValueError("cls must be (%d,)" % self.n_local)
+        return cls
+
+    def pair_tables(self, idxA, idxB, cls=None):
+        """The 3 x 3 tables of stored codes of every pair of a marker of idxA with one of idxB, per class of rows
+        (hgibbs_pair_tables): int32 (na, nb, 2, 3, 3), [a, b, k, i, j] = rows of class k with code i at idxA[a] and code j at idxB[b];
+        cls (n_local,) of 0 / 1, None = every row class 0.  Option ptab_split: ranges of individuals split over workgroups."""
+        A = np.ascontiguousarray(idxA, dtype=np.uint32).reshape(-1)
+        B = np.ascontiguousarray(idxB, dtype=np.uint32).reshape(-1)
+        cls = self._cls(cls)
+        out = np.zeros((A.size, B.size, 2, 3, 3), dtype=np.int32)
+        pad = np.zeros(1, dtype=np.uint32)  # (an empty list still needs an address: the call refuses it by name)
+        check(self.L.hgibbs_pair_tables(self.h, A.size, (A if A.size else pad).ctypes.data_as(C_U32P), B.size, (B if B.size else pad).ctypes.data_as(C_U32P),
+                                        _u8(cls) if cls is not None else None, _ip(out) if out.size else _ip(np.zeros(1, dtype=np.int32))))
+        return out
+
+    def last_pair_tables_ms(self):
+        v = C.c_double()
+        check(self.L.hgibbs_last_pair_tables_ms(self.h, C.byref(v)))
+        return v.value
+
+    def epi_scan(self, idxA, idxB, cls, threshold):
+        """BOOST's screen on the device (hgibbs_epi_scan, then hgibbs_epi_scan_get): every pair of a marker of idxA with one of idxB
+        (idxB None: the pairs a < b of idxA) whose Kirkwood bound reaches threshold (less the rounding slack), sorted by (a, b).  Returns
+        ab uint32 (P, 2) the positions in the lists, tables int32 (P, 2, 3, 3), ksa float64 (P,) the device's values."""
+        A = np.ascontiguousarray(idxA, dtype=np.uint32).reshape(-1)
+        B = None if idxB is None else np.ascontiguousarray(idxB, dtype=np.uint32).reshape(-1)
+        cls = self._cls(cls)
+        pad = np.zeros(1, dtype=np.uint32)
+        n = C.c_uint64()
+        check(self.L.hgibbs_epi_scan(self.h, A.size, (A if A.size else pad).ctypes.data_as(C_U32P), 0 if B is None else B.size,
+                                     None if B is None else (B if B.size else pad).ctypes.data_as(C_U32P), _u8(cls) if cls is not None else None,
+                                     float(threshold), C.byref(n)))
+        P = n.value
+        ab = np.zeros((P, 2), dtype=np.uint32)
+        tab = np.zeros((P, 2, 3, 3), dtype=np.int32)
+        ksa = np.zeros(P)
+        check(self.L.hgibbs_epi_scan_get(self.h, ab.ctypes.data_as(C.POINTER(C.c_uint32)), _ip(tab), _dp(ksa)))
+        return ab, tab, ksa
+
+    def last_epi_ms(self):
+        """(products ms, screen ms) of the last epi_scan"""
+        a, b = C.c_double(), C.c_double()
+        check(self.L.hgibbs_last_epi_ms(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def grm(self, a0=0, acount=None):
         """S = X X' and NSNP of rows [a0, a0 + acount), each with its columns 0 .. a (hgibbs_grm): packed 1-D arrays in GCTA's order,

@@ -220,6 +220,14 @@ struct hgibbs_ctx {
     long long roh_list0 = 0; // option roh_list0: first capacity of hgibbs_roh's segment list (0 = RH_LIST0); a second run follows when it overflows
     double roh_ms = 0.0;     // device time of the last hgibbs_roh (every run of the kernel); 0 after a refused call
     std::vector<hgibbs_roh_seg> roh_segs; // the last hgibbs_roh list, sorted by (row, first)
+    int ptab_split = 0;      // option ptab_split: ranges of individuals the workgroups of hgibbs_pair_tables split the columns into (0 = automatic)
+    double ptab_ms = 0.0;    // device time of the last hgibbs_pair_tables (class image, marker counts, zeroing, products, tables); 0 after a refused call
+    long long epi_list0 = 0; // option epi_list0: first capacity of hgibbs_epi_scan's pair list (0 = EP_LIST0); a second run follows when it overflows
+    int epi_block = 0;       // option epi_block: list positions a side of a block of hgibbs_epi_scan's pair space (0 = EP_BLOCK)
+    double epi_ms[2] = {0, 0}; // device time of the last hgibbs_epi_scan: the products and the screen, every run; 0 after a refused call
+    std::vector<uint32_t> epi_ab;     // the last hgibbs_epi_scan list, sorted by (a, b): the positions a, b per pair
+    std::vector<int32_t> epi_tables;  // 18 counts per pair
+    std::vector<double> epi_ksa;      // the device's KSA per pair
     int grm_split = 0;     // option grm_split: ranges of markers the workgroups of hgibbs_grm split the k dimension into (0 = automatic)
     double grm_ms = 0.0;   // device time of the last hgibbs_grm (scale, table, image, zeroing, products, rounding)
     uint32_t grm_used = 0; // M_used and E of the last hgibbs_grm (hgibbs_grm_info)
@@ -1324,6 +1332,15 @@ int hgibbs_set_option(hgibbs_t h, const char* name, int64_t value)
     } else if (!std::strcmp(name, "roh_list0")) {
         if (value < 0 || value > (1ll << 31)) return fail("roh_list0 must be in [0,2147483648] (0 = automatic: 2^20 segments)");
         h->roh_list0 = (long long)value;
+    } else if (!std::strcmp(name, "ptab_split")) {
+        if (value < 0 || value > 65535) return fail("ptab_split must be in [0,65535] (0 = automatic)");
+        h->ptab_split = (int)value;
+    } else if (!std::strcmp(name, "epi_list0")) {
+        if (value < 0 || value > (1ll << 28)) return fail("epi_list0 must be in [0,268435456] (0 = automatic: 2^20 pairs)");
+        h->epi_list0 = (long long)value;
+    } else if (!std::strcmp(name, "epi_block")) {
+        if (value < 0 || value > 65536) return fail("epi_block must be in [0,65536] (0 = automatic: 1024 list positions a side)");
+        h->epi_block = (int)value;
     } else if (!std::strcmp(name, "grm_split")) {
         if (value < 0 || value > 65535) return fail("grm_split must be in [0,65535] (0 = automatic)");
         h->grm_split = (int)value;
@@ -2229,6 +2246,7 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
 #include "hg_firth.hip.h"
 #include "hg_king.hip.h"
 #include "hg_roh.hip.h"
+#include "hg_pairtab.hip.h"
 #include "hg_pca.hip.h"
 #include "hg_grm.hip.h"
 #include "hg_grmsums.hip.h"

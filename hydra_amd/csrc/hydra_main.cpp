@@ -93,6 +93,13 @@
 // row with F_ROH, PREFIX.hom.summary one per .bim marker; PREFIX defaults to <dir>/<name>.  Tab-separated; PLINK has not been run
 // against it.  Not covered: --homozyg-group, windows above 64 markers, cM.
 //
+// `--epistasis [--epistasis-chisq T] [--epistasis-sets FILE] [--epistasis-gap KB] [--epistasis-out F]` appended to a bayesMPI command line
+// samples nothing either: BOOST's exhaustive pairwise interaction scan of a case/control phenotype on the chain's rows (run_epistasis,
+// DESIGN.md section 30).  ONE call of hgibbs_epi_scan screens every pair of markers by the Kirkwood bound on the device, hgibbs_epi_test
+// fits the listed pairs on the host, and <dir>/<name>.epi.cc (or F) gets one row per pair with CHISQ >= T (default 30) and DF > 0.
+// Covariates only drop rows.  Not covered: covariate adjustment, PLINK's allelic --fast-epistasis, case-only tests; neither PLINK nor
+// BOOST has been run against it.
+//
 // `--sparse-dir D --sparse-basename B` reads the genotypes from hydra's ten sparse files D/B.{dim,sl?,ss?,si?} (? = 1, 2, m) instead of
 // --bfile's .bed, for the chains and every mode above; --bfile is then optional for the chains (N = --number-individuals, the
 // phenotype file is read line by line), and with it only .fam/.bim are taken from it.  `--bed-to-sparse --bfile X [--sparse-dir D
@@ -170,6 +177,8 @@ struct Options { // src/options.hpp:20-138 (subset that reaches bayesMPI)
     bool he = false, heRows = false;                 // --he: Haseman-Elston regression on the chain's rows; --he-rows: the per-row sums too
     std::string heOut;                               // --he-out F
     bool qc = false, qcMafGiven = false, qcGenoGiven = false, qcMindGiven = false, qcHweGiven = false, qcHetSdGiven = false; // --qc; which thresholds were given
+    bool epistasis = false; // --epistasis: BOOST's pairwise interaction scan of a case/control phenotype (run_epistasis)
+    std::string epiChisq, epiSets, epiGap, epiOut; // --epistasis-chisq T, --epistasis-gap KB as given (checked before the device), --epistasis-sets, --epistasis-out F
     bool homozyg = false; // --homozyg: runs of homozygosity of the chain's rows (run_homozyg)
     // --homozyg-window-snp W, -window-het H, -window-missing X, -window-threshold T, -snp S, -kb L, -density D, -gap G, -het H2 as given
     // (empty: PLINK 1.9's default; checked before the device), --homozyg-out PREFIX
@@ -363,6 +372,11 @@ Options parse(int argc, const char* argv[])
         else if (a == "--he") o.he = true;
         else if (a == "--he-out") o.heOut = need(i);
         else if (a == "--he-rows") o.heRows = true;
+        else if (a == "--epistasis") o.epistasis = true;
+        else if (a == "--epistasis-chisq") o.epiChisq = need(i);
+        else if (a == "--epistasis-sets") o.epiSets = need(i);
+        else if (a == "--epistasis-gap") o.epiGap = need(i);
+        else if (a == "--epistasis-out") o.epiOut = need(i);
         else if (a == "--homozyg") o.homozyg = true;
         else if (a == "--homozyg-window-snp") o.hzWindow = need(i);
         else if (a == "--homozyg-window-het") o.hzWindowHet = need(i);
@@ -1986,6 +2000,19 @@ int run_assoc(const Options& opt, const Cohort& co, const std::vector<double>& y
     return 0;
 }
 
+// The two values of a case/control phenotype on the kept rows, ascending (the larger one is the case); anything else is refused in
+// the name of the mode `flag` (--assoc-logistic, --epistasis)
+std::vector<double> case_control_values(const char* flag, const std::vector<double>& y_raw, unsigned N)
+{
+    std::vector<double> vals(y_raw.begin(), y_raw.begin() + N);
+    std::sort(vals.begin(), vals.end());
+    vals.erase(std::unique(vals.begin(), vals.end()), vals.end());
+    if (vals.size() != 2)
+        fatal(std::string("FATAL  : ") + flag + ": the phenotype takes " + std::to_string(vals.size()) +
+              " distinct values on the kept rows, a case/control phenotype takes exactly two (the larger one is the case)");
+    return vals;
+}
+
 // ---- --assoc --assoc-logistic: the logistic score test of a case/control phenotype ----
 struct LogitNull {
     std::vector<double> coef, mu, w, L;
@@ -2008,12 +2035,7 @@ struct LogitNulls {
     LogitNulls(const AssocFrame& fr, const std::vector<double>& y_raw)
         : N(fr.N), q(fr.q), gcol(fr.loco && fr.cr.nchrom > 1), qn(q + (gcol ? 1 : 0)), K(2 + qn), d(fr.N), Zc((size_t)qn * fr.N), U((size_t)K * fr.N)
     {
-        std::vector<double> vals(y_raw.begin(), y_raw.begin() + N);
-        std::sort(vals.begin(), vals.end());
-        vals.erase(std::unique(vals.begin(), vals.end()), vals.end());
-        if (vals.size() != 2)
-            fatal("FATAL  : --assoc-logistic: the phenotype takes " + std::to_string(vals.size()) +
-                  " distinct values on the kept rows, a case/control phenotype takes exactly two (the larger one is the case)");
+        const std::vector<double> vals = case_control_values("--assoc-logistic", y_raw, N);
         if (K > 32)
             fatal("FATAL  : --assoc-logistic: " + std::to_string(fr.C) + " covariates make " + std::to_string(K) + " vectors (y - mu, one per column of the null model" +
                   (gcol ? " with the LOCO predictor" : "") + ", the case indicator), hgibbs_marker_class_sums takes at most 32");
@@ -3466,6 +3488,134 @@ int run_homozyg(const Options& opt, const Cohort& co)
     return 0;
 }
 
+// ---- --epistasis: BOOST's pairwise interaction scan of a case/control phenotype ----
+struct EpistasisArgs {
+    double chisq = 30.0, gapKb = -1.0; // BOOST's screening threshold; gapKb < 0: no gap
+};
+
+EpistasisArgs epistasis_args(const Options& opt)
+{
+    EpistasisArgs a;
+    if (!opt.epiChisq.empty() && (!whole_num(opt.epiChisq, a.chisq) || !std::isfinite(a.chisq) || !(a.chisq > 0.0)))
+        fatal("FATAL  : --epistasis-chisq " + opt.epiChisq + ": the threshold on the statistic must be a finite number > 0");
+    if (!opt.epiGap.empty() && (!whole_num(opt.epiGap, a.gapKb) || !std::isfinite(a.gapKb) || a.gapKb < 0.0 || a.gapKb > 1e12))
+        fatal("FATAL  : --epistasis-gap " + opt.epiGap + ": the gap must be a finite number of kilobases from 0 to 1e12");
+    return a;
+}
+
+int run_epistasis(const Options& opt, const Cohort& co, const std::vector<double>& y_raw)
+{
+    const std::string out = opt.epiOut.empty() ? opt.mcmcOutDir + "/" + opt.mcmcOutNam + ".epi.cc" : opt.epiOut;
+    const EpistasisArgs ea = epistasis_args(opt);
+    const unsigned N = co.Ntot, M = co.Mtot;
+    const std::vector<double> vals = case_control_values("--epistasis", y_raw, N);
+    std::vector<uint8_t> cls(N);
+    unsigned ncase = 0;
+    for (unsigned i = 0; i < N; ++i) ncase += cls[i] = y_raw[i] == vals[1] ? 1 : 0;
+    const BimRows bim = read_bim(opt.bedFile + ".bim", M);
+    if (bim.id.size() != M) fatal("FATAL  : " + opt.bedFile + ".bim: " + std::to_string(bim.id.size()) + " rows, expected " + std::to_string(M));
+    // the lists: every marker against every later one, or the one or two sets of --epistasis-sets
+    std::vector<uint32_t> listA, listB;
+    bool two = false;
+    size_t unknown = 0;
+    if (opt.epiSets.empty()) {
+        listA.resize(M);
+        for (unsigned j = 0; j < M; ++j) listA[j] = j;
+    } else {
+        const MarkerSets ms = read_sets_file(opt.epiSets, opt.bedFile, bim, M, &unknown);
+        if (ms.idx.size() > 2)
+            fatal("FATAL  : --epistasis-sets " + opt.epiSets + " names " + std::to_string(ms.idx.size()) + " sets (" + ms.name[0] + ", " + ms.name[1] + ", " + ms.name[2] +
+                  (ms.idx.size() > 3 ? ", ..." : "") + "): one set is scanned within itself, two against each other, more are not taken");
+        for (size_t s = 0; s < ms.idx.size(); ++s)
+            if (ms.idx[s].empty()) fatal("FATAL  : --epistasis-sets " + opt.epiSets + ": set " + ms.name[s] + " is empty (none of its ids is in " + opt.bedFile + ".bim)");
+        listA = ms.idx[0];
+        two = ms.idx.size() == 2;
+        if (two) listB = ms.idx[1];
+    }
+    auto count_pairs = [&](const std::vector<uint32_t>& A, const std::vector<uint32_t>& B) {
+        if (!two) return (unsigned long long)A.size() * (A.size() - (A.empty() ? 0 : 1)) / 2ull;
+        std::vector<uint8_t> inA(M, 0);
+        for (const uint32_t j : A) inA[j] = 1;
+        unsigned long long both = 0;
+        for (const uint32_t j : B) both += inA[j];
+        return (unsigned long long)A.size() * B.size() - both - both * (both - (both ? 1 : 0)) / 2ull; // less (x, x), and (x, y) with (y, x) once
+    };
+    std::printf("EPISTASIS: %u rows (%u cases, %u controls); %zu markers%s listed, %llu pairs; CHISQ >= %g%s%s\n", N, ncase, N - ncase, listA.size() + listB.size(),
+                two ? " in two sets" : "", count_pairs(listA, listB), ea.chisq, ea.gapKb < 0.0 ? "" : (", gap " + qc_num(ea.gapKb) + " kb").c_str(),
+                unknown ? (", " + std::to_string(unknown) + " ids of the sets are not in the .bim").c_str() : "");
+    std::vector<uint8_t> bed = read_training(opt.bedFile, co.numInds, M);
+    if (opt.epiOut.empty()) make_out_dir(opt);
+    FILE* f = open_out(out, "w");
+    std::fputs("CHR1\tSNP1\tBP1\tCHR2\tSNP2\tBP2\tN\tN_CASE\tN_CTRL\tKSA\tCHISQ\tDF\tP\tOK\n", f);
+
+    hgibbs_t dev = open_training(co, bed);
+    std::vector<double> mstd(M);
+    hg_check(hgibbs_marker_stats(dev, nullptr, mstd.data(), nullptr, nullptr, nullptr), "hgibbs_marker_stats");
+    // a marker without a finite sd (monomorphic, or never called) has one category at most: no interaction to test
+    size_t dropped = 0;
+    for (std::vector<uint32_t>* l : {&listA, &listB}) {
+        const size_t before = l->size();
+        l->erase(std::remove_if(l->begin(), l->end(), [&](uint32_t j) { return !std::isfinite(mstd[j]); }), l->end());
+        dropped += before - l->size();
+    }
+    const unsigned long long tested = count_pairs(listA, listB);
+    uint64_t nlist = 0;
+    double pms = 0.0, sms = 0.0;
+    std::vector<uint32_t> ab;
+    std::vector<int32_t> tab;
+    if (!listA.empty() && (!two || !listB.empty()) && tested) {
+        hg_check(hgibbs_epi_scan(dev, (uint32_t)listA.size(), listA.data(), (uint32_t)listB.size(), two ? listB.data() : nullptr, cls.data(), ea.chisq, &nlist), "hgibbs_epi_scan");
+        ab.resize(2 * nlist);
+        tab.resize(18 * nlist);
+        hg_check(hgibbs_epi_scan_get(dev, ab.data(), tab.data(), nullptr), "hgibbs_epi_scan_get");
+        hg_check(hgibbs_last_epi_ms(dev, &pms, &sms), "hgibbs_last_epi_ms");
+    }
+    hgibbs_destroy(dev);
+
+    // the listed pairs as (first, second) in .bim order with the table turned to match; a pair of two sets that was reached in both
+    // orders is kept once, a marker against itself never
+    struct Row {
+        uint32_t j1, j2;
+        int32_t t[18];
+    };
+    std::vector<Row> rows;
+    rows.reserve(nlist);
+    for (uint64_t p = 0; p < nlist; ++p) {
+        const uint32_t ja = listA[ab[2 * p]], jb = (two ? listB : listA)[ab[2 * p + 1]];
+        if (ja == jb) continue;
+        Row r;
+        r.j1 = std::min(ja, jb);
+        r.j2 = std::max(ja, jb);
+        for (int k = 0; k < 2; ++k)
+            for (int i = 0; i < 3; ++i)
+                for (int j = 0; j < 3; ++j) r.t[9 * k + 3 * i + j] = ja < jb ? tab[18 * p + 9 * k + 3 * i + j] : tab[18 * p + 9 * k + 3 * j + i];
+        rows.push_back(r);
+    }
+    std::sort(rows.begin(), rows.end(), [](const Row& x, const Row& y) { return x.j1 != y.j1 ? x.j1 < y.j1 : x.j2 < y.j2; });
+    rows.erase(std::unique(rows.begin(), rows.end(), [](const Row& x, const Row& y) { return x.j1 == y.j1 && x.j2 == y.j2; }), rows.end());
+    const long long gap = ea.gapKb < 0.0 ? -1 : (long long)std::llround(ea.gapKb * 1000.0);
+    unsigned long long screened = 0, written = 0, near = 0;
+    for (const Row& r : rows) {
+        if (gap >= 0 && bim.chr[r.j1] == bim.chr[r.j2] && std::llabs(bim.bp[r.j1] - bim.bp[r.j2]) <= gap) {
+            ++near;
+            continue;
+        }
+        ++screened;
+        hgibbs_epi_result e{};
+        hg_check(hgibbs_epi_test(r.t, &e), "hgibbs_epi_test");
+        if (!(e.lr >= ea.chisq) || e.df <= 0) continue;
+        long long n0 = 0, n1 = 0;
+        for (int c = 0; c < 9; ++c) n0 += r.t[c], n1 += r.t[9 + c];
+        std::fprintf(f, "%s\t%s\t%lld\t%s\t%s\t%lld\t%lld\t%lld\t%lld\t%.9g\t%.9g\t%d\t%.9g\t%d\n", bim.chr[r.j1].c_str(), bim.id[r.j1].c_str(), bim.bp[r.j1],
+                     bim.chr[r.j2].c_str(), bim.id[r.j2].c_str(), bim.bp[r.j2], n0 + n1, n1, n0, e.ksa, e.lr, e.df, e.p, e.converged);
+        ++written;
+    }
+    close_out(f, out);
+    std::printf("EPISTASIS: %llu pairs tested (%zu listed markers without a finite sd left out), %llu screened in%s, %llu written to %s (%.3f ms of products, %.3f ms of screen on the device)\n",
+                tested, dropped, screened, gap >= 0 ? (" (" + std::to_string(near) + " more within the gap)").c_str() : "", written, out.c_str(), pms, sms);
+    return 0;
+}
+
 // ---- the analysis modes -------------------------------------------------------
 // An analysis mode is an option that, appended to a bayesMPI command line, samples nothing and runs one analysis on the chain's rows
 // (run_predict .. run_qc above).  What the modes share is refused in one place, from one row per mode.
@@ -3475,7 +3625,7 @@ struct Mode {
     const char* wmpi;   // how it refuses --mpibayes bayesWMPI, after its flag
     const char* orphan; // the first of its dependent options that was given: they need the mode (null: none was)
 };
-enum { PREDICT, LD, ASSOC, KING, PCA, PVE, GRM, LDSCORE, CLUMP, LDPRUNE, HE, QC, HOMOZYG, NMODES }; // the order in which a mode names the earlier ones it cannot be combined with
+enum { PREDICT, LD, ASSOC, KING, PCA, PVE, GRM, LDSCORE, CLUMP, LDPRUNE, HE, QC, HOMOZYG, EPISTASIS, NMODES }; // the order in which a mode names the earlier ones it cannot be combined with
 
 const char* first_given(std::initializer_list<std::pair<const char*, bool>> deps)
 {
@@ -3670,8 +3820,11 @@ void check_modes(const Options& opt, int nranks)
                       {"--homozyg-window-missing", !opt.hzWindowMissing.empty()}, {"--homozyg-window-threshold", !opt.hzThreshold.empty()},
                       {"--homozyg-snp", !opt.hzSnp.empty()}, {"--homozyg-kb", !opt.hzKb.empty()}, {"--homozyg-density", !opt.hzDensity.empty()},
                       {"--homozyg-gap", !opt.hzGap.empty()}, {"--homozyg-het", !opt.hzHet.empty()}, {"--homozyg-out", !opt.hzOut.empty()}})},
+        {"--epistasis", opt.epistasis, takes,
+         first_given({{"--epistasis-chisq", !opt.epiChisq.empty()}, {"--epistasis-sets", !opt.epiSets.empty()}, {"--epistasis-gap", !opt.epiGap.empty()},
+                      {"--epistasis-out", !opt.epiOut.empty()}})},
     };
-    for (const int i : {LD, PREDICT, ASSOC, KING, PCA, PVE, GRM, LDSCORE, CLUMP, LDPRUNE, HE, QC, HOMOZYG}) {
+    for (const int i : {LD, PREDICT, ASSOC, KING, PCA, PVE, GRM, LDSCORE, CLUMP, LDPRUNE, HE, QC, HOMOZYG, EPISTASIS}) {
         const Mode& m = modes[i];
         const std::string flag = m.flag;
         if (!m.given) {
@@ -3696,6 +3849,7 @@ void check_modes(const Options& opt, int nranks)
         if (i == LDPRUNE) check_ldprune_args(opt);
         if (i == QC) check_qc_args(opt);
         if (i == HOMOZYG) check_homozyg_args(opt);
+        if (i == EPISTASIS) (void)epistasis_args(opt); // refuses by name what is out of range
     }
 }
 
@@ -3775,6 +3929,7 @@ int main(int argc, const char* argv[])
     if (opt.he) return run_he(opt, co, y, covX, C);
     if (opt.qc) return run_qc(opt, co);
     if (opt.homozyg) return run_homozyg(opt, co);
+    if (opt.epistasis) return run_epistasis(opt, co, y);
 
     std::vector<int32_t> groups;
     std::vector<std::vector<double>> mS;

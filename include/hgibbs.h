@@ -226,6 +226,11 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
  *   ldmask_piece    hgibbs_ld_mask: band rows per piece, 0..2^20 (0 = automatic; rounded up to a multiple of 16)
  *   grm_piece       hgibbs_grm, hgibbs_grm_rowsums: pairs per piece of rows, 0..2^25 (0 = automatic: 2^25; a row alone may exceed it)
  *   roh_list0       hgibbs_roh: first capacity of the segment list, 0..2^31 (0 = automatic: 2^20; a second run follows an overflow)
+ *   ptab_split      hgibbs_pair_tables, hgibbs_epi_scan: ranges of individuals split over workgroups, 0..65535 (0 = automatic)
+ *   epi_list0       hgibbs_epi_scan: first capacity of the pair list, 0..2^28 (0 = automatic: 2^20; a second run follows an overflow)
+ *   epi_block       hgibbs_epi_scan: list positions a side of a block of the pair space, 0..65536 (0 = automatic: 1024; rounded up to
+ *                   a multiple of 32).  A knob for tests of the block scheme, not for tuning: the host waits for the device twice per
+ *                   block, which hgibbs_last_epi_ms does not show, so small blocks cost wall time; a block's tables take 72 bytes a pair
  *   rowsums_ranges  hgibbs_row_sums: at most this many ranges of markers split over workgroups, 0..65535 (0 = automatic)
  *   sparse_piece    hgibbs_sparse_get: bytes of index buffers per piece of markers (0 = automatic: a quarter of the free device memory,
  *                   at most 1 GiB; a marker alone may exceed it)
@@ -636,6 +641,48 @@ int hgibbs_roh(hgibbs_t h, uint32_t nruns, const uint32_t* run_off /* nruns + 1 
                const int64_t* bp /* per entry of idx */, const hgibbs_roh_params* p, uint64_t* nseg);
 int hgibbs_roh_get(hgibbs_t h, hgibbs_roh_seg* segs);   /* sorted by (row, first); kept on the handle until the next call */
 int hgibbs_last_roh_ms(hgibbs_t h, double* ms);         /* every kernel of the last call, not the host copies; 0 after a refused call */
+
+/* ---- joint genotype tables of pairs of markers, and the epistasis screen ------- */
+/* hgibbs_pair_tables: for every a < na and b < nb, tables[((a * nb + b) * 2 + k) * 9 + 3 * i + j] = the number of the handle's rows of
+ * class k at which marker idxA[a] has stored code i and marker idxB[b] has stored code j, i and j in {0, 1, 2} as hgibbs_load_bed reads
+ * them.  A row with a missing call at either marker is counted in no cell; padding slots count nowhere.  cls gives the class (0 or 1)
+ * of each of the n_local rows; NULL puts every row into class 0 (the class-1 tables are then zero).  The lists are arbitrary: unordered,
+ * with holes, the same marker on both sides (the table is then diagonal) or twice in a list.  Every cell is an exact integer: the result
+ * is bit-identical for any tiling, any value of the option ptab_split, any cut of the lists over calls and any repeat.  One rank only.
+ * Refused: a null handle, list or result; na or nb equal to 0; an index >= M; an entry of cls above 1; a handle without genotypes;
+ * several ranks; n_local >= 2^29; buffers (72 bytes a pair) that do not fit in free device memory.  Computes the marker stats when the
+ * handle has none yet. */
+int hgibbs_pair_tables(hgibbs_t h, uint32_t na, const uint32_t* idxA, uint32_t nb, const uint32_t* idxB,
+                       const uint8_t* cls /* n_local: 0 or 1; NULL = every row class 0 */, int32_t* tables /* na x nb x 18 */);
+int hgibbs_last_pair_tables_ms(hgibbs_t h, double* ms); /* every kernel of the last call, not the host copies; 0 after a refused call */
+/* hgibbs_epi_scan: BOOST's screen over the pairs (a, b) of list positions -- with idxB every a < na against every b < nb, with idxB NULL
+ * the pairs a < b of list A -- in blocks of the pair space: a block's tables are made as above, a second kernel evaluates the Kirkwood
+ * superposition bound KSA of each pair from its 18 counts in f64 (the operations of hgibbs_epi_test's ksa, in the same order), and the
+ * pair is appended to a list when KSA >= threshold - delta, delta = 2^-44 * 2 n (4 ln n + ln 18) with n = n_local: the bound of the
+ * evaluation's rounding, so that no pair whose exact KSA reaches the threshold is lost.  Only the list crosses the bus.  The list is an
+ * atomic append counted in full: when it overflows its first capacity (option epi_list0) the scan runs once more with the exact one.  It
+ * is kept in the handle, sorted by (a, b), until the next call; *npairs = its length.  A pair's value depends on its integer table
+ * alone: the list is identical for any ptab_split, any block size (option epi_block) and any repeat.  The host synchronises with the
+ * device after each block's products and after its screen, an overflow of the list recomputes every block, and a scan with idxB NULL
+ * computes its diagonal blocks in full: harmless at the default block size, and the reason epi_block is a test knob.  Refused: threshold not finite or
+ * <= 0, a null npairs, and everything hgibbs_pair_tables refuses.  A refused call leaves the previous list alone. */
+int hgibbs_epi_scan(hgibbs_t h, uint32_t na, const uint32_t* idxA, uint32_t nb, const uint32_t* idxB /* NULL: pairs a < b of list A */,
+                    const uint8_t* cls, double threshold, uint64_t* npairs);
+/* copies the list out: ab[2 p], ab[2 p + 1] = the positions a, b in the lists; tables[18 p + 9 k + 3 i + j]; ksa[p] the device's
+ * value.  Any pointer may be NULL. */
+int hgibbs_epi_scan_get(hgibbs_t h, uint32_t* ab /* 2 per pair: positions in the lists */, int32_t* tables /* 18 per pair */, double* ksa);
+/* device time of the last hgibbs_epi_scan in ms, every run of the list: the products (class image, marker counts, tables) and the
+ * screen; both 0 after a refused call.  Either pointer may be NULL. */
+int hgibbs_last_epi_ms(hgibbs_t h, double* products_ms, double* screen_ms);
+/* hgibbs_epi_test (hg_epi.cpp: no device, no handle): BOOST's interaction test of one table18[9 k + 3 i + j].  ksa: the Kirkwood bound
+ * 2 (sum n log(n_ijk / n) - sum n log p^K_ijk), p^K = pi_ij. pi_i.k pi_.jk / (pi_i.. pi_.j. pi_..k) / eta, over the cells n_ijk > 0.
+ * lr = 2 (L_S - L_H) >= 0: L_H the log-likelihood of the homogeneous-association model fitted by iterative proportional fitting from a
+ * table of ones, cycling over the ij, ik, jk margins, until no cell moves by more than 1e-10 n in a cycle (converged = 1) or 2000 cycles
+ * are done (converged = 0: lr is then an upper bound); iters = the cycles.  df = (I - 1)(J - 1) with I, J the codes of each marker that
+ * occur: 0, 1, 2 or 4; df = 0 gives lr = 0, iters = 0, converged = 1, p = NaN.  p: erfc(sqrt(lr / 2)), exp(-lr / 2),
+ * exp(-lr / 2) (1 + lr / 2) for df = 1, 2, 4.  Refused: a null argument, a negative count. */
+typedef struct { double ksa, lr; int df, iters, converged; double p; } hgibbs_epi_result;
+int hgibbs_epi_test(const int32_t* table18, hgibbs_epi_result* r);
 
 /* ---- principal components of the loaded rows ------- */
 /* The top K eigenpairs of A = X X' / M_used over the handle's n_local rows, X the chain's standardised genotypes (hgibbs_marker_stats;
