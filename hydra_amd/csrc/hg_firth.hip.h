@@ -17,8 +17,10 @@
 //   pass 0   at t = 0: k2_0 = K''(0), scale = 1 / sqrt(k2_0); a k2_0 that is not finite or not positive ends the entry (flag bit 1, every
 //            other field 0).  lo = -inf, hi = +inf, tg = 0 (the last point with a finite g and g').
 //   rule     g and g' finite at t: tg = t; g > 0 sets lo = t, g < 0 sets hi = t; the proposal is t' = t - g / g'.  FIRST the stop rule
-//            |t' - t| <= 1e-9 max(|t|, scale): the entry takes t' and one closing pass for K(t') and K''(t'), then is converged (flag
-//            bit 0).  ONLY THEN the safeguard: a t' not strictly inside (lo, hi) becomes the midpoint when both ends are finite, else
+//            g' < 0 and |t' - t| <= 1e-9 max(|t|, scale): the entry takes t' and one closing pass for K(t') and K''(t'), then is
+//            converged (flag bit 0).  (Without g' < 0 the rule would also stop next to a local MINIMUM of the penalised likelihood:
+//            with few rows and a small mu g'(0) > 0, and a score that leaves g(0) within 1e-9 scale g' of 0 closed the entry at 0.)
+//            ONLY THEN the safeguard: a t' not strictly inside (lo, hi) becomes the midpoint when both ends are finite, else
 //            2 t, or +-scale with g's sign when t = 0.  g or g' not finite at t (the probabilities have saturated): the bracket end on
 //            t's side of tg becomes t and the next point is (t + tg) / 2; no sign is taken.
 //   bound    at most FIRTH_PASSES passes after pass 0, the closing one included; an entry still open then has no flag.  The rule runs
@@ -109,7 +111,7 @@ __global__ __launch_bounds__(SPA_TPB) void k_firth_fit(const uint8_t* __restrict
             if (g > 0.0) lo = t;
             else if (g < 0.0) hi = t;
             tn = t - g / gp;
-            if (fabs(tn - t) <= FIRTH_STOP * fmax(fabs(t), scale)) closing = true;
+            if (gp < 0.0 && fabs(tn - t) <= FIRTH_STOP * fmax(fabs(t), scale)) closing = true;
             else if (!(tn > lo && tn < hi))
                 tn = (isfinite(lo) && isfinite(hi)) ? 0.5 * (lo + hi) : t == 0.0 ? (g > 0.0 ? scale : -scale) : 2.0 * t;
         } else {

@@ -575,7 +575,7 @@ typedef struct {
  *   g(t) = s - K' + K''' / (2 K''),  g'(t) = -K'' + (K'''' / K'' - (K''' / K'')^2) / 2.
  * Root rule, Newton on g with a bracket: pass 0 is at t = 0 and gives k2_0 and scale = 1 / sqrt(k2_0) (a k2_0 that is not finite or not
  * positive sets the degenerate flag and ends the entry); lo = -inf, hi = +inf, tg = 0.  When g and g' are finite at t: tg = t, g > 0
- * sets lo = t, g < 0 sets hi = t, the proposal is t' = t - g / g'; first the stop rule |t' - t| <= 1e-9 max(|t|, scale) (the entry takes
+ * sets lo = t, g < 0 sets hi = t, the proposal is t' = t - g / g'; first the stop rule g' < 0 and |t' - t| <= 1e-9 max(|t|, scale) (the entry takes
  * t', one closing pass gives K(t') and K''(t'), the converged flag is set), only then the safeguard (a t' not strictly inside (lo, hi)
  * becomes the midpoint when both ends are finite, else 2 t, or +-scale with g's sign when t = 0).  When g or g' is not finite at t (the
  * probabilities have saturated): the bracket end on t's side of tg becomes t, the next point is (t + tg) / 2, no sign is taken.  At

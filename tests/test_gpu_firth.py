@@ -9,6 +9,7 @@ import pytest
 from hydra_amd import capi, synth
 
 import firth_restate as F
+import spa_restate as R
 
 pytestmark = pytest.mark.gpu
 
@@ -104,6 +105,103 @@ def test_k2_0_is_that_of_spa_roots_bit_for_bit(q):
     firth, spa = dev.firth_fit(*args), dev.spa_roots(*args)
     for e in idx:
         assert firth[e].k2_0 > 0.0 and firth[e].k2_0.hex() == spa[e].k2_0.hex(), (e, firth[e].k2_0.hex(), spa[e].k2_0.hex())
+    dev.close()
+
+
+# The same for the admitted entries of firth_restate.rule_cases(), as test_rule_cases_admitted_entries_are_well_conditioned prints it.
+# Measured on the CPU: beta 5.53e-13, K 6.92e-13, K'' 4.65e-12, p 4.55e-13.  The margin of ten and its reason are those above.
+RULE_TOL_BETA = 5.6e-12
+RULE_TOL_K = 7.0e-12
+RULE_TOL_K2 = 4.7e-11
+RULE_TOL_P = 4.6e-12
+
+
+def against(case, recs, tol_beta, tol_k, tol_k2, tol_p, passes):
+    """every record of a call on the whole of `case` against the float64 restatement, all converged; with `passes` the numbers of
+    passes too"""
+    for e in range(R.case_size(case)):
+        got, want = recs[e], F.fit(R.case_a(case, e), case["mu"], case["s"][e])
+        where = (case["n"], case["Z"].shape[1], e)
+        assert got.flags == want["flags"] == F.CONVERGED, (where, got.flags, want["flags"])
+        if passes:
+            assert got.iters == want["iters"], (where, got.iters, want["iters"])
+        assert close(got.k2_0, want["k2_0"], 1e-12), where
+        gp, wp = capi.firth_stats(case["s"][e], got), F.stats(case["s"][e], want)
+        assert gp[3] and wp[3], where
+        assert close(got.beta, want["beta"], tol_beta), (where, got.beta, want["beta"])
+        assert close(got.K, want["K"], tol_k), (where, got.K, want["K"])
+        assert close(got.K2, want["K2"], tol_k2), (where, got.K2, want["K2"])
+        assert close(gp[2], wp[2], tol_p), (where, gp, wp)
+
+
+def same_bits_however_called(dev, case, recs):
+    """reversed, entry by entry, repeated, and in pieces of 1, of 3 and automatic"""
+    m = R.case_size(case)
+    everything = np.arange(m)
+    rev = call(dev, case, everything[::-1])
+    assert all(raw(rev, m - 1 - e) == raw(recs, e) for e in range(m))
+    assert b"".join(raw(call(dev, case, [e])) for e in range(m)) == raw(recs)
+    assert raw(call(dev, case, everything)) == raw(recs)
+    for piece in (1, 3, 0):
+        dev.set_option("firth_piece", piece)
+        assert raw(call(dev, case, everything)) == raw(recs), piece
+
+
+def test_admitted_entries_against_the_restatement():
+    """Tiny entries that take the rule's branches one by one (firth_restate.ADMITTED and NEAR_MINIMUM: +-scale from 0, midpoints, 2 t, the
+    saturated point with its bracket end, no stop next to a local minimum) and on which the float64 rule, the longdouble rule and
+    twenty perturbed copies of either agree in every pass: flags and passes are the restatement's, the numbers lie within the tolerance
+    measured for these entries."""
+    for case in F.rule_cases()[0]:
+        dev = device(case["geno"])
+        recs = call(dev, case, np.arange(R.case_size(case)))
+        against(case, recs, RULE_TOL_BETA, RULE_TOL_K, RULE_TOL_K2, RULE_TOL_P, passes=True)
+        same_bits_however_called(dev, case, recs)
+        dev.close()
+
+
+def test_ill_conditioned_entries_end_consistently():
+    """firth_restate.ILL: scores a hair inside the reachable edge and beyond it, first steps that saturate every row, entries that the
+    float64 rule leaves open.  No value and no outcome is the restatement's here: an entry is converged, degenerate or open and says so
+    consistently, and a fit that hgibbs_firth_stats lets stand is a stationary point and a local maximum in longdouble."""
+    entries = opened = stand = 0
+    for case in F.rule_cases()[1]:
+        dev = device(case["geno"])
+        recs = call(dev, case, np.arange(R.case_size(case)))  # (a refusal or a device error raises)
+        for e in range(R.case_size(case)):
+            got = recs[e]
+            where = (case["n"], e)
+            entries += 1
+            assert got.flags in (0, F.CONVERGED, F.DEGENERATE), (where, got.flags)
+            if got.flags == 0:
+                assert got.iters == F.PASSES and got.K == got.K2 == 0.0, where
+                opened += 1
+            elif got.flags == F.DEGENERATE:
+                assert raw(recs, e) == bytes(40) + (0).to_bytes(4, "little") + (2).to_bytes(4, "little"), where
+            else:
+                assert 1 <= got.iters <= F.PASSES, where
+            if capi.firth_stats(case["s"][e], got)[3]:
+                assert got.flags == F.CONVERGED, where
+                assert F.stationary(R.case_a(case, e, np.longdouble), case["mu"], case["s"][e], dict(beta=got.beta, k2_0=got.k2_0)), (where, got.beta)
+                stand += 1
+        same_bits_however_called(dev, case, recs)
+        dev.close()
+    print("ill-conditioned entries: %d of %d are left open on the device, %d fits stand" % (opened, entries, stand))
+
+
+@pytest.mark.parametrize("n,q", R.EDGE_SHAPES)
+def test_edges_of_q_and_n(n, q):
+    """q = 64 = SPA_QMAX and its neighbours, and cohorts of two rows, of one full BED dword and of one row more, against the restatement
+    within the grid's tolerances (test_float64_against_longdouble_on_the_edges_of_q_and_n: the gap stays under a tenth of them); at
+    q = 64 K''(0) has the bits of hgibbs_spa_roots', as in test_k2_0_is_that_of_spa_roots_bit_for_bit"""
+    case = R.edge_case(n, q)
+    dev = device(case["geno"])
+    recs = call(dev, case, np.arange(R.EDGE_M))
+    against(case, recs, TOL_BETA, TOL_K, TOL_K2, TOL_P, passes=False)
+    if q == 64:
+        spa = dev.spa_roots(case["markers"], case["Z"], case["mu"], case["B"], case["xv"], case["s"])
+        for e in range(R.EDGE_M):
+            assert recs[e].k2_0 > 0.0 and recs[e].k2_0.hex() == spa[e].k2_0.hex(), (e, recs[e].k2_0.hex(), spa[e].k2_0.hex())
     dev.close()
 
 

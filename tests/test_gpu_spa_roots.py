@@ -84,6 +84,100 @@ def test_grid_against_the_restatement(n, q):
     dev.close()
 
 
+# The same for the admitted entries of spa_restate.rule_cases(), as test_rule_cases_admitted_entries_are_well_conditioned prints it.
+# Measured on the CPU: t 6.10e-13, K 1.02e-12, K'' 1.29e-11, p 3.09e-12 (the sums of pass 0: 1.9e-15 at the most).  The margin of ten
+# and its reason are those above.
+RULE_TOL_T = 6.1e-12
+RULE_TOL_K = 1.1e-11
+RULE_TOL_K2 = 1.3e-10
+RULE_TOL_P = 3.1e-11
+
+
+def against(case, recs, tol_t, tol_k, tol_k2, tol_p, passes):
+    """every record of a call on the whole of `case` against the float64 restatement; with `passes` the numbers of passes too"""
+    for e in range(R.case_size(case)):
+        got, want = recs[e], R.roots(R.case_a(case, e), case["mu"], case["s"][e])
+        where = (case["n"], case["Z"].shape[1], e)
+        assert got.flags == want["flags"] and got.reserved_ == 0, (where, got.flags, want["flags"])
+        if passes:
+            assert list(got.iters) == want["iters"], (where, list(got.iters), want["iters"])
+        for name in ("k2_0", "s_lo", "s_hi"):
+            assert close(getattr(got, name), want[name], 1e-12), (where, name)
+        for z in range(2):
+            if got.flags >> z & 1:
+                assert close(got.t[z], want["t"][z], tol_t), (where, z, got.t[z], want["t"][z])
+                assert close(got.K[z], want["K"][z], tol_k), (where, z, got.K[z], want["K"][z])
+                assert close(got.K2[z], want["K2"][z], tol_k2), (where, z, got.K2[z], want["K2"][z])
+            else:
+                assert got.flags >> (2 + z) & 1 and (got.t[z], got.K[z], got.K2[z], got.iters[z]) == (0.0, 0.0, 0.0, 0), where
+        gp, wp = capi.spa_pvalue(case["s"][e], got), R.pvalue(case["s"][e], want)
+        assert gp[3] == wp[3], where
+        if wp[3]:
+            assert close(gp[2], wp[2], tol_p), (where, gp, wp)
+
+
+def same_bits_however_called(dev, case, recs):
+    """reversed, entry by entry and repeated"""
+    m = R.case_size(case)
+    everything = np.arange(m)
+    rev = call(dev, case, everything[::-1])
+    assert all(raw(rev, m - 1 - e) == raw(recs, e) for e in range(m))
+    assert b"".join(raw(call(dev, case, [e])) for e in range(m)) == raw(recs)
+    assert raw(call(dev, case, everything)) == raw(recs)
+
+
+def test_admitted_entries_against_the_restatement():
+    """Tiny entries that take the rule's branches one by one (spa_restate.ADMITTED: midpoints, one-tailed entries, the score 0 whose
+    first proposal is the bracket's end) and on which the float64 rule, the longdouble rule and twenty perturbed copies of either agree
+    in every pass: flags and passes are the restatement's, the numbers lie within the tolerance measured for these entries."""
+    for case in R.rule_cases()[0]:
+        dev = device(case["geno"])
+        recs = call(dev, case, np.arange(R.case_size(case)))
+        against(case, recs, RULE_TOL_T, RULE_TOL_K, RULE_TOL_K2, RULE_TOL_P, passes=True)
+        same_bits_however_called(dev, case, recs)
+        dev.close()
+
+
+def test_ill_conditioned_entries_end_in_one_of_three_ways():
+    """spa_restate.ILL: scores a hair inside the reachable edge, first steps that saturate every row, entries that the float64 rule leaves
+    open.  No value and no outcome is the restatement's here; each tail is unreachable, converged or open, and says so consistently."""
+    tails = opened = 0
+    for case in R.rule_cases()[1]:
+        dev = device(case["geno"])
+        recs = call(dev, case, np.arange(R.case_size(case)))  # (a refusal or a device error raises)
+        for e in range(R.case_size(case)):
+            got = recs[e]
+            where = (case["n"], e)
+            assert got.flags < 16 and got.reserved_ == 0, where
+            for z in range(2):
+                unreachable, converged = got.flags >> (2 + z) & 1, got.flags >> z & 1
+                assert not (unreachable and converged), where
+                if unreachable:
+                    assert (got.t[z], got.K[z], got.K2[z], got.iters[z]) == (0.0, 0.0, 0.0, 0), where
+                elif converged:
+                    assert 1 <= got.iters[z] <= R.PASSES, where
+                else:
+                    assert got.iters[z] == R.PASSES and got.K[z] == got.K2[z] == 0.0, where
+                    opened += 1
+                tails += not unreachable
+            if capi.spa_pvalue(case["s"][e], got)[3]:
+                assert got.flags == 3, where
+        same_bits_however_called(dev, case, recs)
+        dev.close()
+    print("ill-conditioned entries: %d of %d reachable tails are left open on the device" % (opened, tails))
+
+
+@pytest.mark.parametrize("n,q", R.EDGE_SHAPES)
+def test_edges_of_q_and_n(n, q):
+    """q = 64 = SPA_QMAX and its neighbours, and cohorts of two rows, of one full BED dword and of one row more, against the restatement
+    within the grid's tolerances (test_float64_against_longdouble_on_the_edges_of_q_and_n: the gap stays under a tenth of them)"""
+    case = R.edge_case(n, q)
+    dev = device(case["geno"])
+    recs = call(dev, case, np.arange(R.EDGE_M))
+    against(case, recs, TOL_T, TOL_K, TOL_K2, TOL_P, passes=False)
+    dev.close()
+
+
 def test_refusals_leave_the_handle_usable():
     case = R.roots_case(261, 5)
     dev = device(case["geno"])

@@ -76,6 +76,87 @@ def test_a_score_beyond_the_range_of_the_derivative_is_unreachable():
         assert one["flags"] & 12 == (4 if r["s_hi"] < -r["s_lo"] else 8)
 
 
+def gaps(cases, worst):
+    """the largest float64 / longdouble relative differences over the entries of `cases`, into worst; the flags agree"""
+    for case in cases:
+        for e in range(R.case_size(case)):
+            a, b = (R.roots(R.case_a(case, e, dt), np.asarray(case["mu"], dt), case["s"][e], dt) for dt in (np.float64, np.longdouble))
+            assert a["flags"] == b["flags"], (case["n"], e)
+            for k in ("k2_0", "s_lo", "s_hi"):
+                worst[k] = max(worst[k], R.rel(a[k], b[k]))
+            for z in range(2):
+                if a["flags"] >> z & 1:
+                    for k in ("t", "K", "K2"):
+                        worst[k] = max(worst[k], R.rel(a[k][z], b[k][z]))
+            pa, pb = R.pvalue(case["s"][e], a), R.pvalue(case["s"][e], b)
+            assert pa[3] == pb[3], (case["n"], e)
+            if pa[3]:
+                worst["p"] = max(worst["p"], R.rel(pa[2], pb[2]))
+    return worst
+
+
+def report(what, worst):
+    print("%s, largest relative difference float64 / longdouble: %s" % (what, ", ".join("%s %.3g" % kv for kv in worst.items())))
+
+
+def case_traces(cases, dtype=np.float64):
+    return [R.traced(R.roots, R.case_a(case, e, dtype), case["mu"], case["s"][e], dtype) + (case, e) for case in cases for e in range(R.case_size(case))]
+
+
+def test_rule_cases_admitted_entries_are_well_conditioned():
+    """Every admitted entry of rule_cases() passes admission(): the GPU test may hold the device to the float64 rule's flags and passes
+    there.  Prints the coverage table and what the tolerances of test_admitted_entries_against_the_restatement are ten times of."""
+    admitted, ill = R.rule_cases()
+    for case in admitted:
+        for e in range(R.case_size(case)):
+            assert R.admission(R.roots, R.case_a(case, e), case["mu"], case["s"][e]) is None, (case["n"], e)
+    here, there = case_traces(admitted), case_traces(ill)
+    print("branch: tails of admitted entries, tails of ill-conditioned entries (float64)")
+    count = {}
+    for letter in "NSCMDO":
+        count[letter] = [sum(letter in t for _, tr, _, _ in which for t in tr) for which in (here, there)]
+        print("  %s: %d, %d" % (letter, *count[letter]))
+    # 2 t needs a proposal outside a bracket with an infinite end.  From inside (0, inf) the sign of K' - tau moves the finite end to t and a
+    # Newton step with K'' > 0 goes towards the other, so it stays inside unless it is not a number or not finite: K'' = 0 to the last
+    # place, every row saturated, and K' - tau <= 0 there -- a score within rounding of the reachable edge.  Ill-conditioned input only.
+    assert all(count[letter][0] > 0 for letter in "NSCM") and count["D"] == [0, count["D"][1]] and count["D"][1] > 0, count
+    assert count["O"][0] == 0 and count["O"][1] > 0  # an open tail in float64: neither bit set, iters == PASSES
+    opened = [(r, z) for r, tr, _, _ in there for z in range(2) if R.OPEN in tr[z]]
+    assert all(r["iters"][z] == R.PASSES and not r["flags"] >> z & 5 and r["K"][z] == r["K2"][z] == 0 for r, z in opened)
+    for which in (admitted, ill):  # the shapes and the inputs the two lists are meant to span
+        assert {case["n"] for case in which} == set(R.RULE_N)
+        assert any((case["geno"] == 3).any() for case in which) and any((case["geno"] != 3).all() for case in which)
+        assert any(case["mu"].min() == 1e-12 and case["mu"].max() == 1 - 1e-12 for case in which)
+        assert any(np.ptp(case["mu"]) == 0 for case in which)
+    assert {r["flags"] for r, _, _, _ in here} >= {3, 1 | 8, 2 | 4}  # both tails, and one reachable tail of either side
+    report("admitted entries", gaps(admitted, dict(t=0.0, K=0.0, K2=0.0, p=0.0, k2_0=0.0, s_lo=0.0, s_hi=0.0)))
+
+
+def test_rule_cases_saturating_entries_saturate():
+    """the five entries before the open ones of ILL: at the first point t = tau / K''(0) every row with a != 0 has p (1 - p) < 1e-7"""
+    k = 0
+    for spec in R.ILL:
+        if spec[4] != 300.0:
+            continue
+        k += 1
+        e = R.rule_entry(*spec)
+        a = e["xv"][e["geno"]]
+        k2_0, _, _ = R.pass0(a, e["mu"])
+        u = a[a != 0] * (abs(e["s"]) / k2_0)
+        p = e["mu"][a != 0] / (e["mu"][a != 0] + (1 - e["mu"][a != 0]) * np.exp(-u))
+        assert np.all(p * (1 - p) < 1e-7), spec
+    assert k == 5
+
+
+def test_float64_against_longdouble_on_the_edges_of_q_and_n():
+    """The existing tolerances of tests/test_gpu_spa_roots.py (t 2.7e-12, K 4.0e-11, K'' 2.5e-12, p 1.2e-10; 1e-12 on the sums of pass 0) hold
+    for test_edges_of_q_and_n there if the gap measured here stays under a tenth of them."""
+    worst = gaps([R.edge_case(n, q) for n, q in R.EDGE_SHAPES], dict(t=0.0, K=0.0, K2=0.0, p=0.0, k2_0=0.0, s_lo=0.0, s_hi=0.0))
+    report("edges of q and n", worst)
+    for k, tol in dict(t=2.7e-12, K=4.0e-11, K2=2.5e-12, p=1.2e-10, k2_0=1e-12, s_lo=1e-12, s_hi=1e-12).items():
+        assert worst[k] < tol / 10, (k, worst[k])
+
+
 def test_float64_against_longdouble_on_the_gpu_tests_markers():
     """prints what the tolerances of tests/test_gpu_spa_roots.py are ten times of"""
     worst = dict(t=0.0, K=0.0, K2=0.0, p=0.0)
