@@ -623,9 +623,33 @@ class Device:
         check(self.L.hgibbs_add_scalar(self.h, c))
 
     def set_covariates(self, X):
+        """X (n_local, C) replaces the covariates on the handle; None takes them off (hgibbs_set_covariates(NULL, 0))."""
+        if X is None:
+            check(self.L.hgibbs_set_covariates(self.h, None, 0))
+            return
         X = np.ascontiguousarray(X, dtype=np.float64)
         assert X.shape[0] == self.n_local
         check(self.L.hgibbs_set_covariates(self.h, _dp(X), X.shape[1]))
+
+    def cov_dot(self, c, gamma_old):
+        """sum_k X[k, c] * (eps_k + gamma_old * X[k, c]) over all ranks (hgibbs_cov_dot)."""
+        v = C.c_double()
+        check(self.L.hgibbs_cov_dot(self.h, c, gamma_old, C.byref(v)))
+        return v.value
+
+    def cov_update(self, c, dgamma):
+        """eps_k = eps_k + dgamma * X[k, c] (hgibbs_cov_update)."""
+        check(self.L.hgibbs_cov_update(self.h, c, dgamma))
+
+    def w_ars_device_probe(self, dens9, beta_old, safe_limit, seed, ndraws):
+        """hgibbs_w_ars_device_probe: `ndraws` adaptive-rejection draws of an effect on one device lane from the density with the nine
+        parameters dens9.  Returns (microseconds per draw, density evaluations per draw, the last draw)."""
+        d = np.ascontiguousarray(dens9, dtype=np.float64).reshape(-1)
+        if d.size != 9:
+            raise ValueError("w_ars_device_probe: dens9 has nine numbers")
+        us, ev, last = C.c_double(), C.c_double(), C.c_double()
+        check(self.L.hgibbs_w_ars_device_probe(self.h, _dp(d), beta_old, safe_limit, seed, ndraws, C.byref(us), C.byref(ev), C.byref(last)))
+        return us.value, ev.value, last.value
 
     def update_marker(self, marker, dbeta):
         check(self.L.hgibbs_update_marker(self.h, marker, dbeta))

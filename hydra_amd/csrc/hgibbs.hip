@@ -1189,7 +1189,8 @@ int hgibbs_set_covariates(hgibbs_t h, const double* X_host, int C)
 
 int hgibbs_cov_dot(hgibbs_t h, int c, double gamma_old, double* num_f)
 {
-    if (!h || !h->covX || !num_f) return fail("hgibbs_cov_dot: no covariates set");
+    if (!h || !h->covX) return fail("hgibbs_cov_dot: no covariates set");
+    if (!num_f) return fail("hgibbs_cov_dot: null output pointer");
     if (c < 0 || c >= h->C) return fail("hgibbs_cov_dot: covariate %d outside [0,%d)", c, h->C);
     HIP_TRY(hipSetDevice(h->device));
     const uint32_t nblk = h->n_pad / BLOCK_IND;
