@@ -959,9 +959,14 @@ int hgibbs_load_bed(hgibbs_t h, const uint8_t* bed_host, uint64_t stride_in, uin
         for (uint32_t m0 = 0; m0 < M; m0 += slab) {
             const uint32_t mc = std::min(slab, M - m0);
             HIP_TRY(hipMemcpyAsync(st.src, bed_host + (size_t)m0 * stride_in, (size_t)mc * stride_in, hipMemcpyHostToDevice, h->stream));
-            dim3 grid((uint32_t)((h->stride + 255) / 256), mc);
-            k_compact_bed<<<grid, 256, 0, h->stream>>>(st.src, stride_in, st.idx, h->bed + (size_t)m0 * h->stride, h->stride, n_local, mc);
-            HIP_TRY(hipGetLastError());
+            // grid.y is limited to 65535: gather the staged columns in slabs of markers (as hgibbs_synth_bed)
+            for (uint32_t k0 = 0; k0 < mc; k0 += 32768) {
+                const uint32_t kc = std::min<uint32_t>(32768, mc - k0);
+                dim3 grid((uint32_t)((h->stride + 255) / 256), kc);
+                k_compact_bed<<<grid, 256, 0, h->stream>>>(st.src + (size_t)k0 * stride_in, stride_in, st.idx, h->bed + ((size_t)m0 + k0) * h->stride,
+                                                           h->stride, n_local, kc);
+                HIP_TRY(hipGetLastError());
+            }
         }
         HIP_TRY(hipStreamSynchronize(h->stream)); // before ~Staging frees what the kernels read
     }

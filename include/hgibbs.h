@@ -72,11 +72,17 @@ int hgibbs_p2p_import(hgibbs_t h, const void* handles /* nranks * 64 bytes */);
 /* ---- data: replaces Data::load_data_from_bed_file + sparse index build
  * (src/data.cpp:671-739, :1224-1290) -------------------------------------- */
 /* bed_host: SNP-major packed columns WITHOUT the 3 magic bytes, M columns of
- * stride_in = ceil(n_total/4) bytes.  keep_host: n_total bytes, 0 drops the
+ * stride_in >= ceil(n_total/4) bytes.  keep_host: n_total bytes, 0 drops the
  * individual (NA phenotype, src/data.cpp:1112-1158), NULL keeps all.  Of the
  * kept individuals this rank takes the half-open range [row_begin,row_end)
  * (row_begin % 4 == 0 unless keep_host is given).  n_global = number of kept
- * individuals over all ranks (the N of every formula). */
+ * individuals over all ranks (the N of every formula).
+ * Pinned by tests/test_gpu_loader.py: the bits of a column beyond n_total and
+ * the bytes beyond ceil(n_total/4) are ignored whatever they hold (PLINK
+ * writes 00 there, a called genotype); a shard without a keep list may end
+ * anywhere, inside a byte whose other slots are the next rank's rows included;
+ * every unused slot of the image (local index >= n_local) is missing, which
+ * is what hgibbs_get_bed, the counts and the index lists then show. */
 int hgibbs_load_bed(hgibbs_t h, const uint8_t* bed_host, uint64_t stride_in, uint32_t n_total, uint32_t M,
                     const uint8_t* keep_host, uint32_t row_begin, uint32_t row_end, uint32_t n_global);
 /* Seeded synthetic genotypes generated directly in HBM (BASELINE.md section 4:
