@@ -553,24 +553,24 @@ __global__ __launch_bounds__(WAVE) void k_bw_ars_probe(BwArsProbe pr)
 // host side
 // ---------------------------------------------------------------------------
 struct BwState {
-    double* vi = nullptr;
-    double* vi2 = nullptr; // the other vi buffer: a batch that applies a pending update writes it (k_bw_sums' update group)
-    uint32_t* failspread = nullptr;
-    double* vi_sum = nullptr; // device scalar
-    double *d_mave = nullptr, *d_sd = nullptr, *d_sumfail = nullptr;
-    double *d_cva = nullptr, *d_pi = nullptr, *d_sigmaG = nullptr;
-    double *d_ghx = nullptr, *d_ghw = nullptr;
-    double* d_unif = nullptr;
-    double* partials = nullptr;
-    BwResult* h_result = nullptr; // pinned, written by the device
+    DevBuf<double> vi;
+    DevBuf<double> vi2; // the other vi buffer: a batch that applies a pending update writes it (k_bw_sums' update group)
+    DevBuf<uint32_t> failspread;
+    DevBuf<double> vi_sum; // device scalar
+    DevBuf<double> d_mave, d_sd, d_sumfail;
+    DevBuf<double> d_cva, d_pi, d_sigmaG;
+    DevBuf<double> d_ghx, d_ghw;
+    DevBuf<double> d_unif;
+    DevBuf<double> partials;
+    PinBuf<BwResult> h_result; // written by the device
     unsigned long long seq = 0;
-    double* vipart = nullptr; // block partials of sum(vi) from the last refresh
-    double* d_rows = nullptr; // BW_ROWS: this rank's row sums, all-reduced between the two batch kernels (several ranks only)
-    int32_t* d_colk = nullptr;
-    uint32_t* d_first_event = nullptr;
-    hipEvent_t evk0 = nullptr, evk1 = nullptr;
-    int32_t* d_picks = nullptr;
-    double* d_colsums = nullptr;
+    DevBuf<double> vipart; // block partials of sum(vi) from the last refresh
+    DevBuf<double> d_rows; // BW_ROWS: this rank's row sums, all-reduced between the two batch kernels (several ranks only)
+    DevBuf<int32_t> d_colk;
+    DevBuf<uint32_t> d_first_event;
+    Event evk0, evk1;
+    DevBuf<int32_t> d_picks;
+    DevBuf<double> d_colsums;
     std::vector<double> mave, sd, sumfail, cva, beta;
     std::vector<int32_t> comp, fail;
     std::vector<double> unif;
@@ -579,19 +579,6 @@ struct BwState {
     bool have_tables = false, have_model = false;
     hgibbs_w_sweep_stats stats{};
 };
-
-static void bw_free(BwState* b)
-{
-    if (!b) return;
-    void* ptrs[] = {b->vi, b->vi2, b->failspread, b->vi_sum, b->d_mave, b->d_sd, b->d_sumfail, b->d_cva, b->d_pi, b->d_sigmaG, b->d_ghx, b->d_ghw,
-                    b->d_unif, b->partials, b->d_picks, b->d_colsums, b->vipart, b->d_colk, b->d_first_event, b->d_rows};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    if (b->h_result) (void)hipHostFree(b->h_result);
-    if (b->evk0) (void)hipEventDestroy(b->evk0);
-    if (b->evk1) (void)hipEventDestroy(b->evk1);
-    delete b;
-}
 
 static int bw_need(hgibbs_ctx* h, const char* who, bool tables = false, bool model = false)
 {
@@ -619,44 +606,35 @@ int hgibbs_w_init(hgibbs_t h, const int32_t* failure_host)
     if (h->bw) return fail("hgibbs_w_init: already initialised on this handle");
     for (uint32_t i = 0; i < h->n_global; ++i)
         if (failure_host[i] != 0 && failure_host[i] != 1) return fail("hgibbs_w_init: failure indicator of individual %u is %d, not 0/1", i, failure_host[i]);
-    BwState* b = new BwState();
-    h->bw = b;
+    // built in a local and stored in the handle last: a failure on the way leaves the handle without a BayesW side, as before the call
+    std::unique_ptr<BwState> b(new BwState());
     b->fail.assign(failure_host, failure_host + h->n_global);
     b->d_total = 0.0;
     for (uint32_t i = 0; i < h->n_global; ++i) b->d_total += (double)failure_host[i];
     const uint32_t ndw = h->n_pad / 16;
-    HIP_TRY(hipMalloc(&b->vi, (size_t)h->n_pad * sizeof(double)));
+    const size_t M = h->M;
+    if (b->vi.alloc(h->n_pad)) return 1;
     HIP_TRY(hipMemsetAsync(b->vi, 0, (size_t)h->n_pad * sizeof(double), h->stream));
-    HIP_TRY(hipMalloc(&b->vi2, (size_t)h->n_pad * sizeof(double)));
+    if (b->vi2.alloc(h->n_pad)) return 1;
     HIP_TRY(hipMemsetAsync(b->vi2, 0, (size_t)h->n_pad * sizeof(double), h->stream));
-    HIP_TRY(hipMalloc(&b->failspread, (size_t)ndw * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&b->vi_sum, sizeof(double)));
-    HIP_TRY(hipMalloc(&b->d_mave, (size_t)h->M * sizeof(double)));
-    HIP_TRY(hipMalloc(&b->d_sd, (size_t)h->M * sizeof(double)));
-    HIP_TRY(hipMalloc(&b->d_sumfail, (size_t)h->M * sizeof(double)));
-    HIP_TRY(hipMalloc(&b->d_unif, (size_t)h->M * sizeof(double)));
-    HIP_TRY(hipMalloc(&b->partials, (size_t)S_CAP * BW_ROWS * sizeof(double)));
-    HIP_TRY(hipHostMalloc(&b->h_result, sizeof(BwResult)));
+    if (b->failspread.alloc(ndw) || b->vi_sum.alloc(1) || b->d_mave.alloc(M) || b->d_sd.alloc(M) || b->d_sumfail.alloc(M) || b->d_unif.alloc(M)) return 1;
+    if (b->partials.alloc((size_t)S_CAP * BW_ROWS) || b->h_result.alloc(1)) return 1;
     std::memset(b->h_result, 0, sizeof(BwResult));
-    HIP_TRY(hipMalloc(&b->vipart, (size_t)(h->n_pad / BLOCK_IND) * sizeof(double)));
-    HIP_TRY(hipMalloc(&b->d_colk, (MAX_BATCH + 1) * sizeof(int32_t)));
-    HIP_TRY(hipMalloc(&b->d_rows, (size_t)BW_ROWS * sizeof(double)));
+    if (b->vipart.alloc(h->n_pad / BLOCK_IND) || b->d_colk.alloc(MAX_BATCH + 1) || b->d_rows.alloc(BW_ROWS)) return 1;
     HIP_TRY(hipMemsetAsync(b->d_rows, 0, (size_t)BW_ROWS * sizeof(double), h->stream));
-    HIP_TRY(hipMalloc(&b->d_first_event, sizeof(uint32_t)));
+    if (b->d_first_event.alloc(1)) return 1;
     HIP_TRY(hipMemsetAsync(b->d_first_event, 0xff, sizeof(uint32_t), h->stream));
-    HIP_TRY(hipEventCreate(&b->evk0));
-    HIP_TRY(hipEventCreate(&b->evk1));
-    HIP_TRY(hipMalloc(&b->d_picks, (MAX_BATCH + 1) * sizeof(int32_t)));
-    HIP_TRY(hipMalloc(&b->d_colsums, (size_t)(MAX_BATCH + 1) * 3 * sizeof(double)));
-    int32_t* d_fail = nullptr;
-    HIP_TRY(hipMalloc(&d_fail, (size_t)h->n_local * sizeof(int32_t)));
+    if (b->evk0.create() || b->evk1.create()) return 1;
+    if (b->d_picks.alloc(MAX_BATCH + 1) || b->d_colsums.alloc((size_t)(MAX_BATCH + 1) * 3)) return 1;
+    DevBuf<int32_t> d_fail;
+    if (d_fail.alloc(h->n_local)) return 1;
     HIP_TRY(hipMemcpyAsync(d_fail, failure_host + h->row_begin, (size_t)h->n_local * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     k_bw_failspread<<<(ndw + 255) / 256, 256, 0, h->stream>>>(d_fail, h->n_local, ndw, b->failspread);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipFree(d_fail));
     b->beta.assign(h->M, 0.0);
     b->comp.assign(h->M, 0);
+    h->bw = std::move(b);
     return 0;
 }
 
@@ -668,20 +646,19 @@ int hgibbs_w_marker_stats(hgibbs_t h, double* mave, double* sd, double* sum_fail
 {
     if (bw_need(h, "hgibbs_w_marker_stats")) return 1;
     HIP_TRY(hipSetDevice(h->device));
-    BwState* b = h->bw;
+    BwState* b = h->bw.get();
     if (!b->have_tables) {
         if (compute_stats(h)) return 1;
         const uint32_t M = h->M;
         std::vector<unsigned long long> cnt((size_t)3 * M), fc((size_t)2 * M);
         HIP_TRY(hipMemcpy(cnt.data(), h->counts, cnt.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        unsigned long long* d_fc = nullptr;
-        HIP_TRY(hipMalloc(&d_fc, fc.size() * sizeof(unsigned long long)));
+        DevBuf<unsigned long long> d_fc;
+        if (d_fc.alloc(fc.size())) return 1;
         k_bw_fail_counts<<<M, BLOCK, 0, h->stream>>>(h->bed, h->stride, b->failspread, h->n_pad / 16, d_fc);
         HIP_TRY(hipGetLastError());
         if (bulk_allreduce(h, d_fc, fc.size(), 1)) return 1; // individuals are sharded: counts add over the ranks
         HIP_TRY(hipMemcpyAsync(fc.data(), d_fc, fc.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
-        HIP_TRY(hipFree(d_fc));
         b->mave.resize(M);
         b->sd.resize(M);
         b->sumfail.resize(M);
@@ -717,36 +694,36 @@ int hgibbs_w_set_model(hgibbs_t h, int G, int K, const int32_t* groups_host, con
     const double *X = nullptr, *W = nullptr;
     if (!hg_gh_lookup(quad_points, &X, &W)) return fail("Possible number of quad_points = 3,5,7,9,11,13,15,17,25 (got %d)", quad_points);
     HIP_TRY(hipSetDevice(h->device));
-    BwState* b = h->bw;
-    h->groups_host.assign(h->M, 0);
+    BwState* b = h->bw.get();
+    // checked and built in locals; the handle changes once nothing can fail any more
+    std::vector<int32_t> groups(h->M, 0);
     if (groups_host)
         for (uint32_t i = 0; i < h->M; ++i) {
             if (groups_host[i] < 0 || groups_host[i] >= G) return fail("hgibbs_w_set_model: marker %u in group %d outside [0,%d)", i, groups_host[i], G);
-            h->groups_host[i] = groups_host[i];
+            groups[i] = groups_host[i];
         }
-    HIP_TRY(hipMemcpy(h->groups, h->groups_host.data(), (size_t)h->M * sizeof(int32_t), hipMemcpyHostToDevice));
-    b->G = G;
-    b->K = K;
-    b->quad = quad_points;
-    b->cva.resize((size_t)G * (K - 1));
+    std::vector<double> cva((size_t)G * (K - 1));
     for (int g = 0; g < G; ++g)
         for (int k = 1; k < K; ++k) {
             if (!(mS[(size_t)g * K + k] > 0.0)) return fail("hgibbs_w_set_model: mixture value can only be strictly positive");
-            b->cva[(size_t)g * (K - 1) + (k - 1)] = mS[(size_t)g * K + k];
+            cva[(size_t)g * (K - 1) + (k - 1)] = mS[(size_t)g * K + k];
         }
-    for (double** p : {&b->d_cva, &b->d_pi, &b->d_sigmaG, &b->d_ghx, &b->d_ghw})
-        if (*p) {
-            HIP_TRY(hipFree(*p));
-            *p = nullptr;
-        }
-    HIP_TRY(hipMalloc(&b->d_cva, b->cva.size() * sizeof(double)));
-    HIP_TRY(hipMalloc(&b->d_pi, (size_t)G * K * sizeof(double)));
-    HIP_TRY(hipMalloc(&b->d_sigmaG, (size_t)G * sizeof(double)));
-    HIP_TRY(hipMalloc(&b->d_ghx, (size_t)(quad_points - 1) * sizeof(double)));
-    HIP_TRY(hipMalloc(&b->d_ghw, (size_t)quad_points * sizeof(double)));
-    HIP_TRY(hipMemcpy(b->d_cva, b->cva.data(), b->cva.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b->d_ghx, X, (size_t)(quad_points - 1) * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b->d_ghw, W, (size_t)quad_points * sizeof(double), hipMemcpyHostToDevice));
+    DevBuf<double> d_cva, d_pi, d_sigmaG, d_ghx, d_ghw;
+    if (d_cva.alloc(cva.size()) || d_pi.alloc((size_t)G * K) || d_sigmaG.alloc(G) || d_ghx.alloc(quad_points - 1) || d_ghw.alloc(quad_points)) return 1;
+    HIP_TRY(hipMemcpy(d_cva, cva.data(), cva.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_ghx, X, (size_t)(quad_points - 1) * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_ghw, W, (size_t)quad_points * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->groups, groups.data(), (size_t)h->M * sizeof(int32_t), hipMemcpyHostToDevice));
+    h->groups_host = std::move(groups);
+    b->G = G;
+    b->K = K;
+    b->quad = quad_points;
+    b->cva = std::move(cva);
+    b->d_cva = std::move(d_cva);
+    b->d_pi = std::move(d_pi);
+    b->d_sigmaG = std::move(d_sigmaG);
+    b->d_ghx = std::move(d_ghx);
+    b->d_ghw = std::move(d_ghw);
     b->have_model = true;
     return 0;
 }
@@ -783,13 +760,12 @@ int hgibbs_w_get_vi(hgibbs_t h, double* vi_host, double* vi_sum)
     if (bw_need(h, "hgibbs_w_get_vi")) return 1;
     HIP_TRY(hipSetDevice(h->device));
     if (vi_host) {
-        double* tmp = nullptr;
-        HIP_TRY(hipMalloc(&tmp, (size_t)h->n_local * sizeof(double)));
+        DevBuf<double> tmp;
+        if (tmp.alloc(h->n_local)) return 1;
         k_get_eps<<<(h->n_local + 255) / 256, 256, 0, h->stream>>>(h->bw->vi, tmp, h->n_local);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(vi_host, tmp, (size_t)h->n_local * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
-        HIP_TRY(hipFree(tmp));
     }
     if (vi_sum) {
         k_final_sum<<<1, BLOCK, 0, h->stream>>>(h->bw->vipart, h->n_pad / BLOCK_IND, 1, h->bw->vi_sum);
@@ -856,7 +832,7 @@ int hgibbs_w_sweep(hgibbs_t h, const int32_t* order_host, double alpha, const do
     if (bw_need(h, "hgibbs_w_sweep", true, true)) return 1;
     if (!order_host || !sigmaG || !pi || !rng || !ars_rng || !cass_host || !beta_sqnorm) return fail("hgibbs_w_sweep: null argument");
     HIP_TRY(hipSetDevice(h->device));
-    BwState* b = h->bw;
+    BwState* b = h->bw.get();
     const uint32_t M = h->M;
     const int G = b->G, K = b->K;
     for (uint32_t i = 0; i < M; ++i)
@@ -1098,7 +1074,7 @@ int hgibbs_w_marker_sums(hgibbs_t h, uint32_t marker, double beta_old, double al
     if (bw_need(h, "hgibbs_w_marker_sums", true)) return 1;
     if (marker >= h->M) return fail("hgibbs_w_marker_sums: marker %u >= M %u", marker, h->M);
     HIP_TRY(hipSetDevice(h->device));
-    BwState* b = h->bw;
+    BwState* b = h->bw.get();
     const uint32_t ntg = h->n_pad / BLOCK_IND;
     const uint32_t nblk = ntg;
     // shifted form reads eps; plain form reads vi

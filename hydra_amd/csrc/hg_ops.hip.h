@@ -4,39 +4,6 @@
 
 namespace {
 
-// Device memory that frees itself: move-only; alloc(n) makes room for n elements (what it held before is freed first).  Converts to
-// the pointer, so it goes where a T* went: kernel arguments, hipMemcpy, pointer arithmetic.
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
-    DevBuf& operator=(DevBuf&& o) noexcept
-    {
-        if (this != &o) {
-            release();
-            p = o.p;
-            o.p = nullptr;
-        }
-        return *this;
-    }
-    ~DevBuf() { release(); }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-    int alloc(size_t n)
-    {
-        release();
-        HIP_TRY(hipMalloc(&p, n * sizeof(T)));
-        return 0;
-    }
-    operator T*() const { return p; }
-};
-
 // The checks every operator makes first.  one_rank: why the operator takes a handle of one rank only (null: any number of ranks)
 int op_guard(const hgibbs_ctx* h, const char* who, const char* one_rank)
 {

@@ -258,14 +258,15 @@ bool pca_jacobi(const double* S, int L, double* theta, double* W)
 // synchronisation points (at most a handful of segments lie between two of them), so the timing adds no synchronisation
 struct PcaClock {
     static constexpr int NSEG = 8;
-    hipEvent_t ev[2 * NSEG] = {};
+    Event ev[2 * NSEG];
     int part[NSEG] = {};
     int used = 0; // events recorded since the last sync
     hipStream_t stream = nullptr;
     double ms[5] = {0, 0, 0, 0, 0};
     int create()
     {
-        for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
+        for (auto& e : ev)
+            if (e.create()) return 1;
         return 0;
     }
     int begin(int p)
@@ -291,11 +292,6 @@ struct PcaClock {
         }
         used = 0;
         return 0;
-    }
-    ~PcaClock()
-    {
-        for (auto e : ev)
-            if (e) (void)hipEventDestroy(e);
     }
 };
 

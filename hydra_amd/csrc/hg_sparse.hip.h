@@ -141,54 +141,27 @@ __global__ __launch_bounds__(BLOCK) void k_sp_compact(const uint8_t* __restrict_
 
 // a load between hgibbs_sparse_begin and hgibbs_sparse_end
 struct SparseLoad {
-    uint8_t* bed = nullptr;          // the image, not yet on the handle
+    DevBuf<uint8_t> bed;             // the image, not yet on the handle
     uint32_t n_total = 0;
-    uint32_t* rank = nullptr;        // device, n_total: row of the file -> local row, or SP_SKIP
-    unsigned long long* err = nullptr; // device: the smallest offence (sp_key), SP_NO_ERR when none
-    uint32_t* stage[3] = {nullptr, nullptr, nullptr}; // device: the piece of each list a part scatters from
+    DevBuf<uint32_t> rank;           // n_total: row of the file -> local row, or SP_SKIP
+    DevBuf<unsigned long long> err;  // the smallest offence (sp_key), SP_NO_ERR when none
+    DevBuf<uint32_t> stage[3];       // the piece of each list a part scatters from
     uint64_t stage_n[3] = {0, 0, 0};
-    unsigned long long* off = nullptr; // device: 3 x SP_SLAB
-    uint32_t* len = nullptr;           // device: 3 x SP_SLAB
+    DevBuf<unsigned long long> off;  // 3 x SP_SLAB
+    DevBuf<uint32_t> len;            // 3 x SP_SLAB
     std::vector<uint8_t> done;       // per marker: put
     double ms = 0.0;
 };
 
-static void sp_free(SparseLoad* s)
+// The load is given up: the handle is as it was before hgibbs_sparse_begin (what alloc_problem allocated is released).  Returns 1 and
+// leaves the message as it stands, so a failed step ends with `return sp_abandon(h)`.
+static int sp_abandon(hgibbs_ctx* h)
 {
-    if (!s) return;
-    void* ptrs[] = {s->bed, s->rank, s->err, s->stage[0], s->stage[1], s->stage[2], s->off, s->len};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    delete s;
-}
-
-// The load is given up: the handle is as it was before hgibbs_sparse_begin (what alloc_problem allocated is released).
-static void sp_abandon(hgibbs_ctx* h)
-{
-    (void)hipStreamSynchronize(h->stream);
-    sp_free(h->sp);
-    h->sp = nullptr;
-    void** ptrs[] = {(void**)&h->bed, (void**)&h->eps[0], (void**)&h->eps[1], (void**)&h->mave, (void**)&h->mstd, (void**)&h->counts, (void**)&h->beta,
-                     (void**)&h->comp, (void**)&h->acum, (void**)&h->order, (void**)&h->adaV, (void**)&h->order_bad, (void**)&h->s_mave, (void**)&h->s_mstd,
-                     (void**)&h->s_bold, (void**)&h->s_ga, (void**)&h->pred, (void**)&h->pred_cnt, (void**)&h->groups, (void**)&h->partials};
-    for (void** p : ptrs) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-    }
-    h->n_global = h->n_local = h->n_pad = h->M = h->row_begin = 0;
-    h->stride = 0;
-    h->have_stats = false;
+    drop_problem(h); // (synchronises the stream first)
+    h->sp.reset();
     h->sparse_ms[0] = 0.0;
+    return 1;
 }
-
-#define SP_TRY(expr)                                                                                              \
-    do {                                                                                                          \
-        hipError_t e_ = (expr);                                                                                   \
-        if (e_ != hipSuccess) {                                                                                   \
-            sp_abandon(h);                                                                                        \
-            return fail("%s:%d %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(e_));                      \
-        }                                                                                                         \
-    } while (0)
 
 // ev0 .. ev1 around what the caller has just launched; waits for it
 static int sp_elapsed(hgibbs_ctx* h, double* ms)
@@ -227,75 +200,46 @@ extern "C" int hgibbs_sparse_begin(hgibbs_t h, uint32_t n_total, uint32_t M, con
         if (row_end > r) return fail("hgibbs_sparse_begin: row_end %u > kept individuals %u", row_end, r);
     }
     if (n_global < 2) return fail("hgibbs_sparse_begin: n_global must be at least 2");
-    if (alloc_problem(h, n_global, row_end - row_begin, M, row_begin)) {
-        const std::string why = g_err;
-        sp_abandon(h);
-        g_err = why;
-        return 1;
-    }
-    SparseLoad* s = new SparseLoad();
-    h->sp = s;
-    s->bed = h->bed; // not published before hgibbs_sparse_end: every other operator sees a handle without genotypes
-    h->bed = nullptr;
+    if (alloc_problem(h, n_global, row_end - row_begin, M, row_begin)) return 1;
+    h->sp.reset(new SparseLoad());
+    SparseLoad* s = h->sp.get();
+    s->bed = std::move(h->bed); // not published before hgibbs_sparse_end: every other operator sees a handle without genotypes
     s->n_total = n_total;
     s->done.assign(M, 0);
-    SP_TRY(hipMalloc(&s->rank, (size_t)n_total * sizeof(uint32_t)));
-    SP_TRY(hipMalloc(&s->err, sizeof(unsigned long long)));
-    SP_TRY(hipMalloc(&s->off, (size_t)3 * SP_SLAB * sizeof(unsigned long long)));
-    SP_TRY(hipMalloc(&s->len, (size_t)3 * SP_SLAB * sizeof(uint32_t)));
-    SP_TRY(hipMemcpyAsync(s->rank, rk.data(), (size_t)n_total * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    SP_TRY(hipMemsetAsync(s->err, 0xff, sizeof(unsigned long long), h->stream));
-    SP_TRY(hipEventRecord(h->ev0, h->stream));
-    k_sp_fill<<<4096, 256, 0, h->stream>>>(reinterpret_cast<uint32_t*>(s->bed), (uint64_t)M * h->stride / 4, (uint32_t)(h->stride / 4), h->n_local);
-    SP_TRY(hipGetLastError());
-    if (sp_elapsed(h, &s->ms)) {
-        const std::string why = g_err;
-        sp_abandon(h);
-        g_err = why;
-        return 1;
-    }
-    return 0;
+    const auto fill = [&]() -> int {
+        if (s->rank.alloc(n_total) || s->err.alloc(1) || s->off.alloc((size_t)3 * SP_SLAB) || s->len.alloc((size_t)3 * SP_SLAB)) return 1;
+        HIP_TRY(hipMemcpyAsync(s->rank, rk.data(), (size_t)n_total * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemsetAsync(s->err, 0xff, sizeof(unsigned long long), h->stream));
+        HIP_TRY(hipEventRecord(h->ev0, h->stream));
+        k_sp_fill<<<4096, 256, 0, h->stream>>>(reinterpret_cast<uint32_t*>(s->bed.p), (uint64_t)M * h->stride / 4, (uint32_t)(h->stride / 4), h->n_local);
+        HIP_TRY(hipGetLastError());
+        return sp_elapsed(h, &s->ms);
+    };
+    return fill() ? sp_abandon(h) : 0;
 }
 
-// sp_abandon, then the message
-static int sp_refuse(hgibbs_ctx* h, const char* fmt, ...)
+// The checks and the device work of hgibbs_sparse_put; whichever fails, the caller gives the load up
+static int sp_put(hgibbs_ctx* h, uint32_t m0, uint32_t count, const hgibbs_sparse_list* const li[3])
 {
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    sp_abandon(h);
-    g_err = buf;
-    return 1;
-}
-
-extern "C" int hgibbs_sparse_put(hgibbs_t h, uint32_t m0, uint32_t count, const hgibbs_sparse_list* ones, const hgibbs_sparse_list* twos,
-                                 const hgibbs_sparse_list* miss)
-{
-    if (!h) return fail("hgibbs_sparse_put: null handle");
-    if (!h->sp) return fail("hgibbs_sparse_put: no sparse load in progress (hgibbs_sparse_begin)");
-    SparseLoad* s = h->sp;
-    HIP_TRY(hipSetDevice(h->device));
-    const hgibbs_sparse_list* li[3] = {ones, twos, miss};
+    SparseLoad* s = h->sp.get();
     static const char* const nm[3] = {"ones", "twos", "miss"};
     // the host's refusals, before any device work
     for (int l = 0; l < 3; ++l)
-        if (!li[l] || (count && (!li[l]->start || !li[l]->len)) || (li[l]->idx_count && !li[l]->idx)) return sp_refuse(h, "hgibbs_sparse_put: null list (%s)", nm[l]);
-    if ((uint64_t)m0 + count > h->M) return sp_refuse(h, "hgibbs_sparse_put: markers [%u, %llu) beyond M = %u", m0, (unsigned long long)m0 + count, h->M);
+        if (!li[l] || (count && (!li[l]->start || !li[l]->len)) || (li[l]->idx_count && !li[l]->idx)) return fail("hgibbs_sparse_put: null list (%s)", nm[l]);
+    if ((uint64_t)m0 + count > h->M) return fail("hgibbs_sparse_put: markers [%u, %llu) beyond M = %u", m0, (unsigned long long)m0 + count, h->M);
     for (uint32_t k = 0; k < count; ++k)
-        if (s->done[m0 + k]) return sp_refuse(h, "hgibbs_sparse_put: marker %u was put already", m0 + k);
+        if (s->done[m0 + k]) return fail("hgibbs_sparse_put: marker %u was put already", m0 + k);
     for (int l = 0; l < 3; ++l)
         for (uint32_t k = 0; k < count; ++k) {
             const uint64_t st = li[l]->start[k], ln = li[l]->len[k];
-            if (ln > s->n_total) return sp_refuse(h, "hgibbs_sparse_put: marker %u, list %s: len %llu > n_total %u", m0 + k, nm[l], (unsigned long long)ln, s->n_total);
+            if (ln > s->n_total) return fail("hgibbs_sparse_put: marker %u, list %s: len %llu > n_total %u", m0 + k, nm[l], (unsigned long long)ln, s->n_total);
             if (st < li[l]->idx_base)
-                return sp_refuse(h, "hgibbs_sparse_put: marker %u, list %s: start %llu < idx_base %llu", m0 + k, nm[l], (unsigned long long)st,
-                                 (unsigned long long)li[l]->idx_base);
+                return fail("hgibbs_sparse_put: marker %u, list %s: start %llu < idx_base %llu", m0 + k, nm[l], (unsigned long long)st,
+                            (unsigned long long)li[l]->idx_base);
             if (st - li[l]->idx_base > li[l]->idx_count || ln > li[l]->idx_count - (st - li[l]->idx_base))
-                return sp_refuse(h, "hgibbs_sparse_put: marker %u, list %s: start %llu + len %llu is beyond the piece [%llu, %llu)", m0 + k, nm[l],
-                                 (unsigned long long)st, (unsigned long long)ln, (unsigned long long)li[l]->idx_base,
-                                 (unsigned long long)(li[l]->idx_base + li[l]->idx_count));
+                return fail("hgibbs_sparse_put: marker %u, list %s: start %llu + len %llu is beyond the piece [%llu, %llu)", m0 + k, nm[l],
+                            (unsigned long long)st, (unsigned long long)ln, (unsigned long long)li[l]->idx_base,
+                            (unsigned long long)(li[l]->idx_base + li[l]->idx_count));
         }
     // parts of at most SP_SLAB markers whose entries, list by list, span at most SP_STAGE_ENTRIES (a marker alone may exceed it)
     std::vector<unsigned long long> off((size_t)3 * SP_SLAB);
@@ -324,65 +268,70 @@ extern "C" int hgibbs_sparse_put(hgibbs_t h, uint32_t m0, uint32_t count, const 
         for (int l = 0; l < 3; ++l) {
             const uint64_t n = hi[l] - lo[l];
             if (n > s->stage_n[l]) {
-                SP_TRY(hipStreamSynchronize(h->stream));
-                if (s->stage[l]) SP_TRY(hipFree(s->stage[l]));
-                s->stage[l] = nullptr;
+                HIP_TRY(hipStreamSynchronize(h->stream));
                 s->stage_n[l] = 0;
-                SP_TRY(hipMalloc(&s->stage[l], (size_t)n * sizeof(uint32_t)));
+                if (s->stage[l].alloc(n)) return 1;
                 s->stage_n[l] = n;
             }
-            if (n) SP_TRY(hipMemcpyAsync(s->stage[l], li[l]->idx + (lo[l] - li[l]->idx_base), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+            if (n) HIP_TRY(hipMemcpyAsync(s->stage[l], li[l]->idx + (lo[l] - li[l]->idx_base), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
             for (uint32_t k = 0; k < pc; ++k) {
                 off[(size_t)l * SP_SLAB + k] = li[l]->start[k0 + k] - lo[l];
                 len[(size_t)l * SP_SLAB + k] = (uint32_t)li[l]->len[k0 + k];
             }
-            SP_TRY(hipMemcpyAsync(s->off + (size_t)l * SP_SLAB, off.data() + (size_t)l * SP_SLAB, (size_t)pc * sizeof(unsigned long long), hipMemcpyHostToDevice, h->stream));
-            SP_TRY(hipMemcpyAsync(s->len + (size_t)l * SP_SLAB, len.data() + (size_t)l * SP_SLAB, (size_t)pc * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(hipMemcpyAsync(s->off + (size_t)l * SP_SLAB, off.data() + (size_t)l * SP_SLAB, (size_t)pc * sizeof(unsigned long long), hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(hipMemcpyAsync(s->len + (size_t)l * SP_SLAB, len.data() + (size_t)l * SP_SLAB, (size_t)pc * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
             L.idx[l] = s->stage[l];
             L.off[l] = s->off + (size_t)l * SP_SLAB;
             L.len[l] = s->len + (size_t)l * SP_SLAB;
         }
         if (maxlen) {
             const uint32_t gx = (uint32_t)std::min<uint64_t>(64, (maxlen + 1023) / 1024);
-            SP_TRY(hipEventRecord(h->ev0, h->stream));
+            HIP_TRY(hipEventRecord(h->ev0, h->stream));
             k_sp_scatter<<<dim3(gx, pc, 3), 256, 0, h->stream>>>(L, s->rank, s->n_total, s->bed, h->stride, m0 + k0, s->err);
-            SP_TRY(hipGetLastError());
-            if (sp_elapsed(h, &s->ms)) {
-                const std::string why = g_err;
-                sp_abandon(h);
-                g_err = why;
-                return 1;
-            }
+            HIP_TRY(hipGetLastError());
+            if (sp_elapsed(h, &s->ms)) return 1;
         } else {
-            SP_TRY(hipStreamSynchronize(h->stream)); // (the host vectors are written again by the next part)
+            HIP_TRY(hipStreamSynchronize(h->stream)); // (the host vectors are written again by the next part)
         }
         k0 = k1;
     }
     unsigned long long e = SP_NO_ERR;
-    SP_TRY(hipMemcpy(&e, s->err, sizeof e, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&e, s->err, sizeof e, hipMemcpyDeviceToHost));
     if (e != SP_NO_ERR) {
         const uint32_t marker = (uint32_t)(e >> 33), row = (uint32_t)(e >> 1);
-        if ((e & 1u) == SP_RANGE) return sp_refuse(h, "hgibbs_sparse_put: marker %u lists row %u, which is not below n_total = %u", marker, row, s->n_total);
-        return sp_refuse(h, "hgibbs_sparse_put: marker %u lists row %u twice (in one list or in two)", marker, row);
+        if ((e & 1u) == SP_RANGE) return fail("hgibbs_sparse_put: marker %u lists row %u, which is not below n_total = %u", marker, row, s->n_total);
+        return fail("hgibbs_sparse_put: marker %u lists row %u twice (in one list or in two)", marker, row);
     }
     for (uint32_t k = 0; k < count; ++k) s->done[m0 + k] = 1;
     return 0;
+}
+
+extern "C" int hgibbs_sparse_put(hgibbs_t h, uint32_t m0, uint32_t count, const hgibbs_sparse_list* ones, const hgibbs_sparse_list* twos,
+                                 const hgibbs_sparse_list* miss)
+{
+    if (!h) return fail("hgibbs_sparse_put: null handle");
+    if (!h->sp) return fail("hgibbs_sparse_put: no sparse load in progress (hgibbs_sparse_begin)");
+    HIP_TRY(hipSetDevice(h->device));
+    const hgibbs_sparse_list* const li[3] = {ones, twos, miss};
+    return sp_put(h, m0, count, li) ? sp_abandon(h) : 0;
 }
 
 extern "C" int hgibbs_sparse_end(hgibbs_t h)
 {
     if (!h) return fail("hgibbs_sparse_end: null handle");
     if (!h->sp) return fail("hgibbs_sparse_end: no sparse load in progress (hgibbs_sparse_begin)");
-    SparseLoad* s = h->sp;
+    SparseLoad* s = h->sp.get();
     HIP_TRY(hipSetDevice(h->device));
-    for (uint32_t j = 0; j < h->M; ++j)
-        if (!s->done[j]) return sp_refuse(h, "hgibbs_sparse_end: marker %u was never put", j);
-    SP_TRY(hipStreamSynchronize(h->stream));
-    h->bed = s->bed; // published
-    s->bed = nullptr;
+    const auto complete = [&]() -> int {
+        for (uint32_t j = 0; j < h->M; ++j)
+            if (!s->done[j]) return fail("hgibbs_sparse_end: marker %u was never put", j);
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        return 0;
+    };
+    if (complete()) return sp_abandon(h);
+    h->bed = std::move(s->bed); // published
     h->sparse_ms[0] = s->ms;
-    sp_free(s);
-    h->sp = nullptr;
+    h->sp.reset();
     h->have_stats = false;
     return 0;
 }
@@ -423,16 +372,10 @@ extern "C" int hgibbs_sparse_get(hgibbs_t h, uint32_t m0, uint32_t count, uint32
         HIP_TRY(hipMemGetInfo(&fr, &tot));
         cap = std::min<uint64_t>(1ull << 30, fr / 4);
     }
-    struct Bufs { // released on every exit
-        unsigned long long* bases = nullptr;
-        uint32_t* out[3] = {nullptr, nullptr, nullptr};
+    struct {
+        DevBuf<unsigned long long> bases;
+        DevBuf<uint32_t> out[3];
         uint64_t out_n[3] = {0, 0, 0};
-        ~Bufs()
-        {
-            if (bases) (void)hipFree(bases);
-            for (uint32_t* p : out)
-                if (p) (void)hipFree(p);
-        }
     } b;
     std::vector<unsigned long long> bases;
     uint64_t done[3] = {0, 0, 0}; // entries handed to the caller so far
@@ -455,10 +398,8 @@ extern "C" int hgibbs_sparse_get(hgibbs_t h, uint32_t m0, uint32_t count, uint32
         }
         const uint32_t pc = k1 - k0;
         if (bases.size() > bases_n) {
-            if (b.bases) HIP_TRY(hipFree(b.bases));
-            b.bases = nullptr;
             bases_n = std::max<size_t>(bases.size(), std::min<size_t>((size_t)3 * (count - k0), (size_t)3 * 65536));
-            HIP_TRY(hipMalloc(&b.bases, bases_n * sizeof(unsigned long long)));
+            if (b.bases.alloc(bases_n)) return 1;
         }
         HIP_TRY(hipMemcpyAsync(b.bases, bases.data(), bases.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, h->stream));
         bool any = false;
@@ -466,10 +407,8 @@ extern "C" int hgibbs_sparse_get(hgibbs_t h, uint32_t m0, uint32_t count, uint32
             if (!out_host[l] || !tot[l]) continue;
             any = true;
             if (tot[l] > b.out_n[l]) {
-                if (b.out[l]) HIP_TRY(hipFree(b.out[l]));
-                b.out[l] = nullptr;
                 b.out_n[l] = 0;
-                HIP_TRY(hipMalloc(&b.out[l], (size_t)tot[l] * sizeof(uint32_t)));
+                if (b.out[l].alloc(tot[l])) return 1;
                 b.out_n[l] = tot[l];
             }
         }

@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -52,20 +53,48 @@ static int fail(const char* fmt, ...)
 
 extern "C" void hgibbs_set_error_(const char* msg) { g_err = msg; }
 
+#include "hg_own.hip.h"
+
 // ---------------------------------------------------------------------------
 // context
 // ---------------------------------------------------------------------------
 struct BwState; // BayesW side of the handle (hg_bayesw.hip.h)
-static void bw_free(BwState* b);
 struct SparseLoad; // a load from index lists between hgibbs_sparse_begin and hgibbs_sparse_end (hg_sparse.hip.h)
-static void sp_free(SparseLoad* s);
 
-struct hgibbs_ctx {
+// What belongs to one loaded problem: alloc_problem builds it whole and only then moves it into the handle; an abandoned sparse load
+// assigns an empty one
+struct Problem {
+    uint32_t n_global = 0, n_local = 0, n_pad = 0, M = 0, row_begin = 0;
+    uint64_t stride = 0;
+    DevBuf<uint8_t> bed;
+    DevBuf<double> eps[2];
+    uint32_t eps_cur = 0;
+    DevBuf<double> mave, mstd;
+    DevBuf<unsigned long long> counts; // 3*M: n1, n2, nmiss (global after all-reduce)
+    bool have_stats = false;
+    bool any_missing = false; // some column has missing calls
+    DevBuf<int32_t> groups;
+    DevBuf<double> beta;
+    DevBuf<int32_t> comp;
+    DevBuf<double> acum;
+    // sweep scratch of the problem's size
+    DevBuf<int32_t> order;
+    DevBuf<uint8_t> adaV;
+    DevBuf<double> s_mave, s_mstd, s_bold;
+    DevBuf<int32_t> s_ga;
+    DevBuf<uint32_t> pred;     // resident engine: the sweep positions whose marker has a non-zero effect at sweep start, ascending, then 16 sentinels
+    DevBuf<uint32_t> pred_cnt; // per 4096 positions: how many of them (k_pred_*)
+    DevBuf<uint32_t> order_bad; // the first sweep position whose order entry is outside [0, M) (k_gather_meta), else 0xffffffff
+    DevBuf<double> partials;
+};
+
+struct hgibbs_ctx : Problem {
+    ~hgibbs_ctx(); // defined below the includes at the end of this file, where BwState and SparseLoad are complete
     int device = 0;
     int num_cu = 256;
-    BwState* bw = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    std::unique_ptr<BwState> bw;
+    Stream stream;
+    Event ev0, ev1;
 
     // sharding
     int nranks = 1, rank = 0;
@@ -73,75 +102,53 @@ struct hgibbs_ctx {
     hgibbs_allreduce_fn ext_fn = nullptr; // bulk reductions through the caller's transport
     void* ext_user = nullptr;
     // in-launch exchange: own mailbox + IPC-mapped peers
-    unsigned char* mbox = nullptr;
+    DevBuf<unsigned char> mbox;
     void* peer_base[MAX_RANKS] = {};
     bool p2p_ready = false, p2p_enabled = true;
     uint64_t batch_seq = 0;
 
-    // data
-    uint32_t n_global = 0, n_local = 0, n_pad = 0, M = 0, row_begin = 0;
-    uint64_t stride = 0;
-    uint8_t* bed = nullptr;
-    double* eps[2] = {nullptr, nullptr};
-    uint32_t eps_cur = 0;
-    double *mave = nullptr, *mstd = nullptr;
-    unsigned long long* counts = nullptr; // 3*M: n1, n2, nmiss (global after all-reduce)
-    bool have_stats = false;
-    bool any_missing = false; // some column has missing calls
     int gram_missing = -1; // carry columns with missing calls through the extension: -1 auto, 0 never, 1 whenever possible
 
     // covariates: C columns of n_pad doubles in the permuted eps layout
-    double* covX = nullptr;
+    DevBuf<double> covX;
     int C = 0;
 
     // model / effects
     int G = 0, K = 0;
-    int32_t* groups = nullptr;
     std::vector<int32_t> groups_host;
     std::vector<double> cVa, cVaI;
-    double* beta = nullptr;
-    int32_t* comp = nullptr;
-    double* acum = nullptr;
 
     // sweep scratch
-    int32_t* order = nullptr;
-    uint8_t* adaV = nullptr;
-    double *s_mave = nullptr, *s_mstd = nullptr, *s_bold = nullptr;
-    int32_t* s_ga = nullptr;
-    uint32_t* pred = nullptr;     // resident engine: the sweep positions whose marker has a non-zero effect at sweep start, ascending, then 16 sentinels
-    uint32_t* pred_cnt = nullptr; // per 4096 positions: how many of them (k_pred_*)
-    unsigned long long* dbg = nullptr; // 8 words, device
+    DevBuf<unsigned long long> dbg; // 8 words, device
     bool debug_timing = false;
     bool w_kernel_timing = false; // BayesW: HIP events around every k_bw_sums launch (bench.py's roofline leg)
-    int32_t* cass = nullptr;
-    double* tables = nullptr; // 4 * G*K
-    uint32_t* mt = nullptr;
-    double* zig = nullptr; // 129+129+257+257
-    SweepDesc* desc = nullptr;
-    SweepDesc* desc_host = nullptr; // pinned
-    double* partials = nullptr;
-    double* totals = nullptr;
-    double* carry = nullptr; // MAX_BATCH dots handed from one launch to the next
-    double* ahead_raw = nullptr; // the ahead phase's buffers (hg_kernels.h: SweepParams)
-    double* apartials = nullptr;
-    uint32_t* aticket = nullptr; // AHEAD_MAX / 2 group tickets, then the two queue counters
+    DevBuf<int32_t> cass;
+    DevBuf<double> tables; // 4 * G*K
+    DevBuf<uint32_t> mt;
+    DevBuf<double> zig; // 129+129+257+257
+    DevBuf<SweepDesc> desc;
+    PinBuf<SweepDesc> desc_host;
+    DevBuf<double> totals;
+    DevBuf<double> carry; // MAX_BATCH dots handed from one launch to the next
+    DevBuf<double> ahead_raw; // the ahead phase's buffers (hg_kernels.h: SweepParams)
+    DevBuf<double> apartials;
+    DevBuf<uint32_t> aticket; // AHEAD_MAX / 2 group tickets, then the two queue counters
     int ahead = -1;          // option ahead: columns streamed ahead per launch (-1 = auto)
     int carry_on = -1;       // option carry: -1 auto (on for shards of 400 000 individuals and more), 0 off, 1 on
-    uint32_t* ticket = nullptr; // word 0: the launch-wide ticket; words 16.. : one per column group
-    double* sums = nullptr;    // 3*MAX_BATCH+1 (multi-GPU exchange buffer)
-    double* scratch = nullptr; // reductions
+    DevBuf<uint32_t> ticket; // word 0: the launch-wide ticket; words 16.. : one per column group
+    DevBuf<double> sums;    // 3*MAX_BATCH+1 (multi-GPU exchange buffer)
+    DevBuf<double> scratch; // reductions
     size_t scratch_n = 0;
-    double* scratch_host = nullptr; // pinned, 4096 doubles
-    double* beta_host = nullptr;    // pinned, M doubles (lazy)
-    uint32_t* bsq_idx_host = nullptr; // pinned, M + 1 words (lazy): hgibbs_beta_sqnorm's list of markers, its length in the last word
+    PinBuf<double> scratch_host; // 4096 doubles
+    PinBuf<double> beta_host;    // M doubles (lazy)
+    PinBuf<uint32_t> bsq_idx_host; // M + 1 words (lazy): hgibbs_beta_sqnorm's list of markers, its length in the last word
     uint32_t bsq_guess = 1024;        // entries of the list fetched with its length (the last call's length and a margin)
     // pinned staging of a sweep's inputs and small results (lazy): what the host writes or reads travels without a bounce buffer
-    int32_t* order_host = nullptr;    // M
-    uint8_t* adaV_host = nullptr;     // M: the caller's adaV as the device holds it
+    PinBuf<int32_t> order_host;    // M
+    PinBuf<uint8_t> adaV_host;     // M: the caller's adaV as the device holds it
     bool adaV_on_device = false;
-    uint32_t* sweep_io_host = nullptr; // MT_N generator words, G*K cass, then the order check's word
+    PinBuf<uint32_t> sweep_io_host; // MT_N generator words, G*K cass, then the order check's word
     size_t sweep_io_words = 0;
-    uint32_t* order_bad = nullptr;     // device: the first sweep position whose order entry is outside [0, M) (k_gather_meta), else 0xffffffff
     const void* occ_kern = nullptr;    // the last occupancy query (resident kernel, LDS bytes) and its answer
     size_t occ_lds = 0;
     int occ_per_cu = 0;
@@ -180,16 +187,16 @@ struct hgibbs_ctx {
     double eps_abs_bound = 0.0; // (sum of eps^8)^(1/8) >= max |eps| as of the last reduce_eps_all
     int res_refill = 0;       // option refill: the streaming workgroups' form -- 1 first (hg_resident.hip.h: fused multiply-adds), 2 second (hg_streamer2.hip.h: integer matrix products), 0 auto
     int res_pivots = 0;       // option pivots: Gram terms with predicted pivots at streaming time (no round trip for those events)
-    unsigned char* res_acc = nullptr; // Gram + raw-dot accumulators, batch counters
-    ResMsg* res_msg = nullptr;
-    ResState* res_state = nullptr;
-    ResState* res_state_host = nullptr; // pinned
-    ResParams* res_params = nullptr;      // the sweep's parameters in device memory (the walker reads them there) and their pinned staging copy
-    ResParams* res_params_host = nullptr;
-    unsigned long long* res_progress = nullptr; // device, written by the kernel while it runs
-    unsigned long long* res_progress_host = nullptr; // pinned copy, fetched on a second stream when the host's deadline passes
-    hipStream_t aux_stream = nullptr;
-    unsigned long long* res_trace = nullptr; // [8][RS_TRACE], debug_timing
+    DevBuf<unsigned char> res_acc; // Gram + raw-dot accumulators, batch counters
+    DevBuf<ResMsg> res_msg;
+    DevBuf<ResState> res_state;
+    PinBuf<ResState> res_state_host;
+    DevBuf<ResParams> res_params;      // the sweep's parameters in device memory (the walker reads them there) and their pinned staging copy
+    PinBuf<ResParams> res_params_host;
+    DevBuf<unsigned long long> res_progress; // device, written by the kernel while it runs
+    PinBuf<unsigned long long> res_progress_host; // pinned copy, fetched on a second stream when the host's deadline passes
+    Stream aux_stream;
+    DevBuf<unsigned long long> res_trace; // [8][RS_TRACE], debug_timing
     double res_timeout_s = 2.0;
     double res_deadline_s = 0.0; // option res_deadline_ms: the host's deadline for a resident sweep (0 = derived)
 
@@ -238,7 +245,7 @@ struct hgibbs_ctx {
     int ldmask_piece = 0;  // option ldmask_piece: band rows per piece of hgibbs_ld_mask (0 = automatic: the 2^24-pair bound)
     double ldm_ms[2] = {0, 0}; // device time of the last hgibbs_ld_mask: the products (zeroing, k_ld) and the reduce (zeroing the masks, k_ldm_reduce)
     double lds_ms[2] = {0, 0}; // device time of the last hgibbs_ld_scores: the products (zeroing, k_ld) and the reduce (k_lds_reduce, k_lds_final)
-    SparseLoad* sp = nullptr;      // hgibbs_sparse_begin .. hgibbs_sparse_end: the image in the making (bed stays null until it is published)
+    std::unique_ptr<SparseLoad> sp; // hgibbs_sparse_begin .. hgibbs_sparse_end: the image in the making (bed stays null until it is published)
     long long sparse_piece = 0;    // option sparse_piece: bytes of index buffers per piece of markers of hgibbs_sparse_get (0 = automatic)
     double sparse_ms[2] = {0, 0};  // device time of the last sparse load (begin .. end, every kernel) and of the last hgibbs_sparse_get
 };
@@ -246,8 +253,8 @@ struct hgibbs_ctx {
 static int ensure_scratch(hgibbs_ctx* h, size_t n)
 {
     if (h->scratch_n >= n) return 0;
-    if (h->scratch) HIP_TRY(hipFree(h->scratch));
-    HIP_TRY(hipMalloc(&h->scratch, n * sizeof(double)));
+    h->scratch_n = 0;
+    if (h->scratch.alloc(n)) return 1;
     h->scratch_n = n;
     return 0;
 }
@@ -711,78 +718,46 @@ int hgibbs_create(int device_id, hgibbs_t* out)
     HIP_TRY(hipGetDeviceProperties(&prop, device_id));
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return fail("hgibbs_create: device %d is %s, this library is built for gfx950 only", device_id, prop.gcnArchName);
-    hgibbs_ctx* h = new hgibbs_ctx();
+    // built whole, then released to the caller: a failure on the way frees what there is
+    std::unique_ptr<hgibbs_ctx> h(new hgibbs_ctx());
     h->device = device_id;
     h->num_cu = prop.multiProcessorCount;
-    HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreate(&h->ev0));
-    HIP_TRY(hipEventCreate(&h->ev1));
-    HIP_TRY(hipMalloc(&h->mt, MT_N * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&h->zig, (129 + 129 + 257 + 257) * sizeof(double)));
+    if (h->stream.create() || h->ev0.create() || h->ev1.create()) return 1;
+    if (h->mt.alloc(MT_N) || h->zig.alloc(129 + 129 + 257 + 257)) return 1;
     HIP_TRY(hipMemcpy(h->zig, HG_ZIG_NORMAL_X, 129 * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->zig + 129, HG_ZIG_NORMAL_Y, 129 * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->zig + 258, HG_ZIG_EXP_X, 257 * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->zig + 515, HG_ZIG_EXP_Y, 257 * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc(&h->desc, sizeof(SweepDesc) + sizeof(SweepCounters)));      // descriptor, then the sweep's counters
-    HIP_TRY(hipHostMalloc(&h->desc_host, sizeof(SweepDesc) + sizeof(SweepCounters)));
-    HIP_TRY(hipMalloc(&h->ticket, (16 + MAX_GROUPS + 256) * sizeof(uint32_t)));
+    if (h->desc.alloc_bytes(sizeof(SweepDesc) + sizeof(SweepCounters))) return 1; // descriptor, then the sweep's counters
+    if (h->desc_host.alloc_bytes(sizeof(SweepDesc) + sizeof(SweepCounters))) return 1;
+    if (h->ticket.alloc(16 + MAX_GROUPS + 256)) return 1;
     HIP_TRY(hipMemset(h->ticket, 0, (16 + MAX_GROUPS + 256) * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&h->totals, (size_t)ROWS_CAP * sizeof(double)));
-    HIP_TRY(hipMalloc(&h->carry, (size_t)MAX_BATCH * sizeof(double)));
-    HIP_TRY(hipMalloc(&h->ahead_raw, (size_t)2 * AHEAD_MAX * 2 * sizeof(double)));
-    HIP_TRY(hipMalloc(&h->apartials, (size_t)S_CAP * 2 * AHEAD_MAX * sizeof(double)));
-    HIP_TRY(hipMalloc(&h->aticket, (AHEAD_MAX / 2 + 4) * sizeof(uint32_t)));
+    if (h->totals.alloc(ROWS_CAP) || h->carry.alloc(MAX_BATCH) || h->ahead_raw.alloc((size_t)2 * AHEAD_MAX * 2)) return 1;
+    if (h->apartials.alloc((size_t)S_CAP * 2 * AHEAD_MAX) || h->aticket.alloc(AHEAD_MAX / 2 + 4)) return 1;
     HIP_TRY(hipMemset(h->aticket, 0, (AHEAD_MAX / 2 + 4) * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&h->sums, (NROW * MAX_BATCH + 1) * sizeof(double)));
-    HIP_TRY(hipMalloc(&h->dbg, 48 * sizeof(unsigned long long)));
+    if (h->sums.alloc(NROW * MAX_BATCH + 1) || h->dbg.alloc(48)) return 1;
     HIP_TRY(hipMemset(h->dbg, 0, 48 * sizeof(unsigned long long)));
-    HIP_TRY(hipHostMalloc(&h->scratch_host, 4096 * sizeof(double)));
-    HIP_TRY(hipMalloc(&h->res_acc, RES_ACC_BYTES));
-    HIP_TRY(hipMalloc(&h->res_msg, RS_MSG * sizeof(ResMsg)));
-    HIP_TRY(hipMalloc(&h->res_state, sizeof(ResState)));
-    HIP_TRY(hipHostMalloc(&h->res_state_host, sizeof(ResState)));
-    HIP_TRY(hipMalloc(&h->res_params, sizeof(ResParams)));
-    HIP_TRY(hipHostMalloc(&h->res_params_host, sizeof(ResParams)));
-    HIP_TRY(hipMalloc(&h->res_progress, 16 * sizeof(unsigned long long)));
-    HIP_TRY(hipHostMalloc(&h->res_progress_host, 16 * sizeof(unsigned long long)));
-    HIP_TRY(hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking));
-    HIP_TRY(hipMalloc(&h->res_trace, (size_t)10 * RS_TRACE * sizeof(unsigned long long)));
+    if (h->scratch_host.alloc(4096)) return 1;
+    if (h->res_acc.alloc(RES_ACC_BYTES) || h->res_msg.alloc(RS_MSG)) return 1;
+    if (h->res_state.alloc(1) || h->res_state_host.alloc(1) || h->res_params.alloc(1) || h->res_params_host.alloc(1)) return 1;
+    if (h->res_progress.alloc(16) || h->res_progress_host.alloc(16)) return 1;
+    if (h->aux_stream.create()) return 1;
+    if (h->res_trace.alloc((size_t)10 * RS_TRACE)) return 1;
     HIP_TRY(hipMemset(h->res_trace, 0, (size_t)10 * RS_TRACE * sizeof(unsigned long long)));
-    *out = h;
+    *out = h.release();
     return 0;
 }
 
+// The members free themselves; what is left to do by hand, in this order: the stream's work ends, the
+// communicator goes, the peers' mappings of THEIR mailboxes are closed (never the own mbox, which is the handle's to free)
 int hgibbs_destroy(hgibbs_t h)
 {
     if (!h) return 0;
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
     if (h->comm) ncclCommDestroy(h->comm);
-    bw_free(h->bw);
-    sp_free(h->sp);
     for (int r = 0; r < MAX_RANKS; ++r)
         if (h->peer_base[r] && h->peer_base[r] != h->mbox) (void)hipIpcCloseMemHandle(h->peer_base[r]);
-    if (h->mbox) (void)hipFree(h->mbox);
-    void* ptrs[] = {h->bed, h->eps[0], h->eps[1], h->mave, h->mstd, h->counts, h->groups, h->beta, h->comp, h->acum, h->order,
-                    h->adaV, h->covX, h->s_mave, h->s_mstd, h->s_bold, h->s_ga, h->pred, h->pred_cnt, h->dbg, h->cass, h->tables, h->mt, h->zig, h->desc, h->partials, h->totals, h->ticket, h->sums, h->scratch, h->carry, h->ahead_raw, h->apartials, h->aticket, h->res_acc, h->res_msg, h->res_state, h->res_trace, h->order_bad};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    if (h->desc_host) (void)hipHostFree(h->desc_host);
-    if (h->scratch_host) (void)hipHostFree(h->scratch_host);
-    if (h->res_state_host) (void)hipHostFree(h->res_state_host);
-    if (h->res_params) (void)hipFree(h->res_params);
-    if (h->res_params_host) (void)hipHostFree(h->res_params_host);
-    if (h->res_progress) (void)hipFree(h->res_progress);
-    if (h->res_progress_host) (void)hipHostFree(h->res_progress_host);
-    if (h->aux_stream) (void)hipStreamDestroy(h->aux_stream);
-    if (h->beta_host) (void)hipHostFree(h->beta_host);
-    if (h->bsq_idx_host) (void)hipHostFree(h->bsq_idx_host);
-    if (h->order_host) (void)hipHostFree(h->order_host);
-    if (h->adaV_host) (void)hipHostFree(h->adaV_host);
-    if (h->sweep_io_host) (void)hipHostFree(h->sweep_io_host);
-    (void)hipEventDestroy(h->ev0);
-    (void)hipEventDestroy(h->ev1);
-    (void)hipStreamDestroy(h->stream);
     delete h;
     return 0;
 }
@@ -829,16 +804,17 @@ extern "C" int hgibbs_p2p_export(hgibbs_t h, void* handle64)
     HIP_TRY(hipSetDevice(h->device));
     if (!h->mbox) {
         // uncached (fine-grained) device memory: remote GPUs' stores must be visible to local loads
+        DevBuf<unsigned char> m;
         void* p = nullptr;
         hipError_t e = hipExtMallocWithFlags(&p, MBOX_BYTES, hipDeviceMallocUncached);
+        if (e == hipSuccess) m.adopt((unsigned char*)p);
         hipIpcMemHandle_t probe;
-        if (e != hipSuccess || hipIpcGetMemHandle(&probe, p) != hipSuccess) {
+        if (e != hipSuccess || hipIpcGetMemHandle(&probe, m) != hipSuccess) {
             (void)hipGetLastError();
-            if (e == hipSuccess) (void)hipFree(p);
-            HIP_TRY(hipMalloc(&p, MBOX_BYTES));
+            if (m.alloc(MBOX_BYTES)) return 1; // (frees what the probe refused first)
         }
-        h->mbox = (unsigned char*)p;
-        HIP_TRY(hipMemset(h->mbox, 0, MBOX_BYTES));
+        HIP_TRY(hipMemset(m, 0, MBOX_BYTES));
+        h->mbox = std::move(m);
     }
     hipIpcMemHandle_t hd;
     HIP_TRY(hipIpcGetMemHandle(&hd, h->mbox));
@@ -868,48 +844,46 @@ extern "C" int hgibbs_p2p_import(hgibbs_t h, const void* handles)
     return 0;
 }
 
+// Builds the problem in a local and moves it into the handle once every allocation has succeeded: a refused or failed call leaves the
+// handle as it was
 static int alloc_problem(hgibbs_ctx* h, uint32_t n_global, uint32_t n_local, uint32_t M, uint32_t row_begin)
 {
     if (n_local == 0 || M == 0) return fail("empty problem: n_local=%u M=%u", n_local, M);
     if (h->bed) return fail("data already loaded on this handle");
     if (h->sp) return fail("a sparse load is in progress on this handle (hgibbs_sparse_end)");
-    h->n_global = n_global;
-    h->n_local = n_local;
-    h->M = M;
-    h->row_begin = row_begin;
-    h->n_pad = (uint32_t)(((uint64_t)n_local + BLOCK_IND - 1) / BLOCK_IND * BLOCK_IND);
-    h->stride = h->n_pad / 4;
-    HIP_TRY(hipMalloc(&h->bed, (size_t)M * h->stride));
+    Problem p;
+    p.n_global = n_global;
+    p.n_local = n_local;
+    p.M = M;
+    p.row_begin = row_begin;
+    p.n_pad = (uint32_t)(((uint64_t)n_local + BLOCK_IND - 1) / BLOCK_IND * BLOCK_IND);
+    p.stride = p.n_pad / 4;
+    if (p.bed.alloc((size_t)M * p.stride)) return 1;
     for (int b = 0; b < 2; ++b) {
-        HIP_TRY(hipMalloc(&h->eps[b], (size_t)h->n_pad * sizeof(double)));
-        HIP_TRY(hipMemsetAsync(h->eps[b], 0, (size_t)h->n_pad * sizeof(double), h->stream));
+        if (p.eps[b].alloc(p.n_pad)) return 1;
+        HIP_TRY(hipMemsetAsync(p.eps[b], 0, (size_t)p.n_pad * sizeof(double), h->stream));
     }
-    HIP_TRY(hipMalloc(&h->mave, (size_t)M * sizeof(double)));
-    HIP_TRY(hipMalloc(&h->mstd, (size_t)M * sizeof(double)));
-    HIP_TRY(hipMalloc(&h->counts, (size_t)M * 3 * sizeof(unsigned long long)));
-    HIP_TRY(hipMalloc(&h->beta, (size_t)M * sizeof(double)));
-    HIP_TRY(hipMalloc(&h->comp, (size_t)M * sizeof(int32_t)));
-    HIP_TRY(hipMalloc(&h->acum, (size_t)M * sizeof(double)));
-    HIP_TRY(hipMalloc(&h->order, (size_t)M * sizeof(int32_t)));
-    HIP_TRY(hipMalloc(&h->adaV, (size_t)M));
-    HIP_TRY(hipMalloc(&h->order_bad, sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&h->s_mave, (size_t)M * sizeof(double)));
-    HIP_TRY(hipMalloc(&h->s_mstd, (size_t)M * sizeof(double)));
-    HIP_TRY(hipMalloc(&h->s_bold, (size_t)M * sizeof(double)));
-    HIP_TRY(hipMalloc(&h->s_ga, (size_t)M * sizeof(int32_t)));
-    HIP_TRY(hipMalloc(&h->pred, ((size_t)M + 16) * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&h->pred_cnt, ((size_t)(M + PRED_CHUNK - 1) / PRED_CHUNK + 1) * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&h->groups, (size_t)M * sizeof(int32_t)));
-    HIP_TRY(hipMemsetAsync(h->beta, 0, (size_t)M * sizeof(double), h->stream));
-    HIP_TRY(hipMemsetAsync(h->comp, 0, (size_t)M * sizeof(int32_t), h->stream));
-    HIP_TRY(hipMemsetAsync(h->acum, 0, (size_t)M * sizeof(double), h->stream));
-    HIP_TRY(hipMemsetAsync(h->groups, 0, (size_t)M * sizeof(int32_t), h->stream));
-    const uint32_t nblk_x = h->n_pad / BLOCK_IND;
-    HIP_TRY(hipMalloc(&h->partials, (size_t)PROWS_CAP * S_CAP * sizeof(double)));
+    if (p.mave.alloc(M) || p.mstd.alloc(M) || p.counts.alloc((size_t)M * 3) || p.beta.alloc(M) || p.comp.alloc(M) || p.acum.alloc(M)) return 1;
+    if (p.order.alloc(M) || p.adaV.alloc(M) || p.order_bad.alloc(1) || p.s_mave.alloc(M) || p.s_mstd.alloc(M) || p.s_bold.alloc(M) || p.s_ga.alloc(M)) return 1;
+    if (p.pred.alloc((size_t)M + 16) || p.pred_cnt.alloc((size_t)(M + PRED_CHUNK - 1) / PRED_CHUNK + 1) || p.groups.alloc(M)) return 1;
+    HIP_TRY(hipMemsetAsync(p.beta, 0, (size_t)M * sizeof(double), h->stream));
+    HIP_TRY(hipMemsetAsync(p.comp, 0, (size_t)M * sizeof(int32_t), h->stream));
+    HIP_TRY(hipMemsetAsync(p.acum, 0, (size_t)M * sizeof(double), h->stream));
+    HIP_TRY(hipMemsetAsync(p.groups, 0, (size_t)M * sizeof(int32_t), h->stream));
+    const uint32_t nblk_x = p.n_pad / BLOCK_IND;
+    if (p.partials.alloc((size_t)PROWS_CAP * S_CAP)) return 1;
     if (ensure_scratch(h, (size_t)nblk_x * 4 + 4096)) return 1;
-    h->eps_cur = 0;
-    h->have_stats = false;
+    static_cast<Problem&>(*h) = std::move(p);
     return 0;
+}
+
+// The loader that called alloc_problem could not fill the image: the handle is empty again.  Returns 1 and leaves the message as it
+// stands, so a failed step ends with `return drop_problem(h)`.
+static int drop_problem(hgibbs_ctx* h)
+{
+    (void)hipStreamSynchronize(h->stream);
+    static_cast<Problem&>(*h) = Problem();
+    return 1;
 }
 
 int hgibbs_load_bed(hgibbs_t h, const uint8_t* bed_host, uint64_t stride_in, uint32_t n_total, uint32_t M,
@@ -933,48 +907,42 @@ int hgibbs_load_bed(hgibbs_t h, const uint8_t* bed_host, uint64_t stride_in, uin
     }
     if (n_global < 2) return fail("hgibbs_load_bed: n_global must be at least 2");
     if (alloc_problem(h, n_global, n_local, M, row_begin)) return 1;
-    HIP_TRY(hipMemsetAsync(h->bed, 0x55, (size_t)M * h->stride, h->stream));
-
-    if (!keep_host) {
-        const size_t width = ((size_t)n_local + 3) / 4;
-        HIP_TRY(hipMemcpy2DAsync(h->bed, h->stride, bed_host + (row_begin >> 2), stride_in, width, M, hipMemcpyHostToDevice, h->stream));
-        k_fix_padding<<<(M + 255) / 256, 256, 0, h->stream>>>(h->bed, h->stride, n_local, M);
-        HIP_TRY(hipGetLastError());
-    } else {
-        // NA rows dropped: build the kept-row index list, then gather on the device in slabs of columns
-        // (the two staging buffers are released on every exit, the error returns included)
-        struct Staging {
-            uint32_t* idx = nullptr;
-            uint8_t* src = nullptr;
-            ~Staging()
-            {
-                if (src) (void)hipFree(src);
-                if (idx) (void)hipFree(idx);
+    const auto fill = [&]() -> int {
+        HIP_TRY(hipMemsetAsync(h->bed, 0x55, (size_t)M * h->stride, h->stream));
+        if (!keep_host) {
+            const size_t width = ((size_t)n_local + 3) / 4;
+            HIP_TRY(hipMemcpy2DAsync(h->bed, h->stride, bed_host + (row_begin >> 2), stride_in, width, M, hipMemcpyHostToDevice, h->stream));
+            k_fix_padding<<<(M + 255) / 256, 256, 0, h->stream>>>(h->bed, h->stride, n_local, M);
+            HIP_TRY(hipGetLastError());
+        } else {
+            // NA rows dropped: build the kept-row index list, then gather on the device in slabs of columns
+            DevBuf<uint32_t> idx;
+            DevBuf<uint8_t> src;
+            if (idx.alloc(n_local)) return 1;
+            HIP_TRY(hipMemcpyAsync(idx, kept.data() + row_begin, (size_t)n_local * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+            const uint32_t slab = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(M, (256ull << 20) / std::max<uint64_t>(1, stride_in)));
+            if (src.alloc((size_t)slab * stride_in)) return 1;
+            for (uint32_t m0 = 0; m0 < M; m0 += slab) {
+                const uint32_t mc = std::min(slab, M - m0);
+                HIP_TRY(hipMemcpyAsync(src, bed_host + (size_t)m0 * stride_in, (size_t)mc * stride_in, hipMemcpyHostToDevice, h->stream));
+                // grid.y is limited to 65535: gather the staged columns in slabs of markers (as hgibbs_synth_bed)
+                for (uint32_t k0 = 0; k0 < mc; k0 += 32768) {
+                    const uint32_t kc = std::min<uint32_t>(32768, mc - k0);
+                    dim3 grid((uint32_t)((h->stride + 255) / 256), kc);
+                    k_compact_bed<<<grid, 256, 0, h->stream>>>(src + (size_t)k0 * stride_in, stride_in, idx, h->bed + ((size_t)m0 + k0) * h->stride,
+                                                               h->stride, n_local, kc);
+                    HIP_TRY(hipGetLastError());
+                }
             }
-        } st;
-        HIP_TRY(hipMalloc(&st.idx, (size_t)n_local * sizeof(uint32_t)));
-        HIP_TRY(hipMemcpyAsync(st.idx, kept.data() + row_begin, (size_t)n_local * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-        const uint32_t slab = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(M, (256ull << 20) / std::max<uint64_t>(1, stride_in)));
-        HIP_TRY(hipMalloc(&st.src, (size_t)slab * stride_in));
-        for (uint32_t m0 = 0; m0 < M; m0 += slab) {
-            const uint32_t mc = std::min(slab, M - m0);
-            HIP_TRY(hipMemcpyAsync(st.src, bed_host + (size_t)m0 * stride_in, (size_t)mc * stride_in, hipMemcpyHostToDevice, h->stream));
-            // grid.y is limited to 65535: gather the staged columns in slabs of markers (as hgibbs_synth_bed)
-            for (uint32_t k0 = 0; k0 < mc; k0 += 32768) {
-                const uint32_t kc = std::min<uint32_t>(32768, mc - k0);
-                dim3 grid((uint32_t)((h->stride + 255) / 256), kc);
-                k_compact_bed<<<grid, 256, 0, h->stream>>>(st.src + (size_t)k0 * stride_in, stride_in, st.idx, h->bed + ((size_t)m0 + k0) * h->stride,
-                                                           h->stride, n_local, kc);
-                HIP_TRY(hipGetLastError());
-            }
+            HIP_TRY(hipStreamSynchronize(h->stream)); // before the two staging buffers, which the kernels read, are freed
         }
-        HIP_TRY(hipStreamSynchronize(h->stream)); // before ~Staging frees what the kernels read
-    }
-    // the file's bytes (padding included: PLINK's missing code) are in place: re-code them for the kernels
-    k_recode_bed<<<4096, 256, 0, h->stream>>>(reinterpret_cast<uint32_t*>(h->bed), (uint64_t)M * h->stride / 4);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return 0;
+        // the file's bytes (padding included: PLINK's missing code) are in place: re-code them for the kernels
+        k_recode_bed<<<4096, 256, 0, h->stream>>>(reinterpret_cast<uint32_t*>(h->bed.p), (uint64_t)M * h->stride / 4);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        return 0;
+    };
+    return fill() ? drop_problem(h) : 0;
 }
 
 int hgibbs_synth_bed(hgibbs_t h, uint32_t n_global, uint32_t M, uint32_t row_begin, uint32_t row_end, uint64_t seed,
@@ -986,15 +954,18 @@ int hgibbs_synth_bed(hgibbs_t h, uint32_t n_global, uint32_t M, uint32_t row_beg
     if (alloc_problem(h, n_global, row_end - row_begin, M, row_begin)) return 1;
     double mr = missing_rate < 0 ? 0 : (missing_rate > 1 ? 1 : missing_rate);
     const uint32_t miss_thr = (uint32_t)std::min(4294967295.0, mr * 4294967296.0);
-    // grid.y is limited to 65535: synthesise in slabs of markers
-    for (uint32_t m0 = 0; m0 < M; m0 += 32768) {
-        const uint32_t mc = std::min<uint32_t>(32768, M - m0);
-        dim3 grid((uint32_t)((h->stride + 255) / 256), mc);
-        k_synth_bed<<<grid, 256, 0, h->stream>>>(h->bed, h->stride, h->n_local, row_begin, m0, seed, miss_thr);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return 0;
+    const auto fill = [&]() -> int {
+        // grid.y is limited to 65535: synthesise in slabs of markers
+        for (uint32_t m0 = 0; m0 < M; m0 += 32768) {
+            const uint32_t mc = std::min<uint32_t>(32768, M - m0);
+            dim3 grid((uint32_t)((h->stride + 255) / 256), mc);
+            k_synth_bed<<<grid, 256, 0, h->stream>>>(h->bed, h->stride, h->n_local, row_begin, m0, seed, miss_thr);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        return 0;
+    };
+    return fill() ? drop_problem(h) : 0;
 }
 
 int hgibbs_dims(hgibbs_t h, uint32_t* n_global, uint32_t* n_local, uint32_t* M, uint32_t* row_begin)
@@ -1066,13 +1037,12 @@ int hgibbs_set_residual(hgibbs_t h, const double* eps_host)
 {
     if (!h || !h->bed) return fail("hgibbs_set_residual: no data loaded");
     HIP_TRY(hipSetDevice(h->device));
-    double* tmp = nullptr;
-    HIP_TRY(hipMalloc(&tmp, (size_t)h->n_local * sizeof(double)));
+    DevBuf<double> tmp;
+    if (tmp.alloc(h->n_local)) return 1;
     HIP_TRY(hipMemcpyAsync(tmp, eps_host, (size_t)h->n_local * sizeof(double), hipMemcpyHostToDevice, h->stream));
     k_set_eps<<<(h->n_pad + 255) / 256, 256, 0, h->stream>>>(h->eps[h->eps_cur], tmp, h->n_local, h->n_pad);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipFree(tmp));
     return 0;
 }
 
@@ -1080,13 +1050,12 @@ int hgibbs_get_residual(hgibbs_t h, double* eps_host)
 {
     if (!h || !h->bed) return fail("hgibbs_get_residual: no data loaded");
     HIP_TRY(hipSetDevice(h->device));
-    double* tmp = nullptr;
-    HIP_TRY(hipMalloc(&tmp, (size_t)h->n_local * sizeof(double)));
+    DevBuf<double> tmp;
+    if (tmp.alloc(h->n_local)) return 1;
     k_get_eps<<<(h->n_local + 255) / 256, 256, 0, h->stream>>>(h->eps[h->eps_cur], tmp, h->n_local);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(eps_host, tmp, (size_t)h->n_local * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipFree(tmp));
     return 0;
 }
 
@@ -1176,19 +1145,19 @@ int hgibbs_set_covariates(hgibbs_t h, const double* X_host, int C)
     if (!h || !h->bed) return fail("hgibbs_set_covariates: load genotypes first");
     if (C < 0 || (C > 0 && !X_host)) return fail("hgibbs_set_covariates: bad argument");
     HIP_TRY(hipSetDevice(h->device));
-    if (h->covX) HIP_TRY(hipFree(h->covX));
-    h->covX = nullptr;
+    // built beside the old columns, which stay the handle's until the new ones are complete
+    DevBuf<double> covX;
+    if (C > 0) {
+        DevBuf<double> tmp;
+        if (covX.alloc((size_t)C * h->n_pad) || tmp.alloc((size_t)h->n_local * C)) return 1;
+        HIP_TRY(hipMemcpyAsync(tmp, X_host, (size_t)h->n_local * C * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        for (int c = 0; c < C; ++c)
+            k_set_cov<<<(h->n_pad + 255) / 256, 256, 0, h->stream>>>(covX + (size_t)c * h->n_pad, tmp, h->n_local, h->n_pad, C, c);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    h->covX = std::move(covX);
     h->C = C;
-    if (C == 0) return 0;
-    HIP_TRY(hipMalloc(&h->covX, (size_t)C * h->n_pad * sizeof(double)));
-    double* tmp = nullptr;
-    HIP_TRY(hipMalloc(&tmp, (size_t)h->n_local * C * sizeof(double)));
-    HIP_TRY(hipMemcpyAsync(tmp, X_host, (size_t)h->n_local * C * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    for (int c = 0; c < C; ++c)
-        k_set_cov<<<(h->n_pad + 255) / 256, 256, 0, h->stream>>>(h->covX + (size_t)c * h->n_pad, tmp, h->n_local, h->n_pad, C, c);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipFree(tmp));
     return 0;
 }
 
@@ -1224,22 +1193,25 @@ int hgibbs_set_model(hgibbs_t h, int G, int K, const int32_t* groups_host, const
     if (!h || !h->bed) return fail("hgibbs_set_model: load data first");
     if (G < 1 || K < 2 || K > MAX_K) return fail("hgibbs_set_model: need G>=1 and 2<=K<=%d (got G=%d K=%d)", MAX_K, G, K);
     HIP_TRY(hipSetDevice(h->device));
-    h->G = G;
-    h->K = K;
-    h->groups_host.assign(h->M, 0);
+    // checked and built in locals; the handle changes once nothing can fail any more
+    std::vector<int32_t> groups(h->M, 0);
     if (groups_host) {
         for (uint32_t i = 0; i < h->M; ++i) {
             if (groups_host[i] < 0 || groups_host[i] >= G) return fail("hgibbs_set_model: groups[%u]=%d outside [0,%d)", i, groups_host[i], G);
-            h->groups_host[i] = groups_host[i];
+            groups[i] = groups_host[i];
         }
     }
-    HIP_TRY(hipMemcpy(h->groups, h->groups_host.data(), (size_t)h->M * sizeof(int32_t), hipMemcpyHostToDevice));
+    DevBuf<int32_t> cass;
+    DevBuf<double> tables;
+    if (cass.alloc((size_t)G * K) || tables.alloc((size_t)4 * G * K)) return 1;
+    HIP_TRY(hipMemcpy(h->groups, groups.data(), (size_t)h->M * sizeof(int32_t), hipMemcpyHostToDevice));
+    h->G = G;
+    h->K = K;
+    h->groups_host = std::move(groups);
     h->cVa.assign(cVa_host, cVa_host + (size_t)G * K);
     h->cVaI.assign(cVaI_host, cVaI_host + (size_t)G * K);
-    if (h->cass) HIP_TRY(hipFree(h->cass));
-    if (h->tables) HIP_TRY(hipFree(h->tables));
-    HIP_TRY(hipMalloc(&h->cass, (size_t)G * K * sizeof(int32_t)));
-    HIP_TRY(hipMalloc(&h->tables, (size_t)4 * G * K * sizeof(double)));
+    h->cass = std::move(cass);
+    h->tables = std::move(tables);
     return 0;
 }
 
@@ -1280,8 +1252,8 @@ int hgibbs_beta_sqnorm(hgibbs_t h, double* bsq_host)
     // sweep's list and its s_bold as the buffers: both are rebuilt at the next sweep's start); the list's length travels with a
     // guessed number of entries, so a sparse model needs one synchronise and about 12 bytes per non-zero effect instead of 8 M.
     const uint32_t M = h->M, nchunk = (M + PRED_CHUNK - 1) / PRED_CHUNK;
-    if (!h->beta_host) HIP_TRY(hipHostMalloc(&h->beta_host, (size_t)M * sizeof(double)));
-    if (!h->bsq_idx_host) HIP_TRY(hipHostMalloc(&h->bsq_idx_host, ((size_t)M + 1) * sizeof(uint32_t)));
+    if (!h->beta_host && h->beta_host.alloc(M)) return 1;
+    if (!h->bsq_idx_host && h->bsq_idx_host.alloc((size_t)M + 1)) return 1;
     k_pred_count<<<nchunk, 256, 0, h->stream>>>(h->beta, M, h->pred_cnt);
     k_pred_scan<<<1, 1024, 0, h->stream>>>(h->pred_cnt, nchunk);
     k_pred_scatter<<<nchunk, 256, 0, h->stream>>>(h->beta, M, h->pred_cnt, nchunk, h->pred, h->s_bold);
@@ -1496,19 +1468,16 @@ int hgibbs_stream_ceiling(hgibbs_t h, uint64_t bytes, int reps, double* gbps)
 {
     if (!h || !gbps || bytes < (1u << 20) || reps < 1) return fail("hgibbs_stream_ceiling: bad argument");
     HIP_TRY(hipSetDevice(h->device));
-    void *a = nullptr, *b = nullptr;
-    HIP_TRY(hipMalloc(&a, bytes));
-    HIP_TRY(hipMalloc(&b, bytes));
+    DevBuf<unsigned char> a, b;
+    if (a.alloc(bytes) || b.alloc(bytes)) return 1;
     HIP_TRY(hipMemsetAsync(a, 1, bytes, h->stream));
     HIP_TRY(hipMemcpyAsync(b, a, bytes, hipMemcpyDeviceToDevice, h->stream)); // warm-up
     HIP_TRY(hipEventRecord(h->ev0, h->stream));
-    for (int i = 0; i < reps; ++i) HIP_TRY(hipMemcpyAsync((i & 1) ? a : b, (i & 1) ? b : a, bytes, hipMemcpyDeviceToDevice, h->stream));
+    for (int i = 0; i < reps; ++i) HIP_TRY(hipMemcpyAsync((i & 1) ? a.p : b.p, (i & 1) ? b.p : a.p, bytes, hipMemcpyDeviceToDevice, h->stream));
     HIP_TRY(hipEventRecord(h->ev1, h->stream));
     HIP_TRY(hipEventSynchronize(h->ev1));
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    HIP_TRY(hipFree(a));
-    HIP_TRY(hipFree(b));
     *gbps = 2.0 * (double)bytes * reps / (ms * 1e-3) / 1e9;
     return 0;
 }
@@ -1697,7 +1666,7 @@ static int sweep_resident(hgibbs_ctx* h, const SweepPlan& pl, const double r0[2]
     p.B = pl.B;
     p.nsh = std::min<uint32_t>(RS_NSH, pl.W);
     p.rsh = std::min<uint32_t>(RS_RSH, pl.W);
-    p.gacc = reinterpret_cast<uint32_t*>(h->res_acc);
+    p.gacc = reinterpret_cast<uint32_t*>(h->res_acc.p);
     p.racc = reinterpret_cast<unsigned long long*>(h->res_acc + RES_GACC_BYTES);
     p.rcnt = reinterpret_cast<uint32_t*>(h->res_acc + RES_GACC_BYTES + RES_RACC_BYTES);
     p.pacc = reinterpret_cast<unsigned long long*>(h->res_acc + RES_GACC_BYTES + RES_RACC_BYTES + RES_RCNT_BYTES);
@@ -2152,13 +2121,12 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
     // when a group is switched off, and the caller owns the pointer: compared, not assumed)
     const size_t io_words = (size_t)MT_N + (size_t)G * K + 1;
     if (h->sweep_io_words != io_words) {
-        if (h->sweep_io_host) HIP_TRY(hipHostFree(h->sweep_io_host));
-        h->sweep_io_host = nullptr;
-        HIP_TRY(hipHostMalloc(&h->sweep_io_host, io_words * sizeof(uint32_t)));
+        h->sweep_io_words = 0;
+        if (h->sweep_io_host.alloc(io_words)) return 1;
         h->sweep_io_words = io_words;
     }
-    if (!h->order_host) HIP_TRY(hipHostMalloc(&h->order_host, (size_t)M * sizeof(int32_t)));
-    if (!h->adaV_host) HIP_TRY(hipHostMalloc(&h->adaV_host, (size_t)M));
+    if (!h->order_host && h->order_host.alloc(M)) return 1;
+    if (!h->adaV_host && h->adaV_host.alloc(M)) return 1;
     uint32_t* const order_bad_host = h->sweep_io_host + MT_N + (size_t)G * K;
     HIP_TRY(hipMemcpyAsync(h->tables, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     std::memcpy(h->order_host, order_host, (size_t)M * sizeof(int32_t));
@@ -2257,3 +2225,5 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
 #include "hg_grm.hip.h"
 #include "hg_grmsums.hip.h"
 #include "hg_sparse.hip.h"
+
+hgibbs_ctx::~hgibbs_ctx() = default; // BwState and SparseLoad are complete here
