@@ -167,6 +167,49 @@ __device__ __forceinline__ void w2_gst(unsigned long long* p, unsigned long long
 // instruction stream, the clobber for the compiler)
 __device__ __forceinline__ void w2_lds_done() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
+// One look at a window slot's eight Gram accumulator words (one per shard row, 4 KiB apart -- 8 KiB in the build MISS) of one parity:
+// their sum.  The base is the parity's first row, the same in every lane (a scalar pair); the lane's part is a 32-bit byte offset that
+// does not change during the sweep.  The eight loads (agent scope: sc1, past this compute unit's cache to where the adds are performed)
+// are issued together and waited for once.  Written by hand: the compiler keeps a 64-bit address pair per row and rebuilds all eight
+// at every event.  Plain words: an immediate offset reaches 4 KiB down, so an offset register serves two rows (o1 = row 1's, ...).
+// Every lane loads, the lanes that take nothing from the event too (their offset is a slot's like any other: inside the rows), so the
+// loads need no exec mask.  No "memory" clobber: the words reach the program through the outputs only, the statement is volatile (run at
+// every look, never merged or hoisted), and its base depends on the record's parity, so it cannot move in front of the record's read.
+__device__ __forceinline__ uint32_t w2_gram_rows32(unsigned long long base, uint32_t o1, uint32_t o3, uint32_t o5, uint32_t o7)
+{
+    static_assert(RS_NSH == 8 && RS_GROW * 4 == 4096, "eight rows, 4 KiB apart");
+    uint32_t v0, v1, v2, v3, v4, v5, v6, v7;
+    asm volatile("global_load_dword %0, %8, %12 offset:-4096 sc1\n\t"
+                 "global_load_dword %1, %8, %12 sc1\n\t"
+                 "global_load_dword %2, %9, %12 offset:-4096 sc1\n\t"
+                 "global_load_dword %3, %9, %12 sc1\n\t"
+                 "global_load_dword %4, %10, %12 offset:-4096 sc1\n\t"
+                 "global_load_dword %5, %10, %12 sc1\n\t"
+                 "global_load_dword %6, %11, %12 offset:-4096 sc1\n\t"
+                 "global_load_dword %7, %11, %12 sc1\n\t"
+                 "s_waitcnt vmcnt(0)"
+                 : "=&v"(v0), "=&v"(v1), "=&v"(v2), "=&v"(v3), "=&v"(v4), "=&v"(v5), "=&v"(v6), "=&v"(v7)
+                 : "v"(o1), "v"(o3), "v"(o5), "v"(o7), "s"(base));
+    return ((v0 + v1 + v2) + (v3 + v4 + v5)) + (v6 + v7);
+}
+__device__ __forceinline__ unsigned long long w2_gram_rows64(unsigned long long base, const uint32_t (&o)[RS_NSH])
+{
+    static_assert(RS_NSH == 8, "eight rows");
+    unsigned long long v0, v1, v2, v3, v4, v5, v6, v7;
+    asm volatile("global_load_dwordx2 %0, %8, %16 sc1\n\t"
+                 "global_load_dwordx2 %1, %9, %16 sc1\n\t"
+                 "global_load_dwordx2 %2, %10, %16 sc1\n\t"
+                 "global_load_dwordx2 %3, %11, %16 sc1\n\t"
+                 "global_load_dwordx2 %4, %12, %16 sc1\n\t"
+                 "global_load_dwordx2 %5, %13, %16 sc1\n\t"
+                 "global_load_dwordx2 %6, %14, %16 sc1\n\t"
+                 "global_load_dwordx2 %7, %15, %16 sc1\n\t"
+                 "s_waitcnt vmcnt(0)"
+                 : "=&v"(v0), "=&v"(v1), "=&v"(v2), "=&v"(v3), "=&v"(v4), "=&v"(v5), "=&v"(v6), "=&v"(v7)
+                 : "v"(o[0]), "v"(o[1]), "v"(o[2]), "v"(o[3]), "v"(o[4]), "v"(o[5]), "v"(o[6]), "v"(o[7]), "s"(base));
+    return ((v0 + v1) + (v2 + v3)) + ((v4 + v5) + (v6 + v7));
+}
+
 // word source over the ring of generator blocks (untempered words)
 struct RingGen {
     const W2_LDS uint32_t* w;
@@ -352,19 +395,26 @@ __device__ __forceinline__ void w2_chain_body(const ResParams& prg)
     uint32_t C = 0, Sx = 0, Fs = 0, base = 0, gposr = rng_idx0 % W2_RING; // (every chain wave follows them through the records)
     // the Gram accumulators' words of this slot as last seen, per shard row and parity (they only ever grow: what an event added is
     // the difference; no store ever touches them -- adds are performed at the memory side, and a store could overtake or be overtaken)
-    // (two arrays with static accesses only -- both values read, one selected -- so that they stay in registers)
-    uint32_t gpa32[RS_NSH], gpb32[RS_NSH];
-    unsigned long long gpa64[RS_NSH], gpb64[RS_NSH];
+    // Kept is the SUM of the slot's eight row words, one per parity, not the words: an add is `count one | term`, so over any set of adds
+    // the sum of the rows grows by arrivals 2^24 + the terms' total mod 2^32 (2^56 and mod 2^64 in the build MISS) -- DESIGN.md 4R, "The
+    // chain's Gram words".  Rows no workgroup adds to (nsh < RS_NSH) are zero since the sweep's memset and are summed with the others.
+    static_assert(RS_NSH == 8, "the row sums are written out for eight rows");
+    uint32_t gsa32 = 0u, gsb32 = 0u;
+    unsigned long long gsa64 = 0ull, gsb64 = 0ull;
+    // (read by w2_gram_rows32 / 64: global loads, a uniform base and a 32-bit byte offset per lane -- the parity moves the base only)
+    const unsigned long long gacc = (unsigned long long)(uintptr_t)pr.gacc, gacc64 = (unsigned long long)(uintptr_t)pr.gacc64;
+    uint32_t gro[RS_NSH]; // the slot's byte offset in row r of a parity
 #pragma unroll
-    for (int r = 0; r < RS_NSH; ++r) {
-        gpa32[r] = gpb32[r] = 0u;
-        gpa64[r] = gpb64[r] = 0ull;
-    }
-    // (global address space, said so: through a generic pointer the polls are FLAT instructions, which the LDS counter counts as well)
-    typedef const __attribute__((address_space(1))) uint32_t* w2_g32;
-    typedef const __attribute__((address_space(1))) unsigned long long* w2_g64;
-    const w2_g32 gacc = (w2_g32)pr.gacc;
-    const w2_g64 gacc64 = (w2_g64)pr.gacc64;
+    for (int r = 0; r < RS_NSH; ++r) gro[r] = (sl + (uint32_t)r * (uint32_t)RS_GROW) * (MISS ? 8u : 4u);
+    // a wait for an event's Gram words goes on: the clock is read where the first look failed, the time limit and the abort word are
+    // looked at every 16th look after it (a look is a round trip to memory: the wait stays bounded by `timeout`)
+    auto gram_wait_fail = [&](uint32_t tries, unsigned long long& t0) {
+        if (tries == 0u) {
+            t0 = wall_clock64();
+            return false;
+        }
+        return (tries & 15u) == 0u && (wall_clock64() - t0 > timeout || aborted());
+    };
     uint32_t rno = 0; // records taken
 
     // ---- the decider's own state (wave 0; uniform) ----
@@ -497,43 +547,36 @@ __device__ __forceinline__ void w2_chain_body(const ResParams& prg)
             const uint32_t jo = pos_of_slot(sl, C); // the slot's position in the window as it was
             const double db = *(const W2_LDS double*)(rc + R_DB), mq = *(const W2_LDS double*)(rc + R_MQ), sq = *(const W2_LDS double*)(rc + R_SQ);
             if (r_type == (uint32_t)RT_EVENT) {
-                // an event that took the round trip: the streaming workgroups' Gram terms of this slot's column, all shard rows; every word
-                // must carry its shard's full arrival count
+                // an event that took the round trip: the streaming workgroups' Gram terms of this slot's column, all shard rows.  The rows'
+                // sum has grown by W arrivals exactly when every row carries its share (a row never exceeds it, and no add of the event after
+                // the next starts before this record is answered); what it grew by below the count is the terms' total.  The wave looks
+                // until every lane that takes the event has it: a lane's words do not move any more once they are complete.
                 const uint32_t par = (w2_uni(rc[R_NEV]) - 1u) & 1u;
                 const bool hit = son && jo > r_q && jo < r_sxo;
-                const unsigned long long t0 = wall_clock64();
-                bool bad = false;
+                const bool any_hit = __ballot(hit) != 0ull;
+                unsigned long long t0 = 0ull;
+                bool bad = false; // (uniform)
                 if constexpr (MISS) {
-                    const w2_g64 wp = gacc64 + (size_t)par * RS_NSH * RS_GROW + sl;
+                    const unsigned long long wp = gacc64 + par * (uint32_t)(RS_NSH * RS_GROW * 8);
                     unsigned long long A = 0ull;
-                    if (hit) {
-                        unsigned long long v[RS_NSH];
-                        for (;;) {
-#pragma unroll
-                            for (int r = 0; r < RS_NSH; ++r) v[r] = (uint32_t)r < nsh ? __hip_atomic_load(wp + (size_t)r * RS_GROW, HG_RLX_AGENT) : 0ull;
-                            bool ok = true;
-#pragma unroll
-                            for (int r = 0; r < RS_NSH; ++r) {
-                                const unsigned long long pa = gpa64[r], pb = gpb64[r];
-                                const unsigned long long d = v[r] - (par ? pb : pa);
-                                ok = ok && ((uint32_t)r >= nsh || (d >> 56) == cntG[(uint32_t)r < W % nsh ? 0 : 1]);
-                            }
-                            if (ok) break;
-                            if (wall_clock64() - t0 > timeout || aborted()) {
+                    if (any_hit) {
+                        const unsigned long long seen = par ? gsb64 : gsa64;
+                        unsigned long long S, D;
+                        for (uint32_t tries = 0;; ++tries) {
+                            S = w2_gram_rows64(wp, gro);
+                            D = S - seen;
+                            if (__builtin_amdgcn_ballot_w64(hit && (uint32_t)(D >> 56) != W) == 0ull) break;
+                            if (gram_wait_fail(tries, t0)) {
                                 bad = true;
                                 break;
                             }
                             __builtin_amdgcn_s_sleep(1);
                         }
-#pragma unroll
-                        for (int r = 0; r < RS_NSH; ++r) {
-                            const unsigned long long pa = gpa64[r], pb = gpb64[r];
-                            const unsigned long long d = v[r] - (par ? pb : pa);
-                            A += d & (RS_ONE64 - 1ull);
-                            gpa64[r] = par ? pa : v[r];
-                            gpb64[r] = par ? v[r] : pb;
-                        }
+                        A = D & (RS_ONE64 - 1ull);
+                        gsa64 = hit && !par ? S : gsa64;
+                        gsb64 = hit && par ? S : gsb64;
                     }
+                    if (RANKS && t0 == 0ull) t0 = wall_clock64(); // (one time limit for the poll and the exchange behind it)
                     if (RANKS && hit && !bad) {
                         // several ranks: the 56-bit sums cross as two words each, tag << 32 | half (tag = 1 | sweep | event: self-validating), by window slot
                         const unsigned long long tag = (0x80000000ull | ((sweep_id & 0x7full) << 24) | (unsigned long long)(w2_uni(rc[R_NEV]) & 0xffffffu)) << 32;
@@ -570,36 +613,26 @@ __device__ __forceinline__ void w2_chain_body(const ResParams& prg)
                     const double xx = mstd * sq * (((Ad - mq * gsm) - mave * gsq) + (mave * mq) * both);
                     dp = hit ? dp + db * xx : dp;
                 } else {
-                    const w2_g32 wp = gacc + (size_t)par * RS_NSH * RS_GROW + sl;
+                    const unsigned long long wp = gacc + par * (uint32_t)(RS_NSH * RS_GROW * 4);
                     uint32_t A = 0u;
-                    if (hit) {
-                        uint32_t v[RS_NSH];
-                        for (;;) {
-#pragma unroll
-                            for (int r = 0; r < RS_NSH; ++r) v[r] = (uint32_t)r < nsh ? __hip_atomic_load(wp + (size_t)r * RS_GROW, HG_RLX_AGENT) : 0u;
-                            bool ok = true;
-#pragma unroll
-                            for (int r = 0; r < RS_NSH; ++r) {
-                                const uint32_t pa = gpa32[r], pb = gpb32[r];
-                                const uint32_t d = v[r] - (par ? pb : pa);
-                                ok = ok && ((uint32_t)r >= nsh || (d >> 24) == cntG[(uint32_t)r < W % nsh ? 0 : 1]);
-                            }
-                            if (ok) break;
-                            if (wall_clock64() - t0 > timeout || aborted()) {
+                    if (any_hit) {
+                        const uint32_t seen = par ? gsb32 : gsa32;
+                        uint32_t S, D;
+                        for (uint32_t tries = 0;; ++tries) {
+                            S = w2_gram_rows32(wp, gro[1], gro[3], gro[5], gro[7]);
+                            D = S - seen;
+                            if (__builtin_amdgcn_ballot_w64(hit && (D >> 24) != W) == 0ull) break;
+                            if (gram_wait_fail(tries, t0)) {
                                 bad = true;
                                 break;
                             }
                             __builtin_amdgcn_s_sleep(1);
                         }
-#pragma unroll
-                        for (int r = 0; r < RS_NSH; ++r) {
-                            const uint32_t pa = gpa32[r], pb = gpb32[r];
-                            const uint32_t d = v[r] - (par ? pb : pa);
-                            A += d & RS_LOW;
-                            gpa32[r] = par ? pa : v[r];
-                            gpb32[r] = par ? v[r] : pb;
-                        }
+                        A = D & RS_LOW;
+                        gsa32 = hit && !par ? S : gsa32;
+                        gsb32 = hit && par ? S : gsb32;
                     }
+                    if (RANKS && t0 == 0ull) t0 = wall_clock64(); // (one time limit for the poll and the exchange behind it)
                     if (RANKS && hit && !bad) {
                         // several ranks: this rank's sum goes to every peer's mailbox, the peers' arrive in mine -- sweep << 48 | event << 24 | sum, one
                         // 8-byte store, self-validating; by window slot

@@ -1553,6 +1553,12 @@ static SweepPlan plan_sweep(const hgibbs_ctx* h)
     if ((h->stride & 1023u) || (uint64_t)h->M * (h->stride >> 10) >= (1ull << 32)) return refuse("a shard's BED columns are addressed in 32 bits of KiB");
     pl.T = (int)T;
     pl.W = (ntile + T - 1) / T;
+    // The Gram accumulator words' fields hold whole-shard totals: the second walker's chain takes an event's term as the growth of the SUM
+    // of a slot's rows ("The chain's Gram words").  The count field counts to W <= num_cu - 1 <= 255 (eight bits); the field
+    // below holds the shard's total term, at most 4 n_local (genotype 2 against genotype 2), which needs 4 n_local < 2^24: 4 194 303
+    // individuals.  T <= 4 tiles of 1024 on at most 255 workgroups are 1 044 480: a quarter of that.  (Build MISS: < 2^55 of 2^56, RS_GFX.)
+    static_assert(4ull * 255ull * (unsigned long long)RL_TMAX * (unsigned long long)TILE < (1ull << 24), "a shard's total Gram term fits the word's low field");
+    if (pl.W > 255u) return refuse("more than 255 streaming workgroups");
     pl.B = h->window ? h->window : (uint32_t)RS_BMAX;
     while (pl.B * T > 512u) pl.B >>= 1;
     // the walker: option walker; auto takes the second where it applies -- every marker takes a uniform, the mixture tables and the

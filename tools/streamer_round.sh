@@ -3,7 +3,7 @@
 # that both see the same machine.  bench.py defaults at c4 (PAIRS runs each), two runs each of c3 and c2; `--config c2 --opt
 # early_advance=0 --dump-outputs` twice on the parent and once on this tree, compared by cmp_dumps.py (no timing-dependent message:
 # the chain must be bit-identical); the stage anatomy of both builds, twice; per tree one rocprofv3 kernel trace and, in a run of
-# its own, the SQ counters (SQ_INSTS_VALU per sweep).  Every GPU step has its own limit and the job stops at the first that fails.
+# its own, the SQ counters (SQ_INSTS_VALU per sweep) and tools/res_anatomy.py's lines on the chain's record stage.  Every GPU step has its own limit and the job stops at the first that fails.
 # The files that are kept are named PREFIX_* (default streamer_round; the decider's round of section 8 used decider_round).
 # usage (repository root, both trees built): bash tools/streamer_round.sh PARENT_TREE [OUT_DIR] [PAIRS] [PREFIX]
 set -o pipefail
@@ -50,6 +50,9 @@ for TAG in parent result; do
   DB=$(ls $O/pmc_$TAG/*results.db $O/pmc_$TAG/*/*results.db 2>/dev/null | head -1)
   python3 $ROOT/tools/rocpd_pmc.py $DB k_sweep_limb 3 > $O/${P}_${TAG}_c4_pmc_SQ1.txt || stop "rocpd_pmc ($TAG)" $?
   rm -rf $O/pmc_$TAG
+  # the chain's record stage ("absorb"), which bench.py's anatomy does not print, and the Gram words' way to the walker
+  timeout -k 10 300 python3 tools/res_anatomy.py 500000 1000000 4 > $O/${TAG}_c4_res_anatomy_full.txt 2> $O/${TAG}_c4_res_anatomy.err || stop "res_anatomy ($TAG)" $?
+  grep -E "^(per message with an update|percentiles of message in flight|walker 2, per round)" $O/${TAG}_c4_res_anatomy_full.txt > $O/${P}_${TAG}_c4_res_anatomy.txt || stop "res_anatomy lines ($TAG)" $?
   cd $ROOT
 done
 python3 $ROOT/tools/streamer_round_fold.py $O | tee $O/${P}_runs.txt
