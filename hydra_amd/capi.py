@@ -24,6 +24,9 @@ ABI_SYMBOLS = [
     "hydra_chain_last_nnz", "hgibbs_score", "hgibbs_last_score_ms", "hgibbs_ld", "hgibbs_last_ld_ms",
     "hgibbs_ld_scores", "hgibbs_last_ld_scores_ms",
     "hgibbs_ld_mask", "hgibbs_last_ld_mask_ms", "hgibbs_ld_greedy", "hgibbs_ld_clump",
+    "hgibbs_ss_begin", "hgibbs_ss_sweep", "hgibbs_ss_state", "hgibbs_ss_band_get", "hgibbs_ss_end", "hgibbs_last_ss_ms", "hgibbs_ss_sweep_host",
+    "hydra_ss_chain_create", "hydra_ss_chain_create_host", "hydra_ss_chain_destroy", "hydra_ss_chain_iterate", "hydra_ss_chain_state",
+    "hydra_ss_chain_effects", "hydra_ss_chain_last_nnz", "hydra_ss_chain_order", "hydra_ss_chain_csv_line",
     "hgibbs_marker_dots", "hgibbs_last_marker_dots_ms", "hgibbs_marker_class_sums", "hgibbs_last_marker_class_sums_ms", "hgibbs_logit_null",
     "hgibbs_set_gram", "hgibbs_last_set_gram_ms", "hgibbs_set_tests",
     "hgibbs_spa_roots", "hgibbs_last_spa_ms", "hgibbs_spa_pvalue",
@@ -271,6 +274,26 @@ def lib():
     L.hgibbs_last_ld_mask_ms.argtypes = [vp, dp, dp]
     L.hgibbs_ld_greedy.argtypes = [C.c_uint32, C.c_uint32, u64p, u64p, u32p, C.c_uint32, u8p, ip]
     L.hgibbs_ld_clump.argtypes = [vp, C.c_uint32, u32p, C.c_double, u32p, C.c_uint32, u8p, ip, u64p]
+    rp = C.POINTER(RngState)
+    L.hgibbs_ss_begin.argtypes = [vp, C.c_double, C.c_uint32, u32p, dp]
+    L.hgibbs_ss_sweep.argtypes = [vp, ip, C.c_double, dp, dp, u8p, rp, ip, u64p]
+    L.hgibbs_ss_state.argtypes = [vp, dp, dp, dp]
+    L.hgibbs_ss_band_get.argtypes = [vp, C.c_uint32, C.c_uint32, dp]
+    L.hgibbs_ss_end.argtypes = [vp]
+    L.hgibbs_last_ss_ms.argtypes = [vp, dp, dp]
+    L.hgibbs_ss_sweep_host.argtypes = [C.c_uint32, C.c_double, C.c_uint32, u32p, dp, dp, dp, ip, dp, C.c_int, C.c_int, ip, dp, dp, ip, C.c_double, dp, dp,
+                                       u8p, rp, ip, u64p]
+    L.hydra_ss_chain_create.argtypes = [vp, C.POINTER(ModelDesc), C.c_double, C.c_uint32, u32p, dp, u8p, C.POINTER(vp)]
+    L.hydra_ss_chain_create_host.argtypes = [C.c_uint32, C.POINTER(ModelDesc), C.c_double, C.c_uint32, u32p, dp, dp, u8p, C.POINTER(vp)]
+    L.hydra_ss_chain_destroy.argtypes = [vp]
+    L.hydra_ss_chain_iterate.argtypes = [vp]
+    L.hydra_ss_chain_state.argtypes = [vp, dp, dp, dp, dp, ip, ip, rp]
+    L.hydra_ss_chain_effects.argtypes = [vp, dp, ip, dp, dp]
+    L.hydra_ss_chain_last_nnz.argtypes = [vp]
+    L.hydra_ss_chain_last_nnz.restype = C.c_uint64
+    L.hydra_ss_chain_order.argtypes = [vp]
+    L.hydra_ss_chain_order.restype = ip
+    L.hydra_ss_chain_csv_line.argtypes = [vp, C.c_uint32, C.c_char_p, C.c_size_t]
     L.hgibbs_marker_dots.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_int, dp, dp, dp]
     L.hgibbs_last_marker_dots_ms.argtypes = [vp, dp]
     L.hgibbs_marker_class_sums.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_int, dp, dp]
@@ -373,6 +396,39 @@ def ld_greedy(M, W, fwd, bwd, order, may_lead=None):
     owner = np.full(max(int(M), 1), -1, dtype=np.int32)
     check(lib().hgibbs_ld_greedy(M, W, _u64(fwd), _u64(bwd), od.ctypes.data_as(C_U32P), od.size, _u8(ml) if ml is not None else None, _ip(owner)))
     return owner[:M]
+
+
+def ss_ahead(M, W, ahead=None):
+    """The window of the summary-statistics engines as they take it: (M,) uint32, min(W, M - 1 - j) where none is given."""
+    if ahead is None:
+        return np.minimum(W, M - 1 - np.arange(M)).astype(np.uint32)
+    return np.ascontiguousarray(ahead, dtype=np.uint32)
+
+
+def ss_sweep_host(n_eff, W, ahead, band, c, beta, components, acum, groups, cVa, cVaI, order, sigmaE, sigmaG, estPi, adaV, rng):
+    """hgibbs_ss_sweep_host (host only): one sweep of the summary-statistics step on host arrays.  band (M, W) float64; c, beta, acum
+    float64 and components int32 of M entries are the state, updated in place (contiguous arrays of those types are required); cVa and
+    cVaI (G, K); rng: RngState, updated in place.  Returns (cass[G, K], nnz_updates)."""
+    for a, t in ((c, np.float64), (beta, np.float64), (acum, np.float64), (components, np.int32)):
+        if a.dtype != t or not a.flags.c_contiguous:
+            raise ValueError("ss_sweep_host: the state must be contiguous float64 / int32 arrays (they are updated in place)")
+    M = c.shape[0]
+    band = np.ascontiguousarray(band, dtype=np.float64)
+    cVa = np.ascontiguousarray(cVa, dtype=np.float64)
+    cVaI = np.ascontiguousarray(cVaI, dtype=np.float64)
+    G, K = cVa.shape
+    ah = ss_ahead(M, W, ahead)
+    groups = None if groups is None else np.ascontiguousarray(groups, dtype=np.int32)
+    order = np.ascontiguousarray(order, dtype=np.int32)
+    sigmaG = np.ascontiguousarray(sigmaG, dtype=np.float64)
+    estPi = np.ascontiguousarray(estPi, dtype=np.float64)
+    adaV = np.ascontiguousarray(adaV, dtype=np.uint8)
+    cass = np.zeros((G, K), dtype=np.int32)
+    nnz = C.c_uint64()
+    check(lib().hgibbs_ss_sweep_host(M, float(n_eff), W, ah.ctypes.data_as(C_U32P), _dp(band), _dp(c), _dp(beta), _ip(components), _dp(acum), G, K,
+                                     _ip(groups) if groups is not None else None, _dp(cVa), _dp(cVaI), _ip(order), float(sigmaE), _dp(sigmaG),
+                                     _dp(estPi), _u8(adaV), C.byref(rng), _ip(cass), C.byref(nnz)))
+    return cass, nnz.value
 
 
 def he_fit(y, ay, ayy, a1, a2, partners):
@@ -1128,6 +1184,53 @@ class Device:
                                   _ip(cass), C.byref(nnz)))
         return cass, nnz.value
 
+    def ss_begin(self, n_eff, W, xty, ahead=None):
+        """hgibbs_ss_begin: the band of the loaded panel on the device, c = xty, every effect 0.  ahead (M,) or None."""
+        xty = np.ascontiguousarray(xty, dtype=np.float64)
+        if xty.shape != (self.M,):
+            raise ValueError("ss_begin: xty must have M entries")
+        ah = None if ahead is None else np.ascontiguousarray(ahead, dtype=np.uint32)
+        if ah is not None and ah.shape != (self.M,):
+            raise ValueError("ss_begin: ahead must have M entries")
+        check(self.L.hgibbs_ss_begin(self.h, float(n_eff), W, ah.ctypes.data_as(C_U32P) if ah is not None else None, _dp(xty)))
+        self.ss_W = W
+
+    def ss_sweep(self, order, sigmaE, sigmaG, estPi, adaV, rng):
+        """hgibbs_ss_sweep; rng: RngState, updated in place.  Returns (cass[G,K], nnz_updates)."""
+        order = np.ascontiguousarray(order, dtype=np.int32)
+        sigmaG = np.ascontiguousarray(sigmaG, dtype=np.float64)
+        estPi = np.ascontiguousarray(estPi, dtype=np.float64)
+        adaV = np.ascontiguousarray(adaV, dtype=np.uint8)
+        if order.shape != (self.M,) or adaV.shape != (self.M,):
+            raise ValueError("ss_sweep: order and adaV must have M entries")
+        cass = np.zeros((self.G, self.K), dtype=np.int32)
+        nnz = C.c_uint64()
+        check(self.L.hgibbs_ss_sweep(self.h, _ip(order), float(sigmaE), _dp(sigmaG), _dp(estPi), _u8(adaV), C.byref(rng), _ip(cass), C.byref(nnz)))
+        return cass, nnz.value
+
+    def ss_state(self):
+        """hgibbs_ss_state: (c, sum beta_j b_j, sum beta_j c_j)."""
+        c = np.zeros(self.M)
+        sb, sc = C.c_double(), C.c_double()
+        check(self.L.hgibbs_ss_state(self.h, _dp(c), C.byref(sb), C.byref(sc)))
+        return c, sb.value, sc.value
+
+    def ss_band(self, m0=0, count=None):
+        """hgibbs_ss_band_get: (count, W) float64, out[j - m0, d - 1] = (n_eff - 1) r(j, j + d), 0 outside the window."""
+        count = self.M - m0 if count is None else count
+        out = np.zeros((count, self.ss_W))
+        check(self.L.hgibbs_ss_band_get(self.h, m0, count, _dp(out)))
+        return out
+
+    def ss_end(self):
+        check(self.L.hgibbs_ss_end(self.h))
+
+    def last_ss_ms(self):
+        """(band_ms, sweep_ms): device time of ss_begin's band and of the last ss_sweep's kernel."""
+        a, b = C.c_double(), C.c_double()
+        check(self.L.hgibbs_last_ss_ms(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def resident_trace(self):
         out = np.zeros((10, 4096), dtype=np.uint64)
         check(self.L.hgibbs_resident_trace(self.h, out.ctypes.data_as(C.POINTER(C.c_uint64)), out.size))
@@ -1226,6 +1329,75 @@ class Chain:
     def csv_line(self, it):
         buf = C.create_string_buffer(50000)
         n = self.L.hydra_chain_csv_line(self.h, it, buf, 50000)
+        return buf.raw[:n].decode()
+
+
+class SsChain:
+    """hydra_ss_chain_t: hydra_chain's iteration from summary statistics.  dev: a Device that holds the panel (the device engine), or
+    None with `band` (M, W) for the host engine, which needs no device."""
+
+    def __init__(self, dev, n_eff, W, xty, ahead=None, band=None, use=None, mS=None, groups=None, seed=1222, shuffle=1):
+        self.dev = dev
+        self.L = lib()
+        if mS is None:
+            mS = np.array([[0.0, 0.0001, 0.001, 0.01]])
+        self.mS = np.ascontiguousarray(mS, dtype=np.float64)
+        self.G, self.K = self.mS.shape
+        self.groups = None if groups is None else np.ascontiguousarray(groups, dtype=np.int32)
+        xty = np.ascontiguousarray(xty, dtype=np.float64)
+        self.M = xty.shape[0]
+        use = None if use is None else np.ascontiguousarray(use, dtype=np.uint8)
+        d = ModelDesc(seed, shuffle, self.G, self.K, _ip(self.groups) if self.groups is not None else None, _dp(self.mS))
+        self.h = C.c_void_p()
+        if dev is not None:
+            assert self.M == dev.M
+            ah = None if ahead is None else np.ascontiguousarray(ahead, dtype=np.uint32)
+            check(self.L.hydra_ss_chain_create(dev.h, C.byref(d), float(n_eff), W, ah.ctypes.data_as(C_U32P) if ah is not None else None, _dp(xty),
+                                               _u8(use) if use is not None else None, C.byref(self.h)))
+            dev.G, dev.K, dev.ss_W = self.G, self.K, W
+        else:
+            band = np.ascontiguousarray(band, dtype=np.float64)
+            assert band.shape == (self.M, W)
+            ah = ss_ahead(self.M, W, ahead)
+            check(self.L.hydra_ss_chain_create_host(self.M, C.byref(d), float(n_eff), W, ah.ctypes.data_as(C_U32P), _dp(band), _dp(xty),
+                                                    _u8(use) if use is not None else None, C.byref(self.h)))
+
+    def __del__(self):
+        try:
+            if self.h:
+                self.L.hydra_ss_chain_destroy(self.h)
+        except Exception:
+            pass
+
+    def iterate(self):
+        check(self.L.hydra_ss_chain_iterate(self.h))
+
+    def state(self):
+        G, K = self.G, self.K
+        sE, mu = C.c_double(), C.c_double()
+        sG, pi = np.zeros(G), np.zeros((G, K))
+        m0, cass = np.zeros(G, dtype=np.int32), np.zeros((G, K), dtype=np.int32)
+        rng = RngState()
+        check(self.L.hydra_ss_chain_state(self.h, C.byref(sE), C.byref(mu), _dp(sG), _dp(pi), _ip(m0), _ip(cass), C.byref(rng)))
+        return {"sigmaE": sE.value, "mu": mu.value, "sigmaG": sG, "estPi": pi, "m0": m0, "cass": cass,
+                "rng_x": np.array(rng.x, dtype=np.uint32), "rng_idx": int(rng.idx)}
+
+    def effects(self):
+        """(beta, components, acum, c)"""
+        beta, acum, c = np.zeros(self.M), np.zeros(self.M), np.zeros(self.M)
+        comp = np.zeros(self.M, dtype=np.int32)
+        check(self.L.hydra_ss_chain_effects(self.h, _dp(beta), _ip(comp), _dp(acum), _dp(c)))
+        return beta, comp, acum, c
+
+    def order(self):
+        return np.ctypeslib.as_array(self.L.hydra_ss_chain_order(self.h), shape=(self.M,)).copy()
+
+    def last_nnz(self):
+        return int(self.L.hydra_ss_chain_last_nnz(self.h))
+
+    def csv_line(self, it):
+        buf = C.create_string_buffer(50000)
+        n = self.L.hydra_ss_chain_csv_line(self.h, it, buf, 50000)
         return buf.raw[:n].decode()
 
 

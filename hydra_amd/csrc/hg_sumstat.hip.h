@@ -1,0 +1,438 @@
+// BayesR from summary statistics and the panel's LD band: the Gibbs step of the chain with c_j = x_j'eps kept
+// per marker instead of the residual per individual.  Inputs: n_eff, b = X'y, and the band B_jk = (n_eff - 1) r_jk of the loaded panel.
+//
+//   band      the band frame of hg_ld.hip.h (ld_band_pieces): k_ld<MISS>, unchanged, fills the 64-bit sums of a piece of band rows;
+//             k_ss_band replaces k_ld_final: r of ld_pair_r times (n_eff - 1), 0 outside ahead[j] and where r is NaN.  M x W doubles,
+//             row j = the markers j + 1 .. j + W; only this `ahead` half is kept.  Nothing of it leaves the device.
+//   sweep     k_ss_sweep: ONE launch per sweep, ONE workgroup, because the chain is sequential through c and through the generator.
+//             decision  every lane runs the step of hg_ss_step.h on the same numbers (uniform): no broadcast, and a marker whose
+//                       effect stays where it was costs no barrier at all.  The generator's block lies in LDS; a block that runs out
+//                       is followed by the next one made by the whole workgroup (the three segments of the recurrence).
+//             update    delta != 0: barrier (every wave has read its c_j), c_k += delta B_jk over the lanes -- j's own row forwards
+//                       (coalesced), the rows of the markers behind at offset j - k (one load each) --, barrier.
+//             ahead     the next marker's c, effect, group and window are loaded before the decision of this one; c is loaded again
+//                       after an update, since the next marker may lie inside the window just updated.
+//             memory    c is read and written with ordinary vector loads and stores; what orders them is the workgroup barrier.
+//   sums      k_ss_sums: sum beta_j b_j and sum beta_j c_j in marker order by one wave, the non-zero effects only (a zero effect adds
+//             +-0 to a sum that is never -0): a fixed order, so the bits repeat.
+#pragma once
+
+#include "hg_ss_step.h"
+
+struct SsResult {
+    unsigned long long nnz;
+    uint32_t rng_idx, err; // err: 0, or 1 + the sweep position whose component walk found no component
+    double sums[2];
+};
+
+// The summary-statistics side of the handle, between hgibbs_ss_begin and hgibbs_ss_end
+struct SsState {
+    double n_eff = 0.0;
+    uint32_t W = 0, M = 0;
+    DevBuf<double> band, c, xty;
+    DevBuf<uint32_t> ahead, back;
+    DevBuf<int32_t> order;
+    DevBuf<uint8_t> ada;
+    DevBuf<SsResult> res;
+    std::vector<uint8_t> ok;     // per marker: its standard deviation is finite
+    std::vector<uint8_t> ada_host;
+    double band_ms = 0.0, sweep_ms = 0.0;
+};
+
+namespace {
+
+constexpr int SS_TPB = 256;
+static_assert(SS_MAX_K == MAX_K, "the step's component arrays hold what hgibbs_set_model takes");
+
+// Thread per pair of the piece's band rows: band[j W + o] = scale r(j, j + o + 1), 0 outside j's window and where r is NaN
+__global__ __launch_bounds__(LD_TPB) void k_ss_band(const unsigned long long* __restrict__ acc, const unsigned long long* __restrict__ counts,
+                                                    const double* __restrict__ mave, const double* __restrict__ mstd, const uint32_t* __restrict__ ahead,
+                                                    uint32_t n_local, uint32_t N, uint32_t W, uint32_t p0, uint32_t pc, double scale,
+                                                    double* __restrict__ band)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * LD_TPB + threadIdx.x;
+    if (k >= (uint64_t)pc * W) return;
+    const uint32_t j = p0 + (uint32_t)(k / W), o = (uint32_t)(k % W);
+    double v = 0.0;
+    if (o < ahead[j]) { // q = j + o + 1 <= j + ahead[j] < M
+        long long G, Bjq, Bqj, Dc;
+        const double r = ld_pair_r(acc + 4 * k, counts, mave, mstd, j, j + o + 1u, n_local, N, G, Bjq, Bqj, Dc);
+        if (r == r) v = scale * r;
+    }
+    band[(uint64_t)j * W + o] = v;
+}
+
+// The generator of the sweep's workgroup: two blocks of untempered words in LDS, the current one at `base`.  Every thread holds the
+// same idx and calls next() at the same places, so the barriers of a refill are met by all.
+struct SsGen {
+    uint32_t* mt;
+    uint32_t base, idx;
+    __device__ __forceinline__ void refill()
+    {
+        const uint32_t* cur = mt + base;
+        uint32_t* nxt = mt + (MT_N - base);
+        const int tid = (int)threadIdx.x;
+        for (int i = tid; i < 227; i += SS_TPB) nxt[i] = mt_mix(cur[i], cur[i + 1], cur[i + MT_M]);
+        __syncthreads();
+        for (int i = 227 + tid; i < 454; i += SS_TPB) nxt[i] = mt_mix(cur[i], cur[i + 1], nxt[i - 227]);
+        __syncthreads();
+        for (int i = 454 + tid; i < 623; i += SS_TPB) nxt[i] = mt_mix(cur[i], cur[i + 1], nxt[i - 227]);
+        __syncthreads();
+        if (tid == 0) nxt[623] = mt_mix(cur[623], nxt[0], nxt[396]);
+        __syncthreads();
+        base = MT_N - base;
+        idx = 0;
+    }
+    __device__ __forceinline__ uint32_t next()
+    {
+        if (idx >= (uint32_t)MT_N) refill();
+        return mt_temper(mt[base + idx++]);
+    }
+};
+
+struct SsSweepParams {
+    const int32_t* order;
+    const int32_t* groups;
+    const uint8_t* ada;
+    const uint32_t* ahead;
+    const uint32_t* back;
+    const double* band;
+    double* c;
+    double* beta;
+    int32_t* comp;
+    double* acum;
+    const double* tables; // denom, logpi, hlog, sdk: G K each
+    uint32_t* mt;         // 624 words, in and out
+    ZigTables zig;
+    int32_t* cass;
+    SsResult* res;
+    uint32_t M, W, rng_idx;
+    int K, GK;
+    double dNm1, i_2sigE;
+};
+
+__global__ __launch_bounds__(SS_TPB) void k_ss_sweep(const SsSweepParams p)
+{
+    __shared__ uint32_t s_mt[2 * MT_N];
+    __shared__ double s_nx[129], s_ny[129];
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t i = tid; i < (uint32_t)MT_N; i += SS_TPB) s_mt[i] = p.mt[i];
+    for (uint32_t i = tid; i < 129u; i += SS_TPB) {
+        s_nx[i] = p.zig.nx[i];
+        s_ny[i] = p.zig.ny[i];
+    }
+    __syncthreads();
+    SsGen gen{s_mt, 0u, p.rng_idx};
+    const ZigTables zt{s_nx, s_ny, p.zig.ex, p.zig.ey};
+    const uint32_t M = p.M, W = p.W;
+    const int K = p.K;
+    const double* denom = p.tables;
+    const double* logpi = denom + p.GK;
+    const double* hlog = logpi + p.GK;
+    const double* sdk = hlog + p.GK;
+    double* const c = p.c;
+
+    unsigned long long nnz = 0;
+    uint32_t err = 0;
+    // the marker of this position (values loaded), the next one (index loaded)
+    uint32_t j = (uint32_t)p.order[0];
+    double cj = c[j], bold = p.beta[j];
+    int g = p.groups[j];
+    uint32_t ada = p.ada[j], ah = p.ahead[j], bk = p.back[j];
+    uint32_t jn = M > 1u ? (uint32_t)p.order[1] : 0u;
+
+    for (uint32_t pos = 0; pos < M; ++pos) {
+        // ahead: the next marker's values, the index of the one after it
+        const bool more = pos + 1u < M;
+        double cn = 0.0, bn = 0.0;
+        int gn = 0;
+        uint32_t adan = 0, ahn = 0, bkn = 0, jnn = 0;
+        if (more) {
+            cn = c[jn];
+            bn = p.beta[jn];
+            gn = p.groups[jn];
+            adan = p.ada[jn];
+            ahn = p.ahead[jn];
+            bkn = p.back[jn];
+            if (pos + 2u < M) jnn = (uint32_t)p.order[pos + 2u];
+        }
+
+        double bnew = 0.0, ac = 1.0;
+        if (ada) {
+            int k = 0;
+            const int o = g * K;
+            if (ss_marker_draw(cj + bold * p.dNm1, K, denom + o, logpi + o, hlog + o, sdk + o, p.i_2sigE, gen, zt, bnew, k, ac)) {
+                err = pos + 1u;
+                break; // (uniform)
+            }
+            if (tid == 0) {
+                p.cass[o + k] += 1;
+                p.comp[j] = k;
+            }
+        }
+        if (tid == 0) {
+            p.beta[j] = bnew;
+            p.acum[j] = ac;
+        }
+        const double delta = bold - bnew;
+        if (delta != 0.0) { // (uniform)
+            __syncthreads(); // every wave has read c_j and what it loaded ahead
+            const double* row = p.band + (uint64_t)j * W;
+            const uint32_t far = ah > bk ? ah : bk;
+            for (uint32_t d = tid + 1u; d <= far; d += SS_TPB) {
+                if (d <= ah) c[j + d] += delta * row[d - 1u];
+                if (d <= bk) {
+                    const uint32_t k = j - d;
+                    if (p.ahead[k] >= d) c[k] += delta * p.band[(uint64_t)k * W + (d - 1u)];
+                }
+            }
+            if (tid == 0) c[j] += delta * p.dNm1;
+            ++nnz;
+            __syncthreads(); // the window's c is written
+            if (more) cn = c[jn]; // (it may lie in that window)
+        }
+        j = jn;
+        cj = cn;
+        bold = bn;
+        g = gn;
+        ada = adan;
+        ah = ahn;
+        bk = bkn;
+        jn = jnn;
+    }
+
+    __syncthreads();
+    for (uint32_t i = tid; i < (uint32_t)MT_N; i += SS_TPB) p.mt[i] = s_mt[gen.base + i];
+    if (tid == 0) {
+        p.res->nnz = nnz;
+        p.res->rng_idx = gen.idx;
+        p.res->err = err;
+    }
+}
+
+// One wave: the two sums in marker order over the non-zero effects
+__global__ __launch_bounds__(64) void k_ss_sums(const double* __restrict__ beta, const double* __restrict__ xty, const double* __restrict__ c, uint32_t M,
+                                                SsResult* __restrict__ res)
+{
+    const uint32_t lane = threadIdx.x;
+    double sb = 0.0, sc = 0.0;
+    for (uint32_t base = 0; base < M; base += 64u) {
+        const uint32_t i = base + lane;
+        const double b = i < M ? beta[i] : 0.0;
+        double pb = 0.0, pc = 0.0;
+        if (b != 0.0) {
+            pb = b * xty[i];
+            pc = b * c[i];
+        }
+        for (unsigned long long m = __ballot(b != 0.0); m; m &= m - 1ull) { // (uniform)
+            const int l = (int)__builtin_ctzll(m);
+            sb += __shfl(pb, l);
+            sc += __shfl(pc, l);
+        }
+    }
+    if (lane == 0) {
+        res->sums[0] = sb;
+        res->sums[1] = sc;
+    }
+}
+
+SsState* ss_of(hgibbs_ctx* h, const char* who)
+{
+    if (!h) {
+        fail("%s: null handle", who);
+        return nullptr;
+    }
+    if (!h->ss) {
+        fail("%s: no summary-statistics state on this handle (hgibbs_ss_begin first)", who);
+        return nullptr;
+    }
+    if (!h->bed || h->ss->M != h->M) {
+        fail("%s: the genotypes were replaced after hgibbs_ss_begin", who);
+        return nullptr;
+    }
+    return h->ss.get();
+}
+
+} // namespace
+
+extern "C" int hgibbs_ss_begin(hgibbs_t h, double n_eff, uint32_t W, const uint32_t* ahead, const double* xty)
+{
+    const char* who = "hgibbs_ss_begin";
+    if (ld_band_check(h, who, W, nullptr)) return 1;
+    if (!(std::isfinite(n_eff) && n_eff >= 2.0)) return fail("%s: n_eff = %g, must be a finite number >= 2", who, n_eff);
+    if (!xty) return fail("%s: null xty", who);
+    const uint32_t M = h->M;
+    for (uint32_t j = 0; j < M; ++j)
+        if (!std::isfinite(xty[j])) return fail("%s: xty[%u] is not finite", who, j);
+    std::vector<uint32_t> ah;
+    if (ld_ahead(who, M, W, ahead, ah)) return 1;
+    std::vector<uint32_t> back(M);
+    ss_back(M, ah.data(), back.data());
+    HIP_TRY(hipSetDevice(h->device));
+    if (compute_stats(h)) return 1;
+
+    const uint32_t piece = ld_piece_rows(W, 0, M);
+    const size_t nb = (size_t)M * W, np = (size_t)piece * W;
+    if (need_device_memory(nb * 8 + np * 32 + (size_t)M * 32 + ld_flag_count(M),
+                           "%s: the band of %u x %u doubles (%.1f MiB) and the sums of a piece of %u band rows (%.1f MiB)", who, M, W, nb * 8 / 1048576.0,
+                           piece, np * 32 / 1048576.0))
+        return 1;
+    std::unique_ptr<SsState> s(new SsState());
+    s->n_eff = n_eff;
+    s->W = W;
+    s->M = M;
+    if (s->band.alloc(nb) || s->c.alloc(M) || s->xty.alloc(M) || s->ahead.alloc(M) || s->back.alloc(M) || s->order.alloc(M) || s->ada.alloc(M) ||
+        s->res.alloc(1))
+        return 1;
+    std::vector<double> mstd(M);
+    HIP_TRY(hipMemcpy(mstd.data(), h->mstd, (size_t)M * sizeof(double), hipMemcpyDeviceToHost));
+    s->ok.resize(M);
+    for (uint32_t j = 0; j < M; ++j) s->ok[j] = std::isfinite(mstd[j]) ? 1 : 0;
+    HIP_TRY(hipMemcpy(s->ahead, ah.data(), (size_t)M * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->back, back.data(), (size_t)M * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->xty, xty, (size_t)M * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->c, xty, (size_t)M * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(s->res, 0, sizeof(SsResult)));
+
+    LdBand band;
+    if (ld_band_open(h, W, piece, band)) return 1;
+    double ms = 0.0;
+    const double scale = n_eff - 1.0;
+    SsState* sp = s.get();
+    // the step of a piece: its band rows inside the products' lap
+    auto fill = [&](uint32_t p0, uint32_t pc, const unsigned long long* acc) -> int {
+        const uint64_t npc = (uint64_t)pc * W;
+        k_ss_band<<<(uint32_t)((npc + LD_TPB - 1) / LD_TPB), LD_TPB, 0, h->stream>>>(acc, h->counts, h->mave, h->mstd, sp->ahead, h->n_local, h->n_global, W, p0,
+                                                                                      pc, scale, sp->band);
+        HIP_TRY(hipGetLastError());
+        return lap_end(h, ms);
+    };
+    if (ld_band_pieces(h, band, 0, M, fill)) return 1;
+    HIP_TRY(hipMemsetAsync(h->beta, 0, (size_t)M * sizeof(double), h->stream));
+    HIP_TRY(hipMemsetAsync(h->comp, 0, (size_t)M * sizeof(int32_t), h->stream));
+    HIP_TRY(hipMemsetAsync(h->acum, 0, (size_t)M * sizeof(double), h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    s->band_ms = ms;
+    h->ss = std::move(s);
+    return 0;
+}
+
+extern "C" int hgibbs_ss_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const double* sigmaG_host, const double* estPi_host,
+                               const uint8_t* adaV_host, hgibbs_rng_state* rng, int32_t* cass_host, uint64_t* nnz_updates)
+{
+    const char* who = "hgibbs_ss_sweep";
+    SsState* s = ss_of(h, who);
+    if (!s) return 1;
+    if (h->G < 1) return fail("%s: model not set", who);
+    if (!order_host || !sigmaG_host || !estPi_host || !adaV_host || !rng || !cass_host) return fail("%s: null argument", who);
+    if (rng->idx > (uint32_t)MT_N) return fail("%s: rng idx %u > 624", who, rng->idx);
+    const uint32_t M = h->M;
+    const int G = h->G, K = h->K;
+    for (uint32_t i = 0; i < M; ++i)
+        if (order_host[i] < 0 || (uint32_t)order_host[i] >= M) return fail("%s: order[%u]=%d outside [0,%u)", who, i, order_host[i], M);
+    HIP_TRY(hipSetDevice(h->device));
+    s->sweep_ms = 0.0;
+
+    std::vector<double> tab((size_t)4 * G * K);
+    ss_tables(G, K, s->n_eff - 1.0, sigmaE, sigmaG_host, estPi_host, h->cVa.data(), h->cVaI.data(), tab.data());
+    s->ada_host.resize(M);
+    for (uint32_t j = 0; j < M; ++j) s->ada_host[j] = (uint8_t)(adaV_host[j] && s->ok[j]); // a marker without a finite sd is never adaptive
+    HIP_TRY(hipMemcpyAsync(h->tables, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(s->order, order_host, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(s->ada, s->ada_host.data(), (size_t)M, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->mt, rng->x, MT_N * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemsetAsync(h->cass, 0, (size_t)G * K * sizeof(int32_t), h->stream));
+
+    SsSweepParams p{};
+    p.order = s->order;
+    p.groups = h->groups;
+    p.ada = s->ada;
+    p.ahead = s->ahead;
+    p.back = s->back;
+    p.band = s->band;
+    p.c = s->c;
+    p.beta = h->beta;
+    p.comp = h->comp;
+    p.acum = h->acum;
+    p.tables = h->tables;
+    p.mt = h->mt;
+    p.zig = ZigTables{h->zig, h->zig + 129, h->zig + 258, h->zig + 515};
+    p.cass = h->cass;
+    p.res = s->res;
+    p.M = M;
+    p.W = s->W;
+    p.rng_idx = rng->idx;
+    p.K = K;
+    p.GK = G * K;
+    p.dNm1 = s->n_eff - 1.0;
+    p.i_2sigE = 1.0 / (2.0 * sigmaE);
+    double ms = 0.0;
+    if (lap_begin(h)) return 1;
+    k_ss_sweep<<<1, SS_TPB, 0, h->stream>>>(p);
+    HIP_TRY(hipGetLastError());
+    if (lap_end(h, ms)) return 1;
+    SsResult res{};
+    HIP_TRY(hipMemcpy(&res, s->res, sizeof res, hipMemcpyDeviceToHost));
+    if (res.err) return fail("%s: sweep position %u (marker %d): the component walk found no component (logL overflow)", who, res.err - 1u, order_host[res.err - 1u]);
+    HIP_TRY(hipMemcpy(rng->x, h->mt, MT_N * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(cass_host, h->cass, (size_t)G * K * sizeof(int32_t), hipMemcpyDeviceToHost));
+    rng->idx = res.rng_idx;
+    if (nnz_updates) *nnz_updates = res.nnz;
+    s->sweep_ms = ms;
+    return 0;
+}
+
+extern "C" int hgibbs_ss_state(hgibbs_t h, double* c_out, double* beta_b, double* beta_c)
+{
+    const char* who = "hgibbs_ss_state";
+    SsState* s = ss_of(h, who);
+    if (!s) return 1;
+    HIP_TRY(hipSetDevice(h->device));
+    if (beta_b || beta_c) {
+        k_ss_sums<<<1, 64, 0, h->stream>>>(h->beta, s->xty, s->c, h->M, s->res);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        SsResult res{};
+        HIP_TRY(hipMemcpy(&res, s->res, sizeof res, hipMemcpyDeviceToHost));
+        if (beta_b) *beta_b = res.sums[0];
+        if (beta_c) *beta_c = res.sums[1];
+    }
+    if (c_out) {
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        HIP_TRY(hipMemcpy(c_out, s->c, (size_t)h->M * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+extern "C" int hgibbs_ss_band_get(hgibbs_t h, uint32_t m0, uint32_t count, double* out)
+{
+    const char* who = "hgibbs_ss_band_get";
+    SsState* s = ss_of(h, who);
+    if (!s) return 1;
+    if ((uint64_t)m0 + count > h->M) return fail("%s: markers [%u, %llu) out of range (M = %u)", who, m0, (unsigned long long)m0 + count, h->M);
+    if (count == 0) return 0;
+    if (!out) return fail("%s: null output", who);
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(out, s->band + (size_t)m0 * s->W, (size_t)count * s->W * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int hgibbs_ss_end(hgibbs_t h)
+{
+    if (!h) return fail("hgibbs_ss_end: null handle");
+    if (h->ss) {
+        HIP_TRY(hipSetDevice(h->device));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    h->ss.reset();
+    return 0;
+}
+
+extern "C" int hgibbs_last_ss_ms(hgibbs_t h, double* band_ms, double* sweep_ms)
+{
+    if (!h || !band_ms || !sweep_ms) return fail("hgibbs_last_ss_ms: null argument");
+    *band_ms = h->ss ? h->ss->band_ms : 0.0;
+    *sweep_ms = h->ss ? h->ss->sweep_ms : 0.0;
+    return 0;
+}

@@ -18,6 +18,7 @@
 
 #include "../../include/hgibbs.h"
 #include "hg_kernels.h"
+#include "hg_ss_step.h"
 #include "hg_sweep.hip.h"
 #include "hg_resident.hip.h"
 
@@ -60,6 +61,7 @@ extern "C" void hgibbs_set_error_(const char* msg) { g_err = msg; }
 // ---------------------------------------------------------------------------
 struct BwState; // BayesW side of the handle (hg_bayesw.hip.h)
 struct SparseLoad; // a load from index lists between hgibbs_sparse_begin and hgibbs_sparse_end (hg_sparse.hip.h)
+struct SsState; // the summary-statistics sweep's side of the handle between hgibbs_ss_begin and hgibbs_ss_end (hg_sumstat.hip.h)
 
 // What belongs to one loaded problem: alloc_problem builds it whole and only then moves it into the handle; an abandoned sparse load
 // assigns an empty one
@@ -248,6 +250,7 @@ struct hgibbs_ctx : Problem {
     std::unique_ptr<SparseLoad> sp; // hgibbs_sparse_begin .. hgibbs_sparse_end: the image in the making (bed stays null until it is published)
     long long sparse_piece = 0;    // option sparse_piece: bytes of index buffers per piece of markers of hgibbs_sparse_get (0 = automatic)
     double sparse_ms[2] = {0, 0};  // device time of the last sparse load (begin .. end, every kernel) and of the last hgibbs_sparse_get
+    std::unique_ptr<SsState> ss;   // hgibbs_ss_begin .. hgibbs_ss_end: the band, c and b of the summary-statistics sweep
 };
 
 static int ensure_scratch(hgibbs_ctx* h, size_t n)
@@ -2104,25 +2107,10 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
     const uint32_t M = h->M;
     if (rng->idx > (uint32_t)MT_N) return fail("hgibbs_sweep: rng idx %u > 624", rng->idx);
 
-    // per-sweep hyper tables (the marker-independent factors of src/BayesRRm.cpp:1721-1723,1750,1875,1901)
-    const double dNm1 = (double)(h->n_global - 1);
+    // per-sweep hyper tables (the marker-independent factors of src/BayesRRm.cpp:1721-1723,1750,1875,1901): denom, log pi, the half
+    // logs and the draws' standard deviations, G*K each (ss_tables, hg_ss_step.h: the summary-statistics sweep takes the same four)
     std::vector<double> tab((size_t)4 * G * K, 0.0);
-    double* denom = tab.data();
-    double* logpi = denom + (size_t)G * K;
-    double* hlog = logpi + (size_t)G * K;
-    double* sdk = hlog + (size_t)G * K;
-    for (int g = 0; g < G; ++g) {
-        const double sigE_G = sigmaE / sigmaG_host[g];
-        const double sigG_E = sigmaG_host[g] / sigmaE;
-        for (int k = 0; k < K; ++k) {
-            logpi[g * K + k] = log(estPi_host[g * K + k]);
-            if (k >= 1) {
-                denom[g * K + k] = dNm1 + sigE_G * h->cVaI[g * K + k];
-                hlog[g * K + k] = 0.5 * log(sigG_E * dNm1 * h->cVa[g * K + k] + 1.0);
-                sdk[g * K + k] = sqrt(sigmaE / denom[g * K + k]);
-            }
-        }
-    }
+    ss_tables(G, K, (double)(h->n_global - 1), sigmaE, sigmaG_host, estPi_host, h->cVa.data(), h->cVaI.data(), tab.data());
     // order and adaV travel through pinned staging in the handle; adaV only when it differs from what the device holds (it changes
     // when a group is switched off, and the caller owns the pointer: compared, not assumed)
     const size_t io_words = (size_t)MT_N + (size_t)G * K + 1;
@@ -2219,6 +2207,7 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
 #include "hg_ld.hip.h"
 #include "hg_ldscore.hip.h"
 #include "hg_ldmask.hip.h"
+#include "hg_sumstat.hip.h"
 #include "hg_mdots.hip.h"
 #include "hg_mclass.hip.h"
 #include "hg_sgram.hip.h"
@@ -2232,4 +2221,4 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
 #include "hg_grmsums.hip.h"
 #include "hg_sparse.hip.h"
 
-hgibbs_ctx::~hgibbs_ctx() = default; // BwState and SparseLoad are complete here
+hgibbs_ctx::~hgibbs_ctx() = default; // BwState, SparseLoad and SsState are complete here

@@ -105,6 +105,12 @@
 // phenotype file is read line by line), and with it only .fam/.bim are taken from it.  `--bed-to-sparse --bfile X [--sparse-dir D
 // --sparse-basename B]` writes those files from the whole X.bed and samples nothing.
 //
+// `--sumstats FILE [--sumstats-window W | --sumstats-window-kb KB] [--sumstats-n N]` on a bayesMPI command line samples the same
+// mixture model from a table of per-marker effects (SNP A1 A2 BETA SE N, as --assoc writes them) and the LD band of the loaded panel
+// (--bfile, or the sparse pair; --pheno is optional and only selects rows): .csv, .bet, .cpn and .acu in the chain's formats, so
+// --predict-bfile and --pve read them.  Not covered: an LD band from a file or another cohort, covariates,
+// BayesW, checkpoint and restart, several processes, GCTB's formats; parity with GCTB's SBayesR has not been run.
+//
 // Not reproduced (out of scope for the hot path): the mixed
 // in-memory representation (--threshold-fnz), --sparse-sync/--bed-sync, --check-RAM,
 // marker-block files, bayesFH, marker-sharded MPI, the .lst/tarball.
@@ -193,6 +199,9 @@ struct Options { // src/options.hpp:20-138 (subset that reaches bayesMPI)
     std::string sparseDir, sparseBsn;                // --sparse-dir D --sparse-basename B: hydra's sparse genotype files D/B.*
     bool bedToSparse = false, preferBed = false;     // --bed-to-sparse: write them from --bfile; --read-from-bed-file: read the BED though the pair is given
     bool blocksPerRankGiven = false;                 // --blocks-per-rank n: hydra's marker-sharded layout, no meaning here
+    bool sumstats = false, sumstatsWindowGiven = false, sumstatsKbGiven = false, sumstatsNGiven = false; // --sumstats FILE; which --sumstats-* were given
+    std::string sumstatsFile, sumstatsWindow, sumstatsKb, sumstatsN; // --sumstats-window W, --sumstats-window-kb KB, --sumstats-n N as given (checked before the device)
+    bool saveGiven = false, ignoreXfilesGiven = false; // --save, --ignore-xfiles on the command line (--sumstats takes no checkpoint option)
     int batch = 0, cpg = 0; // tuning knobs of this build (not hydra's)
 };
 
@@ -293,7 +302,10 @@ Options parse(int argc, const char* argv[])
             o.seed = (unsigned)std::atoi(need(i));
             o.seedGiven = true;
         } else if (a == "--thin") o.thin = (unsigned)std::atoi(need(i));
-        else if (a == "--save") o.save = (unsigned)std::atoi(need(i));
+        else if (a == "--save") {
+            o.save = (unsigned)std::atoi(need(i));
+            o.saveGiven = true;
+        }
         else if (a == "--S") {
             o.S.clear();
             for (const std::string& t : tokens(need(i), " ,")) o.S.push_back(std::stod(t));
@@ -307,7 +319,22 @@ Options parse(int argc, const char* argv[])
         } else if (a == "--failure") o.failureFile = need(i);    // options.cpp:183-186
         else if (a == "--quad_points") o.quad_points = need(i); // options.cpp:188-191
         else if (a == "--restart") o.restart = true;          // options.cpp:63-65
-        else if (a == "--ignore-xfiles") o.useXfilesInRestart = false; // options.cpp:67-69
+        else if (a == "--ignore-xfiles") {                              // options.cpp:67-69
+            o.useXfilesInRestart = false;
+            o.ignoreXfilesGiven = true;
+        } else if (a == "--sumstats") {
+            o.sumstatsFile = need(i);
+            o.sumstats = true;
+        } else if (a == "--sumstats-window") {
+            o.sumstatsWindow = need(i);
+            o.sumstatsWindowGiven = true;
+        } else if (a == "--sumstats-window-kb") {
+            o.sumstatsKb = need(i);
+            o.sumstatsKbGiven = true;
+        } else if (a == "--sumstats-n") {
+            o.sumstatsN = need(i);
+            o.sumstatsNGiven = true;
+        }
         else if (a == "--predict-bfile") o.predictBfile = need(i);
         else if (a == "--predict-out") o.predictOut = need(i);
         else if (a == "--predict-dry-run") o.predictDryRun = true;
@@ -2773,8 +2800,9 @@ struct LdWindow {
 };
 
 LdWindow ld_window(const std::string& flag, const char* op, const BimRows& bim, const std::string& bimp, unsigned M, bool bySnps, long wsnps,
-                   long long maxbp)
+                   long long maxbp, const std::string& snpsOpt = "")
 {
+    const std::string bySnpsOpt = snpsOpt.empty() ? flag + "-snps" : snpsOpt; // the option that gives the window in markers
     auto marker = [&](unsigned j) { return bim.id[j] + " (row " + std::to_string(j + 1) + ")"; };
     std::map<std::string, int> chroms;
     for (unsigned j = 0; j < M; ++j) {
@@ -2784,7 +2812,7 @@ LdWindow ld_window(const std::string& flag, const char* op, const BimRows& bim, 
                       " after another chromosome: " + flag + " needs every chromosome as one contiguous run");
         } else if (!bySnps && bim.bp[j] < bim.bp[j - 1])
             fatal("FATAL  : " + bimp + ": bp decreases at marker " + marker(j) + " inside chromosome " + bim.chr[j] +
-                  ": with a kb window the markers of a chromosome must be in bp order (the window must be an index interval; " + flag + "-snps takes any order)");
+                  ": with a kb window the markers of a chromosome must be in bp order (the window must be an index interval; " + bySnpsOpt + " takes any order)");
     }
     LdWindow w;
     w.ahead.assign(M, 0);
@@ -3616,6 +3644,202 @@ int run_epistasis(const Options& opt, const Cohort& co, const std::vector<double
     return 0;
 }
 
+// ---- --sumstats: BayesR from a table of per-marker effects and the panel's LD band ----
+// The table of --sumstats matched to the .bim by id: b_j = x_j'y on the chain's scale (xty), who takes part (use), and what was counted
+struct SumstatTable {
+    std::vector<double> xty;
+    std::vector<uint8_t> use;
+    double n_eff = 0.0;
+    unsigned rows = 0, matched = 0, swapped = 0, unknown = 0, allele = 0, unusable = 0;
+};
+
+SumstatTable read_sumstats(const std::string& path, const BimRows& bim, unsigned M, const std::string& bimp, bool nGiven, double nOpt)
+{
+    std::ifstream in(path);
+    if (!in) fatal("FATAL  : --sumstats: can not open the file [" + path + "] to read.");
+    std::string line;
+    if (!std::getline(in, line)) fatal("FATAL  : --sumstats: " + path + " has no header line");
+    const std::vector<std::string> head = tokens(line, " \t\r");
+    const char* const want[6] = {"SNP", "A1", "A2", "BETA", "SE", "N"};
+    size_t col[6], last = 0;
+    for (int w = 0; w < 6; ++w) {
+        col[w] = head.size();
+        for (size_t c = 0; c < head.size(); ++c)
+            if (head[c] == want[w] && col[w] == head.size()) col[w] = c;
+        if (col[w] == head.size())
+            fatal("FATAL  : --sumstats: " + path + " has no column " + want[w] + " in its header line (it needs SNP A1 A2 BETA SE N, as --assoc writes them)");
+        last = std::max(last, col[w]);
+    }
+    std::map<std::string, unsigned> at;
+    for (unsigned j = 0; j < M; ++j)
+        if (!at.emplace(bim.id[j], j).second) fatal("FATAL  : " + bimp + " lists SNP id " + bim.id[j] + " twice: --sumstats matches markers by id");
+    SumstatTable t;
+    t.xty.assign(M, 0.0);
+    t.use.assign(M, 0);
+    std::vector<double> z(M, 0.0), nj(M, 0.0), ns;
+    std::map<std::string, unsigned> seen; // id -> line
+    for (unsigned ln = 2; std::getline(in, line); ++ln) {
+        const std::vector<std::string> tok = tokens(line, " \t\r");
+        if (tok.empty()) continue;
+        if (tok.size() <= last)
+            fatal("FATAL  : --sumstats: " + path + " line " + std::to_string(ln) + " has " + std::to_string(tok.size()) + " columns, the header names " + std::to_string(head.size()));
+        ++t.rows;
+        const auto first = seen.emplace(tok[col[0]], ln);
+        if (!first.second)
+            fatal("FATAL  : --sumstats: " + path + " line " + std::to_string(ln) + ": SNP id " + tok[col[0]] + " was already on line " + std::to_string(first.first->second) + ": one row per marker");
+        const auto hit = at.find(tok[col[0]]);
+        if (hit == at.end()) {
+            ++t.unknown;
+            continue;
+        }
+        const unsigned j = hit->second;
+        double sign = 1.0;
+        if (tok[col[1]] == bim.a1[j] && tok[col[2]] == bim.a2[j]) sign = 1.0;
+        else if (tok[col[1]] == bim.a2[j] && tok[col[2]] == bim.a1[j]) sign = -1.0; // the table counts the other allele
+        else {
+            ++t.allele;
+            continue;
+        }
+        double b = 0.0, se = 0.0, n = 0.0;
+        if (!whole_num(tok[col[3]], b) || !whole_num(tok[col[4]], se) || !whole_num(tok[col[5]], n) || !std::isfinite(b) || !std::isfinite(se) || !std::isfinite(n) ||
+            !(se > 0.0) || !(n > 0.0)) { // NA, nan, a non-positive SE or N
+            ++t.unusable;
+            continue;
+        }
+        const double zz = b / se, den = n - 2.0 + zz * zz;
+        if (!std::isfinite(zz) || !(den > 0.0)) {
+            ++t.unusable;
+            continue;
+        }
+        ++t.matched;
+        t.swapped += sign < 0.0 ? 1u : 0u;
+        t.use[j] = 1;
+        z[j] = sign * zz;
+        nj[j] = n;
+        ns.push_back(n);
+    }
+    if (t.matched == 0) fatal("FATAL  : --sumstats: no row of " + path + " matches a marker of " + bimp + " (by SNP id and alleles) with usable BETA, SE and N");
+    if (nGiven) t.n_eff = nOpt;
+    else { // the median N of the matched rows (the mean of the two middle ones)
+        std::sort(ns.begin(), ns.end());
+        t.n_eff = ns.size() % 2 ? ns[ns.size() / 2] : 0.5 * (ns[ns.size() / 2 - 1] + ns[ns.size() / 2]);
+    }
+    if (!(t.n_eff >= 2.0)) fatal("FATAL  : --sumstats: n_eff = " + std::to_string(t.n_eff) + ": the sample size must be at least 2 (--sumstats-n sets it)");
+    // the standardised effect z / sqrt(N_j - 2 + z^2) is x_j'y / (n - 1) for a y with y'y = n - 1
+    for (unsigned j = 0; j < M; ++j)
+        if (t.use[j]) t.xty[j] = (t.n_eff - 1.0) * (z[j] / std::sqrt(nj[j] - 2.0 + z[j] * z[j]));
+    return t;
+}
+
+int run_sumstats(const Options& opt, const Cohort& co, const std::vector<int32_t>& groups, const std::vector<double>& mS_flat, int G, int K)
+{
+    const std::string base = opt.mcmcOutDir + "/" + opt.mcmcOutNam;
+    const std::string bimp = opt.bedFile + ".bim";
+    const unsigned M = co.Mtot;
+    const BimRows bim = read_bim(bimp, M);
+
+    // the window: kilobases (1000 unless markers are asked for), an index interval per chromosome
+    const bool bySnps = opt.sumstatsWindowGiven;
+    long wsnps = 0;
+    if (bySnps) whole_int(opt.sumstatsWindow, wsnps);
+    const long long maxbp = (long long)std::llround(1000.0 * num_or(opt.sumstatsKb, 1000.0));
+    const LdWindow win = ld_window("--sumstats", "hgibbs_ss_begin", bim, bimp, M, bySnps, wsnps, maxbp, "--sumstats-window");
+    const uint32_t W = std::max(1u, win.widest);
+
+    double nOpt = 0.0;
+    if (opt.sumstatsNGiven) whole_num(opt.sumstatsN, nOpt);
+    SumstatTable tab = read_sumstats(opt.sumstatsFile, bim, M, bimp, opt.sumstatsNGiven, nOpt);
+    std::printf("SUMSTAT: %u rows read from %s, %u matched to the .bim (%u with swapped alleles, sign flipped), %u ids not in it, %u with another allele pair, "
+                "%u without usable BETA, SE and N; n_eff %.12g (%s); window %s, %llu pairs in the window, widest window %u markers ahead\n",
+                tab.rows, opt.sumstatsFile.c_str(), tab.matched, tab.swapped, tab.unknown, tab.allele, tab.unusable, tab.n_eff,
+                opt.sumstatsNGiven ? "--sumstats-n" : "the median N of the matched rows", win.what.c_str(), win.npairs, win.widest);
+    std::fflush(stdout);
+
+    std::vector<uint8_t> bed = read_training(opt.bedFile, co.numInds, M);
+    make_out_dir(opt);
+    hgibbs_t dev = open_training(co, bed);
+    std::vector<double> mstd(M);
+    hg_check(hgibbs_marker_stats(dev, nullptr, mstd.data(), nullptr, nullptr, nullptr), "hgibbs_marker_stats");
+    unsigned nosd = 0, used = 0;
+    for (unsigned j = 0; j < M; ++j) {
+        if (tab.use[j] && !std::isfinite(mstd[j])) {
+            tab.use[j] = 0;
+            tab.xty[j] = 0.0;
+            ++nosd;
+        }
+        used += tab.use[j];
+    }
+    if (used == 0) fatal("FATAL  : --sumstats: every matched marker lacks a finite standard deviation in the panel");
+
+    hydra_model_desc md{};
+    md.seed = opt.seed;
+    md.shuffle = opt.shuffleMarkers;
+    md.G = G;
+    md.K = K;
+    md.groups = groups.empty() ? nullptr : groups.data();
+    md.mS = mS_flat.data();
+    hydra_ss_chain_t chain = nullptr;
+    hg_check(hydra_ss_chain_create(dev, &md, tab.n_eff, W, win.ahead.data(), tab.xty.data(), tab.use.data(), &chain), "hydra_ss_chain_create");
+    double band_ms = 0.0, sweep_ms = 0.0;
+    hg_check(hgibbs_last_ss_ms(dev, &band_ms, &sweep_ms), "hgibbs_last_ss_ms");
+
+    // the chain's files and formats (:1302-1309, :2736-2794)
+    FILE* outf = open_out(base + ".csv", "wb+");
+    FILE* betf = open_out(base + ".bet", "wb+");
+    FILE* cpnf = open_out(base + ".cpn", "wb+");
+    FILE* acuf = open_out(base + ".acu", "wb+");
+    for (FILE* f : {betf, cpnf, acuf}) pwrite_at(f, 0, &M, sizeof(unsigned));
+    std::vector<double> beta(M), acum(M), sigmaG(G);
+    std::vector<int32_t> comp(M), m0(G);
+    std::vector<char> buff(50000);
+    unsigned n_thinned_saved = 0, sweeps = 0;
+    double sweep_total_ms = 0.0;
+    for (unsigned iteration = 0; iteration < opt.chainLength; ++iteration) {
+        const double t0 = now_s();
+        hg_check(hydra_ss_chain_iterate(chain), "hydra_ss_chain_iterate");
+        const double t1 = now_s();
+        hg_check(hgibbs_last_ss_ms(dev, &band_ms, &sweep_ms), "hgibbs_last_ss_ms");
+        sweep_total_ms += sweep_ms;
+        ++sweeps;
+        double sigmaE = 0, mu = 0;
+        hydra_ss_chain_state(chain, &sigmaE, &mu, sigmaG.data(), nullptr, m0.data(), nullptr, nullptr);
+        double sg = 0;
+        long m0s = 0;
+        for (int g = 0; g < G; ++g) {
+            sg += sigmaG[g];
+            m0s += m0[g];
+        }
+        std::printf("RESULT : it %4d: proc = %9.3f s, sweep = %9.3f ms on the device, sigmaG = %15.10f, sigmaE = %15.10f, mu = %15.10f, m0 = %10ld\n", iteration, t1 - t0,
+                    sweep_ms, sg, sigmaE, mu, m0s);
+        std::fflush(stdout);
+        if (iteration % opt.thin == 0) {
+            hg_check(hydra_ss_chain_effects(chain, beta.data(), comp.data(), acum.data(), nullptr), "hydra_ss_chain_effects");
+            const int len = hydra_ss_chain_csv_line(chain, iteration, buff.data(), buff.size());
+            pwrite_at(outf, (long)n_thinned_saved * len, buff.data(), (size_t)len);
+            long off = sizeof(unsigned) + (long)n_thinned_saved * (sizeof(unsigned) + (long)M * sizeof(double));
+            pwrite_at(betf, off, &iteration, sizeof(unsigned));
+            pwrite_at(acuf, off, &iteration, sizeof(unsigned));
+            pwrite_at(betf, off + sizeof(unsigned), beta.data(), (size_t)M * sizeof(double));
+            pwrite_at(acuf, off + sizeof(unsigned), acum.data(), (size_t)M * sizeof(double));
+            off = sizeof(unsigned) + (long)n_thinned_saved * (sizeof(unsigned) + (long)M * sizeof(int));
+            pwrite_at(cpnf, off, &iteration, sizeof(unsigned));
+            pwrite_at(cpnf, off + sizeof(unsigned), comp.data(), (size_t)M * sizeof(int));
+            n_thinned_saved += 1;
+        }
+    }
+    close_out(outf, base + ".csv");
+    close_out(betf, base + ".bet");
+    close_out(cpnf, base + ".cpn");
+    close_out(acuf, base + ".acu");
+    hydra_ss_chain_destroy(chain);
+    hgibbs_destroy(dev);
+    std::printf("SUMSTAT: %u markers used, %u left out (%u not in the table, %u with another allele pair, %u without usable BETA, SE and N, %u without a finite sd in the panel), "
+                "n_eff %.12g, band %u x %u doubles = %.1f MiB of device memory (built in %.3f ms), %.3f ms per sweep on the device over %u sweeps, wrote %s.{csv,bet,cpn,acu}\n",
+                used, M - used, M - tab.matched - tab.allele - tab.unusable, tab.allele, tab.unusable, nosd, tab.n_eff, M, W, (double)M * W * 8.0 / 1048576.0, band_ms,
+                sweeps ? sweep_total_ms / sweeps : 0.0, sweeps, base.c_str());
+    return 0;
+}
+
 // ---- the analysis modes -------------------------------------------------------
 // An analysis mode is an option that, appended to a bayesMPI command line, samples nothing and runs one analysis on the chain's rows
 // (run_predict .. run_qc above).  What the modes share is refused in one place, from one row per mode.
@@ -3853,6 +4077,38 @@ void check_modes(const Options& opt, int nranks)
     }
 }
 
+// every refusal of --sumstats, before anything is read
+void check_sumstats(const Options& opt, int nranks)
+{
+    if (!opt.sumstats) {
+        if (const char* o = first_given({{"--sumstats-window", opt.sumstatsWindowGiven}, {"--sumstats-window-kb", opt.sumstatsKbGiven}, {"--sumstats-n", opt.sumstatsNGiven}}))
+            fatal(std::string("FATAL  : ") + o + " needs --sumstats");
+        return;
+    }
+    if (opt.bayesType == "bayesWMPI") fatal("FATAL  : --sumstats takes a bayesMPI command line, not --mpibayes bayesWMPI");
+    const std::pair<const char*, bool> modes[] = {
+        {"--predict-bfile", !opt.predictBfile.empty()}, {"--ld-window", opt.ldGiven}, {"--assoc", opt.assoc}, {"--king", opt.king}, {"--pca", opt.pca}, {"--pve", opt.pve},
+        {"--grm", opt.grm}, {"--ld-score", opt.ldScore}, {"--clump", opt.clump}, {"--ld-prune", opt.ldPrune}, {"--he", opt.he}, {"--qc", opt.qc}, {"--homozyg", opt.homozyg},
+        {"--epistasis", opt.epistasis}};
+    for (const auto& m : modes)
+        if (m.second) fatal(std::string("FATAL  : --sumstats cannot be combined with ") + m.first + ": it samples a chain, the analysis modes sample nothing");
+    if (opt.covariates) fatal("FATAL  : --sumstats cannot be combined with --covariates: summary statistics carry no individual-level covariates");
+    if (nranks > 1) fatal("FATAL  : --sumstats runs on one process (WORLD_SIZE = " + std::to_string(nranks) + ")");
+    if (const char* o = first_given({{"--restart", opt.restart}, {"--save", opt.saveGiven}, {"--ignore-xfiles", opt.ignoreXfilesGiven}}))
+        fatal(std::string("FATAL  : --sumstats cannot be combined with ") + o + ": checkpoint and restart are not built for it");
+    if (opt.bedFile.empty())
+        fatal("FATAL  : --sumstats needs --bfile: its .fam and .bim name the panel's rows and markers (the genotypes may still come from --sparse-dir/--sparse-basename)");
+    if (opt.sumstatsWindowGiven && opt.sumstatsKbGiven) fatal("FATAL  : --sumstats-window-kb cannot be combined with --sumstats-window: one way to define the window");
+    long w = 0;
+    double t = 0.0;
+    if (opt.sumstatsKbGiven && (!whole_num(opt.sumstatsKb, t) || !std::isfinite(t) || t < 0.0))
+        fatal("FATAL  : --sumstats-window-kb " + opt.sumstatsKb + ": the window must be a finite number of kilobases >= 0");
+    if (opt.sumstatsWindowGiven && (!whole_int(opt.sumstatsWindow, w) || w < 1 || w > 4096))
+        fatal("FATAL  : --sumstats-window " + opt.sumstatsWindow + ": the window must be an integer from 1 to 4096 markers (the widest hgibbs_ss_begin takes)");
+    if (opt.sumstatsNGiven && (!whole_num(opt.sumstatsN, t) || !std::isfinite(t) || !(t >= 2.0)))
+        fatal("FATAL  : --sumstats-n " + opt.sumstatsN + ": the sample size must be a finite number >= 2");
+}
+
 } // namespace
 
 int main(int argc, const char* argv[])
@@ -3880,6 +4136,7 @@ int main(int argc, const char* argv[])
         std::printf("WARNING: --sync-rate %d ignored: individuals are sharded, every marker sees the current residual\n", opt.syncRate);
 
     check_modes(opt, nranks);
+    check_sumstats(opt, nranks);
     if (opt.bayesType == "bayesWMPI") return run_bayesw(opt, rank, nranks, local_rank); // main.cpp:164-167
 
     // ---- inputs (main.cpp:69-70,88; BayesRRm.cpp:969-997) -------------------
@@ -3893,7 +4150,10 @@ int main(int argc, const char* argv[])
     std::vector<uint8_t> keep;
     std::vector<double> covX;
     int C = 0;
-    if (opt.covariates) read_phen_cov(opt.phenotypeFile, opt.covariatesFile, numInds, y, keep, covX, C); // main.cpp:80-83
+    if (opt.sumstats && opt.phenotypeFile.empty()) { // --pheno only selects the panel's rows there: without it every row is kept
+        y.assign(numInds, 0.0);
+        keep.assign(numInds, 1);
+    } else if (opt.covariates) read_phen_cov(opt.phenotypeFile, opt.covariatesFile, numInds, y, keep, covX, C); // main.cpp:80-83
     else if (haveBed) read_phen(opt.phenotypeFile, fam_ids, y, keep);
     else read_phen_lines(opt.phenotypeFile, numInds, y, keep);
     const unsigned numNAs = (unsigned)(numInds - y.size());
@@ -3949,6 +4209,7 @@ int main(int argc, const char* argv[])
     const int G = (int)mS.size(), K = (int)mS[0].size();
     std::vector<double> mS_flat;
     for (auto& r : mS) mS_flat.insert(mS_flat.end(), r.begin(), r.end());
+    if (opt.sumstats) return run_sumstats(opt, co, groups, mS_flat, G, K);
 
     // --thin/--save adjustment, BayesRRm.cpp:1058-1066
     if (opt.save < opt.thin) {

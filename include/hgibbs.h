@@ -437,6 +437,42 @@ int hgibbs_ld_greedy(uint32_t M, uint32_t W, const uint64_t* fwd, const uint64_t
 int hgibbs_ld_clump(hgibbs_t h, uint32_t W, const uint32_t* ahead, double t, const uint32_t* order, uint32_t norder,
                     const uint8_t* may_lead, int32_t* owner, uint64_t* npass);
 
+/* ---- the Gibbs sweep from summary statistics and the panel's LD band ---- */
+/* The chain's step with c_j = x_j'eps kept per marker instead of the residual per individual.  Inputs: n_eff; xty[j] = b_j = x_j'y
+ * for a y with y'y = n_eff - 1; and the symmetric band B_jk = (n_eff - 1) r_jk, r exactly hgibbs_ld's r of the loaded panel, for the pairs
+ * of hgibbs_ld_scores' window (ahead: M entries with ahead[j] <= W and j + ahead[j] < M, or NULL for min(W, M - 1 - j)); pairs outside the
+ * window count as 0, and so does every pair with a marker whose mstd is not finite (such a marker is never adaptive either).
+ *   begin    builds the band once on the device from the loaded image (M x W doubles, the `ahead` half only; it never crosses the bus),
+ *            sets c = xty and every effect, component and acum to 0.  n_eff need not be the panel's row count: r comes from the panel,
+ *            the scale from the summary statistics.  Refused by name: a null handle, no genotypes, several ranks, W outside 1..4096,
+ *            an `ahead` entry out of range, n_eff not finite or below 2, a null or non-finite xty, buffers that do not fit in free
+ *            device memory.  A second call replaces the state of the first.
+ *   sweep    hgibbs_sweep's signature and meaning, on the model of hgibbs_set_model.  Per marker j in the given order:
+ *            num = c_j + (n_eff - 1) beta_j; the reference's decision and draw; with delta = beta_old - beta_new != 0,
+ *            c_k += delta B_jk over j's window on both sides and c_j += delta (n_eff - 1).  The effects, components and acum live where
+ *            hgibbs_get_beta, hgibbs_set_beta, hgibbs_set_components and hgibbs_beta_sqnorm read and write them (hgibbs_set_beta changes
+ *            the effects alone: c stays as it is).  One launch, one workgroup; two runs from the same state give the same bits.
+ *   state    c (M doubles, may be NULL) and sum_j beta_j b_j, sum_j beta_j c_j (either may be NULL), each summed in marker order over the
+ *            non-zero effects on the device: a fixed order, bit-reproducible.
+ *   band_get the band rows [m0, m0 + count): count x W doubles, out[(j - m0) W + d - 1] = B_{j, j + d}, 0 for d > ahead[j].
+ *   end      frees the state (hgibbs_destroy does too).
+ *   last_ss_ms   device time of hgibbs_ss_begin's band (zeroing, products, scaling) and of the last hgibbs_ss_sweep's kernel. */
+int hgibbs_ss_begin(hgibbs_t h, double n_eff, uint32_t W, const uint32_t* ahead /* M or NULL */, const double* xty /* M */);
+int hgibbs_ss_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const double* sigmaG_host, const double* estPi_host,
+                    const uint8_t* adaV_host, hgibbs_rng_state* rng, int32_t* cass_host, uint64_t* nnz_updates);
+int hgibbs_ss_state(hgibbs_t h, double* c_out, double* beta_b, double* beta_c);
+int hgibbs_ss_band_get(hgibbs_t h, uint32_t m0, uint32_t count, double* out);
+int hgibbs_ss_end(hgibbs_t h);
+int hgibbs_last_ss_ms(hgibbs_t h, double* band_ms, double* sweep_ms);
+/* The same sweep on host arrays (host only: no handle, no device), the yardstick of the device engine: band is M x W in
+ * hgibbs_ss_band_get's layout (entries beyond ahead[j] are not read), c, beta, components and acum are the state (M each, updated in
+ * place), G, K, groups (M, or NULL for one group), cVa and cVaI are hgibbs_set_model's, the rest is hgibbs_ss_sweep's.  With a band that
+ * covers every pair and b = X'y this is the individual-level sweep: c_j stays x_j'eps. */
+int hgibbs_ss_sweep_host(uint32_t M, double n_eff, uint32_t W, const uint32_t* ahead, const double* band, double* c, double* beta,
+                         int32_t* components, double* acum, int G, int K, const int32_t* groups, const double* cVa, const double* cVaI,
+                         const int32_t* order, double sigmaE, const double* sigmaG, const double* estPi, const uint8_t* adaV,
+                         hgibbs_rng_state* rng, int32_t* cass, uint64_t* nnz_updates);
+
 /* ---- dots of the loaded markers against dense vectors */
 /* For markers j in [m0, m0 + count) of the loaded BED and K vectors u_k over this rank's n_local individuals:
  *   out[(j - m0)*K + k]           = x_j'u_k = mstd_j (P_jk - mave_j Q_jk)      (NaN where mstd_j is not finite)
@@ -832,6 +868,29 @@ int hydra_chain_state(hydra_chain_t c, double* sigmaE, double* mu, double* sigma
 /* the .csv line of src/BayesRRm.cpp:2742-2760 for the given iteration number */
 int hydra_chain_csv_line(hydra_chain_t c, uint32_t iteration, char* buf, size_t len);
 const int32_t* hydra_chain_order(hydra_chain_t c);
+
+/* ---- the same chain from summary statistics -------- */
+/* hydra_chain's initial values and hyper-parameter draws around hgibbs_ss_sweep: sigmaG ~ beta(1, 1) per group, sigmaE = y'y / n 0.5
+ * with y'y = n - 1, n = n_eff; mu ~ N(0, sigmaE / n); e_sqn = (y'y - sum_j beta_j (b_j + c_j)) + n mu^2.  No covariates.  An iteration
+ * whose e_sqn is not positive fails with a message that names the iteration and the value (a truncated band need not be positive
+ * definite); nothing is clamped.  `use` (M bytes or NULL): 0 = the marker is never adaptive.
+ *   create        on a handle that holds the panel: calls hgibbs_ss_begin (which refuses n_eff, W, ahead and xty by name) and
+ *                 hgibbs_set_model; the effects are read with hgibbs_get_beta or hydra_ss_chain_effects
+ *   create_host   host only, no device: the same iteration around hgibbs_ss_sweep_host with the caller's band (M x W) */
+typedef struct hydra_ss_chain* hydra_ss_chain_t;
+int hydra_ss_chain_create(hgibbs_t dev, const hydra_model_desc* model, double n_eff, uint32_t W, const uint32_t* ahead, const double* xty,
+                          const uint8_t* use, hydra_ss_chain_t* out);
+int hydra_ss_chain_create_host(uint32_t M, const hydra_model_desc* model, double n_eff, uint32_t W, const uint32_t* ahead, const double* band,
+                               const double* xty, const uint8_t* use, hydra_ss_chain_t* out);
+int hydra_ss_chain_destroy(hydra_ss_chain_t c);
+int hydra_ss_chain_iterate(hydra_ss_chain_t c);
+int hydra_ss_chain_state(hydra_ss_chain_t c, double* sigmaE, double* mu, double* sigmaG /*G*/, double* estPi /*G*K*/, int32_t* m0 /*G*/,
+                         int32_t* cass /*G*K*/, hgibbs_rng_state* rng);
+/* effects, components, acum and c (M each; any pointer may be NULL) */
+int hydra_ss_chain_effects(hydra_ss_chain_t c, double* beta, int32_t* components, double* acum, double* cvec);
+uint64_t hydra_ss_chain_last_nnz(hydra_ss_chain_t c);
+const int32_t* hydra_ss_chain_order(hydra_ss_chain_t c);
+int hydra_ss_chain_csv_line(hydra_ss_chain_t c, uint32_t iteration, char* buf, size_t len);
 
 /* ======================================================================== */
 /* BayesW: Weibull survival model (src/BayesW.cpp); individuals shard as above  */

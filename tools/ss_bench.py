@@ -1,0 +1,91 @@
+"""Sweep time of the summary-statistics engine (hgibbs_ss_sweep) on a synthetic panel made in HBM (hgibbs_synth_bed).
+
+For a panel of N rows x M markers and a window of W markers: the band's build time (hgibbs_ss_begin: hgibbs_ld's products and the
+scaling), then --iters iterations of hydra_ss_chain on synthetic summary statistics (noise of a GWAS of n_eff individuals plus a
+fraction of signals), each with the device time of its sweep kernel (hgibbs_last_ss_ms, HIP events), markers per second, microseconds
+per marker and the census of non-zero updates (markers whose effect changed: each costs two barriers and a pass over the window).
+Before the chain, one sweep with every marker fixed (adaV = 0, every effect 0: no draw, no update) times the walk alone, in shuffled
+and in marker order.  One JSON line per case; --out appends them to a file as well.  One invocation is one GPU step: run it under
+`timeout`.
+
+    python tools/ss_bench.py [--cases 10000x100000x128,20000x1000000x512] [--n-eff 4000000] [--signals 0.001] [--iters 6] [--out F]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from hydra_amd import capi  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cases", default="10000x100000x128,20000x1000000x512", help="NxMxW, comma-separated")
+    ap.add_argument("--n-eff", type=float, default=4000000.0,
+                    help="above M: independent synthetic markers carry no LD, so the noise of M markers must fit into y'y = n - 1")
+    ap.add_argument("--signals", type=float, default=0.001, help="fraction of markers with an effect")
+    ap.add_argument("--iters", type=int, default=6)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    out = open(args.out, "a") if args.out else None
+
+    def emit(rec):
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if out:
+            out.write(line + "\n")
+            out.flush()
+
+    for case in args.cases.split(","):
+        N, M, W = (int(x) for x in case.split("x"))
+        n = args.n_eff
+        rs = np.random.default_rng(7)
+        # b_j = x_j'y of a y with y'y = n - 1: sqrt(n - 1) times a standard normal under the null, plus (n - 1) beta_j for the signals
+        xty = np.sqrt(n - 1.0) * rs.standard_normal(M)
+        sig = rs.random(M) < args.signals
+        xty[sig] += (n - 1.0) * rs.normal(0.0, np.sqrt(0.5 / max(1, sig.sum())), int(sig.sum()))
+        dev = capi.Device(0)
+        dev.synth_bed(N, M, seed=5)
+        ch = capi.SsChain(dev, n, W, xty, seed=11)
+        band_ms = dev.last_ss_ms()[0]
+        rec = {"n_panel": N, "m": M, "W": W, "n_eff": n, "signals": int(sig.sum()), "band_mib": round(M * W * 8 / 2.0**20, 1), "band_ms": round(band_ms, 3)}
+
+        # the walk alone: nothing adaptive, every effect 0 (the first launch warms the code object up)
+        fixed = np.zeros(M, dtype=np.uint8)
+        sG, pi = np.array([0.5]), np.array([[0.5, 0.25, 0.15, 0.10]])
+        rng = capi.RngState()
+        rng.idx = 624
+        for name, order in (("warm", np.arange(M)), ("walk_marker_order", np.arange(M)), ("walk_shuffled", rs.permutation(M))):
+            _, nnz = dev.ss_sweep(order, 0.5, sG, pi, fixed, rng)
+            assert nnz == 0
+            if name != "warm":
+                ms = dev.last_ss_ms()[1]
+                rec[name + "_ms"] = round(ms, 3)
+                rec[name + "_us_per_marker"] = round(1e3 * ms / M, 4)
+
+        sweeps = []
+        for it in range(args.iters):
+            ch.iterate()
+            ms = dev.last_ss_ms()[1]
+            st = ch.state()
+            sweeps.append({"it": it, "sweep_ms": round(ms, 3), "markers_per_s": float("%.4g" % (M / (ms * 1e-3))), "us_per_marker": round(1e3 * ms / M, 4),
+                           "nnz_updates": ch.last_nnz(), "m0": int(st["m0"].sum()), "sigmaG": float("%.6g" % st["sigmaG"].sum()),
+                           "sigmaE": float("%.6g" % st["sigmaE"])})
+        rec["sweeps"] = sweeps
+        # two unknowns from the sweeps: time = M t_marker + nnz t_update (least squares over the iterations)
+        A = np.array([[M, s["nnz_updates"]] for s in sweeps], dtype=np.float64)
+        t = np.array([s["sweep_ms"] for s in sweeps])
+        if len(sweeps) >= 2 and np.linalg.matrix_rank(A) == 2:
+            sol = np.linalg.lstsq(A, t, rcond=None)[0]
+            rec["fit_us_per_marker"] = round(1e3 * sol[0], 4)
+            rec["fit_us_per_update"] = round(1e3 * sol[1], 4)
+        emit(rec)
+        del ch
+        dev.close()
+
+
+if __name__ == "__main__":
+    main()
