@@ -958,7 +958,8 @@ int run_bed_to_sparse(const Options& opt, int nranks, int local_rank)
 struct CsvRestart {
     unsigned iteration_to_restart_from = 0, first_thinned_iteration = 0, first_saved_iteration = 0;
     std::vector<double> sigmaG, pi;
-    double sigmaE = 0.0;
+    double sigmaE = 0.0;          // BayesR's
+    double mu = 0.0, alpha = 0.0; // BayesW's
 };
 
 // data.cpp:406-514: the last line whose iteration is a multiple of --save wins
@@ -1147,6 +1148,264 @@ void setup_ranks(hgibbs_t dev, const std::string& base, int rank, int nranks)
         }
 }
 
+// ---- what the samplers' command lines share (main for bayesMPI, run_bayesw, and run_sumstats from its chain down) ----
+// Each sampler keeps its own loop; these are the pieces of it that are the same, written once.
+
+// N and M before the phenotypes are read: the .fam/.bim of --bfile, or, on the sparse route (main.cpp:96-118), the options'
+struct Dims {
+    size_t numInds = 0, numSnps = 0;
+    std::vector<std::string> fam_ids;
+};
+
+Dims read_dims(const Options& opt)
+{
+    const bool haveBed = !opt.bedFile.empty();
+    if (!haveBed && opt.numberIndividuals == 0) fatal("FATAL  : opt.numberIndividuals is zero! Set it via --number-individuals in call.");
+    if (!haveBed && opt.numberMarkers == 0) fatal("FATAL  : opt.numberMarkers is zero! Set it via --number-markers in call.");
+    Dims d;
+    d.numInds = haveBed ? count_fam(opt.bedFile + ".fam", &d.fam_ids) : opt.numberIndividuals;
+    d.numSnps = haveBed ? count_bim(opt.bedFile + ".bim") : opt.numberMarkers;
+    return d;
+}
+
+// ... and the options against them, once the phenotypes are read; returns Mtot
+unsigned check_dims(const Options& opt, const Dims& d)
+{
+    if (opt.numberIndividuals == 0) fatal("FATAL  : opt.numberIndividuals is zero! Set it via --number-individuals in call.");
+    if (opt.numberMarkers == 0) fatal("FATAL  : opt.numberMarkers is zero! Set it via --number-markers in call.");
+    if (opt.numberIndividuals != d.numInds) fatal("FATAL  : --number-individuals does not match the .fam file");
+    const unsigned Mtot = opt.numberMarkers;
+    if (Mtot > d.numSnps) fatal("FATAL  : --number-markers exceeds the .bim file");
+    return Mtot;
+}
+
+// The groups and their mixtures from --groupIndexFile/--groupMixtureFile, or the one row of --S behind a zero
+struct Mixtures {
+    std::vector<int32_t> groups; // empty: one group
+    std::vector<double> mS_flat; // G x K
+    int G = 0, K = 0;
+};
+
+Mixtures read_mixtures(const Options& opt, unsigned Mtot, bool positiveS)
+{
+    Mixtures m;
+    std::vector<std::vector<double>> mS;
+    if (!opt.groupIndexFile.empty()) { // src/BayesW.cpp:773-776
+        m.groups = read_groups(opt.groupIndexFile);
+        mS = read_mS(opt.groupMixtureFile);
+        if (m.groups.size() < Mtot) fatal("FATAL  : group file covers fewer markers than --number-markers");
+        m.groups.resize(Mtot);
+    } else {
+        std::vector<double> row{0.0};
+        for (double v : opt.S) {
+            if (positiveS && v <= 0.0) fatal("FATAL  : mixture value can only be strictly positive");
+            row.push_back(v);
+        }
+        mS.push_back(row);
+    }
+    m.G = (int)mS.size();
+    m.K = (int)mS[0].size();
+    for (auto& r : mS) m.mS_flat.insert(m.mS_flat.end(), r.begin(), r.end());
+    return m;
+}
+
+// --save becomes a multiple of --thin (BayesRRm.cpp:1058-1066, BayesW.cpp:981-989).  BayesW says so on every rank and in one
+// line more than BayesR.
+void adjust_save(Options& opt, bool say, bool sayNotMultiple)
+{
+    if (opt.save < opt.thin) {
+        opt.save = opt.thin;
+        if (say) std::printf("WARNING: opt.save was lower that opt.thin ; opt.save reset to opt.thin (%d)\n", opt.thin);
+    }
+    if (opt.save % opt.thin != 0) {
+        if (say && sayNotMultiple) std::printf("WARNING: opt.save (= %d) was not a multiple of opt.thin (= %d)\n", opt.save, opt.thin);
+        opt.save = (opt.save / opt.thin) * opt.thin;
+        if (say) std::printf("         opt.save reset to %d, the closest multiple of opt.thin (%d)\n", opt.save, opt.thin);
+    }
+}
+
+// This rank's rows [lo, hi) of the Ntot kept ones: individuals are sharded in multiples of 4
+struct Shard {
+    unsigned lo = 0, hi = 0;
+    unsigned rows() const { return hi - lo; }
+};
+
+Shard shard_of(unsigned Ntot, int rank, int nranks)
+{
+    const unsigned per = ((Ntot + nranks - 1) / nranks + 3) / 4 * 4;
+    return {std::min(Ntot, rank * per), std::min(Ntot, (rank + 1) * per)};
+}
+
+// A sampler's handle: among its ranks, with this build's tuning knobs (cpg 0: BayesW has no column groups to size)
+hgibbs_t open_device(const Options& opt, const std::string& base, int rank, int nranks, int local_rank, int cpg)
+{
+    hgibbs_t dev = nullptr;
+    hg_check(hgibbs_create(local_rank, &dev), "hgibbs_create");
+    if (nranks > 1) setup_ranks(dev, base, rank, nranks);
+    if (opt.batch) hg_check(hgibbs_set_option(dev, "batch", opt.batch), "batch");
+    if (cpg) hg_check(hgibbs_set_option(dev, "cols_per_group", cpg), "cols_per_group");
+    return dev;
+}
+
+// Data::load_data_from_bed_file, data.cpp:671-739: this rank's shard of the training genotypes, and what it took
+void load_and_report(hgibbs_t dev, const Options& opt, size_t numInds, unsigned Mtot, const uint8_t* keep, const Shard& sh, unsigned Ntot, int rank)
+{
+    const double tl0 = now_s();
+    std::vector<uint8_t> bed = read_training(opt.bedFile, numInds, Mtot);
+    const size_t bytes = put_genotypes(dev, bed, numInds, Mtot, keep, sh.lo, sh.hi, Ntot);
+    std::printf("INFO   : rank %3d took %.3f seconds to load  %lu bytes  =>  BW = %7.3f GB/s\n", rank, now_s() - tl0, (unsigned long)bytes,
+                (double)bytes * 1e-9 / (now_s() - tl0));
+}
+
+// The output files of one run, opened truncated and closed together
+struct OutFiles {
+    std::vector<std::pair<FILE*, std::string>> files;
+    FILE* open(const std::string& p)
+    {
+        files.emplace_back(open_out(p, "wb+"), p);
+        return files.back().first;
+    }
+    void close(bool checked) // checked: a failing close is a short write on that file
+    {
+        for (auto& f : files)
+            if (checked) close_out(f.first, f.second);
+            else std::fclose(f.first);
+    }
+};
+
+// .bet/.acu/.cpn: the marker count at 0 (the caller's), then per thinned iteration (iteration, M elements)
+void write_thinned(FILE* f, unsigned n_thinned_saved, unsigned iteration, const void* v, unsigned M, size_t elem)
+{
+    const long off = sizeof(unsigned) + (long)n_thinned_saved * (sizeof(unsigned) + (long)M * elem);
+    pwrite_at(f, off, &iteration, sizeof(unsigned));
+    pwrite_at(f, off + sizeof(unsigned), v, (size_t)M * elem);
+}
+
+// .mus.<rank>: (iteration, mu) per thinned iteration
+void write_mus(FILE* f, unsigned n_thinned_saved, unsigned iteration, double mu)
+{
+    const long off = (long)n_thinned_saved * (sizeof(unsigned) + sizeof(double));
+    pwrite_at(f, off, &iteration, sizeof(unsigned));
+    pwrite_at(f, off + sizeof(unsigned), &mu, sizeof(double));
+}
+
+// .csv/.gam text: line n of lines of one length
+void write_line(FILE* f, unsigned n_thinned_saved, const char* line, int len)
+{
+    pwrite_at(f, (long)n_thinned_saved * len, line, (size_t)len);
+}
+
+// .eps/.mrk/.gam.<rank>/.xiv dumps, overwritten at every save: (iteration, length, payload)
+void write_dump(FILE* f, unsigned iteration, unsigned length, const void* v, size_t elem)
+{
+    pwrite_at(f, 0, &iteration, sizeof(unsigned));
+    pwrite_at(f, sizeof(unsigned), &length, sizeof(unsigned));
+    pwrite_at(f, 2 * sizeof(unsigned), v, (size_t)length * elem);
+}
+
+// .xbet/.xcpn, overwritten at every save: the marker count at 0 (the caller's), the iteration, M elements
+void write_xfile(FILE* f, unsigned iteration, const void* v, unsigned M, size_t elem)
+{
+    pwrite_at(f, sizeof(unsigned), &iteration, sizeof(unsigned));
+    pwrite_at(f, 2 * sizeof(unsigned), v, (size_t)M * elem);
+}
+
+// What a restart reads the same way for BayesR and BayesW.  Two readers and not one: BayesR reads its .mus between them, and the
+// order of the reads is the order in which bad files are refused.
+struct RestartState {
+    std::vector<double> beta;
+    std::vector<int32_t> comp;
+    std::vector<uint8_t> eps_dump, order_dump;
+    const double* eps = nullptr; // this rank's rows in eps_dump: a full-length dump (hydra's own, or a 1-rank run's) is sliced
+    const int32_t* order() const { return (const int32_t*)order_dump.data(); }
+};
+
+// beta and the components of iteration it_from, from the histories or, with the x-file switch, from .xbet/.xcpn
+void read_restart_effects(RestartState& r, const Options& opt, const std::string& base_in, unsigned Mtot, unsigned it_from, unsigned first_thinned)
+{
+    const bool xf = opt.useXfilesInRestart;
+    r.beta.resize(Mtot);
+    r.comp.resize(Mtot);
+    read_marker_history(base_in + (xf ? ".xbet" : ".bet"), xf, Mtot, it_from, first_thinned, opt.thin, sizeof(double), r.beta.data());
+    read_marker_history(base_in + (xf ? ".xcpn" : ".cpn"), xf, Mtot, it_from, first_thinned, opt.thin, sizeof(int32_t), r.comp.data());
+}
+
+// .eps.<rank> and .mrk.<rank>
+void read_restart_shard(RestartState& r, const std::string& base_in, int rank, unsigned it_from, unsigned Ntot, const Shard& sh, unsigned Mtot)
+{
+    unsigned len = 0;
+    r.eps_dump = read_dump(base_in + ".eps." + std::to_string(rank), it_from, sizeof(double), &len);
+    r.eps = (const double*)r.eps_dump.data();
+    if (len == Ntot && len != sh.rows()) r.eps += sh.lo;
+    else expect_u(len, sh.rows(), ".eps Ntot");
+    r.order_dump = read_dump(base_in + ".mrk." + std::to_string(rank), it_from, sizeof(int32_t), &len);
+    expect_u(len, Mtot, ".mrk M");
+}
+
+void print_restart_banner(const std::string& base_in, unsigned it_from, unsigned iteration_start) // Data::print_restart_banner, data.cpp:20-31
+{
+    const std::string stars(100, '*');
+    std::printf("INFO   : %s\nINFO   : RESTART DETECTED\nINFO   : restarting from: %s.* files\n", stars.c_str(), base_in.c_str());
+    std::printf("INFO   : last saved iteration:        %d\nINFO   : will restart from iteration: %d\nINFO   : %s\n", it_from, iteration_start, stars.c_str());
+}
+
+// BayesW's .csv (src/data.cpp:523-622): the last line whose iteration is a multiple of --save wins
+CsvRestart read_csv_for_restart_w(const std::string& csv, unsigned thin, unsigned save, int G, int K)
+{
+    std::ifstream file(csv);
+    if (!file) fatal("*FATAL*: failed to open csv file " + csv + "!");
+    CsvRestart r;
+    r.sigmaG.assign(G, 0.0);
+    r.pi.assign((size_t)G * K, 0.0);
+    int nSaved = 0, nThinned = 0;
+    std::string str;
+    while (std::getline(file, str)) {
+        if (str.empty()) continue;
+        for (char& ch : str)
+            if (ch == ',') ch = ' ';
+        char* q = &str[0];
+        const long it = std::strtol(q, &q, 10);
+        if (it % thin != 0) fatal("FATAL  : " + csv + ": iteration " + std::to_string(it) + " is not a multiple of --thin");
+        if (++nThinned == 1) r.first_thinned_iteration = (unsigned)it;
+        if (it % save != 0) continue;
+        ++nSaved;
+        r.iteration_to_restart_from = (unsigned)it;
+        r.mu = std::strtod(q, &q);
+        (void)std::strtod(q, &q); // sigmaG.sum()
+        r.alpha = std::strtod(q, &q);
+        (void)std::strtod(q, &q); // h2
+        (void)std::strtol(q, &q, 10); // m0
+        const long rows = std::strtol(q, &q, 10), cols = std::strtol(q, &q, 10);
+        if (rows != G || cols != K) fatal("FATAL  : " + csv + ": pi is " + std::to_string(rows) + "x" + std::to_string(cols) + ", expected " + std::to_string(G) + "x" + std::to_string(K));
+        for (int g = 0; g < G; ++g) r.sigmaG[g] = std::strtod(q, &q);
+        for (size_t i = 0; i < (size_t)G * K; ++i) r.pi[i] = std::strtod(q, &q);
+    }
+    if (nSaved == 0) fatal("FATAL  : No saved iteration could be found when reading " + csv + "!");
+    return r;
+}
+
+// BayesW's text .gam: the last line whose iteration is a multiple of --save (src/data.cpp:624-663), which must be it_from
+std::vector<double> read_gam_for_restart_w(const std::string& gam, unsigned save, int C, unsigned it_from)
+{
+    std::ifstream gf(gam);
+    if (!gf) fatal("*FATAL*: failed to open csv file " + gam + "!");
+    std::vector<double> gamma(C);
+    long g_it = -1;
+    std::string str;
+    while (std::getline(gf, str)) {
+        if (str.empty()) continue;
+        for (char& ch : str)
+            if (ch == ',') ch = ' ';
+        char* q = &str[0];
+        const long it = std::strtol(q, &q, 10);
+        if (it % save != 0) continue;
+        g_it = it;
+        for (int i = 0; i < C; ++i) gamma[i] = std::strtod(q, &q);
+    }
+    expect_u((unsigned)g_it, it_from, ".gam iteration");
+    return gamma;
+}
+
 // Data::readPhenFailFiles / readPhenFailCovFiles, src/data.cpp:1681-1802: .phen, .fail (and .cov)
 // are read line by line in lockstep; an individual is dropped if its phenotype is NA, its failure
 // indicator is -9, or any covariate is NA.
@@ -1198,23 +1457,15 @@ int run_bayesw(const Options& opt_in, int rank, int nranks, int local_rank)
     if (opt.failureFile.empty()) fatal("FATAL  : --failure is mandatory with --mpibayes bayesWMPI");
     if (opt.quad_points.empty()) fatal("Possible number of quad_points = 3,5,7,9,11,13,15,17,25"); // src/BayesW.cpp:706-708
     const int quad = std::atoi(opt.quad_points.c_str());
-    // without --bfile (the sparse route, src/main.cpp:96-118) N and M are the options' and the files are read line by line
-    const bool haveBed = !opt.bedFile.empty();
-    if (!haveBed && opt.numberIndividuals == 0) fatal("FATAL  : opt.numberIndividuals is zero! Set it via --number-individuals in call.");
-    if (!haveBed && opt.numberMarkers == 0) fatal("FATAL  : opt.numberMarkers is zero! Set it via --number-markers in call.");
-    const size_t numInds = haveBed ? count_fam(opt.bedFile + ".fam", nullptr) : opt.numberIndividuals;
-    const size_t numSnps = haveBed ? count_bim(opt.bedFile + ".bim") : opt.numberMarkers;
+    const Dims dims = read_dims(opt); // without --bfile the files are read line by line
+    const size_t numInds = dims.numInds;
     std::vector<double> y, covX;
     std::vector<int32_t> fail;
     std::vector<uint8_t> keep;
     int C = 0;
     read_phen_fail(opt.phenotypeFile, opt.failureFile, opt.covariates ? opt.covariatesFile : std::string(), numInds, y, fail, keep, covX, C);
     const unsigned numNAs = (unsigned)(numInds - y.size());
-    if (opt.numberIndividuals == 0) fatal("FATAL  : opt.numberIndividuals is zero! Set it via --number-individuals in call.");
-    if (opt.numberMarkers == 0) fatal("FATAL  : opt.numberMarkers is zero! Set it via --number-markers in call.");
-    if (opt.numberIndividuals != numInds) fatal("FATAL  : --number-individuals does not match the .fam file");
-    unsigned Mtot = opt.numberMarkers;
-    if (Mtot > numSnps) fatal("FATAL  : --number-markers exceeds the .bim file");
+    const unsigned Mtot = check_dims(opt, dims);
     const unsigned Ntot = (unsigned)numInds - numNAs;
     std::printf("INFO   : Full dataset includes Mtot=%d markers and Ntot=%d individuals.\n", Mtot, (int)numInds);
     if (use_sparse(opt)) {
@@ -1222,49 +1473,17 @@ int run_bayesw(const Options& opt_in, int rank, int nranks, int local_rank)
         sparse_info(opt, rank, nranks);
     }
 
-    std::vector<int32_t> groups;
-    std::vector<std::vector<double>> mS;
-    if (!opt.groupIndexFile.empty()) { // src/BayesW.cpp:773-776
-        groups = read_groups(opt.groupIndexFile);
-        mS = read_mS(opt.groupMixtureFile);
-        if (groups.size() < Mtot) fatal("FATAL  : group file covers fewer markers than --number-markers");
-        groups.resize(Mtot);
-    } else {
-        std::vector<double> row{0.0};
-        for (double v : opt.S) row.push_back(v);
-        mS.push_back(row);
-    }
-    const int G = (int)mS.size(), K = (int)mS[0].size();
+    const Mixtures mix = read_mixtures(opt, Mtot, false);
+    const int G = mix.G, K = mix.K;
     std::printf("numGroups = %d, data.groups.size() = %lu, Mtot = %d\n", G, (unsigned long)Mtot, Mtot); // :778
-    std::vector<double> mS_flat;
-    for (auto& r : mS) mS_flat.insert(mS_flat.end(), r.begin(), r.end());
-    if (opt.save < opt.thin) { // :981-989
-        opt.save = opt.thin;
-        std::printf("WARNING: opt.save was lower that opt.thin ; opt.save reset to opt.thin (%d)\n", opt.thin);
-    }
-    if (opt.save % opt.thin != 0) {
-        std::printf("WARNING: opt.save (= %d) was not a multiple of opt.thin (= %d)\n", opt.save, opt.thin);
-        opt.save = (opt.save / opt.thin) * opt.thin;
-        std::printf("         opt.save reset to %d, the closest multiple of opt.thin (%d)\n", opt.save, opt.thin);
-    }
+    adjust_save(opt, true, true);
     make_out_dir(opt);
     const std::string base_in = opt.mcmcOutDir + "/" + opt.mcmcOutNam; // a restart reads <name>.*, writes <name>_rs.* (:994-1008)
     const std::string base = opt.restart ? base_in + "_rs" : base_in;
 
-    hgibbs_t dev = nullptr;
-    hg_check(hgibbs_create(local_rank, &dev), "hgibbs_create");
-    if (nranks > 1) setup_ranks(dev, base, rank, nranks);
-    if (opt.batch) hg_check(hgibbs_set_option(dev, "batch", opt.batch), "batch");
-    const double tl0 = now_s();
-    // individuals sharded in multiples of 4 of the KEPT rows
-    const unsigned per = ((Ntot + nranks - 1) / nranks + 3) / 4 * 4;
-    const unsigned lo = std::min(Ntot, rank * per), hi = std::min(Ntot, (rank + 1) * per);
-    {
-        std::vector<uint8_t> bed = read_training(opt.bedFile, numInds, Mtot);
-        const size_t bytes = put_genotypes(dev, bed, numInds, Mtot, numNAs ? keep.data() : nullptr, lo, hi, Ntot);
-        std::printf("INFO   : rank %3d took %.3f seconds to load  %lu bytes  =>  BW = %7.3f GB/s\n", rank, now_s() - tl0, (unsigned long)bytes,
-                    (double)bytes * 1e-9 / (now_s() - tl0));
-    }
+    hgibbs_t dev = open_device(opt, base, rank, nranks, local_rank, 0);
+    const Shard sh = shard_of(Ntot, rank, nranks);
+    load_and_report(dev, opt, numInds, Mtot, numNAs ? keep.data() : nullptr, sh, Ntot, rank);
     if (numNAs) std::printf("INFO   : Ntot adjusted by -%d to account for NAs in phenotype file. Now Ntot=%d\n", numNAs, Ntot);
 
     hydraw_model_desc md{};
@@ -1272,8 +1491,8 @@ int run_bayesw(const Options& opt_in, int rank, int nranks, int local_rank)
     md.shuffle = opt.shuffleMarkers;
     md.G = G;
     md.K = K;
-    md.groups = groups.empty() ? nullptr : groups.data();
-    md.mS = mS_flat.data();
+    md.groups = mix.groups.empty() ? nullptr : mix.groups.data();
+    md.mS = mix.mS_flat.data();
     md.quad_points = quad;
     hydraw_chain_t chain = nullptr;
     hg_check(hydraw_chain_create(dev, &md, y.data(), fail.data(), &chain), "hydraw_chain_create");
@@ -1283,92 +1502,42 @@ int run_bayesw(const Options& opt_in, int rank, int nranks, int local_rank)
     unsigned iteration_start = 0;
     if (opt.restart) {
         std::printf("RESTART: from files: %s.* files\n", base_in.c_str());
-        std::ifstream file(base_in + ".csv");
-        if (!file) fatal("*FATAL*: failed to open csv file " + base_in + ".csv!");
-        unsigned it_from = 0, first_thinned = 0;
-        int nSaved = 0, nThinned = 0;
-        double r_mu = 0.0, r_alpha = 0.0;
-        std::vector<double> r_sigmaG(G), r_pi((size_t)G * K);
-        std::string str;
-        while (std::getline(file, str)) {
-            if (str.empty()) continue;
-            for (char& ch : str)
-                if (ch == ',') ch = ' ';
-            char* q = &str[0];
-            const long it = std::strtol(q, &q, 10);
-            if (it % opt.thin != 0) fatal("FATAL  : " + base_in + ".csv: iteration " + std::to_string(it) + " is not a multiple of --thin");
-            if (++nThinned == 1) first_thinned = (unsigned)it;
-            if (it % opt.save != 0) continue;
-            ++nSaved;
-            it_from = (unsigned)it;
-            r_mu = std::strtod(q, &q);
-            (void)std::strtod(q, &q); // sigmaG.sum()
-            r_alpha = std::strtod(q, &q);
-            (void)std::strtod(q, &q); // h2
-            (void)std::strtol(q, &q, 10); // m0
-            const long rows = std::strtol(q, &q, 10), cols = std::strtol(q, &q, 10);
-            if (rows != G || cols != K) fatal("FATAL  : " + base_in + ".csv: pi is " + std::to_string(rows) + "x" + std::to_string(cols) + ", expected " + std::to_string(G) + "x" + std::to_string(K));
-            for (int g = 0; g < G; ++g) r_sigmaG[g] = std::strtod(q, &q);
-            for (size_t i = 0; i < (size_t)G * K; ++i) r_pi[i] = std::strtod(q, &q);
-        }
-        if (nSaved == 0) fatal("FATAL  : No saved iteration could be found when reading " + base_in + ".csv!");
+        const CsvRestart cr = read_csv_for_restart_w(base_in + ".csv", opt.thin, opt.save, G, K);
+        const unsigned it_from = cr.iteration_to_restart_from;
         if (it_from == 0) fatal("FATAL  : There is no point in restarting a chain from iteration 0 (not saved anyway)\n         => restart your analysis from scratch");
-        const bool xf = opt.useXfilesInRestart;
-        std::vector<double> r_beta(Mtot);
-        std::vector<int32_t> r_comp(Mtot);
-        read_marker_history(base_in + (xf ? ".xbet" : ".bet"), xf, Mtot, it_from, first_thinned, opt.thin, sizeof(double), r_beta.data());
-        read_marker_history(base_in + (xf ? ".xcpn" : ".cpn"), xf, Mtot, it_from, first_thinned, opt.thin, sizeof(int32_t), r_comp.data());
-        unsigned len = 0;
-        std::vector<uint8_t> eb = read_dump(base_in + ".eps." + std::to_string(rank), it_from, sizeof(double), &len);
-        const double* r_eps = (const double*)eb.data();
-        if (len == Ntot && len != hi - lo) r_eps += lo; // a full-length dump is sliced
-        else expect_u(len, hi - lo, ".eps Ntot");
-        std::vector<uint8_t> mb = read_dump(base_in + ".mrk." + std::to_string(rank), it_from, sizeof(int32_t), &len);
-        expect_u(len, Mtot, ".mrk M");
-        std::vector<double> r_gamma(C);
+        RestartState r;
+        read_restart_effects(r, opt, base_in, Mtot, it_from, cr.first_thinned_iteration);
+        read_restart_shard(r, base_in, rank, it_from, Ntot, sh, Mtot);
+        std::vector<double> r_gamma;
         std::vector<uint8_t> xb;
-        if (opt.covariates) { // text .gam: the last line whose iteration is a multiple of --save (src/data.cpp:624-663)
-            std::ifstream gf(base_in + ".gam");
-            if (!gf) fatal("*FATAL*: failed to open csv file " + base_in + ".gam!");
-            long g_it = -1;
-            while (std::getline(gf, str)) {
-                if (str.empty()) continue;
-                for (char& ch : str)
-                    if (ch == ',') ch = ' ';
-                char* q = &str[0];
-                const long it = std::strtol(q, &q, 10);
-                if (it % opt.save != 0) continue;
-                g_it = it;
-                for (int i = 0; i < C; ++i) r_gamma[i] = std::strtod(q, &q);
-            }
-            expect_u((unsigned)g_it, it_from, ".gam iteration");
+        if (opt.covariates) {
+            r_gamma = read_gam_for_restart_w(base_in + ".gam", opt.save, C, it_from);
+            unsigned len = 0;
             xb = read_dump(base_in + ".xiv", it_from, sizeof(int32_t), &len);
             expect_u(len, (unsigned)C, ".xiv length");
         }
         hydraw_restart_state rs{};
         rs.iteration = it_from;
-        rs.mu = r_mu;
-        rs.alpha = r_alpha;
-        rs.sigmaG = r_sigmaG.data();
-        rs.pi = r_pi.data();
-        rs.beta = r_beta.data();
-        rs.components = r_comp.data();
-        rs.eps = r_eps;
-        rs.order = (const int32_t*)mb.data();
+        rs.mu = cr.mu;
+        rs.alpha = cr.alpha;
+        rs.sigmaG = cr.sigmaG.data();
+        rs.pi = cr.pi.data();
+        rs.beta = r.beta.data();
+        rs.components = r.comp.data();
+        rs.eps = r.eps;
+        rs.order = r.order();
         rs.gamma = opt.covariates ? r_gamma.data() : nullptr;
         rs.xI = opt.covariates ? (const int32_t*)xb.data() : nullptr;
         rs.ars_seed = opt.seed + it_from; // srand(opt.seed + iteration_to_restart_from), :877
         read_rng_file(base_in + ".rng." + std::to_string(rank), &rs.rng);
         hg_check(hydraw_chain_restore(chain, &rs), "hydraw_chain_restore");
         iteration_start = it_from + 1;
-        std::printf("INFO   : %s\nINFO   : RESTART DETECTED\nINFO   : restarting from: %s.* files\n", std::string(100, '*').c_str(), base_in.c_str());
-        std::printf("INFO   : last saved iteration:        %d\nINFO   : will restart from iteration: %d\nINFO   : %s\n", it_from, iteration_start,
-                    std::string(100, '*').c_str());
+        print_restart_banner(base_in, it_from, iteration_start);
     }
 
-    auto open_trunc = [&](const std::string& p) { return open_out(p, "wb+"); };
+    OutFiles outs;
     // the shared files are rank 0's (every rank holds the same chain); the others write theirs into the void
-    auto open_shared = [&](const std::string& p) { return open_trunc(rank == 0 ? p : std::string("/dev/null")); };
+    auto open_shared = [&](const std::string& p) { return outs.open(rank == 0 ? p : std::string("/dev/null")); };
     FILE* outf = open_shared(base + ".csv");
     FILE* betf = open_shared(base + ".bet");
     FILE* cpnf = open_shared(base + ".cpn");
@@ -1376,11 +1545,11 @@ int run_bayesw(const Options& opt_in, int rank, int nranks, int local_rank)
     FILE* xcpnf = open_shared(base + ".xcpn");
     FILE* gamf = open_shared(base + ".gam"); // text, one line per thinned iteration (:1966-1977)
     FILE* xivf = open_shared(base + ".xiv");
-    FILE* epsf = open_trunc(base + ".eps." + std::to_string(rank));
-    FILE* mrkf = open_trunc(base + ".mrk." + std::to_string(rank));
+    FILE* epsf = outs.open(base + ".eps." + std::to_string(rank));
+    FILE* mrkf = outs.open(base + ".mrk." + std::to_string(rank));
     for (FILE* f : {betf, xbetf, cpnf, xcpnf}) pwrite_at(f, 0, &Mtot, sizeof(unsigned)); // :1096-1101
 
-    std::vector<double> beta(Mtot), eps(hi - lo), sigmaG(G), gamma(C);
+    std::vector<double> beta(Mtot), eps(sh.rows()), sigmaG(G), gamma(C);
     std::vector<int32_t> comp(Mtot), m0(G), xiv(C);
     std::vector<char> buff(50000);
     unsigned n_thinned_saved = 0;
@@ -1405,28 +1574,19 @@ int run_bayesw(const Options& opt_in, int rank, int nranks, int local_rank)
 
         if (iteration % opt.thin == 0) { // :1937-2019
             const int len = hydraw_chain_csv_line(chain, iteration, buff.data(), buff.size());
-            pwrite_at(outf, (long)n_thinned_saved * len, buff.data(), (size_t)len);
+            write_line(outf, n_thinned_saved, buff.data(), len);
             if (opt.covariates) {
                 hydraw_chain_gamma(chain, gamma.data(), xiv.data());
                 std::string gl(64 + 32 * (size_t)C, '\0');
                 int n = std::snprintf(&gl[0], gl.size(), "%5d", iteration);
                 for (int ii = 0; ii < C; ++ii) n += std::snprintf(&gl[n], gl.size() - n, ", %20.17f", gamma[ii]);
                 n += std::snprintf(&gl[n], gl.size() - n, "\n");
-                pwrite_at(gamf, (long)n_thinned_saved * n, gl.data(), (size_t)n);
-                if (iteration > 0 && iteration % opt.save == 0) {
-                    const unsigned nf = (unsigned)C;
-                    pwrite_at(xivf, 0, &iteration, sizeof(unsigned));
-                    pwrite_at(xivf, sizeof(unsigned), &nf, sizeof(unsigned));
-                    pwrite_at(xivf, 2 * sizeof(unsigned), xiv.data(), (size_t)C * sizeof(int));
-                }
+                write_line(gamf, n_thinned_saved, gl.data(), n);
+                if (iteration > 0 && iteration % opt.save == 0) write_dump(xivf, iteration, (unsigned)C, xiv.data(), sizeof(int));
             }
             hg_check(hgibbs_w_get_beta(dev, beta.data(), comp.data()), "hgibbs_w_get_beta");
-            long off = sizeof(unsigned) + (long)n_thinned_saved * (sizeof(unsigned) + (long)Mtot * sizeof(double));
-            pwrite_at(betf, off, &iteration, sizeof(unsigned));
-            pwrite_at(betf, off + sizeof(unsigned), beta.data(), (size_t)Mtot * sizeof(double));
-            off = sizeof(unsigned) + (long)n_thinned_saved * (sizeof(unsigned) + (long)Mtot * sizeof(int));
-            pwrite_at(cpnf, off, &iteration, sizeof(unsigned));
-            pwrite_at(cpnf, off + sizeof(unsigned), comp.data(), (size_t)Mtot * sizeof(int));
+            write_thinned(betf, n_thinned_saved, iteration, beta.data(), Mtot, sizeof(double));
+            write_thinned(cpnf, n_thinned_saved, iteration, comp.data(), Mtot, sizeof(int));
             n_thinned_saved += 1;
         }
         if (iteration > 0 && iteration % opt.save == 0) { // :2028-2052
@@ -1436,22 +1596,14 @@ int run_bayesw(const Options& opt_in, int rank, int nranks, int local_rank)
             write_rng_file(base + ".rng." + std::to_string(rank), rst);
             hg_check(hgibbs_get_residual(dev, eps.data()), "hgibbs_get_residual");
             hg_check(hgibbs_w_get_beta(dev, beta.data(), comp.data()), "hgibbs_w_get_beta");
-            pwrite_at(epsf, 0, &iteration, sizeof(unsigned));
-            const unsigned nloc = hi - lo; // this rank's rows
-            pwrite_at(epsf, sizeof(unsigned), &nloc, sizeof(unsigned));
-            pwrite_at(epsf, 2 * sizeof(unsigned), eps.data(), (size_t)nloc * sizeof(double));
-            pwrite_at(mrkf, 0, &iteration, sizeof(unsigned));
-            pwrite_at(mrkf, sizeof(unsigned), &Mtot, sizeof(unsigned));
-            pwrite_at(mrkf, 2 * sizeof(unsigned), hydraw_chain_order(chain), (size_t)Mtot * sizeof(int));
-            pwrite_at(xbetf, sizeof(unsigned), &iteration, sizeof(unsigned));
-            pwrite_at(xcpnf, sizeof(unsigned), &iteration, sizeof(unsigned));
-            pwrite_at(xbetf, 2 * sizeof(unsigned), beta.data(), (size_t)Mtot * sizeof(double));
-            pwrite_at(xcpnf, 2 * sizeof(unsigned), comp.data(), (size_t)Mtot * sizeof(int));
+            write_dump(epsf, iteration, sh.rows(), eps.data(), sizeof(double)); // this rank's rows
+            write_dump(mrkf, iteration, Mtot, hydraw_chain_order(chain), sizeof(int));
+            write_xfile(xbetf, iteration, beta.data(), Mtot, sizeof(double));
+            write_xfile(xcpnf, iteration, comp.data(), Mtot, sizeof(int));
         }
     }
     std::printf("INFO   : rank %4d, time to process the data: %.3f sec\n", rank, now_s() - t_all);
-    for (FILE* f : {outf, betf, cpnf, xbetf, xcpnf, gamf, xivf, epsf, mrkf})
-        if (f) std::fclose(f);
+    outs.close(false);
     hydraw_chain_destroy(chain);
     hgibbs_destroy(dev);
     return 0;
@@ -3784,10 +3936,11 @@ int run_sumstats(const Options& opt, const Cohort& co, const std::vector<int32_t
     hg_check(hgibbs_last_ss_ms(dev, &band_ms, &sweep_ms), "hgibbs_last_ss_ms");
 
     // the chain's files and formats (:1302-1309, :2736-2794)
-    FILE* outf = open_out(base + ".csv", "wb+");
-    FILE* betf = open_out(base + ".bet", "wb+");
-    FILE* cpnf = open_out(base + ".cpn", "wb+");
-    FILE* acuf = open_out(base + ".acu", "wb+");
+    OutFiles outs;
+    FILE* outf = outs.open(base + ".csv");
+    FILE* betf = outs.open(base + ".bet");
+    FILE* cpnf = outs.open(base + ".cpn");
+    FILE* acuf = outs.open(base + ".acu");
     for (FILE* f : {betf, cpnf, acuf}) pwrite_at(f, 0, &M, sizeof(unsigned));
     std::vector<double> beta(M), acum(M), sigmaG(G);
     std::vector<int32_t> comp(M), m0(G);
@@ -3815,22 +3968,14 @@ int run_sumstats(const Options& opt, const Cohort& co, const std::vector<int32_t
         if (iteration % opt.thin == 0) {
             hg_check(hydra_ss_chain_effects(chain, beta.data(), comp.data(), acum.data(), nullptr), "hydra_ss_chain_effects");
             const int len = hydra_ss_chain_csv_line(chain, iteration, buff.data(), buff.size());
-            pwrite_at(outf, (long)n_thinned_saved * len, buff.data(), (size_t)len);
-            long off = sizeof(unsigned) + (long)n_thinned_saved * (sizeof(unsigned) + (long)M * sizeof(double));
-            pwrite_at(betf, off, &iteration, sizeof(unsigned));
-            pwrite_at(acuf, off, &iteration, sizeof(unsigned));
-            pwrite_at(betf, off + sizeof(unsigned), beta.data(), (size_t)M * sizeof(double));
-            pwrite_at(acuf, off + sizeof(unsigned), acum.data(), (size_t)M * sizeof(double));
-            off = sizeof(unsigned) + (long)n_thinned_saved * (sizeof(unsigned) + (long)M * sizeof(int));
-            pwrite_at(cpnf, off, &iteration, sizeof(unsigned));
-            pwrite_at(cpnf, off + sizeof(unsigned), comp.data(), (size_t)M * sizeof(int));
+            write_line(outf, n_thinned_saved, buff.data(), len);
+            write_thinned(betf, n_thinned_saved, iteration, beta.data(), M, sizeof(double));
+            write_thinned(acuf, n_thinned_saved, iteration, acum.data(), M, sizeof(double));
+            write_thinned(cpnf, n_thinned_saved, iteration, comp.data(), M, sizeof(int));
             n_thinned_saved += 1;
         }
     }
-    close_out(outf, base + ".csv");
-    close_out(betf, base + ".bet");
-    close_out(cpnf, base + ".cpn");
-    close_out(acuf, base + ".acu");
+    outs.close(true);
     hydra_ss_chain_destroy(chain);
     hgibbs_destroy(dev);
     std::printf("SUMSTAT: %u markers used, %u left out (%u not in the table, %u with another allele pair, %u without usable BETA, SE and N, %u without a finite sd in the panel), "
@@ -4140,12 +4285,9 @@ int main(int argc, const char* argv[])
     if (opt.bayesType == "bayesWMPI") return run_bayesw(opt, rank, nranks, local_rank); // main.cpp:164-167
 
     // ---- inputs (main.cpp:69-70,88; BayesRRm.cpp:969-997) -------------------
-    // without --bfile (the sparse route, main.cpp:96-118) N and M are the options' and the phenotype file is read line by line
-    if (!haveBed && opt.numberIndividuals == 0) fatal("FATAL  : opt.numberIndividuals is zero! Set it via --number-individuals in call.");
-    if (!haveBed && opt.numberMarkers == 0) fatal("FATAL  : opt.numberMarkers is zero! Set it via --number-markers in call.");
-    std::vector<std::string> fam_ids;
-    const size_t numInds = haveBed ? count_fam(opt.bedFile + ".fam", &fam_ids) : opt.numberIndividuals;
-    const size_t numSnps = haveBed ? count_bim(opt.bedFile + ".bim") : opt.numberMarkers;
+    const Dims dims = read_dims(opt); // without --bfile the phenotype file is read line by line
+    const size_t numInds = dims.numInds, numSnps = dims.numSnps;
+    const std::vector<std::string>& fam_ids = dims.fam_ids;
     std::vector<double> y;
     std::vector<uint8_t> keep;
     std::vector<double> covX;
@@ -4158,11 +4300,7 @@ int main(int argc, const char* argv[])
     else read_phen_lines(opt.phenotypeFile, numInds, y, keep);
     const unsigned numNAs = (unsigned)(numInds - y.size());
 
-    if (opt.numberIndividuals == 0) fatal("FATAL  : opt.numberIndividuals is zero! Set it via --number-individuals in call.");
-    if (opt.numberMarkers == 0) fatal("FATAL  : opt.numberMarkers is zero! Set it via --number-markers in call.");
-    if (opt.numberIndividuals != numInds) fatal("FATAL  : --number-individuals does not match the .fam file");
-    unsigned Mtot = opt.numberMarkers;
-    if (Mtot > numSnps) fatal("FATAL  : --number-markers exceeds the .bim file");
+    const unsigned Mtot = check_dims(opt, dims);
     if (Mtot < numSnps && rank == 0) std::printf("INFO   : Option passed to process only %d markers!\n", Mtot);
     const unsigned Ntot = (unsigned)numInds - numNAs;
     if (rank == 0) {
@@ -4191,65 +4329,28 @@ int main(int argc, const char* argv[])
     if (opt.homozyg) return run_homozyg(opt, co);
     if (opt.epistasis) return run_epistasis(opt, co, y);
 
-    std::vector<int32_t> groups;
-    std::vector<std::vector<double>> mS;
-    if (!opt.groupIndexFile.empty()) {
-        groups = read_groups(opt.groupIndexFile);
-        mS = read_mS(opt.groupMixtureFile);
-        if (groups.size() < Mtot) fatal("FATAL  : group file covers fewer markers than --number-markers");
-        groups.resize(Mtot);
-    } else {
-        std::vector<double> row{0.0};
-        for (double v : opt.S) {
-            if (v <= 0.0) fatal("FATAL  : mixture value can only be strictly positive");
-            row.push_back(v);
-        }
-        mS.push_back(row);
-    }
-    const int G = (int)mS.size(), K = (int)mS[0].size();
-    std::vector<double> mS_flat;
-    for (auto& r : mS) mS_flat.insert(mS_flat.end(), r.begin(), r.end());
-    if (opt.sumstats) return run_sumstats(opt, co, groups, mS_flat, G, K);
+    const Mixtures mix = read_mixtures(opt, Mtot, true);
+    const int G = mix.G, K = mix.K;
+    if (opt.sumstats) return run_sumstats(opt, co, mix.groups, mix.mS_flat, G, K);
 
-    // --thin/--save adjustment, BayesRRm.cpp:1058-1066
-    if (opt.save < opt.thin) {
-        opt.save = opt.thin;
-        if (rank == 0) std::printf("WARNING: opt.save was lower that opt.thin ; opt.save reset to opt.thin (%d)\n", opt.thin);
-    }
-    if (opt.save % opt.thin != 0) {
-        opt.save = (opt.save / opt.thin) * opt.thin;
-        if (rank == 0) std::printf("         opt.save reset to %d, the closest multiple of opt.thin (%d)\n", opt.save, opt.thin);
-    }
-
+    adjust_save(opt, rank == 0, false);
     if (rank == 0) make_out_dir(opt);
     // a restart reads <name>.* and writes <name>_rs.* so the failed job's files stay untouched (:1206-1220)
     const std::string base_in = opt.mcmcOutDir + "/" + opt.mcmcOutNam;
     const std::string base = opt.restart ? base_in + "_rs" : base_in;
 
-    // ---- device -------------------------------------------------------------
-    hgibbs_t dev = nullptr;
-    hg_check(hgibbs_create(local_rank, &dev), "hgibbs_create");
-    if (nranks > 1) setup_ranks(dev, base, rank, nranks);
-    if (opt.batch) hg_check(hgibbs_set_option(dev, "batch", opt.batch), "batch");
-    if (opt.cpg) hg_check(hgibbs_set_option(dev, "cols_per_group", opt.cpg), "cols_per_group");
-
-    // ---- genotypes: Data::load_data_from_bed_file, data.cpp:671-739 -----------
-    const double tl0 = now_s();
-    std::vector<uint8_t> bed = read_training(opt.bedFile, numInds, Mtot);
-    // individuals sharded in multiples of 4 of the KEPT rows
-    const unsigned per = ((Ntot + nranks - 1) / nranks + 3) / 4 * 4;
-    const unsigned lo = std::min(Ntot, rank * per), hi = std::min(Ntot, (rank + 1) * per);
-    const size_t loaded = put_genotypes(dev, bed, numInds, Mtot, numNAs ? keep.data() : nullptr, lo, hi, Ntot);
-    std::printf("INFO   : rank %3d took %.3f seconds to load  %lu bytes  =>  BW = %7.3f GB/s\n", rank, now_s() - tl0,
-                (unsigned long)loaded, (double)loaded * 1e-9 / (now_s() - tl0));
+    // ---- device and genotypes -------------------------------------------------
+    hgibbs_t dev = open_device(opt, base, rank, nranks, local_rank, opt.cpg);
+    const Shard sh = shard_of(Ntot, rank, nranks);
+    load_and_report(dev, opt, numInds, Mtot, numNAs ? keep.data() : nullptr, sh, Ntot, rank);
 
     hydra_model_desc md{};
     md.seed = opt.seed + (unsigned)0 * 1000; // every rank replicates rank 0's stream (BayesRRm.cpp:1228 with rank = 0)
     md.shuffle = opt.shuffleMarkers;
     md.G = G;
     md.K = K;
-    md.groups = groups.empty() ? nullptr : groups.data();
-    md.mS = mS_flat.data();
+    md.groups = mix.groups.empty() ? nullptr : mix.groups.data();
+    md.mS = mix.mS_flat.data();
     hydra_chain_t chain = nullptr;
     hg_check(hydra_chain_create(dev, &md, y.data(), &chain), "hydra_chain_create");
     if (opt.covariates) {
@@ -4272,11 +4373,8 @@ int main(int argc, const char* argv[])
         if (cr.iteration_to_restart_from == 0)
             fatal("FATAL  : There is no point in restarting a chain from iteration 0 (not saved anyway)\n         => restart your analysis from scratch");
         const unsigned it_from = cr.iteration_to_restart_from;
-        const bool xf = opt.useXfilesInRestart;
-        std::vector<double> r_beta(Mtot);
-        std::vector<int32_t> r_comp(Mtot);
-        read_marker_history(base_in + (xf ? ".xbet" : ".bet"), xf, Mtot, it_from, cr.first_thinned_iteration, opt.thin, sizeof(double), r_beta.data());
-        read_marker_history(base_in + (xf ? ".xcpn" : ".cpn"), xf, Mtot, it_from, cr.first_thinned_iteration, opt.thin, sizeof(int32_t), r_comp.data());
+        RestartState r;
+        read_restart_effects(r, opt, base_in, Mtot, it_from, cr.first_thinned_iteration);
         double r_mu = 0.0;
         { // .mus.<rank>: (iteration, mu) per thinned iteration, data.cpp:207-252
             const std::string mp = base_in + ".mus." + std::to_string(rank);
@@ -4288,16 +4386,10 @@ int main(int argc, const char* argv[])
             pread_at(f, off + (long)sizeof(unsigned), &r_mu, sizeof(double), mp);
             std::fclose(f);
         }
-        unsigned len = 0;
-        // .eps.<rank>: this rank's shard; a full-length dump (hydra's own, or a 1-rank run's) is sliced
-        std::vector<uint8_t> eb = read_dump(base_in + ".eps." + std::to_string(rank), it_from, sizeof(double), &len);
-        const double* r_eps = (const double*)eb.data();
-        if (len == Ntot && len != hi - lo) r_eps += lo;
-        else expect_u(len, hi - lo, ".eps Ntot");
-        std::vector<uint8_t> mb = read_dump(base_in + ".mrk." + std::to_string(rank), it_from, sizeof(int32_t), &len);
-        expect_u(len, Mtot, ".mrk M");
+        read_restart_shard(r, base_in, rank, it_from, Ntot, sh, Mtot);
         std::vector<uint8_t> gb, xb;
         if (opt.covariates) {
+            unsigned len = 0;
             gb = read_dump(base_in + ".gam." + std::to_string(rank), it_from, sizeof(double), &len);
             expect_u(len, (unsigned)C, ".gam length");
             xb = read_dump(base_in + ".xiv." + std::to_string(rank), it_from, sizeof(int32_t), &len);
@@ -4309,46 +4401,39 @@ int main(int argc, const char* argv[])
         rs.mu = r_mu;
         rs.sigmaG = cr.sigmaG.data();
         rs.estPi = cr.pi.data();
-        rs.beta = r_beta.data();
-        rs.components = r_comp.data();
-        rs.eps = r_eps;
-        rs.order = (const int32_t*)mb.data();
+        rs.beta = r.beta.data();
+        rs.components = r.comp.data();
+        rs.eps = r.eps;
+        rs.order = r.order();
         rs.gamma = opt.covariates ? (const double*)gb.data() : nullptr;
         rs.xI = opt.covariates ? (const int32_t*)xb.data() : nullptr;
         read_rng_file(base_in + ".rng." + std::to_string(rank), &rs.rng);
         hg_check(hydra_chain_restore(chain, &rs), "hydra_chain_restore");
         iteration_start = it_from + 1;
-        if (rank == 0) { // Data::print_restart_banner, data.cpp:20-31
-            std::printf("INFO   : %s\n", std::string(100, '*').c_str());
-            std::printf("INFO   : RESTART DETECTED\n");
-            std::printf("INFO   : restarting from: %s.* files\n", base_in.c_str());
-            std::printf("INFO   : last saved iteration:        %d\n", it_from);
-            std::printf("INFO   : will restart from iteration: %d\n", iteration_start);
-            std::printf("INFO   : %s\n", std::string(100, '*').c_str());
-        }
+        if (rank == 0) print_restart_banner(base_in, it_from, iteration_start);
     }
 
     // ---- outputs (rank 0 writes the shared files) ----------------------------
+    OutFiles outs;
     FILE *outf = nullptr, *betf = nullptr, *cpnf = nullptr, *acuf = nullptr, *xbetf = nullptr, *xcpnf = nullptr;
-    auto open_trunc = [&](const std::string& p) { return open_out(p, "wb+"); };
     if (rank == 0) {
-        outf = open_trunc(base + ".csv");
-        betf = open_trunc(base + ".bet");
-        cpnf = open_trunc(base + ".cpn");
-        acuf = open_trunc(base + ".acu");
-        xbetf = open_trunc(base + ".xbet");
-        xcpnf = open_trunc(base + ".xcpn");
+        outf = outs.open(base + ".csv");
+        betf = outs.open(base + ".bet");
+        cpnf = outs.open(base + ".cpn");
+        acuf = outs.open(base + ".acu");
+        xbetf = outs.open(base + ".xbet");
+        xcpnf = outs.open(base + ".xcpn");
         for (FILE* f : {betf, xbetf, cpnf, xcpnf, acuf}) pwrite_at(f, 0, &Mtot, sizeof(unsigned)); // :1302-1309
     }
-    FILE* musf = open_trunc(base + ".mus." + std::to_string(rank));
-    FILE* epsf = open_trunc(base + ".eps." + std::to_string(rank));
-    FILE* mrkf = open_trunc(base + ".mrk." + std::to_string(rank));
-    FILE* gamf = open_trunc(base + ".gam." + std::to_string(rank));
-    FILE* xivf = open_trunc(base + ".xiv." + std::to_string(rank));
+    FILE* musf = outs.open(base + ".mus." + std::to_string(rank));
+    FILE* epsf = outs.open(base + ".eps." + std::to_string(rank));
+    FILE* mrkf = outs.open(base + ".mrk." + std::to_string(rank));
+    FILE* gamf = outs.open(base + ".gam." + std::to_string(rank));
+    FILE* xivf = outs.open(base + ".xiv." + std::to_string(rank));
     std::vector<double> gamma(C);
     std::vector<int32_t> xiv(C);
 
-    std::vector<double> beta(Mtot), acum(Mtot), eps(hi - lo);
+    std::vector<double> beta(Mtot), acum(Mtot), eps(sh.rows());
     std::vector<int32_t> comp(Mtot);
     std::vector<double> sigmaG(G);
     std::vector<int32_t> m0(G);
@@ -4379,19 +4464,12 @@ int main(int argc, const char* argv[])
             hg_check(hgibbs_get_beta(dev, beta.data(), comp.data(), acum.data()), "hgibbs_get_beta");
             if (rank == 0) {
                 const int len = hydra_chain_csv_line(chain, iteration, buff.data(), buff.size());
-                pwrite_at(outf, (long)n_thinned_saved * len, buff.data(), (size_t)len);
-                long off = sizeof(unsigned) + (long)n_thinned_saved * (sizeof(unsigned) + (long)Mtot * sizeof(double));
-                pwrite_at(betf, off, &iteration, sizeof(unsigned));
-                pwrite_at(acuf, off, &iteration, sizeof(unsigned));
-                pwrite_at(betf, off + sizeof(unsigned), beta.data(), (size_t)Mtot * sizeof(double));
-                pwrite_at(acuf, off + sizeof(unsigned), acum.data(), (size_t)Mtot * sizeof(double));
-                off = sizeof(unsigned) + (long)n_thinned_saved * (sizeof(unsigned) + (long)Mtot * sizeof(int));
-                pwrite_at(cpnf, off, &iteration, sizeof(unsigned));
-                pwrite_at(cpnf, off + sizeof(unsigned), comp.data(), (size_t)Mtot * sizeof(int));
+                write_line(outf, n_thinned_saved, buff.data(), len);
+                write_thinned(betf, n_thinned_saved, iteration, beta.data(), Mtot, sizeof(double));
+                write_thinned(acuf, n_thinned_saved, iteration, acum.data(), Mtot, sizeof(double));
+                write_thinned(cpnf, n_thinned_saved, iteration, comp.data(), Mtot, sizeof(int));
             }
-            long off = (long)n_thinned_saved * (sizeof(unsigned) + sizeof(double));
-            pwrite_at(musf, off, &iteration, sizeof(unsigned));
-            pwrite_at(musf, off + sizeof(unsigned), &mu, sizeof(double));
+            write_mus(musf, n_thinned_saved, iteration, mu);
             n_thinned_saved += 1;
         }
 
@@ -4400,37 +4478,24 @@ int main(int argc, const char* argv[])
             hydra_chain_state(chain, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &rst);
             write_rng_file(base + ".rng." + std::to_string(rank), rst);
             hg_check(hgibbs_get_residual(dev, eps.data()), "hgibbs_get_residual");
-            const unsigned nloc = hi - lo;
-            pwrite_at(epsf, 0, &iteration, sizeof(unsigned));
-            pwrite_at(epsf, sizeof(unsigned), &nloc, sizeof(unsigned));
-            pwrite_at(epsf, 2 * sizeof(unsigned), eps.data(), (size_t)nloc * sizeof(double));
-            pwrite_at(mrkf, 0, &iteration, sizeof(unsigned));
-            pwrite_at(mrkf, sizeof(unsigned), &Mtot, sizeof(unsigned));
-            pwrite_at(mrkf, 2 * sizeof(unsigned), hydra_chain_order(chain), (size_t)Mtot * sizeof(int));
+            write_dump(epsf, iteration, sh.rows(), eps.data(), sizeof(double));
+            write_dump(mrkf, iteration, Mtot, hydra_chain_order(chain), sizeof(int));
             if (opt.covariates) { // :2810-2832
-                const unsigned glen = (unsigned)C;
                 hydra_chain_gamma(chain, gamma.data(), xiv.data());
-                for (FILE* f : {gamf, xivf}) {
-                    pwrite_at(f, 0, &iteration, sizeof(unsigned));
-                    pwrite_at(f, sizeof(unsigned), &glen, sizeof(unsigned));
-                }
-                pwrite_at(gamf, 2 * sizeof(unsigned), gamma.data(), (size_t)C * sizeof(double));
-                pwrite_at(xivf, 2 * sizeof(unsigned), xiv.data(), (size_t)C * sizeof(int));
+                write_dump(gamf, iteration, (unsigned)C, gamma.data(), sizeof(double));
+                write_dump(xivf, iteration, (unsigned)C, xiv.data(), sizeof(int));
             }
             if (rank == 0) {
                 hg_check(hgibbs_get_beta(dev, beta.data(), comp.data(), nullptr), "hgibbs_get_beta");
-                pwrite_at(xbetf, sizeof(unsigned), &iteration, sizeof(unsigned));
-                pwrite_at(xcpnf, sizeof(unsigned), &iteration, sizeof(unsigned));
-                pwrite_at(xbetf, 2 * sizeof(unsigned), beta.data(), (size_t)Mtot * sizeof(double));
-                pwrite_at(xcpnf, 2 * sizeof(unsigned), comp.data(), (size_t)Mtot * sizeof(int));
+                write_xfile(xbetf, iteration, beta.data(), Mtot, sizeof(double));
+                write_xfile(xcpnf, iteration, comp.data(), Mtot, sizeof(int));
             }
         }
     }
     if (rank == 0)
         std::printf("INFO   : rank %4d, time to process the data: %.3f sec, with %.3f (%.3f, %.3f) = %4.1f%% spent on allred (%d, %d)\n", rank,
                     now_s() - t_all, 0.0, 0.0, 0.0, 0.0, 0, 0);
-    for (FILE* f : {outf, betf, cpnf, acuf, xbetf, xcpnf, musf, epsf, mrkf, gamf, xivf})
-        if (f) std::fclose(f);
+    outs.close(false);
     hydra_chain_destroy(chain);
     hgibbs_destroy(dev);
     return 0;

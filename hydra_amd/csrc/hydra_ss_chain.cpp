@@ -1,5 +1,5 @@
 // hydra_ss_chain.cpp -- hydra_chain.cpp's iteration for summary statistics: the same initial values and
-// hyper-parameter draws, line for line, around hgibbs_ss_sweep instead of hgibbs_sweep.  What differs:
+// hyper-parameter draws (hg_chain_core.h) around hgibbs_ss_sweep instead of hgibbs_sweep.  What differs:
 //
 //   no residual  the state per marker is c_j = x_j'eps (on the device, or in this file's vectors for the host engine)
 //   mu           norm_rng(0, sigmaE / n): the columns and y sum to zero, so the mean of the residual plus the old mu is 0
@@ -13,97 +13,34 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/hgibbs.h"
-#include "hg_rng.h"
+#include "hg_chain_core.h"
 
-extern "C" void hgibbs_set_error_(const char* msg);
+using hg::V0E, hg::S02E;
 
-namespace {
-const double V0E = 0.0001, S02E = 0.0001, V0G = 0.0001, S02G = 0.0001; // src/BayesRRm.h:30-33
+static int cfail(const std::string& m) { return hg::chain_fail(m); }
 
-int cfail(const std::string& m)
-{
-    hgibbs_set_error_(m.c_str());
-    return 1;
-}
-} // namespace
-
-struct hydra_ss_chain {
+struct hydra_ss_chain : hg::ChainCore {
     hgibbs_t dev = nullptr; // null: the host engine on the vectors below
     uint32_t M = 0, W = 0;
     double n = 0.0;
-    int G = 1, K = 0;
-    int shuffle = 1;
-    std::vector<int32_t> groups, MtotGrp, order, cass, m0;
-    std::vector<double> cVa, cVaI, priorPi, estPi, sigmaG;
-    std::vector<uint8_t> adaV;
-    double sigmaE = 0.0, mu = 0.0;
-    hgibbs_rng_state rng{};
-    uint64_t last_nnz = 0;
-    uint32_t iteration = 0;
     // host engine
     std::vector<uint32_t> ahead;
     std::vector<double> band, xty, c, beta, acum;
     std::vector<int32_t> comp;
 };
 
-// the model tables, the seed and sigmaG ~ beta(1, 1), sigmaE, adaV: hydra_chain_create's, with y'y = n - 1
+// the shared core's initial values, and sigmaE with y'y = n - 1
 static int ss_init(hydra_ss_chain* c, const hydra_model_desc* model, const uint8_t* use)
 {
-    const uint32_t M = c->M;
-    c->G = model->G;
-    c->K = model->K;
-    c->shuffle = model->shuffle;
-    const int G = c->G, K = c->K, km1 = K - 1;
-    if (G < 1) return cfail("hydra_ss_chain_create: G must be >= 1");
-    if (K < 2) return cfail("hydra_ss_chain_create: K must be >= 2 (zero component + at least one mixture)");
-    c->groups.assign(M, 0);
-    if (model->groups) c->groups.assign(model->groups, model->groups + M);
-    for (uint32_t i = 0; i < M; ++i)
-        if (c->groups[i] < 0 || c->groups[i] >= G) return cfail("hydra_ss_chain_create: group index out of range");
-
-    // :1086-1110
-    c->cVa.assign((size_t)G * K, 0.0);
-    c->cVaI.assign((size_t)G * K, 0.0);
-    c->priorPi.assign((size_t)G * K, 0.0);
-    for (int g = 0; g < G; ++g) {
-        c->priorPi[g * K] = 0.5;
-        double s = 0.0;
-        for (int k = 1; k <= km1; ++k) {
-            const double v = model->mS[g * K + k];
-            if (!(v > 0.0)) return cfail("FATAL  : mixture value can only be strictly positive"); // :992-993
-            c->cVa[g * K + k] = v;
-            c->cVaI[g * K + k] = 1.0 / v;
-            s += v;
-        }
-        for (int k = 1; k <= km1; ++k) c->priorPi[g * K + k] = c->priorPi[g * K] * c->cVa[g * K + k] / s;
-    }
-    c->estPi = c->priorPi;
-    c->sigmaG.assign(G, 0.0);
-    c->cass.assign((size_t)G * K, 0);
-    c->m0.assign(G, 0);
-    c->MtotGrp.assign(G, 0);
-    for (uint32_t i = 0; i < M; ++i) c->MtotGrp[c->groups[i]] += 1;
-
-    // :1228-1240
-    hg::Mt gen{c->rng.x, 0};
-    gen.seed(model->seed);
-    for (int g = 0; g < G; ++g) c->sigmaG[g] = hg::beta_rng(gen, 1.0, 1.0);
-    for (int g = 0; g < G; ++g)
-        if (c->MtotGrp[g] == 0) c->sigmaG[g] = 0.0;
-    c->rng.idx = gen.idx;
-
-    c->order.resize(M);
-    for (uint32_t i = 0; i < M; ++i) c->order[i] = (int32_t)i;
+    if (model->G < 1) return cfail("hydra_ss_chain_create: G must be >= 1");
+    if (model->K < 2) return cfail("hydra_ss_chain_create: K must be >= 2 (zero component + at least one mixture)");
+    if (hg::core_init(*c, c->M, model, use, "hydra_ss_chain_create")) return 1;
     c->sigmaE = (c->n - 1.0) / c->n * 0.5; // :1580 with y'y = n - 1
-
-    // :1592-1597, and the markers the caller leaves out
-    c->adaV.assign(M, 1);
-    for (uint32_t i = 0; i < M; ++i)
-        if (c->sigmaG[c->groups[i]] == 0.0 || (use && !use[i])) c->adaV[i] = 0;
     return 0;
 }
 
@@ -116,19 +53,18 @@ int hydra_ss_chain_create(hgibbs_t dev, const hydra_model_desc* model, double n_
     uint32_t n_global = 0, n_local = 0, M = 0, row_begin = 0;
     if (hgibbs_dims(dev, &n_global, &n_local, &M, &row_begin)) return 1;
     if (n_global < 2 || M == 0) return cfail("hydra_ss_chain_create: load the panel's genotypes first (hgibbs_load_bed / hgibbs_synth_bed)");
-    hydra_ss_chain* c = new hydra_ss_chain();
+    std::unique_ptr<hydra_ss_chain> c(new hydra_ss_chain());
     c->dev = dev;
     c->M = M;
     c->W = W;
     c->n = n_eff;
     // the band first: it refuses n_eff, W, ahead and xty by name
-    if (hgibbs_ss_begin(dev, n_eff, W, ahead, xty) || ss_init(c, model, use) ||
+    if (hgibbs_ss_begin(dev, n_eff, W, ahead, xty) || ss_init(c.get(), model, use) ||
         hgibbs_set_model(dev, c->G, c->K, c->groups.data(), c->cVa.data(), c->cVaI.data())) {
         (void)hgibbs_ss_end(dev);
-        delete c;
         return 1;
     }
-    *out = c;
+    *out = c.release();
     return 0;
 }
 
@@ -139,14 +75,11 @@ int hydra_ss_chain_create_host(uint32_t M, const hydra_model_desc* model, double
     if (M == 0) return cfail("hydra_ss_chain_create_host: no markers");
     if (W == 0 || W > 4096u) return cfail("hydra_ss_chain_create_host: W must be in [1, 4096]");
     if (!(std::isfinite(n_eff) && n_eff >= 2.0)) return cfail("hydra_ss_chain_create_host: n_eff must be a finite number >= 2");
-    hydra_ss_chain* c = new hydra_ss_chain();
+    std::unique_ptr<hydra_ss_chain> c(new hydra_ss_chain());
     c->M = M;
     c->W = W;
     c->n = n_eff;
-    if (ss_init(c, model, use)) {
-        delete c;
-        return 1;
-    }
+    if (ss_init(c.get(), model, use)) return 1;
     c->ahead.assign(ahead, ahead + M);
     c->band.assign(band, band + (size_t)M * W);
     c->xty.assign(xty, xty + M);
@@ -154,7 +87,7 @@ int hydra_ss_chain_create_host(uint32_t M, const hydra_model_desc* model, double
     c->beta.assign(M, 0.0);
     c->acum.assign(M, 0.0);
     c->comp.assign(M, 0);
-    *out = c;
+    *out = c.release();
     return 0;
 }
 
@@ -205,24 +138,7 @@ int hydra_ss_chain_iterate(hydra_ss_chain_t c)
             sb += b * c->xty[i];
             sc += b * c->c[i];
         }
-    std::vector<double> dirin(K), pi(K);
-    for (int g = 0; g < G; ++g) {
-        if (c->MtotGrp[g] == 0) continue;
-        c->m0[g] = c->MtotGrp[g] - c->cass[g * K];
-        int rowsum = 0;
-        for (int k = 0; k < K; ++k) rowsum += c->cass[g * K + k];
-        if (c->m0[g] == 0 || rowsum == 0) {
-            for (uint32_t i = 0; i < M; ++i)
-                if (c->groups[i] == g) c->adaV[i] = 0;
-            c->sigmaG[g] = 0.0;
-            continue;
-        }
-        const double dm0 = (double)c->m0[g];
-        c->sigmaG[g] = hg::inv_scaled_chisq_rng(gen, V0G + dm0, (bsq[g] * dm0 + V0G * S02G) / (V0G + dm0));
-        for (int k = 0; k < K; ++k) dirin[k] = (double)c->cass[g * K + k] + 1.0;
-        hg::dirichlet_rng(gen, dirin.data(), K, pi.data());
-        for (int k = 0; k < K; ++k) c->estPi[g * K + k] = pi[k];
-    }
+    hg::core_hyper(*c, bsq.data(), gen);
 
     // :2685-2690
     const double e_sqn = ((dN - 1.0) - (sb + sc)) + dN * c->mu * c->mu;
@@ -243,13 +159,7 @@ int hydra_ss_chain_iterate(hydra_ss_chain_t c)
 int hydra_ss_chain_state(hydra_ss_chain_t c, double* sigmaE, double* mu, double* sigmaG, double* estPi, int32_t* m0, int32_t* cass, hgibbs_rng_state* rng)
 {
     if (!c) return cfail("hydra_ss_chain_state: null chain");
-    if (sigmaE) *sigmaE = c->sigmaE;
-    if (mu) *mu = c->mu;
-    if (sigmaG) std::copy(c->sigmaG.begin(), c->sigmaG.end(), sigmaG);
-    if (estPi) std::copy(c->estPi.begin(), c->estPi.end(), estPi);
-    if (m0) std::copy(c->m0.begin(), c->m0.end(), m0);
-    if (cass) std::copy(c->cass.begin(), c->cass.end(), cass);
-    if (rng) *rng = c->rng;
+    hg::core_state(*c, sigmaE, mu, sigmaG, estPi, m0, cass, rng);
     return 0;
 }
 
@@ -271,25 +181,9 @@ uint64_t hydra_ss_chain_last_nnz(hydra_ss_chain_t c) { return c ? c->last_nnz : 
 
 const int32_t* hydra_ss_chain_order(hydra_ss_chain_t c) { return c ? c->order.data() : nullptr; }
 
-/* the chain's .csv line (src/BayesRRm.cpp:2742-2760) */
 int hydra_ss_chain_csv_line(hydra_ss_chain_t c, uint32_t iteration, char* buf, size_t len)
 {
-    if (!c || !buf) return -1;
-    const int G = c->G, K = c->K;
-    size_t o = 0;
-    o += snprintf(buf + o, len - o, "%5d, %4d", (int)iteration, G);
-    double sg = 0.0;
-    for (int g = 0; g < G; ++g) {
-        o += snprintf(buf + o, len - o, ", %20.15f", c->sigmaG[g]);
-        sg += c->sigmaG[g];
-    }
-    int m0sum = 0;
-    for (int g = 0; g < G; ++g) m0sum += c->m0[g];
-    o += snprintf(buf + o, len - o, ", %20.15f, %20.15f, %7d, %4d, %2d", c->sigmaE, sg / (c->sigmaE + sg), m0sum, G, K);
-    for (int g = 0; g < G; ++g)
-        for (int k = 0; k < K; ++k) o += snprintf(buf + o, len - o, ", %20.15f", c->estPi[g * K + k]);
-    o += snprintf(buf + o, len - o, "\n");
-    return (int)o;
+    return (c && buf) ? hg::core_csv_line(*c, iteration, buf, len) : -1;
 }
 
 } // extern "C"

@@ -17,6 +17,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -111,7 +112,7 @@ int hydraw_chain_create(hgibbs_t dev, const hydraw_model_desc* model, const doub
     if (hgibbs_w_init(dev, failure_host)) return 1;
     if (hgibbs_w_set_model(dev, model->G, model->K, model->groups, model->mS, model->quad_points)) return 1;
     if (hgibbs_w_marker_stats(dev, nullptr, nullptr, nullptr)) return 1;
-    hydraw_chain* c = new hydraw_chain();
+    std::unique_ptr<hydraw_chain> c(new hydraw_chain());
     c->dev = dev;
     c->N = n_global;
     c->M = M;
@@ -147,10 +148,7 @@ int hydraw_chain_create(hgibbs_t dev, const hydraw_model_desc* model, const doub
     c->alpha = bw::PI_BW / std::sqrt(denominator);
     std::vector<double> eps(n_global);
     for (uint32_t i = 0; i < n_global; ++i) eps[i] = y_host[i] - c->mu; // :823-826
-    if (hgibbs_set_residual(dev, eps.data() + row_begin)) { // this rank's rows
-        delete c;
-        return 1;
-    }
+    if (hgibbs_set_residual(dev, eps.data() + row_begin)) return 1; // this rank's rows
     c->sigmaG.assign(G, bw::PI_SQUARED / (6 * std::pow(c->alpha, 2)) / G); // :828
     c->sumSigmaG = 0.0;
     for (int g = 0; g < G; ++g) c->sumSigmaG += c->sigmaG[g];
@@ -161,7 +159,7 @@ int hydraw_chain_create(hgibbs_t dev, const hydraw_model_desc* model, const doub
     Mt gen{c->rng.x, 0};
     gen.seed(model->seed); // dist.reset_rng(seed + rank*1000), rank 0, :937
     c->rng.idx = gen.idx;
-    *out = c;
+    *out = c.release();
     return 0;
 }
 
