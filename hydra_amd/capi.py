@@ -25,6 +25,7 @@ ABI_SYMBOLS = [
     "hgibbs_ld_scores", "hgibbs_last_ld_scores_ms",
     "hgibbs_ld_mask", "hgibbs_last_ld_mask_ms", "hgibbs_ld_greedy", "hgibbs_ld_clump",
     "hgibbs_ss_begin", "hgibbs_ss_sweep", "hgibbs_ss_state", "hgibbs_ss_band_get", "hgibbs_ss_end", "hgibbs_last_ss_ms", "hgibbs_ss_sweep_host",
+    "hgibbs_ss_partition", "hgibbs_ss_sweep_streams", "hgibbs_ss_sweep_streams_host", "hydra_ss_chain_set_streams", "hydra_ss_chain_streams",
     "hydra_ss_chain_create", "hydra_ss_chain_create_host", "hydra_ss_chain_destroy", "hydra_ss_chain_iterate", "hydra_ss_chain_state",
     "hydra_ss_chain_effects", "hydra_ss_chain_last_nnz", "hydra_ss_chain_order", "hydra_ss_chain_csv_line",
     "hgibbs_marker_dots", "hgibbs_last_marker_dots_ms", "hgibbs_marker_class_sums", "hgibbs_last_marker_class_sums_ms", "hgibbs_logit_null",
@@ -283,6 +284,12 @@ def lib():
     L.hgibbs_last_ss_ms.argtypes = [vp, dp, dp]
     L.hgibbs_ss_sweep_host.argtypes = [C.c_uint32, C.c_double, C.c_uint32, u32p, dp, dp, dp, ip, dp, C.c_int, C.c_int, ip, dp, dp, ip, C.c_double, dp, dp,
                                        u8p, rp, ip, u64p]
+    L.hgibbs_ss_partition.argtypes = [C.c_uint32, u32p, C.c_uint32, u32p, u32p]
+    L.hgibbs_ss_sweep_streams.argtypes = [vp, ip, C.c_double, dp, dp, u8p, C.c_uint32, u32p, rp, ip, u64p]
+    L.hgibbs_ss_sweep_streams_host.argtypes = [C.c_uint32, C.c_double, C.c_uint32, u32p, dp, dp, dp, ip, dp, C.c_int, C.c_int, ip, dp, dp, ip, C.c_double, dp,
+                                               dp, u8p, C.c_uint32, u32p, rp, ip, u64p]
+    L.hydra_ss_chain_set_streams.argtypes = [vp, C.c_uint32]
+    L.hydra_ss_chain_streams.argtypes = [vp, u32p, u32p, rp]
     L.hydra_ss_chain_create.argtypes = [vp, C.POINTER(ModelDesc), C.c_double, C.c_uint32, u32p, dp, u8p, C.POINTER(vp)]
     L.hydra_ss_chain_create_host.argtypes = [C.c_uint32, C.POINTER(ModelDesc), C.c_double, C.c_uint32, u32p, dp, dp, u8p, C.POINTER(vp)]
     L.hydra_ss_chain_destroy.argtypes = [vp]
@@ -428,6 +435,58 @@ def ss_sweep_host(n_eff, W, ahead, band, c, beta, components, acum, groups, cVa,
     check(lib().hgibbs_ss_sweep_host(M, float(n_eff), W, ah.ctypes.data_as(C_U32P), _dp(band), _dp(c), _dp(beta), _ip(components), _dp(acum), G, K,
                                      _ip(groups) if groups is not None else None, _dp(cVa), _dp(cVaI), _ip(order), float(sigmaE), _dp(sigmaG),
                                      _dp(estPi), _u8(adaV), C.byref(rng), _ip(cass), C.byref(nnz)))
+    return cass, nnz.value
+
+
+def ss_partition(ahead, S_max):
+    """hgibbs_ss_partition (host only): the bounds of at most S_max intervals of whole LD blocks, (S + 1,) uint32 from 0 to M."""
+    ah = np.ascontiguousarray(ahead, dtype=np.uint32)
+    bounds = np.zeros(max(int(S_max), 0) + 1 if 0 <= int(S_max) <= 1024 else 1, dtype=np.uint32)
+    S = C.c_uint32()
+    check(lib().hgibbs_ss_partition(ah.shape[0], ah.ctypes.data_as(C_U32P), int(S_max) & 0xffffffff, bounds.ctypes.data_as(C_U32P), C.byref(S)))
+    return bounds[:S.value + 1].copy()
+
+
+class _RngArray:
+    """A list of RngState as the contiguous array the streams' calls take; `back()` copies the states into the list's items again."""
+
+    def __init__(self, rngs):
+        self.rngs = list(rngs)
+        self.arr = (RngState * max(len(self.rngs), 1))()
+        for a, r in zip(self.arr, self.rngs):
+            C.memmove(C.byref(a), C.byref(r), C.sizeof(RngState))
+
+    def back(self):
+        for a, r in zip(self.arr, self.rngs):
+            C.memmove(C.byref(r), C.byref(a), C.sizeof(RngState))
+
+
+def ss_sweep_streams_host(n_eff, W, ahead, band, c, beta, components, acum, groups, cVa, cVaI, order, sigmaE, sigmaG, estPi, adaV, bounds, rngs, S=None):
+    """hgibbs_ss_sweep_streams_host (host only): ss_sweep_host with the intervals `bounds` (S + 1) of independent LD blocks, swept one
+    after the other, interval s with rngs[s] (a list of RngState, updated in place).  Returns (cass[G, K], nnz_updates)."""
+    for a, t in ((c, np.float64), (beta, np.float64), (acum, np.float64), (components, np.int32)):
+        if a.dtype != t or not a.flags.c_contiguous:
+            raise ValueError("ss_sweep_streams_host: the state must be contiguous float64 / int32 arrays (they are updated in place)")
+    M = c.shape[0]
+    band = np.ascontiguousarray(band, dtype=np.float64)
+    cVa = np.ascontiguousarray(cVa, dtype=np.float64)
+    cVaI = np.ascontiguousarray(cVaI, dtype=np.float64)
+    G, K = cVa.shape
+    ah = ss_ahead(M, W, ahead)
+    groups = None if groups is None else np.ascontiguousarray(groups, dtype=np.int32)
+    order = np.ascontiguousarray(order, dtype=np.int32)
+    sigmaG = np.ascontiguousarray(sigmaG, dtype=np.float64)
+    estPi = np.ascontiguousarray(estPi, dtype=np.float64)
+    adaV = np.ascontiguousarray(adaV, dtype=np.uint8)
+    bounds = np.ascontiguousarray(bounds, dtype=np.uint32)
+    S = bounds.shape[0] - 1 if S is None else S
+    ra = _RngArray(rngs)
+    cass = np.zeros((G, K), dtype=np.int32)
+    nnz = C.c_uint64()
+    check(lib().hgibbs_ss_sweep_streams_host(M, float(n_eff), W, ah.ctypes.data_as(C_U32P), _dp(band), _dp(c), _dp(beta), _ip(components), _dp(acum), G, K,
+                                             _ip(groups) if groups is not None else None, _dp(cVa), _dp(cVaI), _ip(order), float(sigmaE), _dp(sigmaG),
+                                             _dp(estPi), _u8(adaV), S, bounds.ctypes.data_as(C_U32P), ra.arr, _ip(cass), C.byref(nnz)))
+    ra.back()
     return cass, nnz.value
 
 
@@ -1208,6 +1267,25 @@ class Device:
         check(self.L.hgibbs_ss_sweep(self.h, _ip(order), float(sigmaE), _dp(sigmaG), _dp(estPi), _u8(adaV), C.byref(rng), _ip(cass), C.byref(nnz)))
         return cass, nnz.value
 
+    def ss_sweep_streams(self, order, sigmaE, sigmaG, estPi, adaV, bounds, rngs, S=None):
+        """hgibbs_ss_sweep_streams: ss_sweep with one workgroup per interval of `bounds` (S + 1); rngs: a list of S RngState, updated in
+        place.  Returns (cass[G,K], nnz_updates)."""
+        order = np.ascontiguousarray(order, dtype=np.int32)
+        sigmaG = np.ascontiguousarray(sigmaG, dtype=np.float64)
+        estPi = np.ascontiguousarray(estPi, dtype=np.float64)
+        adaV = np.ascontiguousarray(adaV, dtype=np.uint8)
+        bounds = np.ascontiguousarray(bounds, dtype=np.uint32)
+        if order.shape != (self.M,) or adaV.shape != (self.M,):
+            raise ValueError("ss_sweep_streams: order and adaV must have M entries")
+        S = bounds.shape[0] - 1 if S is None else S
+        ra = _RngArray(rngs)
+        cass = np.zeros((self.G, self.K), dtype=np.int32)
+        nnz = C.c_uint64()
+        check(self.L.hgibbs_ss_sweep_streams(self.h, _ip(order), float(sigmaE), _dp(sigmaG), _dp(estPi), _u8(adaV), S, bounds.ctypes.data_as(C_U32P),
+                                             ra.arr, _ip(cass), C.byref(nnz)))
+        ra.back()
+        return cass, nnz.value
+
     def ss_state(self):
         """hgibbs_ss_state: (c, sum beta_j b_j, sum beta_j c_j)."""
         c = np.zeros(self.M)
@@ -1336,7 +1414,7 @@ class SsChain:
     """hydra_ss_chain_t: hydra_chain's iteration from summary statistics.  dev: a Device that holds the panel (the device engine), or
     None with `band` (M, W) for the host engine, which needs no device."""
 
-    def __init__(self, dev, n_eff, W, xty, ahead=None, band=None, use=None, mS=None, groups=None, seed=1222, shuffle=1):
+    def __init__(self, dev, n_eff, W, xty, ahead=None, band=None, use=None, mS=None, groups=None, seed=1222, shuffle=1, streams=None):
         self.dev = dev
         self.L = lib()
         if mS is None:
@@ -1361,6 +1439,24 @@ class SsChain:
             ah = ss_ahead(self.M, W, ahead)
             check(self.L.hydra_ss_chain_create_host(self.M, C.byref(d), float(n_eff), W, ah.ctypes.data_as(C_U32P), _dp(band), _dp(xty),
                                                     _u8(use) if use is not None else None, C.byref(self.h)))
+        if streams is not None:
+            self.set_streams(streams)
+
+    def set_streams(self, S_max):
+        """hydra_ss_chain_set_streams: independent LD blocks in at most S_max parallel streams; before the first iteration only."""
+        check(self.L.hydra_ss_chain_set_streams(self.h, int(S_max) & 0xffffffff))
+
+    def streams(self):
+        """hydra_ss_chain_streams: (bounds (S + 1,) uint32, [RngState] * S); (empty, []) for the single stream."""
+        S = C.c_uint32()
+        check(self.L.hydra_ss_chain_streams(self.h, C.byref(S), None, None))
+        if S.value == 0:
+            return np.zeros(0, dtype=np.uint32), []
+        bounds = np.zeros(S.value + 1, dtype=np.uint32)
+        ra = _RngArray([RngState() for _ in range(S.value)])
+        check(self.L.hydra_ss_chain_streams(self.h, None, bounds.ctypes.data_as(C_U32P), ra.arr))
+        ra.back()
+        return bounds, ra.rngs
 
     def __del__(self):
         try:

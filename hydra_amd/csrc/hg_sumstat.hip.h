@@ -13,9 +13,14 @@
 //             ahead     the next marker's c, effect, group and window are loaded before the decision of this one; c is loaded again
 //                       after an update, since the next marker may lie inside the window just updated.
 //             memory    c is read and written with ordinary vector loads and stores; what orders them is the workgroup barrier.
+//   streams   k_ss_sweep_streams: the same marker loop (ss_sweep_body), one workgroup per interval of independent
+//             LD blocks, each with a generator of its own.  A workgroup touches c, beta, acum and comp at its own interval only (a cut
+//             is where no window crosses), so the barriers above are all the ordering there is; cass is counted with integer atomics.
 //   sums      k_ss_sums: sum beta_j b_j and sum beta_j c_j in marker order by one wave, the non-zero effects only (a zero effect adds
 //             +-0 to a sum that is never -0): a fixed order, so the bits repeat.
 #pragma once
+
+#include <cstddef>
 
 #include "hg_ss_step.h"
 
@@ -34,6 +39,14 @@ struct SsState {
     DevBuf<int32_t> order;
     DevBuf<uint8_t> ada;
     DevBuf<SsResult> res;
+    // hgibbs_ss_sweep_streams: the S generator states (625 words each), S results, S + 1 bounds; sized on first use
+    DevBuf<uint32_t> mts, bounds;
+    DevBuf<SsResult> sres;
+    uint32_t streams_cap = 0;
+    std::vector<uint32_t> ahead_host;
+    std::vector<uint8_t> cut;    // per marker: no window crosses the place before it
+    std::vector<int32_t> grouped;
+    std::vector<SsResult> sres_host;
     std::vector<uint8_t> ok;     // per marker: its standard deviation is finite
     std::vector<uint8_t> ada_host;
     double band_ms = 0.0, sweep_ms = 0.0;
@@ -42,6 +55,8 @@ struct SsState {
 namespace {
 
 constexpr int SS_TPB = 256;
+constexpr size_t SS_RNG_WORDS = sizeof(hgibbs_rng_state) / sizeof(uint32_t);
+static_assert(SS_RNG_WORDS == (size_t)MT_N + 1 && offsetof(hgibbs_rng_state, idx) == MT_N * sizeof(uint32_t), "a state is its 624 words, then its index");
 static_assert(SS_MAX_K == MAX_K, "the step's component arrays hold what hgibbs_set_model takes");
 
 // Thread per pair of the piece's band rows: band[j W + o] = scale r(j, j + o + 1), 0 outside j's window and where r is NaN
@@ -102,29 +117,35 @@ struct SsSweepParams {
     int32_t* comp;
     double* acum;
     const double* tables; // denom, logpi, hlog, sdk: G K each
-    uint32_t* mt;         // 624 words, in and out
+    uint32_t* mt;         // 624 words, in and out (per interval: S x 624)
     ZigTables zig;
     int32_t* cass;
     SsResult* res;
     uint32_t M, W, rng_idx;
     int K, GK;
     double dNm1, i_2sigE;
+    const uint32_t* bounds; // k_ss_sweep_streams: S + 1 positions of the grouped order (last: k_ss_sweep's arguments lie where they lay)
 };
 
-__global__ __launch_bounds__(SS_TPB) void k_ss_sweep(const SsSweepParams p)
+// The marker loop of both sweep kernels: the positions [p0, p1) of p.order with the generator whose 624 words lie at `mt` (in and
+// out) and whose index is rng_idx; the outcome goes to *res.  SHARED: other workgroups count into p.cass at the same time (an integer
+// atomicAdd, exact in any order); everything else the loop loads or stores lies at the markers of its own positions and their windows.
+template <bool SHARED>
+__device__ __forceinline__ void ss_sweep_body(const SsSweepParams& p, uint32_t p0, uint32_t p1, uint32_t* __restrict__ mt, uint32_t rng_idx,
+                                              SsResult* __restrict__ res)
 {
     __shared__ uint32_t s_mt[2 * MT_N];
     __shared__ double s_nx[129], s_ny[129];
     const uint32_t tid = threadIdx.x;
-    for (uint32_t i = tid; i < (uint32_t)MT_N; i += SS_TPB) s_mt[i] = p.mt[i];
+    for (uint32_t i = tid; i < (uint32_t)MT_N; i += SS_TPB) s_mt[i] = mt[i];
     for (uint32_t i = tid; i < 129u; i += SS_TPB) {
         s_nx[i] = p.zig.nx[i];
         s_ny[i] = p.zig.ny[i];
     }
     __syncthreads();
-    SsGen gen{s_mt, 0u, p.rng_idx};
+    SsGen gen{s_mt, 0u, rng_idx};
     const ZigTables zt{s_nx, s_ny, p.zig.ex, p.zig.ey};
-    const uint32_t M = p.M, W = p.W;
+    const uint32_t W = p.W;
     const int K = p.K;
     const double* denom = p.tables;
     const double* logpi = denom + p.GK;
@@ -135,15 +156,15 @@ __global__ __launch_bounds__(SS_TPB) void k_ss_sweep(const SsSweepParams p)
     unsigned long long nnz = 0;
     uint32_t err = 0;
     // the marker of this position (values loaded), the next one (index loaded)
-    uint32_t j = (uint32_t)p.order[0];
+    uint32_t j = (uint32_t)p.order[p0];
     double cj = c[j], bold = p.beta[j];
     int g = p.groups[j];
     uint32_t ada = p.ada[j], ah = p.ahead[j], bk = p.back[j];
-    uint32_t jn = M > 1u ? (uint32_t)p.order[1] : 0u;
+    uint32_t jn = p0 + 1u < p1 ? (uint32_t)p.order[p0 + 1u] : 0u;
 
-    for (uint32_t pos = 0; pos < M; ++pos) {
+    for (uint32_t pos = p0; pos < p1; ++pos) {
         // ahead: the next marker's values, the index of the one after it
-        const bool more = pos + 1u < M;
+        const bool more = pos + 1u < p1;
         double cn = 0.0, bn = 0.0;
         int gn = 0;
         uint32_t adan = 0, ahn = 0, bkn = 0, jnn = 0;
@@ -154,7 +175,7 @@ __global__ __launch_bounds__(SS_TPB) void k_ss_sweep(const SsSweepParams p)
             adan = p.ada[jn];
             ahn = p.ahead[jn];
             bkn = p.back[jn];
-            if (pos + 2u < M) jnn = (uint32_t)p.order[pos + 2u];
+            if (pos + 2u < p1) jnn = (uint32_t)p.order[pos + 2u];
         }
 
         double bnew = 0.0, ac = 1.0;
@@ -166,7 +187,10 @@ __global__ __launch_bounds__(SS_TPB) void k_ss_sweep(const SsSweepParams p)
                 break; // (uniform)
             }
             if (tid == 0) {
-                p.cass[o + k] += 1;
+                if (SHARED)
+                    atomicAdd(p.cass + (o + k), 1);
+                else
+                    p.cass[o + k] += 1;
                 p.comp[j] = k;
             }
         }
@@ -202,12 +226,27 @@ __global__ __launch_bounds__(SS_TPB) void k_ss_sweep(const SsSweepParams p)
     }
 
     __syncthreads();
-    for (uint32_t i = tid; i < (uint32_t)MT_N; i += SS_TPB) p.mt[i] = s_mt[gen.base + i];
+    for (uint32_t i = tid; i < (uint32_t)MT_N; i += SS_TPB) mt[i] = s_mt[gen.base + i];
     if (tid == 0) {
-        p.res->nnz = nnz;
-        p.res->rng_idx = gen.idx;
-        p.res->err = err;
+        res->nnz = nnz;
+        res->rng_idx = gen.idx;
+        res->err = err;
     }
+}
+
+__global__ __launch_bounds__(SS_TPB) void k_ss_sweep(const SsSweepParams p)
+{
+    ss_sweep_body<false>(p, 0u, p.M, p.mt, p.rng_idx, p.res);
+}
+
+// One workgroup per interval of independent blocks: positions [bounds[s], bounds[s + 1]) of the grouped order,
+// the generator at p.mt + 625 s as the caller's hgibbs_rng_state holds it (624 words, then the index; the new index goes to res[s]).
+// No workgroup waits for another.
+__global__ __launch_bounds__(SS_TPB) void k_ss_sweep_streams(const SsSweepParams p)
+{
+    const uint32_t s = blockIdx.x;
+    uint32_t* mt = p.mt + (size_t)s * SS_RNG_WORDS;
+    ss_sweep_body<true>(p, p.bounds[s], p.bounds[s + 1u], mt, mt[MT_N], p.res + s);
 }
 
 // One wave: the two sums in marker order over the non-zero effects
@@ -288,6 +327,9 @@ extern "C" int hgibbs_ss_begin(hgibbs_t h, double n_eff, uint32_t W, const uint3
     HIP_TRY(hipMemcpy(mstd.data(), h->mstd, (size_t)M * sizeof(double), hipMemcpyDeviceToHost));
     s->ok.resize(M);
     for (uint32_t j = 0; j < M; ++j) s->ok[j] = std::isfinite(mstd[j]) ? 1 : 0;
+    s->cut.resize(M);
+    ss_cuts(M, ah.data(), s->cut.data());
+    s->ahead_host = ah;
     HIP_TRY(hipMemcpy(s->ahead, ah.data(), (size_t)M * sizeof(uint32_t), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(s->back, back.data(), (size_t)M * sizeof(uint32_t), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(s->xty, xty, (size_t)M * sizeof(double), hipMemcpyHostToDevice));
@@ -317,33 +359,23 @@ extern "C" int hgibbs_ss_begin(hgibbs_t h, double n_eff, uint32_t W, const uint3
     return 0;
 }
 
-extern "C" int hgibbs_ss_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const double* sigmaG_host, const double* estPi_host,
-                               const uint8_t* adaV_host, hgibbs_rng_state* rng, int32_t* cass_host, uint64_t* nnz_updates)
+namespace {
+
+// What both sweeps check and upload, and the kernel's arguments but for the generator and the result
+int ss_sweep_prepare(hgibbs_ctx* h, SsState* s, const int32_t* order, double sigmaE, const double* sigmaG_host, const double* estPi_host,
+                     const uint8_t* adaV_host, SsSweepParams& p)
 {
-    const char* who = "hgibbs_ss_sweep";
-    SsState* s = ss_of(h, who);
-    if (!s) return 1;
-    if (h->G < 1) return fail("%s: model not set", who);
-    if (!order_host || !sigmaG_host || !estPi_host || !adaV_host || !rng || !cass_host) return fail("%s: null argument", who);
-    if (rng->idx > (uint32_t)MT_N) return fail("%s: rng idx %u > 624", who, rng->idx);
     const uint32_t M = h->M;
     const int G = h->G, K = h->K;
-    for (uint32_t i = 0; i < M; ++i)
-        if (order_host[i] < 0 || (uint32_t)order_host[i] >= M) return fail("%s: order[%u]=%d outside [0,%u)", who, i, order_host[i], M);
-    HIP_TRY(hipSetDevice(h->device));
-    s->sweep_ms = 0.0;
-
     std::vector<double> tab((size_t)4 * G * K);
     ss_tables(G, K, s->n_eff - 1.0, sigmaE, sigmaG_host, estPi_host, h->cVa.data(), h->cVaI.data(), tab.data());
     s->ada_host.resize(M);
     for (uint32_t j = 0; j < M; ++j) s->ada_host[j] = (uint8_t)(adaV_host[j] && s->ok[j]); // a marker without a finite sd is never adaptive
     HIP_TRY(hipMemcpyAsync(h->tables, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(s->order, order_host, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(s->order, order, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(s->ada, s->ada_host.data(), (size_t)M, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->mt, rng->x, MT_N * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemsetAsync(h->cass, 0, (size_t)G * K * sizeof(int32_t), h->stream));
 
-    SsSweepParams p{};
     p.order = s->order;
     p.groups = h->groups;
     p.ada = s->ada;
@@ -355,17 +387,48 @@ extern "C" int hgibbs_ss_sweep(hgibbs_t h, const int32_t* order_host, double sig
     p.comp = h->comp;
     p.acum = h->acum;
     p.tables = h->tables;
-    p.mt = h->mt;
     p.zig = ZigTables{h->zig, h->zig + 129, h->zig + 258, h->zig + 515};
     p.cass = h->cass;
-    p.res = s->res;
     p.M = M;
     p.W = s->W;
-    p.rng_idx = rng->idx;
     p.K = K;
     p.GK = G * K;
     p.dNm1 = s->n_eff - 1.0;
     p.i_2sigE = 1.0 / (2.0 * sigmaE);
+    return 0;
+}
+
+// the checks of both sweeps on what the caller passes
+int ss_sweep_check(hgibbs_ctx* h, const char* who, const int32_t* order_host, const double* sigmaG_host, const double* estPi_host,
+                   const uint8_t* adaV_host, const void* rng, const int32_t* cass_host)
+{
+    if (h->G < 1) return fail("%s: model not set", who);
+    if (!order_host || !sigmaG_host || !estPi_host || !adaV_host || !rng || !cass_host) return fail("%s: null argument", who);
+    const uint32_t M = h->M;
+    for (uint32_t i = 0; i < M; ++i)
+        if (order_host[i] < 0 || (uint32_t)order_host[i] >= M) return fail("%s: order[%u]=%d outside [0,%u)", who, i, order_host[i], M);
+    return 0;
+}
+
+} // namespace
+
+extern "C" int hgibbs_ss_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const double* sigmaG_host, const double* estPi_host,
+                               const uint8_t* adaV_host, hgibbs_rng_state* rng, int32_t* cass_host, uint64_t* nnz_updates)
+{
+    const char* who = "hgibbs_ss_sweep";
+    SsState* s = ss_of(h, who);
+    if (!s) return 1;
+    if (ss_sweep_check(h, who, order_host, sigmaG_host, estPi_host, adaV_host, rng, cass_host)) return 1;
+    if (rng->idx > (uint32_t)MT_N) return fail("%s: rng idx %u > 624", who, rng->idx);
+    HIP_TRY(hipSetDevice(h->device));
+    s->sweep_ms = 0.0;
+
+    SsSweepParams p{};
+    if (ss_sweep_prepare(h, s, order_host, sigmaE, sigmaG_host, estPi_host, adaV_host, p)) return 1;
+    HIP_TRY(hipMemcpyAsync(h->mt, rng->x, MT_N * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    p.mt = h->mt;
+    p.res = s->res;
+    p.rng_idx = rng->idx;
     double ms = 0.0;
     if (lap_begin(h)) return 1;
     k_ss_sweep<<<1, SS_TPB, 0, h->stream>>>(p);
@@ -375,9 +438,62 @@ extern "C" int hgibbs_ss_sweep(hgibbs_t h, const int32_t* order_host, double sig
     HIP_TRY(hipMemcpy(&res, s->res, sizeof res, hipMemcpyDeviceToHost));
     if (res.err) return fail("%s: sweep position %u (marker %d): the component walk found no component (logL overflow)", who, res.err - 1u, order_host[res.err - 1u]);
     HIP_TRY(hipMemcpy(rng->x, h->mt, MT_N * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(cass_host, h->cass, (size_t)G * K * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(cass_host, h->cass, (size_t)h->G * h->K * sizeof(int32_t), hipMemcpyDeviceToHost));
     rng->idx = res.rng_idx;
     if (nnz_updates) *nnz_updates = res.nnz;
+    s->sweep_ms = ms;
+    return 0;
+}
+
+extern "C" int hgibbs_ss_sweep_streams(hgibbs_t h, const int32_t* order_host, double sigmaE, const double* sigmaG_host, const double* estPi_host,
+                                       const uint8_t* adaV_host, uint32_t S, const uint32_t* bounds, hgibbs_rng_state* rngs, int32_t* cass_host,
+                                       uint64_t* nnz_updates)
+{
+    const char* who = "hgibbs_ss_sweep_streams";
+    SsState* s = ss_of(h, who);
+    if (!s) return 1;
+    if (ss_sweep_check(h, who, order_host, sigmaG_host, estPi_host, adaV_host, rngs, cass_host)) return 1;
+    if (!bounds) return fail("%s: null argument", who);
+    const uint32_t M = h->M;
+    char why[256];
+    if (ss_streams_check(M, s->ahead_host.data(), s->cut.data(), S, bounds, rngs, why, sizeof why)) return fail("%s: %s", who, why);
+    s->grouped.resize(M);
+    if (const uint32_t bad = ss_group_order(M, order_host, S, bounds, s->grouped.data()))
+        return fail("%s: order[%u] = %d repeats a marker: the order must be a permutation", who, bad - 1u, order_host[bad - 1u]);
+    HIP_TRY(hipSetDevice(h->device));
+    s->sweep_ms = 0.0;
+    if (S > s->streams_cap) {
+        s->streams_cap = 0;
+        if (s->mts.alloc((size_t)S * SS_RNG_WORDS) || s->sres.alloc(S) || s->bounds.alloc((size_t)S + 1)) return 1;
+        s->streams_cap = S;
+    }
+
+    SsSweepParams p{};
+    if (ss_sweep_prepare(h, s, s->grouped.data(), sigmaE, sigmaG_host, estPi_host, adaV_host, p)) return 1;
+    HIP_TRY(hipMemcpyAsync(s->mts, rngs, (size_t)S * sizeof(hgibbs_rng_state), hipMemcpyHostToDevice, h->stream)); // the S states in one copy
+    HIP_TRY(hipMemcpyAsync(s->bounds, bounds, ((size_t)S + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    p.mt = s->mts;
+    p.bounds = s->bounds;
+    p.res = s->sres;
+    double ms = 0.0;
+    if (lap_begin(h)) return 1;
+    k_ss_sweep_streams<<<S, SS_TPB, 0, h->stream>>>(p);
+    HIP_TRY(hipGetLastError());
+    if (lap_end(h, ms)) return 1;
+    s->sres_host.resize(S);
+    HIP_TRY(hipMemcpy(s->sres_host.data(), s->sres, (size_t)S * sizeof(SsResult), hipMemcpyDeviceToHost));
+    uint64_t nnz = 0;
+    for (uint32_t i = 0; i < S; ++i) {
+        const SsResult& r = s->sres_host[i];
+        if (r.err)
+            return fail("%s: stream %u, sweep position %u of its %u (marker %d): the component walk found no component (logL overflow)", who, i,
+                        r.err - 1u - bounds[i], bounds[i + 1] - bounds[i], s->grouped[r.err - 1u]);
+        nnz += r.nnz;
+    }
+    HIP_TRY(hipMemcpy(rngs, s->mts, (size_t)S * sizeof(hgibbs_rng_state), hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < S; ++i) rngs[i].idx = s->sres_host[i].rng_idx;
+    HIP_TRY(hipMemcpy(cass_host, h->cass, (size_t)h->G * h->K * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (nnz_updates) *nnz_updates = nnz;
     s->sweep_ms = ms;
     return 0;
 }

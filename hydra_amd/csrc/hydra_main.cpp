@@ -110,6 +110,8 @@
 // (--bfile, or the sparse pair; --pheno is optional and only selects rows): .csv, .bet, .cpn and .acu in the chain's formats, so
 // --predict-bfile and --pve read them.  Not covered: an LD band from a file or another cohort, covariates,
 // BayesW, checkpoint and restart, several processes, GCTB's formats; parity with GCTB's SBayesR has not been run.
+// `--sumstats-streams S` (1..1024) sweeps the independent LD blocks of the window (chromosomes, gaps wider than a kb window) at the
+// same time in up to S streams, each from a generator of its own: the same posterior, another realisation.
 //
 // Not reproduced (out of scope for the hot path): the mixed
 // in-memory representation (--threshold-fnz), --sparse-sync/--bed-sync, --check-RAM,
@@ -201,6 +203,8 @@ struct Options { // src/options.hpp:20-138 (subset that reaches bayesMPI)
     bool blocksPerRankGiven = false;                 // --blocks-per-rank n: hydra's marker-sharded layout, no meaning here
     bool sumstats = false, sumstatsWindowGiven = false, sumstatsKbGiven = false, sumstatsNGiven = false; // --sumstats FILE; which --sumstats-* were given
     std::string sumstatsFile, sumstatsWindow, sumstatsKb, sumstatsN; // --sumstats-window W, --sumstats-window-kb KB, --sumstats-n N as given (checked before the device)
+    bool sumstatsStreamsGiven = false; // --sumstats-streams S: independent LD blocks in up to S parallel streams
+    std::string sumstatsStreams;
     bool saveGiven = false, ignoreXfilesGiven = false; // --save, --ignore-xfiles on the command line (--sumstats takes no checkpoint option)
     int batch = 0, cpg = 0; // tuning knobs of this build (not hydra's)
 };
@@ -331,6 +335,9 @@ Options parse(int argc, const char* argv[])
         } else if (a == "--sumstats-window-kb") {
             o.sumstatsKb = need(i);
             o.sumstatsKbGiven = true;
+        } else if (a == "--sumstats-streams") {
+            o.sumstatsStreams = need(i);
+            o.sumstatsStreamsGiven = true;
         } else if (a == "--sumstats-n") {
             o.sumstatsN = need(i);
             o.sumstatsNGiven = true;
@@ -3932,6 +3939,17 @@ int run_sumstats(const Options& opt, const Cohort& co, const std::vector<int32_t
     md.mS = mS_flat.data();
     hydra_ss_chain_t chain = nullptr;
     hg_check(hydra_ss_chain_create(dev, &md, tab.n_eff, W, win.ahead.data(), tab.xty.data(), tab.use.data(), &chain), "hydra_ss_chain_create");
+    // independent LD blocks in parallel streams: the intervals come from the window, so they are known before the first sweep
+    uint32_t streams = 0, largest = 0;
+    if (opt.sumstatsStreamsGiven) {
+        long smax = 0;
+        whole_int(opt.sumstatsStreams, smax);
+        hg_check(hydra_ss_chain_set_streams(chain, (uint32_t)smax), "hydra_ss_chain_set_streams");
+        hg_check(hydra_ss_chain_streams(chain, &streams, nullptr, nullptr), "hydra_ss_chain_streams");
+        std::vector<uint32_t> bounds((size_t)streams + 1u);
+        hg_check(hydra_ss_chain_streams(chain, nullptr, bounds.data(), nullptr), "hydra_ss_chain_streams");
+        for (uint32_t s = 0; s < streams; ++s) largest = std::max(largest, bounds[s + 1] - bounds[s]);
+    }
     double band_ms = 0.0, sweep_ms = 0.0;
     hg_check(hgibbs_last_ss_ms(dev, &band_ms, &sweep_ms), "hgibbs_last_ss_ms");
 
@@ -3978,10 +3996,12 @@ int run_sumstats(const Options& opt, const Cohort& co, const std::vector<int32_t
     outs.close(true);
     hydra_ss_chain_destroy(chain);
     hgibbs_destroy(dev);
+    char par[96] = "";
+    if (streams) std::snprintf(par, sizeof par, " in %u streams (largest interval %u markers)", streams, largest);
     std::printf("SUMSTAT: %u markers used, %u left out (%u not in the table, %u with another allele pair, %u without usable BETA, SE and N, %u without a finite sd in the panel), "
-                "n_eff %.12g, band %u x %u doubles = %.1f MiB of device memory (built in %.3f ms), %.3f ms per sweep on the device over %u sweeps, wrote %s.{csv,bet,cpn,acu}\n",
+                "n_eff %.12g, band %u x %u doubles = %.1f MiB of device memory (built in %.3f ms), %.3f ms per sweep on the device over %u sweeps%s, wrote %s.{csv,bet,cpn,acu}\n",
                 used, M - used, M - tab.matched - tab.allele - tab.unusable, tab.allele, tab.unusable, nosd, tab.n_eff, M, W, (double)M * W * 8.0 / 1048576.0, band_ms,
-                sweeps ? sweep_total_ms / sweeps : 0.0, sweeps, base.c_str());
+                sweeps ? sweep_total_ms / sweeps : 0.0, sweeps, par, base.c_str());
     return 0;
 }
 
@@ -4226,7 +4246,8 @@ void check_modes(const Options& opt, int nranks)
 void check_sumstats(const Options& opt, int nranks)
 {
     if (!opt.sumstats) {
-        if (const char* o = first_given({{"--sumstats-window", opt.sumstatsWindowGiven}, {"--sumstats-window-kb", opt.sumstatsKbGiven}, {"--sumstats-n", opt.sumstatsNGiven}}))
+        if (const char* o = first_given({{"--sumstats-window", opt.sumstatsWindowGiven}, {"--sumstats-window-kb", opt.sumstatsKbGiven}, {"--sumstats-n", opt.sumstatsNGiven},
+                                          {"--sumstats-streams", opt.sumstatsStreamsGiven}}))
             fatal(std::string("FATAL  : ") + o + " needs --sumstats");
         return;
     }
@@ -4252,6 +4273,8 @@ void check_sumstats(const Options& opt, int nranks)
         fatal("FATAL  : --sumstats-window " + opt.sumstatsWindow + ": the window must be an integer from 1 to 4096 markers (the widest hgibbs_ss_begin takes)");
     if (opt.sumstatsNGiven && (!whole_num(opt.sumstatsN, t) || !std::isfinite(t) || !(t >= 2.0)))
         fatal("FATAL  : --sumstats-n " + opt.sumstatsN + ": the sample size must be a finite number >= 2");
+    if (opt.sumstatsStreamsGiven && (!whole_int(opt.sumstatsStreams, w) || w < 1 || w > 1024))
+        fatal("FATAL  : --sumstats-streams " + opt.sumstatsStreams + ": the number of streams must be an integer from 1 to 1024 (the most hgibbs_ss_sweep_streams takes)");
 }
 
 } // namespace

@@ -6,6 +6,8 @@
 //   e_sqn        (y'y - sum_j beta_j (b_j + c_j)) + n mu^2, with y'y = n - 1, from hgibbs_ss_state's two sums; an e_sqn <= 0 (a
 //                truncated band need not be positive definite) stops the iteration with an error and is never clamped
 //   covariates   none
+//   streams      hydra_ss_chain_set_streams: the sweep runs the band's independent blocks from generators of
+//                their own, seeded from this chain's; mu, the shuffle and the hyper-parameters stay on the chain's generator
 //
 // One struct drives either engine: the device's (hydra_ss_chain_create) or the host's (hydra_ss_chain_create_host, no device at all),
 // so the iteration that a CPU test holds to the oracle's chain is the one the device runs under.
@@ -28,10 +30,13 @@ struct hydra_ss_chain : hg::ChainCore {
     hgibbs_t dev = nullptr; // null: the host engine on the vectors below
     uint32_t M = 0, W = 0;
     double n = 0.0;
+    std::vector<uint32_t> ahead; // the window as the engine holds it
     // host engine
-    std::vector<uint32_t> ahead;
     std::vector<double> band, xty, c, beta, acum;
     std::vector<int32_t> comp;
+    // independent blocks in parallel streams; none: the single stream
+    std::vector<uint32_t> bounds;
+    std::vector<hgibbs_rng_state> streams;
 };
 
 // the shared core's initial values, and sigmaE with y'y = n - 1
@@ -64,6 +69,8 @@ int hydra_ss_chain_create(hgibbs_t dev, const hydra_model_desc* model, double n_
         (void)hgibbs_ss_end(dev);
         return 1;
     }
+    c->ahead.resize(M);
+    for (uint32_t j = 0; j < M; ++j) c->ahead[j] = ahead ? ahead[j] : std::min(W, M - 1u - j);
     *out = c.release();
     return 0;
 }
@@ -115,7 +122,16 @@ int hydra_ss_chain_iterate(hydra_ss_chain_t c)
 
     // :1709-2490; the generator travels with the call
     c->rng.idx = gen.idx;
-    if (c->dev) {
+    const uint32_t S = (uint32_t)c->streams.size();
+    if (S) { // the main generator is not touched by the sweep
+        if (c->dev ? hgibbs_ss_sweep_streams(c->dev, c->order.data(), c->sigmaE, c->sigmaG.data(), c->estPi.data(), c->adaV.data(), S, c->bounds.data(),
+                                             c->streams.data(), c->cass.data(), &c->last_nnz)
+                   : hgibbs_ss_sweep_streams_host(M, c->n, c->W, c->ahead.data(), c->band.data(), c->c.data(), c->beta.data(), c->comp.data(),
+                                                  c->acum.data(), G, K, c->groups.data(), c->cVa.data(), c->cVaI.data(), c->order.data(), c->sigmaE,
+                                                  c->sigmaG.data(), c->estPi.data(), c->adaV.data(), S, c->bounds.data(), c->streams.data(),
+                                                  c->cass.data(), &c->last_nnz))
+            return 1;
+    } else if (c->dev) {
         if (hgibbs_ss_sweep(c->dev, c->order.data(), c->sigmaE, c->sigmaG.data(), c->estPi.data(), c->adaV.data(), &c->rng, c->cass.data(), &c->last_nnz))
             return 1;
     } else if (hgibbs_ss_sweep_host(M, c->n, c->W, c->ahead.data(), c->band.data(), c->c.data(), c->beta.data(), c->comp.data(), c->acum.data(), G, K,
@@ -174,6 +190,40 @@ int hydra_ss_chain_effects(hydra_ss_chain_t c, double* beta, int32_t* components
     if (components) std::copy(c->comp.begin(), c->comp.end(), components);
     if (acum) std::copy(c->acum.begin(), c->acum.end(), acum);
     if (cvec) std::copy(c->c.begin(), c->c.end(), cvec);
+    return 0;
+}
+
+int hydra_ss_chain_set_streams(hydra_ss_chain_t c, uint32_t S_max)
+{
+    const char* who = "hydra_ss_chain_set_streams";
+    if (!c) return cfail(std::string(who) + ": null chain");
+    if (c->iteration > 0) return cfail(std::string(who) + ": the chain has run " + std::to_string(c->iteration) + " iteration(s): streams are set before the first");
+    if (!c->streams.empty()) return cfail(std::string(who) + ": streams are already set");
+    if (S_max < 1u || S_max > 1024u) return cfail(std::string(who) + ": S_max = " + std::to_string(S_max) + ", must be in [1, 1024]");
+    std::vector<uint32_t> bounds((size_t)S_max + 1u);
+    uint32_t S = 0;
+    if (hgibbs_ss_partition(c->M, c->ahead.data(), S_max, bounds.data(), &S)) return 1;
+    bounds.resize((size_t)S + 1u);
+    hg::Mt gen{c->rng.x, c->rng.idx};
+    std::vector<uint32_t> w(S);
+    for (uint32_t s = 0; s < S; ++s) w[s] = gen.next();
+    c->rng.idx = gen.idx;
+    c->streams.resize(S);
+    for (uint32_t s = 0; s < S; ++s) {
+        hg::Mt st{c->streams[s].x, 0};
+        st.seed(w[s]);
+        c->streams[s].idx = st.idx;
+    }
+    c->bounds = bounds;
+    return 0;
+}
+
+int hydra_ss_chain_streams(hydra_ss_chain_t c, uint32_t* S, uint32_t* bounds, hgibbs_rng_state* rngs)
+{
+    if (!c) return cfail("hydra_ss_chain_streams: null chain");
+    if (S) *S = (uint32_t)c->streams.size();
+    if (bounds) std::copy(c->bounds.begin(), c->bounds.end(), bounds);
+    if (rngs) std::copy(c->streams.begin(), c->streams.end(), rngs);
     return 0;
 }
 

@@ -473,6 +473,30 @@ int hgibbs_ss_sweep_host(uint32_t M, double n_eff, uint32_t W, const uint32_t* a
                          const int32_t* order, double sigmaE, const double* sigmaG, const double* estPi, const uint8_t* adaV,
                          hgibbs_rng_state* rng, int32_t* cass, uint64_t* nnz_updates);
 
+/* ---- independent LD blocks swept at the same time ---- */
+/* A cut lies before marker j (1 <= j < M) iff no window crosses that place: max over k < j of (k + ahead[k]) < j.  Between two cuts
+ * the band is a block of its own, and given mu, sigmaE, sigmaG and pi the effects of different blocks are conditionally independent:
+ * sweeping them at the same time, each from a generator of its own, is an exact Gibbs sampler of the same posterior.  It draws another
+ * realisation than hgibbs_ss_sweep does from one generator, so no parity with the single stream (or the reference) is claimed.
+ *   partition      (host only) walks the blocks in marker order into intervals: an interval closes as soon as it holds at least
+ *                  ceil(M / S_max) markers, the remainder is the last.  bounds (room for S_max + 1) gets 0 = bounds[0] < ... < bounds[S] = M,
+ *                  1 <= S <= S_max <= 1024; deterministic.
+ *   sweep_streams  hgibbs_ss_sweep with S generators: one launch, one workgroup per interval.  Interval s sweeps its own markers in the
+ *                  order `order_host` lists them, with rngs[s] (in and out).  cass and nnz_updates are the sums over the intervals.
+ *                  Refused by name beyond hgibbs_ss_sweep's refusals: S outside 1..1024, bounds that do not run from 0 to M strictly
+ *                  ascending, an interior bound that is not a cut (with the marker whose window crosses it), an idx above 624 in any
+ *                  state, an order that is no permutation.  With S = 1 it gives hgibbs_ss_sweep's bits.  hgibbs_last_ss_ms reports its
+ *                  kernel as it does hgibbs_ss_sweep's.
+ *   sweep_streams_host  (host only) the same on host arrays, interval after interval: what the device is held to. */
+int hgibbs_ss_partition(uint32_t M, const uint32_t* ahead, uint32_t S_max, uint32_t* bounds /* S_max + 1 */, uint32_t* S);
+int hgibbs_ss_sweep_streams(hgibbs_t h, const int32_t* order_host, double sigmaE, const double* sigmaG_host, const double* estPi_host,
+                            const uint8_t* adaV_host, uint32_t S, const uint32_t* bounds /* S + 1 */, hgibbs_rng_state* rngs /* S */,
+                            int32_t* cass_host, uint64_t* nnz_updates);
+int hgibbs_ss_sweep_streams_host(uint32_t M, double n_eff, uint32_t W, const uint32_t* ahead, const double* band, double* c, double* beta,
+                                 int32_t* components, double* acum, int G, int K, const int32_t* groups, const double* cVa, const double* cVaI,
+                                 const int32_t* order, double sigmaE, const double* sigmaG, const double* estPi, const uint8_t* adaV, uint32_t S,
+                                 const uint32_t* bounds, hgibbs_rng_state* rngs, int32_t* cass, uint64_t* nnz_updates);
+
 /* ---- dots of the loaded markers against dense vectors */
 /* For markers j in [m0, m0 + count) of the loaded BED and K vectors u_k over this rank's n_local individuals:
  *   out[(j - m0)*K + k]           = x_j'u_k = mstd_j (P_jk - mave_j Q_jk)      (NaN where mstd_j is not finite)
@@ -891,6 +915,13 @@ int hydra_ss_chain_effects(hydra_ss_chain_t c, double* beta, int32_t* components
 uint64_t hydra_ss_chain_last_nnz(hydra_ss_chain_t c);
 const int32_t* hydra_ss_chain_order(hydra_ss_chain_t c);
 int hydra_ss_chain_csv_line(hydra_ss_chain_t c, uint32_t iteration, char* buf, size_t len);
+/* Independent LD blocks in parallel streams, either engine, before the first iteration only: bounds from
+ * hgibbs_ss_partition(S_max); stream s is seeded with the generator's seeding rule from w_s, where w_0 .. w_{S-1} are the next S words
+ * of the chain's own generator at this call.  From then on an iteration calls hgibbs_ss_sweep_streams(_host); mu, the shuffle, the
+ * hyper-parameters and sigmaE stay on the chain's generator.  hydra_ss_chain_streams reads back S (0: single stream), bounds (S + 1)
+ * and the S states (any pointer may be NULL). */
+int hydra_ss_chain_set_streams(hydra_ss_chain_t c, uint32_t S_max);
+int hydra_ss_chain_streams(hydra_ss_chain_t c, uint32_t* S, uint32_t* bounds, hgibbs_rng_state* rngs);
 
 /* ======================================================================== */
 /* BayesW: Weibull survival model (src/BayesW.cpp); individuals shard as above  */

@@ -8,7 +8,13 @@ Before the chain, one sweep with every marker fixed (adaV = 0, every effect 0: n
 and in marker order.  One JSON line per case; --out appends them to a file as well.  One invocation is one GPU step: run it under
 `timeout`.
 
+--chromosomes C cuts the window into C index intervals with the relative sizes of the first C human autosomes (chromosome 1 about
+8 % of M at C = 22), as ld_window does per chromosome.  --streams S sweeps the independent blocks at the same time in at most S
+streams (hgibbs_ss_sweep_streams); the record then names the streams used, the largest interval and the
+ideal ratio M / largest against one stream.  Run the same cases without --streams for the single stream on the same band.
+
     python tools/ss_bench.py [--cases 10000x100000x128,20000x1000000x512] [--n-eff 4000000] [--signals 0.001] [--iters 6] [--out F]
+                             [--chromosomes C] [--streams S]
 """
 import argparse
 import json
@@ -21,6 +27,19 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from hydra_amd import capi  # noqa: E402
 
 
+# lengths of the human autosomes in Mb, rounded
+AUTOSOME_MB = [248, 242, 198, 190, 182, 171, 159, 145, 138, 134, 135, 133, 114, 107, 102, 90, 83, 80, 59, 64, 47, 51]
+
+
+def chromosome_ahead(M, W, C):
+    """(sizes, ahead): C intervals with the autosomes' relative sizes, ahead[j] = min(W, markers left in j's interval)"""
+    mb = np.array(AUTOSOME_MB[:C], dtype=np.float64)
+    ends = np.round(np.cumsum(mb) * (M / mb.sum())).astype(np.int64)
+    sizes = np.diff(np.concatenate([[0], ends]))
+    end_of = np.repeat(ends, sizes)
+    return sizes, np.minimum(W, end_of - 1 - np.arange(M)).astype(np.uint32)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="10000x100000x128,20000x1000000x512", help="NxMxW, comma-separated")
@@ -29,6 +48,8 @@ def main():
     ap.add_argument("--signals", type=float, default=0.001, help="fraction of markers with an effect")
     ap.add_argument("--iters", type=int, default=6)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--chromosomes", type=int, default=0, help="cut the window into this many intervals (1..22) sized like the human autosomes")
+    ap.add_argument("--streams", type=int, default=0, help="sweep independent blocks in at most this many parallel streams (1..1024)")
     args = ap.parse_args()
     out = open(args.out, "a") if args.out else None
 
@@ -49,17 +70,30 @@ def main():
         xty[sig] += (n - 1.0) * rs.normal(0.0, np.sqrt(0.5 / max(1, sig.sum())), int(sig.sum()))
         dev = capi.Device(0)
         dev.synth_bed(N, M, seed=5)
-        ch = capi.SsChain(dev, n, W, xty, seed=11)
+        ahead = chromosome_ahead(M, W, args.chromosomes)[1] if args.chromosomes else None
+        ch = capi.SsChain(dev, n, W, xty, ahead=ahead, seed=11, streams=args.streams or None)
+        bounds, _ = ch.streams()
         band_ms = dev.last_ss_ms()[0]
         rec = {"n_panel": N, "m": M, "W": W, "n_eff": n, "signals": int(sig.sum()), "band_mib": round(M * W * 8 / 2.0**20, 1), "band_ms": round(band_ms, 3)}
+        if args.chromosomes:
+            rec["chromosomes"] = args.chromosomes
+        if args.streams:
+            largest = int(np.diff(bounds.astype(np.int64)).max())
+            rec.update({"streams_max": args.streams, "streams": len(bounds) - 1, "largest_interval": largest, "ideal_ratio": round(M / largest, 3)})
 
         # the walk alone: nothing adaptive, every effect 0 (the first launch warms the code object up)
         fixed = np.zeros(M, dtype=np.uint8)
         sG, pi = np.array([0.5]), np.array([[0.5, 0.25, 0.15, 0.10]])
         rng = capi.RngState()
         rng.idx = 624
+        rngs = [capi.RngState() for _ in range(len(bounds) - 1)] if args.streams else []
+        for r in rngs:
+            r.idx = 624
         for name, order in (("warm", np.arange(M)), ("walk_marker_order", np.arange(M)), ("walk_shuffled", rs.permutation(M))):
-            _, nnz = dev.ss_sweep(order, 0.5, sG, pi, fixed, rng)
+            if args.streams:
+                _, nnz = dev.ss_sweep_streams(order, 0.5, sG, pi, fixed, bounds, rngs)
+            else:
+                _, nnz = dev.ss_sweep(order, 0.5, sG, pi, fixed, rng)
             assert nnz == 0
             if name != "warm":
                 ms = dev.last_ss_ms()[1]
