@@ -28,6 +28,9 @@ ABI_SYMBOLS = [
     "hgibbs_ss_partition", "hgibbs_ss_sweep_streams", "hgibbs_ss_sweep_streams_host", "hydra_ss_chain_set_streams", "hydra_ss_chain_streams",
     "hydra_ss_chain_create", "hydra_ss_chain_create_host", "hydra_ss_chain_destroy", "hydra_ss_chain_iterate", "hydra_ss_chain_state",
     "hydra_ss_chain_effects", "hydra_ss_chain_last_nnz", "hydra_ss_chain_order", "hydra_ss_chain_csv_line",
+    "hgibbs_ss_replicas", "hgibbs_ss_sweep_replicas", "hgibbs_ss_replica_sums", "hgibbs_ss_replica_get", "hgibbs_ss_replica_set_beta", "hgibbs_mcmc_diag",
+    "hydra_ss_multi_create", "hydra_ss_multi_destroy", "hydra_ss_multi_iterate", "hydra_ss_multi_state", "hydra_ss_multi_effects", "hydra_ss_multi_streams",
+    "hydra_ss_multi_last_nnz", "hydra_ss_multi_csv_line",
     "hgibbs_marker_dots", "hgibbs_last_marker_dots_ms", "hgibbs_marker_class_sums", "hgibbs_last_marker_class_sums_ms", "hgibbs_logit_null",
     "hgibbs_set_gram", "hgibbs_last_set_gram_ms", "hgibbs_set_tests",
     "hgibbs_spa_roots", "hgibbs_last_spa_ms", "hgibbs_spa_pvalue",
@@ -301,6 +304,21 @@ def lib():
     L.hydra_ss_chain_order.argtypes = [vp]
     L.hydra_ss_chain_order.restype = ip
     L.hydra_ss_chain_csv_line.argtypes = [vp, C.c_uint32, C.c_char_p, C.c_size_t]
+    L.hgibbs_ss_replicas.argtypes = [vp, C.c_uint32]
+    L.hgibbs_ss_sweep_replicas.argtypes = [vp, C.c_uint32, ip, dp, dp, dp, u8p, C.c_uint32, u32p, rp, ip, u64p]
+    L.hgibbs_ss_replica_sums.argtypes = [vp, dp, dp, dp]
+    L.hgibbs_ss_replica_get.argtypes = [vp, C.c_uint32, dp, ip, dp, dp]
+    L.hgibbs_ss_replica_set_beta.argtypes = [vp, C.c_uint32, dp]
+    L.hgibbs_mcmc_diag.argtypes = [C.c_uint32, C.c_uint32, dp, dp, dp, dp, dp]
+    L.hydra_ss_multi_create.argtypes = [vp, C.POINTER(ModelDesc), C.c_uint32, u32p, C.c_double, C.c_uint32, u32p, dp, u8p, C.c_uint32, C.POINTER(vp)]
+    L.hydra_ss_multi_destroy.argtypes = [vp]
+    L.hydra_ss_multi_iterate.argtypes = [vp]
+    L.hydra_ss_multi_state.argtypes = [vp, C.c_uint32, dp, dp, dp, dp, ip, ip, rp]
+    L.hydra_ss_multi_effects.argtypes = [vp, C.c_uint32, dp, ip, dp, dp]
+    L.hydra_ss_multi_streams.argtypes = [vp, u32p, u32p, rp]
+    L.hydra_ss_multi_last_nnz.argtypes = [vp, C.c_uint32]
+    L.hydra_ss_multi_last_nnz.restype = C.c_uint64
+    L.hydra_ss_multi_csv_line.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_char_p, C.c_size_t]
     L.hgibbs_marker_dots.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_int, dp, dp, dp]
     L.hgibbs_last_marker_dots_ms.argtypes = [vp, dp]
     L.hgibbs_marker_class_sums.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_int, dp, dp]
@@ -459,6 +477,17 @@ class _RngArray:
     def back(self):
         for a, r in zip(self.arr, self.rngs):
             C.memmove(C.byref(r), C.byref(a), C.sizeof(RngState))
+
+
+def mcmc_diag(x):
+    """hgibbs_mcmc_diag (host only): x (R, T), chain-major.  Returns (mean, sd, rhat, ess): split-R^ and the effective sample size of
+    the 2 R half-chains; rhat and ess are NaN where no half-chain moves."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    if x.ndim != 2:
+        raise ValueError("mcmc_diag: x must be (R, T)")
+    out = [C.c_double() for _ in range(4)]
+    check(lib().hgibbs_mcmc_diag(x.shape[0], x.shape[1], _dp(x), *[C.byref(o) for o in out]))
+    return tuple(o.value for o in out)
 
 
 def ss_sweep_streams_host(n_eff, W, ahead, band, c, beta, components, acum, groups, cVa, cVaI, order, sigmaE, sigmaG, estPi, adaV, bounds, rngs, S=None):
@@ -1300,6 +1329,62 @@ class Device:
         check(self.L.hgibbs_ss_band_get(self.h, m0, count, _dp(out)))
         return out
 
+    def ss_replicas(self, R):
+        """hgibbs_ss_replicas: R chains' state beside the handle's own, c = xty and every effect 0."""
+        check(self.L.hgibbs_ss_replicas(self.h, int(R) & 0xffffffff))
+
+    def ss_sweep_replicas(self, orders, sigmaE, sigmaG, estPi, adaV, rngs, bounds=None, R=None, S=None):
+        """hgibbs_ss_sweep_replicas: one launch for R replicas x S intervals.  orders (R, M); sigmaE (R,); sigmaG (R, G); estPi
+        (R, G, K); adaV (M,) for every replica or (R, M); bounds (S + 1) or None for the single stream; rngs: a list of R lists of S
+        RngState (or R RngState for the single stream), updated in place.  Returns (cass[R, G, K], nnz[R])."""
+        orders = np.ascontiguousarray(orders, dtype=np.int32)
+        R = orders.shape[0] if R is None else R
+        n = max(R, 1)
+        sigmaE = np.ascontiguousarray(sigmaE, dtype=np.float64)
+        sigmaG = np.ascontiguousarray(sigmaG, dtype=np.float64)
+        estPi = np.ascontiguousarray(estPi, dtype=np.float64)
+        adaV = np.ascontiguousarray(adaV, dtype=np.uint8)
+        if adaV.ndim == 1:
+            adaV = np.ascontiguousarray(np.broadcast_to(adaV, (orders.shape[0], adaV.shape[0])))
+        if orders.ndim != 2 or orders.shape[1] != self.M or adaV.shape != orders.shape:
+            raise ValueError("ss_sweep_replicas: orders must be (R, M), adaV (M,) or (R, M)")
+        # (an R the library refuses before it reads anything goes through as it is: the refusal is the library's)
+        if 1 <= R <= 64 and (sigmaE.size < R or sigmaG.size < R * self.G or estPi.size < R * self.G * self.K or orders.shape[0] < R):
+            raise ValueError("ss_sweep_replicas: sigmaE, sigmaG, estPi and orders must hold R replicas")
+        bounds = None if bounds is None else np.ascontiguousarray(bounds, dtype=np.uint32)
+        S = (1 if bounds is None else bounds.shape[0] - 1) if S is None else S
+        flat = [r for row in rngs for r in (row if isinstance(row, (list, tuple)) else [row])]
+        if 1 <= R <= 64 and 1 <= S <= 1024 and len(flat) < R * S:
+            raise ValueError("ss_sweep_replicas: rngs must hold R x S generators")
+        ra = _RngArray(flat)
+        cass = np.zeros((n, self.G, self.K), dtype=np.int32)
+        nnz = np.zeros(n, dtype=np.uint64)
+        check(self.L.hgibbs_ss_sweep_replicas(self.h, R, _ip(orders), _dp(sigmaE), _dp(sigmaG), _dp(estPi), _u8(adaV), S,
+                                              bounds.ctypes.data_as(C_U32P) if bounds is not None else None, ra.arr, _ip(cass),
+                                              nnz.ctypes.data_as(C.POINTER(C.c_uint64))))
+        ra.back()
+        return cass, nnz
+
+    def ss_replica_sums(self, R):
+        """hgibbs_ss_replica_sums: (sb[R], sc[R], bsq[R, G]) of the R allocated replicas."""
+        sb, sc, bsq = np.zeros(R), np.zeros(R), np.zeros((R, self.G))
+        check(self.L.hgibbs_ss_replica_sums(self.h, _dp(sb), _dp(sc), _dp(bsq)))
+        return sb, sc, bsq
+
+    def ss_replica_get(self, r):
+        """hgibbs_ss_replica_get: (beta, components, acum, c) of replica r."""
+        beta, acum, c = np.zeros(self.M), np.zeros(self.M), np.zeros(self.M)
+        comp = np.zeros(self.M, dtype=np.int32)
+        check(self.L.hgibbs_ss_replica_get(self.h, int(r) & 0xffffffff, _dp(beta), _ip(comp), _dp(acum), _dp(c)))
+        return beta, comp, acum, c
+
+    def ss_replica_set_beta(self, r, beta):
+        """hgibbs_ss_replica_set_beta: replica r's effects alone (c stays as it is)."""
+        beta = np.ascontiguousarray(beta, dtype=np.float64)
+        if beta.shape != (self.M,):
+            raise ValueError("ss_replica_set_beta: beta must have M entries")
+        check(self.L.hgibbs_ss_replica_set_beta(self.h, int(r) & 0xffffffff, _dp(beta)))
+
     def ss_end(self):
         check(self.L.hgibbs_ss_end(self.h))
 
@@ -1494,6 +1579,80 @@ class SsChain:
     def csv_line(self, it):
         buf = C.create_string_buffer(50000)
         n = self.L.hydra_ss_chain_csv_line(self.h, it, buf, 50000)
+        return buf.raw[:n].decode()
+
+
+class SsMultiChain:
+    """hydra_ss_multi_t: R chains from `seeds` on the one band of `dev`, one sweep launch per iteration; chain r is the SsChain with
+    seed = seeds[r] (and the same streams) bit for bit."""
+
+    def __init__(self, dev, n_eff, W, xty, seeds, ahead=None, use=None, mS=None, groups=None, shuffle=1, streams=None):
+        self.dev = dev
+        self.L = lib()
+        if mS is None:
+            mS = np.array([[0.0, 0.0001, 0.001, 0.01]])
+        self.mS = np.ascontiguousarray(mS, dtype=np.float64)
+        self.G, self.K = self.mS.shape
+        self.groups = None if groups is None else np.ascontiguousarray(groups, dtype=np.int32)
+        xty = np.ascontiguousarray(xty, dtype=np.float64)
+        self.M = xty.shape[0]
+        assert self.M == dev.M
+        use = None if use is None else np.ascontiguousarray(use, dtype=np.uint8)
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
+        self.R = seeds.shape[0]
+        ah = None if ahead is None else np.ascontiguousarray(ahead, dtype=np.uint32)
+        d = ModelDesc(0, shuffle, self.G, self.K, _ip(self.groups) if self.groups is not None else None, _dp(self.mS))
+        self.h = C.c_void_p()
+        check(self.L.hydra_ss_multi_create(dev.h, C.byref(d), self.R, seeds.ctypes.data_as(C_U32P), float(n_eff), W,
+                                           ah.ctypes.data_as(C_U32P) if ah is not None else None, _dp(xty), _u8(use) if use is not None else None,
+                                           0 if streams is None else int(streams) & 0xffffffff, C.byref(self.h)))
+        dev.G, dev.K, dev.ss_W = self.G, self.K, W
+
+    def __del__(self):
+        try:
+            if self.h:
+                self.L.hydra_ss_multi_destroy(self.h)
+        except Exception:
+            pass
+
+    def iterate(self):
+        check(self.L.hydra_ss_multi_iterate(self.h))
+
+    def state(self, r):
+        G, K = self.G, self.K
+        sE, mu = C.c_double(), C.c_double()
+        sG, pi = np.zeros(G), np.zeros((G, K))
+        m0, cass = np.zeros(G, dtype=np.int32), np.zeros((G, K), dtype=np.int32)
+        rng = RngState()
+        check(self.L.hydra_ss_multi_state(self.h, r, C.byref(sE), C.byref(mu), _dp(sG), _dp(pi), _ip(m0), _ip(cass), C.byref(rng)))
+        return {"sigmaE": sE.value, "mu": mu.value, "sigmaG": sG, "estPi": pi, "m0": m0, "cass": cass,
+                "rng_x": np.array(rng.x, dtype=np.uint32), "rng_idx": int(rng.idx)}
+
+    def effects(self, r):
+        """(beta, components, acum, c) of chain r"""
+        beta, acum, c = np.zeros(self.M), np.zeros(self.M), np.zeros(self.M)
+        comp = np.zeros(self.M, dtype=np.int32)
+        check(self.L.hydra_ss_multi_effects(self.h, r, _dp(beta), _ip(comp), _dp(acum), _dp(c)))
+        return beta, comp, acum, c
+
+    def streams(self):
+        """(bounds (S + 1,) uint32, R lists of S RngState); (empty, []) for the single stream."""
+        S = C.c_uint32()
+        check(self.L.hydra_ss_multi_streams(self.h, C.byref(S), None, None))
+        if S.value == 0:
+            return np.zeros(0, dtype=np.uint32), []
+        bounds = np.zeros(S.value + 1, dtype=np.uint32)
+        ra = _RngArray([RngState() for _ in range(self.R * S.value)])
+        check(self.L.hydra_ss_multi_streams(self.h, None, bounds.ctypes.data_as(C_U32P), ra.arr))
+        ra.back()
+        return bounds, [ra.rngs[r * S.value:(r + 1) * S.value] for r in range(self.R)]
+
+    def last_nnz(self, r):
+        return int(self.L.hydra_ss_multi_last_nnz(self.h, r))
+
+    def csv_line(self, r, it):
+        buf = C.create_string_buffer(50000)
+        n = self.L.hydra_ss_multi_csv_line(self.h, r, it, buf, 50000)
         return buf.raw[:n].decode()
 
 

@@ -43,6 +43,18 @@ struct SsState {
     DevBuf<uint32_t> mts, bounds;
     DevBuf<SsResult> sres;
     uint32_t streams_cap = 0;
+    // hgibbs_ss_replicas: R chains on the one band.  Replica r's c, effects, components, acum, order and mask lie at
+    // r M of the R x M arrays, its tables at r 4 G K, its counters at r G K, the generators and results of its S intervals at r S.
+    uint32_t R = 0, rep_gk = 0, rep_rs = 0; // replicas; the G K the tables and counters are sized for; the R S the generators are
+    DevBuf<double> rc, rbeta, racum, rtables, ri2s, rbsq;
+    DevBuf<int32_t> rcomp, rorder, rcass;
+    DevBuf<uint8_t> rada;
+    DevBuf<uint32_t> rmts, rbounds;
+    DevBuf<SsResult> rres, rsums;
+    uint32_t rep_g = 0;
+    std::vector<int32_t> rgrouped;
+    std::vector<uint8_t> rada_host;
+    std::vector<SsResult> rres_host;
     std::vector<uint32_t> ahead_host;
     std::vector<uint8_t> cut;    // per marker: no window crosses the place before it
     std::vector<int32_t> grouped;
@@ -247,6 +259,76 @@ __global__ __launch_bounds__(SS_TPB) void k_ss_sweep_streams(const SsSweepParams
     const uint32_t s = blockIdx.x;
     uint32_t* mt = p.mt + (size_t)s * SS_RNG_WORDS;
     ss_sweep_body<true>(p, p.bounds[s], p.bounds[s + 1u], mt, mt[MT_N], p.res + s);
+}
+
+// What k_ss_sweep_replicas is given beside SsSweepParams (a struct of its own: the two kernels above keep their arguments where they
+// lay).  In its SsSweepParams every per-chain pointer is replica 0's; replica r's lie r M (order, ada, c, beta, comp, acum), r 4 GK
+// (tables), r GK (cass) and r S (mt, res) further on.
+struct SsReplicaParams {
+    const double* i_2sigE; // R: 1 / (2 sigmaE) of each replica
+};
+
+// R chains on one band: the grid is S x R, workgroup (s, r) runs interval s of replica r.  The replica's
+// pointers are derived once, in uniform arithmetic; the marker loop is the one of the two kernels above.  The workgroups of one
+// replica count into that replica's cass; those of different replicas share nothing that is written.
+__global__ __launch_bounds__(SS_TPB) void k_ss_sweep_replicas(const SsSweepParams p0, const SsReplicaParams q)
+{
+    const uint32_t s = blockIdx.x, r = blockIdx.y, S = gridDim.x;
+    SsSweepParams p = p0;
+    const size_t rM = (size_t)r * p.M, rGK = (size_t)r * (size_t)p.GK;
+    p.order += rM;
+    p.ada += rM;
+    p.c += rM;
+    p.beta += rM;
+    p.comp += rM;
+    p.acum += rM;
+    p.tables += 4u * rGK;
+    p.cass += rGK;
+    p.i_2sigE = q.i_2sigE[r];
+    const size_t rs = (size_t)r * S + s;
+    uint32_t* mt = p.mt + rs * SS_RNG_WORDS;
+    ss_sweep_body<true>(p, p.bounds[s], p.bounds[s + 1u], mt, mt[MT_N], p.res + rs);
+}
+
+// One wave per replica: k_ss_sums' two sums, and per group the sum of beta^2 in marker order (hgibbs_beta_sqnorm's order), over the
+// non-zero effects.  The group sums are kept in LDS (G doubles, the launch's dynamic share) by lane 0, one add after the other.
+__global__ __launch_bounds__(64) void k_ss_replica_sums(const double* __restrict__ beta, const double* __restrict__ xty, const double* __restrict__ c,
+                                                        const int32_t* __restrict__ groups, uint32_t M, uint32_t G, SsResult* __restrict__ res,
+                                                        double* __restrict__ bsq)
+{
+    extern __shared__ double s_bsq[];
+    const uint32_t lane = threadIdx.x, r = blockIdx.x;
+    beta += (size_t)r * M;
+    c += (size_t)r * M;
+    for (uint32_t g = lane; g < G; g += 64u) s_bsq[g] = 0.0;
+    __syncthreads();
+    double sb = 0.0, sc = 0.0;
+    for (uint32_t base = 0; base < M; base += 64u) {
+        const uint32_t i = base + lane;
+        const double b = i < M ? beta[i] : 0.0;
+        double pb = 0.0, pc = 0.0, sq = 0.0;
+        int g = 0;
+        if (b != 0.0) {
+            pb = b * xty[i];
+            pc = b * c[i];
+            sq = b * b;
+            g = groups[i];
+        }
+        for (unsigned long long m = __ballot(b != 0.0); m; m &= m - 1ull) { // (uniform)
+            const int l = (int)__builtin_ctzll(m);
+            sb += __shfl(pb, l);
+            sc += __shfl(pc, l);
+            const double v = __shfl(sq, l);
+            const int gl = __shfl(g, l);
+            if (lane == 0) s_bsq[gl] += v;
+        }
+    }
+    __syncthreads();
+    for (uint32_t g = lane; g < G; g += 64u) bsq[(size_t)r * G + g] = s_bsq[g];
+    if (lane == 0) {
+        res[r].sums[0] = sb;
+        res[r].sums[1] = sc;
+    }
 }
 
 // One wave: the two sums in marker order over the non-zero effects
@@ -495,6 +577,241 @@ extern "C" int hgibbs_ss_sweep_streams(hgibbs_t h, const int32_t* order_host, do
     HIP_TRY(hipMemcpy(cass_host, h->cass, (size_t)h->G * h->K * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (nnz_updates) *nnz_updates = nnz;
     s->sweep_ms = ms;
+    return 0;
+}
+
+// ---- R chains on one band ----
+constexpr uint32_t SS_RMAX = 64u;      // replicas of one handle
+constexpr uint32_t SS_SUMS_GMAX = 8192u; // groups whose sums fit the LDS of k_ss_replica_sums
+
+namespace {
+
+// the replicas of a handle as the caller names them: null (with the error set) unless R of them are allocated
+SsState* ss_replicas_of(hgibbs_ctx* h, const char* who, uint32_t R)
+{
+    SsState* s = ss_of(h, who);
+    if (!s) return nullptr;
+    if (R < 1u || R > SS_RMAX) {
+        fail("%s: R = %u, must be in [1, %u]", who, R, SS_RMAX);
+        return nullptr;
+    }
+    if (s->R == 0) {
+        fail("%s: no replicas on this handle (hgibbs_ss_replicas first)", who);
+        return nullptr;
+    }
+    if (R != s->R) {
+        fail("%s: R = %u, but hgibbs_ss_replicas allocated %u replicas", who, R, s->R);
+        return nullptr;
+    }
+    return s;
+}
+
+} // namespace
+
+extern "C" int hgibbs_ss_replicas(hgibbs_t h, uint32_t R)
+{
+    const char* who = "hgibbs_ss_replicas";
+    SsState* s = ss_of(h, who);
+    if (!s) return 1;
+    if (R < 1u || R > SS_RMAX) return fail("%s: R = %u, must be in [1, %u]", who, R, SS_RMAX);
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const size_t M = h->M, n = (size_t)R * M;
+    // the earlier replicas go first: their memory counts as free for the new ones
+    s->R = 0;
+    for (DevBuf<double>* b : {&s->rc, &s->rbeta, &s->racum}) b->release();
+    for (DevBuf<int32_t>* b : {&s->rcomp, &s->rorder}) b->release();
+    s->rada.release();
+    const size_t bytes = n * (3 * sizeof(double) + 2 * sizeof(int32_t) + 1);
+    if (need_device_memory(bytes, "%s: R = %u replicas of %u markers (c, effects, acum, components, order and mask: %zu bytes, %.1f MiB)", who, R, h->M, bytes,
+                           bytes / 1048576.0))
+        return 1;
+    if (s->rc.alloc(n) || s->rbeta.alloc(n) || s->racum.alloc(n) || s->rcomp.alloc(n) || s->rorder.alloc(n) || s->rada.alloc(n) || s->ri2s.alloc(R) ||
+        s->rsums.alloc(R))
+        return 1;
+    for (uint32_t r = 0; r < R; ++r) HIP_TRY(hipMemcpyAsync(s->rc + r * M, s->xty, M * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(hipMemsetAsync(s->rbeta, 0, n * sizeof(double), h->stream));
+    HIP_TRY(hipMemsetAsync(s->racum, 0, n * sizeof(double), h->stream));
+    HIP_TRY(hipMemsetAsync(s->rcomp, 0, n * sizeof(int32_t), h->stream));
+    HIP_TRY(hipMemsetAsync(s->rsums, 0, R * sizeof(SsResult), h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    s->rep_gk = s->rep_rs = s->rep_g = 0; // (sized at the first sweep and the first sums: the model may be set after this call)
+    s->R = R;
+    return 0;
+}
+
+extern "C" int hgibbs_ss_sweep_replicas(hgibbs_t h, uint32_t R, const int32_t* orders, const double* sigmaE, const double* sigmaG, const double* estPi,
+                                        const uint8_t* adaV, uint32_t S, const uint32_t* bounds, hgibbs_rng_state* rngs, int32_t* cass_host,
+                                        uint64_t* nnz_updates)
+{
+    const char* who = "hgibbs_ss_sweep_replicas";
+    SsState* s = ss_replicas_of(h, who, R);
+    if (!s) return 1;
+    if (h->G < 1) return fail("%s: model not set", who);
+    if (!orders || !sigmaE || !sigmaG || !estPi || !adaV || !rngs || !cass_host) return fail("%s: null argument", who);
+    if (!bounds && S != 1u) return fail("%s: null argument", who);
+    const uint32_t M = h->M;
+    const int G = h->G, K = h->K;
+    const size_t GK = (size_t)G * K;
+    const uint32_t whole[2] = {0u, M};
+    if (!bounds) bounds = whole;
+    s->rgrouped.resize((size_t)R * M);
+    char why[256];
+    for (uint32_t r = 0; r < R; ++r) {
+        const int32_t* order = orders + (size_t)r * M;
+        for (uint32_t i = 0; i < M; ++i)
+            if (order[i] < 0 || (uint32_t)order[i] >= M) return fail("%s: replica %u: order[%u]=%d outside [0,%u)", who, r, i, order[i], M);
+        if (ss_streams_check(M, s->ahead_host.data(), s->cut.data(), S, bounds, rngs + (size_t)r * S, why, sizeof why)) return fail("%s: replica %u: %s", who, r, why);
+        if (const uint32_t bad = ss_group_order(M, order, S, bounds, s->rgrouped.data() + (size_t)r * M))
+            return fail("%s: replica %u: order[%u] = %d repeats a marker: the order must be a permutation", who, r, bad - 1u, order[bad - 1u]);
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    s->sweep_ms = 0.0;
+    const size_t RS = (size_t)R * S;
+    if (GK != s->rep_gk) {
+        s->rep_gk = 0;
+        if (s->rtables.alloc((size_t)R * 4 * GK) || s->rcass.alloc((size_t)R * GK)) return 1;
+        s->rep_gk = (uint32_t)GK;
+    }
+    if (RS > s->rep_rs) {
+        s->rep_rs = 0;
+        if (s->rmts.alloc(RS * SS_RNG_WORDS) || s->rres.alloc(RS) || s->rbounds.alloc((size_t)SS_SMAX + 1)) return 1;
+        s->rep_rs = (uint32_t)RS;
+    }
+
+    std::vector<double> tab((size_t)R * 4 * GK), i2s(R);
+    s->rada_host.resize((size_t)R * M);
+    for (uint32_t r = 0; r < R; ++r) {
+        ss_tables(G, K, s->n_eff - 1.0, sigmaE[r], sigmaG + (size_t)r * G, estPi + r * GK, h->cVa.data(), h->cVaI.data(), tab.data() + (size_t)r * 4 * GK);
+        i2s[r] = 1.0 / (2.0 * sigmaE[r]);
+        for (uint32_t j = 0; j < M; ++j) s->rada_host[(size_t)r * M + j] = (uint8_t)(adaV[(size_t)r * M + j] && s->ok[j]);
+    }
+    HIP_TRY(hipMemcpyAsync(s->rtables, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(s->ri2s, i2s.data(), (size_t)R * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(s->rorder, s->rgrouped.data(), (size_t)R * M * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(s->rada, s->rada_host.data(), (size_t)R * M, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemsetAsync(s->rcass, 0, (size_t)R * GK * sizeof(int32_t), h->stream));
+    HIP_TRY(hipMemcpyAsync(s->rmts, rngs, RS * sizeof(hgibbs_rng_state), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(s->rbounds, bounds, ((size_t)S + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+
+    SsSweepParams p{};
+    p.order = s->rorder;
+    p.groups = h->groups;
+    p.ada = s->rada;
+    p.ahead = s->ahead;
+    p.back = s->back;
+    p.band = s->band;
+    p.c = s->rc;
+    p.beta = s->rbeta;
+    p.comp = s->rcomp;
+    p.acum = s->racum;
+    p.tables = s->rtables;
+    p.mt = s->rmts;
+    p.zig = ZigTables{h->zig, h->zig + 129, h->zig + 258, h->zig + 515};
+    p.cass = s->rcass;
+    p.res = s->rres;
+    p.M = M;
+    p.W = s->W;
+    p.K = K;
+    p.GK = G * K;
+    p.dNm1 = s->n_eff - 1.0;
+    p.bounds = s->rbounds;
+    const SsReplicaParams q{s->ri2s};
+    double ms = 0.0;
+    if (lap_begin(h)) return 1;
+    k_ss_sweep_replicas<<<dim3(S, R), SS_TPB, 0, h->stream>>>(p, q);
+    HIP_TRY(hipGetLastError());
+    if (lap_end(h, ms)) return 1;
+    s->rres_host.resize(RS);
+    HIP_TRY(hipMemcpy(s->rres_host.data(), s->rres, RS * sizeof(SsResult), hipMemcpyDeviceToHost));
+    for (uint32_t r = 0; r < R; ++r) {
+        uint64_t nnz = 0;
+        for (uint32_t i = 0; i < S; ++i) {
+            const SsResult& res = s->rres_host[(size_t)r * S + i];
+            if (res.err)
+                return fail("%s: replica %u, stream %u, sweep position %u of its %u (marker %d): the component walk found no component (logL overflow)", who, r, i,
+                            res.err - 1u - bounds[i], bounds[i + 1] - bounds[i], s->rgrouped[(size_t)r * M + res.err - 1u]);
+            nnz += res.nnz;
+        }
+        if (nnz_updates) nnz_updates[r] = nnz;
+    }
+    HIP_TRY(hipMemcpy(rngs, s->rmts, RS * sizeof(hgibbs_rng_state), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < RS; ++i) rngs[i].idx = s->rres_host[i].rng_idx;
+    HIP_TRY(hipMemcpy(cass_host, s->rcass, (size_t)R * GK * sizeof(int32_t), hipMemcpyDeviceToHost));
+    s->sweep_ms = ms;
+    return 0;
+}
+
+extern "C" int hgibbs_ss_replica_sums(hgibbs_t h, double* sb, double* sc, double* bsq)
+{
+    const char* who = "hgibbs_ss_replica_sums";
+    SsState* s = ss_of(h, who);
+    if (!s) return 1;
+    if (s->R == 0) return fail("%s: no replicas on this handle (hgibbs_ss_replicas first)", who);
+    if (h->G < 1) return fail("%s: model not set", who);
+    const uint32_t R = s->R, G = (uint32_t)h->G;
+    if (G > SS_SUMS_GMAX) return fail("%s: G = %u groups, the sums are built for at most %u", who, G, SS_SUMS_GMAX);
+    HIP_TRY(hipSetDevice(h->device));
+    if (G != s->rep_g) {
+        s->rep_g = 0;
+        if (s->rbsq.alloc((size_t)R * G)) return 1;
+        s->rep_g = G;
+    }
+    k_ss_replica_sums<<<R, 64, (size_t)G * sizeof(double), h->stream>>>(s->rbeta, s->xty, s->rc, h->groups, h->M, G, s->rsums, s->rbsq);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    std::vector<SsResult> res(R);
+    HIP_TRY(hipMemcpy(res.data(), s->rsums, (size_t)R * sizeof(SsResult), hipMemcpyDeviceToHost));
+    for (uint32_t r = 0; r < R; ++r) {
+        if (sb) sb[r] = res[r].sums[0];
+        if (sc) sc[r] = res[r].sums[1];
+    }
+    if (bsq) HIP_TRY(hipMemcpy(bsq, s->rbsq, (size_t)R * G * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+namespace {
+
+SsState* ss_replica_at(hgibbs_ctx* h, const char* who, uint32_t r)
+{
+    SsState* s = ss_of(h, who);
+    if (!s) return nullptr;
+    if (s->R == 0) {
+        fail("%s: no replicas on this handle (hgibbs_ss_replicas first)", who);
+        return nullptr;
+    }
+    if (r >= s->R) {
+        fail("%s: replica %u outside [0, %u)", who, r, s->R);
+        return nullptr;
+    }
+    return s;
+}
+
+} // namespace
+
+extern "C" int hgibbs_ss_replica_get(hgibbs_t h, uint32_t r, double* beta, int32_t* comp, double* acum, double* c)
+{
+    SsState* s = ss_replica_at(h, "hgibbs_ss_replica_get", r);
+    if (!s) return 1;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const size_t M = h->M, o = (size_t)r * M;
+    if (beta) HIP_TRY(hipMemcpy(beta, s->rbeta + o, M * sizeof(double), hipMemcpyDeviceToHost));
+    if (comp) HIP_TRY(hipMemcpy(comp, s->rcomp + o, M * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (acum) HIP_TRY(hipMemcpy(acum, s->racum + o, M * sizeof(double), hipMemcpyDeviceToHost));
+    if (c) HIP_TRY(hipMemcpy(c, s->rc + o, M * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int hgibbs_ss_replica_set_beta(hgibbs_t h, uint32_t r, const double* beta)
+{
+    const char* who = "hgibbs_ss_replica_set_beta";
+    SsState* s = ss_replica_at(h, who, r);
+    if (!s) return 1;
+    if (!beta) return fail("%s: null argument", who);
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(s->rbeta + (size_t)r * h->M, beta, (size_t)h->M * sizeof(double), hipMemcpyHostToDevice));
     return 0;
 }
 

@@ -112,6 +112,9 @@
 // BayesW, checkpoint and restart, several processes, GCTB's formats; parity with GCTB's SBayesR has not been run.
 // `--sumstats-streams S` (1..1024) sweeps the independent LD blocks of the window (chromosomes, gaps wider than a kb window) at the
 // same time in up to S streams, each from a generator of its own: the same posterior, another realisation.
+// `--sumstats-chains R` (1..64) runs R chains from the seeds --seed + r on the one band, one launch per iteration for all of them
+// (DESIGN.md section 33): chain 0 writes the files of the run without the option, chain r >= 1 writes <name>.c<r>.{csv,bet,cpn,acu},
+// the files of the run with --seed raised by r; <name>.rhat holds split-R^ and the effective sample size of the hyper-parameters.
 //
 // Not reproduced (out of scope for the hot path): the mixed
 // in-memory representation (--threshold-fnz), --sparse-sync/--bed-sync, --check-RAM,
@@ -205,6 +208,8 @@ struct Options { // src/options.hpp:20-138 (subset that reaches bayesMPI)
     std::string sumstatsFile, sumstatsWindow, sumstatsKb, sumstatsN; // --sumstats-window W, --sumstats-window-kb KB, --sumstats-n N as given (checked before the device)
     bool sumstatsStreamsGiven = false; // --sumstats-streams S: independent LD blocks in up to S parallel streams
     std::string sumstatsStreams;
+    bool sumstatsChainsGiven = false; // --sumstats-chains R: R chains from the seeds --seed + r on one band, with a .rhat table
+    std::string sumstatsChains;
     bool saveGiven = false, ignoreXfilesGiven = false; // --save, --ignore-xfiles on the command line (--sumstats takes no checkpoint option)
     int batch = 0, cpg = 0; // tuning knobs of this build (not hydra's)
 };
@@ -338,6 +343,9 @@ Options parse(int argc, const char* argv[])
         } else if (a == "--sumstats-streams") {
             o.sumstatsStreams = need(i);
             o.sumstatsStreamsGiven = true;
+        } else if (a == "--sumstats-chains") {
+            o.sumstatsChains = need(i);
+            o.sumstatsChainsGiven = true;
         } else if (a == "--sumstats-n") {
             o.sumstatsN = need(i);
             o.sumstatsNGiven = true;
@@ -3890,6 +3898,126 @@ SumstatTable read_sumstats(const std::string& path, const BimRows& bim, unsigned
     return t;
 }
 
+// --sumstats-chains: R chains on the band of `dev`, from the model `md` with the seeds md.seed + r.  Chain 0's
+// files are <base>.*, chain r's <base>.c<r>.*; <base>.rhat holds the convergence table over the thinned records at or after
+// --burn-in.  Returns what the closing line reports: streams, largest interval, sweeps, device ms of all launches, largest R^.
+struct ChainsReport {
+    uint32_t streams = 0, largest = 0, chains = 0;
+    unsigned sweeps = 0;
+    double sweep_total_ms = 0.0, band_ms = 0.0, max_rhat = std::numeric_limits<double>::quiet_NaN();
+};
+
+ChainsReport run_sumstats_chains(const Options& opt, hgibbs_t dev, const hydra_model_desc& md, const SumstatTable& tab, const LdWindow& win, uint32_t W,
+                                 unsigned M, int G, const std::string& base)
+{
+    ChainsReport rep;
+    long R = 1, smax = 0;
+    whole_int(opt.sumstatsChains, R);
+    if (opt.sumstatsStreamsGiven) whole_int(opt.sumstatsStreams, smax);
+    rep.chains = (uint32_t)R;
+    std::vector<uint32_t> seeds(R);
+    for (long r = 0; r < R; ++r) seeds[r] = md.seed + (uint32_t)r; // hydra's rule for ranks
+    hydra_ss_multi_t chains = nullptr;
+    hg_check(hydra_ss_multi_create(dev, &md, (uint32_t)R, seeds.data(), tab.n_eff, W, win.ahead.data(), tab.xty.data(), tab.use.data(), (uint32_t)smax, &chains),
+             "hydra_ss_multi_create");
+    hg_check(hydra_ss_multi_streams(chains, &rep.streams, nullptr, nullptr), "hydra_ss_multi_streams");
+    if (rep.streams) {
+        std::vector<uint32_t> bounds((size_t)rep.streams + 1u);
+        hg_check(hydra_ss_multi_streams(chains, nullptr, bounds.data(), nullptr), "hydra_ss_multi_streams");
+        for (uint32_t s = 0; s < rep.streams; ++s) rep.largest = std::max(rep.largest, bounds[s + 1] - bounds[s]);
+    }
+
+    OutFiles outs;
+    std::vector<FILE*> outf(R), betf(R), cpnf(R), acuf(R);
+    for (long r = 0; r < R; ++r) {
+        const std::string b = r ? base + ".c" + std::to_string(r) : base;
+        outf[r] = outs.open(b + ".csv");
+        betf[r] = outs.open(b + ".bet");
+        cpnf[r] = outs.open(b + ".cpn");
+        acuf[r] = outs.open(b + ".acu");
+        for (FILE* f : {betf[r], cpnf[r], acuf[r]}) pwrite_at(f, 0, &M, sizeof(unsigned));
+    }
+    // the table's parameters: sigmaG[g] per group, their sum, sigmaE, h2 (the .csv's ratio), m0, mu; per chain its records in order
+    const int P = G + 5;
+    std::vector<std::vector<double>> rec((size_t)P * R);
+    std::vector<double> beta(M), acum(M), sigmaG(G);
+    std::vector<int32_t> comp(M), m0(G);
+    std::vector<char> buff(50000);
+    unsigned n_thinned_saved = 0;
+    double sweep_ms = 0.0;
+    for (unsigned iteration = 0; iteration < opt.chainLength; ++iteration) {
+        const double t0 = now_s();
+        hg_check(hydra_ss_multi_iterate(chains), "hydra_ss_multi_iterate");
+        const double t1 = now_s();
+        hg_check(hgibbs_last_ss_ms(dev, &rep.band_ms, &sweep_ms), "hgibbs_last_ss_ms");
+        rep.sweep_total_ms += sweep_ms;
+        ++rep.sweeps;
+        for (long r = 0; r < R; ++r) {
+            double sigmaE = 0, mu = 0;
+            hg_check(hydra_ss_multi_state(chains, (uint32_t)r, &sigmaE, &mu, sigmaG.data(), nullptr, m0.data(), nullptr, nullptr), "hydra_ss_multi_state");
+            double sg = 0;
+            long m0s = 0;
+            for (int g = 0; g < G; ++g) {
+                sg += sigmaG[g];
+                m0s += m0[g];
+            }
+            std::printf("RESULT : chain %2ld it %4d: proc = %9.3f s (all chains), sweep = %9.3f ms on the device (all chains), sigmaG = %15.10f, sigmaE = %15.10f, "
+                        "mu = %15.10f, m0 = %10ld\n",
+                        r, iteration, t1 - t0, sweep_ms, sg, sigmaE, mu, m0s);
+            if (iteration % opt.thin == 0) {
+                hg_check(hydra_ss_multi_effects(chains, (uint32_t)r, beta.data(), comp.data(), acum.data(), nullptr), "hydra_ss_multi_effects");
+                const int len = hydra_ss_multi_csv_line(chains, (uint32_t)r, iteration, buff.data(), buff.size());
+                write_line(outf[r], n_thinned_saved, buff.data(), len);
+                write_thinned(betf[r], n_thinned_saved, iteration, beta.data(), M, sizeof(double));
+                write_thinned(acuf[r], n_thinned_saved, iteration, acum.data(), M, sizeof(double));
+                write_thinned(cpnf[r], n_thinned_saved, iteration, comp.data(), M, sizeof(int));
+                if (iteration >= opt.burnin) {
+                    std::vector<double>* row = &rec[(size_t)r * P];
+                    for (int g = 0; g < G; ++g) row[g].push_back(sigmaG[g]);
+                    row[G].push_back(sg);
+                    row[G + 1].push_back(sigmaE);
+                    row[G + 2].push_back(sg / (sigmaE + sg));
+                    row[G + 3].push_back((double)m0s);
+                    row[G + 4].push_back(mu);
+                }
+            }
+        }
+        std::fflush(stdout);
+        if (iteration % opt.thin == 0) n_thinned_saved += 1;
+    }
+    outs.close(true);
+    hydra_ss_multi_destroy(chains);
+
+    // <base>.rhat
+    const unsigned T = (unsigned)rec[0].size();
+    const std::string rhatp = base + ".rhat";
+    FILE* rf = open_out(rhatp, "wb+");
+    std::fprintf(rf, "PARAM\tNCHAINS\tNREC\tMEAN\tSD\tRHAT\tESS\n");
+    if (T < 4)
+        std::printf("SUMSTAT: %s: %u thinned record(s) per chain at or after --burn-in %u, split-R^ needs at least 4: every statistic is NA\n", rhatp.c_str(), T,
+                    opt.burnin);
+    auto num = [](double v) {
+        char b[40];
+        if (std::isnan(v)) return std::string("NA");
+        std::snprintf(b, sizeof b, "%.9g", v);
+        return std::string(b);
+    };
+    std::vector<double> x((size_t)R * T);
+    for (int p = 0; p < P; ++p) {
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        double mean = nan, sd = nan, rhat = nan, ess = nan;
+        if (T >= 4) {
+            for (long r = 0; r < R; ++r) std::copy(rec[(size_t)r * P + p].begin(), rec[(size_t)r * P + p].end(), x.begin() + (size_t)r * T);
+            hg_check(hgibbs_mcmc_diag((uint32_t)R, T, x.data(), &mean, &sd, &rhat, &ess), "hgibbs_mcmc_diag");
+            if (!std::isnan(rhat) && !(rhat <= rep.max_rhat)) rep.max_rhat = rhat;
+        }
+        std::string name = p < G ? "sigmaG[" + std::to_string(p) + "]" : std::string(p == G ? "sigmaG" : p == G + 1 ? "sigmaE" : p == G + 2 ? "h2" : p == G + 3 ? "m0" : "mu");
+        std::fprintf(rf, "%s\t%ld\t%u\t%s\t%s\t%s\t%s\n", name.c_str(), R, T, num(mean).c_str(), num(sd).c_str(), num(rhat).c_str(), num(ess).c_str());
+    }
+    close_out(rf, rhatp);
+    return rep;
+}
+
 int run_sumstats(const Options& opt, const Cohort& co, const std::vector<int32_t>& groups, const std::vector<double>& mS_flat, int G, int K)
 {
     const std::string base = opt.mcmcOutDir + "/" + opt.mcmcOutNam;
@@ -3937,6 +4065,19 @@ int run_sumstats(const Options& opt, const Cohort& co, const std::vector<int32_t
     md.K = K;
     md.groups = groups.empty() ? nullptr : groups.data();
     md.mS = mS_flat.data();
+    if (opt.sumstatsChainsGiven) { // R chains in one launch per iteration, and the convergence table
+        const ChainsReport rep = run_sumstats_chains(opt, dev, md, tab, win, W, M, G, base);
+        hgibbs_destroy(dev);
+        char par[96] = "", rh[48] = "NA";
+        if (rep.streams) std::snprintf(par, sizeof par, " in %u streams (largest interval %u markers)", rep.streams, rep.largest);
+        if (!std::isnan(rep.max_rhat)) std::snprintf(rh, sizeof rh, "%.9g", rep.max_rhat);
+        std::printf("SUMSTAT: %u markers used, %u left out (%u not in the table, %u with another allele pair, %u without usable BETA, SE and N, %u without a finite sd in the panel), "
+                    "n_eff %.12g, band %u x %u doubles = %.1f MiB of device memory (built in %.3f ms), %u chains, %.3f ms per sweep launch (all chains) on the device over %u "
+                    "sweeps%s, largest R^ %s, wrote %s.{csv,bet,cpn,acu}, %s.c<r>.{csv,bet,cpn,acu} for the chains r >= 1 and %s.rhat\n",
+                    used, M - used, M - tab.matched - tab.allele - tab.unusable, tab.allele, tab.unusable, nosd, tab.n_eff, M, W, (double)M * W * 8.0 / 1048576.0,
+                    rep.band_ms, rep.chains, rep.sweeps ? rep.sweep_total_ms / rep.sweeps : 0.0, rep.sweeps, par, rh, base.c_str(), base.c_str(), base.c_str());
+        return 0;
+    }
     hydra_ss_chain_t chain = nullptr;
     hg_check(hydra_ss_chain_create(dev, &md, tab.n_eff, W, win.ahead.data(), tab.xty.data(), tab.use.data(), &chain), "hydra_ss_chain_create");
     // independent LD blocks in parallel streams: the intervals come from the window, so they are known before the first sweep
@@ -4247,7 +4388,7 @@ void check_sumstats(const Options& opt, int nranks)
 {
     if (!opt.sumstats) {
         if (const char* o = first_given({{"--sumstats-window", opt.sumstatsWindowGiven}, {"--sumstats-window-kb", opt.sumstatsKbGiven}, {"--sumstats-n", opt.sumstatsNGiven},
-                                          {"--sumstats-streams", opt.sumstatsStreamsGiven}}))
+                                          {"--sumstats-streams", opt.sumstatsStreamsGiven}, {"--sumstats-chains", opt.sumstatsChainsGiven}}))
             fatal(std::string("FATAL  : ") + o + " needs --sumstats");
         return;
     }
@@ -4275,6 +4416,8 @@ void check_sumstats(const Options& opt, int nranks)
         fatal("FATAL  : --sumstats-n " + opt.sumstatsN + ": the sample size must be a finite number >= 2");
     if (opt.sumstatsStreamsGiven && (!whole_int(opt.sumstatsStreams, w) || w < 1 || w > 1024))
         fatal("FATAL  : --sumstats-streams " + opt.sumstatsStreams + ": the number of streams must be an integer from 1 to 1024 (the most hgibbs_ss_sweep_streams takes)");
+    if (opt.sumstatsChainsGiven && (!whole_int(opt.sumstatsChains, w) || w < 1 || w > 64))
+        fatal("FATAL  : --sumstats-chains " + opt.sumstatsChains + ": the number of chains must be an integer from 1 to 64 (the most hgibbs_ss_replicas takes)");
 }
 
 } // namespace

@@ -12,8 +12,10 @@
 // One struct drives either engine: the device's (hydra_ss_chain_create) or the host's (hydra_ss_chain_create_host, no device at all),
 // so the iteration that a CPU test holds to the oracle's chain is the one the device runs under.
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -25,6 +27,23 @@
 using hg::V0E, hg::S02E;
 
 static int cfail(const std::string& m) { return hg::chain_fail(m); }
+
+// HGIBBS_TIMING=1: where the host side of an iteration goes (stderr, milliseconds), as hydra_chain.cpp prints it
+static bool ss_timing()
+{
+    static const bool timing = std::getenv("HGIBBS_TIMING") != nullptr;
+    return timing;
+}
+
+static double ss_now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+static void ss_timing_line(const char* who, hgibbs_t dev, uint32_t chains, double t0, double t1, double t2, double t3, double t4)
+{
+    double band_ms = 0.0, sweep_ms = 0.0;
+    if (dev) (void)hgibbs_last_ss_ms(dev, &band_ms, &sweep_ms);
+    std::fprintf(stderr, "%s: %u chain(s): mu and shuffle %.3f, sweep call %.3f (kernel %.3f), sums %.3f, hyper-parameters %.3f, iteration %.3f ms\n", who, chains,
+                 t1 - t0, t2 - t1, sweep_ms, t3 - t2, t4 - t3, t4 - t0);
+}
 
 struct hydra_ss_chain : hg::ChainCore {
     hgibbs_t dev = nullptr; // null: the host engine on the vectors below
@@ -39,14 +58,55 @@ struct hydra_ss_chain : hg::ChainCore {
     std::vector<hgibbs_rng_state> streams;
 };
 
+// R chains on one band of the device: a core per chain, the replicas of the handle for their effects
+struct hydra_ss_multi {
+    hgibbs_t dev = nullptr;
+    uint32_t M = 0, W = 0, S = 0; // S: the streams of every chain, 0 for the single stream
+    double n = 0.0;
+    std::vector<hg::ChainCore> chains;
+    std::vector<uint32_t> ahead, bounds;
+    std::vector<hgibbs_rng_state> streams; // R x S
+    // what one iteration hands to the two launches and takes back, chain after chain
+    std::vector<int32_t> orders, cass;
+    std::vector<uint8_t> ada;
+    std::vector<double> sigmaE, sigmaG, estPi, sb, sc, bsq;
+    std::vector<uint64_t> nnz;
+    std::vector<hgibbs_rng_state> rngs;
+};
+
 // the shared core's initial values, and sigmaE with y'y = n - 1
-static int ss_init(hydra_ss_chain* c, const hydra_model_desc* model, const uint8_t* use)
+static int ss_init(hg::ChainCore& c, uint32_t M, double n, const hydra_model_desc* model, const uint8_t* use)
 {
     if (model->G < 1) return cfail("hydra_ss_chain_create: G must be >= 1");
     if (model->K < 2) return cfail("hydra_ss_chain_create: K must be >= 2 (zero component + at least one mixture)");
-    if (hg::core_init(*c, c->M, model, use, "hydra_ss_chain_create")) return 1;
-    c->sigmaE = (c->n - 1.0) / c->n * 0.5; // :1580 with y'y = n - 1
+    if (hg::core_init(c, M, model, use, "hydra_ss_chain_create")) return 1;
+    c.sigmaE = (n - 1.0) / n * 0.5; // :1580 with y'y = n - 1
     return 0;
+}
+
+// hydra_ss_chain_set_streams' rule: stream s is seeded from w_s, the next S words of the chain's own generator
+static void seed_streams(hgibbs_rng_state& rng, uint32_t S, hgibbs_rng_state* streams)
+{
+    hg::Mt gen{rng.x, rng.idx};
+    std::vector<uint32_t> w(S);
+    for (uint32_t s = 0; s < S; ++s) w[s] = gen.next();
+    rng.idx = gen.idx;
+    for (uint32_t s = 0; s < S; ++s) {
+        hg::Mt st{streams[s].x, 0};
+        st.seed(w[s]);
+        streams[s].idx = st.idx;
+    }
+}
+
+// the message of an e_sqn that is not positive; `chain`: its number among several, or -1
+static std::string esqn_text(const char* who, uint32_t iteration, double e_sqn, int chain)
+{
+    char buf[320];
+    int o = std::snprintf(buf, sizeof buf,
+                          "%s: iteration %u: e_sqn = %.17g is not positive (the truncated band is not positive definite for these effects); not clamped", who,
+                          iteration, e_sqn);
+    if (chain >= 0) std::snprintf(buf + o, sizeof buf - o, " (chain %d)", chain);
+    return buf;
 }
 
 extern "C" {
@@ -64,7 +124,7 @@ int hydra_ss_chain_create(hgibbs_t dev, const hydra_model_desc* model, double n_
     c->W = W;
     c->n = n_eff;
     // the band first: it refuses n_eff, W, ahead and xty by name
-    if (hgibbs_ss_begin(dev, n_eff, W, ahead, xty) || ss_init(c.get(), model, use) ||
+    if (hgibbs_ss_begin(dev, n_eff, W, ahead, xty) || ss_init(*c, M, n_eff, model, use) ||
         hgibbs_set_model(dev, c->G, c->K, c->groups.data(), c->cVa.data(), c->cVaI.data())) {
         (void)hgibbs_ss_end(dev);
         return 1;
@@ -86,7 +146,7 @@ int hydra_ss_chain_create_host(uint32_t M, const hydra_model_desc* model, double
     c->M = M;
     c->W = W;
     c->n = n_eff;
-    if (ss_init(c.get(), model, use)) return 1;
+    if (ss_init(*c, M, n_eff, model, use)) return 1;
     c->ahead.assign(ahead, ahead + M);
     c->band.assign(band, band + (size_t)M * W);
     c->xty.assign(xty, xty + M);
@@ -112,6 +172,8 @@ int hydra_ss_chain_iterate(hydra_ss_chain_t c)
     const uint32_t M = c->M;
     const double dN = c->n;
     hg::Mt gen{c->rng.x, c->rng.idx};
+    const bool timing = ss_timing();
+    const double t0 = timing ? ss_now_ms() : 0.0;
 
     // :1675-1686 with a residual whose mean plus the old mu is 0
     c->mu = hg::norm_rng(gen, 0.0, c->sigmaE / dN);
@@ -122,6 +184,7 @@ int hydra_ss_chain_iterate(hydra_ss_chain_t c)
 
     // :1709-2490; the generator travels with the call
     c->rng.idx = gen.idx;
+    const double t1 = timing ? ss_now_ms() : 0.0;
     const uint32_t S = (uint32_t)c->streams.size();
     if (S) { // the main generator is not touched by the sweep
         if (c->dev ? hgibbs_ss_sweep_streams(c->dev, c->order.data(), c->sigmaE, c->sigmaG.data(), c->estPi.data(), c->adaV.data(), S, c->bounds.data(),
@@ -139,6 +202,7 @@ int hydra_ss_chain_iterate(hydra_ss_chain_t c)
                                     c->adaV.data(), &c->rng, c->cass.data(), &c->last_nnz))
         return 1;
     gen.idx = c->rng.idx;
+    const double t2 = timing ? ss_now_ms() : 0.0;
 
     // :2495-2578
     std::vector<double> bsq(G, 0.0);
@@ -154,21 +218,19 @@ int hydra_ss_chain_iterate(hydra_ss_chain_t c)
             sb += b * c->xty[i];
             sc += b * c->c[i];
         }
+    const double t3 = timing ? ss_now_ms() : 0.0;
     hg::core_hyper(*c, bsq.data(), gen);
 
     // :2685-2690
     const double e_sqn = ((dN - 1.0) - (sb + sc)) + dN * c->mu * c->mu;
     if (!(e_sqn > 0.0)) {
-        char buf[256];
-        std::snprintf(buf, sizeof buf,
-                      "hydra_ss_chain_iterate: iteration %u: e_sqn = %.17g is not positive (the truncated band is not positive definite for these effects); not clamped",
-                      c->iteration, e_sqn);
         c->rng.idx = gen.idx;
-        return cfail(buf);
+        return cfail(esqn_text("hydra_ss_chain_iterate", c->iteration, e_sqn, -1));
     }
     c->sigmaE = hg::inv_scaled_chisq_rng(gen, V0E + dN, (e_sqn + V0E * S02E) / (V0E + dN));
     c->rng.idx = gen.idx;
     c->iteration += 1;
+    if (timing) ss_timing_line("hydra_ss_chain_iterate", c->dev, 1u, t0, t1, t2, t3, ss_now_ms());
     return 0;
 }
 
@@ -204,16 +266,8 @@ int hydra_ss_chain_set_streams(hydra_ss_chain_t c, uint32_t S_max)
     uint32_t S = 0;
     if (hgibbs_ss_partition(c->M, c->ahead.data(), S_max, bounds.data(), &S)) return 1;
     bounds.resize((size_t)S + 1u);
-    hg::Mt gen{c->rng.x, c->rng.idx};
-    std::vector<uint32_t> w(S);
-    for (uint32_t s = 0; s < S; ++s) w[s] = gen.next();
-    c->rng.idx = gen.idx;
     c->streams.resize(S);
-    for (uint32_t s = 0; s < S; ++s) {
-        hg::Mt st{c->streams[s].x, 0};
-        st.seed(w[s]);
-        c->streams[s].idx = st.idx;
-    }
+    seed_streams(c->rng, S, c->streams.data());
     c->bounds = bounds;
     return 0;
 }
@@ -234,6 +288,174 @@ const int32_t* hydra_ss_chain_order(hydra_ss_chain_t c) { return c ? c->order.da
 int hydra_ss_chain_csv_line(hydra_ss_chain_t c, uint32_t iteration, char* buf, size_t len)
 {
     return (c && buf) ? hg::core_csv_line(*c, iteration, buf, len) : -1;
+}
+
+// ---- R chains on one band ----
+// R cores around ONE hgibbs_ss_sweep_replicas and ONE hgibbs_ss_replica_sums per iteration.  Chain r draws what the hydra_ss_chain
+// seeded with seeds[r] draws, in the same order from its own generator, so it is that chain bit for bit.
+
+int hydra_ss_multi_create(hgibbs_t dev, const hydra_model_desc* model, uint32_t R, const uint32_t* seeds, double n_eff, uint32_t W, const uint32_t* ahead,
+                          const double* xty, const uint8_t* use, uint32_t S_max, hydra_ss_multi_t* out)
+{
+    const char* who = "hydra_ss_multi_create";
+    if (!dev || !model || !seeds || !xty || !out) return cfail(std::string(who) + ": null argument");
+    if (R < 1u || R > 64u) return cfail(std::string(who) + ": R = " + std::to_string(R) + ", must be in [1, 64]");
+    if (S_max > 1024u) return cfail(std::string(who) + ": S_max = " + std::to_string(S_max) + ", must be in [0, 1024] (0: the single stream)");
+    uint32_t n_global = 0, n_local = 0, M = 0, row_begin = 0;
+    if (hgibbs_dims(dev, &n_global, &n_local, &M, &row_begin)) return 1;
+    if (n_global < 2 || M == 0) return cfail(std::string(who) + ": load the panel's genotypes first (hgibbs_load_bed / hgibbs_synth_bed)");
+    std::unique_ptr<hydra_ss_multi> c(new hydra_ss_multi());
+    c->dev = dev;
+    c->M = M;
+    c->W = W;
+    c->n = n_eff;
+    c->chains.resize(R);
+    if (hgibbs_ss_begin(dev, n_eff, W, ahead, xty)) return 1;
+    for (uint32_t r = 0; r < R; ++r) {
+        hydra_model_desc md = *model;
+        md.seed = seeds[r];
+        if (ss_init(c->chains[r], M, n_eff, &md, use)) {
+            (void)hgibbs_ss_end(dev);
+            return 1;
+        }
+    }
+    const hg::ChainCore& c0 = c->chains[0];
+    if (hgibbs_set_model(dev, c0.G, c0.K, c0.groups.data(), c0.cVa.data(), c0.cVaI.data()) || hgibbs_ss_replicas(dev, R)) {
+        (void)hgibbs_ss_end(dev);
+        return 1;
+    }
+    c->ahead.resize(M);
+    for (uint32_t j = 0; j < M; ++j) c->ahead[j] = ahead ? ahead[j] : std::min(W, M - 1u - j);
+    if (S_max) {
+        std::vector<uint32_t> bounds((size_t)S_max + 1u);
+        uint32_t S = 0;
+        if (hgibbs_ss_partition(M, c->ahead.data(), S_max, bounds.data(), &S)) {
+            (void)hgibbs_ss_end(dev);
+            return 1;
+        }
+        bounds.resize((size_t)S + 1u);
+        c->bounds = bounds;
+        c->S = S;
+        c->streams.resize((size_t)R * S);
+        for (uint32_t r = 0; r < R; ++r) seed_streams(c->chains[r].rng, S, c->streams.data() + (size_t)r * S);
+    }
+    *out = c.release();
+    return 0;
+}
+
+int hydra_ss_multi_destroy(hydra_ss_multi_t c)
+{
+    if (c && c->dev) (void)hgibbs_ss_end(c->dev);
+    delete c;
+    return 0;
+}
+
+int hydra_ss_multi_iterate(hydra_ss_multi_t c)
+{
+    if (!c) return cfail("hydra_ss_multi_iterate: null chains");
+    const uint32_t M = c->M, R = (uint32_t)c->chains.size(), S = c->S;
+    const int G = c->chains[0].G, K = c->chains[0].K;
+    const size_t GK = (size_t)G * K;
+    const double dN = c->n;
+    c->orders.resize((size_t)R * M);
+    c->ada.resize((size_t)R * M);
+    c->sigmaE.resize(R);
+    c->sigmaG.resize((size_t)R * G);
+    c->estPi.resize(R * GK);
+    c->cass.resize(R * GK);
+    c->nnz.resize(R);
+    c->rngs.resize(R);
+    c->sb.resize(R);
+    c->sc.resize(R);
+    c->bsq.resize((size_t)R * G);
+
+    // per chain: mu and the shuffle on its own generator, as hydra_ss_chain_iterate
+    const bool timing = ss_timing();
+    const double t0 = timing ? ss_now_ms() : 0.0;
+    for (uint32_t r = 0; r < R; ++r) {
+        hg::ChainCore& k = c->chains[r];
+        hg::Mt gen{k.rng.x, k.rng.idx};
+        k.mu = hg::norm_rng(gen, 0.0, k.sigmaE / dN);
+        if (k.shuffle) hg::shuffle_libstdcxx6_fast(k.order.data(), k.order.size(), gen);
+        std::fill(k.m0.begin(), k.m0.end(), 0);
+        k.rng.idx = gen.idx;
+        std::copy(k.order.begin(), k.order.end(), c->orders.begin() + (size_t)r * M);
+        std::copy(k.adaV.begin(), k.adaV.end(), c->ada.begin() + (size_t)r * M);
+        c->sigmaE[r] = k.sigmaE;
+        std::copy(k.sigmaG.begin(), k.sigmaG.end(), c->sigmaG.begin() + (size_t)r * G);
+        std::copy(k.estPi.begin(), k.estPi.end(), c->estPi.begin() + r * GK);
+        c->rngs[r] = k.rng;
+    }
+
+    // one launch for every chain; with streams the chains' own generators are not touched by it
+    const double t1 = timing ? ss_now_ms() : 0.0;
+    if (hgibbs_ss_sweep_replicas(c->dev, R, c->orders.data(), c->sigmaE.data(), c->sigmaG.data(), c->estPi.data(), c->ada.data(), S ? S : 1u,
+                                 S ? c->bounds.data() : nullptr, S ? c->streams.data() : c->rngs.data(), c->cass.data(), c->nnz.data()))
+        return 1;
+    const double t2 = timing ? ss_now_ms() : 0.0;
+    if (hgibbs_ss_replica_sums(c->dev, c->sb.data(), c->sc.data(), c->bsq.data())) return 1;
+    const double t3 = timing ? ss_now_ms() : 0.0;
+
+    for (uint32_t r = 0; r < R; ++r) {
+        hg::ChainCore& k = c->chains[r];
+        if (!S) k.rng = c->rngs[r];
+        std::copy(c->cass.begin() + r * GK, c->cass.begin() + (r + 1) * GK, k.cass.begin());
+        k.last_nnz = c->nnz[r];
+        hg::Mt gen{k.rng.x, k.rng.idx};
+        hg::core_hyper(k, c->bsq.data() + (size_t)r * G, gen);
+        const double e_sqn = ((dN - 1.0) - (c->sb[r] + c->sc[r])) + dN * k.mu * k.mu;
+        k.rng.idx = gen.idx;
+        if (!(e_sqn > 0.0)) return cfail(esqn_text("hydra_ss_multi_iterate", k.iteration, e_sqn, (int)r));
+        k.sigmaE = hg::inv_scaled_chisq_rng(gen, V0E + dN, (e_sqn + V0E * S02E) / (V0E + dN));
+        k.rng.idx = gen.idx;
+        k.iteration += 1;
+    }
+    if (timing) ss_timing_line("hydra_ss_multi_iterate", c->dev, R, t0, t1, t2, t3, ss_now_ms());
+    return 0;
+}
+
+static hg::ChainCore* multi_at(hydra_ss_multi_t c, uint32_t r, const char* who)
+{
+    if (!c) {
+        cfail(std::string(who) + ": null chains");
+        return nullptr;
+    }
+    if (r >= c->chains.size()) {
+        cfail(std::string(who) + ": chain " + std::to_string(r) + " outside [0, " + std::to_string(c->chains.size()) + ")");
+        return nullptr;
+    }
+    return &c->chains[r];
+}
+
+int hydra_ss_multi_state(hydra_ss_multi_t c, uint32_t r, double* sigmaE, double* mu, double* sigmaG, double* estPi, int32_t* m0, int32_t* cass,
+                         hgibbs_rng_state* rng)
+{
+    const hg::ChainCore* k = multi_at(c, r, "hydra_ss_multi_state");
+    if (!k) return 1;
+    hg::core_state(*k, sigmaE, mu, sigmaG, estPi, m0, cass, rng);
+    return 0;
+}
+
+int hydra_ss_multi_effects(hydra_ss_multi_t c, uint32_t r, double* beta, int32_t* components, double* acum, double* cvec)
+{
+    if (!multi_at(c, r, "hydra_ss_multi_effects")) return 1;
+    return hgibbs_ss_replica_get(c->dev, r, beta, components, acum, cvec);
+}
+
+int hydra_ss_multi_streams(hydra_ss_multi_t c, uint32_t* S, uint32_t* bounds, hgibbs_rng_state* rngs)
+{
+    if (!c) return cfail("hydra_ss_multi_streams: null chains");
+    if (S) *S = c->S;
+    if (bounds) std::copy(c->bounds.begin(), c->bounds.end(), bounds);
+    if (rngs) std::copy(c->streams.begin(), c->streams.end(), rngs);
+    return 0;
+}
+
+uint64_t hydra_ss_multi_last_nnz(hydra_ss_multi_t c, uint32_t r) { return (c && r < c->chains.size()) ? c->chains[r].last_nnz : 0; }
+
+int hydra_ss_multi_csv_line(hydra_ss_multi_t c, uint32_t r, uint32_t iteration, char* buf, size_t len)
+{
+    return (c && buf && r < c->chains.size()) ? hg::core_csv_line(c->chains[r], iteration, buf, len) : -1;
 }
 
 } // extern "C"

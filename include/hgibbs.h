@@ -497,6 +497,39 @@ int hgibbs_ss_sweep_streams_host(uint32_t M, double n_eff, uint32_t W, const uin
                                  const int32_t* order, double sigmaE, const double* sigmaG, const double* estPi, const uint8_t* adaV, uint32_t S,
                                  const uint32_t* bounds, hgibbs_rng_state* rngs, int32_t* cass, uint64_t* nnz_updates);
 
+/* ---- several chains on one band ---- */
+/* R replicas of the chain's state beside the handle's own, between hgibbs_ss_begin and hgibbs_ss_end.  A replica has its own c, effects,
+ * components, acum, order, mask, mixture tables, cass and generator(s); the band, its window, xty, the groups and the model are the
+ * handle's.  The handle's own chain (what hgibbs_ss_sweep, hgibbs_get_beta, hgibbs_ss_state and hgibbs_beta_sqnorm use) is no replica:
+ * no call below reads or writes it, and no call above reads or writes a replica.
+ *   replicas        R in 1..64 replicas with c = xty and every effect, component and acum 0; a second call replaces the first's.
+ *                   Refused by name: no ss state, R out of range, memory that does not fit (with R and the bytes).
+ *   sweep_replicas  ONE launch, S x R workgroups: workgroup (s, r) sweeps interval s of replica r.  orders R x M, sigmaE R, sigmaG
+ *                   R x G, estPi R x G x K, adaV R x M (a chain's mask is its own: a group can freeze out in one chain alone),
+ *                   bounds S + 1 (NULL with S = 1: {0, M}), rngs R x S (replica-major, in and out), cass R x G x K, nnz_updates R
+ *                   (or NULL).  Replica r's outcome -- effects, components, acum, c, cass, nnz, every generator's words and index --
+ *                   is bit for bit what hgibbs_ss_sweep_streams gives from the same state and arguments on the handle's own chain,
+ *                   and with S = 1 what hgibbs_ss_sweep gives.  Refused as hgibbs_ss_sweep_streams refuses, with the replica's
+ *                   number; and by name: replicas not allocated, an R other than the allocated one.  hgibbs_last_ss_ms reports it.
+ *   replica_sums    one launch, a wave per replica: sb[r] = sum beta_j b_j, sc[r] = sum beta_j c_j (hgibbs_ss_state's order and bits)
+ *                   and bsq[r G + g] (hgibbs_beta_sqnorm's); any pointer may be NULL.  At most 8192 groups.
+ *   replica_get     replica r's effects, components, acum and c (any pointer may be NULL)
+ *   replica_set_beta  replica r's effects alone: c stays as it is, as with hgibbs_set_beta */
+int hgibbs_ss_replicas(hgibbs_t h, uint32_t R);
+int hgibbs_ss_sweep_replicas(hgibbs_t h, uint32_t R, const int32_t* orders, const double* sigmaE, const double* sigmaG, const double* estPi,
+                             const uint8_t* adaV, uint32_t S, const uint32_t* bounds, hgibbs_rng_state* rngs, int32_t* cass_host,
+                             uint64_t* nnz_updates);
+int hgibbs_ss_replica_sums(hgibbs_t h, double* sb /* R */, double* sc /* R */, double* bsq /* R x G */);
+int hgibbs_ss_replica_get(hgibbs_t h, uint32_t r, double* beta, int32_t* comp, double* acum, double* c);
+int hgibbs_ss_replica_set_beta(hgibbs_t h, uint32_t r, const double* beta);
+
+/* Convergence of R chains of one scalar (host only): x is R x T, chain-major.  mean and sd over all R T draws; rhat: split-R^ (BDA3
+ * section 11.4: every chain halved, an odd T drops the middle draw; no rank normalisation); ess: from the same 2 R half-chains'
+ * combined autocovariances, truncated by Geyer's initial monotone positive sequence (Stan reference manual), at most
+ * 2 R n log10(2 R n) with n = T / 2.  No within-chain variance at all: rhat and ess are NaN.  Any output may be NULL.  Refused by name:
+ * null x, R = 0, T < 4.  Every sum runs in index order. */
+int hgibbs_mcmc_diag(uint32_t R, uint32_t T, const double* x, double* mean, double* sd, double* rhat, double* ess);
+
 /* ---- dots of the loaded markers against dense vectors */
 /* For markers j in [m0, m0 + count) of the loaded BED and K vectors u_k over this rank's n_local individuals:
  *   out[(j - m0)*K + k]           = x_j'u_k = mstd_j (P_jk - mave_j Q_jk)      (NaN where mstd_j is not finite)
@@ -922,6 +955,24 @@ int hydra_ss_chain_csv_line(hydra_ss_chain_t c, uint32_t iteration, char* buf, s
  * and the S states (any pointer may be NULL). */
 int hydra_ss_chain_set_streams(hydra_ss_chain_t c, uint32_t S_max);
 int hydra_ss_chain_streams(hydra_ss_chain_t c, uint32_t* S, uint32_t* bounds, hgibbs_rng_state* rngs);
+
+/* R chains on one band of the device: chain r is, bit for bit, the hydra_ss_chain created on the device with
+ * model.seed = seeds[r] (model->seed is not read) and, with S_max > 0, hydra_ss_chain_set_streams(S_max): every .csv line, effect,
+ * component, acum and generator.  One iteration is one hgibbs_ss_sweep_replicas and one hgibbs_ss_replica_sums between the chains' own
+ * draws; an e_sqn that is not positive stops it with hydra_ss_chain_iterate's message and the chain's number.  R in 1..64, S_max in
+ * 0..1024 (0: the single stream).  No host engine: R host chains are R hydra_ss_chain_create_host calls.
+ *   streams   S (0: single stream), bounds (S + 1) and the R x S states, chain-major (any pointer may be NULL) */
+typedef struct hydra_ss_multi* hydra_ss_multi_t;
+int hydra_ss_multi_create(hgibbs_t dev, const hydra_model_desc* model, uint32_t R, const uint32_t* seeds /* R */, double n_eff, uint32_t W,
+                          const uint32_t* ahead, const double* xty, const uint8_t* use, uint32_t S_max, hydra_ss_multi_t* out);
+int hydra_ss_multi_destroy(hydra_ss_multi_t c);
+int hydra_ss_multi_iterate(hydra_ss_multi_t c);
+int hydra_ss_multi_state(hydra_ss_multi_t c, uint32_t r, double* sigmaE, double* mu, double* sigmaG /*G*/, double* estPi /*G*K*/, int32_t* m0 /*G*/,
+                         int32_t* cass /*G*K*/, hgibbs_rng_state* rng);
+int hydra_ss_multi_effects(hydra_ss_multi_t c, uint32_t r, double* beta, int32_t* components, double* acum, double* cvec);
+int hydra_ss_multi_streams(hydra_ss_multi_t c, uint32_t* S, uint32_t* bounds, hgibbs_rng_state* rngs);
+uint64_t hydra_ss_multi_last_nnz(hydra_ss_multi_t c, uint32_t r);
+int hydra_ss_multi_csv_line(hydra_ss_multi_t c, uint32_t r, uint32_t iteration, char* buf, size_t len);
 
 /* ======================================================================== */
 /* BayesW: Weibull survival model (src/BayesW.cpp); individuals shard as above  */

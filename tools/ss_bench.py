@@ -13,13 +13,20 @@ and in marker order.  One JSON line per case; --out appends them to a file as we
 streams (hgibbs_ss_sweep_streams); the record then names the streams used, the largest interval and the
 ideal ratio M / largest against one stream.  Run the same cases without --streams for the single stream on the same band.
 
+--chains R[,R...] times, after the single chain and in the same process, hydra_ss_multi with R chains from the seeds 11 + r on a band
+of the same panel (hgibbs_ss_sweep_replicas; it composes with --chromosomes and --streams): per R one record
+with the device time of every replica launch, its median against the single chain's median sweep of this run, and the wall time of
+an iteration beside it (what the host adds: R shuffles, the uploads, the sums).  The records go to --chains-out as well
+(profiles/ss_chains_bench.jsonl unless told otherwise).
+
     python tools/ss_bench.py [--cases 10000x100000x128,20000x1000000x512] [--n-eff 4000000] [--signals 0.001] [--iters 6] [--out F]
-                             [--chromosomes C] [--streams S]
+                             [--chromosomes C] [--streams S] [--chains R[,R...]] [--chains-iters I] [--chains-out F]
 """
 import argparse
 import json
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -50,8 +57,14 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--chromosomes", type=int, default=0, help="cut the window into this many intervals (1..22) sized like the human autosomes")
     ap.add_argument("--streams", type=int, default=0, help="sweep independent blocks in at most this many parallel streams (1..1024)")
+    ap.add_argument("--chains", default="", help="numbers of chains (1..64), comma-separated: time the replica launch with each after the single chain")
+    ap.add_argument("--chains-iters", type=int, default=0, help="iterations of every --chains run (default: --iters)")
+    ap.add_argument("--chains-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "ss_chains_bench.jsonl"))
+    ap.add_argument("--label", default=None, help="a word copied into every record (which build, which run)")
     args = ap.parse_args()
     out = open(args.out, "a") if args.out else None
+    chains = [int(x) for x in args.chains.split(",") if x]
+    chains_out = open(args.chains_out, "a") if chains else None
 
     def emit(rec):
         line = json.dumps(rec)
@@ -75,6 +88,8 @@ def main():
         bounds, _ = ch.streams()
         band_ms = dev.last_ss_ms()[0]
         rec = {"n_panel": N, "m": M, "W": W, "n_eff": n, "signals": int(sig.sum()), "band_mib": round(M * W * 8 / 2.0**20, 1), "band_ms": round(band_ms, 3)}
+        if args.label:
+            rec["label"] = args.label
         if args.chromosomes:
             rec["chromosomes"] = args.chromosomes
         if args.streams:
@@ -102,10 +117,12 @@ def main():
 
         sweeps = []
         for it in range(args.iters):
+            t0 = time.perf_counter()
             ch.iterate()
+            wall = 1e3 * (time.perf_counter() - t0)
             ms = dev.last_ss_ms()[1]
             st = ch.state()
-            sweeps.append({"it": it, "sweep_ms": round(ms, 3), "markers_per_s": float("%.4g" % (M / (ms * 1e-3))), "us_per_marker": round(1e3 * ms / M, 4),
+            sweeps.append({"it": it, "sweep_ms": round(ms, 3), "wall_ms": round(wall, 3), "markers_per_s": float("%.4g" % (M / (ms * 1e-3))), "us_per_marker": round(1e3 * ms / M, 4),
                            "nnz_updates": ch.last_nnz(), "m0": int(st["m0"].sum()), "sigmaG": float("%.6g" % st["sigmaG"].sum()),
                            "sigmaE": float("%.6g" % st["sigmaE"])})
         rec["sweeps"] = sweeps
@@ -118,6 +135,30 @@ def main():
             rec["fit_us_per_update"] = round(1e3 * sol[1], 4)
         emit(rec)
         del ch
+
+        single_ms = float(np.median([s["sweep_ms"] for s in sweeps])) if sweeps else None
+        single_host = float(np.median([s["wall_ms"] - s["sweep_ms"] for s in sweeps])) if sweeps else None
+        for R in chains:
+            mc = capi.SsMultiChain(dev, n, W, xty, [11 + r for r in range(R)], ahead=ahead, streams=args.streams or None)
+            its = []
+            for it in range(args.chains_iters or args.iters):
+                t0 = time.perf_counter()
+                mc.iterate()
+                wall = 1e3 * (time.perf_counter() - t0)
+                its.append({"it": it, "launch_ms": round(dev.last_ss_ms()[1], 3), "wall_ms": round(wall, 3), "nnz_updates": [mc.last_nnz(r) for r in range(R)]})
+            launch = float(np.median([x["launch_ms"] for x in its]))
+            host = float(np.median([x["wall_ms"] - x["launch_ms"] for x in its]))
+            crec = {"kind": "chains", "n_panel": N, "m": M, "W": W, "chains": R, "workgroups": R * max(1, len(mc.streams()[0]) - 1),
+                    "single_sweep_ms_median": single_ms, "single_host_ms_median": single_host, "launch_ms_median": round(launch, 3),
+                    "ratio_to_single": round(launch / single_ms, 4) if single_ms else None, "host_ms_median": round(host, 3),
+                    "host_ratio_to_R_singles": round(host / (R * single_host), 4) if single_host else None, "iterations": its}
+            for k in ("chromosomes", "streams_max", "streams", "largest_interval", "label"):
+                if k in rec:
+                    crec[k] = rec[k]
+            emit(crec)
+            chains_out.write(json.dumps(crec) + "\n")
+            chains_out.flush()
+            del mc
         dev.close()
 
 
