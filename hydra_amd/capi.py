@@ -29,6 +29,7 @@ ABI_SYMBOLS = [
     "hydra_ss_chain_create", "hydra_ss_chain_create_host", "hydra_ss_chain_destroy", "hydra_ss_chain_iterate", "hydra_ss_chain_state",
     "hydra_ss_chain_effects", "hydra_ss_chain_last_nnz", "hydra_ss_chain_order", "hydra_ss_chain_csv_line",
     "hgibbs_ss_replicas", "hgibbs_ss_sweep_replicas", "hgibbs_ss_replica_sums", "hgibbs_ss_replica_get", "hgibbs_ss_replica_set_beta", "hgibbs_mcmc_diag",
+    "hgibbs_ss_post_begin", "hgibbs_ss_post_add", "hgibbs_ss_post_get", "hgibbs_ss_post_raw", "hgibbs_ss_post_end", "hgibbs_last_ss_post_ms",
     "hydra_ss_multi_create", "hydra_ss_multi_destroy", "hydra_ss_multi_iterate", "hydra_ss_multi_state", "hydra_ss_multi_effects", "hydra_ss_multi_streams",
     "hydra_ss_multi_last_nnz", "hydra_ss_multi_csv_line",
     "hgibbs_marker_dots", "hgibbs_last_marker_dots_ms", "hgibbs_marker_class_sums", "hgibbs_last_marker_class_sums_ms", "hgibbs_logit_null",
@@ -310,6 +311,12 @@ def lib():
     L.hgibbs_ss_replica_get.argtypes = [vp, C.c_uint32, dp, ip, dp, dp]
     L.hgibbs_ss_replica_set_beta.argtypes = [vp, C.c_uint32, dp]
     L.hgibbs_mcmc_diag.argtypes = [C.c_uint32, C.c_uint32, dp, dp, dp, dp, dp]
+    L.hgibbs_ss_post_begin.argtypes = [vp, C.c_uint32, C.c_uint32]
+    L.hgibbs_ss_post_add.argtypes = [vp]
+    L.hgibbs_ss_post_get.argtypes = [vp, dp, dp, dp, u32p, dp]
+    L.hgibbs_ss_post_raw.argtypes = [vp, C.c_uint32, C.c_uint32, dp, dp]
+    L.hgibbs_ss_post_end.argtypes = [vp]
+    L.hgibbs_last_ss_post_ms.argtypes = [vp, dp, dp]
     L.hydra_ss_multi_create.argtypes = [vp, C.POINTER(ModelDesc), C.c_uint32, u32p, C.c_double, C.c_uint32, u32p, dp, u8p, C.c_uint32, C.POINTER(vp)]
     L.hydra_ss_multi_destroy.argtypes = [vp]
     L.hydra_ss_multi_iterate.argtypes = [vp]
@@ -1384,6 +1391,36 @@ class Device:
         if beta.shape != (self.M,):
             raise ValueError("ss_replica_set_beta: beta must have M entries")
         check(self.L.hgibbs_ss_replica_set_beta(self.h, int(r) & 0xffffffff, _dp(beta)))
+
+    def ss_post_begin(self, R, T):
+        """hgibbs_ss_post_begin: per-marker accumulators over T planned records of the R allocated replicas (R = 0: the handle's own chain)."""
+        check(self.L.hgibbs_ss_post_begin(self.h, int(R) & 0xffffffff, int(T) & 0xffffffff))
+
+    def ss_post_add(self):
+        """hgibbs_ss_post_add: folds the chains' effects and components as they stand into the accumulators (one record)."""
+        check(self.L.hgibbs_ss_post_add(self.h))
+
+    def ss_post_get(self):
+        """hgibbs_ss_post_get, after the last planned record: (mean[M], sd[M], pip[M], cnt[K, M] uint32, rhat[M])."""
+        mean, sd, pip, rhat = np.zeros(self.M), np.zeros(self.M), np.zeros(self.M), np.zeros(self.M)
+        cnt = np.zeros((self.K, self.M), dtype=np.uint32)
+        check(self.L.hgibbs_ss_post_get(self.h, _dp(mean), _dp(sd), _dp(pip), cnt.ctypes.data_as(C_U32P), _dp(rhat)))
+        return mean, sd, pip, cnt, rhat
+
+    def ss_post_raw(self, r, half):
+        """hgibbs_ss_post_raw: the Welford pair (mean[M], m2[M]) of half `half` of chain r; r = the number of chains, half = 0: the pooled pair."""
+        hmean, hm2 = np.zeros(self.M), np.zeros(self.M)
+        check(self.L.hgibbs_ss_post_raw(self.h, int(r) & 0xffffffff, int(half) & 0xffffffff, _dp(hmean), _dp(hm2)))
+        return hmean, hm2
+
+    def ss_post_end(self):
+        check(self.L.hgibbs_ss_post_end(self.h))
+
+    def last_ss_post_ms(self):
+        """(add_ms, final_ms): device time of every ss_post_add since ss_post_begin (their sum) and of ss_post_get's kernel."""
+        a, b = C.c_double(), C.c_double()
+        check(self.L.hgibbs_last_ss_post_ms(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def ss_end(self):
         check(self.L.hgibbs_ss_end(self.h))

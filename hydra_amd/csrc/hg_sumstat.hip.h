@@ -62,6 +62,14 @@ struct SsState {
     std::vector<uint8_t> ok;     // per marker: its standard deviation is finite
     std::vector<uint8_t> ada_host;
     double band_ms = 0.0, sweep_ms = 0.0;
+    // hgibbs_ss_post_* (hg_sspost.hip.h): the per-marker accumulators over post_T records of post_R replicas (0: the
+    // handle's own chain) -- the pooled pair, the pairs of the [chains][2] half-chains, cnt [K][M], the error word, the table's four columns
+    bool post_open = false, post_final = false;
+    uint32_t post_R = 0, post_T = 0, post_t = 0, post_K = 0;
+    DevBuf<double> pmean, pm2, phmean, phm2, pout;
+    DevBuf<uint32_t> pcnt;
+    DevBuf<unsigned long long> pflag;
+    double post_add_ms = 0.0, post_final_ms = 0.0;
 };
 
 namespace {
@@ -614,6 +622,7 @@ extern "C" int hgibbs_ss_replicas(hgibbs_t h, uint32_t R)
     SsState* s = ss_of(h, who);
     if (!s) return 1;
     if (R < 1u || R > SS_RMAX) return fail("%s: R = %u, must be in [1, %u]", who, R, SS_RMAX);
+    if (s->post_open) return fail("%s: posterior accumulators are open on this handle (hgibbs_ss_post_end first): they count these replicas", who);
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
     const size_t M = h->M, n = (size_t)R * M;

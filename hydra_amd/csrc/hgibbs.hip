@@ -62,6 +62,8 @@ extern "C" void hgibbs_set_error_(const char* msg) { g_err = msg; }
 struct BwState; // BayesW side of the handle (hg_bayesw.hip.h)
 struct SparseLoad; // a load from index lists between hgibbs_sparse_begin and hgibbs_sparse_end (hg_sparse.hip.h)
 struct SsState; // the summary-statistics sweep's side of the handle between hgibbs_ss_begin and hgibbs_ss_end (hg_sumstat.hip.h)
+struct hgibbs_ctx;
+bool ss_post_is_open(const hgibbs_ctx* h); // hgibbs_ss_post_begin .. hgibbs_ss_post_end (hg_sspost.hip.h)
 
 // What belongs to one loaded problem: alloc_problem builds it whole and only then moves it into the handle; an abandoned sparse load
 // assigns an empty one
@@ -1195,6 +1197,7 @@ int hgibbs_set_model(hgibbs_t h, int G, int K, const int32_t* groups_host, const
 {
     if (!h || !h->bed) return fail("hgibbs_set_model: load data first");
     if (G < 1 || K < 2 || K > MAX_K) return fail("hgibbs_set_model: need G>=1 and 2<=K<=%d (got G=%d K=%d)", MAX_K, G, K);
+    if (ss_post_is_open(h)) return fail("hgibbs_set_model: posterior accumulators are open on this handle (hgibbs_ss_post_end first): their counts are sized for K = %d", h->K);
     HIP_TRY(hipSetDevice(h->device));
     // checked and built in locals; the handle changes once nothing can fail any more
     std::vector<int32_t> groups(h->M, 0);
@@ -2208,6 +2211,7 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
 #include "hg_ldscore.hip.h"
 #include "hg_ldmask.hip.h"
 #include "hg_sumstat.hip.h"
+#include "hg_sspost.hip.h"
 #include "hg_mdots.hip.h"
 #include "hg_mclass.hip.h"
 #include "hg_sgram.hip.h"

@@ -115,6 +115,9 @@
 // `--sumstats-chains R` (1..64) runs R chains from the seeds --seed + r on the one band, one launch per iteration for all of them
 // (DESIGN.md section 33): chain 0 writes the files of the run without the option, chain r >= 1 writes <name>.c<r>.{csv,bet,cpn,acu},
 // the files of the run with --seed raised by r; <name>.rhat holds split-R^ and the effective sample size of the hyper-parameters.
+// `--sumstats-post [--sumstats-post-all] [--sumstats-post-only] [--sumstats-post-out F]` writes <name>.post (or F), one row per .bim
+// marker: posterior mean and sd of the effect, PIP, component shares and split-R^ over the chains, accumulated on the device from the
+// thinned records at or after --burn-in (-all: every iteration from there; -only: no .bet, .cpn, .acu at all).
 //
 // Not reproduced (out of scope for the hot path): the mixed
 // in-memory representation (--threshold-fnz), --sparse-sync/--bed-sync, --check-RAM,
@@ -210,6 +213,8 @@ struct Options { // src/options.hpp:20-138 (subset that reaches bayesMPI)
     std::string sumstatsStreams;
     bool sumstatsChainsGiven = false; // --sumstats-chains R: R chains from the seeds --seed + r on one band, with a .rhat table
     std::string sumstatsChains;
+    bool sumstatsPost = false, sumstatsPostAll = false, sumstatsPostOnly = false; // --sumstats-post: the per-marker posterior table
+    std::string sumstatsPostOut; // --sumstats-post-out F
     bool saveGiven = false, ignoreXfilesGiven = false; // --save, --ignore-xfiles on the command line (--sumstats takes no checkpoint option)
     int batch = 0, cpg = 0; // tuning knobs of this build (not hydra's)
 };
@@ -346,6 +351,14 @@ Options parse(int argc, const char* argv[])
         } else if (a == "--sumstats-chains") {
             o.sumstatsChains = need(i);
             o.sumstatsChainsGiven = true;
+        } else if (a == "--sumstats-post") {
+            o.sumstatsPost = true;
+        } else if (a == "--sumstats-post-all") {
+            o.sumstatsPostAll = true;
+        } else if (a == "--sumstats-post-only") {
+            o.sumstatsPostOnly = true;
+        } else if (a == "--sumstats-post-out") {
+            o.sumstatsPostOut = need(i);
         } else if (a == "--sumstats-n") {
             o.sumstatsN = need(i);
             o.sumstatsNGiven = true;
@@ -3898,6 +3911,84 @@ SumstatTable read_sumstats(const std::string& path, const BimRows& bim, unsigned
     return t;
 }
 
+// --sumstats-post: which iterations are records, how many there are, and the table.
+bool post_counts(const Options& opt, unsigned iteration) { return iteration >= opt.burnin && (opt.sumstatsPostAll || iteration % opt.thin == 0); }
+
+unsigned post_records(const Options& opt)
+{
+    if (opt.burnin >= opt.chainLength) return 0;
+    if (opt.sumstatsPostAll || opt.thin <= 1) return opt.chainLength - opt.burnin;
+    const unsigned first = (opt.burnin + opt.thin - 1) / opt.thin, last = (opt.chainLength - 1) / opt.thin; // multiples of --thin in [burn-in, length)
+    return last >= first ? last - first + 1 : 0;
+}
+
+struct PostJob {
+    bool on = false, only = false;
+    unsigned T = 0;
+    std::string path;
+    const BimRows* bim = nullptr;
+    const std::vector<double>* mstd = nullptr;
+    const std::vector<uint8_t>* use = nullptr;
+    int K = 0;
+    double add_ms = 0.0, final_ms = 0.0; // device time of every add and of the table's kernel
+};
+
+PostJob post_job(const Options& opt, const std::string& base, const BimRows& bim, const std::vector<double>& mstd, const std::vector<uint8_t>& use, int K)
+{
+    PostJob p;
+    p.on = opt.sumstatsPost;
+    p.only = opt.sumstatsPostOnly;
+    p.T = post_records(opt);
+    p.path = opt.sumstatsPostOut.empty() ? base + ".post" : opt.sumstatsPostOut;
+    p.bim = &bim;
+    p.mstd = &mstd;
+    p.use = &use;
+    p.K = K;
+    return p;
+}
+
+// after the last record, while the chains' ss state still stands: the table of `chains` chains to p.path
+void write_post_table(PostJob& p, hgibbs_t dev, unsigned chains, unsigned M)
+{
+    const int K = p.K;
+    std::vector<double> mean(M), sd(M), pip(M), rhat(M);
+    std::vector<uint32_t> cnt((size_t)K * M);
+    hg_check(hgibbs_ss_post_get(dev, mean.data(), sd.data(), pip.data(), cnt.data(), rhat.data()), "hgibbs_ss_post_get");
+    hg_check(hgibbs_last_ss_post_ms(dev, &p.add_ms, &p.final_ms), "hgibbs_last_ss_post_ms");
+    hg_check(hgibbs_ss_post_end(dev), "hgibbs_ss_post_end");
+    FILE* f = open_out(p.path, "wb+");
+    std::fprintf(f, "CHR\tSNP\tBP\tA1\tA2\tUSED\tNCHAINS\tNREC\tMEAN\tSD\tBETA\tPIP");
+    for (int k = 1; k < K; ++k) std::fprintf(f, "\tPC%d", k);
+    std::fprintf(f, "\tRHAT\n");
+    const double all = (double)chains * (double)p.T;
+    for (unsigned j = 0; j < M; ++j) {
+        const BimRows& b = *p.bim;
+        std::fprintf(f, "%s\t%s\t%lld\t%s\t%s\t%d", b.chr[j].c_str(), b.id[j].c_str(), b.bp[j], b.a1[j].c_str(), b.a2[j].c_str(), (*p.use)[j] ? 1 : 0);
+        if (!(*p.use)[j]) {
+            for (int k = 0; k < K + 6; ++k) std::fprintf(f, "\tNA");
+            std::fprintf(f, "\n");
+            continue;
+        }
+        std::fprintf(f, "\t%u\t%u\t%.9g\t%.9g\t%.9g\t%.9g", chains, p.T, mean[j], sd[j], mean[j] * (*p.mstd)[j], pip[j]);
+        for (int k = 1; k < K; ++k) std::fprintf(f, "\t%.9g", (double)cnt[(size_t)k * M + j] / all);
+        if (std::isnan(rhat[j]))
+            std::fprintf(f, "\tNA\n");
+        else
+            std::fprintf(f, "\t%.9g\n", rhat[j]);
+    }
+    close_out(f, p.path);
+}
+
+// what the closing SUMSTAT: line gains with --sumstats-post
+std::string post_report(const PostJob& p)
+{
+    if (!p.on) return "";
+    char b[512];
+    std::snprintf(b, sizeof b, ", %u records per chain counted on the device into %s (%.3f ms for all adds, %.3f ms for the table's kernel)", p.T, p.path.c_str(), p.add_ms,
+                  p.final_ms);
+    return b;
+}
+
 // --sumstats-chains: R chains on the band of `dev`, from the model `md` with the seeds md.seed + r.  Chain 0's
 // files are <base>.*, chain r's <base>.c<r>.*; <base>.rhat holds the convergence table over the thinned records at or after
 // --burn-in.  Returns what the closing line reports: streams, largest interval, sweeps, device ms of all launches, largest R^.
@@ -3908,7 +3999,7 @@ struct ChainsReport {
 };
 
 ChainsReport run_sumstats_chains(const Options& opt, hgibbs_t dev, const hydra_model_desc& md, const SumstatTable& tab, const LdWindow& win, uint32_t W,
-                                 unsigned M, int G, const std::string& base)
+                                 unsigned M, int G, const std::string& base, PostJob& post)
 {
     ChainsReport rep;
     long R = 1, smax = 0;
@@ -3926,12 +4017,15 @@ ChainsReport run_sumstats_chains(const Options& opt, hgibbs_t dev, const hydra_m
         hg_check(hydra_ss_multi_streams(chains, nullptr, bounds.data(), nullptr), "hydra_ss_multi_streams");
         for (uint32_t s = 0; s < rep.streams; ++s) rep.largest = std::max(rep.largest, bounds[s + 1] - bounds[s]);
     }
+    if (post.on) hg_check(hgibbs_ss_post_begin(dev, (uint32_t)R, post.T), "hgibbs_ss_post_begin");
+    const bool effects = !(post.on && post.only); // --sumstats-post-only: no .bet, .cpn, .acu, and no download of a record
 
     OutFiles outs;
     std::vector<FILE*> outf(R), betf(R), cpnf(R), acuf(R);
     for (long r = 0; r < R; ++r) {
         const std::string b = r ? base + ".c" + std::to_string(r) : base;
         outf[r] = outs.open(b + ".csv");
+        if (!effects) continue;
         betf[r] = outs.open(b + ".bet");
         cpnf[r] = outs.open(b + ".cpn");
         acuf[r] = outs.open(b + ".acu");
@@ -3952,6 +4046,7 @@ ChainsReport run_sumstats_chains(const Options& opt, hgibbs_t dev, const hydra_m
         hg_check(hgibbs_last_ss_ms(dev, &rep.band_ms, &sweep_ms), "hgibbs_last_ss_ms");
         rep.sweep_total_ms += sweep_ms;
         ++rep.sweeps;
+        if (post.on && post_counts(opt, iteration)) hg_check(hgibbs_ss_post_add(dev), "hgibbs_ss_post_add");
         for (long r = 0; r < R; ++r) {
             double sigmaE = 0, mu = 0;
             hg_check(hydra_ss_multi_state(chains, (uint32_t)r, &sigmaE, &mu, sigmaG.data(), nullptr, m0.data(), nullptr, nullptr), "hydra_ss_multi_state");
@@ -3965,12 +4060,14 @@ ChainsReport run_sumstats_chains(const Options& opt, hgibbs_t dev, const hydra_m
                         "mu = %15.10f, m0 = %10ld\n",
                         r, iteration, t1 - t0, sweep_ms, sg, sigmaE, mu, m0s);
             if (iteration % opt.thin == 0) {
-                hg_check(hydra_ss_multi_effects(chains, (uint32_t)r, beta.data(), comp.data(), acum.data(), nullptr), "hydra_ss_multi_effects");
+                if (effects) hg_check(hydra_ss_multi_effects(chains, (uint32_t)r, beta.data(), comp.data(), acum.data(), nullptr), "hydra_ss_multi_effects");
                 const int len = hydra_ss_multi_csv_line(chains, (uint32_t)r, iteration, buff.data(), buff.size());
                 write_line(outf[r], n_thinned_saved, buff.data(), len);
-                write_thinned(betf[r], n_thinned_saved, iteration, beta.data(), M, sizeof(double));
-                write_thinned(acuf[r], n_thinned_saved, iteration, acum.data(), M, sizeof(double));
-                write_thinned(cpnf[r], n_thinned_saved, iteration, comp.data(), M, sizeof(int));
+                if (effects) {
+                    write_thinned(betf[r], n_thinned_saved, iteration, beta.data(), M, sizeof(double));
+                    write_thinned(acuf[r], n_thinned_saved, iteration, acum.data(), M, sizeof(double));
+                    write_thinned(cpnf[r], n_thinned_saved, iteration, comp.data(), M, sizeof(int));
+                }
                 if (iteration >= opt.burnin) {
                     std::vector<double>* row = &rec[(size_t)r * P];
                     for (int g = 0; g < G; ++g) row[g].push_back(sigmaG[g]);
@@ -3986,6 +4083,7 @@ ChainsReport run_sumstats_chains(const Options& opt, hgibbs_t dev, const hydra_m
         if (iteration % opt.thin == 0) n_thinned_saved += 1;
     }
     outs.close(true);
+    if (post.on) write_post_table(post, dev, (unsigned)R, M);
     hydra_ss_multi_destroy(chains);
 
     // <base>.rhat
@@ -4065,17 +4163,20 @@ int run_sumstats(const Options& opt, const Cohort& co, const std::vector<int32_t
     md.K = K;
     md.groups = groups.empty() ? nullptr : groups.data();
     md.mS = mS_flat.data();
+    PostJob post = post_job(opt, base, bim, mstd, tab.use, K);
+    const char* files = post.on && post.only ? "csv" : "{csv,bet,cpn,acu}";
     if (opt.sumstatsChainsGiven) { // R chains in one launch per iteration, and the convergence table
-        const ChainsReport rep = run_sumstats_chains(opt, dev, md, tab, win, W, M, G, base);
+        const ChainsReport rep = run_sumstats_chains(opt, dev, md, tab, win, W, M, G, base, post);
         hgibbs_destroy(dev);
         char par[96] = "", rh[48] = "NA";
         if (rep.streams) std::snprintf(par, sizeof par, " in %u streams (largest interval %u markers)", rep.streams, rep.largest);
         if (!std::isnan(rep.max_rhat)) std::snprintf(rh, sizeof rh, "%.9g", rep.max_rhat);
         std::printf("SUMSTAT: %u markers used, %u left out (%u not in the table, %u with another allele pair, %u without usable BETA, SE and N, %u without a finite sd in the panel), "
                     "n_eff %.12g, band %u x %u doubles = %.1f MiB of device memory (built in %.3f ms), %u chains, %.3f ms per sweep launch (all chains) on the device over %u "
-                    "sweeps%s, largest R^ %s, wrote %s.{csv,bet,cpn,acu}, %s.c<r>.{csv,bet,cpn,acu} for the chains r >= 1 and %s.rhat\n",
+                    "sweeps%s, largest R^ %s, wrote %s.%s, %s.c<r>.%s for the chains r >= 1 and %s.rhat%s\n",
                     used, M - used, M - tab.matched - tab.allele - tab.unusable, tab.allele, tab.unusable, nosd, tab.n_eff, M, W, (double)M * W * 8.0 / 1048576.0,
-                    rep.band_ms, rep.chains, rep.sweeps ? rep.sweep_total_ms / rep.sweeps : 0.0, rep.sweeps, par, rh, base.c_str(), base.c_str(), base.c_str());
+                    rep.band_ms, rep.chains, rep.sweeps ? rep.sweep_total_ms / rep.sweeps : 0.0, rep.sweeps, par, rh, base.c_str(), files, base.c_str(), files, base.c_str(),
+                    post_report(post).c_str());
         return 0;
     }
     hydra_ss_chain_t chain = nullptr;
@@ -4093,14 +4194,19 @@ int run_sumstats(const Options& opt, const Cohort& co, const std::vector<int32_t
     }
     double band_ms = 0.0, sweep_ms = 0.0;
     hg_check(hgibbs_last_ss_ms(dev, &band_ms, &sweep_ms), "hgibbs_last_ss_ms");
+    if (post.on) hg_check(hgibbs_ss_post_begin(dev, 0u, post.T), "hgibbs_ss_post_begin"); // the handle's own chain
+    const bool effects = !(post.on && post.only); // --sumstats-post-only: no .bet, .cpn, .acu, and no download of a record
 
     // the chain's files and formats (:1302-1309, :2736-2794)
     OutFiles outs;
     FILE* outf = outs.open(base + ".csv");
-    FILE* betf = outs.open(base + ".bet");
-    FILE* cpnf = outs.open(base + ".cpn");
-    FILE* acuf = outs.open(base + ".acu");
-    for (FILE* f : {betf, cpnf, acuf}) pwrite_at(f, 0, &M, sizeof(unsigned));
+    FILE *betf = nullptr, *cpnf = nullptr, *acuf = nullptr;
+    if (effects) {
+        betf = outs.open(base + ".bet");
+        cpnf = outs.open(base + ".cpn");
+        acuf = outs.open(base + ".acu");
+        for (FILE* f : {betf, cpnf, acuf}) pwrite_at(f, 0, &M, sizeof(unsigned));
+    }
     std::vector<double> beta(M), acum(M), sigmaG(G);
     std::vector<int32_t> comp(M), m0(G);
     std::vector<char> buff(50000);
@@ -4124,25 +4230,29 @@ int run_sumstats(const Options& opt, const Cohort& co, const std::vector<int32_t
         std::printf("RESULT : it %4d: proc = %9.3f s, sweep = %9.3f ms on the device, sigmaG = %15.10f, sigmaE = %15.10f, mu = %15.10f, m0 = %10ld\n", iteration, t1 - t0,
                     sweep_ms, sg, sigmaE, mu, m0s);
         std::fflush(stdout);
+        if (post.on && post_counts(opt, iteration)) hg_check(hgibbs_ss_post_add(dev), "hgibbs_ss_post_add");
         if (iteration % opt.thin == 0) {
-            hg_check(hydra_ss_chain_effects(chain, beta.data(), comp.data(), acum.data(), nullptr), "hydra_ss_chain_effects");
+            if (effects) hg_check(hydra_ss_chain_effects(chain, beta.data(), comp.data(), acum.data(), nullptr), "hydra_ss_chain_effects");
             const int len = hydra_ss_chain_csv_line(chain, iteration, buff.data(), buff.size());
             write_line(outf, n_thinned_saved, buff.data(), len);
-            write_thinned(betf, n_thinned_saved, iteration, beta.data(), M, sizeof(double));
-            write_thinned(acuf, n_thinned_saved, iteration, acum.data(), M, sizeof(double));
-            write_thinned(cpnf, n_thinned_saved, iteration, comp.data(), M, sizeof(int));
+            if (effects) {
+                write_thinned(betf, n_thinned_saved, iteration, beta.data(), M, sizeof(double));
+                write_thinned(acuf, n_thinned_saved, iteration, acum.data(), M, sizeof(double));
+                write_thinned(cpnf, n_thinned_saved, iteration, comp.data(), M, sizeof(int));
+            }
             n_thinned_saved += 1;
         }
     }
     outs.close(true);
+    if (post.on) write_post_table(post, dev, 1u, M);
     hydra_ss_chain_destroy(chain);
     hgibbs_destroy(dev);
     char par[96] = "";
     if (streams) std::snprintf(par, sizeof par, " in %u streams (largest interval %u markers)", streams, largest);
     std::printf("SUMSTAT: %u markers used, %u left out (%u not in the table, %u with another allele pair, %u without usable BETA, SE and N, %u without a finite sd in the panel), "
-                "n_eff %.12g, band %u x %u doubles = %.1f MiB of device memory (built in %.3f ms), %.3f ms per sweep on the device over %u sweeps%s, wrote %s.{csv,bet,cpn,acu}\n",
+                "n_eff %.12g, band %u x %u doubles = %.1f MiB of device memory (built in %.3f ms), %.3f ms per sweep on the device over %u sweeps%s, wrote %s.%s%s\n",
                 used, M - used, M - tab.matched - tab.allele - tab.unusable, tab.allele, tab.unusable, nosd, tab.n_eff, M, W, (double)M * W * 8.0 / 1048576.0, band_ms,
-                sweeps ? sweep_total_ms / sweeps : 0.0, sweeps, par, base.c_str());
+                sweeps ? sweep_total_ms / sweeps : 0.0, sweeps, par, base.c_str(), files, post_report(post).c_str());
     return 0;
 }
 
@@ -4388,9 +4498,21 @@ void check_sumstats(const Options& opt, int nranks)
 {
     if (!opt.sumstats) {
         if (const char* o = first_given({{"--sumstats-window", opt.sumstatsWindowGiven}, {"--sumstats-window-kb", opt.sumstatsKbGiven}, {"--sumstats-n", opt.sumstatsNGiven},
-                                          {"--sumstats-streams", opt.sumstatsStreamsGiven}, {"--sumstats-chains", opt.sumstatsChainsGiven}}))
+                                          {"--sumstats-streams", opt.sumstatsStreamsGiven}, {"--sumstats-chains", opt.sumstatsChainsGiven},
+                                          {"--sumstats-post", opt.sumstatsPost}}))
             fatal(std::string("FATAL  : ") + o + " needs --sumstats");
-        return;
+    }
+    if (!opt.sumstatsPost)
+        if (const char* o = first_given({{"--sumstats-post-all", opt.sumstatsPostAll}, {"--sumstats-post-only", opt.sumstatsPostOnly},
+                                          {"--sumstats-post-out", !opt.sumstatsPostOut.empty()}}))
+            fatal(std::string("FATAL  : ") + o + " needs --sumstats-post");
+    if (!opt.sumstats) return;
+    if (opt.sumstatsPost) {
+        const unsigned T = post_records(opt);
+        if (T < 4)
+            fatal("FATAL  : --sumstats-post: T = " + std::to_string(T) + " record(s) per chain (--chain-length " + std::to_string(opt.chainLength) + ", --burn-in " +
+                  std::to_string(opt.burnin) + ", --thin " + std::to_string(opt.thin) + (opt.sumstatsPostAll ? ", every iteration at or after the burn-in" : ", the thinned iterations at or after the burn-in") +
+                  "): split-R^ of the halved chains needs at least 4");
     }
     if (opt.bayesType == "bayesWMPI") fatal("FATAL  : --sumstats takes a bayesMPI command line, not --mpibayes bayesWMPI");
     const std::pair<const char*, bool> modes[] = {

@@ -523,6 +523,35 @@ int hgibbs_ss_replica_sums(hgibbs_t h, double* sb /* R */, double* sc /* R */, d
 int hgibbs_ss_replica_get(hgibbs_t h, uint32_t r, double* beta, int32_t* comp, double* acum, double* c);
 int hgibbs_ss_replica_set_beta(hgibbs_t h, uint32_t r, const double* beta);
 
+/* ---- the per-marker posterior table, accumulated on the device ---- */
+/* Per marker over T planned records of every chain: the posterior mean and sd of the effect, the inclusion probability, the draws per
+ * component, and split-R^ over the 2 C half-chains (hgibbs_mcmc_diag's split and formulas), folded where the chains' state lies: no
+ * record crosses the bus.  C = R chains for R >= 1 (the R allocated replicas), C = 1 for R = 0 (the handle's own chain: what
+ * hgibbs_ss_sweep and hgibbs_ss_sweep_streams write).  A record is the chains' effects and components as they stand at the call.
+ *   post_begin  allocates and zeroes the accumulators: the pooled Welford pair (mean, m2) per marker, the pair of every half-chain
+ *               (C x 2 x M), the counts K x M.  T is planned in advance because the split needs it: with n = T / 2, record t (0-based,
+ *               the number of adds so far) lies in half 0 if t < n and in half 1 if t >= T - n; an odd T leaves the middle record in
+ *               neither.  A second call replaces the first's state.  Refused by name: no ss state; R >= 1 without replicas, or another R
+ *               than the allocated one; T < 4; R T >= 2^32; no model set (K is not known); memory that does not fit (with R, T and the
+ *               bytes).  While the state is open hgibbs_ss_replicas and hgibbs_set_model are refused; hgibbs_ss_end frees it too.
+ *   post_add    ONE launch, a thread per marker, the chains in order r = 0 .. C - 1: a Welford step d = x - mean; mean = mean + d / q;
+ *               m2 = m2 + d (x - mean) into the pooled pair with q = t C + r + 1, the same step into chain r's half-chain pair with the
+ *               count inside the half where t lies in one, and cnt[comp][j] += 1.  Only correctly rounded f64 + - x / in a fixed order:
+ *               the accumulators repeat bit for bit.  Reads the chains' state and writes none of it.  Refused: before post_begin; beyond
+ *               T; a component outside [0, K) (with the chain and the marker; the accumulators are dropped).
+ *   post_get    after exactly T adds: mean = the pooled mean, sd = sqrt(m2 / (C T - 1)), pip = (C T - cnt[0]) / (C T), cnt (K x M,
+ *               cnt[k M + j]), rhat (NaN where no half-chain moves: !(W > 0)); M each but cnt, any pointer may be NULL.
+ *   post_raw    after exactly T adds: the pair (mean, m2) of half `half` (0, 1) of chain r in [0, C), or with r = C and half = 0 the pooled
+ *               pair; M doubles each, either may be NULL.  Refused: r or half out of range.
+ *   post_end    frees the accumulators.
+ *   last_ss_post_ms  device time of every post_add kernel since post_begin (their sum) and of post_get's kernel; 0 without a state. */
+int hgibbs_ss_post_begin(hgibbs_t h, uint32_t R, uint32_t T);
+int hgibbs_ss_post_add(hgibbs_t h);
+int hgibbs_ss_post_get(hgibbs_t h, double* mean, double* sd, double* pip, uint32_t* cnt /* K x M */, double* rhat);
+int hgibbs_ss_post_raw(hgibbs_t h, uint32_t r, uint32_t half, double* hmean, double* hm2);
+int hgibbs_ss_post_end(hgibbs_t h);
+int hgibbs_last_ss_post_ms(hgibbs_t h, double* add_ms, double* final_ms);
+
 /* Convergence of R chains of one scalar (host only): x is R x T, chain-major.  mean and sd over all R T draws; rhat: split-R^ (BDA3
  * section 11.4: every chain halved, an odd T drops the middle draw; no rank normalisation); ess: from the same 2 R half-chains'
  * combined autocovariances, truncated by Geyer's initial monotone positive sequence (Stan reference manual), at most

@@ -19,8 +19,14 @@ with the device time of every replica launch, its median against the single chai
 an iteration beside it (what the host adds: R shuffles, the uploads, the sums).  The records go to --chains-out as well
 (profiles/ss_chains_bench.jsonl unless told otherwise).
 
+--post (with --chains) folds every iteration of those runs into the per-marker posterior accumulators (hgibbs_ss_post_add, DESIGN.md
+section 34) and downloads every chain's effects, components and acum as the command line does per record without
+--sumstats-post-only (hydra_ss_multi_effects into buffers made once).  Per R one record in --post-out (profiles/ss_post_bench.jsonl
+unless told otherwise): the device time of an add beside the replica launch of the same iteration, the bytes the add kernel moves and
+the bandwidth that implies, the table's kernel, and the host's wall time of an iteration with the downloads and without them.
+
     python tools/ss_bench.py [--cases 10000x100000x128,20000x1000000x512] [--n-eff 4000000] [--signals 0.001] [--iters 6] [--out F]
-                             [--chromosomes C] [--streams S] [--chains R[,R...]] [--chains-iters I] [--chains-out F]
+                             [--chromosomes C] [--streams S] [--chains R[,R...]] [--chains-iters I] [--chains-out F] [--post] [--post-out F]
 """
 import argparse
 import json
@@ -60,11 +66,14 @@ def main():
     ap.add_argument("--chains", default="", help="numbers of chains (1..64), comma-separated: time the replica launch with each after the single chain")
     ap.add_argument("--chains-iters", type=int, default=0, help="iterations of every --chains run (default: --iters)")
     ap.add_argument("--chains-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "ss_chains_bench.jsonl"))
+    ap.add_argument("--post", action="store_true", help="with --chains: time hgibbs_ss_post_add and the per-record downloads it can replace (at least 4 iterations)")
+    ap.add_argument("--post-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "ss_post_bench.jsonl"))
     ap.add_argument("--label", default=None, help="a word copied into every record (which build, which run)")
     args = ap.parse_args()
     out = open(args.out, "a") if args.out else None
     chains = [int(x) for x in args.chains.split(",") if x]
     chains_out = open(args.chains_out, "a") if chains else None
+    post_out = open(args.post_out, "a") if chains and args.post else None
 
     def emit(rec):
         line = json.dumps(rec)
@@ -140,12 +149,50 @@ def main():
         single_host = float(np.median([s["wall_ms"] - s["sweep_ms"] for s in sweeps])) if sweeps else None
         for R in chains:
             mc = capi.SsMultiChain(dev, n, W, xty, [11 + r for r in range(R)], ahead=ahead, streams=args.streams or None)
-            its = []
-            for it in range(args.chains_iters or args.iters):
+            its, pits = [], []
+            T = args.chains_iters or args.iters
+            if args.post:
+                dev.ss_post_begin(R, T)
+                beta, acum, comp = np.zeros(M), np.zeros(M), np.zeros(M, dtype=np.int32)
+                added = 0.0
+            for it in range(T):
                 t0 = time.perf_counter()
                 mc.iterate()
                 wall = 1e3 * (time.perf_counter() - t0)
                 its.append({"it": it, "launch_ms": round(dev.last_ss_ms()[1], 3), "wall_ms": round(wall, 3), "nnz_updates": [mc.last_nnz(r) for r in range(R)]})
+                if args.post:
+                    t1 = time.perf_counter()
+                    dev.ss_post_add()
+                    t2 = time.perf_counter()
+                    for r in range(R):  # what a record costs the command line without --sumstats-post-only, but for the disk
+                        capi.check(mc.L.hydra_ss_multi_effects(mc.h, r, capi._dp(beta), capi._ip(comp), capi._dp(acum), None))
+                    t3 = time.perf_counter()
+                    total = dev.last_ss_post_ms()[0]
+                    pits.append({"it": it, "launch_ms": its[-1]["launch_ms"], "iterate_wall_ms": round(wall, 3), "add_ms": round(total - added, 4),
+                                 "add_wall_ms": round(1e3 * (t2 - t1), 3), "download_wall_ms": round(1e3 * (t3 - t2), 3)})
+                    added = total
+            if args.post:
+                t1 = time.perf_counter()
+                mean, sd, pip, cnt, rhat = dev.ss_post_get()
+                get_wall = 1e3 * (time.perf_counter() - t1)
+                K = cnt.shape[0]
+                med = {k: float(np.median([x[k] for x in pits])) for k in ("launch_ms", "iterate_wall_ms", "add_ms", "add_wall_ms", "download_wall_ms")}
+                # a record inside a half (every record of an even T): per chain and marker the effect, the component and the half-chain's
+                # pair read and written; per marker the pooled pair and the K counts read and written
+                nbytes = M * (R * (8 + 4 + 32) + 32 + 8 * K)
+                prec = {"kind": "post", "n_panel": N, "m": M, "W": W, "chains": R, "records": T, "K": int(K), "launch_ms_median": round(med["launch_ms"], 3),
+                        "add_ms_median": round(med["add_ms"], 4), "add_to_launch": round(med["add_ms"] / med["launch_ms"], 6), "add_bytes": int(nbytes),
+                        "add_gb_per_s": round(nbytes / (med["add_ms"] * 1e-3) / 1e9, 1), "final_ms": round(dev.last_ss_post_ms()[1], 4),
+                        "get_wall_ms": round(get_wall, 3), "download_bytes_per_record": int(R * M * 20),
+                        "host_s_per_iteration_with_downloads": round(1e-3 * (med["iterate_wall_ms"] + med["add_wall_ms"] + med["download_wall_ms"]), 6),
+                        "host_s_per_iteration_post_only": round(1e-3 * (med["iterate_wall_ms"] + med["add_wall_ms"]), 6),
+                        "pip_between_0_and_1": int(np.count_nonzero((pip > 0) & (pip < 1))), "rhat_finite": int(np.count_nonzero(np.isfinite(rhat))), "iterations": pits}
+                for k in ("chromosomes", "streams_max", "streams", "largest_interval", "label"):
+                    if k in rec:
+                        prec[k] = rec[k]
+                emit(prec)
+                post_out.write(json.dumps(prec) + "\n")
+                post_out.flush()
             launch = float(np.median([x["launch_ms"] for x in its]))
             host = float(np.median([x["wall_ms"] - x["launch_ms"] for x in its]))
             crec = {"kind": "chains", "n_panel": N, "m": M, "W": W, "chains": R, "workgroups": R * max(1, len(mc.streams()[0]) - 1),
