@@ -113,6 +113,9 @@ SsState* ss_post_of(hgibbs_ctx* h, const char* who, bool done)
     return s;
 }
 
+// the chains the open accumulators count: post_R replicas, or (0) the handle's own chain
+SsChains ss_post_chains(hgibbs_ctx* h, SsState* s) { return s->post_R ? ss_replica_chains(s) : ss_own_chain(h, s); }
+
 void ss_post_close(SsState* s)
 {
     s->post_open = false;
@@ -129,7 +132,7 @@ bool ss_post_is_open(const hgibbs_ctx* h) { return h && h->ss && h->ss->post_ope
 extern "C" int hgibbs_ss_post_begin(hgibbs_t h, uint32_t R, uint32_t T)
 {
     const char* who = "hgibbs_ss_post_begin";
-    SsState* s = R >= 1u ? ss_replicas_of(h, who, R) : ss_of(h, who);
+    SsState* s = R >= 1u ? ss_replicas_of(h, who, &R) : ss_of(h, who);
     if (!s) return 1;
     if (T < 4u) return fail("%s: T = %u records per chain, split-R^ needs at least 4", who, T);
     const uint32_t C = R ? R : 1u;
@@ -171,19 +174,18 @@ extern "C" int hgibbs_ss_post_add(hgibbs_t h)
     if (!s) return 1;
     if (s->post_t >= s->post_T) return fail("%s: the %u planned records are all added", who, s->post_T);
     HIP_TRY(hipSetDevice(h->device));
-    const uint32_t M = h->M, C = s->post_R ? s->post_R : 1u, T = s->post_T, t = s->post_t, n = T / 2u;
-    const double* beta = s->post_R ? (const double*)s->rbeta : (const double*)h->beta;
-    const int32_t* comp = s->post_R ? (const int32_t*)s->rcomp : (const int32_t*)h->comp;
+    const SsChains ch = ss_post_chains(h, s);
+    const uint32_t M = h->M, C = ch.C, T = s->post_T, t = s->post_t, n = T / 2u;
     const uint32_t grid = (M + (uint32_t)SP_TPB - 1u) / (uint32_t)SP_TPB;
     double ms = 0.0;
     if (lap_begin(h)) return 1;
     if (t < n)
-        k_ss_post_add<true><<<grid, SP_TPB, 0, h->stream>>>(beta, comp, M, C, (int)s->post_K, t, 0u, t + 1u, s->pmean, s->pm2, s->phmean, s->phm2, s->pcnt, s->pflag);
+        k_ss_post_add<true><<<grid, SP_TPB, 0, h->stream>>>(ch.beta, ch.comp, M, C, (int)s->post_K, t, 0u, t + 1u, s->pmean, s->pm2, s->phmean, s->phm2, s->pcnt, s->pflag);
     else if (t >= T - n)
-        k_ss_post_add<true><<<grid, SP_TPB, 0, h->stream>>>(beta, comp, M, C, (int)s->post_K, t, 1u, t - (T - n) + 1u, s->pmean, s->pm2, s->phmean, s->phm2, s->pcnt,
+        k_ss_post_add<true><<<grid, SP_TPB, 0, h->stream>>>(ch.beta, ch.comp, M, C, (int)s->post_K, t, 1u, t - (T - n) + 1u, s->pmean, s->pm2, s->phmean, s->phm2, s->pcnt,
                                                             s->pflag);
     else // the middle record of an odd T: in no half
-        k_ss_post_add<false><<<grid, SP_TPB, 0, h->stream>>>(beta, comp, M, C, (int)s->post_K, t, 0u, 1u, s->pmean, s->pm2, s->phmean, s->phm2, s->pcnt, s->pflag);
+        k_ss_post_add<false><<<grid, SP_TPB, 0, h->stream>>>(ch.beta, ch.comp, M, C, (int)s->post_K, t, 0u, 1u, s->pmean, s->pm2, s->phmean, s->phm2, s->pcnt, s->pflag);
     HIP_TRY(hipGetLastError());
     if (lap_end(h, ms)) return 1;
     unsigned long long flag = SP_NO_FLAG;
@@ -205,7 +207,7 @@ namespace {
 int ss_post_finish(hgibbs_ctx* h, SsState* s)
 {
     if (s->post_final) return 0;
-    const uint32_t M = h->M, C = s->post_R ? s->post_R : 1u;
+    const uint32_t M = h->M, C = ss_post_chains(h, s).C;
     double ms = 0.0;
     if (lap_begin(h)) return 1;
     k_ss_post_final<<<(M + (uint32_t)SP_TPB - 1u) / (uint32_t)SP_TPB, SP_TPB, 0, h->stream>>>(s->pmean, s->pm2, s->pcnt, s->phmean, s->phm2, M, C, s->post_T, s->pout);
@@ -237,7 +239,7 @@ extern "C" int hgibbs_ss_post_raw(hgibbs_t h, uint32_t r, uint32_t half, double*
     const char* who = "hgibbs_ss_post_raw";
     SsState* s = ss_post_of(h, who, true);
     if (!s) return 1;
-    const uint32_t C = s->post_R ? s->post_R : 1u;
+    const uint32_t C = ss_post_chains(h, s).C;
     if (r > C || half > 1u || (r == C && half != 0u))
         return fail("%s: r = %u, half = %u: a half-chain is r in [0, %u) with half 0 or 1, the pooled pair r = %u with half 0", who, r, half, C, C);
     HIP_TRY(hipSetDevice(h->device));

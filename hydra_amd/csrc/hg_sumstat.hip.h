@@ -39,28 +39,24 @@ struct SsState {
     DevBuf<int32_t> order;
     DevBuf<uint8_t> ada;
     DevBuf<SsResult> res;
-    // hgibbs_ss_sweep_streams: the S generator states (625 words each), S results, S + 1 bounds; sized on first use
+    // What a sweep of C chains in S intervals each stages (ss_sweep_run, the three entry points alike): C S generator states (625 words
+    // each) and results, chain after chain, and S + 1 bounds; the grouped orders and masks of the C chains.  Sized at the largest C S so far.
     DevBuf<uint32_t> mts, bounds;
     DevBuf<SsResult> sres;
-    uint32_t streams_cap = 0;
+    uint32_t stage_cap = 0;
+    std::vector<int32_t> grouped;
+    std::vector<uint8_t> ada_host;
+    std::vector<SsResult> sres_host;
     // hgibbs_ss_replicas: R chains on the one band.  Replica r's c, effects, components, acum, order and mask lie at
-    // r M of the R x M arrays, its tables at r 4 G K, its counters at r G K, the generators and results of its S intervals at r S.
-    uint32_t R = 0, rep_gk = 0, rep_rs = 0; // replicas; the G K the tables and counters are sized for; the R S the generators are
+    // r M of the R x M arrays, its tables at r 4 G K, its counters at r G K.
+    uint32_t R = 0, rep_gk = 0, rep_g = 0; // replicas; the G K the tables and counters are sized for; the G the group sums are
     DevBuf<double> rc, rbeta, racum, rtables, ri2s, rbsq;
     DevBuf<int32_t> rcomp, rorder, rcass;
     DevBuf<uint8_t> rada;
-    DevBuf<uint32_t> rmts, rbounds;
-    DevBuf<SsResult> rres, rsums;
-    uint32_t rep_g = 0;
-    std::vector<int32_t> rgrouped;
-    std::vector<uint8_t> rada_host;
-    std::vector<SsResult> rres_host;
+    DevBuf<SsResult> rsums;
     std::vector<uint32_t> ahead_host;
     std::vector<uint8_t> cut;    // per marker: no window crosses the place before it
-    std::vector<int32_t> grouped;
-    std::vector<SsResult> sres_host;
     std::vector<uint8_t> ok;     // per marker: its standard deviation is finite
-    std::vector<uint8_t> ada_host;
     double band_ms = 0.0, sweep_ms = 0.0;
     // hgibbs_ss_post_* (hg_sspost.hip.h): the per-marker accumulators over post_T records of post_R replicas (0: the
     // handle's own chain) -- the pooled pair, the pairs of the [chains][2] half-chains, cnt [K][M], the error word, the table's four columns
@@ -449,54 +445,175 @@ extern "C" int hgibbs_ss_begin(hgibbs_t h, double n_eff, uint32_t W, const uint3
     return 0;
 }
 
+// ---- the sweep of a set of chains: what hgibbs_ss_sweep, _streams and _replicas do on the host ----
+constexpr uint32_t SS_RMAX = 64u;        // replicas of one handle
+constexpr uint32_t SS_SUMS_GMAX = 8192u; // groups whose sums fit the LDS of k_ss_replica_sums
+
 namespace {
 
-// What both sweeps check and upload, and the kernel's arguments but for the generator and the result
-int ss_sweep_prepare(hgibbs_ctx* h, SsState* s, const int32_t* order, double sigmaE, const double* sigmaG_host, const double* estPi_host,
-                     const uint8_t* adaV_host, SsSweepParams& p)
-{
-    const uint32_t M = h->M;
-    const int G = h->G, K = h->K;
-    std::vector<double> tab((size_t)4 * G * K);
-    ss_tables(G, K, s->n_eff - 1.0, sigmaE, sigmaG_host, estPi_host, h->cVa.data(), h->cVaI.data(), tab.data());
-    s->ada_host.resize(M);
-    for (uint32_t j = 0; j < M; ++j) s->ada_host[j] = (uint8_t)(adaV_host[j] && s->ok[j]); // a marker without a finite sd is never adaptive
-    HIP_TRY(hipMemcpyAsync(h->tables, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(s->order, order, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(s->ada, s->ada_host.data(), (size_t)M, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemsetAsync(h->cass, 0, (size_t)G * K * sizeof(int32_t), h->stream));
+// The per-chain device arrays of C chains on the one band: chain r's order, mask, c, effects, components and acum lie r M behind
+// chain 0's, its tables r 4 G K and its counters r G K (k_ss_sweep_replicas' strides; one chain has none).
+struct SsChains {
+    int32_t* order;
+    uint8_t* ada;
+    double *c, *beta;
+    int32_t* comp;
+    double *acum, *tables;
+    int32_t* cass;
+    uint32_t C;
+};
 
-    p.order = s->order;
+// the handle's own chain
+SsChains ss_own_chain(hgibbs_ctx* h, SsState* s) { return SsChains{s->order, s->ada, s->c, h->beta, h->comp, h->acum, h->tables, h->cass, 1u}; }
+
+// the replicas of hgibbs_ss_replicas
+SsChains ss_replica_chains(SsState* s) { return SsChains{s->rorder, s->rada, s->rc, s->rbeta, s->rcomp, s->racum, s->rtables, s->rcass, s->R}; }
+
+// the ss state of a handle that has replicas: null (with the error set) unless it has, and, where the caller names their number, R of them
+SsState* ss_replicas_of(hgibbs_ctx* h, const char* who, const uint32_t* R = nullptr)
+{
+    SsState* s = ss_of(h, who);
+    if (!s) return nullptr;
+    if (R && (*R < 1u || *R > SS_RMAX)) {
+        fail("%s: R = %u, must be in [1, %u]", who, *R, SS_RMAX);
+        return nullptr;
+    }
+    if (s->R == 0) {
+        fail("%s: no replicas on this handle (hgibbs_ss_replicas first)", who);
+        return nullptr;
+    }
+    if (R && *R != s->R) {
+        fail("%s: R = %u, but hgibbs_ss_replicas allocated %u replicas", who, *R, s->R);
+        return nullptr;
+    }
+    return s;
+}
+
+// What an entry point passes on, chain after chain where there are several: orders [C][M], sigmaE [C], sigmaG [C][G], estPi [C][G K],
+// adaV [C][M], rngs [C][S] (in and out), cass [C][G K] and nnz [C] (out; nnz may be null).
+struct SsSweepCall {
+    const char* who;
+    const char* tag;        // what a chain is called in a refusal ("replica"), null where there is only the one
+    bool intervals;         // S intervals at `bounds`, each with a generator; false: hgibbs_ss_sweep's one generator and an order taken as it comes
+    uint32_t S;
+    const uint32_t* bounds; // S + 1
+    const int32_t* orders;
+    const double *sigmaE, *sigmaG, *estPi;
+    const uint8_t* adaV;
+    hgibbs_rng_state* rngs;
+    int32_t* cass;
+    uint64_t* nnz;
+    uint32_t* mt; // where k_ss_sweep takes the one generator's 624 words (its index goes by value), or null: C S whole states in s->mts
+    double* i2s;  // where k_ss_sweep_replicas takes 1 / (2 sigmaE) of every chain, or null: the kernel takes it by value
+};
+
+// The checks on orders, bounds and generators, the uploads, `launch` (the entry point's kernel on its grid) inside the lap, and the
+// way back of the results, the generators and the counters.  A refused call has touched nothing on the device.
+template <class Launch>
+int ss_sweep_run(hgibbs_ctx* h, SsState* s, const SsChains& ch, const SsSweepCall& a, Launch launch)
+{
+    const char* who = a.who;
+    const uint32_t M = h->M, C = ch.C, S = a.S;
+    const int G = h->G, K = h->K;
+    const size_t GK = (size_t)G * K, CS = (size_t)C * S;
+    char why[256], pre[32] = "";
+    auto chain = [&](uint32_t r, const char* sep) -> const char* { // "replica r: " in a refusal of several chains
+        if (a.tag) snprintf(pre, sizeof pre, "%s %u%s", a.tag, r, sep);
+        return pre;
+    };
+    if (a.intervals) s->grouped.resize((size_t)C * M);
+    for (uint32_t r = 0; r < C; ++r) {
+        const int32_t* order = a.orders + (size_t)r * M;
+        hgibbs_rng_state* rngs = a.rngs + (size_t)r * S;
+        for (uint32_t i = 0; i < M; ++i)
+            if (order[i] < 0 || (uint32_t)order[i] >= M) return fail("%s: %sorder[%u]=%d outside [0,%u)", who, chain(r, ": "), i, order[i], M);
+        if (!a.intervals) { // no permutation check: an order with repeated markers is swept as it stands
+            if (rngs->idx > (uint32_t)MT_N) return fail("%s: rng idx %u > 624", who, rngs->idx);
+            continue;
+        }
+        if (!a.bounds) return fail("%s: null argument", who);
+        if (ss_streams_check(M, s->ahead_host.data(), s->cut.data(), S, a.bounds, rngs, why, sizeof why)) return fail("%s: %s%s", who, chain(r, ": "), why);
+        if (const uint32_t bad = ss_group_order(M, order, S, a.bounds, s->grouped.data() + (size_t)r * M))
+            return fail("%s: %sorder[%u] = %d repeats a marker: the order must be a permutation", who, chain(r, ": "), bad - 1u, order[bad - 1u]);
+    }
+    const int32_t* swept = a.intervals ? s->grouped.data() : a.orders; // the orders as the kernel walks them
+    HIP_TRY(hipSetDevice(h->device));
+    s->sweep_ms = 0.0;
+    if (CS > s->stage_cap) {
+        s->stage_cap = 0;
+        if (s->mts.alloc(CS * SS_RNG_WORDS) || s->sres.alloc(CS) || s->bounds.alloc(CS + 1)) return 1;
+        s->stage_cap = (uint32_t)CS;
+    }
+    uint32_t* const mt = a.mt ? a.mt : s->mts.p;
+    const size_t mt_bytes = a.mt ? MT_N * sizeof(uint32_t) : CS * sizeof(hgibbs_rng_state); // the states of all intervals in one copy
+
+    std::vector<double> tab((size_t)C * 4 * GK), i2s(C);
+    s->ada_host.resize((size_t)C * M);
+    for (uint32_t r = 0; r < C; ++r) {
+        ss_tables(G, K, s->n_eff - 1.0, a.sigmaE[r], a.sigmaG + (size_t)r * G, a.estPi + r * GK, h->cVa.data(), h->cVaI.data(), tab.data() + (size_t)r * 4 * GK);
+        i2s[r] = 1.0 / (2.0 * a.sigmaE[r]);
+        const uint8_t* adaV = a.adaV + (size_t)r * M;
+        uint8_t* ada = s->ada_host.data() + (size_t)r * M;
+        for (uint32_t j = 0; j < M; ++j) ada[j] = (uint8_t)(adaV[j] && s->ok[j]); // a marker without a finite sd is never adaptive
+    }
+    HIP_TRY(hipMemcpyAsync(ch.tables, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (a.i2s) HIP_TRY(hipMemcpyAsync(a.i2s, i2s.data(), (size_t)C * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(ch.order, swept, (size_t)C * M * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(ch.ada, s->ada_host.data(), (size_t)C * M, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemsetAsync(ch.cass, 0, (size_t)C * GK * sizeof(int32_t), h->stream));
+    HIP_TRY(hipMemcpyAsync(mt, a.rngs, mt_bytes, hipMemcpyHostToDevice, h->stream));
+    if (a.intervals) HIP_TRY(hipMemcpyAsync(s->bounds, a.bounds, ((size_t)S + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+
+    SsSweepParams p{};
+    p.order = ch.order;
     p.groups = h->groups;
-    p.ada = s->ada;
+    p.ada = ch.ada;
     p.ahead = s->ahead;
     p.back = s->back;
     p.band = s->band;
-    p.c = s->c;
-    p.beta = h->beta;
-    p.comp = h->comp;
-    p.acum = h->acum;
-    p.tables = h->tables;
+    p.c = ch.c;
+    p.beta = ch.beta;
+    p.comp = ch.comp;
+    p.acum = ch.acum;
+    p.tables = ch.tables;
+    p.mt = mt;
     p.zig = ZigTables{h->zig, h->zig + 129, h->zig + 258, h->zig + 515};
-    p.cass = h->cass;
+    p.cass = ch.cass;
+    p.res = s->sres;
     p.M = M;
     p.W = s->W;
+    p.rng_idx = a.rngs->idx;
     p.K = K;
     p.GK = G * K;
     p.dNm1 = s->n_eff - 1.0;
-    p.i_2sigE = 1.0 / (2.0 * sigmaE);
-    return 0;
-}
-
-// the checks of both sweeps on what the caller passes
-int ss_sweep_check(hgibbs_ctx* h, const char* who, const int32_t* order_host, const double* sigmaG_host, const double* estPi_host,
-                   const uint8_t* adaV_host, const void* rng, const int32_t* cass_host)
-{
-    if (h->G < 1) return fail("%s: model not set", who);
-    if (!order_host || !sigmaG_host || !estPi_host || !adaV_host || !rng || !cass_host) return fail("%s: null argument", who);
-    const uint32_t M = h->M;
-    for (uint32_t i = 0; i < M; ++i)
-        if (order_host[i] < 0 || (uint32_t)order_host[i] >= M) return fail("%s: order[%u]=%d outside [0,%u)", who, i, order_host[i], M);
+    p.i_2sigE = i2s[0];
+    if (a.intervals) p.bounds = s->bounds;
+    double ms = 0.0;
+    if (lap_begin(h)) return 1;
+    launch(p);
+    HIP_TRY(hipGetLastError());
+    if (lap_end(h, ms)) return 1;
+    s->sres_host.resize(CS);
+    HIP_TRY(hipMemcpy(s->sres_host.data(), s->sres, CS * sizeof(SsResult), hipMemcpyDeviceToHost));
+    for (uint32_t r = 0; r < C; ++r) {
+        uint64_t nnz = 0;
+        for (uint32_t i = 0; i < S; ++i) {
+            const SsResult& res = s->sres_host[(size_t)r * S + i];
+            if (res.err) {
+                const uint32_t pos = res.err - 1u;
+                const int32_t marker = swept[(size_t)r * M + pos];
+                if (!a.intervals) return fail("%s: sweep position %u (marker %d): the component walk found no component (logL overflow)", who, pos, marker);
+                return fail("%s: %sstream %u, sweep position %u of its %u (marker %d): the component walk found no component (logL overflow)", who, chain(r, ", "), i,
+                            pos - a.bounds[i], a.bounds[i + 1] - a.bounds[i], marker);
+            }
+            nnz += res.nnz;
+        }
+        if (a.nnz) a.nnz[r] = nnz;
+    }
+    HIP_TRY(hipMemcpy(a.rngs, mt, mt_bytes, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < CS; ++i) a.rngs[i].idx = s->sres_host[i].rng_idx;
+    HIP_TRY(hipMemcpy(a.cass, ch.cass, (size_t)C * GK * sizeof(int32_t), hipMemcpyDeviceToHost));
+    s->sweep_ms = ms;
     return 0;
 }
 
@@ -508,31 +625,10 @@ extern "C" int hgibbs_ss_sweep(hgibbs_t h, const int32_t* order_host, double sig
     const char* who = "hgibbs_ss_sweep";
     SsState* s = ss_of(h, who);
     if (!s) return 1;
-    if (ss_sweep_check(h, who, order_host, sigmaG_host, estPi_host, adaV_host, rng, cass_host)) return 1;
-    if (rng->idx > (uint32_t)MT_N) return fail("%s: rng idx %u > 624", who, rng->idx);
-    HIP_TRY(hipSetDevice(h->device));
-    s->sweep_ms = 0.0;
-
-    SsSweepParams p{};
-    if (ss_sweep_prepare(h, s, order_host, sigmaE, sigmaG_host, estPi_host, adaV_host, p)) return 1;
-    HIP_TRY(hipMemcpyAsync(h->mt, rng->x, MT_N * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    p.mt = h->mt;
-    p.res = s->res;
-    p.rng_idx = rng->idx;
-    double ms = 0.0;
-    if (lap_begin(h)) return 1;
-    k_ss_sweep<<<1, SS_TPB, 0, h->stream>>>(p);
-    HIP_TRY(hipGetLastError());
-    if (lap_end(h, ms)) return 1;
-    SsResult res{};
-    HIP_TRY(hipMemcpy(&res, s->res, sizeof res, hipMemcpyDeviceToHost));
-    if (res.err) return fail("%s: sweep position %u (marker %d): the component walk found no component (logL overflow)", who, res.err - 1u, order_host[res.err - 1u]);
-    HIP_TRY(hipMemcpy(rng->x, h->mt, MT_N * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(cass_host, h->cass, (size_t)h->G * h->K * sizeof(int32_t), hipMemcpyDeviceToHost));
-    rng->idx = res.rng_idx;
-    if (nnz_updates) *nnz_updates = res.nnz;
-    s->sweep_ms = ms;
-    return 0;
+    if (h->G < 1) return fail("%s: model not set", who);
+    if (!order_host || !sigmaG_host || !estPi_host || !adaV_host || !rng || !cass_host) return fail("%s: null argument", who);
+    const SsSweepCall a{who, nullptr, false, 1u, nullptr, order_host, &sigmaE, sigmaG_host, estPi_host, adaV_host, rng, cass_host, nnz_updates, h->mt, nullptr};
+    return ss_sweep_run(h, s, ss_own_chain(h, s), a, [&](const SsSweepParams& p) { k_ss_sweep<<<1, SS_TPB, 0, h->stream>>>(p); });
 }
 
 extern "C" int hgibbs_ss_sweep_streams(hgibbs_t h, const int32_t* order_host, double sigmaE, const double* sigmaG_host, const double* estPi_host,
@@ -542,80 +638,14 @@ extern "C" int hgibbs_ss_sweep_streams(hgibbs_t h, const int32_t* order_host, do
     const char* who = "hgibbs_ss_sweep_streams";
     SsState* s = ss_of(h, who);
     if (!s) return 1;
-    if (ss_sweep_check(h, who, order_host, sigmaG_host, estPi_host, adaV_host, rngs, cass_host)) return 1;
-    if (!bounds) return fail("%s: null argument", who);
-    const uint32_t M = h->M;
-    char why[256];
-    if (ss_streams_check(M, s->ahead_host.data(), s->cut.data(), S, bounds, rngs, why, sizeof why)) return fail("%s: %s", who, why);
-    s->grouped.resize(M);
-    if (const uint32_t bad = ss_group_order(M, order_host, S, bounds, s->grouped.data()))
-        return fail("%s: order[%u] = %d repeats a marker: the order must be a permutation", who, bad - 1u, order_host[bad - 1u]);
-    HIP_TRY(hipSetDevice(h->device));
-    s->sweep_ms = 0.0;
-    if (S > s->streams_cap) {
-        s->streams_cap = 0;
-        if (s->mts.alloc((size_t)S * SS_RNG_WORDS) || s->sres.alloc(S) || s->bounds.alloc((size_t)S + 1)) return 1;
-        s->streams_cap = S;
-    }
-
-    SsSweepParams p{};
-    if (ss_sweep_prepare(h, s, s->grouped.data(), sigmaE, sigmaG_host, estPi_host, adaV_host, p)) return 1;
-    HIP_TRY(hipMemcpyAsync(s->mts, rngs, (size_t)S * sizeof(hgibbs_rng_state), hipMemcpyHostToDevice, h->stream)); // the S states in one copy
-    HIP_TRY(hipMemcpyAsync(s->bounds, bounds, ((size_t)S + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    p.mt = s->mts;
-    p.bounds = s->bounds;
-    p.res = s->sres;
-    double ms = 0.0;
-    if (lap_begin(h)) return 1;
-    k_ss_sweep_streams<<<S, SS_TPB, 0, h->stream>>>(p);
-    HIP_TRY(hipGetLastError());
-    if (lap_end(h, ms)) return 1;
-    s->sres_host.resize(S);
-    HIP_TRY(hipMemcpy(s->sres_host.data(), s->sres, (size_t)S * sizeof(SsResult), hipMemcpyDeviceToHost));
-    uint64_t nnz = 0;
-    for (uint32_t i = 0; i < S; ++i) {
-        const SsResult& r = s->sres_host[i];
-        if (r.err)
-            return fail("%s: stream %u, sweep position %u of its %u (marker %d): the component walk found no component (logL overflow)", who, i,
-                        r.err - 1u - bounds[i], bounds[i + 1] - bounds[i], s->grouped[r.err - 1u]);
-        nnz += r.nnz;
-    }
-    HIP_TRY(hipMemcpy(rngs, s->mts, (size_t)S * sizeof(hgibbs_rng_state), hipMemcpyDeviceToHost));
-    for (uint32_t i = 0; i < S; ++i) rngs[i].idx = s->sres_host[i].rng_idx;
-    HIP_TRY(hipMemcpy(cass_host, h->cass, (size_t)h->G * h->K * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (nnz_updates) *nnz_updates = nnz;
-    s->sweep_ms = ms;
-    return 0;
+    if (h->G < 1) return fail("%s: model not set", who);
+    if (!order_host || !sigmaG_host || !estPi_host || !adaV_host || !rngs || !cass_host) return fail("%s: null argument", who);
+    // (null bounds are refused behind the order's range, as they always were)
+    const SsSweepCall a{who, nullptr, true, S, bounds, order_host, &sigmaE, sigmaG_host, estPi_host, adaV_host, rngs, cass_host, nnz_updates, nullptr, nullptr};
+    return ss_sweep_run(h, s, ss_own_chain(h, s), a, [&](const SsSweepParams& p) { k_ss_sweep_streams<<<S, SS_TPB, 0, h->stream>>>(p); });
 }
 
 // ---- R chains on one band ----
-constexpr uint32_t SS_RMAX = 64u;      // replicas of one handle
-constexpr uint32_t SS_SUMS_GMAX = 8192u; // groups whose sums fit the LDS of k_ss_replica_sums
-
-namespace {
-
-// the replicas of a handle as the caller names them: null (with the error set) unless R of them are allocated
-SsState* ss_replicas_of(hgibbs_ctx* h, const char* who, uint32_t R)
-{
-    SsState* s = ss_of(h, who);
-    if (!s) return nullptr;
-    if (R < 1u || R > SS_RMAX) {
-        fail("%s: R = %u, must be in [1, %u]", who, R, SS_RMAX);
-        return nullptr;
-    }
-    if (s->R == 0) {
-        fail("%s: no replicas on this handle (hgibbs_ss_replicas first)", who);
-        return nullptr;
-    }
-    if (R != s->R) {
-        fail("%s: R = %u, but hgibbs_ss_replicas allocated %u replicas", who, R, s->R);
-        return nullptr;
-    }
-    return s;
-}
-
-} // namespace
-
 extern "C" int hgibbs_ss_replicas(hgibbs_t h, uint32_t R)
 {
     const char* who = "hgibbs_ss_replicas";
@@ -644,7 +674,7 @@ extern "C" int hgibbs_ss_replicas(hgibbs_t h, uint32_t R)
     HIP_TRY(hipMemsetAsync(s->rcomp, 0, n * sizeof(int32_t), h->stream));
     HIP_TRY(hipMemsetAsync(s->rsums, 0, R * sizeof(SsResult), h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    s->rep_gk = s->rep_rs = s->rep_g = 0; // (sized at the first sweep and the first sums: the model may be set after this call)
+    s->rep_gk = s->rep_g = 0; // (sized at the first sweep and the first sums: the model may be set after this call)
     s->R = R;
     return 0;
 }
@@ -654,109 +684,29 @@ extern "C" int hgibbs_ss_sweep_replicas(hgibbs_t h, uint32_t R, const int32_t* o
                                         uint64_t* nnz_updates)
 {
     const char* who = "hgibbs_ss_sweep_replicas";
-    SsState* s = ss_replicas_of(h, who, R);
+    SsState* s = ss_replicas_of(h, who, &R);
     if (!s) return 1;
     if (h->G < 1) return fail("%s: model not set", who);
     if (!orders || !sigmaE || !sigmaG || !estPi || !adaV || !rngs || !cass_host) return fail("%s: null argument", who);
     if (!bounds && S != 1u) return fail("%s: null argument", who);
-    const uint32_t M = h->M;
-    const int G = h->G, K = h->K;
-    const size_t GK = (size_t)G * K;
-    const uint32_t whole[2] = {0u, M};
-    if (!bounds) bounds = whole;
-    s->rgrouped.resize((size_t)R * M);
-    char why[256];
-    for (uint32_t r = 0; r < R; ++r) {
-        const int32_t* order = orders + (size_t)r * M;
-        for (uint32_t i = 0; i < M; ++i)
-            if (order[i] < 0 || (uint32_t)order[i] >= M) return fail("%s: replica %u: order[%u]=%d outside [0,%u)", who, r, i, order[i], M);
-        if (ss_streams_check(M, s->ahead_host.data(), s->cut.data(), S, bounds, rngs + (size_t)r * S, why, sizeof why)) return fail("%s: replica %u: %s", who, r, why);
-        if (const uint32_t bad = ss_group_order(M, order, S, bounds, s->rgrouped.data() + (size_t)r * M))
-            return fail("%s: replica %u: order[%u] = %d repeats a marker: the order must be a permutation", who, r, bad - 1u, order[bad - 1u]);
-    }
-    HIP_TRY(hipSetDevice(h->device));
-    s->sweep_ms = 0.0;
-    const size_t RS = (size_t)R * S;
-    if (GK != s->rep_gk) {
+    const uint32_t whole[2] = {0u, h->M};
+    const size_t GK = (size_t)h->G * h->K;
+    if (GK != s->rep_gk) { // the replicas' tables and counters follow the model
+        HIP_TRY(hipSetDevice(h->device));
         s->rep_gk = 0;
         if (s->rtables.alloc((size_t)R * 4 * GK) || s->rcass.alloc((size_t)R * GK)) return 1;
         s->rep_gk = (uint32_t)GK;
     }
-    if (RS > s->rep_rs) {
-        s->rep_rs = 0;
-        if (s->rmts.alloc(RS * SS_RNG_WORDS) || s->rres.alloc(RS) || s->rbounds.alloc((size_t)SS_SMAX + 1)) return 1;
-        s->rep_rs = (uint32_t)RS;
-    }
-
-    std::vector<double> tab((size_t)R * 4 * GK), i2s(R);
-    s->rada_host.resize((size_t)R * M);
-    for (uint32_t r = 0; r < R; ++r) {
-        ss_tables(G, K, s->n_eff - 1.0, sigmaE[r], sigmaG + (size_t)r * G, estPi + r * GK, h->cVa.data(), h->cVaI.data(), tab.data() + (size_t)r * 4 * GK);
-        i2s[r] = 1.0 / (2.0 * sigmaE[r]);
-        for (uint32_t j = 0; j < M; ++j) s->rada_host[(size_t)r * M + j] = (uint8_t)(adaV[(size_t)r * M + j] && s->ok[j]);
-    }
-    HIP_TRY(hipMemcpyAsync(s->rtables, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(s->ri2s, i2s.data(), (size_t)R * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(s->rorder, s->rgrouped.data(), (size_t)R * M * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(s->rada, s->rada_host.data(), (size_t)R * M, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemsetAsync(s->rcass, 0, (size_t)R * GK * sizeof(int32_t), h->stream));
-    HIP_TRY(hipMemcpyAsync(s->rmts, rngs, RS * sizeof(hgibbs_rng_state), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(s->rbounds, bounds, ((size_t)S + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-
-    SsSweepParams p{};
-    p.order = s->rorder;
-    p.groups = h->groups;
-    p.ada = s->rada;
-    p.ahead = s->ahead;
-    p.back = s->back;
-    p.band = s->band;
-    p.c = s->rc;
-    p.beta = s->rbeta;
-    p.comp = s->rcomp;
-    p.acum = s->racum;
-    p.tables = s->rtables;
-    p.mt = s->rmts;
-    p.zig = ZigTables{h->zig, h->zig + 129, h->zig + 258, h->zig + 515};
-    p.cass = s->rcass;
-    p.res = s->rres;
-    p.M = M;
-    p.W = s->W;
-    p.K = K;
-    p.GK = G * K;
-    p.dNm1 = s->n_eff - 1.0;
-    p.bounds = s->rbounds;
+    const SsSweepCall a{who, "replica", true, S, bounds ? bounds : whole, orders, sigmaE, sigmaG, estPi, adaV, rngs, cass_host, nnz_updates, nullptr, s->ri2s};
     const SsReplicaParams q{s->ri2s};
-    double ms = 0.0;
-    if (lap_begin(h)) return 1;
-    k_ss_sweep_replicas<<<dim3(S, R), SS_TPB, 0, h->stream>>>(p, q);
-    HIP_TRY(hipGetLastError());
-    if (lap_end(h, ms)) return 1;
-    s->rres_host.resize(RS);
-    HIP_TRY(hipMemcpy(s->rres_host.data(), s->rres, RS * sizeof(SsResult), hipMemcpyDeviceToHost));
-    for (uint32_t r = 0; r < R; ++r) {
-        uint64_t nnz = 0;
-        for (uint32_t i = 0; i < S; ++i) {
-            const SsResult& res = s->rres_host[(size_t)r * S + i];
-            if (res.err)
-                return fail("%s: replica %u, stream %u, sweep position %u of its %u (marker %d): the component walk found no component (logL overflow)", who, r, i,
-                            res.err - 1u - bounds[i], bounds[i + 1] - bounds[i], s->rgrouped[(size_t)r * M + res.err - 1u]);
-            nnz += res.nnz;
-        }
-        if (nnz_updates) nnz_updates[r] = nnz;
-    }
-    HIP_TRY(hipMemcpy(rngs, s->rmts, RS * sizeof(hgibbs_rng_state), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < RS; ++i) rngs[i].idx = s->rres_host[i].rng_idx;
-    HIP_TRY(hipMemcpy(cass_host, s->rcass, (size_t)R * GK * sizeof(int32_t), hipMemcpyDeviceToHost));
-    s->sweep_ms = ms;
-    return 0;
+    return ss_sweep_run(h, s, ss_replica_chains(s), a, [&](const SsSweepParams& p) { k_ss_sweep_replicas<<<dim3(S, R), SS_TPB, 0, h->stream>>>(p, q); });
 }
 
 extern "C" int hgibbs_ss_replica_sums(hgibbs_t h, double* sb, double* sc, double* bsq)
 {
     const char* who = "hgibbs_ss_replica_sums";
-    SsState* s = ss_of(h, who);
+    SsState* s = ss_replicas_of(h, who);
     if (!s) return 1;
-    if (s->R == 0) return fail("%s: no replicas on this handle (hgibbs_ss_replicas first)", who);
     if (h->G < 1) return fail("%s: model not set", who);
     const uint32_t R = s->R, G = (uint32_t)h->G;
     if (G > SS_SUMS_GMAX) return fail("%s: G = %u groups, the sums are built for at most %u", who, G, SS_SUMS_GMAX);
@@ -779,44 +729,29 @@ extern "C" int hgibbs_ss_replica_sums(hgibbs_t h, double* sb, double* sc, double
     return 0;
 }
 
-namespace {
-
-SsState* ss_replica_at(hgibbs_ctx* h, const char* who, uint32_t r)
-{
-    SsState* s = ss_of(h, who);
-    if (!s) return nullptr;
-    if (s->R == 0) {
-        fail("%s: no replicas on this handle (hgibbs_ss_replicas first)", who);
-        return nullptr;
-    }
-    if (r >= s->R) {
-        fail("%s: replica %u outside [0, %u)", who, r, s->R);
-        return nullptr;
-    }
-    return s;
-}
-
-} // namespace
-
 extern "C" int hgibbs_ss_replica_get(hgibbs_t h, uint32_t r, double* beta, int32_t* comp, double* acum, double* c)
 {
-    SsState* s = ss_replica_at(h, "hgibbs_ss_replica_get", r);
+    const char* who = "hgibbs_ss_replica_get";
+    SsState* s = ss_replicas_of(h, who);
     if (!s) return 1;
+    if (r >= s->R) return fail("%s: replica %u outside [0, %u)", who, r, s->R);
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
+    const SsChains ch = ss_replica_chains(s);
     const size_t M = h->M, o = (size_t)r * M;
-    if (beta) HIP_TRY(hipMemcpy(beta, s->rbeta + o, M * sizeof(double), hipMemcpyDeviceToHost));
-    if (comp) HIP_TRY(hipMemcpy(comp, s->rcomp + o, M * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (acum) HIP_TRY(hipMemcpy(acum, s->racum + o, M * sizeof(double), hipMemcpyDeviceToHost));
-    if (c) HIP_TRY(hipMemcpy(c, s->rc + o, M * sizeof(double), hipMemcpyDeviceToHost));
+    if (beta) HIP_TRY(hipMemcpy(beta, ch.beta + o, M * sizeof(double), hipMemcpyDeviceToHost));
+    if (comp) HIP_TRY(hipMemcpy(comp, ch.comp + o, M * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (acum) HIP_TRY(hipMemcpy(acum, ch.acum + o, M * sizeof(double), hipMemcpyDeviceToHost));
+    if (c) HIP_TRY(hipMemcpy(c, ch.c + o, M * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 
 extern "C" int hgibbs_ss_replica_set_beta(hgibbs_t h, uint32_t r, const double* beta)
 {
     const char* who = "hgibbs_ss_replica_set_beta";
-    SsState* s = ss_replica_at(h, who, r);
+    SsState* s = ss_replicas_of(h, who);
     if (!s) return 1;
+    if (r >= s->R) return fail("%s: replica %u outside [0, %u)", who, r, s->R);
     if (!beta) return fail("%s: null argument", who);
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));

@@ -3989,106 +3989,41 @@ std::string post_report(const PostJob& p)
     return b;
 }
 
-// --sumstats-chains: R chains on the band of `dev`, from the model `md` with the seeds md.seed + r.  Chain 0's
-// files are <base>.*, chain r's <base>.c<r>.*; <base>.rhat holds the convergence table over the thinned records at or after
-// --burn-in.  Returns what the closing line reports: streams, largest interval, sweeps, device ms of all launches, largest R^.
-struct ChainsReport {
-    uint32_t streams = 0, largest = 0, chains = 0;
-    unsigned sweeps = 0;
-    double sweep_total_ms = 0.0, band_ms = 0.0, max_rhat = std::numeric_limits<double>::quiet_NaN();
+// The chains of --sumstats as the driver's loop sees them: the R of a hydra_ss_multi (--sumstats-chains), or
+// the one hydra_ss_chain as R = 1.
+struct SsChainSet {
+    hydra_ss_chain_t one = nullptr;
+    hydra_ss_multi_t many = nullptr;
+    uint32_t R = 1;
+    void iterate() const { one ? hg_check(hydra_ss_chain_iterate(one), "hydra_ss_chain_iterate") : hg_check(hydra_ss_multi_iterate(many), "hydra_ss_multi_iterate"); }
+    void state(uint32_t r, double* sigmaE, double* mu, double* sigmaG, int32_t* m0) const
+    {
+        one ? hg_check(hydra_ss_chain_state(one, sigmaE, mu, sigmaG, nullptr, m0, nullptr, nullptr), "hydra_ss_chain_state")
+            : hg_check(hydra_ss_multi_state(many, r, sigmaE, mu, sigmaG, nullptr, m0, nullptr, nullptr), "hydra_ss_multi_state");
+    }
+    void effects(uint32_t r, double* beta, int32_t* comp, double* acum) const
+    {
+        one ? hg_check(hydra_ss_chain_effects(one, beta, comp, acum, nullptr), "hydra_ss_chain_effects")
+            : hg_check(hydra_ss_multi_effects(many, r, beta, comp, acum, nullptr), "hydra_ss_multi_effects");
+    }
+    int csv_line(uint32_t r, unsigned iteration, char* buf, size_t len) const
+    {
+        return one ? hydra_ss_chain_csv_line(one, iteration, buf, len) : hydra_ss_multi_csv_line(many, r, iteration, buf, len);
+    }
+    void streams(uint32_t* S, uint32_t* bounds) const
+    {
+        one ? hg_check(hydra_ss_chain_streams(one, S, bounds, nullptr), "hydra_ss_chain_streams") : hg_check(hydra_ss_multi_streams(many, S, bounds, nullptr), "hydra_ss_multi_streams");
+    }
+    void destroy() const { one ? (void)hydra_ss_chain_destroy(one) : (void)hydra_ss_multi_destroy(many); }
 };
 
-ChainsReport run_sumstats_chains(const Options& opt, hgibbs_t dev, const hydra_model_desc& md, const SumstatTable& tab, const LdWindow& win, uint32_t W,
-                                 unsigned M, int G, const std::string& base, PostJob& post)
+// <base>.rhat: the convergence table over the thinned records at or after --burn-in, rec[r P + p] holding parameter p of chain r
+// (sigmaG[g] per group, their sum, sigmaE, h2 as the .csv's ratio, m0, mu).  Returns the largest R^.
+double write_rhat(const Options& opt, const std::string& rhatp, const std::vector<std::vector<double>>& rec, long R, int G)
 {
-    ChainsReport rep;
-    long R = 1, smax = 0;
-    whole_int(opt.sumstatsChains, R);
-    if (opt.sumstatsStreamsGiven) whole_int(opt.sumstatsStreams, smax);
-    rep.chains = (uint32_t)R;
-    std::vector<uint32_t> seeds(R);
-    for (long r = 0; r < R; ++r) seeds[r] = md.seed + (uint32_t)r; // hydra's rule for ranks
-    hydra_ss_multi_t chains = nullptr;
-    hg_check(hydra_ss_multi_create(dev, &md, (uint32_t)R, seeds.data(), tab.n_eff, W, win.ahead.data(), tab.xty.data(), tab.use.data(), (uint32_t)smax, &chains),
-             "hydra_ss_multi_create");
-    hg_check(hydra_ss_multi_streams(chains, &rep.streams, nullptr, nullptr), "hydra_ss_multi_streams");
-    if (rep.streams) {
-        std::vector<uint32_t> bounds((size_t)rep.streams + 1u);
-        hg_check(hydra_ss_multi_streams(chains, nullptr, bounds.data(), nullptr), "hydra_ss_multi_streams");
-        for (uint32_t s = 0; s < rep.streams; ++s) rep.largest = std::max(rep.largest, bounds[s + 1] - bounds[s]);
-    }
-    if (post.on) hg_check(hgibbs_ss_post_begin(dev, (uint32_t)R, post.T), "hgibbs_ss_post_begin");
-    const bool effects = !(post.on && post.only); // --sumstats-post-only: no .bet, .cpn, .acu, and no download of a record
-
-    OutFiles outs;
-    std::vector<FILE*> outf(R), betf(R), cpnf(R), acuf(R);
-    for (long r = 0; r < R; ++r) {
-        const std::string b = r ? base + ".c" + std::to_string(r) : base;
-        outf[r] = outs.open(b + ".csv");
-        if (!effects) continue;
-        betf[r] = outs.open(b + ".bet");
-        cpnf[r] = outs.open(b + ".cpn");
-        acuf[r] = outs.open(b + ".acu");
-        for (FILE* f : {betf[r], cpnf[r], acuf[r]}) pwrite_at(f, 0, &M, sizeof(unsigned));
-    }
-    // the table's parameters: sigmaG[g] per group, their sum, sigmaE, h2 (the .csv's ratio), m0, mu; per chain its records in order
     const int P = G + 5;
-    std::vector<std::vector<double>> rec((size_t)P * R);
-    std::vector<double> beta(M), acum(M), sigmaG(G);
-    std::vector<int32_t> comp(M), m0(G);
-    std::vector<char> buff(50000);
-    unsigned n_thinned_saved = 0;
-    double sweep_ms = 0.0;
-    for (unsigned iteration = 0; iteration < opt.chainLength; ++iteration) {
-        const double t0 = now_s();
-        hg_check(hydra_ss_multi_iterate(chains), "hydra_ss_multi_iterate");
-        const double t1 = now_s();
-        hg_check(hgibbs_last_ss_ms(dev, &rep.band_ms, &sweep_ms), "hgibbs_last_ss_ms");
-        rep.sweep_total_ms += sweep_ms;
-        ++rep.sweeps;
-        if (post.on && post_counts(opt, iteration)) hg_check(hgibbs_ss_post_add(dev), "hgibbs_ss_post_add");
-        for (long r = 0; r < R; ++r) {
-            double sigmaE = 0, mu = 0;
-            hg_check(hydra_ss_multi_state(chains, (uint32_t)r, &sigmaE, &mu, sigmaG.data(), nullptr, m0.data(), nullptr, nullptr), "hydra_ss_multi_state");
-            double sg = 0;
-            long m0s = 0;
-            for (int g = 0; g < G; ++g) {
-                sg += sigmaG[g];
-                m0s += m0[g];
-            }
-            std::printf("RESULT : chain %2ld it %4d: proc = %9.3f s (all chains), sweep = %9.3f ms on the device (all chains), sigmaG = %15.10f, sigmaE = %15.10f, "
-                        "mu = %15.10f, m0 = %10ld\n",
-                        r, iteration, t1 - t0, sweep_ms, sg, sigmaE, mu, m0s);
-            if (iteration % opt.thin == 0) {
-                if (effects) hg_check(hydra_ss_multi_effects(chains, (uint32_t)r, beta.data(), comp.data(), acum.data(), nullptr), "hydra_ss_multi_effects");
-                const int len = hydra_ss_multi_csv_line(chains, (uint32_t)r, iteration, buff.data(), buff.size());
-                write_line(outf[r], n_thinned_saved, buff.data(), len);
-                if (effects) {
-                    write_thinned(betf[r], n_thinned_saved, iteration, beta.data(), M, sizeof(double));
-                    write_thinned(acuf[r], n_thinned_saved, iteration, acum.data(), M, sizeof(double));
-                    write_thinned(cpnf[r], n_thinned_saved, iteration, comp.data(), M, sizeof(int));
-                }
-                if (iteration >= opt.burnin) {
-                    std::vector<double>* row = &rec[(size_t)r * P];
-                    for (int g = 0; g < G; ++g) row[g].push_back(sigmaG[g]);
-                    row[G].push_back(sg);
-                    row[G + 1].push_back(sigmaE);
-                    row[G + 2].push_back(sg / (sigmaE + sg));
-                    row[G + 3].push_back((double)m0s);
-                    row[G + 4].push_back(mu);
-                }
-            }
-        }
-        std::fflush(stdout);
-        if (iteration % opt.thin == 0) n_thinned_saved += 1;
-    }
-    outs.close(true);
-    if (post.on) write_post_table(post, dev, (unsigned)R, M);
-    hydra_ss_multi_destroy(chains);
-
-    // <base>.rhat
+    double max_rhat = std::numeric_limits<double>::quiet_NaN();
     const unsigned T = (unsigned)rec[0].size();
-    const std::string rhatp = base + ".rhat";
     FILE* rf = open_out(rhatp, "wb+");
     std::fprintf(rf, "PARAM\tNCHAINS\tNREC\tMEAN\tSD\tRHAT\tESS\n");
     if (T < 4)
@@ -4107,13 +4042,133 @@ ChainsReport run_sumstats_chains(const Options& opt, hgibbs_t dev, const hydra_m
         if (T >= 4) {
             for (long r = 0; r < R; ++r) std::copy(rec[(size_t)r * P + p].begin(), rec[(size_t)r * P + p].end(), x.begin() + (size_t)r * T);
             hg_check(hgibbs_mcmc_diag((uint32_t)R, T, x.data(), &mean, &sd, &rhat, &ess), "hgibbs_mcmc_diag");
-            if (!std::isnan(rhat) && !(rhat <= rep.max_rhat)) rep.max_rhat = rhat;
+            if (!std::isnan(rhat) && !(rhat <= max_rhat)) max_rhat = rhat;
         }
         std::string name = p < G ? "sigmaG[" + std::to_string(p) + "]" : std::string(p == G ? "sigmaG" : p == G + 1 ? "sigmaE" : p == G + 2 ? "h2" : p == G + 3 ? "m0" : "mu");
         std::fprintf(rf, "%s\t%ld\t%u\t%s\t%s\t%s\t%s\n", name.c_str(), R, T, num(mean).c_str(), num(sd).c_str(), num(rhat).c_str(), num(ess).c_str());
     }
     close_out(rf, rhatp);
-    return rep;
+    return max_rhat;
+}
+
+// --sumstats from its chain(s) down, on the band of `dev`.  --sumstats-chains R: R chains from the model `md` with the seeds
+// md.seed + r in one launch per iteration, chain 0's files <base>.*, chain r's <base>.c<r>.*, and <base>.rhat; without it the one
+// chain of md.seed and the single chain's wording of the RESULT and the closing lines.
+void run_sumstats_chains(const Options& opt, hgibbs_t dev, const hydra_model_desc& md, const SumstatTable& tab, const LdWindow& win, uint32_t W, unsigned M, int G,
+                         const std::string& base, PostJob& post, unsigned used, unsigned nosd)
+{
+    const bool many = opt.sumstatsChainsGiven;
+    long R = 1, smax = 0;
+    if (many) whole_int(opt.sumstatsChains, R);
+    if (opt.sumstatsStreamsGiven) whole_int(opt.sumstatsStreams, smax);
+    SsChainSet cs;
+    cs.R = (uint32_t)R;
+    if (many) {
+        std::vector<uint32_t> seeds(R);
+        for (long r = 0; r < R; ++r) seeds[r] = md.seed + (uint32_t)r; // hydra's rule for ranks
+        hg_check(hydra_ss_multi_create(dev, &md, cs.R, seeds.data(), tab.n_eff, W, win.ahead.data(), tab.xty.data(), tab.use.data(), (uint32_t)smax, &cs.many),
+                 "hydra_ss_multi_create");
+    } else {
+        hg_check(hydra_ss_chain_create(dev, &md, tab.n_eff, W, win.ahead.data(), tab.xty.data(), tab.use.data(), &cs.one), "hydra_ss_chain_create");
+        if (smax) hg_check(hydra_ss_chain_set_streams(cs.one, (uint32_t)smax), "hydra_ss_chain_set_streams");
+    }
+    // independent LD blocks in parallel streams: the intervals come from the window, so they are known before the first sweep
+    uint32_t streams = 0, largest = 0;
+    cs.streams(&streams, nullptr);
+    if (streams) {
+        std::vector<uint32_t> bounds((size_t)streams + 1u);
+        cs.streams(nullptr, bounds.data());
+        for (uint32_t s = 0; s < streams; ++s) largest = std::max(largest, bounds[s + 1] - bounds[s]);
+    }
+    double band_ms = 0.0, sweep_ms = 0.0;
+    hg_check(hgibbs_last_ss_ms(dev, &band_ms, &sweep_ms), "hgibbs_last_ss_ms");
+    if (post.on) hg_check(hgibbs_ss_post_begin(dev, many ? cs.R : 0u, post.T), "hgibbs_ss_post_begin"); // (0: the handle's own chain)
+    const bool effects = !(post.on && post.only); // --sumstats-post-only: no .bet, .cpn, .acu, and no download of a record
+
+    // the chains' files and formats (:1302-1309, :2736-2794)
+    OutFiles outs;
+    std::vector<FILE*> outf(R), betf(R), cpnf(R), acuf(R);
+    for (long r = 0; r < R; ++r) {
+        const std::string b = r ? base + ".c" + std::to_string(r) : base;
+        outf[r] = outs.open(b + ".csv");
+        if (!effects) continue;
+        betf[r] = outs.open(b + ".bet");
+        cpnf[r] = outs.open(b + ".cpn");
+        acuf[r] = outs.open(b + ".acu");
+        for (FILE* f : {betf[r], cpnf[r], acuf[r]}) pwrite_at(f, 0, &M, sizeof(unsigned));
+    }
+    const int P = G + 5; // the .rhat table's parameters; per chain its records in order
+    std::vector<std::vector<double>> rec(many ? (size_t)P * R : 0);
+    std::vector<double> beta(M), acum(M), sigmaG(G);
+    std::vector<int32_t> comp(M), m0(G);
+    std::vector<char> buff(50000);
+    unsigned n_thinned_saved = 0, sweeps = 0;
+    double sweep_total_ms = 0.0;
+    for (unsigned iteration = 0; iteration < opt.chainLength; ++iteration) {
+        const double t0 = now_s();
+        cs.iterate();
+        const double t1 = now_s();
+        hg_check(hgibbs_last_ss_ms(dev, &band_ms, &sweep_ms), "hgibbs_last_ss_ms");
+        sweep_total_ms += sweep_ms;
+        ++sweeps;
+        if (post.on && post_counts(opt, iteration)) hg_check(hgibbs_ss_post_add(dev), "hgibbs_ss_post_add");
+        for (long r = 0; r < R; ++r) {
+            double sigmaE = 0, mu = 0;
+            cs.state((uint32_t)r, &sigmaE, &mu, sigmaG.data(), m0.data());
+            double sg = 0;
+            long m0s = 0;
+            for (int g = 0; g < G; ++g) {
+                sg += sigmaG[g];
+                m0s += m0[g];
+            }
+            if (many)
+                std::printf("RESULT : chain %2ld it %4d: proc = %9.3f s (all chains), sweep = %9.3f ms on the device (all chains), sigmaG = %15.10f, sigmaE = %15.10f, "
+                            "mu = %15.10f, m0 = %10ld\n",
+                            r, iteration, t1 - t0, sweep_ms, sg, sigmaE, mu, m0s);
+            else
+                std::printf("RESULT : it %4d: proc = %9.3f s, sweep = %9.3f ms on the device, sigmaG = %15.10f, sigmaE = %15.10f, mu = %15.10f, m0 = %10ld\n", iteration,
+                            t1 - t0, sweep_ms, sg, sigmaE, mu, m0s);
+            if (iteration % opt.thin != 0) continue;
+            if (effects) cs.effects((uint32_t)r, beta.data(), comp.data(), acum.data());
+            const int len = cs.csv_line((uint32_t)r, iteration, buff.data(), buff.size());
+            write_line(outf[r], n_thinned_saved, buff.data(), len);
+            if (effects) {
+                write_thinned(betf[r], n_thinned_saved, iteration, beta.data(), M, sizeof(double));
+                write_thinned(acuf[r], n_thinned_saved, iteration, acum.data(), M, sizeof(double));
+                write_thinned(cpnf[r], n_thinned_saved, iteration, comp.data(), M, sizeof(int));
+            }
+            if (many && iteration >= opt.burnin) {
+                std::vector<double>* row = &rec[(size_t)r * P];
+                for (int g = 0; g < G; ++g) row[g].push_back(sigmaG[g]);
+                row[G].push_back(sg);
+                row[G + 1].push_back(sigmaE);
+                row[G + 2].push_back(sg / (sigmaE + sg));
+                row[G + 3].push_back((double)m0s);
+                row[G + 4].push_back(mu);
+            }
+        }
+        std::fflush(stdout);
+        if (iteration % opt.thin == 0) n_thinned_saved += 1;
+    }
+    outs.close(true);
+    if (post.on) write_post_table(post, dev, cs.R, M);
+    cs.destroy();
+    const double max_rhat = many ? write_rhat(opt, base + ".rhat", rec, R, G) : 0.0;
+    hgibbs_destroy(dev);
+
+    const char* files = post.on && post.only ? "csv" : "{csv,bet,cpn,acu}";
+    char par[96] = "", rh[48] = "NA";
+    if (streams) std::snprintf(par, sizeof par, " in %u streams (largest interval %u markers)", streams, largest);
+    if (!std::isnan(max_rhat)) std::snprintf(rh, sizeof rh, "%.9g", max_rhat);
+    std::printf("SUMSTAT: %u markers used, %u left out (%u not in the table, %u with another allele pair, %u without usable BETA, SE and N, %u without a finite sd in the panel), "
+                "n_eff %.12g, band %u x %u doubles = %.1f MiB of device memory (built in %.3f ms), ",
+                used, M - used, M - tab.matched - tab.allele - tab.unusable, tab.allele, tab.unusable, nosd, tab.n_eff, M, W, (double)M * W * 8.0 / 1048576.0, band_ms);
+    const double per_sweep = sweeps ? sweep_total_ms / sweeps : 0.0;
+    if (many)
+        std::printf("%u chains, %.3f ms per sweep launch (all chains) on the device over %u sweeps%s, largest R^ %s, wrote %s.%s, %s.c<r>.%s for the chains r >= 1 and %s.rhat%s\n",
+                    cs.R, per_sweep, sweeps, par, rh, base.c_str(), files, base.c_str(), files, base.c_str(), post_report(post).c_str());
+    else
+        std::printf("%.3f ms per sweep on the device over %u sweeps%s, wrote %s.%s%s\n", per_sweep, sweeps, par, base.c_str(), files, post_report(post).c_str());
 }
 
 int run_sumstats(const Options& opt, const Cohort& co, const std::vector<int32_t>& groups, const std::vector<double>& mS_flat, int G, int K)
@@ -4164,95 +4219,7 @@ int run_sumstats(const Options& opt, const Cohort& co, const std::vector<int32_t
     md.groups = groups.empty() ? nullptr : groups.data();
     md.mS = mS_flat.data();
     PostJob post = post_job(opt, base, bim, mstd, tab.use, K);
-    const char* files = post.on && post.only ? "csv" : "{csv,bet,cpn,acu}";
-    if (opt.sumstatsChainsGiven) { // R chains in one launch per iteration, and the convergence table
-        const ChainsReport rep = run_sumstats_chains(opt, dev, md, tab, win, W, M, G, base, post);
-        hgibbs_destroy(dev);
-        char par[96] = "", rh[48] = "NA";
-        if (rep.streams) std::snprintf(par, sizeof par, " in %u streams (largest interval %u markers)", rep.streams, rep.largest);
-        if (!std::isnan(rep.max_rhat)) std::snprintf(rh, sizeof rh, "%.9g", rep.max_rhat);
-        std::printf("SUMSTAT: %u markers used, %u left out (%u not in the table, %u with another allele pair, %u without usable BETA, SE and N, %u without a finite sd in the panel), "
-                    "n_eff %.12g, band %u x %u doubles = %.1f MiB of device memory (built in %.3f ms), %u chains, %.3f ms per sweep launch (all chains) on the device over %u "
-                    "sweeps%s, largest R^ %s, wrote %s.%s, %s.c<r>.%s for the chains r >= 1 and %s.rhat%s\n",
-                    used, M - used, M - tab.matched - tab.allele - tab.unusable, tab.allele, tab.unusable, nosd, tab.n_eff, M, W, (double)M * W * 8.0 / 1048576.0,
-                    rep.band_ms, rep.chains, rep.sweeps ? rep.sweep_total_ms / rep.sweeps : 0.0, rep.sweeps, par, rh, base.c_str(), files, base.c_str(), files, base.c_str(),
-                    post_report(post).c_str());
-        return 0;
-    }
-    hydra_ss_chain_t chain = nullptr;
-    hg_check(hydra_ss_chain_create(dev, &md, tab.n_eff, W, win.ahead.data(), tab.xty.data(), tab.use.data(), &chain), "hydra_ss_chain_create");
-    // independent LD blocks in parallel streams: the intervals come from the window, so they are known before the first sweep
-    uint32_t streams = 0, largest = 0;
-    if (opt.sumstatsStreamsGiven) {
-        long smax = 0;
-        whole_int(opt.sumstatsStreams, smax);
-        hg_check(hydra_ss_chain_set_streams(chain, (uint32_t)smax), "hydra_ss_chain_set_streams");
-        hg_check(hydra_ss_chain_streams(chain, &streams, nullptr, nullptr), "hydra_ss_chain_streams");
-        std::vector<uint32_t> bounds((size_t)streams + 1u);
-        hg_check(hydra_ss_chain_streams(chain, nullptr, bounds.data(), nullptr), "hydra_ss_chain_streams");
-        for (uint32_t s = 0; s < streams; ++s) largest = std::max(largest, bounds[s + 1] - bounds[s]);
-    }
-    double band_ms = 0.0, sweep_ms = 0.0;
-    hg_check(hgibbs_last_ss_ms(dev, &band_ms, &sweep_ms), "hgibbs_last_ss_ms");
-    if (post.on) hg_check(hgibbs_ss_post_begin(dev, 0u, post.T), "hgibbs_ss_post_begin"); // the handle's own chain
-    const bool effects = !(post.on && post.only); // --sumstats-post-only: no .bet, .cpn, .acu, and no download of a record
-
-    // the chain's files and formats (:1302-1309, :2736-2794)
-    OutFiles outs;
-    FILE* outf = outs.open(base + ".csv");
-    FILE *betf = nullptr, *cpnf = nullptr, *acuf = nullptr;
-    if (effects) {
-        betf = outs.open(base + ".bet");
-        cpnf = outs.open(base + ".cpn");
-        acuf = outs.open(base + ".acu");
-        for (FILE* f : {betf, cpnf, acuf}) pwrite_at(f, 0, &M, sizeof(unsigned));
-    }
-    std::vector<double> beta(M), acum(M), sigmaG(G);
-    std::vector<int32_t> comp(M), m0(G);
-    std::vector<char> buff(50000);
-    unsigned n_thinned_saved = 0, sweeps = 0;
-    double sweep_total_ms = 0.0;
-    for (unsigned iteration = 0; iteration < opt.chainLength; ++iteration) {
-        const double t0 = now_s();
-        hg_check(hydra_ss_chain_iterate(chain), "hydra_ss_chain_iterate");
-        const double t1 = now_s();
-        hg_check(hgibbs_last_ss_ms(dev, &band_ms, &sweep_ms), "hgibbs_last_ss_ms");
-        sweep_total_ms += sweep_ms;
-        ++sweeps;
-        double sigmaE = 0, mu = 0;
-        hydra_ss_chain_state(chain, &sigmaE, &mu, sigmaG.data(), nullptr, m0.data(), nullptr, nullptr);
-        double sg = 0;
-        long m0s = 0;
-        for (int g = 0; g < G; ++g) {
-            sg += sigmaG[g];
-            m0s += m0[g];
-        }
-        std::printf("RESULT : it %4d: proc = %9.3f s, sweep = %9.3f ms on the device, sigmaG = %15.10f, sigmaE = %15.10f, mu = %15.10f, m0 = %10ld\n", iteration, t1 - t0,
-                    sweep_ms, sg, sigmaE, mu, m0s);
-        std::fflush(stdout);
-        if (post.on && post_counts(opt, iteration)) hg_check(hgibbs_ss_post_add(dev), "hgibbs_ss_post_add");
-        if (iteration % opt.thin == 0) {
-            if (effects) hg_check(hydra_ss_chain_effects(chain, beta.data(), comp.data(), acum.data(), nullptr), "hydra_ss_chain_effects");
-            const int len = hydra_ss_chain_csv_line(chain, iteration, buff.data(), buff.size());
-            write_line(outf, n_thinned_saved, buff.data(), len);
-            if (effects) {
-                write_thinned(betf, n_thinned_saved, iteration, beta.data(), M, sizeof(double));
-                write_thinned(acuf, n_thinned_saved, iteration, acum.data(), M, sizeof(double));
-                write_thinned(cpnf, n_thinned_saved, iteration, comp.data(), M, sizeof(int));
-            }
-            n_thinned_saved += 1;
-        }
-    }
-    outs.close(true);
-    if (post.on) write_post_table(post, dev, 1u, M);
-    hydra_ss_chain_destroy(chain);
-    hgibbs_destroy(dev);
-    char par[96] = "";
-    if (streams) std::snprintf(par, sizeof par, " in %u streams (largest interval %u markers)", streams, largest);
-    std::printf("SUMSTAT: %u markers used, %u left out (%u not in the table, %u with another allele pair, %u without usable BETA, SE and N, %u without a finite sd in the panel), "
-                "n_eff %.12g, band %u x %u doubles = %.1f MiB of device memory (built in %.3f ms), %.3f ms per sweep on the device over %u sweeps%s, wrote %s.%s%s\n",
-                used, M - used, M - tab.matched - tab.allele - tab.unusable, tab.allele, tab.unusable, nosd, tab.n_eff, M, W, (double)M * W * 8.0 / 1048576.0, band_ms,
-                sweeps ? sweep_total_ms / sweeps : 0.0, sweeps, par, base.c_str(), files, post_report(post).c_str());
+    run_sumstats_chains(opt, dev, md, tab, win, W, M, G, base, post, used, nosd);
     return 0;
 }
 

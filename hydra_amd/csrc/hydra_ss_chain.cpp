@@ -109,16 +109,68 @@ static std::string esqn_text(const char* who, uint32_t iteration, double e_sqn, 
     return buf;
 }
 
+// One chain's step around the sweep; the order in which it draws from its generator is the contract.  Before the sweep: mu, the shuffle, m0.
+static void ss_before_sweep(hg::ChainCore& k, double dN)
+{
+    hg::Mt gen{k.rng.x, k.rng.idx};
+    // :1675-1686 with a residual whose mean plus the old mu is 0
+    k.mu = hg::norm_rng(gen, 0.0, k.sigmaE / dN);
+    // :1691-1694
+    if (k.shuffle) hg::shuffle_libstdcxx6_fast(k.order.data(), k.order.size(), gen);
+    std::fill(k.m0.begin(), k.m0.end(), 0);
+    k.rng.idx = gen.idx;
+}
+
+// After the sums (bsq per group; sb = sum beta_j b_j, sc = sum beta_j c_j): the hyper-parameters, e_sqn and sigmaE.  `chain`: esqn_text's.
+static int ss_after_sums(hg::ChainCore& k, double dN, const double* bsq, double sb, double sc, const char* who, int chain)
+{
+    hg::Mt gen{k.rng.x, k.rng.idx};
+    // :2495-2578
+    hg::core_hyper(k, bsq, gen);
+    // :2685-2690
+    const double e_sqn = ((dN - 1.0) - (sb + sc)) + dN * k.mu * k.mu;
+    k.rng.idx = gen.idx;
+    if (!(e_sqn > 0.0)) return cfail(esqn_text(who, k.iteration, e_sqn, chain));
+    k.sigmaE = hg::inv_scaled_chisq_rng(gen, V0E + dN, (e_sqn + V0E * S02E) / (V0E + dN));
+    k.rng.idx = gen.idx;
+    k.iteration += 1;
+    return 0;
+}
+
+// What both device chains need before the band: the panel's M, and the window as hgibbs_ss_begin will hold it
+static int ss_panel(hgibbs_t dev, const char* who, uint32_t W, const uint32_t* ahead, uint32_t& M, std::vector<uint32_t>& win)
+{
+    uint32_t n_global = 0, n_local = 0, row_begin = 0;
+    if (hgibbs_dims(dev, &n_global, &n_local, &M, &row_begin)) return 1;
+    if (n_global < 2 || M == 0) return cfail(std::string(who) + ": load the panel's genotypes first (hgibbs_load_bed / hgibbs_synth_bed)");
+    win.resize(M);
+    for (uint32_t j = 0; j < M; ++j) win[j] = ahead ? ahead[j] : std::min(W, M - 1u - j);
+    return 0;
+}
+
+// Up to S_max intervals of independent blocks, then the S generators of each of the R chains from its own (streams: [R][S])
+static int ss_make_streams(uint32_t M, const std::vector<uint32_t>& ahead, uint32_t S_max, hg::ChainCore* chains, uint32_t R, std::vector<uint32_t>& bounds,
+                           std::vector<hgibbs_rng_state>& streams)
+{
+    std::vector<uint32_t> b((size_t)S_max + 1u);
+    uint32_t S = 0;
+    if (hgibbs_ss_partition(M, ahead.data(), S_max, b.data(), &S)) return 1;
+    b.resize((size_t)S + 1u);
+    bounds = b;
+    streams.resize((size_t)R * S);
+    for (uint32_t r = 0; r < R; ++r) seed_streams(chains[r].rng, S, streams.data() + (size_t)r * S);
+    return 0;
+}
+
 extern "C" {
 
 int hydra_ss_chain_create(hgibbs_t dev, const hydra_model_desc* model, double n_eff, uint32_t W, const uint32_t* ahead, const double* xty,
                           const uint8_t* use, hydra_ss_chain_t* out)
 {
     if (!dev || !model || !xty || !out) return cfail("hydra_ss_chain_create: null argument");
-    uint32_t n_global = 0, n_local = 0, M = 0, row_begin = 0;
-    if (hgibbs_dims(dev, &n_global, &n_local, &M, &row_begin)) return 1;
-    if (n_global < 2 || M == 0) return cfail("hydra_ss_chain_create: load the panel's genotypes first (hgibbs_load_bed / hgibbs_synth_bed)");
     std::unique_ptr<hydra_ss_chain> c(new hydra_ss_chain());
+    uint32_t M = 0;
+    if (ss_panel(dev, "hydra_ss_chain_create", W, ahead, M, c->ahead)) return 1;
     c->dev = dev;
     c->M = M;
     c->W = W;
@@ -129,8 +181,6 @@ int hydra_ss_chain_create(hgibbs_t dev, const hydra_model_desc* model, double n_
         (void)hgibbs_ss_end(dev);
         return 1;
     }
-    c->ahead.resize(M);
-    for (uint32_t j = 0; j < M; ++j) c->ahead[j] = ahead ? ahead[j] : std::min(W, M - 1u - j);
     *out = c.release();
     return 0;
 }
@@ -170,20 +220,11 @@ int hydra_ss_chain_iterate(hydra_ss_chain_t c)
     if (!c) return cfail("hydra_ss_chain_iterate: null chain");
     const int G = c->G, K = c->K;
     const uint32_t M = c->M;
-    const double dN = c->n;
-    hg::Mt gen{c->rng.x, c->rng.idx};
     const bool timing = ss_timing();
     const double t0 = timing ? ss_now_ms() : 0.0;
-
-    // :1675-1686 with a residual whose mean plus the old mu is 0
-    c->mu = hg::norm_rng(gen, 0.0, c->sigmaE / dN);
-
-    // :1691-1694
-    if (c->shuffle) hg::shuffle_libstdcxx6_fast(c->order.data(), c->order.size(), gen);
-    std::fill(c->m0.begin(), c->m0.end(), 0);
+    ss_before_sweep(*c, c->n);
 
     // :1709-2490; the generator travels with the call
-    c->rng.idx = gen.idx;
     const double t1 = timing ? ss_now_ms() : 0.0;
     const uint32_t S = (uint32_t)c->streams.size();
     if (S) { // the main generator is not touched by the sweep
@@ -201,10 +242,8 @@ int hydra_ss_chain_iterate(hydra_ss_chain_t c)
                                     c->groups.data(), c->cVa.data(), c->cVaI.data(), c->order.data(), c->sigmaE, c->sigmaG.data(), c->estPi.data(),
                                     c->adaV.data(), &c->rng, c->cass.data(), &c->last_nnz))
         return 1;
-    gen.idx = c->rng.idx;
     const double t2 = timing ? ss_now_ms() : 0.0;
 
-    // :2495-2578
     std::vector<double> bsq(G, 0.0);
     double sb = 0.0, sc = 0.0; // sum beta_j b_j, sum beta_j c_j in marker order over the non-zero effects (as hgibbs_ss_state)
     if (c->dev) {
@@ -219,17 +258,7 @@ int hydra_ss_chain_iterate(hydra_ss_chain_t c)
             sc += b * c->c[i];
         }
     const double t3 = timing ? ss_now_ms() : 0.0;
-    hg::core_hyper(*c, bsq.data(), gen);
-
-    // :2685-2690
-    const double e_sqn = ((dN - 1.0) - (sb + sc)) + dN * c->mu * c->mu;
-    if (!(e_sqn > 0.0)) {
-        c->rng.idx = gen.idx;
-        return cfail(esqn_text("hydra_ss_chain_iterate", c->iteration, e_sqn, -1));
-    }
-    c->sigmaE = hg::inv_scaled_chisq_rng(gen, V0E + dN, (e_sqn + V0E * S02E) / (V0E + dN));
-    c->rng.idx = gen.idx;
-    c->iteration += 1;
+    if (ss_after_sums(*c, c->n, bsq.data(), sb, sc, "hydra_ss_chain_iterate", -1)) return 1;
     if (timing) ss_timing_line("hydra_ss_chain_iterate", c->dev, 1u, t0, t1, t2, t3, ss_now_ms());
     return 0;
 }
@@ -262,14 +291,7 @@ int hydra_ss_chain_set_streams(hydra_ss_chain_t c, uint32_t S_max)
     if (c->iteration > 0) return cfail(std::string(who) + ": the chain has run " + std::to_string(c->iteration) + " iteration(s): streams are set before the first");
     if (!c->streams.empty()) return cfail(std::string(who) + ": streams are already set");
     if (S_max < 1u || S_max > 1024u) return cfail(std::string(who) + ": S_max = " + std::to_string(S_max) + ", must be in [1, 1024]");
-    std::vector<uint32_t> bounds((size_t)S_max + 1u);
-    uint32_t S = 0;
-    if (hgibbs_ss_partition(c->M, c->ahead.data(), S_max, bounds.data(), &S)) return 1;
-    bounds.resize((size_t)S + 1u);
-    c->streams.resize(S);
-    seed_streams(c->rng, S, c->streams.data());
-    c->bounds = bounds;
-    return 0;
+    return ss_make_streams(c->M, c->ahead, S_max, c, 1u, c->bounds, c->streams);
 }
 
 int hydra_ss_chain_streams(hydra_ss_chain_t c, uint32_t* S, uint32_t* bounds, hgibbs_rng_state* rngs)
@@ -301,10 +323,9 @@ int hydra_ss_multi_create(hgibbs_t dev, const hydra_model_desc* model, uint32_t 
     if (!dev || !model || !seeds || !xty || !out) return cfail(std::string(who) + ": null argument");
     if (R < 1u || R > 64u) return cfail(std::string(who) + ": R = " + std::to_string(R) + ", must be in [1, 64]");
     if (S_max > 1024u) return cfail(std::string(who) + ": S_max = " + std::to_string(S_max) + ", must be in [0, 1024] (0: the single stream)");
-    uint32_t n_global = 0, n_local = 0, M = 0, row_begin = 0;
-    if (hgibbs_dims(dev, &n_global, &n_local, &M, &row_begin)) return 1;
-    if (n_global < 2 || M == 0) return cfail(std::string(who) + ": load the panel's genotypes first (hgibbs_load_bed / hgibbs_synth_bed)");
     std::unique_ptr<hydra_ss_multi> c(new hydra_ss_multi());
+    uint32_t M = 0;
+    if (ss_panel(dev, who, W, ahead, M, c->ahead)) return 1;
     c->dev = dev;
     c->M = M;
     c->W = W;
@@ -324,20 +345,12 @@ int hydra_ss_multi_create(hgibbs_t dev, const hydra_model_desc* model, uint32_t 
         (void)hgibbs_ss_end(dev);
         return 1;
     }
-    c->ahead.resize(M);
-    for (uint32_t j = 0; j < M; ++j) c->ahead[j] = ahead ? ahead[j] : std::min(W, M - 1u - j);
     if (S_max) {
-        std::vector<uint32_t> bounds((size_t)S_max + 1u);
-        uint32_t S = 0;
-        if (hgibbs_ss_partition(M, c->ahead.data(), S_max, bounds.data(), &S)) {
+        if (ss_make_streams(M, c->ahead, S_max, c->chains.data(), R, c->bounds, c->streams)) {
             (void)hgibbs_ss_end(dev);
             return 1;
         }
-        bounds.resize((size_t)S + 1u);
-        c->bounds = bounds;
-        c->S = S;
-        c->streams.resize((size_t)R * S);
-        for (uint32_t r = 0; r < R; ++r) seed_streams(c->chains[r].rng, S, c->streams.data() + (size_t)r * S);
+        c->S = (uint32_t)c->bounds.size() - 1u;
     }
     *out = c.release();
     return 0;
@@ -369,16 +382,12 @@ int hydra_ss_multi_iterate(hydra_ss_multi_t c)
     c->sc.resize(R);
     c->bsq.resize((size_t)R * G);
 
-    // per chain: mu and the shuffle on its own generator, as hydra_ss_chain_iterate
+    // per chain: mu and the shuffle on its own generator
     const bool timing = ss_timing();
     const double t0 = timing ? ss_now_ms() : 0.0;
     for (uint32_t r = 0; r < R; ++r) {
         hg::ChainCore& k = c->chains[r];
-        hg::Mt gen{k.rng.x, k.rng.idx};
-        k.mu = hg::norm_rng(gen, 0.0, k.sigmaE / dN);
-        if (k.shuffle) hg::shuffle_libstdcxx6_fast(k.order.data(), k.order.size(), gen);
-        std::fill(k.m0.begin(), k.m0.end(), 0);
-        k.rng.idx = gen.idx;
+        ss_before_sweep(k, dN);
         std::copy(k.order.begin(), k.order.end(), c->orders.begin() + (size_t)r * M);
         std::copy(k.adaV.begin(), k.adaV.end(), c->ada.begin() + (size_t)r * M);
         c->sigmaE[r] = k.sigmaE;
@@ -401,14 +410,7 @@ int hydra_ss_multi_iterate(hydra_ss_multi_t c)
         if (!S) k.rng = c->rngs[r];
         std::copy(c->cass.begin() + r * GK, c->cass.begin() + (r + 1) * GK, k.cass.begin());
         k.last_nnz = c->nnz[r];
-        hg::Mt gen{k.rng.x, k.rng.idx};
-        hg::core_hyper(k, c->bsq.data() + (size_t)r * G, gen);
-        const double e_sqn = ((dN - 1.0) - (c->sb[r] + c->sc[r])) + dN * k.mu * k.mu;
-        k.rng.idx = gen.idx;
-        if (!(e_sqn > 0.0)) return cfail(esqn_text("hydra_ss_multi_iterate", k.iteration, e_sqn, (int)r));
-        k.sigmaE = hg::inv_scaled_chisq_rng(gen, V0E + dN, (e_sqn + V0E * S02E) / (V0E + dN));
-        k.rng.idx = gen.idx;
-        k.iteration += 1;
+        if (ss_after_sums(k, dN, c->bsq.data() + (size_t)r * G, c->sb[r], c->sc[r], "hydra_ss_multi_iterate", (int)r)) return 1;
     }
     if (timing) ss_timing_line("hydra_ss_multi_iterate", c->dev, R, t0, t1, t2, t3, ss_now_ms());
     return 0;
