@@ -30,6 +30,8 @@ ABI_SYMBOLS = [
     "hydra_ss_chain_effects", "hydra_ss_chain_last_nnz", "hydra_ss_chain_order", "hydra_ss_chain_csv_line",
     "hgibbs_ss_replicas", "hgibbs_ss_sweep_replicas", "hgibbs_ss_replica_sums", "hgibbs_ss_replica_get", "hgibbs_ss_replica_set_beta", "hgibbs_mcmc_diag",
     "hgibbs_ss_post_begin", "hgibbs_ss_post_add", "hgibbs_ss_post_get", "hgibbs_ss_post_raw", "hgibbs_ss_post_end", "hgibbs_last_ss_post_ms",
+    "hgibbs_cs_begin", "hgibbs_cs_add_flags", "hgibbs_ss_cs_add", "hgibbs_cs_counts", "hgibbs_cs_history", "hgibbs_cs_sets", "hgibbs_cs_end", "hgibbs_last_cs_ms",
+    "hgibbs_cs_select",
     "hydra_ss_multi_create", "hydra_ss_multi_destroy", "hydra_ss_multi_iterate", "hydra_ss_multi_state", "hydra_ss_multi_effects", "hydra_ss_multi_streams",
     "hydra_ss_multi_last_nnz", "hydra_ss_multi_csv_line",
     "hgibbs_marker_dots", "hgibbs_last_marker_dots_ms", "hgibbs_marker_class_sums", "hgibbs_last_marker_class_sums_ms", "hgibbs_logit_null",
@@ -317,6 +319,15 @@ def lib():
     L.hgibbs_ss_post_raw.argtypes = [vp, C.c_uint32, C.c_uint32, dp, dp]
     L.hgibbs_ss_post_end.argtypes = [vp]
     L.hgibbs_last_ss_post_ms.argtypes = [vp, dp, dp]
+    L.hgibbs_cs_begin.argtypes = [vp, C.c_uint32, C.c_uint32]
+    L.hgibbs_cs_add_flags.argtypes = [vp, u8p]
+    L.hgibbs_ss_cs_add.argtypes = [vp, C.c_uint32]
+    L.hgibbs_cs_counts.argtypes = [vp, u32p]
+    L.hgibbs_cs_history.argtypes = [vp, u64p]
+    L.hgibbs_cs_sets.argtypes = [vp, C.c_uint32, u64p, u64p, C.c_uint32, u32p, C.c_uint32, C.c_uint32, u32p, u32p, u64p, u32p, u32p]
+    L.hgibbs_cs_end.argtypes = [vp]
+    L.hgibbs_last_cs_ms.argtypes = [vp, dp, dp, dp]
+    L.hgibbs_cs_select.argtypes = [C.c_uint32, C.c_uint32, u32p, u32p, u32p, u32p, u32p, u32p, C.c_uint32, C.c_uint32, u32p, u32p]
     L.hydra_ss_multi_create.argtypes = [vp, C.POINTER(ModelDesc), C.c_uint32, u32p, C.c_double, C.c_uint32, u32p, dp, u8p, C.c_uint32, C.POINTER(vp)]
     L.hydra_ss_multi_destroy.argtypes = [vp]
     L.hydra_ss_multi_iterate.argtypes = [vp]
@@ -428,6 +439,29 @@ def ld_greedy(M, W, fwd, bwd, order, may_lead=None):
     owner = np.full(max(int(M), 1), -1, dtype=np.int32)
     check(lib().hgibbs_ld_greedy(M, W, _u64(fwd), _u64(bwd), od.ctypes.data_as(C_U32P), od.size, _u8(ml) if ml is not None else None, _ip(owner)))
     return owner[:M]
+
+
+def _u32(a):
+    return a.ctypes.data_as(C_U32P)
+
+
+def cs_select(M, leads, lead_cnt, status, size, pep, members, max_size, min_pep):
+    """hgibbs_cs_select (host only): the walk over Device.cs_sets' candidates by descending lead_cnt, ties by ascending lead; one is
+    accepted iff its status is 0, its pep >= min_pep and none of its members belongs to a set accepted before.  members is
+    (nlead, max_size) uint32.  Returns the accepted candidates' positions in the order taken (uint32)."""
+    leads, lead_cnt, status, size, pep = (np.ascontiguousarray(a, dtype=np.uint32).reshape(-1) for a in (leads, lead_cnt, status, size, pep))
+    n = leads.size
+    members = np.ascontiguousarray(members, dtype=np.uint32)
+    for a in (lead_cnt, status, size, pep):
+        if a.size != n:
+            raise ValueError("lead_cnt, status, size and pep must have one entry per lead")
+    if 1 <= max_size <= 256 and members.size != n * max_size:
+        raise ValueError("members must be (%d, %d)" % (n, max_size))
+    taken = np.zeros(max(n, 1), dtype=np.uint32)
+    nt = C.c_uint32(0)
+    check(lib().hgibbs_cs_select(M, n, _u32(leads), _u32(lead_cnt), _u32(status), _u32(size), _u32(pep), _u32(members), int(max_size) & 0xffffffff,
+                                 int(min_pep) & 0xffffffff, _u32(taken), C.byref(nt)))
+    return taken[:nt.value].copy()
 
 
 def ss_ahead(M, W, ahead=None):
@@ -1421,6 +1455,62 @@ class Device:
         a, b = C.c_double(), C.c_double()
         check(self.L.hgibbs_last_ss_post_ms(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def cs_begin(self, C_, T):
+        """hgibbs_cs_begin: the inclusion history of C_ chains x T planned records, one bit per marker and record, zeroed."""
+        check(self.L.hgibbs_cs_begin(self.h, int(C_) & 0xffffffff, int(T) & 0xffffffff))
+        self._cs_shape = (int(C_), int(T))
+
+    def cs_add_flags(self, flags):
+        """hgibbs_cs_add_flags: one record of every chain from flags (C, M) bytes, non-zero = in the model."""
+        C_ = self._cs_shape[0]
+        fl = np.ascontiguousarray(flags, dtype=np.uint8)
+        if fl.size != C_ * self.M:
+            raise ValueError("flags must be (%d, %d)" % (C_, self.M))
+        check(self.L.hgibbs_cs_add_flags(self.h, _u8(fl)))
+
+    def ss_cs_add(self, R):
+        """hgibbs_ss_cs_add: one record of every chain from the ss chains' components as they stand (R = 0: the handle's own chain)."""
+        check(self.L.hgibbs_ss_cs_add(self.h, int(R) & 0xffffffff))
+
+    def cs_counts(self):
+        """hgibbs_cs_counts: cnt (M,) uint32, the records added so far in which the marker is in the model."""
+        cnt = np.zeros(self.M, dtype=np.uint32)
+        check(self.L.hgibbs_cs_counts(self.h, _u32(cnt)))
+        return cnt
+
+    def cs_history(self):
+        """hgibbs_cs_history: the words (NW, M) uint64, NW = (C T + 63) // 64; bit q % 64 of word [q // 64, j] is marker j in record q."""
+        C_, T = self._cs_shape
+        out = np.zeros(((C_ * T + 63) // 64, self.M), dtype=np.uint64)
+        check(self.L.hgibbs_cs_history(self.h, _u64(out)))
+        return out
+
+    def cs_sets(self, W, fwd, bwd, leads, need, max_size):
+        """hgibbs_cs_sets: the candidate set of every lead on masks in ld_mask's layout.  Returns status, size (nlead,) uint32, sum
+        (nlead,) uint64, pep (nlead,) uint32 and members (nlead, max_size) uint32 (0xFFFFFFFF in the unused slots)."""
+        wpr = (max(int(W), 1) + 63) // 64
+        fwd = np.ascontiguousarray(fwd, dtype=np.uint64)
+        bwd = np.ascontiguousarray(bwd, dtype=np.uint64)
+        if 1 <= W <= 4096 and (fwd.shape != (self.M, wpr) or bwd.shape != (self.M, wpr)):
+            raise ValueError("fwd and bwd must be (%d, %d)" % (self.M, wpr))
+        ld = np.ascontiguousarray(leads, dtype=np.uint32).reshape(-1)
+        n, ms = ld.size, max_size if 1 <= max_size <= 256 else 1
+        status, size, pep = (np.zeros(max(n, 1), dtype=np.uint32) for _ in range(3))
+        total = np.zeros(max(n, 1), dtype=np.uint64)
+        members = np.zeros((max(n, 1), ms), dtype=np.uint32)
+        check(self.L.hgibbs_cs_sets(self.h, W, _u64(fwd), _u64(bwd), n, _u32(ld), int(need) & 0xffffffff, int(max_size) & 0xffffffff, _u32(status), _u32(size),
+                                    _u64(total), _u32(pep), _u32(members)))
+        return status[:n], size[:n], total[:n], pep[:n], members[:n]
+
+    def cs_end(self):
+        check(self.L.hgibbs_cs_end(self.h))
+
+    def last_cs_ms(self):
+        """(add_ms, counts_ms, sets_ms): device time of every add since cs_begin (their sum), of the last counts kernel, of the last sets kernel."""
+        a, b, c = C.c_double(), C.c_double(), C.c_double()
+        check(self.L.hgibbs_last_cs_ms(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
 
     def ss_end(self):
         check(self.L.hgibbs_ss_end(self.h))

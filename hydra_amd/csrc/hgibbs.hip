@@ -62,6 +62,7 @@ extern "C" void hgibbs_set_error_(const char* msg) { g_err = msg; }
 struct BwState; // BayesW side of the handle (hg_bayesw.hip.h)
 struct SparseLoad; // a load from index lists between hgibbs_sparse_begin and hgibbs_sparse_end (hg_sparse.hip.h)
 struct SsState; // the summary-statistics sweep's side of the handle between hgibbs_ss_begin and hgibbs_ss_end (hg_sumstat.hip.h)
+struct CsState; // the inclusion history between hgibbs_cs_begin and hgibbs_cs_end (hg_cs.hip.h)
 struct hgibbs_ctx;
 bool ss_post_is_open(const hgibbs_ctx* h); // hgibbs_ss_post_begin .. hgibbs_ss_post_end (hg_sspost.hip.h)
 
@@ -253,6 +254,7 @@ struct hgibbs_ctx : Problem {
     long long sparse_piece = 0;    // option sparse_piece: bytes of index buffers per piece of markers of hgibbs_sparse_get (0 = automatic)
     double sparse_ms[2] = {0, 0};  // device time of the last sparse load (begin .. end, every kernel) and of the last hgibbs_sparse_get
     std::unique_ptr<SsState> ss;   // hgibbs_ss_begin .. hgibbs_ss_end: the band, c and b of the summary-statistics sweep
+    std::unique_ptr<CsState> cs;   // hgibbs_cs_begin .. hgibbs_cs_end: one bit per marker and record, its counts (independent of ss)
 };
 
 static int ensure_scratch(hgibbs_ctx* h, size_t n)
@@ -2212,6 +2214,7 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
 #include "hg_ldmask.hip.h"
 #include "hg_sumstat.hip.h"
 #include "hg_sspost.hip.h"
+#include "hg_cs.hip.h"
 #include "hg_mdots.hip.h"
 #include "hg_mclass.hip.h"
 #include "hg_sgram.hip.h"
@@ -2225,4 +2228,4 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
 #include "hg_grmsums.hip.h"
 #include "hg_sparse.hip.h"
 
-hgibbs_ctx::~hgibbs_ctx() = default; // BwState, SparseLoad and SsState are complete here
+hgibbs_ctx::~hgibbs_ctx() = default; // BwState, SparseLoad, SsState and CsState are complete here

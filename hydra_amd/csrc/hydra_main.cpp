@@ -118,6 +118,12 @@
 // `--sumstats-post [--sumstats-post-all] [--sumstats-post-only] [--sumstats-post-out F]` writes <name>.post (or F), one row per .bim
 // marker: posterior mean and sd of the effect, PIP, component shares and split-R^ over the chains, accumulated on the device from the
 // thinned records at or after --burn-in (-all: every iteration from there; -only: no .bet, .cpn, .acu at all).
+// `--sumstats-cs [--sumstats-cs-r2 T] [--sumstats-cs-alpha A] [--sumstats-cs-pep P] [--sumstats-cs-lead L] [--sumstats-cs-max-size K]
+// [--sumstats-cs-out F]` writes <name>.cs (or F): local credible sets from the inclusion history of the thinned records at or after
+// --burn-in, one bit per marker and record kept on the device.  `--cs [--cs-chains R] [--cs-window-kb KB |
+// --cs-window-snps W] [--cs-r2 T] [--cs-alpha A] [--cs-pep P] [--cs-lead L] [--cs-max-size K] [--cs-out F]`, appended to a bayesMPI
+// command line, samples nothing and writes the same table from a finished chain's <name>.bet (and <name>.c<r>.bet).  Not covered:
+// GCTB's rule for overlapping sets and its .lcs layout, the share of heritability per set; GCTB has not been run against it.
 //
 // Not reproduced (out of scope for the hot path): the mixed
 // in-memory representation (--threshold-fnz), --sparse-sync/--bed-sync, --check-RAM,
@@ -150,6 +156,11 @@
 #include "../../include/hgibbs.h"
 
 namespace {
+
+// the sub-options the two credible-set routes share, as given (empty: not given; checked before the device)
+struct CsStrings {
+    std::string r2, alpha, pep, lead, maxSize, out; // -r2 T, -alpha A, -pep P, -lead L, -max-size K, -out F
+};
 
 struct Options { // src/options.hpp:20-138 (subset that reaches bayesMPI)
     std::string bayesType, analysisType = "Bayes";
@@ -215,6 +226,11 @@ struct Options { // src/options.hpp:20-138 (subset that reaches bayesMPI)
     std::string sumstatsChains;
     bool sumstatsPost = false, sumstatsPostAll = false, sumstatsPostOnly = false; // --sumstats-post: the per-marker posterior table
     std::string sumstatsPostOut; // --sumstats-post-out F
+    bool sumstatsCs = false; // --sumstats-cs: local credible sets from the chains' inclusion history on the device
+    CsStrings ssCs;          // --sumstats-cs-* as given
+    bool cs = false, csKbGiven = false, csSnpsGiven = false; // --cs: the same sets from a finished chain's .bet; which window option was given
+    std::string csChains, csKb, csSnps; // --cs-chains R, --cs-window-kb KB, --cs-window-snps W as given
+    CsStrings csArgs;                   // --cs-r2 .. --cs-out as given
     bool saveGiven = false, ignoreXfilesGiven = false; // --save, --ignore-xfiles on the command line (--sumstats takes no checkpoint option)
     int batch = 0, cpg = 0; // tuning knobs of this build (not hydra's)
 };
@@ -362,7 +378,27 @@ Options parse(int argc, const char* argv[])
         } else if (a == "--sumstats-n") {
             o.sumstatsN = need(i);
             o.sumstatsNGiven = true;
-        }
+        } else if (a == "--sumstats-cs") o.sumstatsCs = true;
+        else if (a == "--sumstats-cs-r2") o.ssCs.r2 = need(i);
+        else if (a == "--sumstats-cs-alpha") o.ssCs.alpha = need(i);
+        else if (a == "--sumstats-cs-pep") o.ssCs.pep = need(i);
+        else if (a == "--sumstats-cs-lead") o.ssCs.lead = need(i);
+        else if (a == "--sumstats-cs-max-size") o.ssCs.maxSize = need(i);
+        else if (a == "--sumstats-cs-out") o.ssCs.out = need(i);
+        else if (a == "--cs") o.cs = true;
+        else if (a == "--cs-chains") o.csChains = need(i);
+        else if (a == "--cs-window-kb") {
+            o.csKb = need(i);
+            o.csKbGiven = true;
+        } else if (a == "--cs-window-snps") {
+            o.csSnps = need(i);
+            o.csSnpsGiven = true;
+        } else if (a == "--cs-r2") o.csArgs.r2 = need(i);
+        else if (a == "--cs-alpha") o.csArgs.alpha = need(i);
+        else if (a == "--cs-pep") o.csArgs.pep = need(i);
+        else if (a == "--cs-lead") o.csArgs.lead = need(i);
+        else if (a == "--cs-max-size") o.csArgs.maxSize = need(i);
+        else if (a == "--cs-out") o.csArgs.out = need(i);
         else if (a == "--predict-bfile") o.predictBfile = need(i);
         else if (a == "--predict-out") o.predictOut = need(i);
         else if (a == "--predict-dry-run") o.predictDryRun = true;
@@ -3912,12 +3948,13 @@ SumstatTable read_sumstats(const std::string& path, const BimRows& bim, unsigned
 }
 
 // --sumstats-post: which iterations are records, how many there are, and the table.
-bool post_counts(const Options& opt, unsigned iteration) { return iteration >= opt.burnin && (opt.sumstatsPostAll || iteration % opt.thin == 0); }
+// `all`: every iteration at or after --burn-in (--sumstats-post-all), not only the thinned ones
+bool post_counts(const Options& opt, unsigned iteration, bool all) { return iteration >= opt.burnin && (all || iteration % opt.thin == 0); }
 
-unsigned post_records(const Options& opt)
+unsigned post_records(const Options& opt, bool all)
 {
     if (opt.burnin >= opt.chainLength) return 0;
-    if (opt.sumstatsPostAll || opt.thin <= 1) return opt.chainLength - opt.burnin;
+    if (all || opt.thin <= 1) return opt.chainLength - opt.burnin;
     const unsigned first = (opt.burnin + opt.thin - 1) / opt.thin, last = (opt.chainLength - 1) / opt.thin; // multiples of --thin in [burn-in, length)
     return last >= first ? last - first + 1 : 0;
 }
@@ -3938,7 +3975,7 @@ PostJob post_job(const Options& opt, const std::string& base, const BimRows& bim
     PostJob p;
     p.on = opt.sumstatsPost;
     p.only = opt.sumstatsPostOnly;
-    p.T = post_records(opt);
+    p.T = post_records(opt, opt.sumstatsPostAll);
     p.path = opt.sumstatsPostOut.empty() ? base + ".post" : opt.sumstatsPostOut;
     p.bim = &bim;
     p.mstd = &mstd;
@@ -3986,6 +4023,143 @@ std::string post_report(const PostJob& p)
     char b[512];
     std::snprintf(b, sizeof b, ", %u records per chain counted on the device into %s (%.3f ms for all adds, %.3f ms for the table's kernel)", p.T, p.path.c_str(), p.add_ms,
                   p.final_ms);
+    return b;
+}
+
+// ---- local credible sets: what --sumstats-cs and --cs share ----
+// The sub-options of a route under its prefix ("--sumstats-cs", "--cs"): refused by name where they do not parse
+void check_cs_values(const std::string& prefix, const CsStrings& a)
+{
+    const struct { const char* opt; const std::string& t; const char* what; } unit[4] = {
+        {"-r2", a.r2, "the threshold on r^2"},
+        {"-alpha", a.alpha, "the sum of PIPs a set must reach"},
+        {"-pep", a.pep, "the posterior existence probability a set must have"},
+        {"-lead", a.lead, "the PIP a marker needs to lead a set"},
+    };
+    double v = 0.0;
+    for (const auto& u : unit)
+        if (!u.t.empty() && (!whole_num(u.t, v) || !(v > 0.0 && v <= 1.0)))
+            fatal("FATAL  : " + prefix + u.opt + " " + u.t + ": " + u.what + " must be a number in (0, 1]");
+    long k = 0;
+    if (!a.maxSize.empty() && (!whole_int(a.maxSize, k) || k < 1 || k > 256))
+        fatal("FATAL  : " + prefix + "-max-size " + a.maxSize + ": the largest set must be an integer from 1 to 256 markers (the most hgibbs_cs_sets takes)");
+}
+
+// a plan without a record: the history counts the thinned iterations at or after --burn-in
+void check_cs_plan(const std::string& flag, const Options& opt)
+{
+    if (post_records(opt, false) == 0)
+        fatal("FATAL  : " + flag + ": 0 records per chain (--chain-length " + std::to_string(opt.chainLength) + ", --burn-in " + std::to_string(opt.burnin) + ", --thin " +
+              std::to_string(opt.thin) + "): the history needs a thinned iteration at or after the burn-in");
+}
+
+// x of NREC records as a count: at least 1
+uint32_t cs_ceil(double x, uint64_t NREC) { return std::max<uint32_t>(1u, (uint32_t)std::ceil(x * (double)NREC)); }
+
+struct CsJob {
+    bool on = false;
+    double r2 = 0.5, alpha = 0.9, pep = 0.7, lead = 0.01;
+    uint32_t maxSize = 64;
+    std::string path;
+    uint32_t C = 1, T = 0; // the history's chains and records per chain
+    // what the five steps found
+    uint32_t nleads = 0, reached = 0, fell_short = 0, capped = 0, low_pep = 0, written = 0;
+    double add_ms = 0.0, mask_ms = 0.0, sets_ms = 0.0;
+};
+
+CsJob cs_job(bool on, const CsStrings& a, const std::string& dflt_path)
+{
+    CsJob c;
+    c.on = on;
+    c.r2 = num_or(a.r2, 0.5);
+    c.alpha = num_or(a.alpha, 0.9);
+    c.pep = num_or(a.pep, 0.7);
+    c.lead = num_or(a.lead, 0.01);
+    long k = 64;
+    if (!a.maxSize.empty()) whole_int(a.maxSize, k);
+    c.maxSize = (uint32_t)k;
+    c.path = a.out.empty() ? dflt_path : a.out;
+    return c;
+}
+
+// the table of the accepted sets, in the order taken
+void write_cs_table(FILE* f, const BimRows& bim, uint64_t NREC, const std::vector<uint32_t>& cnt, const std::vector<uint32_t>& leads, const std::vector<uint32_t>& size,
+                    const std::vector<uint64_t>& sum, const std::vector<uint32_t>& pep, const std::vector<uint32_t>& members, uint32_t max_size,
+                    const std::vector<uint32_t>& taken)
+{
+    std::fprintf(f, "CS\tLEAD\tCHR\tBP_FIRST\tBP_LAST\tSIZE\tNREC\tPIP_LEAD\tPIP_SUM\tPEP\tSNPS\tPIPS\n");
+    const double all = (double)NREC;
+    for (size_t k = 0; k < taken.size(); ++k) {
+        const uint32_t i = taken[k], v = leads[i];
+        const uint32_t* mem = &members[(size_t)i * max_size];
+        long long first = bim.bp[v], last = bim.bp[v];
+        for (uint32_t m = 0; m < size[i]; ++m) {
+            first = std::min(first, bim.bp[mem[m]]);
+            last = std::max(last, bim.bp[mem[m]]);
+        }
+        std::fprintf(f, "%zu\t%s\t%s\t%lld\t%lld\t%u\t%llu\t%.9g\t%.9g\t%.9g\t", k + 1, bim.id[v].c_str(), bim.chr[v].c_str(), first, last, size[i],
+                     (unsigned long long)NREC, (double)cnt[v] / all, (double)sum[i] / all, (double)pep[i] / all);
+        for (uint32_t m = 0; m < size[i]; ++m) std::fprintf(f, "%s%s", m ? "," : "", bim.id[mem[m]].c_str());
+        std::fprintf(f, "\t");
+        for (uint32_t m = 0; m < size[i]; ++m) std::fprintf(f, "%s%.9g", m ? "," : "", (double)cnt[mem[m]] / all);
+        std::fprintf(f, "\n");
+    }
+}
+
+// After the last add, while the handle stands: counts, leads, the LD mask on the run's window, the candidate sets, the walk, the table
+void cs_finish(CsJob& c, hgibbs_t dev, const BimRows& bim, const LdWindow& win, uint32_t W, unsigned M, FILE* f)
+{
+    const uint64_t NREC = (uint64_t)c.C * c.T;
+    std::vector<uint32_t> cnt(M);
+    hg_check(hgibbs_cs_counts(dev, cnt.data()), "hgibbs_cs_counts");
+    const uint32_t min_lead = cs_ceil(c.lead, NREC), need = cs_ceil(c.alpha, NREC), min_pep = cs_ceil(c.pep, NREC);
+    std::vector<uint32_t> leads, lead_cnt;
+    for (unsigned j = 0; j < M; ++j)
+        if (cnt[j] >= min_lead) {
+            leads.push_back(j);
+            lead_cnt.push_back(cnt[j]);
+        }
+    const uint32_t nlead = (uint32_t)leads.size();
+    const size_t nm = (size_t)M * ((W + 63u) / 64u);
+    std::vector<uint64_t> fwd(nm), bwd(nm);
+    hg_check(hgibbs_ld_mask(dev, W, win.ahead.data(), c.r2, fwd.data(), bwd.data(), nullptr), "hgibbs_ld_mask");
+    double products_ms = 0.0, reduce_ms = 0.0;
+    hg_check(hgibbs_last_ld_mask_ms(dev, &products_ms, &reduce_ms), "hgibbs_last_ld_mask_ms");
+    c.mask_ms = products_ms + reduce_ms;
+    std::vector<uint32_t> status(nlead), size(nlead), pep(nlead), members((size_t)nlead * c.maxSize), taken(nlead);
+    std::vector<uint64_t> sum(nlead);
+    hg_check(hgibbs_cs_sets(dev, W, fwd.data(), bwd.data(), nlead, leads.data(), need, c.maxSize, status.data(), size.data(), sum.data(), pep.data(), members.data()),
+             "hgibbs_cs_sets");
+    double counts_ms = 0.0;
+    hg_check(hgibbs_last_cs_ms(dev, &c.add_ms, &counts_ms, &c.sets_ms), "hgibbs_last_cs_ms");
+    hg_check(hgibbs_cs_end(dev), "hgibbs_cs_end");
+    uint32_t ntaken = 0;
+    hg_check(hgibbs_cs_select(M, nlead, leads.data(), lead_cnt.data(), status.data(), size.data(), pep.data(), members.data(), c.maxSize, min_pep, taken.data(), &ntaken),
+             "hgibbs_cs_select");
+    taken.resize(ntaken);
+    c.nleads = nlead;
+    for (uint32_t i = 0; i < nlead; ++i) {
+        c.reached += status[i] == 0u;
+        c.fell_short += status[i] == 1u;
+        c.capped += status[i] == 2u;
+        c.low_pep += status[i] == 0u && pep[i] < min_pep;
+    }
+    c.written = ntaken;
+    write_cs_table(f, bim, NREC, cnt, leads, size, sum, pep, members, c.maxSize, taken);
+    close_out(f, c.path);
+}
+
+// what the closing line gains with the credible sets
+std::string cs_report(const CsJob& c, unsigned M)
+{
+    if (!c.on) return "";
+    const uint64_t NREC = (uint64_t)c.C * c.T;
+    char b[768];
+    std::snprintf(b, sizeof b,
+                  ", credible sets from %llu records: %u leads, %u candidates reached alpha, %u ran short, %u hit the cap of %u markers, %u below the PEP bound, %u sets written to %s "
+                  "(history %llu bytes on the device; %.3f ms for all adds, %.3f ms for the LD mask, %.3f ms for the sets' kernel)",
+                  (unsigned long long)NREC, c.nleads, c.reached, c.fell_short, c.capped, c.maxSize, c.low_pep, c.written, c.path.c_str(),
+                  (unsigned long long)((NREC + 63u) / 64u * 8u * M), c.add_ms, c.mask_ms, c.sets_ms);
     return b;
 }
 
@@ -4055,7 +4229,7 @@ double write_rhat(const Options& opt, const std::string& rhatp, const std::vecto
 // md.seed + r in one launch per iteration, chain 0's files <base>.*, chain r's <base>.c<r>.*, and <base>.rhat; without it the one
 // chain of md.seed and the single chain's wording of the RESULT and the closing lines.
 void run_sumstats_chains(const Options& opt, hgibbs_t dev, const hydra_model_desc& md, const SumstatTable& tab, const LdWindow& win, uint32_t W, unsigned M, int G,
-                         const std::string& base, PostJob& post, unsigned used, unsigned nosd)
+                         const std::string& base, PostJob& post, CsJob& csj, unsigned used, unsigned nosd)
 {
     const bool many = opt.sumstatsChainsGiven;
     long R = 1, smax = 0;
@@ -4083,6 +4257,11 @@ void run_sumstats_chains(const Options& opt, hgibbs_t dev, const hydra_model_des
     double band_ms = 0.0, sweep_ms = 0.0;
     hg_check(hgibbs_last_ss_ms(dev, &band_ms, &sweep_ms), "hgibbs_last_ss_ms");
     if (post.on) hg_check(hgibbs_ss_post_begin(dev, many ? cs.R : 0u, post.T), "hgibbs_ss_post_begin"); // (0: the handle's own chain)
+    if (csj.on) { // the thinned iterations at or after --burn-in, whatever --sumstats-post-all says
+        csj.C = cs.R;
+        csj.T = post_records(opt, false);
+        hg_check(hgibbs_cs_begin(dev, csj.C, csj.T), "hgibbs_cs_begin");
+    }
     const bool effects = !(post.on && post.only); // --sumstats-post-only: no .bet, .cpn, .acu, and no download of a record
 
     // the chains' files and formats (:1302-1309, :2736-2794)
@@ -4111,7 +4290,8 @@ void run_sumstats_chains(const Options& opt, hgibbs_t dev, const hydra_model_des
         hg_check(hgibbs_last_ss_ms(dev, &band_ms, &sweep_ms), "hgibbs_last_ss_ms");
         sweep_total_ms += sweep_ms;
         ++sweeps;
-        if (post.on && post_counts(opt, iteration)) hg_check(hgibbs_ss_post_add(dev), "hgibbs_ss_post_add");
+        if (post.on && post_counts(opt, iteration, opt.sumstatsPostAll)) hg_check(hgibbs_ss_post_add(dev), "hgibbs_ss_post_add");
+        if (csj.on && post_counts(opt, iteration, false)) hg_check(hgibbs_ss_cs_add(dev, many ? cs.R : 0u), "hgibbs_ss_cs_add");
         for (long r = 0; r < R; ++r) {
             double sigmaE = 0, mu = 0;
             cs.state((uint32_t)r, &sigmaE, &mu, sigmaG.data(), m0.data());
@@ -4152,6 +4332,7 @@ void run_sumstats_chains(const Options& opt, hgibbs_t dev, const hydra_model_des
     }
     outs.close(true);
     if (post.on) write_post_table(post, dev, cs.R, M);
+    if (csj.on) cs_finish(csj, dev, *post.bim, win, W, M, open_out(csj.path, "wb+"));
     cs.destroy();
     const double max_rhat = many ? write_rhat(opt, base + ".rhat", rec, R, G) : 0.0;
     hgibbs_destroy(dev);
@@ -4166,9 +4347,64 @@ void run_sumstats_chains(const Options& opt, hgibbs_t dev, const hydra_model_des
     const double per_sweep = sweeps ? sweep_total_ms / sweeps : 0.0;
     if (many)
         std::printf("%u chains, %.3f ms per sweep launch (all chains) on the device over %u sweeps%s, largest R^ %s, wrote %s.%s, %s.c<r>.%s for the chains r >= 1 and %s.rhat%s\n",
-                    cs.R, per_sweep, sweeps, par, rh, base.c_str(), files, base.c_str(), files, base.c_str(), post_report(post).c_str());
+                    cs.R, per_sweep, sweeps, par, rh, base.c_str(), files, base.c_str(), files, base.c_str(), (post_report(post) + cs_report(csj, M)).c_str());
     else
-        std::printf("%.3f ms per sweep on the device over %u sweeps%s, wrote %s.%s%s\n", per_sweep, sweeps, par, base.c_str(), files, post_report(post).c_str());
+        std::printf("%.3f ms per sweep on the device over %u sweeps%s, wrote %s.%s%s\n", per_sweep, sweeps, par, base.c_str(), files, (post_report(post) + cs_report(csj, M)).c_str());
+}
+
+// ---- --cs: the credible sets of a finished chain, from its .bet records ----
+int run_cs(const Options& opt, const Cohort& co)
+{
+    const std::string base = opt.mcmcOutDir + "/" + opt.mcmcOutNam;
+    const std::string bimp = opt.bedFile + ".bim";
+    const unsigned M = co.Mtot;
+    const BimRows bim = read_bim(bimp, M);
+    long R = 1;
+    if (!opt.csChains.empty()) whole_int(opt.csChains, R);
+
+    // the pooled records at or after --burn-in: a marker is in the model iff its effect is not 0
+    std::vector<unsigned> its;
+    std::vector<double> betas;
+    for (long r = 0; r < R; ++r) {
+        const size_t before = its.size();
+        const std::string path = (r ? base + ".c" + std::to_string(r) : base) + ".bet";
+        read_bet_records(path, M, opt.burnin, its, betas, "--cs takes the inclusion history from the chain's effects");
+        if (its.size() == before) fatal("FATAL  : " + path + ": no record at or after --burn-in " + std::to_string(opt.burnin));
+    }
+    const size_t total = its.size();
+    if (total >= (1ull << 32)) fatal("FATAL  : --cs: " + std::to_string(total) + " records, the history takes fewer than 2^32");
+
+    // the window: kilobases (1000 unless markers are asked for), an index interval per chromosome
+    const bool bySnps = opt.csSnpsGiven;
+    long wsnps = 0;
+    if (bySnps) whole_int(opt.csSnps, wsnps);
+    const long long maxbp = (long long)std::llround(1000.0 * num_or(opt.csKb, 1000.0));
+    const LdWindow win = ld_window("--cs", "hgibbs_ld_mask", bim, bimp, M, bySnps, wsnps, maxbp, "--cs-window-snps");
+    const uint32_t W = std::max(1u, win.widest);
+
+    CsJob csj = cs_job(true, opt.csArgs, base + ".cs");
+    csj.C = 1;
+    csj.T = (uint32_t)total;
+    std::printf("CS     : %zu records at or after --burn-in %u from %ld chain(s) of %s, window %s, %llu pairs in the window, widest window %u markers ahead, r^2 >= %g -> %s\n",
+                total, opt.burnin, R, base.c_str(), win.what.c_str(), win.npairs, win.widest, csj.r2, csj.path.c_str());
+    std::fflush(stdout);
+
+    std::vector<uint8_t> bed = read_training(opt.bedFile, co.numInds, M);
+    if (opt.csArgs.out.empty()) make_out_dir(opt);
+    FILE* f = open_out(csj.path, "wb+");
+
+    hgibbs_t dev = open_training(co, bed);
+    hg_check(hgibbs_cs_begin(dev, csj.C, csj.T), "hgibbs_cs_begin");
+    std::vector<uint8_t> flags(M);
+    for (size_t q = 0; q < total; ++q) {
+        const double* b = &betas[q * M];
+        for (unsigned j = 0; j < M; ++j) flags[j] = b[j] != 0.0 ? 1 : 0;
+        hg_check(hgibbs_cs_add_flags(dev, flags.data()), "hgibbs_cs_add_flags");
+    }
+    cs_finish(csj, dev, bim, win, W, M, f);
+    hgibbs_destroy(dev);
+    std::printf("CS     : %u markers%s\n", M, cs_report(csj, M).c_str());
+    return 0;
 }
 
 int run_sumstats(const Options& opt, const Cohort& co, const std::vector<int32_t>& groups, const std::vector<double>& mS_flat, int G, int K)
@@ -4219,7 +4455,8 @@ int run_sumstats(const Options& opt, const Cohort& co, const std::vector<int32_t
     md.groups = groups.empty() ? nullptr : groups.data();
     md.mS = mS_flat.data();
     PostJob post = post_job(opt, base, bim, mstd, tab.use, K);
-    run_sumstats_chains(opt, dev, md, tab, win, W, M, G, base, post, used, nosd);
+    CsJob csj = cs_job(opt.sumstatsCs, opt.ssCs, base + ".cs");
+    run_sumstats_chains(opt, dev, md, tab, win, W, M, G, base, post, csj, used, nosd);
     return 0;
 }
 
@@ -4232,7 +4469,7 @@ struct Mode {
     const char* wmpi;   // how it refuses --mpibayes bayesWMPI, after its flag
     const char* orphan; // the first of its dependent options that was given: they need the mode (null: none was)
 };
-enum { PREDICT, LD, ASSOC, KING, PCA, PVE, GRM, LDSCORE, CLUMP, LDPRUNE, HE, QC, HOMOZYG, EPISTASIS, NMODES }; // the order in which a mode names the earlier ones it cannot be combined with
+enum { PREDICT, LD, ASSOC, KING, PCA, PVE, GRM, LDSCORE, CLUMP, LDPRUNE, HE, QC, HOMOZYG, EPISTASIS, CS, NMODES }; // the order in which a mode names the earlier ones it cannot be combined with
 
 const char* first_given(std::initializer_list<std::pair<const char*, bool>> deps)
 {
@@ -4382,6 +4619,16 @@ void check_qc_args(const Options& opt)
         fatal("FATAL  : --qc-het-sd " + opt.qcHetSd + ": the number of standard deviations must be a finite number > 0");
 }
 
+void check_cs_args(const Options& opt)
+{
+    long r = 0;
+    if (!opt.csChains.empty() && (!whole_int(opt.csChains, r) || r < 1 || r > 64))
+        fatal("FATAL  : --cs-chains " + opt.csChains + ": the number of chains must be an integer from 1 to 64 (the most --sumstats-chains writes)");
+    check_ldselect_window("--cs-window", opt.csKbGiven, opt.csKb, opt.csSnpsGiven, opt.csSnps);
+    check_cs_values("--cs", opt.csArgs);
+    check_cs_plan("--cs", opt);
+}
+
 void check_homozyg_args(const Options& opt)
 {
     (void)homozyg_args(opt); // refuses by name what is out of range
@@ -4430,8 +4677,12 @@ void check_modes(const Options& opt, int nranks)
         {"--epistasis", opt.epistasis, takes,
          first_given({{"--epistasis-chisq", !opt.epiChisq.empty()}, {"--epistasis-sets", !opt.epiSets.empty()}, {"--epistasis-gap", !opt.epiGap.empty()},
                       {"--epistasis-out", !opt.epiOut.empty()}})},
+        {"--cs", opt.cs, takes,
+         first_given({{"--cs-chains", !opt.csChains.empty()}, {"--cs-window-kb", opt.csKbGiven}, {"--cs-window-snps", opt.csSnpsGiven}, {"--cs-r2", !opt.csArgs.r2.empty()},
+                      {"--cs-alpha", !opt.csArgs.alpha.empty()}, {"--cs-pep", !opt.csArgs.pep.empty()}, {"--cs-lead", !opt.csArgs.lead.empty()},
+                      {"--cs-max-size", !opt.csArgs.maxSize.empty()}, {"--cs-out", !opt.csArgs.out.empty()}})},
     };
-    for (const int i : {LD, PREDICT, ASSOC, KING, PCA, PVE, GRM, LDSCORE, CLUMP, LDPRUNE, HE, QC, HOMOZYG, EPISTASIS}) {
+    for (const int i : {LD, PREDICT, ASSOC, KING, PCA, PVE, GRM, LDSCORE, CLUMP, LDPRUNE, HE, QC, HOMOZYG, EPISTASIS, CS}) {
         const Mode& m = modes[i];
         const std::string flag = m.flag;
         if (!m.given) {
@@ -4457,6 +4708,7 @@ void check_modes(const Options& opt, int nranks)
         if (i == QC) check_qc_args(opt);
         if (i == HOMOZYG) check_homozyg_args(opt);
         if (i == EPISTASIS) (void)epistasis_args(opt); // refuses by name what is out of range
+        if (i == CS) check_cs_args(opt);
     }
 }
 
@@ -4466,26 +4718,35 @@ void check_sumstats(const Options& opt, int nranks)
     if (!opt.sumstats) {
         if (const char* o = first_given({{"--sumstats-window", opt.sumstatsWindowGiven}, {"--sumstats-window-kb", opt.sumstatsKbGiven}, {"--sumstats-n", opt.sumstatsNGiven},
                                           {"--sumstats-streams", opt.sumstatsStreamsGiven}, {"--sumstats-chains", opt.sumstatsChainsGiven},
-                                          {"--sumstats-post", opt.sumstatsPost}}))
+                                          {"--sumstats-post", opt.sumstatsPost}, {"--sumstats-cs", opt.sumstatsCs}}))
             fatal(std::string("FATAL  : ") + o + " needs --sumstats");
     }
+    if (!opt.sumstatsCs)
+        if (const char* o = first_given({{"--sumstats-cs-r2", !opt.ssCs.r2.empty()}, {"--sumstats-cs-alpha", !opt.ssCs.alpha.empty()}, {"--sumstats-cs-pep", !opt.ssCs.pep.empty()},
+                                          {"--sumstats-cs-lead", !opt.ssCs.lead.empty()}, {"--sumstats-cs-max-size", !opt.ssCs.maxSize.empty()},
+                                          {"--sumstats-cs-out", !opt.ssCs.out.empty()}}))
+            fatal(std::string("FATAL  : ") + o + " needs --sumstats-cs");
     if (!opt.sumstatsPost)
         if (const char* o = first_given({{"--sumstats-post-all", opt.sumstatsPostAll}, {"--sumstats-post-only", opt.sumstatsPostOnly},
                                           {"--sumstats-post-out", !opt.sumstatsPostOut.empty()}}))
             fatal(std::string("FATAL  : ") + o + " needs --sumstats-post");
     if (!opt.sumstats) return;
     if (opt.sumstatsPost) {
-        const unsigned T = post_records(opt);
+        const unsigned T = post_records(opt, opt.sumstatsPostAll);
         if (T < 4)
             fatal("FATAL  : --sumstats-post: T = " + std::to_string(T) + " record(s) per chain (--chain-length " + std::to_string(opt.chainLength) + ", --burn-in " +
                   std::to_string(opt.burnin) + ", --thin " + std::to_string(opt.thin) + (opt.sumstatsPostAll ? ", every iteration at or after the burn-in" : ", the thinned iterations at or after the burn-in") +
                   "): split-R^ of the halved chains needs at least 4");
     }
+    if (opt.sumstatsCs) {
+        check_cs_values("--sumstats-cs", opt.ssCs);
+        check_cs_plan("--sumstats-cs", opt);
+    }
     if (opt.bayesType == "bayesWMPI") fatal("FATAL  : --sumstats takes a bayesMPI command line, not --mpibayes bayesWMPI");
     const std::pair<const char*, bool> modes[] = {
         {"--predict-bfile", !opt.predictBfile.empty()}, {"--ld-window", opt.ldGiven}, {"--assoc", opt.assoc}, {"--king", opt.king}, {"--pca", opt.pca}, {"--pve", opt.pve},
         {"--grm", opt.grm}, {"--ld-score", opt.ldScore}, {"--clump", opt.clump}, {"--ld-prune", opt.ldPrune}, {"--he", opt.he}, {"--qc", opt.qc}, {"--homozyg", opt.homozyg},
-        {"--epistasis", opt.epistasis}};
+        {"--epistasis", opt.epistasis}, {"--cs", opt.cs}};
     for (const auto& m : modes)
         if (m.second) fatal(std::string("FATAL  : --sumstats cannot be combined with ") + m.first + ": it samples a chain, the analysis modes sample nothing");
     if (opt.covariates) fatal("FATAL  : --sumstats cannot be combined with --covariates: summary statistics carry no individual-level covariates");
@@ -4583,6 +4844,7 @@ int main(int argc, const char* argv[])
     if (opt.qc) return run_qc(opt, co);
     if (opt.homozyg) return run_homozyg(opt, co);
     if (opt.epistasis) return run_epistasis(opt, co, y);
+    if (opt.cs) return run_cs(opt, co);
 
     const Mixtures mix = read_mixtures(opt, Mtot, true);
     const int G = mix.G, K = mix.K;

@@ -552,6 +552,51 @@ int hgibbs_ss_post_raw(hgibbs_t h, uint32_t r, uint32_t half, double* hmean, dou
 int hgibbs_ss_post_end(hgibbs_t h);
 int hgibbs_last_ss_post_ms(hgibbs_t h, double* add_ms, double* final_ms);
 
+/* ---- local credible sets from the chains' inclusion history, kept on the device ---- */
+/* One bit per marker and record, kept where the chains' state lies; counts, candidate sets and their posterior existence probabilities
+ * (PEP) come from it with bit operations: exact integers, no record over the bus.  Everything below is integer.
+ *   history   a state is opened for C chains x T planned records, NREC = C T < 2^32.  Record q = t C + r (t adds so far, chain r);
+ *             marker j's bit q is 1 iff it is in the model in that record.  hist[(q / 64) M + j] bit q % 64; NW = (NREC + 63) / 64 words
+ *             per marker; every bit at or above the records added so far is 0.  cnt[j] = the popcount of marker j's words.
+ *   cs_begin  allocates and zeroes the history.  A second call replaces the first's state; hgibbs_destroy frees it; hgibbs_ss_end does
+ *             not (the state does not depend on the ss state).  Refused by name: a null handle or no genotypes, several ranks, C = 0,
+ *             T = 0, C T >= 2^32, memory that does not fit (with M, NREC and the bytes).
+ *   adds      cs_add_flags (flags: C x M bytes, non-zero = in the model) and ss_cs_add (chain r's component != 0; R as
+ *             hgibbs_ss_post_begin's: 0 the handle's own ss chain, >= 1 the replicas) each add ONE record of every chain: one launch, a
+ *             thread per marker, plain loads and stores.  ss_cs_add reads the chains' state and writes none of it.  Refused by name:
+ *             before cs_begin, beyond T, null flags; ss_cs_add without ss state, R >= 1 without replicas or another R than allocated,
+ *             max(R, 1) != C.
+ *   cs_counts, cs_history, cs_sets  may be called after any number of adds and describe the records added so far (NREC = t C).
+ *             cs_history always copies the whole NW x M words.
+ *   cs_sets   masks fwd, bwd in hgibbs_ld_mask's layout for window width W (wpr = (W + 63) / 64): marker v + d is a friend of lead v iff
+ *             bit d - 1 of v's forward row is set, marker v - d iff bit d - 1 of its backward row is; bits of offsets above W and of
+ *             markers that do not exist are ignored.  Per lead v: members = [v], sum = cnt[v]; while sum < need: with max_size members
+ *             the set fails with status 2 (cap); otherwise the friend not yet taken with the largest cnt > 0, ties to the smallest
+ *             index, is appended and its cnt added; if there is none the set fails with status 1 (short).  On success (status 0) size =
+ *             the number of members and pep = the popcount of the OR of the members' history words.  A failed candidate reports size 0,
+ *             pep 0 and the sum it reached.  members is nlead x max_size; the slots from `size` on hold 0xFFFFFFFF (all of a failed
+ *             candidate's).  The results do not depend on the order of the leads or on how they are split over calls.  Refused by
+ *             name: no open state, W outside 1..4096, null masks, a lead >= M, a lead listed twice, need = 0, max_size outside 1..256.
+ *   last_cs_ms  the sum of all add kernels since cs_begin, the last counts kernel, the last sets kernel (the latter two 0 after a
+ *             refused call of theirs); all 0 without a state. */
+int hgibbs_cs_begin(hgibbs_t h, uint32_t C, uint32_t T);
+int hgibbs_cs_add_flags(hgibbs_t h, const uint8_t* flags /* C x M, non-zero = in the model */);
+int hgibbs_ss_cs_add(hgibbs_t h, uint32_t R);
+int hgibbs_cs_counts(hgibbs_t h, uint32_t* cnt /* M */);
+int hgibbs_cs_history(hgibbs_t h, uint64_t* out /* NW x M */);
+int hgibbs_cs_sets(hgibbs_t h, uint32_t W, const uint64_t* fwd, const uint64_t* bwd, uint32_t nlead, const uint32_t* leads,
+                   uint32_t need, uint32_t max_size, uint32_t* status, uint32_t* size, uint64_t* sum, uint32_t* pep,
+                   uint32_t* members /* nlead x max_size */);
+int hgibbs_cs_end(hgibbs_t h);
+int hgibbs_last_cs_ms(hgibbs_t h, double* add_ms, double* counts_ms, double* sets_ms);
+/* The walk over hgibbs_cs_sets' candidates (host only: no handle, no device): by descending lead_cnt, ties by ascending lead index
+ * (std::stable_sort); a candidate is accepted iff its status is 0, its pep >= min_pep and none of its members belongs to a set accepted
+ * before it.  taken[0 .. *ntaken) are the accepted candidates' positions in the order taken: the sets are disjoint.  Refused by name:
+ * null pointers, max_size outside 1..256, a size above max_size, a member >= M inside a size. */
+int hgibbs_cs_select(uint32_t M, uint32_t nlead, const uint32_t* leads, const uint32_t* lead_cnt, const uint32_t* status,
+                     const uint32_t* size, const uint32_t* pep, const uint32_t* members, uint32_t max_size, uint32_t min_pep,
+                     uint32_t* taken /* nlead */, uint32_t* ntaken);
+
 /* Convergence of R chains of one scalar (host only): x is R x T, chain-major.  mean and sd over all R T draws; rhat: split-R^ (BDA3
  * section 11.4: every chain halved, an odd T drops the middle draw; no rank normalisation); ess: from the same 2 R half-chains'
  * combined autocovariances, truncated by Geyer's initial monotone positive sequence (Stan reference manual), at most

@@ -25,8 +25,16 @@ section 34) and downloads every chain's effects, components and acum as the comm
 unless told otherwise): the device time of an add beside the replica launch of the same iteration, the bytes the add kernel moves and
 the bandwidth that implies, the table's kernel, and the host's wall time of an iteration with the downloads and without them.
 
+--cs (with --chains, not with --post) opens the inclusion history beside the posterior accumulators (hgibbs_cs_begin, DESIGN.md section
+35) and folds every iteration into both, the calls alternating: per R one record in --cs-out (profiles/ss_cs_bench.jsonl unless told
+otherwise) with the device time of one hgibbs_ss_cs_add beside one hgibbs_ss_post_add and beside the replica launch of the same
+iteration.  Then, on the same handle, hgibbs_ld_mask at r^2 >= --cs-r2 (the synthetic markers are independent: the default 1e-4 is
+about 1 / N, so that a third of the window's pairs pass and a lead has friends), and hgibbs_cs_sets for 10^4 random leads on a
+history of 40 x 100 = 4000 records of random flags (each marker in 2 % of the records), need = 0.9 NREC, at most 64 members.
+
     python tools/ss_bench.py [--cases 10000x100000x128,20000x1000000x512] [--n-eff 4000000] [--signals 0.001] [--iters 6] [--out F]
                              [--chromosomes C] [--streams S] [--chains R[,R...]] [--chains-iters I] [--chains-out F] [--post] [--post-out F]
+                             [--cs] [--cs-out F] [--cs-r2 T]
 """
 import argparse
 import json
@@ -68,12 +76,18 @@ def main():
     ap.add_argument("--chains-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "ss_chains_bench.jsonl"))
     ap.add_argument("--post", action="store_true", help="with --chains: time hgibbs_ss_post_add and the per-record downloads it can replace (at least 4 iterations)")
     ap.add_argument("--post-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "ss_post_bench.jsonl"))
+    ap.add_argument("--cs", action="store_true", help="with --chains: time hgibbs_ss_cs_add beside hgibbs_ss_post_add, then hgibbs_ld_mask and hgibbs_cs_sets (at least 4 iterations)")
+    ap.add_argument("--cs-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "ss_cs_bench.jsonl"))
+    ap.add_argument("--cs-r2", type=float, default=1e-4, help="the threshold of the mask the sets are timed on")
     ap.add_argument("--label", default=None, help="a word copied into every record (which build, which run)")
     args = ap.parse_args()
     out = open(args.out, "a") if args.out else None
     chains = [int(x) for x in args.chains.split(",") if x]
     chains_out = open(args.chains_out, "a") if chains else None
     post_out = open(args.post_out, "a") if chains and args.post else None
+    if args.cs and args.post:
+        ap.error("--cs and --post each open the posterior accumulators: one at a time")
+    cs_out = open(args.cs_out, "a") if chains and args.cs else None
 
     def emit(rec):
         line = json.dumps(rec)
@@ -155,6 +169,10 @@ def main():
                 dev.ss_post_begin(R, T)
                 beta, acum, comp = np.zeros(M), np.zeros(M), np.zeros(M, dtype=np.int32)
                 added = 0.0
+            if args.cs:
+                dev.ss_post_begin(R, T)
+                dev.cs_begin(R, T)
+                cits = []
             for it in range(T):
                 t0 = time.perf_counter()
                 mc.iterate()
@@ -171,6 +189,48 @@ def main():
                     pits.append({"it": it, "launch_ms": its[-1]["launch_ms"], "iterate_wall_ms": round(wall, 3), "add_ms": round(total - added, 4),
                                  "add_wall_ms": round(1e3 * (t2 - t1), 3), "download_wall_ms": round(1e3 * (t3 - t2), 3)})
                     added = total
+                if args.cs:  # the two adds alternate on the one handle
+                    p0, c0 = dev.last_ss_post_ms()[0], dev.last_cs_ms()[0]
+                    dev.ss_post_add()
+                    dev.ss_cs_add(R)
+                    cits.append({"it": it, "launch_ms": its[-1]["launch_ms"], "post_add_ms": round(dev.last_ss_post_ms()[0] - p0, 4),
+                                 "cs_add_ms": round(dev.last_cs_ms()[0] - c0, 4)})
+            if args.cs:
+                med = {k: float(np.median([x[k] for x in cits])) for k in ("launch_ms", "post_add_ms", "cs_add_ms")}
+                in_model = dev.cs_counts()
+                dev.ss_post_end()
+                fwd, bwd, npass = dev.ld_mask(W, args.cs_r2, ahead=ahead)
+                mask_ms = dev.last_ld_mask_ms()
+                # the sets' kernel on a history of its own: 40 chains x 100 records, a block of random flags shifted from record to record
+                CC, TT, nlead, max_size = 40, 100, min(10000, M), 64
+                nrec = CC * TT
+                dev.cs_begin(CC, TT)
+                block = (rs.random((CC, M)) < 0.02).astype(np.uint8)
+                for t in range(TT):
+                    dev.cs_add_flags(np.roll(block, 9973 * t, axis=1))
+                cnt = dev.cs_counts()
+                leads = np.sort(rs.choice(M, nlead, replace=False)).astype(np.uint32)
+                need = int(np.ceil(0.9 * nrec))
+                status, size, total, pep, members = dev.cs_sets(W, fwd, bwd, leads, need, max_size)
+                add_ms, counts_ms, sets_ms = dev.last_cs_ms()
+                dev.cs_end()
+                words = (R + 63) // 64 + 1  # at most: the words one record's R bits touch
+                crec_cs = {"kind": "cs", "n_panel": N, "m": M, "W": W, "chains": R, "records": T, "launch_ms_median": round(med["launch_ms"], 3),
+                           "post_add_ms_median": round(med["post_add_ms"], 4), "cs_add_ms_median": round(med["cs_add_ms"], 4),
+                           "cs_add_to_post_add": round(med["cs_add_ms"] / med["post_add_ms"], 4), "cs_add_bytes_at_most": int(M * (4 * R + 16 * words)),
+                           "history_bytes": int((R * T + 63) // 64 * 8 * M), "markers_ever_in_the_model": int(np.count_nonzero(in_model)),
+                           "mask_r2": args.cs_r2, "mask_pairs_passing": int(npass), "mask_products_ms": round(mask_ms[0], 3), "mask_reduce_ms": round(mask_ms[1], 3),
+                           "sets_nrec": nrec, "sets_leads": int(nlead), "sets_need": need, "sets_max_size": max_size, "sets_history_add_ms_mean": round(add_ms / TT, 4),
+                           "sets_counts_ms": round(counts_ms, 4), "sets_ms": round(sets_ms, 3), "sets_reached": int(np.count_nonzero(status == 0)),
+                           "sets_short": int(np.count_nonzero(status == 1)), "sets_capped": int(np.count_nonzero(status == 2)),
+                           "sets_mean_size": round(float(size[status == 0].mean()), 2) if np.any(status == 0) else None,
+                           "sets_mean_cnt": round(float(cnt.mean()), 2), "iterations": cits}
+                for k in ("chromosomes", "streams_max", "streams", "largest_interval", "label"):
+                    if k in rec:
+                        crec_cs[k] = rec[k]
+                emit(crec_cs)
+                cs_out.write(json.dumps(crec_cs) + "\n")
+                cs_out.flush()
             if args.post:
                 t1 = time.perf_counter()
                 mean, sd, pip, cnt, rhat = dev.ss_post_get()
