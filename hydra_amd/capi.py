@@ -44,6 +44,7 @@ ABI_SYMBOLS = [
     "hgibbs_pca", "hgibbs_last_pca_ms", "hgibbs_region_var", "hgibbs_last_region_var_ms",
     "hgibbs_grm", "hgibbs_grm_info", "hgibbs_last_grm_ms",
     "hgibbs_grm_rowsums", "hgibbs_last_grm_rowsums_ms", "hgibbs_he_fit",
+    "hgibbs_reml_solve", "hgibbs_reml_eval", "hgibbs_reml", "hgibbs_reml_next", "hgibbs_reml_finish", "hgibbs_last_reml_ms",
     "hgibbs_row_sums", "hgibbs_last_row_sums_ms", "hgibbs_hwe_exact",
     "hgibbs_sparse_begin", "hgibbs_sparse_put", "hgibbs_sparse_end", "hgibbs_sparse_counts", "hgibbs_sparse_get", "hgibbs_last_sparse_ms",
     # BayesW
@@ -123,6 +124,26 @@ class HeForm(C.Structure):
 
 class HeResult(C.Structure):
     _fields_ = [("n_used", C.c_uint32), ("n_left_out", C.c_uint32), ("pairs", C.c_uint64), ("vp", C.c_double), ("cp", HeForm), ("sd", HeForm)]
+
+
+class RemlEstimate(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("logdelta", "delta", "vg", "ve", "vp", "h2", "se_vg", "se_ve", "se_vp", "se_h2", "se_mc", "se_logdelta_mc")]
+
+
+class RemlOpts(C.Structure):
+    _fields_ = [("trials", C.c_int), ("h2_start", C.c_double), ("cg_tol", C.c_double), ("cg_iters", C.c_int), ("x_tol", C.c_double),
+                ("max_steps", C.c_int), ("seed", C.c_uint64)]
+
+
+class RemlResult(C.Structure):
+    _fields_ = [("status", C.c_int), ("steps", C.c_int), ("x", C.c_double * 32), ("f", C.c_double * 32), ("cg_iters", C.c_int * 32),
+                ("sums_prev", C.c_double * 96), ("sums_last", C.c_double * 96), ("ai3", C.c_double * 3), ("ai_cg_iters", C.c_int),
+                ("est", RemlEstimate), ("n", C.c_uint32), ("m_used", C.c_uint32), ("q", C.c_int), ("trials", C.c_int),
+                ("products_ms", C.c_double), ("algebra_ms", C.c_double)]
+
+
+REML_CONTINUE, REML_CONVERGED, REML_AT_BOUND = 0, 1, 2
+REML_STATUS = {REML_CONTINUE: "CONTINUE", REML_CONVERGED: "CONVERGED", REML_AT_BOUND: "AT_BOUND"}
 
 
 class SparseList(C.Structure):
@@ -374,6 +395,13 @@ def lib():
     L.hgibbs_grm_rowsums.argtypes = [vp, C.c_int, dp, dp, dp, dp, dp, u32p]
     L.hgibbs_last_grm_rowsums_ms.argtypes = [vp, dp, dp]
     L.hgibbs_he_fit.argtypes = [C.c_uint32, dp, dp, dp, dp, dp, u32p, C.POINTER(HeResult)]
+    ip = C.POINTER(C.c_int)
+    L.hgibbs_reml_solve.argtypes = [vp, C.c_int, C.c_int, dp, C.c_double, C.c_double, C.c_int, dp, dp, ip, dp]
+    L.hgibbs_reml_eval.argtypes = [vp, C.c_int, C.c_int, dp, dp, C.c_uint64, C.c_double, C.c_double, C.c_int, dp, ip]
+    L.hgibbs_reml.argtypes = [vp, C.POINTER(RemlOpts), C.c_int, dp, dp, C.POINTER(RemlResult), dp]
+    L.hgibbs_reml_next.argtypes = [C.c_int, dp, dp, C.c_double, C.c_double, C.c_int, dp, ip]
+    L.hgibbs_reml_finish.argtypes = [C.c_int, C.c_uint32, C.c_int, dp, dp, dp, dp, C.POINTER(RemlEstimate)]
+    L.hgibbs_last_reml_ms.argtypes = [vp, dp, dp]
     L.hgibbs_row_sums.argtypes = [vp, C.c_int, dp, dp]
     L.hgibbs_last_row_sums_ms.argtypes = [vp, dp]
     sl = C.POINTER(SparseList)
@@ -575,6 +603,33 @@ def he_fit(y, ay, ayy, a1, a2, partners):
     for form in ("cp", "sd"):
         out[form] = {k: getattr(getattr(res, form), k) for k, _ in HeForm._fields_}
     return out
+
+
+def reml_next(x, f, h2_start=0.25, x_tol=0.01, max_steps=12):
+    """hgibbs_reml_next (host only): the root rule of --reml on x = log delta from the points evaluated so far.  Returns (x_next,
+    status): REML_CONTINUE to evaluate x_next, REML_CONVERGED or REML_AT_BOUND when x[-1] is the estimate.  A flat f or max_steps
+    evaluations without a root raise."""
+    xs = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+    fs = np.ascontiguousarray(f, dtype=np.float64).reshape(-1)
+    if xs.size != fs.size:
+        raise ValueError("reml_next: x and f must have one length")
+    xn, st = C.c_double(), C.c_int()
+    check(lib().hgibbs_reml_next(xs.size, _dp(xs), _dp(fs), float(h2_start), float(x_tol), int(max_steps), C.byref(xn), C.byref(st)))
+    return xn.value, st.value
+
+
+def reml_finish(n, q, x2, sums_prev, sums_last, ai3=None):
+    """hgibbs_reml_finish (host only): the estimate at x2[1] from the sums ((T + 1, 3)) of the last two evaluations and, with ai3 =
+    (a'z1, a'z2, v'z2), the standard errors of the average-information matrix.  Returns a dict of hgibbs_reml_estimate's fields."""
+    sp = np.ascontiguousarray(sums_prev, dtype=np.float64).reshape(-1)
+    sl = np.ascontiguousarray(sums_last, dtype=np.float64).reshape(-1)
+    if sp.size != sl.size or sp.size % 3 or sp.size < 6:
+        raise ValueError("reml_finish: the sums must be (T + 1, 3) each")
+    xx = np.ascontiguousarray(x2, dtype=np.float64).reshape(2)
+    ai = np.ascontiguousarray(ai3, dtype=np.float64).reshape(3) if ai3 is not None else None
+    est = RemlEstimate()
+    check(lib().hgibbs_reml_finish(sp.size // 3 - 1, int(n), int(q), _dp(xx), _dp(sp), _dp(sl), _dp(ai) if ai is not None else None, C.byref(est)))
+    return {k: getattr(est, k) for k, _ in RemlEstimate._fields_}
 
 
 def hwe_exact(n_het, n_hom_a, n_hom_b):
@@ -1287,6 +1342,69 @@ class Device:
                                 _dp(val), _dp(pcs), _dp(ld) if loadings else None, C.byref(rep)))
         return val, pcs, ld, {"iters_run": rep.iters_run, "m_used": rep.m_used, "ritz_change": rep.ritz_change,
                               "resid": np.array(rep.resid[:kk], dtype=np.float64)}
+
+    def _reml_z(self, Z):
+        """the design (n_local, q), the column of ones included, as the q x n_local the library takes"""
+        z = np.asarray(Z, dtype=np.float64)
+        if z.ndim != 2 or z.shape[0] != self.n_local:
+            raise ValueError("Z must be (%d, q)" % self.n_local)
+        return np.ascontiguousarray(z.T)
+
+    def reml_solve(self, B, Z, delta, tol=1e-5, max_iters=200):
+        """hgibbs_reml_solve: V[k] = H(delta)^-1 P_c B[k] for the K rows of B (K, n_local) by conjugate gradients, H = P_c A P_c +
+        delta I with A = X X'/M_used and P_c the projection off the columns of Z (n_local, q).  Returns V (K, n_local), the iterations
+        (K,) and the recurrence's relative residuals (K,)."""
+        b = np.ascontiguousarray(B, dtype=np.float64)
+        if b.ndim != 2 or b.shape[1] != self.n_local:
+            raise ValueError("B must be (K, %d)" % self.n_local)
+        z = self._reml_z(Z)
+        K = b.shape[0]
+        V = np.zeros((K, self.n_local))
+        iters = np.zeros(max(K, 1), dtype=np.intc)
+        rel = np.zeros(max(K, 1))
+        check(self.L.hgibbs_reml_solve(self.h, K, z.shape[0], _dp(z), float(delta), float(tol), int(max_iters), _dp(b), _dp(V),
+                                       iters.ctypes.data_as(C.POINTER(C.c_int)), _dp(rel)))
+        return V, iters[:K].astype(np.int64), rel[:K]
+
+    def reml_eval(self, y, Z, delta, trials=15, seed=1, tol=1e-5, max_iters=200):
+        """hgibbs_reml_eval: the sums (trials + 1, 3) of vAv, vv, vb at delta from `trials` sign probes and y, and the largest
+        iteration count of the solve."""
+        z = self._reml_z(Z)
+        yy = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+        if yy.size != self.n_local:
+            raise ValueError("y must have %d entries" % self.n_local)
+        T = int(trials)
+        sums = np.zeros((max(T, 0) + 1, 3))
+        it = C.c_int()
+        check(self.L.hgibbs_reml_eval(self.h, T, z.shape[0], _dp(z), _dp(yy), int(seed) & (2 ** 64 - 1), float(delta), float(tol), int(max_iters),
+                                      _dp(sums), C.byref(it)))
+        return sums, it.value
+
+    def reml(self, y, Z, trials=15, h2_start=0.25, cg_tol=1e-5, cg_iters=200, x_tol=0.01, max_steps=12, seed=1, blup=False):
+        """hgibbs_reml: the REML estimate of h2 of the loaded rows without the relationship matrix.  Returns a dict: status (a
+        REML_* value), steps, the trace x, f, cg_iters (steps,), sums_prev and sums_last (trials + 1, 3), ai3, ai_cg_iters, the
+        estimate's fields (logdelta, delta, vg, ve, vp, h2, se_*), n, m_used, q, trials, products_ms, algebra_ms, and blup (M,) or None."""
+        z = self._reml_z(Z)
+        yy = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+        if yy.size != self.n_local:
+            raise ValueError("y must have %d entries" % self.n_local)
+        opt = RemlOpts(int(trials), float(h2_start), float(cg_tol), int(cg_iters), float(x_tol), int(max_steps), int(seed) & (2 ** 64 - 1))
+        res = RemlResult()
+        bl = np.zeros(self.M) if blup else None
+        check(self.L.hgibbs_reml(self.h, C.byref(opt), z.shape[0], _dp(z), _dp(yy), C.byref(res), _dp(bl) if blup else None))
+        k, T1 = res.steps, res.trials + 1
+        out = {"status": res.status, "steps": k, "x": np.array(res.x[:k]), "f": np.array(res.f[:k]), "cg_iters": np.array(res.cg_iters[:k], dtype=np.int64),
+               "sums_prev": np.array(res.sums_prev[:3 * T1]).reshape(T1, 3), "sums_last": np.array(res.sums_last[:3 * T1]).reshape(T1, 3),
+               "ai3": np.array(res.ai3[:3]), "ai_cg_iters": res.ai_cg_iters, "n": res.n, "m_used": res.m_used, "q": res.q, "trials": res.trials,
+               "products_ms": res.products_ms, "algebra_ms": res.algebra_ms, "blup": bl}
+        out.update({k2: getattr(res.est, k2) for k2, _ in RemlEstimate._fields_})
+        return out
+
+    def last_reml_ms(self):
+        """(products ms, algebra ms) of the last reml_solve() / reml_eval() / reml()"""
+        a, b = C.c_double(), C.c_double()
+        check(self.L.hgibbs_last_reml_ms(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def last_pca_ms(self):
         """Device ms of the last pca(): whole call, X'Q products, X T products, panel algebra of the iterations."""

@@ -226,6 +226,7 @@ struct hgibbs_ctx : Problem {
     int rvar_kb_max = 0;   // option rvar_kb_max: a marker set of more blocks of 64 than this takes hgibbs_region_var's large-set path (0 = SC_KB_MAX)
     double rvar_ms = 0.0;  // device time of the last hgibbs_region_var (scales, digits, products and epilogue, the large sets' scores, mean and var)
     double pca_ms[5] = {0, 0, 0, 0, 0}; // device time of the last hgibbs_pca: whole call, X'Q products, X T products, panel algebra of the iterations, the rest
+    double reml_ms[2] = {0, 0}; // device time of the last hgibbs_reml_solve / _eval / hgibbs_reml: the X'P and X T products, every other kernel
     std::vector<uint32_t> king_ab;    // the last hgibbs_king_pairs list, sorted by (a, b): a, b per pair
     std::vector<int32_t> king_counts; // NSNP, HET_a, HET_b, HETHET, IBS0 per pair
     std::vector<double> king_kin;     // KINSHIP per pair
@@ -2224,6 +2225,7 @@ int hgibbs_sweep(hgibbs_t h, const int32_t* order_host, double sigmaE, const dou
 #include "hg_roh.hip.h"
 #include "hg_pairtab.hip.h"
 #include "hg_pca.hip.h"
+#include "hg_reml.hip.h"
 #include "hg_grm.hip.h"
 #include "hg_grmsums.hip.h"
 #include "hg_sparse.hip.h"

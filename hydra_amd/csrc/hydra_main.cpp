@@ -79,6 +79,13 @@
 // DESIGN.md section 22).  <dir>/<name>.HEreg (or F) has the layout of GCTA's --HEreg; with --he-rows <out>.rows has the per-row sums.
 // Not covered: bivariate HE, several matrices, REML.
 //
+// `--reml [--reml-trials T] [--reml-h2-start H] [--reml-cg-tol E] [--reml-cg-iters I] [--reml-tol X] [--reml-out F] [--reml-blup]` appended
+// to a bayesMPI command line samples nothing either: the REML estimate of the SNP heritability of the same phenotype as --he, with
+// [1 | covariates] as fixed effects, without ever forming the relationship matrix (run_reml): T sign probes seeded
+// by --seed, a batched conjugate-gradient solve on the marker-dots and score pipelines, a secant search on log delta.
+// <dir>/<name>.reml (or F) has the shape of GCTA's .hsq, then `key value` lines; --reml-blup adds <out>.blup with the marker effects.
+// Not covered: several variance components, bivariate REML, LOCO, a likelihood value.  No parity with GCTA or BOLT is claimed.
+//
 // `--qc [--qc-out PREFIX] [--qc-maf X] [--qc-geno X] [--qc-mind X] [--qc-hwe P] [--qc-het-sd K]` appended to a bayesMPI command line samples
 // nothing either: the quality control that comes before everything else, on the chain's rows.  Per marker, from the counts of
 // hgibbs_marker_stats: allele frequency (.frq), call rate (.lmiss) and the exact Hardy-Weinberg test of hgibbs_hwe_exact (.hwe); per
@@ -201,6 +208,8 @@ struct Options { // src/options.hpp:20-138 (subset that reaches bayesMPI)
     std::string grmOut, grmSparse;                   // --grm-out PREFIX, --grm-sparse T as given (checked before the device)
     bool he = false, heRows = false;                 // --he: Haseman-Elston regression on the chain's rows; --he-rows: the per-row sums too
     std::string heOut;                               // --he-out F
+    bool reml = false, remlBlup = false;             // --reml: REML heritability without the relationship matrix; --reml-blup: the marker effects too
+    std::string remlTrials, remlH2, remlCgTol, remlCgIters, remlTol, remlOut; // --reml-trials T, --reml-h2-start H, --reml-cg-tol E, --reml-cg-iters I, --reml-tol X as given, --reml-out F
     bool qc = false, qcMafGiven = false, qcGenoGiven = false, qcMindGiven = false, qcHweGiven = false, qcHetSdGiven = false; // --qc; which thresholds were given
     bool epistasis = false; // --epistasis: BOOST's pairwise interaction scan of a case/control phenotype (run_epistasis)
     std::string epiChisq, epiSets, epiGap, epiOut; // --epistasis-chisq T, --epistasis-gap KB as given (checked before the device), --epistasis-sets, --epistasis-out F
@@ -463,6 +472,14 @@ Options parse(int argc, const char* argv[])
         else if (a == "--he") o.he = true;
         else if (a == "--he-out") o.heOut = need(i);
         else if (a == "--he-rows") o.heRows = true;
+        else if (a == "--reml") o.reml = true;
+        else if (a == "--reml-trials") o.remlTrials = need(i);
+        else if (a == "--reml-h2-start") o.remlH2 = need(i);
+        else if (a == "--reml-cg-tol") o.remlCgTol = need(i);
+        else if (a == "--reml-cg-iters") o.remlCgIters = need(i);
+        else if (a == "--reml-tol") o.remlTol = need(i);
+        else if (a == "--reml-out") o.remlOut = need(i);
+        else if (a == "--reml-blup") o.remlBlup = true;
         else if (a == "--epistasis") o.epistasis = true;
         else if (a == "--epistasis-chisq") o.epiChisq = need(i);
         else if (a == "--epistasis-sets") o.epiSets = need(i);
@@ -3413,6 +3430,103 @@ int run_he(const Options& opt, const Cohort& co, const std::vector<double>& y_ra
     return 0;
 }
 
+// ---- --reml: REML heritability without the relationship matrix ----
+struct RemlArgs {
+    long trials = 15, cgIters = 200;
+    double h2 = 0.25, cgTol = 1e-5, tol = 0.01;
+};
+
+// the values of --reml's options; refuses by name what is out of range
+RemlArgs reml_args(const Options& opt)
+{
+    RemlArgs a;
+    if (!opt.remlTrials.empty() && (!whole_int(opt.remlTrials, a.trials) || a.trials < 1 || a.trials > 31))
+        fatal("FATAL  : --reml-trials " + opt.remlTrials + ": the number of probes must be an integer from 1 to 31 (with y, the 32 columns hgibbs_reml_solve takes)");
+    if (!opt.remlH2.empty() && (!whole_num(opt.remlH2, a.h2) || !(a.h2 > 0.0 && a.h2 < 1.0)))
+        fatal("FATAL  : --reml-h2-start " + opt.remlH2 + ": the start value must be a number inside (0, 1)");
+    if (!opt.remlCgTol.empty() && (!whole_num(opt.remlCgTol, a.cgTol) || !std::isfinite(a.cgTol) || !(a.cgTol > 0.0)))
+        fatal("FATAL  : --reml-cg-tol " + opt.remlCgTol + ": the tolerance must be a finite number > 0");
+    if (!opt.remlCgIters.empty() && (!whole_int(opt.remlCgIters, a.cgIters) || a.cgIters < 1 || a.cgIters > std::numeric_limits<int>::max()))
+        fatal("FATAL  : --reml-cg-iters " + opt.remlCgIters + ": needs at least one iteration");
+    if (!opt.remlTol.empty() && (!whole_num(opt.remlTol, a.tol) || !std::isfinite(a.tol) || !(a.tol > 0.0)))
+        fatal("FATAL  : --reml-tol " + opt.remlTol + ": the tolerance on log delta must be a finite number > 0");
+    return a;
+}
+
+int run_reml(const Options& opt, const Cohort& co, const std::vector<double>& y_raw, const std::vector<double>& covX, int C)
+{
+    const RemlArgs args = reml_args(opt);
+    const std::string out = opt.remlOut.empty() ? opt.mcmcOutDir + "/" + opt.mcmcOutNam + ".reml" : opt.remlOut;
+    const std::string blupp = out + ".blup";
+    const unsigned N = co.Ntot, M = co.Mtot;
+    if (C > 31) fatal("FATAL  : --reml takes at most 31 covariates (" + std::to_string(C) + " given): with the column of ones, the 32 columns hgibbs_reml takes");
+    if ((long long)N <= (long long)C + 2) fatal("FATAL  : --reml needs more individuals (" + std::to_string(N) + ") than covariates + 2");
+    BimRows bim;
+    if (opt.remlBlup) {
+        bim = read_bim(opt.bedFile + ".bim", M);
+        if (bim.id.size() != M) fatal("FATAL  : " + opt.bedFile + ".bim: " + std::to_string(bim.id.size()) + " rows, expected " + std::to_string(M));
+    }
+
+    // the phenotype of --he: the chain's scaling; with covariates [1 | covariates] projected out, then scaled again.  Z goes to the
+    // library as well, whose P_c keeps every probe and iterate off its columns.
+    std::vector<double> y(y_raw);
+    scale_phenotype(y, N);
+    const CovProjector proj("--reml", covX, C, N);
+    if (C > 0) {
+        proj.project(y);
+        scale_phenotype(y, N);
+    }
+    std::vector<uint8_t> bed = read_training(opt.bedFile, co.numInds, M);
+    if (opt.remlOut.empty()) make_out_dir(opt);
+    FILE* f = open_out(out, "w");
+    FILE* fb = opt.remlBlup ? open_out(blupp, "w") : nullptr;
+
+    hgibbs_t dev = open_training(co, bed);
+    hgibbs_reml_opts ro{};
+    ro.trials = (int)args.trials;
+    ro.h2_start = args.h2;
+    ro.cg_tol = args.cgTol;
+    ro.cg_iters = (int)args.cgIters;
+    ro.x_tol = args.tol;
+    ro.max_steps = 12;
+    ro.seed = (uint64_t)opt.seed;
+    hgibbs_reml_result r{};
+    std::vector<double> blup(fb ? M : 0), mstd(fb ? M : 0), mave(fb ? M : 0);
+    hg_check(hgibbs_reml(dev, &ro, proj.q, proj.Z.data(), y.data(), &r, fb ? blup.data() : nullptr), "hgibbs_reml");
+    if (fb) {
+        std::vector<uint64_t> n1(M), n2(M), nm(M);
+        hg_check(hgibbs_marker_stats(dev, mave.data(), mstd.data(), n1.data(), n2.data(), nm.data()), "hgibbs_marker_stats");
+    }
+    hgibbs_destroy(dev);
+
+    const hgibbs_reml_estimate& e = r.est;
+    const char* status = r.status == HGIBBS_REML_AT_BOUND ? "AT_BOUND" : "CONVERGED";
+    int cg = 0;
+    for (int k = 0; k < r.steps; ++k) cg += r.cg_iters[k];
+    std::fprintf(f, "Source\tVariance\tSE\n");
+    std::fprintf(f, "V(G)\t%.9g\t%.9g\nV(e)\t%.9g\t%.9g\nVp\t%.9g\t%.9g\nV(G)/Vp\t%.9g\t%.9g\n", e.vg, e.se_vg, e.ve, e.se_ve, e.vp, e.se_vp, e.h2, e.se_h2);
+    std::fprintf(f, "logdelta\t%.9g\nSE_MC\t%.9g\nn\t%u\nM_used\t%u\nq\t%d\ntrials\t%d\nsteps\t%d\ncg_iters\t%d\nstatus\t%s\n", e.logdelta, e.se_mc, r.n, r.m_used,
+                 r.q, r.trials, r.steps, cg, status);
+    close_out(f, out);
+    if (fb) {
+        std::fprintf(fb, "CHR\tSNP\tBP\tA1\tA2\tBETA\n");
+        for (unsigned j = 0; j < M; ++j) {
+            std::fprintf(fb, "%s\t%s\t%lld\t%s\t%s\t", bim.chr[j].c_str(), bim.id[j].c_str(), bim.bp[j], bim.a1[j].c_str(), bim.a2[j].c_str());
+            if (std::isfinite(mstd[j])) std::fprintf(fb, "%.9g\n", blup[j] * mstd[j]);
+            else std::fprintf(fb, "NA\n");
+        }
+        close_out(fb, blupp);
+    }
+    if (r.status == HGIBBS_REML_AT_BOUND) std::printf("WARNING: --reml stopped at the bound of its search, |log delta| = log 9999: the estimate is the bound, not a root\n");
+    std::printf("REML   : %u rows, %u of %u markers used, %d covariates, %d probes (seed %u), %d evaluations, %d CG iterations, %s -> %s\n", N, r.m_used, M, C, r.trials,
+                opt.seed, r.steps, cg, status, out.c_str());
+    std::printf("REML   : V(G)/Vp %.6g (SE %.3g, SE_MC %.3g), V(G) %.6g, V(e) %.6g, log delta %.6g; products %.3f ms, algebra %.3f ms on the device", e.h2, e.se_h2,
+                e.se_mc, e.vg, e.ve, e.logdelta, r.products_ms, r.algebra_ms);
+    if (fb) std::printf(", the marker effects in %s", blupp.c_str());
+    std::printf("\n");
+    return 0;
+}
+
 // ---- --qc: quality control of the chain's rows and the training markers ----
 // a number as the tables print it: nine digits, NA when it is not defined
 std::string qc_num(double v)
@@ -4469,7 +4583,7 @@ struct Mode {
     const char* wmpi;   // how it refuses --mpibayes bayesWMPI, after its flag
     const char* orphan; // the first of its dependent options that was given: they need the mode (null: none was)
 };
-enum { PREDICT, LD, ASSOC, KING, PCA, PVE, GRM, LDSCORE, CLUMP, LDPRUNE, HE, QC, HOMOZYG, EPISTASIS, CS, NMODES }; // the order in which a mode names the earlier ones it cannot be combined with
+enum { PREDICT, LD, ASSOC, KING, PCA, PVE, GRM, LDSCORE, CLUMP, LDPRUNE, HE, QC, HOMOZYG, EPISTASIS, CS, REML, NMODES }; // the order in which a mode names the earlier ones it cannot be combined with
 
 const char* first_given(std::initializer_list<std::pair<const char*, bool>> deps)
 {
@@ -4681,8 +4795,12 @@ void check_modes(const Options& opt, int nranks)
          first_given({{"--cs-chains", !opt.csChains.empty()}, {"--cs-window-kb", opt.csKbGiven}, {"--cs-window-snps", opt.csSnpsGiven}, {"--cs-r2", !opt.csArgs.r2.empty()},
                       {"--cs-alpha", !opt.csArgs.alpha.empty()}, {"--cs-pep", !opt.csArgs.pep.empty()}, {"--cs-lead", !opt.csArgs.lead.empty()},
                       {"--cs-max-size", !opt.csArgs.maxSize.empty()}, {"--cs-out", !opt.csArgs.out.empty()}})},
+        {"--reml", opt.reml, takes,
+         first_given({{"--reml-trials", !opt.remlTrials.empty()}, {"--reml-h2-start", !opt.remlH2.empty()}, {"--reml-cg-tol", !opt.remlCgTol.empty()},
+                      {"--reml-cg-iters", !opt.remlCgIters.empty()}, {"--reml-tol", !opt.remlTol.empty()}, {"--reml-out", !opt.remlOut.empty()},
+                      {"--reml-blup", opt.remlBlup}})},
     };
-    for (const int i : {LD, PREDICT, ASSOC, KING, PCA, PVE, GRM, LDSCORE, CLUMP, LDPRUNE, HE, QC, HOMOZYG, EPISTASIS, CS}) {
+    for (const int i : {LD, PREDICT, ASSOC, KING, PCA, PVE, GRM, LDSCORE, CLUMP, LDPRUNE, HE, QC, HOMOZYG, EPISTASIS, CS, REML}) {
         const Mode& m = modes[i];
         const std::string flag = m.flag;
         if (!m.given) {
@@ -4709,6 +4827,7 @@ void check_modes(const Options& opt, int nranks)
         if (i == HOMOZYG) check_homozyg_args(opt);
         if (i == EPISTASIS) (void)epistasis_args(opt); // refuses by name what is out of range
         if (i == CS) check_cs_args(opt);
+        if (i == REML) (void)reml_args(opt); // refuses by name what is out of range
     }
 }
 
@@ -4746,7 +4865,7 @@ void check_sumstats(const Options& opt, int nranks)
     const std::pair<const char*, bool> modes[] = {
         {"--predict-bfile", !opt.predictBfile.empty()}, {"--ld-window", opt.ldGiven}, {"--assoc", opt.assoc}, {"--king", opt.king}, {"--pca", opt.pca}, {"--pve", opt.pve},
         {"--grm", opt.grm}, {"--ld-score", opt.ldScore}, {"--clump", opt.clump}, {"--ld-prune", opt.ldPrune}, {"--he", opt.he}, {"--qc", opt.qc}, {"--homozyg", opt.homozyg},
-        {"--epistasis", opt.epistasis}, {"--cs", opt.cs}};
+        {"--epistasis", opt.epistasis}, {"--cs", opt.cs}, {"--reml", opt.reml}};
     for (const auto& m : modes)
         if (m.second) fatal(std::string("FATAL  : --sumstats cannot be combined with ") + m.first + ": it samples a chain, the analysis modes sample nothing");
     if (opt.covariates) fatal("FATAL  : --sumstats cannot be combined with --covariates: summary statistics carry no individual-level covariates");
@@ -4845,6 +4964,7 @@ int main(int argc, const char* argv[])
     if (opt.homozyg) return run_homozyg(opt, co);
     if (opt.epistasis) return run_epistasis(opt, co, y);
     if (opt.cs) return run_cs(opt, co);
+    if (opt.reml) return run_reml(opt, co, y, covX, C);
 
     const Mixtures mix = read_mixtures(opt, Mtot, true);
     const int G = mix.G, K = mix.K;

@@ -1147,6 +1147,74 @@ typedef struct {
 } hydraw_restart_state;
 int hydraw_chain_restore(hydraw_chain_t c, const hydraw_restart_state* st);
 
+/* ---- REML heritability without the relationship matrix ---- */
+/* n = the handle's rows, M_used the markers with a finite mstd, X the chain's standardisation (0 at a missing call), A = X X'/M_used.
+ * Z (q x n, vector-major: column c of the design at Z + c n) holds every covariate column, the column of ones included; Q is an
+ * orthonormal basis of it (modified Gram-Schmidt, twice, on the host; a dependent column is refused by its index), P_c = I - QQ',
+ * H(delta) = P_c A P_c + delta I.  One rank only.  Every sum over rows or markers is taken in a fixed order (blocks of 1024 from
+ * index 0, in order inside a thread, partials in block order), so each call is a deterministic function of its arguments.
+ *
+ * hgibbs_reml_solve: V[k] = H(delta)^-1 P_c B[k] for K <= 32 right-hand sides (B, V: K x n, vector-major) by conjugate gradients from
+ * V = 0 with per-column scalars.  Column k is frozen once r'r <= tol^2 b'b (b the projected right-hand side), tested before every
+ * iteration; the loop ends when every column is frozen.  iters[k] = the iterations column k took, relres[k] = sqrt(r'r / b'b) of the
+ * recurrence at its end (0 for a zero column).  Reaching max_iters with a live column, or a p'Hp that is not positive and finite,
+ * refuses the call. */
+int hgibbs_reml_solve(hgibbs_t h, int K, int q, const double* Z, double delta, double tol, int max_iters, const double* B, double* V,
+                      int* iters, double* relres);
+/* hgibbs_reml_eval: the sums of f at delta from T sign probes (1 <= T <= 31) and y.  With s(c, i) = +1 when the top bit of
+ * mix64((seed ^ mix64(c)) + i 0xD1B54A32D192ED03) is 0, else -1:  G_t = P_c X s(2t, marker index) / sqrt(M_used),
+ * E_t = P_c s(2t + 1, row_begin + row),  b_t = G_t + sqrt(delta) E_t (t < T),  b_T = P_c y,  v_k = H^-1 b_k,  u_k = X'v_k.
+ * sums[3 k + 0 .. 2] = u_k'u_k / M_used, v_k'v_k, v_k'b_k for k = 0 .. T;  f(delta) = log(sum_{t<T} vAv_t / sum_{t<T} vv_t) -
+ * log(vAv_T / vv_T), the sums ascending in t.  iters (or NULL) takes the largest iteration count of the columns. */
+int hgibbs_reml_eval(hgibbs_t h, int T, int q, const double* Z, const double* y, uint64_t seed, double delta, double tol, int max_iters,
+                     double* sums, int* iters);
+/* the root rule on x = log delta (host only).  x, f: the k >= 0 points evaluated so far.  status CONTINUE: evaluate *x_next next;
+ * CONVERGED / AT_BOUND: x[k - 1] (= *x_next) is the estimate.  k = 0: log((1 - h0)/h0); k = 1: h1 = min(2 h0, (1 + h0)/2) if
+ * f[0] < 0, else h0/2; then secant steps clamped to |x| <= log 9999.  Done when |x[k-1] - x[k-2]| < x_tol; the same bound twice
+ * gives AT_BOUND.  f[k-1] == f[k-2], or k >= max_steps without being done, is refused. */
+enum { HGIBBS_REML_CONTINUE = 0, HGIBBS_REML_CONVERGED = 1, HGIBBS_REML_AT_BOUND = 2 };
+int hgibbs_reml_next(int k, const double* x, const double* f, double h0, double x_tol, int max_steps, double* x_next, int* status);
+/* the estimate (host only) from the last two evaluated points x2[0], x2[1] and their sums ((T + 1) x 3 each): delta = exp(x2[1]),
+ * vg = vb_T / (n - q), ve = delta vg, vp = vg + ve, h2 = 1 / (1 + delta).  ai3 (or NULL: the SEs are NaN) = a'z1, a'z2, v'z2 with
+ * v = v_T, a = P_c A P_c v, H z1 = a, H z2 = v: AI = [[ai3[0], ai3[1]], [ai3[1], ai3[2]]] / (2 vg^3), the covariance of (vg, ve) is
+ * its inverse and se_h2 follows by the delta method.  se_logdelta_mc: the leave-one-probe-out jackknife of the secant root through
+ * the two points, sqrt((T - 1)/T sum (x_(-t) - mean)^2); se_mc = se_logdelta_mc h2 (1 - h2).  NaN when T = 1. */
+typedef struct {
+    double logdelta, delta, vg, ve, vp, h2;
+    double se_vg, se_ve, se_vp, se_h2;
+    double se_mc, se_logdelta_mc;
+} hgibbs_reml_estimate;
+int hgibbs_reml_finish(int T, uint32_t n, int q, const double* x2, const double* sums_prev, const double* sums_last, const double* ai3,
+                       hgibbs_reml_estimate* out);
+/* hgibbs_reml: the whole estimate in one call; G and E are made once and everything stays on the device across the evaluations */
+#define HGIBBS_REML_MAX_STEPS 32
+typedef struct {
+    int trials;        /* T, 1 .. 31 */
+    double h2_start;   /* h0 inside (0, 1) */
+    double cg_tol;     /* positive and finite */
+    int cg_iters;      /* at least 1 */
+    double x_tol;      /* positive and finite */
+    int max_steps;     /* 2 .. HGIBBS_REML_MAX_STEPS evaluations */
+    uint64_t seed;
+} hgibbs_reml_opts;
+typedef struct {
+    int status;        /* HGIBBS_REML_CONVERGED or HGIBBS_REML_AT_BOUND */
+    int steps;         /* evaluations made */
+    double x[HGIBBS_REML_MAX_STEPS], f[HGIBBS_REML_MAX_STEPS];
+    int cg_iters[HGIBBS_REML_MAX_STEPS];
+    double sums_prev[96], sums_last[96]; /* (T + 1) x 3 of the last two evaluations */
+    double ai3[3];
+    int ai_cg_iters;
+    hgibbs_reml_estimate est;
+    uint32_t n, m_used;
+    int q, trials;
+    double products_ms, algebra_ms; /* device time of the X'P and X T products, and of every other kernel */
+} hgibbs_reml_result;
+/* blup (or NULL): M doubles, beta_j = x_j'v_T / M_used at the estimate, NaN outside M_used */
+int hgibbs_reml(hgibbs_t h, const hgibbs_reml_opts* opt, int q, const double* Z, const double* y, hgibbs_reml_result* res, double* blup);
+/* device time of the last hgibbs_reml_solve / _eval / hgibbs_reml in ms: the products, the rest */
+int hgibbs_last_reml_ms(hgibbs_t h, double* products_ms, double* algebra_ms);
+
 /* ---- checkpoint / restart (src/BayesRRm.cpp:842-928, :2802-2838) --------- */
 /* State a --restart run reads back from the dump files; arrays are host
  * pointers, eps has this rank's individuals.  gamma/xI may be NULL without
